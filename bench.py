@@ -5,7 +5,7 @@ One "step" = one pass of the predict hot path (x/255 -> pad -> fcn_skip -> crop 
 argmax) over `--pages` synthetic pages per rank, inputs already resident in HBM, uint8 label
 maps left in HBM (the task's measurement contract; the host-buffer / PCIe-inclusive rate of the
 drop-in boundary -- SURVEY.md 8d's "uint8 page in pinned host memory -> label map in host memory" -- is
-reported next to it at the top level as `value_host_path` and in detail under `extra.host_path`, never as
+reported next to it by `--full` at the top level as `value_host_path` and in detail under `extra.host_path`, never as
 `value`).  N=1 runs BASELINE.json configs[1] (single 2048x1536 page, 3 classes, bf16 activations).  N>1:
 one process per GPU, BASELINE.json configs[2]'s shape -- 32 independent pages per rank per step (`--pages`),
 no data-path collective (weak scaling); value = pixels of all ranks / max-over-ranks time.
@@ -14,11 +14,18 @@ no data-path collective (weak scaling); value = pixels of all ranks / max-over-r
 that never touches the GPU spawns fresh children with RANK / LOCAL_RANK / WORLD_SIZE set and
 relays rank 0's line); under torchrun (WORLD_SIZE set) the process is one rank.
 
-Prints ONE JSON line on rank 0 with `roofline` (dominant kernel, algorithmic FLOPs / HIP-event
-duration measured here), `cpu_baseline` (the float32 restatement on torch-CPU / oneDNN at n = all
-cores and n = 1; the reference's TensorFlow path cannot run offline) and
-`extra` (host path from pinned memory, float32 engine, configs[3] train step, label-exact mode, unet, res_unet,
-configs[4] pipeline, the drop-in Predictor chain).
+Prints ONE JSON line on rank 0.  A plain run sets up, spins the clocks up, runs the W warm-up steps, times the K steps
+and prints the headline (`value`, `ms_per_step`, ...); `roofline`, `cpu_baseline` and `extra` are null / empty.
+`--full` adds what takes runs of its own: `roofline` (dominant kernel, algorithmic FLOPs / HIP-event duration of a
+separate per-kernel pass), the per-step spread (`extra.ms_per_step_*`), `cpu_baseline` (the float32 restatement on
+torch-CPU / oneDNN at n = all cores and n = 1; the reference's TensorFlow path cannot run
+offline) and `extra` (host path from pinned memory, float32 engine, configs[3] train step, label-exact mode, unet,
+res_unet, configs[4] pipeline, the drop-in Predictor chain); `--no-extra` / `--no-cpu-baseline` drop legs of it.
+
+`--dump-outputs DIR` writes, after the timed steps, the label maps of the last timed step as float32 `.npy` (`labels`,
+or `labels_rank<r>` per rank when N > 1): the whole (pages, H, W) array, or a fixed seeded sample of its pixels when
+that would exceed DUMP_BUDGET_BYTES.  Inputs (synthetic pages, weights) are seeded: the same arguments give the same
+inputs on every run, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -35,6 +42,7 @@ for _p in (ROOT, os.path.join(ROOT, "page-segmentation_amd")):
 
 PEAK_TFLOPS = {"bf16": 2500.0, "f32": 157.3}   # MI355X_MICROARCH.md: dense MFMA peaks
 HBM_PEAK_GBS = 8000.0
+DUMP_BUDGET_BYTES = 60 * 1000 * 1000   # --dump-outputs: all ranks' files together stay under 64 MB
 
 
 def parse_args(argv=None):
@@ -49,8 +57,11 @@ def parse_args(argv=None):
     ap.add_argument("--width", type=int, default=1536)
     ap.add_argument("--page-by-page", action="store_true", help="with --pages > 1: one pseg_predict_device call per page instead of pseg_predict_pages_device (A/B)")
     ap.add_argument("--pages", type=int, default=None, help="pages per rank per step (default: 1 at --gpus 1 = configs[1]; 32 at --gpus N > 1 = configs[2])")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra.* legs (host path, unet, configs[4], label-exact)")
+    ap.add_argument("--full", action="store_true", help="also the per-step spread, the per-kernel roofline pass, the extra.* legs and the CPU baseline "
+                                                         "(a plain run measures the headline only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the extra.* legs (host path, unet, configs[4], label-exact)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the label maps of the last timed step to DIR/*.npy (float32)")
     args = ap.parse_args(argv)
     if args.pages is None:
         args.pages = 1 if args.gpus <= 1 else 32
@@ -385,6 +396,19 @@ def leg_cpu_baseline(np, weights, page, arch):
                             "sample": "rows 0..256 of the page, oracle/pseg_oracle.c (sequential fmaf chains, OpenMP), one pass %.2f s" % t_port}}
 
 
+def dump_outputs(np, d_labels, out_dir, name, budget_bytes):
+    """The uint8 label maps of the last timed step (what a caller of pseg_predict[_pages]_device receives) as float32
+    DIR/<name>.npy: the whole (pages, H, W) array when it fits `budget_bytes`, otherwise a fixed sample of its pixels
+    (flat indices drawn by default_rng(0), sorted; the same for every run with the same arguments)."""
+    labels = d_labels.cpu().numpy()
+    limit = max(1, budget_bytes // 4)
+    if labels.size > limit:
+        idx = np.sort(np.random.default_rng(0).integers(0, labels.size, size=limit))
+        labels = labels.reshape(-1)[idx]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, name + ".npy"), labels.astype(np.float32))
+
+
 # ---------------------------------------------------------------------------------------------------
 # one rank
 # ---------------------------------------------------------------------------------------------------
@@ -455,34 +479,40 @@ def run_rank(args):
             dist.barrier()
         torch.cuda.synchronize(dev)
 
-    # Order of the legs: the per-step spread pass and the per-kernel roofline pass run FIRST, then the W warm-up steps, then the
-    # K timed steps.  A cold MI355X needs about 25 pages (12 ms) of load before it holds its sustained clocks: with W = 5
-    # straight after process start the 20-step region measured 0.509 ms/page, with W = 50 or K = 200 0.457-0.461 ms/page
-    # (gpurun, round 2) -- the sustained rate is the one a page stream sees, and the one the roofline leg is priced at.
-    for _ in range(32):      # spin-up, untimed: every leg below (spread, roofline, the timed region) sees the sustained clocks
-        step()
-    torch.cuda.synchronize(dev)
-    # per-step spread (separate pass, events on the launch stream): the timed region below is a single sample
-    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(max(args.steps, 10))]
-    for a, b in evs:
-        a.record()
-        step()
-        b.record()
-    torch.cuda.synchronize(dev)
-    per = sorted(a.elapsed_time(b) for a, b in evs)
-    step_stats = {"ms_per_step_median": round(per[len(per) // 2], 4), "ms_per_step_min": round(per[0], 4),
-                  "ms_per_step_max": round(per[-1], 4), "samples": len(per)}
+    # Order of the legs: the spin-up, then (--full) the per-step spread pass and the per-kernel roofline pass, then the W
+    # warm-up steps, then the K timed steps.  A cold MI355X needs about 25 pages (12 ms) of load before it holds its sustained
+    # clocks: with W = 5 straight after process start the 20-step region measured 0.509 ms/page, with W = 50 or K = 200
+    # 0.457-0.461 ms/page (round 2) -- the sustained rate is the one a page stream sees, and the one the roofline leg is priced at.
+    # 32 steps alone left a plain run (no spread / roofline pass before its timed region) ~2 % short of the sustained rate, so
+    # the spin-up lasts at least 32 steps AND 0.2 s of back-to-back load.
+    t_spin, n_spin = time.perf_counter(), 0
+    while n_spin < 32 or time.perf_counter() - t_spin < 0.2:   # spin-up, untimed: every leg below sees the sustained clocks
+        for _ in range(8):
+            step()
+        n_spin += 8
+        torch.cuda.synchronize(dev)
+    step_stats, slots, roof = {}, [], None
+    if args.full:
+        # per-step spread (separate pass, events on the launch stream): the timed region below is a single sample
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(max(args.steps, 10))]
+        for a, b in evs:
+            a.record()
+            step()
+            b.record()
+        torch.cuda.synchronize(dev)
+        per = sorted(a.elapsed_time(b) for a, b in evs)
+        step_stats = {"ms_per_step_median": round(per[len(per) // 2], 4), "ms_per_step_min": round(per[0], 4),
+                      "ms_per_step_max": round(per[-1], 4), "samples": len(per)}
 
-    # ---- roofline: per-kernel HIP-event timing on the same stream, separate untimed pass --------
-    roof = None
-    eng.timing_enable(True)
-    eng.timing_reset()
-    nroof = max(3, min(args.steps, 10))
-    for _ in range(nroof):
-        step()
-    torch.cuda.synchronize(dev)
-    slots = [s for s in eng.timing() if s[2] > 0]
-    eng.timing_enable(False)
+        # ---- roofline: per-kernel HIP-event timing on the same stream, separate untimed pass --------
+        eng.timing_enable(True)
+        eng.timing_reset()
+        nroof = max(3, min(args.steps, 10))
+        for _ in range(nroof):
+            step()
+        torch.cuda.synchronize(dev)
+        slots = [s for s in eng.timing() if s[2] > 0]
+        eng.timing_enable(False)
 
     for _ in range(args.warmup):
         step()
@@ -497,6 +527,9 @@ def run_rank(args):
         t = torch.tensor([dt], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs:
+        dump_outputs(np, d_labels, os.path.abspath(args.dump_outputs), "labels" if world == 1 else "labels_rank%d" % rank,
+                     DUMP_BUDGET_BYTES // world)
 
     total_px = float(world) * args.pages * H * W * args.steps
     value = total_px / dt / 1e6
@@ -548,7 +581,7 @@ def run_rank(args):
 
     extra = dict(step_stats)
     cpu = None
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         default_cfg = (H, W, C, args.arch, args.mode) == (2048, 1536, 3, "fcn_skip", "bf16")
         if not args.no_extra and default_cfg:
             for key, fn in (("pages32", lambda: leg_pages32(torch, np, eng, synth, H, W, C, dev, args.steps, args.warmup)),
@@ -591,7 +624,7 @@ def run_rank(args):
                                    + ", inputs resident in HBM, uint8 label maps left in HBM (value = HBM-resident rate per the measurement "
                                      "contract; SURVEY 8d's pinned-host-in / host-out rate is value_host_path)",
                        "pages_per_rank_per_step": args.pages, "parallelism": "page-parallel x%d" % world,
-                       "per_rank_baseline": ("extra.pages32 of the --gpus 1 line (the same %d pages per step through pseg_predict_pages_device on one GPU), "
+                       "per_rank_baseline": ("extra.pages32 of the --gpus 1 --full line (the same %d pages per step through pseg_predict_pages_device on one GPU), "
                                              "not its `value` (one page per step)" % args.pages) if world > 1 else None},
             "roofline": roof,
             "cpu_baseline": cpu,

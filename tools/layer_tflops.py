@@ -1,7 +1,7 @@
 """Per-layer time and algorithmic TFLOP/s of one bf16 predict (bench.py timing slots)."""
 import json, subprocess, sys
 arch = sys.argv[1] if len(sys.argv) > 1 else "unet"
-out = subprocess.run([sys.executable, "bench.py", "--arch", arch, "--no-cpu-baseline", "--steps", "5"], capture_output=True, text=True).stdout.strip().split("\n")[-1]
+out = subprocess.run([sys.executable, "bench.py", "--full", "--arch", arch, "--no-cpu-baseline", "--steps", "5"], capture_output=True, text=True).stdout.strip().split("\n")[-1]
 d = json.loads(out)
 print(d["ms_per_step"], "ms/page  whole-net frac", d["roofline"]["whole_net_frac"])
 sys.path[:0] = [".", "page-segmentation_amd"]
