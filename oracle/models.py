@@ -241,14 +241,24 @@ def _fcn(c, x, skip):
     return c.conv(d5, name="logits")
 
 
-def _unet(c, x):
-    """lib/model.py:151-203.  Dropout is the identity at inference."""
+def _dropped(t, drop, op_index):
+    """Dropout(0.5) of the train step with the engine's counter-based mask (oracle/train_ref.py: dropout_keep), scale 2."""
+    from .train_ref import dropout_keep, dropout_key
+    keep = dropout_keep(t.size, dropout_key(drop[0], drop[1], op_index), 0.5).reshape(t.shape)
+    return np.where(keep, t * np.float32(2.0), np.float32(0.0)).astype(np.float32)
+
+
+def _unet(c, x, drop=None):
+    """lib/model.py:151-203.  Dropout is the identity at inference; drop = (seed, step) applies the train step's Dropout
+    behind levels 3 and 4 (op indices 10 and 13 of the engine's op list), after the level's activation is recorded."""
     x, pads = _pad32(x)
     skips = []
     t = x
     for lvl in range(5):
         t = c.conv(t, relu=True)
         t = c.conv(t, relu=True)
+        if drop is not None and lvl >= 3:
+            t = _dropped(t, drop, 10 if lvl == 3 else 13)
         if lvl < 4:
             skips.append(t)
             t = core.maxpool2(t)
@@ -308,11 +318,13 @@ def _res_unet(c, x, bn=False):
     return c.conv(d, name="logits")
 
 
-def forward(arch, Wt, image_u8, mode="f32", return_acts=False):
+def forward(arch, Wt, image_u8, mode="f32", return_acts=False, drop=None):
     """uint8 (H,W) network input (already inverted / line-height normalised) -> logits (H,W,C) f32.
-    lib/network.py:250-257: preprocess = x/255.0, batch of one."""
+    lib/network.py:250-257: preprocess = x/255.0, batch of one.  drop (unet): (seed, step) of a train step's Dropout masks --
+    the forward pass of that step, whose activations route the train referee (oracle/train_ref.py: route_acts)."""
     img = np.asarray(image_u8)
     assert img.dtype == np.uint8 and img.ndim in (2, 3)      # (H,W) gray or (H,W,3) (input_image_dimension = 3, lib/network.py:28,56)
+    assert drop is None or arch == "unet", "only unet has Dropout layers"
     c = _Ctx(Wt, mode)
     x = c.q(core.preprocess(img))
     if img.ndim == 2:
@@ -322,7 +334,7 @@ def forward(arch, Wt, image_u8, mode="f32", return_acts=False):
     elif arch == "fcn":
         z = _fcn(c, x, False)
     elif arch == "unet":
-        z = _unet(c, x)
+        z = _unet(c, x, drop)
     elif arch == "res_unet":
         z = _res_unet(c, x, bn="batch_normalization/gamma" in Wt)
     else:

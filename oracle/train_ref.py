@@ -100,7 +100,7 @@ def dropout_key(seed, step, op_index):
     return (base + 0x85EBCA77 * op_index) & 0xFFFFFFFF
 
 
-def graph_loss_and_grads(arch, Wt, image_u8, mask_u8, drop=None, float64=False, bn_stats=None, route_acts=None):
+def graph_loss_and_grads(arch, Wt, image_u8, mask_u8, drop=None, float64=False, bn_stats=None, route_acts=None, route_relu=False):
     """unet (lib/model.py:151-203) and res_unet (:237-307) in torch with the reference's cross-entropy (lib/metrics.py:8-9);
     `drop` = (seed, step) enables unet's two Dropout(0.5) layers with the engine's masks (op indices 10 and 13 of the
     engine's op list; masks are laid out over the (H/8, W/8, 512) and (H/16, W/16, 1024) canvases).
@@ -115,6 +115,10 @@ def graph_loss_and_grads(arch, Wt, image_u8, mask_u8, drop=None, float64=False, 
     one such window in 5 215 puts 1e-2 relative error on conv2d_5/kernel, every float32 order has its own).  With
     route_acts the referee takes each window's winner from the float32 activations (first maximum in (0,0), (0,1),
     (1,0), (1,1) order, as pool_bwd_kernel does), so that only rounding separates it from the engine.
+    `route_relu` (unet, with route_acts): the same for the ReLUs behind the convolutions -- the gradient passes where the
+    float32 activation is positive, as the engine's mask does, not where the referee's own pre-activation is.  route_acts must
+    then be the forward pass of the same step (oracle.forward(..., drop=drop)): behind the Dropout layers the inference
+    activations are other tensors.
     -> (loss, grads dict in Keras layouts, logits (H,W,C))."""
     import torch
     import torch.nn.functional as F
@@ -134,6 +138,9 @@ def graph_loss_and_grads(arch, Wt, image_u8, mask_u8, drop=None, float64=False, 
         tw = max((-(-Win // stride) - 1) * stride + k - Win, 0)
         x = F.pad(x, (tw // 2, tw - tw // 2, th // 2, th - th // 2))           # TF SAME
         y = F.conv2d(x, T[n + "/kernel"].permute(3, 2, 0, 1), T[n + "/bias"], stride=stride)
+        if relu and route_relu:
+            pos = np.ascontiguousarray((np.asarray(route_acts[n]) > 0).transpose(2, 0, 1)[None])
+            return y * torch.from_numpy(pos).to(dt)
         return F.relu(y) if relu else y
 
     last_keep = [None]
