@@ -256,6 +256,29 @@ int pseg_train_forward_backward(pseg_engine* e, const uint8_t* img, const uint8_
 int pseg_train_forward_backward_f32(pseg_engine* e, const float* img, const uint8_t* mask, int H, int W,
                                     float metrics[4]);
 
+/* lib/network.py:149-161 as ONE device-resident call: image (uint8 (H,W[,in_channels])) -> float32 ->
+ * per channel cubic warp (order 3, image fill mode / cval) -> flips -> brightness; mask (uint8 (H,W)) ->
+ * order-0 warp (mask fill mode / cval) -> flips -> uint8; then the step of pseg_train_forward_backward_f32.
+ * m (4 doubles) / off (2): output pixel (r,c) samples the input at m (r,c) + off; m == NULL: no warp (the
+ * generator skips it for the identity).  flips: bit 0 horizontal, bit 1 vertical.  fill modes 0..3 as
+ * pseg_affine_warp_fill.  mask_cval must be an integer in 0..255 (else PSEG_EINVAL).  use_brightness != 0:
+ * pseg_brightness_shift(brightness) over all channels of the warped, flipped sample.
+ * Both uint8 arrays are uploaded once on the engine's stream and the sample is built in buffers of the train state
+ * (grown on the first page of a size -- PSEG_ENOMEM when that fails --, none allocated in steady state); all work runs
+ * on the engine's stream and the only host wait is the metrics read.  The sample has the bits of the host-array path
+ * (pseg_affine_warp_fill per channel, NumPy flips, pseg_brightness_shift): the float64 operation sequences are shared. */
+int pseg_train_forward_backward_aug(pseg_engine* e, const uint8_t* img, const uint8_t* mask, int H, int W,
+                                    const double* m, const double* off, unsigned flips,
+                                    int image_fill_mode, float image_cval, int mask_fill_mode, float mask_cval,
+                                    int use_brightness, float brightness, float metrics[4]);
+/* The sample that call trains on, copied to the host (tests, create-your-own-loop users): out_img float32
+ * (H,W[,in_channels]) on the 0..255 scale, out_mask uint8 (H,W).  Needs pseg_train_init, no canvas.  Host-synchronous:
+ * waits for the engine's stream before it returns (both outputs are then complete). */
+int pseg_train_augment_sample(pseg_engine* e, const uint8_t* img, const uint8_t* mask, int H, int W,
+                              const double* m, const double* off, unsigned flips,
+                              int image_fill_mode, float image_cval, int mask_fill_mode, float mask_cval,
+                              int use_brightness, float brightness, float* out_img, uint8_t* out_mask);
+
 /* The flat device gradient buffer (all parameters in weight-table order, then the metric
  * accumulators): data-parallel training all-reduces exactly this buffer (one RCCL call), then
  * applies with grad_scale = 1/world. */

@@ -308,6 +308,28 @@ int run_exact(Engine& e, const uint8_t* d_img, float* d_logits, float* d_probs, 
 // training state (pseg_train.hip)
 int train_sync_weights_to_host(Engine& e);
 void train_free(Engine& e);
+// one augmented training sample built on the device (pseg_resize.hip; arguments as pseg_train_forward_backward_aug).  d_src_*: the
+// uploaded uint8 page (H,W,C) and mask; d_coef: augment_coef_count() doubles (unused when m == NULL); d_mm: 2 unsigned;
+// d_img: float32 (H,W,C) out, d_mask: uint8 (H,W) out.  All work is enqueued on the stream; nothing is allocated.
+struct AugSample {
+    const uint8_t* d_src_img;
+    const uint8_t* d_src_mask;
+    int H, W, C;
+    const double* m;        // host, 4 doubles; NULL: no warp
+    const double* off;      // host, 2 doubles
+    unsigned flips;
+    int image_fill, mask_fill;
+    float image_cval, mask_cval;
+    int use_brightness;
+    float brightness;
+    double* d_coef;
+    unsigned* d_mm;
+    float* d_img;
+    uint8_t* d_mask;
+};
+int augment_check(int H, int W, const double* m, const double* off, unsigned flips, int image_fill, int mask_fill, float mask_cval);
+size_t augment_coef_count(int H, int W, int image_fill);
+int augment_sample_device(const AugSample& a, hipStream_t st);
 
 int time_begin(Engine& e, Op& op, hipStream_t st, hipEvent_t* ev0);
 int time_end(Engine& e, Op& op, hipStream_t st, hipEvent_t ev0);

@@ -216,65 +216,102 @@ __global__ __launch_bounds__(256) void warp_pad_kernel(const float* src, int H, 
     dst[(size_t)y * Wp + x] = (double)src[(size_t)sy * W + sx];
 }
 
-// one thread = one line (row: AXIS 1, column: AXIS 0) of the padded plane, in place
+// ---- the line recurrence of the cubic prefilter, shared by the thread-per-line kernel below and the tiled kernel of the device
+// sample builder (spline3_prefilter_tile_kernel).  A line is reached through an accessor `a(i)` (sample i of the line: strided
+// global memory there, an LDS tile here); every function keeps one sequence of float64 operations, so both users give the same bits.
 // reflect = 0: mirror boundary (whole-sample symmetric: scipy's 'mirror', and what it uses for 'constant' and 'wrap');
 // reflect = 1: half-sample symmetric ('reflect': c[-1 - i] = c[i]) -- scipy >= 1.6 ni_splines.c _init_causal_reflect / _anticausal_reflect
-template <int AXIS>
-__global__ __launch_bounds__(64) void spline3_prefilter_kernel(double* c, int Hp, int Wp, int reflect = 0) {
-    const int line = blockIdx.x * 64 + threadIdx.x;
-    const int nlines = AXIS == 1 ? Hp : Wp, n = AXIS == 1 ? Wp : Hp;
-    if (line >= nlines) return;
-    double* p = AXIS == 1 ? c + (size_t)line * Wp : c + line;
-    const size_t st = AXIS == 1 ? 1 : (size_t)Wp;
-    if (n == 1) return;                             // (scipy leaves a line of one sample as it is)
-    const double z = -0.2679491924311227;          // sqrt(3) - 2
-    for (int i = 0; i < n; ++i) p[i * st] *= 6.0;   // gain (1 - z)(1 - 1/z)
+constexpr double SPLINE3_Z = -0.2679491924311227;          // sqrt(3) - 2
+constexpr int SPLINE3_HORIZON = 28;                        // |z|^k < 1e-15 after 27 terms
+
+struct LineGlobal {
+    double* p;
+    size_t st;
+    __device__ __forceinline__ double& operator()(int i) const { return p[i * st]; }
+};
+
+template <class A>
+__device__ __forceinline__ void spline3_gain(const A& a, int i0, int i1) {
+    for (int i = i0; i < i1; ++i) a(i) *= 6.0;      // gain (1 - z)(1 - 1/z)
+}
+
+// c+[0] of a line of n > 1 gained samples: reads a(0 .. 27) of a long line, the whole line (closed form) when n <= 28
+template <class A>
+__device__ __forceinline__ double spline3_causal_init(const A& a, int n, int reflect) {
+    const double z = SPLINE3_Z;
+    const int hor = min(n, SPLINE3_HORIZON);
     if (reflect) {
         // c+[0] = c[0] + z sum_{i >= 0} z^i c[i] over the half-sample-symmetric extension; exact closed form for short lines
-        const int hor = min(n, 28);
-        const double c0 = p[0];
+        const double c0 = a(0);
         double sum;
         if (hor < n) {
             double zi = 1.0;
             sum = 0.0;
-            for (int i = 0; i < hor; ++i) { sum += zi * p[i * st]; zi *= z; }
+            for (int i = 0; i < hor; ++i) { sum += zi * a(i); zi *= z; }
             sum *= z;
         } else {
             double zn = 1.0;
             for (int i = 0; i < n; ++i) zn *= z;              // z^n
             double zi = z;
-            sum = p[0] + zn * p[(size_t)(n - 1) * st];
-            for (int i = 1; i < n; ++i) { sum += zi * (p[i * st] + zn * p[(size_t)(n - 1 - i) * st]); zi *= z; }
+            sum = a(0) + zn * a(n - 1);
+            for (int i = 1; i < n; ++i) { sum += zi * (a(i) + zn * a(n - 1 - i)); zi *= z; }
             sum *= z / (1.0 - zn * zn);
         }
-        p[0] = sum + c0;
-        for (int i = 1; i < n; ++i) p[i * st] += z * p[(i - 1) * st];
-        p[(size_t)(n - 1) * st] *= z / (z - 1.0);
-        for (int i = n - 2; i >= 0; --i) p[i * st] = z * (p[(i + 1) * st] - p[i * st]);
-        return;
+        return sum + c0;
     }
-    // causal initialisation, mirror boundary: c+[0] = sum_k z^k c[k] (|z|^k < 1e-15 after 27 terms)
-    {
-        const int hor = min(n, 28);
-        double zi = z, sum = p[0];
-        if (hor < n) {
-            for (int i = 1; i < hor; ++i) { sum += zi * p[i * st]; zi *= z; }
-        } else {
-            const double iz = 1.0 / z;
-            double z2 = 1.0;
-            for (int i = 0; i < n - 1; ++i) z2 *= z;          // z^(n-1)
-            double z2n = z2;
-            sum = p[0] + z2 * p[(size_t)(n - 1) * st];
-            z2 = z2 * z2 * iz;
-            zi = z;
-            for (int i = 1; i < n - 1; ++i) { sum += (zi + z2) * p[i * st]; zi *= z; z2 *= iz; }
-            sum /= (1.0 - z2n * z2n);
-        }
-        p[0] = sum;
+    // mirror boundary: c+[0] = sum_k z^k c[k]
+    double zi = z, sum = a(0);
+    if (hor < n) {
+        for (int i = 1; i < hor; ++i) { sum += zi * a(i); zi *= z; }
+    } else {
+        const double iz = 1.0 / z;
+        double z2 = 1.0;
+        for (int i = 0; i < n - 1; ++i) z2 *= z;          // z^(n-1)
+        double z2n = z2;
+        sum = a(0) + z2 * a(n - 1);
+        z2 = z2 * z2 * iz;
+        zi = z;
+        for (int i = 1; i < n - 1; ++i) { sum += (zi + z2) * a(i); zi *= z; z2 *= iz; }
+        sum /= (1.0 - z2n * z2n);
     }
-    for (int i = 1; i < n; ++i) p[i * st] += z * p[(i - 1) * st];
-    p[(size_t)(n - 1) * st] = (z / (z * z - 1.0)) * (n > 1 ? z * p[(size_t)(n - 2) * st] + p[(size_t)(n - 1) * st] : p[0] * (1.0 + z));
-    for (int i = n - 2; i >= 0; --i) p[i * st] = z * (p[(i + 1) * st] - p[i * st]);
+    return sum;
+}
+
+// a(i) += z a(i - 1) for i in [i0, i1); prev = a(i0 - 1); returns a(i1 - 1)
+template <class A>
+__device__ __forceinline__ double spline3_causal_sweep(const A& a, int i0, int i1, double prev) {
+    const double z = SPLINE3_Z;
+    for (int i = i0; i < i1; ++i) { prev = a(i) + z * prev; a(i) = prev; }
+    return prev;
+}
+
+// c-[n - 1] from the causal results c+[n - 2], c+[n - 1]
+__device__ __forceinline__ double spline3_anticausal_init(double before_last, double last, int reflect) {
+    const double z = SPLINE3_Z;
+    return reflect ? last * (z / (z - 1.0)) : (z / (z * z - 1.0)) * (z * before_last + last);
+}
+
+// a(i) = z (a(i + 1) - a(i)) for i = i1 down to i0; next = a(i1 + 1); returns a(i0)
+template <class A>
+__device__ __forceinline__ double spline3_anticausal_sweep(const A& a, int i1, int i0, double next) {
+    const double z = SPLINE3_Z;
+    for (int i = i1; i >= i0; --i) { next = z * (next - a(i)); a(i) = next; }
+    return next;
+}
+
+// one thread = one line (row: AXIS 1, column: AXIS 0) of the padded plane, in place
+template <int AXIS>
+__global__ __launch_bounds__(64) void spline3_prefilter_kernel(double* c, int Hp, int Wp, int reflect = 0) {
+    const int line = blockIdx.x * 64 + threadIdx.x;
+    const int nlines = AXIS == 1 ? Hp : Wp, n = AXIS == 1 ? Wp : Hp;
+    if (line >= nlines) return;
+    const LineGlobal a{AXIS == 1 ? c + (size_t)line * Wp : c + line, AXIS == 1 ? (size_t)1 : (size_t)Wp};
+    if (n == 1) return;                             // (scipy leaves a line of one sample as it is)
+    spline3_gain(a, 0, n);
+    a(0) = spline3_causal_init(a, n, reflect);
+    spline3_causal_sweep(a, 1, n, a(0));
+    a(n - 1) = spline3_anticausal_init(a(n - 2), a(n - 1), reflect);
+    spline3_anticausal_sweep(a, n - 2, 0, a(n - 1));
 }
 
 // fill_mode 'constant' / 'reflect' / 'wrap' (scipy.ndimage >= 1.6 geometric transforms, ni_interpolation.c map_coordinate): the plane
@@ -323,45 +360,80 @@ __device__ __forceinline__ double warp_map_coord(double x, int n) {   // scipy m
     }
     return x;
 }
+// ---- the sampling arithmetic of the warp, shared by the one-plane kernels below and the fused kernel of the device sample
+// builder (aug_warp_kernel): coordinate mapping, tap index mapping, the B-spline weights and their row-then-column accumulation.
+// MODE 0 is 'nearest' (scipy's mode of keras-preprocessing's default): cubic taps on the plane edge-padded by WARP_PAD.
+__device__ __forceinline__ void warp_src_coord(double m00, double m01, double m10, double m11, double o0, double o1, int r, int c,
+                                               double* y, double* x) {
+    *y = m00 * (double)r + m01 * (double)c + o0;
+    *x = m10 * (double)r + m11 * (double)c + o1;
+}
+// maps (y, x) by the mode; false: the pixel takes `cval` ('constant', source coordinate outside the plane)
+template <int MODE>
+__device__ __forceinline__ bool warp_map_point(double* y, double* x, int H, int W) {
+    if (MODE == WARP_CONST) {
+        if (*y < 0.0 || *y > (double)(H - 1) || *x < 0.0 || *x > (double)(W - 1)) return false;
+    } else if (MODE != 0) {
+        *y = warp_map_coord<MODE>(*y, H);
+        *x = warp_map_coord<MODE>(*x, W);
+    }
+    return true;
+}
+template <int MODE>
+__device__ __forceinline__ int warp_tap(int i, int n) {
+    if (MODE == 0) return min(max(i, 0), n - 1);
+    return MODE == WARP_REFLECT ? warp_reflect_idx(i, n) : warp_mirror(i, n);
+}
+// order 0: index of the source pixel of the mapped point
+template <int MODE>
+__device__ __forceinline__ size_t warp_nearest_index(double y, double x, int H, int W) {
+    return (size_t)warp_tap<MODE>((int)floor(y + 0.5), H) * W + warp_tap<MODE>((int)floor(x + 0.5), W);
+}
+__device__ __forceinline__ void bspline3_weights(double t, double* w) {
+    const double u = 1.0 - t;
+    w[0] = u * u * u / 6.0;
+    w[1] = (4.0 - 6.0 * t * t + 3.0 * t * t * t) / 6.0;
+    w[2] = (4.0 - 6.0 * u * u + 3.0 * u * u * u) / 6.0;
+    w[3] = t * t * t / 6.0;
+}
+// order 3: the four-by-four B-spline sum around the mapped point on the (Hc, Wc) coefficient plane (MODE 0: the padded plane,
+// the point moved by the pad and clamped to it)
+template <int MODE>
+__device__ __forceinline__ double warp_cubic_sample(const double* coef, int Hc, int Wc, double y, double x) {
+    if (MODE == 0) {
+        y = fmin(fmax(y + WARP_PAD, 0.0), (double)(Hc - 1));
+        x = fmin(fmax(x + WARP_PAD, 0.0), (double)(Wc - 1));
+    }
+    const int y0 = (int)floor(y), x0 = (int)floor(x);
+    const double ty = y - y0, tx = x - x0;
+    double wy[4], wx[4];
+    bspline3_weights(ty, wy);
+    bspline3_weights(tx, wx);
+    double acc = 0.0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int yy = warp_tap<MODE>(y0 - 1 + i, Hc);
+        double row = 0.0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) row += wx[j] * coef[(size_t)yy * Wc + warp_tap<MODE>(x0 - 1 + j, Wc)];
+        acc += wy[i] * row;
+    }
+    return acc;
+}
+
 template <int ORDER, int MODE>
 __global__ __launch_bounds__(256) void affine_warp_mode_kernel(const double* coef, const float* src, int H, int W, float* dst,
                                                                double m00, double m01, double m10, double m11, double o0, double o1, float cval) {
     const int c = blockIdx.x * 256 + threadIdx.x, r = blockIdx.y;
     if (c >= W) return;
-    double y = m00 * (double)r + m01 * (double)c + o0, x = m10 * (double)r + m11 * (double)c + o1;
-    if (MODE == WARP_CONST) {
-        if (y < 0.0 || y > (double)(H - 1) || x < 0.0 || x > (double)(W - 1)) { dst[(size_t)r * W + c] = cval; return; }
-    } else {
-        y = warp_map_coord<MODE>(y, H);
-        x = warp_map_coord<MODE>(x, W);
-    }
-    auto tap = [](int i, int n) { return MODE == WARP_REFLECT ? warp_reflect_idx(i, n) : warp_mirror(i, n); };
+    double y, x;
+    warp_src_coord(m00, m01, m10, m11, o0, o1, r, c, &y, &x);
+    if (!warp_map_point<MODE>(&y, &x, H, W)) { dst[(size_t)r * W + c] = cval; return; }
     if (ORDER == 0) {
-        dst[(size_t)r * W + c] = src[(size_t)tap((int)floor(y + 0.5), H) * W + tap((int)floor(x + 0.5), W)];
+        dst[(size_t)r * W + c] = src[warp_nearest_index<MODE>(y, x, H, W)];
         return;
     }
-    const int y0 = (int)floor(y), x0 = (int)floor(x);
-    const double ty = y - y0, tx = x - x0;
-    auto w3 = [](double t, double* w) {
-        const double u = 1.0 - t;
-        w[0] = u * u * u / 6.0;
-        w[1] = (4.0 - 6.0 * t * t + 3.0 * t * t * t) / 6.0;
-        w[2] = (4.0 - 6.0 * u * u + 3.0 * u * u * u) / 6.0;
-        w[3] = t * t * t / 6.0;
-    };
-    double wy[4], wx[4];
-    w3(ty, wy);
-    w3(tx, wx);
-    double acc = 0.0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int yy = tap(y0 - 1 + i, H);
-        double row = 0.0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) row += wx[j] * coef[(size_t)yy * W + tap(x0 - 1 + j, W)];
-        acc += wy[i] * row;
-    }
-    dst[(size_t)r * W + c] = (float)acc;
+    dst[(size_t)r * W + c] = (float)warp_cubic_sample<MODE>(coef, H, W, y, x);
 }
 
 template <int ORDER>
@@ -369,39 +441,13 @@ __global__ __launch_bounds__(256) void affine_warp_kernel(const double* coef, co
                                                           double m00, double m01, double m10, double m11, double o0, double o1) {
     const int c = blockIdx.x * 256 + threadIdx.x, r = blockIdx.y;
     if (c >= W) return;
-    const double y = m00 * (double)r + m01 * (double)c + o0, x = m10 * (double)r + m11 * (double)c + o1;
+    double y, x;
+    warp_src_coord(m00, m01, m10, m11, o0, o1, r, c, &y, &x);
     if (ORDER == 0) {
-        const int iy = min(max((int)floor(y + 0.5), 0), H - 1), ix = min(max((int)floor(x + 0.5), 0), W - 1);
-        dst[(size_t)r * W + c] = src[(size_t)iy * W + ix];
+        dst[(size_t)r * W + c] = src[warp_nearest_index<0>(y, x, H, W)];
         return;
     }
-    const int Hp = H + 2 * WARP_PAD, Wp = W + 2 * WARP_PAD;
-    const double yp = fmin(fmax(y + WARP_PAD, 0.0), (double)(Hp - 1)), xp = fmin(fmax(x + WARP_PAD, 0.0), (double)(Wp - 1));
-    const int y0 = (int)floor(yp), x0 = (int)floor(xp);
-    const double ty = yp - y0, tx = xp - x0;
-    auto w3 = [](double t, double* w) {
-        const double u = 1.0 - t;
-        w[0] = u * u * u / 6.0;
-        w[1] = (4.0 - 6.0 * t * t + 3.0 * t * t * t) / 6.0;
-        w[2] = (4.0 - 6.0 * u * u + 3.0 * u * u * u) / 6.0;
-        w[3] = t * t * t / 6.0;
-    };
-    double wy[4], wx[4];
-    w3(ty, wy);
-    w3(tx, wx);
-    double acc = 0.0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int yy = min(max(y0 - 1 + i, 0), Hp - 1);
-        double row = 0.0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int xx = min(max(x0 - 1 + j, 0), Wp - 1);
-            row += wx[j] * coef[(size_t)yy * Wp + xx];
-        }
-        acc += wy[i] * row;
-    }
-    dst[(size_t)r * W + c] = (float)acc;
+    dst[(size_t)r * W + c] = (float)warp_cubic_sample<0>(coef, H + 2 * WARP_PAD, W + 2 * WARP_PAD, y, x);
 }
 
 static void warp_coeffs(int n_in, int n_out, double* f, double* t) {
@@ -747,3 +793,241 @@ int pseg_prepare_images(int device, const uint8_t* image, const uint8_t* binary,
 }
 
 }  // extern "C"
+
+// ---- device-resident augmented training sample (pseg_train_forward_backward_aug / pseg_train_augment_sample) ------------------
+// lib/network.py:149-161 for one sample without a trip through host arrays: uint8 page -> float64 coefficient plane -> tiled
+// prefilter -> ONE fused warp launch per channel that also warps the mask (order 0) and writes both at their flipped
+// positions -> brightness in place.  The float64 arithmetic is that of the one-plane entries above (the shared inline functions),
+// so the sample has their bits; what differs is staging (uint8 in, no host planes), fusion and how the prefilter is spread.
+namespace pseg {
+
+// uint8 (H,W,C) channel ch -> float64 (H + 2 pad, W + 2 pad), edge-padded (uint8 -> float32 -> float64 is exact, so is this)
+__global__ __launch_bounds__(256) void aug_pad_u8_kernel(const uint8_t* src, int H, int W, int C, int ch, double* dst, int pad) {
+    const int Wp = W + 2 * pad, Hp = H + 2 * pad;
+    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+    if (x >= Wp || y >= Hp) return;
+    const int sy = min(max(y - pad, 0), H - 1), sx = min(max(x - pad, 0), W - 1);
+    dst[(size_t)y * Wp + x] = (double)src[((size_t)sy * W + sx) * C + ch];
+}
+
+// The prefilter of one axis, 64 lines per workgroup.  The thread-per-line kernel walks global memory sample by sample: a
+// dependent load and store per step, and along rows (AXIS 1) adjacent lanes Wp * 8 bytes apart.  Here the workgroup moves
+// 64 x 64 sample tiles between the plane and LDS with 512-byte row segments (all 256 threads, the next tile's loads in flight
+// while the current one is filtered), and lane l of wave 0 advances line l through the tile: forward over the chunks (gain,
+// causal initialisation from the first chunk, causal sweep, anticausal initialisation at the line's end), then backward.
+// Tile pitch 65 doubles: a row pass reads tile[l][i] -- lane stride 130 dwords = 2 mod 64, a ds_read_b64 half-wave covers the 64
+// banks once; a column pass reads tile[i][l], consecutive.
+constexpr int PF_TILE = 64, PF_PITCH = 65;
+
+struct LineTile {
+    double* t;      // sample i0 of the lane's line
+    int st, i0;
+    __device__ __forceinline__ double& operator()(int i) const { return t[(i - i0) * st]; }
+};
+
+template <int AXIS>
+__global__ __launch_bounds__(256) void spline3_prefilter_tile_kernel(double* c, int Hp, int Wp, int reflect) {
+    __shared__ double tile[PF_TILE * PF_PITCH];
+    const int nlines = AXIS == 1 ? Hp : Wp, n = AXIS == 1 ? Wp : Hp;
+    if (n == 1) return;                             // (scipy leaves a line of one sample as it is)
+    const int line0 = blockIdx.x * PF_TILE;
+    const int tid = threadIdx.x, tc = tid & 63, tr0 = tid >> 6;
+    const int nchunks = (n + PF_TILE - 1) / PF_TILE;
+    double reg[16];
+    // tile (r, tc) <-> plane (R0 + r, C0 + tc); a thread always moves the same 16 elements of a tile
+    auto load = [&](int k) {
+        const int R0 = AXIS == 1 ? line0 : k * PF_TILE, C0 = AXIS == 1 ? k * PF_TILE : line0;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            const int r = R0 + tr0 + 4 * j;
+            reg[j] = (r < Hp && C0 + tc < Wp) ? c[(size_t)r * Wp + C0 + tc] : 0.0;
+        }
+    };
+    auto store = [&](int k) {
+        const int R0 = AXIS == 1 ? line0 : k * PF_TILE, C0 = AXIS == 1 ? k * PF_TILE : line0;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            const int r = R0 + tr0 + 4 * j;
+            if (r < Hp && C0 + tc < Wp) c[(size_t)r * Wp + C0 + tc] = tile[(tr0 + 4 * j) * PF_PITCH + tc];
+        }
+    };
+    const bool active = tid < PF_TILE && line0 + tid < nlines;
+    double* const lane = tile + (AXIS == 1 ? tid * PF_PITCH : tid);   // (only dereferenced by active lanes: tid < 64)
+    const int lst = AXIS == 1 ? 1 : PF_PITCH;
+    double carry = 0.0;
+    load(0);
+    for (int k = 0; k < nchunks; ++k) {
+#pragma unroll
+        for (int j = 0; j < 16; ++j) tile[(tr0 + 4 * j) * PF_PITCH + tc] = reg[j] * 6.0;     // spline3_gain on the way in
+        __syncthreads();
+        if (k + 1 < nchunks) load(k + 1);
+        if (active) {
+            const int i0 = k * PF_TILE, i1 = min(n, i0 + PF_TILE);
+            const LineTile a{lane, lst, i0};
+            double before = carry;                  // c+[i0 - 1]
+            if (k == 0) {
+                carry = spline3_causal_init(a, n, reflect);
+                a(0) = carry;
+                carry = spline3_causal_sweep(a, 1, i1, carry);
+            } else {
+                carry = spline3_causal_sweep(a, i0, i1, carry);
+            }
+            if (k == nchunks - 1) {
+                if (n - 2 >= i0) before = a(n - 2);
+                carry = spline3_anticausal_init(before, carry, reflect);
+                a(n - 1) = carry;
+            }
+        }
+        __syncthreads();
+        store(k);
+        __syncthreads();
+    }
+    // backward: the last chunk is still in the tile; a thread reloads only what it stored itself
+    if (nchunks > 1) load(nchunks - 2);
+    for (int k = nchunks - 1; k >= 0; --k) {
+        if (k < nchunks - 1) {
+#pragma unroll
+            for (int j = 0; j < 16; ++j) tile[(tr0 + 4 * j) * PF_PITCH + tc] = reg[j];
+            __syncthreads();
+            if (k > 0) load(k - 1);
+        }
+        if (active) {
+            const int i0 = k * PF_TILE;
+            const LineTile a{lane, lst, i0};
+            const int i1 = k == nchunks - 1 ? n - 2 : i0 + PF_TILE - 1;     // carry = c-[i1 + 1]
+            carry = spline3_anticausal_sweep(a, i1, i0, carry);
+        }
+        __syncthreads();
+        store(k);
+        __syncthreads();
+    }
+}
+
+__device__ __forceinline__ unsigned brightness_key(float f) {     // the keys of brightness_minmax_kernel
+    const unsigned u = __float_as_uint(f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+// every lane of the wave calls this (lanes without a pixel pass +inf / -inf)
+__device__ __forceinline__ void aug_minmax(float lo, float hi, unsigned* mm) {
+    for (int o = 32; o > 0; o >>= 1) { lo = fminf(lo, __shfl_xor(lo, o)); hi = fmaxf(hi, __shfl_xor(hi, o)); }
+    if ((threadIdx.x & 63) == 0) {
+        atomicMin(&mm[0], brightness_key(lo));
+        atomicMax(&mm[1], brightness_key(hi));
+    }
+}
+
+template <int MODE>
+__device__ __forceinline__ uint8_t aug_mask_sample(const uint8_t* mask, int H, int W, double y, double x, uint8_t fill) {
+    if (!warp_map_point<MODE>(&y, &x, H, W)) return fill;
+    return mask[warp_nearest_index<MODE>(y, x, H, W)];
+}
+
+// One thread per output pixel of channel ch: cubic sample of the channel's coefficient plane, order-0 sample of the mask
+// (with channel 0), both written at the flipped position; min / max of the float sample for the brightness stretch (mm != NULL).
+template <int IMODE>
+__global__ __launch_bounds__(256) void aug_warp_kernel(const double* coef, const uint8_t* mask, int H, int W, int C, int ch,
+                                                       float* out_img, uint8_t* out_mask, double m00, double m01, double m10, double m11,
+                                                       double o0, double o1, unsigned flips, float image_cval, int mask_mode,
+                                                       uint8_t mask_fill, unsigned* mm) {
+    const int c = blockIdx.x * 256 + threadIdx.x, r = blockIdx.y;
+    float lo = INFINITY, hi = -INFINITY;
+    if (c < W) {
+        double y, x;
+        warp_src_coord(m00, m01, m10, m11, o0, o1, r, c, &y, &x);
+        const size_t o = (size_t)((flips & 2u) ? H - 1 - r : r) * W + ((flips & 1u) ? W - 1 - c : c);
+        if (ch == 0) {
+            uint8_t mv;
+            switch (mask_mode) {
+                case 0: mv = aug_mask_sample<0>(mask, H, W, y, x, mask_fill); break;
+                case WARP_CONST: mv = aug_mask_sample<WARP_CONST>(mask, H, W, y, x, mask_fill); break;
+                case WARP_REFLECT: mv = aug_mask_sample<WARP_REFLECT>(mask, H, W, y, x, mask_fill); break;
+                default: mv = aug_mask_sample<WARP_WRAP>(mask, H, W, y, x, mask_fill); break;
+            }
+            out_mask[o] = mv;
+        }
+        float v = image_cval;
+        if (warp_map_point<IMODE>(&y, &x, H, W))
+            v = (float)warp_cubic_sample<IMODE>(coef, IMODE == 0 ? H + 2 * WARP_PAD : H, IMODE == 0 ? W + 2 * WARP_PAD : W, y, x);
+        out_img[o * C + ch] = v;
+        lo = hi = v;
+    }
+    if (mm) aug_minmax(lo, hi, mm);
+}
+
+// no warp (the generator skips it for the identity): the exact uint8 values, flipped
+__global__ __launch_bounds__(256) void aug_flip_kernel(const uint8_t* img, const uint8_t* mask, int H, int W, int C, float* out_img,
+                                                       uint8_t* out_mask, unsigned flips, unsigned* mm) {
+    const int c = blockIdx.x * 256 + threadIdx.x, r = blockIdx.y;
+    float lo = INFINITY, hi = -INFINITY;
+    if (c < W) {
+        const size_t i = (size_t)r * W + c;
+        const size_t o = (size_t)((flips & 2u) ? H - 1 - r : r) * W + ((flips & 1u) ? W - 1 - c : c);
+        out_mask[o] = mask[i];
+        for (int ch = 0; ch < C; ++ch) {
+            const float v = (float)img[i * C + ch];
+            out_img[o * C + ch] = v;
+            lo = fminf(lo, v);
+            hi = fmaxf(hi, v);
+        }
+    }
+    if (mm) aug_minmax(lo, hi, mm);
+}
+
+size_t augment_coef_count(int H, int W, int image_fill) {
+    const int pad = image_fill == 0 ? WARP_PAD : 0;
+    return (size_t)(H + 2 * pad) * (W + 2 * pad);
+}
+
+int augment_sample_device(const AugSample& a, hipStream_t st) {
+    const int H = a.H, W = a.W, C = a.C;
+    const dim3 grid(cdiv(W, 256), H);
+    unsigned* mm = a.use_brightness ? a.d_mm : nullptr;
+    if (mm) {
+        static const unsigned init[2] = {0xffffffffu, 0u};
+        PSEG_HIP(hipMemcpyAsync(mm, init, 8, hipMemcpyHostToDevice, st));
+    }
+    if (!a.m) {
+        aug_flip_kernel<<<grid, 256, 0, st>>>(a.d_src_img, a.d_src_mask, H, W, C, a.d_img, a.d_mask, a.flips, mm);
+    } else {
+        const int pad = a.image_fill == 0 ? WARP_PAD : 0;       // (every mode but 'nearest': scipy filters the plane itself)
+        const int Hp = H + 2 * pad, Wp = W + 2 * pad;
+        const uint8_t mfill = (uint8_t)(int)a.mask_cval;
+        const double* m = a.m;
+        const double* off = a.off;
+        for (int ch = 0; ch < C; ++ch) {
+            aug_pad_u8_kernel<<<dim3(cdiv(Wp, 256), Hp), 256, 0, st>>>(a.d_src_img, H, W, C, ch, a.d_coef, pad);
+            spline3_prefilter_tile_kernel<0><<<cdiv(Wp, PF_TILE), 256, 0, st>>>(a.d_coef, Hp, Wp, a.image_fill == 2);   // axis 0 first, as scipy's spline_filter
+            spline3_prefilter_tile_kernel<1><<<cdiv(Hp, PF_TILE), 256, 0, st>>>(a.d_coef, Hp, Wp, a.image_fill == 2);
+#define PSEG_AUG_WARP(MODE_)                                                                                                              \
+    aug_warp_kernel<MODE_><<<grid, 256, 0, st>>>(a.d_coef, a.d_src_mask, H, W, C, ch, a.d_img, a.d_mask, m[0], m[1], m[2], m[3], off[0], \
+                                                 off[1], a.flips, a.image_cval, a.mask_fill, mfill, mm)
+            switch (a.image_fill) {
+                case 0: PSEG_AUG_WARP(0); break;
+                case 1: PSEG_AUG_WARP(WARP_CONST); break;
+                case 2: PSEG_AUG_WARP(WARP_REFLECT); break;
+                default: PSEG_AUG_WARP(WARP_WRAP); break;
+            }
+#undef PSEG_AUG_WARP
+        }
+    }
+    if (a.use_brightness) {
+        const size_t n = (size_t)H * W * C;
+        const int bgrid = (int)std::min<size_t>((n + 255) / 256, 2048);
+        brightness_apply_kernel<<<bgrid, 256, 0, st>>>(a.d_img, a.d_img, n, a.d_mm, a.brightness);
+    }
+    PSEG_HIP(hipGetLastError());
+    return PSEG_OK;
+}
+
+int augment_check(int H, int W, const double* m, const double* off, unsigned flips, int image_fill, int mask_fill, float mask_cval) {
+    PSEG_TRY(check_shape(H, W, H, W));
+    if ((m == nullptr) != (off == nullptr)) return fail(PSEG_EINVAL, "matrix and offset come together (both NULL: no warp)");
+    if (flips & ~3u) return fail(PSEG_EINVAL, "flips 0x%x (bit 0 horizontal, bit 1 vertical)", flips);
+    if (image_fill < 0 || image_fill > 3 || mask_fill < 0 || mask_fill > 3)
+        return fail(PSEG_EUNSUPPORTED, "fill modes %d / %d (0 'nearest', 1 'constant', 2 'reflect', 3 'wrap')", image_fill, mask_fill);
+    if (!(mask_cval >= 0.0f && mask_cval <= 255.0f) || mask_cval != (float)(int)mask_cval)
+        return fail(PSEG_EINVAL, "mask_cval %g is not an integer in 0..255 (the mask is built as uint8)", (double)mask_cval);
+    return PSEG_OK;
+}
+
+}  // namespace pseg

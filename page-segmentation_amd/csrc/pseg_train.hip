@@ -62,6 +62,13 @@ struct TrainState {
     uint8_t* d_mask = nullptr;
     uint8_t* d_img = nullptr;
     size_t logits_bytes = 0, mask_bytes = 0, img_bytes = 0;
+    // device-resident augmentation (pseg_train_forward_backward_aug): the uploaded uint8 page and mask, the float64 spline
+    // coefficient plane of one channel, min / max keys of the brightness stretch; the sample itself lands in d_img / d_mask
+    uint8_t* d_aug_img = nullptr;
+    uint8_t* d_aug_mask = nullptr;
+    double* d_aug_coef = nullptr;
+    unsigned* d_aug_mm = nullptr;
+    size_t aug_img_bytes = 0, aug_mask_bytes = 0, aug_coef_bytes = 0, aug_mm_bytes = 0;
     int H = 0, W = 0;
     // weight gradients run on a stream of their own beside the data gradients (both only read dY; see train_forward_backward)
     hipStream_t wstream = nullptr;
@@ -79,6 +86,7 @@ void train_free(Engine& e) {
     (void)hipFree(t->d_wd); (void)hipFree(t->d_wdrem); (void)hipFree(t->d_logits); (void)hipFree(t->d_dlogits);
     (void)hipFree(t->d_wpart); (void)hipFree(t->d_mpart); (void)hipFree(t->d_bpart);
     (void)hipFree(t->d_mask); (void)hipFree(t->d_img); (void)hipFree(t->d_tmp); (void)hipFree(t->d_tmp2);
+    (void)hipFree(t->d_aug_img); (void)hipFree(t->d_aug_mask); (void)hipFree(t->d_aug_coef); (void)hipFree(t->d_aug_mm);
     if (t->wstream) { (void)hipStreamSynchronize(t->wstream); (void)hipStreamDestroy(t->wstream); }
     if (t->ev_dy) (void)hipEventDestroy(t->ev_dy);
     if (t->ev_wdone) (void)hipEventDestroy(t->ev_wdone);
@@ -1149,9 +1157,10 @@ static int train_init(Engine& e, float b1, float b2, float eps, float clipnorm, 
     return PSEG_OK;
 }
 
-// forward + loss/metrics (+ backward when `backward`); inputs are host pointers
-static int train_fwd_bwd(Engine& e, const uint8_t* img, const uint8_t* mask, int H, int W, bool backward,
-                         const float* img_f32 = nullptr) {
+static int train_compute(Engine& e, int H, int W, bool backward, bool img_f32);
+
+// the step's device state for an (H, W) page: weights uploaded, canvas set, page / mask / logits buffers sized
+static int train_stage(Engine& e, int H, int W, bool img_f32) {
     TrainState* t = TS(e);
     if (!t) return fail(PSEG_EINVAL, "pseg_train_init has not been called");
     PSEG_HIP(hipSetDevice(e.device));
@@ -1159,7 +1168,6 @@ static int train_fwd_bwd(Engine& e, const uint8_t* img, const uint8_t* mask, int
         if (!p.set) return fail(PSEG_EINVAL, "weight '%s' was never set", p.name.c_str());
     if (e.weights_dirty) PSEG_TRY(upload_weights(e));
     PSEG_TRY(set_canvas(e, H, W, e.stream));
-    hipStream_t st = e.stream;
     const int C = e.n_classes;
     const size_t npx = (size_t)H * W;
     PSEG_TRY(ensure_buf((void**)&t->d_img, &t->img_bytes, npx * e.in_ch * (img_f32 ? 4 : 1)));
@@ -1170,9 +1178,28 @@ static int train_fwd_bwd(Engine& e, const uint8_t* img, const uint8_t* mask, int
     PSEG_TRY(ensure_buf((void**)&t->d_dlogits, &lb, npx * C * 4));
     t->logits_bytes = lb;
     t->H = H; t->W = W;
+    return PSEG_OK;
+}
+
+// forward + loss/metrics (+ backward when `backward`); inputs are host pointers
+static int train_fwd_bwd(Engine& e, const uint8_t* img, const uint8_t* mask, int H, int W, bool backward,
+                         const float* img_f32 = nullptr) {
+    PSEG_TRY(train_stage(e, H, W, img_f32 != nullptr));
+    TrainState* t = TS(e);
+    hipStream_t st = e.stream;
+    const size_t npx = (size_t)H * W;
     if (img_f32) PSEG_HIP(hipMemcpyAsync(t->d_img, img_f32, npx * e.in_ch * 4, hipMemcpyHostToDevice, st));
     else PSEG_HIP(hipMemcpyAsync(t->d_img, img, npx * e.in_ch, hipMemcpyHostToDevice, st));
     PSEG_HIP(hipMemcpyAsync(t->d_mask, mask, npx, hipMemcpyHostToDevice, st));
+    return train_compute(e, H, W, backward, img_f32 != nullptr);
+}
+
+// the compute part of the step on the page in t->d_img (uint8, or float32 on the 0..255 scale) and the mask in t->d_mask
+static int train_compute(Engine& e, int H, int W, bool backward, bool img_f32) {
+    TrainState* t = TS(e);
+    hipStream_t st = e.stream;
+    const int C = e.n_classes;
+    const size_t npx = (size_t)H * W;
     e.cur_img_f32 = img_f32 ? (const float*)t->d_img : nullptr;
     // Dropout layers are live in a training forward (Keras fit), the identity in an evaluation step
     const uint32_t drop_key = backward ? (t->drop_seed * 0x632BE5ABu + (uint32_t)t->fwd_count * 0x9E3779B9u) | 1u : 0u;
@@ -1453,6 +1480,31 @@ static int train_fwd_bwd(Engine& e, const uint8_t* img, const uint8_t* mask, int
     return PSEG_OK;
 }
 
+// uploads the uint8 page and mask once and builds the augmented sample in t->d_img (float32) / t->d_mask on e.stream
+static int train_augment(Engine& e, const uint8_t* img, const uint8_t* mask, int H, int W, const double* m, const double* off,
+                         unsigned flips, int image_fill, float image_cval, int mask_fill, float mask_cval, int use_brightness,
+                         float brightness) {
+    TrainState* t = TS(e);
+    hipStream_t st = e.stream;
+    const size_t npx = (size_t)H * W;
+    auto grow = [](void** p, size_t* cap, size_t bytes) -> int {
+        if (ensure_buf(p, cap, bytes) == PSEG_OK) return PSEG_OK;
+        const std::string why = last_error();
+        return fail(PSEG_ENOMEM, "augmentation buffer of %zu bytes: %s", bytes, why.c_str());
+    };
+    PSEG_TRY(grow((void**)&t->d_img, &t->img_bytes, npx * e.in_ch * 4));
+    PSEG_TRY(grow((void**)&t->d_mask, &t->mask_bytes, npx));
+    PSEG_TRY(grow((void**)&t->d_aug_img, &t->aug_img_bytes, npx * e.in_ch));
+    PSEG_TRY(grow((void**)&t->d_aug_mask, &t->aug_mask_bytes, npx));
+    PSEG_TRY(grow((void**)&t->d_aug_mm, &t->aug_mm_bytes, 8));
+    if (m) PSEG_TRY(grow((void**)&t->d_aug_coef, &t->aug_coef_bytes, augment_coef_count(H, W, image_fill) * 8));
+    PSEG_HIP(hipMemcpyAsync(t->d_aug_img, img, npx * e.in_ch, hipMemcpyHostToDevice, st));
+    PSEG_HIP(hipMemcpyAsync(t->d_aug_mask, mask, npx, hipMemcpyHostToDevice, st));
+    const AugSample a{t->d_aug_img, t->d_aug_mask, H, W, e.in_ch, m, off, flips, image_fill, mask_fill, image_cval, mask_cval,
+                      use_brightness, brightness, t->d_aug_coef, t->d_aug_mm, (float*)t->d_img, t->d_mask};
+    return augment_sample_device(a, st);
+}
+
 static int train_metrics(Engine& e, float out[4]) {
     TrainState* t = TS(e);
     const int C = e.n_classes;
@@ -1662,6 +1714,39 @@ int pseg_train_forward_backward_f32(pseg_engine* h, const float* img, const uint
     if (H <= 0 || W <= 0) return fail(PSEG_EINVAL, "empty page %dx%d", H, W);
     PSEG_TRY(train_fwd_bwd(h->e, nullptr, mask, H, W, true, img));
     if (metrics) PSEG_TRY(train_metrics(h->e, metrics));
+    return PSEG_OK;
+}
+
+int pseg_train_forward_backward_aug(pseg_engine* h, const uint8_t* img, const uint8_t* mask, int H, int W, const double* m,
+                                    const double* off, unsigned flips, int image_fill_mode, float image_cval, int mask_fill_mode,
+                                    float mask_cval, int use_brightness, float brightness, float metrics[4]) {
+    if (!h || !img || !mask) return fail(PSEG_EINVAL, "NULL argument");
+    KnobScope knob_scope(h->e);
+    PSEG_TRY(augment_check(H, W, m, off, flips, image_fill_mode, mask_fill_mode, mask_cval));
+    PSEG_TRY(train_stage(h->e, H, W, true));
+    PSEG_TRY(train_augment(h->e, img, mask, H, W, m, off, flips, image_fill_mode, image_cval, mask_fill_mode, mask_cval,
+                           use_brightness, brightness));
+    PSEG_TRY(train_compute(h->e, H, W, true, true));
+    if (metrics) PSEG_TRY(train_metrics(h->e, metrics));
+    return PSEG_OK;
+}
+
+int pseg_train_augment_sample(pseg_engine* h, const uint8_t* img, const uint8_t* mask, int H, int W, const double* m,
+                              const double* off, unsigned flips, int image_fill_mode, float image_cval, int mask_fill_mode,
+                              float mask_cval, int use_brightness, float brightness, float* out_img, uint8_t* out_mask) {
+    if (!h || !img || !mask || !out_img || !out_mask) return fail(PSEG_EINVAL, "NULL argument");
+    Engine& e = h->e;
+    KnobScope knob_scope(e);
+    TrainState* t = TS(e);
+    if (!t) return fail(PSEG_EINVAL, "pseg_train_init has not been called");
+    PSEG_TRY(augment_check(H, W, m, off, flips, image_fill_mode, mask_fill_mode, mask_cval));
+    PSEG_HIP(hipSetDevice(e.device));
+    PSEG_TRY(train_augment(e, img, mask, H, W, m, off, flips, image_fill_mode, image_cval, mask_fill_mode, mask_cval,
+                           use_brightness, brightness));
+    const size_t npx = (size_t)H * W;
+    PSEG_HIP(hipMemcpyAsync(out_img, t->d_img, npx * e.in_ch * 4, hipMemcpyDeviceToHost, e.stream));
+    PSEG_HIP(hipMemcpyAsync(out_mask, t->d_mask, npx, hipMemcpyDeviceToHost, e.stream));
+    PSEG_HIP(hipStreamSynchronize(e.stream));
     return PSEG_OK;
 }
 

@@ -41,6 +41,7 @@ class ImageDataGeneratorCustom:
         self.horizontal_flip = horizontal_flip
         self.vertical_flip = vertical_flip
         self.rescale = rescale
+        self.preprocessing_function = preprocessing_function
         self.interpolation_order = interpolation_order
         self.fill_mode = fill_mode
         self.cval = cval
@@ -147,3 +148,47 @@ class ImageDataGeneratorCustom:
                     seen += 1
                     yield out[None].astype(gen.dtype)
         return it()
+
+
+def draw_sample_transforms(image_gen, mask_gen, image_shape, mask_shape, seed):
+    """The NumPy draws of one training sample (lib/network.py:149-153), without the pixel work:
+        next(image_gen.flow(image[None], seed=seed, batch_size=1)); next(mask_gen.flow(mask[None], seed=seed, batch_size=1))
+    -- each flow() re-seeds the global RandomState, permutes its one sample and draws its transform parameters (the image
+    generator's brightness factor last).  -> (image parameters, mask parameters); the global state is left exactly where the
+    two flow() calls leave it (it decides the next epoch's np.random.shuffle)."""
+    out = []
+    for gen, shape in ((image_gen, image_shape), (mask_gen, mask_shape)):
+        np.random.seed(seed)
+        np.random.permutation(1)
+        out.append(gen.get_random_transform(shape))
+    return tuple(out)
+
+
+def device_transform_args(params, h, w):
+    """Transform parameters -> the (matrix, offset, flips) arguments of Engine.train_forward_backward_augmented: affine_matrix's
+    2x2 matrix (flat, float64) and offset, both None for the identity (no warp runs); flips bit 0 horizontal, bit 1 vertical."""
+    flips = (1 if params.get('flip_horizontal', False) else 0) | (2 if params.get('flip_vertical', False) else 0)
+    mo = ImageDataGeneratorCustom.affine_matrix(params, h, w)
+    if mo is None:
+        return None, None, flips
+    return (np.ascontiguousarray(mo[0], dtype=np.float64).reshape(4), np.ascontiguousarray(mo[1], dtype=np.float64).reshape(2), flips)
+
+
+_SHARED_FIELDS = ('rotation_range', 'width_shift_range', 'height_shift_range', 'shear_range', 'zoom_range', 'horizontal_flip',
+                  'vertical_flip')
+
+
+def device_path_covers(image_gen, mask_gen):
+    """Whether one device-resident call builds what the two generators build: cubic image / order-0 mask generators that draw
+    the same affine parameters, float32 output, no rescale / preprocessing_function, no mask brightness, and a mask fill value that a uint8
+    mask holds (the host path casts the float mask with astype(uint8))."""
+    if image_gen.interpolation_order != 3 or mask_gen.interpolation_order != 0 or mask_gen.brightness_range is not None:
+        return False
+    if any(getattr(image_gen, k) != getattr(mask_gen, k) for k in _SHARED_FIELDS):
+        return False
+    if any(g.rescale or g.preprocessing_function is not None for g in (image_gen, mask_gen)):
+        return False
+    if any(np.dtype(g.dtype) != np.float32 for g in (image_gen, mask_gen)):     # flow() casts with astype(gen.dtype)
+        return False
+    cv = mask_gen.cval
+    return bool(np.isscalar(cv) and float(cv) == int(cv) and 0 <= cv <= 255)

@@ -23,6 +23,11 @@ logger = logging.getLogger(__name__)
 
 
 class Network:
+    # train_dataset with data_augmentation: build each sample on the device in one call (Engine.train_forward_backward_augmented).
+    # False -- or settings that call does not cover (data_generator.device_path_covers) -- takes the host-array path through the
+    # generators' flow(); both paths make the same NumPy draws and the same sample.
+    device_augmentation = True
+
     def __init__(self,
                  type: str,
                  n_classes: int = -1,
@@ -354,7 +359,9 @@ class Network:
         train = s.train_data.data
         n = len(train)
         if s.data_augmentation:
+            from .data_generator import device_path_covers, device_transform_args, draw_sample_transforms
             image_gen, _, mask_gen = self._create_data_augmentation(s.data_augmentation_settings)
+            on_device = bool(self.device_augmentation) and device_path_covers(image_gen, mask_gen)
         it = 0
         for epoch in range(s.n_epoch):
             np.random.shuffle(train)                      # lib/network.py:134-135 (in place)
@@ -370,6 +377,11 @@ class Network:
                 # the same numbers at world 1 and independent of the rank count), shared by the image (cubic)
                 # and mask (nearest) warps; the float page keeps the 0..255 scale, the engine divides by 255
                 seed = epoch * n + k + 1
+                if on_device and img.dtype == np.uint8 and m.dtype == np.uint8:
+                    p_img, _ = draw_sample_transforms(image_gen, mask_gen, img.shape[:2] + (1,), m.shape + (1,), seed)
+                    matrix, offset, flips = device_transform_args(p_img, img.shape[0], img.shape[1])
+                    return self.model.train_forward_backward_augmented(img, m, matrix, offset, flips, image_gen.fill_mode, image_gen.cval,
+                                                                       mask_gen.fill_mode, mask_gen.cval, p_img['brightness'])
                 from .util import image_to_batch
                 i_n = next(image_gen.flow(image_to_batch(img), seed=seed, batch_size=1))[0]
                 m_n = next(mask_gen.flow(image_to_batch(m), seed=seed, batch_size=1))[0, ..., 0]

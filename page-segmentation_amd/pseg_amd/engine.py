@@ -20,7 +20,8 @@ EXPORTED_SYMBOLS = (
     "pseg_host_alloc", "pseg_host_free", "pseg_host_register", "pseg_host_unregister",
     "pseg_predict_margin_device", "pseg_predict_exact_labels_device", "pseg_predict_exact_labels", "pseg_label_exact_stats", "pseg_label_exact_stats_ex",
     "pseg_timing_enable", "pseg_timing_reset", "pseg_timing_num_slots", "pseg_timing_get",
-    "pseg_train_init", "pseg_train_set_optimizer", "pseg_train_set_loss", "pseg_train_set_dropout_seed", "pseg_train_forward_backward", "pseg_train_forward_backward_f32", "pseg_train_grad_buffer", "pseg_train_metrics",
+    "pseg_train_init", "pseg_train_set_optimizer", "pseg_train_set_loss", "pseg_train_set_dropout_seed", "pseg_train_forward_backward", "pseg_train_forward_backward_f32",
+    "pseg_train_forward_backward_aug", "pseg_train_augment_sample", "pseg_train_grad_buffer", "pseg_train_metrics",
     "pseg_train_apply", "pseg_train_get_gradient", "pseg_eval_step",
     "pseg_allreduce_unique_id", "pseg_allreduce_init", "pseg_train_allreduce", "pseg_allreduce_destroy",
     "pseg_cc_vote", "pseg_cc_vote_device", "pseg_cc_vote_device_u8", "pseg_release_workspace", "pseg_bbox_fill",
@@ -103,6 +104,8 @@ def lib():
     L.pseg_train_set_dropout_seed.argtypes = [vp, c.c_uint32]
     L.pseg_train_forward_backward.argtypes = [vp, vp, vp, i, i, c.POINTER(f)]
     L.pseg_train_forward_backward_f32.argtypes = [vp, vp, vp, i, i, c.POINTER(f)]
+    L.pseg_train_forward_backward_aug.argtypes = [vp, vp, vp, i, i, vp, vp, c.c_uint, i, f, i, f, i, f, c.POINTER(f)]
+    L.pseg_train_augment_sample.argtypes = [vp, vp, vp, i, i, vp, vp, c.c_uint, i, f, i, f, i, f, vp, vp]
     L.pseg_train_grad_buffer.argtypes = [vp, c.POINTER(vp), c.POINTER(i64)]
     L.pseg_train_metrics.argtypes = [vp, c.POINTER(f)]
     L.pseg_train_apply.argtypes = [vp, f, f]
@@ -515,6 +518,47 @@ class Engine:
         out = (ctypes.c_float * 4)()
         _check(lib().pseg_train_forward_backward_f32(self._h, _ptr(img), _ptr(m), img.shape[0], img.shape[1], out))
         return tuple(float(v) for v in out)
+
+    def _augment_args(self, image_u8, mask_u8, matrix, offset, flips, image_fill, image_cval, mask_fill, mask_cval, brightness):
+        """The common arguments of pseg_train_forward_backward_aug / pseg_train_augment_sample (arrays first: they stay alive
+        with the tuple)."""
+        img, msk = self._img_mask(image_u8, mask_u8)
+        if np.asarray(image_u8).dtype != np.uint8 or np.asarray(mask_u8).dtype != np.uint8:
+            raise PsegError("the device augmentation takes the uint8 page and the uint8 mask")
+        if msk.ndim != 2 or img.shape[2:] not in ((), (self.in_channels,)) or (img.ndim == 2 and self.in_channels != 1):
+            raise PsegError("page %r / mask %r do not fit an engine with %d input channels" % (img.shape, msk.shape, self.in_channels))
+        if (matrix is None) != (offset is None):
+            raise PsegError("matrix and offset come together (both None: no warp)")
+        m = None if matrix is None else np.ascontiguousarray(matrix, dtype=np.float64).reshape(4)
+        o = None if offset is None else np.ascontiguousarray(offset, dtype=np.float64).reshape(2)
+        fills = []
+        for fm in (image_fill, mask_fill):
+            if fm not in FILL_MODES and fm not in FILL_MODES.values():
+                raise PsegError("unknown fill mode %r" % (fm,))
+            fills.append(FILL_MODES.get(fm, fm))
+        return (img, msk, m, o), (self._h, _ptr(img), _ptr(msk), img.shape[0], img.shape[1], _ptr(m), _ptr(o), int(flips),
+                                  int(fills[0]), float(image_cval), int(fills[1]), float(mask_cval),
+                                  0 if brightness is None else 1, 0.0 if brightness is None else float(brightness))
+
+    def train_forward_backward_augmented(self, image_u8, mask_u8, matrix, offset, flips, image_fill, image_cval, mask_fill,
+                                         mask_cval, brightness=None):
+        """One augmented training step without host arrays in between (pseg_train_forward_backward_aug): the uint8 page (H,W[,C])
+        and mask (H,W) go up once, the sample of lib/network.py:149-161 -- cubic warp of the image by (matrix, offset) with
+        image_fill / image_cval, order-0 warp of the mask with mask_fill / mask_cval, flips (bit 0 horizontal, bit 1 vertical),
+        brightness factor (None: none) -- is built on the device and trained on.  matrix None: no warp.
+        -> (loss, accuracy, jacard_coef, dice_coef)."""
+        keep, args = self._augment_args(image_u8, mask_u8, matrix, offset, flips, image_fill, image_cval, mask_fill, mask_cval, brightness)
+        out = (ctypes.c_float * 4)()
+        _check(lib().pseg_train_forward_backward_aug(*args, out))
+        return tuple(float(v) for v in out)
+
+    def augment_sample(self, image_u8, mask_u8, matrix, offset, flips, image_fill, image_cval, mask_fill, mask_cval, brightness=None):
+        """The sample train_forward_backward_augmented trains on -> (float32 image (H,W[,C]) on the 0..255 scale, uint8 mask)."""
+        keep, args = self._augment_args(image_u8, mask_u8, matrix, offset, flips, image_fill, image_cval, mask_fill, mask_cval, brightness)
+        o_img = np.empty(keep[0].shape, np.float32)
+        o_msk = np.empty(keep[1].shape, np.uint8)
+        _check(lib().pseg_train_augment_sample(*args, _ptr(o_img), _ptr(o_msk)))
+        return o_img, o_msk
 
     def eval_step(self, image, mask):
         img, msk = self._img_mask(image, mask)
