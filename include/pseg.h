@@ -351,6 +351,40 @@ int pseg_masks_device_u8(int device, const uint8_t* d_pred, const uint8_t* d_bin
                          const uint8_t* d_lut, int n_lut, int H, int W, uint8_t* d_color,
                          uint8_t* d_overlay, uint8_t* d_inverted, uint8_t* d_fg_color, void* stream);
 
+/* ---- PNG output: lib/output.py:20-41 (Image.fromarray(mask).save(...)) --------------------------------------------- */
+
+/* PNG encoder whose pixels are in device memory.  The stream is signature | IHDR | IDAT(zlib header) | one IDAT per band of
+ * `band_rows` rows | IDAT(final empty stored block, Adler-32) | IEND; 8-bit truecolour (channels = 3) or 8-bit gray (1),
+ * non-interlaced, every scanline filtered with Up.  A band is one fixed-Huffman deflate block closed by an empty stored block
+ * (zlib's sync flush), encoded by one workgroup independently of all others; matches are runs against the pixel to the left.
+ * band_rows = 0: the default, max(1, 16384 / (channels * W + 1)) rows; any value is cut to H and to 2^30 filtered bytes per band.
+ *
+ * pseg_png_bound: upper bound of the encoded size, pure arithmetic (no device).  With L = channels * W + 1 bytes per filtered
+ * scanline and bands of n = rows * L bytes each,
+ *     bound = 80 + sum over the bands of (12 + n + n / 8 + 8)
+ * (80 = signature 8 + IHDR 25 + first IDAT 14 + last IDAT 21 + IEND 12; 12 = chunk framing; a band costs at most 3 + 9 n + 7 + 3
+ * bits -- block header, 9 bits per byte, end of block, stored-block header -- padded to a byte, plus 4).  0 for a bad shape. */
+size_t pseg_png_bound(int H, int W, int channels, int band_rows);
+/* d_src: (H,W[,3]) uint8 in device memory; out: host memory (page-locked for best speed) of cap >= pseg_png_bound(...) bytes
+ * (else PSEG_EINVAL); *n_bytes = the stream's size.  Runs on `stream` and waits for it (synchronous); never writes past cap. */
+int pseg_png_encode_device(int device, const uint8_t* d_src, int H, int W, int channels, int band_rows, uint8_t* out, size_t cap,
+                           size_t* n_bytes, void* stream);
+/* generate_output_masks (lib/output.py:44-60) + PNG in one pass: the band kernel computes the masks' pixels from the uint8 label
+ * map, the binarisation and the colour table (pseg_masks_device_u8's selection), the RGB masks never exist in memory.
+ * Order: color / overlay / inverted / fg_color; out[k] == NULL: mask k is not wanted (n_bytes[k] = 0). */
+int pseg_masks_png_device_u8(int device, const uint8_t* d_pred, const uint8_t* d_binary, const uint8_t* d_lut, int n_lut, int H, int W,
+                             int band_rows, uint8_t* const out[4], const size_t cap[4], size_t n_bytes[4], void* stream);
+/* Host-array counterparts: upload, encode, download (pseg_masks' pattern).  pseg_masks_png takes the reference's int64 label map;
+ * labels outside the colour table are black, as in pseg_masks (PSEG_EINVAL if the table has all 256 entries and such a label occurs). */
+int pseg_png_encode(int device, const uint8_t* src, int H, int W, int channels, int band_rows, uint8_t* out, size_t cap, size_t* n_bytes);
+int pseg_masks_png(int device, const int64_t* pred, const uint8_t* binary, const uint8_t* lut, int n_lut, int H, int W, int band_rows,
+                   uint8_t* const out[4], const size_t cap[4], size_t n_bytes[4]);
+/* pseg_predict_chain with the masks as PNG streams: same stages, same label outputs; png[k] (host, cap[k] >= pseg_png_bound(Hl, Wl,
+ * 3, 0) bytes, NULL: not wanted) in the order color / overlay / inverted / fg_color, n_bytes[k] their sizes. */
+int pseg_predict_chain_png(pseg_engine* e, const uint8_t* img, int H, int W, int Ho, int Wo, const uint8_t* binary,
+                           const int* post_ops, int n_post, unsigned flags, int64_t* labels, uint8_t* labels_u8,
+                           const uint8_t* lut, int n_lut, uint8_t* const png[4], const size_t cap[4], size_t n_bytes[4]);
+
 /* compute_char_height (lib/image_ops.py:58-82) minus the file read: Otsu threshold, invert
  * unless `inverse`, 4-connected components, keep glyph-shaped ones, upper median of heights.
  * *height = -1 when no component qualifies (the reference returns None). *otsu gets the

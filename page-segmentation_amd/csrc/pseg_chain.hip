@@ -48,10 +48,13 @@ __global__ void chain_widen_kernel(const uint8_t* in, int64_t* out, size_t n) {
 
 using namespace pseg;
 
-extern "C" int pseg_predict_chain(pseg_engine* h, const uint8_t* img, int H, int W, int Ho, int Wo, const uint8_t* binary,
-                                  const int* post_ops, int n_post, unsigned flags, int64_t* labels, uint8_t* labels_u8,
-                                  const uint8_t* lut, int n_lut, uint8_t* color, uint8_t* overlay, uint8_t* inverted,
-                                  uint8_t* fg_color) {
+// the masks of a chain call as PNG streams (pseg_predict_chain_png) instead of raw arrays
+struct ChainPng { uint8_t* const* out; const size_t* cap; size_t* n_bytes; };
+
+static int chain_run(pseg_engine* h, const uint8_t* img, int H, int W, int Ho, int Wo, const uint8_t* binary,
+                     const int* post_ops, int n_post, unsigned flags, int64_t* labels, uint8_t* labels_u8,
+                     const uint8_t* lut, int n_lut, uint8_t* color, uint8_t* overlay, uint8_t* inverted,
+                     uint8_t* fg_color, const ChainPng* png) {
     if (!h || !img) return fail(PSEG_EINVAL, "NULL argument");
     KnobScope knob_scope(h->e);
     Engine& e = h->e;
@@ -60,7 +63,8 @@ extern "C" int pseg_predict_chain(pseg_engine* h, const uint8_t* img, int H, int
     if (flags & ~(unsigned)PSEG_CHAIN_EXACT_LABELS) return fail(PSEG_EINVAL, "unknown flag bits 0x%x", flags);
     const bool resize = Ho > 0 && Wo > 0 && (Ho != H || Wo != W);
     const int Hl = resize ? Ho : H, Wl = resize ? Wo : W;
-    const bool want_masks = color || overlay || inverted || fg_color;
+    const bool want_png = png && (png->out[0] || png->out[1] || png->out[2] || png->out[3]);
+    const bool want_masks = color || overlay || inverted || fg_color || want_png;
     bool need_bin = want_masks;
     for (int i = 0; i < n_post; ++i) {
         if (post_ops[i] != PSEG_POST_CC_VOTE && post_ops[i] != PSEG_POST_BBOX) return fail(PSEG_EINVAL, "unknown post-processor id %d", post_ops[i]);
@@ -68,6 +72,12 @@ extern "C" int pseg_predict_chain(pseg_engine* h, const uint8_t* img, int H, int
     }
     if (need_bin && !binary) return fail(PSEG_EINVAL, "the vote / the masks need the binarisation");
     if (want_masks && (!lut || n_lut < 1)) return fail(PSEG_EINVAL, "the masks need the colour table");
+    if (want_png) {
+        if (n_lut > 256) return fail(PSEG_EINVAL, "n_lut %d out of range (1..256)", n_lut);
+        const size_t bound = pseg_png_bound(Hl, Wl, 3, 0);
+        for (int k = 0; k < 4; ++k)
+            if (png->out[k] && png->cap[k] < bound) return fail(PSEG_EINVAL, "png: output buffer %d of %zu bytes, pseg_png_bound is %zu", k, png->cap[k], bound);
+    }
     PSEG_HIP(hipSetDevice(e.device));
     if (!e.chain) {
         auto* nc = new ChainState();
@@ -84,7 +94,7 @@ extern "C" int pseg_predict_chain(pseg_engine* h, const uint8_t* img, int H, int
     PSEG_TRY(censure(c, CB_LAB, npx));
     PSEG_TRY(censure(c, CB_LAB2, 2 * nla));          // resize target + bounding-box ping-pong
     if (need_bin) PSEG_TRY(censure(c, CB_BIN, nl));
-    if (want_masks) { PSEG_TRY(censure(c, CB_MASKS, 4 * nla * 3)); PSEG_TRY(censure(c, CB_LUT, (size_t)n_lut * 3)); }
+    if (want_masks) { if (!want_png) PSEG_TRY(censure(c, CB_MASKS, 4 * nla * 3)); PSEG_TRY(censure(c, CB_LUT, (size_t)n_lut * 3)); }
     if (labels) PSEG_TRY(censure(c, CB_I64, nl * 8));
     // every way out -- also an error return in the middle -- ends with both streams drained: copies from / to the caller's host
     // arrays must not be in flight when the caller gets its buffers back
@@ -124,7 +134,10 @@ extern "C" int pseg_predict_chain(pseg_engine* h, const uint8_t* img, int H, int
         chain_widen_kernel<<<(int)std::min<size_t>((nl + 255) / 256, 8192), 256, 0, st>>>(cur, (int64_t*)c.d_buf[CB_I64], nl);
         PSEG_HIP(hipMemcpyAsync(labels, c.d_buf[CB_I64], nl * 8, hipMemcpyDeviceToHost, st));
     }
-    if (want_masks) {
+    if (want_png) {
+        // the band kernel selects the masks' pixels itself: the RGB masks are never written; synchronises `st`
+        PSEG_TRY(pseg_masks_png_device_u8(e.device, cur, c.d_buf[CB_BIN], c.d_buf[CB_LUT], n_lut, Hl, Wl, 0, png->out, png->cap, png->n_bytes, st));
+    } else if (want_masks) {
         uint8_t* m = c.d_buf[CB_MASKS];
         uint8_t* dm[4] = {color ? m : nullptr, overlay ? m + nla * 3 : nullptr, inverted ? m + 2 * nla * 3 : nullptr, fg_color ? m + 3 * nla * 3 : nullptr};
         PSEG_TRY(pseg_masks_device_u8(e.device, cur, c.d_buf[CB_BIN], c.d_buf[CB_LUT], n_lut, Hl, Wl, dm[0], dm[1], dm[2], dm[3], st));
@@ -134,4 +147,20 @@ extern "C" int pseg_predict_chain(pseg_engine* h, const uint8_t* img, int H, int
     }
     PSEG_HIP(hipStreamSynchronize(c.s_aux));
     return engine_status(e, st);
+}
+
+extern "C" int pseg_predict_chain(pseg_engine* h, const uint8_t* img, int H, int W, int Ho, int Wo, const uint8_t* binary,
+                                  const int* post_ops, int n_post, unsigned flags, int64_t* labels, uint8_t* labels_u8,
+                                  const uint8_t* lut, int n_lut, uint8_t* color, uint8_t* overlay, uint8_t* inverted,
+                                  uint8_t* fg_color) {
+    return chain_run(h, img, H, W, Ho, Wo, binary, post_ops, n_post, flags, labels, labels_u8, lut, n_lut, color, overlay, inverted, fg_color, nullptr);
+}
+
+extern "C" int pseg_predict_chain_png(pseg_engine* h, const uint8_t* img, int H, int W, int Ho, int Wo, const uint8_t* binary,
+                                      const int* post_ops, int n_post, unsigned flags, int64_t* labels, uint8_t* labels_u8,
+                                      const uint8_t* lut, int n_lut, uint8_t* const png[4], const size_t cap[4], size_t n_bytes[4]) {
+    if (!png || !cap || !n_bytes) return fail(PSEG_EINVAL, "NULL argument");
+    for (int k = 0; k < 4; ++k) n_bytes[k] = 0;
+    const ChainPng req{png, cap, n_bytes};
+    return chain_run(h, img, H, W, Ho, Wo, binary, post_ops, n_post, flags, labels, labels_u8, lut, n_lut, nullptr, nullptr, nullptr, nullptr, &req);
 }

@@ -286,6 +286,7 @@ size_t bn_saved_bytes(int C);
 // Dropout mask of element i under `key`: keep iff hash(i, key) >= rate (inverted dropout, kept values * 1/(1-rate))
 void launch_dropout(float* x, size_t n, uint32_t key, float rate, hipStream_t st);
 int ccl_roots(const uint8_t* d_bin, int* d_L, int H, int W, int connectivity, hipStream_t st);   // pseg_post.hip
+void png_release_workspace(int dev);   // pseg_png.hip: the encoder's per-device workspace (pseg_release_workspace)
 int upload_weights(Engine& e);
 // one page through the engine's graph, device buffers, asynchronous on `st` (every output optional)
 int predict_device(Engine& e, const uint8_t* d_img, int H, int W, float* d_logits, float* d_probs, int64_t* d_labels,

@@ -1,0 +1,610 @@
+// pseg_png.hip -- PNG encoder whose pixels are in device memory (lib/output.py:20-41 writes the three masks with
+// PIL.Image.save; the reference has no device-side counterpart).  The output is a complete PNG byte stream:
+//
+//   signature | IHDR | IDAT(78 01) | IDAT(band 0) | IDAT(band 1) | ... | IDAT(01 00 00 FF FF, Adler-32) | IEND
+//
+// The image is cut into bands of R rows; one workgroup deflates one band, independently of every other, into its own slot
+// of the workspace.  A band is ONE fixed-Huffman block (BFINAL = 0) followed by an empty stored block (the zlib "sync
+// flush": 00 00 FF FF after the three header bits and the padding), so it ends on a byte and the bands concatenate into one
+// valid deflate stream; the last IDAT holds the final empty stored block and the Adler-32.  Three launches, ordered by the
+// stream -- no workgroup waits for another:
+//   1. png_band_kernel   bands -> slots, per band {bytes, Adler partial (sum, weighted sum)}
+//   2. png_frame_kernel  scan of the band sizes -> final offsets, the combined Adler-32, signature / IHDR / first and last
+//                        IDAT / IEND, the total size
+//   3. png_gather_kernel bands -> their final offsets with the chunk framing
+// The chunk CRCs run over the COMPRESSED bytes; the host fills them in on the downloaded stream (table-driven, slicing by 8).
+//
+// Inside a band: every scanline is filtered with Up (filter byte 2; the row above comes from the SOURCE, also for a band's
+// first row; the image's first row sees zeros).  The band's filtered bytes are walked in segments of 4096 bytes: 256 threads
+// x 16 bytes.  Matches are runs against the byte `channels` back (the pixel to the left; zeros of the Up filter match at any
+// distance), never reaching in front of the band's first byte; a run is cut at a segment start and into tokens of 258
+// with a remainder of >= 3 as a shorter match and 1 or 2 as literals.  Token bit lengths are prefix-summed over the workgroup,
+// the bits are ORed into an LDS bit buffer (deflate packs LSB first, Huffman codes go in bit-reversed) and whole 32-bit words
+// are streamed to the slot; the partial last word is carried into the next segment.  No match has a distance other than
+// `channels` (1 or 3), so deflate's 32 768-byte window is never a concern.
+#include <algorithm>
+#include <mutex>
+
+#include "pseg_common.h"
+
+namespace pseg {
+
+constexpr int PNG_T = 256;                    // threads of a band workgroup
+constexpr int PNG_BPT = 16;                   // filtered bytes per thread and segment
+constexpr int PNG_SEG = PNG_T * PNG_BPT;      // 4096
+constexpr int PNG_BITW = PNG_SEG * 9 / 32 + 8;   // words of the bit buffer: 31 carried bits + 9 bits per byte + 49 bits of band end
+constexpr unsigned ADLER_M = 65521u;
+constexpr size_t PNG_MAX_ROW = (size_t)1 << 30;  // filtered bytes of a row / of a band: in-band indices are ints
+constexpr size_t PNG_FIXED = 8 + 25 + 14 + 21 + 12;   // signature, IHDR, IDAT(78 01), IDAT(final block + Adler), IEND
+constexpr size_t PNG_HEAD = 8 + 25 + 14;
+
+struct PngBandMeta { unsigned bytes, a, b, pad; };    // compressed bytes; Adler partial: sum of bytes, sum of byte * (n - i), both mod 65521
+
+struct PngJob {
+    int H, W, C, R, nb, L;                    // L = C * W + 1 filtered bytes per row, nb = ceil(H / R) bands
+    size_t slot;                              // bytes between two bands' slots
+    uint8_t* slots[4];
+    PngBandMeta* meta[4];
+    unsigned long long* offs[4];              // final offset of every band's chunk
+    uint8_t* out[4];                          // the assembled stream
+    unsigned long long* total;                // [4] its size
+    int mask_id[4];
+};
+
+// ---- host arithmetic ------------------------------------------------------------------------------------------------
+static inline size_t png_band_bound(size_t n) { return n + n / 8 + 8; }   // header 3 + 9 n + end-of-block 7 + stored header 3 bits, padded, + 4
+static int png_rows(int H, int W, int C, int band_rows) {
+    const size_t L = (size_t)W * C + 1;
+    size_t r = band_rows > 0 ? (size_t)band_rows : std::max<size_t>(1, 16384 / L);
+    r = std::min(r, (size_t)H);
+    r = std::min(r, std::max<size_t>(1, PNG_MAX_ROW / L));
+    return (int)r;
+}
+static bool png_shape_ok(int H, int W, int C) { return H >= 1 && W >= 1 && (C == 1 || C == 3) && (size_t)W * C + 1 <= PNG_MAX_ROW; }
+static size_t png_bound(int H, int W, int C, int band_rows) {
+    if (!png_shape_ok(H, W, C) || band_rows < 0) return 0;
+    const size_t L = (size_t)W * C + 1, R = png_rows(H, W, C, band_rows);
+    const size_t nfull = (size_t)H / R, rem = (size_t)H % R;
+    size_t t = PNG_FIXED + nfull * (12 + png_band_bound(R * L));
+    if (rem) t += 12 + png_band_bound(rem * L);
+    return t;
+}
+
+// ---- fixed Huffman codes (RFC 1951 3.2.6), already bit-reversed for LSB-first packing -----------------------------------
+__device__ __forceinline__ void png_lit(unsigned v, unsigned& code, int& nb) {
+    if (v < 144) { nb = 8; code = __brev(0x30u + v) >> 24; }
+    else { nb = 9; code = __brev(0x190u + (v - 144)) >> 23; }
+}
+// match of `len` (3..258) at distance D (1 or 3): length symbol + extra bits + 5-bit distance code (no extra bits)
+__device__ __forceinline__ void png_match(int len, int D, unsigned& code, int& nb) {
+    int sym, eb = 0;
+    unsigned extra = 0;
+    if (len == 258) sym = 285;
+    else {
+        const int l = len - 3;
+        if (l < 8) sym = 257 + l;
+        else {
+            const int n = 31 - __clz(l);
+            eb = n - 2;
+            sym = 261 + 4 * eb + ((l - (1 << n)) >> eb);
+            extra = (unsigned)(l - (1 << n)) & ((1u << eb) - 1);
+        }
+    }
+    unsigned c;
+    int cb;
+    if (sym < 280) { cb = 7; c = __brev((unsigned)(sym - 256)) >> 25; }
+    else { cb = 8; c = __brev(0xC0u + (unsigned)(sym - 280)) >> 24; }
+    const unsigned dist = D == 1 ? 0u : 8u;               // distance code 0 (00000) / 2 (00010 -> reversed 01000)
+    code = c | (extra << cb) | (dist << (cb + eb));
+    nb = cb + eb + 5;
+}
+
+// ---- workgroup scans over one int per thread (four waves of 64) -------------------------------------------------------------
+__device__ __forceinline__ int png_scan_max_before(int v, int* sh) {      // max over the threads in front, -1 if none
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int x = v;
+    for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(x, d, 64); if (lane >= d) x = max(x, o); }
+    if (lane == 63) sh[w] = x;
+    __syncthreads();
+    int ex = __shfl_up(x, 1, 64);
+    if (lane == 0) ex = -1;
+    for (int k = 0; k < w; ++k) ex = max(ex, sh[k]);
+    __syncthreads();
+    return ex;
+}
+__device__ __forceinline__ int png_scan_min_after(int v, int none, int* sh) {   // min over the threads behind, `none` if none
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int x = v;
+    for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_down(x, d, 64); if (lane + d < 64) x = min(x, o); }
+    if (lane == 0) sh[w] = x;
+    __syncthreads();
+    int ex = __shfl_down(x, 1, 64);
+    if (lane == 63) ex = none;
+    for (int k = w + 1; k < PNG_T / 64; ++k) ex = min(ex, sh[k]);
+    __syncthreads();
+    return ex;
+}
+__device__ __forceinline__ int png_scan_sum_before(int v, int* sh, int& total) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int x = v;
+    for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(x, d, 64); if (lane >= d) x += o; }
+    if (lane == 63) sh[w] = x;
+    __syncthreads();
+    int ex = x - v;
+    total = 0;
+    for (int k = 0; k < PNG_T / 64; ++k) { if (k < w) ex += sh[k]; total += sh[k]; }
+    __syncthreads();
+    return ex;
+}
+
+// ---- pixel sources: one pixel as 0x00BBGGRR (gray: the low byte) ------------------------------------------------------------
+struct PngSrcPlain {                          // interleaved 8-bit buffer, 1 or 3 channels
+    static constexpr bool LUT = false;
+    const uint8_t* p;
+    int W, C;
+    __device__ __forceinline__ uint32_t px(int row, int x, int, const uint32_t*) const {
+        const uint8_t* q = p + ((size_t)row * W + x) * C;
+        return C == 1 ? (uint32_t)q[0] : ((uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16));
+    }
+};
+struct PngSrcMasks {                          // generate_output_masks (lib/output.py:44-60) on the fly: masks_kernel's selection
+    static constexpr bool LUT = true;
+    const uint8_t* pred;
+    const uint8_t* bin;
+    const uint8_t* lut;
+    int n_lut, W;
+    __device__ __forceinline__ uint32_t px(int row, int x, int mask, const uint32_t* slut) const {
+        const size_t p = (size_t)row * W + x;
+        const uint32_t rgb = slut[pred[p]];
+        const unsigned b = bin[p];
+        switch (mask) {
+            case 0: return rgb;
+            case 1: return b == 1 ? 0u : rgb;
+            case 2: return b == 0 ? 0u : rgb;
+            default: return b != 1 ? 0u : rgb;
+        }
+    }
+};
+
+// The tokens of one thread's 16 bytes: emit(code, nbits) in stream order.  eqm: bit j set = byte j continues a run; pl: last
+// run break in front of the chunk (segment position, -1: none); nf: first break behind it (slen: none).
+template <class F>
+__device__ __forceinline__ void png_walk(const uint32_t (&w4)[4], int cnt, unsigned eqm, int p0, int pl, int nf, int D, F emit) {
+    const unsigned brk = ~eqm & ((1u << cnt) - 1u);
+    int last_break = pl;
+    for (int j = 0; j < cnt; ++j) {
+        const unsigned v = (w4[j >> 2] >> (8 * (j & 3))) & 255u;
+        const int p = p0 + j;
+        unsigned code;
+        int nb;
+        if (!((eqm >> j) & 1u)) {
+            last_break = p;
+            png_lit(v, code, nb);
+            emit(code, nb);
+            continue;
+        }
+        const unsigned behind = j + 1 < 32 ? brk >> (j + 1) : 0u;
+        const int e = behind ? p + 1 + (__ffs(behind) - 1) : nf;
+        const int s = last_break + 1;
+        const int k = p - s, q = k - k % 258;
+        const int c = min(258, (e - s) - q);
+        if (c < 3) { png_lit(v, code, nb); emit(code, nb); }
+        else if (k == q) { png_match(c, D, code, nb); emit(code, nb); }
+    }
+}
+
+template <class SRC>
+__global__ __launch_bounds__(PNG_T) void png_band_kernel(SRC src, PngJob J) {
+    __shared__ __attribute__((aligned(16))) uint8_t s_in[16 + PNG_SEG];   // [13..15]: the three bytes in front of the segment
+    __shared__ uint32_t s_bits[PNG_BITW];
+    __shared__ int s_w[4];
+    __shared__ unsigned s_ad[2];
+    __shared__ uint32_t s_lut[256];
+    const int t = threadIdx.x, band = blockIdx.x, o = blockIdx.y, mask = J.mask_id[o];
+    if constexpr (SRC::LUT) {
+        s_lut[t] = t < src.n_lut ? (uint32_t)src.lut[t * 3] | ((uint32_t)src.lut[t * 3 + 1] << 8) | ((uint32_t)src.lut[t * 3 + 2] << 16) : 0u;
+    }
+    __syncthreads();
+    const int row0 = band * J.R, rows = min(J.R, J.H - row0);
+    const int L = J.L, D = J.C;
+    const int n = rows * L;                                   // <= 2^30 (png_rows)
+    uint32_t* const out = (uint32_t*)(J.slots[o] + (size_t)band * J.slot);
+    unsigned out_w = 0;                                       // words of the slot written so far
+    uint32_t carry_word = 2u;                                 // block header: BFINAL = 0, BTYPE = 01 (fixed Huffman), LSB first
+    int carry_bits = 3;
+    unsigned adA = 0, adB = 0;
+    const int nseg = (n + PNG_SEG - 1) / PNG_SEG;
+    for (int sg = 0; sg < nseg; ++sg) {
+        const int base = sg * PNG_SEG, slen = min(PNG_SEG, n - base);
+        const bool last = sg == nseg - 1;
+        // 1. the filtered bytes of this thread's chunk; the bit buffer starts as the carried partial word
+        for (int k = t; k < PNG_BITW; k += PNG_T) s_bits[k] = k == 0 ? carry_word : 0u;
+        if (t == 0) { s_ad[0] = 0; s_ad[1] = 0; }
+        const int p0 = t * PNG_BPT;
+        const int cnt = min(PNG_BPT, max(0, slen - p0));
+        uint32_t w4[4] = {0u, 0u, 0u, 0u};
+        unsigned a_sum = 0, b_sum = 0;
+        if (cnt > 0) {
+            const int i0 = base + p0;
+            int r = i0 / L, c = i0 - r * L;
+            int grow = row0 + r, x = 0, ch = 0;
+            if (c > 0) { x = (c - 1) / D; ch = (c - 1) - x * D; }
+            bool need = true;
+            uint32_t cur = 0, up = 0;
+            for (int j = 0; j < cnt; ++j) {
+                uint32_t v;
+                if (c == 0) { v = 2u; x = 0; ch = 0; need = true; }          // filter type: Up
+                else {
+                    if (need) {
+                        cur = src.px(grow, x, mask, s_lut);
+                        up = grow > 0 ? src.px(grow - 1, x, mask, s_lut) : 0u;
+                        need = false;
+                    }
+                    v = ((cur >> (8 * ch)) - (up >> (8 * ch))) & 255u;
+                    if (++ch == D) { ch = 0; ++x; need = true; }
+                }
+                w4[j >> 2] |= v << (8 * (j & 3));
+                a_sum += v;
+                b_sum += v * (unsigned)(cnt - j);
+                if (++c == L) { c = 0; ++grow; }
+            }
+        }
+        *(uint4*)(s_in + 16 + p0) = make_uint4(w4[0], w4[1], w4[2], w4[3]);
+        __syncthreads();
+        // 2. Adler partial of the segment; run flags: byte == the byte D in front of it (none in front of the band or the segment)
+        if (cnt > 0) {
+            const unsigned after = (unsigned)(slen - (p0 + cnt));
+            atomicAdd(&s_ad[0], a_sum);
+            atomicAdd(&s_ad[1], (b_sum + a_sum * after) % ADLER_M);
+        }
+        unsigned eqm = 0;
+        for (int j = 0; j < cnt; ++j) {
+            const int p = p0 + j;
+            if (base + p >= D && s_in[16 + p] == s_in[16 + p - D]) eqm |= 1u << j;
+        }
+        const unsigned brk = ~eqm & ((1u << cnt) - 1u);
+        const int lb = brk ? p0 + (31 - __clz(brk)) : -1;
+        const int fb = brk ? p0 + (__ffs(brk) - 1) : slen;
+        const int pl = png_scan_max_before(lb, s_w);
+        const int nf = png_scan_min_after(fb, slen, s_w);
+        // 3. bit lengths -> bit offsets
+        int bits = 0;
+        png_walk(w4, cnt, eqm, p0, pl, nf, D, [&](unsigned, int nb) { bits += nb; });
+        int seg_bits = 0;
+        int off = carry_bits + png_scan_sum_before(bits, s_w, seg_bits);
+        // 4. pack
+        png_walk(w4, cnt, eqm, p0, pl, nf, D, [&](unsigned code, int nb) {
+            const unsigned long long v = (unsigned long long)code << (off & 31);
+            atomicOr(&s_bits[off >> 5], (uint32_t)v);
+            if (v >> 32) atomicOr(&s_bits[(off >> 5) + 1], (uint32_t)(v >> 32));
+            off += nb;
+        });
+        int T = carry_bits + seg_bits;
+        if (last) {
+            T += 7 + 3;                       // end-of-block (0000000), then an empty stored block: BFINAL = 0, BTYPE = 00
+            T = (T + 7) & ~7;                 // ... padded to a byte, LEN = 0000, NLEN = FFFF
+            if (t == 0) {
+                const int f = T + 16;
+                const unsigned long long v = 0xFFFFull << (f & 31);
+                atomicOr(&s_bits[f >> 5], (uint32_t)v);
+                if (v >> 32) atomicOr(&s_bits[(f >> 5) + 1], (uint32_t)(v >> 32));
+            }
+            T += 32;
+        }
+        __syncthreads();
+        // 5. whole words to the slot; the partial word and the Adler sums are carried
+        const int nW = last ? (T + 31) >> 5 : T >> 5;
+        for (int k = t; k < nW; k += PNG_T) out[out_w + k] = s_bits[k];
+        carry_word = s_bits[T >> 5];
+        carry_bits = T & 31;
+        {
+            const unsigned A2 = s_ad[0] % ADLER_M, B2 = s_ad[1] % ADLER_M;
+            adB = (adB + (unsigned)slen * adA + B2) % ADLER_M;      // 4096 * 65520 + 2 * 65520 < 2^32
+            adA = (adA + A2) % ADLER_M;
+        }
+        if (last) {
+            if (t == 0) {
+                PngBandMeta m;
+                m.bytes = out_w * 4u + (unsigned)(T >> 3);
+                m.a = adA; m.b = adB; m.pad = 0;
+                J.meta[o][band] = m;
+            }
+        } else {
+            out_w += (unsigned)nW;
+            if (t < 3) {
+                const uint8_t v = s_in[16 + PNG_SEG - 3 + t];
+                s_in[13 + t] = v;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+__device__ __forceinline__ void png_be32(uint8_t* p, uint32_t v) { p[0] = v >> 24; p[1] = v >> 16; p[2] = v >> 8; p[3] = v; }
+
+// One workgroup per output: band sizes -> final offsets; Adler-32 of the whole filtered image; everything but the IDAT bands.
+__global__ __launch_bounds__(PNG_T) void png_frame_kernel(PngJob J) {
+    __shared__ unsigned long long s_tot[PNG_T];
+    __shared__ unsigned long long s_a, s_b;
+    const int t = threadIdx.x, o = blockIdx.x;
+    const PngBandMeta* meta = J.meta[o];
+    const int per = (J.nb + PNG_T - 1) / PNG_T;
+    const int b0 = min(J.nb, t * per), b1 = min(J.nb, b0 + per);
+    if (t == 0) { s_a = 0; s_b = 0; }
+    unsigned long long sum = 0;
+    for (int b = b0; b < b1; ++b) sum += (unsigned long long)meta[b].bytes + 12u;
+    s_tot[t] = sum;
+    __syncthreads();
+    if (t == 0) {
+        unsigned long long run = PNG_HEAD;
+        for (int k = 0; k < PNG_T; ++k) { const unsigned long long v = s_tot[k]; s_tot[k] = run; run += v; }
+    }
+    __syncthreads();
+    const unsigned long long ntotal = (unsigned long long)J.H * (unsigned long long)J.L;
+    unsigned long long off = s_tot[t], a = 0, bsum = 0;
+    for (int b = b0; b < b1; ++b) {
+        J.offs[o][b] = off;
+        off += (unsigned long long)meta[b].bytes + 12u;
+        const unsigned long long end = (unsigned long long)min((long long)(b + 1) * J.R, (long long)J.H) * (unsigned long long)J.L;
+        const unsigned long long after = (ntotal - end) % ADLER_M;           // the "length mod 65521" of the combine
+        a += meta[b].a;
+        bsum += ((unsigned long long)meta[b].b + (unsigned long long)meta[b].a * after) % ADLER_M;
+    }
+    atomicAdd(&s_a, a);
+    atomicAdd(&s_b, bsum);
+    __syncthreads();
+    if (t == PNG_T - 1) {
+        const unsigned long long end = off;                   // behind the last band's chunk (the threads behind the last band hold it too)
+        const uint32_t s1 = (uint32_t)((1u + s_a % ADLER_M) % ADLER_M);
+        const uint32_t s2 = (uint32_t)((ntotal % ADLER_M + s_b % ADLER_M) % ADLER_M);
+        uint8_t* p = J.out[o];
+        const uint8_t sig[8] = {0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A};
+        for (int k = 0; k < 8; ++k) p[k] = sig[k];
+        png_be32(p + 8, 13);
+        p[12] = 'I'; p[13] = 'H'; p[14] = 'D'; p[15] = 'R';
+        png_be32(p + 16, (uint32_t)J.W);
+        png_be32(p + 20, (uint32_t)J.H);
+        p[24] = 8; p[25] = J.C == 3 ? 2 : 0; p[26] = 0; p[27] = 0; p[28] = 0;
+        png_be32(p + 29, 0);                                  // CRCs: the host fills them in
+        png_be32(p + 33, 2);
+        p[37] = 'I'; p[38] = 'D'; p[39] = 'A'; p[40] = 'T';
+        p[41] = 0x78; p[42] = 0x01;                           // zlib header: deflate, 32 KiB window, fastest
+        png_be32(p + 43, 0);
+        uint8_t* q = p + end;
+        png_be32(q, 9);
+        q[4] = 'I'; q[5] = 'D'; q[6] = 'A'; q[7] = 'T';
+        q[8] = 0x01; q[9] = 0; q[10] = 0; q[11] = 0xFF; q[12] = 0xFF;     // final empty stored block
+        png_be32(q + 13, (s2 << 16) | s1);
+        png_be32(q + 17, 0);
+        png_be32(q + 21, 0);
+        q[25] = 'I'; q[26] = 'E'; q[27] = 'N'; q[28] = 'D';
+        png_be32(q + 29, 0);
+        J.total[o] = end + 21 + 12;
+    }
+}
+
+__global__ __launch_bounds__(PNG_T) void png_gather_kernel(PngJob J) {
+    const int t = threadIdx.x, band = blockIdx.x, o = blockIdx.y;
+    const unsigned sz = J.meta[o][band].bytes;
+    const uint8_t* src = J.slots[o] + (size_t)band * J.slot;
+    uint8_t* dst = J.out[o] + J.offs[o][band];
+    if (t == 0) { png_be32(dst, sz); dst[4] = 'I'; dst[5] = 'D'; dst[6] = 'A'; dst[7] = 'T'; png_be32(dst + 8 + sz, 0); }
+    for (unsigned k = t; k < sz; k += PNG_T) dst[8 + k] = src[k];
+}
+
+// ---- CRC-32 (host, over the downloaded stream) ------------------------------------------------------------------------------
+static uint32_t g_crc_tab[8][256];
+static std::once_flag g_crc_once;
+static void crc_init() {
+    for (uint32_t i = 0; i < 256; ++i) {
+        uint32_t c = i;
+        for (int k = 0; k < 8; ++k) c = (c & 1) ? 0xEDB88320u ^ (c >> 1) : c >> 1;
+        g_crc_tab[0][i] = c;
+    }
+    for (uint32_t i = 0; i < 256; ++i)
+        for (int s = 1; s < 8; ++s) g_crc_tab[s][i] = (g_crc_tab[s - 1][i] >> 8) ^ g_crc_tab[0][g_crc_tab[s - 1][i] & 255];
+}
+static uint32_t crc32_of(const uint8_t* p, size_t n) {
+    std::call_once(g_crc_once, crc_init);
+    uint32_t c = 0xFFFFFFFFu;
+    while (n >= 8) {
+        const uint32_t lo = ((uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24)) ^ c;
+        c = g_crc_tab[7][lo & 255] ^ g_crc_tab[6][(lo >> 8) & 255] ^ g_crc_tab[5][(lo >> 16) & 255] ^ g_crc_tab[4][lo >> 24] ^
+            g_crc_tab[3][p[4]] ^ g_crc_tab[2][p[5]] ^ g_crc_tab[1][p[6]] ^ g_crc_tab[0][p[7]];
+        p += 8;
+        n -= 8;
+    }
+    while (n--) c = g_crc_tab[0][(c ^ *p++) & 255] ^ (c >> 8);
+    return c ^ 0xFFFFFFFFu;
+}
+static int png_fill_crcs(uint8_t* png, size_t total) {
+    size_t pos = 8;
+    while (pos < total) {
+        if (pos + 12 > total) return fail(PSEG_EHIP, "png: chunk framing runs past the stream");
+        const size_t len = ((size_t)png[pos] << 24) | ((size_t)png[pos + 1] << 16) | ((size_t)png[pos + 2] << 8) | png[pos + 3];
+        if (pos + 12 + len > total) return fail(PSEG_EHIP, "png: chunk framing runs past the stream");
+        const uint32_t c = crc32_of(png + pos + 4, 4 + len);
+        uint8_t* q = png + pos + 8 + len;
+        q[0] = c >> 24; q[1] = c >> 16; q[2] = c >> 8; q[3] = c;
+        pos += 12 + len;
+    }
+    return PSEG_OK;
+}
+
+// ---- workspace: grow-only, one per device (band slots, band tables, the assembled streams); a call holds the device's lock to
+// its end and ends synchronised, so one call at a time uses it.  pseg_release_workspace frees it. -------------------------------
+struct PngWs { void* p = nullptr; size_t bytes = 0; };
+static std::mutex g_png_mu[64];
+static PngWs g_png_ws[64];
+
+void png_release_workspace(int dev) {
+    std::lock_guard<std::mutex> lk(g_png_mu[dev & 63]);
+    PngWs& w = g_png_ws[dev & 63];
+    if (w.p) (void)hipFree(w.p);
+    w.p = nullptr;
+    w.bytes = 0;
+}
+
+static inline size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// Encodes `nout` images of one shape from `src` (output k = mask mask_id[k]) into host[k]; synchronises `st`.
+template <class SRC>
+static int png_run(int device, const SRC& src, int H, int W, int C, int band_rows, int nout, uint8_t* const host[4],
+                   size_t* const nbytes[4], const int mask_id[4], hipStream_t st) {
+    const size_t bound = png_bound(H, W, C, band_rows);
+    PngJob J;
+    J.H = H; J.W = W; J.C = C; J.R = png_rows(H, W, C, band_rows);
+    J.nb = (int)(((size_t)H + J.R - 1) / J.R);
+    J.L = W * C + 1;
+    J.slot = (png_band_bound((size_t)J.R * J.L) + 3) & ~(size_t)3;
+    const size_t slots_b = al256((size_t)J.nb * J.slot), meta_b = al256((size_t)J.nb * sizeof(PngBandMeta)), offs_b = al256((size_t)J.nb * 8),
+                 out_b = al256(bound + 32);
+    const size_t per = slots_b + meta_b + offs_b + out_b, need = 256 + (size_t)nout * per;
+    std::lock_guard<std::mutex> lk(g_png_mu[device & 63]);
+    PngWs& w = g_png_ws[device & 63];
+    if (w.bytes < need) {
+        if (w.p) (void)hipFree(w.p);
+        w.p = nullptr;
+        w.bytes = 0;
+        if (hipMalloc(&w.p, need) != hipSuccess) {
+            w.p = nullptr;
+            (void)hipGetLastError();
+            return fail(PSEG_ENOMEM, "hipMalloc(png workspace, %zu bytes) failed", need);
+        }
+        w.bytes = need;
+    }
+    uint8_t* base = (uint8_t*)w.p;
+    J.total = (unsigned long long*)base;
+    for (int k = 0; k < 4; ++k) {
+        uint8_t* q = base + 256 + (size_t)std::min(k, nout - 1) * per;
+        J.slots[k] = q;
+        J.meta[k] = (PngBandMeta*)(q + slots_b);
+        J.offs[k] = (unsigned long long*)(q + slots_b + meta_b);
+        J.out[k] = q + slots_b + meta_b + offs_b;
+        J.mask_id[k] = mask_id[std::min(k, nout - 1)];
+    }
+    png_band_kernel<SRC><<<dim3(J.nb, nout), PNG_T, 0, st>>>(src, J);
+    png_frame_kernel<<<nout, PNG_T, 0, st>>>(J);
+    png_gather_kernel<<<dim3(J.nb, nout), PNG_T, 0, st>>>(J);
+    PSEG_HIP(hipGetLastError());
+    unsigned long long total[4] = {0, 0, 0, 0};
+    PSEG_HIP(hipMemcpyAsync(total, J.total, sizeof(total), hipMemcpyDeviceToHost, st));
+    PSEG_HIP(hipStreamSynchronize(st));
+    for (int k = 0; k < nout; ++k)
+        if (total[k] < PNG_FIXED || total[k] > bound) return fail(PSEG_EHIP, "png: encoded size %llu outside (0, bound %zu]", total[k], bound);
+    for (int k = 0; k < nout; ++k) PSEG_HIP(hipMemcpyAsync(host[k], J.out[k], (size_t)total[k], hipMemcpyDeviceToHost, st));
+    PSEG_HIP(hipStreamSynchronize(st));
+    for (int k = 0; k < nout; ++k) {
+        PSEG_TRY(png_fill_crcs(host[k], (size_t)total[k]));
+        *nbytes[k] = (size_t)total[k];
+    }
+    return PSEG_OK;
+}
+
+static int png_set_dev(int device) {
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n == 0)
+        return fail(PSEG_EHIP, "no HIP device visible: libpseg has no CPU fallback");
+    if (device < 0 || device >= n) return fail(PSEG_EINVAL, "device %d of %d", device, n);
+    PSEG_HIP(hipSetDevice(device));
+    return PSEG_OK;
+}
+
+static int png_check(int H, int W, int channels, int band_rows) {
+    if (H < 1 || W < 1) return fail(PSEG_EINVAL, "png: image of %d x %d pixels", H, W);
+    if (channels != 1 && channels != 3) return fail(PSEG_EINVAL, "png: %d channels (1 = gray or 3 = RGB)", channels);
+    if (band_rows < 0) return fail(PSEG_EINVAL, "png: band_rows %d (0 = default)", band_rows);
+    if (!png_shape_ok(H, W, channels)) return fail(PSEG_EINVAL, "png: a row of %d pixels is too long", W);
+    return PSEG_OK;
+}
+
+}  // namespace pseg
+
+using namespace pseg;
+
+extern "C" {
+
+size_t pseg_png_bound(int H, int W, int channels, int band_rows) { return png_bound(H, W, channels, band_rows); }
+
+int pseg_png_encode_device(int device, const uint8_t* d_src, int H, int W, int channels, int band_rows, uint8_t* out, size_t cap,
+                           size_t* n_bytes, void* stream) {
+    if (!d_src || !out || !n_bytes) return fail(PSEG_EINVAL, "NULL argument");
+    PSEG_TRY(png_check(H, W, channels, band_rows));
+    if (cap < png_bound(H, W, channels, band_rows))
+        return fail(PSEG_EINVAL, "png: output buffer of %zu bytes, pseg_png_bound is %zu", cap, png_bound(H, W, channels, band_rows));
+    PSEG_TRY(png_set_dev(device));
+    PngSrcPlain src{d_src, W, channels};
+    uint8_t* const host[4] = {out, nullptr, nullptr, nullptr};
+    size_t* const nb[4] = {n_bytes, nullptr, nullptr, nullptr};
+    const int ids[4] = {0, 0, 0, 0};
+    return png_run(device, src, H, W, channels, band_rows, 1, host, nb, ids, (hipStream_t)stream);
+}
+
+int pseg_masks_png_device_u8(int device, const uint8_t* d_pred, const uint8_t* d_binary, const uint8_t* d_lut, int n_lut, int H, int W,
+                             int band_rows, uint8_t* const out[4], const size_t cap[4], size_t n_bytes[4], void* stream) {
+    if (!d_pred || !d_binary || !d_lut || !out || !cap || !n_bytes) return fail(PSEG_EINVAL, "NULL argument");
+    if (n_lut < 1 || n_lut > 256) return fail(PSEG_EINVAL, "n_lut %d out of range (1..256)", n_lut);
+    PSEG_TRY(png_check(H, W, 3, band_rows));
+    const size_t bound = png_bound(H, W, 3, band_rows);
+    uint8_t* host[4] = {nullptr, nullptr, nullptr, nullptr};
+    size_t* nb[4] = {nullptr, nullptr, nullptr, nullptr};
+    int ids[4] = {0, 0, 0, 0}, nout = 0;
+    for (int k = 0; k < 4; ++k) {
+        n_bytes[k] = 0;
+        if (!out[k]) continue;
+        if (cap[k] < bound) return fail(PSEG_EINVAL, "png: output buffer %d of %zu bytes, pseg_png_bound is %zu", k, cap[k], bound);
+        host[nout] = out[k]; nb[nout] = &n_bytes[k]; ids[nout] = k;
+        ++nout;
+    }
+    if (nout == 0) return PSEG_OK;
+    PSEG_TRY(png_set_dev(device));
+    PngSrcMasks src{d_pred, d_binary, d_lut, n_lut, W};
+    return png_run(device, src, H, W, 3, band_rows, nout, host, nb, ids, (hipStream_t)stream);
+}
+
+int pseg_png_encode(int device, const uint8_t* src, int H, int W, int channels, int band_rows, uint8_t* out, size_t cap, size_t* n_bytes) {
+    if (!src || !out || !n_bytes) return fail(PSEG_EINVAL, "NULL argument");
+    PSEG_TRY(png_check(H, W, channels, band_rows));
+    if (cap < png_bound(H, W, channels, band_rows))
+        return fail(PSEG_EINVAL, "png: output buffer of %zu bytes, pseg_png_bound is %zu", cap, png_bound(H, W, channels, band_rows));
+    PSEG_TRY(png_set_dev(device));
+    const size_t n = (size_t)H * W * channels;
+    uint8_t* d = nullptr;
+    if (hipMalloc((void**)&d, n) != hipSuccess) { (void)hipGetLastError(); return fail(PSEG_ENOMEM, "hipMalloc failed in png_encode"); }
+    int rc = PSEG_OK;
+    if (hipMemcpy(d, src, n, hipMemcpyHostToDevice) != hipSuccess) rc = fail(PSEG_EHIP, "H2D copy failed");
+    if (rc == PSEG_OK) rc = pseg_png_encode_device(device, d, H, W, channels, band_rows, out, cap, n_bytes, nullptr);
+    (void)hipFree(d);
+    return rc;
+}
+
+int pseg_masks_png(int device, const int64_t* pred, const uint8_t* binary, const uint8_t* lut, int n_lut, int H, int W, int band_rows,
+                   uint8_t* const out[4], const size_t cap[4], size_t n_bytes[4]) {
+    if (!pred || !binary || !lut || !out || !cap || !n_bytes) return fail(PSEG_EINVAL, "NULL argument");
+    if (n_lut < 1 || n_lut > 256) return fail(PSEG_EINVAL, "n_lut %d out of range (1..256)", n_lut);
+    PSEG_TRY(png_check(H, W, 3, band_rows));
+    PSEG_TRY(png_set_dev(device));
+    const size_t n = (size_t)H * W;
+    // labels outside the colour table are black (masks_kernel): on the uint8 map they become 255, which is black while the table
+    // has fewer than 256 entries
+    std::vector<uint8_t> lab(n);
+    bool outside = false;
+    for (size_t i = 0; i < n; ++i) {
+        const int64_t l = pred[i];
+        if (l >= 0 && l < n_lut) lab[i] = (uint8_t)l;
+        else { lab[i] = 255; outside = true; }
+    }
+    if (outside && n_lut == 256) return fail(PSEG_EINVAL, "png: labels outside a 256-entry colour table");
+    uint8_t* d = nullptr;
+    const size_t off_bin = (n + 255) & ~(size_t)255, off_lut = off_bin + ((n + 255) & ~(size_t)255);
+    if (hipMalloc((void**)&d, off_lut + 768) != hipSuccess) { (void)hipGetLastError(); return fail(PSEG_ENOMEM, "hipMalloc failed in masks_png"); }
+    int rc = PSEG_OK;
+    if (hipMemcpy(d, lab.data(), n, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d + off_bin, binary, n, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d + off_lut, lut, (size_t)n_lut * 3, hipMemcpyHostToDevice) != hipSuccess)
+        rc = fail(PSEG_EHIP, "H2D copy failed");
+    if (rc == PSEG_OK) rc = pseg_masks_png_device_u8(device, d, d + off_bin, d + off_lut, n_lut, H, W, band_rows, out, cap, n_bytes, nullptr);
+    (void)hipFree(d);
+    return rc;
+}
+
+}  // extern "C"

@@ -1117,6 +1117,7 @@ int pseg_cc_vote_device_u8(int device, uint8_t* d_pred, const uint8_t* d_binary,
 
 int pseg_release_workspace(int device) {
     PSEG_TRY(set_dev(device));
+    png_release_workspace(device);
     return release_workspace(device);
 }
 

@@ -25,12 +25,13 @@ def generate_output_masks(data: SingleData, pred: np.ndarray, color_map: ColorMa
     return Masks(color=color, overlay=overlay, inverted_overlay=inverted, fg_color_mask=fg)
 
 
-def output_data(output_dir, pred, data: SingleData, color_map):
-    """lib/output.py:20-41: PNG writing stays host-side."""
-    from PIL import Image
-    if pred.ndim == 3:
-        assert pred.shape[0] == 1
-        pred = pred[0]
+#: write ".png" targets with the device encoder (pseg_masks_png); False: PIL writes every file, as the reference does
+DEVICE_PNG = True
+
+
+def output_paths(output_dir, data: SingleData):
+    """The three files output_data writes for this page (lib/output.py:20-38), their directories created:
+    (color, overlay, inverted)."""
     if data.output_path:
         filename = data.output_path
         d = os.path.dirname(filename)
@@ -41,10 +42,36 @@ def output_data(output_dir, pred, data: SingleData, color_map):
                 os.makedirs(os.path.join(output_dir, category, d), exist_ok=True)
     else:
         filename = os.path.basename(data.image_path)
+    return tuple(os.path.join(output_dir, category, filename) for category in ("color", "overlay", "inverted"))
+
+
+def is_png_target(path):
+    """PIL picks the file format from the extension; the device encoder writes PNG only."""
+    return str(path).lower().endswith(".png")
+
+
+def write_png_streams(paths, streams):
+    for path, stream in zip(paths, streams):
+        with open(path, "wb") as f:
+            f.write(stream)
+
+
+def output_data(output_dir, pred, data: SingleData, color_map):
+    """lib/output.py:20-41.  A ".png" target (any letter case) is encoded on the device straight from the label map
+    (engine.masks_png: the RGB masks never exist); every other extension, and DEVICE_PNG = False, goes through PIL."""
+    if pred.ndim == 3:
+        assert pred.shape[0] == 1
+        pred = pred[0]
+    paths = output_paths(output_dir, data)
+    if DEVICE_PNG and is_png_target(paths[0]):
+        png = engine.masks_png(pred, np.asarray(data.binary).astype(np.uint8), color_map.lut())
+        write_png_streams(paths, (png["color"], png["overlay"], png["inverted"]))
+        return
+    from PIL import Image
     masks = generate_output_masks(data, pred, color_map)
-    Image.fromarray(masks.color).save(os.path.join(output_dir, "color", filename))
-    Image.fromarray(masks.overlay).save(os.path.join(output_dir, "overlay", filename))
-    Image.fromarray(masks.inverted_overlay).save(os.path.join(output_dir, "inverted", filename))
+    Image.fromarray(masks.color).save(paths[0])
+    Image.fromarray(masks.overlay).save(paths[1])
+    Image.fromarray(masks.inverted_overlay).save(paths[2])
 
 
 def scale_to_original_shape(data: SingleData, pred):

@@ -65,7 +65,7 @@ class Predictor:
         img = gray_to_rgb(image) if getattr(net, "_rgb", False) else image
         res = net.model.predict_chain(img, binary=np.asarray(binary).astype(np.uint8) if need_bin else None, out_shape=out_shape,
                                       post_ops=ops, exact_labels=net.exact == "labels", labels=None if want_masks else "u8",
-                                      lut=self.settings.color_map.lut() if want_masks else None, masks=want_masks)
+                                      lut=self.settings.color_map.lut() if want_masks else None, masks=want_masks)  # True or "png"
         return page, res["labels"], res["masks"]
 
     def _labels(self, data: SingleData):
@@ -120,3 +120,30 @@ class Predictor:
             return Masks(color=color, overlay=overlay, inverted_overlay=inverted, fg_color_mask=fg)
         data, _, pred = self._labels(data)
         return generate_output_masks(data, pred, self.settings.color_map)
+
+    def write_masks(self, data: SingleData, output_dir=None):
+        """predict_masks + output_data (lib/predictor.py:49-54, lib/output.py:20-41) for ".png" targets as ONE device call:
+        predict -> [rescale] -> post-processors -> masks -> PNG (pseg_predict_chain_png); only the three PNG streams come
+        down, and they are written to color/, overlay/ and inverted/ under output_dir (default: settings.output) with
+        output_data's names.  Other extensions, output.DEVICE_PNG = False and pages that need the host chain go through
+        predict_masks' stages and output_data.  Returns the three paths."""
+        from . import output
+        output_dir = output_dir if output_dir is not None else self.settings.output
+        if output_dir is None:
+            raise Exception("write_masks needs an output directory")
+        for sub in ("color", "overlay", "inverted"):
+            os.makedirs(os.path.join(output_dir, sub), exist_ok=True)
+        paths = output.output_paths(output_dir, data)
+        if not (output.DEVICE_PNG and output.is_png_target(paths[0])):
+            from PIL import Image
+            m = self.predict_masks(data)
+            for path, mask in zip(paths, (m.color, m.overlay, m.inverted_overlay)):
+                Image.fromarray(np.asarray(mask)).save(path)
+            return paths
+        got = self._chain(data, want_masks="png")
+        if got is not None:
+            output.write_png_streams(paths, got[2][:3])
+            return paths
+        data, _, pred = self._labels(data)
+        output.output_data(output_dir, np.asarray(pred), data, self.settings.color_map)
+        return paths

@@ -27,6 +27,7 @@ EXPORTED_SYMBOLS = (
     "pseg_cc_vote", "pseg_cc_vote_device", "pseg_cc_vote_device_u8", "pseg_release_workspace", "pseg_bbox_fill",
     "pseg_masks", "pseg_masks_device", "pseg_masks_device_u8", "pseg_bbox_fill_device_u8",
     "pseg_otsu_char_height",
+    "pseg_png_bound", "pseg_png_encode_device", "pseg_masks_png_device_u8", "pseg_png_encode", "pseg_masks_png", "pseg_predict_chain_png",
     "pseg_rescale_shape", "pseg_gaussian_kernel", "pseg_resize_nearest", "pseg_resize_nearest_device", "pseg_scale_image",
     "pseg_prepare_images", "pseg_affine_warp", "pseg_affine_warp_fill", "pseg_brightness_shift",
     "pseg_eval_confusion", "pseg_cc_label", "pseg_cc_tables",
@@ -136,6 +137,14 @@ def lib():
     L.pseg_masks.argtypes = [i, vp, vp, vp, i, i, i, vp, vp, vp, vp]
     L.pseg_masks_device.argtypes = [i, vp, vp, vp, i, i, i, vp, vp, vp, vp, vp]
     L.pseg_otsu_char_height.argtypes = [i, vp, i, i, i, c.POINTER(i), c.POINTER(i)]
+    sz = c.c_size_t
+    L.pseg_png_bound.argtypes = [i, i, i, i]
+    L.pseg_png_bound.restype = sz
+    L.pseg_png_encode_device.argtypes = [i, vp, i, i, i, i, vp, sz, c.POINTER(sz), vp]
+    L.pseg_masks_png_device_u8.argtypes = [i, vp, vp, vp, i, i, i, i, c.POINTER(vp), c.POINTER(sz), c.POINTER(sz), vp]
+    L.pseg_png_encode.argtypes = [i, vp, i, i, i, i, vp, sz, c.POINTER(sz)]
+    L.pseg_masks_png.argtypes = [i, vp, vp, vp, i, i, i, i, c.POINTER(vp), c.POINTER(sz), c.POINTER(sz)]
+    L.pseg_predict_chain_png.argtypes = [vp, vp, i, i, i, i, vp, c.POINTER(i), i, c.c_uint, vp, vp, vp, i, c.POINTER(vp), c.POINTER(sz), c.POINTER(sz)]
     _LIB = L
     return L
 
@@ -389,7 +398,8 @@ class Engine:
         """The Predictor chain on the device (pseg_predict_chain; lib/predictor.py:32-54): predict -> [nearest resize of
         the label map to out_shape] -> post-processors ("cc_vote" / "bbox", in order) -> [the four masks].  `binary` must
         have the label map's final shape.  Returns {"labels": uint8 or int64 map or None, "masks": (color, overlay,
-        inverted, fg_color) or None}; the arrays live in recycled page-locked memory."""
+        inverted, fg_color) or None}; the arrays live in recycled page-locked memory.  masks="png": the four masks come back as
+        PNG streams (bytes objects) encoded on the device (pseg_predict_chain_png), decoding to the arrays masks=True returns."""
         img = np.ascontiguousarray(image, dtype=np.uint8)
         H, W = img.shape[:2]
         Ho, Wo = (int(out_shape[0]), int(out_shape[1])) if out_shape is not None else (0, 0)
@@ -409,6 +419,13 @@ class Engine:
             raise PsegError("labels must be 'u8', 'i64' or None")
         t = None
         outs = [None] * 4
+        if masks == "png":
+            t = np.ascontiguousarray(lut, dtype=np.uint8).reshape(-1, 3)
+            bufs, P, caps, sizes = _png_buffers(Hl, Wl, 3, 0, [True] * 4)
+            _check(lib().pseg_predict_chain_png(self._h, _ptr(img), H, W, Ho, Wo, _ptr(b), ops, len(post_ops), 1 if exact_labels else 0,
+                                                _ptr(lab) if labels == "i64" else None, _ptr(lab) if labels == "u8" else None,
+                                                _ptr(t), t.shape[0], P, caps, sizes))
+            return {"labels": lab, "masks": tuple(bufs[k][:sizes[k]].tobytes() for k in range(4))}
         if masks:
             t = np.ascontiguousarray(lut, dtype=np.uint8).reshape(-1, 3)
             outs = [pinned_empty_pooled((Hl, Wl, 3), np.uint8) for _ in range(4)]
@@ -642,6 +659,61 @@ def masks(pred, binary, lut, device=0):
     _check(lib().pseg_masks(int(device), _ptr(p), _ptr(b), _ptr(t), t.shape[0], H, W,
                             *[_ptr(o) for o in outs]))
     return tuple(outs)
+
+
+# -- PNG output on the device (lib/output.py:20-41) -------------------------------------------------------------------
+MASK_NAMES = ("color", "overlay", "inverted", "fg_color")
+
+
+def png_bound(H, W, channels=3, band_rows=0):
+    """Upper bound of the encoded size of an (H,W[,3]) image (pseg_png_bound: arithmetic, no device)."""
+    n = int(lib().pseg_png_bound(int(H), int(W), int(channels), int(band_rows)))
+    if n == 0:
+        raise PsegError("png_bound: bad shape (%r, %r), channels %r or band_rows %r" % (H, W, channels, band_rows))
+    return n
+
+
+def _png_buffers(H, W, channels, band_rows, wanted):
+    """Page-locked output buffers of the bound's size for the wanted streams + the ctypes arrays the C entries take."""
+    n = png_bound(H, W, channels, band_rows)
+    bufs = [pinned_empty_pooled((n,), np.uint8) if w else None for w in wanted]
+    P = (ctypes.c_void_p * 4)(*[None if b is None else b.ctypes.data for b in bufs])
+    caps = (ctypes.c_size_t * 4)(*[0 if b is None else n for b in bufs])
+    return bufs, P, caps, (ctypes.c_size_t * 4)()
+
+
+def png_encode(array, band_rows=0, device=0):
+    """uint8 (H,W) or (H,W,3) -> the bytes of a PNG file (8-bit gray / truecolour), encoded on the GPU (pseg_png_encode)."""
+    a = np.asarray(array)
+    if a.dtype != np.uint8 or a.ndim not in (2, 3) or (a.ndim == 3 and a.shape[2] != 3) or a.size == 0:
+        raise PsegError("png_encode takes a non-empty uint8 (H,W) or (H,W,3) array, got %s %r" % (a.dtype, a.shape))
+    a = np.ascontiguousarray(a)
+    H, W = a.shape[:2]
+    ch = 1 if a.ndim == 2 else 3
+    L = lib()
+    cap = int(L.pseg_png_bound(H, W, ch, int(band_rows)))
+    out = pinned_empty_pooled((max(cap, 1),), np.uint8)
+    n = ctypes.c_size_t()
+    _check(L.pseg_png_encode(int(device), _ptr(a), H, W, ch, int(band_rows), _ptr(out), cap, ctypes.byref(n)))
+    return out[:n.value].tobytes()
+
+
+def masks_png(pred, binary, lut, which=("color", "overlay", "inverted"), band_rows=0, device=0):
+    """generate_output_masks (lib/output.py:44-60) straight to PNG streams: {name: bytes} for the names in `which` (of "color",
+    "overlay", "inverted", "fg_color"), each decoding to the array masks() returns (pseg_masks_png)."""
+    for w in which:
+        if w not in MASK_NAMES:
+            raise PsegError("unknown mask %r (one of %r)" % (w, MASK_NAMES))
+    p = np.ascontiguousarray(pred, dtype=np.int64)
+    b = np.ascontiguousarray(binary, dtype=np.uint8)
+    t = np.ascontiguousarray(lut, dtype=np.uint8).reshape(-1, 3)
+    if p.ndim != 2 or b.shape != p.shape or p.size == 0:
+        raise PsegError("pred %r and binary %r must be non-empty (H,W) arrays of one shape" % (p.shape, b.shape))
+    H, W = p.shape
+    L = lib()
+    bufs, P, caps, sizes = _png_buffers(H, W, 3, band_rows, [m in which for m in MASK_NAMES])
+    _check(L.pseg_masks_png(int(device), _ptr(p), _ptr(b), _ptr(t), t.shape[0], H, W, int(band_rows), P, caps, sizes))
+    return {m: bufs[k][:sizes[k]].tobytes() for k, m in enumerate(MASK_NAMES) if m in which}
 
 
 def otsu_char_height(gray, inverse=False, device=0):
