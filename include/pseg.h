@@ -385,6 +385,32 @@ int pseg_predict_chain_png(pseg_engine* e, const uint8_t* img, int H, int W, int
                            const int* post_ops, int n_post, unsigned flags, int64_t* labels, uint8_t* labels_u8,
                            const uint8_t* lut, int n_lut, uint8_t* const png[4], const size_t cap[4], size_t n_bytes[4]);
 
+/* The same entries with a compression `level`; the entries above are level 0.  Any other level than 0 or 1: PSEG_EINVAL (the
+ * bound: 0).
+ *   0  one fixed-Huffman block per band, as described above.
+ *   1  a band's workgroup walks its tokens twice: it counts the literal/length symbols, builds a Huffman code of at most 15
+ *      bits for them (two one-bit distance codes beside it: every match of a band has the same distance), prices the band as a
+ *      dynamic block -- header included -- and as a fixed one, and writes the smaller (a tie: fixed, the band is then level 0's
+ *      band of the same rows bit for bit).  The tokens are level 0's.  No band grows, so the bound's formula holds; only the
+ *      default band differs: band_rows = 0 is max(1, 65536 / (channels * W + 1)) rows, over which the header amortises. */
+size_t pseg_png_bound_lv(int H, int W, int channels, int band_rows, int level);
+int pseg_png_encode_device_lv(int device, const uint8_t* d_src, int H, int W, int channels, int band_rows, int level, uint8_t* out,
+                              size_t cap, size_t* n_bytes, void* stream);
+int pseg_masks_png_device_u8_lv(int device, const uint8_t* d_pred, const uint8_t* d_binary, const uint8_t* d_lut, int n_lut, int H, int W,
+                                int band_rows, int level, uint8_t* const out[4], const size_t cap[4], size_t n_bytes[4], void* stream);
+int pseg_png_encode_lv(int device, const uint8_t* src, int H, int W, int channels, int band_rows, int level, uint8_t* out, size_t cap,
+                       size_t* n_bytes);
+int pseg_masks_png_lv(int device, const int64_t* pred, const uint8_t* binary, const uint8_t* lut, int n_lut, int H, int W, int band_rows,
+                      int level, uint8_t* const out[4], const size_t cap[4], size_t n_bytes[4]);
+int pseg_predict_chain_png_lv(pseg_engine* e, const uint8_t* img, int H, int W, int Ho, int Wo, const uint8_t* binary,
+                              const int* post_ops, int n_post, unsigned flags, int64_t* labels, uint8_t* labels_u8,
+                              const uint8_t* lut, int n_lut, int level, uint8_t* const png[4], const size_t cap[4], size_t n_bytes[4]);
+/* The code lengths level 1 uses, on the host (pure arithmetic, no device; the device runs the same function): counts[n] ->
+ * lengths[n], 0 exactly for a count of 0, none above `limit`, a complete prefix code when two or more symbols occur (one symbol:
+ * length 1), the Huffman code's lengths whenever those fit the limit.  n in 1..286, limit in 1..15, at most 2^limit symbols in
+ * use, the counts' sum below 2^32; else PSEG_EINVAL. */
+int pseg_png_code_lengths(const uint32_t* counts, int n, int limit, uint8_t* lengths);
+
 /* compute_char_height (lib/image_ops.py:58-82) minus the file read: Otsu threshold, invert
  * unless `inverse`, 4-connected components, keep glyph-shaped ones, upper median of heights.
  * *height = -1 when no component qualifies (the reference returns None). *otsu gets the

@@ -49,7 +49,7 @@ __global__ void chain_widen_kernel(const uint8_t* in, int64_t* out, size_t n) {
 using namespace pseg;
 
 // the masks of a chain call as PNG streams (pseg_predict_chain_png) instead of raw arrays
-struct ChainPng { uint8_t* const* out; const size_t* cap; size_t* n_bytes; };
+struct ChainPng { uint8_t* const* out; const size_t* cap; size_t* n_bytes; int level; };
 
 static int chain_run(pseg_engine* h, const uint8_t* img, int H, int W, int Ho, int Wo, const uint8_t* binary,
                      const int* post_ops, int n_post, unsigned flags, int64_t* labels, uint8_t* labels_u8,
@@ -74,7 +74,8 @@ static int chain_run(pseg_engine* h, const uint8_t* img, int H, int W, int Ho, i
     if (want_masks && (!lut || n_lut < 1)) return fail(PSEG_EINVAL, "the masks need the colour table");
     if (want_png) {
         if (n_lut > 256) return fail(PSEG_EINVAL, "n_lut %d out of range (1..256)", n_lut);
-        const size_t bound = pseg_png_bound(Hl, Wl, 3, 0);
+        if (png->level != 0 && png->level != 1) return fail(PSEG_EINVAL, "png: level %d (0 = fixed Huffman codes, 1 = dynamic codes per band)", png->level);
+        const size_t bound = pseg_png_bound_lv(Hl, Wl, 3, 0, png->level);
         for (int k = 0; k < 4; ++k)
             if (png->out[k] && png->cap[k] < bound) return fail(PSEG_EINVAL, "png: output buffer %d of %zu bytes, pseg_png_bound is %zu", k, png->cap[k], bound);
     }
@@ -136,7 +137,7 @@ static int chain_run(pseg_engine* h, const uint8_t* img, int H, int W, int Ho, i
     }
     if (want_png) {
         // the band kernel selects the masks' pixels itself: the RGB masks are never written; synchronises `st`
-        PSEG_TRY(pseg_masks_png_device_u8(e.device, cur, c.d_buf[CB_BIN], c.d_buf[CB_LUT], n_lut, Hl, Wl, 0, png->out, png->cap, png->n_bytes, st));
+        PSEG_TRY(pseg_masks_png_device_u8_lv(e.device, cur, c.d_buf[CB_BIN], c.d_buf[CB_LUT], n_lut, Hl, Wl, 0, png->level, png->out, png->cap, png->n_bytes, st));
     } else if (want_masks) {
         uint8_t* m = c.d_buf[CB_MASKS];
         uint8_t* dm[4] = {color ? m : nullptr, overlay ? m + nla * 3 : nullptr, inverted ? m + 2 * nla * 3 : nullptr, fg_color ? m + 3 * nla * 3 : nullptr};
@@ -156,11 +157,17 @@ extern "C" int pseg_predict_chain(pseg_engine* h, const uint8_t* img, int H, int
     return chain_run(h, img, H, W, Ho, Wo, binary, post_ops, n_post, flags, labels, labels_u8, lut, n_lut, color, overlay, inverted, fg_color, nullptr);
 }
 
+extern "C" int pseg_predict_chain_png_lv(pseg_engine* h, const uint8_t* img, int H, int W, int Ho, int Wo, const uint8_t* binary,
+                                         const int* post_ops, int n_post, unsigned flags, int64_t* labels, uint8_t* labels_u8,
+                                         const uint8_t* lut, int n_lut, int level, uint8_t* const png[4], const size_t cap[4], size_t n_bytes[4]) {
+    if (!png || !cap || !n_bytes) return fail(PSEG_EINVAL, "NULL argument");
+    for (int k = 0; k < 4; ++k) n_bytes[k] = 0;
+    const ChainPng req{png, cap, n_bytes, level};
+    return chain_run(h, img, H, W, Ho, Wo, binary, post_ops, n_post, flags, labels, labels_u8, lut, n_lut, nullptr, nullptr, nullptr, nullptr, &req);
+}
+
 extern "C" int pseg_predict_chain_png(pseg_engine* h, const uint8_t* img, int H, int W, int Ho, int Wo, const uint8_t* binary,
                                       const int* post_ops, int n_post, unsigned flags, int64_t* labels, uint8_t* labels_u8,
                                       const uint8_t* lut, int n_lut, uint8_t* const png[4], const size_t cap[4], size_t n_bytes[4]) {
-    if (!png || !cap || !n_bytes) return fail(PSEG_EINVAL, "NULL argument");
-    for (int k = 0; k < 4; ++k) n_bytes[k] = 0;
-    const ChainPng req{png, cap, n_bytes};
-    return chain_run(h, img, H, W, Ho, Wo, binary, post_ops, n_post, flags, labels, labels_u8, lut, n_lut, nullptr, nullptr, nullptr, nullptr, &req);
+    return pseg_predict_chain_png_lv(h, img, H, W, Ho, Wo, binary, post_ops, n_post, flags, labels, labels_u8, lut, n_lut, 0, png, cap, n_bytes);
 }

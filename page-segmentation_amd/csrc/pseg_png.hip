@@ -22,6 +22,11 @@
 // the bits are ORed into an LDS bit buffer (deflate packs LSB first, Huffman codes go in bit-reversed) and whole 32-bit words
 // are streamed to the slot; the partial last word is carried into the next segment.  No match has a distance other than
 // `channels` (1 or 3), so deflate's 32 768-byte window is never a concern.
+//
+// Level 1 (png_band_kernel<SRC, 1>): the same tokens, but the band's workgroup first counts them (pass A), builds a Huffman code
+// of at most 15 bits for the literal/length symbols it saw (png_code_lengths; two one-bit distance codes beside it), prices the
+// band as a dynamic and as a fixed block and packs the cheaper one (pass B; the dynamic header goes into the bit buffer in front
+// of segment 0).  A band that stays fixed is level 0's band bit for bit, so no band outgrows png_band_bound.
 #include <algorithm>
 #include <mutex>
 
@@ -33,6 +38,10 @@ constexpr int PNG_T = 256;                    // threads of a band workgroup
 constexpr int PNG_BPT = 16;                   // filtered bytes per thread and segment
 constexpr int PNG_SEG = PNG_T * PNG_BPT;      // 4096
 constexpr int PNG_BITW = PNG_SEG * 9 / 32 + 8;   // words of the bit buffer: 31 carried bits + 9 bits per byte + 49 bits of band end
+constexpr int PNG_NSYM = 286;                 // literal/length alphabet; the histogram holds two more counters: matches, extra bits
+constexpr int PNG_CLWS = 1024;                // words of png_code_lengths' work space (n <= 286)
+constexpr int PNG_HDRW = 136;                 // words kept for a dynamic block header: 17 + 19 * 3 + 289 code-length tokens of <= 14 bits
+constexpr int PNG_BITW1 = PNG_SEG * 15 / 32 + PNG_HDRW + 8;   // level 1: 15 bits per byte + header or carry + band end
 constexpr unsigned ADLER_M = 65521u;
 constexpr size_t PNG_MAX_ROW = (size_t)1 << 30;  // filtered bytes of a row / of a band: in-band indices are ints
 constexpr size_t PNG_FIXED = 8 + 25 + 14 + 21 + 12;   // signature, IHDR, IDAT(78 01), IDAT(final block + Adler), IEND
@@ -53,17 +62,17 @@ struct PngJob {
 
 // ---- host arithmetic ------------------------------------------------------------------------------------------------
 static inline size_t png_band_bound(size_t n) { return n + n / 8 + 8; }   // header 3 + 9 n + end-of-block 7 + stored header 3 bits, padded, + 4
-static int png_rows(int H, int W, int C, int band_rows) {
+static int png_rows(int H, int W, int C, int band_rows, int level) {
     const size_t L = (size_t)W * C + 1;
-    size_t r = band_rows > 0 ? (size_t)band_rows : std::max<size_t>(1, 16384 / L);
+    size_t r = band_rows > 0 ? (size_t)band_rows : std::max<size_t>(1, (level ? 65536 : 16384) / L);   // level 1: the header amortises
     r = std::min(r, (size_t)H);
     r = std::min(r, std::max<size_t>(1, PNG_MAX_ROW / L));
     return (int)r;
 }
 static bool png_shape_ok(int H, int W, int C) { return H >= 1 && W >= 1 && (C == 1 || C == 3) && (size_t)W * C + 1 <= PNG_MAX_ROW; }
-static size_t png_bound(int H, int W, int C, int band_rows) {
-    if (!png_shape_ok(H, W, C) || band_rows < 0) return 0;
-    const size_t L = (size_t)W * C + 1, R = png_rows(H, W, C, band_rows);
+static size_t png_bound(int H, int W, int C, int band_rows, int level) {
+    if (!png_shape_ok(H, W, C) || band_rows < 0 || (level != 0 && level != 1)) return 0;
+    const size_t L = (size_t)W * C + 1, R = png_rows(H, W, C, band_rows, level);
     const size_t nfull = (size_t)H / R, rem = (size_t)H % R;
     size_t t = PNG_FIXED + nfull * (12 + png_band_bound(R * L));
     if (rem) t += 12 + png_band_bound(rem * L);
@@ -71,14 +80,17 @@ static size_t png_bound(int H, int W, int C, int band_rows) {
 }
 
 // ---- fixed Huffman codes (RFC 1951 3.2.6), already bit-reversed for LSB-first packing -----------------------------------
-__device__ __forceinline__ void png_lit(unsigned v, unsigned& code, int& nb) {
-    if (v < 144) { nb = 8; code = __brev(0x30u + v) >> 24; }
-    else { nb = 9; code = __brev(0x190u + (v - 144)) >> 23; }
+__host__ __device__ __forceinline__ int png_fixed_len(int sym) { return sym < 144 ? 8 : sym < 256 ? 9 : sym < 280 ? 7 : 8; }
+__device__ __forceinline__ void png_fixed(int sym, unsigned& code, int& cb) {
+    if (sym < 144) { cb = 8; code = __brev(0x30u + (unsigned)sym) >> 24; }
+    else if (sym < 256) { cb = 9; code = __brev(0x190u + (unsigned)(sym - 144)) >> 23; }
+    else if (sym < 280) { cb = 7; code = __brev((unsigned)(sym - 256)) >> 25; }
+    else { cb = 8; code = __brev(0xC0u + (unsigned)(sym - 280)) >> 24; }
 }
-// match of `len` (3..258) at distance D (1 or 3): length symbol + extra bits + 5-bit distance code (no extra bits)
-__device__ __forceinline__ void png_match(int len, int D, unsigned& code, int& nb) {
-    int sym, eb = 0;
-    unsigned extra = 0;
+// match of `len` (3..258): its length symbol and extra bits (RFC 1951 3.2.5); the distance code follows it
+__device__ __forceinline__ void png_match(int len, int& sym, unsigned& extra, int& eb) {
+    eb = 0;
+    extra = 0;
     if (len == 258) sym = 285;
     else {
         const int l = len - 3;
@@ -90,13 +102,74 @@ __device__ __forceinline__ void png_match(int len, int D, unsigned& code, int& n
             extra = (unsigned)(l - (1 << n)) & ((1u << eb) - 1);
         }
     }
-    unsigned c;
-    int cb;
-    if (sym < 280) { cb = 7; c = __brev((unsigned)(sym - 256)) >> 25; }
-    else { cb = 8; c = __brev(0xC0u + (unsigned)(sym - 280)) >> 24; }
-    const unsigned dist = D == 1 ? 0u : 8u;               // distance code 0 (00000) / 2 (00010 -> reversed 01000)
-    code = c | (extra << cb) | (dist << (cb + eb));
-    nb = cb + eb + 5;
+}
+// a token's bits: the symbol's code (bit-reversed, `cb` bits), the extra bits, for a match the band's distance code
+__device__ __forceinline__ void png_bits(unsigned c, int cb, unsigned extra, int eb, bool dist, unsigned dcode, int dbits, unsigned& code, int& nb) {
+    code = c | (extra << cb);
+    nb = cb + eb;
+    if (dist) { code |= dcode << nb; nb += dbits; }
+}
+
+// ---- code lengths of a length-limited prefix code (level 1; both the literal/length and the code-length alphabet) ----------
+// counts[n] -> lengths[n]: 0 for a symbol that does not occur, 1 for a single used symbol, otherwise a complete prefix code
+// with no length above `limit` (n <= 286, used symbols <= 2^limit, sum of the counts < 2^32).  Where the Huffman tree fits
+// the limit its lengths are returned (an optimal code); where it does not, leaves below the limit are raised to it and the
+// Kraft sum is brought back to 1 by moving codes one level down, then the lengths go to the symbols by descending count.
+// Two steps so that a workgroup can share the first: png_cl_rank sorts (every symbol counts the symbols in front of it;
+// symbols first, first + stride, ...), png_cl_build is serial.  ws: PNG_CLWS words.
+__host__ __device__ inline void png_cl_rank(const uint32_t* counts, int n, uint8_t* lengths, uint32_t* ws, int first, int stride) {
+    uint16_t* ord = (uint16_t*)(ws + 857);
+    for (int s = first; s < n; s += stride) {
+        lengths[s] = 0;
+        const uint32_t c = counts[s];
+        if (!c) continue;
+        int r = 0;
+        for (int q = 0; q < n; ++q) {
+            const uint32_t d = counts[q];
+            r += (d != 0 && (d < c || (d == c && q < s))) ? 1 : 0;
+        }
+        ord[r] = (uint16_t)s;                 // ascending by (count, symbol)
+    }
+}
+__host__ __device__ inline void png_cl_build(const uint32_t* counts, int n, int limit, uint8_t* lengths, uint32_t* ws) {
+    uint32_t* wt = ws;                        // [2k-1] node weights, then node depths: leaves in sorted order, then the inner nodes
+    uint16_t* par = (uint16_t*)(ws + 571);    // [2k-1] parent of a node
+    const uint16_t* ord = (const uint16_t*)(ws + 857);
+    uint32_t* num = ws + 1000;                // [limit+1] codes per length
+    int k = 0;
+    for (int s = 0; s < n; ++s) k += counts[s] != 0 ? 1 : 0;
+    if (k == 0) return;
+    if (k == 1) { lengths[ord[0]] = 1; return; }
+    for (int i = 0; i < k; ++i) wt[i] = counts[ord[i]];
+    int i = 0, j = k, next = k;               // two queues: sorted leaves, inner nodes in creation order (ascending too)
+    while (next < 2 * k - 1) {
+        uint32_t w = 0;
+        for (int two = 0; two < 2; ++two) {
+            const int pick = (i < k && (j >= next || wt[i] <= wt[j])) ? i++ : j++;
+            w += wt[pick];
+            par[pick] = (uint16_t)next;
+        }
+        wt[next++] = w;
+    }
+    wt[2 * k - 2] = 0;
+    for (int v = 2 * k - 3; v >= 0; --v) wt[v] = wt[par[v]] + 1;      // a parent is created behind its children
+    for (int l = 0; l <= limit; ++l) num[l] = 0;
+    for (int v = 0; v < k; ++v) ++num[wt[v] < (uint32_t)limit ? wt[v] : (uint32_t)limit];
+    uint32_t total = 0;                       // Kraft sum in units of 2^-limit: above 2^limit only where leaves were raised
+    for (int l = 1; l <= limit; ++l) total += num[l] << (limit - l);
+    while (total > (1u << limit)) {
+        --num[limit];
+        for (int l = limit - 1; l > 0; --l)
+            if (num[l]) { --num[l]; num[l + 1] += 2; break; }
+        --total;
+    }
+    int p = 0;
+    for (int l = limit; l >= 1; --l)
+        for (uint32_t c = 0; c < num[l]; ++c) lengths[ord[p++]] = (uint8_t)l;
+}
+__host__ __device__ inline void png_code_lengths(const uint32_t* counts, int n, int limit, uint8_t* lengths, uint32_t* ws) {
+    png_cl_rank(counts, n, lengths, ws, 0, 1);
+    png_cl_build(counts, n, limit, lengths, ws);
 }
 
 // ---- workgroup scans over one int per thread (four waves of 64) -------------------------------------------------------------
@@ -166,21 +239,19 @@ struct PngSrcMasks {                          // generate_output_masks (lib/outp
     }
 };
 
-// The tokens of one thread's 16 bytes: emit(code, nbits) in stream order.  eqm: bit j set = byte j continues a run; pl: last
-// run break in front of the chunk (segment position, -1: none); nf: first break behind it (slen: none).
+// The tokens of one thread's 16 bytes: emit(symbol 0..285, extra bits, their count, has a distance) in stream order; the code
+// comes from a lookup afterwards.  eqm: bit j set = byte j continues a run; pl: last run break in front of the chunk (segment
+// position, -1: none); nf: first break behind it (slen: none).
 template <class F>
-__device__ __forceinline__ void png_walk(const uint32_t (&w4)[4], int cnt, unsigned eqm, int p0, int pl, int nf, int D, F emit) {
+__device__ __forceinline__ void png_walk(const uint32_t (&w4)[4], int cnt, unsigned eqm, int p0, int pl, int nf, F emit) {
     const unsigned brk = ~eqm & ((1u << cnt) - 1u);
     int last_break = pl;
     for (int j = 0; j < cnt; ++j) {
         const unsigned v = (w4[j >> 2] >> (8 * (j & 3))) & 255u;
         const int p = p0 + j;
-        unsigned code;
-        int nb;
         if (!((eqm >> j) & 1u)) {
             last_break = p;
-            png_lit(v, code, nb);
-            emit(code, nb);
+            emit((int)v, 0u, 0, false);
             continue;
         }
         const unsigned behind = j + 1 < 32 ? brk >> (j + 1) : 0u;
@@ -188,21 +259,155 @@ __device__ __forceinline__ void png_walk(const uint32_t (&w4)[4], int cnt, unsig
         const int s = last_break + 1;
         const int k = p - s, q = k - k % 258;
         const int c = min(258, (e - s) - q);
-        if (c < 3) { png_lit(v, code, nb); emit(code, nb); }
-        else if (k == q) { png_match(c, D, code, nb); emit(code, nb); }
+        if (c < 3) emit((int)v, 0u, 0, false);
+        else if (k == q) {
+            int sym, eb;
+            unsigned extra;
+            png_match(c, sym, extra, eb);
+            emit(sym, extra, eb, true);
+        }
     }
 }
 
+// One segment of a band: the filtered bytes of this thread's chunk (w4, also to s_in), their Adler sums, the run flags and the
+// two scans over the run breaks.  Ends behind a workgroup barrier; what the caller wrote to LDS in front of it is visible.
 template <class SRC>
+__device__ __forceinline__ void png_segment(const SRC& src, int mask, int row0, int L, int D, int base, int slen, const uint32_t* s_lut,
+                                            uint8_t* s_in, int* s_w, uint32_t (&w4)[4], int& cnt, unsigned& eqm, int& pl, int& nf,
+                                            unsigned& a_sum, unsigned& b_sum) {
+    const int t = threadIdx.x, p0 = t * PNG_BPT;
+    cnt = min(PNG_BPT, max(0, slen - p0));
+    w4[0] = w4[1] = w4[2] = w4[3] = 0u;
+    a_sum = 0;
+    b_sum = 0;
+    if (cnt > 0) {
+        const int i0 = base + p0;
+        int r = i0 / L, c = i0 - r * L;
+        int grow = row0 + r, x = 0, ch = 0;
+        if (c > 0) { x = (c - 1) / D; ch = (c - 1) - x * D; }
+        bool need = true;
+        uint32_t cur = 0, up = 0;
+        for (int j = 0; j < cnt; ++j) {
+            uint32_t v;
+            if (c == 0) { v = 2u; x = 0; ch = 0; need = true; }          // filter type: Up
+            else {
+                if (need) {
+                    cur = src.px(grow, x, mask, s_lut);
+                    up = grow > 0 ? src.px(grow - 1, x, mask, s_lut) : 0u;
+                    need = false;
+                }
+                v = ((cur >> (8 * ch)) - (up >> (8 * ch))) & 255u;
+                if (++ch == D) { ch = 0; ++x; need = true; }
+            }
+            w4[j >> 2] |= v << (8 * (j & 3));
+            a_sum += v;
+            b_sum += v * (unsigned)(cnt - j);
+            if (++c == L) { c = 0; ++grow; }
+        }
+    }
+    *(uint4*)(s_in + 16 + p0) = make_uint4(w4[0], w4[1], w4[2], w4[3]);
+    __syncthreads();
+    // run flags: byte == the byte D in front of it (none in front of the band or the segment)
+    eqm = 0;
+    for (int j = 0; j < cnt; ++j) {
+        const int p = p0 + j;
+        if (base + p >= D && s_in[16 + p] == s_in[16 + p - D]) eqm |= 1u << j;
+    }
+    const unsigned brk = ~eqm & ((1u << cnt) - 1u);
+    const int lb = brk ? p0 + (31 - __clz(brk)) : -1;
+    const int fb = brk ? p0 + (__ffs(brk) - 1) : slen;
+    pl = png_scan_max_before(lb, s_w);
+    nf = png_scan_min_after(fb, slen, s_w);
+}
+
+// The dynamic block header of a band (RFC 1951 3.2.7) from the literal/length code lengths: thread 0.  The code-length sequence
+// (HLIT literal/length lengths, then the two distance codes) is run-length coded with 17 / 18 for runs of zeros, no 16; its 19
+// symbols get a code of at most 7 bits from the same png_code_lengths.  With `bits` the header is also written to the (zeroed)
+// bit buffer.  -> its size in bits.  hw: 256 words of LDS behind png_code_lengths' work space.
+__device__ inline int png_dyn_header(const uint8_t* s_len, int D, uint32_t* ws, uint32_t* bits) {
+    uint32_t* hw = ws + PNG_CLWS;
+    uint16_t* tok = (uint16_t*)hw;            // [<= 289] symbol | extra << 5
+    uint32_t* cl_cnt = hw + 152;              // [19]
+    uint8_t* cl_len = (uint8_t*)(hw + 172);   // [19]
+    uint16_t* cl_code = (uint16_t*)(hw + 180);   // [19] bit-reversed
+    int hlit = 257;
+    for (int s = PNG_NSYM - 1; s >= 257; --s)
+        if (s_len[s]) { hlit = s + 1; break; }
+    const int hdist = D == 1 ? 2 : 3;         // two distance codes of one bit: 0 and 1, or 0 and 2 (the band's only distance is D)
+    const int nseq = hlit + hdist;
+    auto seq = [&](int i) -> int { return i < hlit ? (int)s_len[i] : (D == 3 && i - hlit == 1) ? 0 : 1; };
+    for (int k = 0; k < 19; ++k) cl_cnt[k] = 0;
+    int ntok = 0;
+    for (int i = 0; i < nseq;) {
+        const int v = seq(i);
+        int r = 1;
+        if (v == 0) while (r < 138 && i + r < nseq && seq(i + r) == 0) ++r;
+        int sym = v, extra = 0;
+        if (r >= 11) { sym = 18; extra = r - 11; }
+        else if (r >= 3) { sym = 17; extra = r - 3; }
+        else r = 1;
+        tok[ntok++] = (uint16_t)(sym | (extra << 5));
+        ++cl_cnt[sym];
+        i += r;
+    }
+    png_code_lengths(cl_cnt, 19, 7, cl_len, ws);
+    const int order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
+    int hclen = 4;
+    for (int k = 18; k >= 4; --k)
+        if (cl_len[order[k]]) { hclen = k + 1; break; }
+    int size = 3 + 5 + 5 + 4 + 3 * hclen;
+    for (int k = 0; k < 19; ++k) size += (int)cl_cnt[k] * ((int)cl_len[k] + (k == 17 ? 3 : k == 18 ? 7 : 0));
+    if (!bits) return size;
+    unsigned code = 0;                        // canonical codes (RFC 1951 3.2.2), shortest first, symbols ascending
+    for (int l = 1; l <= 7; ++l) {
+        for (int k = 0; k < 19; ++k)
+            if (cl_len[k] == l) cl_code[k] = (uint16_t)(__brev(code++) >> (32 - l));
+        code <<= 1;
+    }
+    int pos = 0;
+    auto put = [&](unsigned v, int nb) {
+        const unsigned long long x = (unsigned long long)v << (pos & 31);
+        bits[pos >> 5] |= (uint32_t)x;
+        if (x >> 32) bits[(pos >> 5) + 1] |= (uint32_t)(x >> 32);
+        pos += nb;
+    };
+    put(4u, 3);                               // BFINAL = 0, BTYPE = 10 (dynamic Huffman), LSB first
+    put((unsigned)(hlit - 257), 5);
+    put((unsigned)(hdist - 1), 5);
+    put((unsigned)(hclen - 4), 4);
+    for (int k = 0; k < hclen; ++k) put(cl_len[order[k]], 3);
+    for (int k = 0; k < ntok; ++k) {
+        const int sym = tok[k] & 31, extra = tok[k] >> 5;
+        put(cl_code[sym], cl_len[sym]);
+        if (sym == 17) put((unsigned)extra, 3);
+        else if (sym == 18) put((unsigned)extra, 7);
+    }
+    return pos;
+}
+
+// LV 0: one fixed-Huffman block per band.  LV 1: two passes over the band's tokens -- A counts the symbols, the workgroup builds
+// a code for them and prices the band both ways, B packs with the cheaper of the two (a tie goes to the fixed code: the band is
+// then LV 0's band bit for bit).
+template <class SRC, int LV>
 __global__ __launch_bounds__(PNG_T) void png_band_kernel(SRC src, PngJob J) {
     __shared__ __attribute__((aligned(16))) uint8_t s_in[16 + PNG_SEG];   // [13..15]: the three bytes in front of the segment
-    __shared__ uint32_t s_bits[PNG_BITW];
+    __shared__ uint32_t s_bits[LV ? PNG_BITW1 : PNG_BITW];
     __shared__ int s_w[4];
     __shared__ unsigned s_ad[2];
     __shared__ uint32_t s_lut[256];
+    __shared__ uint32_t s_hist[LV ? PNG_NSYM + 2 : 1];        // [286]: matches, [287]: extra bits
+    __shared__ uint32_t s_code[LV ? PNG_NSYM : 1];            // code (bit-reversed) | length << 16
+    __shared__ uint8_t s_len[LV ? PNG_NSYM + 2 : 1];
+    __shared__ uint32_t s_ws[LV ? PNG_CLWS + 256 : 1];
+    __shared__ unsigned long long s_cost[2];                  // literal/length bits of the band: dynamic, fixed
+    __shared__ int s_hdr[18];                                 // [0]: the dynamic header's bits; [1..15]: first code of a length; [17]: the written header's bits
     const int t = threadIdx.x, band = blockIdx.x, o = blockIdx.y, mask = J.mask_id[o];
     if constexpr (SRC::LUT) {
         s_lut[t] = t < src.n_lut ? (uint32_t)src.lut[t * 3] | ((uint32_t)src.lut[t * 3 + 1] << 8) | ((uint32_t)src.lut[t * 3 + 2] << 16) : 0u;
+    }
+    if constexpr (LV != 0) {
+        for (int k = t; k < PNG_NSYM + 2; k += PNG_T) s_hist[k] = 0u;
+        if (t < 2) s_cost[t] = 0ull;
     }
     __syncthreads();
     const int row0 = band * J.R, rows = min(J.R, J.H - row0);
@@ -211,69 +416,131 @@ __global__ __launch_bounds__(PNG_T) void png_band_kernel(SRC src, PngJob J) {
     uint32_t* const out = (uint32_t*)(J.slots[o] + (size_t)band * J.slot);
     unsigned out_w = 0;                                       // words of the slot written so far
     uint32_t carry_word = 2u;                                 // block header: BFINAL = 0, BTYPE = 01 (fixed Huffman), LSB first
-    int carry_bits = 3;
+    int carry_bits = 3;                                       // LV 1, first segment: the header's whole words and its partial word
+    unsigned dcode = D == 1 ? 0u : 8u;                        // fixed: distance code 0 (00000) / 2 (00010 -> reversed 01000)
+    int dbits = 5;
     unsigned adA = 0, adB = 0;
     const int nseg = (n + PNG_SEG - 1) / PNG_SEG;
+    uint32_t w4[4];
+    int cnt, pl, nf;
+    unsigned eqm, a_sum, b_sum;
+    const int p0 = t * PNG_BPT;
+    if constexpr (LV != 0) {
+        // pass A: the band's histogram
+        unsigned n_match = 0, n_extra = 0;
+        for (int sg = 0; sg < nseg; ++sg) {
+            const int base = sg * PNG_SEG, slen = min(PNG_SEG, n - base);
+            png_segment(src, mask, row0, L, D, base, slen, s_lut, s_in, s_w, w4, cnt, eqm, pl, nf, a_sum, b_sum);
+            int hs = 0;
+            unsigned hc = 0;                                  // equal symbols in a row go to the histogram as one add
+            png_walk(w4, cnt, eqm, p0, pl, nf, [&](int sym, unsigned, int eb, bool dist) {
+                if (sym != hs && hc) { atomicAdd(&s_hist[hs], hc); hc = 0; }
+                hs = sym;
+                ++hc;
+                n_extra += (unsigned)eb;
+                n_match += dist ? 1u : 0u;
+            });
+            if (hc) atomicAdd(&s_hist[hs], hc);
+            if (sg + 1 < nseg && t < 3) {
+                const uint8_t v = s_in[16 + PNG_SEG - 3 + t];
+                s_in[13 + t] = v;
+            }
+            __syncthreads();
+        }
+        if (n_match) atomicAdd(&s_hist[PNG_NSYM], n_match);
+        if (n_extra) atomicAdd(&s_hist[PNG_NSYM + 1], n_extra);
+        if (t == 0) atomicAdd(&s_hist[256], 1u);              // end of block
+        for (int k = t; k < PNG_BITW1; k += PNG_T) s_bits[k] = 0u;
+        __syncthreads();
+        // the literal/length code, the header's size, the band's size both ways
+        png_cl_rank(s_hist, PNG_NSYM, s_len, s_ws, t, PNG_T);
+        __syncthreads();
+        if (t == 0) {
+            png_cl_build(s_hist, PNG_NSYM, 15, s_len, s_ws);
+            unsigned code = 0;                                // first canonical code of every length (RFC 1951 3.2.2)
+            for (int l = 1; l <= 15; ++l) {
+                s_hdr[l] = (int)code;
+                unsigned c = 0;
+                for (int s = 0; s < PNG_NSYM; ++s) c += s_len[s] == l ? 1u : 0u;
+                code = (code + c) << 1;
+            }
+            s_hdr[0] = png_dyn_header(s_len, D, s_ws, nullptr);
+        }
+        __syncthreads();
+        {
+            unsigned long long dyn = 0, fix = 0;
+            for (int s = t; s < PNG_NSYM; s += PNG_T) {
+                const unsigned long long h = s_hist[s];
+                dyn += h * s_len[s];
+                fix += h * (unsigned)png_fixed_len(s);
+            }
+            if (dyn) atomicAdd(&s_cost[0], dyn);
+            if (fix) atomicAdd(&s_cost[1], fix);
+        }
+        __syncthreads();
+        const unsigned long long matches = s_hist[PNG_NSYM];  // (the extra bits cost the same both ways)
+        const bool dynamic = (unsigned long long)s_hdr[0] + s_cost[0] + matches < 3ull + s_cost[1] + 5ull * matches;
+        for (int s = t; s < PNG_NSYM; s += PNG_T) {
+            unsigned code = 0;
+            int cb = 0;
+            if (dynamic) {
+                cb = s_len[s];
+                if (cb) {
+                    unsigned r = 0;                           // symbols of this length in front of s
+                    for (int q = 0; q < s; ++q) r += s_len[q] == cb ? 1u : 0u;
+                    code = __brev((unsigned)s_hdr[cb] + r) >> (32 - cb);
+                }
+            } else png_fixed(s, code, cb);
+            s_code[s] = code | ((unsigned)cb << 16);
+        }
+        if (dynamic) {
+            dcode = D == 1 ? 0u : 1u;                         // distance code 0 is "0"; D = 3: code 2 is "1"
+            dbits = 1;
+            if (t == 0) s_hdr[17] = png_dyn_header(s_len, D, s_ws, s_bits);
+            __syncthreads();
+            carry_bits = s_hdr[17];
+        } else {
+            if (t == 0) s_bits[0] = carry_word;
+            __syncthreads();
+        }
+    }
+    // LV 0: the only pass; LV 1: pass B
     for (int sg = 0; sg < nseg; ++sg) {
         const int base = sg * PNG_SEG, slen = min(PNG_SEG, n - base);
         const bool last = sg == nseg - 1;
         // 1. the filtered bytes of this thread's chunk; the bit buffer starts as the carried partial word
-        for (int k = t; k < PNG_BITW; k += PNG_T) s_bits[k] = k == 0 ? carry_word : 0u;
+        if (LV == 0 || sg > 0)
+            for (int k = t; k < (LV ? PNG_BITW1 : PNG_BITW); k += PNG_T) s_bits[k] = k == 0 ? carry_word : 0u;
         if (t == 0) { s_ad[0] = 0; s_ad[1] = 0; }
-        const int p0 = t * PNG_BPT;
-        const int cnt = min(PNG_BPT, max(0, slen - p0));
-        uint32_t w4[4] = {0u, 0u, 0u, 0u};
-        unsigned a_sum = 0, b_sum = 0;
-        if (cnt > 0) {
-            const int i0 = base + p0;
-            int r = i0 / L, c = i0 - r * L;
-            int grow = row0 + r, x = 0, ch = 0;
-            if (c > 0) { x = (c - 1) / D; ch = (c - 1) - x * D; }
-            bool need = true;
-            uint32_t cur = 0, up = 0;
-            for (int j = 0; j < cnt; ++j) {
-                uint32_t v;
-                if (c == 0) { v = 2u; x = 0; ch = 0; need = true; }          // filter type: Up
-                else {
-                    if (need) {
-                        cur = src.px(grow, x, mask, s_lut);
-                        up = grow > 0 ? src.px(grow - 1, x, mask, s_lut) : 0u;
-                        need = false;
-                    }
-                    v = ((cur >> (8 * ch)) - (up >> (8 * ch))) & 255u;
-                    if (++ch == D) { ch = 0; ++x; need = true; }
-                }
-                w4[j >> 2] |= v << (8 * (j & 3));
-                a_sum += v;
-                b_sum += v * (unsigned)(cnt - j);
-                if (++c == L) { c = 0; ++grow; }
-            }
-        }
-        *(uint4*)(s_in + 16 + p0) = make_uint4(w4[0], w4[1], w4[2], w4[3]);
-        __syncthreads();
-        // 2. Adler partial of the segment; run flags: byte == the byte D in front of it (none in front of the band or the segment)
+        png_segment(src, mask, row0, L, D, base, slen, s_lut, s_in, s_w, w4, cnt, eqm, pl, nf, a_sum, b_sum);
+        // 2. Adler partial of the segment
         if (cnt > 0) {
             const unsigned after = (unsigned)(slen - (p0 + cnt));
             atomicAdd(&s_ad[0], a_sum);
             atomicAdd(&s_ad[1], (b_sum + a_sum * after) % ADLER_M);
         }
-        unsigned eqm = 0;
-        for (int j = 0; j < cnt; ++j) {
-            const int p = p0 + j;
-            if (base + p >= D && s_in[16 + p] == s_in[16 + p - D]) eqm |= 1u << j;
-        }
-        const unsigned brk = ~eqm & ((1u << cnt) - 1u);
-        const int lb = brk ? p0 + (31 - __clz(brk)) : -1;
-        const int fb = brk ? p0 + (__ffs(brk) - 1) : slen;
-        const int pl = png_scan_max_before(lb, s_w);
-        const int nf = png_scan_min_after(fb, slen, s_w);
+        auto lookup = [&](int sym, unsigned extra, int eb, bool dist, unsigned& code, int& nb) {
+            unsigned c;
+            int cb;
+            if constexpr (LV == 0) png_fixed(sym, c, cb);
+            else { const uint32_t e = s_code[sym]; c = e & 0xFFFFu; cb = (int)(e >> 16); }
+            png_bits(c, cb, extra, eb, dist, dcode, dbits, code, nb);
+        };
         // 3. bit lengths -> bit offsets
         int bits = 0;
-        png_walk(w4, cnt, eqm, p0, pl, nf, D, [&](unsigned, int nb) { bits += nb; });
+        png_walk(w4, cnt, eqm, p0, pl, nf, [&](int sym, unsigned extra, int eb, bool dist) {
+            unsigned code;
+            int nb;
+            lookup(sym, extra, eb, dist, code, nb);
+            bits += nb;
+        });
         int seg_bits = 0;
         int off = carry_bits + png_scan_sum_before(bits, s_w, seg_bits);
         // 4. pack
-        png_walk(w4, cnt, eqm, p0, pl, nf, D, [&](unsigned code, int nb) {
+        png_walk(w4, cnt, eqm, p0, pl, nf, [&](int sym, unsigned extra, int eb, bool dist) {
+            unsigned code;
+            int nb;
+            lookup(sym, extra, eb, dist, code, nb);
             const unsigned long long v = (unsigned long long)code << (off & 31);
             atomicOr(&s_bits[off >> 5], (uint32_t)v);
             if (v >> 32) atomicOr(&s_bits[(off >> 5) + 1], (uint32_t)(v >> 32));
@@ -281,7 +548,17 @@ __global__ __launch_bounds__(PNG_T) void png_band_kernel(SRC src, PngJob J) {
         });
         int T = carry_bits + seg_bits;
         if (last) {
-            T += 7 + 3;                       // end-of-block (0000000), then an empty stored block: BFINAL = 0, BTYPE = 00
+            if constexpr (LV == 0) T += 7;    // end-of-block (0000000)
+            else {
+                const uint32_t e = s_code[256];
+                if (t == 0) {
+                    const unsigned long long v = (unsigned long long)(e & 0xFFFFu) << (T & 31);
+                    atomicOr(&s_bits[T >> 5], (uint32_t)v);
+                    if (v >> 32) atomicOr(&s_bits[(T >> 5) + 1], (uint32_t)(v >> 32));
+                }
+                T += (int)(e >> 16);
+            }
+            T += 3;                           // ... then an empty stored block: BFINAL = 0, BTYPE = 00
             T = (T + 7) & ~7;                 // ... padded to a byte, LEN = 0000, NLEN = FFFF
             if (t == 0) {
                 const int f = T + 16;
@@ -449,11 +726,11 @@ static inline size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // Encodes `nout` images of one shape from `src` (output k = mask mask_id[k]) into host[k]; synchronises `st`.
 template <class SRC>
-static int png_run(int device, const SRC& src, int H, int W, int C, int band_rows, int nout, uint8_t* const host[4],
+static int png_run(int device, const SRC& src, int H, int W, int C, int band_rows, int level, int nout, uint8_t* const host[4],
                    size_t* const nbytes[4], const int mask_id[4], hipStream_t st) {
-    const size_t bound = png_bound(H, W, C, band_rows);
+    const size_t bound = png_bound(H, W, C, band_rows, level);
     PngJob J;
-    J.H = H; J.W = W; J.C = C; J.R = png_rows(H, W, C, band_rows);
+    J.H = H; J.W = W; J.C = C; J.R = png_rows(H, W, C, band_rows, level);
     J.nb = (int)(((size_t)H + J.R - 1) / J.R);
     J.L = W * C + 1;
     J.slot = (png_band_bound((size_t)J.R * J.L) + 3) & ~(size_t)3;
@@ -483,7 +760,8 @@ static int png_run(int device, const SRC& src, int H, int W, int C, int band_row
         J.out[k] = q + slots_b + meta_b + offs_b;
         J.mask_id[k] = mask_id[std::min(k, nout - 1)];
     }
-    png_band_kernel<SRC><<<dim3(J.nb, nout), PNG_T, 0, st>>>(src, J);
+    if (level == 0) png_band_kernel<SRC, 0><<<dim3(J.nb, nout), PNG_T, 0, st>>>(src, J);
+    else png_band_kernel<SRC, 1><<<dim3(J.nb, nout), PNG_T, 0, st>>>(src, J);
     png_frame_kernel<<<nout, PNG_T, 0, st>>>(J);
     png_gather_kernel<<<dim3(J.nb, nout), PNG_T, 0, st>>>(J);
     PSEG_HIP(hipGetLastError());
@@ -510,7 +788,8 @@ static int png_set_dev(int device) {
     return PSEG_OK;
 }
 
-static int png_check(int H, int W, int channels, int band_rows) {
+static int png_check(int H, int W, int channels, int band_rows, int level) {
+    if (level != 0 && level != 1) return fail(PSEG_EINVAL, "png: level %d (0 = fixed Huffman codes, 1 = dynamic codes per band)", level);
     if (H < 1 || W < 1) return fail(PSEG_EINVAL, "png: image of %d x %d pixels", H, W);
     if (channels != 1 && channels != 3) return fail(PSEG_EINVAL, "png: %d channels (1 = gray or 3 = RGB)", channels);
     if (band_rows < 0) return fail(PSEG_EINVAL, "png: band_rows %d (0 = default)", band_rows);
@@ -524,28 +803,46 @@ using namespace pseg;
 
 extern "C" {
 
-size_t pseg_png_bound(int H, int W, int channels, int band_rows) { return png_bound(H, W, channels, band_rows); }
+size_t pseg_png_bound_lv(int H, int W, int channels, int band_rows, int level) { return png_bound(H, W, channels, band_rows, level); }
+size_t pseg_png_bound(int H, int W, int channels, int band_rows) { return pseg_png_bound_lv(H, W, channels, band_rows, 0); }
 
-int pseg_png_encode_device(int device, const uint8_t* d_src, int H, int W, int channels, int band_rows, uint8_t* out, size_t cap,
-                           size_t* n_bytes, void* stream) {
+int pseg_png_code_lengths(const uint32_t* counts, int n, int limit, uint8_t* lengths) {
+    if (!counts || !lengths) return fail(PSEG_EINVAL, "NULL argument");
+    if (n < 1 || n > PNG_NSYM || limit < 1 || limit > 15) return fail(PSEG_EINVAL, "png_code_lengths: %d symbols (1..286), limit %d (1..15)", n, limit);
+    unsigned long long sum = 0;
+    int used = 0;
+    for (int s = 0; s < n; ++s) { sum += counts[s]; used += counts[s] != 0; }
+    if (sum >> 32) return fail(PSEG_EINVAL, "png_code_lengths: the counts sum to 2^32 or more");
+    if (used > (1 << limit)) return fail(PSEG_EINVAL, "png_code_lengths: %d used symbols have no code of at most %d bits", used, limit);
+    uint32_t ws[PNG_CLWS];
+    png_code_lengths(counts, n, limit, lengths, ws);
+    return PSEG_OK;
+}
+
+int pseg_png_encode_device_lv(int device, const uint8_t* d_src, int H, int W, int channels, int band_rows, int level, uint8_t* out, size_t cap,
+                              size_t* n_bytes, void* stream) {
     if (!d_src || !out || !n_bytes) return fail(PSEG_EINVAL, "NULL argument");
-    PSEG_TRY(png_check(H, W, channels, band_rows));
-    if (cap < png_bound(H, W, channels, band_rows))
-        return fail(PSEG_EINVAL, "png: output buffer of %zu bytes, pseg_png_bound is %zu", cap, png_bound(H, W, channels, band_rows));
+    PSEG_TRY(png_check(H, W, channels, band_rows, level));
+    if (cap < png_bound(H, W, channels, band_rows, level))
+        return fail(PSEG_EINVAL, "png: output buffer of %zu bytes, pseg_png_bound is %zu", cap, png_bound(H, W, channels, band_rows, level));
     PSEG_TRY(png_set_dev(device));
     PngSrcPlain src{d_src, W, channels};
     uint8_t* const host[4] = {out, nullptr, nullptr, nullptr};
     size_t* const nb[4] = {n_bytes, nullptr, nullptr, nullptr};
     const int ids[4] = {0, 0, 0, 0};
-    return png_run(device, src, H, W, channels, band_rows, 1, host, nb, ids, (hipStream_t)stream);
+    return png_run(device, src, H, W, channels, band_rows, level, 1, host, nb, ids, (hipStream_t)stream);
+}
+int pseg_png_encode_device(int device, const uint8_t* d_src, int H, int W, int channels, int band_rows, uint8_t* out, size_t cap,
+                           size_t* n_bytes, void* stream) {
+    return pseg_png_encode_device_lv(device, d_src, H, W, channels, band_rows, 0, out, cap, n_bytes, stream);
 }
 
-int pseg_masks_png_device_u8(int device, const uint8_t* d_pred, const uint8_t* d_binary, const uint8_t* d_lut, int n_lut, int H, int W,
-                             int band_rows, uint8_t* const out[4], const size_t cap[4], size_t n_bytes[4], void* stream) {
+int pseg_masks_png_device_u8_lv(int device, const uint8_t* d_pred, const uint8_t* d_binary, const uint8_t* d_lut, int n_lut, int H, int W,
+                                int band_rows, int level, uint8_t* const out[4], const size_t cap[4], size_t n_bytes[4], void* stream) {
     if (!d_pred || !d_binary || !d_lut || !out || !cap || !n_bytes) return fail(PSEG_EINVAL, "NULL argument");
     if (n_lut < 1 || n_lut > 256) return fail(PSEG_EINVAL, "n_lut %d out of range (1..256)", n_lut);
-    PSEG_TRY(png_check(H, W, 3, band_rows));
-    const size_t bound = png_bound(H, W, 3, band_rows);
+    PSEG_TRY(png_check(H, W, 3, band_rows, level));
+    const size_t bound = png_bound(H, W, 3, band_rows, level);
     uint8_t* host[4] = {nullptr, nullptr, nullptr, nullptr};
     size_t* nb[4] = {nullptr, nullptr, nullptr, nullptr};
     int ids[4] = {0, 0, 0, 0}, nout = 0;
@@ -559,30 +856,38 @@ int pseg_masks_png_device_u8(int device, const uint8_t* d_pred, const uint8_t* d
     if (nout == 0) return PSEG_OK;
     PSEG_TRY(png_set_dev(device));
     PngSrcMasks src{d_pred, d_binary, d_lut, n_lut, W};
-    return png_run(device, src, H, W, 3, band_rows, nout, host, nb, ids, (hipStream_t)stream);
+    return png_run(device, src, H, W, 3, band_rows, level, nout, host, nb, ids, (hipStream_t)stream);
+}
+int pseg_masks_png_device_u8(int device, const uint8_t* d_pred, const uint8_t* d_binary, const uint8_t* d_lut, int n_lut, int H, int W,
+                             int band_rows, uint8_t* const out[4], const size_t cap[4], size_t n_bytes[4], void* stream) {
+    return pseg_masks_png_device_u8_lv(device, d_pred, d_binary, d_lut, n_lut, H, W, band_rows, 0, out, cap, n_bytes, stream);
 }
 
-int pseg_png_encode(int device, const uint8_t* src, int H, int W, int channels, int band_rows, uint8_t* out, size_t cap, size_t* n_bytes) {
+int pseg_png_encode_lv(int device, const uint8_t* src, int H, int W, int channels, int band_rows, int level, uint8_t* out, size_t cap,
+                       size_t* n_bytes) {
     if (!src || !out || !n_bytes) return fail(PSEG_EINVAL, "NULL argument");
-    PSEG_TRY(png_check(H, W, channels, band_rows));
-    if (cap < png_bound(H, W, channels, band_rows))
-        return fail(PSEG_EINVAL, "png: output buffer of %zu bytes, pseg_png_bound is %zu", cap, png_bound(H, W, channels, band_rows));
+    PSEG_TRY(png_check(H, W, channels, band_rows, level));
+    if (cap < png_bound(H, W, channels, band_rows, level))
+        return fail(PSEG_EINVAL, "png: output buffer of %zu bytes, pseg_png_bound is %zu", cap, png_bound(H, W, channels, band_rows, level));
     PSEG_TRY(png_set_dev(device));
     const size_t n = (size_t)H * W * channels;
     uint8_t* d = nullptr;
     if (hipMalloc((void**)&d, n) != hipSuccess) { (void)hipGetLastError(); return fail(PSEG_ENOMEM, "hipMalloc failed in png_encode"); }
     int rc = PSEG_OK;
     if (hipMemcpy(d, src, n, hipMemcpyHostToDevice) != hipSuccess) rc = fail(PSEG_EHIP, "H2D copy failed");
-    if (rc == PSEG_OK) rc = pseg_png_encode_device(device, d, H, W, channels, band_rows, out, cap, n_bytes, nullptr);
+    if (rc == PSEG_OK) rc = pseg_png_encode_device_lv(device, d, H, W, channels, band_rows, level, out, cap, n_bytes, nullptr);
     (void)hipFree(d);
     return rc;
 }
+int pseg_png_encode(int device, const uint8_t* src, int H, int W, int channels, int band_rows, uint8_t* out, size_t cap, size_t* n_bytes) {
+    return pseg_png_encode_lv(device, src, H, W, channels, band_rows, 0, out, cap, n_bytes);
+}
 
-int pseg_masks_png(int device, const int64_t* pred, const uint8_t* binary, const uint8_t* lut, int n_lut, int H, int W, int band_rows,
-                   uint8_t* const out[4], const size_t cap[4], size_t n_bytes[4]) {
+int pseg_masks_png_lv(int device, const int64_t* pred, const uint8_t* binary, const uint8_t* lut, int n_lut, int H, int W, int band_rows,
+                      int level, uint8_t* const out[4], const size_t cap[4], size_t n_bytes[4]) {
     if (!pred || !binary || !lut || !out || !cap || !n_bytes) return fail(PSEG_EINVAL, "NULL argument");
     if (n_lut < 1 || n_lut > 256) return fail(PSEG_EINVAL, "n_lut %d out of range (1..256)", n_lut);
-    PSEG_TRY(png_check(H, W, 3, band_rows));
+    PSEG_TRY(png_check(H, W, 3, band_rows, level));
     PSEG_TRY(png_set_dev(device));
     const size_t n = (size_t)H * W;
     // labels outside the colour table are black (masks_kernel): on the uint8 map they become 255, which is black while the table
@@ -602,9 +907,13 @@ int pseg_masks_png(int device, const int64_t* pred, const uint8_t* binary, const
     if (hipMemcpy(d, lab.data(), n, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d + off_bin, binary, n, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(d + off_lut, lut, (size_t)n_lut * 3, hipMemcpyHostToDevice) != hipSuccess)
         rc = fail(PSEG_EHIP, "H2D copy failed");
-    if (rc == PSEG_OK) rc = pseg_masks_png_device_u8(device, d, d + off_bin, d + off_lut, n_lut, H, W, band_rows, out, cap, n_bytes, nullptr);
+    if (rc == PSEG_OK) rc = pseg_masks_png_device_u8_lv(device, d, d + off_bin, d + off_lut, n_lut, H, W, band_rows, level, out, cap, n_bytes, nullptr);
     (void)hipFree(d);
     return rc;
+}
+int pseg_masks_png(int device, const int64_t* pred, const uint8_t* binary, const uint8_t* lut, int n_lut, int H, int W, int band_rows,
+                   uint8_t* const out[4], const size_t cap[4], size_t n_bytes[4]) {
+    return pseg_masks_png_lv(device, pred, binary, lut, n_lut, H, W, band_rows, 0, out, cap, n_bytes);
 }
 
 }  // extern "C"

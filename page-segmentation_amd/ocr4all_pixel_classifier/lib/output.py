@@ -27,6 +27,8 @@ def generate_output_masks(data: SingleData, pred: np.ndarray, color_map: ColorMa
 
 #: write ".png" targets with the device encoder (pseg_masks_png); False: PIL writes every file, as the reference does
 DEVICE_PNG = True
+#: the device encoder's level: 0 = fixed Huffman codes, 1 = a dynamic code per band (smaller files, a second pass on the device)
+DEVICE_PNG_LEVEL = 0
 
 
 def output_paths(output_dir, data: SingleData):
@@ -56,15 +58,17 @@ def write_png_streams(paths, streams):
             f.write(stream)
 
 
-def output_data(output_dir, pred, data: SingleData, color_map):
+def output_data(output_dir, pred, data: SingleData, color_map, level=None):
     """lib/output.py:20-41.  A ".png" target (any letter case) is encoded on the device straight from the label map
-    (engine.masks_png: the RGB masks never exist); every other extension, and DEVICE_PNG = False, goes through PIL."""
+    (engine.masks_png: the RGB masks never exist); every other extension, and DEVICE_PNG = False, goes through PIL.
+    level: the device encoder's; None: DEVICE_PNG_LEVEL."""
     if pred.ndim == 3:
         assert pred.shape[0] == 1
         pred = pred[0]
     paths = output_paths(output_dir, data)
     if DEVICE_PNG and is_png_target(paths[0]):
-        png = engine.masks_png(pred, np.asarray(data.binary).astype(np.uint8), color_map.lut())
+        png = engine.masks_png(pred, np.asarray(data.binary).astype(np.uint8), color_map.lut(),
+                               level=DEVICE_PNG_LEVEL if level is None else level)
         write_png_streams(paths, (png["color"], png["overlay"], png["inverted"]))
         return
     from PIL import Image

@@ -37,7 +37,7 @@ class Predictor:
             ops.append(known[processor])
         return ops
 
-    def _chain(self, data: SingleData, want_masks: bool):
+    def _chain(self, data: SingleData, want_masks: bool, png_level=0):
         """predict -> [scale_to_original_shape] -> post-processors -> [masks] without the label map leaving the device
         (lib/predictor.py:32-54).  Returns (data', labels_u8, masks or None), or None when this page / these settings
         need the host chain (a post-processor that is not one of this package's, > 256 classes, no binary for the vote)."""
@@ -65,7 +65,8 @@ class Predictor:
         img = gray_to_rgb(image) if getattr(net, "_rgb", False) else image
         res = net.model.predict_chain(img, binary=np.asarray(binary).astype(np.uint8) if need_bin else None, out_shape=out_shape,
                                       post_ops=ops, exact_labels=net.exact == "labels", labels=None if want_masks else "u8",
-                                      lut=self.settings.color_map.lut() if want_masks else None, masks=want_masks)  # True or "png"
+                                      lut=self.settings.color_map.lut() if want_masks else None, masks=want_masks,  # True or "png"
+                                      png_level=png_level)
         return page, res["labels"], res["masks"]
 
     def _labels(self, data: SingleData):
@@ -121,13 +122,15 @@ class Predictor:
         data, _, pred = self._labels(data)
         return generate_output_masks(data, pred, self.settings.color_map)
 
-    def write_masks(self, data: SingleData, output_dir=None):
+    def write_masks(self, data: SingleData, output_dir=None, level=None):
         """predict_masks + output_data (lib/predictor.py:49-54, lib/output.py:20-41) for ".png" targets as ONE device call:
         predict -> [rescale] -> post-processors -> masks -> PNG (pseg_predict_chain_png); only the three PNG streams come
         down, and they are written to color/, overlay/ and inverted/ under output_dir (default: settings.output) with
         output_data's names.  Other extensions, output.DEVICE_PNG = False and pages that need the host chain go through
-        predict_masks' stages and output_data.  Returns the three paths."""
+        predict_masks' stages and output_data.  level: the device encoder's (0: fixed Huffman codes, 1: a dynamic code per
+        band, smaller files); None: output.DEVICE_PNG_LEVEL.  Returns the three paths."""
         from . import output
+        level = output.DEVICE_PNG_LEVEL if level is None else level
         output_dir = output_dir if output_dir is not None else self.settings.output
         if output_dir is None:
             raise Exception("write_masks needs an output directory")
@@ -140,10 +143,10 @@ class Predictor:
             for path, mask in zip(paths, (m.color, m.overlay, m.inverted_overlay)):
                 Image.fromarray(np.asarray(mask)).save(path)
             return paths
-        got = self._chain(data, want_masks="png")
+        got = self._chain(data, want_masks="png", png_level=level)
         if got is not None:
             output.write_png_streams(paths, got[2][:3])
             return paths
         data, _, pred = self._labels(data)
-        output.output_data(output_dir, np.asarray(pred), data, self.settings.color_map)
+        output.output_data(output_dir, np.asarray(pred), data, self.settings.color_map, level=level)
         return paths

@@ -28,6 +28,8 @@ EXPORTED_SYMBOLS = (
     "pseg_masks", "pseg_masks_device", "pseg_masks_device_u8", "pseg_bbox_fill_device_u8",
     "pseg_otsu_char_height",
     "pseg_png_bound", "pseg_png_encode_device", "pseg_masks_png_device_u8", "pseg_png_encode", "pseg_masks_png", "pseg_predict_chain_png",
+    "pseg_png_bound_lv", "pseg_png_encode_device_lv", "pseg_masks_png_device_u8_lv", "pseg_png_encode_lv", "pseg_masks_png_lv",
+    "pseg_predict_chain_png_lv", "pseg_png_code_lengths",
     "pseg_rescale_shape", "pseg_gaussian_kernel", "pseg_resize_nearest", "pseg_resize_nearest_device", "pseg_scale_image",
     "pseg_prepare_images", "pseg_affine_warp", "pseg_affine_warp_fill", "pseg_brightness_shift",
     "pseg_eval_confusion", "pseg_cc_label", "pseg_cc_tables",
@@ -145,6 +147,14 @@ def lib():
     L.pseg_png_encode.argtypes = [i, vp, i, i, i, i, vp, sz, c.POINTER(sz)]
     L.pseg_masks_png.argtypes = [i, vp, vp, vp, i, i, i, i, c.POINTER(vp), c.POINTER(sz), c.POINTER(sz)]
     L.pseg_predict_chain_png.argtypes = [vp, vp, i, i, i, i, vp, c.POINTER(i), i, c.c_uint, vp, vp, vp, i, c.POINTER(vp), c.POINTER(sz), c.POINTER(sz)]
+    L.pseg_png_bound_lv.argtypes = [i, i, i, i, i]
+    L.pseg_png_bound_lv.restype = sz
+    L.pseg_png_encode_device_lv.argtypes = [i, vp, i, i, i, i, i, vp, sz, c.POINTER(sz), vp]
+    L.pseg_masks_png_device_u8_lv.argtypes = [i, vp, vp, vp, i, i, i, i, i, c.POINTER(vp), c.POINTER(sz), c.POINTER(sz), vp]
+    L.pseg_png_encode_lv.argtypes = [i, vp, i, i, i, i, i, vp, sz, c.POINTER(sz)]
+    L.pseg_masks_png_lv.argtypes = [i, vp, vp, vp, i, i, i, i, i, c.POINTER(vp), c.POINTER(sz), c.POINTER(sz)]
+    L.pseg_predict_chain_png_lv.argtypes = [vp, vp, i, i, i, i, vp, c.POINTER(i), i, c.c_uint, vp, vp, vp, i, i, c.POINTER(vp), c.POINTER(sz), c.POINTER(sz)]
+    L.pseg_png_code_lengths.argtypes = [vp, i, i, vp]
     _LIB = L
     return L
 
@@ -394,12 +404,13 @@ class Engine:
     POST_OPS = {"cc_vote": 1, "bbox": 2}
 
     def predict_chain(self, image, binary=None, out_shape=None, post_ops=(), exact_labels=False, labels="u8", lut=None,
-                      masks=False):
+                      masks=False, png_level=0):
         """The Predictor chain on the device (pseg_predict_chain; lib/predictor.py:32-54): predict -> [nearest resize of
         the label map to out_shape] -> post-processors ("cc_vote" / "bbox", in order) -> [the four masks].  `binary` must
         have the label map's final shape.  Returns {"labels": uint8 or int64 map or None, "masks": (color, overlay,
         inverted, fg_color) or None}; the arrays live in recycled page-locked memory.  masks="png": the four masks come back as
-        PNG streams (bytes objects) encoded on the device (pseg_predict_chain_png), decoding to the arrays masks=True returns."""
+        PNG streams (bytes objects) encoded on the device (pseg_predict_chain_png_lv, at `png_level`), decoding to the arrays
+        masks=True returns."""
         img = np.ascontiguousarray(image, dtype=np.uint8)
         H, W = img.shape[:2]
         Ho, Wo = (int(out_shape[0]), int(out_shape[1])) if out_shape is not None else (0, 0)
@@ -421,10 +432,10 @@ class Engine:
         outs = [None] * 4
         if masks == "png":
             t = np.ascontiguousarray(lut, dtype=np.uint8).reshape(-1, 3)
-            bufs, P, caps, sizes = _png_buffers(Hl, Wl, 3, 0, [True] * 4)
-            _check(lib().pseg_predict_chain_png(self._h, _ptr(img), H, W, Ho, Wo, _ptr(b), ops, len(post_ops), 1 if exact_labels else 0,
-                                                _ptr(lab) if labels == "i64" else None, _ptr(lab) if labels == "u8" else None,
-                                                _ptr(t), t.shape[0], P, caps, sizes))
+            bufs, P, caps, sizes = _png_buffers(Hl, Wl, 3, 0, [True] * 4, png_level)
+            _check(lib().pseg_predict_chain_png_lv(self._h, _ptr(img), H, W, Ho, Wo, _ptr(b), ops, len(post_ops), 1 if exact_labels else 0,
+                                                   _ptr(lab) if labels == "i64" else None, _ptr(lab) if labels == "u8" else None,
+                                                   _ptr(t), t.shape[0], int(png_level), P, caps, sizes))
             return {"labels": lab, "masks": tuple(bufs[k][:sizes[k]].tobytes() for k in range(4))}
         if masks:
             t = np.ascontiguousarray(lut, dtype=np.uint8).reshape(-1, 3)
@@ -665,25 +676,35 @@ def masks(pred, binary, lut, device=0):
 MASK_NAMES = ("color", "overlay", "inverted", "fg_color")
 
 
-def png_bound(H, W, channels=3, band_rows=0):
-    """Upper bound of the encoded size of an (H,W[,3]) image (pseg_png_bound: arithmetic, no device)."""
-    n = int(lib().pseg_png_bound(int(H), int(W), int(channels), int(band_rows)))
+def png_bound(H, W, channels=3, band_rows=0, level=0):
+    """Upper bound of the encoded size of an (H,W[,3]) image (pseg_png_bound_lv: arithmetic, no device)."""
+    n = int(lib().pseg_png_bound_lv(int(H), int(W), int(channels), int(band_rows), int(level)))
     if n == 0:
-        raise PsegError("png_bound: bad shape (%r, %r), channels %r or band_rows %r" % (H, W, channels, band_rows))
+        raise PsegError("png_bound: bad shape (%r, %r), channels %r, band_rows %r or level %r" % (H, W, channels, band_rows, level))
     return n
 
 
-def _png_buffers(H, W, channels, band_rows, wanted):
+def png_code_lengths(counts, limit):
+    """Code lengths of a prefix code of at most `limit` bits for the symbol counts (pseg_png_code_lengths: the host
+    instantiation of the function the level-1 band kernel runs; arithmetic, no device) -> uint8 array, 0 where the count is 0."""
+    cnt = np.ascontiguousarray(counts, dtype=np.uint32).ravel()
+    out = np.zeros(cnt.size, np.uint8)
+    _check(lib().pseg_png_code_lengths(_ptr(cnt), int(cnt.size), int(limit), _ptr(out)))
+    return out
+
+
+def _png_buffers(H, W, channels, band_rows, wanted, level=0):
     """Page-locked output buffers of the bound's size for the wanted streams + the ctypes arrays the C entries take."""
-    n = png_bound(H, W, channels, band_rows)
+    n = png_bound(H, W, channels, band_rows, level)
     bufs = [pinned_empty_pooled((n,), np.uint8) if w else None for w in wanted]
     P = (ctypes.c_void_p * 4)(*[None if b is None else b.ctypes.data for b in bufs])
     caps = (ctypes.c_size_t * 4)(*[0 if b is None else n for b in bufs])
     return bufs, P, caps, (ctypes.c_size_t * 4)()
 
 
-def png_encode(array, band_rows=0, device=0):
-    """uint8 (H,W) or (H,W,3) -> the bytes of a PNG file (8-bit gray / truecolour), encoded on the GPU (pseg_png_encode)."""
+def png_encode(array, band_rows=0, device=0, level=0):
+    """uint8 (H,W) or (H,W,3) -> the bytes of a PNG file (8-bit gray / truecolour), encoded on the GPU (pseg_png_encode_lv).
+    level 0: fixed Huffman codes; level 1: a dynamic code per band where it is smaller (include/pseg.h)."""
     a = np.asarray(array)
     if a.dtype != np.uint8 or a.ndim not in (2, 3) or (a.ndim == 3 and a.shape[2] != 3) or a.size == 0:
         raise PsegError("png_encode takes a non-empty uint8 (H,W) or (H,W,3) array, got %s %r" % (a.dtype, a.shape))
@@ -691,16 +712,16 @@ def png_encode(array, band_rows=0, device=0):
     H, W = a.shape[:2]
     ch = 1 if a.ndim == 2 else 3
     L = lib()
-    cap = int(L.pseg_png_bound(H, W, ch, int(band_rows)))
+    cap = int(L.pseg_png_bound_lv(H, W, ch, int(band_rows), int(level)))
     out = pinned_empty_pooled((max(cap, 1),), np.uint8)
     n = ctypes.c_size_t()
-    _check(L.pseg_png_encode(int(device), _ptr(a), H, W, ch, int(band_rows), _ptr(out), cap, ctypes.byref(n)))
+    _check(L.pseg_png_encode_lv(int(device), _ptr(a), H, W, ch, int(band_rows), int(level), _ptr(out), cap, ctypes.byref(n)))
     return out[:n.value].tobytes()
 
 
-def masks_png(pred, binary, lut, which=("color", "overlay", "inverted"), band_rows=0, device=0):
+def masks_png(pred, binary, lut, which=("color", "overlay", "inverted"), band_rows=0, device=0, level=0):
     """generate_output_masks (lib/output.py:44-60) straight to PNG streams: {name: bytes} for the names in `which` (of "color",
-    "overlay", "inverted", "fg_color"), each decoding to the array masks() returns (pseg_masks_png)."""
+    "overlay", "inverted", "fg_color"), each decoding to the array masks() returns (pseg_masks_png_lv; `level` as in png_encode)."""
     for w in which:
         if w not in MASK_NAMES:
             raise PsegError("unknown mask %r (one of %r)" % (w, MASK_NAMES))
@@ -711,8 +732,8 @@ def masks_png(pred, binary, lut, which=("color", "overlay", "inverted"), band_ro
         raise PsegError("pred %r and binary %r must be non-empty (H,W) arrays of one shape" % (p.shape, b.shape))
     H, W = p.shape
     L = lib()
-    bufs, P, caps, sizes = _png_buffers(H, W, 3, band_rows, [m in which for m in MASK_NAMES])
-    _check(L.pseg_masks_png(int(device), _ptr(p), _ptr(b), _ptr(t), t.shape[0], H, W, int(band_rows), P, caps, sizes))
+    bufs, P, caps, sizes = _png_buffers(H, W, 3, band_rows, [m in which for m in MASK_NAMES], level)
+    _check(L.pseg_masks_png_lv(int(device), _ptr(p), _ptr(b), _ptr(t), t.shape[0], H, W, int(band_rows), int(level), P, caps, sizes))
     return {m: bufs[k][:sizes[k]].tobytes() for k, m in enumerate(MASK_NAMES) if m in which}
 
 

@@ -7,7 +7,10 @@ On synthetic pages of 2048x1536 (3 classes) and 4096x3072 (6 classes) -- labels 
       as GB/s over the raw bytes of the three masks;
   (c) the whole page, bf16 fcn_skip engine + cc_majority vote: Predictor.write_masks (one pseg_predict_chain_png call) against
       Predictor.predict_single + output_data (which builds the masks and saves them through PIL: output.DEVICE_PNG = False), both into --tmp (a tmpfs directory).
-Wall ms per page after warm-up; (a) and (b), and the two sides of (c), alternate three times in one process.  Writes --out."""
+Wall ms per page after warm-up; (a) and (b), and the two sides of (c), alternate three times in one process.  The device legs
+(b), (d) and (c) run at every level of --level (0: fixed Huffman codes, 1: a dynamic code per band), the levels alternating inside
+each of the three rounds; --band-rows sets the band of (b) and (d) (0: the level's default).  The size table has a row per level
+and, for level 1, one per band size of 16 / 64 / 256 KB of filtered bytes, each with leg (d)'s time.  Writes --out."""
 import argparse, ctypes, io, os, shutil, sys, time
 os.environ.setdefault("PSEG_PLAN_FROM_ENV", "1")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -25,8 +28,11 @@ def main():
     ap.add_argument("--sizes", default="2048x1536x3,4096x3072x6")
     ap.add_argument("--skip-pil", action="store_true", help="device legs only (profiler runs)")
     ap.add_argument("--tmp", default="/dev/shm/pseg_bench_png")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "png_device.txt"))
+    ap.add_argument("--level", default="0,1", help="levels of the device legs, comma-separated")
+    ap.add_argument("--band-rows", type=int, default=0, help="rows per band of legs (b) and (d); 0: the level's default")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "png_dynamic.txt"))
     a = ap.parse_args()
+    levels = [int(v) for v in a.level.split(",")]
     import torch
     torch.cuda.is_available()               # torch's bundled HIP runtime initialises first (as bench.py)
     from PIL import Image
@@ -71,38 +77,52 @@ def main():
                 out.append(buf.tell())
             sizes["pil%s" % ("" if level is None else level)] = out
 
-        def dev():
-            got = E.masks_png(pred, binary, lut)
-            sizes["device"] = [len(got[n]) for n in NAMES]
+        def dev(level):
+            got = E.masks_png(pred, binary, lut, band_rows=a.band_rows, level=level)
+            sizes["level %d" % level] = [len(got[n]) for n in NAMES]
 
         # the streams decode to the parent path's arrays
         ref = E.masks(pred, binary, lut)
-        got = E.masks_png(pred, binary, lut)
-        for n, m in zip(NAMES, ref):
-            assert np.array_equal(np.asarray(Image.open(io.BytesIO(got[n]))), m), n
+        for level in levels:
+            got = E.masks_png(pred, binary, lut, band_rows=a.band_rows, level=level)
+            for n, m in zip(NAMES, ref):
+                assert np.array_equal(np.asarray(Image.open(io.BytesIO(got[n]))), m), (n, level)
         # (d) resident inputs
         d_pred = torch.from_numpy(pred.astype(np.uint8)).cuda()
         d_bin = torch.from_numpy(binary).cuda()
         d_lut = torch.from_numpy(np.ascontiguousarray(lut)).cuda()
-        cap = E.png_bound(H, W, 3, 0)
+        cap = max(E.png_bound(H, W, 3, br, lv) for lv in (0, 1) for br in (0, 1, a.band_rows))
         bufs = [E.pinned_empty((cap,), np.uint8) for _ in range(3)]
         P = (ctypes.c_void_p * 4)(bufs[0].ctypes.data, bufs[1].ctypes.data, bufs[2].ctypes.data, None)
         caps = (ctypes.c_size_t * 4)(cap, cap, cap, 0)
         nb = (ctypes.c_size_t * 4)()
         torch.cuda.synchronize()
 
-        def resident():
-            E._check(E.lib().pseg_masks_png_device_u8(0, ctypes.c_void_p(d_pred.data_ptr()), ctypes.c_void_p(d_bin.data_ptr()),
-                                                      ctypes.c_void_p(d_lut.data_ptr()), C, H, W, 0, P, caps, nb, None))
+        def resident(level, band_rows=None):
+            E._check(E.lib().pseg_masks_png_device_u8_lv(0, ctypes.c_void_p(d_pred.data_ptr()), ctypes.c_void_p(d_bin.data_ptr()),
+                                                         ctypes.c_void_p(d_lut.data_ptr()), C, H, W, a.band_rows if band_rows is None else band_rows,
+                                                         level, P, caps, nb, None))
 
         rows = []
         for r in range(3):
             if not a.skip_pil:
                 rows.append(("(a) masks + 3 x PIL save, level 6, run %d" % (r + 1), timed(pil)))
                 rows.append(("(a) masks + 3 x PIL save, level 1, run %d" % (r + 1), timed(lambda: pil(1))))
-            rows.append(("(b) masks_png, run %d" % (r + 1), timed(dev, 4 * a.steps)))
-        res = timed(resident, 8 * a.steps)
-        rows.append(("(d) resident label map -> 3 streams", res))
+            for lv in levels:
+                rows.append(("(b) masks_png, level %d, run %d" % (lv, r + 1), timed(lambda: dev(lv), 4 * a.steps)))
+        res = {}
+        for r in range(3):
+            for lv in levels:
+                res[lv] = timed(lambda: resident(lv), 8 * a.steps)
+                rows.append(("(d) resident label map -> 3 streams, level %d, run %d" % (lv, r + 1), res[lv]))
+        band = {}
+        if 1 in levels:                         # level 1 at three band sizes: bytes and leg (d)
+            for kb in (16, 64, 256):
+                br = max(1, kb * 1024 // (3 * W + 1))
+                got = E.masks_png(pred, binary, lut, band_rows=br, level=1)
+                for n, m in zip(NAMES, ref):
+                    assert np.array_equal(np.asarray(Image.open(io.BytesIO(got[n]))), m), (n, kb)
+                band[kb] = (br, [len(got[n]) for n in NAMES], timed(lambda: resident(1, br), 8 * a.steps))
         # (c) the whole page
         cm = ColorMap({str(tuple(int(v) for v in LUT[k])): [k, "c%d" % k] for k in range(C)})
         net = Network("Predict", n_classes=C, exact=False)
@@ -122,16 +142,22 @@ def main():
         for r in range(3):
             if not a.skip_pil:
                 rows.append(("(c) predict_single + output_data (PIL), run %d" % (r + 1), timed(parent_page)))
-            rows.append(("(c) Predictor.write_masks, run %d" % (r + 1), timed(lambda: pr.write_masks(data), 4 * a.steps)))
+            for lv in levels:
+                rows.append(("(c) Predictor.write_masks, level %d, run %d" % (lv, r + 1), timed(lambda: pr.write_masks(data, level=lv), 4 * a.steps)))
         shutil.rmtree(a.tmp, ignore_errors=True)
         net.model.close()
         lines += ["%dx%d page, %d classes: raw RGB %.1f MB per mask, three masks %.1f MB" % (H, W, C, raw / 1e6, 3 * raw / 1e6),
                   "wall ms per page (median / min / max after %d warm-up)" % a.warmup, ""]
-        lines += ["%-48s %9.2f %9.2f %9.2f" % ((name,) + t) for name, t in rows]
-        lines += ["", "bytes per mask (color / overlay / inverted):"]
-        lines += ["  %-10s %s" % (k, "  ".join("%9d" % v for v in sizes[k])) for k in ("pil", "pil1", "device") if k in sizes]
-        lines += ["(d) over the raw bytes of the three masks: %.1f GB/s (median %.2f ms; includes framing, the size read-back and the download)"
-                  % (3 * raw / res[0] / 1e6, res[0]), ""]
+        lines += ["%-56s %9.2f %9.2f %9.2f" % ((name,) + t) for name, t in rows]
+        lines += ["", "bytes per mask (color / overlay / inverted), band_rows %d:" % a.band_rows]
+        lines += ["  %-10s %s" % (k, "  ".join("%9d" % v for v in sizes[k])) for k in ("pil", "pil1", "level 0", "level 1") if k in sizes]
+        if band:
+            lines += ["level 1 by band size (rows; bytes per mask; (d) median / min / max ms):"]
+            lines += ["  %3d KB %4d rows  %s   %9.2f %9.2f %9.2f" % ((kb, band[kb][0], "  ".join("%9d" % v for v in band[kb][1])) + band[kb][2])
+                      for kb in sorted(band)]
+        lines += ["(d), level %d, over the raw bytes of the three masks: %.1f GB/s (median %.2f ms; includes framing, the size read-back and the download)"
+                  % (lv, 3 * raw / res[lv][0] / 1e6, res[lv][0]) for lv in levels]
+        lines += [""]
     text = "\n".join(lines) + "\n"
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
