@@ -40,7 +40,8 @@ enum {
     PSEG_ENOTFOUND = -2, /* unknown weight name */
     PSEG_EHIP = -3,     /* HIP runtime error (message has the hipError string) */
     PSEG_ENOMEM = -4,
-    PSEG_EUNSUPPORTED = -5
+    PSEG_EUNSUPPORTED = -5,
+    PSEG_ECALLBACK = -6 /* a caller's callback asked to stop (pseg_predict_chain_pages_png's sink) */
 };
 
 typedef struct pseg_engine pseg_engine;
@@ -405,6 +406,40 @@ int pseg_masks_png_lv(int device, const int64_t* pred, const uint8_t* binary, co
 int pseg_predict_chain_png_lv(pseg_engine* e, const uint8_t* img, int H, int W, int Ho, int Wo, const uint8_t* binary,
                               const int* post_ops, int n_post, unsigned flags, int64_t* labels, uint8_t* labels_u8,
                               const uint8_t* lut, int n_lut, int level, uint8_t* const png[4], const size_t cap[4], size_t n_bytes[4]);
+/* Predictor.predict's page loop (lib/predictor.py:27-30) over the whole chain, to PNG: a list of pages in, their mask PNG streams
+ * (and, with bit 4 of `want`, the final uint8 label maps) out through `sink`.  Stages, post-processors, `flags`, `lut` and `level`
+ * are pseg_predict_chain_png_lv's, and every stream and label map has that call's bytes for the page alone.  Ho / Wo: NULL, or per page
+ * the final shape (0: no rescale); binaries[i]: the page's ink map in its final shape (the array, or an entry, may be NULL where
+ * neither the vote nor a mask needs it).  All pages are checked before any device work starts (PSEG_EINVAL names the page).
+ *
+ * The list is cut into units by pseg_chain_units (at most `unit_cap` pages; 0: pseg_predict_batch's choice for the list).  A unit's
+ * pages go up together; a bf16 engine without PSEG_CHAIN_EXACT_LABELS runs their network stage over page slots
+ * (pseg_predict_pages_device's path), any other engine page after page; resize, vote and boxes follow per page on the engine's
+ * stream; then ONE set of encoder launches writes all requested masks of all pages of the unit.  Two staging sets and
+ * pseg_predict_batch's two copy streams: unit u + 1 is enqueued before the host waits for unit u's sizes, the downloads carry
+ * exactly the encoded bytes, and the host fills the chunk CRCs of unit u - 1 and hands it to `sink` while the device works.
+ *
+ * sink(user, page, which, data, n_bytes): called on the calling thread only (no thread is created), in page order and `which`
+ * ascending (0 color, 1 overlay, 2 inverted, 3 fg_color: PNG streams; 4: the uint8 label map); `data` is valid during the call
+ * only.  A non-zero return stops the call: PSEG_ECALLBACK.  Every return -- also an error in the middle -- leaves the streams
+ * drained and the engine usable.  The call ends with pseg_engine_status's check: on PSEG_EHIP the pages delivered by it are not to
+ * be trusted.  n_pages == 0: PSEG_OK, no sink call.
+ *
+ * The staging sets (device: pages, label maps, binarisations, the encoder's workspace for a unit; page-locked host: uploads of
+ * pageable arrays and the encoded streams, grown to the largest unit's actual bytes, not to pseg_png_bound x pages) belong to the
+ * engine.  pseg_engine_trim frees their memory (device and page-locked); their events, the colour table and pseg_predict_chain's
+ * own single-page buffers stay until pseg_destroy. */
+typedef int (*pseg_chain_sink)(void* user, int page, int which, const uint8_t* data, size_t n_bytes);
+int pseg_predict_chain_pages_png(pseg_engine* e, int n_pages, const uint8_t* const* imgs, const int* H, const int* W,
+                                 const int* Ho, const int* Wo, const uint8_t* const* binaries,
+                                 const int* post_ops, int n_post, unsigned flags,
+                                 const uint8_t* lut, int n_lut, int level, unsigned want, int unit_cap,
+                                 pseg_chain_sink sink, void* user);
+/* How that call cuts its list (host logic only): pseg_batch_units' rule with (H, W, Ho, Wo) as a page's shape; Ho / Wo NULL: exactly
+ * pseg_batch_units. */
+int pseg_chain_units(int n_pages, const int* H, const int* W, const int* Ho, const int* Wo, int cap,
+                     int* unit_first, int* unit_count, int max_units);
+
 /* The code lengths level 1 uses, on the host (pure arithmetic, no device; the device runs the same function): counts[n] ->
  * lengths[n], 0 exactly for a count of 0, none above `limit`, a complete prefix code when two or more symbols occur (one symbol:
  * length 1), the Huffman code's lengths whenever those fit the limit.  n in 1..286, limit in 1..15, at most 2^limit symbols in

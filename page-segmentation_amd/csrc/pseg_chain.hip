@@ -7,16 +7,34 @@
 // binarisation go up once, and only what the caller asked for comes down -- by DMA straight into the caller's arrays when
 // those are page-locked (pseg_host_alloc / the Python shim's pooled pinned arrays).
 #include <algorithm>
+#include <cstring>
 
 #include "pseg_common.h"
 
 namespace pseg {
+
+// One of the two staging sets of the page chain (pseg_predict_chain_pages_png): everything a unit of same-shape pages touches.
+struct PagesSet {
+    enum { IMG = 0, LAB = 1, LAB2 = 2, BIN = 3, PNG = 4, NDEV = 5 };
+    uint8_t* d[NDEV] = {nullptr, nullptr, nullptr, nullptr, nullptr};      // pages / network labels / resize + bbox ping-pong / binarisations / encoder workspace
+    size_t d_bytes[NDEV] = {0, 0, 0, 0, 0};
+    uint8_t* h_in = nullptr;            // page-locked: pages and binarisations of callers with pageable arrays
+    uint8_t* h_out = nullptr;           // page-locked: the unit's encoded streams (+ label maps), grown to the bytes units really have
+    unsigned long long* h_tot = nullptr;   // page-locked: [pages][4] stream sizes
+    size_t h_in_bytes = 0, h_out_bytes = 0, h_tot_bytes = 0;
+    hipEvent_t up = nullptr, done = nullptr, down = nullptr;   // uploads landed / compute + sizes landed / downloads landed
+};
+struct ChainPagesState {
+    PagesSet set[2];
+    uint8_t* d_lut = nullptr;
+};
 
 struct ChainState {
     hipStream_t s_aux = nullptr;        // uploads of the binarisation / colour table beside the network's kernels
     hipEvent_t ev_aux = nullptr;
     uint8_t* d_buf[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     size_t cap[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    ChainPagesState* pages = nullptr;
 };
 enum { CB_IMG = 0, CB_LAB = 1, CB_LAB2 = 2, CB_BIN = 3, CB_MASKS = 4, CB_LUT = 5, CB_I64 = 6 };
 
@@ -30,9 +48,37 @@ static int censure(ChainState& c, int slot, size_t bytes) {
     return PSEG_OK;
 }
 
+// the staging sets' memory (device and page-locked); the events stay.  The caller has waited for the device.
+static void pages_release(ChainPagesState& p) {
+    for (PagesSet& s : p.set) {
+        for (int i = 0; i < PagesSet::NDEV; ++i) { if (s.d[i]) (void)hipFree(s.d[i]); s.d[i] = nullptr; s.d_bytes[i] = 0; }
+        if (s.h_in) (void)hipHostFree(s.h_in);
+        if (s.h_out) (void)hipHostFree(s.h_out);
+        if (s.h_tot) (void)hipHostFree(s.h_tot);
+        s.h_in = s.h_out = nullptr;
+        s.h_tot = nullptr;
+        s.h_in_bytes = s.h_out_bytes = s.h_tot_bytes = 0;
+    }
+}
+
+void chain_trim(Engine& e) {
+    auto* c = (ChainState*)e.chain;
+    if (c && c->pages) pages_release(*c->pages);
+}
+
 void chain_free(Engine& e) {
     auto* c = (ChainState*)e.chain;
     if (!c) return;
+    if (c->pages) {
+        pages_release(*c->pages);
+        for (PagesSet& s : c->pages->set) {
+            if (s.up) (void)hipEventDestroy(s.up);
+            if (s.done) (void)hipEventDestroy(s.done);
+            if (s.down) (void)hipEventDestroy(s.down);
+        }
+        if (c->pages->d_lut) (void)hipFree(c->pages->d_lut);
+        delete c->pages;
+    }
     for (int i = 0; i < 8; ++i) if (c->d_buf[i]) (void)hipFree(c->d_buf[i]);
     if (c->ev_aux) (void)hipEventDestroy(c->ev_aux);
     if (c->s_aux) (void)hipStreamDestroy(c->s_aux);
@@ -51,6 +97,34 @@ using namespace pseg;
 // the masks of a chain call as PNG streams (pseg_predict_chain_png) instead of raw arrays
 struct ChainPng { uint8_t* const* out; const size_t* cap; size_t* n_bytes; int level; };
 
+// The argument checks of a chain call, shared by the single-page entries (page < 0) and the page list (the message names the page).
+struct ChainReq { bool resize, want_masks, need_bin; int Hl, Wl; };
+static int chain_check(const Engine& e, int page, const uint8_t* img, int H, int W, int Ho, int Wo, const uint8_t* binary, const int* post_ops,
+                       int n_post, unsigned flags, bool want_masks, bool want_png, const uint8_t* lut, int n_lut, int level, ChainReq* r) {
+    char at[32] = "";
+    if (page >= 0) snprintf(at, sizeof at, "page %d: ", page);
+    if (!img) return fail(PSEG_EINVAL, "%sNULL argument", at);
+    if (H <= 0 || W <= 0 || n_post < 0 || (n_post > 0 && !post_ops)) return fail(PSEG_EINVAL, "%sbad argument", at);
+    if (e.n_classes > 256) return fail(PSEG_EUNSUPPORTED, "the chain keeps a uint8 label map (<= 256 classes)");
+    if (flags & ~(unsigned)PSEG_CHAIN_EXACT_LABELS) return fail(PSEG_EINVAL, "unknown flag bits 0x%x", flags);
+    r->resize = Ho > 0 && Wo > 0 && (Ho != H || Wo != W);
+    r->Hl = r->resize ? Ho : H;
+    r->Wl = r->resize ? Wo : W;
+    r->want_masks = want_masks;
+    r->need_bin = want_masks;
+    for (int i = 0; i < n_post; ++i) {
+        if (post_ops[i] != PSEG_POST_CC_VOTE && post_ops[i] != PSEG_POST_BBOX) return fail(PSEG_EINVAL, "unknown post-processor id %d", post_ops[i]);
+        r->need_bin |= post_ops[i] == PSEG_POST_CC_VOTE;
+    }
+    if (r->need_bin && !binary) return fail(PSEG_EINVAL, "%sthe vote / the masks need the binarisation", at);
+    if (want_masks && (!lut || n_lut < 1)) return fail(PSEG_EINVAL, "the masks need the colour table");
+    if (want_png) {
+        if (n_lut > 256) return fail(PSEG_EINVAL, "n_lut %d out of range (1..256)", n_lut);
+        if (level != 0 && level != 1) return fail(PSEG_EINVAL, "png: level %d (0 = fixed Huffman codes, 1 = dynamic codes per band)", level);
+    }
+    return PSEG_OK;
+}
+
 static int chain_run(pseg_engine* h, const uint8_t* img, int H, int W, int Ho, int Wo, const uint8_t* binary,
                      const int* post_ops, int n_post, unsigned flags, int64_t* labels, uint8_t* labels_u8,
                      const uint8_t* lut, int n_lut, uint8_t* color, uint8_t* overlay, uint8_t* inverted,
@@ -58,23 +132,13 @@ static int chain_run(pseg_engine* h, const uint8_t* img, int H, int W, int Ho, i
     if (!h || !img) return fail(PSEG_EINVAL, "NULL argument");
     KnobScope knob_scope(h->e);
     Engine& e = h->e;
-    if (H <= 0 || W <= 0 || n_post < 0 || (n_post > 0 && !post_ops)) return fail(PSEG_EINVAL, "bad argument");
-    if (e.n_classes > 256) return fail(PSEG_EUNSUPPORTED, "the chain keeps a uint8 label map (<= 256 classes)");
-    if (flags & ~(unsigned)PSEG_CHAIN_EXACT_LABELS) return fail(PSEG_EINVAL, "unknown flag bits 0x%x", flags);
-    const bool resize = Ho > 0 && Wo > 0 && (Ho != H || Wo != W);
-    const int Hl = resize ? Ho : H, Wl = resize ? Wo : W;
     const bool want_png = png && (png->out[0] || png->out[1] || png->out[2] || png->out[3]);
     const bool want_masks = color || overlay || inverted || fg_color || want_png;
-    bool need_bin = want_masks;
-    for (int i = 0; i < n_post; ++i) {
-        if (post_ops[i] != PSEG_POST_CC_VOTE && post_ops[i] != PSEG_POST_BBOX) return fail(PSEG_EINVAL, "unknown post-processor id %d", post_ops[i]);
-        need_bin |= post_ops[i] == PSEG_POST_CC_VOTE;
-    }
-    if (need_bin && !binary) return fail(PSEG_EINVAL, "the vote / the masks need the binarisation");
-    if (want_masks && (!lut || n_lut < 1)) return fail(PSEG_EINVAL, "the masks need the colour table");
+    ChainReq req;
+    PSEG_TRY(chain_check(e, -1, img, H, W, Ho, Wo, binary, post_ops, n_post, flags, want_masks, want_png, lut, n_lut, png ? png->level : 0, &req));
+    const bool resize = req.resize, need_bin = req.need_bin;
+    const int Hl = req.Hl, Wl = req.Wl;
     if (want_png) {
-        if (n_lut > 256) return fail(PSEG_EINVAL, "n_lut %d out of range (1..256)", n_lut);
-        if (png->level != 0 && png->level != 1) return fail(PSEG_EINVAL, "png: level %d (0 = fixed Huffman codes, 1 = dynamic codes per band)", png->level);
         const size_t bound = pseg_png_bound_lv(Hl, Wl, 3, 0, png->level);
         for (int k = 0; k < 4; ++k)
             if (png->out[k] && png->cap[k] < bound) return fail(PSEG_EINVAL, "png: output buffer %d of %zu bytes, pseg_png_bound is %zu", k, png->cap[k], bound);
@@ -170,4 +234,298 @@ extern "C" int pseg_predict_chain_png(pseg_engine* h, const uint8_t* img, int H,
                                       const int* post_ops, int n_post, unsigned flags, int64_t* labels, uint8_t* labels_u8,
                                       const uint8_t* lut, int n_lut, uint8_t* const png[4], const size_t cap[4], size_t n_bytes[4]) {
     return pseg_predict_chain_png_lv(h, img, H, W, Ho, Wo, binary, post_ops, n_post, flags, labels, labels_u8, lut, n_lut, 0, png, cap, n_bytes);
+}
+
+// ---- a page list through the chain to PNG streams (lib/predictor.py:27-30 x :49-54) ------------------------------------------
+static int pages_ensure_dev(PagesSet& s, int slot, size_t bytes) {
+    if (s.d_bytes[slot] >= bytes && s.d[slot]) return PSEG_OK;
+    if (s.d[slot]) (void)hipFree(s.d[slot]);
+    s.d[slot] = nullptr;
+    s.d_bytes[slot] = 0;
+    if (hipMalloc((void**)&s.d[slot], bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(PSEG_ENOMEM, "hipMalloc(page chain staging, %zu bytes) failed", bytes);
+    }
+    s.d_bytes[slot] = bytes;
+    return PSEG_OK;
+}
+template <class T>
+static int pages_ensure_host(T** p, size_t* cap, size_t bytes) {
+    if (*cap >= bytes && *p) return PSEG_OK;
+    if (*p) (void)hipHostFree(*p);
+    *p = nullptr;
+    *cap = 0;
+    if (hipHostMalloc((void**)p, bytes, hipHostMallocDefault) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(PSEG_ENOMEM, "hipHostMalloc(page chain staging, %zu bytes) failed", bytes);
+    }
+    *cap = bytes;
+    return PSEG_OK;
+}
+static bool pages_is_pinned(const void* p) {
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return false; }
+    return at.type == hipMemoryTypeHost;
+}
+static inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+extern "C" int pseg_chain_units(int n_pages, const int* H, const int* W, const int* Ho, const int* Wo, int cap, int* unit_first, int* unit_count,
+                                int max_units) {
+    if (n_pages < 0 || (n_pages > 0 && (!H || !W)) || cap < 1) return fail(PSEG_EINVAL, "bad argument");
+    std::vector<int> ub, ug;
+    plan_units(n_pages, H, W, Ho, Wo, cap, ub, ug);
+    if ((int)ub.size() > max_units && (unit_first || unit_count)) return fail(PSEG_EINVAL, "%zu units, room for %d", ub.size(), max_units);
+    for (size_t u = 0; u < ub.size(); ++u) {
+        if (unit_first) unit_first[u] = ub[u];
+        if (unit_count) unit_count[u] = ug[u];
+    }
+    return (int)ub.size();
+}
+
+extern "C" int pseg_predict_chain_pages_png(pseg_engine* h, int n, const uint8_t* const* imgs, const int* H, const int* W, const int* Ho,
+                                            const int* Wo, const uint8_t* const* binaries, const int* post_ops, int n_post, unsigned flags,
+                                            const uint8_t* lut, int n_lut, int level, unsigned want, int unit_cap, pseg_chain_sink sink,
+                                            void* user) {
+    if (!h) return fail(PSEG_EINVAL, "NULL engine");
+    KnobScope knob_scope(h->e);
+    Engine& e = h->e;
+    if (n < 0 || (n > 0 && (!imgs || !H || !W))) return fail(PSEG_EINVAL, "bad argument");
+    if (!sink) return fail(PSEG_EINVAL, "NULL sink");
+    if (want == 0 || (want & ~31u)) return fail(PSEG_EINVAL, "want 0x%x: bits 0..3 select the masks, bit 4 the label map, at least one", want);
+    if (unit_cap < 0 || unit_cap > 64) return fail(PSEG_EINVAL, "unit_cap %d (0 = default, at most 64)", unit_cap);
+    int mask_id[4] = {0, 0, 0, 0}, nout = 0;
+    for (int k = 0; k < 4; ++k)
+        if (want & (1u << k)) mask_id[nout++] = k;
+    const bool want_lab = (want & 16u) != 0, want_png = nout > 0;
+    // every page is checked before any device work starts
+    std::vector<ChainReq> req(n);
+    bool any_bin = false, two_maps = false;
+    for (int i = 0; i < n; ++i) {
+        PSEG_TRY(chain_check(e, i, imgs[i], H[i], W[i], Ho ? Ho[i] : 0, Wo ? Wo[i] : 0, binaries ? binaries[i] : nullptr, post_ops, n_post, flags,
+                             want_png, want_png, lut, n_lut, level, &req[i]));
+        if (want_png && pseg_png_bound_lv(req[i].Hl, req[i].Wl, 3, 0, level) == 0) return fail(PSEG_EINVAL, "page %d: png: a row of %d pixels is too long", i, req[i].Wl);
+        any_bin |= req[i].need_bin;
+        two_maps |= req[i].resize;
+    }
+    if (n == 0) return PSEG_OK;
+    for (int i = 0; i < n_post; ++i) two_maps |= post_ops[i] == PSEG_POST_BBOX;
+    PSEG_HIP(hipSetDevice(e.device));
+    if (!e.chain) {
+        auto* nc = new ChainState();
+        e.chain = nc;
+        PSEG_HIP(hipStreamCreateWithFlags(&nc->s_aux, hipStreamNonBlocking));
+        PSEG_HIP(hipEventCreateWithFlags(&nc->ev_aux, hipEventDisableTiming));
+    }
+    ChainState& c = *(ChainState*)e.chain;
+    if (!c.pages) c.pages = new ChainPagesState();
+    ChainPagesState& ps = *c.pages;
+    for (PagesSet& s : ps.set) {
+        if (!s.up) PSEG_HIP(hipEventCreateWithFlags(&s.up, hipEventDisableTiming));
+        if (!s.done) PSEG_HIP(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
+        if (!s.down) PSEG_HIP(hipEventCreateWithFlags(&s.down, hipEventDisableTiming));
+    }
+    hipStream_t s_in = nullptr, s_out = nullptr, st = e.stream;
+    PSEG_TRY(batch_copy_streams(e, &s_in, &s_out));
+    // units: pseg_predict_batch's rule over (H, W, final H, final W).  A bf16 engine's unit goes through the network as page slots
+    // (run_bf16_pages) unless the label-exact mode is asked for; any unit's masks are encoded in one set of launches.
+    const bool exact = (flags & PSEG_CHAIN_EXACT_LABELS) && e.mode == PSEG_MODE_BF16;
+    int cap = batch_unit_cap(e, n, H, W);     // (uploads the weights: the plans decide whether pages travel as page slots)
+    if (cap < 0) return cap;
+    const bool page_slots = !exact && pages_capable(e);
+    if (unit_cap > 0) {
+        cap = unit_cap;
+        if (page_slots) {
+            int hm = 0, wm = 0;
+            for (int i = 0; i < n; ++i)
+                if ((size_t)H[i] * W[i] > (size_t)hm * wm) { hm = H[i]; wm = W[i]; }
+            cap = fit_unit_slots(e, hm, wm, cap);
+        }
+    } else if (!page_slots) cap = std::min(8, std::max(1, n / 4));       // (the encoder's launches still take a unit's pages together)
+    std::vector<int> ub, ug;
+    plan_units(n, H, W, Ho, Wo, cap, ub, ug);
+    const int nu = (int)ub.size();
+    // per unit: shapes, strides and the encoder's layout
+    struct Unit { size_t npx, nl, nla, lab_stride; bool slots; PngPages L; };
+    std::vector<Unit> un(nu);
+    size_t mx[PagesSet::NDEV] = {0, 0, 0, 0, 0}, mx_in = 0, mx_tot = 0;
+    for (int u = 0; u < nu; ++u) {
+        const int i0 = ub[u], g = ug[u];
+        Unit& q = un[u];
+        q.npx = (size_t)H[i0] * W[i0];
+        q.nl = (size_t)req[i0].Hl * req[i0].Wl;
+        q.nla = up256(q.nl);                   // the vote kernels want 4-byte aligned maps
+        q.slots = page_slots && g > 1 && q.npx % 4 == 0;      // (page slots write the unit's maps one behind the other)
+        q.lab_stride = q.slots ? q.npx : up256(q.npx);
+        q.L = PngPages{0, 0, 0, 0, 0, 0, 0, 0};
+        if (want_png) PSEG_TRY(png_pages_layout(req[i0].Hl, req[i0].Wl, level, nout, g, &q.L));
+        const size_t in_b = (size_t)g * (q.npx * e.in_ch + (req[i0].need_bin ? q.nl : 0));
+        mx[PagesSet::IMG] = std::max(mx[PagesSet::IMG], (size_t)g * q.npx * e.in_ch);
+        mx[PagesSet::LAB] = std::max(mx[PagesSet::LAB], (size_t)g * up256(q.npx));
+        if (two_maps) mx[PagesSet::LAB2] = std::max(mx[PagesSet::LAB2], (size_t)g * 2 * q.nla);
+        if (any_bin) mx[PagesSet::BIN] = std::max(mx[PagesSet::BIN], (size_t)g * q.nla);
+        mx[PagesSet::PNG] = std::max(mx[PagesSet::PNG], q.L.bytes);
+        mx_in = std::max(mx_in, in_b);
+        mx_tot = std::max(mx_tot, (size_t)g * 4 * sizeof(unsigned long long));
+    }
+    // every way out -- also an error return in the middle and a sink that says stop -- ends with the three streams drained
+    struct Drain { hipStream_t a, b, c; ~Drain() { (void)hipStreamSynchronize(a); (void)hipStreamSynchronize(b); (void)hipStreamSynchronize(c); } } drain{s_in, st, s_out};
+    // a reallocation must not race with work that uses the block: every call ends drained, so the sets are idle here, and they are
+    // sized for the largest unit up front.  The page-locked stream staging alone grows while the call runs (see download).
+    bool any_pageable = false;
+    for (int i = 0; i < n && !any_pageable; ++i)
+        any_pageable = !pages_is_pinned(imgs[i]) || (req[i].need_bin && !pages_is_pinned(binaries[i]));
+    for (PagesSet& s : ps.set) {
+        for (int k = 0; k < PagesSet::NDEV; ++k)
+            if (mx[k]) PSEG_TRY(pages_ensure_dev(s, k, mx[k]));
+        if (any_pageable) PSEG_TRY(pages_ensure_host(&s.h_in, &s.h_in_bytes, mx_in));
+        PSEG_TRY(pages_ensure_host(&s.h_tot, &s.h_tot_bytes, std::max<size_t>(mx_tot, 64)));
+    }
+    if (want_png) {
+        if (!ps.d_lut) PSEG_HIP(hipMalloc((void**)&ps.d_lut, 768));
+        PSEG_HIP(hipMemcpyAsync(ps.d_lut, lut, (size_t)n_lut * 3, hipMemcpyHostToDevice, s_in));      // (ordered in front of every unit's up event)
+    }
+    auto upload = [&](int u) -> int {          // unit u -> set u % 2
+        PagesSet& s = ps.set[u & 1];
+        const Unit& q = un[u];
+        const int i0 = ub[u], g = ug[u];
+        const size_t pb = q.npx * e.in_ch;
+        const bool bin = req[i0].need_bin;
+        PSEG_HIP(hipStreamWaitEvent(s_in, s.done, 0));         // the set's pages and binarisations have been read (unit u - 2)
+        bool pinned = true;
+        for (int k = 0; k < g; ++k) pinned = pinned && pages_is_pinned(imgs[i0 + k]) && (!bin || pages_is_pinned(binaries[i0 + k]));
+        if (pinned) {
+            for (int k = 0; k < g; ++k) {
+                PSEG_HIP(hipMemcpyAsync(s.d[PagesSet::IMG] + (size_t)k * pb, imgs[i0 + k], pb, hipMemcpyHostToDevice, s_in));
+                if (bin) PSEG_HIP(hipMemcpyAsync(s.d[PagesSet::BIN] + (size_t)k * q.nla, binaries[i0 + k], q.nl, hipMemcpyHostToDevice, s_in));
+            }
+        } else {                               // through the page-locked slot: last read by the uploads of unit u - 2
+            PSEG_HIP(hipEventSynchronize(s.up));
+            uint8_t* hb = s.h_in + (size_t)g * pb;
+            for (int k = 0; k < g; ++k) {
+                memcpy(s.h_in + (size_t)k * pb, imgs[i0 + k], pb);
+                if (bin) memcpy(hb + (size_t)k * q.nl, binaries[i0 + k], q.nl);
+            }
+            PSEG_HIP(hipMemcpyAsync(s.d[PagesSet::IMG], s.h_in, (size_t)g * pb, hipMemcpyHostToDevice, s_in));
+            for (int k = 0; k < g && bin; ++k)
+                PSEG_HIP(hipMemcpyAsync(s.d[PagesSet::BIN] + (size_t)k * q.nla, hb + (size_t)k * q.nl, q.nl, hipMemcpyHostToDevice, s_in));
+        }
+        PSEG_HIP(hipEventRecord(s.up, s_in));
+        return PSEG_OK;
+    };
+    std::vector<uint8_t*> fin(nu, nullptr);    // page 0's final label map of the unit; fin_stride: bytes to the next page's
+    std::vector<size_t> fin_stride(nu, 0);
+    auto compute = [&](int u) -> int {
+        PagesSet& s = ps.set[u & 1];
+        const Unit& q = un[u];
+        const int i0 = ub[u], g = ug[u], Hi = H[i0], Wi = W[i0], Hl = req[i0].Hl, Wl = req[i0].Wl;
+        const size_t pb = q.npx * e.in_ch;
+        // a canvas change re-allocates / clears the activation tensors: the previous unit must have left them
+        if (round_up(Hi, 32) != e.Hp || round_up(Wi, 32) != e.Wp || (q.slots && g > e.pages)) PSEG_HIP(hipStreamSynchronize(st));
+        PSEG_HIP(hipStreamWaitEvent(st, s.up, 0));
+        PSEG_HIP(hipStreamWaitEvent(st, s.down, 0));           // the streams and maps of unit u - 2 have left the set
+        // 1. the network
+        if (q.slots) PSEG_TRY(predict_device_pages(e, s.d[PagesSet::IMG], g, Hi, Wi, nullptr, s.d[PagesSet::LAB], st));
+        else
+            for (int k = 0; k < g; ++k) {
+                const uint8_t* im = s.d[PagesSet::IMG] + (size_t)k * pb;
+                uint8_t* lab = s.d[PagesSet::LAB] + (size_t)k * q.lab_stride;
+                if (exact) PSEG_TRY(pseg_predict_exact_labels_device(h, im, Hi, Wi, lab, nullptr, nullptr, st));
+                else PSEG_TRY(predict_device(e, im, Hi, Wi, nullptr, nullptr, nullptr, lab, st, nullptr));
+            }
+        // 2./3. per page, in chain_run's order: resize, then the post-processors (the vote's workspace is one per device)
+        for (int k = 0; k < g; ++k) {
+            uint8_t* cur = s.d[PagesSet::LAB] + (size_t)k * q.lab_stride;
+            uint8_t* const bufA = two_maps ? s.d[PagesSet::LAB2] + (size_t)k * 2 * q.nla : nullptr;
+            uint8_t* const bufB = two_maps ? bufA + q.nla : nullptr;
+            if (req[i0].resize) {
+                PSEG_TRY(pseg_resize_nearest_device(e.device, cur, Hi, Wi, 1, bufA, Hl, Wl, st));
+                cur = bufA;
+            }
+            for (int i = 0; i < n_post; ++i) {
+                if (post_ops[i] == PSEG_POST_CC_VOTE) {
+                    PSEG_TRY(pseg_cc_vote_device_u8(e.device, cur, s.d[PagesSet::BIN] + (size_t)k * q.nla, Hl, Wl, e.n_classes, st));
+                } else {
+                    uint8_t* const dst = cur == bufA ? bufB : bufA;
+                    PSEG_TRY(pseg_bbox_fill_device_u8(e.device, cur, dst, Hl, Wl, e.n_classes, st));
+                    cur = dst;
+                }
+            }
+            if (k == 0) { fin[u] = cur; fin_stride[u] = cur == s.d[PagesSet::LAB] ? q.lab_stride : 2 * q.nla; }
+        }
+        // 4. the masks of all pages as PNG streams: one set of launches; the sizes go to page-locked memory
+        if (want_png) {
+            PSEG_TRY(png_pages_enqueue(q.L, s.d[PagesSet::PNG], fin[u], fin_stride[u], s.d[PagesSet::BIN], q.nla, ps.d_lut, n_lut, Hl, Wl, level, nout,
+                                       mask_id, g, st));
+            PSEG_HIP(hipMemcpyAsync(s.h_tot, s.d[PagesSet::PNG], (size_t)g * 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        }
+        PSEG_HIP(hipEventRecord(s.done, st));
+        return PSEG_OK;
+    };
+    // where a unit's outputs lie in its page-locked slot: per page the requested streams (8-byte aligned), then the label map
+    // (and the sizes, copied out of the set's page-locked words: those are written again by the unit after next while this one is
+    // still being delivered)
+    std::vector<std::vector<size_t>> offs(2), tot(2);
+    auto download = [&](int u) -> int {
+        PagesSet& s = ps.set[u & 1];
+        const Unit& q = un[u];
+        const int g = ug[u];
+        PSEG_HIP(hipEventSynchronize(s.done));                 // the sizes are here
+        std::vector<size_t>& of = offs[u & 1];
+        of.assign((size_t)g * 5 + 1, 0);
+        std::vector<size_t>& tt = tot[u & 1];
+        tt.assign((size_t)g * 4, 0);
+        size_t pos = 0;
+        for (int k = 0; k < g; ++k) {
+            for (int j = 0; j < 4; ++j) {
+                of[(size_t)k * 5 + j] = pos;
+                if (j >= nout) continue;
+                const unsigned long long t = s.h_tot[(size_t)k * 4 + j];
+                if (t < 80 || t > q.L.bound) return fail(PSEG_EHIP, "png: encoded size %llu outside (0, bound %zu] (page %d)", t, q.L.bound, ub[u] + k);
+                tt[(size_t)k * 4 + j] = (size_t)t;
+                pos += ((size_t)t + 7) & ~(size_t)7;
+            }
+            of[(size_t)k * 5 + 4] = pos;
+            if (want_lab) pos += (q.nl + 7) & ~(size_t)7;
+        }
+        of[(size_t)g * 5] = pos;
+        // the slot was handed to the sink by deliver(u - 2): idle.  It grows to what units really hold, with a quarter of headroom.
+        if (s.h_out_bytes < pos) PSEG_TRY(pages_ensure_host(&s.h_out, &s.h_out_bytes, pos + pos / 4 + 4096));
+        for (int k = 0; k < g; ++k) {
+            for (int j = 0; j < nout; ++j) {
+                const uint8_t* src = s.d[PagesSet::PNG] + q.L.head + (size_t)(g > 1 ? k : 0) * q.L.page + (size_t)j * q.L.per + q.L.slots_b + q.L.meta_b + q.L.offs_b;
+                PSEG_HIP(hipMemcpyAsync(s.h_out + of[(size_t)k * 5 + j], src, tt[(size_t)k * 4 + j], hipMemcpyDeviceToHost, s_out));
+            }
+            if (want_lab) PSEG_HIP(hipMemcpyAsync(s.h_out + of[(size_t)k * 5 + 4], fin[u] + (size_t)k * fin_stride[u], q.nl, hipMemcpyDeviceToHost, s_out));
+        }
+        PSEG_HIP(hipEventRecord(s.down, s_out));
+        return PSEG_OK;
+    };
+    auto deliver = [&](int u) -> int {         // chunk CRCs, then the sink: page order, `which` ascending; on the calling thread
+        PagesSet& s = ps.set[u & 1];
+        const Unit& q = un[u];
+        const std::vector<size_t>& of = offs[u & 1];
+        PSEG_HIP(hipEventSynchronize(s.down));
+        for (int k = 0; k < ug[u]; ++k) {
+            for (int j = 0; j < nout; ++j) {
+                uint8_t* p = s.h_out + of[(size_t)k * 5 + j];
+                const size_t t = tot[u & 1][(size_t)k * 4 + j];
+                PSEG_TRY(png_finish_host(p, t));
+                if (sink(user, ub[u] + k, mask_id[j], p, t) != 0) return fail(PSEG_ECALLBACK, "the sink stopped the call at page %d, output %d", ub[u] + k, mask_id[j]);
+            }
+            if (want_lab && sink(user, ub[u] + k, 4, s.h_out + of[(size_t)k * 5 + 4], q.nl) != 0)
+                return fail(PSEG_ECALLBACK, "the sink stopped the call at page %d, output 4", ub[u] + k);
+        }
+        return PSEG_OK;
+    };
+    // the host enqueues unit u + 1 before it waits for unit u's sizes; while the device works it finishes unit u - 1
+    PSEG_TRY(upload(0));
+    PSEG_TRY(compute(0));
+    for (int u = 0; u < nu; ++u) {
+        if (u + 1 < nu) { PSEG_TRY(upload(u + 1)); PSEG_TRY(compute(u + 1)); }
+        PSEG_TRY(download(u));
+        if (u > 0) PSEG_TRY(deliver(u - 1));
+    }
+    PSEG_TRY(deliver(nu - 1));
+    PSEG_HIP(hipStreamSynchronize(s_out));
+    return engine_status(e, st);
 }

@@ -287,6 +287,23 @@ size_t bn_saved_bytes(int C);
 void launch_dropout(float* x, size_t n, uint32_t key, float rate, hipStream_t st);
 int ccl_roots(const uint8_t* d_bin, int* d_L, int H, int W, int connectivity, hipStream_t st);   // pseg_post.hip
 void png_release_workspace(int dev);   // pseg_png.hip: the encoder's per-device workspace (pseg_release_workspace)
+// pseg_png.hip, for the page chain: the masks of `pages` label maps of one shape as PNG streams in one set of launches, enqueued on
+// `st` without a wait; the workspace (PngPages::bytes, from png_pages_layout) is the caller's.  Page p's sizes: ((u64*)d_ws)[4 p + k];
+// its stream k (k-th requested mask): d_ws + head + p * page + k * per + slots_b + meta_b + offs_b, chunk CRCs left to
+// png_finish_host on the downloaded bytes.
+struct PngPages { size_t bytes, head, page, per, slots_b, meta_b, offs_b, bound; };
+int png_pages_layout(int H, int W, int level, int nout, int pages, PngPages* L);
+int png_pages_enqueue(const PngPages& L, uint8_t* d_ws, const uint8_t* d_pred, size_t page_pred, const uint8_t* d_bin, size_t page_bin,
+                      const uint8_t* d_lut, int n_lut, int H, int W, int level, int nout, const int mask_id[4], int pages, hipStream_t st);
+int png_finish_host(uint8_t* png, size_t total);
+// pseg_engine.hip, shared by pseg_predict_batch and the page chain
+void plan_units(int n, const int* H, const int* W, const int* Ho, const int* Wo, int cap, std::vector<int>& ub, std::vector<int>& ug);
+int fit_unit_slots(Engine& e, int H, int W, int want);              // page slots a unit of `want` pages of this shape gets (1: no page units)
+int batch_copy_streams(Engine& e, hipStream_t* s_in, hipStream_t* s_out);   // pseg_predict_batch's upload / download streams
+void chain_trim(Engine& e);                                          // pseg_chain.hip: frees the page chain's staging sets (pseg_engine_trim)
+int batch_unit_cap(Engine& e, int n, const int* H, const int* W);   // pseg_predict_batch's pages per unit for this list (uploads the weights)
+int predict_device_pages(Engine& e, const uint8_t* d_imgs, int n, int H, int W, int64_t* d_labels, uint8_t* d_labels_u8, hipStream_t st);
+bool pages_capable(Engine& e);
 int upload_weights(Engine& e);
 // one page through the engine's graph, device buffers, asynchronous on `st` (every output optional)
 int predict_device(Engine& e, const uint8_t* d_img, int H, int W, float* d_logits, float* d_probs, int64_t* d_labels,

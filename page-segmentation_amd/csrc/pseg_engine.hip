@@ -1045,11 +1045,14 @@ int predict_device_pages(Engine& e, const uint8_t* d_imgs, int n, int H, int W, 
 bool pages_capable(Engine& e);
 
 // units of a page list (see predict_batch): runs of same-shape pages, at most `cap` per unit, sizes 1, 2, 4 ... at the head and
-// ... 4, 2, 1 at the tail of the list
-static void plan_units(int n, const int* H, const int* W, int cap, std::vector<int>& ub, std::vector<int>& ug) {
+// ... 4, 2, 1 at the tail of the list.  Ho / Wo (the page chain: the label map's final shape; NULL: none) are part of a page's shape.
+void plan_units(int n, const int* H, const int* W, const int* Ho, const int* Wo, int cap, std::vector<int>& ub, std::vector<int>& ug) {
+    auto same = [&](int a, int b) {
+        return H[a] == H[b] && W[a] == W[b] && (!Ho || Ho[a] == Ho[b]) && (!Wo || Wo[a] == Wo[b]);
+    };
     for (int i = 0; i < n;) {
         int run = 1;
-        while (i + run < n && H[i + run] == H[i] && W[i + run] == W[i]) ++run;
+        while (i + run < n && same(i + run, i)) ++run;
         std::vector<int> front, back;
         int left = run;
         if (cap > 1) {
@@ -1066,20 +1069,58 @@ static void plan_units(int n, const int* H, const int* W, int cap, std::vector<i
     }
 }
 
+static int batch_state(Engine& e) {
+    if (e.batch) return PSEG_OK;
+    auto* nb = new BatchState();
+    e.batch = nb;
+    PSEG_HIP(hipStreamCreateWithFlags(&nb->s_in, hipStreamNonBlocking));
+    PSEG_HIP(hipStreamCreateWithFlags(&nb->s_out, hipStreamNonBlocking));
+    for (int i = 0; i < 2; ++i) {
+        PSEG_HIP(hipEventCreateWithFlags(&nb->up[i], hipEventDisableTiming));
+        PSEG_HIP(hipEventCreateWithFlags(&nb->done[i], hipEventDisableTiming));
+        PSEG_HIP(hipEventCreateWithFlags(&nb->down[i], hipEventDisableTiming));
+    }
+    return PSEG_OK;
+}
+// the two copy streams of pseg_predict_batch: the page chain's pipeline runs on the same ones (a call of either ends drained)
+int batch_copy_streams(Engine& e, hipStream_t* s_in, hipStream_t* s_out) {
+    PSEG_TRY(batch_state(e));
+    auto* b = (BatchState*)e.batch;
+    if (!b->s_in || !b->s_out) return fail(PSEG_EHIP, "the batch state has no copy streams");
+    *s_in = b->s_in;
+    *s_out = b->s_out;
+    return PSEG_OK;
+}
+
+// pages per unit of a list (PSEG_BATCH_PAGES caps a unit; default 8: 7 GB of activations at 2048x1536; 1 = page by page)
+static int unit_cap_of(Engine& e, int n, const int* H, const int* W) {
+    int cap = 8;
+    if (const char* ev = PSEG_KNOB("PSEG_BATCH_PAGES")) cap = std::max(1, std::min(64, atoi(ev)));
+    // ... and the copies of a unit overlap the compute of its NEIGHBOURS only: a list shorter than four units would wait for its first
+    // upload and its last download with nothing beside them (8 pages as one unit: 0.70 ms per page against 0.49 page by page)
+    cap = std::min(cap, std::max(1, n / 4));
+    if (!pages_capable(e)) cap = 1;
+    if (cap > 1) {                          // ... and by what the device has room for (the largest page of the list decides)
+        int hm = 0, wm = 0;
+        for (int i = 0; i < n; ++i)
+            if ((size_t)H[i] * W[i] > (size_t)hm * wm) { hm = H[i]; wm = W[i]; }
+        cap = fit_page_slots(e, hm, wm, cap);
+    }
+    return cap;
+}
+int batch_unit_cap(Engine& e, int n, const int* H, const int* W) {
+    for (auto& p : e.params)
+        if (!p.set) return fail(PSEG_EINVAL, "weight '%s' was never set", p.name.c_str());
+    if (e.weights_dirty) PSEG_TRY(upload_weights(e));
+    return unit_cap_of(e, n, H, W);
+}
+// the page slots a unit of `want` same-shape pages gets on this device (the page chain with a caller's unit_cap)
+int fit_unit_slots(Engine& e, int H, int W, int want) { return pages_capable(e) ? fit_page_slots(e, H, W, want) : 1; }
+
 static int predict_batch(Engine& e, int n, const uint8_t* const* imgs, const int* H, const int* W,
                          int64_t* const* labels, uint8_t* const* labels_u8) {
     PSEG_HIP(hipSetDevice(e.device));
-    if (!e.batch) {
-        auto* nb = new BatchState();
-        e.batch = nb;
-        PSEG_HIP(hipStreamCreateWithFlags(&nb->s_in, hipStreamNonBlocking));
-        PSEG_HIP(hipStreamCreateWithFlags(&nb->s_out, hipStreamNonBlocking));
-        for (int i = 0; i < 2; ++i) {
-            PSEG_HIP(hipEventCreateWithFlags(&nb->up[i], hipEventDisableTiming));
-            PSEG_HIP(hipEventCreateWithFlags(&nb->done[i], hipEventDisableTiming));
-            PSEG_HIP(hipEventCreateWithFlags(&nb->down[i], hipEventDisableTiming));
-        }
-    }
+    PSEG_TRY(batch_state(e));
     auto* b = (BatchState*)e.batch;
     for (auto& p : e.params)
         if (!p.set) return fail(PSEG_EINVAL, "weight '%s' was never set", p.name.c_str());
@@ -1096,18 +1137,7 @@ static int predict_batch(Engine& e, int n, const uint8_t* const* imgs, const int
     // Units: runs of consecutive pages of one shape go through the graph together (run_bf16_pages: every tensor holds a page slot
     // per page of the unit, the low-resolution layers take all slots in one launch); everything else is a unit of one page.
     // PSEG_BATCH_PAGES caps a unit (default 8: 7 GB of activations at 2048x1536; 1 = page by page as before).
-    int cap = 8;
-    if (const char* ev = PSEG_KNOB("PSEG_BATCH_PAGES")) cap = std::max(1, std::min(64, atoi(ev)));
-    // ... and the copies of a unit overlap the compute of its NEIGHBOURS only: a list shorter than four units would wait for its first
-    // upload and its last download with nothing beside them (8 pages as one unit: 0.70 ms per page against 0.49 page by page)
-    cap = std::min(cap, std::max(1, n / 4));
-    if (!pages_capable(e)) cap = 1;
-    if (cap > 1) {                          // ... and by what the device has room for (the largest page of the list decides)
-        int hm = 0, wm = 0;
-        for (int i = 0; i < n; ++i)
-            if ((size_t)H[i] * W[i] > (size_t)hm * wm) { hm = H[i]; wm = W[i]; }
-        cap = fit_page_slots(e, hm, wm, cap);
-    }
+    const int cap = unit_cap_of(e, n, H, W);
     // Unit sizes.  The upload of the FIRST unit and the download of the LAST one have no compute beside them: a list cut into
     // equal units of 8 pages waits 8 page uploads at its head and 8 downloads at its tail (32 pages: 2 of 14 ms).  So a run of same-shape
     // pages that opens the list starts with units of 1, 2, 4, ... pages, one that closes it ends ... 4, 2, 1 (every unit's copies
@@ -1115,7 +1145,7 @@ static int predict_batch(Engine& e, int n, const uint8_t* const* imgs, const int
     // Same box, 32 / 8 pages of 2048x1536, ms per page, ramped against equal units: pinned uint8 0.410-0.445 vs 0.430 / 0.458 vs 0.466,
     // pageable arrays through the ring 0.456 vs 0.57 / 0.51-0.52 vs 0.55 (tools/gpu_r05_hostpath.sh).
     std::vector<int> ub, ug;                 // first page, page count of every unit
-    plan_units(n, H, W, cap, ub, ug);
+    plan_units(n, H, W, nullptr, nullptr, cap, ub, ug);
     const int nu = (int)ub.size();
     auto upx = [&](int u) { return (size_t)H[ub[u]] * W[ub[u]]; };
     auto lab_off8 = [&](int u, int k) { return (size_t)k * upx(u) * 8; };                                   // int64 map of page k of the unit
@@ -1461,6 +1491,7 @@ int pseg_engine_trim(pseg_engine* h) {
     e.Hp = e.Wp = 0;
     e.pages = 1;
     free_dev((void*&)e.d_logits_tmp); e.logits_tmp_bytes = 0;
+    chain_trim(e);
     return PSEG_OK;
 }
 
@@ -1475,7 +1506,7 @@ int pseg_predict_batch(pseg_engine* h, int n_pages, const uint8_t* const* imgs, 
 int pseg_batch_units(int n_pages, const int* H, const int* W, int cap, int* unit_first, int* unit_count, int max_units) {
     if (n_pages < 0 || (n_pages > 0 && (!H || !W)) || cap < 1) return fail(PSEG_EINVAL, "bad argument");
     std::vector<int> ub, ug;
-    plan_units(n_pages, H, W, cap, ub, ug);
+    plan_units(n_pages, H, W, nullptr, nullptr, cap, ub, ug);
     if ((int)ub.size() > max_units && (unit_first || unit_count)) return fail(PSEG_EINVAL, "%zu units, room for %d", ub.size(), max_units);
     for (size_t u = 0; u < ub.size(); ++u) {
         if (unit_first) unit_first[u] = ub[u];

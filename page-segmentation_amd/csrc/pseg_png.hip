@@ -56,9 +56,12 @@ struct PngJob {
     PngBandMeta* meta[4];
     unsigned long long* offs[4];              // final offset of every band's chunk
     uint8_t* out[4];                          // the assembled stream
-    unsigned long long* total;                // [4] its size
+    unsigned long long* total;                // [pages][4] its size
     int mask_id[4];
+    size_t page;                              // bytes between two pages' slots, band tables, offsets and streams (blockIdx.z / blockIdx.y
+                                              // selects the page); 0 with one page
 };
+
 
 // ---- host arithmetic ------------------------------------------------------------------------------------------------
 static inline size_t png_band_bound(size_t n) { return n + n / 8 + 8; }   // header 3 + 9 n + end-of-block 7 + stored header 3 bits, padded, + 4
@@ -215,6 +218,8 @@ struct PngSrcPlain {                          // interleaved 8-bit buffer, 1 or 
     static constexpr bool LUT = false;
     const uint8_t* p;
     int W, C;
+    size_t page = 0;                          // bytes between two pages' images
+    __device__ __forceinline__ PngSrcPlain at(unsigned pg) const { PngSrcPlain s = *this; s.p += pg * page; return s; }
     __device__ __forceinline__ uint32_t px(int row, int x, int, const uint32_t*) const {
         const uint8_t* q = p + ((size_t)row * W + x) * C;
         return C == 1 ? (uint32_t)q[0] : ((uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16));
@@ -226,6 +231,8 @@ struct PngSrcMasks {                          // generate_output_masks (lib/outp
     const uint8_t* bin;
     const uint8_t* lut;
     int n_lut, W;
+    size_t page_pred = 0, page_bin = 0;       // bytes between two pages' label maps / binarisations
+    __device__ __forceinline__ PngSrcMasks at(unsigned pg) const { PngSrcMasks s = *this; s.pred += pg * page_pred; s.bin += pg * page_bin; return s; }
     __device__ __forceinline__ uint32_t px(int row, int x, int mask, const uint32_t* slut) const {
         const size_t p = (size_t)row * W + x;
         const uint32_t rgb = slut[pred[p]];
@@ -388,8 +395,12 @@ __device__ inline int png_dyn_header(const uint8_t* s_len, int D, uint32_t* ws, 
 // LV 0: one fixed-Huffman block per band.  LV 1: two passes over the band's tokens -- A counts the symbols, the workgroup builds
 // a code for them and prices the band both ways, B packs with the cheaper of the two (a tie goes to the fixed code: the band is
 // then LV 0's band bit for bit).
-template <class SRC, int LV>
-__global__ __launch_bounds__(PNG_T) void png_band_kernel(SRC src, PngJob J) {
+// PAGES: blockIdx.z selects one of several images of one shape (J.page, the source's page strides); without it the kernel is the
+// single-image kernel, instruction for instruction.
+template <class SRC, int LV, bool PAGES = false>
+__global__ __launch_bounds__(PNG_T) void png_band_kernel(SRC src0, PngJob J) {
+    const SRC src = PAGES ? src0.at(blockIdx.z) : src0;
+    const size_t pg = PAGES ? (size_t)blockIdx.z * J.page : 0;
     __shared__ __attribute__((aligned(16))) uint8_t s_in[16 + PNG_SEG];   // [13..15]: the three bytes in front of the segment
     __shared__ uint32_t s_bits[LV ? PNG_BITW1 : PNG_BITW];
     __shared__ int s_w[4];
@@ -413,7 +424,7 @@ __global__ __launch_bounds__(PNG_T) void png_band_kernel(SRC src, PngJob J) {
     const int row0 = band * J.R, rows = min(J.R, J.H - row0);
     const int L = J.L, D = J.C;
     const int n = rows * L;                                   // <= 2^30 (png_rows)
-    uint32_t* const out = (uint32_t*)(J.slots[o] + (size_t)band * J.slot);
+    uint32_t* const out = (uint32_t*)(J.slots[o] + pg + (size_t)band * J.slot);
     unsigned out_w = 0;                                       // words of the slot written so far
     uint32_t carry_word = 2u;                                 // block header: BFINAL = 0, BTYPE = 01 (fixed Huffman), LSB first
     int carry_bits = 3;                                       // LV 1, first segment: the header's whole words and its partial word
@@ -584,7 +595,7 @@ __global__ __launch_bounds__(PNG_T) void png_band_kernel(SRC src, PngJob J) {
                 PngBandMeta m;
                 m.bytes = out_w * 4u + (unsigned)(T >> 3);
                 m.a = adA; m.b = adB; m.pad = 0;
-                J.meta[o][band] = m;
+                ((PngBandMeta*)((uint8_t*)J.meta[o] + pg))[band] = m;
             }
         } else {
             out_w += (unsigned)nW;
@@ -604,7 +615,9 @@ __global__ __launch_bounds__(PNG_T) void png_frame_kernel(PngJob J) {
     __shared__ unsigned long long s_tot[PNG_T];
     __shared__ unsigned long long s_a, s_b;
     const int t = threadIdx.x, o = blockIdx.x;
-    const PngBandMeta* meta = J.meta[o];
+    const size_t pg = (size_t)blockIdx.y * J.page;
+    const PngBandMeta* meta = (const PngBandMeta*)((const uint8_t*)J.meta[o] + pg);
+    unsigned long long* const offs = (unsigned long long*)((uint8_t*)J.offs[o] + pg);
     const int per = (J.nb + PNG_T - 1) / PNG_T;
     const int b0 = min(J.nb, t * per), b1 = min(J.nb, b0 + per);
     if (t == 0) { s_a = 0; s_b = 0; }
@@ -620,7 +633,7 @@ __global__ __launch_bounds__(PNG_T) void png_frame_kernel(PngJob J) {
     const unsigned long long ntotal = (unsigned long long)J.H * (unsigned long long)J.L;
     unsigned long long off = s_tot[t], a = 0, bsum = 0;
     for (int b = b0; b < b1; ++b) {
-        J.offs[o][b] = off;
+        offs[b] = off;
         off += (unsigned long long)meta[b].bytes + 12u;
         const unsigned long long end = (unsigned long long)min((long long)(b + 1) * J.R, (long long)J.H) * (unsigned long long)J.L;
         const unsigned long long after = (ntotal - end) % ADLER_M;           // the "length mod 65521" of the combine
@@ -634,7 +647,7 @@ __global__ __launch_bounds__(PNG_T) void png_frame_kernel(PngJob J) {
         const unsigned long long end = off;                   // behind the last band's chunk (the threads behind the last band hold it too)
         const uint32_t s1 = (uint32_t)((1u + s_a % ADLER_M) % ADLER_M);
         const uint32_t s2 = (uint32_t)((ntotal % ADLER_M + s_b % ADLER_M) % ADLER_M);
-        uint8_t* p = J.out[o];
+        uint8_t* p = J.out[o] + pg;
         const uint8_t sig[8] = {0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A};
         for (int k = 0; k < 8; ++k) p[k] = sig[k];
         png_be32(p + 8, 13);
@@ -656,15 +669,16 @@ __global__ __launch_bounds__(PNG_T) void png_frame_kernel(PngJob J) {
         png_be32(q + 21, 0);
         q[25] = 'I'; q[26] = 'E'; q[27] = 'N'; q[28] = 'D';
         png_be32(q + 29, 0);
-        J.total[o] = end + 21 + 12;
+        J.total[(size_t)blockIdx.y * 4 + o] = end + 21 + 12;
     }
 }
 
 __global__ __launch_bounds__(PNG_T) void png_gather_kernel(PngJob J) {
     const int t = threadIdx.x, band = blockIdx.x, o = blockIdx.y;
-    const unsigned sz = J.meta[o][band].bytes;
-    const uint8_t* src = J.slots[o] + (size_t)band * J.slot;
-    uint8_t* dst = J.out[o] + J.offs[o][band];
+    const size_t pg = (size_t)blockIdx.z * J.page;
+    const unsigned sz = ((const PngBandMeta*)((const uint8_t*)J.meta[o] + pg))[band].bytes;
+    const uint8_t* src = J.slots[o] + pg + (size_t)band * J.slot;
+    uint8_t* dst = J.out[o] + pg + ((const unsigned long long*)((const uint8_t*)J.offs[o] + pg))[band];
     if (t == 0) { png_be32(dst, sz); dst[4] = 'I'; dst[5] = 'D'; dst[6] = 'A'; dst[7] = 'T'; png_be32(dst + 8 + sz, 0); }
     for (unsigned k = t; k < sz; k += PNG_T) dst[8 + k] = src[k];
 }
@@ -734,6 +748,7 @@ static int png_run(int device, const SRC& src, int H, int W, int C, int band_row
     J.nb = (int)(((size_t)H + J.R - 1) / J.R);
     J.L = W * C + 1;
     J.slot = (png_band_bound((size_t)J.R * J.L) + 3) & ~(size_t)3;
+    J.page = 0;
     const size_t slots_b = al256((size_t)J.nb * J.slot), meta_b = al256((size_t)J.nb * sizeof(PngBandMeta)), offs_b = al256((size_t)J.nb * 8),
                  out_b = al256(bound + 32);
     const size_t per = slots_b + meta_b + offs_b + out_b, need = 256 + (size_t)nout * per;
@@ -778,6 +793,58 @@ static int png_run(int device, const SRC& src, int H, int W, int C, int band_row
     }
     return PSEG_OK;
 }
+
+// ---- many images of one shape in one set of launches, asynchronously (the page chain, pseg_chain.hip) ------------------------------
+// The workspace is the caller's: [pages][4] sizes, then per page `nout` blocks of {band slots, band table, offsets, stream}.  Nothing
+// here waits, locks or allocates.
+int png_pages_layout(int H, int W, int level, int nout, int pages, PngPages* L) {
+    if (!png_shape_ok(H, W, 3) || (level != 0 && level != 1) || nout < 1 || nout > 4 || pages < 1 || pages > 65535)
+        return fail(PSEG_EINVAL, "png: %d pages of %d x %d pixels, %d outputs, level %d", pages, H, W, nout, level);
+    const int R = png_rows(H, W, 3, 0, level), nb = (int)(((size_t)H + R - 1) / R);
+    const size_t Lb = (size_t)W * 3 + 1, slot = (png_band_bound((size_t)R * Lb) + 3) & ~(size_t)3;
+    L->bound = png_bound(H, W, 3, 0, level);
+    L->slots_b = al256((size_t)nb * slot);
+    L->meta_b = al256((size_t)nb * sizeof(PngBandMeta));
+    L->offs_b = al256((size_t)nb * 8);
+    L->per = L->slots_b + L->meta_b + L->offs_b + al256(L->bound + 32);
+    L->page = (size_t)nout * L->per;
+    L->head = al256((size_t)pages * 4 * sizeof(unsigned long long));
+    L->bytes = L->head + (size_t)pages * L->page;
+    return PSEG_OK;
+}
+
+int png_pages_enqueue(const PngPages& L, uint8_t* d_ws, const uint8_t* d_pred, size_t page_pred, const uint8_t* d_bin, size_t page_bin,
+                      const uint8_t* d_lut, int n_lut, int H, int W, int level, int nout, const int mask_id[4], int pages, hipStream_t st) {
+    PngJob J;
+    J.H = H; J.W = W; J.C = 3; J.R = png_rows(H, W, 3, 0, level);
+    J.nb = (int)(((size_t)H + J.R - 1) / J.R);
+    J.L = W * 3 + 1;
+    J.slot = (png_band_bound((size_t)J.R * J.L) + 3) & ~(size_t)3;
+    J.page = pages > 1 ? L.page : 0;
+    J.total = (unsigned long long*)d_ws;
+    for (int k = 0; k < 4; ++k) {
+        uint8_t* q = d_ws + L.head + (size_t)std::min(k, nout - 1) * L.per;
+        J.slots[k] = q;
+        J.meta[k] = (PngBandMeta*)(q + L.slots_b);
+        J.offs[k] = (unsigned long long*)(q + L.slots_b + L.meta_b);
+        J.out[k] = q + L.slots_b + L.meta_b + L.offs_b;
+        J.mask_id[k] = mask_id[std::min(k, nout - 1)];
+    }
+    PngSrcMasks src{d_pred, d_bin, d_lut, n_lut, W, pages > 1 ? page_pred : 0, pages > 1 ? page_bin : 0};
+    if (pages == 1) {
+        if (level == 0) png_band_kernel<PngSrcMasks, 0><<<dim3(J.nb, nout), PNG_T, 0, st>>>(src, J);
+        else png_band_kernel<PngSrcMasks, 1><<<dim3(J.nb, nout), PNG_T, 0, st>>>(src, J);
+    } else {
+        if (level == 0) png_band_kernel<PngSrcMasks, 0, true><<<dim3(J.nb, nout, pages), PNG_T, 0, st>>>(src, J);
+        else png_band_kernel<PngSrcMasks, 1, true><<<dim3(J.nb, nout, pages), PNG_T, 0, st>>>(src, J);
+    }
+    png_frame_kernel<<<dim3(nout, pages), PNG_T, 0, st>>>(J);
+    png_gather_kernel<<<dim3(J.nb, nout, pages), PNG_T, 0, st>>>(J);
+    PSEG_HIP(hipGetLastError());
+    return PSEG_OK;
+}
+
+int png_finish_host(uint8_t* png, size_t total) { return png_fill_crcs(png, total); }
 
 static int png_set_dev(int device) {
     int n = 0;

@@ -37,10 +37,10 @@ class Predictor:
             ops.append(known[processor])
         return ops
 
-    def _chain(self, data: SingleData, want_masks: bool, png_level=0):
-        """predict -> [scale_to_original_shape] -> post-processors -> [masks] without the label map leaving the device
-        (lib/predictor.py:32-54).  Returns (data', labels_u8, masks or None), or None when this page / these settings
-        need the host chain (a post-processor that is not one of this package's, > 256 classes, no binary for the vote)."""
+    def _chain_inputs(self, data: SingleData, want_masks):
+        """What the device chain takes for this page: (data', network input, uint8 binarisation or None, out_shape or None, op
+        names), or None when this page / these settings need the host chain (a post-processor that is not one of this package's,
+        > 256 classes, no binary for the vote)."""
         net = self.network
         ops = self._chain_ops()
         if ops is None or net.n_classes > 256 or getattr(net, "_rgb", False) and np.asarray(data.image).ndim != 2:
@@ -63,7 +63,17 @@ class Predictor:
             return None
         from .util import gray_to_rgb
         img = gray_to_rgb(image) if getattr(net, "_rgb", False) else image
-        res = net.model.predict_chain(img, binary=np.asarray(binary).astype(np.uint8) if need_bin else None, out_shape=out_shape,
+        return page, img, np.asarray(binary).astype(np.uint8) if need_bin else None, out_shape, ops
+
+    def _chain(self, data: SingleData, want_masks: bool, png_level=0):
+        """predict -> [scale_to_original_shape] -> post-processors -> [masks] without the label map leaving the device
+        (lib/predictor.py:32-54).  Returns (data', labels_u8, masks or None), or None when the host chain has to run (_chain_inputs)."""
+        got = self._chain_inputs(data, want_masks)
+        if got is None:
+            return None
+        page, img, binary, out_shape, ops = got
+        net = self.network
+        res = net.model.predict_chain(img, binary=binary, out_shape=out_shape,
                                       post_ops=ops, exact_labels=net.exact == "labels", labels=None if want_masks else "u8",
                                       lut=self.settings.color_map.lut() if want_masks else None, masks=want_masks,  # True or "png"
                                       png_level=png_level)
@@ -150,3 +160,41 @@ class Predictor:
         data, _, pred = self._labels(data)
         output.output_data(output_dir, np.asarray(pred), data, self.settings.color_map, level=level)
         return paths
+
+    def write_masks_dataset(self, dataset: Dataset, output_dir=None, level=None, chunk_pages=64):
+        """write_masks for every page of a dataset (lib/predictor.py:27-30 over :49-54), the pages streamed through the device chain
+        chunk_pages at a time (Engine.predict_chain_pages: units of same-shape pages, uploads, encoder and downloads of neighbouring
+        units overlapped); each PNG stream is written to its file as it arrives.  Same files, names and bytes as write_masks.  Pages
+        the device path cannot take -- other extensions than ".png", output.DEVICE_PNG = False, a foreign post-processor, more than
+        256 classes, no binarisation where one is needed -- go through write_masks, in place.  Yields the three paths per page, in
+        dataset order."""
+        from . import output
+        level = output.DEVICE_PNG_LEVEL if level is None else level
+        output_dir = output_dir if output_dir is not None else self.settings.output
+        if output_dir is None:
+            raise Exception("write_masks needs an output directory")
+        for sub in ("color", "overlay", "inverted"):
+            os.makedirs(os.path.join(output_dir, sub), exist_ok=True)
+        pages = list(dataset.data)
+        names = ("color", "overlay", "inverted")
+        for i in range(0, len(pages), max(1, int(chunk_pages))):
+            chunk = pages[i:i + max(1, int(chunk_pages))]
+            paths, inputs = [], []
+            for data in chunk:
+                p = output.output_paths(output_dir, data)
+                paths.append(p)
+                inputs.append(self._chain_inputs(data, "png") if output.DEVICE_PNG and output.is_png_target(p[0]) else None)
+            on_device = [k for k, got in enumerate(inputs) if got is not None]
+            if on_device:
+                def to_file(page, name, stream, paths=paths, on_device=on_device):
+                    with open(paths[on_device[page]][names.index(name)], "wb") as f:
+                        f.write(stream)
+                self.network.model.predict_chain_pages(
+                    [inputs[k][1] for k in on_device], binaries=[inputs[k][2] for k in on_device],
+                    out_shapes=[inputs[k][3] for k in on_device], post_ops=inputs[on_device[0]][4],
+                    exact_labels=self.network.exact == "labels", lut=self.settings.color_map.lut(), which=names,
+                    png_level=level, sink=to_file)
+            for k, data in enumerate(chunk):
+                if inputs[k] is None:
+                    self.write_masks(data, output_dir=output_dir, level=level)
+                yield paths[k]

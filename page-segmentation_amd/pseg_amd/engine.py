@@ -29,7 +29,7 @@ EXPORTED_SYMBOLS = (
     "pseg_otsu_char_height",
     "pseg_png_bound", "pseg_png_encode_device", "pseg_masks_png_device_u8", "pseg_png_encode", "pseg_masks_png", "pseg_predict_chain_png",
     "pseg_png_bound_lv", "pseg_png_encode_device_lv", "pseg_masks_png_device_u8_lv", "pseg_png_encode_lv", "pseg_masks_png_lv",
-    "pseg_predict_chain_png_lv", "pseg_png_code_lengths",
+    "pseg_predict_chain_png_lv", "pseg_png_code_lengths", "pseg_predict_chain_pages_png", "pseg_chain_units",
     "pseg_rescale_shape", "pseg_gaussian_kernel", "pseg_resize_nearest", "pseg_resize_nearest_device", "pseg_scale_image",
     "pseg_prepare_images", "pseg_affine_warp", "pseg_affine_warp_fill", "pseg_brightness_shift",
     "pseg_eval_confusion", "pseg_cc_label", "pseg_cc_tables",
@@ -37,6 +37,10 @@ EXPORTED_SYMBOLS = (
 
 
 PLAN_FROM_ENV = bool(os.environ.get("PSEG_PLAN_FROM_ENV"))   # test harness / tools: PSEG_* of os.environ -> plan switches of new engines (see Engine)
+
+
+# pseg_chain_sink: int (*)(void* user, int page, int which, const uint8_t* data, size_t n_bytes)
+CHAIN_SINK = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_uint8), ctypes.c_size_t)
 
 
 class PsegError(Exception):
@@ -155,6 +159,8 @@ def lib():
     L.pseg_masks_png_lv.argtypes = [i, vp, vp, vp, i, i, i, i, i, c.POINTER(vp), c.POINTER(sz), c.POINTER(sz)]
     L.pseg_predict_chain_png_lv.argtypes = [vp, vp, i, i, i, i, vp, c.POINTER(i), i, c.c_uint, vp, vp, vp, i, i, c.POINTER(vp), c.POINTER(sz), c.POINTER(sz)]
     L.pseg_png_code_lengths.argtypes = [vp, i, i, vp]
+    L.pseg_predict_chain_pages_png.argtypes = [vp, i, vp, vp, vp, vp, vp, vp, c.POINTER(i), i, c.c_uint, vp, i, i, c.c_uint, i, CHAIN_SINK, vp]
+    L.pseg_chain_units.argtypes = [i, vp, vp, vp, vp, i, vp, vp, i]
     _LIB = L
     return L
 
@@ -444,6 +450,71 @@ class Engine:
                                         _ptr(lab) if labels == "i64" else None, _ptr(lab) if labels == "u8" else None,
                                         _ptr(t), 0 if t is None else t.shape[0], *[_ptr(o) for o in outs]))
         return {"labels": lab, "masks": tuple(outs) if masks else None}
+
+    def predict_chain_pages(self, images, binaries=None, out_shapes=None, post_ops=(), exact_labels=False, lut=None,
+                            which=("color", "overlay", "inverted"), labels=False, png_level=0, unit_cap=0, sink=None):
+        """A page list through the chain to PNG streams (pseg_predict_chain_pages_png; lib/predictor.py:27-30 over :49-54): per page
+        predict -> [nearest resize to out_shapes[i]] -> post-processors -> the masks named in `which` as PNG streams, units of
+        same-shape pages pipelined on the device; every stream (and label map, with labels=True) has predict_chain's bytes for that
+        page alone.  binaries[i] / out_shapes[i] may be None.  sink=None: a list of {"labels": uint8 map or None, "masks": {name:
+        bytes}} per page.  With a callable, sink(page, name, data) is called per output as it arrives -- page order, then color /
+        overlay / inverted / fg_color / "labels" (data: bytes, for "labels" the uint8 map) -- and None is returned; an exception in
+        the sink stops the call and is raised again after it."""
+        for w in which:
+            if w not in MASK_NAMES:
+                raise PsegError("unknown mask %r (one of %r)" % (w, MASK_NAMES))
+        imgs = [np.ascontiguousarray(im, dtype=np.uint8) for im in images]
+        n = len(imgs)
+        outs = list(out_shapes) if out_shapes is not None else [None] * n
+        bins_in = list(binaries) if binaries is not None else [None] * n
+        if len(outs) != n or len(bins_in) != n:
+            raise PsegError("binaries / out_shapes must have one entry per page")
+        final, bins = [], []
+        for k in range(n):
+            fs = (int(outs[k][0]), int(outs[k][1])) if outs[k] is not None else imgs[k].shape[:2]
+            b = None
+            if bins_in[k] is not None:
+                b = np.ascontiguousarray(bins_in[k], dtype=np.uint8)
+                if b.shape != fs:
+                    raise PsegError("page %d: binary has shape %r, the label map %r" % (k, b.shape, fs))
+            final.append(fs)
+            bins.append(b)
+        want = sum(1 << MASK_NAMES.index(w) for w in set(which)) | (16 if labels else 0)
+        P, I = ctypes.c_void_p * max(n, 1), ctypes.c_int * max(n, 1)
+        ip = P(*[im.ctypes.data for im in imgs])
+        bp = P(*[None if b is None else b.ctypes.data for b in bins])
+        hs, ws = I(*[im.shape[0] for im in imgs]), I(*[im.shape[1] for im in imgs])
+        ho = I(*[0 if o is None else int(o[0]) for o in outs])
+        wo = I(*[0 if o is None else int(o[1]) for o in outs])
+        ops = (ctypes.c_int * max(len(post_ops), 1))(*[self.POST_OPS[o] if isinstance(o, str) else int(o) for o in post_ops])
+        t = None if lut is None else np.ascontiguousarray(lut, dtype=np.uint8).reshape(-1, 3)
+        collected = [{"labels": None, "masks": {}} for _ in range(n)] if sink is None else None
+        raised = []
+
+        def on_output(_user, page, k, data, n_bytes):
+            try:
+                if k == 4:
+                    item, name = np.ctypeslib.as_array(data, (n_bytes,)).reshape(final[page]).copy(), "labels"
+                else:
+                    item, name = ctypes.string_at(data, n_bytes), MASK_NAMES[k]
+                if sink is not None:
+                    sink(page, name, item)
+                elif k == 4:
+                    collected[page]["labels"] = item
+                else:
+                    collected[page]["masks"][name] = item
+                return 0
+            except BaseException as exc:          # (an exception must not cross the C frames: stop the call, raise afterwards)
+                raised.append(exc)
+                return 1
+
+        rc = lib().pseg_predict_chain_pages_png(self._h, n, ip, hs, ws, ho, wo, bp, ops, len(post_ops), 1 if exact_labels else 0,
+                                                _ptr(t), 0 if t is None else t.shape[0], int(png_level), want, int(unit_cap),
+                                                CHAIN_SINK(on_output), None)
+        if raised:
+            raise raised[0]
+        _check(rc)
+        return collected
 
     def predict_batch(self, images, dtype=np.int64, out=None):
         """Label maps of a list of (H,W) uint8 pages (sizes may differ); copies overlap compute.
@@ -856,6 +927,24 @@ def batch_units(shapes, cap=8):
     W = (ctypes.c_int * max(n, 1))(*[int(s[1]) for s in shapes])
     first, count = (ctypes.c_int * max(n, 1))(), (ctypes.c_int * max(n, 1))()
     nu = lib().pseg_batch_units(n, H, W, int(cap), first, count, n)
+    _check(min(nu, 0))
+    return [(first[u], count[u]) for u in range(nu)]
+
+
+def chain_units(shapes, out_shapes=None, cap=8):
+    """The units pseg_predict_chain_pages_png cuts a page list into: [(first page, page count), ...]; out_shapes[i]: the final shape
+    of page i's label map or None (host logic, no GPU).  Without out_shapes: batch_units."""
+    n = len(shapes)
+    I = ctypes.c_int * max(n, 1)
+    H, W = I(*[int(s[0]) for s in shapes]), I(*[int(s[1]) for s in shapes])
+    Ho = Wo = None
+    if out_shapes is not None:
+        if len(out_shapes) != n:
+            raise PsegError("out_shapes must have one entry per page")
+        Ho = I(*[0 if o is None else int(o[0]) for o in out_shapes])
+        Wo = I(*[0 if o is None else int(o[1]) for o in out_shapes])
+    first, count = I(), I()
+    nu = lib().pseg_chain_units(n, H, W, Ho, Wo, int(cap), first, count, n)
     _check(min(nu, 0))
     return [(first[u], count[u]) for u in range(nu)]
 
