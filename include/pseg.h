@@ -439,6 +439,28 @@ int pseg_predict_chain_pages_png(pseg_engine* e, int n_pages, const uint8_t* con
  * pseg_batch_units. */
 int pseg_chain_units(int n_pages, const int* H, const int* W, const int* Ho, const int* Wo, int cap,
                      int* unit_first, int* unit_count, int max_units);
+/* pseg_predict_chain_pages_png for lists whose pages differ in shape (every scan scaled by its own line height): same arguments,
+ * same bytes per (page, output), other units.  A page's label map equals the top-left H x W of the label map of the page
+ * zero-padded to its canvas (H, W rounded up to multiples of 32), so the list is cut by CANVAS: pseg_chain_units_mixed brings the
+ * pages of one canvas together and cuts them with pseg_chain_units' rule; the final shapes play no part.  A unit's pages go up
+ * densely.  A bf16 engine without PSEG_CHAIN_EXACT_LABELS pads the pages of a unit of two or more into canvas-sized page slots
+ * (one launch), runs the network stage over the slots and crops every label map back to its page (one launch); any other engine
+ * runs the unit's pages one after the other at their own shapes, on the one canvas.  Resize, vote and boxes follow per page, and
+ * ONE set of encoder launches over the flattened (page, band) pairs writes the masks of all pages of the unit, whatever their final
+ * shapes.  The device changes canvas once per distinct canvas of the list, not once per page.
+ * The sink is called unit by unit in the planner's order, the pages of a unit in the permuted order, `which` ascending; `page` is
+ * the page's index in the caller's list, and every (page, output) arrives exactly once.  Everything else -- checks, staging sets,
+ * the drained return, PSEG_ECALLBACK, the final status check -- is pseg_predict_chain_pages_png's. */
+int pseg_predict_chain_pages_mixed_png(pseg_engine* e, int n_pages, const uint8_t* const* imgs, const int* H, const int* W,
+                                       const int* Ho, const int* Wo, const uint8_t* const* binaries,
+                                       const int* post_ops, int n_post, unsigned flags,
+                                       const uint8_t* lut, int n_lut, int level, unsigned want, int unit_cap,
+                                       pseg_chain_sink sink, void* user);
+/* How that call cuts its list (host logic only).  order[n_pages] (may be NULL): a permutation of the pages -- stable, canvases by
+ * first appearance, list order within a canvas.  The units are pseg_chain_units' cut of the permuted list with the canvas as the
+ * page's shape; unit_first indexes permuted positions.  Returns the number of units; errors as pseg_chain_units. */
+int pseg_chain_units_mixed(int n_pages, const int* H, const int* W, int cap, int* order,
+                           int* unit_first, int* unit_count, int max_units);
 
 /* The code lengths level 1 uses, on the host (pure arithmetic, no device; the device runs the same function): counts[n] ->
  * lengths[n], 0 exactly for a count of 0, none above `limit`, a complete prefix code when two or more symbols occur (one symbol:

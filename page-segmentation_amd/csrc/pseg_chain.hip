@@ -13,11 +13,13 @@
 
 namespace pseg {
 
-// One of the two staging sets of the page chain (pseg_predict_chain_pages_png): everything a unit of same-shape pages touches.
+// One of the two staging sets of the page chain (pseg_predict_chain_pages_png): everything a unit of pages touches.
 struct PagesSet {
-    enum { IMG = 0, LAB = 1, LAB2 = 2, BIN = 3, PNG = 4, NDEV = 5 };
-    uint8_t* d[NDEV] = {nullptr, nullptr, nullptr, nullptr, nullptr};      // pages / network labels / resize + bbox ping-pong / binarisations / encoder workspace
-    size_t d_bytes[NDEV] = {0, 0, 0, 0, 0};
+    enum { IMG = 0, LAB = 1, LAB2 = 2, BIN = 3, PNG = 4, PAD = 5, CLAB = 6, NDEV = 7 };
+    // pages / network labels / resize + bbox ping-pong / binarisations / encoder workspace / mixed units: the pages padded to canvas-sized
+    // page slots / the slots' canvas-sized label maps
+    uint8_t* d[NDEV] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    size_t d_bytes[NDEV] = {0, 0, 0, 0, 0, 0, 0};
     uint8_t* h_in = nullptr;            // page-locked: pages and binarisations of callers with pageable arrays
     uint8_t* h_out = nullptr;           // page-locked: the unit's encoded streams (+ label maps), grown to the bytes units really have
     unsigned long long* h_tot = nullptr;   // page-locked: [pages][4] stream sizes
@@ -27,6 +29,9 @@ struct PagesSet {
 struct ChainPagesState {
     PagesSet set[2];
     uint8_t* d_lut = nullptr;
+    MixedPage* d_tab = nullptr;         // the page table of a mixed call (one entry per page of the list, in the planner's order) ...
+    MixedPage* h_tab = nullptr;         // ... and its page-locked source
+    size_t tab_entries = 0;
 };
 
 struct ChainState {
@@ -50,6 +55,10 @@ static int censure(ChainState& c, int slot, size_t bytes) {
 
 // the staging sets' memory (device and page-locked); the events stay.  The caller has waited for the device.
 static void pages_release(ChainPagesState& p) {
+    if (p.d_tab) (void)hipFree(p.d_tab);
+    if (p.h_tab) (void)hipHostFree(p.h_tab);
+    p.d_tab = p.h_tab = nullptr;
+    p.tab_entries = 0;
     for (PagesSet& s : p.set) {
         for (int i = 0; i < PagesSet::NDEV; ++i) { if (s.d[i]) (void)hipFree(s.d[i]); s.d[i] = nullptr; s.d_bytes[i] = 0; }
         if (s.h_in) (void)hipHostFree(s.h_in);
@@ -88,6 +97,34 @@ void chain_free(Engine& e) {
 
 __global__ void chain_widen_kernel(const uint8_t* in, int64_t* out, size_t n) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) out[i] = in[i];
+}
+
+// Mixed units: every page of the unit (blockIdx.y) from its dense H x W x C bytes into its canvas-sized slot, zeros outside the page.
+// Four bytes per thread: a slot's rows are multiples of 32 bytes, so a word never crosses a row.
+__global__ __launch_bounds__(256) void pages_pad_kernel(const uint8_t* img, uint8_t* padded, const MixedPage* tab, int Hp, int Wp, int C) {
+    const MixedPage& m = tab[blockIdx.y];
+    const size_t rowb = (size_t)Wp * C, n4 = (size_t)Hp * rowb / 4, wb = (size_t)m.W * C;
+    const uint8_t* src = img + m.img_off;
+    uint32_t* dst = (uint32_t*)(padded + (size_t)blockIdx.y * Hp * rowb);
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t b = i * 4, r = b / rowb, c = b - r * rowb;
+        uint32_t v = 0;
+        if (r < (size_t)m.H)
+            for (int j = 0; j < 4; ++j)
+                if (c + j < wb) v |= (uint32_t)src[r * wb + c + j] << (8 * j);
+        dst[i] = v;
+    }
+}
+// ... and back: the top-left H x W of every slot's canvas-sized label map, densely, where resize, vote and encoder expect the page's map
+__global__ __launch_bounds__(256) void pages_crop_kernel(const uint8_t* clab, uint8_t* lab, const MixedPage* tab, int Hp, int Wp) {
+    const MixedPage& m = tab[blockIdx.y];
+    const uint8_t* src = clab + (size_t)blockIdx.y * Hp * Wp;
+    uint8_t* dst = lab + m.lab_off;
+    const size_t n = (size_t)m.H * m.W, w = (size_t)m.W;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t r = i / w;
+        dst[i] = src[r * Wp + (i - r * w)];
+    }
 }
 
 }  // namespace pseg
@@ -269,6 +306,39 @@ static bool pages_is_pinned(const void* p) {
 }
 static inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
+// The mixed planner: pages by canvas (stable: canvases by first appearance, list order within one), then plan_units over the canvases
+static void plan_units_mixed(int n, const int* H, const int* W, int cap, std::vector<int>& order, std::vector<int>& ub, std::vector<int>& ug) {
+    std::vector<int> Hc(n), Wc(n), first(n);
+    std::vector<std::pair<int, int>> seen;
+    for (int i = 0; i < n; ++i) {
+        const std::pair<int, int> cv(round_up(H[i], 32), round_up(W[i], 32));
+        size_t k = 0;
+        while (k < seen.size() && seen[k] != cv) ++k;
+        if (k == seen.size()) seen.push_back(cv);
+        first[i] = (int)k;
+    }
+    order.resize(n);
+    for (int i = 0; i < n; ++i) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return first[a] < first[b]; });
+    for (int i = 0; i < n; ++i) { Hc[i] = seen[first[order[i]]].first; Wc[i] = seen[first[order[i]]].second; }
+    plan_units(n, Hc.data(), Wc.data(), nullptr, nullptr, cap, ub, ug);
+}
+
+extern "C" int pseg_chain_units_mixed(int n_pages, const int* H, const int* W, int cap, int* order, int* unit_first, int* unit_count, int max_units) {
+    if (n_pages < 0 || (n_pages > 0 && (!H || !W)) || cap < 1) return fail(PSEG_EINVAL, "bad argument");
+    for (int i = 0; i < n_pages; ++i)
+        if (H[i] <= 0 || W[i] <= 0 || H[i] > 0x7FFFFFE0 || W[i] > 0x7FFFFFE0) return fail(PSEG_EINVAL, "page %d: bad shape %d x %d", i, H[i], W[i]);
+    std::vector<int> ord, ub, ug;
+    plan_units_mixed(n_pages, H, W, cap, ord, ub, ug);
+    if ((int)ub.size() > max_units && (unit_first || unit_count)) return fail(PSEG_EINVAL, "%zu units, room for %d", ub.size(), max_units);
+    for (int i = 0; i < n_pages && order; ++i) order[i] = ord[i];
+    for (size_t u = 0; u < ub.size(); ++u) {
+        if (unit_first) unit_first[u] = ub[u];
+        if (unit_count) unit_count[u] = ug[u];
+    }
+    return (int)ub.size();
+}
+
 extern "C" int pseg_chain_units(int n_pages, const int* H, const int* W, const int* Ho, const int* Wo, int cap, int* unit_first, int* unit_count,
                                 int max_units) {
     if (n_pages < 0 || (n_pages > 0 && (!H || !W)) || cap < 1) return fail(PSEG_EINVAL, "bad argument");
@@ -282,10 +352,11 @@ extern "C" int pseg_chain_units(int n_pages, const int* H, const int* W, const i
     return (int)ub.size();
 }
 
-extern "C" int pseg_predict_chain_pages_png(pseg_engine* h, int n, const uint8_t* const* imgs, const int* H, const int* W, const int* Ho,
-                                            const int* Wo, const uint8_t* const* binaries, const int* post_ops, int n_post, unsigned flags,
-                                            const uint8_t* lut, int n_lut, int level, unsigned want, int unit_cap, pseg_chain_sink sink,
-                                            void* user) {
+// The body of both page-list entries.  mixed = false: units are runs of same-shape pages in list order (pseg_chain_units).  mixed = true:
+// units are pages of one canvas (pseg_chain_units_mixed); `ord` maps a position of the planner's order to the caller's page.
+static int chain_pages_run(pseg_engine* h, int n, const uint8_t* const* imgs, const int* H, const int* W, const int* Ho, const int* Wo,
+                           const uint8_t* const* binaries, const int* post_ops, int n_post, unsigned flags, const uint8_t* lut, int n_lut, int level,
+                           unsigned want, int unit_cap, pseg_chain_sink sink, void* user, const bool mixed) {
     if (!h) return fail(PSEG_EINVAL, "NULL engine");
     KnobScope knob_scope(h->e);
     Engine& e = h->e;
@@ -304,6 +375,7 @@ extern "C" int pseg_predict_chain_pages_png(pseg_engine* h, int n, const uint8_t
         PSEG_TRY(chain_check(e, i, imgs[i], H[i], W[i], Ho ? Ho[i] : 0, Wo ? Wo[i] : 0, binaries ? binaries[i] : nullptr, post_ops, n_post, flags,
                              want_png, want_png, lut, n_lut, level, &req[i]));
         if (want_png && pseg_png_bound_lv(req[i].Hl, req[i].Wl, 3, 0, level) == 0) return fail(PSEG_EINVAL, "page %d: png: a row of %d pixels is too long", i, req[i].Wl);
+        if (mixed && (H[i] > 0x7FFFFFE0 || W[i] > 0x7FFFFFE0)) return fail(PSEG_EINVAL, "page %d: bad shape %d x %d", i, H[i], W[i]);
         any_bin |= req[i].need_bin;
         two_maps |= req[i].resize;
     }
@@ -326,8 +398,8 @@ extern "C" int pseg_predict_chain_pages_png(pseg_engine* h, int n, const uint8_t
     }
     hipStream_t s_in = nullptr, s_out = nullptr, st = e.stream;
     PSEG_TRY(batch_copy_streams(e, &s_in, &s_out));
-    // units: pseg_predict_batch's rule over (H, W, final H, final W).  A bf16 engine's unit goes through the network as page slots
-    // (run_bf16_pages) unless the label-exact mode is asked for; any unit's masks are encoded in one set of launches.
+    // units: pseg_predict_batch's rule over (H, W, final H, final W), or over the canvas.  A bf16 engine's unit goes through the network
+    // as page slots (run_bf16_pages) unless the label-exact mode is asked for; any unit's masks are encoded in one set of launches.
     const bool exact = (flags & PSEG_CHAIN_EXACT_LABELS) && e.mode == PSEG_MODE_BF16;
     int cap = batch_unit_cap(e, n, H, W);     // (uploads the weights: the plans decide whether pages travel as page slots)
     if (cap < 0) return cap;
@@ -341,29 +413,64 @@ extern "C" int pseg_predict_chain_pages_png(pseg_engine* h, int n, const uint8_t
             cap = fit_unit_slots(e, hm, wm, cap);
         }
     } else if (!page_slots) cap = std::min(8, std::max(1, n / 4));       // (the encoder's launches still take a unit's pages together)
-    std::vector<int> ub, ug;
-    plan_units(n, H, W, Ho, Wo, cap, ub, ug);
+    std::vector<int> ord, ub, ug;
+    if (mixed) plan_units_mixed(n, H, W, cap, ord, ub, ug);
+    else {
+        ord.resize(n);
+        for (int i = 0; i < n; ++i) ord[i] = i;
+        plan_units(n, H, W, Ho, Wo, cap, ub, ug);
+    }
     const int nu = (int)ub.size();
-    // per unit: shapes, strides and the encoder's layout
-    struct Unit { size_t npx, nl, nla, lab_stride; bool slots; PngPages L; };
+    // per position of the planner's order: where the page, its maps and its binarisation lie in the unit's staging set (tab; a mixed
+    // call's kernels read it on the device); per unit: the encoder's layout
+    struct Unit { bool slots; PngPages L; PngPagesMixed M; };
     std::vector<Unit> un(nu);
-    size_t mx[PagesSet::NDEV] = {0, 0, 0, 0, 0}, mx_in = 0, mx_tot = 0;
+    std::vector<MixedPage> tab(n);
+    std::vector<size_t> lab2_off(n, 0);
+    size_t mx[PagesSet::NDEV] = {0, 0, 0, 0, 0, 0, 0}, mx_in = 0, mx_tot = 0;
     for (int u = 0; u < nu; ++u) {
-        const int i0 = ub[u], g = ug[u];
+        const int i0 = ub[u], g = ug[u], p0 = ord[i0];
         Unit& q = un[u];
-        q.npx = (size_t)H[i0] * W[i0];
-        q.nl = (size_t)req[i0].Hl * req[i0].Wl;
-        q.nla = up256(q.nl);                   // the vote kernels want 4-byte aligned maps
-        q.slots = page_slots && g > 1 && q.npx % 4 == 0;      // (page slots write the unit's maps one behind the other)
-        q.lab_stride = q.slots ? q.npx : up256(q.npx);
+        // (same-shape page slots write the unit's maps one behind the other; mixed slots are canvases, cropped to aligned maps)
+        q.slots = page_slots && g > 1 && (mixed || ((size_t)H[p0] * W[p0]) % 4 == 0);
         q.L = PngPages{0, 0, 0, 0, 0, 0, 0, 0};
-        if (want_png) PSEG_TRY(png_pages_layout(req[i0].Hl, req[i0].Wl, level, nout, g, &q.L));
-        const size_t in_b = (size_t)g * (q.npx * e.in_ch + (req[i0].need_bin ? q.nl : 0));
-        mx[PagesSet::IMG] = std::max(mx[PagesSet::IMG], (size_t)g * q.npx * e.in_ch);
-        mx[PagesSet::LAB] = std::max(mx[PagesSet::LAB], (size_t)g * up256(q.npx));
-        if (two_maps) mx[PagesSet::LAB2] = std::max(mx[PagesSet::LAB2], (size_t)g * 2 * q.nla);
-        if (any_bin) mx[PagesSet::BIN] = std::max(mx[PagesSet::BIN], (size_t)g * q.nla);
-        mx[PagesSet::PNG] = std::max(mx[PagesSet::PNG], q.L.bytes);
+        q.M = PngPagesMixed{0, 0, 0};
+        size_t o_img = 0, o_lab = 0, o_bin = 0, o_lab2 = 0, lab_b = 0, in_b = 0;
+        for (int k = 0; k < g; ++k) {
+            const int pi = ord[i0 + k];
+            MixedPage& m = tab[i0 + k];
+            memset(&m, 0, sizeof m);
+            const size_t npx = (size_t)H[pi] * W[pi], nl = (size_t)req[pi].Hl * req[pi].Wl, nla = up256(nl);   // (the vote kernels want 4-byte aligned maps)
+            m.H = H[pi]; m.W = W[pi]; m.Hl = req[pi].Hl; m.Wl = req[pi].Wl;
+            m.img_off = o_img; m.lab_off = o_lab; m.bin_off = o_bin;
+            lab2_off[i0 + k] = o_lab2;
+            o_img += mixed ? up256(npx * e.in_ch) : npx * e.in_ch;
+            o_lab += !mixed && q.slots ? npx : up256(npx);
+            lab_b += up256(npx);
+            o_bin += nla;
+            o_lab2 += 2 * nla;
+            in_b += npx * e.in_ch + (req[pi].need_bin ? nl : 0);
+            // where the page's final map will lie: compute()'s walk through resize and post-processors, ahead of time
+            int where = req[pi].resize ? 1 : 0;                        // 0: LAB, 1: bufA, 2: bufB
+            for (int i = 0; i < n_post; ++i)
+                if (post_ops[i] == PSEG_POST_BBOX) where = where == 1 ? 2 : 1;
+            m.pred_sel = where ? 1 : 0;
+            m.pred_off = where == 0 ? m.lab_off : lab2_off[i0 + k] + (where == 2 ? nla : 0);
+        }
+        if (want_png) {
+            if (mixed) PSEG_TRY(png_pages_layout_mixed(level, nout, g, &tab[i0], &q.M));
+            else PSEG_TRY(png_pages_layout(req[p0].Hl, req[p0].Wl, level, nout, g, &q.L));
+        }
+        mx[PagesSet::IMG] = std::max(mx[PagesSet::IMG], o_img);
+        mx[PagesSet::LAB] = std::max(mx[PagesSet::LAB], lab_b);
+        if (two_maps) mx[PagesSet::LAB2] = std::max(mx[PagesSet::LAB2], o_lab2);
+        if (any_bin) mx[PagesSet::BIN] = std::max(mx[PagesSet::BIN], o_bin);
+        mx[PagesSet::PNG] = std::max(mx[PagesSet::PNG], mixed ? q.M.bytes : q.L.bytes);
+        if (mixed && q.slots) {
+            const size_t cpx = (size_t)round_up(H[p0], 32) * round_up(W[p0], 32);
+            mx[PagesSet::PAD] = std::max(mx[PagesSet::PAD], (size_t)g * cpx * e.in_ch);
+            mx[PagesSet::CLAB] = std::max(mx[PagesSet::CLAB], (size_t)g * cpx);
+        }
         mx_in = std::max(mx_in, in_b);
         mx_tot = std::max(mx_tot, (size_t)g * 4 * sizeof(unsigned long long));
     }
@@ -384,78 +491,128 @@ extern "C" int pseg_predict_chain_pages_png(pseg_engine* h, int n, const uint8_t
         if (!ps.d_lut) PSEG_HIP(hipMalloc((void**)&ps.d_lut, 768));
         PSEG_HIP(hipMemcpyAsync(ps.d_lut, lut, (size_t)n_lut * 3, hipMemcpyHostToDevice, s_in));      // (ordered in front of every unit's up event)
     }
+    if (mixed) {
+        // the whole call's page table goes up once, on the copy stream, in front of every unit's up event: no unit waits for it
+        if (ps.tab_entries < (size_t)n) {
+            if (ps.d_tab) (void)hipFree(ps.d_tab);
+            if (ps.h_tab) (void)hipHostFree(ps.h_tab);
+            ps.d_tab = ps.h_tab = nullptr;
+            ps.tab_entries = 0;
+            if (hipMalloc((void**)&ps.d_tab, (size_t)n * sizeof(MixedPage)) != hipSuccess || hipHostMalloc((void**)&ps.h_tab, (size_t)n * sizeof(MixedPage), hipHostMallocDefault) != hipSuccess) {
+                (void)hipGetLastError();
+                return fail(PSEG_ENOMEM, "page chain: no memory for the table of %d pages", n);
+            }
+            ps.tab_entries = (size_t)n;
+        }
+        memcpy(ps.h_tab, tab.data(), (size_t)n * sizeof(MixedPage));
+        PSEG_HIP(hipMemcpyAsync(ps.d_tab, ps.h_tab, (size_t)n * sizeof(MixedPage), hipMemcpyHostToDevice, s_in));
+    }
     auto upload = [&](int u) -> int {          // unit u -> set u % 2
         PagesSet& s = ps.set[u & 1];
-        const Unit& q = un[u];
         const int i0 = ub[u], g = ug[u];
-        const size_t pb = q.npx * e.in_ch;
-        const bool bin = req[i0].need_bin;
+        const bool bin = req[ord[i0]].need_bin;                 // (the same for every page of a call)
         PSEG_HIP(hipStreamWaitEvent(s_in, s.done, 0));         // the set's pages and binarisations have been read (unit u - 2)
         bool pinned = true;
-        for (int k = 0; k < g; ++k) pinned = pinned && pages_is_pinned(imgs[i0 + k]) && (!bin || pages_is_pinned(binaries[i0 + k]));
+        for (int k = 0; k < g; ++k) pinned = pinned && pages_is_pinned(imgs[ord[i0 + k]]) && (!bin || pages_is_pinned(binaries[ord[i0 + k]]));
         if (pinned) {
             for (int k = 0; k < g; ++k) {
-                PSEG_HIP(hipMemcpyAsync(s.d[PagesSet::IMG] + (size_t)k * pb, imgs[i0 + k], pb, hipMemcpyHostToDevice, s_in));
-                if (bin) PSEG_HIP(hipMemcpyAsync(s.d[PagesSet::BIN] + (size_t)k * q.nla, binaries[i0 + k], q.nl, hipMemcpyHostToDevice, s_in));
+                const MixedPage& m = tab[i0 + k];
+                const int pi = ord[i0 + k];
+                PSEG_HIP(hipMemcpyAsync(s.d[PagesSet::IMG] + m.img_off, imgs[pi], (size_t)m.H * m.W * e.in_ch, hipMemcpyHostToDevice, s_in));
+                if (bin) PSEG_HIP(hipMemcpyAsync(s.d[PagesSet::BIN] + m.bin_off, binaries[pi], (size_t)m.Hl * m.Wl, hipMemcpyHostToDevice, s_in));
             }
         } else {                               // through the page-locked slot: last read by the uploads of unit u - 2
             PSEG_HIP(hipEventSynchronize(s.up));
-            uint8_t* hb = s.h_in + (size_t)g * pb;
+            size_t hp = 0;                     // the pages densely, the binarisations densely behind them
             for (int k = 0; k < g; ++k) {
-                memcpy(s.h_in + (size_t)k * pb, imgs[i0 + k], pb);
-                if (bin) memcpy(hb + (size_t)k * q.nl, binaries[i0 + k], q.nl);
+                const size_t pb = (size_t)tab[i0 + k].H * tab[i0 + k].W * e.in_ch;
+                memcpy(s.h_in + hp, imgs[ord[i0 + k]], pb);
+                hp += pb;
             }
-            PSEG_HIP(hipMemcpyAsync(s.d[PagesSet::IMG], s.h_in, (size_t)g * pb, hipMemcpyHostToDevice, s_in));
-            for (int k = 0; k < g && bin; ++k)
-                PSEG_HIP(hipMemcpyAsync(s.d[PagesSet::BIN] + (size_t)k * q.nla, hb + (size_t)k * q.nl, q.nl, hipMemcpyHostToDevice, s_in));
+            const size_t all_pages = hp;
+            for (int k = 0; k < g && bin; ++k) {
+                const size_t nl = (size_t)tab[i0 + k].Hl * tab[i0 + k].Wl;
+                memcpy(s.h_in + hp, binaries[ord[i0 + k]], nl);
+                hp += nl;
+            }
+            if (!mixed) PSEG_HIP(hipMemcpyAsync(s.d[PagesSet::IMG], s.h_in, all_pages, hipMemcpyHostToDevice, s_in));
+            hp = 0;
+            for (int k = 0; k < g && mixed; ++k) {             // (a mixed unit's pages start at aligned offsets)
+                const size_t pb = (size_t)tab[i0 + k].H * tab[i0 + k].W * e.in_ch;
+                PSEG_HIP(hipMemcpyAsync(s.d[PagesSet::IMG] + tab[i0 + k].img_off, s.h_in + hp, pb, hipMemcpyHostToDevice, s_in));
+                hp += pb;
+            }
+            hp = all_pages;
+            for (int k = 0; k < g && bin; ++k) {
+                const size_t nl = (size_t)tab[i0 + k].Hl * tab[i0 + k].Wl;
+                PSEG_HIP(hipMemcpyAsync(s.d[PagesSet::BIN] + tab[i0 + k].bin_off, s.h_in + hp, nl, hipMemcpyHostToDevice, s_in));
+                hp += nl;
+            }
         }
         PSEG_HIP(hipEventRecord(s.up, s_in));
         return PSEG_OK;
     };
-    std::vector<uint8_t*> fin(nu, nullptr);    // page 0's final label map of the unit; fin_stride: bytes to the next page's
-    std::vector<size_t> fin_stride(nu, 0);
+    std::vector<uint8_t*> fin(n, nullptr);     // per position: the page's final label map
     auto compute = [&](int u) -> int {
         PagesSet& s = ps.set[u & 1];
         const Unit& q = un[u];
-        const int i0 = ub[u], g = ug[u], Hi = H[i0], Wi = W[i0], Hl = req[i0].Hl, Wl = req[i0].Wl;
-        const size_t pb = q.npx * e.in_ch;
+        const int i0 = ub[u], g = ug[u], Hc = round_up(H[ord[i0]], 32), Wc = round_up(W[ord[i0]], 32);
         // a canvas change re-allocates / clears the activation tensors: the previous unit must have left them
-        if (round_up(Hi, 32) != e.Hp || round_up(Wi, 32) != e.Wp || (q.slots && g > e.pages)) PSEG_HIP(hipStreamSynchronize(st));
+        if (Hc != e.Hp || Wc != e.Wp || (q.slots && g > e.pages)) PSEG_HIP(hipStreamSynchronize(st));
         PSEG_HIP(hipStreamWaitEvent(st, s.up, 0));
         PSEG_HIP(hipStreamWaitEvent(st, s.down, 0));           // the streams and maps of unit u - 2 have left the set
         // 1. the network
-        if (q.slots) PSEG_TRY(predict_device_pages(e, s.d[PagesSet::IMG], g, Hi, Wi, nullptr, s.d[PagesSet::LAB], st));
+        if (q.slots && mixed) {
+            // pad every page into its canvas-sized slot, run the slots, crop every label map back to its page: three steps whatever g
+            const size_t cpx = (size_t)Hc * Wc;
+            if ((size_t)g * cpx * e.in_ch > s.d_bytes[PagesSet::PAD] || (size_t)g * cpx > s.d_bytes[PagesSet::CLAB])
+                return fail(PSEG_EHIP, "page chain: the padded slots of unit %d outgrow their staging", u);
+            const unsigned bx = (unsigned)std::min<size_t>((cpx * e.in_ch / 4 + 255) / 256, 1024);
+            pages_pad_kernel<<<dim3(bx, g), 256, 0, st>>>(s.d[PagesSet::IMG], s.d[PagesSet::PAD], ps.d_tab + i0, Hc, Wc, e.in_ch);
+            PSEG_HIP(hipGetLastError());
+            PSEG_TRY(predict_device_pages(e, s.d[PagesSet::PAD], g, Hc, Wc, nullptr, s.d[PagesSet::CLAB], st));
+            pages_crop_kernel<<<dim3((unsigned)std::min<size_t>((cpx + 255) / 256, 1024), g), 256, 0, st>>>(s.d[PagesSet::CLAB], s.d[PagesSet::LAB], ps.d_tab + i0, Hc, Wc);
+            PSEG_HIP(hipGetLastError());
+        } else if (q.slots) PSEG_TRY(predict_device_pages(e, s.d[PagesSet::IMG], g, H[ord[i0]], W[ord[i0]], nullptr, s.d[PagesSet::LAB], st));
         else
-            for (int k = 0; k < g; ++k) {
-                const uint8_t* im = s.d[PagesSet::IMG] + (size_t)k * pb;
-                uint8_t* lab = s.d[PagesSet::LAB] + (size_t)k * q.lab_stride;
-                if (exact) PSEG_TRY(pseg_predict_exact_labels_device(h, im, Hi, Wi, lab, nullptr, nullptr, st));
-                else PSEG_TRY(predict_device(e, im, Hi, Wi, nullptr, nullptr, nullptr, lab, st, nullptr));
+            for (int k = 0; k < g; ++k) {                      // (a mixed unit's pages share the canvas: no change between them)
+                const MixedPage& m = tab[i0 + k];
+                const uint8_t* im = s.d[PagesSet::IMG] + m.img_off;
+                uint8_t* lab = s.d[PagesSet::LAB] + m.lab_off;
+                if (exact) PSEG_TRY(pseg_predict_exact_labels_device(h, im, m.H, m.W, lab, nullptr, nullptr, st));
+                else PSEG_TRY(predict_device(e, im, m.H, m.W, nullptr, nullptr, nullptr, lab, st, nullptr));
             }
         // 2./3. per page, in chain_run's order: resize, then the post-processors (the vote's workspace is one per device)
         for (int k = 0; k < g; ++k) {
-            uint8_t* cur = s.d[PagesSet::LAB] + (size_t)k * q.lab_stride;
-            uint8_t* const bufA = two_maps ? s.d[PagesSet::LAB2] + (size_t)k * 2 * q.nla : nullptr;
-            uint8_t* const bufB = two_maps ? bufA + q.nla : nullptr;
-            if (req[i0].resize) {
-                PSEG_TRY(pseg_resize_nearest_device(e.device, cur, Hi, Wi, 1, bufA, Hl, Wl, st));
+            const MixedPage& m = tab[i0 + k];
+            const size_t nla = up256((size_t)m.Hl * m.Wl);
+            uint8_t* cur = s.d[PagesSet::LAB] + m.lab_off;
+            uint8_t* const bufA = two_maps ? s.d[PagesSet::LAB2] + lab2_off[i0 + k] : nullptr;
+            uint8_t* const bufB = two_maps ? bufA + nla : nullptr;
+            if (req[ord[i0 + k]].resize) {
+                PSEG_TRY(pseg_resize_nearest_device(e.device, cur, m.H, m.W, 1, bufA, m.Hl, m.Wl, st));
                 cur = bufA;
             }
             for (int i = 0; i < n_post; ++i) {
                 if (post_ops[i] == PSEG_POST_CC_VOTE) {
-                    PSEG_TRY(pseg_cc_vote_device_u8(e.device, cur, s.d[PagesSet::BIN] + (size_t)k * q.nla, Hl, Wl, e.n_classes, st));
+                    PSEG_TRY(pseg_cc_vote_device_u8(e.device, cur, s.d[PagesSet::BIN] + m.bin_off, m.Hl, m.Wl, e.n_classes, st));
                 } else {
                     uint8_t* const dst = cur == bufA ? bufB : bufA;
-                    PSEG_TRY(pseg_bbox_fill_device_u8(e.device, cur, dst, Hl, Wl, e.n_classes, st));
+                    PSEG_TRY(pseg_bbox_fill_device_u8(e.device, cur, dst, m.Hl, m.Wl, e.n_classes, st));
                     cur = dst;
                 }
             }
-            if (k == 0) { fin[u] = cur; fin_stride[u] = cur == s.d[PagesSet::LAB] ? q.lab_stride : 2 * q.nla; }
+            if (cur != s.d[m.pred_sel ? PagesSet::LAB2 : PagesSet::LAB] + m.pred_off) return fail(PSEG_EHIP, "page chain: the final map of page %d is not where the table says", ord[i0 + k]);
+            fin[i0 + k] = cur;
         }
         // 4. the masks of all pages as PNG streams: one set of launches; the sizes go to page-locked memory
         if (want_png) {
-            PSEG_TRY(png_pages_enqueue(q.L, s.d[PagesSet::PNG], fin[u], fin_stride[u], s.d[PagesSet::BIN], q.nla, ps.d_lut, n_lut, Hl, Wl, level, nout,
-                                       mask_id, g, st));
+            if (mixed)
+                PSEG_TRY(png_pages_enqueue_mixed(q.M, &tab[i0], ps.d_tab + i0, g, s.d[PagesSet::PNG], s.d_bytes[PagesSet::PNG], s.d[PagesSet::LAB],
+                                                 s.d[PagesSet::LAB2], s.d[PagesSet::BIN], ps.d_lut, n_lut, level, nout, mask_id, st));
+            else
+                PSEG_TRY(png_pages_enqueue(q.L, s.d[PagesSet::PNG], fin[i0], g > 1 ? (size_t)(tab[i0 + 1].pred_off - tab[i0].pred_off) : 0, s.d[PagesSet::BIN],
+                                           up256((size_t)tab[i0].Hl * tab[i0].Wl), ps.d_lut, n_lut, tab[i0].Hl, tab[i0].Wl, level, nout, mask_id, g, st));
             PSEG_HIP(hipMemcpyAsync(s.h_tot, s.d[PagesSet::PNG], (size_t)g * 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
         }
         PSEG_HIP(hipEventRecord(s.done, st));
@@ -468,7 +625,7 @@ extern "C" int pseg_predict_chain_pages_png(pseg_engine* h, int n, const uint8_t
     auto download = [&](int u) -> int {
         PagesSet& s = ps.set[u & 1];
         const Unit& q = un[u];
-        const int g = ug[u];
+        const int i0 = ub[u], g = ug[u];
         PSEG_HIP(hipEventSynchronize(s.done));                 // the sizes are here
         std::vector<size_t>& of = offs[u & 1];
         of.assign((size_t)g * 5 + 1, 0);
@@ -476,44 +633,47 @@ extern "C" int pseg_predict_chain_pages_png(pseg_engine* h, int n, const uint8_t
         tt.assign((size_t)g * 4, 0);
         size_t pos = 0;
         for (int k = 0; k < g; ++k) {
+            const size_t bound = mixed ? (size_t)tab[i0 + k].bound : q.L.bound;
             for (int j = 0; j < 4; ++j) {
                 of[(size_t)k * 5 + j] = pos;
                 if (j >= nout) continue;
                 const unsigned long long t = s.h_tot[(size_t)k * 4 + j];
-                if (t < 80 || t > q.L.bound) return fail(PSEG_EHIP, "png: encoded size %llu outside (0, bound %zu] (page %d)", t, q.L.bound, ub[u] + k);
+                if (t < 80 || t > bound) return fail(PSEG_EHIP, "png: encoded size %llu outside (0, bound %zu] (page %d)", t, bound, ord[i0 + k]);
                 tt[(size_t)k * 4 + j] = (size_t)t;
                 pos += ((size_t)t + 7) & ~(size_t)7;
             }
             of[(size_t)k * 5 + 4] = pos;
-            if (want_lab) pos += (q.nl + 7) & ~(size_t)7;
+            if (want_lab) pos += ((size_t)tab[i0 + k].Hl * tab[i0 + k].Wl + 7) & ~(size_t)7;
         }
         of[(size_t)g * 5] = pos;
         // the slot was handed to the sink by deliver(u - 2): idle.  It grows to what units really hold, with a quarter of headroom.
         if (s.h_out_bytes < pos) PSEG_TRY(pages_ensure_host(&s.h_out, &s.h_out_bytes, pos + pos / 4 + 4096));
         for (int k = 0; k < g; ++k) {
+            const MixedPage& m = tab[i0 + k];
             for (int j = 0; j < nout; ++j) {
-                const uint8_t* src = s.d[PagesSet::PNG] + q.L.head + (size_t)(g > 1 ? k : 0) * q.L.page + (size_t)j * q.L.per + q.L.slots_b + q.L.meta_b + q.L.offs_b;
+                const uint8_t* src = mixed ? s.d[PagesSet::PNG] + m.ws_off + (size_t)j * m.per + m.slots_b + m.meta_b + m.offs_b
+                                           : s.d[PagesSet::PNG] + q.L.head + (size_t)(g > 1 ? k : 0) * q.L.page + (size_t)j * q.L.per + q.L.slots_b + q.L.meta_b + q.L.offs_b;
                 PSEG_HIP(hipMemcpyAsync(s.h_out + of[(size_t)k * 5 + j], src, tt[(size_t)k * 4 + j], hipMemcpyDeviceToHost, s_out));
             }
-            if (want_lab) PSEG_HIP(hipMemcpyAsync(s.h_out + of[(size_t)k * 5 + 4], fin[u] + (size_t)k * fin_stride[u], q.nl, hipMemcpyDeviceToHost, s_out));
+            if (want_lab) PSEG_HIP(hipMemcpyAsync(s.h_out + of[(size_t)k * 5 + 4], fin[i0 + k], (size_t)m.Hl * m.Wl, hipMemcpyDeviceToHost, s_out));
         }
         PSEG_HIP(hipEventRecord(s.down, s_out));
         return PSEG_OK;
     };
-    auto deliver = [&](int u) -> int {         // chunk CRCs, then the sink: page order, `which` ascending; on the calling thread
+    auto deliver = [&](int u) -> int {         // chunk CRCs, then the sink: the planner's order, `which` ascending; on the calling thread
         PagesSet& s = ps.set[u & 1];
-        const Unit& q = un[u];
         const std::vector<size_t>& of = offs[u & 1];
         PSEG_HIP(hipEventSynchronize(s.down));
         for (int k = 0; k < ug[u]; ++k) {
+            const int pi = ord[ub[u] + k];
             for (int j = 0; j < nout; ++j) {
                 uint8_t* p = s.h_out + of[(size_t)k * 5 + j];
                 const size_t t = tot[u & 1][(size_t)k * 4 + j];
                 PSEG_TRY(png_finish_host(p, t));
-                if (sink(user, ub[u] + k, mask_id[j], p, t) != 0) return fail(PSEG_ECALLBACK, "the sink stopped the call at page %d, output %d", ub[u] + k, mask_id[j]);
+                if (sink(user, pi, mask_id[j], p, t) != 0) return fail(PSEG_ECALLBACK, "the sink stopped the call at page %d, output %d", pi, mask_id[j]);
             }
-            if (want_lab && sink(user, ub[u] + k, 4, s.h_out + of[(size_t)k * 5 + 4], q.nl) != 0)
-                return fail(PSEG_ECALLBACK, "the sink stopped the call at page %d, output 4", ub[u] + k);
+            if (want_lab && sink(user, pi, 4, s.h_out + of[(size_t)k * 5 + 4], (size_t)tab[ub[u] + k].Hl * tab[ub[u] + k].Wl) != 0)
+                return fail(PSEG_ECALLBACK, "the sink stopped the call at page %d, output 4", pi);
         }
         return PSEG_OK;
     };
@@ -528,4 +688,18 @@ extern "C" int pseg_predict_chain_pages_png(pseg_engine* h, int n, const uint8_t
     PSEG_TRY(deliver(nu - 1));
     PSEG_HIP(hipStreamSynchronize(s_out));
     return engine_status(e, st);
+}
+
+extern "C" int pseg_predict_chain_pages_png(pseg_engine* h, int n, const uint8_t* const* imgs, const int* H, const int* W, const int* Ho,
+                                            const int* Wo, const uint8_t* const* binaries, const int* post_ops, int n_post, unsigned flags,
+                                            const uint8_t* lut, int n_lut, int level, unsigned want, int unit_cap, pseg_chain_sink sink,
+                                            void* user) {
+    return chain_pages_run(h, n, imgs, H, W, Ho, Wo, binaries, post_ops, n_post, flags, lut, n_lut, level, want, unit_cap, sink, user, false);
+}
+
+extern "C" int pseg_predict_chain_pages_mixed_png(pseg_engine* h, int n, const uint8_t* const* imgs, const int* H, const int* W, const int* Ho,
+                                                  const int* Wo, const uint8_t* const* binaries, const int* post_ops, int n_post, unsigned flags,
+                                                  const uint8_t* lut, int n_lut, int level, unsigned want, int unit_cap, pseg_chain_sink sink,
+                                                  void* user) {
+    return chain_pages_run(h, n, imgs, H, W, Ho, Wo, binaries, post_ops, n_post, flags, lut, n_lut, level, want, unit_cap, sink, user, true);
 }

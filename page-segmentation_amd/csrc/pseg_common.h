@@ -296,6 +296,26 @@ int png_pages_layout(int H, int W, int level, int nout, int pages, PngPages* L);
 int png_pages_enqueue(const PngPages& L, uint8_t* d_ws, const uint8_t* d_pred, size_t page_pred, const uint8_t* d_bin, size_t page_bin,
                       const uint8_t* d_lut, int n_lut, int H, int W, int level, int nout, const int mask_id[4], int pages, hipStream_t st);
 int png_finish_host(uint8_t* png, size_t total);
+// One page of a mixed unit (pseg_predict_chain_pages_mixed_png): pages of one canvas, each with its own shape.  The chain fills the
+// first block, png_pages_layout_mixed the encoder's.  All offsets are bytes from the start of the staging block they name.
+struct MixedPage {
+    int H, W;                                 // the network's page; dense in IMG at img_off, its dense H x W label map in LAB at lab_off
+    int Hl, Wl;                               // the final label map: in LAB (pred_sel 0) or LAB2 (pred_sel 1) at pred_off, binarisation at bin_off
+    int pred_sel, L, R, nb;                   // encoder: filtered bytes per row, rows per band, bands
+    int band0, pad;                           // bands of the unit's pages in front of this one (the prefix table of the ragged launches)
+    unsigned long long img_off, lab_off, pred_off, bin_off;
+    unsigned long long slot, ws_off, per, slots_b, meta_b, offs_b, bound;   // the page's part of the encoder workspace (as PngPages, per page)
+};
+constexpr int PNG_MIXED_MAX = 64;             // pages of one ragged launch
+// The masks of `pages` label maps of DIFFERENT shapes as PNG streams in one set of launches over the flattened (page, band) pairs.
+// png_pages_layout_mixed reads Hl, Wl of tab[0..pages) and fills the encoder's fields; png_pages_enqueue_mixed validates the table
+// (h_tab, the host's copy of d_tab) against the workspace and launches.  Page p's sizes: ((u64*)d_ws)[4 p + k]; its stream k:
+// d_ws + ws_off + k * per + slots_b + meta_b + offs_b.  A page's stream is the single-image encoder's, byte for byte.
+struct PngPagesMixed { size_t bytes, head; int bands; };
+int png_pages_layout_mixed(int level, int nout, int pages, MixedPage* tab, PngPagesMixed* L);
+int png_pages_enqueue_mixed(const PngPagesMixed& L, const MixedPage* h_tab, const MixedPage* d_tab, int pages, uint8_t* d_ws, size_t ws_bytes,
+                            const uint8_t* d_pred0, const uint8_t* d_pred1, const uint8_t* d_bin, const uint8_t* d_lut, int n_lut, int level,
+                            int nout, const int mask_id[4], hipStream_t st);
 // pseg_engine.hip, shared by pseg_predict_batch and the page chain
 void plan_units(int n, const int* H, const int* W, const int* Ho, const int* Wo, int cap, std::vector<int>& ub, std::vector<int>& ug);
 int fit_unit_slots(Engine& e, int H, int W, int want);              // page slots a unit of `want` pages of this shape gets (1: no page units)

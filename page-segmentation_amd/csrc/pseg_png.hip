@@ -60,7 +60,20 @@ struct PngJob {
     int mask_id[4];
     size_t page;                              // bytes between two pages' slots, band tables, offsets and streams (blockIdx.z / blockIdx.y
                                               // selects the page); 0 with one page
+    // ragged launches over pages of different shapes (png_pages_enqueue_mixed) alone: H .. slot, the per-output pointers and `page`
+    // above are unused, slots[0] is the workspace and a page's geometry and offsets come from its table entry
+    const MixedPage* tab;                     // [npages], band0 ascending from 0
+    int npages;
+    const uint8_t* pred_alt;                  // the label maps of pages with pred_sel = 1
 };
+
+// the page of workgroup `b` of a ragged launch: the last entry whose first band is not behind b (uniform: scalar loads)
+__device__ __forceinline__ const MixedPage* png_mixed_page(const PngJob& J, int b) {
+    int p = 0;
+    for (int k = 1; k < J.npages; ++k)
+        if (J.tab[k].band0 <= b) p = k;
+    return J.tab + p;
+}
 
 
 // ---- host arithmetic ------------------------------------------------------------------------------------------------
@@ -233,6 +246,13 @@ struct PngSrcMasks {                          // generate_output_masks (lib/outp
     int n_lut, W;
     size_t page_pred = 0, page_bin = 0;       // bytes between two pages' label maps / binarisations
     __device__ __forceinline__ PngSrcMasks at(unsigned pg) const { PngSrcMasks s = *this; s.pred += pg * page_pred; s.bin += pg * page_bin; return s; }
+    __device__ __forceinline__ PngSrcMasks mixed(const MixedPage& m, const uint8_t* pred_alt) const {
+        PngSrcMasks s = *this;
+        s.pred = (m.pred_sel ? pred_alt : pred) + m.pred_off;
+        s.bin = bin + m.bin_off;
+        s.W = m.Wl;
+        return s;
+    }
     __device__ __forceinline__ uint32_t px(int row, int x, int mask, const uint32_t* slut) const {
         const size_t p = (size_t)row * W + x;
         const uint32_t rgb = slut[pred[p]];
@@ -395,12 +415,20 @@ __device__ inline int png_dyn_header(const uint8_t* s_len, int D, uint32_t* ws, 
 // LV 0: one fixed-Huffman block per band.  LV 1: two passes over the band's tokens -- A counts the symbols, the workgroup builds
 // a code for them and prices the band both ways, B packs with the cheaper of the two (a tie goes to the fixed code: the band is
 // then LV 0's band bit for bit).
-// PAGES: blockIdx.z selects one of several images of one shape (J.page, the source's page strides); without it the kernel is the
-// single-image kernel, instruction for instruction.
-template <class SRC, int LV, bool PAGES = false>
+// PAGES 1: blockIdx.z selects one of several images of one shape (J.page, the source's page strides); PAGES 0: the kernel is the
+// single-image kernel, instruction for instruction.  PAGES 2: blockIdx.x runs over the flattened (page, band) pairs of images of
+// different shapes; the workgroup finds its page in J.tab and takes every bound and offset from that entry.
+template <class SRC, int PAGES>
+__device__ __forceinline__ SRC png_src_of(const SRC& s, const PngJob& J, const MixedPage* mp) {
+    if constexpr (PAGES == 2) return s.mixed(*mp, J.pred_alt);
+    else if constexpr (PAGES == 1) return s.at(blockIdx.z);
+    else return s;
+}
+template <class SRC, int LV, int PAGES = 0>
 __global__ __launch_bounds__(PNG_T) void png_band_kernel(SRC src0, PngJob J) {
-    const SRC src = PAGES ? src0.at(blockIdx.z) : src0;
-    const size_t pg = PAGES ? (size_t)blockIdx.z * J.page : 0;
+    const MixedPage* const mp = PAGES == 2 ? png_mixed_page(J, (int)blockIdx.x) : nullptr;
+    const SRC src = png_src_of<SRC, PAGES>(src0, J, mp);
+    const size_t pg = PAGES == 1 ? (size_t)blockIdx.z * J.page : 0;
     __shared__ __attribute__((aligned(16))) uint8_t s_in[16 + PNG_SEG];   // [13..15]: the three bytes in front of the segment
     __shared__ uint32_t s_bits[LV ? PNG_BITW1 : PNG_BITW];
     __shared__ int s_w[4];
@@ -412,7 +440,8 @@ __global__ __launch_bounds__(PNG_T) void png_band_kernel(SRC src0, PngJob J) {
     __shared__ uint32_t s_ws[LV ? PNG_CLWS + 256 : 1];
     __shared__ unsigned long long s_cost[2];                  // literal/length bits of the band: dynamic, fixed
     __shared__ int s_hdr[18];                                 // [0]: the dynamic header's bits; [1..15]: first code of a length; [17]: the written header's bits
-    const int t = threadIdx.x, band = blockIdx.x, o = blockIdx.y, mask = J.mask_id[o];
+    const int t = threadIdx.x, band = PAGES == 2 ? (int)blockIdx.x - mp->band0 : (int)blockIdx.x, o = blockIdx.y, mask = J.mask_id[o];
+    const int jR = PAGES == 2 ? mp->R : J.R, jH = PAGES == 2 ? mp->Hl : J.H;
     if constexpr (SRC::LUT) {
         s_lut[t] = t < src.n_lut ? (uint32_t)src.lut[t * 3] | ((uint32_t)src.lut[t * 3 + 1] << 8) | ((uint32_t)src.lut[t * 3 + 2] << 16) : 0u;
     }
@@ -421,10 +450,11 @@ __global__ __launch_bounds__(PNG_T) void png_band_kernel(SRC src0, PngJob J) {
         if (t < 2) s_cost[t] = 0ull;
     }
     __syncthreads();
-    const int row0 = band * J.R, rows = min(J.R, J.H - row0);
-    const int L = J.L, D = J.C;
+    const int row0 = band * jR, rows = min(jR, jH - row0);
+    const int L = PAGES == 2 ? mp->L : J.L, D = J.C;
     const int n = rows * L;                                   // <= 2^30 (png_rows)
-    uint32_t* const out = (uint32_t*)(J.slots[o] + pg + (size_t)band * J.slot);
+    uint32_t* const out = PAGES == 2 ? (uint32_t*)(J.slots[0] + mp->ws_off + (size_t)o * mp->per + (size_t)band * mp->slot)
+                                     : (uint32_t*)(J.slots[o] + pg + (size_t)band * J.slot);
     unsigned out_w = 0;                                       // words of the slot written so far
     uint32_t carry_word = 2u;                                 // block header: BFINAL = 0, BTYPE = 01 (fixed Huffman), LSB first
     int carry_bits = 3;                                       // LV 1, first segment: the header's whole words and its partial word
@@ -595,7 +625,8 @@ __global__ __launch_bounds__(PNG_T) void png_band_kernel(SRC src0, PngJob J) {
                 PngBandMeta m;
                 m.bytes = out_w * 4u + (unsigned)(T >> 3);
                 m.a = adA; m.b = adB; m.pad = 0;
-                ((PngBandMeta*)((uint8_t*)J.meta[o] + pg))[band] = m;
+                if constexpr (PAGES == 2) ((PngBandMeta*)(J.slots[0] + mp->ws_off + (size_t)o * mp->per + mp->slots_b))[band] = m;
+                else ((PngBandMeta*)((uint8_t*)J.meta[o] + pg))[band] = m;
             }
         } else {
             out_w += (unsigned)nW;
@@ -611,13 +642,13 @@ __global__ __launch_bounds__(PNG_T) void png_band_kernel(SRC src0, PngJob J) {
 __device__ __forceinline__ void png_be32(uint8_t* p, uint32_t v) { p[0] = v >> 24; p[1] = v >> 16; p[2] = v >> 8; p[3] = v; }
 
 // One workgroup per output: band sizes -> final offsets; Adler-32 of the whole filtered image; everything but the IDAT bands.
-__global__ __launch_bounds__(PNG_T) void png_frame_kernel(PngJob J) {
+// (the geometry and the output's band table, offsets, stream and size word are arguments: the same body frames a page of a ragged launch)
+struct PngFrameGeo { int H, W, C, R, L, nb; };
+__device__ __forceinline__ void png_frame_body(const PngFrameGeo J, const PngBandMeta* meta, unsigned long long* const offs, uint8_t* const stream,
+                                               unsigned long long* const total) {
     __shared__ unsigned long long s_tot[PNG_T];
     __shared__ unsigned long long s_a, s_b;
-    const int t = threadIdx.x, o = blockIdx.x;
-    const size_t pg = (size_t)blockIdx.y * J.page;
-    const PngBandMeta* meta = (const PngBandMeta*)((const uint8_t*)J.meta[o] + pg);
-    unsigned long long* const offs = (unsigned long long*)((uint8_t*)J.offs[o] + pg);
+    const int t = threadIdx.x;
     const int per = (J.nb + PNG_T - 1) / PNG_T;
     const int b0 = min(J.nb, t * per), b1 = min(J.nb, b0 + per);
     if (t == 0) { s_a = 0; s_b = 0; }
@@ -647,7 +678,7 @@ __global__ __launch_bounds__(PNG_T) void png_frame_kernel(PngJob J) {
         const unsigned long long end = off;                   // behind the last band's chunk (the threads behind the last band hold it too)
         const uint32_t s1 = (uint32_t)((1u + s_a % ADLER_M) % ADLER_M);
         const uint32_t s2 = (uint32_t)((ntotal % ADLER_M + s_b % ADLER_M) % ADLER_M);
-        uint8_t* p = J.out[o] + pg;
+        uint8_t* p = stream;
         const uint8_t sig[8] = {0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A};
         for (int k = 0; k < 8; ++k) p[k] = sig[k];
         png_be32(p + 8, 13);
@@ -669,18 +700,45 @@ __global__ __launch_bounds__(PNG_T) void png_frame_kernel(PngJob J) {
         png_be32(q + 21, 0);
         q[25] = 'I'; q[26] = 'E'; q[27] = 'N'; q[28] = 'D';
         png_be32(q + 29, 0);
-        J.total[(size_t)blockIdx.y * 4 + o] = end + 21 + 12;
+        *total = end + 21 + 12;
     }
 }
+__global__ __launch_bounds__(PNG_T) void png_frame_kernel(PngJob J) {
+    const int o = blockIdx.x;
+    const size_t pg = (size_t)blockIdx.y * J.page;
+    png_frame_body(PngFrameGeo{J.H, J.W, J.C, J.R, J.L, J.nb}, (const PngBandMeta*)((const uint8_t*)J.meta[o] + pg),
+                   (unsigned long long*)((uint8_t*)J.offs[o] + pg), J.out[o] + pg, J.total + (size_t)blockIdx.y * 4 + o);
+}
+// ragged: blockIdx.y is the page of the unit, its geometry and workspace from the table
+__global__ __launch_bounds__(PNG_T) void png_frame_mixed_kernel(PngJob J) {
+    const int o = blockIdx.x;
+    const MixedPage& m = J.tab[blockIdx.y];
+    uint8_t* const q = J.slots[0] + m.ws_off + (size_t)o * m.per;
+    png_frame_body(PngFrameGeo{m.Hl, m.Wl, J.C, m.R, m.L, m.nb}, (const PngBandMeta*)(q + m.slots_b), (unsigned long long*)(q + m.slots_b + m.meta_b),
+                   q + m.slots_b + m.meta_b + m.offs_b, J.total + (size_t)blockIdx.y * 4 + o);
+}
 
-__global__ __launch_bounds__(PNG_T) void png_gather_kernel(PngJob J) {
-    const int t = threadIdx.x, band = blockIdx.x, o = blockIdx.y;
-    const size_t pg = (size_t)blockIdx.z * J.page;
-    const unsigned sz = ((const PngBandMeta*)((const uint8_t*)J.meta[o] + pg))[band].bytes;
-    const uint8_t* src = J.slots[o] + pg + (size_t)band * J.slot;
-    uint8_t* dst = J.out[o] + pg + ((const unsigned long long*)((const uint8_t*)J.offs[o] + pg))[band];
+__device__ __forceinline__ void png_gather_body(const PngBandMeta* meta, const uint8_t* slots, size_t slot, const unsigned long long* offs,
+                                                uint8_t* stream, int band) {
+    const int t = threadIdx.x;
+    const unsigned sz = meta[band].bytes;
+    const uint8_t* src = slots + (size_t)band * slot;
+    uint8_t* dst = stream + offs[band];
     if (t == 0) { png_be32(dst, sz); dst[4] = 'I'; dst[5] = 'D'; dst[6] = 'A'; dst[7] = 'T'; png_be32(dst + 8 + sz, 0); }
     for (unsigned k = t; k < sz; k += PNG_T) dst[8 + k] = src[k];
+}
+__global__ __launch_bounds__(PNG_T) void png_gather_kernel(PngJob J) {
+    const int o = blockIdx.y;
+    const size_t pg = (size_t)blockIdx.z * J.page;
+    png_gather_body((const PngBandMeta*)((const uint8_t*)J.meta[o] + pg), J.slots[o] + pg, J.slot,
+                    (const unsigned long long*)((const uint8_t*)J.offs[o] + pg), J.out[o] + pg, (int)blockIdx.x);
+}
+__global__ __launch_bounds__(PNG_T) void png_gather_mixed_kernel(PngJob J) {
+    const int o = blockIdx.y;
+    const MixedPage* const mp = png_mixed_page(J, (int)blockIdx.x);
+    uint8_t* const q = J.slots[0] + mp->ws_off + (size_t)o * mp->per;
+    png_gather_body((const PngBandMeta*)(q + mp->slots_b), q, mp->slot, (const unsigned long long*)(q + mp->slots_b + mp->meta_b),
+                    q + mp->slots_b + mp->meta_b + mp->offs_b, (int)blockIdx.x - mp->band0);
 }
 
 // ---- CRC-32 (host, over the downloaded stream) ------------------------------------------------------------------------------
@@ -749,6 +807,7 @@ static int png_run(int device, const SRC& src, int H, int W, int C, int band_row
     J.L = W * C + 1;
     J.slot = (png_band_bound((size_t)J.R * J.L) + 3) & ~(size_t)3;
     J.page = 0;
+    J.tab = nullptr; J.npages = 0; J.pred_alt = nullptr;
     const size_t slots_b = al256((size_t)J.nb * J.slot), meta_b = al256((size_t)J.nb * sizeof(PngBandMeta)), offs_b = al256((size_t)J.nb * 8),
                  out_b = al256(bound + 32);
     const size_t per = slots_b + meta_b + offs_b + out_b, need = 256 + (size_t)nout * per;
@@ -821,6 +880,7 @@ int png_pages_enqueue(const PngPages& L, uint8_t* d_ws, const uint8_t* d_pred, s
     J.L = W * 3 + 1;
     J.slot = (png_band_bound((size_t)J.R * J.L) + 3) & ~(size_t)3;
     J.page = pages > 1 ? L.page : 0;
+    J.tab = nullptr; J.npages = 0; J.pred_alt = nullptr;
     J.total = (unsigned long long*)d_ws;
     for (int k = 0; k < 4; ++k) {
         uint8_t* q = d_ws + L.head + (size_t)std::min(k, nout - 1) * L.per;
@@ -835,11 +895,86 @@ int png_pages_enqueue(const PngPages& L, uint8_t* d_ws, const uint8_t* d_pred, s
         if (level == 0) png_band_kernel<PngSrcMasks, 0><<<dim3(J.nb, nout), PNG_T, 0, st>>>(src, J);
         else png_band_kernel<PngSrcMasks, 1><<<dim3(J.nb, nout), PNG_T, 0, st>>>(src, J);
     } else {
-        if (level == 0) png_band_kernel<PngSrcMasks, 0, true><<<dim3(J.nb, nout, pages), PNG_T, 0, st>>>(src, J);
-        else png_band_kernel<PngSrcMasks, 1, true><<<dim3(J.nb, nout, pages), PNG_T, 0, st>>>(src, J);
+        if (level == 0) png_band_kernel<PngSrcMasks, 0, 1><<<dim3(J.nb, nout, pages), PNG_T, 0, st>>>(src, J);
+        else png_band_kernel<PngSrcMasks, 1, 1><<<dim3(J.nb, nout, pages), PNG_T, 0, st>>>(src, J);
     }
     png_frame_kernel<<<dim3(nout, pages), PNG_T, 0, st>>>(J);
     png_gather_kernel<<<dim3(J.nb, nout, pages), PNG_T, 0, st>>>(J);
+    PSEG_HIP(hipGetLastError());
+    return PSEG_OK;
+}
+
+// ---- many images of different shapes in one set of launches (the page chain's mixed units) ----------------------------------------
+int png_pages_layout_mixed(int level, int nout, int pages, MixedPage* tab, PngPagesMixed* L) {
+    if (!tab || !L || (level != 0 && level != 1) || nout < 1 || nout > 4 || pages < 1 || pages > PNG_MIXED_MAX)
+        return fail(PSEG_EINVAL, "png: a ragged launch of %d pages (1..%d), %d outputs, level %d", pages, PNG_MIXED_MAX, nout, level);
+    L->head = al256((size_t)pages * 4 * sizeof(unsigned long long));
+    size_t pos = L->head;
+    long long bands = 0;
+    for (int p = 0; p < pages; ++p) {
+        MixedPage& m = tab[p];
+        if (!png_shape_ok(m.Hl, m.Wl, 3)) return fail(PSEG_EINVAL, "png: page %d of the unit: %d x %d pixels", p, m.Hl, m.Wl);
+        m.R = png_rows(m.Hl, m.Wl, 3, 0, level);
+        m.nb = (int)(((size_t)m.Hl + m.R - 1) / m.R);
+        m.L = m.Wl * 3 + 1;
+        m.slot = (png_band_bound((size_t)m.R * m.L) + 3) & ~(size_t)3;
+        m.bound = png_bound(m.Hl, m.Wl, 3, 0, level);
+        m.slots_b = al256((size_t)m.nb * m.slot);
+        m.meta_b = al256((size_t)m.nb * sizeof(PngBandMeta));
+        m.offs_b = al256((size_t)m.nb * 8);
+        m.per = m.slots_b + m.meta_b + m.offs_b + al256(m.bound + 32);
+        m.ws_off = pos;
+        m.band0 = (int)bands;
+        m.pad = 0;
+        pos += (size_t)nout * m.per;
+        bands += m.nb;
+        if (bands > 0x7FFFFFFF) return fail(PSEG_EINVAL, "png: more than 2^31 bands in one ragged launch");
+    }
+    L->bytes = pos;
+    L->bands = (int)bands;
+    return PSEG_OK;
+}
+
+int png_pages_enqueue_mixed(const PngPagesMixed& L, const MixedPage* h_tab, const MixedPage* d_tab, int pages, uint8_t* d_ws, size_t ws_bytes,
+                            const uint8_t* d_pred0, const uint8_t* d_pred1, const uint8_t* d_bin, const uint8_t* d_lut, int n_lut, int level,
+                            int nout, const int mask_id[4], hipStream_t st) {
+    // the kernels take every loop bound and every offset from the table: it is checked against the workspace before anything runs
+    if (!h_tab || !d_tab || !d_ws || pages < 1 || pages > PNG_MIXED_MAX || nout < 1 || nout > 4 || (level != 0 && level != 1) || L.bytes > ws_bytes)
+        return fail(PSEG_EINVAL, "png: bad ragged launch (%d pages, %d outputs, workspace %zu of %zu bytes)", pages, nout, ws_bytes, L.bytes);
+    long long bands = 0;
+    size_t pos = L.head;
+    for (int p = 0; p < pages; ++p) {
+        const MixedPage& m = h_tab[p];
+        bool ok = png_shape_ok(m.Hl, m.Wl, 3) && m.R == png_rows(m.Hl, m.Wl, 3, 0, level) && m.R >= 1 && m.L == m.Wl * 3 + 1 &&
+                  m.nb == (int)(((size_t)m.Hl + m.R - 1) / m.R) && m.band0 == bands && m.ws_off == pos && m.ws_off % 256 == 0 &&
+                  m.slot >= png_band_bound((size_t)m.R * m.L) && m.slot % 4 == 0 && m.slots_b >= (size_t)m.nb * m.slot && m.slots_b % 256 == 0 &&
+                  m.meta_b >= (size_t)m.nb * sizeof(PngBandMeta) && m.meta_b % 256 == 0 && m.offs_b >= (size_t)m.nb * 8 && m.offs_b % 256 == 0 &&
+                  m.bound == png_bound(m.Hl, m.Wl, 3, 0, level) && m.per >= m.slots_b + m.meta_b + m.offs_b + m.bound + 32 &&
+                  (m.pred_sel == 0 || (m.pred_sel == 1 && d_pred1));
+        if (!ok) return fail(PSEG_EINVAL, "png: ragged launch: the table entry of page %d does not fit its shape %d x %d", p, m.Hl, m.Wl);
+        pos += (size_t)nout * m.per;
+        bands += m.nb;
+    }
+    if (pos != L.bytes || bands != L.bands || bands < 1) return fail(PSEG_EINVAL, "png: ragged launch: the table does not fit the layout");
+    PngJob J;
+    J.H = J.W = J.R = J.nb = J.L = 0;
+    J.C = 3;
+    J.slot = 0;
+    J.page = 0;
+    J.total = (unsigned long long*)d_ws;
+    for (int k = 0; k < 4; ++k) {
+        J.slots[k] = d_ws;
+        J.meta[k] = nullptr; J.offs[k] = nullptr; J.out[k] = nullptr;
+        J.mask_id[k] = mask_id[std::min(k, nout - 1)];
+    }
+    J.tab = d_tab;
+    J.npages = pages;
+    J.pred_alt = d_pred1;
+    PngSrcMasks src{d_pred0, d_bin, d_lut, n_lut, 0, 0, 0};
+    if (level == 0) png_band_kernel<PngSrcMasks, 0, 2><<<dim3(L.bands, nout), PNG_T, 0, st>>>(src, J);
+    else png_band_kernel<PngSrcMasks, 1, 2><<<dim3(L.bands, nout), PNG_T, 0, st>>>(src, J);
+    png_frame_mixed_kernel<<<dim3(nout, pages), PNG_T, 0, st>>>(J);
+    png_gather_mixed_kernel<<<dim3(L.bands, nout), PNG_T, 0, st>>>(J);
     PSEG_HIP(hipGetLastError());
     return PSEG_OK;
 }

@@ -37,10 +37,11 @@ class Predictor:
             ops.append(known[processor])
         return ops
 
-    def _chain_inputs(self, data: SingleData, want_masks):
+    def _chain_inputs(self, data: SingleData, want_masks, record=True):
         """What the device chain takes for this page: (data', network input, uint8 binarisation or None, out_shape or None, op
         names), or None when this page / these settings need the host chain (a post-processor that is not one of this package's,
-        > 256 classes, no binary for the vote)."""
+        > 256 classes, no binary for the vote).  record=False (the list path, which reads no data'): the record's image is not
+        resized to the original resolution -- the masks need the binarisation alone."""
         net = self.network
         ops = self._chain_ops()
         if ops is None or net.n_classes > 256 or getattr(net, "_rgb", False) and np.asarray(data.image).ndim != 2:
@@ -54,7 +55,7 @@ class Predictor:
             # not on the hot path); the label map's resize is a stage of the device chain (identity when the shapes agree)
             from .util import preserving_resize
             out_shape = tuple(int(v) for v in data.original_shape[:2])
-            resized_image = preserving_resize(data.image, data.original_shape)
+            resized_image = preserving_resize(data.image, data.original_shape) if record else data.image
             if np.asarray(data.binary).shape != tuple(data.original_shape):
                 binary = data.orig_binary if data.orig_binary is not None else preserving_resize(data.binary, data.original_shape).astype('bool')
             page = dataclasses.replace(data, binary=binary, image=resized_image)
@@ -161,13 +162,19 @@ class Predictor:
         output.output_data(output_dir, np.asarray(pred), data, self.settings.color_map, level=level)
         return paths
 
-    def write_masks_dataset(self, dataset: Dataset, output_dir=None, level=None, chunk_pages=64):
+    #: what write_masks_dataset(mixed=None) does with a chunk whose pages differ in shape: True = units by canvas
+    #: (Engine.predict_chain_pages(mixed=True)); see DESIGN.md 5c for the measurement this default rests on
+    MIXED_DEFAULT = True
+
+    def write_masks_dataset(self, dataset: Dataset, output_dir=None, level=None, chunk_pages=64, mixed=None):
         """write_masks for every page of a dataset (lib/predictor.py:27-30 over :49-54), the pages streamed through the device chain
         chunk_pages at a time (Engine.predict_chain_pages: units of same-shape pages, uploads, encoder and downloads of neighbouring
         units overlapped); each PNG stream is written to its file as it arrives.  Same files, names and bytes as write_masks.  Pages
         the device path cannot take -- other extensions than ".png", output.DEVICE_PNG = False, a foreign post-processor, more than
         256 classes, no binarisation where one is needed -- go through write_masks, in place.  Yields the three paths per page, in
-        dataset order."""
+        dataset order.  mixed: True forms the units from the pages of one canvas whatever their shapes (chain_units_mixed; same
+        bytes), False from runs of same-shape pages; None: MIXED_DEFAULT where the device pages of a chunk have more than one
+        distinct (H, W, final H, final W) -- a one-shape chunk always takes the same-shape path."""
         from . import output
         level = output.DEVICE_PNG_LEVEL if level is None else level
         output_dir = output_dir if output_dir is not None else self.settings.output
@@ -183,17 +190,19 @@ class Predictor:
             for data in chunk:
                 p = output.output_paths(output_dir, data)
                 paths.append(p)
-                inputs.append(self._chain_inputs(data, "png") if output.DEVICE_PNG and output.is_png_target(p[0]) else None)
+                inputs.append(self._chain_inputs(data, "png", record=False) if output.DEVICE_PNG and output.is_png_target(p[0]) else None)
             on_device = [k for k, got in enumerate(inputs) if got is not None]
             if on_device:
                 def to_file(page, name, stream, paths=paths, on_device=on_device):
                     with open(paths[on_device[page]][names.index(name)], "wb") as f:
                         f.write(stream)
+                shapes = set((tuple(np.shape(inputs[k][1])[:2]), inputs[k][3] or tuple(np.shape(inputs[k][1])[:2])) for k in on_device)
+                use_mixed = (self.MIXED_DEFAULT and len(shapes) > 1) if mixed is None else bool(mixed)
                 self.network.model.predict_chain_pages(
                     [inputs[k][1] for k in on_device], binaries=[inputs[k][2] for k in on_device],
                     out_shapes=[inputs[k][3] for k in on_device], post_ops=inputs[on_device[0]][4],
                     exact_labels=self.network.exact == "labels", lut=self.settings.color_map.lut(), which=names,
-                    png_level=level, sink=to_file)
+                    png_level=level, sink=to_file, mixed=use_mixed)
             for k, data in enumerate(chunk):
                 if inputs[k] is None:
                     self.write_masks(data, output_dir=output_dir, level=level)

@@ -30,6 +30,7 @@ EXPORTED_SYMBOLS = (
     "pseg_png_bound", "pseg_png_encode_device", "pseg_masks_png_device_u8", "pseg_png_encode", "pseg_masks_png", "pseg_predict_chain_png",
     "pseg_png_bound_lv", "pseg_png_encode_device_lv", "pseg_masks_png_device_u8_lv", "pseg_png_encode_lv", "pseg_masks_png_lv",
     "pseg_predict_chain_png_lv", "pseg_png_code_lengths", "pseg_predict_chain_pages_png", "pseg_chain_units",
+    "pseg_predict_chain_pages_mixed_png", "pseg_chain_units_mixed",
     "pseg_rescale_shape", "pseg_gaussian_kernel", "pseg_resize_nearest", "pseg_resize_nearest_device", "pseg_scale_image",
     "pseg_prepare_images", "pseg_affine_warp", "pseg_affine_warp_fill", "pseg_brightness_shift",
     "pseg_eval_confusion", "pseg_cc_label", "pseg_cc_tables",
@@ -161,6 +162,8 @@ def lib():
     L.pseg_png_code_lengths.argtypes = [vp, i, i, vp]
     L.pseg_predict_chain_pages_png.argtypes = [vp, i, vp, vp, vp, vp, vp, vp, c.POINTER(i), i, c.c_uint, vp, i, i, c.c_uint, i, CHAIN_SINK, vp]
     L.pseg_chain_units.argtypes = [i, vp, vp, vp, vp, i, vp, vp, i]
+    L.pseg_predict_chain_pages_mixed_png.argtypes = L.pseg_predict_chain_pages_png.argtypes
+    L.pseg_chain_units_mixed.argtypes = [i, vp, vp, i, vp, vp, vp, i]
     _LIB = L
     return L
 
@@ -452,14 +455,17 @@ class Engine:
         return {"labels": lab, "masks": tuple(outs) if masks else None}
 
     def predict_chain_pages(self, images, binaries=None, out_shapes=None, post_ops=(), exact_labels=False, lut=None,
-                            which=("color", "overlay", "inverted"), labels=False, png_level=0, unit_cap=0, sink=None):
+                            which=("color", "overlay", "inverted"), labels=False, png_level=0, unit_cap=0, sink=None, mixed=False):
         """A page list through the chain to PNG streams (pseg_predict_chain_pages_png; lib/predictor.py:27-30 over :49-54): per page
         predict -> [nearest resize to out_shapes[i]] -> post-processors -> the masks named in `which` as PNG streams, units of
         same-shape pages pipelined on the device; every stream (and label map, with labels=True) has predict_chain's bytes for that
         page alone.  binaries[i] / out_shapes[i] may be None.  sink=None: a list of {"labels": uint8 map or None, "masks": {name:
         bytes}} per page.  With a callable, sink(page, name, data) is called per output as it arrives -- page order, then color /
         overlay / inverted / fg_color / "labels" (data: bytes, for "labels" the uint8 map) -- and None is returned; an exception in
-        the sink stops the call and is raised again after it."""
+        the sink stops the call and is raised again after it.
+        mixed=True (pseg_predict_chain_pages_mixed_png): for lists whose pages differ in shape.  Units are formed from the pages of
+        one canvas (chain_units_mixed) whatever their own and their final shapes; the bytes are the same, the list return stays in
+        page order, a callable sink sees the units in the planner's order (pages of a unit in the permuted order)."""
         for w in which:
             if w not in MASK_NAMES:
                 raise PsegError("unknown mask %r (one of %r)" % (w, MASK_NAMES))
@@ -508,9 +514,9 @@ class Engine:
                 raised.append(exc)
                 return 1
 
-        rc = lib().pseg_predict_chain_pages_png(self._h, n, ip, hs, ws, ho, wo, bp, ops, len(post_ops), 1 if exact_labels else 0,
-                                                _ptr(t), 0 if t is None else t.shape[0], int(png_level), want, int(unit_cap),
-                                                CHAIN_SINK(on_output), None)
+        entry = lib().pseg_predict_chain_pages_mixed_png if mixed else lib().pseg_predict_chain_pages_png
+        rc = entry(self._h, n, ip, hs, ws, ho, wo, bp, ops, len(post_ops), 1 if exact_labels else 0,
+                   _ptr(t), 0 if t is None else t.shape[0], int(png_level), want, int(unit_cap), CHAIN_SINK(on_output), None)
         if raised:
             raise raised[0]
         _check(rc)
@@ -947,6 +953,19 @@ def chain_units(shapes, out_shapes=None, cap=8):
     nu = lib().pseg_chain_units(n, H, W, Ho, Wo, int(cap), first, count, n)
     _check(min(nu, 0))
     return [(first[u], count[u]) for u in range(nu)]
+
+
+def chain_units_mixed(shapes, cap=8):
+    """How pseg_predict_chain_pages_mixed_png cuts a list of page shapes: (order, units).  order: a permutation of the pages, canvases
+    (shapes rounded up to multiples of 32) by first appearance, list order within a canvas; units: [(first position in order, page
+    count), ...], chain_units' cut of the permuted canvas list (host logic, no GPU)."""
+    n = len(shapes)
+    I = ctypes.c_int * max(n, 1)
+    H, W = I(*[int(s[0]) for s in shapes]), I(*[int(s[1]) for s in shapes])
+    order, first, count = I(), I(), I()
+    nu = lib().pseg_chain_units_mixed(n, H, W, int(cap), order, first, count, n)
+    _check(min(nu, 0))
+    return [order[k] for k in range(n)], [(first[u], count[u]) for u in range(nu)]
 
 
 def brightness_shift(x, brightness, device=0):
