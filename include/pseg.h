@@ -561,6 +561,48 @@ int pseg_prepare_images(int device, const uint8_t* image, const uint8_t* binary,
                         uint8_t* out_img, uint8_t* out_bin, uint8_t* out_orig_bin,
                         double* out_stage1);
 
+/* ---- Scans straight into the page chain: binarisation and line-height normalisation on the device ------------------------ */
+
+/* One gray scan and the page it becomes.  gray: uint8 (H0,W0), ink dark.  (H,W) = pseg_rescale_shape(H0, W0, target_line_height /
+ * line_height_px).  wy / wx: the anti-aliasing weights of axis 0 / axis 1 (2 r + 1 doubles; NULL: built with
+ * pseg_gaussian_kernel); ry / rx must equal int(4 sigma + 0.5) with sigma = max(0, (in / out - 1) / 2) of the axis, and are not
+ * read where sigma <= 1e-15 (no pass on that axis).  final_is_scan (pseg_predict_chain_scans_png only): the label map is rescaled
+ * to (H0,W0) and voted / masked against the scan-sized ink map (PredictSettings.high_res_output). */
+typedef struct pseg_scan {
+    const uint8_t* gray;
+    int H0, W0;
+    int H, W;
+    const double* wy;
+    int ry;
+    const double* wx;
+    int rx;
+    int final_is_scan;
+} pseg_scan;
+
+/* pseg_prepare_images(scan, where(scan > 127, 255, 0)) without a max_width stage for n scans, bit for bit, by the device-resident
+ * front end of pseg_predict_chain_scans_png: the binarisation is never an input (ink is scan <= 127), and per scan at most three
+ * launches run -- a pass that ORs the scan's 256-bit value bitmap into its record (min, max and "more than two distinct values"
+ * are read from it on the device) and writes the scan-sized ink map where asked for; a tiled Gaussian that runs both
+ * anti-aliasing passes through LDS (radii up to 8; larger ones take the one-pass-per-launch kernels) and stores the scan
+ * unfiltered where the record says two values or fewer; a sampler that does the bicubic taps, the clip, the inversion and the
+ * nearest gather of the ink map per output pixel.  No allocation, device-to-host read or wait happens between the launches.
+ * Host pointers: out_img[i], out_bin[i]: uint8 (H,W); out_orig[i]: uint8 (H0,W0), the array or an entry may be NULL.  Every scan is
+ * checked before any device work starts (PSEG_EINVAL names the scan). */
+int pseg_prepare_scans(int device, int n, const pseg_scan* scans, uint8_t* const* out_img, uint8_t* const* out_bin,
+                       uint8_t* const* out_orig);
+
+/* pseg_predict_chain_pages_mixed_png with scans in place of pages and binarisations: a unit's scans go up into a staging slot of
+ * the set, the front end above writes every page and its ink map (final_is_scan: the scan-sized one) where the unit's network
+ * stage and post-processors read them, and everything behind that is the mixed page chain -- same units (by the canvas of
+ * (H,W)), same bytes per (scan, output) as that call fed with pseg_prepare_images' outputs, same sink contract, same drained
+ * return.  The filtered planes, the per-scan records and the call's weights table (page-locked, uploaded once) are staging of the
+ * engine, sized up front for the largest unit; pseg_engine_trim frees them.  Only an engine with one input channel takes this
+ * entry (PSEG_EUNSUPPORTED otherwise).  Every scan is checked before any device work starts. */
+int pseg_predict_chain_scans_png(pseg_engine* e, int n_scans, const pseg_scan* scans,
+                                 const int* post_ops, int n_post, unsigned flags,
+                                 const uint8_t* lut, int n_lut, int level, unsigned want, int unit_cap,
+                                 pseg_chain_sink sink, void* user);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,11 +15,11 @@ namespace pseg {
 
 // One of the two staging sets of the page chain (pseg_predict_chain_pages_png): everything a unit of pages touches.
 struct PagesSet {
-    enum { IMG = 0, LAB = 1, LAB2 = 2, BIN = 3, PNG = 4, PAD = 5, CLAB = 6, NDEV = 7 };
+    enum { IMG = 0, LAB = 1, LAB2 = 2, BIN = 3, PNG = 4, PAD = 5, CLAB = 6, SCAN = 7, FILT = 8, REC = 9, NDEV = 10 };
     // pages / network labels / resize + bbox ping-pong / binarisations / encoder workspace / mixed units: the pages padded to canvas-sized
-    // page slots / the slots' canvas-sized label maps
-    uint8_t* d[NDEV] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    size_t d_bytes[NDEV] = {0, 0, 0, 0, 0, 0, 0};
+    // page slots / the slots' canvas-sized label maps / scan chain: the unit's scans / their filtered planes / their records
+    uint8_t* d[NDEV] = {};
+    size_t d_bytes[NDEV] = {};
     uint8_t* h_in = nullptr;            // page-locked: pages and binarisations of callers with pageable arrays
     uint8_t* h_out = nullptr;           // page-locked: the unit's encoded streams (+ label maps), grown to the bytes units really have
     unsigned long long* h_tot = nullptr;   // page-locked: [pages][4] stream sizes
@@ -32,6 +32,9 @@ struct ChainPagesState {
     MixedPage* d_tab = nullptr;         // the page table of a mixed call (one entry per page of the list, in the planner's order) ...
     MixedPage* h_tab = nullptr;         // ... and its page-locked source
     size_t tab_entries = 0;
+    double* d_wt = nullptr;             // the anti-aliasing weights of a scan call (every scan's, in the planner's order) ...
+    double* h_wt = nullptr;             // ... and their page-locked source
+    size_t wt_entries = 0;
 };
 
 struct ChainState {
@@ -59,6 +62,10 @@ static void pages_release(ChainPagesState& p) {
     if (p.h_tab) (void)hipHostFree(p.h_tab);
     p.d_tab = p.h_tab = nullptr;
     p.tab_entries = 0;
+    if (p.d_wt) (void)hipFree(p.d_wt);
+    if (p.h_wt) (void)hipHostFree(p.h_wt);
+    p.d_wt = p.h_wt = nullptr;
+    p.wt_entries = 0;
     for (PagesSet& s : p.set) {
         for (int i = 0; i < PagesSet::NDEV; ++i) { if (s.d[i]) (void)hipFree(s.d[i]); s.d[i] = nullptr; s.d_bytes[i] = 0; }
         if (s.h_in) (void)hipHostFree(s.h_in);
@@ -352,15 +359,19 @@ extern "C" int pseg_chain_units(int n_pages, const int* H, const int* W, const i
     return (int)ub.size();
 }
 
-// The body of both page-list entries.  mixed = false: units are runs of same-shape pages in list order (pseg_chain_units).  mixed = true:
+// The body of the page-list entries.  mixed = false: units are runs of same-shape pages in list order (pseg_chain_units).  mixed = true:
 // units are pages of one canvas (pseg_chain_units_mixed); `ord` maps a position of the planner's order to the caller's page.
+// scans != NULL (pseg_predict_chain_scans_png; mixed): imgs[i] is scan i's gray plane and binaries[i] stands for the ink map that the
+// front end makes on the device -- upload() brings the unit's scans, compute() starts with the front end (scan_front_enqueue), which
+// writes the pages and ink maps where upload() puts them otherwise; H, W, Ho, Wo are the pages' shapes as for the page entries.
 static int chain_pages_run(pseg_engine* h, int n, const uint8_t* const* imgs, const int* H, const int* W, const int* Ho, const int* Wo,
                            const uint8_t* const* binaries, const int* post_ops, int n_post, unsigned flags, const uint8_t* lut, int n_lut, int level,
-                           unsigned want, int unit_cap, pseg_chain_sink sink, void* user, const bool mixed) {
+                           unsigned want, int unit_cap, pseg_chain_sink sink, void* user, const bool mixed, const pseg_scan* scans = nullptr) {
     if (!h) return fail(PSEG_EINVAL, "NULL engine");
     KnobScope knob_scope(h->e);
     Engine& e = h->e;
     if (n < 0 || (n > 0 && (!imgs || !H || !W))) return fail(PSEG_EINVAL, "bad argument");
+    if (scans && (e.in_ch != 1 || !mixed)) return fail(PSEG_EUNSUPPORTED, "the scan chain takes an engine with one input channel (this one has %d)", e.in_ch);
     if (!sink) return fail(PSEG_EINVAL, "NULL sink");
     if (want == 0 || (want & ~31u)) return fail(PSEG_EINVAL, "want 0x%x: bits 0..3 select the masks, bit 4 the label map, at least one", want);
     if (unit_cap < 0 || unit_cap > 64) return fail(PSEG_EINVAL, "unit_cap %d (0 = default, at most 64)", unit_cap);
@@ -427,7 +438,10 @@ static int chain_pages_run(pseg_engine* h, int n, const uint8_t* const* imgs, co
     std::vector<Unit> un(nu);
     std::vector<MixedPage> tab(n);
     std::vector<size_t> lab2_off(n, 0);
-    size_t mx[PagesSet::NDEV] = {0, 0, 0, 0, 0, 0, 0}, mx_in = 0, mx_tot = 0;
+    // a scan call, per position: where the scan and its filtered plane lie in the set's SCAN / FILT blocks, its weights in the call's table
+    std::vector<size_t> scan_off(scans ? n : 0, 0), filt_off(scans ? n : 0, 0), wt_off(scans ? n : 0, 0);
+    size_t n_wt = 0;
+    size_t mx[PagesSet::NDEV] = {}, mx_in = 0, mx_tot = 0;
     for (int u = 0; u < nu; ++u) {
         const int i0 = ub[u], g = ug[u], p0 = ord[i0];
         Unit& q = un[u];
@@ -435,7 +449,7 @@ static int chain_pages_run(pseg_engine* h, int n, const uint8_t* const* imgs, co
         q.slots = page_slots && g > 1 && (mixed || ((size_t)H[p0] * W[p0]) % 4 == 0);
         q.L = PngPages{0, 0, 0, 0, 0, 0, 0, 0};
         q.M = PngPagesMixed{0, 0, 0};
-        size_t o_img = 0, o_lab = 0, o_bin = 0, o_lab2 = 0, lab_b = 0, in_b = 0;
+        size_t o_img = 0, o_lab = 0, o_bin = 0, o_lab2 = 0, lab_b = 0, in_b = 0, o_scan = 0, o_filt = 0;
         for (int k = 0; k < g; ++k) {
             const int pi = ord[i0 + k];
             MixedPage& m = tab[i0 + k];
@@ -449,7 +463,15 @@ static int chain_pages_run(pseg_engine* h, int n, const uint8_t* const* imgs, co
             lab_b += up256(npx);
             o_bin += nla;
             o_lab2 += 2 * nla;
-            in_b += npx * e.in_ch + (req[pi].need_bin ? nl : 0);
+            in_b += scans ? (size_t)scans[pi].H0 * scans[pi].W0 : npx * e.in_ch + (req[pi].need_bin ? nl : 0);
+            if (scans) {
+                scan_off[i0 + k] = o_scan;
+                filt_off[i0 + k] = o_filt;
+                wt_off[i0 + k] = n_wt;
+                o_scan += up256((size_t)scans[pi].H0 * scans[pi].W0);
+                o_filt += scan_front_work(scans[pi]);
+                n_wt += scan_front_weights(scans[pi], nullptr);
+            }
             // where the page's final map will lie: compute()'s walk through resize and post-processors, ahead of time
             int where = req[pi].resize ? 1 : 0;                        // 0: LAB, 1: bufA, 2: bufB
             for (int i = 0; i < n_post; ++i)
@@ -466,6 +488,11 @@ static int chain_pages_run(pseg_engine* h, int n, const uint8_t* const* imgs, co
         if (two_maps) mx[PagesSet::LAB2] = std::max(mx[PagesSet::LAB2], o_lab2);
         if (any_bin) mx[PagesSet::BIN] = std::max(mx[PagesSet::BIN], o_bin);
         mx[PagesSet::PNG] = std::max(mx[PagesSet::PNG], mixed ? q.M.bytes : q.L.bytes);
+        if (scans) {
+            mx[PagesSet::SCAN] = std::max(mx[PagesSet::SCAN], o_scan);
+            mx[PagesSet::FILT] = std::max(mx[PagesSet::FILT], o_filt);
+            mx[PagesSet::REC] = std::max(mx[PagesSet::REC], (size_t)g * SCAN_REC_WORDS * sizeof(unsigned));
+        }
         if (mixed && q.slots) {
             const size_t cpx = (size_t)round_up(H[p0], 32) * round_up(W[p0], 32);
             mx[PagesSet::PAD] = std::max(mx[PagesSet::PAD], (size_t)g * cpx * e.in_ch);
@@ -480,7 +507,7 @@ static int chain_pages_run(pseg_engine* h, int n, const uint8_t* const* imgs, co
     // sized for the largest unit up front.  The page-locked stream staging alone grows while the call runs (see download).
     bool any_pageable = false;
     for (int i = 0; i < n && !any_pageable; ++i)
-        any_pageable = !pages_is_pinned(imgs[i]) || (req[i].need_bin && !pages_is_pinned(binaries[i]));
+        any_pageable = !pages_is_pinned(imgs[i]) || (!scans && req[i].need_bin && !pages_is_pinned(binaries[i]));
     for (PagesSet& s : ps.set) {
         for (int k = 0; k < PagesSet::NDEV; ++k)
             if (mx[k]) PSEG_TRY(pages_ensure_dev(s, k, mx[k]));
@@ -507,7 +534,42 @@ static int chain_pages_run(pseg_engine* h, int n, const uint8_t* const* imgs, co
         memcpy(ps.h_tab, tab.data(), (size_t)n * sizeof(MixedPage));
         PSEG_HIP(hipMemcpyAsync(ps.d_tab, ps.h_tab, (size_t)n * sizeof(MixedPage), hipMemcpyHostToDevice, s_in));
     }
+    if (scans && n_wt) {
+        // the weights of the whole call, in the planner's order: one page-locked table, one upload in front of every unit's up event
+        if (ps.wt_entries < n_wt) {
+            if (ps.d_wt) (void)hipFree(ps.d_wt);
+            if (ps.h_wt) (void)hipHostFree(ps.h_wt);
+            ps.d_wt = ps.h_wt = nullptr;
+            ps.wt_entries = 0;
+            if (hipMalloc((void**)&ps.d_wt, n_wt * 8) != hipSuccess || hipHostMalloc((void**)&ps.h_wt, n_wt * 8, hipHostMallocDefault) != hipSuccess) {
+                (void)hipGetLastError();
+                return fail(PSEG_ENOMEM, "scan chain: no memory for the table of %zu weights", n_wt);
+            }
+            ps.wt_entries = n_wt;
+        }
+        for (int i = 0; i < n; ++i) scan_front_weights(scans[ord[i]], ps.h_wt + wt_off[i]);
+        PSEG_HIP(hipMemcpyAsync(ps.d_wt, ps.h_wt, n_wt * 8, hipMemcpyHostToDevice, s_in));
+    }
+    auto upload_scans = [&](int u) -> int {    // a scan call's upload(u): the unit's scans into the set's SCAN block
+        PagesSet& s = ps.set[u & 1];
+        const int i0 = ub[u], g = ug[u];
+        PSEG_HIP(hipStreamWaitEvent(s_in, s.done, 0));         // the set's scans have been read (unit u - 2)
+        bool pinned = true;
+        for (int k = 0; k < g; ++k) pinned = pinned && pages_is_pinned(imgs[ord[i0 + k]]);
+        if (!pinned) PSEG_HIP(hipEventSynchronize(s.up));      // the page-locked slot: last read by the uploads of unit u - 2
+        size_t hp = 0;
+        for (int k = 0; k < g; ++k) {
+            const pseg_scan& sc = scans[ord[i0 + k]];
+            const size_t nb = (size_t)sc.H0 * sc.W0;
+            const uint8_t* src = sc.gray;
+            if (!pinned) { memcpy(s.h_in + hp, sc.gray, nb); src = s.h_in + hp; hp += nb; }
+            PSEG_HIP(hipMemcpyAsync(s.d[PagesSet::SCAN] + scan_off[i0 + k], src, nb, hipMemcpyHostToDevice, s_in));
+        }
+        PSEG_HIP(hipEventRecord(s.up, s_in));
+        return PSEG_OK;
+    };
     auto upload = [&](int u) -> int {          // unit u -> set u % 2
+        if (scans) return upload_scans(u);
         PagesSet& s = ps.set[u & 1];
         const int i0 = ub[u], g = ug[u];
         const bool bin = req[ord[i0]].need_bin;                 // (the same for every page of a call)
@@ -561,6 +623,20 @@ static int chain_pages_run(pseg_engine* h, int n, const uint8_t* const* imgs, co
         if (Hc != e.Hp || Wc != e.Wp || (q.slots && g > e.pages)) PSEG_HIP(hipStreamSynchronize(st));
         PSEG_HIP(hipStreamWaitEvent(st, s.up, 0));
         PSEG_HIP(hipStreamWaitEvent(st, s.down, 0));           // the streams and maps of unit u - 2 have left the set
+        // 0. a scan call: the front end per scan writes the page and the ink map of the final shape
+        if (scans) {
+            PSEG_HIP(hipMemsetAsync(s.d[PagesSet::REC], 0, (size_t)g * SCAN_REC_WORDS * sizeof(unsigned), st));
+            for (int k = 0; k < g; ++k) {
+                const int pi = ord[i0 + k];
+                const MixedPage& m = tab[i0 + k];
+                uint8_t* const ink = req[pi].need_bin ? s.d[PagesSet::BIN] + m.bin_off : nullptr;
+                const bool hi = scans[pi].final_is_scan != 0;
+                PSEG_TRY(scan_front_enqueue(scans[pi], s.d[PagesSet::SCAN] + scan_off[i0 + k], ps.d_wt ? ps.d_wt + wt_off[i0 + k] : nullptr,
+                                            s.d[PagesSet::FILT] ? s.d[PagesSet::FILT] + filt_off[i0 + k] : nullptr,
+                                            (unsigned*)s.d[PagesSet::REC] + (size_t)k * SCAN_REC_WORDS, s.d[PagesSet::IMG] + m.img_off,
+                                            hi ? nullptr : ink, hi ? ink : nullptr, st));
+            }
+        }
         // 1. the network
         if (q.slots && mixed) {
             // pad every page into its canvas-sized slot, run the slots, crop every label map back to its page: three steps whatever g
@@ -702,4 +778,23 @@ extern "C" int pseg_predict_chain_pages_mixed_png(pseg_engine* h, int n, const u
                                                   const uint8_t* lut, int n_lut, int level, unsigned want, int unit_cap, pseg_chain_sink sink,
                                                   void* user) {
     return chain_pages_run(h, n, imgs, H, W, Ho, Wo, binaries, post_ops, n_post, flags, lut, n_lut, level, want, unit_cap, sink, user, true);
+}
+
+extern "C" int pseg_predict_chain_scans_png(pseg_engine* h, int n, const pseg_scan* scans, const int* post_ops, int n_post, unsigned flags,
+                                            const uint8_t* lut, int n_lut, int level, unsigned want, int unit_cap, pseg_chain_sink sink, void* user) {
+    if (n < 0 || (n > 0 && !scans)) return fail(PSEG_EINVAL, "bad argument");
+    if (!sink) return fail(PSEG_EINVAL, "NULL sink");
+    // every scan is checked before any device work starts; the pages' shapes then go through the page entries' checks
+    std::vector<const uint8_t*> gray(n);
+    std::vector<int> H(n), W(n), Ho(n), Wo(n);
+    for (int i = 0; i < n; ++i) {
+        PSEG_TRY(scan_front_check(scans[i], i));
+        gray[i] = scans[i].gray;
+        H[i] = scans[i].H;
+        W[i] = scans[i].W;
+        Ho[i] = scans[i].final_is_scan ? scans[i].H0 : 0;
+        Wo[i] = scans[i].final_is_scan ? scans[i].W0 : 0;
+    }
+    return chain_pages_run(h, n, gray.data(), H.data(), W.data(), Ho.data(), Wo.data(), gray.data(), post_ops, n_post, flags, lut, n_lut, level, want,
+                           unit_cap, sink, user, true, scans);
 }

@@ -316,6 +316,18 @@ int png_pages_layout_mixed(int level, int nout, int pages, MixedPage* tab, PngPa
 int png_pages_enqueue_mixed(const PngPagesMixed& L, const MixedPage* h_tab, const MixedPage* d_tab, int pages, uint8_t* d_ws, size_t ws_bytes,
                             const uint8_t* d_pred0, const uint8_t* d_pred1, const uint8_t* d_bin, const uint8_t* d_lut, int n_lut, int level,
                             int nout, const int mask_id[4], hipStream_t st);
+// pseg_resize.hip, for the scan chain (pseg_predict_chain_scans_png): the device-resident front end of one scan.
+// scan_front_check validates shapes and radii; scan_front_weights writes the scan's weights (axis 0, then axis 1; 2 r + 1 doubles
+// each, none for an axis without a pass) to `dst` (NULL: count only) and returns their number; scan_front_work is the bytes of
+// filtered-plane workspace the scan needs (0: no pass on either axis).  scan_front_enqueue launches on `st` without a wait: d_rec
+// (SCAN_REC_WORDS zeroed words) is the scan's record, d_w its weights on the device, d_img / d_bin the (H,W) outputs, d_orig the
+// scan-sized ink map; d_bin and d_orig may be NULL.  d_scan, d_work and d_orig are 16-byte aligned.
+constexpr int SCAN_REC_WORDS = 16;
+int scan_front_check(const pseg_scan& s, int index);
+size_t scan_front_weights(const pseg_scan& s, double* dst);
+size_t scan_front_work(const pseg_scan& s);
+int scan_front_enqueue(const pseg_scan& s, const uint8_t* d_scan, const double* d_w, uint8_t* d_work, unsigned* d_rec, uint8_t* d_img,
+                       uint8_t* d_bin, uint8_t* d_orig, hipStream_t st);
 // pseg_engine.hip, shared by pseg_predict_batch and the page chain
 void plan_units(int n, const int* H, const int* W, const int* Ho, const int* Wo, int cap, std::vector<int>& ub, std::vector<int>& ug);
 int fit_unit_slots(Engine& e, int H, int W, int want);              // page slots a unit of `want` pages of this shape gets (1: no page units)

@@ -1031,3 +1031,338 @@ int augment_check(int H, int W, const double* m, const double* off, unsigned fli
 }
 
 }  // namespace pseg
+
+// ---- device-resident front end of the scan chain (pseg_predict_chain_scans_png / pseg_prepare_scans) ---------------------------
+// pseg_prepare_images(scan, where(scan > 127, 255, 0)) without the max_width stage, for the case it is called for: a uint8 scan whose
+// binarisation is a function of the scan (ink = scan <= 127, also where no pixel is above 127: the 0 / 255 map has max 0 there, is not
+// divided, and 1 - 0 is ink everywhere).  The float64 operations per pixel are those of gauss_pass_kernel, bicubic_kernel and
+// prep_map_kernel<2> in their order (the shared inline functions, -ffp-contract=off), so the bytes are theirs.  What differs: min, max
+// and "more than two distinct values" of a uint8 plane are read off a 256-bit presence bitmap that the kernels OR into the scan's
+// record (no ordered-double atomics, no read on the host: the anti-aliasing decision stays on the device); both Gaussian passes run
+// through LDS in one launch; clip, inversion, conversion and the ink map's gather ride in the sampler.  At most three launches a scan.
+namespace pseg {
+
+constexpr int SF_TH = 32, SF_TW = 64, SF_RMAX = 8;            // output tile of the fused Gaussian and its radius cap
+constexpr int SF_PITCH = SF_TW + 2 * SF_RMAX;                 // bytes per LDS tile row
+
+// ORs value v into the workgroup's LDS bitmap; `prev` (the last value this thread has set) skips the runs of a page
+__device__ __forceinline__ void bm_or(unsigned* s_bm, unsigned v, unsigned& prev) {
+    if (v == prev) return;
+    prev = v;
+    const unsigned bit = 1u << (v & 31);
+    if (!(s_bm[v >> 5] & bit)) atomicOr(&s_bm[v >> 5], bit);
+}
+__device__ __forceinline__ void bm_or_word(unsigned* s_bm, unsigned word, unsigned& prev) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) bm_or(s_bm, (word >> (8 * k)) & 255u, prev);
+}
+// the workgroup's bitmap into the record: eight 32-bit atomics (every thread calls this)
+__device__ __forceinline__ void bm_flush(const unsigned* s_bm, unsigned* rec) {
+    __syncthreads();
+    if (threadIdx.x < 8 && s_bm[threadIdx.x]) atomicOr(&rec[threadIdx.x], s_bm[threadIdx.x]);
+}
+__device__ __forceinline__ int bm_count(const unsigned* rec) {
+    int n = 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) n += __popc(rec[k]);
+    return n;
+}
+__device__ __forceinline__ void bm_range(const unsigned* rec, double* lo, double* hi) {
+    int mn = 0, mx = 0;
+    for (int k = 7; k >= 0; --k)
+        if (rec[k]) mn = 32 * k + __ffs(rec[k]) - 1;
+    for (int k = 0; k < 8; ++k)
+        if (rec[k]) mx = 32 * k + 31 - __clz(rec[k]);
+    *lo = (double)mn;
+    *hi = (double)mx;
+}
+
+// One pass over the scan, 16-byte loads: the presence bitmap -> rec[0..8), and (orig != NULL) the scan-sized ink map scan <= 127
+__global__ __launch_bounds__(256) void scan_stats_kernel(const uint8_t* scan, size_t n, unsigned* rec, uint8_t* orig) {
+    __shared__ unsigned s_bm[8];
+    if (threadIdx.x < 8) s_bm[threadIdx.x] = 0;
+    __syncthreads();
+    unsigned prev = 256;
+    const size_t nv = n / 16;
+    const uint4* sv = (const uint4*)scan;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < nv; i += (size_t)gridDim.x * 256) {
+        const uint4 v = sv[i];
+        bm_or_word(s_bm, v.x, prev);
+        bm_or_word(s_bm, v.y, prev);
+        bm_or_word(s_bm, v.z, prev);
+        bm_or_word(s_bm, v.w, prev);
+        // a byte is <= 127 where its top bit is clear
+        if (orig) ((uint4*)orig)[i] = make_uint4((~v.x >> 7) & 0x01010101u, (~v.y >> 7) & 0x01010101u, (~v.z >> 7) & 0x01010101u, (~v.w >> 7) & 0x01010101u);
+    }
+    if (blockIdx.x == 0 && threadIdx.x < n - nv * 16) {
+        const unsigned v = scan[nv * 16 + threadIdx.x];
+        bm_or(s_bm, v, prev);
+        if (orig) orig[nv * 16 + threadIdx.x] = v <= 127u;
+    }
+    bm_flush(s_bm, rec);
+}
+
+// Both anti-aliasing passes of one SF_TH x SF_TW tile through LDS: the tile with its halo as bytes (mirror indexing, as the passes
+// index the plane), axis 0 into a second tile truncated to uint8, axis 1 from that tile, the result to `dst` and its bitmap to
+// rec[8..16).  ry / rx = 0: no pass on that axis.  w: the scan's weights, axis 0 then axis 1.  Where the scan's bitmap rec[0..8) holds
+// two values or fewer the scan's bytes are stored instead (scale_image filters only images of more than two distinct values).
+__global__ __launch_bounds__(256) void scan_gauss_tile_kernel(const uint8_t* scan, int H, int W, const double* w, int ry, int rx,
+                                                              uint8_t* dst, unsigned* rec) {
+    __shared__ uint8_t s_in[(SF_TH + 2 * SF_RMAX) * SF_PITCH];
+    __shared__ uint8_t s_mid[SF_TH * SF_PITCH];
+    __shared__ double s_w[2][2 * SF_RMAX + 1];
+    __shared__ unsigned s_bm[8];
+    const int tid = threadIdx.x, x0 = blockIdx.x * SF_TW, y0 = blockIdx.y * SF_TH;
+    const int cw = SF_TW + 2 * rx, ch = SF_TH + 2 * ry;
+    if (tid < 8) s_bm[tid] = 0;
+    if (ry > 0 && tid < 2 * ry + 1) s_w[0][tid] = w[tid];
+    if (rx > 0 && tid < 2 * rx + 1) s_w[1][tid] = w[(ry > 0 ? 2 * ry + 1 : 0) + tid];
+    for (int i = tid; i < ch * cw; i += 256) {
+        const int r = i / cw, c = i - r * cw;
+        int gy = y0 - ry + r, gx = x0 - rx + c;
+        if ((unsigned)gy >= (unsigned)H) gy = mirror_idx(gy, H);
+        if ((unsigned)gx >= (unsigned)W) gx = mirror_idx(gx, W);
+        s_in[r * SF_PITCH + c] = scan[(size_t)gy * W + gx];
+    }
+    __syncthreads();
+    const bool aa = bm_count(rec) > 2;
+    unsigned prev = 256;
+    if (aa) {
+        // axis 0: every column of the tile with its halo, the SF_TH rows of the output
+        for (int i = tid; i < SF_TH * cw; i += 256) {
+            const int r = i / cw, c = i - r * cw;
+            const uint8_t* p = s_in + (r + ry) * SF_PITCH + c;
+            uint8_t v = *p;
+            if (ry > 0) {
+                double acc = ld(p, 0) * s_w[0][ry];
+                for (int j = ry; j >= 1; --j) acc = acc + (ld(p - j * SF_PITCH, 0) + ld(p + j * SF_PITCH, 0)) * s_w[0][ry - j];
+                v = (uint8_t)acc;   // C truncation between the passes, as gauss_pass_kernel<uint8_t, 0> stores it
+            }
+            s_mid[r * SF_PITCH + c] = v;
+        }
+        __syncthreads();
+    }
+    const uint8_t* s_src = aa ? s_mid : s_in + ry * SF_PITCH;
+    for (int i = tid; i < SF_TH * SF_TW; i += 256) {
+        const int r = i / SF_TW, c = i - r * SF_TW;
+        const uint8_t* p = s_src + r * SF_PITCH + c + rx;
+        uint8_t v = *p;
+        if (aa && rx > 0) {
+            double acc = ld(p, 0) * s_w[1][rx];
+            for (int j = rx; j >= 1; --j) acc = acc + (ld(p - j, 0) + ld(p + j, 0)) * s_w[1][rx - j];
+            v = (uint8_t)acc;
+        }
+        if (y0 + r < H && x0 + c < W) {
+            dst[(size_t)(y0 + r) * W + x0 + c] = v;
+            bm_or(s_bm, v, prev);
+        }
+    }
+    bm_flush(s_bm, rec + 8);
+}
+
+// Behind the one-pass-per-launch kernels (a radius above SF_RMAX): the bitmap of the filtered plane -> rec[8..16); where the scan's
+// own bitmap holds two values or fewer, the scan's bytes replace the plane first.  Both planes are 16-byte aligned.
+__global__ __launch_bounds__(256) void scan_select_kernel(const uint8_t* scan, uint8_t* filt, size_t n, unsigned* rec) {
+    __shared__ unsigned s_bm[8];
+    if (threadIdx.x < 8) s_bm[threadIdx.x] = 0;
+    __syncthreads();
+    const bool aa = bm_count(rec) > 2;
+    unsigned prev = 256;
+    const size_t nv = n / 16;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < nv; i += (size_t)gridDim.x * 256) {
+        const uint4 v = aa ? ((const uint4*)filt)[i] : ((const uint4*)scan)[i];
+        if (!aa) ((uint4*)filt)[i] = v;
+        bm_or_word(s_bm, v.x, prev);
+        bm_or_word(s_bm, v.y, prev);
+        bm_or_word(s_bm, v.z, prev);
+        bm_or_word(s_bm, v.w, prev);
+    }
+    if (blockIdx.x == 0 && threadIdx.x < n - nv * 16) {
+        const size_t i = nv * 16 + threadIdx.x;
+        const uint8_t v = aa ? filt[i] : scan[i];
+        if (!aa) filt[i] = v;
+        bm_or(s_bm, v, prev);
+    }
+    bm_flush(s_bm, rec + 8);
+}
+
+// One thread per page pixel: bicubic_kernel's taps from the (filtered) uint8 plane, the clip to the plane's range (bm: its bitmap),
+// prep_map_kernel<2>'s inversion and conversion; and for the same pixel nearest_kernel's coordinate into the scan, ink = scan <= 127
+// (the gather commutes with the per-pixel map).  bin may be NULL.
+__global__ __launch_bounds__(256) void scan_sample_kernel(const uint8_t* plane, const uint8_t* scan, int H, int W, uint8_t* img, uint8_t* bin,
+                                                          int Ho, int Wo, double fy, double ty, double fx, double tx, const unsigned* bm) {
+    const int ox = blockIdx.x * 256 + threadIdx.x, oy = blockIdx.y;
+    if (ox >= Wo) return;
+    const double yr = fy * (double)oy + ty, xc = fx * (double)ox + tx;
+    const double r0f = floor(yr), c0f = floor(xc);
+    const double tr = yr - r0f, tc = xc - c0f;
+    const int r0 = (int)r0f - 1, c0 = (int)c0f - 1;
+    int cols[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) cols[k] = mirror_idx(c0 + k, W);
+    double fr[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const size_t row = (size_t)mirror_idx(r0 + k, H) * W;
+        fr[k] = cubic(tc, ld(plane, row + cols[0]), ld(plane, row + cols[1]), ld(plane, row + cols[2]), ld(plane, row + cols[3]));
+    }
+    double v = cubic(tr, fr[0], fr[1], fr[2], fr[3]);
+    double lo, hi;
+    bm_range(bm, &lo, &hi);
+    v = v < lo ? lo : (v > hi ? hi : v);     // np.clip
+    const size_t o = (size_t)oy * Wo + ox;
+    img[o] = (uint8_t)((1.0 - v / 255.0) * 255.0);
+    if (bin) {
+        const int r = mirror_idx((int)(yr > 0.0 ? yr + 0.5 : yr - 0.5), H);
+        const int c = mirror_idx((int)(xc > 0.0 ? xc + 0.5 : xc - 0.5), W);
+        bin[o] = scan[(size_t)r * W + c] <= 127;
+    }
+}
+
+// the passes of a scan: radius per axis, 0 where scale_image_dev runs none (sigma <= 1e-15) or the pass is the identity (radius 0:
+// its one weight is 1.0)
+static void scan_radii(const pseg_scan& s, double sig[2], int rad[2]) {
+    sig[0] = std::max(0.0, ((double)s.H0 / (double)s.H - 1.0) / 2.0);
+    sig[1] = std::max(0.0, ((double)s.W0 / (double)s.W - 1.0) / 2.0);
+    for (int a = 0; a < 2; ++a) rad[a] = sig[a] <= 1e-15 ? 0 : (int)(4.0 * sig[a] + 0.5);
+}
+
+int scan_front_check(const pseg_scan& s, int index) {
+    if (!s.gray) return fail(PSEG_EINVAL, "scan %d: NULL argument", index);
+    if (s.H0 <= 0 || s.W0 <= 0 || s.H <= 0 || s.W <= 0) return fail(PSEG_EINVAL, "scan %d: empty scan or page shape (%d,%d)->(%d,%d)", index, s.H0, s.W0, s.H, s.W);
+    if ((int64_t)s.H0 * s.W0 > 0x7fffffffLL || (int64_t)s.H * s.W > 0x7fffffffLL || s.H0 > 65535 || s.H > 65535)
+        return fail(PSEG_EUNSUPPORTED, "scan %d: image too large", index);
+    double sig[2];
+    int rad[2];
+    scan_radii(s, sig, rad);
+    const double* w[2] = {s.wy, s.wx};
+    const int given[2] = {s.ry, s.rx};
+    for (int a = 0; a < 2; ++a)
+        if (sig[a] > 1e-15 && w[a] && given[a] != rad[a])
+            return fail(PSEG_EINVAL, "scan %d: anti-aliasing kernel radius %d does not match sigma %.17g", index, given[a], sig[a]);
+    return PSEG_OK;
+}
+
+size_t scan_front_weights(const pseg_scan& s, double* dst) {
+    double sig[2];
+    int rad[2];
+    scan_radii(s, sig, rad);
+    const double* w[2] = {s.wy, s.wx};
+    size_t n = 0;
+    for (int a = 0; a < 2; ++a) {
+        if (rad[a] == 0) continue;
+        const size_t k = (size_t)2 * rad[a] + 1;
+        if (dst) {
+            if (w[a]) memcpy(dst + n, w[a], k * 8);
+            else {
+                int r = 0;
+                const std::vector<double> own = host_gauss(sig[a], &r);
+                memcpy(dst + n, own.data(), k * 8);
+            }
+        }
+        n += k;
+    }
+    return n;
+}
+
+static inline size_t sf_up256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+size_t scan_front_work(const pseg_scan& s) {
+    double sig[2];
+    int rad[2];
+    scan_radii(s, sig, rad);
+    if (rad[0] == 0 && rad[1] == 0) return 0;
+    const bool fused = rad[0] <= SF_RMAX && rad[1] <= SF_RMAX;
+    return sf_up256((size_t)s.H0 * s.W0) * (!fused && rad[0] > 0 && rad[1] > 0 ? 2 : 1);
+}
+
+int scan_front_enqueue(const pseg_scan& s, const uint8_t* d_scan, const double* d_w, uint8_t* d_work, unsigned* d_rec, uint8_t* d_img,
+                       uint8_t* d_bin, uint8_t* d_orig, hipStream_t st) {
+    const int H0 = s.H0, W0 = s.W0;
+    const size_t n0 = (size_t)H0 * W0;
+    double sig[2];
+    int rad[2];
+    scan_radii(s, sig, rad);
+    const int sgrid = (int)std::min<size_t>((n0 / 16 + 255) / 256 + 1, 1024);
+    scan_stats_kernel<<<sgrid, 256, 0, st>>>(d_scan, n0, d_rec, d_orig);
+    const uint8_t* plane = d_scan;
+    const unsigned* bm = d_rec;
+    if (rad[0] > 0 || rad[1] > 0) {
+        if (!d_work || !d_w) return fail(PSEG_EINVAL, "scan front end: no workspace for the filtered plane");
+        if (rad[0] <= SF_RMAX && rad[1] <= SF_RMAX) {
+            scan_gauss_tile_kernel<<<dim3(cdiv(W0, SF_TW), cdiv(H0, SF_TH)), 256, 0, st>>>(d_scan, H0, W0, d_w, rad[0], rad[1], d_work, d_rec);
+        } else {
+            // one pass per launch, the last one into the first plane of the workspace
+            const dim3 grid(cdiv(W0, 256), H0);
+            uint8_t* const second = d_work + sf_up256(n0);
+            const uint8_t* cur = d_scan;
+            if (rad[0] > 0) {
+                uint8_t* const out = rad[1] > 0 ? second : d_work;
+                gauss_pass_kernel<uint8_t, 0><<<grid, 256, 0, st>>>(cur, H0, W0, d_w, rad[0], out);
+                cur = out;
+            }
+            if (rad[1] > 0) gauss_pass_kernel<uint8_t, 1><<<grid, 256, 0, st>>>(cur, H0, W0, d_w + (rad[0] > 0 ? 2 * rad[0] + 1 : 0), rad[1], d_work);
+            scan_select_kernel<<<sgrid, 256, 0, st>>>(d_scan, d_work, n0, d_rec);
+        }
+        plane = d_work;
+        bm = d_rec + 8;
+    }
+    double fy, ty, fx, tx;
+    warp_coeffs(H0, s.H, &fy, &ty);
+    warp_coeffs(W0, s.W, &fx, &tx);
+    scan_sample_kernel<<<dim3(cdiv(s.W, 256), s.H), 256, 0, st>>>(plane, d_scan, H0, W0, d_img, d_bin, s.H, s.W, fy, ty, fx, tx, bm);
+    PSEG_HIP(hipGetLastError());
+    return PSEG_OK;
+}
+
+}  // namespace pseg
+
+extern "C" int pseg_prepare_scans(int device, int n, const pseg_scan* scans, uint8_t* const* out_img, uint8_t* const* out_bin,
+                                  uint8_t* const* out_orig) {
+    if (n < 0 || (n > 0 && (!scans || !out_img || !out_bin))) return fail(PSEG_EINVAL, "bad argument");
+    // every scan is checked, and the staging laid out, before any device work starts
+    struct At { size_t scan, work, w, img; };
+    std::vector<At> at(n);
+    size_t b_scan = 0, b_work = 0, n_w = 0, b_img = 0;
+    for (int i = 0; i < n; ++i) {
+        PSEG_TRY(scan_front_check(scans[i], i));
+        if (!out_img[i] || !out_bin[i]) return fail(PSEG_EINVAL, "scan %d: NULL argument", i);
+        at[i] = At{b_scan, b_work, n_w, b_img};
+        b_scan += sf_up256((size_t)scans[i].H0 * scans[i].W0);
+        b_work += scan_front_work(scans[i]);
+        n_w += scan_front_weights(scans[i], nullptr);
+        b_img += sf_up256((size_t)scans[i].H * scans[i].W);
+    }
+    if (n == 0) return PSEG_OK;
+    PSEG_TRY(rz_set_dev(device));
+    DevMem mem;
+    hipStream_t st = nullptr;
+    uint8_t *d_scan = nullptr, *d_work = nullptr, *d_img = nullptr, *d_bin = nullptr, *d_orig = nullptr;
+    double* d_w = nullptr;
+    unsigned* d_rec = nullptr;
+    PSEG_TRY(mem.alloc(&d_scan, b_scan));
+    PSEG_TRY(mem.alloc(&d_work, b_work));
+    PSEG_TRY(mem.alloc(&d_w, n_w));
+    PSEG_TRY(mem.alloc(&d_rec, (size_t)n * SCAN_REC_WORDS));
+    PSEG_TRY(mem.alloc(&d_img, b_img));
+    PSEG_TRY(mem.alloc(&d_bin, b_img));
+    PSEG_TRY(mem.alloc(&d_orig, b_scan));
+    std::vector<double> h_w(std::max<size_t>(n_w, 1));
+    for (int i = 0; i < n; ++i) scan_front_weights(scans[i], h_w.data() + at[i].w);
+    struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{st};     // (h_w and the caller's arrays outlive the copies)
+    if (n_w) PSEG_HIP(hipMemcpyAsync(d_w, h_w.data(), n_w * 8, hipMemcpyHostToDevice, st));
+    PSEG_HIP(hipMemsetAsync(d_rec, 0, (size_t)n * SCAN_REC_WORDS * sizeof(unsigned), st));
+    for (int i = 0; i < n; ++i) {
+        const pseg_scan& s = scans[i];
+        const size_t n0 = (size_t)s.H0 * s.W0, n1 = (size_t)s.H * s.W;
+        uint8_t* const orig = out_orig && out_orig[i] ? d_orig + at[i].scan : nullptr;
+        PSEG_HIP(hipMemcpyAsync(d_scan + at[i].scan, s.gray, n0, hipMemcpyHostToDevice, st));
+        PSEG_TRY(scan_front_enqueue(s, d_scan + at[i].scan, d_w + at[i].w, d_work + at[i].work, d_rec + (size_t)i * SCAN_REC_WORDS,
+                                    d_img + at[i].img, d_bin + at[i].img, orig, st));
+        PSEG_HIP(hipMemcpyAsync(out_img[i], d_img + at[i].img, n1, hipMemcpyDeviceToHost, st));
+        PSEG_HIP(hipMemcpyAsync(out_bin[i], d_bin + at[i].img, n1, hipMemcpyDeviceToHost, st));
+        if (orig) PSEG_HIP(hipMemcpyAsync(out_orig[i], orig, n0, hipMemcpyDeviceToHost, st));
+    }
+    PSEG_HIP(hipStreamSynchronize(st));
+    return PSEG_OK;
+}

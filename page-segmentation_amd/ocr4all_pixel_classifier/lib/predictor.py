@@ -207,3 +207,80 @@ class Predictor:
                 if inputs[k] is None:
                     self.write_masks(data, output_dir=output_dir, level=level)
                 yield paths[k]
+
+    def _scan_route(self, entry: SingleData, path):
+        """Whether write_masks_scans may send this entry through the scan chain, as far as that shows before the file is read."""
+        from . import output
+        net = self.network
+        return (entry.image is None and entry.image_path is not None and output.DEVICE_PNG and output.is_png_target(path)
+                and self._chain_ops() is not None and net.n_classes <= 256 and not getattr(net, "_rgb", False))
+
+    def write_masks_scans(self, entries, loader, output_dir=None, level=None, chunk_pages=64, decode_threads=2):
+        """loader.load_images + write_masks_dataset for entries that name their scan by image_path, without the normalised page, the
+        binarisation or the label map visiting the host: the decoded gray scans go through Engine.predict_chain_scans chunk_pages at
+        a time (binarisation and line-height normalisation on the device, then the page chain), and each PNG stream is written to
+        its file as it arrives.  Same files, names and bytes as that pair of calls; settings.high_res_output as there.  loader: a
+        DatasetLoader, read for target_line_height and max_width.  While the device call of one chunk runs, decode_threads threads
+        decode the files of the next one (dataset._imread_gray; the call releases the GIL).  Entries the scan chain cannot take -- a
+        pre-loaded entry.image, a max_width that brings the second stage, another extension than ".png", output.DEVICE_PNG = False,
+        a foreign post-processor, an rgb network, more than 256 classes -- go through loader.load_images + write_masks, in place;
+        the others are not modified.  Yields the three paths per entry, in order; a file that cannot be decoded raises when its
+        entry is reached, after the paths of the entries in front of it."""
+        from concurrent.futures import ThreadPoolExecutor
+        from pseg_amd import engine as _eng
+        from . import dataset as _ds
+        from . import output
+        level = output.DEVICE_PNG_LEVEL if level is None else level
+        output_dir = output_dir if output_dir is not None else self.settings.output
+        if output_dir is None:
+            raise Exception("write_masks needs an output directory")
+        for sub in ("color", "overlay", "inverted"):
+            os.makedirs(os.path.join(output_dir, sub), exist_ok=True)
+        entries = list(entries)
+        step = max(1, int(chunk_pages))
+        names = ("color", "overlay", "inverted")
+        high_res = bool(self.settings.high_res_output)
+
+        def decode(entry):
+            return np.ascontiguousarray(_ds._imread_gray(entry.image_path), dtype=np.uint8)
+
+        with ThreadPoolExecutor(max(1, int(decode_threads))) as pool:
+            def start(i):
+                """Chunk i's paths and the decodes of its device candidates, in flight."""
+                chunk = entries[i:i + step]
+                paths = [output.output_paths(output_dir, e) for e in chunk]
+                return chunk, paths, [pool.submit(decode, e) if self._scan_route(e, p[0]) else None for e, p in zip(chunk, paths)]
+
+            ahead = start(0) if entries else None
+            for i in range(0, len(entries), step):
+                chunk, paths, pending = ahead
+                ahead = start(i + step) if i + step < len(entries) else None
+                scans, failed = [None] * len(chunk), None
+                for k, fut in enumerate(pending):
+                    if fut is None:
+                        continue
+                    try:
+                        scan = fut.result()
+                    except BaseException as exc:
+                        failed = (k, exc)
+                        break
+                    scale = loader.target_line_height / chunk[k].line_height_px
+                    # (the max_width stage shows only once the scan's shape is known)
+                    if loader.max_width is None or loader.max_width / _eng.rescale_shape(scan.shape, scale)[1] >= 1.0:
+                        scans[k] = (scan, scale)
+                stop = len(chunk) if failed is None else failed[0]
+                on_device = [k for k in range(stop) if scans[k] is not None]
+                if on_device:
+                    def to_file(page, name, stream, paths=paths, on_device=on_device):
+                        with open(paths[on_device[page]][names.index(name)], "wb") as f:
+                            f.write(stream)
+                    self.network.model.predict_chain_scans(
+                        [scans[k][0] for k in on_device], [scans[k][1] for k in on_device], high_res=high_res,
+                        post_ops=self._chain_ops(), exact_labels=self.network.exact == "labels", lut=self.settings.color_map.lut(),
+                        which=names, png_level=level, sink=to_file)
+                for k in range(stop):
+                    if scans[k] is None:
+                        self.write_masks(loader.load_images(chunk[k]), output_dir=output_dir, level=level)
+                    yield paths[k]
+                if failed is not None:
+                    raise failed[1]

@@ -30,7 +30,7 @@ EXPORTED_SYMBOLS = (
     "pseg_png_bound", "pseg_png_encode_device", "pseg_masks_png_device_u8", "pseg_png_encode", "pseg_masks_png", "pseg_predict_chain_png",
     "pseg_png_bound_lv", "pseg_png_encode_device_lv", "pseg_masks_png_device_u8_lv", "pseg_png_encode_lv", "pseg_masks_png_lv",
     "pseg_predict_chain_png_lv", "pseg_png_code_lengths", "pseg_predict_chain_pages_png", "pseg_chain_units",
-    "pseg_predict_chain_pages_mixed_png", "pseg_chain_units_mixed",
+    "pseg_predict_chain_pages_mixed_png", "pseg_chain_units_mixed", "pseg_predict_chain_scans_png", "pseg_prepare_scans",
     "pseg_rescale_shape", "pseg_gaussian_kernel", "pseg_resize_nearest", "pseg_resize_nearest_device", "pseg_scale_image",
     "pseg_prepare_images", "pseg_affine_warp", "pseg_affine_warp_fill", "pseg_brightness_shift",
     "pseg_eval_confusion", "pseg_cc_label", "pseg_cc_tables",
@@ -42,6 +42,12 @@ PLAN_FROM_ENV = bool(os.environ.get("PSEG_PLAN_FROM_ENV"))   # test harness / to
 
 # pseg_chain_sink: int (*)(void* user, int page, int which, const uint8_t* data, size_t n_bytes)
 CHAIN_SINK = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_uint8), ctypes.c_size_t)
+
+
+class SCAN(ctypes.Structure):
+    """pseg_scan: one gray scan and the page it becomes (pseg_prepare_scans, pseg_predict_chain_scans_png)."""
+    _fields_ = [("gray", ctypes.c_void_p), ("H0", ctypes.c_int), ("W0", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int),
+                ("wy", ctypes.c_void_p), ("ry", ctypes.c_int), ("wx", ctypes.c_void_p), ("rx", ctypes.c_int), ("final_is_scan", ctypes.c_int)]
 
 
 class PsegError(Exception):
@@ -164,6 +170,8 @@ def lib():
     L.pseg_chain_units.argtypes = [i, vp, vp, vp, vp, i, vp, vp, i]
     L.pseg_predict_chain_pages_mixed_png.argtypes = L.pseg_predict_chain_pages_png.argtypes
     L.pseg_chain_units_mixed.argtypes = [i, vp, vp, i, vp, vp, vp, i]
+    L.pseg_prepare_scans.argtypes = [i, i, c.POINTER(SCAN), vp, vp, vp]
+    L.pseg_predict_chain_scans_png.argtypes = [vp, i, c.POINTER(SCAN), c.POINTER(i), i, c.c_uint, vp, i, i, c.c_uint, i, CHAIN_SINK, vp]
     _LIB = L
     return L
 
@@ -485,13 +493,22 @@ class Engine:
                     raise PsegError("page %d: binary has shape %r, the label map %r" % (k, b.shape, fs))
             final.append(fs)
             bins.append(b)
-        want = sum(1 << MASK_NAMES.index(w) for w in set(which)) | (16 if labels else 0)
         P, I = ctypes.c_void_p * max(n, 1), ctypes.c_int * max(n, 1)
         ip = P(*[im.ctypes.data for im in imgs])
         bp = P(*[None if b is None else b.ctypes.data for b in bins])
         hs, ws = I(*[im.shape[0] for im in imgs]), I(*[im.shape[1] for im in imgs])
         ho = I(*[0 if o is None else int(o[0]) for o in outs])
         wo = I(*[0 if o is None else int(o[1]) for o in outs])
+        entry = lib().pseg_predict_chain_pages_mixed_png if mixed else lib().pseg_predict_chain_pages_png
+        return self._chain_list(final, post_ops, lut, which, labels, sink,
+                                lambda ops, t, want, cb: entry(self._h, n, ip, hs, ws, ho, wo, bp, ops, len(post_ops), 1 if exact_labels else 0,
+                                                               _ptr(t), 0 if t is None else t.shape[0], int(png_level), want, int(unit_cap), cb, None))
+
+    def _chain_list(self, final, post_ops, lut, which, labels, sink, call):
+        """The part the list entries share: op ids, colour table, `want` bits and the C sink that feeds `sink` or collects the result
+        dicts; call(ops, table, want, c_sink) -> the entry's return code.  final[i]: the shape of page i's label map."""
+        n = len(final)
+        want = sum(1 << MASK_NAMES.index(w) for w in set(which)) | (16 if labels else 0)
         ops = (ctypes.c_int * max(len(post_ops), 1))(*[self.POST_OPS[o] if isinstance(o, str) else int(o) for o in post_ops])
         t = None if lut is None else np.ascontiguousarray(lut, dtype=np.uint8).reshape(-1, 3)
         collected = [{"labels": None, "masks": {}} for _ in range(n)] if sink is None else None
@@ -514,13 +531,31 @@ class Engine:
                 raised.append(exc)
                 return 1
 
-        entry = lib().pseg_predict_chain_pages_mixed_png if mixed else lib().pseg_predict_chain_pages_png
-        rc = entry(self._h, n, ip, hs, ws, ho, wo, bp, ops, len(post_ops), 1 if exact_labels else 0,
-                   _ptr(t), 0 if t is None else t.shape[0], int(png_level), want, int(unit_cap), CHAIN_SINK(on_output), None)
+        rc = call(ops, t, want, CHAIN_SINK(on_output))
         if raised:
             raise raised[0]
         _check(rc)
         return collected
+
+    def predict_chain_scans(self, scans, scales, high_res=False, post_ops=(), exact_labels=False, lut=None,
+                            which=("color", "overlay", "inverted"), labels=False, png_level=0, unit_cap=0, sink=None):
+        """Scans as they come off disk through the chain to PNG streams (pseg_predict_chain_scans_png): scans[i] a gray uint8 (H0,W0)
+        array, scales[i] = target_line_height / line_height_px.  The binarisation (ink = scan <= 127) and the line-height
+        normalisation run on the device in front of the network: neither the normalised page nor the ink map visits the host.
+        Every stream and label map equals predict_chain_pages(mixed=True) fed with prepare_images(scan, where(scan > 127, 255, 0),
+        scale): the page, `bin` as the binarisation -- with high_res the label map is rescaled to the scan's shape and `orig` is the
+        binarisation (PredictSettings.high_res_output).  Keywords, result dicts and the sink contract are predict_chain_pages'
+        (mixed=True: a callable sink sees the planner's order)."""
+        for w in which:
+            if w not in MASK_NAMES:
+                raise PsegError("unknown mask %r (one of %r)" % (w, MASK_NAMES))
+        table, keep, plans = scan_table(scans, scales, high_res)
+        n = len(plans)
+        final = [keep[k].shape if high_res else plans[k][:2] for k in range(n)]
+        return self._chain_list(final, post_ops, lut, which, labels, sink,
+                                lambda ops, t, want, cb: lib().pseg_predict_chain_scans_png(
+                                    self._h, n, table, ops, len(post_ops), 1 if exact_labels else 0, _ptr(t), 0 if t is None else t.shape[0],
+                                    int(png_level), want, int(unit_cap), cb, None))
 
     def predict_batch(self, images, dtype=np.int64, out=None):
         """Label maps of a list of (H,W) uint8 pages (sizes may differ); copies overlap compute.
@@ -904,6 +939,43 @@ def prepare_images(image, binary, scale, max_width=None, device=0, want_stage1=F
                                      _kptr(k2[0]), k2[0][1], _kptr(k2[1]), k2[1][1],
                                      _ptr(o_img), _ptr(o_bin), _ptr(o_orig), _ptr(st1) if st1 is not None else None))
     return (o_img, o_bin, o_orig, st1) if want_stage1 else (o_img, o_bin, o_orig)
+
+
+def scan_plan(shape, scale):
+    """What the scan entries are told about one scan: (H, W, (wy or None, ry), (wx or None, rx)) -- the page's shape
+    (rescale_shape) and the per-axis anti-aliasing kernels (aa_kernels).  Host arithmetic."""
+    H, W = rescale_shape(shape, scale)
+    if H <= 0 or W <= 0:
+        raise PsegError("scale %r leaves no page of a %r scan" % (scale, tuple(shape)))
+    ky, kx = aa_kernels(shape, (H, W))
+    return H, W, ky, kx
+
+
+def scan_table(scans, scales, high_res=False):
+    """The pseg_scan array of a list of gray scans -> (table, scans as contiguous uint8 arrays, plans); the table points into the
+    arrays and the plans' kernels: keep all three alive while it is in use."""
+    arrs = [np.ascontiguousarray(s, dtype=np.uint8) for s in scans]
+    if len(arrs) != len(scales):
+        raise PsegError("scales must have one entry per scan")
+    if any(a.ndim != 2 for a in arrs):
+        raise PsegError("scans must be 2-D uint8 arrays")
+    plans = [scan_plan(a.shape, float(sc)) for a, sc in zip(arrs, scales)]
+    table = (SCAN * max(len(arrs), 1))()
+    for k, (a, (H, W, ky, kx)) in enumerate(zip(arrs, plans)):
+        table[k] = SCAN(a.ctypes.data, a.shape[0], a.shape[1], H, W, None if ky[0] is None else ky[0].ctypes.data, ky[1],
+                        None if kx[0] is None else kx[0].ctypes.data, kx[1], 1 if high_res else 0)
+    return table, arrs, plans
+
+
+def prepare_scans(scans, scales, device=0):
+    """prepare_images(scan, where(scan > 127, 255, 0), scale) for a list of gray scans in one call of the scan chain's front end
+    (pseg_prepare_scans) -> [(img uint8, bin uint8, orig_bin uint8)], bit for bit."""
+    table, arrs, plans = scan_table(scans, scales)
+    n = len(arrs)
+    out = [(np.empty(p[:2], np.uint8), np.empty(p[:2], np.uint8), np.empty(a.shape, np.uint8)) for a, p in zip(arrs, plans)]
+    P = ctypes.c_void_p * max(n, 1)
+    _check(lib().pseg_prepare_scans(int(device), n, table, *[P(*[o[k].ctypes.data for o in out]) for k in range(3)]))
+    return out
 
 
 FILL_MODES = {"nearest": 0, "constant": 1, "reflect": 2, "wrap": 3}
