@@ -18,62 +18,36 @@ struct PagesSet {
     enum { IMG = 0, LAB = 1, LAB2 = 2, BIN = 3, PNG = 4, PAD = 5, CLAB = 6, SCAN = 7, FILT = 8, REC = 9, NDEV = 10 };
     // pages / network labels / resize + bbox ping-pong / binarisations / encoder workspace / mixed units: the pages padded to canvas-sized
     // page slots / the slots' canvas-sized label maps / scan chain: the unit's scans / their filtered planes / their records
-    uint8_t* d[NDEV] = {};
-    size_t d_bytes[NDEV] = {};
-    uint8_t* h_in = nullptr;            // page-locked: pages and binarisations of callers with pageable arrays
-    uint8_t* h_out = nullptr;           // page-locked: the unit's encoded streams (+ label maps), grown to the bytes units really have
-    unsigned long long* h_tot = nullptr;   // page-locked: [pages][4] stream sizes
-    size_t h_in_bytes = 0, h_out_bytes = 0, h_tot_bytes = 0;
-    hipEvent_t up = nullptr, done = nullptr, down = nullptr;   // uploads landed / compute + sizes landed / downloads landed
+    GrowDev d[NDEV];
+    GrowPin h_in;                        // pages and binarisations of callers with pageable arrays
+    GrowPin h_out;                       // the unit's encoded streams (+ label maps), grown to the bytes units really have
+    GrowPin h_tot;                       // [pages][4] stream sizes (unsigned long long)
 };
 struct ChainPagesState {
     PagesSet set[2];
-    uint8_t* d_lut = nullptr;
-    MixedPage* d_tab = nullptr;         // the page table of a mixed call (one entry per page of the list, in the planner's order) ...
-    MixedPage* h_tab = nullptr;         // ... and its page-locked source
-    size_t tab_entries = 0;
-    double* d_wt = nullptr;             // the anti-aliasing weights of a scan call (every scan's, in the planner's order) ...
-    double* h_wt = nullptr;             // ... and their page-locked source
-    size_t wt_entries = 0;
+    PipeSet ev[2];                      // uploads landed / compute + sizes landed / downloads landed
+    GrowDev d_lut;
+    GrowDev d_tab;                       // the page table of a mixed call (one MixedPage per page of the list, in the planner's order) ...
+    GrowPin h_tab;                       // ... and its page-locked source
+    GrowDev d_wt;                        // the anti-aliasing weights of a scan call (every scan's doubles, in the planner's order) ...
+    GrowPin h_wt;                        // ... and their page-locked source
 };
 
 struct ChainState {
     hipStream_t s_aux = nullptr;        // uploads of the binarisation / colour table beside the network's kernels
     hipEvent_t ev_aux = nullptr;
-    uint8_t* d_buf[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    size_t cap[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    GrowDev buf[7];
     ChainPagesState* pages = nullptr;
 };
 enum { CB_IMG = 0, CB_LAB = 1, CB_LAB2 = 2, CB_BIN = 3, CB_MASKS = 4, CB_LUT = 5, CB_I64 = 6 };
 
-static int censure(ChainState& c, int slot, size_t bytes) {
-    if (c.cap[slot] >= bytes && c.d_buf[slot]) return PSEG_OK;
-    if (c.d_buf[slot]) (void)hipFree(c.d_buf[slot]);
-    c.d_buf[slot] = nullptr;
-    c.cap[slot] = 0;
-    PSEG_HIP(hipMalloc((void**)&c.d_buf[slot], bytes));
-    c.cap[slot] = bytes;
-    return PSEG_OK;
-}
-
-// the staging sets' memory (device and page-locked); the events stay.  The caller has waited for the device.
+// the staging sets' memory (device and page-locked); the events and the colour table stay.  The caller has waited for the device.
 static void pages_release(ChainPagesState& p) {
-    if (p.d_tab) (void)hipFree(p.d_tab);
-    if (p.h_tab) (void)hipHostFree(p.h_tab);
-    p.d_tab = p.h_tab = nullptr;
-    p.tab_entries = 0;
-    if (p.d_wt) (void)hipFree(p.d_wt);
-    if (p.h_wt) (void)hipHostFree(p.h_wt);
-    p.d_wt = p.h_wt = nullptr;
-    p.wt_entries = 0;
+    for (GrowDev* b : {&p.d_tab, &p.d_wt}) b->release();
+    for (GrowPin* b : {&p.h_tab, &p.h_wt}) b->release();
     for (PagesSet& s : p.set) {
-        for (int i = 0; i < PagesSet::NDEV; ++i) { if (s.d[i]) (void)hipFree(s.d[i]); s.d[i] = nullptr; s.d_bytes[i] = 0; }
-        if (s.h_in) (void)hipHostFree(s.h_in);
-        if (s.h_out) (void)hipHostFree(s.h_out);
-        if (s.h_tot) (void)hipHostFree(s.h_tot);
-        s.h_in = s.h_out = nullptr;
-        s.h_tot = nullptr;
-        s.h_in_bytes = s.h_out_bytes = s.h_tot_bytes = 0;
+        for (GrowDev& b : s.d) b.release();
+        for (GrowPin* b : {&s.h_in, &s.h_out, &s.h_tot}) b->release();
     }
 }
 
@@ -87,19 +61,25 @@ void chain_free(Engine& e) {
     if (!c) return;
     if (c->pages) {
         pages_release(*c->pages);
-        for (PagesSet& s : c->pages->set) {
-            if (s.up) (void)hipEventDestroy(s.up);
-            if (s.done) (void)hipEventDestroy(s.done);
-            if (s.down) (void)hipEventDestroy(s.down);
-        }
-        if (c->pages->d_lut) (void)hipFree(c->pages->d_lut);
+        for (PipeSet& s : c->pages->ev) s.destroy();
+        c->pages->d_lut.release();
         delete c->pages;
     }
-    for (int i = 0; i < 8; ++i) if (c->d_buf[i]) (void)hipFree(c->d_buf[i]);
+    for (GrowDev& b : c->buf) b.release();
     if (c->ev_aux) (void)hipEventDestroy(c->ev_aux);
     if (c->s_aux) (void)hipStreamDestroy(c->s_aux);
     delete c;
     e.chain = nullptr;
+}
+
+// the engine's chain state with its stream and event, made on the first chain call
+static int chain_state(Engine& e) {
+    if (e.chain) return PSEG_OK;
+    auto* nc = new ChainState();
+    e.chain = nc;
+    PSEG_HIP(hipStreamCreateWithFlags(&nc->s_aux, hipStreamNonBlocking));
+    PSEG_HIP(hipEventCreateWithFlags(&nc->ev_aux, hipEventDisableTiming));
+    return PSEG_OK;
 }
 
 __global__ void chain_widen_kernel(const uint8_t* in, int64_t* out, size_t n) {
@@ -133,7 +113,6 @@ __global__ __launch_bounds__(256) void pages_crop_kernel(const uint8_t* clab, ui
         dst[i] = src[r * Wp + (i - r * w)];
     }
 }
-
 }  // namespace pseg
 
 using namespace pseg;
@@ -168,6 +147,37 @@ static int chain_check(const Engine& e, int page, const uint8_t* img, int H, int
     }
     return PSEG_OK;
 }
+// Where chain_post_enqueue's walk ends: 0 = the network's map, 1 = bufA, 2 = bufB.  The page list's plan places the final maps with
+// this before anything runs, so it stands beside the walk: the two change together.
+static int chain_final_slot(bool resize, const int* post_ops, int n_post) {
+    int where = resize ? 1 : 0;
+    for (int i = 0; i < n_post; ++i)
+        if (post_ops[i] == PSEG_POST_BBOX) where = where == 1 ? 2 : 1;
+    return where;
+}
+// scale_to_original_shape (an order-0 gather of the label map, preserving_resize(pred, original_shape)), then the post-processors in
+// order: the vote works in place, the boxes ping-pong between bufA and bufB.  bin_ready (may be NULL): the binarisation's upload, waited
+// for behind the resize.  *final (may be NULL): the map the walk ended in.
+static int chain_post_enqueue(Engine& e, uint8_t* lab, uint8_t* bufA, uint8_t* bufB, const uint8_t* bin, int H, int W, int Hl, int Wl, bool resize,
+                              const int* post_ops, int n_post, hipStream_t st, uint8_t** final, hipEvent_t bin_ready = nullptr) {
+    uint8_t* cur = lab;
+    if (resize) {
+        PSEG_TRY(pseg_resize_nearest_device(e.device, cur, H, W, 1, bufA, Hl, Wl, st));
+        cur = bufA;
+    }
+    if (bin_ready) PSEG_HIP(hipStreamWaitEvent(st, bin_ready, 0));
+    for (int i = 0; i < n_post; ++i) {
+        if (post_ops[i] == PSEG_POST_CC_VOTE) {
+            PSEG_TRY(pseg_cc_vote_device_u8(e.device, cur, bin, Hl, Wl, e.n_classes, st));
+        } else {
+            uint8_t* const dst = cur == bufA ? bufB : bufA;
+            PSEG_TRY(pseg_bbox_fill_device_u8(e.device, cur, dst, Hl, Wl, e.n_classes, st));
+            cur = dst;
+        }
+    }
+    if (final) *final = cur;
+    return PSEG_OK;
+}
 
 static int chain_run(pseg_engine* h, const uint8_t* img, int H, int W, int Ho, int Wo, const uint8_t* binary,
                      const int* post_ops, int n_post, unsigned flags, int64_t* labels, uint8_t* labels_u8,
@@ -180,7 +190,7 @@ static int chain_run(pseg_engine* h, const uint8_t* img, int H, int W, int Ho, i
     const bool want_masks = color || overlay || inverted || fg_color || want_png;
     ChainReq req;
     PSEG_TRY(chain_check(e, -1, img, H, W, Ho, Wo, binary, post_ops, n_post, flags, want_masks, want_png, lut, n_lut, png ? png->level : 0, &req));
-    const bool resize = req.resize, need_bin = req.need_bin;
+    const bool need_bin = req.need_bin;
     const int Hl = req.Hl, Wl = req.Wl;
     if (want_png) {
         const size_t bound = pseg_png_bound_lv(Hl, Wl, 3, 0, png->level);
@@ -188,68 +198,48 @@ static int chain_run(pseg_engine* h, const uint8_t* img, int H, int W, int Ho, i
             if (png->out[k] && png->cap[k] < bound) return fail(PSEG_EINVAL, "png: output buffer %d of %zu bytes, pseg_png_bound is %zu", k, png->cap[k], bound);
     }
     PSEG_HIP(hipSetDevice(e.device));
-    if (!e.chain) {
-        auto* nc = new ChainState();
-        e.chain = nc;
-        PSEG_HIP(hipStreamCreateWithFlags(&nc->s_aux, hipStreamNonBlocking));
-        PSEG_HIP(hipEventCreateWithFlags(&nc->ev_aux, hipEventDisableTiming));
-    }
+    PSEG_TRY(chain_state(e));
     ChainState& c = *(ChainState*)e.chain;
     hipStream_t st = e.stream;
     const size_t npx = (size_t)H * W, nl = (size_t)Hl * Wl;
     const size_t nla = (nl + 255) & ~(size_t)255;          // buffer stride: the mask / vote kernels want 4-byte aligned maps
     // a reallocation must not race with the previous call's work: every call ends synchronised, so the buffers are idle here
-    PSEG_TRY(censure(c, CB_IMG, npx * e.in_ch));
-    PSEG_TRY(censure(c, CB_LAB, npx));
-    PSEG_TRY(censure(c, CB_LAB2, 2 * nla));          // resize target + bounding-box ping-pong
-    if (need_bin) PSEG_TRY(censure(c, CB_BIN, nl));
-    if (want_masks) { if (!want_png) PSEG_TRY(censure(c, CB_MASKS, 4 * nla * 3)); PSEG_TRY(censure(c, CB_LUT, (size_t)n_lut * 3)); }
-    if (labels) PSEG_TRY(censure(c, CB_I64, nl * 8));
-    // every way out -- also an error return in the middle -- ends with both streams drained: copies from / to the caller's host
-    // arrays must not be in flight when the caller gets its buffers back
-    struct Drain { hipStream_t a, b; ~Drain() { (void)hipStreamSynchronize(a); (void)hipStreamSynchronize(b); } } drain{st, c.s_aux};
+    PSEG_TRY(c.buf[CB_IMG].ensure(npx * e.in_ch, "chain page"));
+    PSEG_TRY(c.buf[CB_LAB].ensure(npx, "chain labels"));
+    PSEG_TRY(c.buf[CB_LAB2].ensure(2 * nla, "chain resize + box maps"));          // resize target + bounding-box ping-pong
+    if (need_bin) PSEG_TRY(c.buf[CB_BIN].ensure(nl, "chain binarisation"));
+    if (want_masks && !want_png) PSEG_TRY(c.buf[CB_MASKS].ensure(4 * nla * 3, "chain masks"));
+    if (want_masks) PSEG_TRY(c.buf[CB_LUT].ensure((size_t)n_lut * 3, "chain colour table"));
+    if (labels) PSEG_TRY(c.buf[CB_I64].ensure(nl * 8, "chain int64 labels"));
+    uint8_t* const d_img = c.buf[CB_IMG].p, * const d_bin = c.buf[CB_BIN].p, * const d_lut = c.buf[CB_LUT].p;
+    StreamDrain drain{{st, c.s_aux, nullptr}};
     // uploads: the page on the engine's stream (the network waits for it anyway), binarisation and colour table beside it
-    PSEG_HIP(hipMemcpyAsync(c.d_buf[CB_IMG], img, npx * e.in_ch, hipMemcpyHostToDevice, st));
-    if (need_bin) PSEG_HIP(hipMemcpyAsync(c.d_buf[CB_BIN], binary, nl, hipMemcpyHostToDevice, c.s_aux));
-    if (want_masks) PSEG_HIP(hipMemcpyAsync(c.d_buf[CB_LUT], lut, (size_t)n_lut * 3, hipMemcpyHostToDevice, c.s_aux));
+    PSEG_HIP(hipMemcpyAsync(d_img, img, npx * e.in_ch, hipMemcpyHostToDevice, st));
+    if (need_bin) PSEG_HIP(hipMemcpyAsync(d_bin, binary, nl, hipMemcpyHostToDevice, c.s_aux));
+    if (want_masks) PSEG_HIP(hipMemcpyAsync(d_lut, lut, (size_t)n_lut * 3, hipMemcpyHostToDevice, c.s_aux));
     if (need_bin) PSEG_HIP(hipEventRecord(c.ev_aux, c.s_aux));
     // 1. the network: uint8 argmax labels (float32 engine: bit-exact; bf16 engine: throughput labels, or the label-exact mode)
     if ((flags & PSEG_CHAIN_EXACT_LABELS) && e.mode == PSEG_MODE_BF16)
-        PSEG_TRY(pseg_predict_exact_labels_device(h, c.d_buf[CB_IMG], H, W, c.d_buf[CB_LAB], nullptr, nullptr, st));
+        PSEG_TRY(pseg_predict_exact_labels_device(h, d_img, H, W, c.buf[CB_LAB].p, nullptr, nullptr, st));
     else
-        PSEG_TRY(predict_device(e, c.d_buf[CB_IMG], H, W, nullptr, nullptr, nullptr, c.d_buf[CB_LAB], st, nullptr));
-    uint8_t* cur = c.d_buf[CB_LAB];
-    uint8_t* const bufA = c.d_buf[CB_LAB2];
-    uint8_t* const bufB = c.d_buf[CB_LAB2] + nla;
-    // 2. scale_to_original_shape: order-0 gather of the label map (preserving_resize(pred, original_shape))
-    if (resize) {
-        PSEG_TRY(pseg_resize_nearest_device(e.device, cur, H, W, 1, bufA, Hl, Wl, st));
-        cur = bufA;
-    }
-    // 3. post-processors, in order
-    if (need_bin) PSEG_HIP(hipStreamWaitEvent(st, c.ev_aux, 0));
-    for (int i = 0; i < n_post; ++i) {
-        if (post_ops[i] == PSEG_POST_CC_VOTE) {
-            PSEG_TRY(pseg_cc_vote_device_u8(e.device, cur, c.d_buf[CB_BIN], Hl, Wl, e.n_classes, st));
-        } else {
-            uint8_t* const dst = cur == bufA ? bufB : bufA;
-            PSEG_TRY(pseg_bbox_fill_device_u8(e.device, cur, dst, Hl, Wl, e.n_classes, st));
-            cur = dst;
-        }
-    }
+        PSEG_TRY(predict_device(e, d_img, H, W, nullptr, nullptr, nullptr, c.buf[CB_LAB].p, st, nullptr));
+    // 2. / 3. resize and post-processors
+    uint8_t* cur = nullptr;
+    PSEG_TRY(chain_post_enqueue(e, c.buf[CB_LAB].p, c.buf[CB_LAB2].p, c.buf[CB_LAB2].p + nla, d_bin, H, W, Hl, Wl, req.resize, post_ops, n_post, st, &cur,
+                                need_bin ? c.ev_aux : nullptr));
     // 4. outputs
     if (labels_u8) PSEG_HIP(hipMemcpyAsync(labels_u8, cur, nl, hipMemcpyDeviceToHost, st));
     if (labels) {
-        chain_widen_kernel<<<(int)std::min<size_t>((nl + 255) / 256, 8192), 256, 0, st>>>(cur, (int64_t*)c.d_buf[CB_I64], nl);
-        PSEG_HIP(hipMemcpyAsync(labels, c.d_buf[CB_I64], nl * 8, hipMemcpyDeviceToHost, st));
+        chain_widen_kernel<<<(int)std::min<size_t>((nl + 255) / 256, 8192), 256, 0, st>>>(cur, (int64_t*)c.buf[CB_I64].p, nl);
+        PSEG_HIP(hipMemcpyAsync(labels, c.buf[CB_I64].p, nl * 8, hipMemcpyDeviceToHost, st));
     }
     if (want_png) {
         // the band kernel selects the masks' pixels itself: the RGB masks are never written; synchronises `st`
-        PSEG_TRY(pseg_masks_png_device_u8_lv(e.device, cur, c.d_buf[CB_BIN], c.d_buf[CB_LUT], n_lut, Hl, Wl, 0, png->level, png->out, png->cap, png->n_bytes, st));
+        PSEG_TRY(pseg_masks_png_device_u8_lv(e.device, cur, d_bin, d_lut, n_lut, Hl, Wl, 0, png->level, png->out, png->cap, png->n_bytes, st));
     } else if (want_masks) {
-        uint8_t* m = c.d_buf[CB_MASKS];
+        uint8_t* m = c.buf[CB_MASKS].p;
         uint8_t* dm[4] = {color ? m : nullptr, overlay ? m + nla * 3 : nullptr, inverted ? m + 2 * nla * 3 : nullptr, fg_color ? m + 3 * nla * 3 : nullptr};
-        PSEG_TRY(pseg_masks_device_u8(e.device, cur, c.d_buf[CB_BIN], c.d_buf[CB_LUT], n_lut, Hl, Wl, dm[0], dm[1], dm[2], dm[3], st));
+        PSEG_TRY(pseg_masks_device_u8(e.device, cur, d_bin, d_lut, n_lut, Hl, Wl, dm[0], dm[1], dm[2], dm[3], st));
         uint8_t* hm[4] = {color, overlay, inverted, fg_color};
         for (int k = 0; k < 4; ++k)
             if (hm[k]) PSEG_HIP(hipMemcpyAsync(hm[k], dm[k], nl * 3, hipMemcpyDeviceToHost, st));
@@ -279,38 +269,7 @@ extern "C" int pseg_predict_chain_png(pseg_engine* h, const uint8_t* img, int H,
                                       const uint8_t* lut, int n_lut, uint8_t* const png[4], const size_t cap[4], size_t n_bytes[4]) {
     return pseg_predict_chain_png_lv(h, img, H, W, Ho, Wo, binary, post_ops, n_post, flags, labels, labels_u8, lut, n_lut, 0, png, cap, n_bytes);
 }
-
 // ---- a page list through the chain to PNG streams (lib/predictor.py:27-30 x :49-54) ------------------------------------------
-static int pages_ensure_dev(PagesSet& s, int slot, size_t bytes) {
-    if (s.d_bytes[slot] >= bytes && s.d[slot]) return PSEG_OK;
-    if (s.d[slot]) (void)hipFree(s.d[slot]);
-    s.d[slot] = nullptr;
-    s.d_bytes[slot] = 0;
-    if (hipMalloc((void**)&s.d[slot], bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(PSEG_ENOMEM, "hipMalloc(page chain staging, %zu bytes) failed", bytes);
-    }
-    s.d_bytes[slot] = bytes;
-    return PSEG_OK;
-}
-template <class T>
-static int pages_ensure_host(T** p, size_t* cap, size_t bytes) {
-    if (*cap >= bytes && *p) return PSEG_OK;
-    if (*p) (void)hipHostFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    if (hipHostMalloc((void**)p, bytes, hipHostMallocDefault) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(PSEG_ENOMEM, "hipHostMalloc(page chain staging, %zu bytes) failed", bytes);
-    }
-    *cap = bytes;
-    return PSEG_OK;
-}
-static bool pages_is_pinned(const void* p) {
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return at.type == hipMemoryTypeHost;
-}
 static inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // The mixed planner: pages by canvas (stable: canvases by first appearance, list order within one), then plan_units over the canvases
@@ -358,12 +317,377 @@ extern "C" int pseg_chain_units(int n_pages, const int* H, const int* W, const i
     }
     return (int)ub.size();
 }
+// ---- the page-list entries: check -> plan -> reserve -> run ---------------------------------------------------------------
+// The plan of a call, host arithmetic alone.  Positions are those of the planner's order: ord maps one to the caller's page (the
+// identity unless mixed); unit u holds positions ub[u] .. ub[u] + ug[u].  tab says per position where the page, its maps and its
+// binarisation lie in the unit's staging set (a mixed call's kernels read it on the device); mx* are the blocks' largest extents.
+struct ChainUnit { bool slots; PngPages L; PngPagesMixed M; };      // page slots through the network; the encoder's layout (same-shape / mixed)
+struct ChainPlan {
+    bool mixed = false, two_maps = false, any_bin = false;
+    int n = 0, in_ch = 1;
+    std::vector<int> ord, ub, ug;
+    std::vector<ChainUnit> un;
+    std::vector<MixedPage> tab;
+    std::vector<size_t> lab2_off, scan_off, filt_off, wt_off;       // LAB2; a scan call: the scan in SCAN, its filtered plane in FILT, its weights in the call's table
+    size_t n_wt = 0, mx[PagesSet::NDEV] = {}, mx_in = 0, mx_tot = 0;
+};
 
-// The body of the page-list entries.  mixed = false: units are runs of same-shape pages in list order (pseg_chain_units).  mixed = true:
-// units are pages of one canvas (pseg_chain_units_mixed); `ord` maps a position of the planner's order to the caller's page.
-// scans != NULL (pseg_predict_chain_scans_png; mixed): imgs[i] is scan i's gray plane and binaries[i] stands for the ink map that the
-// front end makes on the device -- upload() brings the unit's scans, compute() starts with the front end (scan_front_enqueue), which
-// writes the pages and ink maps where upload() puts them otherwise; H, W, Ho, Wo are the pages' shapes as for the page entries.
+// The pass that ends the plan: every block of every page lies inside its mx[], the offsets that kernels and DMA rely on are aligned
+// (or dense: same-shape pages go up in one DMA, same-shape page slots write their maps one behind the other), the units tile the list
+// and the final maps are where chain_post_enqueue's walk will leave them.  O(n); a violation is a bug of the planner.
+static int chain_plan_check(const ChainPlan& p, const std::vector<ChainReq>& req, const pseg_scan* scans, const int* post_ops, int n_post) {
+    typedef PagesSet B;
+    std::vector<char> seen(p.n, 0);
+    int next = 0;
+    for (size_t u = 0; u < p.ub.size(); ++u) {
+        const int i0 = p.ub[u], g = p.ug[u];
+        const ChainUnit& q = p.un[u];
+        if (i0 != next || g < 1 || g > p.n - i0) return fail(PSEG_EHIP, "page chain plan: unit %zu does not continue the list at position %d", u, next);
+        next = i0 + g;
+        const size_t cpx = (size_t)round_up(p.tab[i0].H, 32) * round_up(p.tab[i0].W, 32);
+        bool unit_ok = (p.mixed ? q.M.bytes : q.L.bytes) <= p.mx[B::PNG] && (size_t)g * 4 * sizeof(unsigned long long) <= p.mx_tot &&
+                       (!scans || (size_t)g * SCAN_REC_WORDS * sizeof(unsigned) <= p.mx[B::REC]) &&
+                       (!(p.mixed && q.slots) || ((size_t)g * cpx * p.in_ch <= p.mx[B::PAD] && (size_t)g * cpx <= p.mx[B::CLAB]));
+        size_t in_b = 0, dense_img = 0, dense_lab = 0;
+        for (int i = i0; i < next; ++i) {
+            const int pi = p.ord[i];
+            if (pi < 0 || pi >= p.n || seen[pi]) return fail(PSEG_EHIP, "page chain plan: position %d names page %d twice or none", i, pi);
+            seen[pi] = 1;
+            const MixedPage& m = p.tab[i];
+            const size_t npx = (size_t)m.H * m.W, nl = (size_t)m.Hl * m.Wl, nla = up256(nl);
+            bool ok = m.img_off + npx * p.in_ch <= p.mx[B::IMG] && m.lab_off + npx <= p.mx[B::LAB];
+            ok = ok && (p.mixed ? m.img_off % 256 == 0 : m.img_off == dense_img) && (!p.mixed && q.slots ? m.lab_off == dense_lab : m.lab_off % 256 == 0);
+            if (p.two_maps) ok = ok && p.lab2_off[i] % 256 == 0 && p.lab2_off[i] + 2 * nla <= p.mx[B::LAB2];
+            if (req[pi].need_bin) ok = ok && m.bin_off % 256 == 0 && m.bin_off + nl <= p.mx[B::BIN];
+            const int where = chain_final_slot(req[pi].resize, post_ops, n_post);
+            ok = ok && (where == 0 || p.two_maps) && m.pred_sel == (where ? 1 : 0) &&
+                 m.pred_off == (where == 0 ? m.lab_off : p.lab2_off[i] + (where == 2 ? nla : 0));
+            if (scans) {
+                const size_t sb = (size_t)scans[pi].H0 * scans[pi].W0;
+                ok = ok && p.scan_off[i] % 256 == 0 && p.scan_off[i] + sb <= p.mx[B::SCAN] && p.filt_off[i] % 16 == 0 &&
+                     p.filt_off[i] + scan_front_work(scans[pi]) <= p.mx[B::FILT] && p.wt_off[i] + scan_front_weights(scans[pi], nullptr) <= p.n_wt;
+                in_b += sb;
+            } else in_b += npx * p.in_ch + (req[pi].need_bin ? nl : 0);
+            if (!ok) return fail(PSEG_EHIP, "page chain plan: page %d does not lie inside its staging blocks", pi);
+            dense_img += npx * p.in_ch;
+            dense_lab += npx;
+        }
+        if (!unit_ok || in_b > p.mx_in) return fail(PSEG_EHIP, "page chain plan: unit %zu (page %d ...) outgrows its staging", u, p.ord[i0]);
+    }
+    if (next != p.n) return fail(PSEG_EHIP, "page chain plan: the units end at position %d of %d", next, p.n);
+    return PSEG_OK;
+}
+
+// No HIP call.  mixed = false: units are runs of same-shape pages in list order (pseg_chain_units); mixed = true: pages of one canvas
+// (pseg_chain_units_mixed).  scans != NULL: a scan call (mixed), whose pages and ink maps the front end writes on the device.
+static int chain_pages_plan(int n, const int* H, const int* W, const int* Ho, const int* Wo, const std::vector<ChainReq>& req, const pseg_scan* scans,
+                            const int* post_ops, int n_post, int in_ch, int cap, bool page_slots, bool mixed, int level, int nout, ChainPlan* out) {
+    typedef PagesSet B;
+    ChainPlan& p = *out;
+    p.mixed = mixed;
+    p.n = n;
+    p.in_ch = in_ch;
+    for (int i = 0; i < n; ++i) { p.any_bin |= req[i].need_bin; p.two_maps |= req[i].resize; }
+    for (int i = 0; i < n_post; ++i) p.two_maps |= post_ops[i] == PSEG_POST_BBOX;
+    if (mixed) plan_units_mixed(n, H, W, cap, p.ord, p.ub, p.ug);
+    else {
+        p.ord.resize(n);
+        for (int i = 0; i < n; ++i) p.ord[i] = i;
+        plan_units(n, H, W, Ho, Wo, cap, p.ub, p.ug);
+    }
+    p.un.resize(p.ub.size());
+    p.tab.resize(n);
+    p.lab2_off.assign(n, 0);
+    for (auto* v : {&p.scan_off, &p.filt_off, &p.wt_off}) v->assign(scans ? n : 0, 0);
+    for (size_t u = 0; u < p.ub.size(); ++u) {
+        const int i0 = p.ub[u], g = p.ug[u], p0 = p.ord[i0];
+        ChainUnit& q = p.un[u];
+        // (same-shape page slots write the unit's maps one behind the other; mixed slots are canvases, cropped to aligned maps)
+        q.slots = page_slots && g > 1 && (mixed || ((size_t)H[p0] * W[p0]) % 4 == 0);
+        q.L = PngPages{0, 0, 0, 0, 0, 0, 0, 0};
+        q.M = PngPagesMixed{0, 0, 0};
+        size_t o_img = 0, o_lab = 0, o_bin = 0, o_lab2 = 0, lab_b = 0, in_b = 0, o_scan = 0, o_filt = 0;
+        for (int i = i0; i < i0 + g; ++i) {
+            const int pi = p.ord[i];
+            MixedPage& m = p.tab[i];
+            memset(&m, 0, sizeof m);
+            const size_t npx = (size_t)H[pi] * W[pi], nl = (size_t)req[pi].Hl * req[pi].Wl, nla = up256(nl);   // (the vote kernels want 4-byte aligned maps)
+            m.H = H[pi]; m.W = W[pi]; m.Hl = req[pi].Hl; m.Wl = req[pi].Wl;
+            m.img_off = o_img; m.lab_off = o_lab; m.bin_off = o_bin;
+            p.lab2_off[i] = o_lab2;
+            o_img += mixed ? up256(npx * in_ch) : npx * in_ch;
+            o_lab += !mixed && q.slots ? npx : up256(npx);
+            lab_b += up256(npx);
+            o_bin += nla;
+            o_lab2 += 2 * nla;
+            in_b += scans ? (size_t)scans[pi].H0 * scans[pi].W0 : npx * in_ch + (req[pi].need_bin ? nl : 0);
+            if (scans) {
+                p.scan_off[i] = o_scan;
+                p.filt_off[i] = o_filt;
+                p.wt_off[i] = p.n_wt;
+                o_scan += up256((size_t)scans[pi].H0 * scans[pi].W0);
+                o_filt += scan_front_work(scans[pi]);
+                p.n_wt += scan_front_weights(scans[pi], nullptr);
+            }
+            const int where = chain_final_slot(req[pi].resize, post_ops, n_post);      // the page's final map, ahead of time
+            m.pred_sel = where ? 1 : 0;
+            m.pred_off = where == 0 ? m.lab_off : p.lab2_off[i] + (where == 2 ? nla : 0);
+        }
+        if (nout > 0) {
+            if (mixed) PSEG_TRY(png_pages_layout_mixed(level, nout, g, &p.tab[i0], &q.M));
+            else PSEG_TRY(png_pages_layout(req[p0].Hl, req[p0].Wl, level, nout, g, &q.L));
+        }
+        const size_t cpx = mixed && q.slots ? (size_t)round_up(H[p0], 32) * round_up(W[p0], 32) : 0;
+        const size_t ext[B::NDEV] = {o_img, lab_b, p.two_maps ? o_lab2 : 0, p.any_bin ? o_bin : 0, mixed ? q.M.bytes : q.L.bytes, (size_t)g * cpx * in_ch,
+                                     (size_t)g * cpx, o_scan, o_filt, scans ? (size_t)g * SCAN_REC_WORDS * sizeof(unsigned) : 0};
+        for (int k = 0; k < B::NDEV; ++k) p.mx[k] = std::max(p.mx[k], ext[k]);
+        p.mx_in = std::max(p.mx_in, in_b);
+        p.mx_tot = std::max(p.mx_tot, (size_t)g * 4 * sizeof(unsigned long long));
+    }
+    return chain_plan_check(p, req, scans, post_ops, n_post);
+}
+
+// Both sets sized for the largest unit while they are idle (a call ends drained; the page-locked stream staging alone grows while the call runs,
+// see download), then the call-wide tables -- colour table, page table, weights: one upload each on the copy stream in front of every unit's up event.
+static int pages_reserve(ChainPagesState& ps, const ChainPlan& p, bool any_pageable, const uint8_t* lut, int n_lut, const pseg_scan* scans, hipStream_t s_in) {
+    for (PagesSet& s : ps.set) {
+        for (int k = 0; k < PagesSet::NDEV; ++k)
+            if (p.mx[k]) PSEG_TRY(s.d[k].ensure(p.mx[k], "page chain staging"));
+        if (any_pageable) PSEG_TRY(s.h_in.ensure(p.mx_in, "page chain staging"));
+        PSEG_TRY(s.h_tot.ensure(std::max<size_t>(p.mx_tot, 64), "page chain staging"));
+    }
+    if (lut) {
+        PSEG_TRY(ps.d_lut.ensure(768, "page chain colour table"));
+        PSEG_HIP(hipMemcpyAsync(ps.d_lut.p, lut, (size_t)n_lut * 3, hipMemcpyHostToDevice, s_in));
+    }
+    if (p.mixed) {
+        const size_t nb = (size_t)p.n * sizeof(MixedPage);
+        PSEG_TRY(ps.d_tab.ensure(nb, "page chain page table"));
+        PSEG_TRY(ps.h_tab.ensure(nb, "page chain page table"));
+        memcpy(ps.h_tab.p, p.tab.data(), nb);
+        PSEG_HIP(hipMemcpyAsync(ps.d_tab.p, ps.h_tab.p, nb, hipMemcpyHostToDevice, s_in));
+    }
+    if (scans && p.n_wt) {
+        PSEG_TRY(ps.d_wt.ensure(p.n_wt * 8, "scan chain weights"));
+        PSEG_TRY(ps.h_wt.ensure(p.n_wt * 8, "scan chain weights"));
+        for (int i = 0; i < p.n; ++i) scan_front_weights(scans[p.ord[i]], (double*)ps.h_wt.p + p.wt_off[i]);
+        PSEG_HIP(hipMemcpyAsync(ps.d_wt.p, ps.h_wt.p, p.n_wt * 8, hipMemcpyHostToDevice, s_in));
+    }
+    return PSEG_OK;
+}
+
+// The page chain's stages of run_pipeline: unit u in set u % 2.  imgs[i] is page i -- a scan call: scan i's gray plane, and binaries
+// stands for the ink map that the front end makes on the device.
+struct PagesRun {
+    typedef PagesSet B;
+    pseg_engine* h;
+    const ChainPlan& p;
+    ChainPagesState& ps;
+    const std::vector<ChainReq>& req;
+    const uint8_t* const* imgs; const uint8_t* const* binaries; const pseg_scan* scans;
+    const int* post_ops; int n_post; bool exact;
+    const uint8_t* lut; int n_lut, level, nout; const int* mask_id; bool want_lab;      // lut NULL: no masks
+    pseg_chain_sink sink; void* user;
+    hipStream_t s_in, st, s_out;
+    // where a unit's outputs lie in its page-locked slot: per page the requested streams (8-byte aligned), then the label map (and the
+    // sizes, copied out of the set's page-locked words: those are written again by the unit after next while this one is delivered)
+    std::vector<size_t> offs[2], tot[2];
+
+    static uint8_t* final_map(const PagesSet& s, const MixedPage& m) { return s.d[m.pred_sel ? B::LAB2 : B::LAB].p + m.pred_off; }
+    bool pinned(int pi) const { return host_is_pinned(imgs[pi]) && (scans || !req[pi].need_bin || host_is_pinned(binaries[pi])); }
+    bool unit_pinned(int u) const { bool all = true; for (int k = 0; k < p.ug[u]; ++k) all = all && pinned(p.ord[p.ub[u] + k]); return all; }
+    int reserve() {
+        bool any_pageable = false;
+        for (int i = 0; i < p.n && !any_pageable; ++i) any_pageable = !pinned(i);
+        return pages_reserve(ps, p, any_pageable, lut, n_lut, scans, s_in);
+    }
+    int upload_scans(int u, const PipeSet& ev) {      // a scan call's upload(u): the unit's scans into the set's SCAN block
+        PagesSet& s = ps.set[u & 1];
+        const int i0 = p.ub[u], g = p.ug[u];
+        const bool direct = unit_pinned(u);
+        if (!direct) PSEG_HIP(hipEventSynchronize(ev.up));     // the page-locked slot: last read by the uploads of unit u - 2
+        size_t hp = 0;
+        for (int i = i0; i < i0 + g; ++i) {
+            const pseg_scan& sc = scans[p.ord[i]];
+            const size_t nb = (size_t)sc.H0 * sc.W0;
+            const uint8_t* src = sc.gray;
+            if (!direct) { memcpy(s.h_in.p + hp, sc.gray, nb); src = s.h_in.p + hp; hp += nb; }
+            PSEG_HIP(hipMemcpyAsync(s.d[B::SCAN].p + p.scan_off[i], src, nb, hipMemcpyHostToDevice, s_in));
+        }
+        return PSEG_OK;
+    }
+    int upload(int u, const PipeSet& ev) {
+        if (scans) return upload_scans(u, ev);
+        PagesSet& s = ps.set[u & 1];
+        const int i0 = p.ub[u], i1 = i0 + p.ug[u];
+        const bool bin = req[p.ord[i0]].need_bin;               // (the same for every page of a call)
+        if (unit_pinned(u)) {
+            for (int i = i0; i < i1; ++i) {
+                const MixedPage& m = p.tab[i];
+                PSEG_HIP(hipMemcpyAsync(s.d[B::IMG].p + m.img_off, imgs[p.ord[i]], (size_t)m.H * m.W * p.in_ch, hipMemcpyHostToDevice, s_in));
+                if (bin) PSEG_HIP(hipMemcpyAsync(s.d[B::BIN].p + m.bin_off, binaries[p.ord[i]], (size_t)m.Hl * m.Wl, hipMemcpyHostToDevice, s_in));
+            }
+            return PSEG_OK;
+        }
+        PSEG_HIP(hipEventSynchronize(ev.up));                  // through the page-locked slot: last read by the uploads of unit u - 2
+        size_t hp = 0;                                         // the pages densely, the binarisations densely behind them
+        for (int pass = 0; pass < (bin ? 2 : 1); ++pass)
+            for (int i = i0; i < i1; ++i) {
+                const size_t nb = pass ? (size_t)p.tab[i].Hl * p.tab[i].Wl : (size_t)p.tab[i].H * p.tab[i].W * p.in_ch;
+                memcpy(s.h_in.p + hp, pass ? binaries[p.ord[i]] : imgs[p.ord[i]], nb);
+                hp += nb;
+            }
+        hp = 0;                                                // same-shape pages lie densely in IMG too: one DMA; a mixed unit's start at aligned offsets
+        for (int pass = 0; pass < (bin ? 2 : 1); ++pass)
+            for (int i = i0; i < i1; ++i) {
+                const MixedPage& m = p.tab[i];
+                const size_t nb = pass ? (size_t)m.Hl * m.Wl : (size_t)m.H * m.W * p.in_ch;
+                if (pass) PSEG_HIP(hipMemcpyAsync(s.d[B::BIN].p + m.bin_off, s.h_in.p + hp, nb, hipMemcpyHostToDevice, s_in));
+                else if (p.mixed) PSEG_HIP(hipMemcpyAsync(s.d[B::IMG].p + m.img_off, s.h_in.p + hp, nb, hipMemcpyHostToDevice, s_in));
+                else if (i + 1 == i1) PSEG_HIP(hipMemcpyAsync(s.d[B::IMG].p, s.h_in.p, hp + nb, hipMemcpyHostToDevice, s_in));
+                hp += nb;
+            }
+        return PSEG_OK;
+    }
+    int before_compute(int u) {
+        // a canvas change re-allocates / clears the activation tensors: the previous unit must have left them
+        const Engine& e = h->e;
+        const MixedPage& m = p.tab[p.ub[u]];
+        if (round_up(m.H, 32) != e.Hp || round_up(m.W, 32) != e.Wp || (p.un[u].slots && p.ug[u] > e.pages)) PSEG_HIP(hipStreamSynchronize(st));
+        return PSEG_OK;
+    }
+    // 0. a scan call: the front end per scan writes the page and the ink map of the final shape
+    int front_end(int u, PagesSet& s) {
+        const int i0 = p.ub[u], g = p.ug[u];
+        PSEG_HIP(hipMemsetAsync(s.d[B::REC].p, 0, (size_t)g * SCAN_REC_WORDS * sizeof(unsigned), st));
+        for (int i = i0; i < i0 + g; ++i) {
+            const int pi = p.ord[i];
+            const MixedPage& m = p.tab[i];
+            uint8_t* const ink = req[pi].need_bin ? s.d[B::BIN].p + m.bin_off : nullptr;
+            const bool hi = scans[pi].final_is_scan != 0;
+            PSEG_TRY(scan_front_enqueue(scans[pi], s.d[B::SCAN].p + p.scan_off[i], ps.d_wt.p ? (double*)ps.d_wt.p + p.wt_off[i] : nullptr,
+                                        s.d[B::FILT].p ? s.d[B::FILT].p + p.filt_off[i] : nullptr, (unsigned*)s.d[B::REC].p + (size_t)(i - i0) * SCAN_REC_WORDS,
+                                        s.d[B::IMG].p + m.img_off, hi ? nullptr : ink, hi ? ink : nullptr, st));
+        }
+        return PSEG_OK;
+    }
+    // 1. the network, in one of three forms
+    int network(int u, PagesSet& s) {
+        Engine& e = h->e;
+        const int i0 = p.ub[u], g = p.ug[u];
+        const MixedPage* d_tab = (const MixedPage*)ps.d_tab.p + i0;
+        if (p.un[u].slots && p.mixed) {
+            // pad every page into its canvas-sized slot, run the slots, crop every label map back to its page: three steps whatever g
+            const int Hc = round_up(p.tab[i0].H, 32), Wc = round_up(p.tab[i0].W, 32);
+            const size_t cpx = (size_t)Hc * Wc;
+            const unsigned bx = (unsigned)std::min<size_t>((cpx * e.in_ch / 4 + 255) / 256, 1024);
+            pages_pad_kernel<<<dim3(bx, g), 256, 0, st>>>(s.d[B::IMG].p, s.d[B::PAD].p, d_tab, Hc, Wc, e.in_ch);
+            PSEG_HIP(hipGetLastError());
+            PSEG_TRY(predict_device_pages(e, s.d[B::PAD].p, g, Hc, Wc, nullptr, s.d[B::CLAB].p, st));
+            pages_crop_kernel<<<dim3((unsigned)std::min<size_t>((cpx + 255) / 256, 1024), g), 256, 0, st>>>(s.d[B::CLAB].p, s.d[B::LAB].p, d_tab, Hc, Wc);
+            PSEG_HIP(hipGetLastError());
+        } else if (p.un[u].slots) PSEG_TRY(predict_device_pages(e, s.d[B::IMG].p, g, p.tab[i0].H, p.tab[i0].W, nullptr, s.d[B::LAB].p, st));
+        else
+            for (int i = i0; i < i0 + g; ++i) {                // (a mixed unit's pages share the canvas: no change between them)
+                const MixedPage& m = p.tab[i];
+                const uint8_t* im = s.d[B::IMG].p + m.img_off;
+                uint8_t* lab = s.d[B::LAB].p + m.lab_off;
+                if (exact) PSEG_TRY(pseg_predict_exact_labels_device(h, im, m.H, m.W, lab, nullptr, nullptr, st));
+                else PSEG_TRY(predict_device(e, im, m.H, m.W, nullptr, nullptr, nullptr, lab, st, nullptr));
+            }
+        return PSEG_OK;
+    }
+    // 2./3. per page, in chain_run's order: resize, then the post-processors (the vote's workspace is one per device)
+    int post(int u, PagesSet& s) {
+        for (int i = p.ub[u]; i < p.ub[u] + p.ug[u]; ++i) {
+            const MixedPage& m = p.tab[i];
+            uint8_t* const bufA = p.two_maps ? s.d[B::LAB2].p + p.lab2_off[i] : nullptr;
+            uint8_t* const bufB = p.two_maps ? bufA + up256((size_t)m.Hl * m.Wl) : nullptr;
+            PSEG_TRY(chain_post_enqueue(h->e, s.d[B::LAB].p + m.lab_off, bufA, bufB, s.d[B::BIN].p + m.bin_off, m.H, m.W, m.Hl, m.Wl, req[p.ord[i]].resize,
+                                        post_ops, n_post, st, nullptr));
+        }
+        return PSEG_OK;
+    }
+    // 4. the masks of all pages as PNG streams: one set of launches; the sizes go to page-locked memory
+    int encode(int u, PagesSet& s) {
+        const int i0 = p.ub[u], g = p.ug[u];
+        const MixedPage* t = &p.tab[i0];
+        if (p.mixed)
+            PSEG_TRY(png_pages_enqueue_mixed(p.un[u].M, t, (const MixedPage*)ps.d_tab.p + i0, g, s.d[B::PNG].p, s.d[B::PNG].cap, s.d[B::LAB].p, s.d[B::LAB2].p,
+                                             s.d[B::BIN].p, ps.d_lut.p, n_lut, level, nout, mask_id, st));
+        else
+            PSEG_TRY(png_pages_enqueue(p.un[u].L, s.d[B::PNG].p, final_map(s, t[0]), g > 1 ? (size_t)(t[1].pred_off - t[0].pred_off) : 0, s.d[B::BIN].p,
+                                       up256((size_t)t[0].Hl * t[0].Wl), ps.d_lut.p, n_lut, t[0].Hl, t[0].Wl, level, nout, mask_id, g, st));
+        PSEG_HIP(hipMemcpyAsync(s.h_tot.p, s.d[B::PNG].p, (size_t)g * 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        return PSEG_OK;
+    }
+    int compute(int u, const PipeSet&) {
+        PagesSet& s = ps.set[u & 1];
+        if (scans) PSEG_TRY(front_end(u, s));
+        PSEG_TRY(network(u, s));
+        PSEG_TRY(post(u, s));
+        return nout > 0 ? encode(u, s) : PSEG_OK;
+    }
+    int download(int u, const PipeSet& ev) {
+        PagesSet& s = ps.set[u & 1];
+        const int i0 = p.ub[u], g = p.ug[u];
+        const PngPages& L = p.un[u].L;
+        PSEG_HIP(hipEventSynchronize(ev.done));                // the sizes are here
+        const unsigned long long* h_tot = (const unsigned long long*)s.h_tot.p;
+        std::vector<size_t>& of = offs[u & 1];
+        of.assign((size_t)g * 5 + 1, 0);
+        std::vector<size_t>& tt = tot[u & 1];
+        tt.assign((size_t)g * 4, 0);
+        size_t pos = 0;
+        for (int k = 0; k < g; ++k) {
+            const size_t bound = p.mixed ? (size_t)p.tab[i0 + k].bound : L.bound;
+            for (int j = 0; j < 4; ++j) {
+                of[(size_t)k * 5 + j] = pos;
+                if (j >= nout) continue;
+                const unsigned long long t = h_tot[(size_t)k * 4 + j];
+                if (t < 80 || t > bound) return fail(PSEG_EHIP, "png: encoded size %llu outside (0, bound %zu] (page %d)", t, bound, p.ord[i0 + k]);
+                tt[(size_t)k * 4 + j] = (size_t)t;
+                pos += ((size_t)t + 7) & ~(size_t)7;
+            }
+            of[(size_t)k * 5 + 4] = pos;
+            if (want_lab) pos += ((size_t)p.tab[i0 + k].Hl * p.tab[i0 + k].Wl + 7) & ~(size_t)7;
+        }
+        of[(size_t)g * 5] = pos;
+        // the slot was handed to the sink by finish(u - 2): idle.  It grows to what units really hold, with a quarter of headroom.
+        if (s.h_out.cap < pos) PSEG_TRY(s.h_out.ensure(pos + pos / 4 + 4096, "page chain streams"));
+        for (int k = 0; k < g; ++k) {
+            const MixedPage& m = p.tab[i0 + k];
+            for (int j = 0; j < nout; ++j) {
+                const uint8_t* src = p.mixed ? s.d[B::PNG].p + m.ws_off + (size_t)j * m.per + m.slots_b + m.meta_b + m.offs_b
+                                             : s.d[B::PNG].p + L.head + (size_t)(g > 1 ? k : 0) * L.page + (size_t)j * L.per + L.slots_b + L.meta_b + L.offs_b;
+                PSEG_HIP(hipMemcpyAsync(s.h_out.p + of[(size_t)k * 5 + j], src, tt[(size_t)k * 4 + j], hipMemcpyDeviceToHost, s_out));
+            }
+            if (want_lab) PSEG_HIP(hipMemcpyAsync(s.h_out.p + of[(size_t)k * 5 + 4], final_map(s, m), (size_t)m.Hl * m.Wl, hipMemcpyDeviceToHost, s_out));
+        }
+        return PSEG_OK;
+    }
+    bool has_finish(int) const { return true; }
+    int finish(int u) {                        // chunk CRCs, then the sink: the planner's order, `which` ascending; on the calling thread
+        const PagesSet& s = ps.set[u & 1];
+        const std::vector<size_t>& of = offs[u & 1];
+        for (int k = 0; k < p.ug[u]; ++k) {
+            const int pi = p.ord[p.ub[u] + k];
+            const MixedPage& m = p.tab[p.ub[u] + k];
+            for (int j = 0; j < nout; ++j) {
+                uint8_t* out = s.h_out.p + of[(size_t)k * 5 + j];
+                const size_t t = tot[u & 1][(size_t)k * 4 + j];
+                PSEG_TRY(png_finish_host(out, t));
+                if (sink(user, pi, mask_id[j], out, t) != 0) return fail(PSEG_ECALLBACK, "the sink stopped the call at page %d, output %d", pi, mask_id[j]);
+            }
+            if (want_lab && sink(user, pi, 4, s.h_out.p + of[(size_t)k * 5 + 4], (size_t)m.Hl * m.Wl) != 0)
+                return fail(PSEG_ECALLBACK, "the sink stopped the call at page %d, output 4", pi);
+        }
+        return PSEG_OK;
+    }
+};
+
+// The body of the page-list entries (pages, mixed pages; scans != NULL: pseg_predict_chain_scans_png, where H, W, Ho, Wo are the
+// pages' shapes as for the page entries).
 static int chain_pages_run(pseg_engine* h, int n, const uint8_t* const* imgs, const int* H, const int* W, const int* Ho, const int* Wo,
                            const uint8_t* const* binaries, const int* post_ops, int n_post, unsigned flags, const uint8_t* lut, int n_lut, int level,
                            unsigned want, int unit_cap, pseg_chain_sink sink, void* user, const bool mixed, const pseg_scan* scans = nullptr) {
@@ -378,36 +702,22 @@ static int chain_pages_run(pseg_engine* h, int n, const uint8_t* const* imgs, co
     int mask_id[4] = {0, 0, 0, 0}, nout = 0;
     for (int k = 0; k < 4; ++k)
         if (want & (1u << k)) mask_id[nout++] = k;
-    const bool want_lab = (want & 16u) != 0, want_png = nout > 0;
+    const bool want_png = nout > 0;
     // every page is checked before any device work starts
     std::vector<ChainReq> req(n);
-    bool any_bin = false, two_maps = false;
     for (int i = 0; i < n; ++i) {
         PSEG_TRY(chain_check(e, i, imgs[i], H[i], W[i], Ho ? Ho[i] : 0, Wo ? Wo[i] : 0, binaries ? binaries[i] : nullptr, post_ops, n_post, flags,
                              want_png, want_png, lut, n_lut, level, &req[i]));
         if (want_png && pseg_png_bound_lv(req[i].Hl, req[i].Wl, 3, 0, level) == 0) return fail(PSEG_EINVAL, "page %d: png: a row of %d pixels is too long", i, req[i].Wl);
         if (mixed && (H[i] > 0x7FFFFFE0 || W[i] > 0x7FFFFFE0)) return fail(PSEG_EINVAL, "page %d: bad shape %d x %d", i, H[i], W[i]);
-        any_bin |= req[i].need_bin;
-        two_maps |= req[i].resize;
     }
     if (n == 0) return PSEG_OK;
-    for (int i = 0; i < n_post; ++i) two_maps |= post_ops[i] == PSEG_POST_BBOX;
     PSEG_HIP(hipSetDevice(e.device));
-    if (!e.chain) {
-        auto* nc = new ChainState();
-        e.chain = nc;
-        PSEG_HIP(hipStreamCreateWithFlags(&nc->s_aux, hipStreamNonBlocking));
-        PSEG_HIP(hipEventCreateWithFlags(&nc->ev_aux, hipEventDisableTiming));
-    }
+    PSEG_TRY(chain_state(e));
     ChainState& c = *(ChainState*)e.chain;
     if (!c.pages) c.pages = new ChainPagesState();
-    ChainPagesState& ps = *c.pages;
-    for (PagesSet& s : ps.set) {
-        if (!s.up) PSEG_HIP(hipEventCreateWithFlags(&s.up, hipEventDisableTiming));
-        if (!s.done) PSEG_HIP(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
-        if (!s.down) PSEG_HIP(hipEventCreateWithFlags(&s.down, hipEventDisableTiming));
-    }
-    hipStream_t s_in = nullptr, s_out = nullptr, st = e.stream;
+    for (PipeSet& s : c.pages->ev) PSEG_TRY(s.create());
+    hipStream_t s_in = nullptr, s_out = nullptr;
     PSEG_TRY(batch_copy_streams(e, &s_in, &s_out));
     // units: pseg_predict_batch's rule over (H, W, final H, final W), or over the canvas.  A bf16 engine's unit goes through the network
     // as page slots (run_bf16_pages) unless the label-exact mode is asked for; any unit's masks are encoded in one set of launches.
@@ -424,346 +734,12 @@ static int chain_pages_run(pseg_engine* h, int n, const uint8_t* const* imgs, co
             cap = fit_unit_slots(e, hm, wm, cap);
         }
     } else if (!page_slots) cap = std::min(8, std::max(1, n / 4));       // (the encoder's launches still take a unit's pages together)
-    std::vector<int> ord, ub, ug;
-    if (mixed) plan_units_mixed(n, H, W, cap, ord, ub, ug);
-    else {
-        ord.resize(n);
-        for (int i = 0; i < n; ++i) ord[i] = i;
-        plan_units(n, H, W, Ho, Wo, cap, ub, ug);
-    }
-    const int nu = (int)ub.size();
-    // per position of the planner's order: where the page, its maps and its binarisation lie in the unit's staging set (tab; a mixed
-    // call's kernels read it on the device); per unit: the encoder's layout
-    struct Unit { bool slots; PngPages L; PngPagesMixed M; };
-    std::vector<Unit> un(nu);
-    std::vector<MixedPage> tab(n);
-    std::vector<size_t> lab2_off(n, 0);
-    // a scan call, per position: where the scan and its filtered plane lie in the set's SCAN / FILT blocks, its weights in the call's table
-    std::vector<size_t> scan_off(scans ? n : 0, 0), filt_off(scans ? n : 0, 0), wt_off(scans ? n : 0, 0);
-    size_t n_wt = 0;
-    size_t mx[PagesSet::NDEV] = {}, mx_in = 0, mx_tot = 0;
-    for (int u = 0; u < nu; ++u) {
-        const int i0 = ub[u], g = ug[u], p0 = ord[i0];
-        Unit& q = un[u];
-        // (same-shape page slots write the unit's maps one behind the other; mixed slots are canvases, cropped to aligned maps)
-        q.slots = page_slots && g > 1 && (mixed || ((size_t)H[p0] * W[p0]) % 4 == 0);
-        q.L = PngPages{0, 0, 0, 0, 0, 0, 0, 0};
-        q.M = PngPagesMixed{0, 0, 0};
-        size_t o_img = 0, o_lab = 0, o_bin = 0, o_lab2 = 0, lab_b = 0, in_b = 0, o_scan = 0, o_filt = 0;
-        for (int k = 0; k < g; ++k) {
-            const int pi = ord[i0 + k];
-            MixedPage& m = tab[i0 + k];
-            memset(&m, 0, sizeof m);
-            const size_t npx = (size_t)H[pi] * W[pi], nl = (size_t)req[pi].Hl * req[pi].Wl, nla = up256(nl);   // (the vote kernels want 4-byte aligned maps)
-            m.H = H[pi]; m.W = W[pi]; m.Hl = req[pi].Hl; m.Wl = req[pi].Wl;
-            m.img_off = o_img; m.lab_off = o_lab; m.bin_off = o_bin;
-            lab2_off[i0 + k] = o_lab2;
-            o_img += mixed ? up256(npx * e.in_ch) : npx * e.in_ch;
-            o_lab += !mixed && q.slots ? npx : up256(npx);
-            lab_b += up256(npx);
-            o_bin += nla;
-            o_lab2 += 2 * nla;
-            in_b += scans ? (size_t)scans[pi].H0 * scans[pi].W0 : npx * e.in_ch + (req[pi].need_bin ? nl : 0);
-            if (scans) {
-                scan_off[i0 + k] = o_scan;
-                filt_off[i0 + k] = o_filt;
-                wt_off[i0 + k] = n_wt;
-                o_scan += up256((size_t)scans[pi].H0 * scans[pi].W0);
-                o_filt += scan_front_work(scans[pi]);
-                n_wt += scan_front_weights(scans[pi], nullptr);
-            }
-            // where the page's final map will lie: compute()'s walk through resize and post-processors, ahead of time
-            int where = req[pi].resize ? 1 : 0;                        // 0: LAB, 1: bufA, 2: bufB
-            for (int i = 0; i < n_post; ++i)
-                if (post_ops[i] == PSEG_POST_BBOX) where = where == 1 ? 2 : 1;
-            m.pred_sel = where ? 1 : 0;
-            m.pred_off = where == 0 ? m.lab_off : lab2_off[i0 + k] + (where == 2 ? nla : 0);
-        }
-        if (want_png) {
-            if (mixed) PSEG_TRY(png_pages_layout_mixed(level, nout, g, &tab[i0], &q.M));
-            else PSEG_TRY(png_pages_layout(req[p0].Hl, req[p0].Wl, level, nout, g, &q.L));
-        }
-        mx[PagesSet::IMG] = std::max(mx[PagesSet::IMG], o_img);
-        mx[PagesSet::LAB] = std::max(mx[PagesSet::LAB], lab_b);
-        if (two_maps) mx[PagesSet::LAB2] = std::max(mx[PagesSet::LAB2], o_lab2);
-        if (any_bin) mx[PagesSet::BIN] = std::max(mx[PagesSet::BIN], o_bin);
-        mx[PagesSet::PNG] = std::max(mx[PagesSet::PNG], mixed ? q.M.bytes : q.L.bytes);
-        if (scans) {
-            mx[PagesSet::SCAN] = std::max(mx[PagesSet::SCAN], o_scan);
-            mx[PagesSet::FILT] = std::max(mx[PagesSet::FILT], o_filt);
-            mx[PagesSet::REC] = std::max(mx[PagesSet::REC], (size_t)g * SCAN_REC_WORDS * sizeof(unsigned));
-        }
-        if (mixed && q.slots) {
-            const size_t cpx = (size_t)round_up(H[p0], 32) * round_up(W[p0], 32);
-            mx[PagesSet::PAD] = std::max(mx[PagesSet::PAD], (size_t)g * cpx * e.in_ch);
-            mx[PagesSet::CLAB] = std::max(mx[PagesSet::CLAB], (size_t)g * cpx);
-        }
-        mx_in = std::max(mx_in, in_b);
-        mx_tot = std::max(mx_tot, (size_t)g * 4 * sizeof(unsigned long long));
-    }
-    // every way out -- also an error return in the middle and a sink that says stop -- ends with the three streams drained
-    struct Drain { hipStream_t a, b, c; ~Drain() { (void)hipStreamSynchronize(a); (void)hipStreamSynchronize(b); (void)hipStreamSynchronize(c); } } drain{s_in, st, s_out};
-    // a reallocation must not race with work that uses the block: every call ends drained, so the sets are idle here, and they are
-    // sized for the largest unit up front.  The page-locked stream staging alone grows while the call runs (see download).
-    bool any_pageable = false;
-    for (int i = 0; i < n && !any_pageable; ++i)
-        any_pageable = !pages_is_pinned(imgs[i]) || (!scans && req[i].need_bin && !pages_is_pinned(binaries[i]));
-    for (PagesSet& s : ps.set) {
-        for (int k = 0; k < PagesSet::NDEV; ++k)
-            if (mx[k]) PSEG_TRY(pages_ensure_dev(s, k, mx[k]));
-        if (any_pageable) PSEG_TRY(pages_ensure_host(&s.h_in, &s.h_in_bytes, mx_in));
-        PSEG_TRY(pages_ensure_host(&s.h_tot, &s.h_tot_bytes, std::max<size_t>(mx_tot, 64)));
-    }
-    if (want_png) {
-        if (!ps.d_lut) PSEG_HIP(hipMalloc((void**)&ps.d_lut, 768));
-        PSEG_HIP(hipMemcpyAsync(ps.d_lut, lut, (size_t)n_lut * 3, hipMemcpyHostToDevice, s_in));      // (ordered in front of every unit's up event)
-    }
-    if (mixed) {
-        // the whole call's page table goes up once, on the copy stream, in front of every unit's up event: no unit waits for it
-        if (ps.tab_entries < (size_t)n) {
-            if (ps.d_tab) (void)hipFree(ps.d_tab);
-            if (ps.h_tab) (void)hipHostFree(ps.h_tab);
-            ps.d_tab = ps.h_tab = nullptr;
-            ps.tab_entries = 0;
-            if (hipMalloc((void**)&ps.d_tab, (size_t)n * sizeof(MixedPage)) != hipSuccess || hipHostMalloc((void**)&ps.h_tab, (size_t)n * sizeof(MixedPage), hipHostMallocDefault) != hipSuccess) {
-                (void)hipGetLastError();
-                return fail(PSEG_ENOMEM, "page chain: no memory for the table of %d pages", n);
-            }
-            ps.tab_entries = (size_t)n;
-        }
-        memcpy(ps.h_tab, tab.data(), (size_t)n * sizeof(MixedPage));
-        PSEG_HIP(hipMemcpyAsync(ps.d_tab, ps.h_tab, (size_t)n * sizeof(MixedPage), hipMemcpyHostToDevice, s_in));
-    }
-    if (scans && n_wt) {
-        // the weights of the whole call, in the planner's order: one page-locked table, one upload in front of every unit's up event
-        if (ps.wt_entries < n_wt) {
-            if (ps.d_wt) (void)hipFree(ps.d_wt);
-            if (ps.h_wt) (void)hipHostFree(ps.h_wt);
-            ps.d_wt = ps.h_wt = nullptr;
-            ps.wt_entries = 0;
-            if (hipMalloc((void**)&ps.d_wt, n_wt * 8) != hipSuccess || hipHostMalloc((void**)&ps.h_wt, n_wt * 8, hipHostMallocDefault) != hipSuccess) {
-                (void)hipGetLastError();
-                return fail(PSEG_ENOMEM, "scan chain: no memory for the table of %zu weights", n_wt);
-            }
-            ps.wt_entries = n_wt;
-        }
-        for (int i = 0; i < n; ++i) scan_front_weights(scans[ord[i]], ps.h_wt + wt_off[i]);
-        PSEG_HIP(hipMemcpyAsync(ps.d_wt, ps.h_wt, n_wt * 8, hipMemcpyHostToDevice, s_in));
-    }
-    auto upload_scans = [&](int u) -> int {    // a scan call's upload(u): the unit's scans into the set's SCAN block
-        PagesSet& s = ps.set[u & 1];
-        const int i0 = ub[u], g = ug[u];
-        PSEG_HIP(hipStreamWaitEvent(s_in, s.done, 0));         // the set's scans have been read (unit u - 2)
-        bool pinned = true;
-        for (int k = 0; k < g; ++k) pinned = pinned && pages_is_pinned(imgs[ord[i0 + k]]);
-        if (!pinned) PSEG_HIP(hipEventSynchronize(s.up));      // the page-locked slot: last read by the uploads of unit u - 2
-        size_t hp = 0;
-        for (int k = 0; k < g; ++k) {
-            const pseg_scan& sc = scans[ord[i0 + k]];
-            const size_t nb = (size_t)sc.H0 * sc.W0;
-            const uint8_t* src = sc.gray;
-            if (!pinned) { memcpy(s.h_in + hp, sc.gray, nb); src = s.h_in + hp; hp += nb; }
-            PSEG_HIP(hipMemcpyAsync(s.d[PagesSet::SCAN] + scan_off[i0 + k], src, nb, hipMemcpyHostToDevice, s_in));
-        }
-        PSEG_HIP(hipEventRecord(s.up, s_in));
-        return PSEG_OK;
-    };
-    auto upload = [&](int u) -> int {          // unit u -> set u % 2
-        if (scans) return upload_scans(u);
-        PagesSet& s = ps.set[u & 1];
-        const int i0 = ub[u], g = ug[u];
-        const bool bin = req[ord[i0]].need_bin;                 // (the same for every page of a call)
-        PSEG_HIP(hipStreamWaitEvent(s_in, s.done, 0));         // the set's pages and binarisations have been read (unit u - 2)
-        bool pinned = true;
-        for (int k = 0; k < g; ++k) pinned = pinned && pages_is_pinned(imgs[ord[i0 + k]]) && (!bin || pages_is_pinned(binaries[ord[i0 + k]]));
-        if (pinned) {
-            for (int k = 0; k < g; ++k) {
-                const MixedPage& m = tab[i0 + k];
-                const int pi = ord[i0 + k];
-                PSEG_HIP(hipMemcpyAsync(s.d[PagesSet::IMG] + m.img_off, imgs[pi], (size_t)m.H * m.W * e.in_ch, hipMemcpyHostToDevice, s_in));
-                if (bin) PSEG_HIP(hipMemcpyAsync(s.d[PagesSet::BIN] + m.bin_off, binaries[pi], (size_t)m.Hl * m.Wl, hipMemcpyHostToDevice, s_in));
-            }
-        } else {                               // through the page-locked slot: last read by the uploads of unit u - 2
-            PSEG_HIP(hipEventSynchronize(s.up));
-            size_t hp = 0;                     // the pages densely, the binarisations densely behind them
-            for (int k = 0; k < g; ++k) {
-                const size_t pb = (size_t)tab[i0 + k].H * tab[i0 + k].W * e.in_ch;
-                memcpy(s.h_in + hp, imgs[ord[i0 + k]], pb);
-                hp += pb;
-            }
-            const size_t all_pages = hp;
-            for (int k = 0; k < g && bin; ++k) {
-                const size_t nl = (size_t)tab[i0 + k].Hl * tab[i0 + k].Wl;
-                memcpy(s.h_in + hp, binaries[ord[i0 + k]], nl);
-                hp += nl;
-            }
-            if (!mixed) PSEG_HIP(hipMemcpyAsync(s.d[PagesSet::IMG], s.h_in, all_pages, hipMemcpyHostToDevice, s_in));
-            hp = 0;
-            for (int k = 0; k < g && mixed; ++k) {             // (a mixed unit's pages start at aligned offsets)
-                const size_t pb = (size_t)tab[i0 + k].H * tab[i0 + k].W * e.in_ch;
-                PSEG_HIP(hipMemcpyAsync(s.d[PagesSet::IMG] + tab[i0 + k].img_off, s.h_in + hp, pb, hipMemcpyHostToDevice, s_in));
-                hp += pb;
-            }
-            hp = all_pages;
-            for (int k = 0; k < g && bin; ++k) {
-                const size_t nl = (size_t)tab[i0 + k].Hl * tab[i0 + k].Wl;
-                PSEG_HIP(hipMemcpyAsync(s.d[PagesSet::BIN] + tab[i0 + k].bin_off, s.h_in + hp, nl, hipMemcpyHostToDevice, s_in));
-                hp += nl;
-            }
-        }
-        PSEG_HIP(hipEventRecord(s.up, s_in));
-        return PSEG_OK;
-    };
-    std::vector<uint8_t*> fin(n, nullptr);     // per position: the page's final label map
-    auto compute = [&](int u) -> int {
-        PagesSet& s = ps.set[u & 1];
-        const Unit& q = un[u];
-        const int i0 = ub[u], g = ug[u], Hc = round_up(H[ord[i0]], 32), Wc = round_up(W[ord[i0]], 32);
-        // a canvas change re-allocates / clears the activation tensors: the previous unit must have left them
-        if (Hc != e.Hp || Wc != e.Wp || (q.slots && g > e.pages)) PSEG_HIP(hipStreamSynchronize(st));
-        PSEG_HIP(hipStreamWaitEvent(st, s.up, 0));
-        PSEG_HIP(hipStreamWaitEvent(st, s.down, 0));           // the streams and maps of unit u - 2 have left the set
-        // 0. a scan call: the front end per scan writes the page and the ink map of the final shape
-        if (scans) {
-            PSEG_HIP(hipMemsetAsync(s.d[PagesSet::REC], 0, (size_t)g * SCAN_REC_WORDS * sizeof(unsigned), st));
-            for (int k = 0; k < g; ++k) {
-                const int pi = ord[i0 + k];
-                const MixedPage& m = tab[i0 + k];
-                uint8_t* const ink = req[pi].need_bin ? s.d[PagesSet::BIN] + m.bin_off : nullptr;
-                const bool hi = scans[pi].final_is_scan != 0;
-                PSEG_TRY(scan_front_enqueue(scans[pi], s.d[PagesSet::SCAN] + scan_off[i0 + k], ps.d_wt ? ps.d_wt + wt_off[i0 + k] : nullptr,
-                                            s.d[PagesSet::FILT] ? s.d[PagesSet::FILT] + filt_off[i0 + k] : nullptr,
-                                            (unsigned*)s.d[PagesSet::REC] + (size_t)k * SCAN_REC_WORDS, s.d[PagesSet::IMG] + m.img_off,
-                                            hi ? nullptr : ink, hi ? ink : nullptr, st));
-            }
-        }
-        // 1. the network
-        if (q.slots && mixed) {
-            // pad every page into its canvas-sized slot, run the slots, crop every label map back to its page: three steps whatever g
-            const size_t cpx = (size_t)Hc * Wc;
-            if ((size_t)g * cpx * e.in_ch > s.d_bytes[PagesSet::PAD] || (size_t)g * cpx > s.d_bytes[PagesSet::CLAB])
-                return fail(PSEG_EHIP, "page chain: the padded slots of unit %d outgrow their staging", u);
-            const unsigned bx = (unsigned)std::min<size_t>((cpx * e.in_ch / 4 + 255) / 256, 1024);
-            pages_pad_kernel<<<dim3(bx, g), 256, 0, st>>>(s.d[PagesSet::IMG], s.d[PagesSet::PAD], ps.d_tab + i0, Hc, Wc, e.in_ch);
-            PSEG_HIP(hipGetLastError());
-            PSEG_TRY(predict_device_pages(e, s.d[PagesSet::PAD], g, Hc, Wc, nullptr, s.d[PagesSet::CLAB], st));
-            pages_crop_kernel<<<dim3((unsigned)std::min<size_t>((cpx + 255) / 256, 1024), g), 256, 0, st>>>(s.d[PagesSet::CLAB], s.d[PagesSet::LAB], ps.d_tab + i0, Hc, Wc);
-            PSEG_HIP(hipGetLastError());
-        } else if (q.slots) PSEG_TRY(predict_device_pages(e, s.d[PagesSet::IMG], g, H[ord[i0]], W[ord[i0]], nullptr, s.d[PagesSet::LAB], st));
-        else
-            for (int k = 0; k < g; ++k) {                      // (a mixed unit's pages share the canvas: no change between them)
-                const MixedPage& m = tab[i0 + k];
-                const uint8_t* im = s.d[PagesSet::IMG] + m.img_off;
-                uint8_t* lab = s.d[PagesSet::LAB] + m.lab_off;
-                if (exact) PSEG_TRY(pseg_predict_exact_labels_device(h, im, m.H, m.W, lab, nullptr, nullptr, st));
-                else PSEG_TRY(predict_device(e, im, m.H, m.W, nullptr, nullptr, nullptr, lab, st, nullptr));
-            }
-        // 2./3. per page, in chain_run's order: resize, then the post-processors (the vote's workspace is one per device)
-        for (int k = 0; k < g; ++k) {
-            const MixedPage& m = tab[i0 + k];
-            const size_t nla = up256((size_t)m.Hl * m.Wl);
-            uint8_t* cur = s.d[PagesSet::LAB] + m.lab_off;
-            uint8_t* const bufA = two_maps ? s.d[PagesSet::LAB2] + lab2_off[i0 + k] : nullptr;
-            uint8_t* const bufB = two_maps ? bufA + nla : nullptr;
-            if (req[ord[i0 + k]].resize) {
-                PSEG_TRY(pseg_resize_nearest_device(e.device, cur, m.H, m.W, 1, bufA, m.Hl, m.Wl, st));
-                cur = bufA;
-            }
-            for (int i = 0; i < n_post; ++i) {
-                if (post_ops[i] == PSEG_POST_CC_VOTE) {
-                    PSEG_TRY(pseg_cc_vote_device_u8(e.device, cur, s.d[PagesSet::BIN] + m.bin_off, m.Hl, m.Wl, e.n_classes, st));
-                } else {
-                    uint8_t* const dst = cur == bufA ? bufB : bufA;
-                    PSEG_TRY(pseg_bbox_fill_device_u8(e.device, cur, dst, m.Hl, m.Wl, e.n_classes, st));
-                    cur = dst;
-                }
-            }
-            if (cur != s.d[m.pred_sel ? PagesSet::LAB2 : PagesSet::LAB] + m.pred_off) return fail(PSEG_EHIP, "page chain: the final map of page %d is not where the table says", ord[i0 + k]);
-            fin[i0 + k] = cur;
-        }
-        // 4. the masks of all pages as PNG streams: one set of launches; the sizes go to page-locked memory
-        if (want_png) {
-            if (mixed)
-                PSEG_TRY(png_pages_enqueue_mixed(q.M, &tab[i0], ps.d_tab + i0, g, s.d[PagesSet::PNG], s.d_bytes[PagesSet::PNG], s.d[PagesSet::LAB],
-                                                 s.d[PagesSet::LAB2], s.d[PagesSet::BIN], ps.d_lut, n_lut, level, nout, mask_id, st));
-            else
-                PSEG_TRY(png_pages_enqueue(q.L, s.d[PagesSet::PNG], fin[i0], g > 1 ? (size_t)(tab[i0 + 1].pred_off - tab[i0].pred_off) : 0, s.d[PagesSet::BIN],
-                                           up256((size_t)tab[i0].Hl * tab[i0].Wl), ps.d_lut, n_lut, tab[i0].Hl, tab[i0].Wl, level, nout, mask_id, g, st));
-            PSEG_HIP(hipMemcpyAsync(s.h_tot, s.d[PagesSet::PNG], (size_t)g * 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-        }
-        PSEG_HIP(hipEventRecord(s.done, st));
-        return PSEG_OK;
-    };
-    // where a unit's outputs lie in its page-locked slot: per page the requested streams (8-byte aligned), then the label map
-    // (and the sizes, copied out of the set's page-locked words: those are written again by the unit after next while this one is
-    // still being delivered)
-    std::vector<std::vector<size_t>> offs(2), tot(2);
-    auto download = [&](int u) -> int {
-        PagesSet& s = ps.set[u & 1];
-        const Unit& q = un[u];
-        const int i0 = ub[u], g = ug[u];
-        PSEG_HIP(hipEventSynchronize(s.done));                 // the sizes are here
-        std::vector<size_t>& of = offs[u & 1];
-        of.assign((size_t)g * 5 + 1, 0);
-        std::vector<size_t>& tt = tot[u & 1];
-        tt.assign((size_t)g * 4, 0);
-        size_t pos = 0;
-        for (int k = 0; k < g; ++k) {
-            const size_t bound = mixed ? (size_t)tab[i0 + k].bound : q.L.bound;
-            for (int j = 0; j < 4; ++j) {
-                of[(size_t)k * 5 + j] = pos;
-                if (j >= nout) continue;
-                const unsigned long long t = s.h_tot[(size_t)k * 4 + j];
-                if (t < 80 || t > bound) return fail(PSEG_EHIP, "png: encoded size %llu outside (0, bound %zu] (page %d)", t, bound, ord[i0 + k]);
-                tt[(size_t)k * 4 + j] = (size_t)t;
-                pos += ((size_t)t + 7) & ~(size_t)7;
-            }
-            of[(size_t)k * 5 + 4] = pos;
-            if (want_lab) pos += ((size_t)tab[i0 + k].Hl * tab[i0 + k].Wl + 7) & ~(size_t)7;
-        }
-        of[(size_t)g * 5] = pos;
-        // the slot was handed to the sink by deliver(u - 2): idle.  It grows to what units really hold, with a quarter of headroom.
-        if (s.h_out_bytes < pos) PSEG_TRY(pages_ensure_host(&s.h_out, &s.h_out_bytes, pos + pos / 4 + 4096));
-        for (int k = 0; k < g; ++k) {
-            const MixedPage& m = tab[i0 + k];
-            for (int j = 0; j < nout; ++j) {
-                const uint8_t* src = mixed ? s.d[PagesSet::PNG] + m.ws_off + (size_t)j * m.per + m.slots_b + m.meta_b + m.offs_b
-                                           : s.d[PagesSet::PNG] + q.L.head + (size_t)(g > 1 ? k : 0) * q.L.page + (size_t)j * q.L.per + q.L.slots_b + q.L.meta_b + q.L.offs_b;
-                PSEG_HIP(hipMemcpyAsync(s.h_out + of[(size_t)k * 5 + j], src, tt[(size_t)k * 4 + j], hipMemcpyDeviceToHost, s_out));
-            }
-            if (want_lab) PSEG_HIP(hipMemcpyAsync(s.h_out + of[(size_t)k * 5 + 4], fin[i0 + k], (size_t)m.Hl * m.Wl, hipMemcpyDeviceToHost, s_out));
-        }
-        PSEG_HIP(hipEventRecord(s.down, s_out));
-        return PSEG_OK;
-    };
-    auto deliver = [&](int u) -> int {         // chunk CRCs, then the sink: the planner's order, `which` ascending; on the calling thread
-        PagesSet& s = ps.set[u & 1];
-        const std::vector<size_t>& of = offs[u & 1];
-        PSEG_HIP(hipEventSynchronize(s.down));
-        for (int k = 0; k < ug[u]; ++k) {
-            const int pi = ord[ub[u] + k];
-            for (int j = 0; j < nout; ++j) {
-                uint8_t* p = s.h_out + of[(size_t)k * 5 + j];
-                const size_t t = tot[u & 1][(size_t)k * 4 + j];
-                PSEG_TRY(png_finish_host(p, t));
-                if (sink(user, pi, mask_id[j], p, t) != 0) return fail(PSEG_ECALLBACK, "the sink stopped the call at page %d, output %d", pi, mask_id[j]);
-            }
-            if (want_lab && sink(user, pi, 4, s.h_out + of[(size_t)k * 5 + 4], (size_t)tab[ub[u] + k].Hl * tab[ub[u] + k].Wl) != 0)
-                return fail(PSEG_ECALLBACK, "the sink stopped the call at page %d, output 4", pi);
-        }
-        return PSEG_OK;
-    };
-    // the host enqueues unit u + 1 before it waits for unit u's sizes; while the device works it finishes unit u - 1
-    PSEG_TRY(upload(0));
-    PSEG_TRY(compute(0));
-    for (int u = 0; u < nu; ++u) {
-        if (u + 1 < nu) { PSEG_TRY(upload(u + 1)); PSEG_TRY(compute(u + 1)); }
-        PSEG_TRY(download(u));
-        if (u > 0) PSEG_TRY(deliver(u - 1));
-    }
-    PSEG_TRY(deliver(nu - 1));
-    PSEG_HIP(hipStreamSynchronize(s_out));
-    return engine_status(e, st);
+    ChainPlan plan;
+    PSEG_TRY(chain_pages_plan(n, H, W, Ho, Wo, req, scans, post_ops, n_post, e.in_ch, cap, page_slots, mixed, level, nout, &plan));
+    PagesRun run{h, plan, *c.pages, req, imgs, binaries, scans, post_ops, n_post, exact, want_png ? lut : nullptr, n_lut, level, nout, mask_id,
+                 (want & 16u) != 0, sink, user, s_in, e.stream, s_out, {}, {}};
+    PSEG_TRY(run_pipeline(run, (int)plan.ub.size(), c.pages->ev, s_in, e.stream, s_out));
+    return engine_status(e, e.stream);
 }
 
 extern "C" int pseg_predict_chain_pages_png(pseg_engine* h, int n, const uint8_t* const* imgs, const int* H, const int* W, const int* Ho,

@@ -34,6 +34,90 @@ int fail(int code, const char* fmt, ...);
         if (_rc != PSEG_OK) return _rc;                                                        \
     } while (0)
 
+// ---- host-side plumbing shared by pseg_predict_batch and the page chain ---------------------
+// A grow-only buffer of device (HOST = false) or page-locked host memory.  ensure() keeps a block that is large enough, else frees it and
+// allocates `bytes` (the caller knows that nothing on the device still uses it); a failure is PSEG_ENOMEM with the buffer's name and size.
+template <bool HOST>
+struct GrowBuf {
+    uint8_t* p = nullptr;
+    size_t cap = 0;
+    template <class T> T* as() const { return (T*)p; }
+    int ensure(size_t bytes, const char* what) {
+        if (cap >= bytes && p) return PSEG_OK;
+        release();
+        if ((HOST ? hipHostMalloc((void**)&p, bytes, hipHostMallocDefault) : hipMalloc((void**)&p, bytes)) != hipSuccess) {
+            (void)hipGetLastError();
+            p = nullptr;
+            return fail(PSEG_ENOMEM, "%s(%s, %zu bytes) failed", HOST ? "hipHostMalloc" : "hipMalloc", what, bytes);
+        }
+        cap = bytes;
+        return PSEG_OK;
+    }
+    void release() { if (p) (void)(HOST ? hipHostFree(p) : hipFree(p)); p = nullptr; cap = 0; }
+};
+typedef GrowBuf<false> GrowDev;
+typedef GrowBuf<true> GrowPin;
+// true when `p` is page-locked host memory the runtime knows (hipHostMalloc / hipHostRegister): DMA goes straight to it
+inline bool host_is_pinned(const void* p) {
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return false; }
+    return at.type == hipMemoryTypeHost;
+}
+// Every way out of a call -- also an error return in the middle -- ends with its streams drained: copies from / to the caller's
+// host arrays and the page-locked slots must not be in flight when the caller gets its buffers back.
+struct StreamDrain {
+    hipStream_t s[3];
+    ~StreamDrain() { for (hipStream_t x : s) if (x) (void)hipStreamSynchronize(x); }
+};
+
+// The two-set pipeline of pseg_predict_batch and the page chain.  Unit u works in set u % 2; the set's events say when its buffers
+// are free again:  up = the unit's uploads landed (s_in),  done = its compute landed (st),  down = its downloads landed (s_out).
+struct PipeSet {
+    hipEvent_t up = nullptr, done = nullptr, down = nullptr;
+    int create() {
+        for (hipEvent_t* ev : {&up, &done, &down})
+            if (!*ev) PSEG_HIP(hipEventCreateWithFlags(ev, hipEventDisableTiming));
+        return PSEG_OK;
+    }
+    void destroy() { for (hipEvent_t* ev : {&up, &done, &down}) { if (*ev) (void)hipEventDestroy(*ev); *ev = nullptr; } }
+};
+// upload(u) and compute(u) of one unit.  The uploads wait until unit u - 2's compute has read the set's inputs; the compute waits for them
+// and until unit u - 2's downloads have left the set's outputs.  before_compute: the stage's host-side hook (the wait in front of a canvas change).
+template <class Stage>
+int pipe_enqueue(Stage& g, int u, const PipeSet& s, hipStream_t s_in, hipStream_t st) {
+    PSEG_HIP(hipStreamWaitEvent(s_in, s.done, 0));          // (a no-op before the first record)
+    PSEG_TRY(g.upload(u, s));
+    PSEG_HIP(hipEventRecord(s.up, s_in));
+    PSEG_TRY(g.before_compute(u));
+    PSEG_HIP(hipStreamWaitEvent(st, s.up, 0));
+    PSEG_HIP(hipStreamWaitEvent(st, s.down, 0));
+    PSEG_TRY(g.compute(u, s));
+    PSEG_HIP(hipEventRecord(s.done, st));
+    return PSEG_OK;
+}
+// `nu` units of `g` over set[0..1]: g.reserve() sizes every buffer for the largest unit while the sets are idle (a call ends drained), then
+// the host enqueues unit u + 1 before it downloads unit u, and finishes unit u - 1 while the device works.  download(u) keeps its own wait for
+// `done` (on the host where it needs the unit's sizes, else on s_out); finish(u), for the units that have one, runs on the calling thread.
+template <class Stage>
+int run_pipeline(Stage& g, int nu, const PipeSet* set, hipStream_t s_in, hipStream_t st, hipStream_t s_out) {
+    StreamDrain drain{{s_in, st, s_out}};
+    PSEG_TRY(g.reserve());
+    if (nu > 0) PSEG_TRY(pipe_enqueue(g, 0, set[0], s_in, st));
+    for (int u = 0; u <= nu; ++u) {
+        if (u + 1 < nu) PSEG_TRY(pipe_enqueue(g, u + 1, set[(u + 1) & 1], s_in, st));
+        if (u < nu) {
+            PSEG_TRY(g.download(u, set[u & 1]));
+            PSEG_HIP(hipEventRecord(set[u & 1].down, s_out));
+        }
+        if (u > 0 && g.has_finish(u - 1)) {
+            PSEG_HIP(hipEventSynchronize(set[(u - 1) & 1].down));
+            PSEG_TRY(g.finish(u - 1));
+        }
+    }
+    PSEG_HIP(hipStreamSynchronize(s_out));
+    return PSEG_OK;
+}
+
 // Knobs.  Two kinds, one lookup (PSEG_KNOB):
 //   * ENVIRONMENT knobs -- the PSEG_ENV_KNOBS list below, fourteen names, documented in README.md: operational choices a deployment
 //     may make (page-unit size, the persistent kernel families off, checks, logging).  Nothing else in the process environment
@@ -201,18 +285,15 @@ struct Engine {
     uint8_t* cur_labels_u8 = nullptr;
     float* cur_margin = nullptr;       // bf16 mode: top-1 minus top-2 logit map requested by the running call (label-exact mode)
     bool margin_done = false;          // ... and whether the tail kernel of the graph wrote it (else it is derived from the logits)
-    float* d_logits_tmp = nullptr; // H*W*C f32 when the caller does not want logits
-    size_t logits_tmp_bytes = 0;
-    uint8_t* d_img_stage = nullptr;
-    size_t img_stage_bytes = 0;
-    int64_t* d_lab_stage = nullptr;
-    float* d_prob_stage = nullptr;
-    float* d_logit_stage = nullptr;
-    size_t lab_stage_bytes = 0, prob_stage_bytes = 0, logit_stage_bytes = 0;
+    GrowDev logits_tmp;            // H*W*C f32 when the caller does not want logits
+    GrowDev img_stage, lab_stage, prob_stage, logit_stage;   // pseg_predict's device copies of the caller's arrays
     void* train = nullptr;   // TrainState (pseg_train.hip), f32 mode only
     void* exact = nullptr;   // ExactState (pseg_exactlabels.hip): float32 companion engine, margin / flag buffers of the label-exact mode
-    void* batch = nullptr;   // BatchState (pseg_predict_batch): copy streams, events, two staging slots
-    void* chain = nullptr;   // ChainState (pseg_predict_chain): device buffers of the Predictor chain
+    // BatchState owns the two copy streams (s_in, s_out), its event triples and staging slots; the page chain borrows the streams
+    // (batch_copy_streams) and owns everything else it uses: ChainState has the aux stream and event of the single-page chain, its
+    // buffers, and the page list's two staging sets with their own event triples.  Compute of both runs on Engine::stream.
+    void* batch = nullptr;   // BatchState (pseg_engine.hip), freed by pseg_destroy
+    void* chain = nullptr;   // ChainState (pseg_chain.hip), freed by chain_free; chain_trim frees the page list's staging memory
     void* dist = nullptr;    // DistState (pseg_allreduce_init): RCCL communicator of the data-parallel train step
     int relaxed_f32 = 0;     // != 0 during a train / eval step: wide float32 layers may run channel-blocked on the matrix cores
     uint32_t drop_key = 0;   // != 0 while a TRAINING forward runs: Dropout layers are live (key = seed / step mix)

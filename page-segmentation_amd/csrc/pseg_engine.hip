@@ -411,16 +411,6 @@ static void free_dev(void*& p) {
     p = nullptr;
 }
 
-static int ensure(void** p, size_t* cap, size_t bytes) {
-    if (*cap >= bytes && *p) return PSEG_OK;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    PSEG_HIP(hipMalloc(p, bytes));
-    *cap = bytes;
-    return PSEG_OK;
-}
-
 // Upload weights in correlation form.  Conv2D: as is.  Conv2DTranspose s1 (kh,kw,Cout,Cin):
 // Wc[ky][kx][ci][co] = K[KH-1-ky][KW-1-kx][co][ci].  Conv2DTranspose k2 s2: [a][b][ci][co] =
 // K[a][b][co][ci].
@@ -694,9 +684,8 @@ int run_exact(Engine& e, const uint8_t* d_img, float* d_logits, float* d_probs,
                 a.pt = a.pl = 0;
                 float* zl = d_logits;
                 if (!zl) {
-                    PSEG_TRY(ensure((void**)&e.d_logits_tmp, &e.logits_tmp_bytes,
-                                    (size_t)e.H * e.W * op.Cout * sizeof(float)));
-                    zl = e.d_logits_tmp;
+                    PSEG_TRY(e.logits_tmp.ensure((size_t)e.H * e.W * op.Cout * sizeof(float), "logits"));
+                    zl = e.logits_tmp.as<float>();
                 }
                 a.dst = zl;
                 // the kernel indexes src rows with Win: rows of the padded canvas
@@ -762,8 +751,8 @@ int run_exact(Engine& e, const uint8_t* d_img, float* d_logits, float* d_probs,
                         ta.wl = nx->d_w; ta.bl = nx->d_b; ta.ncls = nx->Cout; ta.H = e.H; ta.W = e.W;
                         float* zl = d_logits;
                         if (!zl && d_probs) {
-                            PSEG_TRY(ensure((void**)&e.d_logits_tmp, &e.logits_tmp_bytes, (size_t)e.H * e.W * nx->Cout * sizeof(float)));
-                            zl = e.d_logits_tmp;
+                            PSEG_TRY(e.logits_tmp.ensure((size_t)e.H * e.W * nx->Cout * sizeof(float), "logits"));
+                            zl = e.logits_tmp.as<float>();
                         }
                         ta.logits = zl; ta.labels = d_labels; ta.labels_u8 = d_labels_u8;
                     }
@@ -843,8 +832,8 @@ static int run_bf16(Engine& e, const uint8_t* d_img, float* d_logits, float* d_p
     e.margin_done = false;
     if (d_margin && !d_logits && !mfma_tail_emits_margin(e)) {
         // this graph's tail kernel has no margin output: take the float32 logits and derive the margin from them
-        PSEG_TRY(ensure((void**)&e.d_logits_tmp, &e.logits_tmp_bytes, (size_t)e.H * e.W * e.n_classes * sizeof(float)));
-        d_logits = e.d_logits_tmp;
+        PSEG_TRY(e.logits_tmp.ensure((size_t)e.H * e.W * e.n_classes * sizeof(float), "logits"));
+        d_logits = e.logits_tmp.as<float>();
     }
     e.cur_logits = d_logits;
     e.cur_probs = d_probs;
@@ -983,8 +972,8 @@ int predict_device(Engine& e, const uint8_t* d_img, int H, int W, float* d_logit
     if (e.mode == PSEG_MODE_BF16)
         return run_bf16(e, d_img, d_logits, d_probs, d_labels, d_labels_u8, d_margin, st);
     if (d_margin && !d_logits) {
-        PSEG_TRY(ensure((void**)&e.d_logits_tmp, &e.logits_tmp_bytes, (size_t)H * W * e.n_classes * sizeof(float)));
-        d_logits = e.d_logits_tmp;
+        PSEG_TRY(e.logits_tmp.ensure((size_t)H * W * e.n_classes * sizeof(float), "logits"));
+        d_logits = e.logits_tmp.as<float>();
     }
     PSEG_TRY(run_exact(e, d_img, d_logits, d_probs, d_labels, d_labels_u8, st));
     if (d_margin) launch_margin_from_logits(d_logits, (size_t)H * W, e.n_classes, d_margin, st);
@@ -994,55 +983,27 @@ int predict_device(Engine& e, const uint8_t* d_img, int H, int W, float* d_logit
 // ---- page batches: copies of neighbouring pages overlap the compute of the current one -----------
 struct BatchState {
     hipStream_t s_in = nullptr, s_out = nullptr;
-    hipEvent_t up[2] = {nullptr, nullptr}, done[2] = {nullptr, nullptr}, down[2] = {nullptr, nullptr};
-    uint8_t* d_img[2] = {nullptr, nullptr};
-    void* d_lab[2] = {nullptr, nullptr};
-    size_t img_bytes[2] = {0, 0}, lab_bytes[2] = {0, 0};
+    PipeSet set[2];
+    GrowDev d_img[2], d_lab[2];
     // pinned staging ring for callers whose pages / label maps live in pageable memory: the page is copied into the
     // slot by the calling thread and leaves it by DMA; label maps arrive in the slot by DMA and are copied out by the
     // calling thread while the next page computes.  Buffers from pseg_host_alloc / pseg_host_register skip the ring.
-    uint8_t* h_in[2] = {nullptr, nullptr};
-    uint8_t* h_out[2] = {nullptr, nullptr};
-    size_t h_in_bytes[2] = {0, 0}, h_out_bytes[2] = {0, 0};
+    GrowPin h_in[2], h_out[2];
 };
-
-static int ensure_pinned(uint8_t** p, size_t* cap, size_t bytes) {
-    if (*cap >= bytes && *p) return PSEG_OK;
-    if (*p) (void)hipHostFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    PSEG_HIP(hipHostMalloc((void**)p, bytes, hipHostMallocDefault));
-    *cap = bytes;
-    return PSEG_OK;
-}
-
-// true when `p` is page-locked host memory the runtime knows (hipHostMalloc / hipHostRegister): DMA goes straight to it
-static bool is_pinned(const void* p) {
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return at.type == hipMemoryTypeHost;
-}
 
 static void batch_free(Engine& e) {
     auto* b = (BatchState*)e.batch;
     if (!b) return;
     for (int i = 0; i < 2; ++i) {
-        if (b->up[i]) (void)hipEventDestroy(b->up[i]);
-        if (b->done[i]) (void)hipEventDestroy(b->done[i]);
-        if (b->down[i]) (void)hipEventDestroy(b->down[i]);
-        free_dev((void*&)b->d_img[i]);
-        free_dev(b->d_lab[i]);
-        if (b->h_in[i]) (void)hipHostFree(b->h_in[i]);
-        if (b->h_out[i]) (void)hipHostFree(b->h_out[i]);
+        b->set[i].destroy();
+        for (GrowDev* d : {&b->d_img[i], &b->d_lab[i]}) d->release();
+        for (GrowPin* p : {&b->h_in[i], &b->h_out[i]}) p->release();
     }
     if (b->s_in) (void)hipStreamDestroy(b->s_in);
     if (b->s_out) (void)hipStreamDestroy(b->s_out);
     delete b;
     e.batch = nullptr;
 }
-
-int predict_device_pages(Engine& e, const uint8_t* d_imgs, int n, int H, int W, int64_t* d_labels, uint8_t* d_labels_u8, hipStream_t st);
-bool pages_capable(Engine& e);
 
 // units of a page list (see predict_batch): runs of same-shape pages, at most `cap` per unit, sizes 1, 2, 4 ... at the head and
 // ... 4, 2, 1 at the tail of the list.  Ho / Wo (the page chain: the label map's final shape; NULL: none) are part of a page's shape.
@@ -1075,11 +1036,7 @@ static int batch_state(Engine& e) {
     e.batch = nb;
     PSEG_HIP(hipStreamCreateWithFlags(&nb->s_in, hipStreamNonBlocking));
     PSEG_HIP(hipStreamCreateWithFlags(&nb->s_out, hipStreamNonBlocking));
-    for (int i = 0; i < 2; ++i) {
-        PSEG_HIP(hipEventCreateWithFlags(&nb->up[i], hipEventDisableTiming));
-        PSEG_HIP(hipEventCreateWithFlags(&nb->done[i], hipEventDisableTiming));
-        PSEG_HIP(hipEventCreateWithFlags(&nb->down[i], hipEventDisableTiming));
-    }
+    for (PipeSet& ps : nb->set) PSEG_TRY(ps.create());
     return PSEG_OK;
 }
 // the two copy streams of pseg_predict_batch: the page chain's pipeline runs on the same ones (a call of either ends drained)
@@ -1117,6 +1074,89 @@ int batch_unit_cap(Engine& e, int n, const int* H, const int* W) {
 // the page slots a unit of `want` same-shape pages gets on this device (the page chain with a caller's unit_cap)
 int fit_unit_slots(Engine& e, int H, int W, int want) { return pages_capable(e) ? fit_page_slots(e, H, W, want) : 1; }
 
+// pseg_predict_batch's stages of run_pipeline.  Units: runs of consecutive pages of one shape go through the graph together
+// (run_bf16_pages: every tensor holds a page slot per page of the unit, the low-resolution layers take all slots in one launch);
+// everything else is a unit of one page.
+struct BatchRun {
+    Engine& e;
+    BatchState& b;
+    int n; const uint8_t* const* imgs; const int *H, *W; int64_t* const* labels; uint8_t* const* labels_u8;
+    std::vector<char> in_pinned, out_pinned;
+    std::vector<int> ub, ug;                 // first page, page count of every unit
+
+    size_t upx(int u) const { return (size_t)H[ub[u]] * W[ub[u]]; }
+    size_t lab_off8(int u, int k) const { return (size_t)k * upx(u) * 8; }                                   // int64 map of page k of the unit
+    size_t lab_off1(int u, int k) const { return (labels ? (size_t)ug[u] * upx(u) * 8 : 0) + (size_t)k * upx(u); }   // its uint8 map
+    size_t unit_out_bytes(int u) const { return (size_t)ug[u] * upx(u) * ((labels ? 8 : 0) + (labels_u8 ? 1 : 0)); }
+    bool unit_pinned(int u, const std::vector<char>& v) const { bool all = true; for (int k = 0; k < ug[u]; ++k) all = all && v[ub[u] + k]; return all; }
+
+    // a reallocation of a slot must not race with work still using it: every slot is sized for the largest unit up front
+    int reserve() {
+        size_t max_in = 0, max_out = 0;
+        for (size_t u = 0; u < ub.size(); ++u) { max_in = std::max(max_in, upx(u) * e.in_ch * ug[u]); max_out = std::max(max_out, unit_out_bytes(u)); }
+        for (int s = 0; s < 2; ++s) {
+            PSEG_TRY(b.d_img[s].ensure(max_in, "batch pages"));
+            PSEG_TRY(b.d_lab[s].ensure(max_out + 16, "batch label maps"));
+        }
+        bool any_in = false, any_out = false;
+        for (int i = 0; i < n; ++i) { any_in |= !in_pinned[i]; any_out |= !out_pinned[i]; }
+        for (int s = 0; s < 2 && (any_in || any_out); ++s) {
+            PSEG_HIP(hipEventSynchronize(b.set[s].up));
+            PSEG_HIP(hipEventSynchronize(b.set[s].down));
+            if (any_in) PSEG_TRY(b.h_in[s].ensure(max_in, "batch page ring"));
+            if (any_out) PSEG_TRY(b.h_out[s].ensure(max_out, "batch label ring"));
+        }
+        return PSEG_OK;
+    }
+    int upload(int u, const PipeSet& ev) {
+        const int s = u & 1;
+        const size_t pb = upx(u) * e.in_ch;
+        if (!unit_pinned(u, in_pinned)) {
+            PSEG_HIP(hipEventSynchronize(ev.up));       // the ring slot was last read by the upload of unit u-2
+            for (int k = 0; k < ug[u]; ++k) memcpy(b.h_in[s].p + (size_t)k * pb, imgs[ub[u] + k], pb);
+            PSEG_HIP(hipMemcpyAsync(b.d_img[s].p, b.h_in[s].p, pb * ug[u], hipMemcpyHostToDevice, b.s_in));
+        } else {
+            for (int k = 0; k < ug[u]; ++k)
+                PSEG_HIP(hipMemcpyAsync(b.d_img[s].p + (size_t)k * pb, imgs[ub[u] + k], pb, hipMemcpyHostToDevice, b.s_in));
+        }
+        return PSEG_OK;
+    }
+    int before_compute(int u) {
+        // a canvas change re-allocates / clears the activation tensors: the previous unit must have left them
+        if (round_up(H[ub[u]], 32) != e.Hp || round_up(W[ub[u]], 32) != e.Wp || ug[u] > e.pages) PSEG_HIP(hipStreamSynchronize(e.stream));
+        return PSEG_OK;
+    }
+    int compute(int u, const PipeSet&) {
+        const int s = u & 1, i0 = ub[u];
+        int64_t* dl = labels ? (int64_t*)b.d_lab[s].p : nullptr;
+        uint8_t* du = labels_u8 ? b.d_lab[s].p + lab_off1(u, 0) : nullptr;
+        if (ug[u] > 1) return predict_device_pages(e, b.d_img[s].p, ug[u], H[i0], W[i0], dl, du, e.stream);
+        return predict_device(e, b.d_img[s].p, H[i0], W[i0], nullptr, nullptr, dl, du, e.stream, nullptr);
+    }
+    int download(int u, const PipeSet& ev) {
+        const int s = u & 1;
+        const size_t npx = upx(u);
+        PSEG_HIP(hipStreamWaitEvent(b.s_out, ev.done, 0));
+        if (unit_pinned(u, out_pinned)) {
+            for (int k = 0; k < ug[u]; ++k) {
+                if (labels) PSEG_HIP(hipMemcpyAsync(labels[ub[u] + k], b.d_lab[s].p + lab_off8(u, k), npx * 8, hipMemcpyDeviceToHost, b.s_out));
+                if (labels_u8) PSEG_HIP(hipMemcpyAsync(labels_u8[ub[u] + k], b.d_lab[s].p + lab_off1(u, k), npx, hipMemcpyDeviceToHost, b.s_out));
+            }
+        } else      // all maps of the unit in one DMA into the ring slot (its previous content was copied out by finish(u - 2))
+            PSEG_HIP(hipMemcpyAsync(b.h_out[s].p, b.d_lab[s].p, unit_out_bytes(u), hipMemcpyDeviceToHost, b.s_out));
+        return PSEG_OK;
+    }
+    bool has_finish(int u) const { return !unit_pinned(u, out_pinned); }
+    int finish(int u) {                      // pageable destination: ring slot -> caller's arrays, on the calling thread
+        const size_t npx = upx(u);
+        for (int k = 0; k < ug[u]; ++k) {
+            if (labels) memcpy(labels[ub[u] + k], b.h_out[u & 1].p + lab_off8(u, k), npx * 8);
+            if (labels_u8) memcpy(labels_u8[ub[u] + k], b.h_out[u & 1].p + lab_off1(u, k), npx);
+        }
+        return PSEG_OK;
+    }
+};
+
 static int predict_batch(Engine& e, int n, const uint8_t* const* imgs, const int* H, const int* W,
                          int64_t* const* labels, uint8_t* const* labels_u8) {
     PSEG_HIP(hipSetDevice(e.device));
@@ -1129,115 +1169,20 @@ static int predict_batch(Engine& e, int n, const uint8_t* const* imgs, const int
         if (H[i] <= 0 || W[i] <= 0 || !imgs[i] || (labels && !labels[i]) || (labels_u8 && !labels_u8[i]))
             return fail(PSEG_EINVAL, "page %d: empty shape or NULL buffer", i);
     }
-    std::vector<char> in_pinned(n), out_pinned(n);
+    BatchRun run{e, *b, n, imgs, H, W, labels, labels_u8, std::vector<char>(n), std::vector<char>(n), {}, {}};
     for (int i = 0; i < n; ++i) {
-        in_pinned[i] = is_pinned(imgs[i]);
-        out_pinned[i] = (!labels || is_pinned(labels[i])) && (!labels_u8 || is_pinned(labels_u8[i]));
+        run.in_pinned[i] = host_is_pinned(imgs[i]);
+        run.out_pinned[i] = (!labels || host_is_pinned(labels[i])) && (!labels_u8 || host_is_pinned(labels_u8[i]));
     }
-    // Units: runs of consecutive pages of one shape go through the graph together (run_bf16_pages: every tensor holds a page slot
-    // per page of the unit, the low-resolution layers take all slots in one launch); everything else is a unit of one page.
-    // PSEG_BATCH_PAGES caps a unit (default 8: 7 GB of activations at 2048x1536; 1 = page by page as before).
-    const int cap = unit_cap_of(e, n, H, W);
-    // Unit sizes.  The upload of the FIRST unit and the download of the LAST one have no compute beside them: a list cut into
-    // equal units of 8 pages waits 8 page uploads at its head and 8 downloads at its tail (32 pages: 2 of 14 ms).  So a run of same-shape
-    // pages that opens the list starts with units of 1, 2, 4, ... pages, one that closes it ends ... 4, 2, 1 (every unit's copies
-    // still fit under its neighbour's compute: a page computes for 0.4 ms and travels for 0.12), the middle goes in units of `cap`.
+    // Unit sizes.  PSEG_BATCH_PAGES caps a unit (default 8: 7 GB of activations at 2048x1536; 1 = page by page).  The upload of the
+    // FIRST unit and the download of the LAST one have no compute beside them: a list cut into equal units of 8 pages waits 8 page
+    // uploads at its head and 8 downloads at its tail (32 pages: 2 of 14 ms).  So a run of same-shape pages that opens the list
+    // starts with units of 1, 2, 4, ... pages, one that closes it ends ... 4, 2, 1 (every unit's copies still fit under its
+    // neighbour's compute: a page computes for 0.4 ms and travels for 0.12), the middle goes in units of `cap`.
     // Same box, 32 / 8 pages of 2048x1536, ms per page, ramped against equal units: pinned uint8 0.410-0.445 vs 0.430 / 0.458 vs 0.466,
     // pageable arrays through the ring 0.456 vs 0.57 / 0.51-0.52 vs 0.55 (tools/gpu_r05_hostpath.sh).
-    std::vector<int> ub, ug;                 // first page, page count of every unit
-    plan_units(n, H, W, nullptr, nullptr, cap, ub, ug);
-    const int nu = (int)ub.size();
-    auto upx = [&](int u) { return (size_t)H[ub[u]] * W[ub[u]]; };
-    auto lab_off8 = [&](int u, int k) { return (size_t)k * upx(u) * 8; };                                   // int64 map of page k of the unit
-    auto lab_off1 = [&](int u, int k) { return (labels ? (size_t)ug[u] * upx(u) * 8 : 0) + (size_t)k * upx(u); };   // its uint8 map
-    auto unit_out_bytes = [&](int u) { return (size_t)ug[u] * upx(u) * ((labels ? 8 : 0) + (labels_u8 ? 1 : 0)); };
-    auto unit_pinned = [&](int u, const std::vector<char>& v) { bool all = true; for (int k = 0; k < ug[u]; ++k) all = all && v[ub[u] + k]; return all; };
-    auto upload = [&](int u) -> int {        // unit u -> slot u % 2 (its previous compute has been waited for)
-        const int s = u & 1;
-        const size_t npx = upx(u), pb = npx * e.in_ch;
-        PSEG_TRY(ensure((void**)&b->d_img[s], &b->img_bytes[s], pb * ug[u]));
-        PSEG_TRY(ensure(&b->d_lab[s], &b->lab_bytes[s], unit_out_bytes(u) + 16));
-        PSEG_HIP(hipStreamWaitEvent(b->s_in, b->done[s], 0));      // slot input consumed (no-op before first record)
-        const bool pinned = unit_pinned(u, in_pinned);
-        if (!pinned) {
-            // the ring slot was last read by the upload of unit u-2, recorded in up[s]
-            PSEG_HIP(hipEventSynchronize(b->up[s]));
-            PSEG_TRY(ensure_pinned(&b->h_in[s], &b->h_in_bytes[s], pb * ug[u]));
-            for (int k = 0; k < ug[u]; ++k) memcpy(b->h_in[s] + (size_t)k * pb, imgs[ub[u] + k], pb);
-            PSEG_HIP(hipMemcpyAsync(b->d_img[s], b->h_in[s], pb * ug[u], hipMemcpyHostToDevice, b->s_in));
-        } else {
-            for (int k = 0; k < ug[u]; ++k)
-                PSEG_HIP(hipMemcpyAsync(b->d_img[s] + (size_t)k * pb, imgs[ub[u] + k], pb, hipMemcpyHostToDevice, b->s_in));
-        }
-        PSEG_HIP(hipEventRecord(b->up[s], b->s_in));
-        return PSEG_OK;
-    };
-    auto compute = [&](int u) -> int {
-        const int s = u & 1, i0 = ub[u];
-        // a canvas change re-allocates / clears the activation tensors: the previous unit must have left them
-        if (round_up(H[i0], 32) != e.Hp || round_up(W[i0], 32) != e.Wp || ug[u] > e.pages) PSEG_HIP(hipStreamSynchronize(e.stream));
-        PSEG_HIP(hipStreamWaitEvent(e.stream, b->up[s], 0));
-        PSEG_HIP(hipStreamWaitEvent(e.stream, b->down[s], 0));      // slot output of unit u-2 has left
-        int64_t* dl = labels ? (int64_t*)b->d_lab[s] : nullptr;
-        uint8_t* du = labels_u8 ? (uint8_t*)b->d_lab[s] + lab_off1(u, 0) : nullptr;
-        if (ug[u] > 1) PSEG_TRY(predict_device_pages(e, b->d_img[s], ug[u], H[i0], W[i0], dl, du, e.stream));
-        else PSEG_TRY(predict_device(e, b->d_img[s], H[i0], W[i0], nullptr, nullptr, dl, du, e.stream, nullptr));
-        PSEG_HIP(hipEventRecord(b->done[s], e.stream));
-        return PSEG_OK;
-    };
-    auto download = [&](int u) -> int {
-        const int s = u & 1;
-        const size_t npx = upx(u);
-        PSEG_HIP(hipStreamWaitEvent(b->s_out, b->done[s], 0));
-        if (unit_pinned(u, out_pinned)) {
-            for (int k = 0; k < ug[u]; ++k) {
-                if (labels) PSEG_HIP(hipMemcpyAsync(labels[ub[u] + k], (uint8_t*)b->d_lab[s] + lab_off8(u, k), npx * 8, hipMemcpyDeviceToHost, b->s_out));
-                if (labels_u8) PSEG_HIP(hipMemcpyAsync(labels_u8[ub[u] + k], (uint8_t*)b->d_lab[s] + lab_off1(u, k), npx, hipMemcpyDeviceToHost, b->s_out));
-            }
-        } else {   // all maps of the unit in one DMA into the ring slot (its previous content was copied out by finish(u - 2))
-            PSEG_TRY(ensure_pinned(&b->h_out[s], &b->h_out_bytes[s], unit_out_bytes(u)));
-            PSEG_HIP(hipMemcpyAsync(b->h_out[s], b->d_lab[s], unit_out_bytes(u), hipMemcpyDeviceToHost, b->s_out));
-        }
-        PSEG_HIP(hipEventRecord(b->down[s], b->s_out));
-        return PSEG_OK;
-    };
-    auto finish = [&](int u) -> int {        // pageable destination: ring slot -> caller's arrays, on the calling thread
-        if (unit_pinned(u, out_pinned)) return PSEG_OK;
-        const int s = u & 1;
-        const size_t npx = upx(u);
-        PSEG_HIP(hipEventSynchronize(b->down[s]));
-        for (int k = 0; k < ug[u]; ++k) {
-            if (labels) memcpy(labels[ub[u] + k], b->h_out[s] + lab_off8(u, k), npx * 8);
-            if (labels_u8) memcpy(labels_u8[ub[u] + k], b->h_out[s] + lab_off1(u, k), npx);
-        }
-        return PSEG_OK;
-    };
-    // every way out -- also an error return in the middle -- ends with the three streams drained: copies from / to the caller's
-    // host arrays and the ring slots must not be in flight when the caller gets its buffers back
-    struct Drain { hipStream_t a, b, c; ~Drain() { (void)hipStreamSynchronize(a); (void)hipStreamSynchronize(b); (void)hipStreamSynchronize(c); } } drain{b->s_in, e.stream, b->s_out};
-    // a reallocation of a slot must not race with work still using it: size every slot for the largest unit up front
-    size_t max_in = 0, max_out = 0;
-    for (int u = 0; u < nu; ++u) { max_in = std::max(max_in, upx(u) * e.in_ch * ug[u]); max_out = std::max(max_out, unit_out_bytes(u)); }
-    for (int s = 0; s < 2; ++s) {
-        PSEG_TRY(ensure((void**)&b->d_img[s], &b->img_bytes[s], max_in));
-        PSEG_TRY(ensure(&b->d_lab[s], &b->lab_bytes[s], max_out + 16));
-    }
-    bool any_in = false, any_out = false;
-    for (int i = 0; i < n; ++i) { any_in |= !in_pinned[i]; any_out |= !out_pinned[i]; }
-    for (int s = 0; s < 2 && (any_in || any_out); ++s) {
-        PSEG_HIP(hipEventSynchronize(b->up[s]));
-        PSEG_HIP(hipEventSynchronize(b->down[s]));
-        if (any_in) PSEG_TRY(ensure_pinned(&b->h_in[s], &b->h_in_bytes[s], max_in));
-        if (any_out) PSEG_TRY(ensure_pinned(&b->h_out[s], &b->h_out_bytes[s], max_out));
-    }
-    if (nu > 0) { PSEG_TRY(upload(0)); PSEG_TRY(compute(0)); }
-    for (int u = 0; u < nu; ++u) {
-        if (u + 1 < nu) { PSEG_TRY(upload(u + 1)); PSEG_TRY(compute(u + 1)); }
-        PSEG_TRY(download(u));
-        if (u > 0) PSEG_TRY(finish(u - 1));
-    }
-    if (nu > 0) PSEG_TRY(finish(nu - 1));
-    PSEG_HIP(hipStreamSynchronize(b->s_out));
+    plan_units(n, H, W, nullptr, nullptr, unit_cap_of(e, n, H, W), run.ub, run.ug);
+    PSEG_TRY(run_pipeline(run, (int)run.ub.size(), b->set, b->s_in, e.stream, b->s_out));
     return engine_status(e, e.stream);     // (waits for the stream; a give-up of conv_sp_kernel in any unit is an error here)
 }
 
@@ -1349,11 +1294,7 @@ int pseg_destroy(pseg_engine* h) {
     free_dev((void*&)e.d_lut);
     free_dev((void*&)e.d_sp_err);
     if (e.h_sp_err) { (void)hipHostFree(e.h_sp_err); e.h_sp_err = nullptr; }
-    free_dev((void*&)e.d_logits_tmp);
-    free_dev((void*&)e.d_img_stage);
-    free_dev((void*&)e.d_lab_stage);
-    free_dev((void*&)e.d_prob_stage);
-    free_dev((void*&)e.d_logit_stage);
+    for (GrowDev* b : {&e.logits_tmp, &e.img_stage, &e.lab_stage, &e.prob_stage, &e.logit_stage}) b->release();
     for (auto& s : e.slots)
         for (auto& pr : s.pending) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
     for (auto ev : e.event_pool) (void)hipEventDestroy(ev);
@@ -1460,17 +1401,16 @@ int pseg_predict(pseg_engine* h, const uint8_t* img, int H, int W, float* logits
     Engine& e = h->e;
     PSEG_HIP(hipSetDevice(e.device));
     const size_t npx = (size_t)H * W, C = e.n_classes;
-    PSEG_TRY(ensure((void**)&e.d_img_stage, &e.img_stage_bytes, npx * e.in_ch));
-    if (labels) PSEG_TRY(ensure((void**)&e.d_lab_stage, &e.lab_stage_bytes, npx * 8));
-    if (probs) PSEG_TRY(ensure((void**)&e.d_prob_stage, &e.prob_stage_bytes, npx * C * 4));
-    if (logits) PSEG_TRY(ensure((void**)&e.d_logit_stage, &e.logit_stage_bytes, npx * C * 4));
-    PSEG_HIP(hipMemcpyAsync(e.d_img_stage, img, npx * e.in_ch, hipMemcpyHostToDevice, e.stream));
-    PSEG_TRY(predict_device(e, e.d_img_stage, H, W, logits ? e.d_logit_stage : nullptr,
-                            probs ? e.d_prob_stage : nullptr, labels ? e.d_lab_stage : nullptr,
-                            nullptr, e.stream, nullptr));
-    if (logits) PSEG_HIP(hipMemcpyAsync(logits, e.d_logit_stage, npx * C * 4, hipMemcpyDeviceToHost, e.stream));
-    if (probs) PSEG_HIP(hipMemcpyAsync(probs, e.d_prob_stage, npx * C * 4, hipMemcpyDeviceToHost, e.stream));
-    if (labels) PSEG_HIP(hipMemcpyAsync(labels, e.d_lab_stage, npx * 8, hipMemcpyDeviceToHost, e.stream));
+    PSEG_TRY(e.img_stage.ensure(npx * e.in_ch, "page"));
+    if (labels) PSEG_TRY(e.lab_stage.ensure(npx * 8, "labels"));
+    if (probs) PSEG_TRY(e.prob_stage.ensure(npx * C * 4, "probabilities"));
+    if (logits) PSEG_TRY(e.logit_stage.ensure(npx * C * 4, "logits"));
+    PSEG_HIP(hipMemcpyAsync(e.img_stage.p, img, npx * e.in_ch, hipMemcpyHostToDevice, e.stream));
+    PSEG_TRY(predict_device(e, e.img_stage.p, H, W, logits ? e.logit_stage.as<float>() : nullptr, probs ? e.prob_stage.as<float>() : nullptr,
+                            labels ? e.lab_stage.as<int64_t>() : nullptr, nullptr, e.stream, nullptr));
+    if (logits) PSEG_HIP(hipMemcpyAsync(logits, e.logit_stage.p, npx * C * 4, hipMemcpyDeviceToHost, e.stream));
+    if (probs) PSEG_HIP(hipMemcpyAsync(probs, e.prob_stage.p, npx * C * 4, hipMemcpyDeviceToHost, e.stream));
+    if (labels) PSEG_HIP(hipMemcpyAsync(labels, e.lab_stage.p, npx * 8, hipMemcpyDeviceToHost, e.stream));
     return engine_status(e, e.stream);
 }
 
@@ -1490,7 +1430,7 @@ int pseg_engine_trim(pseg_engine* h) {
     for (auto& op : e.ops) mfma_trim_op(op);                 // (the skip-logits planes grow with canvas x slots too)
     e.Hp = e.Wp = 0;
     e.pages = 1;
-    free_dev((void*&)e.d_logits_tmp); e.logits_tmp_bytes = 0;
+    e.logits_tmp.release();
     chain_trim(e);
     return PSEG_OK;
 }
