@@ -114,6 +114,51 @@ int pseg_predict_device(pseg_engine* e, const uint8_t* d_img, int H, int W, floa
 int pseg_predict_pages_device(pseg_engine* e, const uint8_t* d_imgs, int n_pages, int H, int W, int64_t* d_labels,
                               uint8_t* d_labels_u8, void* stream);
 
+/* ---- Tiled prediction: the label map of a page of any size ------------------------------------------------------- */
+
+/* The reference pads a page to a multiple of 32, runs the graph on the whole of it and crops (lib/model.py:10-42); it has no tiles.
+ * A bf16 engine refuses a page once a tensor of its graph would reach 4 GiB (fcn_skip: a canvas of 8192 x 8192, unet: about
+ * 5790 x 5790), and any engine fails with PSEG_ENOMEM where one page's activation tensors do not fit the device.  These entries cut
+ * such a page into same-shape tiles whose stitched label map EQUALS the whole page's wherever the whole page can run -- no
+ * tolerance: a tile carries `halo` pixels of context (96 for fcn / fcn_skip, 160 for unet / res_unet: at least the receptive-field
+ * radius) on every side that is not the canvas edge, starts on the page's 32-pixel grid and never extends past the page's own
+ * canvas (a page zero-extended past its canvas is another page to lib/model.py:20-26's padding).
+ *
+ * pseg_tile_plan -- host arithmetic, no device.  Per axis, with Np = the extent rounded up to 32 and T = `tile` (a multiple of 32,
+ * at least 2 halo + 32; 0: the default, 2048): tile extent t = min(T, Np); stride s = t - 2 halo; origins y_k = min(k s, Np - t)
+ * for k = 0, 1, ... up to the first y_k == Np - t; tile k owns [end of tile k - 1's range, y_k + t - halo), the first range starts
+ * at 0, the last ends at Np.  A tile is a row range x a column range (row-major: column index fastest); all tiles of a page have
+ * the shape (*tile_h, *tile_w); tile content = the page's pixels in [y, y + tile_h) x [x, x + tile_w), zeros outside the H x W page.
+ * Returns the number of tiles (>= 1) and fills origin_y / origin_x [n] and owned [n][4] = {y0, y1, x0, x1} (canvas coordinates,
+ * half-open; every output may be NULL; PSEG_EINVAL when there are more than max_tiles tiles and an array to fill), or a negative
+ * PSEG_E* (PSEG_EINVAL: bad arch / shape / tile).  Checked before it returns: every canvas pixel has exactly one owner, an owned
+ * pixel lies at least halo from every tile edge that is not a canvas edge, origins are multiples of 32, tiles lie inside the canvas. */
+int pseg_tile_plan(int arch, int H, int W, int tile, int* tile_h, int* tile_w, int* origin_y, int* origin_x, int* owned, int max_tiles);
+
+/* Network.predict_single_data's `pred` (lib/network.py:259) of a device-resident page through that plan: one launch cuts up to 16
+ * tiles out of the page, they run as one unit of page slots (pseg_predict_pages_device's path; the count is cut to what the
+ * device's free memory holds; float32 engines and PSEG_NO_PAGE_BATCH run tile by tile), one launch writes every tile's owned
+ * rectangle into d_labels (int64) and / or d_labels_u8 (dense H x W; either may be NULL, not both).  A page of one tile runs as
+ * pseg_predict_device.  Asynchronous on `stream`; the tile staging (two grow-only buffers of the engine, freed by pseg_engine_trim)
+ * is grown behind a wait for `stream`.  <= 256 classes.  pseg_predict_tiled: the host-array form, synchronous. */
+int pseg_predict_tiled_device(pseg_engine* e, const uint8_t* d_img, int H, int W, int tile, int64_t* d_labels, uint8_t* d_labels_u8,
+                              void* stream);
+int pseg_predict_tiled(pseg_engine* e, const uint8_t* img, int H, int W, int tile, int64_t* labels, uint8_t* labels_u8);
+
+/* Where tiles are used without the caller asking.  The mode is read by the network stage of pseg_predict, pseg_predict_device and
+ * pseg_predict_chain[_png[_lv]] when label maps alone are requested (logits and probs NULL) and PSEG_CHAIN_EXACT_LABELS is not set;
+ * every other request keeps the whole-page path and its refusals, as do the page-list entries (_batch, _chain_pages*, _chain_scans*).
+ *   PSEG_TILING_OFF     the default: the whole page, always.
+ *   PSEG_TILING_AUTO    tiles for the pages the whole-page path cannot take: the bf16 4 GiB guard refuses the canvas, or one
+ *                       page slot of it does not fit the device's free memory (pseg_engine_page_fits says which pages those are).
+ *   PSEG_TILING_ALWAYS  tiles for every page.
+ * The maps are identical, so the route a page took does not show in the output.  `tile`: pseg_tile_plan's. */
+enum { PSEG_TILING_OFF = 0, PSEG_TILING_AUTO = 1, PSEG_TILING_ALWAYS = 2 };
+int pseg_engine_set_tiling(pseg_engine* e, int mode, int tile);
+/* 1: the whole-page path takes an H x W page on this engine now; 0: it would refuse it (4 GiB guard) or its slot does not fit the
+ * free device memory -- the pages PSEG_TILING_AUTO tiles; negative: PSEG_E*. */
+int pseg_engine_page_fits(pseg_engine* e, int H, int W);
+
 /* Device-side error record of the engine -- the asynchronous `_device` entries cannot report what a kernel finds while it
  * runs.  Waits for `stream` (NULL: the engine's own), then reports AND clears: PSEG_OK, or PSEG_EHIP when one of the bounded
  * counter waits of the streamed-weights kernel (conv_sp_kernel: the 1/8-resolution layers of every page) gave up since the last
@@ -122,7 +167,7 @@ int pseg_predict_pages_device(pseg_engine* e, const uint8_t* d_imgs, int n_pages
  * before it returns; callers of pseg_predict_device / pseg_predict_pages_device call this where they synchronise. */
 int pseg_engine_status(pseg_engine* e, void* stream);
 
-/* Frees the activation tensors (all page slots) of the engine; the next predict call allocates what its page needs.  An
+/* Frees the activation tensors (all page slots) and the tile staging of the engine; the next predict call allocates what its page needs.  An
  * engine grows to the largest canvas x page-slot count it has seen (16 slots at 2048x1536: 14 GB) and keeps that; this is the
  * way back (tf.keras.backend.clear_session in lib/trainer.py:112 is the reference's).  Waits for the device. */
 int pseg_engine_trim(pseg_engine* e);

@@ -222,7 +222,7 @@ static int chain_run(pseg_engine* h, const uint8_t* img, int H, int W, int Ho, i
     if ((flags & PSEG_CHAIN_EXACT_LABELS) && e.mode == PSEG_MODE_BF16)
         PSEG_TRY(pseg_predict_exact_labels_device(h, d_img, H, W, c.buf[CB_LAB].p, nullptr, nullptr, st));
     else
-        PSEG_TRY(predict_device(e, d_img, H, W, nullptr, nullptr, nullptr, c.buf[CB_LAB].p, st, nullptr));
+        PSEG_TRY(predict_labels_routed(e, d_img, H, W, nullptr, c.buf[CB_LAB].p, st));      // (in tiles where the engine's tiling mode says so: the same map)
     // 2. / 3. resize and post-processors
     uint8_t* cur = nullptr;
     PSEG_TRY(chain_post_enqueue(e, c.buf[CB_LAB].p, c.buf[CB_LAB2].p, c.buf[CB_LAB2].p + nla, d_bin, H, W, Hl, Wl, req.resize, post_ops, n_post, st, &cur,

@@ -175,6 +175,9 @@ constexpr int PSEG_CHAIN_BLOCK = 16;   // float32 mode: input channels per pass 
 constexpr int PSEG_MAXC = 64;   // classes the train-step metric slots and the wide bf16 logits kernel are sized for
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline int round_up(int a, int b) { return cdiv(a, b) * b; }
+// crop / tile halo: >= the receptive-field radius of the graph (fcn / fcn_skip: 75 pixels counting the one-sided growth of the
+// 2x2 pools; unet ~122, res_unet ~124), a multiple of 32.  Shared by the label-exact mode's crops and the tile plan.
+static inline int halo_of(int arch) { return (arch == PSEG_ARCH_FCN_SKIP || arch == PSEG_ARCH_FCN) ? 96 : 160; }
 
 // ---- graph description ---------------------------------------------------------------------
 enum OpType { OP_CONV = 0, OP_DECONV2 = 1, OP_POOL = 2, OP_LOGITS = 3, OP_BN = 4 };
@@ -287,6 +290,8 @@ struct Engine {
     bool margin_done = false;          // ... and whether the tail kernel of the graph wrote it (else it is derived from the logits)
     GrowDev logits_tmp;            // H*W*C f32 when the caller does not want logits
     GrowDev img_stage, lab_stage, prob_stage, logit_stage;   // pseg_predict's device copies of the caller's arrays
+    int tiling_mode = 0, tiling_tile = 0;   // pseg_engine_set_tiling: PSEG_TILING_*, the tile edge (0: the default)
+    GrowDev tile_img, tile_lab;    // tiled prediction (pseg_tiles.hip): the tiles of a unit one behind the other, their uint8 label maps
     void* train = nullptr;   // TrainState (pseg_train.hip), f32 mode only
     void* exact = nullptr;   // ExactState (pseg_exactlabels.hip): float32 companion engine, margin / flag buffers of the label-exact mode
     // BatchState owns the two copy streams (s_in, s_out), its event triples and staging slots; the page chain borrows the streams
@@ -429,6 +434,17 @@ void exact_free(Engine& e);
 void chain_free(Engine& e);
 void dist_free(Engine& e);                      // RCCL communicator (pseg_dist.hip)                     // Predictor chain buffers (pseg_chain.hip)                     // label-exact mode state (pseg_exactlabels.hip)
 int set_canvas(Engine& e, int H, int W, hipStream_t st, int pages = 1);
+// What set_canvas refuses and what a page slot costs, host arithmetic over the graph's tensors (shared with fit_page_slots and the
+// AUTO tiling mode).  canvas_refused: a bf16 engine whose largest tensor at this canvas would reach 4 GiB; canvas_slot_bytes: the
+// activation tensors of one page slot; page_slot_fits: one whole-page slot leaves a fifth of the device's free memory untouched
+// (what the engine already holds counts as free).
+bool canvas_refused(const Engine& e, int Hp, int Wp);
+size_t canvas_slot_bytes(const Engine& e, int Hp, int Wp);
+bool page_slot_fits(Engine& e, int H, int W);
+// pseg_tiles.hip: one page's label map(s) from same-shape tiles through the page-slot path, asynchronous on `st`; and the network
+// stage of the label-only entries: tiled where the engine's tiling mode asks for it, else predict_device
+int predict_tiled_device(Engine& e, const uint8_t* d_img, int H, int W, int tile, int64_t* d_labels, uint8_t* d_labels_u8, hipStream_t st);
+int predict_labels_routed(Engine& e, const uint8_t* d_img, int H, int W, int64_t* d_labels, uint8_t* d_labels_u8, hipStream_t st);
 // Waits for `st`, then reports -- and clears -- the engine's device-side error record: PSEG_EHIP when a counter wait of
 // conv_sp_kernel gave up since the last report (the label maps produced since then are not to be trusted).  Called by every
 // entry that synchronises with the host anyway and by pseg_engine_status (for the callers of the asynchronous _device entries).

@@ -524,6 +524,23 @@ int upload_weights(Engine& e) {
     return PSEG_OK;
 }
 
+// The throughput kernels address every tensor through 32-bit buffer descriptors / offsets (out-of-range reads give zeros,
+// out-of-range stores are dropped -- silently wrong labels, not a fault): a canvas whose largest tensor, or the 16 B/px
+// skip-logits / margin planes, reach 4 GiB is refused (unet: 64 bf16 channels -> about 5790 x 5790).  Per page slot: every launch,
+// also one over several slots, builds its descriptors on the slot's own base.
+bool canvas_refused(const Engine& e, int Hp, int Wp) {
+    if (e.mode != PSEG_MODE_BF16) return false;
+    size_t worst = (size_t)Hp * Wp * 16 * 4;
+    for (auto& t : e.tensors) worst = std::max(worst, (size_t)(Hp >> t.s) * (Wp >> t.s) * t.Cs * 2);
+    return worst >= ((size_t)1 << 32);
+}
+size_t canvas_slot_bytes(const Engine& e, int Hp, int Wp) {
+    const size_t esz = e.mode == PSEG_MODE_BF16 ? 2 : 4;
+    size_t b = 0;
+    for (auto& t : e.tensors) b += (size_t)(Hp >> t.s) * (Wp >> t.s) * t.Cs * esz;
+    return b;
+}
+
 int set_canvas(Engine& e, int H, int W, hipStream_t st, int pages) {
     if (H <= 0 || W <= 0) return fail(PSEG_EINVAL, "empty page %dx%d", H, W);
     const int Hp = round_up(H, 32), Wp = round_up(W, 32);
@@ -536,17 +553,10 @@ int set_canvas(Engine& e, int H, int W, hipStream_t st, int pages) {
     // the stream the coming kernels run on -- a hipMemset on the null stream is NOT ordered with non-blocking
     // streams (that race corrupted the first predict after shrinking from a 4096x3072 canvas).
     const size_t esz = e.mode == PSEG_MODE_BF16 ? 2 : 4;
-    if (e.mode == PSEG_MODE_BF16) {
-        // the throughput kernels address every tensor through 32-bit buffer descriptors / offsets (out-of-range reads give
-        // zeros, out-of-range stores are dropped -- silently wrong labels, not a fault): refuse canvases whose largest
-        // tensor, or the 16 B/px skip-logits / margin planes, reach 4 GiB (unet: 64 bf16 channels -> about 5790 x 5790)
-        // (per page slot: every launch, also one over several slots, builds its descriptors on the slot's own base)
-        size_t worst = (size_t)Hp * Wp * 16 * 4;
-        for (auto& t : e.tensors) worst = std::max(worst, (size_t)(Hp >> t.s) * (Wp >> t.s) * t.Cs * esz);
-        if (worst >= ((size_t)1 << 32))
-            return fail(PSEG_EUNSUPPORTED, "page %dx%d: a tensor of this graph would reach 4 GiB (32-bit buffer addressing in the bf16 kernels); "
-                                           "predict it in tiles or use the float32 mode", H, W);
-    }
+    if (canvas_refused(e, Hp, Wp))
+        return fail(PSEG_EUNSUPPORTED, "page %dx%d: a tensor of this graph would reach 4 GiB (32-bit buffer addressing in the bf16 kernels); "
+                                       "predict its label map in tiles (pseg_predict_tiled_device, or pseg_engine_set_tiling for pseg_predict, "
+                                       "pseg_predict_device and pseg_predict_chain) or use the float32 mode", H, W);
     PSEG_HIP(hipDeviceSynchronize());
     // The new canvas is committed only when every tensor has its buffer: a failed allocation leaves the engine with NO canvas
     // (Hp = Wp = 0, one slot, every pointer null or valid for its recorded size), so the next call allocates again instead of
@@ -622,19 +632,29 @@ int engine_status(Engine& e, hipStream_t st) {
                 layer, r[0], r[1], r[6], r[2], r[3], r[4], r[5]);
 }
 
+// *per_slot: the bytes of one slot of this canvas (skip logits: 16 B/px per slot); *room: four fifths of free + held.  false: no answer from the device.
+static bool page_slot_room(Engine& e, int H, int W, double* per_slot, double* room) {
+    const int Hp = round_up(H, 32), Wp = round_up(W, 32);
+    size_t held = 0;
+    for (auto& t : e.tensors) held += t.bytes;
+    *per_slot = (double)((size_t)Hp * Wp * 16 + canvas_slot_bytes(e, Hp, Wp));
+    size_t fr = 0, tot = 0;
+    if (hipMemGetInfo(&fr, &tot) != hipSuccess) { (void)hipGetLastError(); return false; }
+    *room = 0.8 * ((double)fr + (double)held);
+    return true;
+}
 // Page slots that fit the device: `want` slots of this canvas, halved until the activation tensors of the unit (what the engine
 // already holds counts as free) leave a fifth of the free memory untouched.  >= 1 (one slot is what a single page needs anyway).
 static int fit_page_slots(Engine& e, int H, int W, int want) {
     if (want <= 1) return 1;
-    const int Hp = round_up(H, 32), Wp = round_up(W, 32);
-    const size_t esz = e.mode == PSEG_MODE_BF16 ? 2 : 4;
-    size_t per_slot = (size_t)Hp * Wp * 16, held = 0;          // (skip logits: 16 B/px per slot)
-    for (auto& t : e.tensors) { per_slot += (size_t)(Hp >> t.s) * (Wp >> t.s) * t.Cs * esz; held += t.bytes; }
-    size_t fr = 0, tot = 0;
-    if (hipMemGetInfo(&fr, &tot) != hipSuccess) { (void)hipGetLastError(); return want; }
-    const double room = 0.8 * ((double)fr + (double)held);
-    while (want > 1 && (double)per_slot * want > room) want = (want + 1) / 2;
+    double per_slot = 0, room = 0;
+    if (!page_slot_room(e, H, W, &per_slot, &room)) return want;
+    while (want > 1 && per_slot * want > room) want = (want + 1) / 2;
     return want;
+}
+bool page_slot_fits(Engine& e, int H, int W) {
+    double per_slot = 0, room = 0;
+    return !page_slot_room(e, H, W, &per_slot, &room) || per_slot <= room;
 }
 
 int run_exact(Engine& e, const uint8_t* d_img, float* d_logits, float* d_probs,
@@ -1294,7 +1314,7 @@ int pseg_destroy(pseg_engine* h) {
     free_dev((void*&)e.d_lut);
     free_dev((void*&)e.d_sp_err);
     if (e.h_sp_err) { (void)hipHostFree(e.h_sp_err); e.h_sp_err = nullptr; }
-    for (GrowDev* b : {&e.logits_tmp, &e.img_stage, &e.lab_stage, &e.prob_stage, &e.logit_stage}) b->release();
+    for (GrowDev* b : {&e.logits_tmp, &e.img_stage, &e.lab_stage, &e.prob_stage, &e.logit_stage, &e.tile_img, &e.tile_lab}) b->release();
     for (auto& s : e.slots)
         for (auto& pr : s.pending) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
     for (auto ev : e.event_pool) (void)hipEventDestroy(ev);
@@ -1357,6 +1377,7 @@ int pseg_predict_device(pseg_engine* h, const uint8_t* d_img, int H, int W, floa
     if (!h || !d_img) return fail(PSEG_EINVAL, "NULL argument");
     KnobScope knob_scope(h->e);
     hipStream_t st = stream ? (hipStream_t)stream : h->e.stream;
+    if (!d_logits && !d_probs) return predict_labels_routed(h->e, d_img, H, W, d_labels, d_labels_u8, st);   // (labels alone: the engine's tiling mode applies)
     return predict_device(h->e, d_img, H, W, d_logits, d_probs, d_labels, d_labels_u8, st, nullptr);
 }
 
@@ -1406,8 +1427,11 @@ int pseg_predict(pseg_engine* h, const uint8_t* img, int H, int W, float* logits
     if (probs) PSEG_TRY(e.prob_stage.ensure(npx * C * 4, "probabilities"));
     if (logits) PSEG_TRY(e.logit_stage.ensure(npx * C * 4, "logits"));
     PSEG_HIP(hipMemcpyAsync(e.img_stage.p, img, npx * e.in_ch, hipMemcpyHostToDevice, e.stream));
-    PSEG_TRY(predict_device(e, e.img_stage.p, H, W, logits ? e.logit_stage.as<float>() : nullptr, probs ? e.prob_stage.as<float>() : nullptr,
-                            labels ? e.lab_stage.as<int64_t>() : nullptr, nullptr, e.stream, nullptr));
+    if (!logits && !probs)      // (labels alone: the engine's tiling mode applies)
+        PSEG_TRY(predict_labels_routed(e, e.img_stage.p, H, W, labels ? e.lab_stage.as<int64_t>() : nullptr, nullptr, e.stream));
+    else
+        PSEG_TRY(predict_device(e, e.img_stage.p, H, W, logits ? e.logit_stage.as<float>() : nullptr, probs ? e.prob_stage.as<float>() : nullptr,
+                                labels ? e.lab_stage.as<int64_t>() : nullptr, nullptr, e.stream, nullptr));
     if (logits) PSEG_HIP(hipMemcpyAsync(logits, e.logit_stage.p, npx * C * 4, hipMemcpyDeviceToHost, e.stream));
     if (probs) PSEG_HIP(hipMemcpyAsync(probs, e.prob_stage.p, npx * C * 4, hipMemcpyDeviceToHost, e.stream));
     if (labels) PSEG_HIP(hipMemcpyAsync(labels, e.lab_stage.p, npx * 8, hipMemcpyDeviceToHost, e.stream));
@@ -1431,6 +1455,8 @@ int pseg_engine_trim(pseg_engine* h) {
     e.Hp = e.Wp = 0;
     e.pages = 1;
     e.logits_tmp.release();
+    e.tile_img.release();
+    e.tile_lab.release();
     chain_trim(e);
     return PSEG_OK;
 }

@@ -31,9 +31,7 @@
 namespace pseg {
 
 constexpr int XB = 32;        // flag block edge (pixels): a multiple of the graphs' pad unit, so crops start on the page's 32-pixel grid
-// crop halo: >= the receptive-field radius of the graph (fcn / fcn_skip: 75 pixels counting the one-sided growth of the
-// 2x2 pools; unet ~122, res_unet ~124), a multiple of 32
-static int halo_of(const Engine& e) { return (e.arch == PSEG_ARCH_FCN_SKIP || e.arch == PSEG_ARCH_FCN) ? 96 : 160; }
+// (the crop halo is pseg_common.h's halo_of: the tile plan shares it)
 
 struct ExactState {
     pseg_engine* f32 = nullptr;          // float32 companion (PSEG_MODE_F32_EXACT, same graph and weights)
@@ -334,7 +332,7 @@ static int exact_labels(Engine& e, const uint8_t* d_img, int H, int W, uint8_t* 
     x.h_done.assign(nblk, 0);
     bool full = false;
     double area = 0, spent = 0;
-    const int XHALO = halo_of(e);
+    const int XHALO = halo_of(e.arch);
     const double full_cost = (double)npx + X_FIXED;
     for (int iter = 0; iter < 6 && !full; ++iter) {
         PSEG_HIP(hipMemsetAsync(x.d_counters, 0, 32, st));

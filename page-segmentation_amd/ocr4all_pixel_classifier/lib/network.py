@@ -27,6 +27,11 @@ class Network:
     # False -- or settings that call does not cover (data_generator.device_path_covers) -- takes the host-array path through the
     # generators' flow(); both paths make the same NumPy draws and the same sample.
     device_augmentation = True
+    # Label maps of pages the whole-page path cannot take -- a bf16 engine's 4 GiB guard, a page whose activation tensors do not fit
+    # the device's free memory -- come from tiles (Engine.set_tiling): the same map, so nothing shows in the output.  "off": such
+    # pages are refused as before; "always": every page in tiles.  Read when the engine is created.  predict_single_data asks for
+    # logits and probabilities and is not affected.
+    tiling = "auto"
 
     def __init__(self,
                  type: str,
@@ -104,6 +109,8 @@ class Network:
         else:
             raise Exception("exact must be True (float32), 'labels' (bf16 + float32 referee) or False (bf16)")
         self.model = _eng.Engine(Architecture(self.architecture).model(), n_classes, in_channels=in_ch, device=device, mode=mode)
+        if self.tiling != "off":
+            self.model.set_tiling(self.tiling)
         if file_w is not None:
             self._set_file_weights(path, file_w)
         else:

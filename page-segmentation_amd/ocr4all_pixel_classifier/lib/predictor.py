@@ -162,6 +162,12 @@ class Predictor:
         output.output_data(output_dir, np.asarray(pred), data, self.settings.color_map, level=level)
         return paths
 
+    def _list_takes(self, shape):
+        """Whether the page-list entries take a page of this shape: they run whole pages only, so a page the whole-page path would
+        refuse (Engine.page_fits) goes through write_masks, which tiles it.  A model object without page_fits refuses none."""
+        fits = getattr(self.network.model, "page_fits", None)
+        return True if fits is None else fits(int(shape[0]), int(shape[1]))
+
     #: what write_masks_dataset(mixed=None) does with a chunk whose pages differ in shape: True = units by canvas
     #: (Engine.predict_chain_pages(mixed=True)); see DESIGN.md 5c for the measurement this default rests on
     MIXED_DEFAULT = True
@@ -171,7 +177,8 @@ class Predictor:
         chunk_pages at a time (Engine.predict_chain_pages: units of same-shape pages, uploads, encoder and downloads of neighbouring
         units overlapped); each PNG stream is written to its file as it arrives.  Same files, names and bytes as write_masks.  Pages
         the device path cannot take -- other extensions than ".png", output.DEVICE_PNG = False, a foreign post-processor, more than
-        256 classes, no binarisation where one is needed -- go through write_masks, in place.  Yields the three paths per page, in
+        256 classes, no binarisation where one is needed, a page the whole-page path would refuse (write_masks predicts it in
+        tiles) -- go through write_masks, in place.  Yields the three paths per page, in
         dataset order.  mixed: True forms the units from the pages of one canvas whatever their shapes (chain_units_mixed; same
         bytes), False from runs of same-shape pages; None: MIXED_DEFAULT where the device pages of a chunk have more than one
         distinct (H, W, final H, final W) -- a one-shape chunk always takes the same-shape path."""
@@ -191,6 +198,8 @@ class Predictor:
                 p = output.output_paths(output_dir, data)
                 paths.append(p)
                 inputs.append(self._chain_inputs(data, "png", record=False) if output.DEVICE_PNG and output.is_png_target(p[0]) else None)
+                if inputs[-1] is not None and not self._list_takes(np.shape(inputs[-1][1])[:2]):
+                    inputs[-1] = None
             on_device = [k for k, got in enumerate(inputs) if got is not None]
             if on_device:
                 def to_file(page, name, stream, paths=paths, on_device=on_device):
@@ -223,7 +232,8 @@ class Predictor:
         DatasetLoader, read for target_line_height and max_width.  While the device call of one chunk runs, decode_threads threads
         decode the files of the next one (dataset._imread_gray; the call releases the GIL).  Entries the scan chain cannot take -- a
         pre-loaded entry.image, a max_width that brings the second stage, another extension than ".png", output.DEVICE_PNG = False,
-        a foreign post-processor, an rgb network, more than 256 classes -- go through loader.load_images + write_masks, in place;
+        a foreign post-processor, an rgb network, more than 256 classes, a page the whole-page path would refuse -- go through
+        loader.load_images + write_masks, in place;
         the others are not modified.  Yields the three paths per entry, in order; a file that cannot be decoded raises when its
         entry is reached, after the paths of the entries in front of it."""
         from concurrent.futures import ThreadPoolExecutor
@@ -266,7 +276,8 @@ class Predictor:
                         break
                     scale = loader.target_line_height / chunk[k].line_height_px
                     # (the max_width stage shows only once the scan's shape is known)
-                    if loader.max_width is None or loader.max_width / _eng.rescale_shape(scan.shape, scale)[1] >= 1.0:
+                    page_shape = _eng.rescale_shape(scan.shape, scale)
+                    if (loader.max_width is None or loader.max_width / page_shape[1] >= 1.0) and self._list_takes(page_shape):
                         scans[k] = (scan, scale)
                 stop = len(chunk) if failed is None else failed[0]
                 on_device = [k for k in range(stop) if scans[k] is not None]

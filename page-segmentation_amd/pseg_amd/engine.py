@@ -34,6 +34,7 @@ EXPORTED_SYMBOLS = (
     "pseg_rescale_shape", "pseg_gaussian_kernel", "pseg_resize_nearest", "pseg_resize_nearest_device", "pseg_scale_image",
     "pseg_prepare_images", "pseg_affine_warp", "pseg_affine_warp_fill", "pseg_brightness_shift",
     "pseg_eval_confusion", "pseg_cc_label", "pseg_cc_tables",
+    "pseg_tile_plan", "pseg_predict_tiled_device", "pseg_predict_tiled", "pseg_engine_set_tiling", "pseg_engine_page_fits",
 )
 
 
@@ -172,6 +173,11 @@ def lib():
     L.pseg_chain_units_mixed.argtypes = [i, vp, vp, i, vp, vp, vp, i]
     L.pseg_prepare_scans.argtypes = [i, i, c.POINTER(SCAN), vp, vp, vp]
     L.pseg_predict_chain_scans_png.argtypes = [vp, i, c.POINTER(SCAN), c.POINTER(i), i, c.c_uint, vp, i, i, c.c_uint, i, CHAIN_SINK, vp]
+    L.pseg_tile_plan.argtypes = [i, i, i, i, c.POINTER(i), c.POINTER(i), vp, vp, vp, i]
+    L.pseg_predict_tiled_device.argtypes = [vp, vp, i, i, i, vp, vp, vp]
+    L.pseg_predict_tiled.argtypes = [vp, vp, i, i, i, vp, vp]
+    L.pseg_engine_set_tiling.argtypes = [vp, i, i]
+    L.pseg_engine_page_fits.argtypes = [vp, i, i]
     _LIB = L
     return L
 
@@ -382,6 +388,47 @@ class Engine:
     def trim(self):
         """Frees the activation tensors (every page slot); the next predict call allocates what it needs (pseg_engine_trim)."""
         _check(lib().pseg_engine_trim(self._h))
+
+    # -- tiled prediction (pseg_tile_plan's plan; include/pseg.h) -----------------------------------
+    TILING = {"off": 0, "auto": 1, "always": 2}
+
+    def set_tiling(self, mode, tile=0):
+        """Where predict / predict_device / predict_chain use tiles when label maps alone are asked for (pseg_engine_set_tiling):
+        "off" (the default: never), "auto" (the pages the whole-page path refuses or has no memory for) or "always"; tile: the
+        tile edge, 0 = the default.  The label maps are the whole page's, so the route does not show in the output."""
+        if mode not in self.TILING and mode not in self.TILING.values():
+            raise PsegError("tiling mode %r (one of %r)" % (mode, tuple(self.TILING)))
+        _check(lib().pseg_engine_set_tiling(self._h, int(self.TILING.get(mode, mode)), int(tile)))
+
+    def page_fits(self, H, W):
+        """True when the whole-page path takes an H x W page on this engine now (pseg_engine_page_fits); False: the pages that
+        tiling mode "auto" tiles and the page-list entries refuse."""
+        rc = lib().pseg_engine_page_fits(self._h, int(H), int(W))
+        _check(min(rc, 0))
+        return rc == 1
+
+    def predict_tiled(self, image, tile=0, dtype=np.int64):
+        """uint8 (H,W) [or (H,W,3)] page of any size -> its label map, computed in tiles of edge `tile` (0: the default) through
+        the page-slot path (pseg_predict_tiled): equal to predict(...)[2] wherever the whole page can run."""
+        img = np.ascontiguousarray(image, dtype=np.uint8)
+        if img.ndim == 3 and img.shape[2] == 1:
+            img = img[..., 0]
+        if img.ndim != (2 if self.in_channels == 1 else 3):
+            raise PsegError("image of shape %r does not match in_channels=%d" % (img.shape, self.in_channels))
+        H, W = img.shape[:2]
+        out = np.empty((H, W), dtype)
+        if np.dtype(dtype) == np.int64:
+            _check(lib().pseg_predict_tiled(self._h, _ptr(img), H, W, int(tile), _ptr(out), None))
+        elif np.dtype(dtype) == np.uint8:
+            _check(lib().pseg_predict_tiled(self._h, _ptr(img), H, W, int(tile), None, _ptr(out)))
+        else:
+            raise PsegError("labels dtype must be int64 or uint8")
+        return out
+
+    def predict_tiled_device(self, d_img, H, W, tile=0, d_labels=0, d_labels_u8=0, stream=0):
+        """Raw device pointers (ints); asynchronous (pseg_predict_tiled_device)."""
+        _check(lib().pseg_predict_tiled_device(self._h, ctypes.c_void_p(d_img), int(H), int(W), int(tile), ctypes.c_void_p(d_labels or None),
+                                               ctypes.c_void_p(d_labels_u8 or None), ctypes.c_void_p(stream or None)))
 
     def predict_margin_device(self, d_img, H, W, d_margin, d_labels_u8=0, stream=0):
         """As predict_device, plus the float32 (H,W) margin map: top-1 minus top-2 logit per pixel."""
@@ -1038,6 +1085,20 @@ def chain_units_mixed(shapes, cap=8):
     nu = lib().pseg_chain_units_mixed(n, H, W, int(cap), order, first, count, n)
     _check(min(nu, 0))
     return [order[k] for k in range(n)], [(first[u], count[u]) for u in range(nu)]
+
+
+def tile_plan(arch, shape, tile=0):
+    """The tiles pseg_predict_tiled_device cuts an (H, W) page into (pseg_tile_plan; host arithmetic, no GPU):
+    ((tile_h, tile_w), [(y, x), ...] origins on the page's canvas, [(y0, y1, x0, x1), ...] the owned rectangles, half-open).
+    arch: a graph name or id; tile: the tile edge, 0 = the default."""
+    arch_id = ARCH_IDS[arch] if isinstance(arch, str) else int(arch)
+    H, W = int(shape[0]), int(shape[1])
+    th, tw = ctypes.c_int(), ctypes.c_int()
+    n = lib().pseg_tile_plan(arch_id, H, W, int(tile), ctypes.byref(th), ctypes.byref(tw), None, None, None, 0)
+    _check(min(n, 0))
+    oy, ox, own = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros((n, 4), np.int32)
+    _check(min(lib().pseg_tile_plan(arch_id, H, W, int(tile), ctypes.byref(th), ctypes.byref(tw), _ptr(oy), _ptr(ox), _ptr(own), n), 0))
+    return (th.value, tw.value), [(int(a), int(b)) for a, b in zip(oy, ox)], [tuple(int(v) for v in r) for r in own]
 
 
 def brightness_shift(x, brightness, device=0):
