@@ -520,6 +520,30 @@ int pseg_png_code_lengths(const uint32_t* counts, int n, int limit, uint8_t* len
 int pseg_otsu_char_height(int device, const uint8_t* gray, int H, int W, int inverse,
                           int* height, int* otsu);
 
+/* compute_char_height (lib/image_ops.py:58-82) for a list of scans in one device-resident call: heights[i] and otsu[i] (may be
+ * NULL) are what pseg_otsu_char_height returns for gray[i] (H[i] x W[i], dense), for every input; a height of -1 means that no
+ * component qualifies.  Host pointers, synchronous.  No label image and no component list: per scan a histogram launch, the Otsu
+ * loop on the device, and a launch that labels a window around every 32 x 64 tile in LDS and bins the heights of the glyph-shaped
+ * components (lib/image_ops.py:70-76) whose first pixel the tile owns; the upper median (lib/image_ops.py:77-82) is taken from 49
+ * bins on the host.  The list is cut into GROUPS in list order: a group ends after 64 scans, or before the scan that would bring
+ * its bytes above 64 MiB (a larger scan is a group of its own).  A group costs three launches and ONE host wait, for its records;
+ * nothing is allocated per scan.  The workspace -- the group's scan bytes, 1280 bytes of record and 32 bytes of table per scan -- is
+ * grow-only, cached per device and freed by pseg_release_workspace.
+ * n == 0 returns PSEG_OK before a device is touched.  Every scan is checked before any device work and the message names it
+ * ("scan 3: ..."): a NULL pointer or an empty shape is PSEG_EINVAL, H * W > 0x7fffffff PSEG_EUNSUPPORTED; nothing is written to
+ * heights / otsu then, nor on any other error. */
+int pseg_char_heights(int device, int n, const uint8_t* const* gray, const int* H, const int* W, int inverse,
+                      int* heights, int* otsu);
+/* The geometry that call's window kernel was compiled with (host arithmetic, no device; every pointer may be NULL): the owned
+ * tile and the rows / columns of the scan a workgroup labels around it.  The glyph filter of lib/image_ops.py:72-76 admits boxes
+ * of at most 59 rows and 49 columns, so with below >= 59, left >= 49, right >= 49 and above >= 1 a window decides exactly which
+ * components with their first pixel in its tile qualify. */
+int pseg_char_height_window(int* tile_h, int* tile_w, int* above, int* below, int* left, int* right);
+/* The upper median of lib/image_ops.py:77-82 from height bins, as pseg_char_heights takes it (host arithmetic): bins[k] components
+ * of height first + k; *height = the smallest height whose cumulative count exceeds n / 2 (integer division; sorted(hs)[len(hs) / 2]),
+ * -1 when all bins are empty. */
+int pseg_char_height_median(const uint32_t* bins, int n_bins, int first, int* height);
+
 /* ---- Line-height normalisation: lib/dataset.py:114-150, lib/util.py:21-29 ------------------ */
 
 /* Output shape of skimage.transform.rescale as scale_binary calls it (lib/dataset.py:115):

@@ -372,6 +372,41 @@ size_t bn_saved_bytes(int C);
 // Dropout mask of element i under `key`: keep iff hash(i, key) >= rate (inverted dropout, kept values * 1/(1-rate))
 void launch_dropout(float* x, size_t n, uint32_t key, float rate, hipStream_t st);
 int ccl_roots(const uint8_t* d_bin, int* d_L, int H, int W, int connectivity, hipStream_t st);   // pseg_post.hip
+// cv2 getThreshVal_Otsu_8u restated (OpenCV 4.5.5 modules/imgproc/src/thresh.cpp, published algorithm): first maximum of
+// q1*q2*(mu1-mu2)^2, double precision.  One body for the host (pseg_otsu_char_height) and the device (otsu_kernel of
+// pseg_lineheight.hip): every source is built with -ffp-contract=off, so both give the same bits.
+__host__ __device__ inline int otsu_from_hist(const unsigned* h, int64_t n) {
+    const double scale = 1.0 / (double)n;
+    double mu = 0;
+    for (int i = 0; i < 256; ++i) mu += i * (double)h[i];
+    mu *= scale;
+    double mu1 = 0, q1 = 0, max_sigma = 0;
+    int max_val = 0;
+    const double eps = 1.1920928955078125e-07;  // FLT_EPSILON
+    for (int i = 0; i < 256; ++i) {
+        const double p_i = h[i] * scale;
+        mu1 *= q1;
+        q1 += p_i;
+        const double q2 = 1.0 - q1;
+        const double lo = q2 < q1 ? q2 : q1, hi = q1 < q2 ? q2 : q1;   // std::min / std::max
+        if (lo < eps || hi > 1.0 - eps) continue;
+        mu1 = (mu1 + i * p_i) / q1;
+        const double mu2 = (mu - q1 * mu1) / q2;
+        const double sigma = q1 * q2 * (mu1 - mu2) * (mu1 - mu2);
+        if (sigma > max_sigma) { max_sigma = sigma; max_val = i; }
+    }
+    return max_val;
+}
+// The glyph filter of compute_char_height (lib/image_ops.py:70-76), the one place its six constants live: a component counts when
+// GLYPH_H_LO < h < GLYPH_H_HI, GLYPH_W_LO < w < GLYPH_W_HI and GLYPH_AR_LO < w / h < GLYPH_AR_HI (h, w: extents of its bounding box).
+constexpr int GLYPH_H_LO = 10, GLYPH_H_HI = 60, GLYPH_W_LO = 5, GLYPH_W_HI = 50;
+constexpr double GLYPH_AR_LO = 0.5, GLYPH_AR_HI = 2;
+__host__ __device__ inline bool glyph_shaped(int h, int w) {
+    if (!(GLYPH_H_LO < h && h < GLYPH_H_HI && GLYPH_W_LO < w && w < GLYPH_W_HI)) return false;
+    const double ar = (double)w / (double)h;
+    return GLYPH_AR_LO < ar && ar < GLYPH_AR_HI;
+}
+void char_heights_release_workspace(int dev);   // pseg_lineheight.hip: the list entry's per-device workspace (pseg_release_workspace)
 void png_release_workspace(int dev);   // pseg_png.hip: the encoder's per-device workspace (pseg_release_workspace)
 // pseg_png.hip, for the page chain: the masks of `pages` label maps of one shape as PNG streams in one set of launches, enqueued on
 // `st` without a wait; the workspace (PngPages::bytes, from png_pages_layout) is the caller's.  Page p's sizes: ((u64*)d_ws)[4 p + k];

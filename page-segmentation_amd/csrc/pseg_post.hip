@@ -1060,29 +1060,7 @@ __global__ void binarize_kernel(const uint8_t* img, int n, int t, int inverse, u
     }
 }
 
-// cv2 getThreshVal_Otsu_8u restated (OpenCV 4.5.5 modules/imgproc/src/thresh.cpp, published
-// algorithm): first maximum of q1*q2*(mu1-mu2)^2, double precision.
-static int otsu_from_hist(const unsigned* h, int64_t n) {
-    const double scale = 1.0 / (double)n;
-    double mu = 0;
-    for (int i = 0; i < 256; ++i) mu += i * (double)h[i];
-    mu *= scale;
-    double mu1 = 0, q1 = 0, max_sigma = 0;
-    int max_val = 0;
-    const double eps = 1.1920928955078125e-07;  // FLT_EPSILON
-    for (int i = 0; i < 256; ++i) {
-        const double p_i = h[i] * scale;
-        mu1 *= q1;
-        q1 += p_i;
-        const double q2 = 1.0 - q1;
-        if (std::min(q1, q2) < eps || std::max(q1, q2) > 1.0 - eps) continue;
-        mu1 = (mu1 + i * p_i) / q1;
-        const double mu2 = (mu - q1 * mu1) / q2;
-        const double sigma = q1 * q2 * (mu1 - mu2) * (mu1 - mu2);
-        if (sigma > max_sigma) { max_sigma = sigma; max_val = i; }
-    }
-    return max_val;
-}
+// (otsu_from_hist: pseg_common.h, shared with the list entry's device launch in pseg_lineheight.hip)
 
 }  // namespace pseg
 
@@ -1118,6 +1096,7 @@ int pseg_cc_vote_device_u8(int device, uint8_t* d_pred, const uint8_t* d_binary,
 int pseg_release_workspace(int device) {
     PSEG_TRY(set_dev(device));
     png_release_workspace(device);
+    char_heights_release_workspace(device);
     return release_workspace(device);
 }
 
@@ -1321,8 +1300,7 @@ int pseg_otsu_char_height(int device, const uint8_t* gray, int H, int W, int inv
     std::vector<int> hs;
     for (auto& c : comps) {
         const int w = c.x1 - c.x0 + 1, h = c.y1 - c.y0 + 1;
-        const double ar = (double)w / (double)h;
-        if (0.5 < ar && ar < 2 && 10 < h && h < 60 && 5 < w && w < 50) hs.push_back(h);
+        if (glyph_shaped(h, w)) hs.push_back(h);
     }
     if (hs.empty()) { *height = -1; return PSEG_OK; }
     std::sort(hs.begin(), hs.end());

@@ -1,6 +1,7 @@
 """compute_char_height (reference: lib/image_ops.py:58-82) on the GPU: Otsu histogram,
 binarise, union-find CCL, bounding boxes; the glyph filter and the upper median run on the host
-over the component list."""
+over the component list.  compute_char_heights is its list form: one device-resident call per
+chunk of files, the heights binned on the device."""
 import os
 
 import numpy as np
@@ -15,6 +16,33 @@ def compute_char_height(file_name: str, inverse: bool):
     gray = np.asarray(Image.open(file_name).convert("L"))
     height, _ = engine.otsu_char_height(gray, inverse)
     return height
+
+
+def compute_char_heights(file_names, inverse: bool, decode_threads=2, chunk_files=64):
+    """compute_char_height for a list of files: the same heights (None where no component qualifies), the files decoded on
+    decode_threads threads chunk_files at a time and every chunk measured in ONE device call (engine.char_heights: no label
+    image, no component list, one wait per group of scans).  While the device call of one chunk runs, the next chunk is being
+    decoded.  A missing file raises compute_char_height's exception before anything is decoded."""
+    from concurrent.futures import ThreadPoolExecutor
+    file_names = list(file_names)
+    for file_name in file_names:
+        if not os.path.exists(file_name):
+            raise Exception(f"File does not exist at {file_name}")
+    from PIL import Image
+
+    def decode(file_name):
+        return np.ascontiguousarray(Image.open(file_name).convert("L"), dtype=np.uint8)
+
+    step, out = max(1, int(chunk_files)), []
+    with ThreadPoolExecutor(max(1, int(decode_threads))) as pool:
+        start = lambda i: [pool.submit(decode, f) for f in file_names[i:i + step]]
+        ahead = start(0) if file_names else None
+        for i in range(0, len(file_names), step):
+            pending = ahead
+            scans = [fut.result() for fut in pending]
+            ahead = start(i + step) if i + step < len(file_names) else None
+            out += engine.char_heights(scans, inverse)[0]
+    return out
 
 
 def _fg_counts(pred, mask, bin, n_classes):

@@ -235,7 +235,12 @@ class Predictor:
         a foreign post-processor, an rgb network, more than 256 classes, a page the whole-page path would refuse -- go through
         loader.load_images + write_masks, in place;
         the others are not modified.  Yields the three paths per entry, in order; a file that cannot be decoded raises when its
-        entry is reached, after the paths of the entries in front of it."""
+        entry is reached, after the paths of the entries in front of it.
+        An entry whose line_height_px is None is measured here: once a chunk's files are decoded, the scans of such entries go
+        through engine.char_heights(inverse=False) in ONE device call (compute_char_height's value, without a second decode), and
+        the height is stored into entry.line_height_px -- the entry is modified, as the reference's loader modifies its records.
+        It gives the scale on both routes, the scan chain and the fallback.  A scan without a measurable height (no glyph-shaped
+        component) raises Exception naming the file when its entry is reached, as a file that cannot be decoded does."""
         from concurrent.futures import ThreadPoolExecutor
         from pseg_amd import engine as _eng
         from . import dataset as _ds
@@ -259,21 +264,36 @@ class Predictor:
                 """Chunk i's paths and the decodes of its device candidates, in flight."""
                 chunk = entries[i:i + step]
                 paths = [output.output_paths(output_dir, e) for e in chunk]
-                return chunk, paths, [pool.submit(decode, e) if self._scan_route(e, p[0]) else None for e, p in zip(chunk, paths)]
+                return chunk, paths, [pool.submit(decode, e) if self._scan_route(e, p[0]) or (e.line_height_px is None and e.image_path is not None)
+                                      else None for e, p in zip(chunk, paths)]
 
             ahead = start(0) if entries else None
             for i in range(0, len(entries), step):
                 chunk, paths, pending = ahead
                 ahead = start(i + step) if i + step < len(entries) else None
                 scans, failed = [None] * len(chunk), None
+                decoded = [None] * len(chunk)
                 for k, fut in enumerate(pending):
                     if fut is None:
                         continue
                     try:
-                        scan = fut.result()
+                        decoded[k] = fut.result()
                     except BaseException as exc:
                         failed = (k, exc)
                         break
+                # the entries without a line height: one device call over the chunk's scans (a pre-loaded image is measured as it is)
+                unmeasured = [k for k in range(len(chunk) if failed is None else failed[0]) if chunk[k].line_height_px is None]
+                if unmeasured:
+                    grays = [decoded[k] if decoded[k] is not None else np.ascontiguousarray(chunk[k].image, dtype=np.uint8) for k in unmeasured]
+                    for k, h in zip(unmeasured, _eng.char_heights(grays, inverse=False)[0]):
+                        if h is None:
+                            if failed is None or k < failed[0]:
+                                failed = (k, Exception(f"No line height could be measured in {chunk[k].image_path}"))
+                        else:
+                            chunk[k].line_height_px = h
+                for k, scan in enumerate(decoded):
+                    if scan is None or (failed is not None and k >= failed[0]) or not self._scan_route(chunk[k], paths[k][0]):
+                        continue
                     scale = loader.target_line_height / chunk[k].line_height_px
                     # (the max_width stage shows only once the scan's shape is known)
                     page_shape = _eng.rescale_shape(scan.shape, scale)

@@ -26,7 +26,7 @@ EXPORTED_SYMBOLS = (
     "pseg_allreduce_unique_id", "pseg_allreduce_init", "pseg_train_allreduce", "pseg_allreduce_destroy",
     "pseg_cc_vote", "pseg_cc_vote_device", "pseg_cc_vote_device_u8", "pseg_release_workspace", "pseg_bbox_fill",
     "pseg_masks", "pseg_masks_device", "pseg_masks_device_u8", "pseg_bbox_fill_device_u8",
-    "pseg_otsu_char_height",
+    "pseg_otsu_char_height", "pseg_char_heights", "pseg_char_height_window", "pseg_char_height_median",
     "pseg_png_bound", "pseg_png_encode_device", "pseg_masks_png_device_u8", "pseg_png_encode", "pseg_masks_png", "pseg_predict_chain_png",
     "pseg_png_bound_lv", "pseg_png_encode_device_lv", "pseg_masks_png_device_u8_lv", "pseg_png_encode_lv", "pseg_masks_png_lv",
     "pseg_predict_chain_png_lv", "pseg_png_code_lengths", "pseg_predict_chain_pages_png", "pseg_chain_units",
@@ -151,6 +151,9 @@ def lib():
     L.pseg_masks.argtypes = [i, vp, vp, vp, i, i, i, vp, vp, vp, vp]
     L.pseg_masks_device.argtypes = [i, vp, vp, vp, i, i, i, vp, vp, vp, vp, vp]
     L.pseg_otsu_char_height.argtypes = [i, vp, i, i, i, c.POINTER(i), c.POINTER(i)]
+    L.pseg_char_heights.argtypes = [i, i, vp, vp, vp, i, vp, vp]
+    L.pseg_char_height_window.argtypes = [c.POINTER(i)] * 6
+    L.pseg_char_height_median.argtypes = [vp, i, i, c.POINTER(i)]
     sz = c.c_size_t
     L.pseg_png_bound.argtypes = [i, i, i, i]
     L.pseg_png_bound.restype = sz
@@ -904,6 +907,41 @@ def otsu_char_height(gray, inverse=False, device=0):
     _check(lib().pseg_otsu_char_height(int(device), _ptr(g), H, W, int(bool(inverse)),
                                        ctypes.byref(h), ctypes.byref(t)))
     return (None if h.value < 0 else h.value), t.value
+
+
+def char_heights(scans, inverse=False, device=0):
+    """otsu_char_height for a list of gray scans in one device-resident call (pseg_char_heights): -> (heights, thresholds), two
+    lists; heights[i] is an int or None.  The library cuts the list into groups of at most 64 scans / 64 MiB, three launches and
+    one wait each."""
+    gs = [np.ascontiguousarray(g, dtype=np.uint8) for g in scans]
+    for k, g in enumerate(gs):
+        if g.ndim != 2:
+            raise PsegError("scan %d: an (H,W) gray array is expected, got shape %r" % (k, g.shape))
+    n = len(gs)
+    if n == 0:
+        _check(lib().pseg_char_heights(int(device), 0, None, None, None, int(bool(inverse)), None, None))
+        return [], []
+    ptrs = (ctypes.c_void_p * n)(*[g.ctypes.data for g in gs])
+    Hs = (ctypes.c_int * n)(*[g.shape[0] for g in gs])
+    Ws = (ctypes.c_int * n)(*[g.shape[1] for g in gs])
+    hs, ts = (ctypes.c_int * n)(), (ctypes.c_int * n)()
+    _check(lib().pseg_char_heights(int(device), n, ptrs, Hs, Ws, int(bool(inverse)), hs, ts))
+    return [None if h < 0 else int(h) for h in hs], [int(t) for t in ts]
+
+
+def char_height_window():
+    """(tile_h, tile_w, above, below, left, right) of pseg_char_heights' window kernel (pseg_char_height_window; no device)."""
+    v = [ctypes.c_int() for _ in range(6)]
+    _check(lib().pseg_char_height_window(*[ctypes.byref(x) for x in v]))
+    return tuple(x.value for x in v)
+
+
+def char_height_median(bins, first):
+    """The upper median pseg_char_heights takes from its height bins (bins[k]: components of height first + k), or None."""
+    b = np.ascontiguousarray(bins, dtype=np.uint32)
+    h = ctypes.c_int()
+    _check(lib().pseg_char_height_median(_ptr(b), int(b.size), int(first), ctypes.byref(h)))
+    return None if h.value < 0 else h.value
 
 
 # ---- line-height normalisation (lib/dataset.py:114-150, lib/util.py:21-29) --------------------------
