@@ -544,6 +544,34 @@ int pseg_char_height_window(int* tile_h, int* tile_w, int* above, int* below, in
  * -1 when all bins are empty. */
 int pseg_char_height_median(const uint32_t* bins, int n_bins, int first, int* height);
 
+/* ---- PNG scans decoded on the device ---------------------------------------- */
+
+/* The container of a PNG file held in memory (host arithmetic, no device): signature, IHDR first with length 13, the CRC of every
+ * critical chunk, consecutive IDAT chunks (any of them may be empty), IEND.  Ancillary chunks are skipped unread, except tRNS.
+ * *H, *W, *channels (each may be NULL) are set whenever IHDR could be read, else 0.  Returns PSEG_OK for what the decoder takes: bit
+ * depth 8, colour type 0 (gray) or 2 (RGB), no interlace, no tRNS, H * (1 + W * channels) <= 0x7fffffff; PSEG_EUNSUPPORTED for every
+ * other sound PNG (1/2/4/16 bit, palette, alpha, Adam7, tRNS, a critical chunk it does not know); PSEG_EINVAL for a broken
+ * container.  No message is set: the value is a classification, not a failure of the call. */
+int pseg_png_probe(const uint8_t* file, size_t n_bytes, int* H, int* W, int* channels);
+/* n PNG files held in memory -> their gray scans, PIL's Image.open(f).convert("L") (RGB: (R*19595 + G*38470 + B*7471 + 0x8000) >> 16),
+ * inflated and unfiltered on the device.  out[i]: H * W bytes of host memory for file i (shape from pseg_png_probe).  status[i] is
+ * pseg_png_probe's value, or PSEG_EINVAL where the container is sound but the zlib stream is not (bad header, code set, symbol or
+ * distance, wrong length, wrong Adler-32) or a row's filter byte is above 4.  out[i] of a file whose status is not PSEG_OK is left
+ * untouched, and the other files are unaffected.  The call itself fails only on bad arguments (nothing is written then, status
+ * included) or HIP errors.  n == 0 returns PSEG_OK before a device is touched; so does a list without a single sound file.
+ * The sound files are cut into groups in list order: 64 files, or 64 MiB of inflated bytes.  A group is one upload of its IDAT
+ * payloads (copied by the host into page-locked staging), two launches with one workgroup per file, one read-back and ONE host
+ * wait.  The workspace (staging, IDAT and inflated bytes, gray scans, one record per file) is grow-only, cached per device, guarded
+ * by its own lock and used on its own stream: the call may run on one thread while another thread runs an engine entry.
+ * pseg_release_workspace frees it. */
+int pseg_png_decode_gray(int device, int n, const uint8_t* const* files, const size_t* n_bytes, uint8_t* const* out, int* status);
+/* The same with d_out[i] in device memory.  stream: the caller's stream whose enqueued work still uses the outputs (NULL: none); the
+ * decoder's own stream waits for it.  The call returns after its last group's wait: the outputs are complete then. */
+int pseg_png_decode_gray_device(int device, int n, const uint8_t* const* files, const size_t* n_bytes, uint8_t* const* d_out, int* status,
+                                void* stream);
+/* The same decoder run serially on the host, no device: the code the kernels are compiled from (csrc/pseg_pngdec.h). */
+int pseg_png_decode_gray_host(int n, const uint8_t* const* files, const size_t* n_bytes, uint8_t* const* out, int* status);
+
 /* ---- Line-height normalisation: lib/dataset.py:114-150, lib/util.py:21-29 ------------------ */
 
 /* Output shape of skimage.transform.rescale as scale_binary calls it (lib/dataset.py:115):

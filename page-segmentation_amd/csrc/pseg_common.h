@@ -407,6 +407,7 @@ __host__ __device__ inline bool glyph_shaped(int h, int w) {
     return GLYPH_AR_LO < ar && ar < GLYPH_AR_HI;
 }
 void char_heights_release_workspace(int dev);   // pseg_lineheight.hip: the list entry's per-device workspace (pseg_release_workspace)
+void pngdec_release_workspace(int dev);   // pseg_pngdec.hip: the PNG decoder's per-device workspace and stream (pseg_release_workspace)
 void png_release_workspace(int dev);   // pseg_png.hip: the encoder's per-device workspace (pseg_release_workspace)
 // pseg_png.hip, for the page chain: the masks of `pages` label maps of one shape as PNG streams in one set of launches, enqueued on
 // `st` without a wait; the workspace (PngPages::bytes, from png_pages_layout) is the caller's.  Page p's sizes: ((u64*)d_ws)[4 p + k];

@@ -1097,6 +1097,7 @@ int pseg_release_workspace(int device) {
     PSEG_TRY(set_dev(device));
     png_release_workspace(device);
     char_heights_release_workspace(device);
+    pngdec_release_workspace(device);
     return release_workspace(device);
 }
 

@@ -18,11 +18,16 @@ def compute_char_height(file_name: str, inverse: bool):
     return height
 
 
-def compute_char_heights(file_names, inverse: bool, decode_threads=2, chunk_files=64):
+def compute_char_heights(file_names, inverse: bool, decode_threads=2, chunk_files=64, decode="host"):
     """compute_char_height for a list of files: the same heights (None where no component qualifies), the files decoded on
     decode_threads threads chunk_files at a time and every chunk measured in ONE device call (engine.char_heights: no label
     image, no component list, one wait per group of scans).  While the device call of one chunk runs, the next chunk is being
-    decoded.  A missing file raises compute_char_height's exception before anything is decoded."""
+    decoded.  A missing file raises compute_char_height's exception before anything is decoded.
+    decode="device": the pool threads only read the files' bytes and one pool task per chunk decodes them on the device
+    (engine.png_decode_gray: 8-bit gray and RGB PNG files; every other file, and every file the decoder refuses, is read with PIL as
+    under "host", so the heights -- and the exception for a file PIL cannot read -- are the same)."""
+    if decode not in ("host", "device"):
+        raise Exception(f"decode must be 'host' or 'device', got {decode!r}")
     from concurrent.futures import ThreadPoolExecutor
     file_names = list(file_names)
     for file_name in file_names:
@@ -30,16 +35,25 @@ def compute_char_heights(file_names, inverse: bool, decode_threads=2, chunk_file
             raise Exception(f"File does not exist at {file_name}")
     from PIL import Image
 
-    def decode(file_name):
+    def decode_file(file_name):
         return np.ascontiguousarray(Image.open(file_name).convert("L"), dtype=np.uint8)
 
     step, out = max(1, int(chunk_files)), []
     with ThreadPoolExecutor(max(1, int(decode_threads))) as pool:
-        start = lambda i: [pool.submit(decode, f) for f in file_names[i:i + step]]
+        if decode == "device":
+            def chunk_task(names, reads):
+                got = engine.decode_gray_files(names, fallback=decode_file, reads=reads)
+                for g in got:
+                    if isinstance(g, BaseException):
+                        raise g
+                return got
+            start = lambda i: pool.submit(chunk_task, file_names[i:i + step], [pool.submit(engine.read_file_bytes, f) for f in file_names[i:i + step]])
+        else:
+            start = lambda i: [pool.submit(decode_file, f) for f in file_names[i:i + step]]
         ahead = start(0) if file_names else None
         for i in range(0, len(file_names), step):
             pending = ahead
-            scans = [fut.result() for fut in pending]
+            scans = pending.result() if decode == "device" else [fut.result() for fut in pending]
             ahead = start(i + step) if i + step < len(file_names) else None
             out += engine.char_heights(scans, inverse)[0]
     return out

@@ -224,7 +224,7 @@ class Predictor:
         return (entry.image is None and entry.image_path is not None and output.DEVICE_PNG and output.is_png_target(path)
                 and self._chain_ops() is not None and net.n_classes <= 256 and not getattr(net, "_rgb", False))
 
-    def write_masks_scans(self, entries, loader, output_dir=None, level=None, chunk_pages=64, decode_threads=2):
+    def write_masks_scans(self, entries, loader, output_dir=None, level=None, chunk_pages=64, decode_threads=2, decode="host"):
         """loader.load_images + write_masks_dataset for entries that name their scan by image_path, without the normalised page, the
         binarisation or the label map visiting the host: the decoded gray scans go through Engine.predict_chain_scans chunk_pages at
         a time (binarisation and line-height normalisation on the device, then the page chain), and each PNG stream is written to
@@ -240,7 +240,14 @@ class Predictor:
         through engine.char_heights(inverse=False) in ONE device call (compute_char_height's value, without a second decode), and
         the height is stored into entry.line_height_px -- the entry is modified, as the reference's loader modifies its records.
         It gives the scale on both routes, the scan chain and the fallback.  A scan without a measurable height (no glyph-shaped
-        component) raises Exception naming the file when its entry is reached, as a file that cannot be decoded does."""
+        component) raises Exception naming the file when its entry is reached, as a file that cannot be decoded does.
+        decode="device": the pool threads only read the files' bytes, and ONE pool task per chunk decodes them on the device
+        (engine.png_decode_gray, 8-bit gray and RGB PNG files) -- on the decoder's own stream and workspace, while the calling
+        thread runs the chain of the chunk before.  A file the decoder does not take or refuses is read with
+        dataset._imread_gray, as under "host": its array, or its exception when the entry is reached, is PIL's.  Same files and
+        bytes as decode="host"."""
+        if decode not in ("host", "device"):
+            raise Exception(f"decode must be 'host' or 'device', got {decode!r}")
         from concurrent.futures import ThreadPoolExecutor
         from pseg_amd import engine as _eng
         from . import dataset as _ds
@@ -256,16 +263,35 @@ class Predictor:
         names = ("color", "overlay", "inverted")
         high_res = bool(self.settings.high_res_output)
 
-        def decode(entry):
+        def decode_entry(entry):
             return np.ascontiguousarray(_ds._imread_gray(entry.image_path), dtype=np.uint8)
+
+        class _OfChunk:
+            """One file's share of a chunk's decode task, with a future's result()."""
+            def __init__(self, fut, k):
+                self.fut, self.k = fut, k
+
+            def result(self):
+                r = self.fut.result()[self.k]
+                if isinstance(r, BaseException):
+                    raise r
+                return r
+
+        device = getattr(self.network.model, "device", 0)
 
         with ThreadPoolExecutor(max(1, int(decode_threads))) as pool:
             def start(i):
                 """Chunk i's paths and the decodes of its device candidates, in flight."""
                 chunk = entries[i:i + step]
                 paths = [output.output_paths(output_dir, e) for e in chunk]
-                return chunk, paths, [pool.submit(decode, e) if self._scan_route(e, p[0]) or (e.line_height_px is None and e.image_path is not None)
-                                      else None for e, p in zip(chunk, paths)]
+                wanted = [self._scan_route(e, p[0]) or (e.line_height_px is None and e.image_path is not None) for e, p in zip(chunk, paths)]
+                if decode == "device":
+                    ks = [k for k, w in enumerate(wanted) if w]
+                    reads = [pool.submit(_eng.read_file_bytes, chunk[k].image_path) for k in ks]
+                    fut = pool.submit(_eng.decode_gray_files, [chunk[k].image_path for k in ks], device, _ds._imread_gray, reads) if ks else None
+                    slot = {k: j for j, k in enumerate(ks)}
+                    return chunk, paths, [_OfChunk(fut, slot[k]) if w else None for k, w in enumerate(wanted)]
+                return chunk, paths, [pool.submit(decode_entry, e) if w else None for e, w in zip(chunk, wanted)]
 
             ahead = start(0) if entries else None
             for i in range(0, len(entries), step):

@@ -27,6 +27,7 @@ EXPORTED_SYMBOLS = (
     "pseg_cc_vote", "pseg_cc_vote_device", "pseg_cc_vote_device_u8", "pseg_release_workspace", "pseg_bbox_fill",
     "pseg_masks", "pseg_masks_device", "pseg_masks_device_u8", "pseg_bbox_fill_device_u8",
     "pseg_otsu_char_height", "pseg_char_heights", "pseg_char_height_window", "pseg_char_height_median",
+    "pseg_png_probe", "pseg_png_decode_gray", "pseg_png_decode_gray_device", "pseg_png_decode_gray_host",
     "pseg_png_bound", "pseg_png_encode_device", "pseg_masks_png_device_u8", "pseg_png_encode", "pseg_masks_png", "pseg_predict_chain_png",
     "pseg_png_bound_lv", "pseg_png_encode_device_lv", "pseg_masks_png_device_u8_lv", "pseg_png_encode_lv", "pseg_masks_png_lv",
     "pseg_predict_chain_png_lv", "pseg_png_code_lengths", "pseg_predict_chain_pages_png", "pseg_chain_units",
@@ -181,6 +182,10 @@ def lib():
     L.pseg_predict_tiled.argtypes = [vp, vp, i, i, i, vp, vp]
     L.pseg_engine_set_tiling.argtypes = [vp, i, i]
     L.pseg_engine_page_fits.argtypes = [vp, i, i]
+    L.pseg_png_probe.argtypes = [vp, sz, c.POINTER(i), c.POINTER(i), c.POINTER(i)]
+    L.pseg_png_decode_gray.argtypes = [i, i, vp, vp, vp, vp]
+    L.pseg_png_decode_gray_device.argtypes = [i, i, vp, vp, vp, vp, vp]
+    L.pseg_png_decode_gray_host.argtypes = [i, vp, vp, vp, vp]
     _LIB = L
     return L
 
@@ -897,6 +902,87 @@ def masks_png(pred, binary, lut, which=("color", "overlay", "inverted"), band_ro
     bufs, P, caps, sizes = _png_buffers(H, W, 3, band_rows, [m in which for m in MASK_NAMES], level)
     _check(L.pseg_masks_png_lv(int(device), _ptr(p), _ptr(b), _ptr(t), t.shape[0], H, W, int(band_rows), int(level), P, caps, sizes))
     return {m: bufs[k][:sizes[k]].tobytes() for k, m in enumerate(MASK_NAMES) if m in which}
+
+
+# ---- PNG scans decoded on the device (include/pseg.h) ---------------------------------
+
+PNG_OK, PNG_EINVAL, PNG_EUNSUPPORTED = 0, -1, -5      # PSEG_OK, PSEG_EINVAL, PSEG_EUNSUPPORTED: the per-file statuses
+
+
+def _file_ptr(data):
+    """(address, length, keep-alive) of a bytes-like object, without a copy for bytes."""
+    if isinstance(data, bytes):
+        return ctypes.cast(ctypes.c_char_p(data), ctypes.c_void_p).value or 0, len(data), data
+    a = np.frombuffer(data, dtype=np.uint8)
+    return a.ctypes.data, a.size, a
+
+
+def png_probe(data):
+    """(status, H, W, channels) of a PNG file held in memory (pseg_png_probe; no device): PNG_OK for what png_decode_gray decodes
+    (8-bit gray or RGB, no interlace, no tRNS), PNG_EUNSUPPORTED for every other sound PNG, PNG_EINVAL for a broken container.
+    H, W, channels are 0 where no IHDR chunk could be read."""
+    p, n, keep = _file_ptr(data)
+    H, W, ch = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    st = lib().pseg_png_probe(ctypes.c_void_p(p), n, ctypes.byref(H), ctypes.byref(W), ctypes.byref(ch))
+    return int(st), H.value, W.value, ch.value
+
+
+def png_decode_gray(files, device=0, host=False):
+    """The gray scans of PNG files held in memory (bytes), as PIL's Image.open(f).convert("L"): a list of (array, status), the
+    array in pooled page-locked memory, or None where the status is not PNG_OK (PNG_EUNSUPPORTED: a PNG this decoder does not take;
+    PNG_EINVAL: a broken file) -- the other files of the list are unaffected.  Inflate and unfilter run on the device, one workgroup
+    per file, 64 files or 64 MiB a group (pseg_png_decode_gray); host=True runs the same code serially on the host, no device."""
+    files = list(files)
+    n = len(files)
+    L = lib()
+    if n == 0:
+        _check(L.pseg_png_decode_gray_host(0, None, None, None, None) if host else L.pseg_png_decode_gray(int(device), 0, None, None, None, None))
+        return []
+    refs = [_file_ptr(f) for f in files]
+    outs = []
+    for f in files:
+        st, H, W, _ch = png_probe(f)
+        outs.append(None if st != PNG_OK else np.empty((H, W), np.uint8) if host else pinned_empty_pooled((H, W), np.uint8))
+    dummy = np.zeros(1, np.uint8)                    # a refused file's output pointer: never written
+    ptrs = (ctypes.c_void_p * n)(*[r[0] for r in refs])
+    lens = (ctypes.c_size_t * n)(*[r[1] for r in refs])
+    optr = (ctypes.c_void_p * n)(*[(dummy if o is None else o).ctypes.data for o in outs])
+    status = (ctypes.c_int * n)()
+    if host:
+        _check(L.pseg_png_decode_gray_host(n, ptrs, lens, optr, status))
+    else:
+        _check(L.pseg_png_decode_gray(int(device), n, ptrs, lens, optr, status))
+    return [(outs[k] if status[k] == PNG_OK else None, int(status[k])) for k in range(n)]
+
+
+def read_file_bytes(path):
+    with open(path, "rb") as f:
+        return f.read()
+
+
+def decode_gray_files(paths, device=0, fallback=None, reads=None):
+    """The gray scans of the files at `paths` through png_decode_gray: one entry per path, the array, or the exception that
+    `fallback(path)` raised.  A file that cannot be read, and every file whose status is not PNG_OK, goes to fallback(path) (the
+    callers pass their PIL read), so what comes back for such a file is the fallback's array or the fallback's exception.
+    reads: futures of read_file_bytes(path), one per path, submitted to a pool BEFORE the task that runs this function (a pool
+    runs its tasks in order, so the task never waits for a read queued behind it); None: the files are read here."""
+    datas = []
+    for k, path in enumerate(paths):
+        try:
+            datas.append(read_file_bytes(path) if reads is None else reads[k].result())
+        except OSError:
+            datas.append(None)
+    known = [k for k, d in enumerate(datas) if d is not None]
+    out = [None] * len(datas)
+    for k, (arr, st) in zip(known, png_decode_gray([datas[k] for k in known], device=device)):
+        out[k] = arr if st == PNG_OK else None
+    for k, path in enumerate(paths):
+        if out[k] is None:
+            try:
+                out[k] = np.ascontiguousarray(fallback(path), dtype=np.uint8)
+            except BaseException as exc:
+                out[k] = exc
+    return out
 
 
 def otsu_char_height(gray, inverse=False, device=0):
