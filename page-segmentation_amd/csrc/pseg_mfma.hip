@@ -107,6 +107,7 @@ struct MConv {
     float* skip_logits; int skip_CP;   // FL_SKIPLOG: [pixel][skip_CP] f32 logits contribution of this layer's output (it is not stored itself)
     unsigned long long* trace;  // PSEG_TRACE: per-workgroup s_memtime stamps (diagnostic builds only)
     int dbg;   // ablation bits (PSEG_DBG): 1 skip input staging, 2 skip MFMAs, 4 skip epilogue, 8 skip weight DMA
+    int rowreuse;   // the k-chunk table is tap-major with one k-step per tap (checked on the host, MfmaPlan::rowreuse): row-reuse k-loops may run
 };
 
 // single v_max_f32: fmaxf() makes hipcc canonicalise both operands first (3 instructions per max
@@ -226,7 +227,7 @@ enum { FL_POOL = 1, FL_ADD = 2, FL_INRELU = 4, FL_UP0 = 8, FL_UP1 = 16, FL_FUSE1
 // NW_ = waves per workgroup: 4 (two workgroups per CU) or 8 (one workgroup per CU owning all 160 KiB
 // of LDS: a 16-row tile shares one weight stream among twice the pixels -- the mid layers are
 // bound by LDS-DMA bytes per CU).
-template <int MT, int NT, int KS_, int ST_, int SG_, int MODE_, int FL_, int NW_ = 4>
+template <int MT, int NT, int KS_, int ST_, int SG_, int MODE_, int FL_, int NW_ = 4, int RR_ = 0>   // RR_ > 0: row-reuse k-loop for weight groups of RR_ k-steps
 __global__ __launch_bounds__(NW_ * 64) __attribute__((amdgpu_waves_per_eu((MT == 4 && NT == 4 && NW_ == 4 && (KS_ == 5 || KS_ == 3 || KS_ == 2) && (SG_ == 4 || SG_ == 5) && MODE_ == 0) ? 3 : 2))) void conv_mfma_kernel(MConv a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int NW = NW_, NTHR = NW_ * 64;
@@ -632,6 +633,89 @@ __global__ __launch_bounds__(NW_ * 64) __attribute__((amdgpu_waves_per_eu((MT ==
         if (b == 0) { PSEG_STAMP(3) }
 
         const int groups_b = (ks + a.GK - 1) / a.GK;
+        if constexpr (RR_ > 0) {
+            // Row reuse (host: MfmaPlan::rowreuse -- every channel block is 25 k-steps and the table entry of step s + 5 is the entry
+            // of step s plus one tile row; a.GK == RR_): the fragments this wave's UPPER row (m = 2, 3) reads at step s are the ones
+            // its LOWER row (m = 0, 1) needs at step s + 5 -- see conv_pp_kernel.  The block's 25 steps are spelled out, weight
+            // groups and their barriers included, so that every fragment has a static register name across the group barriers:
+            // hi[s] is read once and used at steps s and s + 5, only steps 0-4 read the lower row.  Same group protocol (counted
+            // waits, ring slots), same pipeline inside a group, same operands per accumulator in the same order: the same bits.
+            static_assert(RR_ == 0 || (FIXED && KS_ == 5 && ST_ == 1 && SG_ == 4 && MT == 4 && MODE_ == MODE_CONV && !(FL_ & (FL_INRELU | FL_UP0 | FL_UP1 | FL_FUSE1 | FL_PERSIST))),
+                          "row reuse: k5 stride-1 instances with four chunks per pixel and two rows x two column tiles per wave");
+            constexpr int GKC = RR_;
+            bf16x8 hi[26][2], lo0[5][2], wr[2][NT];
+            int offp[2];
+            const char* wb = nullptr;
+            const int* const tb = tab_l + g;
+            const char* const px0 = in_t + pixbase[0];
+            const char* const px1 = in_t + pixbase[1];
+            const char* const px2 = in_t + pixbase[2];
+            const char* const px3 = in_t + pixbase[3];
+            auto group_begin = [&](int lg) {
+                const int younger = min(D - 1, G - 1 - gq);
+                wait_vmcnt_le(((c_dbg & 8) || lg == 0) ? 0 : L * (younger > 0 ? younger : 0));
+                lds_barrier();
+                if (b == 0 && lg == 0) { PSEG_STAMP(4) }
+                if (gq + D < G) stage_w(gq + D, slot_n);
+                slot_n = slot_n + 1 == a.NB ? 0 : slot_n + 1;
+                wb = w_t + slot_c * WBUF + lane * 16;
+                slot_c = slot_c + 1 == a.NB ? 0 : slot_c + 1;
+                ++gq;
+            };
+#define RR_LOAD(S, OFF)                                                                          \
+            {                                                                                    \
+                constexpr int sg_ = (S) % GKC;                                                   \
+                wr[(S) & 1][0] = *(const bf16x8*)(wb + (sg_ * NT) * 1024);                       \
+                if constexpr ((S) < 5) {                                                         \
+                    lo0[(S) % 5][0] = *(const bf16x8*)(px0 + OFF);                               \
+                    lo0[(S) % 5][1] = *(const bf16x8*)(px1 + OFF);                               \
+                }                                                                                \
+                hi[S][0] = *(const bf16x8*)(px2 + OFF);                                          \
+                hi[S][1] = *(const bf16x8*)(px3 + OFF);                                          \
+                _Pragma("unroll") for (int t = 1; t < NT; ++t)                                   \
+                    wr[(S) & 1][t] = *(const bf16x8*)(wb + (sg_ * NT + t) * 1024);               \
+            }
+#define RR_MMA(S)                                                                                \
+            _Pragma("unroll") for (int t = 0; t < NT; ++t) {                                     \
+                acc[0][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wr[(S) & 1][t], (S) < 5 ? lo0[(S) % 5][0] : hi[(S) < 5 ? 0 : (S) - 5][0], acc[0][t], 0, 0, 0); \
+                acc[1][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wr[(S) & 1][t], (S) < 5 ? lo0[(S) % 5][1] : hi[(S) < 5 ? 0 : (S) - 5][1], acc[1][t], 0, 0, 0); \
+                acc[2][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wr[(S) & 1][t], hi[S][0], acc[2][t], 0, 0, 0); \
+                acc[3][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wr[(S) & 1][t], hi[S][1], acc[3][t], 0, 0, 0); \
+            }
+            // step S: first of its weight group -> the group protocol, then its own reads (the pipeline starts over behind every
+            // group barrier, as in the loop below); not the group's last -> the next step's reads between this step's MFMAs
+#define RR_STEP(S)                                                                               \
+            {                                                                                    \
+                constexpr bool first_ = (S) % GKC == 0, last_ = (S) % GKC == GKC - 1 || (S) == 24; \
+                if constexpr (first_) {                                                          \
+                    group_begin((S) / GKC);                                                      \
+                    offp[(S) & 1] = tb[(S) * 4];                                                 \
+                    if constexpr (!last_) offp[((S) + 1) & 1] = tb[((S) + 1) * 4];               \
+                    RR_LOAD(S, offp[(S) & 1])                                                    \
+                }                                                                                \
+                __builtin_amdgcn_sched_barrier(0);                                               \
+                if constexpr (!last_) {                                                          \
+                    if constexpr (((S) + 1) % GKC != GKC - 1 && (S) + 1 != 24) offp[(S) & 1] = tb[((S) + 2) * 4]; \
+                    RR_LOAD((S) + 1, offp[((S) + 1) & 1])                                        \
+                    RR_MMA(S)                                                                    \
+                    _Pragma("unroll") for (int q_ = 0; q_ < MT * NT; ++q_) {                      \
+                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                        \
+                        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                        \
+                        __builtin_amdgcn_sched_group_barrier(0x002, 1, 0);                        \
+                    }                                                                            \
+                } else {                                                                         \
+                    RR_MMA(S)                                                                    \
+                }                                                                                \
+            }
+            RR_STEP(0) RR_STEP(1) RR_STEP(2) RR_STEP(3) RR_STEP(4)
+            RR_STEP(5) RR_STEP(6) RR_STEP(7) RR_STEP(8) RR_STEP(9)
+            RR_STEP(10) RR_STEP(11) RR_STEP(12) RR_STEP(13) RR_STEP(14)
+            RR_STEP(15) RR_STEP(16) RR_STEP(17) RR_STEP(18) RR_STEP(19)
+            RR_STEP(20) RR_STEP(21) RR_STEP(22) RR_STEP(23) RR_STEP(24)
+#undef RR_STEP
+#undef RR_MMA
+#undef RR_LOAD
+        } else
         for (int lg = 0; lg < groups_b; ++lg, ++gq) {
             // group gq has landed once at most the loads of the younger groups are pending
             const int younger = min(D - 1, G - 1 - gq);
@@ -2458,8 +2542,9 @@ __global__ __launch_bounds__(256) void logits_bf16_kernel(const uint16_t* src0, 
 // the empty rows read a zero slot): conv4's weights 96 -> 80 KB, which is what lets two 35 KB tiles fit.
 // Same products, same k order, same start value as conv_mfma_kernel: the same bits.
 // ---------------------------------------------------------------------------------------------
-template <int SG, bool POOL>
+template <int SG, bool POOL, bool RR = false>
 __global__ __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(3, 3))) void conv_pp_kernel(MConv a) {
+    static_assert(!RR || SG == 4, "row reuse needs one k-step per tap: four chunks per pixel");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int MT = 4, NT = 3, TH = 8, KS = 5, THH = TH + KS - 1, TWH = TW + KS - 1, PS2 = SG * 16;
     constexpr int WSTEP = 2 * 1024 + 512;                 // LDS bytes of one k-step's A fragments (third tile: rows 0-7 only)
@@ -2594,6 +2679,64 @@ __global__ __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
                     __builtin_amdgcn_sched_group_barrier(0x002, 1, 0);                            \
                 }
                 if (a.dbg & 0x400) __builtin_amdgcn_s_setprio(3);      // PSEG_PP_PRIO=1
+                if constexpr (RR) {
+                    // Row reuse (host: MfmaPlan::rowreuse -- 25 k-steps, table entry of step s + 5 = entry of step s + one tile row): the
+                    // fragments this wave's UPPER row (m = 2, 3) reads at step s are the ones its LOWER row (m = 0, 1) needs at step s + 5.
+                    // The 25 steps are spelled out so that every fragment has a static register name: hi[s] is read once, used as the upper
+                    // row's operand at step s and as the lower row's at step s + 5; only steps 0-4 read the lower row (lo0).  Twelve
+                    // fragments are live (ten carried, two incoming) instead of eight; pixel reads per tile 60 instead of 100.
+                    // Same pipeline as below: the reads of step s + 1 issue between the MFMAs of step s, same operands per accumulator
+                    // in the same order -- the same bits.
+                    bf16x8 hi[25][2], lo0[5][2], wr[2][NT];
+                    int offp[2];
+                    const char* const px0 = in_t + pixbase[0];
+                    const char* const px1 = in_t + pixbase[1];
+                    const char* const px2 = in_t + pixbase[2];
+                    const char* const px3 = in_t + pixbase[3];
+                    int w2s = w2step;                     // opaque per tile: otherwise the 24 products S * w2step are hoisted out of the tile
+                    asm volatile("" : "+v"(w2s));          // loop and held in registers (168 VGPRs + scratch instead of 151)
+#define PPR_LOAD(S, OFF)                                                                         \
+                    {                                                                            \
+                        wr[(S) & 1][0] = *(const bf16x8*)(wb0 + (S) * WSTEP);                    \
+                        if constexpr ((S) < 5) {                                                 \
+                            lo0[(S) % 5][0] = *(const bf16x8*)(px0 + OFF);                       \
+                            lo0[(S) % 5][1] = *(const bf16x8*)(px1 + OFF);                       \
+                        }                                                                        \
+                        hi[S][0] = *(const bf16x8*)(px2 + OFF);                                  \
+                        hi[S][1] = *(const bf16x8*)(px3 + OFF);                                  \
+                        wr[(S) & 1][1] = *(const bf16x8*)(wb0 + (S) * WSTEP + 1024);             \
+                        wr[(S) & 1][2] = *(const bf16x8*)(wb2 + (S) * w2s);                      \
+                    }
+#define PPR_MMA(S)                                                                               \
+                    _Pragma("unroll") for (int t = 0; t < NT; ++t) {                             \
+                        acc[0][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wr[(S) & 1][t], (S) < 5 ? lo0[(S) % 5][0] : hi[(S) < 5 ? 0 : (S) - 5][0], acc[0][t], 0, 0, 0); \
+                        acc[1][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wr[(S) & 1][t], (S) < 5 ? lo0[(S) % 5][1] : hi[(S) < 5 ? 0 : (S) - 5][1], acc[1][t], 0, 0, 0); \
+                        acc[2][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wr[(S) & 1][t], hi[S][0], acc[2][t], 0, 0, 0); \
+                        acc[3][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wr[(S) & 1][t], hi[S][1], acc[3][t], 0, 0, 0); \
+                    }
+#define PPR_STEP(S)                                                                              \
+                    __builtin_amdgcn_sched_barrier(0);                                           \
+                    offp[(S) & 1] = tb[((S) + 2) * 4];                                           \
+                    PPR_LOAD((S) + 1, offp[((S) + 1) & 1])                                       \
+                    PPR_MMA(S)                                                                   \
+                    PP_INTERLEAVE
+                    offp[0] = tb[0]; offp[1] = tb[4];
+                    PPR_LOAD(0, offp[0])
+                    PPR_STEP(0) PPR_STEP(1) PPR_STEP(2) PPR_STEP(3) PPR_STEP(4)
+                    PPR_STEP(5) PPR_STEP(6) PPR_STEP(7) PPR_STEP(8) PPR_STEP(9)
+                    PPR_STEP(10) PPR_STEP(11) PPR_STEP(12) PPR_STEP(13) PPR_STEP(14)
+                    PPR_STEP(15) PPR_STEP(16) PPR_STEP(17) PPR_STEP(18) PPR_STEP(19)
+                    PPR_STEP(20) PPR_STEP(21) PPR_STEP(22)
+                    __builtin_amdgcn_sched_barrier(0);
+                    PPR_LOAD(24, offp[0])
+                    PPR_MMA(23)
+                    PP_INTERLEAVE
+                    __builtin_amdgcn_sched_barrier(0);
+                    PPR_MMA(24)
+#undef PPR_STEP
+#undef PPR_MMA
+#undef PPR_LOAD
+                } else {
                 int offa = PP_TAB(0), offb = PP_TAB(1);
                 PP_LOAD(xa, wa, 0, offa)
                 int s = 0;
@@ -2611,6 +2754,7 @@ __global__ __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
                 }
                 __builtin_amdgcn_sched_barrier(0);
                 if (ks & 1) { PP_MMA(xa, wa) }
+                }
                 if (a.dbg & 0x400) __builtin_amdgcn_s_setprio(0);
 #undef PP_INTERLEAVE
 #undef PP_TAB
@@ -3708,6 +3852,7 @@ enum PlanKind { PLAN_GENERIC = 0, PLAN_CONV1 = 1, PLAN_LOGITS = 2, PLAN_UPSPLIT 
 struct MfmaPlan {
     int kind = PLAN_GENERIC;
     bool pp = false;          // eligible for the persistent ping-pong kernel (conv_pp_kernel) when the page has enough tiles
+    bool rowreuse = false;    // k5, four chunks per pixel: k-step (ky, kx) of a wave's lower row reads what (ky + 1, kx) of its upper row reads (mfma_pack_op)
     int MT = 4, NT = 2, KS = 1, stride = 1, NW = 4;
     int nblk = 1, nc_full = 1, nc_last = 1, ks_full = 1, ks_last = 1;
     int PS2 = 0, row_pitch = 0, THH = 0, TWH = 0, GK = 4, NB = 3, G = 1, lds_w_off = 0, lds_tab_off = 0, lds_bytes = 0;
@@ -4315,8 +4460,29 @@ int mfma_pack_op(Engine& e, Op& op, const std::vector<float>& w, const std::vect
         }
         return t;
     };
-    PSEG_TRY(upload(&P->d_tab_full, mk_tab(ord_full)));
-    PSEG_TRY(upload(&P->d_tab_last, mk_tab(ord_last)));
+    const std::vector<int> tab_full = mk_tab(ord_full), tab_last = mk_tab(ord_last);
+    PSEG_TRY(upload(&P->d_tab_full, tab_full));
+    PSEG_TRY(upload(&P->d_tab_last, tab_last));
+    // Row reuse (k5, four chunks per pixel, a wave owning two adjacent output rows): when every k-step is one tap and the steps run
+    // tap-major, the pixel fragments of the wave's UPPER row under tap (ky, kx) are the fragments of its LOWER row under tap
+    // (ky - 1, kx) -- same LDS address, same lane layout -- so the k-loop keeps them in registers for five steps instead of reading
+    // them again: 60 instead of 100 pixel-fragment reads per tile and channel block.  Same operands in the same order for every
+    // accumulator: the same bits.  Decided on the tables as uploaded, not on how pair_chunks happens to order them.
+    {
+        auto shifts = [&](const std::vector<Chunk>& ord, const std::vector<int>& t) {
+            if (ord.size() != 100) return false;
+            for (const Chunk& c : ord)
+                if (c.cc < 0) return false;
+            for (int s = 0; s < 20; ++s)
+                for (int gq = 0; gq < 4; ++gq)
+                    if (t[(s + 5) * 4 + gq] != t[s * 4 + gq] + P->row_pitch) return false;
+            return true;
+        };
+        P->rowreuse = !deconv && KS == 5 && op.stride == 1 && !op.up0 && !op.up1 && !op.in_relu && P->MT == 4 && P->NW == 4 &&
+                      shifts(ord_full, tab_full) && shifts(ord_last, tab_last) && !PSEG_KNOB("PSEG_NO_ROWREUSE") && !PSEG_KNOB("PSEG_GENERIC");
+        if (PSEG_KNOB("PSEG_LOG_GENERIC") && KS == 5 && P->MT == 4 && sigma == 4)
+            fprintf(stderr, "[pseg] rowreuse %s: %d\n", op.layer.c_str(), P->rowreuse ? 1 : 0);
+    }
     // LDS budget: input tile + a ring of NB weight groups (GK k-steps each) + table; aim at two
     // workgroups per CU (<= 80 KiB each).  GK*NT must be a multiple of 4 so that every wave
     // issues the same number of LDS-DMA loads per group (counted vmcnt).  PSEG_GK / PSEG_NB /
@@ -4758,17 +4924,17 @@ int mfma_pack_op(Engine& e, Op& op, const std::vector<float>& w, const std::vect
     return PSEG_OK;
 }
 
-template <int MT, int NT, int KS, int ST, int SG, int MODE, int FL, int NW = 4>
+template <int MT, int NT, int KS, int ST, int SG, int MODE, int FL, int NW = 4, int RR = 0>
 static int launch_inst(const MConv& a, const MfmaPlan& P, dim3 grid, hipStream_t st) {
     static bool attr_set[64] = {false};
     int dev = 0;
     PSEG_HIP(hipGetDevice(&dev));
     if (!attr_set[dev & 63]) {
-        PSEG_HIP(hipFuncSetAttribute((const void*)conv_mfma_kernel<MT, NT, KS, ST, SG, MODE, FL, NW>,
+        PSEG_HIP(hipFuncSetAttribute((const void*)conv_mfma_kernel<MT, NT, KS, ST, SG, MODE, FL, NW, RR>,
                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         attr_set[dev & 63] = true;
     }
-    conv_mfma_kernel<MT, NT, KS, ST, SG, MODE, FL, NW><<<grid, NW * 64, P.lds_bytes, st>>>(a);
+    conv_mfma_kernel<MT, NT, KS, ST, SG, MODE, FL, NW, RR><<<grid, NW * 64, P.lds_bytes, st>>>(a);
     return PSEG_OK;
 }
 
@@ -4806,6 +4972,10 @@ static int launch_generic_any2(const MConv& a, const MfmaPlan& P, dim3 grid, hip
     PSEG_TRY_INST(8, 2, 5, 1, 6, MODE_CONV, FL_POOL)      // conv2 (padded tile)
     PSEG_TRY_INST(4, 3, 5, 1, 6, MODE_CONV, 0)            // conv3, deconv3
     PSEG_TRY_INST(4, 3, 5, 1, 6, MODE_CONV, FL_POOL)      // conv4
+    // row reuse (MfmaPlan::rowreuse): the instance is compiled for the plan's weight-group size
+    if (a.rowreuse && P.GK == 4 && P.ks_full == 25 && P.ks_last == 25 && !a.trace && P.MT == 4 && P.NT == 3 && ks == 5 && st_ == 1 && sg == 4 &&
+        mode == MODE_CONV && fl == 0 && !PSEG_KNOB("PSEG_GENERIC"))
+        return launch_inst<4, 3, 5, 1, 4, MODE_CONV, 0, 4, 4>(a, P, grid, st);   // conv3 (small pages), deconv3
     PSEG_TRY_INST(4, 3, 5, 1, 4, MODE_CONV, 0)            // conv3, deconv3: dense 64-byte pixels, three workgroups per CU
     PSEG_TRY_INST(4, 3, 5, 1, 5, MODE_CONV, FL_POOL)      // conv4: dense 80-byte pixels, three workgroups per CU
     PSEG_TRY_INST(4, 3, 5, 1, 5, MODE_CONV, 0)
@@ -4927,6 +5097,7 @@ static void fill_common(const Engine& e, const Op& op, const MfmaPlan& P, MConv&
     a.tab_full = P.d_tab_full; a.tab_last = P.d_tab_last; a.wpk = P.d_wpk; a.NTtot = P.NTtot; a.bias = P.d_bias;
     a.PS2 = P.PS2; a.row_pitch = P.row_pitch; a.THH = P.THH; a.TWH = P.TWH; a.GK = P.GK; a.NB = P.NB; a.G = P.G;
     a.lds_w_off = P.lds_w_off; a.lds_tab_off = P.lds_tab_off;
+    a.rowreuse = P.rowreuse ? 1 : 0;
     const Tensor& d = e.tensors[op.dst];
     a.dst = (uint16_t*)d.d;
     a.dst2 = op.relu_dst >= 0 ? (uint16_t*)e.tensors[op.relu_dst].d : nullptr;
@@ -5231,18 +5402,20 @@ int mfma_launch_conv(Engine& e, Op& op, hipStream_t st) {
             if (PSEG_DIAG_KNOB("PSEG_PP_NODMA")) w.dbg |= 0x800;     // wrong results, timing only: diagnostic build only
             if (PSEG_DIAG_KNOB("PSEG_PP_NOEPI")) w.dbg |= 0x1000;
             const dim3 gp((unsigned)cus_pp);
-#define PSEG_PP(SG_, POOL_)                                                                                       \
-            if (a.sigma == SG_ && (a.pool_dst != nullptr) == POOL_) {                                             \
+            const bool rr = P->rowreuse && P->ks_full == 25;   // conv3: the k-loop that keeps a wave's shared pixel fragments in registers
+#define PSEG_PP(SG_, POOL_, RR_)                                                                                  \
+            if (a.sigma == SG_ && (a.pool_dst != nullptr) == POOL_ && rr == RR_) {                                \
                 static bool attr_set[64] = {false};                                                               \
                 if (!attr_set[dev & 63]) {                                                                        \
-                    PSEG_HIP(hipFuncSetAttribute((const void*)conv_pp_kernel<SG_, POOL_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
+                    PSEG_HIP(hipFuncSetAttribute((const void*)conv_pp_kernel<SG_, POOL_, RR_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
                     attr_set[dev & 63] = true;                                                                    \
                 }                                                                                                 \
-                conv_pp_kernel<SG_, POOL_><<<gp, 768, lds, st>>>(w);                                              \
+                conv_pp_kernel<SG_, POOL_, RR_><<<gp, 768, lds, st>>>(w);                                         \
                 PSEG_HIP(hipGetLastError());                                                                      \
                 return PSEG_OK;                                                                                   \
             }
-            PSEG_PP(4, false) PSEG_PP(4, true) PSEG_PP(5, false) PSEG_PP(5, true)
+            PSEG_PP(4, false, true) PSEG_PP(4, true, true)
+            PSEG_PP(4, false, false) PSEG_PP(4, true, false) PSEG_PP(5, false, false) PSEG_PP(5, true, false)
 #undef PSEG_PP
         }
     }
