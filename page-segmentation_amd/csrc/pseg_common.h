@@ -131,7 +131,9 @@ int run_pipeline(Stage& g, int nu, const PipeSet* set, hipStream_t s_in, hipStre
 // (KnobScope, thread-local) -- plan-time and launch-time reads of one engine always agree, and neither a later change of the
 // environment nor the creation of another engine (the float32 companion of the label-exact mode inherits its parent's snapshot)
 // can alter a running engine.  Engine-less entries (post-process, resize) read the newest environment snapshot.  Each call site
-// caches its answer per snapshot id.
+// caches its answer per snapshot id.  The bf16 conv path relies on that agreement: the switches that select a kernel are read when a
+// layer is packed (mfma_pack_op keeps the answers in the plan's flags) and no launch reads them again.  The diagnostic build reads
+// the live environment instead; changing a switch between weight upload and launch was never supported there.
 // Knobs that produce WRONG results (timing ablations: PSEG_DBG, PSEG_XM_DBG, PSEG_SP_DBG, PSEG_PP_NODMA, PSEG_PP_NOEPI, the
 // in-kernel trace stamps) exist only in the diagnostic build (libpseg_diag.so, -DPSEG_DIAG=1, which reads everything from the
 // environment): PSEG_DIAG_KNOB is a constant nullptr in the release library (tests/test_abi.py checks that the release .so does

@@ -3851,7 +3851,6 @@ enum PlanKind { PLAN_GENERIC = 0, PLAN_CONV1 = 1, PLAN_LOGITS = 2, PLAN_UPSPLIT 
 
 struct MfmaPlan {
     int kind = PLAN_GENERIC;
-    bool pp = false;          // eligible for the persistent ping-pong kernel (conv_pp_kernel) when the page has enough tiles
     bool rowreuse = false;    // k5, four chunks per pixel: k-step (ky, kx) of a wave's lower row reads what (ky + 1, kx) of its upper row reads (mfma_pack_op)
     int MT = 4, NT = 2, KS = 1, stride = 1, NW = 4;
     int nblk = 1, nc_full = 1, nc_last = 1, ks_full = 1, ks_last = 1;
@@ -3892,22 +3891,27 @@ struct MfmaPlan {
     size_t skiplog_bytes = 0;
     int skip_CP = 0;
     UpSplit* upsplit = nullptr;   // PLAN_UPSPLIT: GEMM + gather-sum form of upsample -> k2 conv
-    // conv_sp_kernel (streamed weights, persistent workgroups, loader waves): a second packing of the same layer
-    bool sp = false;
+    // ---- which kernel family may take this layer: everything about the choice that does not depend on the canvas (the layer-shape
+    // tests and the plan switches), decided once in mfma_pack_op.  The launch adds only the size predicates (sp_pays ... s2_persists).
+    bool spec = true;           // specialised conv_mfma_kernel instances, deconv N-block walks and the composed tail allowed (no PSEG_GENERIC)
+    bool sp = false;            // conv_sp_kernel (streamed weights, persistent workgroups, loader waves): a second packing of the same layer
+    bool pp_shape = false;      // a conv3 / conv4 shape planned for conv_pp_kernel: kept off conv_sp_kernel and the layer-major page launches
+    bool pp = false;            // ... that conv_pp_kernel can run (one channel block), when the page has enough tiles
+    bool ws = false;            // conv12_ws_kernel (fused conv1 + conv2, wave-specialised)
+    int ws_form = 0;            // ... its alternative tile loops (PSEG_WS_FORM = 1 / 2: the default packing with skip logits only)
+    bool persist_f1 = false;    // fused conv1 + conv2 on conv_mfma_kernel: two persistent workgroups per CU
+    bool persist_s2 = false;    // single-block stride-2 k3 layer: persistent instances, when a page has many tiles
+    bool sp2_all = false;       // PSEG_SP2 set (tests, A/B): conv_sp2_kernel for every eligible launch ...
+    int sp2_tw = 0;             // ... = 24 / 32: with that tile width
     int sp_NT = 0, sp_sigma = 0, sp_fl = 0, sp_K = 0, sp_S = 0, sp_blk_steps = 0, sp_nblk = 0, sp_nc_full = 0, sp_nc_last = 0;
-    int sp_row_pitch = 0, sp_TBLK = 0, sp_RK = 0, sp_ring_off = 0, sp_patch_off = 0, sp_tab_off = 0, sp_flag_off = 0, sp_lds = 0;
-    // the same layer on tiles of 8 x 24 pixels (conv_sp_kernel<..., 24>): its own LDS layout and k-chunk table, the same weight stream
-    struct SpNarrow { bool ok = false; int row_pitch = 0, TBLK = 0, RK = 0, ring_off = 0, patch_off = 0, tab_off = 0, flag_off = 0, lds = 0; int* d_tab = nullptr; } sp24;
-    int* d_sp_tab = nullptr;
+    // LDS layout and k-chunk table of one streamed-weight kernel at one tile width; [0] tiles of 8 x 32, [1] of 8 x 24.  Every
+    // layout of a layer reads the same weight stream (d_sp_wpk) in the same chunk order: the same bits.
+    struct SpLayout { bool ok = false; int row_pitch = 0, TBLK = 0, RK = 0, ring_off = 0, patch_off = 0, tab_off = 0, flag_off = 0, lds = 0; int* d_tab = nullptr; };
+    SpLayout sp_lay[2];         // conv_sp_kernel ([0].ok == sp)
+    SpLayout sp2_lay[2];        // conv_sp2_kernel (two compute teams, four block slots): block-relative tables, one entry per column & 7
     uint16_t* d_sp_wpk = nullptr;
-    // conv_sp2_kernel (two compute teams, four block slots): [0] tiles of 8 x 32, [1] of 8 x 24; block-relative k-chunk tables, the same weight stream
-    struct Sp2 { bool ok = false; int TBLK = 0, RK = 0, ring_off = 0, patch_off = 0, tab_off = 0, flag_off = 0, lds = 0; int* d_tab = nullptr; } sp2[2];
 };
 
-static bool sp2_off() {
-    const char* v = PSEG_KNOB("PSEG_SP2");
-    return v && atoi(v) == 0;
-}
 static bool tracing_req(const Op& op) {
     const char* trl = PSEG_DIAG_KNOB("PSEG_SP_TRACE");
     return trl && op.layer == trl;
@@ -3924,7 +3928,8 @@ void mfma_free_op(Op& op) {
     (void)hipFree(p->d_skiplog);
     (void)hipFree(p->d_dq_w); (void)hipFree(p->d_dq_bias);
     (void)hipFree(p->d_q_w); (void)hipFree(p->d_q_bias); (void)hipFree(p->d_t2_wD); (void)hipFree(p->d_t2_wC);
-    (void)hipFree(p->d_sp_tab); (void)hipFree(p->sp24.d_tab); (void)hipFree(p->d_sp_wpk); (void)hipFree(p->sp2[0].d_tab); (void)hipFree(p->sp2[1].d_tab);
+    (void)hipFree(p->d_sp_wpk);
+    for (int v = 0; v < 2; ++v) { (void)hipFree(p->sp_lay[v].d_tab); (void)hipFree(p->sp2_lay[v].d_tab); }
     delete p;
     op.plan = nullptr;
 }
@@ -3946,12 +3951,13 @@ static int producer_of(const Engine& e, int tensor) {
 
 // Fold every MaxPooling2D into the epilogue of the conv that produces its input.
 int mfma_plan_graph(Engine& e) {
+    const bool spec = !PSEG_KNOB("PSEG_GENERIC");   // the fusions below need specialised kernel instances
     // Pre-activation ReLU moved into the producer (res_unet).  A conv output whose EVERY reader is a convolution that
     // applies ReLU to its input first -- conv_block 1's output (read by conv_block 2 only), the stem's first conv, the
     // bridge, e5 -- is stored ReLU'd by the conv that produces it (after the residual add, where it has one), and the
     // readers stage it as it is: bf16(max(x, 0)) == max(bf16(x), 0), so every value the readers see is unchanged, and
     // they no longer run the in-LDS ReLU pass over their halo tile (15-17 % of conv_block 2 at every level).
-    if (!PSEG_KNOB("PSEG_NO_RELU_FWD") && !PSEG_KNOB("PSEG_GENERIC")) {
+    if (!PSEG_KNOB("PSEG_NO_RELU_FWD") && spec) {
         std::vector<char> ok(e.tensors.size(), 0);
         for (size_t t = 0; t < e.tensors.size(); ++t) {
             const int pi = producer_of(e, (int)t);
@@ -3988,7 +3994,7 @@ int mfma_plan_graph(Engine& e) {
     // The second store costs the producer about three times its share of the HBM bandwidth (8-byte lane stores), so it
     // pays only for the low-resolution tensors (<= 8 elements per canvas pixel: e3, e4, the bridge, d1 -- measured on a
     // 2048x1536 page: producers +28 / +10 / +5 / +16 us, readers -105 / -76 us; e1 / e2 / d2 / d3: +253 us vs -198 us).
-    if (!PSEG_KNOB("PSEG_NO_RELU_FWD") && !PSEG_KNOB("PSEG_NO_RELU_COPY") && !PSEG_KNOB("PSEG_GENERIC")) {
+    if (!PSEG_KNOB("PSEG_NO_RELU_FWD") && !PSEG_KNOB("PSEG_NO_RELU_COPY") && spec) {
         auto can_copy = [&](int t) {
             const int pi = producer_of(e, t);
             if (pi < 0) return false;
@@ -4077,7 +4083,7 @@ int mfma_plan_graph(Engine& e) {
     // Conv2DTranspose k2 s2 behind a k5 conv whose 80-channel output nothing else reads (fcn / fcn_skip: deconv1 -> deconv2, 1/8
     // -> 1/4 resolution): the transposed conv is pointwise in the conv's output pixels, so it runs on the conv's accumulators in
     // its epilogue (FL_DQ) -- one launch less, the 1/8-resolution tensor is neither written nor read
-    if (!PSEG_KNOB("PSEG_NO_DQ") && !PSEG_KNOB("PSEG_GENERIC"))
+    if (!PSEG_KNOB("PSEG_NO_DQ") && spec)
         for (size_t di = 0; di < e.ops.size(); ++di) {
             Op& dq = e.ops[di];
             if (dq.type != OP_DECONV2 || dq.src1 >= 0 || dq.tail_logits >= 0 || dq.into_tail >= 0 || dq.fused_away || dq.Cout > 64) continue;
@@ -4113,7 +4119,7 @@ int mfma_plan_graph(Engine& e) {
     // skip connection into a composed tail (fcn_skip: conv2 -> logits): when the full-resolution conv output has no
     // other reader than its fused pool and the logits layer, the conv stores its logits contribution (4 or 8 floats
     // per pixel) instead of the tensor, and the tail adds it: 64 + 64 B/px of HBM traffic become 16 + 16 (32 + 32).
-    if (!PSEG_KNOB("PSEG_NO_SKIPLOG") && !PSEG_KNOB("PSEG_NO_TAIL_COMPOSE") && !PSEG_KNOB("PSEG_NO_TAIL_FUSION") && !PSEG_KNOB("PSEG_GENERIC") &&
+    if (!PSEG_KNOB("PSEG_NO_SKIPLOG") && !PSEG_KNOB("PSEG_NO_TAIL_COMPOSE") && !PSEG_KNOB("PSEG_NO_TAIL_FUSION") && spec &&
         !PSEG_KNOB("PSEG_NO_CONV1_FUSION") && e.n_classes <= 8)
         for (auto& dc : e.ops) {
             if (dc.type != OP_DECONV2 || dc.tail_logits < 0 || dc.relu) continue;
@@ -4147,7 +4153,7 @@ int mfma_plan_graph(Engine& e) {
             e.tensors[dq.dst].fused = true;
         }
     // the same inner-deconv fusion for a tail without skips (fcn: deconv4 -> deconv5 o logits)
-    if (!PSEG_KNOB("PSEG_NO_TAIL2") && !PSEG_KNOB("PSEG_NO_TAIL_COMPOSE") && !PSEG_KNOB("PSEG_NO_TAIL_FUSION") && !PSEG_KNOB("PSEG_GENERIC") && e.n_classes <= 8)
+    if (!PSEG_KNOB("PSEG_NO_TAIL2") && !PSEG_KNOB("PSEG_NO_TAIL_COMPOSE") && !PSEG_KNOB("PSEG_NO_TAIL_FUSION") && spec && e.n_classes <= 8)
         for (auto& dc : e.ops) {
             if (dc.type != OP_DECONV2 || dc.tail_logits < 0 || dc.relu || dc.src1 >= 0 || e.ops[dc.tail_logits].src1 >= 0) continue;
             if (e.tensors[dc.src0].Cs != 32) continue;
@@ -4261,6 +4267,9 @@ int mfma_pack_op(Engine& e, Op& op, const std::vector<float>& w, const std::vect
     op.plan = P;
     P->w_keep = w;
     P->b_keep = bias;
+    // the switches that several kernel families share; every family's flag below includes its own
+    const bool spec = P->spec = !PSEG_KNOB("PSEG_GENERIC");
+    const bool persist = !PSEG_KNOB("PSEG_NO_PERSIST"), ws_on = !PSEG_KNOB("PSEG_NO_WS");
     const Tensor& s0 = e.tensors[op.src0];
     const Tensor* s1 = op.src1 >= 0 ? &e.tensors[op.src1] : nullptr;
     const int C0 = s0.C, Cs0 = s0.Cs, C1 = s1 ? s1->C : 0, Cs1 = s1 ? s1->Cs : 0;
@@ -4346,7 +4355,7 @@ int mfma_pack_op(Engine& e, Op& op, const std::vector<float>& w, const std::vect
     // Measured at 2048x1536 (unet): 1024->512 216 -> ~75 us, 512->256 228 -> ~110 us, 256->128 246 -> ~185 us; at
     // 128->64 the two extra passes over the full-resolution tensor cost more than the direct kernel (PSEG_UPSPLIT_MIN_CIN).
     if (op.type == OP_CONV && k == 2 && op.up0 && !s1 && op.stride == 1 && !op.in_relu && op.add < 0 && op.pool_dst < 0 &&
-        op.tail_logits < 0 && op.fuse1 < 0 && !op.transposed && !PSEG_KNOB("PSEG_NO_UPSPLIT") && !PSEG_KNOB("PSEG_GENERIC")) {
+        op.tail_logits < 0 && op.fuse1 < 0 && !op.transposed && !PSEG_KNOB("PSEG_NO_UPSPLIT") && spec) {
         // (the two-pass form lost to the direct kernel at 128 -> 64 channels on the full-resolution map; the fused form does not)
         const int min_cin = PSEG_KNOB("PSEG_UPSPLIT_TWO_PASS") ? 256 : 64;
         if (Cin >= min_cin) {
@@ -4372,7 +4381,7 @@ int mfma_pack_op(Engine& e, Op& op, const std::vector<float>& w, const std::vect
     // stride 2 (res_unet's encoder): the halo tile of an 8 x 32 output tile is 17 x 65 pixels -- 71 KB at 32 channels, one
     // four-wave workgroup per CU beside its weights.  Four-row tiles (9 x 65 pixels) fit twice.
     const bool deint = !deconv && op.stride == 2;
-    if (deint && NT == 4 && KS == 3 && !PSEG_KNOB("PSEG_NO_S2_MT2") && !PSEG_KNOB("PSEG_GENERIC")) P->MT = 2;
+    if (deint && NT == 4 && KS == 3 && !PSEG_KNOB("PSEG_NO_S2_MT2") && spec) P->MT = 2;
     // (the fused conv1+conv2 kernel was also tried with 8-row tiles -- 136 registers, 42 KB, three workgroups per
     // CU: 182 vs 164 us; the halo recompute of conv1 grows from 1.41x to 1.69x and the weights stream twice as often)
     // (the 1/8-resolution k5 layers -- conv7, deconv1: 192 eight-row tiles for 256 CUs on a 2048x1536 page -- were tried
@@ -4382,15 +4391,14 @@ int mfma_pack_op(Engine& e, Op& op, const std::vector<float>& w, const std::vect
     P->stride = deconv ? 1 : op.stride;
     // 8-wave workgroups (16-row tiles, the whole CU's LDS) exist for the k5 stride-1 mid-layer shapes
     P->nw8_ok = !deconv && (KS == 5 || (KS == 3 && NT == 4)) && op.stride == 1 && P->MT == 4 && (NT == 3 || NT == 4) && !op.up0 && !op.up1 &&
-                !op.in_relu && op.add < 0 && op.fuse1 < 0 && (P->nblocks_n == 1 || KS == 3) && !PSEG_KNOB("PSEG_GENERIC");
+                !op.in_relu && op.add < 0 && op.fuse1 < 0 && (P->nblocks_n == 1 || KS == 3) && spec;
     P->NW = (P->nw8_ok && op.nw_hint == 8) ? 8 : 4;
     const int TH = P->NW * (P->MT / 2);
     const int totc = (Cs0 + Cs1) / 8;
     // fused conv1 + conv2 on the wave-specialised kernel: 20 input channels = 2.5 chunks per pixel -- the half chunk pairs up
     // with the right neighbour's (the producers write the tile that way), 65 k-chunks instead of 75
     P->pairc2 = op.fuse1 >= 0 && !deconv && KS == 5 && C0 == 20 && Cs0 == 24 && !s1 && op.stride == 1 && op.pool_dst >= 0 && !op.relu &&
-                op.add < 0 && !op.in_relu && Cout <= 32 && !PSEG_KNOB("PSEG_NO_WS") && !PSEG_KNOB("PSEG_NO_PAIRC2") && !PSEG_KNOB("PSEG_NO_PERSIST") &&
-                !PSEG_KNOB("PSEG_GENERIC");
+                op.add < 0 && !op.in_relu && Cout <= 32 && ws_on && !PSEG_KNOB("PSEG_NO_PAIRC2") && persist && spec;
     P->nc_full = totc <= 5 ? totc : (KS == 1 && totc <= 16 ? totc : 4);
     P->nblk = cdiv(totc, P->nc_full);
     P->nc_last = totc - (P->nblk - 1) * P->nc_full;
@@ -4401,6 +4409,16 @@ int mfma_pack_op(Engine& e, Op& op, const std::vector<float>& w, const std::vect
     // conflicts are far cheaper than streaming the weights group by group).
     int sigma = sigma_for(P->nc_full);
     int pitch_pad = 1;   // extra 16-byte slots per tile row
+    // ... for a dense tile: the pad whose k-chunk pairing the bank model likes best
+    auto best_pad = [&](int sg, int row_slots, bool pair2, int plane) {
+        int pad = 0, best_cyc = 1 << 30;
+        for (int pd = 0; pd < 16; ++pd) {
+            int cyc = 0;
+            (void)pair_chunks(KS, P->nc_full, sg, row_slots + pd, &cyc, pair2, plane);
+            if (cyc < best_cyc) { best_cyc = cyc; pad = pd; }
+        }
+        return pad;
+    };
     P->THH = (TH - 1) * P->stride + KS;
     P->TWH = (TW - 1) * P->stride + KS;
     {
@@ -4419,22 +4437,18 @@ int mfma_pack_op(Engine& e, Op& op, const std::vector<float>& w, const std::vect
         P->wg3 = P->NW == 4 && !deconv && ((KS == 5 && (NT == 3 || NT == 4) && P->nblocks_n == 1) || (KS == 3 && NT == 4) ||
                                                  (KS == 2 && NT == 4 && op.up0 && !s1)) &&
                  (P->nc_full == 4 || P->nc_full == 5) && op.stride == 1 &&
-                 (!op.up0 || KS == 2 || KS == 3) && !op.up1 && ((!op.in_relu && op.add < 0) || (KS == 3)) && op.fuse1 < 0 &&
-                 !PSEG_KNOB("PSEG_GENERIC");
+                 (!op.up0 || KS == 2 || KS == 3) && !op.up1 && ((!op.in_relu && op.add < 0) || (KS == 3)) && op.fuse1 < 0 && spec;
         // (stride 2: always the dense tile -- its columns are de-interleaved by parity at staging time, which makes the fragment
         // reads those of a stride-1 layer, and the 4.3 input pixels per output pixel are the layer's LDS and DMA bill)
         // conv_pp_kernel (conv3 / conv4: resident weights, two tile buffers).  (A 64-byte pixel pitch -- conv3's four chunks -- cannot be
         // read without 2-way bank conflicts: the eight lanes of a 16-lane read group that share a chunk cover four distinct 16-byte
         // windows.  An 80-byte pitch removes them and was measured in this kernel: 52.1 vs 52.0 us, so the dense tile stays.)
-        P->pp = P->wg3 && KS == 5 && NT == 3 && P->nblocks_n == 1 && op.Cout <= 40 && !op.transposed && op.src1 < 0 && !PSEG_KNOB("PSEG_NO_PP");
+        // (wg3 gives the rest of the kernel's shape: four waves, MT 4, stride 1, sigma 4 or 5, no fused input or epilogue work)
+        P->pp_shape = P->wg3 && KS == 5 && NT == 3 && P->nblocks_n == 1 && op.Cout <= 40 && !op.transposed && op.src1 < 0 && !PSEG_KNOB("PSEG_NO_PP");
+        P->pp = P->pp_shape && P->nblk == 1;
         if (P->wg3 || (deint && P->nc_full >= 2) || (P->nblk == 1 && !fits(sigma, 1) && P->nc_full < sigma && fits(P->nc_full, 16))) {
             sigma = P->nc_full;
-            int best_cyc = 1 << 30;
-            for (int pad = 0; pad < 16; ++pad) {
-                int cyc = 0;
-                (void)pair_chunks(KS, P->nc_full, sigma, P->TWH * sigma + pad, &cyc, P->pairc2, deint ? ((P->TWH + 1) / 2) * sigma : 0);
-                if (cyc < best_cyc) { best_cyc = cyc; pitch_pad = pad; }
-            }
+            pitch_pad = best_pad(sigma, P->TWH * sigma, P->pairc2, deint ? ((P->TWH + 1) / 2) * sigma : 0);
         }
     }
     if (P->pairc2) {
@@ -4479,7 +4493,7 @@ int mfma_pack_op(Engine& e, Op& op, const std::vector<float>& w, const std::vect
             return true;
         };
         P->rowreuse = !deconv && KS == 5 && op.stride == 1 && !op.up0 && !op.up1 && !op.in_relu && P->MT == 4 && P->NW == 4 &&
-                      shifts(ord_full, tab_full) && shifts(ord_last, tab_last) && !PSEG_KNOB("PSEG_NO_ROWREUSE") && !PSEG_KNOB("PSEG_GENERIC");
+                      shifts(ord_full, tab_full) && shifts(ord_last, tab_last) && !PSEG_KNOB("PSEG_NO_ROWREUSE") && spec;
         if (PSEG_KNOB("PSEG_LOG_GENERIC") && KS == 5 && P->MT == 4 && sigma == 4)
             fprintf(stderr, "[pseg] rowreuse %s: %d\n", op.layer.c_str(), P->rowreuse ? 1 : 0);
     }
@@ -4526,6 +4540,21 @@ int mfma_pack_op(Engine& e, Op& op, const std::vector<float>& w, const std::vect
         P->lds_f1_off = round_up(P->lds_bytes, 16);
         P->lds_bytes = P->lds_f1_off + 2 * (TH + 8) * 96;
     }
+    // ---- persistent forms of a single-block layer with resident weights (PSEG_NO_PERSIST=1: none of them) -----------------------
+    // Two workgroups per CU walking 12 tiles each: the 38 KB weight set and the k-chunk table are staged once per workgroup instead
+    // of once per tile.  Worth 1-3 % on the fused conv1+conv2 kernel (the DMA it saves was mostly hidden by the co-resident
+    // workgroup); needs the per-trip opaque lane ids to keep two waves per SIMD.
+    const bool resident1 = P->NB == 1 && P->nblk == 1 && P->nblocks_n == 1 && persist && spec;
+    P->persist_f1 = op.fuse1 >= 0 && resident1;
+    // wave-specialised persistent kernel (conv12_ws_kernel): one 512-thread workgroup per CU, two input tiles + the resident weights
+    // in LDS.  PSEG_NO_WS=1 falls back to the every-wave-does-everything fused instance above.
+    P->ws = P->persist_f1 && !deconv && P->MT == 8 && NT == 2 && KS == 5 && sigma == 3 && op.pool_dst >= 0 && op.add < 0 && !op.in_relu && !op.relu && ws_on;
+    // (the alternative tile loops exist for the default packing only)
+    const char* const ws_form = PSEG_KNOB("PSEG_WS_FORM");
+    P->ws_form = (ws_form && P->ws && P->pairc2 && op.skiplog >= 0 && (atoi(ws_form) == 1 || atoi(ws_form) == 2)) ? atoi(ws_form) : 0;
+    // ... and the k3 stride-2 single-block layers whose instances exist (launch_generic_any2): many tiles, nine k-steps each
+    P->persist_s2 = op.fuse1 < 0 && resident1 && !deconv && KS == 3 && sigma == 4 && P->MT == 2 && NT == 4 && op.stride == 2 && !op.up0 && !op.up1 &&
+                    op.pool_dst < 0 && op.relu_dst < 0 && op.skiplog < 0 && op.tail_logits < 0 && op.dq_fuse < 0 && op.add < 0;
 
     // ---- pack weights into MFMA A-fragment order -----------------------------------------------
     // concat-storage channel cs -> true input channel (or -1 for pad)
@@ -4578,16 +4607,10 @@ int mfma_pack_op(Engine& e, Op& op, const std::vector<float>& w, const std::vect
     PSEG_TRY(upload(&P->d_bias, bb));
     // ---- second packing for conv_sp_kernel: k5 stride-1 layers with one N block whose weights are streamed ----------
     if (!deconv && KS == 5 && op.stride == 1 && !op.up0 && !op.up1 && !op.in_relu && op.add < 0 && op.fuse1 < 0 && op.tail_logits < 0 &&
-        op.skiplog < 0 && op.relu_dst < 0 && P->nblocks_n == 1 && NT >= 3 && NT <= 5 && (op.dq_fuse < 0 || NT == 5) && !P->pp &&
-        !PSEG_KNOB("PSEG_NO_SP") && !PSEG_KNOB("PSEG_GENERIC")) {
+        op.skiplog < 0 && op.relu_dst < 0 && P->nblocks_n == 1 && NT >= 3 && NT <= 5 && (op.dq_fuse < 0 || NT == 5) && !P->pp_shape &&
+        !PSEG_KNOB("PSEG_NO_SP") && spec) {
         const int sg = P->nc_full;                 // dense tile: sigma = chunks per pixel of a block
-        int pad = 1, best_cyc = 1 << 30;
-        for (int pd = 0; pd < 16; ++pd) {
-            int cyc = 0;
-            (void)pair_chunks(KS, P->nc_full, sg, (TW + KS - 1) * sg + pd, &cyc);
-            if (cyc < best_cyc) { best_cyc = cyc; pad = pd; }
-        }
-        const int rowp = ((TW + KS - 1) * sg + pad) * 16, TBLK = round_up((8 + KS - 1) * rowp, 16);
+        const int rowp = ((TW + KS - 1) * sg + best_pad(sg, (TW + KS - 1) * sg, false, 0)) * 16, TBLK = round_up((8 + KS - 1) * rowp, 16);
         const auto o_full = pair_chunks(KS, P->nc_full, sg, rowp / 16), o_last = pair_chunks(KS, P->nc_last, sg, rowp / 16);
         const int ksf = (int)o_full.size() / 4, ksl = (int)o_last.size() / 4;
         const int K0 = (P->nblk - 1) * ksf + ksl, K = round_up(K0, 2);
@@ -4604,7 +4627,7 @@ int mfma_pack_op(Engine& e, Op& op, const std::vector<float>& w, const std::vect
         const int rk_min = dq ? 12 : 10;           // five ring slots of two k-steps; the transposed conv's 10 pseudo-steps sit in the ring at once
         const bool patch = dq || ring_for(true) >= rk_min;
         const int RK = ring_for(patch);
-        // the kernel instances (mfma_launch_conv), a row pitch the kernel is compiled for, channel blocks that have ONE source each,
+        // the kernel instances (sp_run), a row pitch the kernel is compiled for, channel blocks that have ONE source each,
         // at most four of them (the tile loaders' counted waits), 64 output channels behind a fused transposed conv
         const bool inst = (NT == 5 && sg == 4 && (dq || patch)) || (NT == 4 && (sg == 4 || sg == 5) && patch) || (NT == 3 && sg == 4);
         const bool shape_ok = rowp == sp_row_pitch(sg) && P->nblk <= 4 && (!s1 || (Cs0 / 8) % P->nc_full == 0) &&
@@ -4613,90 +4636,82 @@ int mfma_pack_op(Engine& e, Op& op, const std::vector<float>& w, const std::vect
             P->sp = true;
             P->sp_NT = NT; P->sp_sigma = sg; P->sp_K = K; P->sp_S = S; P->sp_blk_steps = ksf;
             P->sp_nblk = P->nblk; P->sp_nc_full = P->nc_full; P->sp_nc_last = P->nc_last;
-            P->sp_row_pitch = rowp; P->sp_TBLK = TBLK; P->sp_RK = RK;
             P->sp_fl = (dq ? SP_DQ : 0) | (patch && !dq ? SP_PATCH : 0) | (op.pool_dst >= 0 ? SP_POOL : 0);
-            P->sp_ring_off = tiles_b;
-            P->sp_patch_off = tiles_b + RK * NT * 1024;
-            P->sp_tab_off = P->sp_patch_off + (patch ? patchb : 0);
-            P->sp_flag_off = P->sp_tab_off + round_up(tabb, 1024);      // (the table arrives in 1 KiB DMA pieces)
-            P->sp_lds = P->sp_flag_off + 64;
-            std::vector<int> tab((size_t)K * 4, 0);
+            // every real k-chunk of the layer in stream order: f(k-step of the tile, lane group, channel block, chunk).  (Dummies keep
+            // offset 0 -- finite data -- and zero weights.)
+            auto walk = [&](auto f) {
+                for (int b = 0; b < P->nblk; ++b) {
+                    const bool last = b == P->nblk - 1;
+                    const auto& ord = last ? o_last : o_full;
+                    const int ksb = last ? ksl : ksf;
+                    for (int st = 0; st < ksb; ++st)
+                        for (int gi = 0; gi < 4; ++gi) {
+                            const Chunk c = ord[(size_t)st * 4 + gi];
+                            if (c.cc >= 0) f(b * ksf + st, gi, b, c);
+                        }
+                }
+            };
+            // conv_sp_kernel's k-chunk table for a tile of row pitch `pitch` in block slots of `tblk` bytes
+            auto sp_table = [&](int pitch, int tblk) {
+                std::vector<int> tab((size_t)K * 4, 0);
+                walk([&](int st, int gi, int b, Chunk c) {
+                    tab[(size_t)st * 4 + gi] = (P->nblk == 1 ? 0 : b * tblk) + (c.tap / KS) * pitch + (c.tap % KS) * sg * 16 + c.cc * 16;
+                });
+                return tab;
+            };
+            // LDS of one kernel at one tile width: block slots | weight ring of rk steps | store patch | k-chunk table | flags
+            auto lay_out = [&](MfmaPlan::SpLayout& L, int pitch, int tblk, int slots, int rk, int patch_b, int tab_b, int flag_b) {
+                L.ok = true; L.row_pitch = pitch; L.TBLK = tblk; L.RK = rk;
+                L.ring_off = slots * tblk; L.patch_off = L.ring_off + rk * NT * 1024; L.tab_off = L.patch_off + patch_b;
+                L.flag_off = L.tab_off + tab_b; L.lds = L.flag_off + flag_b;
+            };
+            lay_out(P->sp_lay[0], rowp, TBLK, nslot, RK, patch ? patchb : 0, round_up(tabb, 1024), 64);      // (the table arrives in 1 KiB DMA pieces)
             std::vector<uint16_t> spk((size_t)S * NT * 512, 0);
-            for (int b = 0; b < P->nblk; ++b) {
-                const bool last = b == P->nblk - 1;
-                const auto& ord = last ? o_last : o_full;
-                const int ksb = last ? ksl : ksf, st0 = b * ksf, slot_base = P->nblk == 1 ? 0 : b * TBLK;
-                for (int st = 0; st < ksb; ++st)
-                    for (int gi = 0; gi < 4; ++gi) {
-                        const Chunk c = ord[(size_t)st * 4 + gi];
-                        if (c.cc < 0) continue;                          // dummy: offset 0 (finite data), zero weights
-                        tab[(size_t)(st0 + st) * 4 + gi] = slot_base + (c.tap / KS) * rowp + (c.tap % KS) * sg * 16 + c.cc * 16;
-                        for (int t = 0; t < NT; ++t)
-                            for (int p16 = 0; p16 < 16; ++p16) {
-                                uint16_t* o = &spk[(((size_t)(st0 + st) * NT + t) * 64 + gi * 16 + p16) * 8];
-                                for (int j = 0; j < 8; ++j) {
-                                    const int ci = true_ci((b * P->nc_full + c.cc) * 8 + j);
-                                    if (ci >= 0) o[j] = f2bf(wval(c.tap, ci, t * 16 + p16));
-                                }
-                            }
+            walk([&](int st, int gi, int b, Chunk c) {
+                for (int t = 0; t < NT; ++t)
+                    for (int p16 = 0; p16 < 16; ++p16) {
+                        uint16_t* o = &spk[(((size_t)st * NT + t) * 64 + gi * 16 + p16) * 8];
+                        for (int j = 0; j < 8; ++j) {
+                            const int ci = true_ci((b * P->nc_full + c.cc) * 8 + j);
+                            if (ci >= 0) o[j] = f2bf(wval(c.tap, ci, t * 16 + p16));
+                        }
                     }
-            }
-            PSEG_TRY(upload(&P->d_sp_tab, tab));
+            });
+            PSEG_TRY(upload(&P->sp_lay[0].d_tab, sp_table(rowp, TBLK)));
             PSEG_TRY(upload(&P->d_sp_wpk, spk));
             // the narrow tile (8 x 24, instances for the 80-channel layers): same chunk ORDER (same products in the same order: same
             // bits), offsets for its own row pitch, a ring as deep as its smaller tile allows
             if (NT == 5 && sg == 4 && op.pool_dst < 0 && !PSEG_KNOB("PSEG_NO_SP24")) {
-                auto& N = P->sp24;
                 const int TWN = 24, rowpn = sp_row_pitch(sg, TWN), TBLKn = round_up((8 + KS - 1) * rowpn, 16), tiles_n = nslot * TBLKn;
                 const int patchn = dq ? patchb : 4 * 2 * TWN * (NT * 32 + 8);
                 const int rkn = std::min((LDS_MAX - tiles_n - round_up(tabb, 1024) - 64 - patchn) / (NT * 1024), 16) & ~1;
                 if (rkn >= rk_min) {
-                    N.ok = true; N.row_pitch = rowpn; N.TBLK = TBLKn; N.RK = rkn;
-                    N.ring_off = tiles_n; N.patch_off = tiles_n + rkn * NT * 1024; N.tab_off = N.patch_off + patchn;
-                    N.flag_off = N.tab_off + round_up(tabb, 1024); N.lds = N.flag_off + 64;
-                    std::vector<int> tabn((size_t)K * 4, 0);
-                    for (int b = 0; b < P->nblk; ++b) {
-                        const bool last = b == P->nblk - 1;
-                        const auto& ord = last ? o_last : o_full;
-                        const int ksb = last ? ksl : ksf, st0 = b * ksf, slot_base = P->nblk == 1 ? 0 : b * TBLKn;
-                        for (int st = 0; st < ksb; ++st)
-                            for (int gi = 0; gi < 4; ++gi) {
-                                const Chunk c = ord[(size_t)st * 4 + gi];
-                                if (c.cc >= 0) tabn[(size_t)(st0 + st) * 4 + gi] = slot_base + (c.tap / KS) * rowpn + (c.tap % KS) * sg * 16 + c.cc * 16;
-                            }
-                    }
-                    PSEG_TRY(upload(&N.d_tab, tabn));
+                    lay_out(P->sp_lay[1], rowpn, TBLKn, nslot, rkn, patchn, round_up(tabb, 1024), 64);
+                    PSEG_TRY(upload(&P->sp_lay[1].d_tab, sp_table(rowpn, TBLKn)));
                 }
             }
-            // conv_sp2_kernel: two compute teams on a pool of four block slots (NT 3 / 4 layers; the fused transposed conv stays above)
-            if (!dq && NT <= 4 && !sp2_off()) {
+            // conv_sp2_kernel: two compute teams on a pool of four block slots (NT 3 / 4 layers; the fused transposed conv stays above).
+            // PSEG_SP2 (plan switch: tests, A/B): 0 off, 1 every eligible launch, 24 / 32 likewise with that tile width
+            const char* const sp2_sw = PSEG_KNOB("PSEG_SP2");
+            P->sp2_all = sp2_sw && atoi(sp2_sw) != 0;
+            P->sp2_tw = sp2_sw ? atoi(sp2_sw) : 0;
+            if (!dq && NT <= 4 && !(sp2_sw && atoi(sp2_sw) == 0)) {
                 for (int v = 0; v < 2; ++v) {
-                    auto& Q = P->sp2[v];
                     const int twv = v == 0 ? 32 : 24, rowpv = sp_row_pitch(sg, twv), TBLKv = round_up((8 + KS - 1) * rowpv, 16);
                     const int patchv = 8 * 8 * (NT * 32 + 8), tabv = round_up((K + 2) * 128, 1024);     // table: [k-step][lane group][column & 7]
                     const int rkv = std::min((LDS_MAX - SP2_NSLOT * TBLKv - patchv - tabv - 128) / (NT * 1024), 16) & ~1;
                     if (rkv < 10) continue;
-                    Q.ok = true; Q.TBLK = TBLKv; Q.RK = rkv;
-                    Q.ring_off = SP2_NSLOT * TBLKv; Q.patch_off = Q.ring_off + rkv * NT * 1024; Q.tab_off = Q.patch_off + patchv;
-                    Q.flag_off = Q.tab_off + tabv; Q.lds = Q.flag_off + 128;
+                    lay_out(P->sp2_lay[v], rowpv, TBLKv, SP2_NSLOT, rkv, patchv, tabv, 128);
                     std::vector<int> tabq((size_t)(K + 2) * 32, 0);       // (two rows beyond K: the loop looks its offsets up two steps ahead, unclamped)
-                    for (int b = 0; b < P->nblk; ++b) {
-                        const bool last = b == P->nblk - 1;
-                        const auto& ord = last ? o_last : o_full;
-                        const int ksb = last ? ksl : ksf, st0 = b * ksf;
-                        for (int st = 0; st < ksb; ++st)
-                            for (int gi = 0; gi < 4; ++gi) {
-                                const Chunk c = ord[(size_t)st * 4 + gi];
-                                if (c.cc < 0) continue;
-                                for (int p7 = 0; p7 < 8; ++p7) {
-                                    // four-chunk blocks are stored swizzled: chunk c of halo column x in slot c ^ 2 ((x >> 2) & 1); x = p + kx (+ 16)
-                                    const int slot = sg == 4 ? c.cc ^ ((((p7 + c.tap % KS) >> 2) & 1) << 1) : c.cc;
-                                    tabq[((size_t)(st0 + st) * 4 + gi) * 8 + p7] = (c.tap / KS) * rowpv + (c.tap % KS) * sg * 16 + slot * 16;   // inside the block's slot
-                                }
-                            }
-                    }
+                    walk([&](int st, int gi, int, Chunk c) {
+                        for (int p7 = 0; p7 < 8; ++p7) {
+                            // four-chunk blocks are stored swizzled: chunk c of halo column x in slot c ^ 2 ((x >> 2) & 1); x = p + kx (+ 16)
+                            const int slot = sg == 4 ? c.cc ^ ((((p7 + c.tap % KS) >> 2) & 1) << 1) : c.cc;
+                            tabq[((size_t)st * 4 + gi) * 8 + p7] = (c.tap / KS) * rowpv + (c.tap % KS) * sg * 16 + slot * 16;   // inside the block's slot
+                        }
+                    });
                     for (int r = K; r < K + 2; ++r) std::copy(tabq.begin() + (size_t)(K - 1) * 32, tabq.begin() + (size_t)K * 32, tabq.begin() + (size_t)r * 32);
-                    PSEG_TRY(upload(&Q.d_tab, tabq));
+                    PSEG_TRY(upload(&P->sp2_lay[v].d_tab, tabq));
                 }
             }
             if (!e.d_sp_err) {   // the engine's give-up record of conv_sp_kernel (engine_status)
@@ -4706,7 +4721,7 @@ int mfma_pack_op(Engine& e, Op& op, const std::vector<float>& w, const std::vect
             }
             if (PSEG_KNOB("PSEG_LOG_SP"))
                 fprintf(stderr, "[pseg] conv_sp plan %s: NT %d sigma %d fl %d nblk %d (nc %d / %d) K %d S %d blk_steps %d row_pitch %d TBLK %d RK %d lds %d\n", op.layer.c_str(),
-                        NT, sg, P->sp_fl, P->nblk, P->nc_full, P->nc_last, K, S, ksf, rowp, TBLK, RK, P->sp_lds);
+                        NT, sg, P->sp_fl, P->nblk, P->nc_full, P->nc_last, K, S, ksf, rowp, TBLK, RK, P->sp_lay[0].lds);
         }
     }
     if (deconv && op.into_tail >= 0) {
@@ -4924,22 +4939,136 @@ int mfma_pack_op(Engine& e, Op& op, const std::vector<float>& w, const std::vect
     return PSEG_OK;
 }
 
-template <int MT, int NT, int KS, int ST, int SG, int MODE, int FL, int NW = 4, int RR = 0>
-static int launch_inst(const MConv& a, const MfmaPlan& P, dim3 grid, hipStream_t st) {
-    static bool attr_set[64] = {false};
+// ---- launch plumbing ------------------------------------------------------------------------------------------------------------
+// How a bf16 conv launch is chosen: the plan's flags (mfma_pack_op: layer shape + plan switches) say which kernel families may
+// take the layer, the size predicates below (canvas, page slots, CUs) say which of them pays for THIS launch, and mfma_launch_conv
+// asks the routes in a fixed order.  A route answers PSEG_OK (launched), ROUTE_NO (not this route: ask the next) or an error (< 0).
+constexpr int ROUTE_NO = 1;
+
+// what a launch knows beyond its plan
+struct Extent {
+    int Hout, Wout;   // output pixels of one page
+    int tiles;        // tiles of the plan's own shape per page (the plain launch's grid.x)
+    int pages;        // page slots this launch covers (layer-major launches of a page unit, mfma_op_batchable), else 1
+    int cus, dev;     // compute units of the current device, its index
+};
+
+// compute units of the current device (cached per device: persistent kernels launch one workgroup per CU)
+static int device_cus(int* dev_out = nullptr) {
+    static int cache[64] = {0};
     int dev = 0;
-    PSEG_HIP(hipGetDevice(&dev));
+    if (hipGetDevice(&dev) != hipSuccess) return 256;
+    if (dev_out) *dev_out = dev;
+    int& n = cache[dev & 63];
+    if (n == 0 && (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1)) n = 256;
+    return n;
+}
+
+// Every conv kernel with dynamic LDS is launched here: the CU's whole 160 KB allowed once per device and kernel, the launch, its error.
+template <auto KERNEL, typename Arg>
+static int launch_lds(const Arg& a, dim3 grid, unsigned threads, int lds, int dev, hipStream_t st) {
+    static bool attr_set[64] = {false};
     if (!attr_set[dev & 63]) {
-        PSEG_HIP(hipFuncSetAttribute((const void*)conv_mfma_kernel<MT, NT, KS, ST, SG, MODE, FL, NW, RR>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        PSEG_HIP(hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         attr_set[dev & 63] = true;
     }
-    conv_mfma_kernel<MT, NT, KS, ST, SG, MODE, FL, NW, RR><<<grid, NW * 64, P.lds_bytes, st>>>(a);
+    KERNEL<<<grid, threads, lds, st>>>(a);
+    PSEG_HIP(hipGetLastError());
     return PSEG_OK;
 }
 
-// Specialised instances of the hot fcn / fcn_skip layer shapes, then the runtime-generic fallback.
-static int launch_generic_any2(const MConv& a, const MfmaPlan& P, dim3 grid, hipStream_t st) {
+// the XCD bands of a launch of `units` workgroups' worth of work (PSEG_NO_XCD=1: plain order)
+static void xcd_bands(MConv& a, unsigned units) {
+    a.xq = PSEG_KNOB("PSEG_NO_XCD") ? -1 : (int)units / 8;
+    a.xr = (int)units % 8;
+}
+
+// ---- size predicates: what depends on the canvas, the page slots or the device, each decided in one place --------------------------
+// 16-row tiles (eight waves) when they still fill the chip (one workgroup per CU).  Measured (MI355X, 2048x1536): they pay off where
+// the layer's whole weight set then stays resident in LDS (conv3: 80 -> 68 us); with a streamed ring they only tie (the halved
+// weight traffic is offset by losing the second workgroup's overlap).
+static int nw_wanted(const MfmaPlan& P, int Hout, int Wout) {
+    return (cdiv(Wout, TW) * cdiv(Hout, 16) >= 224 && sigma_for(P.nc_full) == 6 && !P.wg3) ? 8 : 4;
+}
+
+// Where conv_sp_kernel pays (same box, us per layer, conv_sp_kernel vs conv_mfma_kernel): the 80-channel layers always (2048x1536: conv7
+// 20.5 vs 27.0, deconv1 + deconv2 30.4 vs 39.3; 4096x3072: 48.7 vs 73.1, 75.3 vs 112.1 -- their five cout tiles leave conv_mfma_kernel two
+// workgroups per CU at best); the 40- / 60-channel layers while a launch is one round of tiles (1024x768: 14.7 / 19.7 / 26.7 vs
+// 19.4 / 25.5 / 37.0) -- with several tiles per CU three co-resident conv_mfma_kernel workgroups (three waves per SIMD, each
+// hiding the others' fragment reads) still beat one compute wave per SIMD by 3-10 %.  PSEG_SP_ALL=1: every eligible layer.
+static bool sp_pays(const MfmaPlan& P, const Extent& x) {
+    return P.sp_NT == 5 || x.tiles * x.pages <= x.cus || PSEG_KNOB("PSEG_SP_ALL");
+}
+
+// conv_sp_kernel on tiles of 8 x 24 where they need fewer pixel columns per CU than tiles of 8 x 32: rounds of the launch x tile width
+// (a 2048x1536 page at 1/8 resolution: 192 wide tiles on 256 CUs = 32 columns each, or 256 narrow ones = 24).  *tiles: per page.
+static bool sp_narrow(const MfmaPlan& P, const Extent& x, int* tiles) {
+    const int tiles24 = cdiv(x.Wout, 24) * cdiv(x.Hout, 8);
+    const bool narrow = P.sp_lay[1].ok && cdiv(tiles24 * x.pages, x.cus) * 24 < cdiv(x.tiles * x.pages, x.cus) * 32;
+    *tiles = narrow ? tiles24 : x.tiles;
+    return narrow;
+}
+
+// conv_sp2_kernel (two compute teams) for the 40- / 60-channel layers once every CU gets a tile pair: the layout ([0] 8 x 32, [1]
+// 8 x 24) this launch takes, or -1.  Tile width by rounds of pairs x width: a 2048x1536 page at 1/4 resolution is 768 tiles of
+// 8 x 32 (1.5 pairs per CU: two rounds) or 1024 of 8 x 24 (exactly two pairs per CU).  *tiles: per page.
+static int sp2_pick(const MfmaPlan& P, const Extent& x, int* tiles) {
+    int bestv = -1, best_cost = 1 << 30;
+    auto tiles_of = [&](int v) { return cdiv(x.Wout, v == 0 ? 32 : 24) * cdiv(x.Hout, 8); };
+    for (int v = 0; v < 2; ++v) {
+        if (!P.sp2_lay[v].ok) continue;
+        const int cost = cdiv((tiles_of(v) * x.pages + 1) / 2, x.cus) * (v == 0 ? 32 : 24);
+        if (cost < best_cost) { best_cost = cost; bestv = v; }
+    }
+    if ((P.sp2_tw == 24 || P.sp2_tw == 32) && P.sp2_lay[P.sp2_tw == 24].ok) bestv = P.sp2_tw == 24;
+    if (bestv < 0) return -1;
+    *tiles = tiles_of(bestv);
+    // Where it runs by default: measured on the 2048x1536 page and in 32-page units against conv_mfma_kernel (tools/gpu_r05_sp2_ab.sh,
+    // gpu_r05_sp2_pages.sh, us per page): deconv3 60.8-61.9 vs 60.6 / 47.7-48.4 vs 50.2-50.7; conv6 41.2-41.9 vs 41.8-42.3 / 33.1 vs
+    // 30.2; conv5 32.1-32.5 vs 31.5-32.0 (before its table took the ring's room) -- a tie on the single page, a gain only for the
+    // three-cout-tile layer in page units.  PSEG_SP2=1 / 24 / 32 (plan switch): every eligible layer.
+    const int npairs = (*tiles * x.pages + 1) / 2;
+    return ((npairs >= x.cus && P.sp_NT == 3 && x.pages > 1) || P.sp2_all) ? bestv : -1;
+}
+
+// conv_pp_kernel and conv12_ws_kernel keep TWO input tiles of this size in LDS
+static int tile_bytes(const MfmaPlan& P) { return round_up(P.THH * P.row_pitch, 16); }
+
+// conv_pp_kernel: the weights fit LDS beside two tiles, and every CU's workgroup walks at least two of them
+static bool pp_pays(const MfmaPlan& P, const Extent& x, int* lds) {
+    *lds = 2 * tile_bytes(P) + P.ks_full * 2560 + 16 + round_up(P.ks_full * 16, 16);
+    return *lds <= 160 * 1024 && x.tiles >= 2 * x.cus;
+}
+
+// conv12_ws_kernel: its LDS fits and the plan has the row pitch and the k-steps the kernel is compiled for
+static bool ws_fits(const MfmaPlan& P, int* lds) {
+    *lds = WS_TILE0 + 2 * tile_bytes(P) + P.ks_full * P.NT * 1024 + round_up(P.ks_full * 16, 16) + 4 * (2 * 9 * 96 + 16);
+    return *lds <= 160 * 1024 && P.GK >= P.ks_full && P.row_pitch == WS_ROWP && P.ks_full == (P.pairc2 ? WS_KSTEPS_PAIR : WS_KSTEPS);
+}
+
+// Single-block stride-2 layers with resident weights as PERSISTENT workgroups (res_unet 32 -> 64), when a page has more than two
+// rounds of tiles: the workgroups to launch, else 0.  A tile of theirs is 9 k-steps -- tools/trace_layers.py: ring issue 1.6 k +
+// table 2.1 k + tile stage 5.5 k + wait 1.0 k cycles around a k-loop of 3.3 k; the walk stages weights and table once per workgroup:
+// 103 -> 96 and 99 -> 85 us on one box.  (The 32 -> 32 full-resolution layer lost as a persistent instance, 152 -> 157-167 us: it
+// gives up the epilogue's LDS store patch, which lives in the resident weights' place.)
+static unsigned s2_persists(const MfmaPlan& P, const Extent& x) {
+    const unsigned slots = (P.wg3 ? 3u : 2u) * (unsigned)x.cus;
+    return (x.pages == 1 && (unsigned)x.tiles > 2 * slots) ? slots : 0u;
+}
+
+// ---- conv_mfma_kernel: specialised instances of the hot layer shapes, then the runtime-generic fallback --------------------------
+template <int MT, int NT, int KS, int ST, int SG, int MODE, int FL, int NW = 4, int RR = 0>
+static int launch_inst(const MConv& a, const MfmaPlan& P, dim3 grid, int dev, hipStream_t st) {
+    return launch_lds<conv_mfma_kernel<MT, NT, KS, ST, SG, MODE, FL, NW, RR>>(a, grid, NW * 64, P.lds_bytes, dev, st);
+}
+
+#define PSEG_TRY_INST8(MT_, NT_, KS_, ST_, SG_, MODE_, FL_)                                         \
+    if (P.NW == 8 && P.MT == MT_ && P.NT == NT_ && ks == KS_ && st_ == ST_ && sg == SG_ && mode == MODE_ && fl == (FL_)) \
+        return launch_inst<MT_, NT_, KS_, ST_, SG_, MODE_, (FL_), 8>(a, P, grid, dev, st);
+#define PSEG_TRY_INST(MT_, NT_, KS_, ST_, SG_, MODE_, FL_)                                          \
+    if (P.spec && P.MT == MT_ && P.NT == NT_ && ks == KS_ && st_ == ST_ && sg == SG_ && mode == MODE_ && fl == (FL_)) \
+        return launch_inst<MT_, NT_, KS_, ST_, SG_, MODE_, (FL_)>(a, P, grid, dev, st);
+static int launch_generic_any2(const MConv& a, const MfmaPlan& P, dim3 grid, int dev, hipStream_t st) {
     const int mode = a.tail ? MODE_TAIL : (a.deconv ? MODE_DECONV : MODE_CONV);
     const int fl = (a.pool_dst ? FL_POOL : 0) | (a.add ? FL_ADD : 0) | (a.in_relu ? FL_INRELU : 0) |
                    (a.up0 ? FL_UP0 : 0) | (a.up1 ? FL_UP1 : 0) | (a.f1_img ? FL_FUSE1 : 0) | (a.ntiles > 0 ? FL_PERSIST : 0) |
@@ -4947,23 +5076,16 @@ static int launch_generic_any2(const MConv& a, const MfmaPlan& P, dim3 grid, hip
     const int sg = a.sigma, st_ = a.stride, ks = P.KS;
     if (a.f1_img && !(P.MT == 8 && P.NT == 2 && ks == 5 && sg == 3 && mode == MODE_CONV && (fl & ~(FL_PERSIST | FL_SKIPLOG)) == (FL_POOL | FL_FUSE1)))
         return fail(PSEG_EUNSUPPORTED, "first-layer fusion has no kernel instance for this shape");
-#define PSEG_TRY_INST8(MT_, NT_, KS_, ST_, SG_, MODE_, FL_)                                         \
-    if (P.NW == 8 && P.MT == MT_ && P.NT == NT_ && ks == KS_ && st_ == ST_ && sg == SG_ && mode == MODE_ && fl == (FL_)) \
-        return launch_inst<MT_, NT_, KS_, ST_, SG_, MODE_, (FL_), 8>(a, P, grid, st);
     PSEG_TRY_INST8(4, 3, 5, 1, 6, MODE_CONV, 0)           // conv3, deconv3 (16-row tiles)
     PSEG_TRY_INST8(4, 3, 5, 1, 6, MODE_CONV, FL_POOL)     // conv4
     PSEG_TRY_INST8(4, 4, 5, 1, 6, MODE_CONV, 0)           // conv5
     PSEG_TRY_INST8(4, 4, 5, 1, 6, MODE_CONV, FL_POOL)     // conv6
     PSEG_TRY_INST8(4, 4, 3, 1, 6, MODE_CONV, 0)           // unet k3 convs, 16-row tiles
     PSEG_TRY_INST8(4, 4, 3, 1, 6, MODE_CONV, FL_POOL)
-#undef PSEG_TRY_INST8
     // (six-wave workgroups -- 12-row tiles, two per CU, three waves per SIMD -- were measured too: conv3 113 vs
     // 79 us, conv4 131 vs 93 us; 2064 workgroups on 512 slots leave a nearly empty fifth round and the smaller
     // ring doubles the group barriers)
     if (P.NW != 4) return fail(PSEG_EUNSUPPORTED, "no %d-wave kernel instance for this layer shape", P.NW);
-#define PSEG_TRY_INST(MT_, NT_, KS_, ST_, SG_, MODE_, FL_)                                          \
-    if (!PSEG_KNOB("PSEG_GENERIC") && P.MT == MT_ && P.NT == NT_ && ks == KS_ && st_ == ST_ && sg == SG_ && mode == MODE_ && fl == (FL_)) \
-        return launch_inst<MT_, NT_, KS_, ST_, SG_, MODE_, (FL_)>(a, P, grid, st);
     PSEG_TRY_INST(8, 2, 5, 1, 3, MODE_CONV, FL_POOL | FL_FUSE1 | FL_PERSIST | FL_SKIPLOG)   // conv1 + conv2 fused, persistent, skip logits instead of the tensor
     PSEG_TRY_INST(8, 2, 5, 1, 3, MODE_CONV, FL_POOL | FL_FUSE1 | FL_SKIPLOG)
     PSEG_TRY_INST(8, 2, 5, 1, 3, MODE_CONV, FL_POOL | FL_FUSE1 | FL_PERSIST)   // conv1 + conv2 fused, persistent
@@ -4974,8 +5096,8 @@ static int launch_generic_any2(const MConv& a, const MfmaPlan& P, dim3 grid, hip
     PSEG_TRY_INST(4, 3, 5, 1, 6, MODE_CONV, FL_POOL)      // conv4
     // row reuse (MfmaPlan::rowreuse): the instance is compiled for the plan's weight-group size
     if (a.rowreuse && P.GK == 4 && P.ks_full == 25 && P.ks_last == 25 && !a.trace && P.MT == 4 && P.NT == 3 && ks == 5 && st_ == 1 && sg == 4 &&
-        mode == MODE_CONV && fl == 0 && !PSEG_KNOB("PSEG_GENERIC"))
-        return launch_inst<4, 3, 5, 1, 4, MODE_CONV, 0, 4, 4>(a, P, grid, st);   // conv3 (small pages), deconv3
+        mode == MODE_CONV && fl == 0 && P.spec)
+        return launch_inst<4, 3, 5, 1, 4, MODE_CONV, 0, 4, 4>(a, P, grid, dev, st);   // conv3 (small pages), deconv3
     PSEG_TRY_INST(4, 3, 5, 1, 4, MODE_CONV, 0)            // conv3, deconv3: dense 64-byte pixels, three workgroups per CU
     PSEG_TRY_INST(4, 3, 5, 1, 5, MODE_CONV, FL_POOL)      // conv4: dense 80-byte pixels, three workgroups per CU
     PSEG_TRY_INST(4, 3, 5, 1, 5, MODE_CONV, 0)
@@ -5007,11 +5129,7 @@ static int launch_generic_any2(const MConv& a, const MfmaPlan& P, dim3 grid, hip
     if (fl & FL_SKIPLOG) return fail(PSEG_EUNSUPPORTED, "skip-logits fusion has no kernel instance for this shape");
     if (fl & FL_DQ) return fail(PSEG_EUNSUPPORTED, "the fused transposed conv has no kernel instance for this shape (MT %d NT %d k %d sigma %d flags %d)", P.MT, P.NT, ks, sg, fl);
     PSEG_TRY_INST(4, 4, 2, 1, 6, MODE_CONV, FL_UP0)       // unet: UpSampling2D + k2 conv
-    // single-block stride-2 layers with resident weights as PERSISTENT workgroups (res_unet 32 -> 64): a tile of theirs is 9 k-steps --
-    // tools/trace_layers.py: ring issue 1.6 k + table 2.1 k + tile stage 5.5 k + wait 1.0 k cycles around a k-loop of 3.3 k; the walk stages
-    // weights and table once per workgroup: 103 -> 96 and 99 -> 85 us on one box.  (The 32 -> 32 full-resolution layer lost as a
-    // persistent instance, 152 -> 157-167 us: it gives up the epilogue's LDS store patch, which lives in the resident weights' place.)
-    PSEG_TRY_INST(2, 4, 3, 2, 4, MODE_CONV, FL_PERSIST)
+    PSEG_TRY_INST(2, 4, 3, 2, 4, MODE_CONV, FL_PERSIST)   // res_unet encoder, persistent (s2_persists)
     PSEG_TRY_INST(2, 4, 3, 2, 4, MODE_CONV, FL_INRELU | FL_PERSIST)
     PSEG_TRY_INST(2, 4, 3, 2, 4, MODE_CONV, 0)            // res_unet encoder: stride-2 shortcut conv (four-row tiles, dense de-interleaved tile)
     PSEG_TRY_INST(2, 4, 3, 2, 4, MODE_CONV, FL_INRELU)    // res_unet encoder: stride-2 first conv of the block
@@ -5024,58 +5142,60 @@ static int launch_generic_any2(const MConv& a, const MfmaPlan& P, dim3 grid, hip
         PSEG_TRY_INST(4, 4, 1, 1, 10, MODE_TAIL, 0)       // deconv5 + logits (fcn_skip)
         PSEG_TRY_INST(4, 4, 1, 1, 6, MODE_TAIL, 0)        // deconv5 + logits (fcn)
     }
-#undef PSEG_TRY_INST
     if (PSEG_KNOB("PSEG_LOG_GENERIC"))
         fprintf(stderr, "[pseg] generic instance: MT %d NT %d KS %d stride %d sigma %d mode %d flags %d\n", P.MT, P.NT, ks, P.stride, sg, mode, fl);
     if (P.MT != 4 && P.MT != 8) return fail(PSEG_EUNSUPPORTED, "no runtime-generic kernel for %d pixel tiles per wave", P.MT);
     if (P.MT == 8) {
-        if (P.NT == 1) return launch_inst<8, 1, -1, -1, -1, -1, -1>(a, P, grid, st);
-        return launch_inst<8, 2, -1, -1, -1, -1, -1>(a, P, grid, st);
+        if (P.NT == 1) return launch_inst<8, 1, -1, -1, -1, -1, -1>(a, P, grid, dev, st);
+        return launch_inst<8, 2, -1, -1, -1, -1, -1>(a, P, grid, dev, st);
     }
     switch (P.NT) {
-        case 1: return launch_inst<4, 1, -1, -1, -1, -1, -1>(a, P, grid, st);
-        case 2: return launch_inst<4, 2, -1, -1, -1, -1, -1>(a, P, grid, st);
-        case 3: return launch_inst<4, 3, -1, -1, -1, -1, -1>(a, P, grid, st);
-        case 4: return launch_inst<4, 4, -1, -1, -1, -1, -1>(a, P, grid, st);
-        case 5: return launch_inst<4, 5, -1, -1, -1, -1, -1>(a, P, grid, st);
+        case 1: return launch_inst<4, 1, -1, -1, -1, -1, -1>(a, P, grid, dev, st);
+        case 2: return launch_inst<4, 2, -1, -1, -1, -1, -1>(a, P, grid, dev, st);
+        case 3: return launch_inst<4, 3, -1, -1, -1, -1, -1>(a, P, grid, dev, st);
+        case 4: return launch_inst<4, 4, -1, -1, -1, -1, -1>(a, P, grid, dev, st);
+        case 5: return launch_inst<4, 5, -1, -1, -1, -1, -1>(a, P, grid, dev, st);
     }
     return fail(PSEG_EUNSUPPORTED, "no kernel instance for NT=%d (sigma %d)", P.NT, sg);
 }
+#undef PSEG_TRY_INST
+#undef PSEG_TRY_INST8
 
-static int launch_generic_any(const MConv& a0, const MfmaPlan& P, dim3 grid, hipStream_t st, const char* layer) {
+// Runs `launch`.  The diagnostic build, where `want`, first hangs a zeroed buffer of `words` stamps into *slot and, after a launch
+// that took place, writes it into the trace directory as <stem><layer>.bin -- trace_<layer> (tools/trace_layers.py), sp_trace_<layer>
+// (sp_trace.py), sp2_trace_<layer> (sp2_trace.py), ws_trace (ws_trace.py).  The release library neither stamps nor writes files.
+template <class F>
+static int with_trace(bool want, unsigned long long** slot, size_t words, const char* stem, const char* layer, hipStream_t st, F launch) {
 #if PSEG_DIAG
-    const char* tr = PSEG_DIAG_KNOB("PSEG_TRACE");
-    if (tr && strcmp(tr, layer) == 0) {
-        MConv a = a0;
-        const size_t n = (size_t)grid.x * grid.y * 12;
-        PSEG_HIP(hipMalloc((void**)&a.trace, n * 8));
-        PSEG_HIP(hipMemset(a.trace, 0, n * 8));
-        int rc = launch_generic_any2(a, P, grid, st);
+    if (want) {
+        PSEG_HIP(hipMalloc((void**)slot, words * 8));
+        PSEG_HIP(hipMemset(*slot, 0, words * 8));
+        const int rc = launch();
+        if (rc != PSEG_OK) { (void)hipFree(*slot); return rc; }
         PSEG_HIP(hipStreamSynchronize(st));
-        std::vector<unsigned long long> h(n);
-        PSEG_HIP(hipMemcpy(h.data(), a.trace, n * 8, hipMemcpyDeviceToHost));
-        (void)hipFree(a.trace);
+        std::vector<unsigned long long> h(words);
+        PSEG_HIP(hipMemcpy(h.data(), *slot, words * 8, hipMemcpyDeviceToHost));
+        (void)hipFree(*slot);
         std::string fn = std::string("gpurun_out/trace_") + layer + ".bin";
-        if (FILE* f = fopen(fn.c_str(), "wb")) { fwrite(h.data(), 8, n, f); fclose(f); }
+        fn.replace(fn.find("trace_"), 6, stem);      // (the directory is spelled once; the other kernel families' files differ in the stem)
+        if (FILE* f = fopen(fn.c_str(), "wb")) { fwrite(h.data(), 8, words, f); fclose(f); }
         return rc;
     }
 #else
-    (void)layer;
+    (void)want; (void)slot; (void)words; (void)stem; (void)layer; (void)st;
 #endif
-    return launch_generic_any2(a0, P, grid, st);
+    return launch();
 }
 
-// compute units of the current device (cached per device: persistent kernels launch one workgroup per CU)
-static int device_cus(int* dev_out = nullptr) {
-    static int cache[64] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 256;
-    if (dev_out) *dev_out = dev;
-    int& n = cache[dev & 63];
-    if (n == 0 && (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1)) n = 256;
-    return n;
+// (diagnostic build, PSEG_TRACE=<layer>: 12 stamps per workgroup -> trace_<layer>.bin)
+static int launch_generic_any(MConv& a, const MfmaPlan& P, dim3 grid, int dev, hipStream_t st, const char* layer) {
+    const char* tr = PSEG_DIAG_KNOB("PSEG_TRACE");
+    return with_trace(tr && strcmp(tr, layer) == 0, &a.trace, (size_t)grid.x * grid.y * 12, "trace_", layer, st,
+                      [&] { return launch_generic_any2(a, P, grid, dev, st); });
 }
 
+// ---- the kernel-argument records ----------------------------------------------------------------------------------------------------
+// what a conv and a transposed conv share
 static void fill_common(const Engine& e, const Op& op, const MfmaPlan& P, MConv& a) {
     const Tensor& s0 = e.tensors[op.src0];
     const Tensor* s1 = op.src1 >= 0 ? &e.tensors[op.src1] : nullptr;
@@ -5110,56 +5230,18 @@ static void fill_common(const Engine& e, const Op& op, const MfmaPlan& P, MConv&
     if (PSEG_KNOB("PSEG_NO_LDS_STORE")) a.dbg |= 32;   // direct 8-byte stores instead of the LDS patch (same bytes)
 }
 
-int mfma_launch_conv(Engine& e, Op& op, hipStream_t st) {
-    auto* P = (MfmaPlan*)op.plan;
-    if (!P) return fail(PSEG_EINVAL, "layer %s has no bf16 plan", op.layer.c_str());
+// the logits layer fused behind a conv or a transposed conv: its weights and the page's outputs
+static void fill_tail(const Engine& e, const Op& op, const MfmaPlan& P, MConv& a) {
+    a.tail_C = e.ops[op.tail_logits].Cout;
+    a.H0 = e.H; a.W0 = e.W;
+    a.tail_wa = P.d_tail_wa; a.tail_wb = P.d_tail_wb; a.tail_bias = P.d_tail_bias;
+    a.out_logits = e.cur_logits; a.out_probs = e.cur_probs; a.out_labels = e.cur_labels; a.out_labels_u8 = e.cur_labels_u8;
+}
+
+// a conv's MConv: padding, pool, add, tail logits, skip-logits plane, fused first layer, fused transposed conv, and the plain launch's grid
+static int fill_conv(Engine& e, const Op& op, MfmaPlan& P, MConv& a, dim3* grid) {
     const Tensor& d = e.tensors[op.dst];
-    if (op.relu_dst >= 0 && (P->kind != PLAN_GENERIC || op.pool_dst >= 0 || op.tail_logits >= 0 || op.skiplog >= 0 || op.fuse1 >= 0))
-        return fail(PSEG_EUNSUPPORTED, "layer %s: the ReLU'd second output exists only in the direct-store epilogue", op.layer.c_str());
-    if (P->kind == PLAN_CONV1) {
-        const uint8_t* img = e.cur_img;  // raw uint8 page (x/255 and pad-to-32 are fused)
-        if ((P->KS == 3 && (op.Cout == 64 || op.Cout == 32))) {
-            constexpr int RB = 16;
-            dim3 g(cdiv(e.Wp, 64), cdiv(e.Hp, 4 * RB));
-            if (op.Cout == 64) conv1_rows_kernel<3, 64, RB><<<g, 256, 0, st>>>(img, e.H, e.W, e.Hp, e.Wp, P->d_wf, P->d_bias, (uint16_t*)d.d, op.relu);
-            else conv1_rows_kernel<3, 32, RB><<<g, 256, 0, st>>>(img, e.H, e.W, e.Hp, e.Wp, P->d_wf, P->d_bias, (uint16_t*)d.d, op.relu);
-            return PSEG_OK;
-        }
-        dim3 g1(e.Wp / 32, cdiv(e.Hp, 16));
-        uint16_t* o = (uint16_t*)d.d;
-        if (P->KS == 5 && op.Cout == 20) conv1_mfma_kernel<5, 20><<<g1, 256, 0, st>>>(img, e.H, e.W, e.Wp, P->d_wpk, P->d_bias, o, op.relu);
-        else if (P->KS == 3 && op.Cout == 64) conv1_mfma_kernel<3, 64><<<g1, 256, 0, st>>>(img, e.H, e.W, e.Wp, P->d_wpk, P->d_bias, o, op.relu);
-        else if (P->KS == 3 && op.Cout == 32) conv1_mfma_kernel<3, 32><<<g1, 256, 0, st>>>(img, e.H, e.W, e.Wp, P->d_wpk, P->d_bias, o, op.relu);
-        else conv1_mfma_kernel<1, 32><<<g1, 256, 0, st>>>(img, e.H, e.W, e.Wp, P->d_wpk, P->d_bias, o, op.relu);
-        return PSEG_OK;
-    }
-    if (P->kind == PLAN_UPSPLIT) {
-        const Tensor& s0 = e.tensors[op.src0];
-        return upsplit_launch(P->upsplit, (const uint16_t*)s0.d, e.tH(s0), e.tW(s0), (uint16_t*)d.d, op.relu, st);
-    }
-    if (P->nw8_ok) {
-        // 16-row tiles when they still fill the chip (one workgroup per CU); re-pack on a change
-        // Measured (MI355X, 2048x1536): 16-row tiles pay off where the layer's whole weight set then
-        // stays resident in LDS (conv3: 80 -> 68 us); with a streamed ring they only tie (the halved
-        // weight traffic is offset by losing the second workgroup's overlap).
-        const int want = (cdiv(e.tW(d), TW) * cdiv(e.tH(d), 16) >= 224 && sigma_for(P->nc_full) == 6 && !P->wg3) ? 8 : 4;
-        const char* const ev = nullptr;
-        if (want != P->NW && want != P->nw_tried) {
-            const std::vector<float> w = P->w_keep, b = P->b_keep;
-            op.nw_hint = want;
-            PSEG_TRY(mfma_pack_op(e, op, w, b));
-            P = (MfmaPlan*)op.plan;
-            P->nw_tried = want;      // the shape may not have an instance for `want`: do not re-pack every launch
-            if (want == 8 && !P->nw8_resident && !ev) {   // ring only: keep two workgroups per CU
-                op.nw_hint = 4;
-                PSEG_TRY(mfma_pack_op(e, op, w, b));
-                P = (MfmaPlan*)op.plan;
-                P->nw8_ok = false;                        // decided for this engine
-            }
-        }
-    }
-    MConv a{};
-    fill_common(e, op, *P, a);
+    fill_common(e, op, P, a);
     a.Hout = e.tH(d);
     a.Wout = e.tW(d);
     a.stride = op.stride;
@@ -5172,44 +5254,28 @@ int mfma_launch_conv(Engine& e, Op& op, hipStream_t st) {
     if (op.pool_dst >= 0) { const Tensor& pt = e.tensors[op.pool_dst]; a.pool_bytes = (unsigned)((size_t)e.tH(pt) * e.tW(pt) * pt.Cs * 2); }
     a.add = op.add >= 0 ? (const uint16_t*)e.tensors[op.add].d : nullptr;
     a.deconv = 0;
-    if (op.tail_logits >= 0) {   // logits / softmax / argmax in this conv's epilogue
-        const Op& lg = e.ops[op.tail_logits];
-        a.tail_C = lg.Cout;
-        a.H0 = e.H;
-        a.W0 = e.W;
-        a.tail_wa = P->d_tail_wa;
-        a.tail_wb = P->d_tail_wb;
-        a.tail_bias = P->d_tail_bias;
-        a.out_logits = e.cur_logits;
-        a.out_probs = e.cur_probs;
-        a.out_labels = e.cur_labels;
-        a.out_labels_u8 = e.cur_labels_u8;
-    }
+    if (op.tail_logits >= 0) fill_tail(e, op, P, a);   // logits / softmax / argmax in this conv's epilogue
     if (op.skiplog >= 0) {
-        const size_t need = (size_t)a.Hout * a.Wout * P->skip_CP * 4;     // one page slot
-        if (need * e.pages > P->skiplog_bytes) {
+        const size_t need = (size_t)a.Hout * a.Wout * P.skip_CP * 4;     // one page slot
+        if (need * e.pages > P.skiplog_bytes) {
             PSEG_HIP(hipDeviceSynchronize());
-            (void)hipFree(P->d_skiplog);
-            P->d_skiplog = nullptr; P->skiplog_bytes = 0;
-            PSEG_HIP(hipMalloc((void**)&P->d_skiplog, need * e.pages));
-            P->skiplog_bytes = need * e.pages;
+            (void)hipFree(P.d_skiplog);
+            P.d_skiplog = nullptr; P.skiplog_bytes = 0;
+            PSEG_HIP(hipMalloc((void**)&P.d_skiplog, need * e.pages));
+            P.skiplog_bytes = need * e.pages;
         }
-        a.skip_logits = (float*)((char*)P->d_skiplog + (size_t)e.page * need);
-        a.skip_CP = P->skip_CP;
-        a.tail_wa = P->d_tail_wa;
+        a.skip_logits = (float*)((char*)P.d_skiplog + (size_t)e.page * need);
+        a.skip_CP = P.skip_CP;
+        a.tail_wa = P.d_tail_wa;
     }
     if (op.fuse1 >= 0) {
         const Op& c1 = e.ops[op.fuse1];
         auto* P1 = (MfmaPlan*)c1.plan;
         if (!P1 || P1->kind != PLAN_CONV1) return fail(PSEG_EINVAL, "fused first layer has no plan");
-        a.f1_img = e.cur_img;
-        a.f1_H = e.H;
-        a.f1_W = e.W;
-        a.f1_wpk = P1->d_wpk;
+        a.f1_img = e.cur_img; a.f1_H = e.H; a.f1_W = e.W;
+        a.f1_wpk = P1->d_wpk; a.f1_bias = P1->d_bias; a.f1_relu = c1.relu;
         a.f1_wpk32 = PSEG_KNOB("PSEG_NO_C32") ? nullptr : P1->d_wpk32;
-        a.f1_bias = P1->d_bias;
-        a.f1_relu = c1.relu;
-        a.lds_f1_off = P->lds_f1_off;
+        a.lds_f1_off = P.lds_f1_off;
     }
     if (op.dq_fuse >= 0) {
         const Op& dq = e.ops[op.dq_fuse];
@@ -5220,268 +5286,228 @@ int mfma_launch_conv(Engine& e, Op& op, hipStream_t st) {
         a.dq_bytes = (unsigned)((size_t)e.tH(qd) * e.tW(qd) * qd.Cs * 2);
         a.dst_bytes = 0;          // (the conv's own tensor is not stored)
     }
-    dim3 grid(cdiv(a.Wout, TW) * cdiv(a.Hout, P->NW * (P->MT / 2)), P->nblocks_n);
-    a.xq = PSEG_KNOB("PSEG_NO_XCD") ? -1 : (int)grid.x / 8;
-    a.xr = (int)grid.x % 8;
-    // persistent instance (PSEG_NO_PERSIST=1 disables): resident weights (NB == 1), single channel block, two
-    // workgroups per CU walking 12 tiles each: the 38 KB weight set and the k-chunk table are staged once per
-    // workgroup instead of once per tile.  Worth 1-3 % on the fused conv1+conv2 kernel (the DMA it saves was
-    // mostly hidden by the co-resident workgroup); needs the per-trip opaque lane ids to keep two waves per SIMD.
-    // wave-specialised persistent kernel (conv12_ws_kernel): one 512-thread workgroup per CU, two input tiles + the resident
-    // weights in LDS.  PSEG_NO_WS=1 falls back to the every-wave-does-everything fused instance below.
-    // streamed-weights persistent kernel with loader waves (conv_sp_kernel): conv5, conv6, conv7, deconv1 (+ deconv2), deconv3
-    if (P->sp && !a.trace && !PSEG_KNOB("PSEG_NO_SP") && !PSEG_KNOB("PSEG_GENERIC") && (op.dq_fuse >= 0) == ((P->sp_fl & SP_DQ) != 0) &&
-        (op.pool_dst >= 0) == ((P->sp_fl & SP_POOL) != 0)) {
-        int dev = 0;
-        const int cus_sp = device_cus(&dev);
-        // Where it pays (same box, us per layer, conv_sp_kernel vs conv_mfma_kernel): the 80-channel layers always (2048x1536: conv7 20.5 vs
-        // 27.0, deconv1 + deconv2 30.4 vs 39.3; 4096x3072: 48.7 vs 73.1, 75.3 vs 112.1 -- their five cout tiles leave conv_mfma_kernel two
-        // workgroups per CU at best); the 40- / 60-channel layers while a launch is one round of tiles (1024x768: 14.7 / 19.7 / 26.7 vs
-        // 19.4 / 25.5 / 37.0) -- with several tiles per CU three co-resident conv_mfma_kernel workgroups (three waves per SIMD, each
-        // hiding the others' fragment reads) still beat one compute wave per SIMD by 3-10 %.  PSEG_SP_ALL=1: every eligible layer.
-        const bool sp_pays = P->sp_NT == 5 || (int)grid.x * (e.batch_pages > 1 ? e.batch_pages : 1) <= cus_sp || PSEG_KNOB("PSEG_SP_ALL");
-        SConv c{};
-        c.src0 = a.src0; c.src1 = a.src1; c.nch0 = a.nch0; c.nch1 = a.nch1; c.bytes0 = a.bytes0; c.bytes1 = a.bytes1;
-        c.Hin = a.Hin; c.Win = a.Win; c.Hout = a.Hout; c.Wout = a.Wout; c.pt = a.pt; c.pl = a.pl; c.relu = a.relu;
-        c.nblk = P->sp_nblk; c.nc_full = P->sp_nc_full; c.nc_last = P->sp_nc_last; c.K = P->sp_K; c.S = P->sp_S; c.blk_steps = P->sp_blk_steps;
-        c.tab = P->d_sp_tab; c.wpk = P->d_sp_wpk; c.bias = P->d_bias;
-        c.row_pitch = P->sp_row_pitch; c.TBLK = P->sp_TBLK; c.RK = P->sp_RK;
-        c.lds_ring_off = P->sp_ring_off; c.lds_patch_off = P->sp_patch_off; c.lds_tab_off = P->sp_tab_off; c.lds_flag_off = P->sp_flag_off;
-        // tiles of 8 x 24 where they need fewer pixel columns per CU than tiles of 8 x 32: rounds of the launch x tile width (a
-        // 2048x1536 page at 1/8 resolution: 192 wide tiles on 256 CUs = 32 columns each, or 256 narrow ones = 24)
-        const int npg_ = e.batch_pages > 1 ? e.batch_pages : 1;
-        const int tiles24 = cdiv(a.Wout, 24) * cdiv(a.Hout, 8);
-        const bool narrow = P->sp24.ok && cdiv(tiles24 * npg_, cus_sp) * 24 < cdiv((int)grid.x * npg_, cus_sp) * 32;
-        int tiles_pp = (int)grid.x, sp_lds = P->sp_lds;
-        if (narrow) {
-            const auto& N = P->sp24;
-            c.tab = N.d_tab; c.row_pitch = N.row_pitch; c.TBLK = N.TBLK; c.RK = N.RK;
-            c.lds_ring_off = N.ring_off; c.lds_patch_off = N.patch_off; c.lds_tab_off = N.tab_off; c.lds_flag_off = N.flag_off;
-            tiles_pp = tiles24; sp_lds = N.lds;
-        }
-        c.dst = a.dst; c.dst_bytes = a.dst_bytes; c.nch_out = a.nch_out; c.pool_dst = a.pool_dst; c.pool_bytes = a.pool_bytes;
-        c.dq_bias = a.dq_bias; c.dq_dst = a.dq_dst; c.dq_bytes = a.dq_bytes; c.dq_nch = a.dq_nch; c.dq_relu = a.dq_relu;
-        const int npg = e.batch_pages > 1 ? e.batch_pages : 1;               // page slots of this launch: a tile index carries the page
-        // ---- two compute teams (conv_sp2_kernel): the 40- / 60-channel layers once every CU gets a tile pair --------------------------
-        // Tile width by rounds of pairs x width, as above: a 2048x1536 page at 1/4 resolution is 768 tiles of 8 x 32 (1.5 pairs per CU: two
-        // rounds) or 1024 of 8 x 24 (exactly two pairs per CU).
-        if ((!tracing_req(op) || PSEG_DIAG_KNOB("PSEG_SP2_TRACE")) && (P->sp2[0].ok || P->sp2[1].ok) && !sp2_off()) {
-            const char* const sp2_sw = PSEG_KNOB("PSEG_SP2");   // plan switch (tests, A/B): 0 off, 1 every eligible launch, 24 / 32 likewise with that tile width
-            int bestv = -1, best_cost = 1 << 30, best_tiles = 0;
-            for (int v = 0; v < 2; ++v) {
-                if (!P->sp2[v].ok) continue;
-                const int twv = v == 0 ? 32 : 24;
-                const int tl = cdiv(a.Wout, twv) * cdiv(a.Hout, 8);
-                const int cost = cdiv((tl * npg + 1) / 2, cus_sp) * twv;
-                if (cost < best_cost) { best_cost = cost; bestv = v; best_tiles = tl; }
-            }
-            if (sp2_sw && (atoi(sp2_sw) == 24 || atoi(sp2_sw) == 32)) {
-                const int v = atoi(sp2_sw) == 24 ? 1 : 0;
-                if (P->sp2[v].ok) { bestv = v; best_tiles = cdiv(a.Wout, v == 0 ? 32 : 24) * cdiv(a.Hout, 8); }
-            }
-            const int npairs = (best_tiles * npg + 1) / 2;
-            // Where it runs by default: measured on the 2048x1536 page and in 32-page units against conv_mfma_kernel (tools/gpu_r05_sp2_ab.sh,
-            // gpu_r05_sp2_pages.sh, us per page): deconv3 60.8-61.9 vs 60.6 / 47.7-48.4 vs 50.2-50.7; conv6 41.2-41.9 vs 41.8-42.3 / 33.1 vs
-            // 30.2; conv5 32.1-32.5 vs 31.5-32.0 (before its table took the ring's room) -- a tie on the single page, a gain only for the
-            // three-cout-tile layer in page units.  PSEG_SP2=1 / 24 / 32 (plan switch): every eligible layer.
-            if (bestv >= 0 && ((npairs >= cus_sp && P->sp_NT == 3 && npg > 1) || sp2_sw)) {
-                const auto& Q = P->sp2[bestv];
-                SConv d = c;
-                d.tab = Q.d_tab; d.TBLK = Q.TBLK; d.RK = Q.RK; d.row_pitch = sp_row_pitch(P->sp_sigma, bestv == 0 ? 32 : 24);
-                d.lds_ring_off = Q.ring_off; d.lds_patch_off = Q.patch_off; d.lds_tab_off = Q.tab_off; d.lds_flag_off = Q.flag_off;
-                d.ntiles = best_tiles * npg; d.tiles_per_page = best_tiles;
-                d.xq = a.xq < 0 ? -1 : npairs / 8; d.xr = npairs % 8;
-                d.err = e.d_sp_err;
-                d.layer_id = (int)(&op - e.ops.data());
-                d.dbg = PSEG_DIAG_KNOB("PSEG_SP_DBG") ? atoi(PSEG_DIAG_KNOB("PSEG_SP_DBG")) : 0;
-                const dim3 g2((unsigned)std::min<int>(npairs, cus_sp));
-                const int fl2 = P->sp_fl & SP_POOL;
-                bool done2 = false;
-                const bool trace2 = PSEG_DIAG_KNOB("PSEG_SP2_TRACE") && tracing_req(op);   // diagnostic build: stamps -> gpurun_out/sp2_trace_<layer>.bin
-                if (trace2) {
-                    PSEG_HIP(hipMalloc((void**)&d.trace, (size_t)g2.x * 16 * 8));
-                    PSEG_HIP(hipMemset(d.trace, 0, (size_t)g2.x * 16 * 8));
-                }
-                if (PSEG_KNOB("PSEG_LOG_SP")) fprintf(stderr, "[pseg] conv_sp2 launch %s: tw %d tiles %d pairs %d grid %u RK %d lds %d\n", op.layer.c_str(), bestv ? 24 : 32, d.ntiles, npairs, g2.x, d.RK, Q.lds);
-#define PSEG_SP2(NT_, SG_, FL_, TW_)                                                                                \
-                if (!done2 && P->sp_NT == NT_ && P->sp_sigma == SG_ && fl2 == (FL_) && (bestv == 1) == (TW_ == 24)) {    \
-                    static bool attr_set[64] = {false};                                                               \
-                    if (!attr_set[dev & 63]) {                                                                        \
-                        PSEG_HIP(hipFuncSetAttribute((const void*)conv_sp2_kernel<NT_, SG_, (FL_), TW_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
-                        attr_set[dev & 63] = true;                                                                    \
-                    }                                                                                                 \
-                    conv_sp2_kernel<NT_, SG_, (FL_), TW_><<<g2, 768, Q.lds, st>>>(d);                                  \
-                    PSEG_HIP(hipGetLastError());                                                                      \
-                    done2 = true;                                                                                     \
-                }
-                PSEG_SP2(4, 5, 0, 24)           // conv5 (its 8 x 32 blocks leave no room for a ring)
-                PSEG_SP2(4, 4, SP_POOL, 24) PSEG_SP2(4, 4, SP_POOL, 32)   // conv6
-                PSEG_SP2(4, 4, 0, 24) PSEG_SP2(4, 4, 0, 32)
-                PSEG_SP2(4, 5, SP_POOL, 24)
-                PSEG_SP2(3, 4, 0, 24) PSEG_SP2(3, 4, 0, 32)               // deconv3
+    *grid = dim3(cdiv(a.Wout, TW) * cdiv(a.Hout, P.NW * (P.MT / 2)), P.nblocks_n);
+    xcd_bands(a, grid->x);
+    return PSEG_OK;
+}
+
+// the streamed-weight kernels' SConv: sources, output and weight stream of the conv (from its MConv); layout and tiles by sp_place
+static SConv sp_args(const Engine& e, const Op& op, const MfmaPlan& P, const MConv& a) {
+    SConv c{};
+    c.src0 = a.src0; c.src1 = a.src1; c.nch0 = a.nch0; c.nch1 = a.nch1; c.bytes0 = a.bytes0; c.bytes1 = a.bytes1;
+    c.Hin = a.Hin; c.Win = a.Win; c.Hout = a.Hout; c.Wout = a.Wout; c.pt = a.pt; c.pl = a.pl; c.relu = a.relu;
+    c.nblk = P.sp_nblk; c.nc_full = P.sp_nc_full; c.nc_last = P.sp_nc_last; c.K = P.sp_K; c.S = P.sp_S; c.blk_steps = P.sp_blk_steps;
+    c.wpk = P.d_sp_wpk; c.bias = P.d_bias;
+    c.dst = a.dst; c.dst_bytes = a.dst_bytes; c.nch_out = a.nch_out; c.pool_dst = a.pool_dst; c.pool_bytes = a.pool_bytes;
+    c.dq_bias = a.dq_bias; c.dq_dst = a.dq_dst; c.dq_bytes = a.dq_bytes; c.dq_nch = a.dq_nch; c.dq_relu = a.dq_relu;
+    c.err = e.d_sp_err;
+    c.layer_id = (int)(&op - e.ops.data());
+    c.dbg = PSEG_DIAG_KNOB("PSEG_SP_DBG") ? atoi(PSEG_DIAG_KNOB("PSEG_SP_DBG")) : 0;
+    return c;
+}
+
+// ... one layout, and the launch's tiles: a tile index carries the page; `units` of work (tiles, or tile pairs) are spread over the XCD bands
+static void sp_place(SConv& c, const MfmaPlan::SpLayout& L, int tiles_per_page, int pages, int units, bool xcd) {
+    c.tab = L.d_tab; c.row_pitch = L.row_pitch; c.TBLK = L.TBLK; c.RK = L.RK;
+    c.lds_ring_off = L.ring_off; c.lds_patch_off = L.patch_off; c.lds_tab_off = L.tab_off; c.lds_flag_off = L.flag_off;
+    c.ntiles = tiles_per_page * pages; c.tiles_per_page = tiles_per_page;
+    c.xq = xcd ? units / 8 : -1; c.xr = units % 8;
+}
+
+// tests (PSEG_SP_CHECK): the give-up record of the streamed-weight kernels is looked at after EVERY launch; the product looks at it
+// wherever the host synchronises anyway (engine_status: pseg_predict, _batch, _chain, _exact_labels, pseg_engine_status)
+static int sp_launched(Engine& e, hipStream_t st) {
+    if (PSEG_KNOB("PSEG_SP_CHECK")) PSEG_TRY(engine_status(e, st));
+    return PSEG_OK;
+}
+
+// ---- the routes of a conv launch, in the order mfma_launch_conv asks them ------------------------------------------------------------
+#define PSEG_SP2(NT_, SG_, FL_, TW_)                                                                  \
+    if (P.sp_NT == NT_ && P.sp_sigma == SG_ && (P.sp_fl & SP_POOL) == (FL_) && tw == TW_)              \
+        return launch_lds<conv_sp2_kernel<NT_, SG_, (FL_), TW_>>(c, grid, 768, lds, dev, st);
+static int sp2_run(const MfmaPlan& P, const SConv& c, int tw, dim3 grid, int lds, int dev, hipStream_t st) {
+    PSEG_SP2(4, 5, 0, 24)           // conv5 (its 8 x 32 blocks leave no room for a ring)
+    PSEG_SP2(4, 4, SP_POOL, 24) PSEG_SP2(4, 4, SP_POOL, 32)   // conv6
+    PSEG_SP2(4, 4, 0, 24) PSEG_SP2(4, 4, 0, 32)
+    PSEG_SP2(4, 5, SP_POOL, 24)
+    PSEG_SP2(3, 4, 0, 24) PSEG_SP2(3, 4, 0, 32)               // deconv3
+    return ROUTE_NO;
+}
 #undef PSEG_SP2
-                if (done2 && trace2) {
-                    PSEG_HIP(hipStreamSynchronize(st));
-                    std::vector<unsigned long long> hbuf((size_t)g2.x * 16);
-                    PSEG_HIP(hipMemcpy(hbuf.data(), d.trace, hbuf.size() * 8, hipMemcpyDeviceToHost));
-                    (void)hipFree(d.trace);
-                    const std::string fn = std::string("gpurun_out/sp2_trace_") + op.layer + ".bin";
-                    if (FILE* f = fopen(fn.c_str(), "wb")) { fwrite(hbuf.data(), 8, hbuf.size(), f); fclose(f); }
-                }
-                if (done2) {
-                    if (PSEG_KNOB("PSEG_SP_CHECK")) PSEG_TRY(engine_status(e, st));
-                    return PSEG_OK;
-                }
-            }
-        }
-        c.ntiles = tiles_pp * npg; c.tiles_per_page = tiles_pp;
-        c.xq = a.xq < 0 ? -1 : c.ntiles / 8; c.xr = c.ntiles % 8;
-        c.err = e.d_sp_err;
-        c.layer_id = (int)(&op - e.ops.data());
-        c.dbg = PSEG_DIAG_KNOB("PSEG_SP_DBG") ? atoi(PSEG_DIAG_KNOB("PSEG_SP_DBG")) : 0;
-        const dim3 gs((unsigned)std::min<int>(c.ntiles, cus_sp));
-        const char* trl = PSEG_DIAG_KNOB("PSEG_SP_TRACE");     // diagnostic build only: the release library neither stamps nor writes files
-        const bool tracing = sp_pays && trl && op.layer == trl;
-        if (tracing) {
-            PSEG_HIP(hipMalloc((void**)&c.trace, (size_t)gs.x * 16 * 8));
-            PSEG_HIP(hipMemset(c.trace, 0, (size_t)gs.x * 16 * 8));
-        }
-        bool launched = !sp_pays;
-#define PSEG_SP_TW(NT_, SG_, FL_, TW_)                                                                              \
-        if (!launched && P->sp_NT == NT_ && P->sp_sigma == SG_ && P->sp_fl == (FL_) && narrow == (TW_ == 24)) {      \
-            static bool attr_set[64] = {false};                                                                   \
-            if (!attr_set[dev & 63]) {                                                                            \
-                PSEG_HIP(hipFuncSetAttribute((const void*)conv_sp_kernel<NT_, SG_, (FL_), TW_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
-                attr_set[dev & 63] = true;                                                                        \
-            }                                                                                                     \
-            conv_sp_kernel<NT_, SG_, (FL_), TW_><<<gs, 512, sp_lds, st>>>(c);                                      \
-            PSEG_HIP(hipGetLastError());                                                                          \
-            launched = true;                                                                                      \
-        }
-#define PSEG_SP(NT_, SG_, FL_) PSEG_SP_TW(NT_, SG_, FL_, 32)
-        PSEG_SP(5, 4, SP_PATCH)                 // conv7
-        PSEG_SP(5, 4, SP_DQ)                    // deconv1 + deconv2 (k2 s2) on its accumulators
-        PSEG_SP_TW(5, 4, SP_PATCH, 24)          // ... and on tiles of 8 x 24 (one round of 256 tiles on a 2048x1536 page)
-        PSEG_SP_TW(5, 4, SP_DQ, 24)
-        PSEG_SP(4, 5, SP_PATCH)                 // conv5
-        PSEG_SP(4, 4, SP_PATCH | SP_POOL)       // conv6
-        PSEG_SP(4, 4, SP_PATCH)
-        PSEG_SP(4, 5, SP_PATCH | SP_POOL)
-        PSEG_SP(3, 4, 0)                        // deconv3 (fcn_skip: four channel blocks, no room for the store patch)
-        PSEG_SP(3, 4, SP_PATCH)                 // deconv3 (fcn)
+
+static int route_sp2(Engine& e, const Op& op, const MfmaPlan& P, const MConv& a, const Extent& x, hipStream_t st) {
+    const bool traced = tracing_req(op);     // diagnostic build, PSEG_SP_TRACE=<layer>: with PSEG_SP2_TRACE this kernel's stamps, else the layer stays on conv_sp_kernel
+    if (!P.sp || (traced && !PSEG_DIAG_KNOB("PSEG_SP2_TRACE"))) return ROUTE_NO;
+    int tiles = 0;
+    const int v = sp2_pick(P, x, &tiles);
+    if (v < 0) return ROUTE_NO;
+    const int npairs = (tiles * x.pages + 1) / 2;
+    SConv c = sp_args(e, op, P, a);
+    sp_place(c, P.sp2_lay[v], tiles, x.pages, npairs, a.xq >= 0);
+    const dim3 grid((unsigned)std::min(npairs, x.cus));
+    if (PSEG_KNOB("PSEG_LOG_SP"))
+        fprintf(stderr, "[pseg] conv_sp2 launch %s: tw %d tiles %d pairs %d grid %u RK %d lds %d\n", op.layer.c_str(), v ? 24 : 32, c.ntiles, npairs, grid.x, c.RK, P.sp2_lay[v].lds);
+    const int rc = with_trace(traced, &c.trace, (size_t)grid.x * 16, "sp2_trace_", op.layer.c_str(), st,
+                              [&] { return sp2_run(P, c, v ? 24 : 32, grid, P.sp2_lay[v].lds, x.dev, st); });
+    return rc == PSEG_OK ? sp_launched(e, st) : rc;
+}
+
+#define PSEG_SP(NT_, SG_, FL_, TW_)                                                                   \
+    if (P.sp_NT == NT_ && P.sp_sigma == SG_ && P.sp_fl == (FL_) && tw == TW_)                          \
+        return launch_lds<conv_sp_kernel<NT_, SG_, (FL_), TW_>>(c, grid, 512, lds, dev, st);
+static int sp_run(const MfmaPlan& P, const SConv& c, int tw, dim3 grid, int lds, int dev, hipStream_t st) {
+    PSEG_SP(5, 4, SP_PATCH, 32)                 // conv7
+    PSEG_SP(5, 4, SP_DQ, 32)                    // deconv1 + deconv2 (k2 s2) on its accumulators
+    PSEG_SP(5, 4, SP_PATCH, 24)                 // ... and on tiles of 8 x 24 (one round of 256 tiles on a 2048x1536 page)
+    PSEG_SP(5, 4, SP_DQ, 24)
+    PSEG_SP(4, 5, SP_PATCH, 32)                 // conv5
+    PSEG_SP(4, 4, SP_PATCH | SP_POOL, 32)       // conv6
+    PSEG_SP(4, 4, SP_PATCH, 32)
+    PSEG_SP(4, 5, SP_PATCH | SP_POOL, 32)
+    PSEG_SP(3, 4, 0, 32)                        // deconv3 (fcn_skip: four channel blocks, no room for the store patch)
+    PSEG_SP(3, 4, SP_PATCH, 32)                 // deconv3 (fcn)
+    return ROUTE_NO;
+}
 #undef PSEG_SP
-#undef PSEG_SP_TW
-        if (!sp_pays) launched = false;
-        if (launched && tracing) {
-            PSEG_HIP(hipStreamSynchronize(st));
-            std::vector<unsigned long long> hbuf((size_t)gs.x * 16);
-            PSEG_HIP(hipMemcpy(hbuf.data(), c.trace, hbuf.size() * 8, hipMemcpyDeviceToHost));
-            (void)hipFree(c.trace);
-            const std::string fn = std::string("gpurun_out/sp_trace_") + op.layer + ".bin";
-            if (FILE* f = fopen(fn.c_str(), "wb")) { fwrite(hbuf.data(), 8, hbuf.size(), f); fclose(f); }
-        }
-        if (launched) {
-            // tests (PSEG_SP_CHECK): the give-up record is looked at after EVERY launch; the product looks at it wherever the host
-            // synchronises anyway (engine_status: pseg_predict, _batch, _chain, _exact_labels, pseg_engine_status)
-            if (PSEG_KNOB("PSEG_SP_CHECK")) PSEG_TRY(engine_status(e, st));
-            return PSEG_OK;
-        }
-    }
-    // ping-pong persistent kernel (conv_pp_kernel) for the k5 mid layers whose weights fit LDS beside two tiles: conv3, conv4
-    if (P->wg3 && P->KS == 5 && P->NT == 3 && P->MT == 4 && P->NW == 4 && P->nblk == 1 && P->nblocks_n == 1 && op.Cout <= 40 && !op.transposed &&
-        op.src1 < 0 && !a.add && !a.in_relu && !a.up0 && op.fuse1 < 0 && op.tail_logits < 0 && op.skiplog < 0 && op.relu_dst < 0 &&
-        P->pp && (a.sigma == 4 || a.sigma == 5) && !a.trace && !PSEG_KNOB("PSEG_NO_PP") && !PSEG_KNOB("PSEG_GENERIC")) {
-        int dev = 0;
-        const int cus_pp = device_cus(&dev);
-        const int TB = round_up(P->THH * P->row_pitch, 16);
-        const int lds = 2 * TB + P->ks_full * 2560 + 16 + round_up(P->ks_full * 16, 16);
-        if (lds <= 160 * 1024 && (int)grid.x >= 2 * cus_pp) {
-            MConv w = a;
-            w.lds_w_off = TB;
-            w.ntiles = (int)grid.x;
-            if (PSEG_DIAG_KNOB("PSEG_PP_NODMA")) w.dbg |= 0x800;     // wrong results, timing only: diagnostic build only
-            if (PSEG_DIAG_KNOB("PSEG_PP_NOEPI")) w.dbg |= 0x1000;
-            const dim3 gp((unsigned)cus_pp);
-            const bool rr = P->rowreuse && P->ks_full == 25;   // conv3: the k-loop that keeps a wave's shared pixel fragments in registers
-#define PSEG_PP(SG_, POOL_, RR_)                                                                                  \
-            if (a.sigma == SG_ && (a.pool_dst != nullptr) == POOL_ && rr == RR_) {                                \
-                static bool attr_set[64] = {false};                                                               \
-                if (!attr_set[dev & 63]) {                                                                        \
-                    PSEG_HIP(hipFuncSetAttribute((const void*)conv_pp_kernel<SG_, POOL_, RR_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
-                    attr_set[dev & 63] = true;                                                                    \
-                }                                                                                                 \
-                conv_pp_kernel<SG_, POOL_, RR_><<<gp, 768, lds, st>>>(w);                                         \
-                PSEG_HIP(hipGetLastError());                                                                      \
-                return PSEG_OK;                                                                                   \
-            }
-            PSEG_PP(4, false, true) PSEG_PP(4, true, true)
-            PSEG_PP(4, false, false) PSEG_PP(4, true, false) PSEG_PP(5, false, false) PSEG_PP(5, true, false)
+
+// streamed-weights persistent kernel with loader waves: conv5, conv6, conv7, deconv1 (+ deconv2), deconv3
+static int route_sp(Engine& e, const Op& op, const MfmaPlan& P, const MConv& a, const Extent& x, hipStream_t st) {
+    if (!P.sp || !sp_pays(P, x)) return ROUTE_NO;
+    int tiles = 0;
+    const bool narrow = sp_narrow(P, x, &tiles);
+    SConv c = sp_args(e, op, P, a);
+    sp_place(c, P.sp_lay[narrow], tiles, x.pages, tiles * x.pages, a.xq >= 0);
+    const dim3 grid((unsigned)std::min(c.ntiles, x.cus));
+    const int rc = with_trace(tracing_req(op), &c.trace, (size_t)grid.x * 16, "sp_trace_", op.layer.c_str(), st,
+                              [&] { return sp_run(P, c, narrow ? 24 : 32, grid, P.sp_lay[narrow].lds, x.dev, st); });
+    return rc == PSEG_OK ? sp_launched(e, st) : rc;
+}
+
+#define PSEG_PP(SG_, POOL_, RR_)                                                                      \
+    if (w.sigma == SG_ && (w.pool_dst != nullptr) == POOL_ && rr == RR_)                               \
+        return launch_lds<conv_pp_kernel<SG_, POOL_, RR_>>(w, grid, 768, lds, dev, st);
+static int pp_run(const MConv& w, bool rr, dim3 grid, int lds, int dev, hipStream_t st) {
+    PSEG_PP(4, false, true) PSEG_PP(4, true, true)
+    PSEG_PP(4, false, false) PSEG_PP(4, true, false) PSEG_PP(5, false, false) PSEG_PP(5, true, false)
+    return ROUTE_NO;
+}
 #undef PSEG_PP
-        }
+
+// ping-pong persistent kernel for the k5 mid layers whose weights fit LDS beside two tiles: conv3, conv4
+static int route_pp(const MfmaPlan& P, const MConv& a, const Extent& x, hipStream_t st) {
+    int lds = 0;
+    if (!P.pp || !pp_pays(P, x, &lds)) return ROUTE_NO;
+    MConv w = a;
+    w.lds_w_off = tile_bytes(P);
+    w.ntiles = x.tiles;
+    if (PSEG_DIAG_KNOB("PSEG_PP_NODMA")) w.dbg |= 0x800;     // wrong results, timing only: diagnostic build only
+    if (PSEG_DIAG_KNOB("PSEG_PP_NOEPI")) w.dbg |= 0x1000;
+    const bool rr = P.rowreuse && P.ks_full == 25;           // conv3: the k-loop that keeps a wave's shared pixel fragments in registers
+    return pp_run(w, rr, dim3((unsigned)x.cus), lds, x.dev, st);
+}
+
+#define PSEG_WS(SKIP_, PAIR_, FORM_)                                                                  \
+    if ((w.skip_logits != nullptr) == SKIP_ && P.pairc2 == PAIR_ && P.ws_form == FORM_)                \
+        return launch_lds<conv12_ws_kernel<SKIP_, PAIR_, FORM_>>(w, grid, 512, lds, dev, st);
+static int ws_run(const MfmaPlan& P, const MConv& w, dim3 grid, int lds, int dev, hipStream_t st) {
+    PSEG_WS(false, false, 0) PSEG_WS(false, true, 0) PSEG_WS(true, false, 0)
+    PSEG_WS(true, true, 0) PSEG_WS(true, true, 1) PSEG_WS(true, true, 2)       // (PSEG_WS_FORM: the alternative tile loops)
+    return ROUTE_NO;
+}
+#undef PSEG_WS
+
+// fused conv1 + conv2, wave-specialised.  A layer packed with paired half chunks has no other kernel: the plan's flags must agree.
+static int route_ws(const Op& op, const MfmaPlan& P, const MConv& a, const Extent& x, hipStream_t st) {
+    int lds = 0;
+    if (!P.ws || !ws_fits(P, &lds)) {
+        if (P.pairc2) return fail(PSEG_EUNSUPPORTED, "layer %s is packed for conv12_ws_kernel (paired half chunks), which cannot take this launch", op.layer.c_str());
+        return ROUTE_NO;
     }
-    if (op.fuse1 >= 0 && P->NB == 1 && P->nblk == 1 && P->nblocks_n == 1 && P->MT == 8 && P->NT == 2 && P->KS == 5 && a.sigma == 3 &&
-        a.pool_dst && !a.add && !a.in_relu && !a.relu && !PSEG_KNOB("PSEG_NO_WS") && !PSEG_KNOB("PSEG_NO_PERSIST") && !PSEG_KNOB("PSEG_GENERIC") && !a.trace) {
-        const bool ws_trace = PSEG_DIAG_KNOB("PSEG_WS_TRACE") != nullptr;   // developer aid: per-wave phase cycles -> gpurun_out/ws_trace.bin
-        int dev = 0;
-        const int cus_ws = device_cus(&dev);
-        MConv w = a;
-        const int TB = round_up(P->THH * P->row_pitch, 16);
-        w.lds_w_off = TB;                                   // the kernel's tile stride
-        w.ntiles = (int)grid.x;
-        const int lds = WS_TILE0 + 2 * TB + P->ks_full * P->NT * 1024 + round_up(P->ks_full * 16, 16) + 4 * (2 * 9 * 96 + 16);
-        const int form = PSEG_KNOB("PSEG_WS_FORM") ? atoi(PSEG_KNOB("PSEG_WS_FORM")) : 0;
-        if (lds <= 160 * 1024 && P->GK >= P->ks_full && P->row_pitch == WS_ROWP && P->ks_full == (P->pairc2 ? WS_KSTEPS_PAIR : WS_KSTEPS)) {
-            const unsigned gx = std::min<unsigned>(grid.x, (unsigned)cus_ws);
-            const int sk = op.skiplog >= 0 ? 1 : 0;
-            int variant = sk * 2 + (P->pairc2 ? 1 : 0);
-            if (variant == 3 && (form == 1 || form == 2)) variant = 3 + form;       // the alternative tile loops exist for the default packing only
-            const void* fn = variant == 5 ? (const void*)conv12_ws_kernel<true, true, 2> : variant == 4 ? (const void*)conv12_ws_kernel<true, true, 1>
-                           : variant == 3 ? (const void*)conv12_ws_kernel<true, true, 0> : variant == 2 ? (const void*)conv12_ws_kernel<true, false, 0>
-                           : variant == 1 ? (const void*)conv12_ws_kernel<false, true, 0> : (const void*)conv12_ws_kernel<false, false, 0>;
-            static bool attr_ws[64][6] = {{false}};
-            if (!attr_ws[dev & 63][variant]) {
-                PSEG_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                attr_ws[dev & 63][variant] = true;
-            }
-            if (ws_trace) {
-                PSEG_HIP(hipMalloc((void**)&w.trace, (size_t)gx * 8 * 4 * 8));
-                PSEG_HIP(hipMemset(w.trace, 0, (size_t)gx * 8 * 4 * 8));
-            }
-            switch (variant) {
-                case 5: conv12_ws_kernel<true, true, 2><<<dim3(gx), 512, lds, st>>>(w); break;
-                case 4: conv12_ws_kernel<true, true, 1><<<dim3(gx), 512, lds, st>>>(w); break;
-                case 3: conv12_ws_kernel<true, true, 0><<<dim3(gx), 512, lds, st>>>(w); break;
-                case 2: conv12_ws_kernel<true, false, 0><<<dim3(gx), 512, lds, st>>>(w); break;
-                case 1: conv12_ws_kernel<false, true, 0><<<dim3(gx), 512, lds, st>>>(w); break;
-                default: conv12_ws_kernel<false, false, 0><<<dim3(gx), 512, lds, st>>>(w); break;
-            }
-            if (ws_trace) {
-                PSEG_HIP(hipStreamSynchronize(st));
-                std::vector<unsigned long long> hbuf((size_t)gx * 8 * 4);
-                PSEG_HIP(hipMemcpy(hbuf.data(), w.trace, hbuf.size() * 8, hipMemcpyDeviceToHost));
-                (void)hipFree(w.trace);
-                if (FILE* f = fopen("gpurun_out/ws_trace.bin", "wb")) { fwrite(hbuf.data(), 8, hbuf.size(), f); fclose(f); }
-            }
-            return PSEG_OK;
-        }
+    MConv w = a;
+    w.lds_w_off = tile_bytes(P);                        // the kernel's tile stride
+    w.ntiles = x.tiles;
+    const dim3 grid((unsigned)std::min(x.tiles, x.cus));
+    // (diagnostic build, PSEG_WS_TRACE: per-wave phase cycles -> ws_trace.bin)
+    return with_trace(PSEG_DIAG_KNOB("PSEG_WS_TRACE") != nullptr, &w.trace, (size_t)grid.x * 8 * 4, "ws_trace", "", st,
+                      [&] { return ws_run(P, w, grid, lds, x.dev, st); });
+}
+
+// conv_mfma_kernel: one workgroup per tile, or its two persistent forms
+static int route_mfma(const Op& op, const MfmaPlan& P, MConv& a, dim3 grid, const Extent& x, hipStream_t st) {
+    if (P.persist_f1) {
+        a.ntiles = x.tiles;
+        grid.x = std::min<unsigned>(grid.x, 2u * (unsigned)x.cus);
+    } else if (P.persist_s2) {
+        if (const unsigned slots = s2_persists(P, x)) { a.ntiles = x.tiles; grid.x = slots; }
     }
-    if (P->pairc2) return fail(PSEG_EUNSUPPORTED, "layer %s is packed for conv12_ws_kernel (paired half chunks), which cannot take this launch", op.layer.c_str());
-    if (op.fuse1 >= 0 && P->NB == 1 && P->nblk == 1 && P->nblocks_n == 1 && !PSEG_KNOB("PSEG_NO_PERSIST") && !PSEG_KNOB("PSEG_GENERIC")) {
-        const int cus = device_cus();
-        a.ntiles = (int)grid.x;
-        grid.x = std::min<unsigned>(grid.x, 2u * (unsigned)cus);
+    if (x.pages > 1) grid.z = (unsigned)x.pages;   // (mfma_op_batchable layers only: the page slot is blockIdx.z)
+    return launch_generic_any(a, P, grid, x.dev, st, op.layer.c_str());
+}
+
+// the first layer on the uint8 page (x/255 and pad-to-32 are fused)
+static int launch_conv1(const Engine& e, const Op& op, const MfmaPlan& P, hipStream_t st) {
+    const Tensor& d = e.tensors[op.dst];
+    const uint8_t* img = e.cur_img;
+    if ((P.KS == 3 && (op.Cout == 64 || op.Cout == 32))) {
+        constexpr int RB = 16;
+        dim3 g(cdiv(e.Wp, 64), cdiv(e.Hp, 4 * RB));
+        if (op.Cout == 64) conv1_rows_kernel<3, 64, RB><<<g, 256, 0, st>>>(img, e.H, e.W, e.Hp, e.Wp, P.d_wf, P.d_bias, (uint16_t*)d.d, op.relu);
+        else conv1_rows_kernel<3, 32, RB><<<g, 256, 0, st>>>(img, e.H, e.W, e.Hp, e.Wp, P.d_wf, P.d_bias, (uint16_t*)d.d, op.relu);
+        return PSEG_OK;
     }
-    // ... and the k3 single-block layers whose instances exist (launch_generic_any2): many tiles, nine k-steps each
-    if (op.fuse1 < 0 && P->NB == 1 && P->nblk == 1 && P->nblocks_n == 1 && P->KS == 3 && a.sigma == 4 && !a.deconv && !a.tail && !a.up0 && !a.up1 &&
-        !a.pool_dst && !a.dst2 && !a.skip_logits && !a.tail_wa && !a.dq_w && e.batch_pages <= 1 &&
-        P->MT == 2 && P->NT == 4 && op.stride == 2 && !a.add &&
-        !PSEG_KNOB("PSEG_NO_PERSIST") && !PSEG_KNOB("PSEG_GENERIC")) {
-        const int cus = device_cus();
-        const unsigned slots = (P->wg3 ? 3u : 2u) * (unsigned)cus;
-        if (grid.x > 2 * slots) { a.ntiles = (int)grid.x; grid.x = slots; }
+    dim3 g1(e.Wp / 32, cdiv(e.Hp, 16));
+    uint16_t* o = (uint16_t*)d.d;
+    if (P.KS == 5 && op.Cout == 20) conv1_mfma_kernel<5, 20><<<g1, 256, 0, st>>>(img, e.H, e.W, e.Wp, P.d_wpk, P.d_bias, o, op.relu);
+    else if (P.KS == 3 && op.Cout == 64) conv1_mfma_kernel<3, 64><<<g1, 256, 0, st>>>(img, e.H, e.W, e.Wp, P.d_wpk, P.d_bias, o, op.relu);
+    else if (P.KS == 3 && op.Cout == 32) conv1_mfma_kernel<3, 32><<<g1, 256, 0, st>>>(img, e.H, e.W, e.Wp, P.d_wpk, P.d_bias, o, op.relu);
+    else conv1_mfma_kernel<1, 32><<<g1, 256, 0, st>>>(img, e.H, e.W, e.Wp, P.d_wpk, P.d_bias, o, op.relu);
+    return PSEG_OK;
+}
+
+// Re-pack the layer for the other workgroup shape when this canvas wants it (nw_wanted); the plan object changes.
+static int repack_for_canvas(Engine& e, Op& op) {
+    auto* P = (MfmaPlan*)op.plan;
+    const Tensor& d = e.tensors[op.dst];
+    const int want = nw_wanted(*P, e.tH(d), e.tW(d));
+    if (want == P->NW || want == P->nw_tried) return PSEG_OK;
+    const std::vector<float> w = P->w_keep, b = P->b_keep;
+    op.nw_hint = want;
+    PSEG_TRY(mfma_pack_op(e, op, w, b));
+    P = (MfmaPlan*)op.plan;
+    P->nw_tried = want;      // the shape may not have an instance for `want`: do not re-pack every launch
+    if (want == 8 && !P->nw8_resident) {   // ring only: keep two workgroups per CU
+        op.nw_hint = 4;
+        PSEG_TRY(mfma_pack_op(e, op, w, b));
+        P = (MfmaPlan*)op.plan;
+        P->nw8_ok = false;                 // decided for this engine
     }
-    if (e.batch_pages > 1) grid.z = (unsigned)e.batch_pages;   // (mfma_op_batchable layers only: the page slot is blockIdx.z)
-    return launch_generic_any(a, *P, grid, st, op.layer.c_str());
+    return PSEG_OK;
+}
+
+int mfma_launch_conv(Engine& e, Op& op, hipStream_t st) {
+    if (!op.plan) return fail(PSEG_EINVAL, "layer %s has no bf16 plan", op.layer.c_str());
+    const int kind = ((MfmaPlan*)op.plan)->kind;
+    if (op.relu_dst >= 0 && (kind != PLAN_GENERIC || op.pool_dst >= 0 || op.tail_logits >= 0 || op.skiplog >= 0 || op.fuse1 >= 0))
+        return fail(PSEG_EUNSUPPORTED, "layer %s: the ReLU'd second output exists only in the direct-store epilogue", op.layer.c_str());
+    if (kind == PLAN_CONV1) return launch_conv1(e, op, *(MfmaPlan*)op.plan, st);
+    if (kind == PLAN_UPSPLIT) {
+        const Tensor& s0 = e.tensors[op.src0];
+        return upsplit_launch(((MfmaPlan*)op.plan)->upsplit, (const uint16_t*)s0.d, e.tH(s0), e.tW(s0), (uint16_t*)e.tensors[op.dst].d, op.relu, st);
+    }
+    if (((MfmaPlan*)op.plan)->nw8_ok) PSEG_TRY(repack_for_canvas(e, op));
+    MfmaPlan& P = *(MfmaPlan*)op.plan;
+    MConv a{};
+    dim3 grid;
+    PSEG_TRY(fill_conv(e, op, P, a, &grid));
+    Extent x{a.Hout, a.Wout, (int)grid.x, e.batch_pages > 1 ? e.batch_pages : 1, 0, 0};
+    x.cus = device_cus(&x.dev);
+    // the route order is part of the behaviour: the first family that is eligible (plan) and pays (size predicates) takes the launch
+    int rc;
+    if ((rc = route_sp2(e, op, P, a, x, st)) != ROUTE_NO) return rc;
+    if ((rc = route_sp(e, op, P, a, x, st)) != ROUTE_NO) return rc;
+    if ((rc = route_pp(P, a, x, st)) != ROUTE_NO) return rc;
+    if ((rc = route_ws(op, P, a, x, st)) != ROUTE_NO) return rc;
+    return route_mfma(op, P, a, grid, x, st);
 }
 
 // Layers whose kernel takes all page slots of a batch in ONE launch (run_bf16_pages): conv_sp_kernel (a tile index carries
@@ -5493,7 +5519,7 @@ bool mfma_op_batchable(const Engine& e, const Op& op) {
     if (op.add >= 0 || op.relu_dst >= 0 || op.fuse1 >= 0 || op.tail_logits >= 0 || op.skiplog >= 0 || op.in_relu || op.up0 || op.up1 ||
         op.src0 == e.input_tensor || op.src1 == e.input_tensor)
         return false;
-    if (P->pp) return false;
+    if (P->pp_shape) return false;
     // layer-major launches pay where one page leaves the chip partly filled or its launch is mostly ramp and drain: from 1/4 resolution
     // down (a 2048x1536 page: 768 tiles there).  The full- and half-resolution layers of the 3x3 graphs stay page-major: a page's
     // tensors are in the caches for its next layer.
@@ -5502,9 +5528,75 @@ bool mfma_op_batchable(const Engine& e, const Op& op) {
     return true;
 }
 
+// the composed tail (deconv5 o logits as one small GEMM per half-resolution pixel, no LDS), with or without the inner deconv
+static int launch_composed_tail(Engine& e, const Op& op, const MfmaPlan& P, hipStream_t st) {
+    const Op& lg = e.ops[op.tail_logits];
+    const Tensor& s0 = e.tensors[op.src0];
+    TailC t{};
+    t.src0 = (const uint16_t*)s0.d;
+    t.src1 = op.src1 >= 0 ? (const uint16_t*)e.tensors[op.src1].d : nullptr;
+    t.skip = lg.src1 >= 0 ? (const uint16_t*)e.tensors[lg.src1].d : nullptr;
+    t.nch0 = s0.Cs / 8;
+    t.nch1 = op.src1 >= 0 ? e.tensors[op.src1].Cs / 8 : 0;
+    t.nch_skip = lg.src1 >= 0 ? e.tensors[lg.src1].Cs / 8 : 0;
+    t.Hh = e.tH(s0); t.Wh = e.tW(s0);
+    t.H0 = e.H; t.W0 = e.W; t.C = lg.Cout;
+    t.wA1 = P.d_tc_wA1; t.wA2 = P.d_tc_wA2; t.beta = P.d_tc_beta;
+    if (lg.src1 >= 0) {
+        const int sp = producer_of(e, lg.src1);
+        if (sp >= 0 && e.ops[sp].skiplog >= 0) {
+            auto* PS = (MfmaPlan*)e.ops[sp].plan;
+            if (!PS || !PS->d_skiplog || PS->skip_CP != P.tc_CP) return fail(PSEG_EINVAL, "skip-logits buffer missing for the composed tail");
+            t.S = (const float*)((const char*)PS->d_skiplog + (size_t)e.page * ((size_t)e.Hp * e.Wp * PS->skip_CP * 4));   // this page slot's plane
+            t.skip = nullptr;
+        }
+    }
+    t.out_logits = e.cur_logits; t.out_probs = e.cur_probs; t.out_labels = e.cur_labels; t.out_labels_u8 = e.cur_labels_u8;
+    t.out_margin = e.cur_margin;
+    e.margin_done = e.cur_margin != nullptr;
+    if (t.Wh % 16) return fail(PSEG_EINVAL, "composed tail needs a canvas width multiple of 32");
+    if (P.tail2) {
+        const Op& dq = e.ops[producer_of(e, op.src0)];
+        auto* PQ = (MfmaPlan*)dq.plan;
+        if (!PQ || !PQ->d_q_w || (!t.S && lg.src1 >= 0) || (P.tc_CP != 4 && P.tc_CP != 8)) return fail(PSEG_EINVAL, "fused inner deconv: plan data missing");
+        Tail2 u{};
+        const Tensor& q0 = e.tensors[dq.src0];
+        u.q0 = (const uint16_t*)q0.d; u.nq0 = q0.Cs / 8;
+        u.q1 = dq.src1 >= 0 ? (const uint16_t*)e.tensors[dq.src1].d : nullptr;
+        u.nq1 = dq.src1 >= 0 ? e.tensors[dq.src1].Cs / 8 : 0;
+        u.c3 = t.src1; u.nc3 = t.nch1;
+        u.S = t.S; u.Hh = t.Hh; u.Wh = t.Wh; u.H0 = t.H0; u.W0 = t.W0; u.C = t.C;
+        u.wQ = PQ->d_q_w; u.biasQ = PQ->d_q_bias; u.wD = P.d_t2_wD; u.wC = P.d_t2_wC; u.beta = P.d_tc_beta;
+        u.out_logits = t.out_logits; u.out_probs = t.out_probs; u.out_labels = t.out_labels; u.out_labels_u8 = t.out_labels_u8;
+        u.out_margin = t.out_margin;
+        const int nwg = cdiv(t.Hh, 2) * cdiv((t.Wh + 31) / 32, T2_ITER);      // one workgroup = 2 rows x 2 column parities
+        if (P.tc_CP == 4) tail_fused2_kernel<4><<<nwg, 256, 0, st>>>(u);
+        else tail_fused2_kernel<8><<<nwg, 256, 0, st>>>(u);
+        PSEG_HIP(hipGetLastError());
+        return PSEG_OK;
+    }
+    const int waves = t.Hh * (t.Wh / 16);
+    const dim3 grid(cdiv(waves, 4));
+    const int key = P.tc_CP * 100 + P.tc_nks0 * 10 + P.tc_nkss;
+    switch (key) {
+        case 430: tail_composed_kernel<4, 3, 0><<<grid, 256, 0, st>>>(t); break;   // skip logits from the producer's buffer
+        case 830: tail_composed_kernel<8, 3, 0><<<grid, 256, 0, st>>>(t); break;
+        case 431: tail_composed_kernel<4, 3, 1><<<grid, 256, 0, st>>>(t); break;
+        case 831: tail_composed_kernel<8, 3, 1><<<grid, 256, 0, st>>>(t); break;
+        case 1631: tail_composed_kernel<16, 3, 1><<<grid, 256, 0, st>>>(t); break;
+        case 410: tail_composed_kernel<4, 1, 0><<<grid, 256, 0, st>>>(t); break;
+        case 810: tail_composed_kernel<8, 1, 0><<<grid, 256, 0, st>>>(t); break;
+        case 1610: tail_composed_kernel<16, 1, 0><<<grid, 256, 0, st>>>(t); break;
+        default: return fail(PSEG_EUNSUPPORTED, "no composed-tail instance %d", key);
+    }
+    PSEG_HIP(hipGetLastError());
+    return PSEG_OK;
+}
+
 int mfma_launch_deconv2(Engine& e, Op& op, hipStream_t st) {
     auto* P = (MfmaPlan*)op.plan;
     if (!P) return fail(PSEG_EINVAL, "layer %s has no bf16 plan", op.layer.c_str());
+    if (op.tail_logits >= 0 && P->tc_CP > 0 && P->spec) return launch_composed_tail(e, op, *P, st);
     MConv a{};
     fill_common(e, op, *P, a);
     a.Hout = a.Hin;  // the GEMM pixel grid is the input grid
@@ -5512,93 +5604,23 @@ int mfma_launch_deconv2(Engine& e, Op& op, hipStream_t st) {
     a.stride = 1;
     a.pt = a.pl = 0;
     a.deconv = 1;
+    // the specialised instances that walk both N blocks in one workgroup (NBL = 2 in the kernel): the tails, deconv4 (fcn_skip)
+    const bool two_blocks = P->nblk == 1 && P->nblocks_n == 2 && P->spec;
     if (op.tail_logits >= 0) {
         const Op& lg = e.ops[op.tail_logits];
-        if (P->tc_CP > 0 && !PSEG_KNOB("PSEG_GENERIC")) {
-            // composed tail: one small GEMM per half-resolution pixel, no LDS
-            const Tensor& s0 = e.tensors[op.src0];
-            TailC t{};
-            t.src0 = (const uint16_t*)s0.d;
-            t.src1 = op.src1 >= 0 ? (const uint16_t*)e.tensors[op.src1].d : nullptr;
-            t.skip = lg.src1 >= 0 ? (const uint16_t*)e.tensors[lg.src1].d : nullptr;
-            t.nch0 = s0.Cs / 8;
-            t.nch1 = op.src1 >= 0 ? e.tensors[op.src1].Cs / 8 : 0;
-            t.nch_skip = lg.src1 >= 0 ? e.tensors[lg.src1].Cs / 8 : 0;
-            t.Hh = e.tH(s0); t.Wh = e.tW(s0);
-            t.H0 = e.H; t.W0 = e.W; t.C = lg.Cout;
-            t.wA1 = P->d_tc_wA1; t.wA2 = P->d_tc_wA2; t.beta = P->d_tc_beta;
-            if (lg.src1 >= 0) {
-                const int sp = producer_of(e, lg.src1);
-                if (sp >= 0 && e.ops[sp].skiplog >= 0) {
-                    auto* PS = (MfmaPlan*)e.ops[sp].plan;
-                    if (!PS || !PS->d_skiplog || PS->skip_CP != P->tc_CP) return fail(PSEG_EINVAL, "skip-logits buffer missing for the composed tail");
-                    t.S = (const float*)((const char*)PS->d_skiplog + (size_t)e.page * ((size_t)e.Hp * e.Wp * PS->skip_CP * 4));   // this page slot's plane
-                    t.skip = nullptr;
-                }
-            }
-            t.out_logits = e.cur_logits; t.out_probs = e.cur_probs; t.out_labels = e.cur_labels; t.out_labels_u8 = e.cur_labels_u8;
-            t.out_margin = e.cur_margin;
-            e.margin_done = e.cur_margin != nullptr;
-            if (t.Wh % 16) return fail(PSEG_EINVAL, "composed tail needs a canvas width multiple of 32");
-            if (P->tail2) {
-                const Op& dq = e.ops[producer_of(e, op.src0)];
-                auto* PQ = (MfmaPlan*)dq.plan;
-                if (!PQ || !PQ->d_q_w || (!t.S && lg.src1 >= 0) || (P->tc_CP != 4 && P->tc_CP != 8)) return fail(PSEG_EINVAL, "fused inner deconv: plan data missing");
-                Tail2 u{};
-                const Tensor& q0 = e.tensors[dq.src0];
-                u.q0 = (const uint16_t*)q0.d; u.nq0 = q0.Cs / 8;
-                u.q1 = dq.src1 >= 0 ? (const uint16_t*)e.tensors[dq.src1].d : nullptr;
-                u.nq1 = dq.src1 >= 0 ? e.tensors[dq.src1].Cs / 8 : 0;
-                u.c3 = t.src1; u.nc3 = t.nch1;
-                u.S = t.S; u.Hh = t.Hh; u.Wh = t.Wh; u.H0 = t.H0; u.W0 = t.W0; u.C = t.C;
-                u.wQ = PQ->d_q_w; u.biasQ = PQ->d_q_bias; u.wD = P->d_t2_wD; u.wC = P->d_t2_wC; u.beta = P->d_tc_beta;
-                u.out_logits = t.out_logits; u.out_probs = t.out_probs; u.out_labels = t.out_labels; u.out_labels_u8 = t.out_labels_u8;
-                u.out_margin = t.out_margin;
-                const int nwg = cdiv(t.Hh, 2) * cdiv((t.Wh + 31) / 32, T2_ITER);      // one workgroup = 2 rows x 2 column parities
-                if (P->tc_CP == 4) tail_fused2_kernel<4><<<nwg, 256, 0, st>>>(u);
-                else tail_fused2_kernel<8><<<nwg, 256, 0, st>>>(u);
-                PSEG_HIP(hipGetLastError());
-                return PSEG_OK;
-            }
-            const int waves = t.Hh * (t.Wh / 16);
-            const dim3 grid(cdiv(waves, 4));
-            const int key = P->tc_CP * 100 + P->tc_nks0 * 10 + P->tc_nkss;
-            switch (key) {
-                case 430: tail_composed_kernel<4, 3, 0><<<grid, 256, 0, st>>>(t); break;   // skip logits from the producer's buffer
-                case 830: tail_composed_kernel<8, 3, 0><<<grid, 256, 0, st>>>(t); break;
-                case 431: tail_composed_kernel<4, 3, 1><<<grid, 256, 0, st>>>(t); break;
-                case 831: tail_composed_kernel<8, 3, 1><<<grid, 256, 0, st>>>(t); break;
-                case 1631: tail_composed_kernel<16, 3, 1><<<grid, 256, 0, st>>>(t); break;
-                case 410: tail_composed_kernel<4, 1, 0><<<grid, 256, 0, st>>>(t); break;
-                case 810: tail_composed_kernel<8, 1, 0><<<grid, 256, 0, st>>>(t); break;
-                case 1610: tail_composed_kernel<16, 1, 0><<<grid, 256, 0, st>>>(t); break;
-                default: return fail(PSEG_EUNSUPPORTED, "no composed-tail instance %d", key);
-            }
-            PSEG_HIP(hipGetLastError());
-            return PSEG_OK;
-        }
         a.tail = 1;
-        a.tail_C = lg.Cout;
-        a.H0 = e.H;
-        a.W0 = e.W;
+        fill_tail(e, op, *P, a);
         a.skip = lg.src1 >= 0 ? (const uint16_t*)e.tensors[lg.src1].d : nullptr;
         a.nch_skip = lg.src1 >= 0 ? e.tensors[lg.src1].Cs / 8 : 0;
-        a.tail_wa = P->d_tail_wa;
-        a.tail_wb = P->d_tail_wb;
-        a.tail_bias = P->d_tail_bias;
-        a.out_logits = e.cur_logits;
-        a.out_probs = e.cur_probs;
-        a.out_labels = e.cur_labels;
-        a.out_labels_u8 = e.cur_labels_u8;
-        // the specialised tail instances walk both N blocks in one workgroup (NBL = 2 in the kernel)
-        if (P->nblk == 1 && P->nblocks_n == 2 && !PSEG_KNOB("PSEG_GENERIC") && (a.sigma == 10 || a.sigma == 6)) a.nb_loop = 2;
-    }
-    if (op.tail_logits < 0 && P->nblk == 1 && P->nblocks_n == 2 && !PSEG_KNOB("PSEG_GENERIC") && a.sigma == 14 && P->NT == 4) a.nb_loop = 2;   // deconv4 (fcn_skip)
+        if (two_blocks && (a.sigma == 10 || a.sigma == 6)) a.nb_loop = 2;
+    } else if (two_blocks && a.sigma == 14 && P->NT == 4) a.nb_loop = 2;
     dim3 grid(cdiv(a.Wout, TW) * cdiv(a.Hout, 2 * P->MT), P->nblocks_n / a.nb_loop);
-    a.xq = PSEG_KNOB("PSEG_NO_XCD") ? -1 : (int)grid.x / 8;
-    a.xr = (int)grid.x % 8;
-    return launch_generic_any(a, *P, grid, st, op.layer.c_str());
+    xcd_bands(a, grid.x);
+    int dev = 0;
+    (void)device_cus(&dev);
+    return launch_generic_any(a, *P, grid, dev, st, op.layer.c_str());
 }
+
 
 int mfma_launch_pool(Engine& e, Op& op, hipStream_t st) {
     const Tensor& s = e.tensors[op.src0];
@@ -5637,11 +5659,10 @@ int mfma_launch_logits(Engine& e, Op& op, float* d_logits, float* d_probs, int64
 }
 
 bool mfma_tail_emits_margin(const Engine& e) {
-    if (PSEG_KNOB("PSEG_GENERIC")) return false;
     for (auto& op : e.ops)
         if (op.type == OP_DECONV2 && op.tail_logits >= 0 && !op.fused_away) {
             auto* P = (MfmaPlan*)op.plan;
-            return P && P->tc_CP > 0;
+            return P && P->tc_CP > 0 && P->spec;      // (the composed tail: mfma_launch_deconv2)
         }
     return false;
 }
