@@ -105,6 +105,7 @@ struct MConv {
     float* out_logits; float* out_probs; int64_t* out_labels; uint8_t* out_labels_u8;
     int xq, xr;          // XCD-aware tile order: tiles / 8 and tiles % 8 (xq < 0: off)
     float* skip_logits; int skip_CP;   // FL_SKIPLOG: [pixel][skip_CP] f32 logits contribution of this layer's output (it is not stored itself)
+    int tr_tiles, tr_stride;   // tile triples (TT_ = 3): tiles of the page (team j of workgroup b runs tile 3b + j, if there is one); bytes from one team's LDS tile to the next
     unsigned long long* trace;  // PSEG_TRACE: per-workgroup s_memtime stamps (diagnostic builds only)
     int dbg;   // ablation bits (PSEG_DBG): 1 skip input staging, 2 skip MFMAs, 4 skip epilogue, 8 skip weight DMA
     int rowreuse;   // the k-chunk table is tap-major with one k-step per tap (checked on the host, MfmaPlan::rowreuse): row-reuse k-loops may run
@@ -227,10 +228,24 @@ enum { FL_POOL = 1, FL_ADD = 2, FL_INRELU = 4, FL_UP0 = 8, FL_UP1 = 16, FL_FUSE1
 // NW_ = waves per workgroup: 4 (two workgroups per CU) or 8 (one workgroup per CU owning all 160 KiB
 // of LDS: a 16-row tile shares one weight stream among twice the pixels -- the mid layers are
 // bound by LDS-DMA bytes per CU).
-template <int MT, int NT, int KS_, int ST_, int SG_, int MODE_, int FL_, int NW_ = 4, int RR_ = 0>   // RR_ > 0: row-reuse k-loop for weight groups of RR_ k-steps
-__global__ __launch_bounds__(NW_ * 64) __attribute__((amdgpu_waves_per_eu((MT == 4 && NT == 4 && NW_ == 4 && (KS_ == 5 || KS_ == 3 || KS_ == 2) && (SG_ == 4 || SG_ == 5) && MODE_ == 0) ? 3 : 2))) void conv_mfma_kernel(MConv a) {
+//
+// TT_ = 3: TILE TRIPLES.  One 768-thread workgroup per CU owns three consecutive tiles of the tile order.  Waves 0-3, 4-7 and 8-11
+// are three TEAMS; a team is the four-wave workgroup above on its own tile -- its own tile area in LDS, its own accumulators, its
+// own store patch -- and everything it computes is what that workgroup computes (same table, k order, start value, epilogue: the
+// same bits).  What the teams share is ONE weight ring and one k-chunk table in the CU's pooled 160 KB: a weight group is fetched
+// from L2 once per CU instead of three times, every wave issues a twelfth of its 1-KB pieces, and the room three private rings
+// took goes into weight groups three times as long (a third of the group barriers).  Synchronisation stays s_barrier: all twelve
+// waves walk the same groups, so every wave meets the same barriers on every path -- and every barrier stops the whole CU, which
+// is why the host plans few, long groups (mfma_pack_op) and where the form stops paying (triple_pays).  A team without a tile (tile
+// count not a multiple of three) stages zeros through out-of-range descriptors, computes on them and has every store dropped by the
+// bounds checks of the epilogue.
+template <int MT, int NT, int KS_, int ST_, int SG_, int MODE_, int FL_, int NW_ = 4, int RR_ = 0, int TT_ = 1>   // RR_ > 0: row-reuse k-loop for weight groups of RR_ k-steps
+__global__ __launch_bounds__(NW_ * TT_ * 64) __attribute__((amdgpu_waves_per_eu((TT_ == 3 || (MT == 4 && NT == 4 && NW_ == 4 && (KS_ == 5 || KS_ == 3 || KS_ == 2) && (SG_ == 4 || SG_ == 5) && MODE_ == 0)) ? 3 : 2))) void conv_mfma_kernel(MConv a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int NW = NW_, NTHR = NW_ * 64;
+    static_assert(TT_ == 1 || (TT_ == 3 && NW_ == 4 && MT == 4 && KS_ == 5 && ST_ == 1 && (SG_ == 4 || SG_ == 5) && MODE_ == MODE_CONV && (FL_ & ~FL_POOL) == 0),
+                  "tile triples: the plain k5 stride-1 instances on dense 8 x 32 tiles");
+    constexpr int NW = NW_, NTHR = NW_ * TT_ * 64;   // NW: waves of a team (= of the workgroup unless TT_ > 1)
+    constexpr int NWR = NW_ * TT_;                   // waves that share the weight ring
     constexpr int TH = NW * (MT / 2);  // NW waves x (MT/2) rows
     if (gridDim.z > 1) {
         // a launch over several page slots (pseg_predict_batch): blockIdx.z = the slot; only plain layers are launched this way
@@ -264,12 +279,15 @@ __global__ __launch_bounds__(NW_ * 64) __attribute__((amdgpu_waves_per_eu((MT ==
     // (read-modify-write of the whole tile + a barrier: 637 vs 544 us for the two full-resolution layers on the same input)
     constexpr bool c_relu_frag = FIXED && (FL_ & FL_INRELU) != 0;
     unsigned long long* const c_trace = PSEG_DIAG ? a.trace : nullptr;
-    char* in_t = smem;
     char* w_t = smem + a.lds_w_off;
     int* tab_l = (int*)(smem + a.lds_tab_off);
 
     int tid = threadIdx.x, lane = tid & 63;
-    int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // provably wave-uniform: SALU address math
+    const int wave_r = __builtin_amdgcn_readfirstlane(tid >> 6);  // provably wave-uniform: SALU address math; this wave's place among the ring's NWR waves
+    const int team = TT_ > 1 ? wave_r / NW : 0;
+    int wave = TT_ > 1 ? wave_r - team * NW : wave_r;     // ... and inside its team: which tile rows it owns
+    char* in_t = smem + (TT_ > 1 ? team * a.tr_stride : 0);
+    bool tvalid = true;                                   // (TT_ > 1) this team has a tile
     int p16 = lane & 15, g = lane >> 4;
     const int tiles_x = (a.Wout + TW - 1) / TW;
     int oy0, ox0, iy0, ix0;
@@ -284,6 +302,11 @@ __global__ __launch_bounds__(NW_ * 64) __attribute__((amdgpu_waves_per_eu((MT ==
     };
     auto set_tile = [&](int t) {
         t = xcd_tile(t);
+        if constexpr (TT_ > 1) {
+            // (the XCD bands are bands of triples; a tile number past the page gives oy0 >= Hout: the epilogue's bounds drop its stores)
+            t = t * TT_ + team;
+            tvalid = t < a.tr_tiles;
+        }
         const int ty = t / tiles_x, tx = t - ty * tiles_x;
         oy0 = ty * TH; ox0 = tx * TW;
         iy0 = oy0 * c_stride - a.pt; ix0 = ox0 * c_stride - a.pl;
@@ -307,7 +330,7 @@ __global__ __launch_bounds__(NW_ * 64) __attribute__((amdgpu_waves_per_eu((MT ==
     // ---- weight ring: group q (GK k-steps x NT tiles, zero-padded to full groups on the host)
     // goes to ring slot q % NB by LDS-DMA; every wave issues exactly L = GK*NT/4 loads per group,
     // which is what the counted vmcnt waits below rely on.
-    const int L = (a.GK * NT - wave + NW - 1) / NW;   // pieces wave, wave + NW, ... of a group (wave-uniform)
+    const int L = (a.GK * NT - wave_r + NWR - 1) / NWR;   // pieces wave_r, wave_r + NWR, ... of a group (wave-uniform)
     const int G = a.G;
     // packed weights are laid out [group][N block][piece][lane][8]: one group of one N block is
     // a contiguous run of GK*NT KiB in exactly the order of its LDS ring slot, so the DMA source
@@ -328,15 +351,15 @@ __global__ __launch_bounds__(NW_ * 64) __attribute__((amdgpu_waves_per_eu((MT ==
     // no epilogue adds it, and all paths of the engine round in one order
     constexpr bool c_bias0 = true;
 
-    const uint16_t* wsrc = a.wpk + ((size_t)nb * a.GK * NT + wave) * 512 + lane * 8;
+    const uint16_t* wsrc = a.wpk + ((size_t)nb * a.GK * NT + wave_r) * 512 + lane * 8;
     const size_t wgstride = (size_t)a.nb_total * a.GK * NT * 512;   // elements per group
     auto stage_w = [&](int q, int slot) {
         if (c_dbg & 8) return;
         const uint16_t* src = wsrc + (size_t)q * wgstride;
-        char* dstb = w_t + slot * WBUF + wave * 1024;
+        char* dstb = w_t + slot * WBUF + wave_r * 1024;
         for (int j = 0; j < L; ++j)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + (size_t)j * (NW * 512)),
-                                             (__attribute__((address_space(3))) void*)(dstb + j * (NW * 1024)), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + (size_t)j * (NWR * 512)),
+                                             (__attribute__((address_space(3))) void*)(dstb + j * (NWR * 1024)), 16, 0, 0);
     };
     // fused tail: the skip-tensor fragments of this lane are requested now, before stage 1; the
     // barriers of the k-loop keep them above it, so their latency hides under the deconv GEMM.
@@ -567,7 +590,7 @@ __global__ __launch_bounds__(NW_ * 64) __attribute__((amdgpu_waves_per_eu((MT ==
             }
             for (int py = wave; py < c_THH; py += NW) {
                 const int iy = iy0 + py;
-                const bool rowv = (iy >= 0 && iy < a.Hin);
+                const bool rowv = (iy >= 0 && iy < a.Hin) && tvalid;   // (a team without a tile: zeros, no memory touched)
                 const unsigned rb0 = rowv ? (unsigned)(iy >> c_up0) * (unsigned)W0 * (unsigned)(a.nch0 * 16) : OOB;
                 const unsigned rb1 = rowv ? (unsigned)(iy >> c_up1) * (unsigned)W1 * (unsigned)(a.nch1 * 16) : OOB;
                 char* drow = in_t + py * a.row_pitch;
@@ -1115,7 +1138,7 @@ __global__ __launch_bounds__(NW_ * 64) __attribute__((amdgpu_waves_per_eu((MT ==
     constexpr bool c_lst = FIXED && MODE_ == MODE_CONV && MT == 4 && (FL_ & (FL_ADD | FL_SKIPLOG | FL_LOGITS | FL_DQ | FL_PERSIST | FL_FUSE1)) == 0;
     constexpr int LST_PP = NT * 32 + 8;                                   // patch bytes per pixel
     const bool lst = c_lst && !a.dst2 && a.dst_bytes != 0u && !(a.dbg & 32);
-    char* const patch = smem + wave * ((MT / 2) * TW * LST_PP);           // this wave's rows
+    char* const patch = smem + wave_r * ((MT / 2) * TW * LST_PP);         // this wave's rows (tile triples: the teams' patches follow each other)
     if (lst) lds_barrier();
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
@@ -3901,6 +3924,10 @@ struct MfmaPlan {
     int ws_form = 0;            // ... its alternative tile loops (PSEG_WS_FORM = 1 / 2: the default packing with skip logits only)
     bool persist_f1 = false;    // fused conv1 + conv2 on conv_mfma_kernel: two persistent workgroups per CU
     bool persist_s2 = false;    // single-block stride-2 k3 layer: persistent instances, when a page has many tiles
+    bool triple = false;        // conv_mfma_kernel as tile triples (three teams on one weight ring): shape, switches and its ring layout below
+    bool triple_all = false;    // PSEG_TRIPLE=1 (tests, A/B): on any page size
+    struct TripleLayout { int GK = 0, NB = 0, G = 0, stride = 0, w_off = 0, tab_off = 0, lds = 0; uint16_t* d_wpk = nullptr; };
+    TripleLayout tr;            // d_wpk: the weights packed for its group size, null where that is the plan's own (d_wpk above)
     bool sp2_all = false;       // PSEG_SP2 set (tests, A/B): conv_sp2_kernel for every eligible launch ...
     int sp2_tw = 0;             // ... = 24 / 32: with that tile width
     int sp_NT = 0, sp_sigma = 0, sp_fl = 0, sp_K = 0, sp_S = 0, sp_blk_steps = 0, sp_nblk = 0, sp_nc_full = 0, sp_nc_last = 0;
@@ -3928,7 +3955,7 @@ void mfma_free_op(Op& op) {
     (void)hipFree(p->d_skiplog);
     (void)hipFree(p->d_dq_w); (void)hipFree(p->d_dq_bias);
     (void)hipFree(p->d_q_w); (void)hipFree(p->d_q_bias); (void)hipFree(p->d_t2_wD); (void)hipFree(p->d_t2_wC);
-    (void)hipFree(p->d_sp_wpk);
+    (void)hipFree(p->d_sp_wpk); (void)hipFree(p->tr.d_wpk);
     for (int v = 0; v < 2; ++v) { (void)hipFree(p->sp_lay[v].d_tab); (void)hipFree(p->sp2_lay[v].d_tab); }
     delete p;
     op.plan = nullptr;
@@ -4044,7 +4071,7 @@ int mfma_plan_graph(Engine& e) {
         }
     // conv (64 couts = one N block of four tiles, stride 1) feeding only the logits layer -> logits / softmax /
     // argmax in that conv's epilogue (unet): its 64-channel full-resolution output is never written
-    if (!PSEG_KNOB("PSEG_NO_TAIL_FUSION") && !PSEG_KNOB("PSEG_NO_CONV_LOGITS"))
+    if (!PSEG_KNOB("PSEG_NO_TAIL_FUSION"))
         for (size_t li = 0; li < e.ops.size(); ++li) {
             Op& lg = e.ops[li];
             if (lg.type != OP_LOGITS || lg.fused_away || e.n_classes > 16 || lg.src1 >= 0) continue;
@@ -4571,7 +4598,9 @@ int mfma_pack_op(Engine& e, Op& op, const std::vector<float>& w, const std::vect
     };
     // layout [group][N block][k-step in group][cout tile][lane][8]; every channel block is
     // zero-padded to whole groups
-    std::vector<uint16_t> pk((size_t)P->G * GK * P->NTtot * 512, 0);
+    auto pack_w = [&](const int GK, const int G) {      // ... for weight groups of GK k-steps, G of them
+    const int gpb_full = cdiv(P->ks_full, GK);
+    std::vector<uint16_t> pk((size_t)G * GK * P->NTtot * 512, 0);
     for (int b = 0; b < P->nblk; ++b) {
         const bool last = b == P->nblk - 1;
         const auto& ord = last ? ord_last : ord_full;
@@ -4598,7 +4627,42 @@ int mfma_pack_op(Engine& e, Op& op, const std::vector<float>& w, const std::vect
                     }
                 }
     }
-    PSEG_TRY(upload(&P->d_wpk, pk));
+    return pk;
+    };
+    PSEG_TRY(upload(&P->d_wpk, pack_w(GK, P->G)));
+    // ---- tile triples (conv_mfma_kernel, TT_ = 3): three teams on their own tiles share ONE weight ring in the CU's pooled LDS --------
+    // Same tile, table, k order and epilogue per team; what is planned here is the second ring layout: 160 KB minus three tiles (the
+    // teams' store patches lie over tiles and ring once every wave is out of the k-loop) and the table.  PSEG_NO_TRIPLE=1: the plan
+    // switch back; PSEG_TRIPLE=1: every planned layer on any page size, page units included (tests, A/B).
+    {
+        const bool inst = KS == 5 && P->MT == 4 && ((NT == 4 && (sigma == 4 || sigma == 5)) || (NT == 3 && sigma == 4 && op.pool_dst < 0));   // triple_run
+        const bool shape = P->wg3 && !P->pp_shape && inst && P->nblocks_n == 1 && !op.up0 && !op.up1 && !op.in_relu && op.add < 0 && op.fuse1 < 0 &&
+                           op.tail_logits < 0 && op.skiplog < 0 && op.relu_dst < 0 && op.dq_fuse < 0 && NB > 1;
+        const int stride = round_up(in_bytes, 16), LDS_MAX = 160 * 1024;
+        const int steps = (LDS_MAX - 3 * stride - tab_bytes - 16) / (NT * 1024);      // k-steps the shared ring can hold
+        // two slots of the largest BALANCED groups that fit: every group boundary is a barrier of all twelve waves, with no other
+        // workgroup on the CU to fill it, so fewer and longer groups win over more groups in flight (measured -- profiles/tile_triples.txt,
+        // conv6: 9 x 2 39.5, 5 x 3 40.5, 4 x 4 42.5, 2 x 6 46.9 us).  A row-reuse layer takes the groups of eight its triple instance is
+        // compiled for (25 = 3 x 8 + 1; groups of four, the one-tile workgroup's: 58 us against its 55).
+        const bool rr8 = P->rowreuse && NT == 3 && P->ks_full == 25 && P->ks_last == 25 && steps >= 16;
+        const int nb3 = 2, cap = std::min(steps / 2, 16);
+        const int gk3 = rr8 ? 8 : (cap >= 1 ? cdiv(ks_max, cdiv(ks_max, cap)) : 0);
+        if (shape && gk3 >= 1 && nb3 >= 2 && !PSEG_KNOB("PSEG_NO_TRIPLE")) {
+            const char* const sw = PSEG_KNOB("PSEG_TRIPLE");
+            P->triple = true;
+            P->triple_all = sw && atoi(sw) != 0;
+            MfmaPlan::TripleLayout& T = P->tr;
+            T.GK = gk3; T.NB = nb3; T.stride = stride;
+            T.G = (P->nblk - 1) * cdiv(P->ks_full, gk3) + cdiv(P->ks_last, gk3);
+            T.w_off = 3 * stride;
+            T.tab_off = T.w_off + nb3 * gk3 * NT * 1024;
+            T.lds = std::max(T.tab_off + tab_bytes + 16, 3 * 4 * (P->MT / 2) * TW * (NT * 32 + 8));
+            if (gk3 != GK) PSEG_TRY(upload(&T.d_wpk, pack_w(gk3, T.G)));
+        }
+        if (PSEG_KNOB("PSEG_LOG_GENERIC") && shape)
+            fprintf(stderr, "[pseg] triple %s: %d (one tile per workgroup: GK %d NB %d lds %d; triples: GK %d NB %d lds %d)\n", op.layer.c_str(),
+                    P->triple ? 1 : 0, GK, NB, P->lds_bytes, P->triple ? P->tr.GK : 0, P->triple ? P->tr.NB : 0, P->triple ? P->tr.lds : 0);
+    }
     std::vector<float> bb((size_t)P->NTtot * 16, 0.0f);
     for (int n = 0; n < P->NTtot * 16; ++n) {
         if (!deconv) { if (n < Cout) bb[n] = bias[n]; }
@@ -5031,6 +5095,15 @@ static int sp2_pick(const MfmaPlan& P, const Extent& x, int* tiles) {
     return ((npairs >= x.cus && P.sp_NT == 3 && x.pages > 1) || P.sp2_all) ? bestv : -1;
 }
 
+// Tile triples (conv_mfma_kernel, three teams on one weight ring): the four-cout-tile layers of a single page once every CU gets a
+// whole triple.  Measured (profiles/tile_triples.txt: 2048x1536, parent and new build alternating three times, us): conv5 32.6 / 32.2 /
+// 32.3 -> 29.7 / 29.5 / 29.8, conv6 42.5 / 42.4 / 42.3 -> 41.3 / 40.7 / 40.7; deconv3 (three cout tiles, four channel blocks: each
+// block change and group boundary stops the whole CU) 56.5 / 56.6 / 56.8 -> 57.3 / 57.0 / 56.7 and 32-page units 0.3747 / 0.3740 /
+// 0.3750 -> 0.3780 / 0.3771 / 0.3814 ms per page lose: they keep route_mfma.  PSEG_TRIPLE=1 (plan switch): every planned layer, any size.
+static bool triple_pays(const MfmaPlan& P, const Extent& x) {
+    return P.triple_all || (P.NT == 4 && x.pages == 1 && x.tiles >= 3 * x.cus);
+}
+
 // conv_pp_kernel and conv12_ws_kernel keep TWO input tiles of this size in LDS
 static int tile_bytes(const MfmaPlan& P) { return round_up(P.THH * P.row_pitch, 16); }
 
@@ -5432,6 +5505,35 @@ static int route_ws(const Op& op, const MfmaPlan& P, const MConv& a, const Exten
                       [&] { return ws_run(P, w, grid, lds, x.dev, st); });
 }
 
+#define PSEG_TRIPLE(NT_, SG_, FL_, RR_)                                                                \
+    if (P.NT == NT_ && w.sigma == SG_ && (w.pool_dst ? FL_POOL : 0) == (FL_) && rr == RR_)             \
+        return launch_lds<conv_mfma_kernel<4, NT_, 5, 1, SG_, MODE_CONV, (FL_), 4, RR_, 3>>(w, grid, 768, P.tr.lds, dev, st);
+static int triple_run(const MfmaPlan& P, const MConv& w, int rr, dim3 grid, int dev, hipStream_t st) {
+    PSEG_TRIPLE(4, 5, 0, 0)                                // conv5
+    PSEG_TRIPLE(4, 4, FL_POOL, 0)                          // conv6
+    PSEG_TRIPLE(3, 4, 0, 8)                                // deconv3, row reuse (weight groups of eight k-steps)
+    PSEG_TRIPLE(3, 4, 0, 0) PSEG_TRIPLE(4, 4, 0, 0) PSEG_TRIPLE(4, 5, FL_POOL, 0)
+    return fail(PSEG_EUNSUPPORTED, "tile triples: no kernel instance for NT %d sigma %d (the plan's flag says there is one)", P.NT, w.sigma);
+}
+#undef PSEG_TRIPLE
+
+// conv_mfma_kernel as tile triples: one 768-thread workgroup per three tiles, the teams' weight ring shared (MfmaPlan::triple)
+static int route_triple(const Op& op, const MfmaPlan& P, const MConv& a, const Extent& x, hipStream_t st) {
+    const char* const tr = PSEG_DIAG_KNOB("PSEG_TRACE");     // (diagnostic build: a traced layer stays on the one-tile workgroups its stamps are read for)
+    if (!P.triple || !triple_pays(P, x) || (tr && op.layer == tr)) return ROUTE_NO;
+    MConv w = a;
+    w.GK = P.tr.GK; w.NB = P.tr.NB; w.G = P.tr.G;
+    w.lds_w_off = P.tr.w_off; w.lds_tab_off = P.tr.tab_off;
+    if (P.tr.d_wpk) w.wpk = P.tr.d_wpk;
+    w.tr_tiles = x.tiles; w.tr_stride = P.tr.stride;
+    dim3 grid((unsigned)cdiv(x.tiles, 3), 1, (unsigned)x.pages);      // (page units: blockIdx.z = the page slot, as in route_mfma)
+    xcd_bands(w, grid.x);
+    const int rr = (w.rowreuse && P.NT == 3 && P.tr.GK == 8 && P.ks_full == 25 && P.ks_last == 25) ? 8 : 0;   // (the row-reuse instance is compiled for the plan's group size)
+    if (PSEG_KNOB("PSEG_LOG_GENERIC"))
+        fprintf(stderr, "[pseg] triple launch %s: tiles %d triples %u pages %d\n", op.layer.c_str(), x.tiles, grid.x, x.pages);
+    return triple_run(P, w, rr, grid, x.dev, st);
+}
+
 // conv_mfma_kernel: one workgroup per tile, or its two persistent forms
 static int route_mfma(const Op& op, const MfmaPlan& P, MConv& a, dim3 grid, const Extent& x, hipStream_t st) {
     if (P.persist_f1) {
@@ -5507,6 +5609,7 @@ int mfma_launch_conv(Engine& e, Op& op, hipStream_t st) {
     if ((rc = route_sp(e, op, P, a, x, st)) != ROUTE_NO) return rc;
     if ((rc = route_pp(P, a, x, st)) != ROUTE_NO) return rc;
     if ((rc = route_ws(op, P, a, x, st)) != ROUTE_NO) return rc;
+    if ((rc = route_triple(op, P, a, x, st)) != ROUTE_NO) return rc;
     return route_mfma(op, P, a, grid, x, st);
 }
 
