@@ -645,6 +645,60 @@ int pseg_cc_tables(int device, const int32_t* labels, int H, int W, int num_labe
                    int pred_bytes, const void* mask, int mask_bytes, int n_classes, int32_t* stats,
                    double* centroids, int64_t* eq, int64_t* hist_pred, int64_t* hist_mask, int32_t* order);
 
+/* ---- a list of pages scored in one device-resident call ----------------------------- */
+
+/* One page of pseg_eval_pages: pred and mask are uint8 (H,W) label maps; binary is uint8 (H,W) with ink != 0, or NULL. */
+typedef struct pseg_eval_page {
+    const uint8_t* pred;
+    const uint8_t* mask;
+    const uint8_t* binary;
+    int H, W;
+} pseg_eval_page;
+
+/* One component matcher of lib/evaluation.py with its only_label filter (lib/evaluation.py:52-70, 87-101). */
+typedef struct pseg_eval_rule {
+    int kind;                    /* 0: cc_matching, 1: cc_equal (its threshold in threshold_tp) */
+    int label;
+    double threshold_tp, threshold_fp, threshold_mask;
+    int filter_label;            /* only_label(); 0: no filter */
+    double filter_threshold;
+} pseg_eval_rule;
+
+/* count_matches / total_accuracy / fgpa / fgoverlap_per_class (lib/evaluation.py:8-32, lib/image_ops.py:8-55) and the summed
+ * verdicts of ConnectedComponentEval.run_per_component(cc_matching(...) / cc_equal(...)) (lib/evaluation.py:73-117) for a list of
+ * pages.  All arrays are host pointers; any of the three outputs may be NULL.
+ *   counts[page]     = what pseg_eval_confusion(pred, 1, mask, 1, binary, H*W, n_classes, ...) returns for the page (binary == NULL:
+ *                      every pixel counts as ink).
+ *   components[page] = the `connectivity`-connected components of binary != 0 (0 for binary == NULL: such a page has no components,
+ *                      and its verdicts are zero).
+ *   verdicts[page][r] for rule r, over the components the rule KEEPS: with s the component's pixel count, e its pixels with
+ *                      pred == mask (raw bytes), P[L] / M[L] its pixels with pred == L / mask == L, a component is kept when
+ *                      filter_label == 0, or M[fl] / s >= filter_threshold, or P[fl] > 0 (ConnectedComponentEval._filter: a falsy
+ *                      label is no filter).  kind 0 adds (ptp && mm, pfp && !mm, mm && !ptp) to slots 0..2, with ptp = P[l] / s >=
+ *                      threshold_tp, pfp = P[l] / s >= threshold_fp, mm = M[l] / s >= threshold_mask; kind 1 adds 1 to slot 0 when
+ *                      e / s >= threshold_tp, else to slot 1.  Slot 3 counts the kept components.  The quotients are IEEE double
+ *                      divisions of the two integers, the comparisons double comparisons: a decision has Python's bits.
+ * These are the sums of what run_per_component yields; they are order-free, and no component numbering is produced.
+ * n_classes in 1..255, connectivity 4 or 8, n_rules in 0..8, every rule label and filter label in [0, n_classes), H, W >= 0 (a page
+ * without pixels gives zeros).  Every page and rule is checked before the first device call and PSEG_EINVAL names it ("page 3: ...",
+ * "rule 1: ..."); the caller's arrays are written only after the last group has run, and not at all on an error.  n_pages == 0
+ * returns PSEG_OK with no device work.
+ * The list is cut into GROUPS in list order (pseg_eval_page_groups): a group ends after 64 pages, or before the page that would
+ * bring its pixels above 64 Mi (a larger page is a group of its own).  A group is one table upload, one memset of its records, its
+ * maps copied to 256-byte-aligned offsets, five launches ragged over the group (histogram; 32 x 64 tiles: closed components judged
+ * in LDS, open ones to root slots; unions across tile edges; counters to final roots; final roots judged), the records into
+ * page-locked memory and ONE host wait.  No label image, sort or component list: beyond the maps the workspace is 192 root slots
+ * (4 + 4 * (2 + 2 * watched labels) bytes each), 192 bytes of rim table, 768 bytes of union tasks and 8 bytes of list lengths per
+ * tile.  It is grow-only, cached per device, guarded by its own lock and used on its own stream; pseg_release_workspace frees it. */
+int pseg_eval_pages(int device, int n_pages, const pseg_eval_page* pages, int n_classes, int connectivity,
+                    int n_rules, const pseg_eval_rule* rules,
+                    int64_t* counts,      /* [n_pages][2][K][K], K = n_classes + 1: pseg_eval_confusion's layout per page */
+                    int64_t* components,  /* [n_pages]: ink components of the page */
+                    int64_t* verdicts);   /* [n_pages][n_rules][4] */
+/* How pseg_eval_pages cuts a page list into groups (host logic, no device needed).  Returns the number of groups (>= 0) and fills
+ * first / count (each may be NULL) for the first max_groups of them, or a negative PSEG_E*. */
+int pseg_eval_page_groups(int n_pages, const int* H, const int* W, int* first, int* count, int max_groups); /* host only */
+
 /* prepare_images (lib/dataset.py:131-150), all pixel work on the device in one call.
  * image, binary: uint8 (H0,W0) scan and binarisation (paper = 1 or 255).  (H1,W1) =
  * pseg_rescale_shape(H0, W0, target_line_height / line_height_px); (H2,W2) = the max_width stage

@@ -411,6 +411,7 @@ __host__ __device__ inline bool glyph_shaped(int h, int w) {
 void char_heights_release_workspace(int dev);   // pseg_lineheight.hip: the list entry's per-device workspace (pseg_release_workspace)
 void pngdec_release_workspace(int dev);   // pseg_pngdec.hip: the PNG decoder's per-device workspace and stream (pseg_release_workspace)
 void png_release_workspace(int dev);   // pseg_png.hip: the encoder's per-device workspace (pseg_release_workspace)
+void eval_pages_release_workspace(int dev);   // pseg_evalpages.hip: the page scorer's per-device workspace and stream (pseg_release_workspace)
 // pseg_png.hip, for the page chain: the masks of `pages` label maps of one shape as PNG streams in one set of launches, enqueued on
 // `st` without a wait; the workspace (PngPages::bytes, from png_pages_layout) is the caller's.  Page p's sizes: ((u64*)d_ws)[4 p + k];
 // its stream k (k-th requested mask): d_ws + head + p * page + k * per + slots_b + meta_b + offs_b, chunk CRCs left to

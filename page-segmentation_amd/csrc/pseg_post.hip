@@ -1098,6 +1098,7 @@ int pseg_release_workspace(int device) {
     png_release_workspace(device);
     char_heights_release_workspace(device);
     pngdec_release_workspace(device);
+    eval_pages_release_workspace(device);
     return release_workspace(device);
 }
 

@@ -155,3 +155,76 @@ class ConnectedComponentEval:
             elif not self._filter(i):
                 continue
             yield func.from_tables(self._t, i) if fast else self._call_masked(i, func)
+
+
+# ---- a list of pages in one device call (pseg_eval_pages) ------------------------------------------------------------
+# The arithmetic of count_matches / total_accuracy over a joint histogram counts[b][m][p] (image_ops has fgpa's and
+# fgoverlap_per_class's): the list route and the per-page functions derive the same numbers from the same table.
+
+def matches_from_counts(counts: np.ndarray, label: int) -> Tuple[int, int, int]:
+    """count_matches from counts[b][m][p]: both planes together are _counts' table."""
+    c = np.asarray(counts)
+    c = c[0] + c[1]
+    if not 0 <= label < c.shape[0]:
+        return 0, 0, 0
+    tp = int(c[label, label])
+    return tp, int(c[label].sum()) - tp, int(c[:, label].sum()) - tp
+
+
+def accuracy_from_counts(counts: np.ndarray) -> Tuple[int, int]:
+    """total_accuracy from counts[b][m][p]: (pixels with mask == pred, pixels)."""
+    c = np.asarray(counts)
+    return int(np.trace(c[0]) + np.trace(c[1])), int(c.sum())
+
+
+def rule_tuple(rule):
+    """A rule of evaluate_pages as engine.eval_rule's tuple.  rule: a cc_matching(...) / cc_equal(...) object, or a pair
+    (object, (filter_label, filter_threshold)) for ConnectedComponentEval.only_label; a falsy filter label is no filter
+    (_filter), a falsy threshold_mask is threshold_tp (_CcMatching)."""
+    flt = (0, 0.0)
+    if isinstance(rule, (tuple, list)):
+        rule, flt = rule
+    fl, ft = (int(flt[0]), float(flt[1])) if flt and flt[0] else (0, 0.0)
+    if isinstance(rule, _CcMatching):
+        tm = rule.threshold_mask if rule.threshold_mask else rule.threshold_tp
+        return _eng.eval_rule(0, rule.label, rule.threshold_tp, rule.threshold_fp, tm, fl, ft)
+    if isinstance(rule, _CcEqual):
+        return _eng.eval_rule(1, 0, rule.threshold, 0.0, 0.0, fl, ft)
+    raise Exception("evaluate_pages takes cc_matching(...) / cc_equal(...) rules; other callbacks keep ConnectedComponentEval")
+
+
+class PageScore:
+    """One page of evaluate_pages: the joint histogram counts[b][m][p], the number of ink components, and per rule the four
+    integers (cc_matching: TP, FP, FN; cc_equal: matching, not matching, 0; then the components the rule kept)."""
+
+    def __init__(self, counts, num_components, verdicts):
+        self.counts = counts
+        self.num_components = int(num_components)
+        self.verdicts = verdicts
+
+    def count_matches(self, label: int) -> Tuple[int, int, int]:
+        return matches_from_counts(self.counts, label)
+
+    def total_accuracy(self) -> Tuple[int, int]:
+        return accuracy_from_counts(self.counts)
+
+    def fgpa(self):
+        from .image_ops import fgpa_from_counts
+        return fgpa_from_counts(self.counts)
+
+    def fgoverlap_per_class(self, n_classes: int):
+        from .image_ops import fgoverlap_from_counts
+        return fgoverlap_from_counts(self.counts, n_classes)
+
+    def cc(self, i: int) -> Tuple[int, int, int, int]:
+        return tuple(int(v) for v in self.verdicts[i])
+
+
+def evaluate_pages(masks, preds, binaries, rules=(), connectivity=4):
+    """One PageScore per page from ONE device call (engine.eval_pages): what count_matches, total_accuracy, image_ops.fgpa,
+    image_ops.fgoverlap_per_class and the summed run_per_component(cc_matching(...) / cc_equal(...)) give page by page.
+    binaries: a list whose entries may be None (no components; every pixel counts as ink in the histogram), or None."""
+    masks, preds = list(masks), list(preds)
+    r = _eng.eval_pages(preds, masks, None if binaries is None else list(binaries), None, connectivity,
+                        [rule_tuple(x) for x in rules])
+    return [PageScore(r["counts"][k], r["components"][k], r["verdicts"][k]) for k in range(len(masks))]

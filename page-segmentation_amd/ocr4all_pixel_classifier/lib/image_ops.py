@@ -71,7 +71,12 @@ def fgpa(pred: np.ndarray, mask: np.ndarray, bin: np.ndarray):
     top = int(max(pred.max(initial=0), mask.max(initial=0))) + 1
     if pred.min(initial=0) < 0 or mask.min(initial=0) < 0 or top > 255:
         raise Exception("fgpa: labels must lie in 0..254")
-    c = _fg_counts(pred, mask, bin, top)[1]
+    return fgpa_from_counts(_fg_counts(pred, mask, bin, top))
+
+
+def fgpa_from_counts(counts):
+    """fgpa from the joint histogram counts[b][m][p] (shared with evaluation.PageScore)."""
+    c = np.asarray(counts)[1]
     fg_count = int(c.sum())
     wrong = fg_count - int(np.trace(c))
     return (fg_count - wrong) / fg_count                      # ZeroDivisionError on a page without ink, as the reference
@@ -85,9 +90,20 @@ def fgoverlap_per_class(pred: np.ndarray, mask: np.ndarray, bin: np.ndarray, n_c
     if bin.size and bin.max() > 1:
         raise Exception("fgoverlap_per_class: bin must be 0/1 (1 is foreground)")
     k = int(n_classes) + 1                                    # classes 0..n_classes are reported
-    c_full = _fg_counts(pred, mask, bin, k)[1]                 # ink plane, [mask][pred]; slot k = other labels
+    return fgoverlap_from_counts(_fg_counts(pred, mask, bin, k), n_classes)
+
+
+def fgoverlap_from_counts(counts, n_classes: int):
+    """fgoverlap_per_class from the joint histogram counts[b][m][p] (shared with evaluation.PageScore).  The table may have
+    more or fewer class slots than n_classes + 1: a class it has no slot for has no pixels, its last slot collects the labels
+    beyond its range, and a row / column sum runs over every slot either way."""
+    k = int(n_classes) + 1
+    c_full = np.asarray(counts)[1]                             # ink plane, [mask][pred]; last slot = other labels
     overlaps, tps, fps, fns = [], [], [], []
     for i in range(k):
+        if i >= c_full.shape[0]:
+            overlaps.append(np.nan); tps.append(0); fps.append(0); fns.append(0)
+            continue
         tp = int(c_full[i, i])
         fp = int(c_full[:, i].sum()) - tp                      # predicted i, expected something else
         fn = int(c_full[i, :].sum()) - tp

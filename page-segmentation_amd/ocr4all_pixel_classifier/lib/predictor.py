@@ -217,6 +217,51 @@ class Predictor:
                     self.write_masks(data, output_dir=output_dir, level=level)
                 yield paths[k]
 
+    def evaluate_dataset(self, dataset: Dataset, rules=(), connectivity=4, chunk=64, mixed=None):
+        """Every page of a dataset predicted and scored against its mask: one evaluation.PageScore per page, in dataset order.
+        Per chunk of `chunk` pages the list chain (Engine.predict_chain_pages with which=(), labels=True; the settings'
+        post-processors and high_res_output, prepared as write_masks_dataset prepares them) hands down the uint8 label maps, and
+        ONE evaluation.evaluate_pages call scores them against data.mask and the binarisation the chain used.  Pages the list
+        chain cannot take (_chain_inputs, _list_takes) go through predict_single.  rules / connectivity: evaluate_pages'.
+        mixed: write_masks_dataset's.  A page without a mask, or whose mask has not the shape of the final label map, raises
+        and names the entry."""
+        from .evaluation import evaluate_pages
+        pages = list(dataset.data)
+        name = lambda k, data: "entry %d (%s)" % (k, data.image_path or data.mask_path or "unnamed")
+        for k, data in enumerate(pages):
+            if data.mask is None:
+                raise Exception("evaluate_dataset: %s has no mask" % name(k, data))
+        scores = []
+        step = max(1, int(chunk))
+        for i in range(0, len(pages), step):
+            part = pages[i:i + step]
+            inputs = []
+            for data in part:
+                inputs.append(self._chain_inputs(data, True, record=False))
+                if inputs[-1] is not None and not self._list_takes(np.shape(inputs[-1][1])[:2]):
+                    inputs[-1] = None
+            labels, binaries = [None] * len(part), [None] * len(part)
+            on_device = [k for k, got in enumerate(inputs) if got is not None]
+            if on_device:
+                shapes = set((tuple(np.shape(inputs[k][1])[:2]), inputs[k][3] or tuple(np.shape(inputs[k][1])[:2])) for k in on_device)
+                use_mixed = (self.MIXED_DEFAULT and len(shapes) > 1) if mixed is None else bool(mixed)
+                got = self.network.model.predict_chain_pages(
+                    [inputs[k][1] for k in on_device], binaries=[inputs[k][2] for k in on_device],
+                    out_shapes=[inputs[k][3] for k in on_device], post_ops=inputs[on_device[0]][4],
+                    exact_labels=self.network.exact == "labels", which=(), labels=True, mixed=use_mixed)
+                for j, k in enumerate(on_device):
+                    labels[k], binaries[k] = got[j]["labels"], inputs[k][2]
+            for k, data in enumerate(part):
+                if inputs[k] is None:
+                    pred = self.predict_single(data)
+                    labels[k] = np.asarray(pred.labels)
+                    binaries[k] = None if pred.data.binary is None else np.asarray(pred.data.binary)
+                if np.shape(data.mask) != np.shape(labels[k]):
+                    raise Exception("evaluate_dataset: %s: the mask has shape %r, the label map %r"
+                                    % (name(i + k, data), np.shape(data.mask), np.shape(labels[k])))
+            scores += evaluate_pages([data.mask for data in part], labels, binaries, rules, connectivity)
+        return scores
+
     def _scan_route(self, entry: SingleData, path):
         """Whether write_masks_scans may send this entry through the scan chain, as far as that shows before the file is read."""
         from . import output

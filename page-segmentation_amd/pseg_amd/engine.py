@@ -34,7 +34,7 @@ EXPORTED_SYMBOLS = (
     "pseg_predict_chain_pages_mixed_png", "pseg_chain_units_mixed", "pseg_predict_chain_scans_png", "pseg_prepare_scans",
     "pseg_rescale_shape", "pseg_gaussian_kernel", "pseg_resize_nearest", "pseg_resize_nearest_device", "pseg_scale_image",
     "pseg_prepare_images", "pseg_affine_warp", "pseg_affine_warp_fill", "pseg_brightness_shift",
-    "pseg_eval_confusion", "pseg_cc_label", "pseg_cc_tables",
+    "pseg_eval_confusion", "pseg_cc_label", "pseg_cc_tables", "pseg_eval_pages", "pseg_eval_page_groups",
     "pseg_tile_plan", "pseg_predict_tiled_device", "pseg_predict_tiled", "pseg_engine_set_tiling", "pseg_engine_page_fits",
 )
 
@@ -50,6 +50,17 @@ class SCAN(ctypes.Structure):
     """pseg_scan: one gray scan and the page it becomes (pseg_prepare_scans, pseg_predict_chain_scans_png)."""
     _fields_ = [("gray", ctypes.c_void_p), ("H0", ctypes.c_int), ("W0", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int),
                 ("wy", ctypes.c_void_p), ("ry", ctypes.c_int), ("wx", ctypes.c_void_p), ("rx", ctypes.c_int), ("final_is_scan", ctypes.c_int)]
+
+
+class EVAL_PAGE(ctypes.Structure):
+    """pseg_eval_page: one page of pseg_eval_pages."""
+    _fields_ = [("pred", ctypes.c_void_p), ("mask", ctypes.c_void_p), ("binary", ctypes.c_void_p), ("H", ctypes.c_int), ("W", ctypes.c_int)]
+
+
+class EVAL_RULE(ctypes.Structure):
+    """pseg_eval_rule: cc_matching (kind 0) or cc_equal (kind 1) with its only_label filter."""
+    _fields_ = [("kind", ctypes.c_int), ("label", ctypes.c_int), ("threshold_tp", ctypes.c_double), ("threshold_fp", ctypes.c_double),
+                ("threshold_mask", ctypes.c_double), ("filter_label", ctypes.c_int), ("filter_threshold", ctypes.c_double)]
 
 
 class PsegError(Exception):
@@ -148,6 +159,8 @@ def lib():
     L.pseg_eval_confusion.argtypes = [i, vp, i, vp, i, vp, i64, i, vp]
     L.pseg_cc_label.argtypes = [i, vp, i, i, i, vp, c.POINTER(c.c_int32)]
     L.pseg_cc_tables.argtypes = [i, vp, i, i, i, vp, i, vp, i, i, vp, vp, vp, vp, vp, vp]
+    L.pseg_eval_pages.argtypes = [i, i, c.POINTER(EVAL_PAGE), i, i, i, c.POINTER(EVAL_RULE), vp, vp, vp]
+    L.pseg_eval_page_groups.argtypes = [i, vp, vp, vp, vp, i]
     L.pseg_bbox_fill.argtypes = [i, vp, vp, i, i, i]
     L.pseg_masks.argtypes = [i, vp, vp, vp, i, i, i, vp, vp, vp, vp]
     L.pseg_masks_device.argtypes = [i, vp, vp, vp, i, i, i, vp, vp, vp, vp, vp]
@@ -1298,4 +1311,92 @@ def cc_tables(labels, num_labels, pred=None, mask=None, n_classes=0, want_stats=
     _check(lib().pseg_cc_tables(int(device), _ptr(lab), lab.shape[0], lab.shape[1], n, opt(p), p.dtype.itemsize if p is not None else 0,
                                 opt(m), m.dtype.itemsize if m is not None else 0, int(n_classes), opt(stats), opt(cent), opt(eq),
                                 opt(hp), opt(hm), opt(order)))
+    return out
+
+
+EVAL_MAX_RULES = 8
+
+
+def eval_rule(kind, label=0, threshold_tp=0.0, threshold_fp=0.0, threshold_mask=0.0, filter_label=0, filter_threshold=0.0):
+    """One rule of eval_pages as a plain tuple: kind 0 cc_matching(label, threshold_tp, threshold_fp, threshold_mask), kind 1
+    cc_equal(threshold_tp); filter_label / filter_threshold are only_label()'s arguments (a falsy label: no filter)."""
+    return (int(kind), int(label), float(threshold_tp), float(threshold_fp), float(threshold_mask), int(filter_label or 0),
+            float(filter_threshold or 0.0))
+
+
+def eval_page_groups(shapes):
+    """The groups pseg_eval_pages would cut a list of page shapes into: [(first page, page count), ...] (host logic, no GPU)."""
+    n = len(shapes)
+    H = (ctypes.c_int * max(n, 1))(*[int(s[0]) for s in shapes])
+    W = (ctypes.c_int * max(n, 1))(*[int(s[1]) for s in shapes])
+    first, count = (ctypes.c_int * max(n, 1))(), (ctypes.c_int * max(n, 1))()
+    ng = lib().pseg_eval_page_groups(n, H, W, first, count, n)
+    _check(min(ng, 0))
+    return [(first[g], count[g]) for g in range(ng)]
+
+
+def _eval_map(a, what, k):
+    """A label map of eval_pages as a contiguous uint8 (H,W) array; labels outside 0..254 raise, naming the page."""
+    a = np.asarray(a)
+    if a.ndim != 2:
+        raise PsegError("page %d: %s must be an (H,W) label map, got shape %r" % (k, what, a.shape))
+    if a.dtype == np.bool_:
+        a = a.view(np.uint8)
+    if a.dtype.kind not in "iu":
+        raise PsegError("page %d: %s must hold integer labels, got %s" % (k, what, a.dtype))
+    if a.dtype != np.uint8:
+        if a.size and (a.min() < 0 or a.max() > 254):
+            raise PsegError("page %d: %s has labels outside 0..254" % (k, what))
+        a = a.astype(np.uint8)
+    elif a.size and a.max() > 254:
+        raise PsegError("page %d: %s has labels outside 0..254" % (k, what))
+    return np.ascontiguousarray(a)
+
+
+def eval_pages(preds, masks, binaries=None, n_classes=None, connectivity=4, rules=(), device=0):
+    """A list of pages scored against ground truth in one device-resident call (pseg_eval_pages): {"counts": (n, 2, K, K) int64, the
+    joint histogram eval_confusion gives per page (K = n_classes + 1; binaries[i] None: every pixel counts as ink), "components":
+    (n,) int64, the ink components per page, "verdicts": (n, len(rules), 4) int64, per rule (eval_rule tuples) the summed
+    cc_matching vector or the cc_equal (true, false) counts over the components the rule keeps, and their number}.
+    n_classes None: the top label over maps and rules, plus 1."""
+    preds, masks = list(preds), list(masks)
+    n = len(preds)
+    if len(masks) != n or (binaries is not None and len(binaries) != n):
+        raise PsegError("preds, masks and binaries must have one entry per page")
+    rules = [eval_rule(*r) for r in rules]
+    if len(rules) > EVAL_MAX_RULES:
+        raise PsegError("%d rules (at most %d in one call)" % (len(rules), EVAL_MAX_RULES))
+    if connectivity not in (4, 8):
+        raise PsegError("connectivity %r (4 or 8)" % (connectivity,))
+    ps, ms, bs = [], [], []
+    for k in range(n):
+        p, m = _eval_map(preds[k], "pred", k), _eval_map(masks[k], "mask", k)
+        if p.shape != m.shape:
+            raise PsegError("page %d: pred %r and mask %r differ in shape" % (k, p.shape, m.shape))
+        b = None
+        if binaries is not None and binaries[k] is not None:
+            b = np.ascontiguousarray(np.asarray(binaries[k]) != 0).view(np.uint8)
+            if b.shape != p.shape:
+                raise PsegError("page %d: binary %r and pred %r differ in shape" % (k, b.shape, p.shape))
+        ps.append(p); ms.append(m); bs.append(b)
+    if n_classes is None:
+        top = max([int(a.max(initial=0)) for a in ps + ms] + [max(r[1], r[5]) for r in rules] + [0])
+        n_classes = top + 1
+    n_classes = int(n_classes)
+    if not 1 <= n_classes <= 255:
+        raise PsegError("n_classes %d outside 1..255" % n_classes)
+    for k, r in enumerate(rules):
+        if r[0] not in (0, 1):
+            raise PsegError("rule %d: kind %d (0: cc_matching, 1: cc_equal)" % (k, r[0]))
+        if not (0 <= r[1] < n_classes and 0 <= r[5] < n_classes):
+            raise PsegError("rule %d: label %d / filter label %d outside [0, %d)" % (k, r[1], r[5], n_classes))
+    K, nr = n_classes + 1, len(rules)
+    out = {"counts": np.zeros((n, 2, K, K), np.int64), "components": np.zeros(n, np.int64), "verdicts": np.zeros((n, nr, 4), np.int64)}
+    pages = (EVAL_PAGE * max(n, 1))()
+    for k in range(n):
+        pages[k] = EVAL_PAGE(ps[k].ctypes.data, ms[k].ctypes.data, bs[k].ctypes.data if bs[k] is not None else None,
+                             ps[k].shape[0], ps[k].shape[1])
+    crules = (EVAL_RULE * max(nr, 1))(*[EVAL_RULE(*r) for r in rules])
+    _check(lib().pseg_eval_pages(int(device), n, pages, n_classes, int(connectivity), nr, crules, _ptr(out["counts"]),
+                                 _ptr(out["components"]), _ptr(out["verdicts"]) if nr else None))
     return out
