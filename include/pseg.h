@@ -754,6 +754,55 @@ int pseg_predict_chain_scans_png(pseg_engine* e, int n_scans, const pseg_scan* s
                                  const uint8_t* lut, int n_lut, int level, unsigned want, int unit_cap,
                                  pseg_chain_sink sink, void* user);
 
+/* ---- Adaptive binarisation of scans on the device ------------------------------------------------------- */
+
+/* How a scan becomes its ink map.  window == 0: the fixed threshold, ink = scan <= 127 (k and R are not read).  Otherwise Sauvola's
+ * threshold over a square window of odd side `window`, 3 .. 255, radius r = window / 2, indices outside the scan mirrored without an
+ * edge repeat (NumPy's mode='reflect'), so that every pixel has n = window * window samples:
+ *   S1 = sum of the window's values, S2 = sum of their squares (integers);  m = S1 / n;  var = S2 / n - m * m;
+ *   s = sqrt(max(var, 0));  T = m * (1 + k * (s / R - 1));  ink = value <= T
+ * in float64, in this operation order.  0 <= k <= 1, R > 0; the usual choice is k = 0.2, R = 128. */
+typedef struct pseg_binarize {
+    int window;
+    double k, R;
+} pseg_binarize;
+
+/* The ink maps of n gray scans (gray[i]: uint8 H[i] x W[i], dense) in one device-resident call: out_ink[i] uint8 H x W, ink = 1;
+ * out_threshold (the array or any entry may be NULL): float64 H x W, the threshold T of every pixel (127 for a fixed entry).  how has
+ * one entry per scan.  Host pointers, synchronous.  The cost per pixel does not depend on the window: a launch writes the packed
+ * row sums (one 64-bit word per pixel), a second one slides the window sums down every column and decides; integer sums only.  The
+ * list is cut into groups as pseg_char_heights cuts it (64 scans, or 64 MiB of scan bytes); a group costs two ragged launches and
+ * ONE host wait, nothing is allocated per scan.  The workspace (per pixel: the scan, the ink map, 8 bytes of row sums and 8 bytes
+ * of threshold where asked for) is grow-only, cached per device and freed by pseg_release_workspace.
+ * n == 0 returns PSEG_OK before a device is touched.  Every scan is checked before any device work and the message names it
+ * ("scan 3: ..."): an even window, a window outside 3 .. 255 other than 0, k outside [0, 1], R <= 0, a NULL pointer or an empty
+ * shape is PSEG_EINVAL; nothing is written to the outputs then. */
+int pseg_binarize_scans(int device, int n, const uint8_t* const* gray, const int* H, const int* W, const pseg_binarize* how,
+                        uint8_t* const* out_ink, double* const* out_threshold);
+/* The same on the host, without a device: the same decision function over the same integer sums, the same bits. */
+int pseg_binarize_scans_host(int n, const uint8_t* const* gray, const int* H, const int* W, const pseg_binarize* how,
+                             uint8_t* const* out_ink, double* const* out_threshold);
+
+/* The geometry the device kernels were compiled with (host arithmetic, no device; every pointer may be NULL): a row workgroup takes
+ * *segment padded pixels, i.e. owns segment - (window - 1) columns of a row; a column workgroup slides *tile columns down *band
+ * rows; rows go through LDS in *vector-byte loads from an aligned address. */
+int pseg_binarize_geometry(int* segment, int* band, int* tile, int* vector);
+
+/* pseg_prepare_scans with the binarisation of scan i given by how[i]: equals pseg_prepare_images(scan, where(ink, 0, 255)) with ink
+ * from pseg_binarize_scans, bit for bit.  how == NULL, or window == 0, is pseg_prepare_scans' own path.  With an adaptive entry the
+ * scan-sized ink map is written by the binarisation kernels (into out_orig's staging where asked for, else into workspace), the
+ * statistics pass writes none and the sampler gathers from it; no allocation, read-back or wait enters the front end.  how is
+ * checked for every scan before any device work, as above. */
+int pseg_prepare_scans_bin(int device, int n, const pseg_scan* scans, const pseg_binarize* how, uint8_t* const* out_img,
+                           uint8_t* const* out_bin, uint8_t* const* out_orig);
+/* pseg_predict_chain_scans_png with the binarisation of scan i given by how[i] (NULL, or window == 0: that call's own path): the
+ * ink map that the vote, the masks and the final_is_scan route work on is the adaptive one.  The ink plane (where the scan-sized
+ * map is not the unit's binarisation itself) and the row sums are part of the filtered-plane staging, sized up front. */
+int pseg_predict_chain_scans_bin_png(pseg_engine* e, int n_scans, const pseg_scan* scans, const pseg_binarize* how,
+                                     const int* post_ops, int n_post, unsigned flags,
+                                     const uint8_t* lut, int n_lut, int level, unsigned want, int unit_cap,
+                                     pseg_chain_sink sink, void* user);
+
 #ifdef __cplusplus
 }
 #endif

@@ -448,11 +448,23 @@ int png_pages_enqueue_mixed(const PngPagesMixed& L, const MixedPage* h_tab, cons
 // (SCAN_REC_WORDS zeroed words) is the scan's record, d_w its weights on the device, d_img / d_bin the (H,W) outputs, d_orig the
 // scan-sized ink map; d_bin and d_orig may be NULL.  d_scan, d_work and d_orig are 16-byte aligned.
 constexpr int SCAN_REC_WORDS = 16;
+// how: the scan's binarisation (NULL or window 0: ink = scan <= 127).  With an adaptive one the workspace grows by the row-sum plane
+// and -- unless final_is_scan, where d_orig is the destination -- the scan-sized ink plane, both behind the filtered planes; the
+// binarisation kernels write the ink map and the sampler gathers from it.  d_scan is readable up to the next multiple of 16 bytes.
 int scan_front_check(const pseg_scan& s, int index);
 size_t scan_front_weights(const pseg_scan& s, double* dst);
-size_t scan_front_work(const pseg_scan& s);
+size_t scan_front_work(const pseg_scan& s, const pseg_binarize* how = nullptr);
 int scan_front_enqueue(const pseg_scan& s, const uint8_t* d_scan, const double* d_w, uint8_t* d_work, unsigned* d_rec, uint8_t* d_img,
-                       uint8_t* d_bin, uint8_t* d_orig, hipStream_t st);
+                       uint8_t* d_bin, uint8_t* d_orig, hipStream_t st, const pseg_binarize* how = nullptr);
+// pseg_binarize.hip: binarize_check refuses a bad pseg_binarize ("scan <index>: ..."); binarize_rows_bytes is the row-sum plane of an
+// H x W scan (a multiple of 256); binarize_enqueue launches the two kernels of one scan on `st` without a wait: d_scan 16-byte
+// aligned and readable up to the next multiple of 16 bytes, d_rows 16-byte aligned, d_ink H x W, d_thr float64 H x W or NULL.
+int binarize_check(const pseg_binarize& b, int index);
+size_t binarize_rows_bytes(int H, int W);
+int binarize_enqueue(const uint8_t* d_scan, int H, int W, const pseg_binarize& how, uint8_t* d_rows, uint8_t* d_ink, double* d_thr, hipStream_t st);
+void binarize_release_workspace(int dev);   // the list entry's per-device workspace (pseg_release_workspace)
+// the entry of a list that asks for an adaptive binarisation, or NULL
+inline const pseg_binarize* binarize_of(const pseg_binarize* how, int i) { return how && how[i].window != 0 ? &how[i] : nullptr; }
 // pseg_engine.hip, shared by pseg_predict_batch and the page chain
 void plan_units(int n, const int* H, const int* W, const int* Ho, const int* Wo, int cap, std::vector<int>& ub, std::vector<int>& ug);
 int fit_unit_slots(Engine& e, int H, int W, int want);              // page slots a unit of `want` pages of this shape gets (1: no page units)

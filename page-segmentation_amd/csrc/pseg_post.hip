@@ -1099,6 +1099,7 @@ int pseg_release_workspace(int device) {
     char_heights_release_workspace(device);
     pngdec_release_workspace(device);
     eval_pages_release_workspace(device);
+    binarize_release_workspace(device);
     return release_workspace(device);
 }
 

@@ -1188,7 +1188,9 @@ __global__ __launch_bounds__(256) void scan_select_kernel(const uint8_t* scan, u
 
 // One thread per page pixel: bicubic_kernel's taps from the (filtered) uint8 plane, the clip to the plane's range (bm: its bitmap),
 // prep_map_kernel<2>'s inversion and conversion; and for the same pixel nearest_kernel's coordinate into the scan, ink = scan <= 127
-// (the gather commutes with the per-pixel map).  bin may be NULL.
+// (the gather commutes with the per-pixel map).  bin may be NULL.  INK: `scan` is the scan-sized ink map (an adaptive binarisation
+// has written it), gathered as it is.
+template <bool INK>
 __global__ __launch_bounds__(256) void scan_sample_kernel(const uint8_t* plane, const uint8_t* scan, int H, int W, uint8_t* img, uint8_t* bin,
                                                           int Ho, int Wo, double fy, double ty, double fx, double tx, const unsigned* bm) {
     const int ox = blockIdx.x * 256 + threadIdx.x, oy = blockIdx.y;
@@ -1215,7 +1217,7 @@ __global__ __launch_bounds__(256) void scan_sample_kernel(const uint8_t* plane, 
     if (bin) {
         const int r = mirror_idx((int)(yr > 0.0 ? yr + 0.5 : yr - 0.5), H);
         const int c = mirror_idx((int)(xc > 0.0 ? xc + 0.5 : xc - 0.5), W);
-        bin[o] = scan[(size_t)r * W + c] <= 127;
+        bin[o] = INK ? scan[(size_t)r * W + c] : (uint8_t)(scan[(size_t)r * W + c] <= 127);
     }
 }
 
@@ -1267,7 +1269,8 @@ size_t scan_front_weights(const pseg_scan& s, double* dst) {
 
 static inline size_t sf_up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
-size_t scan_front_work(const pseg_scan& s) {
+// the filtered planes of a scan
+static size_t scan_filt_work(const pseg_scan& s) {
     double sig[2];
     int rad[2];
     scan_radii(s, sig, rad);
@@ -1276,15 +1279,32 @@ size_t scan_front_work(const pseg_scan& s) {
     return sf_up256((size_t)s.H0 * s.W0) * (!fused && rad[0] > 0 && rad[1] > 0 ? 2 : 1);
 }
 
+// behind them, for an adaptive binarisation: the row-sum plane, then the scan-sized ink plane unless d_orig takes it
+size_t scan_front_work(const pseg_scan& s, const pseg_binarize* how) {
+    size_t b = scan_filt_work(s);
+    if (how && how->window != 0) b += binarize_rows_bytes(s.H0, s.W0) + (s.final_is_scan ? 0 : sf_up256((size_t)s.H0 * s.W0));
+    return b;
+}
+
 int scan_front_enqueue(const pseg_scan& s, const uint8_t* d_scan, const double* d_w, uint8_t* d_work, unsigned* d_rec, uint8_t* d_img,
-                       uint8_t* d_bin, uint8_t* d_orig, hipStream_t st) {
+                       uint8_t* d_bin, uint8_t* d_orig, hipStream_t st, const pseg_binarize* how) {
     const int H0 = s.H0, W0 = s.W0;
     const size_t n0 = (size_t)H0 * W0;
     double sig[2];
     int rad[2];
     scan_radii(s, sig, rad);
     const int sgrid = (int)std::min<size_t>((n0 / 16 + 255) / 256 + 1, 1024);
-    scan_stats_kernel<<<sgrid, 256, 0, st>>>(d_scan, n0, d_rec, d_orig);
+    // an adaptive ink map: into d_orig where that is asked for, else (for the sampler's gather alone) into the workspace
+    const uint8_t* d_ink = nullptr;
+    if (how && how->window != 0 && (d_bin || d_orig)) {
+        if (!d_work) return fail(PSEG_EINVAL, "scan front end: no workspace for the binarisation");
+        uint8_t* const rows = d_work + scan_filt_work(s);
+        uint8_t* const ink = d_orig ? d_orig : rows + binarize_rows_bytes(H0, W0);
+        if (!d_orig && s.final_is_scan) return fail(PSEG_EINVAL, "scan front end: no ink plane in the workspace of a final_is_scan scan");
+        PSEG_TRY(binarize_enqueue(d_scan, H0, W0, *how, rows, ink, nullptr, st));
+        d_ink = ink;
+    }
+    scan_stats_kernel<<<sgrid, 256, 0, st>>>(d_scan, n0, d_rec, d_ink ? nullptr : d_orig);
     const uint8_t* plane = d_scan;
     const unsigned* bm = d_rec;
     if (rad[0] > 0 || rad[1] > 0) {
@@ -1310,7 +1330,8 @@ int scan_front_enqueue(const pseg_scan& s, const uint8_t* d_scan, const double* 
     double fy, ty, fx, tx;
     warp_coeffs(H0, s.H, &fy, &ty);
     warp_coeffs(W0, s.W, &fx, &tx);
-    scan_sample_kernel<<<dim3(cdiv(s.W, 256), s.H), 256, 0, st>>>(plane, d_scan, H0, W0, d_img, d_bin, s.H, s.W, fy, ty, fx, tx, bm);
+    if (d_ink) scan_sample_kernel<true><<<dim3(cdiv(s.W, 256), s.H), 256, 0, st>>>(plane, d_ink, H0, W0, d_img, d_bin, s.H, s.W, fy, ty, fx, tx, bm);
+    else scan_sample_kernel<false><<<dim3(cdiv(s.W, 256), s.H), 256, 0, st>>>(plane, d_scan, H0, W0, d_img, d_bin, s.H, s.W, fy, ty, fx, tx, bm);
     PSEG_HIP(hipGetLastError());
     return PSEG_OK;
 }
@@ -1319,6 +1340,11 @@ int scan_front_enqueue(const pseg_scan& s, const uint8_t* d_scan, const double* 
 
 extern "C" int pseg_prepare_scans(int device, int n, const pseg_scan* scans, uint8_t* const* out_img, uint8_t* const* out_bin,
                                   uint8_t* const* out_orig) {
+    return pseg_prepare_scans_bin(device, n, scans, nullptr, out_img, out_bin, out_orig);
+}
+
+extern "C" int pseg_prepare_scans_bin(int device, int n, const pseg_scan* scans, const pseg_binarize* how, uint8_t* const* out_img,
+                                      uint8_t* const* out_bin, uint8_t* const* out_orig) {
     if (n < 0 || (n > 0 && (!scans || !out_img || !out_bin))) return fail(PSEG_EINVAL, "bad argument");
     // every scan is checked, and the staging laid out, before any device work starts
     struct At { size_t scan, work, w, img; };
@@ -1326,10 +1352,13 @@ extern "C" int pseg_prepare_scans(int device, int n, const pseg_scan* scans, uin
     size_t b_scan = 0, b_work = 0, n_w = 0, b_img = 0;
     for (int i = 0; i < n; ++i) {
         PSEG_TRY(scan_front_check(scans[i], i));
+        if (how) PSEG_TRY(binarize_check(how[i], i));
         if (!out_img[i] || !out_bin[i]) return fail(PSEG_EINVAL, "scan %d: NULL argument", i);
         at[i] = At{b_scan, b_work, n_w, b_img};
         b_scan += sf_up256((size_t)scans[i].H0 * scans[i].W0);
-        b_work += scan_front_work(scans[i]);
+        pseg_scan alone = scans[i];                             // (final_is_scan is the chain's: here the ink plane may have no other home)
+        alone.final_is_scan = 0;
+        b_work += scan_front_work(alone, binarize_of(how, i));
         n_w += scan_front_weights(scans[i], nullptr);
         b_img += sf_up256((size_t)scans[i].H * scans[i].W);
     }
@@ -1353,12 +1382,13 @@ extern "C" int pseg_prepare_scans(int device, int n, const pseg_scan* scans, uin
     if (n_w) PSEG_HIP(hipMemcpyAsync(d_w, h_w.data(), n_w * 8, hipMemcpyHostToDevice, st));
     PSEG_HIP(hipMemsetAsync(d_rec, 0, (size_t)n * SCAN_REC_WORDS * sizeof(unsigned), st));
     for (int i = 0; i < n; ++i) {
-        const pseg_scan& s = scans[i];
+        pseg_scan s = scans[i];
+        s.final_is_scan = 0;
         const size_t n0 = (size_t)s.H0 * s.W0, n1 = (size_t)s.H * s.W;
         uint8_t* const orig = out_orig && out_orig[i] ? d_orig + at[i].scan : nullptr;
         PSEG_HIP(hipMemcpyAsync(d_scan + at[i].scan, s.gray, n0, hipMemcpyHostToDevice, st));
         PSEG_TRY(scan_front_enqueue(s, d_scan + at[i].scan, d_w + at[i].w, d_work + at[i].work, d_rec + (size_t)i * SCAN_REC_WORDS,
-                                    d_img + at[i].img, d_bin + at[i].img, orig, st));
+                                    d_img + at[i].img, d_bin + at[i].img, orig, st, binarize_of(how, i)));
         PSEG_HIP(hipMemcpyAsync(out_img[i], d_img + at[i].img, n1, hipMemcpyDeviceToHost, st));
         PSEG_HIP(hipMemcpyAsync(out_bin[i], d_bin + at[i].img, n1, hipMemcpyDeviceToHost, st));
         if (orig) PSEG_HIP(hipMemcpyAsync(out_orig[i], orig, n0, hipMemcpyDeviceToHost, st));

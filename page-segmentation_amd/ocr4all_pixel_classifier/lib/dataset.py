@@ -81,19 +81,45 @@ def _imread_bin(path):
     return np.where(g > 127, 255, 0).astype(np.uint8)
 
 
+def check_binarize(binarize):
+    """binarize=None (the reference's > 127) or a pseg_amd.Sauvola; anything else raises."""
+    from pseg_amd import engine as _eng
+    if binarize is not None and not isinstance(binarize, _eng.Sauvola):
+        raise Exception(f"binarize must be None or a pseg_amd.Sauvola, got {binarize!r}")
+    return binarize
+
+
+def _binarize_gray(gray, binarize, line_height_px):
+    """The 0 / 255 map (paper = 255) of a gray scan under an adaptive threshold: where(ink, 0, 255) of pseg_amd.binarize_scans, a
+    window=None resolved from the entry's line height."""
+    from pseg_amd import engine as _eng
+    ink = _eng.binarize_scans([gray], binarize.resolved(line_height_px))[0]
+    return np.where(ink != 0, 0, 255).astype(np.uint8)
+
+
 class DatasetLoader:
-    def __init__(self, target_line_height, color_map: ColorMap, prediction=False, max_width=None):
+    def __init__(self, target_line_height, color_map: ColorMap, prediction=False, max_width=None, binarize=None):
         self.target_line_height = target_line_height
         self.prediction = prediction
         self.color_map = color_map
         self.max_width = max_width
+        self.binarize = check_binarize(binarize)    # None: > 127 (imread_bin); a pseg_amd.Sauvola: the adaptive ink map on the device
 
     def load_images(self, entry: SingleData) -> SingleData:
         """lib/dataset.py:160-191.  The reference derives the binary from the *image* attribute /
-        path (attr 'image', :172) and never reads binary_path; kept."""
+        path (attr 'image', :172) and never reads binary_path; kept.  With a binarize, the adaptive map of the gray scan takes
+        _imread_bin's place: the records carry the ink map the scan chain works on."""
+        return self._load_images(entry, self.binarize)
+
+    def _load_images(self, entry: SingleData, binarize) -> SingleData:
         img = entry.image if entry.image is not None else _imread_gray(entry.image_path)
         original_shape = img.shape
-        bin_ = entry.image if entry.image is not None else _imread_bin(entry.image_path)
+        if entry.image is not None:
+            bin_ = entry.image
+        elif binarize is not None:
+            bin_ = _binarize_gray(img, binarize, entry.line_height_px)
+        else:
+            bin_ = _imread_bin(entry.image_path)
         img, bin_, orig_bin = prepare_images(img, bin_, self.target_line_height, entry.line_height_px,
                                              self.max_width, keep_orig_bin=True)
         if not self.prediction:

@@ -269,7 +269,7 @@ class Predictor:
         return (entry.image is None and entry.image_path is not None and output.DEVICE_PNG and output.is_png_target(path)
                 and self._chain_ops() is not None and net.n_classes <= 256 and not getattr(net, "_rgb", False))
 
-    def write_masks_scans(self, entries, loader, output_dir=None, level=None, chunk_pages=64, decode_threads=2, decode="host"):
+    def write_masks_scans(self, entries, loader, output_dir=None, level=None, chunk_pages=64, decode_threads=2, decode="host", binarize=None):
         """loader.load_images + write_masks_dataset for entries that name their scan by image_path, without the normalised page, the
         binarisation or the label map visiting the host: the decoded gray scans go through Engine.predict_chain_scans chunk_pages at
         a time (binarisation and line-height normalisation on the device, then the page chain), and each PNG stream is written to
@@ -290,9 +290,15 @@ class Predictor:
         (engine.png_decode_gray, 8-bit gray and RGB PNG files) -- on the decoder's own stream and workspace, while the calling
         thread runs the chain of the chunk before.  A file the decoder does not take or refuses is read with
         dataset._imread_gray, as under "host": its array, or its exception when the entry is reached, is PIL's.  Same files and
-        bytes as decode="host"."""
+        bytes as decode="host".
+        binarize: None (ink = scan <= 127) or a pseg_amd.Sauvola: the adaptive ink map, made on the device inside the chain, is what
+        the vote and the masks work on -- the files of DatasetLoader(binarize=...).load_images + write_masks_dataset.  A window=None
+        takes pseg_amd.sauvola_window of the entry's line height, the measured one for entries measured here; the fallback route
+        loads the entry with the same binarisation."""
         if decode not in ("host", "device"):
             raise Exception(f"decode must be 'host' or 'device', got {decode!r}")
+        from .dataset import check_binarize
+        check_binarize(binarize)
         from concurrent.futures import ThreadPoolExecutor
         from pseg_amd import engine as _eng
         from . import dataset as _ds
@@ -376,13 +382,16 @@ class Predictor:
                     def to_file(page, name, stream, paths=paths, on_device=on_device):
                         with open(paths[on_device[page]][names.index(name)], "wb") as f:
                             f.write(stream)
+                    # (the keyword goes only with a binarisation: today's call is unchanged)
+                    how = {} if binarize is None else {"binarize": [binarize.resolved(chunk[k].line_height_px) for k in on_device]}
                     self.network.model.predict_chain_scans(
                         [scans[k][0] for k in on_device], [scans[k][1] for k in on_device], high_res=high_res,
                         post_ops=self._chain_ops(), exact_labels=self.network.exact == "labels", lut=self.settings.color_map.lut(),
-                        which=names, png_level=level, sink=to_file)
+                        which=names, png_level=level, sink=to_file, **how)
                 for k in range(stop):
                     if scans[k] is None:
-                        self.write_masks(loader.load_images(chunk[k]), output_dir=output_dir, level=level)
+                        loaded = loader.load_images(chunk[k]) if binarize is None else loader._load_images(chunk[k], binarize)
+                        self.write_masks(loaded, output_dir=output_dir, level=level)
                     yield paths[k]
                 if failed is not None:
                     raise failed[1]

@@ -6,5 +6,6 @@ from .engine import (  # noqa: F401
     ARCH_IDS, MODE_F32_EXACT, MODE_BF16, EXPORTED_SYMBOLS, eval_confusion, cc_label, cc_tables, eval_pages, eval_page_groups, eval_rule, pinned_empty, pinned_empty_pooled, pinned_copy,
     png_encode, masks_png, png_bound, png_code_lengths, tile_plan,
     png_probe, png_decode_gray, PNG_OK, PNG_EINVAL, PNG_EUNSUPPORTED,
+    Sauvola, sauvola_window, binarize_scans,
 )
 from .build import build_library  # noqa: F401

@@ -32,6 +32,7 @@ EXPORTED_SYMBOLS = (
     "pseg_png_bound_lv", "pseg_png_encode_device_lv", "pseg_masks_png_device_u8_lv", "pseg_png_encode_lv", "pseg_masks_png_lv",
     "pseg_predict_chain_png_lv", "pseg_png_code_lengths", "pseg_predict_chain_pages_png", "pseg_chain_units",
     "pseg_predict_chain_pages_mixed_png", "pseg_chain_units_mixed", "pseg_predict_chain_scans_png", "pseg_prepare_scans",
+    "pseg_binarize_scans", "pseg_binarize_scans_host", "pseg_binarize_geometry", "pseg_prepare_scans_bin", "pseg_predict_chain_scans_bin_png",
     "pseg_rescale_shape", "pseg_gaussian_kernel", "pseg_resize_nearest", "pseg_resize_nearest_device", "pseg_scale_image",
     "pseg_prepare_images", "pseg_affine_warp", "pseg_affine_warp_fill", "pseg_brightness_shift",
     "pseg_eval_confusion", "pseg_cc_label", "pseg_cc_tables", "pseg_eval_pages", "pseg_eval_page_groups",
@@ -50,6 +51,11 @@ class SCAN(ctypes.Structure):
     """pseg_scan: one gray scan and the page it becomes (pseg_prepare_scans, pseg_predict_chain_scans_png)."""
     _fields_ = [("gray", ctypes.c_void_p), ("H0", ctypes.c_int), ("W0", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int),
                 ("wy", ctypes.c_void_p), ("ry", ctypes.c_int), ("wx", ctypes.c_void_p), ("rx", ctypes.c_int), ("final_is_scan", ctypes.c_int)]
+
+
+class BINARIZE(ctypes.Structure):
+    """pseg_binarize: how a scan becomes its ink map (window 0: scan <= 127; else Sauvola over an odd window)."""
+    _fields_ = [("window", ctypes.c_int), ("k", ctypes.c_double), ("R", ctypes.c_double)]
 
 
 class EVAL_PAGE(ctypes.Structure):
@@ -190,6 +196,11 @@ def lib():
     L.pseg_chain_units_mixed.argtypes = [i, vp, vp, i, vp, vp, vp, i]
     L.pseg_prepare_scans.argtypes = [i, i, c.POINTER(SCAN), vp, vp, vp]
     L.pseg_predict_chain_scans_png.argtypes = [vp, i, c.POINTER(SCAN), c.POINTER(i), i, c.c_uint, vp, i, i, c.c_uint, i, CHAIN_SINK, vp]
+    L.pseg_binarize_scans.argtypes = [i, i, vp, vp, vp, c.POINTER(BINARIZE), vp, vp]
+    L.pseg_binarize_scans_host.argtypes = [i, vp, vp, vp, c.POINTER(BINARIZE), vp, vp]
+    L.pseg_binarize_geometry.argtypes = [c.POINTER(i)] * 4
+    L.pseg_prepare_scans_bin.argtypes = [i, i, c.POINTER(SCAN), c.POINTER(BINARIZE), vp, vp, vp]
+    L.pseg_predict_chain_scans_bin_png.argtypes = [vp, i, c.POINTER(SCAN), c.POINTER(BINARIZE), c.POINTER(i), i, c.c_uint, vp, i, i, c.c_uint, i, CHAIN_SINK, vp]
     L.pseg_tile_plan.argtypes = [i, i, i, i, c.POINTER(i), c.POINTER(i), vp, vp, vp, i]
     L.pseg_predict_tiled_device.argtypes = [vp, vp, i, i, i, vp, vp, vp]
     L.pseg_predict_tiled.argtypes = [vp, vp, i, i, i, vp, vp]
@@ -606,23 +617,26 @@ class Engine:
         return collected
 
     def predict_chain_scans(self, scans, scales, high_res=False, post_ops=(), exact_labels=False, lut=None,
-                            which=("color", "overlay", "inverted"), labels=False, png_level=0, unit_cap=0, sink=None):
+                            which=("color", "overlay", "inverted"), labels=False, png_level=0, unit_cap=0, sink=None, binarize=None):
         """Scans as they come off disk through the chain to PNG streams (pseg_predict_chain_scans_png): scans[i] a gray uint8 (H0,W0)
         array, scales[i] = target_line_height / line_height_px.  The binarisation (ink = scan <= 127) and the line-height
         normalisation run on the device in front of the network: neither the normalised page nor the ink map visits the host.
         Every stream and label map equals predict_chain_pages(mixed=True) fed with prepare_images(scan, where(scan > 127, 255, 0),
         scale): the page, `bin` as the binarisation -- with high_res the label map is rescaled to the scan's shape and `orig` is the
         binarisation (PredictSettings.high_res_output).  Keywords, result dicts and the sink contract are predict_chain_pages'
-        (mixed=True: a callable sink sees the planner's order)."""
+        (mixed=True: a callable sink sees the planner's order).
+        binarize: None (ink = scan <= 127), a Sauvola with a window, or one of either per scan (binarize_table): the ink map of
+        binarize_scans takes the place of scan <= 127 everywhere (pseg_predict_chain_scans_bin_png)."""
         for w in which:
             if w not in MASK_NAMES:
                 raise PsegError("unknown mask %r (one of %r)" % (w, MASK_NAMES))
         table, keep, plans = scan_table(scans, scales, high_res)
         n = len(plans)
+        how = None if binarize is None else binarize_table(binarize, n)
         final = [keep[k].shape if high_res else plans[k][:2] for k in range(n)]
         return self._chain_list(final, post_ops, lut, which, labels, sink,
-                                lambda ops, t, want, cb: lib().pseg_predict_chain_scans_png(
-                                    self._h, n, table, ops, len(post_ops), 1 if exact_labels else 0, _ptr(t), 0 if t is None else t.shape[0],
+                                lambda ops, t, want, cb: lib().pseg_predict_chain_scans_bin_png(
+                                    self._h, n, table, how, ops, len(post_ops), 1 if exact_labels else 0, _ptr(t), 0 if t is None else t.shape[0],
                                     int(png_level), want, int(unit_cap), cb, None))
 
     def predict_batch(self, images, dtype=np.int64, out=None):
@@ -1151,15 +1165,108 @@ def scan_table(scans, scales, high_res=False):
     return table, arrs, plans
 
 
-def prepare_scans(scans, scales, device=0):
+def prepare_scans(scans, scales, device=0, binarize=None):
     """prepare_images(scan, where(scan > 127, 255, 0), scale) for a list of gray scans in one call of the scan chain's front end
-    (pseg_prepare_scans) -> [(img uint8, bin uint8, orig_bin uint8)], bit for bit."""
+    (pseg_prepare_scans) -> [(img uint8, bin uint8, orig_bin uint8)], bit for bit.  binarize: None, a Sauvola with a window, or one of
+    either per scan (binarize_table): prepare_images(scan, where(ink, 0, 255), scale) with ink from binarize_scans
+    (pseg_prepare_scans_bin)."""
     table, arrs, plans = scan_table(scans, scales)
     n = len(arrs)
+    how = None if binarize is None else binarize_table(binarize, n)
     out = [(np.empty(p[:2], np.uint8), np.empty(p[:2], np.uint8), np.empty(a.shape, np.uint8)) for a, p in zip(arrs, plans)]
     P = ctypes.c_void_p * max(n, 1)
-    _check(lib().pseg_prepare_scans(int(device), n, table, *[P(*[o[k].ctypes.data for o in out]) for k in range(3)]))
+    _check(lib().pseg_prepare_scans_bin(int(device), n, table, how, *[P(*[o[k].ctypes.data for o in out]) for k in range(3)]))
     return out
+
+
+# ---- adaptive binarisation (pseg_binarize_scans) ------------------------------------------------------
+
+def sauvola_window(line_height_px):
+    """The window Sauvola(window=None) takes for a scan of this line height: two line heights and the centre pixel, at most 255.
+    Host arithmetic."""
+    if line_height_px is None or not np.isfinite(line_height_px) or line_height_px <= 0:
+        raise PsegError("sauvola_window needs a positive line height, got %r" % (line_height_px,))
+    return min(255, 2 * max(1, int(round(line_height_px))) + 1)
+
+
+class Sauvola:
+    """Sauvola's adaptive threshold over a square window of odd side `window` (3 .. 255): T = m (1 + k (s / R - 1)) from the
+    window's mean m and standard deviation s, ink = value <= T (include/pseg.h, pseg_binarize).  window=None: sauvola_window of the
+    scan's line height, for the callers that know it (resolved)."""
+
+    def __init__(self, window=None, k=0.2, R=128.0):
+        if window is not None:
+            if isinstance(window, bool) or int(window) != window:
+                raise PsegError("Sauvola: window must be an odd integer in 3..255 or None, got %r" % (window,))
+            window = int(window)
+            if window < 3 or window > 255 or window % 2 == 0:
+                raise PsegError("Sauvola: window must be an odd integer in 3..255 or None, got %r" % (window,))
+        k, R = float(k), float(R)
+        if not 0.0 <= k <= 1.0:
+            raise PsegError("Sauvola: k must lie in [0, 1], got %r" % (k,))
+        if not (R > 0.0 and np.isfinite(R)):
+            raise PsegError("Sauvola: R must be a positive number, got %r" % (R,))
+        self.window, self.k, self.R = window, k, R
+
+    def resolved(self, line_height_px):
+        """This threshold with its window fixed for a scan of the given line height."""
+        return self if self.window is not None else Sauvola(sauvola_window(line_height_px), self.k, self.R)
+
+    def __repr__(self):
+        return "Sauvola(window=%r, k=%r, R=%r)" % (self.window, self.k, self.R)
+
+    def __eq__(self, other):
+        return isinstance(other, Sauvola) and (self.window, self.k, self.R) == (other.window, other.k, other.R)
+
+    def __hash__(self):
+        return hash((self.window, self.k, self.R))
+
+
+def binarize_geometry():
+    """(segment, band, tile, vector) of pseg_binarize_scans' kernels (pseg_binarize_geometry; no device)."""
+    v = [ctypes.c_int() for _ in range(4)]
+    _check(lib().pseg_binarize_geometry(*[ctypes.byref(x) for x in v]))
+    return tuple(x.value for x in v)
+
+
+def binarize_table(how, n):
+    """The pseg_binarize array of n scans: how is a Sauvola for all of them, or a sequence with a Sauvola or None (the fixed
+    threshold, ink = scan <= 127) per scan.  Every Sauvola must have its window (Sauvola.resolved)."""
+    entries = [how] * n if how is None or isinstance(how, Sauvola) else list(how)
+    if len(entries) != n:
+        raise PsegError("binarize must have one entry per scan (%d for %d scans)" % (len(entries), n))
+    table = (BINARIZE * max(n, 1))()
+    for k, b in enumerate(entries):
+        if b is None:
+            table[k] = BINARIZE(0, 0.0, 0.0)
+            continue
+        if not isinstance(b, Sauvola):
+            raise PsegError("scan %d: binarize takes None or a Sauvola, got %r" % (k, b))
+        if b.window is None:
+            raise PsegError("scan %d: Sauvola(window=None) needs the scan's line height: pass Sauvola.resolved(line_height_px)" % k)
+        table[k] = BINARIZE(b.window, b.k, b.R)
+    return table
+
+
+def binarize_scans(scans, how, device=0, thresholds=False, host=False):
+    """The ink maps (uint8, ink = 1) of a list of gray scans in one device-resident call (pseg_binarize_scans): how is a Sauvola or
+    one per scan (None: ink = scan <= 127), see binarize_table.  thresholds=True: -> [(ink, T)] with the float64 threshold of
+    every pixel.  host=True: the same bits from the host entry (pseg_binarize_scans_host), no device."""
+    gs = [np.ascontiguousarray(g, dtype=np.uint8) for g in scans]
+    for k, g in enumerate(gs):
+        if g.ndim != 2:
+            raise PsegError("scan %d: an (H,W) gray array is expected, got shape %r" % (k, g.shape))
+    n = len(gs)
+    table = binarize_table(how, n)
+    if n == 0:
+        return []
+    P, I = ctypes.c_void_p * n, ctypes.c_int * n
+    inks = [np.empty(g.shape, np.uint8) for g in gs]
+    thr = [np.empty(g.shape, np.float64) for g in gs] if thresholds else None
+    args = (n, P(*[g.ctypes.data for g in gs]), I(*[g.shape[0] for g in gs]), I(*[g.shape[1] for g in gs]), table,
+            P(*[a.ctypes.data for a in inks]), None if thr is None else P(*[a.ctypes.data for a in thr]))
+    _check(lib().pseg_binarize_scans_host(*args) if host else lib().pseg_binarize_scans(int(device), *args))
+    return list(zip(inks, thr)) if thresholds else inks
 
 
 FILL_MODES = {"nearest": 0, "constant": 1, "reflect": 2, "wrap": 3}
