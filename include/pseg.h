@@ -803,6 +803,45 @@ int pseg_predict_chain_scans_bin_png(pseg_engine* e, int n_scans, const pseg_sca
                                      const uint8_t* lut, int n_lut, int level, unsigned want, int unit_cap,
                                      pseg_chain_sink sink, void* user);
 
+/* ---- Training masks as label maps on the device ---------------------------------------------------------- */
+
+/* One ground-truth mask as it was decoded: px is H0 x W0 x channels bytes, dense.  channels == 3: RGB, a colour table turns a pixel
+ * into its label id; channels == 1: the bytes are label ids already. */
+typedef struct pseg_mask_src {
+    const uint8_t* px;
+    int H0, W0, channels;
+} pseg_mask_src;
+
+/* The label maps of n masks at the shapes of their pages, in one device-resident call: out_labels[i] is uint8 H[i] x W[i], dense.
+ * Output pixel (r, c) reads source pixel (sr, sc), the coordinate of pseg_resize_nearest: per axis f = n_in / n_out,
+ * v = f * o + (f * 0.5 - 0.5) in float64, rounded half away from zero, mirrored without an edge repeat.  Its label is, for an RGB
+ * source, the id of the table entry whose colour equals the pixel's three bytes, and 0 where none does (an unknown colour); for a
+ * 1-channel source the byte itself.  The table: n_colors entries, 0 .. 256, colors n_colors x 3 bytes and ids n_colors bytes; a
+ * colour mapped to id 0 is a known colour; n_colors == 0 is legal (every RGB pixel is unknown; colors and ids may be NULL then, and
+ * for a list of 1-channel masks).  This is the label map of "colours to ids on the whole mask, then pseg_resize_nearest", byte for
+ * byte: the lookup is pointwise and the gather moves whole pixels, so the two commute and only the sampled pixels are looked up.
+ * out_counts (may be NULL): n x 257 int64; [i][k], k < 256: the output pixels of mask i that received id k; [i][256]: its output
+ * pixels of unknown colour (they are counted under id 0 as well).
+ * Host pointers, synchronous.  The list is cut into groups as pseg_char_heights and pseg_binarize_scans cut theirs (64 masks, or 64
+ * MiB of source bytes; a single larger mask is a group of its own); a group costs ONE ragged launch and ONE host wait, nothing is
+ * allocated per mask.  The workspace (per source pixel its 3 or 1 bytes, per output pixel 1 byte, the tables and 257 64-bit
+ * counters per mask of a group) is grow-only, cached per device and freed by pseg_release_workspace.
+ * n == 0 returns PSEG_OK before a device is touched.  Every mask is checked before any device work and the message names it
+ * ("mask 3: ..."): a NULL pointer, an empty source or output shape, channels other than 1 or 3, n_colors outside 0 .. 256, a
+ * duplicate colour, or an RGB mask with n_colors > 0 and a NULL table is PSEG_EINVAL; nothing is written to any output then. */
+int pseg_label_masks(int device, int n, const pseg_mask_src* masks, const int* H, const int* W,
+                     const uint8_t* colors, const uint8_t* ids, int n_colors, uint8_t* const* out_labels, int64_t* out_counts);
+/* The same on the host, without a device: the same coordinate and lookup functions, the same bytes and counts. */
+int pseg_label_masks_host(int n, const pseg_mask_src* masks, const int* H, const int* W,
+                          const uint8_t* colors, const uint8_t* ids, int n_colors, uint8_t* const* out_labels, int64_t* out_counts);
+
+/* The geometry the device kernel was compiled with and the group cut (host arithmetic, no device; every pointer may be NULL): a
+ * thread owns *run consecutive output pixels of a row, written with one *run-byte store where the run is whole; a workgroup owns
+ * *runs runs of each of *rows rows; a group ends after *group_masks masks or before *group_bytes source bytes are passed. */
+int pseg_label_masks_geometry(int* run, int* runs, int* rows, int* group_masks, int64_t* group_bytes);
+/* group_of[i]: the group pseg_label_masks puts mask i into (only H0, W0 and channels are read; host arithmetic, no device). */
+int pseg_label_masks_groups(int n, const pseg_mask_src* masks, int* group_of);
+
 #ifdef __cplusplus
 }
 #endif

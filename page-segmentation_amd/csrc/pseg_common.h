@@ -463,6 +463,7 @@ int binarize_check(const pseg_binarize& b, int index);
 size_t binarize_rows_bytes(int H, int W);
 int binarize_enqueue(const uint8_t* d_scan, int H, int W, const pseg_binarize& how, uint8_t* d_rows, uint8_t* d_ink, double* d_thr, hipStream_t st);
 void binarize_release_workspace(int dev);   // the list entry's per-device workspace (pseg_release_workspace)
+void label_masks_release_workspace(int dev);   // pseg_labelmasks.hip: pseg_label_masks' per-device workspace (pseg_release_workspace)
 // the entry of a list that asks for an adaptive binarisation, or NULL
 inline const pseg_binarize* binarize_of(const pseg_binarize* how, int i) { return how && how[i].window != 0 ? &how[i] : nullptr; }
 // pseg_engine.hip, shared by pseg_predict_batch and the page chain

@@ -1100,6 +1100,7 @@ int pseg_release_workspace(int device) {
     pngdec_release_workspace(device);
     eval_pages_release_workspace(device);
     binarize_release_workspace(device);
+    label_masks_release_workspace(device);
     return release_workspace(device);
 }
 

@@ -30,6 +30,18 @@ class ColorMap:
             t[lid] = rgb
         return t
 
+    def table(self):
+        """(colors (n,3) uint8, ids (n,) uint8) in mapping order: the table of pseg_amd.label_masks.  A label id above 255 does not
+        fit a uint8 label map and raises."""
+        for rgb, (lid, name) in self.mapping.items():
+            if not 0 <= lid <= 255:
+                raise Exception(f"ColorMap.table: label id {lid} of {rgb} ({name}) does not fit a uint8 label map")
+            if not all(0 <= t <= 255 for t in rgb) or len(rgb) != 3:
+                raise Exception(f"ColorMap.table: {rgb} ({name}) is not an 8-bit RGB colour")
+        colors = np.array([rgb for rgb in self.mapping], dtype=np.uint8).reshape(-1, 3)
+        ids = np.array([v[0] for v in self.mapping.values()], dtype=np.uint8)
+        return colors, ids
+
     def to_rgb_array(self, labels):
         from pseg_amd import engine
         lab = np.ascontiguousarray(labels, dtype=np.int64)

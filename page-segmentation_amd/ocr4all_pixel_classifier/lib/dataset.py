@@ -6,12 +6,15 @@ callers build them positionally and from the dataset JSON ({"train": [...], "tes
 Records stay picklable: no GPU handles live in them.
 """
 import json
+import logging
 from dataclasses import dataclass
 from typing import Any, List, Optional, Tuple
 
 import numpy as np
 
 from .colors import ColorMap
+
+_log = logging.getLogger(__name__)
 
 
 @dataclass
@@ -81,6 +84,17 @@ def _imread_bin(path):
     return np.where(g > 127, 255, 0).astype(np.uint8)
 
 
+def _imread_scan(path):
+    """_imread_gray as the contiguous uint8 array the list entries take (load_data_list's pool threads)."""
+    return np.ascontiguousarray(_imread_gray(path), dtype=np.uint8)
+
+
+def _imread_rgb(path):
+    """A mask file as ColorMap.imread_labels reads it, before the lookup: (H,W,3) uint8 (RGB, palette and RGBA files alike)."""
+    from PIL import Image
+    return np.ascontiguousarray(np.asarray(Image.open(path).convert("RGB")), dtype=np.uint8)
+
+
 def check_binarize(binarize):
     """binarize=None (the reference's > 127) or a pseg_amd.Sauvola; anything else raises."""
     from pseg_amd import engine as _eng
@@ -137,8 +151,124 @@ class DatasetLoader:
     def load_data(self, all_dataset_files) -> Dataset:
         return Dataset([self.load_images(d) for d in all_dataset_files], self.color_map)
 
-    def load_data_from_json(self, files, type) -> Dataset:
-        """lib/dataset.py:200-208."""
+    def _list_candidate(self, entry: SingleData):
+        """Whether load_data_list may take this entry, as far as that shows before a file is read: the scan comes from image_path
+        (a pre-loaded image is its own binary in load_images, a quirk that stays there), and the mask from mask_path or from a
+        pre-loaded (H,W) array of uint8 / bool label ids."""
+        if entry.image is not None or entry.image_path is None:
+            return False
+        if self.prediction:
+            return True
+        if entry.mask is None:
+            return entry.mask_path is not None
+        m = np.asarray(entry.mask)
+        return m.ndim == 2 and m.dtype in (np.uint8, np.bool_)
+
+    def load_data_list(self, entries, chunk=64, decode_threads=2, report=None) -> Dataset:
+        """load_data for entries that name their files, as lists on the device: the records of load_data field by field (image,
+        binary, orig_binary, mask, original_shape, dtypes included), the entries modified in place as load_images modifies them.
+        Per chunk of `chunk` entries: every scan is decoded ONCE (_imread_gray) and every mask file with PIL's convert("RGB"), by
+        decode_threads pool threads that work on the next chunk while the device works on this one; ONE engine.prepare_scans call
+        gives page, ink map and scan-sized ink map (self.binarize as in load_images, a window=None resolved from the entry's line
+        height); ONE engine.label_masks call turns the decoded masks into label maps of the pages' shapes (skipped under
+        self.prediction).  A pre-loaded entry.mask of uint8 / bool ids stays on this route as a 1-channel source.
+        An entry whose line_height_px is None is measured in one engine.char_heights call over the chunk's decoded scans and the
+        height is stored into the entry (Predictor.write_masks_scans does the same); a scan without a measurable height raises
+        naming the file.  Entries this route cannot take go through self.load_images, in place and in order: a pre-loaded
+        entry.image, a pre-loaded mask of another kind, an entry without the paths, and a max_width that brings the second stage
+        (which shows only once the scan's shape is known).  A file that cannot be decoded raises when its entry is reached; the
+        entries in front of it are loaded.
+        report: a list that receives one item per entry, {"label_counts": int64[256] pixels per label id, "unknown": int pixels of
+        a colour the colour map does not know (they became label 0)}, or None for a fallback or prediction entry.  Every mask with
+        unknown > 0 is logged as one warning with its file name and the count."""
+        from concurrent.futures import ThreadPoolExecutor
+        from pseg_amd import engine as _eng
+        entries = list(entries)
+        step = max(1, int(chunk))
+        colors, ids = (None, None) if self.prediction else self.color_map.table()
+
+        with ThreadPoolExecutor(max(1, int(decode_threads))) as pool:
+            def start(i):
+                """Chunk i and the decodes of its candidates, in flight: (scan, mask file or None) per entry, or None."""
+                part = entries[i:i + step]
+                jobs = []
+                for e in part:
+                    if not self._list_candidate(e):
+                        jobs.append(None)
+                        continue
+                    from_file = not self.prediction and e.mask is None
+                    jobs.append((pool.submit(_imread_scan, e.image_path), pool.submit(_imread_rgb, e.mask_path) if from_file else None))
+                return part, jobs
+
+            ahead = start(0) if entries else None
+            for i in range(0, len(entries), step):
+                part, jobs = ahead
+                ahead = start(i + step) if i + step < len(entries) else None
+                scans, masks, failed = [None] * len(part), [None] * len(part), None
+                for k, job in enumerate(jobs):
+                    if job is None:
+                        continue
+                    try:
+                        scans[k] = job[0].result()
+                        masks[k] = job[1].result() if job[1] is not None else None
+                    except BaseException as exc:
+                        scans[k], failed = None, (k, exc)
+                        break
+                stop = len(part) if failed is None else failed[0]
+                # the entries without a line height: one device call over the chunk's decoded scans
+                unmeasured = [k for k in range(stop) if scans[k] is not None and part[k].line_height_px is None]
+                if unmeasured:
+                    for k, h in zip(unmeasured, _eng.char_heights([scans[k] for k in unmeasured], inverse=False)[0]):
+                        if h is None:
+                            if failed is None or k < failed[0]:
+                                failed = (k, Exception(f"No line height could be measured in {part[k].image_path}"))
+                        else:
+                            part[k].line_height_px = h
+                    stop = len(part) if failed is None else failed[0]
+                on_device = []
+                for k in range(stop):
+                    if scans[k] is None:
+                        continue
+                    scale = self.target_line_height / part[k].line_height_px
+                    # (the max_width stage shows only once the scan's shape is known)
+                    if self.max_width is None or self.max_width / _eng.rescale_shape(scans[k].shape, scale)[1] >= 1.0:
+                        on_device.append((k, scale))
+                loaded = {}
+                if on_device:
+                    # (the keyword goes only with a binarisation, as in write_masks_scans)
+                    how = {} if self.binarize is None else {"binarize": [self.binarize.resolved(part[k].line_height_px) for k, _ in on_device]}
+                    pages = _eng.prepare_scans([scans[k] for k, _ in on_device], [sc for _, sc in on_device], **how)
+                    labels = [None] * len(on_device)
+                    if not self.prediction:
+                        src = [masks[k] if masks[k] is not None else np.ascontiguousarray(part[k].mask).view(np.uint8) for k, _ in on_device]
+                        labels = _eng.label_masks(src, [p[0].shape for p in pages], colors, ids, counts=True)
+                    loaded = {k: (page, lab) for (k, _), page, lab in zip(on_device, pages, labels)}
+                for k in range(stop):
+                    entry = part[k]
+                    if k not in loaded:
+                        self.load_images(entry)
+                        if report is not None:
+                            report.append(None)
+                        continue
+                    (img, bin_, orig_bin), lab = loaded[k]
+                    item = None
+                    if lab is not None:
+                        entry.mask, counts = lab
+                        item = {"label_counts": counts[:256].copy(), "unknown": int(counts[256])}
+                        if item["unknown"] > 0:
+                            _log.warning("%s: %d pixels of a colour the colour map does not know became label 0", entry.mask_path, item["unknown"])
+                    entry.binary = bin_
+                    entry.orig_binary = orig_bin
+                    entry.image = img
+                    entry.original_shape = scans[k].shape
+                    if report is not None:
+                        report.append(item)
+                if failed is not None:
+                    raise failed[1]
+        return Dataset(entries, self.color_map)
+
+    def load_data_from_json(self, files, type, as_list=False) -> Dataset:
+        """lib/dataset.py:200-208.  as_list=True: the entries go through load_data_list."""
         entries = []
         for f in files:
             with open(f, 'r') as fh:
@@ -147,4 +277,4 @@ class DatasetLoader:
             for t in kinds:
                 entries += [SingleData(**d) for d in js[t]]
         print(f"Loading {len(entries)} data of type {type}")
-        return self.load_data(entries)
+        return self.load_data_list(entries) if as_list else self.load_data(entries)

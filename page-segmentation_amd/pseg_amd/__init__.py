@@ -7,5 +7,6 @@ from .engine import (  # noqa: F401
     png_encode, masks_png, png_bound, png_code_lengths, tile_plan,
     png_probe, png_decode_gray, PNG_OK, PNG_EINVAL, PNG_EUNSUPPORTED,
     Sauvola, sauvola_window, binarize_scans,
+    label_masks, label_masks_geometry, label_mask_groups,
 )
 from .build import build_library  # noqa: F401

@@ -33,6 +33,7 @@ EXPORTED_SYMBOLS = (
     "pseg_predict_chain_png_lv", "pseg_png_code_lengths", "pseg_predict_chain_pages_png", "pseg_chain_units",
     "pseg_predict_chain_pages_mixed_png", "pseg_chain_units_mixed", "pseg_predict_chain_scans_png", "pseg_prepare_scans",
     "pseg_binarize_scans", "pseg_binarize_scans_host", "pseg_binarize_geometry", "pseg_prepare_scans_bin", "pseg_predict_chain_scans_bin_png",
+    "pseg_label_masks", "pseg_label_masks_host", "pseg_label_masks_geometry", "pseg_label_masks_groups",
     "pseg_rescale_shape", "pseg_gaussian_kernel", "pseg_resize_nearest", "pseg_resize_nearest_device", "pseg_scale_image",
     "pseg_prepare_images", "pseg_affine_warp", "pseg_affine_warp_fill", "pseg_brightness_shift",
     "pseg_eval_confusion", "pseg_cc_label", "pseg_cc_tables", "pseg_eval_pages", "pseg_eval_page_groups",
@@ -56,6 +57,11 @@ class SCAN(ctypes.Structure):
 class BINARIZE(ctypes.Structure):
     """pseg_binarize: how a scan becomes its ink map (window 0: scan <= 127; else Sauvola over an odd window)."""
     _fields_ = [("window", ctypes.c_int), ("k", ctypes.c_double), ("R", ctypes.c_double)]
+
+
+class MASK_SRC(ctypes.Structure):
+    """pseg_mask_src: one decoded ground-truth mask (channels 3: RGB, 1: label ids)."""
+    _fields_ = [("px", ctypes.c_void_p), ("H0", ctypes.c_int), ("W0", ctypes.c_int), ("channels", ctypes.c_int)]
 
 
 class EVAL_PAGE(ctypes.Structure):
@@ -201,6 +207,10 @@ def lib():
     L.pseg_binarize_geometry.argtypes = [c.POINTER(i)] * 4
     L.pseg_prepare_scans_bin.argtypes = [i, i, c.POINTER(SCAN), c.POINTER(BINARIZE), vp, vp, vp]
     L.pseg_predict_chain_scans_bin_png.argtypes = [vp, i, c.POINTER(SCAN), c.POINTER(BINARIZE), c.POINTER(i), i, c.c_uint, vp, i, i, c.c_uint, i, CHAIN_SINK, vp]
+    L.pseg_label_masks.argtypes = [i, i, c.POINTER(MASK_SRC), vp, vp, vp, vp, i, vp, vp]
+    L.pseg_label_masks_host.argtypes = [i, c.POINTER(MASK_SRC), vp, vp, vp, vp, i, vp, vp]
+    L.pseg_label_masks_geometry.argtypes = [c.POINTER(i)] * 4 + [c.POINTER(i64)]
+    L.pseg_label_masks_groups.argtypes = [i, c.POINTER(MASK_SRC), vp]
     L.pseg_tile_plan.argtypes = [i, i, i, i, c.POINTER(i), c.POINTER(i), vp, vp, vp, i]
     L.pseg_predict_tiled_device.argtypes = [vp, vp, i, i, i, vp, vp, vp]
     L.pseg_predict_tiled.argtypes = [vp, vp, i, i, i, vp, vp]
@@ -1267,6 +1277,90 @@ def binarize_scans(scans, how, device=0, thresholds=False, host=False):
             P(*[a.ctypes.data for a in inks]), None if thr is None else P(*[a.ctypes.data for a in thr]))
     _check(lib().pseg_binarize_scans_host(*args) if host else lib().pseg_binarize_scans(int(device), *args))
     return list(zip(inks, thr)) if thresholds else inks
+
+
+# ---- training masks as label maps (pseg_label_masks) ----------------------------------------------------
+
+def label_masks_geometry():
+    """(run, runs, rows, group_masks, group_bytes) of pseg_label_masks (pseg_label_masks_geometry; no device): pixels per thread,
+    runs and rows per workgroup, and the group cut."""
+    v = [ctypes.c_int() for _ in range(4)] + [ctypes.c_int64()]
+    _check(lib().pseg_label_masks_geometry(*[ctypes.byref(x) for x in v]))
+    return tuple(x.value for x in v)
+
+
+def color_table(colors, ids):
+    """The checked table of label_masks: -> (colors (n,3) uint8, ids (n,) uint8).  More than 256 colours, a colour channel or an id
+    outside 0..255, or a duplicate colour raises."""
+    col = np.asarray(colors if len(colors) else np.zeros((0, 3), np.uint8))
+    idv = np.asarray(ids if len(ids) else np.zeros((0,), np.uint8))
+    if col.ndim != 2 or col.shape[1] != 3 or idv.ndim != 1 or idv.shape[0] != col.shape[0]:
+        raise PsegError("label_masks: colors must be (n,3) and ids (n,), got shapes %r and %r" % (col.shape, idv.shape))
+    if col.shape[0] > 256:
+        raise PsegError("label_masks: %d colours, at most 256 fit the table" % col.shape[0])
+    for name, a in (("colour channel", col), ("id", idv)):
+        if a.size and (a.dtype.kind not in "iub" or int(a.min()) < 0 or int(a.max()) > 255):
+            raise PsegError("label_masks: every %s must be an integer in 0..255" % name)
+    col, idv = np.ascontiguousarray(col, dtype=np.uint8), np.ascontiguousarray(idv, dtype=np.uint8)
+    seen = {}
+    for k, rgb in enumerate(map(tuple, col.tolist())):
+        if rgb in seen:
+            raise PsegError("label_masks: colour %d repeats colour %d %r" % (k, seen[rgb], rgb))
+        seen[rgb] = k
+    return col, idv
+
+
+def _mask_sources(masks):
+    arrs = []
+    for k, m in enumerate(masks):
+        a = np.asarray(m)
+        if a.dtype != np.uint8:
+            raise PsegError("mask %d: a uint8 array is expected, got dtype %s" % (k, a.dtype))
+        if a.ndim == 3 and a.shape[2] == 4:
+            raise PsegError("mask %d: an (H,W,4) array has an alpha channel; pass RGB, (H,W,3), or label ids, (H,W)" % k)
+        if a.ndim not in (2, 3) or (a.ndim == 3 and a.shape[2] != 3):
+            raise PsegError("mask %d: an (H,W,3) RGB or (H,W) id array is expected, got shape %r" % (k, a.shape))
+        arrs.append(np.ascontiguousarray(a))
+    table = (MASK_SRC * max(len(arrs), 1))()
+    for k, a in enumerate(arrs):
+        table[k] = MASK_SRC(a.ctypes.data, a.shape[0], a.shape[1], 3 if a.ndim == 3 else 1)
+    return table, arrs
+
+
+def label_mask_groups(masks):
+    """The group pseg_label_masks puts each mask of the list into (pseg_label_masks_groups; no device)."""
+    table, arrs = _mask_sources(masks)
+    n = len(arrs)
+    out = (ctypes.c_int * max(n, 1))()
+    _check(lib().pseg_label_masks_groups(n, table, out))
+    return [int(g) for g in out[:n]]
+
+
+def label_masks(masks, out_shapes, colors, ids, device=0, counts=False, host=False):
+    """The label maps of a list of ground-truth masks at the shapes of their pages in one device-resident call (pseg_label_masks):
+    masks[i] is a uint8 (H0,W0,3) RGB array, looked up in the table (colors (n,3), ids (n,), at most 256; an unknown colour gives
+    0), or a uint8 (H0,W0) array of label ids; out_shapes[i] = (H,W).  Equals
+    preserving_resize(color_map.to_labels(rgb), (H,W)).astype(uint8).  -> [labels uint8 (H,W)], or with counts=True
+    [(labels, counts int64[257])]: pixels per id, and under [256] the pixels of unknown colour (also counted under id 0).
+    host=True: the same bytes from the host entry (pseg_label_masks_host), no device."""
+    table, arrs = _mask_sources(masks)
+    n = len(arrs)
+    if len(out_shapes) != n:
+        raise PsegError("label_masks: out_shapes must have one entry per mask (%d for %d masks)" % (len(out_shapes), n))
+    col, idv = color_table(colors, ids)
+    if n == 0:
+        return []
+    shapes = [(int(s[0]), int(s[1])) for s in out_shapes]
+    for k, s in enumerate(shapes):
+        if s[0] <= 0 or s[1] <= 0:
+            raise PsegError("mask %d: empty output shape %r" % (k, s))
+    P, I = ctypes.c_void_p * n, ctypes.c_int * n
+    labs = [np.empty(s, np.uint8) for s in shapes]
+    cnt = np.zeros((n, 257), np.int64) if counts else None
+    args = (n, table, I(*[s[0] for s in shapes]), I(*[s[1] for s in shapes]), _ptr(col) if len(col) else None, _ptr(idv) if len(col) else None,
+            len(col), P(*[a.ctypes.data for a in labs]), _ptr(cnt))
+    _check(lib().pseg_label_masks_host(*args) if host else lib().pseg_label_masks(int(device), *args))
+    return [(a, cnt[k].copy()) for k, a in enumerate(labs)] if counts else labs
 
 
 FILL_MODES = {"nearest": 0, "constant": 1, "reflect": 2, "wrap": 3}
