@@ -109,6 +109,7 @@ struct MConv {
     unsigned long long* trace;  // PSEG_TRACE: per-workgroup s_memtime stamps (diagnostic builds only)
     int dbg;   // ablation bits (PSEG_DBG): 1 skip input staging, 2 skip MFMAs, 4 skip epilogue, 8 skip weight DMA
     int rowreuse;   // the k-chunk table is tap-major with one k-step per tap (checked on the host, MfmaPlan::rowreuse): row-reuse k-loops may run
+    const uint16_t* wpk_pair;   // paired third cout tile (MfmaPlan::pair8): [30 entries][64 lanes][8] bf16 A fragments, or null
 };
 
 // single v_max_f32: fmaxf() makes hipcc canonicalise both operands first (3 instructions per max
@@ -239,11 +240,12 @@ enum { FL_POOL = 1, FL_ADD = 2, FL_INRELU = 4, FL_UP0 = 8, FL_UP1 = 16, FL_FUSE1
 // is why the host plans few, long groups (mfma_pack_op) and where the form stops paying (triple_pays).  A team without a tile (tile
 // count not a multiple of three) stages zeros through out-of-range descriptors, computes on them and has every store dropped by the
 // bounds checks of the epilogue.
-template <int MT, int NT, int KS_, int ST_, int SG_, int MODE_, int FL_, int NW_ = 4, int RR_ = 0, int TT_ = 1>   // RR_ > 0: row-reuse k-loop for weight groups of RR_ k-steps
+template <int MT, int NT, int KS_, int ST_, int SG_, int MODE_, int FL_, int NW_ = 4, int RR_ = 0, int TT_ = 1, bool P8_ = false>   // RR_ > 0: row-reuse k-loop for weight groups of RR_ k-steps; P8_: ... with the paired third cout tile
 __global__ __launch_bounds__(NW_ * TT_ * 64) __attribute__((amdgpu_waves_per_eu((TT_ == 3 || (MT == 4 && NT == 4 && NW_ == 4 && (KS_ == 5 || KS_ == 3 || KS_ == 2) && (SG_ == 4 || SG_ == 5) && MODE_ == 0)) ? 3 : 2))) void conv_mfma_kernel(MConv a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     static_assert(TT_ == 1 || (TT_ == 3 && NW_ == 4 && MT == 4 && KS_ == 5 && ST_ == 1 && (SG_ == 4 || SG_ == 5) && MODE_ == MODE_CONV && (FL_ & ~FL_POOL) == 0),
                   "tile triples: the plain k5 stride-1 instances on dense 8 x 32 tiles");
+    static_assert(!P8_ || (RR_ == 4 && TT_ == 1 && NT == 3 && FL_ == 0), "the paired third tile: the row-reuse instance for weight groups of four k-steps");
     constexpr int NW = NW_, NTHR = NW_ * TT_ * 64;   // NW: waves of a team (= of the workgroup unless TT_ > 1)
     constexpr int NWR = NW_ * TT_;                   // waves that share the weight ring
     constexpr int TH = NW * (MT / 2);  // NW waves x (MT/2) rows
@@ -347,6 +349,7 @@ __global__ __launch_bounds__(NW_ * TT_ * 64) __attribute__((amdgpu_waves_per_eu(
     for (int m = 0; m < MT; ++m)
 #pragma unroll
         for (int n = 0; n < NT; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
+    f32x4 accp[2];      // P8_: the paired third cout tile of the two column tiles -- rows 0-7 couts 32-39 of the wave's first row, rows 8-15 of its second (acc[.][2] unused)
     // the bias is the accumulators' start value (the first MFMA's C operand) in every instance, as in conv12_ws_kernel:
     // no epilogue adds it, and all paths of the engine round in one order
     constexpr bool c_bias0 = true;
@@ -390,6 +393,10 @@ __global__ __launch_bounds__(NW_ * TT_ * 64) __attribute__((amdgpu_waves_per_eu(
         for (int m = 0; m < MT; ++m)
 #pragma unroll
             for (int n = 0; n < NT; ++n) acc[m][n] = f32x4{biasr[n].x, biasr[n].y, biasr[n].z, biasr[n].w};
+    }
+    if constexpr (P8_) {
+        const float4 bp = *(const float4*)(a.bias + 32 + 4 * (g & 1));
+        accp[0] = accp[1] = f32x4{bp.x, bp.y, bp.z, bp.w};
     }
     const int D = a.NB > 1 ? a.NB - 1 : 1;  // prefetch distance in groups (NB == 1: single resident group)
     for (int q = 0; q < D && q < G; ++q) stage_w(q, q);
@@ -665,8 +672,13 @@ __global__ __launch_bounds__(NW_ * TT_ * 64) __attribute__((amdgpu_waves_per_eu(
             // waits, ring slots), same pipeline inside a group, same operands per accumulator in the same order: the same bits.
             static_assert(RR_ == 0 || (FIXED && KS_ == 5 && ST_ == 1 && SG_ == 4 && MT == 4 && MODE_ == MODE_CONV && !(FL_ & (FL_INRELU | FL_UP0 | FL_UP1 | FL_FUSE1 | FL_PERSIST))),
                           "row reuse: k5 stride-1 instances with four chunks per pixel and two rows x two column tiles per wave");
+            // P8_ (host: MfmaPlan::pair8, the ring packing of mfma_pack_op): the third-tile piece of k-step s holds paired entry s --
+            // couts 32-39 of step s in rows 0-7 (row r), of step s - 5 in rows 8-15 (row r + 1) -- and entries 25-29 sit in pieces
+            // 3-7 of the block's last group, which were zero padding: the ring, its groups and the counted waits are the unpaired
+            // instance's.  accp[c] replaces acc[c][2] and acc[2 + c][2]; the entry's B operand is the lower row's (lo0[s] / hi[s - 5]),
+            // entries 25-29 take hi[20..24] AFTER entry 24, so that each row meets its taps in the old order -- see conv_pp_kernel.
             constexpr int GKC = RR_;
-            bf16x8 hi[26][2], lo0[5][2], wr[2][NT];
+            bf16x8 hi[26][2], lo0[5][2], wr[2][NT], wq[5];
             int offp[2];
             const char* wb = nullptr;
             const int* const tb = tab_l + g;
@@ -699,7 +711,11 @@ __global__ __launch_bounds__(NW_ * TT_ * 64) __attribute__((amdgpu_waves_per_eu(
                     wr[(S) & 1][t] = *(const bf16x8*)(wb + (sg_ * NT + t) * 1024);               \
             }
 #define RR_MMA(S)                                                                                \
-            _Pragma("unroll") for (int t = 0; t < NT; ++t) {                                     \
+            if constexpr (P8_) {                                                                 \
+                accp[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wr[(S) & 1][2], (S) < 5 ? lo0[(S) % 5][0] : hi[(S) < 5 ? 0 : (S) - 5][0], accp[0], 0, 0, 0); \
+                accp[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wr[(S) & 1][2], (S) < 5 ? lo0[(S) % 5][1] : hi[(S) < 5 ? 0 : (S) - 5][1], accp[1], 0, 0, 0); \
+            }                                                                                    \
+            _Pragma("unroll") for (int t = 0; t < (P8_ ? 2 : NT); ++t) {                         \
                 acc[0][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wr[(S) & 1][t], (S) < 5 ? lo0[(S) % 5][0] : hi[(S) < 5 ? 0 : (S) - 5][0], acc[0][t], 0, 0, 0); \
                 acc[1][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wr[(S) & 1][t], (S) < 5 ? lo0[(S) % 5][1] : hi[(S) < 5 ? 0 : (S) - 5][1], acc[1][t], 0, 0, 0); \
                 acc[2][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wr[(S) & 1][t], hi[S][0], acc[2][t], 0, 0, 0); \
@@ -721,13 +737,22 @@ __global__ __launch_bounds__(NW_ * TT_ * 64) __attribute__((amdgpu_waves_per_eu(
                     if constexpr (((S) + 1) % GKC != GKC - 1 && (S) + 1 != 24) offp[(S) & 1] = tb[((S) + 2) * 4]; \
                     RR_LOAD((S) + 1, offp[((S) + 1) & 1])                                        \
                     RR_MMA(S)                                                                    \
-                    _Pragma("unroll") for (int q_ = 0; q_ < MT * NT; ++q_) {                      \
+                    _Pragma("unroll") for (int q_ = 0; q_ < (P8_ ? 10 : MT * NT); ++q_) {         \
                         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                        \
                         __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                        \
                         __builtin_amdgcn_sched_group_barrier(0x002, 1, 0);                        \
                     }                                                                            \
                 } else {                                                                         \
+                    if constexpr (P8_ && (S) == 24) {                                            \
+                        _Pragma("unroll") for (int q_ = 0; q_ < 5; ++q_) wq[q_] = *(const bf16x8*)(wb + (3 + q_) * 1024); \
+                    }                                                                            \
                     RR_MMA(S)                                                                    \
+                    if constexpr (P8_ && (S) == 24) {                                            \
+                        _Pragma("unroll") for (int q_ = 0; q_ < 5; ++q_) {                       \
+                            accp[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wq[q_], hi[20 + q_][0], accp[0], 0, 0, 0); \
+                            accp[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wq[q_], hi[20 + q_][1], accp[1], 0, 0, 0); \
+                        }                                                                        \
+                    }                                                                            \
                 }                                                                                \
             }
             RR_STEP(0) RR_STEP(1) RR_STEP(2) RR_STEP(3) RR_STEP(4)
@@ -1140,8 +1165,34 @@ __global__ __launch_bounds__(NW_ * TT_ * 64) __attribute__((amdgpu_waves_per_eu(
     const bool lst = c_lst && !a.dst2 && a.dst_bytes != 0u && !(a.dbg & 32);
     char* const patch = smem + wave_r * ((MT / 2) * TW * LST_PP);         // this wave's rows (tile triples: the teams' patches follow each other)
     if (lst) lds_barrier();
+    if constexpr (P8_) {
+        // the paired tile: lane (p16, g) holds couts 32 + 4 (g & 1) ... of the wave's first row (g < 2) or of its second (g >= 2)
+        const int n = 32 + 4 * (g & 1);
+        const unsigned noff = n < CsO ? (unsigned)n * 2u : OOBS;
 #pragma unroll
-    for (int t = 0; t < NT; ++t) {
+        for (int c = 0; c < 2; ++c) {
+            float v[4] = {accp[c][0], accp[c][1], accp[c][2], accp[c][3]};
+            if (a.relu) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) v[r] = vmax(v[r], 0.0f);
+            }
+            const uint2 pk = make_uint2(pk_bf16(v[0], v[1]), pk_bf16(v[2], v[3]));
+            if (lst) {
+                *(uint2*)(patch + ((g >> 1) * TW + c * 16 + p16) * LST_PP + 64 + (g & 1) * 8) = pk;
+            } else {
+                const int y = oy0 + wave * (MT / 2) + (g >> 1), x = ox0 + c * 16 + p16;
+                const unsigned po = (y < a.Hout && x < a.Wout) ? (unsigned)(y * a.Wout + x) * (unsigned)(CsO * 2) : OOBS;
+                const unsigned o = (po == OOBS || noff == OOBS) ? OOBS : po + noff;
+                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, pk), rd, o, 0, 0);
+                if (a.dst2) {
+                    const uint2 pr = make_uint2(relu_pk_bf16(pk.x, 0u), relu_pk_bf16(pk.y, 0u));
+                    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, pr), rd2, o, 0, 0);
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < (P8_ ? 2 : NT); ++t) {
         const int n = (nb * NT + t) * 16 + 4 * g;
         const unsigned noff = n < CsO ? (unsigned)n * 2u : OOBS;
         float v[MT][4];
@@ -2565,16 +2616,20 @@ __global__ __launch_bounds__(256) void logits_bf16_kernel(const uint16_t* src0, 
 // the empty rows read a zero slot): conv4's weights 96 -> 80 KB, which is what lets two 35 KB tiles fit.
 // Same products, same k order, same start value as conv_mfma_kernel: the same bits.
 // ---------------------------------------------------------------------------------------------
-template <int SG, bool POOL, bool RR = false>
+template <int SG, bool POOL, bool RR = false, bool P8 = false>
 __global__ __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(3, 3))) void conv_pp_kernel(MConv a) {
     static_assert(!RR || SG == 4, "row reuse needs one k-step per tap: four chunks per pixel");
+    static_assert(!P8 || RR, "the paired third tile lives in the row-reuse loop");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int MT = 4, NT = 3, TH = 8, KS = 5, THH = TH + KS - 1, TWH = TW + KS - 1, PS2 = SG * 16;
-    constexpr int WSTEP = 2 * 1024 + 512;                 // LDS bytes of one k-step's A fragments (third tile: rows 0-7 only)
+    // LDS bytes of one k-step's A fragments (third tile: rows 0-7 only).  P8 (MConv::wpk_pair): the third tile is not kept per k-step;
+    // its paired form -- 30 whole fragments, rows 0-7 for the wave's first row, rows 8-15 for its second -- follows the k-steps
+    constexpr int WSTEP = P8 ? 2 * 1024 : 2 * 1024 + 512, WPAIR = P8 ? 30 * 1024 : 0;
     const int TB = a.lds_w_off;                           // bytes of one input tile (THH rows), 16-aligned (host)
     const int ks = a.ks_full;
     char* const w_t = smem + 2 * TB;
-    char* const zero16 = w_t + ks * WSTEP;                // 16 zero bytes: the A rows that do not exist
+    char* const wp_t = w_t + ks * WSTEP;                  // P8: the paired table
+    char* const zero16 = wp_t + WPAIR;                    // 16 zero bytes: the A rows that do not exist
     int* const tab_l = (int*)(zero16 + 16);
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -2592,6 +2647,15 @@ __global__ __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     };
     const int n_my = ((int)a.ntiles - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;   // tiles of this workgroup
     // ---- resident weights + k-chunk table + clean tile buffers: once per workgroup ---------------------------------
+    if constexpr (P8) {
+        for (int pc = wave; pc < ks * 2 + 30; pc += 12) {
+            const int en = pc - ks * 2;                       // >= 0: entry of the paired table
+            const uint16_t* const gsrc = en < 0 ? a.wpk + (size_t)((pc >> 1) * NT + (pc & 1)) * 512 : a.wpk_pair + (size_t)en * 512;
+            char* const ldst = en < 0 ? w_t + (pc >> 1) * WSTEP + (pc & 1) * 1024 : wp_t + en * 1024;
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gsrc + lane * 8),
+                                             (__attribute__((address_space(3))) void*)ldst, 16, 0, 0);
+        }
+    } else
     for (int pc = wave; pc < ks * NT; pc += 12) {
         const int s_ = pc / NT, t_ = pc - s_ * NT;
         // packed A fragments: [k-step][cout tile][lane = (row p16, k-group g)][8]; tile 2 keeps lanes with p16 < 8 as slots g*8 + p16
@@ -2662,12 +2726,15 @@ __global__ __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     const char* const wb0 = w_t + lane * 16;
     const char* const wb2 = p16 < 8 ? w_t + 2048 + (g * 8 + p16) * 16 : zero16 - 0;   // third cout tile: rows 8-15 do not exist
     const int w2step = p16 < 8 ? WSTEP : 0;
+    const char* const wbp = wp_t + lane * 16;
+    const float4 biasp = *(const float4*)(a.bias + 32 + 4 * (g & 1));   // P8: couts 32-39 in both halves of the paired tile
     const int* const tb = tab_l + g;
     const int CsO = a.nch_out * 8;
     constexpr unsigned OOBS = 0xfffffff0u;
     const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc((void*)a.dst, 0, a.dst_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc((void*)(POOL ? a.pool_dst : a.dst), 0, POOL ? a.pool_bytes : 0u, 0x00020000);
     f32x4 acc[MT][NT];
+    f32x4 accp[2];                                        // P8: the paired third tile of the two column tiles (acc[.][2] stays unused)
     int eoy = 0, eox = 0;                                 // origin of the tile held in acc
     lds_barrier();                                        // (pairs with the producers' "tile 0 is in buffer 0")
     for (int ph = 0; ph <= n_my; ++ph) {
@@ -2679,7 +2746,8 @@ __global__ __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
 #pragma unroll
                 for (int m = 0; m < MT; ++m)
 #pragma unroll
-                    for (int n = 0; n < NT; ++n) acc[m][n] = f32x4{biasr[n].x, biasr[n].y, biasr[n].z, biasr[n].w};
+                    for (int n = 0; n < (P8 ? 2 : NT); ++n) acc[m][n] = f32x4{biasr[n].x, biasr[n].y, biasr[n].z, biasr[n].w};
+                accp[0] = accp[1] = f32x4{biasp.x, biasp.y, biasp.z, biasp.w};
                 bf16x8 xa[MT], wa[NT], xb[MT], wbq[NT];
 #define PP_LOAD(XF, WF, S, OFF)                                                                  \
                 {                                                                                \
@@ -2701,6 +2769,13 @@ __global__ __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
                     __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                            \
                     __builtin_amdgcn_sched_group_barrier(0x002, 1, 0);                            \
                 }
+                // (the paired loop has ten MFMAs per step for the same five to seven reads: one read and one address add behind each)
+#define PPR_INTERLEAVE                                                                           \
+                _Pragma("unroll") for (int q_ = 0; q_ < (P8 ? 10 : MT * NT); ++q_) {              \
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                            \
+                    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                            \
+                    __builtin_amdgcn_sched_group_barrier(0x002, 1, 0);                            \
+                }
                 if (a.dbg & 0x400) __builtin_amdgcn_s_setprio(3);      // PSEG_PP_PRIO=1
                 if constexpr (RR) {
                     // Row reuse (host: MfmaPlan::rowreuse -- 25 k-steps, table entry of step s + 5 = entry of step s + one tile row): the
@@ -2710,7 +2785,16 @@ __global__ __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
                     // fragments are live (ten carried, two incoming) instead of eight; pixel reads per tile 60 instead of 100.
                     // Same pipeline as below: the reads of step s + 1 issue between the MFMAs of step s, same operands per accumulator
                     // in the same order -- the same bits.
-                    bf16x8 hi[25][2], lo0[5][2], wr[2][NT];
+                    // P8 (host: MfmaPlan::pair8): the third cout tile has eight real rows, so the wave's two output rows share ONE A
+                    // fragment per tap: paired entry e carries couts 32-39 of k-step e in rows 0-7 (for row r) and of k-step e - 5 in rows
+                    // 8-15 (for row r + 1), and its B operand is the fragment the lower row uses at step e anyway (lo0[e] / hi[e - 5]);
+                    // entries 25-29 (B = hi[20..24]) finish row r + 1.  accp[c] replaces acc[c][2] and acc[2 + c][2]: 260 MFMAs per tile
+                    // instead of 300.  Same bits: one k-step is still one tap, so the 32 products of an MFMA are grouped as before; rows
+                    // 0-7 meet k-steps 0-24 in order and then five all-zero fragments, rows 8-15 five all-zero fragments and then k-steps
+                    // 0-24 in order -- entries 25-29 are issued AFTER entry 24 (not beside entries 20-24, which would put tap 20 before
+                    // tap 16 in row r + 1's sum).  The zero terms are sums of 0 * finite
+                    // added to an accumulator that starts at the bias: at most -0 becomes +0, which compares equal.
+                    bf16x8 hi[25][2], lo0[5][2], wr[2][NT], wq[5];
                     int offp[2];
                     const char* const px0 = in_t + pixbase[0];
                     const char* const px1 = in_t + pixbase[1];
@@ -2728,10 +2812,18 @@ __global__ __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
                         hi[S][0] = *(const bf16x8*)(px2 + OFF);                                  \
                         hi[S][1] = *(const bf16x8*)(px3 + OFF);                                  \
                         wr[(S) & 1][1] = *(const bf16x8*)(wb0 + (S) * WSTEP + 1024);             \
+                        if constexpr (P8) {                                                      \
+                            wr[(S) & 1][2] = *(const bf16x8*)(wbp + (S) * 1024);                 \
+                        } else                                                                   \
                         wr[(S) & 1][2] = *(const bf16x8*)(wb2 + (S) * w2s);                      \
                     }
+#define PPR_PAIR(S, C) accp[C] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wr[(S) & 1][2], (S) < 5 ? lo0[(S) % 5][C] : hi[(S) < 5 ? 0 : (S) - 5][C], accp[C], 0, 0, 0);
+#define PPR_TAIL(E) /* paired entry E = 25..29 */                                                \
+                    accp[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wq[(E) % 5], hi[(E) - 5][0], accp[0], 0, 0, 0); \
+                    accp[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wq[(E) % 5], hi[(E) - 5][1], accp[1], 0, 0, 0);
 #define PPR_MMA(S)                                                                               \
-                    _Pragma("unroll") for (int t = 0; t < NT; ++t) {                             \
+                    if constexpr (P8) { PPR_PAIR(S, 0) PPR_PAIR(S, 1) }                          \
+                    _Pragma("unroll") for (int t = 0; t < (P8 ? 2 : NT); ++t) {                  \
                         acc[0][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wr[(S) & 1][t], (S) < 5 ? lo0[(S) % 5][0] : hi[(S) < 5 ? 0 : (S) - 5][0], acc[0][t], 0, 0, 0); \
                         acc[1][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wr[(S) & 1][t], (S) < 5 ? lo0[(S) % 5][1] : hi[(S) < 5 ? 0 : (S) - 5][1], acc[1][t], 0, 0, 0); \
                         acc[2][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wr[(S) & 1][t], hi[S][0], acc[2][t], 0, 0, 0); \
@@ -2742,7 +2834,7 @@ __global__ __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
                     offp[(S) & 1] = tb[((S) + 2) * 4];                                           \
                     PPR_LOAD((S) + 1, offp[((S) + 1) & 1])                                       \
                     PPR_MMA(S)                                                                   \
-                    PP_INTERLEAVE
+                    PPR_INTERLEAVE
                     offp[0] = tb[0]; offp[1] = tb[4];
                     PPR_LOAD(0, offp[0])
                     PPR_STEP(0) PPR_STEP(1) PPR_STEP(2) PPR_STEP(3) PPR_STEP(4)
@@ -2753,11 +2845,23 @@ __global__ __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
                     __builtin_amdgcn_sched_barrier(0);
                     PPR_LOAD(24, offp[0])
                     PPR_MMA(23)
-                    PP_INTERLEAVE
+                    PPR_INTERLEAVE
                     __builtin_amdgcn_sched_barrier(0);
+                    if constexpr (P8) {
+                        // the last step: no fragment of a next step is incoming, so the five A fragments of entries 25-29 are read
+                        // here (they take the registers of dead hi[] fragments) and the step's own ten MFMAs cover the reads
+#pragma unroll
+                        for (int q_ = 0; q_ < 5; ++q_) wq[q_] = *(const bf16x8*)(wbp + (25 + q_) * 1024);
+                        PPR_MMA(24)
+                        PPR_TAIL(25) PPR_TAIL(26) PPR_TAIL(27) PPR_TAIL(28) PPR_TAIL(29)
+                    } else {
                     PPR_MMA(24)
+                    }
 #undef PPR_STEP
 #undef PPR_MMA
+#undef PPR_TAIL
+#undef PPR_PAIR
+#undef PPR_INTERLEAVE
 #undef PPR_LOAD
                 } else {
                 int offa = PP_TAB(0), offb = PP_TAB(1);
@@ -2793,8 +2897,45 @@ __global__ __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
                 const int y = eoy + wv * 2 + (m >> 1), x = eox + (m & 1) * 16 + p16;
                 pixoff[m] = (y < a.Hout && x < a.Wout) ? (unsigned)(y * a.Wout + x) * (unsigned)(CsO * 2) : OOBS;
             }
+            if constexpr (P8) {
+                // the paired tile: lane (p16, g) holds couts 32 + 4 (g & 1) ... of row r (g < 2) or of row r + 1 (g >= 2)
+                const int n = 32 + 4 * (g & 1);
+                const unsigned noff = n < CsO ? (unsigned)n * 2u : OOBS;
+                float v[2][4];
 #pragma unroll
-            for (int t = 0; t < NT; ++t) {
+                for (int c = 0; c < 2; ++c) {
+                    v[c][0] = accp[c][0]; v[c][1] = accp[c][1]; v[c][2] = accp[c][2]; v[c][3] = accp[c][3];
+                    const int y = eoy + wv * 2 + (g >> 1), x = eox + c * 16 + p16;   // (a row r + 1 below the image: out of bounds as ever)
+                    const unsigned po = (y < a.Hout && x < a.Wout) ? (unsigned)(y * a.Wout + x) * (unsigned)(CsO * 2) : OOBS;
+                    const unsigned o = (po == OOBS || noff == OOBS) ? OOBS : po + noff;
+                    if (a.relu) {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) v[c][r] = vmax(v[c][r], 0.0f);
+                    }
+                    const uint2 pk = make_uint2(pk_bf16(v[c][0], v[c][1]), pk_bf16(v[c][2], v[c][3]));
+                    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, pk), rd, o, 0, 0);
+                }
+                if (POOL) {
+                    const int Wo2 = a.Wout >> 1, Ho2 = a.Hout >> 1;
+#pragma unroll
+                    for (int c = 0; c < 2; ++c) {             // the other row of the pair sits 32 lanes away
+                        float q[4];
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const float o32 = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute((lane ^ 32) * 4, __builtin_bit_cast(int, v[c][r])));
+                            q[r] = vmax_xor1(vmax(v[c][r], o32));
+                        }
+                        const int y = (eoy >> 1) + wv;
+                        const int x = (eox >> 1) + ((c * 16 + p16) >> 1);
+                        const bool ok = g < 2 && !(p16 & 1) && y < Ho2 && x < Wo2 && noff != OOBS;
+                        const unsigned o = ok ? (unsigned)(y * Wo2 + x) * (unsigned)(CsO * 2) + noff : OOBS;
+                        const uint2 pk = make_uint2(pk_bf16(q[0], q[1]), pk_bf16(q[2], q[3]));
+                        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, pk), rp, o, 0, 0);
+                    }
+                }
+            }
+#pragma unroll
+            for (int t = 0; t < (P8 ? 2 : NT); ++t) {
                 const int n = t * 16 + 4 * g;
                 const unsigned noff = n < CsO ? (unsigned)n * 2u : OOBS;
                 float v[MT][4];
@@ -3875,6 +4016,9 @@ enum PlanKind { PLAN_GENERIC = 0, PLAN_CONV1 = 1, PLAN_LOGITS = 2, PLAN_UPSPLIT 
 struct MfmaPlan {
     int kind = PLAN_GENERIC;
     bool rowreuse = false;    // k5, four chunks per pixel: k-step (ky, kx) of a wave's lower row reads what (ky + 1, kx) of its upper row reads (mfma_pack_op)
+    bool pair8 = false;       // row reuse, 40 couts: the eight left-over couts of a wave's two rows share one A fragment per tap (d_wpk_pair, mfma_pack_op)
+    uint16_t* d_wpk_pair = nullptr;      // ... conv_pp_kernel's table: [channel block][30 entries][64][8]
+    uint16_t* d_wpk_rpair = nullptr;     // ... conv_mfma_kernel's ring stream (groups of four k-steps) with the paired entries in place of the third tile
     int MT = 4, NT = 2, KS = 1, stride = 1, NW = 4;
     int nblk = 1, nc_full = 1, nc_last = 1, ks_full = 1, ks_last = 1;
     int PS2 = 0, row_pitch = 0, THH = 0, TWH = 0, GK = 4, NB = 3, G = 1, lds_w_off = 0, lds_tab_off = 0, lds_bytes = 0;
@@ -3955,7 +4099,7 @@ void mfma_free_op(Op& op) {
     (void)hipFree(p->d_skiplog);
     (void)hipFree(p->d_dq_w); (void)hipFree(p->d_dq_bias);
     (void)hipFree(p->d_q_w); (void)hipFree(p->d_q_bias); (void)hipFree(p->d_t2_wD); (void)hipFree(p->d_t2_wC);
-    (void)hipFree(p->d_sp_wpk); (void)hipFree(p->tr.d_wpk);
+    (void)hipFree(p->d_sp_wpk); (void)hipFree(p->tr.d_wpk); (void)hipFree(p->d_wpk_pair); (void)hipFree(p->d_wpk_rpair);
     for (int v = 0; v < 2; ++v) { (void)hipFree(p->sp_lay[v].d_tab); (void)hipFree(p->sp2_lay[v].d_tab); }
     delete p;
     op.plan = nullptr;
@@ -4509,6 +4653,7 @@ int mfma_pack_op(Engine& e, Op& op, const std::vector<float>& w, const std::vect
     // (ky - 1, kx) -- same LDS address, same lane layout -- so the k-loop keeps them in registers for five steps instead of reading
     // them again: 60 instead of 100 pixel-fragment reads per tile and channel block.  Same operands in the same order for every
     // accumulator: the same bits.  Decided on the tables as uploaded, not on how pair_chunks happens to order them.
+    bool no_pair8 = false;
     {
         auto shifts = [&](const std::vector<Chunk>& ord, const std::vector<int>& t) {
             if (ord.size() != 100) return false;
@@ -4519,8 +4664,12 @@ int mfma_pack_op(Engine& e, Op& op, const std::vector<float>& w, const std::vect
                     if (t[(s + 5) * 4 + gq] != t[s * 4 + gq] + P->row_pitch) return false;
             return true;
         };
+        // PSEG_NO_ROWREUSE (plan switch: tests, A/B): "pair" keeps row reuse and takes only the paired third tile (below) away; any other
+        // value takes both
+        const char* const sw = PSEG_KNOB("PSEG_NO_ROWREUSE");
+        no_pair8 = sw != nullptr;
         P->rowreuse = !deconv && KS == 5 && op.stride == 1 && !op.up0 && !op.up1 && !op.in_relu && P->MT == 4 && P->NW == 4 &&
-                      shifts(ord_full, tab_full) && shifts(ord_last, tab_last) && !PSEG_KNOB("PSEG_NO_ROWREUSE") && spec;
+                      shifts(ord_full, tab_full) && shifts(ord_last, tab_last) && !(sw && strcmp(sw, "pair") != 0) && spec;
         if (PSEG_KNOB("PSEG_LOG_GENERIC") && KS == 5 && P->MT == 4 && sigma == 4)
             fprintf(stderr, "[pseg] rowreuse %s: %d\n", op.layer.c_str(), P->rowreuse ? 1 : 0);
     }
@@ -4630,6 +4779,69 @@ int mfma_pack_op(Engine& e, Op& op, const std::vector<float>& w, const std::vect
     return pk;
     };
     PSEG_TRY(upload(&P->d_wpk, pack_w(GK, P->G)));
+    // ---- paired third tile (conv_pp_kernel's row-reuse loop, 40 couts) ----------------------------------------------------------
+    // The third cout tile of a 40-channel layer has eight real rows.  A wave owns output rows r and r + 1, and under row reuse the
+    // B fragment of k-step s + 5 of row r IS the B fragment of k-step s of row r + 1.  So one A fragment serves both rows: entry
+    // e = 0..29 holds the third tile's rows 0-7 of k-step e in its rows 0-7 (zero for e >= 25) and the same eight rows of k-step
+    // e - 5 in its rows 8-15 (zero for e < 5); the k layout inside a fragment is the tile's own.  30 MFMAs per column tile and
+    // channel block instead of 2 x 25, one accumulator tile instead of two.  Stated on k-steps, not taps: it holds for whatever
+    // tap order the row-reuse check accepted, given that steps s and s + 5 read the same chunk of a pixel (checked here).
+    {
+        auto same_chunks = [&](const std::vector<Chunk>& ord) {
+            for (int s = 0; s < 20; ++s)
+                for (int gq = 0; gq < 4; ++gq)
+                    if (ord[(size_t)(s + 5) * 4 + gq].cc != ord[(size_t)s * 4 + gq].cc) return false;
+            return true;
+        };
+        P->pair8 = P->rowreuse && (P->pp || (GK == 4 && NB > 1)) && !no_pair8 && NT == 3 && P->nblocks_n == 1 && Cout > 32 && Cout <= 40 && P->ks_full == 25 &&
+                   P->ks_last == 25 && same_chunks(ord_full) && same_chunks(ord_last);
+        if (P->pair8) {
+            std::vector<uint16_t> pr((size_t)P->nblk * 30 * 512, 0);
+            for (int b = 0; b < P->nblk; ++b) {
+                const auto& ord = b == P->nblk - 1 ? ord_last : ord_full;
+                for (int en = 0; en < 30; ++en)
+                    for (int l = 0; l < 64; ++l) {
+                        const int row = l & 15, s = row < 8 ? en : en - 5;          // the k-step whose weights this row carries
+                        if (s < 0 || s >= 25) continue;
+                        const Chunk c = ord[(size_t)s * 4 + (l >> 4)];
+                        uint16_t* o = &pr[(((size_t)b * 30 + en) * 64 + l) * 8];
+                        for (int j = 0; j < 8; ++j) {
+                            const int ci = true_ci((b * P->nc_full + c.cc) * 8 + j);
+                            if (ci >= 0) o[j] = f2bf(wval(c.tap, ci, 32 + (row & 7)));
+                        }
+                    }
+            }
+            if (P->pp) PSEG_TRY(upload(&P->d_wpk_pair, pr));
+            // The ring stream of conv_mfma_kernel's row-reuse instance (groups of four k-steps, every channel block padded to whole
+            // groups): entry e < 25 takes the place of the third-tile piece of k-step e -- its rows 8-15 were the zero rows of couts
+            // 40-47 -- and entries 25-29 go to pieces 3-7 of the block's last group, which holds k-step 24 and three steps of zero
+            // padding.  Same groups, same 12 KB per group, same number of DMA pieces per wave: the ring layout does not change.
+            if (GK == 4 && NB > 1) {
+                std::vector<uint16_t> rp = pack_w(GK, P->G);
+                const std::vector<uint16_t> orig = rp;
+                const int gpb = cdiv(P->ks_full, GK);
+                auto piece = [&](int b, int en) -> size_t {      // first element of the piece that holds paired entry en of block b
+                    const int s = std::min(en, 24), k0 = b * gpb * GK + s;
+                    return ((size_t)(k0 / GK) * GK * NT + (size_t)(k0 % GK) * NT + (en < 25 ? 2 : 3 + (en - 25))) * 512;
+                };
+                for (int b = 0; b < P->nblk; ++b)
+                    for (int en = 5; en < 30; ++en)
+                        for (int gq = 0; gq < 4; ++gq)
+                            for (int row = 0; row < 8; ++row)
+                                std::copy_n(&orig[piece(b, en - 5) + (size_t)(gq * 16 + row) * 8], 8, &rp[piece(b, en) + (size_t)(gq * 16 + 8 + row) * 8]);
+                PSEG_TRY(upload(&P->d_wpk_rpair, rp));
+            }
+            if (PSEG_KNOB("PSEG_LOG_GENERIC")) {
+                uint32_t h = 2166136261u;                    // FNV-1a of the table's bytes: tests restate the packing and compare
+                for (const uint16_t v : pr) { h = (h ^ (v & 0xffu)) * 16777619u; h = (h ^ (uint32_t)(v >> 8)) * 16777619u; }
+                fprintf(stderr, "[pseg] pair8 %s: 1 (%d channel block(s) x 30 entries, %zu bytes, fnv1a %08x; pp table %d: resident weights %d -> %d bytes; "
+                        "ring stream %d: groups of %d k-steps and %d KB as unpaired, entry s in the third-tile piece of k-step s, entries 25-29 in pieces 3-7 of a block's last group)\n",
+                        op.layer.c_str(), P->nblk, pr.size() * 2, h, P->d_wpk_pair ? 1 : 0, P->ks_full * 2560, P->ks_full * 2048 + 30 * 1024,
+                        P->d_wpk_rpair ? 1 : 0, GK, GK * NT);
+            }
+        } else if (PSEG_KNOB("PSEG_LOG_GENERIC") && P->rowreuse && NT == 3)
+            fprintf(stderr, "[pseg] pair8 %s: 0\n", op.layer.c_str());
+    }
     // ---- tile triples (conv_mfma_kernel, TT_ = 3): three teams on their own tiles share ONE weight ring in the CU's pooled LDS --------
     // Same tile, table, k order and epilogue per team; what is planned here is the second ring layout: 160 KB minus three tiles (the
     // teams' store patches lie over tiles and ring once every wave is out of the k-loop) and the table.  PSEG_NO_TRIPLE=1: the plan
@@ -5108,8 +5320,13 @@ static bool triple_pays(const MfmaPlan& P, const Extent& x) {
 static int tile_bytes(const MfmaPlan& P) { return round_up(P.THH * P.row_pitch, 16); }
 
 // conv_pp_kernel: the weights fit LDS beside two tiles, and every CU's workgroup walks at least two of them
-static bool pp_pays(const MfmaPlan& P, const Extent& x, int* lds) {
-    *lds = 2 * tile_bytes(P) + P.ks_full * 2560 + 16 + round_up(P.ks_full * 16, 16);
+// (the paired third tile -- MfmaPlan::pair8 -- keeps 2 KB per k-step plus its 30 KB table resident instead of 2.5 KB per k-step; a plan
+// whose paired form does not fit runs unpaired: *pair says which)
+static bool pp_pays(const MfmaPlan& P, const Extent& x, int* lds, bool* pair) {
+    const int rest = 2 * tile_bytes(P) + 16 + round_up(P.ks_full * 16, 16);
+    const int paired = rest + P.ks_full * 2048 + 30 * 1024;
+    *pair = P.pair8 && paired <= 160 * 1024;
+    *lds = *pair ? paired : rest + P.ks_full * 2560;
     return *lds <= 160 * 1024 && x.tiles >= 2 * x.cus;
 }
 
@@ -5169,8 +5386,16 @@ static int launch_generic_any2(const MConv& a, const MfmaPlan& P, dim3 grid, int
     PSEG_TRY_INST(4, 3, 5, 1, 6, MODE_CONV, FL_POOL)      // conv4
     // row reuse (MfmaPlan::rowreuse): the instance is compiled for the plan's weight-group size
     if (a.rowreuse && P.GK == 4 && P.ks_full == 25 && P.ks_last == 25 && !a.trace && P.MT == 4 && P.NT == 3 && ks == 5 && st_ == 1 && sg == 4 &&
-        mode == MODE_CONV && fl == 0 && P.spec)
+        mode == MODE_CONV && fl == 0 && P.spec) {
+        if (P.d_wpk_rpair && a.wpk == P.d_wpk) {           // ... with the paired third tile (MfmaPlan::pair8): the same ring, the paired stream
+            MConv w = a;
+            w.wpk = P.d_wpk_rpair;
+            if (PSEG_KNOB("PSEG_LOG_GENERIC")) fprintf(stderr, "[pseg] rowreuse launch: pair8 1 (Cout %d, %d channel blocks)\n", w.nch_out * 8, w.nblk);
+            return launch_lds<conv_mfma_kernel<4, 3, 5, 1, 4, MODE_CONV, 0, 4, 4, 1, true>>(w, grid, 256, P.lds_bytes, dev, st);
+        }
+        if (PSEG_KNOB("PSEG_LOG_GENERIC")) fprintf(stderr, "[pseg] rowreuse launch: pair8 0 (Cout %d, %d channel blocks)\n", a.nch_out * 8, a.nblk);
         return launch_inst<4, 3, 5, 1, 4, MODE_CONV, 0, 4, 4>(a, P, grid, dev, st);   // conv3 (small pages), deconv3
+    }
     PSEG_TRY_INST(4, 3, 5, 1, 4, MODE_CONV, 0)            // conv3, deconv3: dense 64-byte pixels, three workgroups per CU
     PSEG_TRY_INST(4, 3, 5, 1, 5, MODE_CONV, FL_POOL)      // conv4: dense 80-byte pixels, three workgroups per CU
     PSEG_TRY_INST(4, 3, 5, 1, 5, MODE_CONV, 0)
@@ -5456,26 +5681,31 @@ static int route_sp(Engine& e, const Op& op, const MfmaPlan& P, const MConv& a, 
     return rc == PSEG_OK ? sp_launched(e, st) : rc;
 }
 
-#define PSEG_PP(SG_, POOL_, RR_)                                                                      \
-    if (w.sigma == SG_ && (w.pool_dst != nullptr) == POOL_ && rr == RR_)                               \
-        return launch_lds<conv_pp_kernel<SG_, POOL_, RR_>>(w, grid, 768, lds, dev, st);
+#define PSEG_PP(SG_, POOL_, RR_, P8_)                                                                 \
+    if (w.sigma == SG_ && (w.pool_dst != nullptr) == POOL_ && rr == RR_ && (w.wpk_pair != nullptr) == P8_) \
+        return launch_lds<conv_pp_kernel<SG_, POOL_, RR_, P8_>>(w, grid, 768, lds, dev, st);
 static int pp_run(const MConv& w, bool rr, dim3 grid, int lds, int dev, hipStream_t st) {
-    PSEG_PP(4, false, true) PSEG_PP(4, true, true)
-    PSEG_PP(4, false, false) PSEG_PP(4, true, false) PSEG_PP(5, false, false) PSEG_PP(5, true, false)
+    PSEG_PP(4, false, true, true) PSEG_PP(4, true, true, true)
+    PSEG_PP(4, false, true, false) PSEG_PP(4, true, true, false)
+    PSEG_PP(4, false, false, false) PSEG_PP(4, true, false, false) PSEG_PP(5, false, false, false) PSEG_PP(5, true, false, false)
     return ROUTE_NO;
 }
 #undef PSEG_PP
 
 // ping-pong persistent kernel for the k5 mid layers whose weights fit LDS beside two tiles: conv3, conv4
-static int route_pp(const MfmaPlan& P, const MConv& a, const Extent& x, hipStream_t st) {
+static int route_pp(const Op& op, const MfmaPlan& P, const MConv& a, const Extent& x, hipStream_t st) {
     int lds = 0;
-    if (!P.pp || !pp_pays(P, x, &lds)) return ROUTE_NO;
+    bool pair = false;
+    if (!P.pp || !pp_pays(P, x, &lds, &pair)) return ROUTE_NO;
     MConv w = a;
     w.lds_w_off = tile_bytes(P);
     w.ntiles = x.tiles;
     if (PSEG_DIAG_KNOB("PSEG_PP_NODMA")) w.dbg |= 0x800;     // wrong results, timing only: diagnostic build only
     if (PSEG_DIAG_KNOB("PSEG_PP_NOEPI")) w.dbg |= 0x1000;
     const bool rr = P.rowreuse && P.ks_full == 25;           // conv3: the k-loop that keeps a wave's shared pixel fragments in registers
+    w.wpk_pair = (rr && pair) ? P.d_wpk_pair : nullptr;      // ... and shares one A fragment per tap between its two rows' left-over couts
+    if (PSEG_KNOB("PSEG_LOG_GENERIC"))
+        fprintf(stderr, "[pseg] pp launch %s: tiles %d rowreuse %d pair8 %d lds %d\n", op.layer.c_str(), x.tiles, rr ? 1 : 0, w.wpk_pair ? 1 : 0, lds);
     return pp_run(w, rr, dim3((unsigned)x.cus), lds, x.dev, st);
 }
 
@@ -5607,7 +5837,7 @@ int mfma_launch_conv(Engine& e, Op& op, hipStream_t st) {
     int rc;
     if ((rc = route_sp2(e, op, P, a, x, st)) != ROUTE_NO) return rc;
     if ((rc = route_sp(e, op, P, a, x, st)) != ROUTE_NO) return rc;
-    if ((rc = route_pp(P, a, x, st)) != ROUTE_NO) return rc;
+    if ((rc = route_pp(op, P, a, x, st)) != ROUTE_NO) return rc;
     if ((rc = route_ws(op, P, a, x, st)) != ROUTE_NO) return rc;
     if ((rc = route_triple(op, P, a, x, st)) != ROUTE_NO) return rc;
     return route_mfma(op, P, a, grid, x, st);
