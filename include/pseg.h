@@ -842,6 +842,54 @@ int pseg_label_masks_geometry(int* run, int* runs, int* rows, int* group_masks, 
 /* group_of[i]: the group pseg_label_masks puts mask i into (only H0, W0 and channels are read; host arithmetic, no device). */
 int pseg_label_masks_groups(int n, const pseg_mask_src* masks, int* group_of);
 
+/* ---- Despeckling of ink maps on the device ---------------------------------------------------------------- */
+
+/* How an ink map is despeckled: every ink component (connectivity 4 or 8) of at most max_area pixels becomes paper.
+ * 1 <= max_area <= 16 777 216.  max_area == 0: the map is not despeckled (connectivity is not read). */
+typedef struct pseg_despeckle {
+    int max_area;
+    int connectivity;
+} pseg_despeckle;
+
+/* n ink maps (ink[i]: uint8 H[i] x W[i], dense, non-zero = ink) without their specks, in one device-resident call.  For a map with
+ * max_area >= 1, integer-exact:
+ *   lab, k = scipy.ndimage.label(ink != 0, structure)          (the cross for connectivity 4, 3 x 3 ones for 8)
+ *   size   = bincount(lab);   out = (lab > 0) & (size[lab] > max_area)          as uint8: kept ink is 1, everything else 0
+ * so the operation is idempotent.  A map with max_area == 0 is copied to out[i] byte for byte and causes no device work.
+ * out[i] may be ink[i].  out_counts (may be NULL): n x 3 int64: the components erased, the pixels erased, the components kept
+ * (zeros for a map that is not despeckled).
+ * Host pointers, synchronous.  The list is cut into groups as pseg_binarize_scans cuts it (64 maps, or 64 MiB of map bytes); a group
+ * costs four ragged launches (five where both connectivities occur in it) and ONE host wait, nothing is allocated per map.  The
+ * workspace (per pixel the map's byte; per 32 x 64 tile the bytes pseg_despeckle_geometry's constants imply: root slots with parent
+ * and size, rim table, task list, run list) is grow-only, cached per device with its own stream and freed by pseg_release_workspace.
+ * n == 0 returns PSEG_OK before a device is touched.  Every map is checked before any device work and the message names it
+ * ("map 3: ..."): max_area outside 0 .. 16 777 216, a connectivity other than 4 or 8, a NULL pointer or an empty shape is
+ * PSEG_EINVAL, a map of 2^31 pixels or more PSEG_EUNSUPPORTED; nothing is written to the outputs then.  An output is written only
+ * by a group that ran. */
+int pseg_despeckle_maps(int device, int n, const uint8_t* const* ink, const int* H, const int* W, const pseg_despeckle* how,
+                        uint8_t* const* out, int64_t* out_counts);
+/* The same on the host, without a device: a two-pass union-find over the whole page (not the tile scheme), the same bytes and counts. */
+int pseg_despeckle_maps_host(int n, const uint8_t* const* ink, const int* H, const int* W, const pseg_despeckle* how,
+                             uint8_t* const* out, int64_t* out_counts);
+/* pseg_prepare_scans_bin with the despeckling of scan i given by dsp[i]: equals pseg_prepare_images(scan, where(clean, 0, 255)) with
+ * clean = pseg_despeckle_maps of the scan's ink map (pseg_binarize_scans' for an adaptive entry, scan <= 127 else), bit for bit.
+ * dsp == NULL, or max_area == 0, is pseg_prepare_scans_bin's own path and bytes.  With a despeckle entry the scan-sized ink plane is
+ * always materialised (for a fixed threshold the statistics pass writes it), the despeckle launches run on it in front of the
+ * sampler, which gathers from it; the plane and the per-tile workspace are part of the staging, sized up front: no allocation,
+ * read-back or wait enters the front end.  how and dsp are checked for every scan before any device work ("scan 3: ..."). */
+int pseg_prepare_scans_clean(int device, int n, const pseg_scan* scans, const pseg_binarize* how, const pseg_despeckle* dsp,
+                             uint8_t* const* out_img, uint8_t* const* out_bin, uint8_t* const* out_orig);
+/* pseg_predict_chain_scans_bin_png with the despeckling of scan i given by dsp[i] (NULL, or max_area == 0: that call's own path): the
+ * ink map that the vote, the masks and the final_is_scan route work on is the despeckled one (on that route the plane is the unit's
+ * binarisation block itself).  A call that needs no ink map -- neither masks nor a vote -- launches nothing for it. */
+int pseg_predict_chain_scans_clean_png(pseg_engine* e, int n_scans, const pseg_scan* scans, const pseg_binarize* how,
+                                       const pseg_despeckle* dsp, const int* post_ops, int n_post, unsigned flags,
+                                       const uint8_t* lut, int n_lut, int level, unsigned want, int unit_cap,
+                                       pseg_chain_sink sink, void* user);
+/* The geometry the device kernels were compiled with (host arithmetic, no device; every pointer may be NULL): a workgroup labels a
+ * *tile_h x *tile_w tile; a tile has *slots root slots for the components that reach across its edge and lists at most *run_cap runs. */
+int pseg_despeckle_geometry(int* tile_h, int* tile_w, int* slots, int* run_cap);
+
 #ifdef __cplusplus
 }
 #endif

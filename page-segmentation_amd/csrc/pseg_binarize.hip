@@ -22,8 +22,6 @@ constexpr int BZ_NTH = 256, BZ_EPT = 8, BZ_CAP = BZ_NTH * BZ_EPT;      // row ke
 constexpr int BZ_BAND = 64, BZ_CT = 64;                                // column kernel: rows per band, columns per workgroup (one wave)
 static_assert(BZ_CAP <= BZ_PACK_MAX, "a segment's prefix fits the packed word");
 static_assert(BZ_CAP - (BZ_WINDOW_MAX - 1) > 0 && (BZ_CAP % 2) == 0, "a segment owns an even, positive number of columns at every window");
-constexpr int BZ_GROUP_SCANS = 64;                                     // how pseg_binarize_scans cuts its list (include/pseg.h)
-constexpr size_t BZ_GROUP_BYTES = (size_t)64 << 20;
 
 // one scan: geometry, parameters, planes (device pointers) and the prefix tables of the ragged launches
 struct BzScan {
@@ -199,6 +197,7 @@ void binarize_release_workspace(int dev) {
     std::lock_guard<std::mutex> lk(g_bz_mu[dev & 63]);
     g_bz_ws[dev & 63].dev.release();
     g_bz_ws[dev & 63].pin.release();
+    despeckle_release_workspace(dev);                                  // the stage behind the binarisation (pseg_despeckle.hip): its own lock
 }
 
 static int bz_group(BzWs& ws, int g0, int g1, const uint8_t* const* gray, const int* H, const int* W, const pseg_binarize* how,
@@ -325,12 +324,7 @@ int pseg_binarize_scans(int device, int n, const uint8_t* const* gray, const int
     PSEG_HIP(hipSetDevice(device));
     std::lock_guard<std::mutex> lk(g_bz_mu[device & 63]);
     for (int g0 = 0; g0 < n;) {
-        int g1 = g0;
-        size_t bytes = 0;
-        while (g1 < n && g1 - g0 < BZ_GROUP_SCANS && (g1 == g0 || bytes + (size_t)H[g1] * W[g1] <= BZ_GROUP_BYTES)) {
-            bytes += (size_t)H[g1] * W[g1];
-            ++g1;
-        }
+        const int g1 = binarize_group_end(n, H, W, g0);
         PSEG_TRY(bz_group(g_bz_ws[device & 63], g0, g1, gray, H, W, how, out_ink, out_threshold));
         g0 = g1;
     }

@@ -335,7 +335,8 @@ struct ChainPlan {
 // The pass that ends the plan: every block of every page lies inside its mx[], the offsets that kernels and DMA rely on are aligned
 // (or dense: same-shape pages go up in one DMA, same-shape page slots write their maps one behind the other), the units tile the list
 // and the final maps are where chain_post_enqueue's walk will leave them.  O(n); a violation is a bug of the planner.
-static int chain_plan_check(const ChainPlan& p, const std::vector<ChainReq>& req, const pseg_scan* scans, const pseg_binarize* how, const int* post_ops, int n_post) {
+static int chain_plan_check(const ChainPlan& p, const std::vector<ChainReq>& req, const pseg_scan* scans, const pseg_binarize* how, const pseg_despeckle* dsp,
+                            const int* post_ops, int n_post) {
     typedef PagesSet B;
     std::vector<char> seen(p.n, 0);
     int next = 0;
@@ -365,7 +366,7 @@ static int chain_plan_check(const ChainPlan& p, const std::vector<ChainReq>& req
             if (scans) {
                 const size_t sb = (size_t)scans[pi].H0 * scans[pi].W0;
                 ok = ok && p.scan_off[i] % 256 == 0 && p.scan_off[i] + sb <= p.mx[B::SCAN] && p.filt_off[i] % 16 == 0 &&
-                     p.filt_off[i] + scan_front_work(scans[pi], binarize_of(how, pi)) <= p.mx[B::FILT] && p.wt_off[i] + scan_front_weights(scans[pi], nullptr) <= p.n_wt;
+                     p.filt_off[i] + scan_front_work(scans[pi], binarize_of(how, pi), despeckle_of(dsp, pi)) <= p.mx[B::FILT] && p.wt_off[i] + scan_front_weights(scans[pi], nullptr) <= p.n_wt;
                 in_b += sb;
             } else in_b += npx * p.in_ch + (req[pi].need_bin ? nl : 0);
             if (!ok) return fail(PSEG_EHIP, "page chain plan: page %d does not lie inside its staging blocks", pi);
@@ -381,7 +382,8 @@ static int chain_plan_check(const ChainPlan& p, const std::vector<ChainReq>& req
 // No HIP call.  mixed = false: units are runs of same-shape pages in list order (pseg_chain_units); mixed = true: pages of one canvas
 // (pseg_chain_units_mixed).  scans != NULL: a scan call (mixed), whose pages and ink maps the front end writes on the device.
 static int chain_pages_plan(int n, const int* H, const int* W, const int* Ho, const int* Wo, const std::vector<ChainReq>& req, const pseg_scan* scans,
-                            const pseg_binarize* how, const int* post_ops, int n_post, int in_ch, int cap, bool page_slots, bool mixed, int level, int nout, ChainPlan* out) {
+                            const pseg_binarize* how, const pseg_despeckle* dsp, const int* post_ops, int n_post, int in_ch, int cap, bool page_slots, bool mixed,
+                            int level, int nout, ChainPlan* out) {
     typedef PagesSet B;
     ChainPlan& p = *out;
     p.mixed = mixed;
@@ -426,7 +428,7 @@ static int chain_pages_plan(int n, const int* H, const int* W, const int* Ho, co
                 p.filt_off[i] = o_filt;
                 p.wt_off[i] = p.n_wt;
                 o_scan += up256((size_t)scans[pi].H0 * scans[pi].W0);
-                o_filt += scan_front_work(scans[pi], binarize_of(how, pi));
+                o_filt += scan_front_work(scans[pi], binarize_of(how, pi), despeckle_of(dsp, pi));
                 p.n_wt += scan_front_weights(scans[pi], nullptr);
             }
             const int where = chain_final_slot(req[pi].resize, post_ops, n_post);      // the page's final map, ahead of time
@@ -444,7 +446,7 @@ static int chain_pages_plan(int n, const int* H, const int* W, const int* Ho, co
         p.mx_in = std::max(p.mx_in, in_b);
         p.mx_tot = std::max(p.mx_tot, (size_t)g * 4 * sizeof(unsigned long long));
     }
-    return chain_plan_check(p, req, scans, how, post_ops, n_post);
+    return chain_plan_check(p, req, scans, how, dsp, post_ops, n_post);
 }
 
 // Both sets sized for the largest unit while they are idle (a call ends drained; the page-locked stream staging alone grows while the call runs,
@@ -484,7 +486,7 @@ struct PagesRun {
     const ChainPlan& p;
     ChainPagesState& ps;
     const std::vector<ChainReq>& req;
-    const uint8_t* const* imgs; const uint8_t* const* binaries; const pseg_scan* scans; const pseg_binarize* how;
+    const uint8_t* const* imgs; const uint8_t* const* binaries; const pseg_scan* scans; const pseg_binarize* how; const pseg_despeckle* dsp;
     const int* post_ops; int n_post; bool exact;
     const uint8_t* lut; int n_lut, level, nout; const int* mask_id; bool want_lab;      // lut NULL: no masks
     pseg_chain_sink sink; void* user;
@@ -567,7 +569,7 @@ struct PagesRun {
             const bool hi = scans[pi].final_is_scan != 0;
             PSEG_TRY(scan_front_enqueue(scans[pi], s.d[B::SCAN].p + p.scan_off[i], ps.d_wt.p ? (double*)ps.d_wt.p + p.wt_off[i] : nullptr,
                                         s.d[B::FILT].p ? s.d[B::FILT].p + p.filt_off[i] : nullptr, (unsigned*)s.d[B::REC].p + (size_t)(i - i0) * SCAN_REC_WORDS,
-                                        s.d[B::IMG].p + m.img_off, hi ? nullptr : ink, hi ? ink : nullptr, st, binarize_of(how, pi)));
+                                        s.d[B::IMG].p + m.img_off, hi ? nullptr : ink, hi ? ink : nullptr, st, binarize_of(how, pi), despeckle_of(dsp, pi)));
         }
         return PSEG_OK;
     }
@@ -691,7 +693,7 @@ struct PagesRun {
 static int chain_pages_run(pseg_engine* h, int n, const uint8_t* const* imgs, const int* H, const int* W, const int* Ho, const int* Wo,
                            const uint8_t* const* binaries, const int* post_ops, int n_post, unsigned flags, const uint8_t* lut, int n_lut, int level,
                            unsigned want, int unit_cap, pseg_chain_sink sink, void* user, const bool mixed, const pseg_scan* scans = nullptr,
-                           const pseg_binarize* how = nullptr) {
+                           const pseg_binarize* how = nullptr, const pseg_despeckle* dsp = nullptr) {
     if (!h) return fail(PSEG_EINVAL, "NULL engine");
     KnobScope knob_scope(h->e);
     Engine& e = h->e;
@@ -736,8 +738,8 @@ static int chain_pages_run(pseg_engine* h, int n, const uint8_t* const* imgs, co
         }
     } else if (!page_slots) cap = std::min(8, std::max(1, n / 4));       // (the encoder's launches still take a unit's pages together)
     ChainPlan plan;
-    PSEG_TRY(chain_pages_plan(n, H, W, Ho, Wo, req, scans, how, post_ops, n_post, e.in_ch, cap, page_slots, mixed, level, nout, &plan));
-    PagesRun run{h, plan, *c.pages, req, imgs, binaries, scans, how, post_ops, n_post, exact, want_png ? lut : nullptr, n_lut, level, nout, mask_id,
+    PSEG_TRY(chain_pages_plan(n, H, W, Ho, Wo, req, scans, how, dsp, post_ops, n_post, e.in_ch, cap, page_slots, mixed, level, nout, &plan));
+    PagesRun run{h, plan, *c.pages, req, imgs, binaries, scans, how, dsp, post_ops, n_post, exact, want_png ? lut : nullptr, n_lut, level, nout, mask_id,
                  (want & 16u) != 0, sink, user, s_in, e.stream, s_out, {}, {}};
     PSEG_TRY(run_pipeline(run, (int)plan.ub.size(), c.pages->ev, s_in, e.stream, s_out));
     return engine_status(e, e.stream);
@@ -765,6 +767,12 @@ extern "C" int pseg_predict_chain_scans_png(pseg_engine* h, int n, const pseg_sc
 extern "C" int pseg_predict_chain_scans_bin_png(pseg_engine* h, int n, const pseg_scan* scans, const pseg_binarize* how, const int* post_ops, int n_post,
                                                 unsigned flags, const uint8_t* lut, int n_lut, int level, unsigned want, int unit_cap,
                                                 pseg_chain_sink sink, void* user) {
+    return pseg_predict_chain_scans_clean_png(h, n, scans, how, nullptr, post_ops, n_post, flags, lut, n_lut, level, want, unit_cap, sink, user);
+}
+
+extern "C" int pseg_predict_chain_scans_clean_png(pseg_engine* h, int n, const pseg_scan* scans, const pseg_binarize* how, const pseg_despeckle* dsp,
+                                                  const int* post_ops, int n_post, unsigned flags, const uint8_t* lut, int n_lut, int level, unsigned want,
+                                                  int unit_cap, pseg_chain_sink sink, void* user) {
     if (n < 0 || (n > 0 && !scans)) return fail(PSEG_EINVAL, "bad argument");
     if (!sink) return fail(PSEG_EINVAL, "NULL sink");
     // every scan is checked before any device work starts; the pages' shapes then go through the page entries' checks
@@ -773,6 +781,7 @@ extern "C" int pseg_predict_chain_scans_bin_png(pseg_engine* h, int n, const pse
     for (int i = 0; i < n; ++i) {
         PSEG_TRY(scan_front_check(scans[i], i));
         if (how) PSEG_TRY(binarize_check(how[i], i));
+        if (dsp) PSEG_TRY(despeckle_check(dsp[i], i, "scan"));
         gray[i] = scans[i].gray;
         H[i] = scans[i].H;
         W[i] = scans[i].W;
@@ -780,5 +789,5 @@ extern "C" int pseg_predict_chain_scans_bin_png(pseg_engine* h, int n, const pse
         Wo[i] = scans[i].final_is_scan ? scans[i].W0 : 0;
     }
     return chain_pages_run(h, n, gray.data(), H.data(), W.data(), Ho.data(), Wo.data(), gray.data(), post_ops, n_post, flags, lut, n_lut, level, want,
-                           unit_cap, sink, user, true, scans, how);
+                           unit_cap, sink, user, true, scans, how, dsp);
 }

@@ -451,11 +451,14 @@ constexpr int SCAN_REC_WORDS = 16;
 // how: the scan's binarisation (NULL or window 0: ink = scan <= 127).  With an adaptive one the workspace grows by the row-sum plane
 // and -- unless final_is_scan, where d_orig is the destination -- the scan-sized ink plane, both behind the filtered planes; the
 // binarisation kernels write the ink map and the sampler gathers from it.  d_scan is readable up to the next multiple of 16 bytes.
+// dsp: the scan's despeckling (NULL or max_area 0: none).  With one the scan-sized ink plane is always materialised (a fixed
+// threshold's by the statistics pass), the workspace grows by that plane (unless final_is_scan) and, behind it, by
+// despeckle_work_bytes(H0, W0); the despeckle launches run on the plane in front of the sampler, which gathers from it.
 int scan_front_check(const pseg_scan& s, int index);
 size_t scan_front_weights(const pseg_scan& s, double* dst);
-size_t scan_front_work(const pseg_scan& s, const pseg_binarize* how = nullptr);
+size_t scan_front_work(const pseg_scan& s, const pseg_binarize* how = nullptr, const pseg_despeckle* dsp = nullptr);
 int scan_front_enqueue(const pseg_scan& s, const uint8_t* d_scan, const double* d_w, uint8_t* d_work, unsigned* d_rec, uint8_t* d_img,
-                       uint8_t* d_bin, uint8_t* d_orig, hipStream_t st, const pseg_binarize* how = nullptr);
+                       uint8_t* d_bin, uint8_t* d_orig, hipStream_t st, const pseg_binarize* how = nullptr, const pseg_despeckle* dsp = nullptr);
 // pseg_binarize.hip: binarize_check refuses a bad pseg_binarize ("scan <index>: ..."); binarize_rows_bytes is the row-sum plane of an
 // H x W scan (a multiple of 256); binarize_enqueue launches the two kernels of one scan on `st` without a wait: d_scan 16-byte
 // aligned and readable up to the next multiple of 16 bytes, d_rows 16-byte aligned, d_ink H x W, d_thr float64 H x W or NULL.
@@ -464,6 +467,19 @@ size_t binarize_rows_bytes(int H, int W);
 int binarize_enqueue(const uint8_t* d_scan, int H, int W, const pseg_binarize& how, uint8_t* d_rows, uint8_t* d_ink, double* d_thr, hipStream_t st);
 void binarize_release_workspace(int dev);   // the list entry's per-device workspace (pseg_release_workspace)
 void label_masks_release_workspace(int dev);   // pseg_labelmasks.hip: pseg_label_masks' per-device workspace (pseg_release_workspace)
+// pseg_despeckle.hip: despeckle_check refuses a bad pseg_despeckle ("map <index>: ..."); despeckle_tile_bytes is the workspace of one
+// 32 x 64 tile (root slots, rim table, task list, run list, list lengths); the per-device workspace and stream of pseg_despeckle_maps
+// are freed with the binarisation's (binarize_release_workspace, i.e. pseg_release_workspace).  For the scan chain's front end:
+// despeckle_work_bytes is the workspace of one H x W map (a multiple of 256: 256 bytes, then the per-tile arrays); despeckle_enqueue
+// launches the four kernels of one map on `st` without a wait, in place on d_ink (H x W, non-zero = ink; kept ink becomes 1); d_work
+// is 256-byte aligned.  max_area == 0: no launch.
+int despeckle_check(const pseg_despeckle& d, int index, const char* what = "map");
+size_t despeckle_tile_bytes();
+size_t despeckle_work_bytes(int H, int W);
+int despeckle_enqueue(uint8_t* d_ink, int H, int W, const pseg_despeckle& how, uint8_t* d_work, hipStream_t st);
+void despeckle_release_workspace(int dev);
+// the entry of a list that asks for a despeckling, or NULL
+inline const pseg_despeckle* despeckle_of(const pseg_despeckle* how, int i) { return how && how[i].max_area != 0 ? &how[i] : nullptr; }
 // the entry of a list that asks for an adaptive binarisation, or NULL
 inline const pseg_binarize* binarize_of(const pseg_binarize* how, int i) { return how && how[i].window != 0 ? &how[i] : nullptr; }
 // pseg_engine.hip, shared by pseg_predict_batch and the page chain

@@ -1279,15 +1279,19 @@ static size_t scan_filt_work(const pseg_scan& s) {
     return sf_up256((size_t)s.H0 * s.W0) * (!fused && rad[0] > 0 && rad[1] > 0 ? 2 : 1);
 }
 
-// behind them, for an adaptive binarisation: the row-sum plane, then the scan-sized ink plane unless d_orig takes it
-size_t scan_front_work(const pseg_scan& s, const pseg_binarize* how) {
+// behind them, for an adaptive binarisation: the row-sum plane; for that or a despeckling: the scan-sized ink plane unless d_orig takes
+// it; for a despeckling: its per-tile workspace
+size_t scan_front_work(const pseg_scan& s, const pseg_binarize* how, const pseg_despeckle* dsp) {
+    const bool adaptive = how && how->window != 0, clean = dsp && dsp->max_area != 0;
     size_t b = scan_filt_work(s);
-    if (how && how->window != 0) b += binarize_rows_bytes(s.H0, s.W0) + (s.final_is_scan ? 0 : sf_up256((size_t)s.H0 * s.W0));
+    if (adaptive) b += binarize_rows_bytes(s.H0, s.W0);
+    if ((adaptive || clean) && !s.final_is_scan) b += sf_up256((size_t)s.H0 * s.W0);
+    if (clean) b += despeckle_work_bytes(s.H0, s.W0);
     return b;
 }
 
 int scan_front_enqueue(const pseg_scan& s, const uint8_t* d_scan, const double* d_w, uint8_t* d_work, unsigned* d_rec, uint8_t* d_img,
-                       uint8_t* d_bin, uint8_t* d_orig, hipStream_t st, const pseg_binarize* how) {
+                       uint8_t* d_bin, uint8_t* d_orig, hipStream_t st, const pseg_binarize* how, const pseg_despeckle* dsp) {
     const int H0 = s.H0, W0 = s.W0;
     const size_t n0 = (size_t)H0 * W0;
     double sig[2];
@@ -1295,16 +1299,25 @@ int scan_front_enqueue(const pseg_scan& s, const uint8_t* d_scan, const double* 
     scan_radii(s, sig, rad);
     const int sgrid = (int)std::min<size_t>((n0 / 16 + 255) / 256 + 1, 1024);
     // an adaptive ink map: into d_orig where that is asked for, else (for the sampler's gather alone) into the workspace
-    const uint8_t* d_ink = nullptr;
-    if (how && how->window != 0 && (d_bin || d_orig)) {
+    // a despeckling: the ink plane is materialised whatever the threshold (a fixed one's by the statistics pass) and cleaned in place
+    uint8_t* d_ink = nullptr;
+    const bool adaptive = how && how->window != 0, clean = dsp && dsp->max_area != 0;
+    uint8_t* stats_orig = d_orig;
+    if ((adaptive || clean) && (d_bin || d_orig)) {
         if (!d_work) return fail(PSEG_EINVAL, "scan front end: no workspace for the binarisation");
         uint8_t* const rows = d_work + scan_filt_work(s);
-        uint8_t* const ink = d_orig ? d_orig : rows + binarize_rows_bytes(H0, W0);
+        uint8_t* const plane = rows + (adaptive ? binarize_rows_bytes(H0, W0) : 0);
+        uint8_t* const ink = d_orig ? d_orig : plane;
         if (!d_orig && s.final_is_scan) return fail(PSEG_EINVAL, "scan front end: no ink plane in the workspace of a final_is_scan scan");
-        PSEG_TRY(binarize_enqueue(d_scan, H0, W0, *how, rows, ink, nullptr, st));
+        if (adaptive) PSEG_TRY(binarize_enqueue(d_scan, H0, W0, *how, rows, ink, nullptr, st));
+        stats_orig = adaptive ? nullptr : ink;
         d_ink = ink;
     }
-    scan_stats_kernel<<<sgrid, 256, 0, st>>>(d_scan, n0, d_rec, d_ink ? nullptr : d_orig);
+    scan_stats_kernel<<<sgrid, 256, 0, st>>>(d_scan, n0, d_rec, stats_orig);
+    if (clean && d_ink) {
+        uint8_t* const dwork = d_work + scan_filt_work(s) + (adaptive ? binarize_rows_bytes(H0, W0) : 0) + (s.final_is_scan ? 0 : sf_up256(n0));
+        PSEG_TRY(despeckle_enqueue(d_ink, H0, W0, *dsp, dwork, st));
+    }
     const uint8_t* plane = d_scan;
     const unsigned* bm = d_rec;
     if (rad[0] > 0 || rad[1] > 0) {
@@ -1345,6 +1358,11 @@ extern "C" int pseg_prepare_scans(int device, int n, const pseg_scan* scans, uin
 
 extern "C" int pseg_prepare_scans_bin(int device, int n, const pseg_scan* scans, const pseg_binarize* how, uint8_t* const* out_img,
                                       uint8_t* const* out_bin, uint8_t* const* out_orig) {
+    return pseg_prepare_scans_clean(device, n, scans, how, nullptr, out_img, out_bin, out_orig);
+}
+
+extern "C" int pseg_prepare_scans_clean(int device, int n, const pseg_scan* scans, const pseg_binarize* how, const pseg_despeckle* dsp,
+                                        uint8_t* const* out_img, uint8_t* const* out_bin, uint8_t* const* out_orig) {
     if (n < 0 || (n > 0 && (!scans || !out_img || !out_bin))) return fail(PSEG_EINVAL, "bad argument");
     // every scan is checked, and the staging laid out, before any device work starts
     struct At { size_t scan, work, w, img; };
@@ -1353,12 +1371,13 @@ extern "C" int pseg_prepare_scans_bin(int device, int n, const pseg_scan* scans,
     for (int i = 0; i < n; ++i) {
         PSEG_TRY(scan_front_check(scans[i], i));
         if (how) PSEG_TRY(binarize_check(how[i], i));
+        if (dsp) PSEG_TRY(despeckle_check(dsp[i], i, "scan"));
         if (!out_img[i] || !out_bin[i]) return fail(PSEG_EINVAL, "scan %d: NULL argument", i);
         at[i] = At{b_scan, b_work, n_w, b_img};
         b_scan += sf_up256((size_t)scans[i].H0 * scans[i].W0);
         pseg_scan alone = scans[i];                             // (final_is_scan is the chain's: here the ink plane may have no other home)
         alone.final_is_scan = 0;
-        b_work += scan_front_work(alone, binarize_of(how, i));
+        b_work += scan_front_work(alone, binarize_of(how, i), despeckle_of(dsp, i));
         n_w += scan_front_weights(scans[i], nullptr);
         b_img += sf_up256((size_t)scans[i].H * scans[i].W);
     }
@@ -1388,7 +1407,7 @@ extern "C" int pseg_prepare_scans_bin(int device, int n, const pseg_scan* scans,
         uint8_t* const orig = out_orig && out_orig[i] ? d_orig + at[i].scan : nullptr;
         PSEG_HIP(hipMemcpyAsync(d_scan + at[i].scan, s.gray, n0, hipMemcpyHostToDevice, st));
         PSEG_TRY(scan_front_enqueue(s, d_scan + at[i].scan, d_w + at[i].w, d_work + at[i].work, d_rec + (size_t)i * SCAN_REC_WORDS,
-                                    d_img + at[i].img, d_bin + at[i].img, orig, st, binarize_of(how, i)));
+                                    d_img + at[i].img, d_bin + at[i].img, orig, st, binarize_of(how, i), despeckle_of(dsp, i)));
         PSEG_HIP(hipMemcpyAsync(out_img[i], d_img + at[i].img, n1, hipMemcpyDeviceToHost, st));
         PSEG_HIP(hipMemcpyAsync(out_bin[i], d_bin + at[i].img, n1, hipMemcpyDeviceToHost, st));
         if (orig) PSEG_HIP(hipMemcpyAsync(out_orig[i], orig, n0, hipMemcpyDeviceToHost, st));

@@ -111,21 +111,39 @@ def _binarize_gray(gray, binarize, line_height_px):
     return np.where(ink != 0, 0, 255).astype(np.uint8)
 
 
+def check_despeckle(despeckle):
+    """despeckle=None (the ink map as the threshold leaves it) or a pseg_amd.Despeckle; anything else raises."""
+    from pseg_amd import engine as _eng
+    if despeckle is not None and not isinstance(despeckle, _eng.Despeckle):
+        raise Exception(f"despeckle must be None or a pseg_amd.Despeckle, got {despeckle!r}")
+    return despeckle
+
+
+def _despeckle_binary(bin_, despeckle, line_height_px):
+    """A 0 / 255 map (paper = 255) without its specks: where(clean, 0, 255) of pseg_amd.despeckle_maps of the one ink map, a
+    max_area=None resolved from the entry's line height."""
+    from pseg_amd import engine as _eng
+    clean = _eng.despeckle_maps([bin_ == 0], despeckle.resolved(line_height_px))[0]
+    return np.where(clean != 0, 0, 255).astype(np.uint8)
+
+
 class DatasetLoader:
-    def __init__(self, target_line_height, color_map: ColorMap, prediction=False, max_width=None, binarize=None):
+    def __init__(self, target_line_height, color_map: ColorMap, prediction=False, max_width=None, binarize=None, despeckle=None):
         self.target_line_height = target_line_height
         self.prediction = prediction
         self.color_map = color_map
         self.max_width = max_width
         self.binarize = check_binarize(binarize)    # None: > 127 (imread_bin); a pseg_amd.Sauvola: the adaptive ink map on the device
+        self.despeckle = check_despeckle(despeckle)  # None, or a pseg_amd.Despeckle: the ink map derived from the scan loses its specks
 
     def load_images(self, entry: SingleData) -> SingleData:
         """lib/dataset.py:160-191.  The reference derives the binary from the *image* attribute /
         path (attr 'image', :172) and never reads binary_path; kept.  With a binarize, the adaptive map of the gray scan takes
-        _imread_bin's place: the records carry the ink map the scan chain works on."""
-        return self._load_images(entry, self.binarize)
+        _imread_bin's place: the records carry the ink map the scan chain works on.  With a despeckle, the ink map derived from the
+        scan's file (either way) loses its specks first; a pre-loaded entry.image, which is its own binary, is left as it is."""
+        return self._load_images(entry, self.binarize, getattr(self, "despeckle", None))
 
-    def _load_images(self, entry: SingleData, binarize) -> SingleData:
+    def _load_images(self, entry: SingleData, binarize, despeckle=None) -> SingleData:
         img = entry.image if entry.image is not None else _imread_gray(entry.image_path)
         original_shape = img.shape
         if entry.image is not None:
@@ -134,6 +152,8 @@ class DatasetLoader:
             bin_ = _binarize_gray(img, binarize, entry.line_height_px)
         else:
             bin_ = _imread_bin(entry.image_path)
+        if despeckle is not None and entry.image is None:
+            bin_ = _despeckle_binary(bin_, despeckle, entry.line_height_px)
         img, bin_, orig_bin = prepare_images(img, bin_, self.target_line_height, entry.line_height_px,
                                              self.max_width, keep_orig_bin=True)
         if not self.prediction:
@@ -169,8 +189,8 @@ class DatasetLoader:
         binary, orig_binary, mask, original_shape, dtypes included), the entries modified in place as load_images modifies them.
         Per chunk of `chunk` entries: every scan is decoded ONCE (_imread_gray) and every mask file with PIL's convert("RGB"), by
         decode_threads pool threads that work on the next chunk while the device works on this one; ONE engine.prepare_scans call
-        gives page, ink map and scan-sized ink map (self.binarize as in load_images, a window=None resolved from the entry's line
-        height); ONE engine.label_masks call turns the decoded masks into label maps of the pages' shapes (skipped under
+        gives page, ink map and scan-sized ink map (self.binarize and self.despeckle as in load_images, a window=None or
+        max_area=None resolved from the entry's line height); ONE engine.label_masks call turns the decoded masks into label maps of the pages' shapes (skipped under
         self.prediction).  A pre-loaded entry.mask of uint8 / bool ids stays on this route as a 1-channel source.
         An entry whose line_height_px is None is measured in one engine.char_heights call over the chunk's decoded scans and the
         height is stored into the entry (Predictor.write_masks_scans does the same); a scan without a measurable height raises
@@ -237,6 +257,8 @@ class DatasetLoader:
                 if on_device:
                     # (the keyword goes only with a binarisation, as in write_masks_scans)
                     how = {} if self.binarize is None else {"binarize": [self.binarize.resolved(part[k].line_height_px) for k, _ in on_device]}
+                    if getattr(self, "despeckle", None) is not None:
+                        how["despeckle"] = [self.despeckle.resolved(part[k].line_height_px) for k, _ in on_device]
                     pages = _eng.prepare_scans([scans[k] for k, _ in on_device], [sc for _, sc in on_device], **how)
                     labels = [None] * len(on_device)
                     if not self.prediction:

@@ -269,7 +269,8 @@ class Predictor:
         return (entry.image is None and entry.image_path is not None and output.DEVICE_PNG and output.is_png_target(path)
                 and self._chain_ops() is not None and net.n_classes <= 256 and not getattr(net, "_rgb", False))
 
-    def write_masks_scans(self, entries, loader, output_dir=None, level=None, chunk_pages=64, decode_threads=2, decode="host", binarize=None):
+    def write_masks_scans(self, entries, loader, output_dir=None, level=None, chunk_pages=64, decode_threads=2, decode="host", binarize=None,
+                          despeckle=None):
         """loader.load_images + write_masks_dataset for entries that name their scan by image_path, without the normalised page, the
         binarisation or the label map visiting the host: the decoded gray scans go through Engine.predict_chain_scans chunk_pages at
         a time (binarisation and line-height normalisation on the device, then the page chain), and each PNG stream is written to
@@ -294,11 +295,16 @@ class Predictor:
         binarize: None (ink = scan <= 127) or a pseg_amd.Sauvola: the adaptive ink map, made on the device inside the chain, is what
         the vote and the masks work on -- the files of DatasetLoader(binarize=...).load_images + write_masks_dataset.  A window=None
         takes pseg_amd.sauvola_window of the entry's line height, the measured one for entries measured here; the fallback route
-        loads the entry with the same binarisation."""
+        loads the entry with the same binarisation.
+        despeckle: None or a pseg_amd.Despeckle: the ink map (of either threshold) loses every component of at most max_area pixels
+        on the device inside the chain, in front of the sampler -- the files of DatasetLoader(despeckle=...).load_images +
+        write_masks_dataset.  A max_area=None takes pseg_amd.despeckle_area of the entry's line height, the measured one for
+        entries measured here; the fallback route loads the entry with the same despeckling."""
         if decode not in ("host", "device"):
             raise Exception(f"decode must be 'host' or 'device', got {decode!r}")
-        from .dataset import check_binarize
+        from .dataset import check_binarize, check_despeckle
         check_binarize(binarize)
+        check_despeckle(despeckle)
         from concurrent.futures import ThreadPoolExecutor
         from pseg_amd import engine as _eng
         from . import dataset as _ds
@@ -384,13 +390,18 @@ class Predictor:
                             f.write(stream)
                     # (the keyword goes only with a binarisation: today's call is unchanged)
                     how = {} if binarize is None else {"binarize": [binarize.resolved(chunk[k].line_height_px) for k in on_device]}
+                    if despeckle is not None:
+                        how["despeckle"] = [despeckle.resolved(chunk[k].line_height_px) for k in on_device]
                     self.network.model.predict_chain_scans(
                         [scans[k][0] for k in on_device], [scans[k][1] for k in on_device], high_res=high_res,
                         post_ops=self._chain_ops(), exact_labels=self.network.exact == "labels", lut=self.settings.color_map.lut(),
                         which=names, png_level=level, sink=to_file, **how)
                 for k in range(stop):
                     if scans[k] is None:
-                        loaded = loader.load_images(chunk[k]) if binarize is None else loader._load_images(chunk[k], binarize)
+                        if despeckle is not None:
+                            loaded = loader._load_images(chunk[k], binarize if binarize is not None else getattr(loader, "binarize", None), despeckle)
+                        else:
+                            loaded = loader.load_images(chunk[k]) if binarize is None else loader._load_images(chunk[k], binarize)
                         self.write_masks(loaded, output_dir=output_dir, level=level)
                     yield paths[k]
                 if failed is not None:

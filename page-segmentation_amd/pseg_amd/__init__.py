@@ -8,5 +8,6 @@ from .engine import (  # noqa: F401
     png_probe, png_decode_gray, PNG_OK, PNG_EINVAL, PNG_EUNSUPPORTED,
     Sauvola, sauvola_window, binarize_scans,
     label_masks, label_masks_geometry, label_mask_groups,
+    Despeckle, despeckle_area, despeckle_maps, despeckle_geometry,
 )
 from .build import build_library  # noqa: F401

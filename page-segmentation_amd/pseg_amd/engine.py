@@ -34,6 +34,7 @@ EXPORTED_SYMBOLS = (
     "pseg_predict_chain_pages_mixed_png", "pseg_chain_units_mixed", "pseg_predict_chain_scans_png", "pseg_prepare_scans",
     "pseg_binarize_scans", "pseg_binarize_scans_host", "pseg_binarize_geometry", "pseg_prepare_scans_bin", "pseg_predict_chain_scans_bin_png",
     "pseg_label_masks", "pseg_label_masks_host", "pseg_label_masks_geometry", "pseg_label_masks_groups",
+    "pseg_despeckle_maps", "pseg_despeckle_maps_host", "pseg_despeckle_geometry", "pseg_prepare_scans_clean", "pseg_predict_chain_scans_clean_png",
     "pseg_rescale_shape", "pseg_gaussian_kernel", "pseg_resize_nearest", "pseg_resize_nearest_device", "pseg_scale_image",
     "pseg_prepare_images", "pseg_affine_warp", "pseg_affine_warp_fill", "pseg_brightness_shift",
     "pseg_eval_confusion", "pseg_cc_label", "pseg_cc_tables", "pseg_eval_pages", "pseg_eval_page_groups",
@@ -57,6 +58,11 @@ class SCAN(ctypes.Structure):
 class BINARIZE(ctypes.Structure):
     """pseg_binarize: how a scan becomes its ink map (window 0: scan <= 127; else Sauvola over an odd window)."""
     _fields_ = [("window", ctypes.c_int), ("k", ctypes.c_double), ("R", ctypes.c_double)]
+
+
+class DESPECKLE(ctypes.Structure):
+    """pseg_despeckle: how an ink map loses its specks (max_area 0: not at all; else components of at most max_area pixels)."""
+    _fields_ = [("max_area", ctypes.c_int), ("connectivity", ctypes.c_int)]
 
 
 class MASK_SRC(ctypes.Structure):
@@ -205,6 +211,12 @@ def lib():
     L.pseg_binarize_scans.argtypes = [i, i, vp, vp, vp, c.POINTER(BINARIZE), vp, vp]
     L.pseg_binarize_scans_host.argtypes = [i, vp, vp, vp, c.POINTER(BINARIZE), vp, vp]
     L.pseg_binarize_geometry.argtypes = [c.POINTER(i)] * 4
+    L.pseg_despeckle_maps.argtypes = [i, i, vp, vp, vp, c.POINTER(DESPECKLE), vp, vp]
+    L.pseg_despeckle_maps_host.argtypes = [i, vp, vp, vp, c.POINTER(DESPECKLE), vp, vp]
+    L.pseg_despeckle_geometry.argtypes = [c.POINTER(i)] * 4
+    L.pseg_prepare_scans_clean.argtypes = [i, i, c.POINTER(SCAN), c.POINTER(BINARIZE), c.POINTER(DESPECKLE), vp, vp, vp]
+    L.pseg_predict_chain_scans_clean_png.argtypes = [vp, i, c.POINTER(SCAN), c.POINTER(BINARIZE), c.POINTER(DESPECKLE), c.POINTER(i), i, c.c_uint, vp, i, i,
+                                                     c.c_uint, i, CHAIN_SINK, vp]
     L.pseg_prepare_scans_bin.argtypes = [i, i, c.POINTER(SCAN), c.POINTER(BINARIZE), vp, vp, vp]
     L.pseg_predict_chain_scans_bin_png.argtypes = [vp, i, c.POINTER(SCAN), c.POINTER(BINARIZE), c.POINTER(i), i, c.c_uint, vp, i, i, c.c_uint, i, CHAIN_SINK, vp]
     L.pseg_label_masks.argtypes = [i, i, c.POINTER(MASK_SRC), vp, vp, vp, vp, i, vp, vp]
@@ -627,7 +639,8 @@ class Engine:
         return collected
 
     def predict_chain_scans(self, scans, scales, high_res=False, post_ops=(), exact_labels=False, lut=None,
-                            which=("color", "overlay", "inverted"), labels=False, png_level=0, unit_cap=0, sink=None, binarize=None):
+                            which=("color", "overlay", "inverted"), labels=False, png_level=0, unit_cap=0, sink=None, binarize=None,
+                            despeckle=None):
         """Scans as they come off disk through the chain to PNG streams (pseg_predict_chain_scans_png): scans[i] a gray uint8 (H0,W0)
         array, scales[i] = target_line_height / line_height_px.  The binarisation (ink = scan <= 127) and the line-height
         normalisation run on the device in front of the network: neither the normalised page nor the ink map visits the host.
@@ -636,7 +649,9 @@ class Engine:
         binarisation (PredictSettings.high_res_output).  Keywords, result dicts and the sink contract are predict_chain_pages'
         (mixed=True: a callable sink sees the planner's order).
         binarize: None (ink = scan <= 127), a Sauvola with a window, or one of either per scan (binarize_table): the ink map of
-        binarize_scans takes the place of scan <= 127 everywhere (pseg_predict_chain_scans_bin_png)."""
+        binarize_scans takes the place of scan <= 127 everywhere (pseg_predict_chain_scans_bin_png).
+        despeckle: None, a Despeckle with its max_area, or one of either per scan (despeckle_table): despeckle_maps of that ink map
+        takes its place everywhere (pseg_predict_chain_scans_clean_png); None is the call without the argument."""
         for w in which:
             if w not in MASK_NAMES:
                 raise PsegError("unknown mask %r (one of %r)" % (w, MASK_NAMES))
@@ -644,6 +659,12 @@ class Engine:
         n = len(plans)
         how = None if binarize is None else binarize_table(binarize, n)
         final = [keep[k].shape if high_res else plans[k][:2] for k in range(n)]
+        if despeckle is not None:
+            dsp = despeckle_table(despeckle, n, "scan")
+            return self._chain_list(final, post_ops, lut, which, labels, sink,
+                                    lambda ops, t, want, cb: lib().pseg_predict_chain_scans_clean_png(
+                                        self._h, n, table, how, dsp, ops, len(post_ops), 1 if exact_labels else 0, _ptr(t), 0 if t is None else t.shape[0],
+                                        int(png_level), want, int(unit_cap), cb, None))
         return self._chain_list(final, post_ops, lut, which, labels, sink,
                                 lambda ops, t, want, cb: lib().pseg_predict_chain_scans_bin_png(
                                     self._h, n, table, how, ops, len(post_ops), 1 if exact_labels else 0, _ptr(t), 0 if t is None else t.shape[0],
@@ -1175,16 +1196,21 @@ def scan_table(scans, scales, high_res=False):
     return table, arrs, plans
 
 
-def prepare_scans(scans, scales, device=0, binarize=None):
+def prepare_scans(scans, scales, device=0, binarize=None, despeckle=None):
     """prepare_images(scan, where(scan > 127, 255, 0), scale) for a list of gray scans in one call of the scan chain's front end
     (pseg_prepare_scans) -> [(img uint8, bin uint8, orig_bin uint8)], bit for bit.  binarize: None, a Sauvola with a window, or one of
     either per scan (binarize_table): prepare_images(scan, where(ink, 0, 255), scale) with ink from binarize_scans
-    (pseg_prepare_scans_bin)."""
+    (pseg_prepare_scans_bin).  despeckle: None, a Despeckle with its max_area, or one of either per scan (despeckle_table): the ink
+    map loses its specks first, prepare_images(scan, where(despeckle_maps(ink), 0, 255), scale) (pseg_prepare_scans_clean)."""
     table, arrs, plans = scan_table(scans, scales)
     n = len(arrs)
     how = None if binarize is None else binarize_table(binarize, n)
     out = [(np.empty(p[:2], np.uint8), np.empty(p[:2], np.uint8), np.empty(a.shape, np.uint8)) for a, p in zip(arrs, plans)]
     P = ctypes.c_void_p * max(n, 1)
+    if despeckle is not None:
+        dsp = despeckle_table(despeckle, n, "scan")
+        _check(lib().pseg_prepare_scans_clean(int(device), n, table, how, dsp, *[P(*[o[k].ctypes.data for o in out]) for k in range(3)]))
+        return out
     _check(lib().pseg_prepare_scans_bin(int(device), n, table, how, *[P(*[o[k].ctypes.data for o in out]) for k in range(3)]))
     return out
 
@@ -1277,6 +1303,97 @@ def binarize_scans(scans, how, device=0, thresholds=False, host=False):
             P(*[a.ctypes.data for a in inks]), None if thr is None else P(*[a.ctypes.data for a in thr]))
     _check(lib().pseg_binarize_scans_host(*args) if host else lib().pseg_binarize_scans(int(device), *args))
     return list(zip(inks, thr)) if thresholds else inks
+
+
+# ---- despeckling of ink maps (pseg_despeckle_maps) -------------------------------------------------------
+
+DESPECKLE_AREA_MAX = 1 << 24
+
+
+def despeckle_area(line_height_px):
+    """The max_area Despeckle(max_area=None) takes for a scan of this line height: the square of an eighth of the line height, at
+    least 1.  A convention (a full stop, about a fifth of the line height across, survives it), not a measured optimum.  Host
+    arithmetic."""
+    if line_height_px is None or not np.isfinite(line_height_px) or line_height_px <= 0:
+        raise PsegError("despeckle_area needs a positive line height, got %r" % (line_height_px,))
+    return max(1, int(round(line_height_px)) // 8) ** 2
+
+
+class Despeckle:
+    """Erase every ink component (connectivity 4 or 8) of at most max_area pixels, 1 .. 16 777 216 (include/pseg.h,
+    pseg_despeckle).  max_area=None: despeckle_area of the scan's line height, for the callers that know it (resolved)."""
+
+    def __init__(self, max_area=None, connectivity=8):
+        if max_area is not None:
+            if isinstance(max_area, bool) or int(max_area) != max_area:
+                raise PsegError("Despeckle: max_area must be an integer in 1..%d or None, got %r" % (DESPECKLE_AREA_MAX, max_area))
+            max_area = int(max_area)
+            if max_area < 1 or max_area > DESPECKLE_AREA_MAX:
+                raise PsegError("Despeckle: max_area must be an integer in 1..%d or None, got %r" % (DESPECKLE_AREA_MAX, max_area))
+        if isinstance(connectivity, bool) or connectivity not in (4, 8):
+            raise PsegError("Despeckle: connectivity must be 4 or 8, got %r" % (connectivity,))
+        self.max_area, self.connectivity = max_area, int(connectivity)
+
+    def resolved(self, line_height_px):
+        """This despeckling with its max_area fixed for a scan of the given line height."""
+        return self if self.max_area is not None else Despeckle(min(DESPECKLE_AREA_MAX, despeckle_area(line_height_px)), self.connectivity)
+
+    def __repr__(self):
+        return "Despeckle(max_area=%r, connectivity=%r)" % (self.max_area, self.connectivity)
+
+    def __eq__(self, other):
+        return isinstance(other, Despeckle) and (self.max_area, self.connectivity) == (other.max_area, other.connectivity)
+
+    def __hash__(self):
+        return hash((self.max_area, self.connectivity))
+
+
+def despeckle_geometry():
+    """(tile_h, tile_w, slots, run_cap) of pseg_despeckle_maps' kernels (pseg_despeckle_geometry; no device)."""
+    v = [ctypes.c_int() for _ in range(4)]
+    _check(lib().pseg_despeckle_geometry(*[ctypes.byref(x) for x in v]))
+    return tuple(x.value for x in v)
+
+
+def despeckle_table(how, n, what="map"):
+    """The pseg_despeckle array of n maps: how is a Despeckle for all of them, or a sequence with a Despeckle or None (the map is
+    not despeckled) per map.  Every Despeckle must have its max_area (Despeckle.resolved).  what: the word the messages use."""
+    entries = [how] * n if how is None or isinstance(how, Despeckle) else list(how)
+    if len(entries) != n:
+        raise PsegError("despeckle must have one entry per %s (%d for %d %ss)" % (what, len(entries), n, what))
+    table = (DESPECKLE * max(n, 1))()
+    for k, d in enumerate(entries):
+        if d is None:
+            table[k] = DESPECKLE(0, 8)
+            continue
+        if not isinstance(d, Despeckle):
+            raise PsegError("%s %d: despeckle takes None or a Despeckle, got %r" % (what, k, d))
+        if d.max_area is None:
+            raise PsegError("%s %d: Despeckle(max_area=None) needs the scan's line height: pass Despeckle.resolved(line_height_px)" % (what, k))
+        table[k] = DESPECKLE(d.max_area, d.connectivity)
+    return table
+
+
+def despeckle_maps(maps, how, device=0, counts=False, host=False):
+    """A list of ink maps (uint8, non-zero = ink) without their specks in one device-resident call (pseg_despeckle_maps): how is a
+    Despeckle or one per map (None: the map comes back as it is), see despeckle_table.  Kept ink is 1.  counts=True:
+    -> (maps, int64 (n, 3)) with the components erased, the pixels erased and the components kept of every map.  host=True: the
+    same bytes from the host entry (pseg_despeckle_maps_host), no device."""
+    ms = [np.ascontiguousarray(m, dtype=np.uint8) for m in maps]
+    for k, m in enumerate(ms):
+        if m.ndim != 2:
+            raise PsegError("map %d: an (H,W) ink map is expected, got shape %r" % (k, m.shape))
+    n = len(ms)
+    table = despeckle_table(how, n)
+    cnt = np.zeros((n, 3), np.int64)
+    if n == 0:
+        return ([], cnt) if counts else []
+    P, I = ctypes.c_void_p * n, ctypes.c_int * n
+    outs = [np.empty(m.shape, np.uint8) for m in ms]
+    args = (n, P(*[m.ctypes.data for m in ms]), I(*[m.shape[0] for m in ms]), I(*[m.shape[1] for m in ms]), table,
+            P(*[a.ctypes.data for a in outs]), cnt.ctypes.data if counts else None)
+    _check(lib().pseg_despeckle_maps_host(*args) if host else lib().pseg_despeckle_maps(int(device), *args))
+    return (outs, cnt) if counts else outs
 
 
 # ---- training masks as label maps (pseg_label_masks) ----------------------------------------------------
