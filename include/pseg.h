@@ -890,6 +890,59 @@ int pseg_predict_chain_scans_clean_png(pseg_engine* e, int n_scans, const pseg_s
  * *tile_h x *tile_w tile; a tile has *slots root slots for the components that reach across its edge and lists at most *run_cap runs. */
 int pseg_despeckle_geometry(int* tile_h, int* tile_w, int* slots, int* run_cap);
 
+/* ---- Text regions from label maps on the device: rectangle morphology, hole filling, a region table ---------- */
+
+/* How a label map becomes text regions: the label id (0..255) and the sides of the three rectangles (each 1..255; a side of 1 is the
+ * identity): k_close closes, k_open opens, k_join joins (two dilations, one erosion). */
+typedef struct pseg_regions {
+    int label;
+    int k_close;
+    int k_open;
+    int k_join;
+} pseg_regions;
+
+/* The text regions of n label maps (labels[i]: uint8 H[i] x W[i], dense) in one device-resident call.  Integer-exact, for map i with
+ * t = how[i].label and the sides k1, k2, k3:
+ *   dil(m, k)[y, x] = OR  over dy, dx in 0..k-1 of m[y + dy - k/2, x + dx - k/2],  m = 0 outside the map
+ *   ero(m, k)[y, x] = AND over the SAME offsets,                                    m = 1 outside the map
+ *   m0 = (lab == t);  m1 = ero(dil(m0, k1), k1);  m3 = dil(ero(m1, k2), k2);  rt = ero(dil(dil(m3, k3), k3), k3)
+ *   T  = m3 | fill(rt)        fill: rt plus every 4-connected component of ~rt that touches no edge of the map
+ *                             (scipy.ndimage.binary_fill_holes with its default structure)
+ * Both operations use the same offsets (anchor k/2, the element is not reflected): with an even k a close is a close shifted by one
+ * pixel, neither extensive nor idempotent, and the contract keeps that.  This restates OpenCV's documented rules for cv2.dilate /
+ * cv2.erode with a rectangle and what the reference's get_text_contours does with them; parity with cv2 itself is UNPINNED (OpenCV
+ * is not part of the build or test environment).  Not reproduced on purpose: cv2's reversed contour order, the white islands inside
+ * a region that RETR_CCOMP would also list, and cv2's vertex sets.
+ * The regions are the 4-connected components of T.  out_mask (may be NULL, and so may single entries): out_mask[i] is uint8
+ * H[i] x W[i], 1 = T.  out_table (may be NULL with max_regions == 0): n x max_regions x 8 int32, one row per region: x0, y0, x1, y1
+ * (exclusive), area, seed_y, seed_x, 0; the seed is the region's first pixel in raster order and the rows are sorted by it.
+ * out_count[i] is always the true number of regions of map i; its rows are valid only when out_count[i] <= max_regions and are left
+ * untouched otherwise.
+ * Host pointers, synchronous.  The list is cut into groups as pseg_despeckle_maps cuts it (64 maps, or 64 MiB of map bytes); a group
+ * costs a fixed number of ragged launches (pack, seven rectangle operations, four per component pass, unpack) and ONE host wait,
+ * nothing is allocated per map.  The workspace (per pixel the map's byte and three bit planes; per 32 x 64 tile the bytes
+ * pseg_regions_geometry's constants imply; the tables) is grow-only, cached per device with its own stream and freed by
+ * pseg_release_workspace.  n == 0 returns PSEG_OK before a device is touched.  Every map is checked before any device work and the
+ * message names it ("map 3: ..."): a side outside 1..255, a label outside 0..255, a NULL pointer or an empty shape is PSEG_EINVAL, a
+ * map of 2^31 pixels or more PSEG_EUNSUPPORTED; nothing is written to the outputs then. */
+int pseg_text_regions(int device, int n, const uint8_t* const* labels, const int* H, const int* W, const pseg_regions* how,
+                      uint8_t* const* out_mask, int max_regions, int32_t* out_table, int* out_count);
+/* The same bytes on the host, without a device: the same word arithmetic for the x pass, a plain y pass, and a two-pass union-find
+ * over the whole page (not the tile scheme). */
+int pseg_text_regions_host(int n, const uint8_t* const* labels, const int* H, const int* W, const pseg_regions* how,
+                           uint8_t* const* out_mask, int max_regions, int32_t* out_table, int* out_count);
+/* The constants the kernels were compiled with (host arithmetic, no device; every pointer may be NULL): a plane word holds *word
+ * pixels; a morphology workgroup owns *band rows of *band_words words; a component workgroup labels a *tile_h x *tile_w tile, which
+ * has *slots root slots for the components that reach across its edge. */
+int pseg_regions_geometry(int* word, int* band, int* band_words, int* tile_h, int* tile_w, int* slots);
+/* The crack polygons of the regions of a mask (uint8 H x W, non-zero = T; table: n_regions rows as above, only the seeds are read), on
+ * the host: the outer boundary of a region along pixel edges, clockwise, from the seed's top-left corner; vertices are pixel corners
+ * (x in 0..W, y in 0..H) and only direction changes are kept; where two pixels meet only diagonally the walk turns so that they stay
+ * apart.  xy: cap int32 (x, y) pairs; first: n_regions + 1 offsets in vertices (region i owns [first[i], first[i + 1])).  When cap is
+ * too small, the needed size is returned in first[n_regions], no vertex and no other offset is written, and the call is PSEG_OK.  A
+ * row whose seed is not the first pixel of a region of the mask is PSEG_EINVAL. */
+int pseg_trace_regions_host(const uint8_t* mask, int H, int W, int n_regions, const int32_t* table, int32_t* xy, int64_t cap, int64_t* first);
+
 #ifdef __cplusplus
 }
 #endif

@@ -467,6 +467,7 @@ size_t binarize_rows_bytes(int H, int W);
 int binarize_enqueue(const uint8_t* d_scan, int H, int W, const pseg_binarize& how, uint8_t* d_rows, uint8_t* d_ink, double* d_thr, hipStream_t st);
 void binarize_release_workspace(int dev);   // the list entry's per-device workspace (pseg_release_workspace)
 void label_masks_release_workspace(int dev);   // pseg_labelmasks.hip: pseg_label_masks' per-device workspace (pseg_release_workspace)
+void regions_release_workspace(int dev);   // pseg_regions.hip: pseg_text_regions' per-device workspace and stream (pseg_release_workspace)
 // pseg_despeckle.hip: despeckle_check refuses a bad pseg_despeckle ("map <index>: ..."); despeckle_tile_bytes is the workspace of one
 // 32 x 64 tile (root slots, rim table, task list, run list, list lengths); the per-device workspace and stream of pseg_despeckle_maps
 // are freed with the binarisation's (binarize_release_workspace, i.e. pseg_release_workspace).  For the scan chain's front end:

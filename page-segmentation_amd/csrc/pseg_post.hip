@@ -1101,6 +1101,7 @@ int pseg_release_workspace(int device) {
     eval_pages_release_workspace(device);
     binarize_release_workspace(device);
     label_masks_release_workspace(device);
+    regions_release_workspace(device);
     return release_workspace(device);
 }
 

@@ -262,6 +262,46 @@ class Predictor:
             scores += evaluate_pages([data.mask for data in part], labels, binaries, rules, connectivity)
         return scores
 
+    def predict_regions(self, dataset: Dataset, label, chunk=64):
+        """The text regions of every page of a dataset: one list of pc_segmentation.TextRegion per page, in dataset order.  Per
+        chunk of `chunk` pages the label maps come from the list route evaluate_dataset uses (the settings' post-processors and
+        high_res_output; pages it cannot take go through predict_single), at their final shape, and ONE pseg_amd.text_regions call
+        turns them into masks and region tables; the polygons are traced on the host.  label: the label id, or a ColorMap (its
+        label named "text").  A page's char_height is its line_height_px at the scale of its label map."""
+        from pseg_amd import engine
+        from .pc_segmentation import _label_of, regions_of_record
+        lid = _label_of(label)
+        pages = list(dataset.data)
+        out = []
+        step = max(1, int(chunk))
+        for i in range(0, len(pages), step):
+            part = pages[i:i + step]
+            inputs = []
+            for data in part:
+                inputs.append(self._chain_inputs(data, False, record=False))
+                if inputs[-1] is not None and not self._list_takes(np.shape(inputs[-1][1])[:2]):
+                    inputs[-1] = None
+            labels = [None] * len(part)
+            on_device = [k for k, got in enumerate(inputs) if got is not None]
+            if on_device:
+                shapes = set((tuple(np.shape(inputs[k][1])[:2]), inputs[k][3] or tuple(np.shape(inputs[k][1])[:2])) for k in on_device)
+                got = self.network.model.predict_chain_pages(
+                    [inputs[k][1] for k in on_device], binaries=[inputs[k][2] for k in on_device],
+                    out_shapes=[inputs[k][3] for k in on_device], post_ops=inputs[on_device[0]][4],
+                    exact_labels=self.network.exact == "labels", which=(), labels=True, mixed=self.MIXED_DEFAULT and len(shapes) > 1)
+                for j, k in enumerate(on_device):
+                    labels[k] = got[j]["labels"]
+            how = []
+            for k, data in enumerate(part):
+                if inputs[k] is None:
+                    labels[k] = np.asarray(self.predict_single(data).labels).astype(np.uint8)
+                ch = data.line_height_px or 1
+                if data.original_shape is not None and data.original_shape[0]:
+                    ch = ch * np.shape(labels[k])[0] / data.original_shape[0]
+                how.append(engine.TextRegions(lid, char_height=ch))
+            out += [regions_of_record(rec) for rec in engine.text_regions(labels, how)]
+        return out
+
     def _scan_route(self, entry: SingleData, path):
         """Whether write_masks_scans may send this entry through the scan chain, as far as that shows before the file is read."""
         from . import output

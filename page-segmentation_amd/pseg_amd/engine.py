@@ -35,6 +35,7 @@ EXPORTED_SYMBOLS = (
     "pseg_binarize_scans", "pseg_binarize_scans_host", "pseg_binarize_geometry", "pseg_prepare_scans_bin", "pseg_predict_chain_scans_bin_png",
     "pseg_label_masks", "pseg_label_masks_host", "pseg_label_masks_geometry", "pseg_label_masks_groups",
     "pseg_despeckle_maps", "pseg_despeckle_maps_host", "pseg_despeckle_geometry", "pseg_prepare_scans_clean", "pseg_predict_chain_scans_clean_png",
+    "pseg_text_regions", "pseg_text_regions_host", "pseg_regions_geometry", "pseg_trace_regions_host",
     "pseg_rescale_shape", "pseg_gaussian_kernel", "pseg_resize_nearest", "pseg_resize_nearest_device", "pseg_scale_image",
     "pseg_prepare_images", "pseg_affine_warp", "pseg_affine_warp_fill", "pseg_brightness_shift",
     "pseg_eval_confusion", "pseg_cc_label", "pseg_cc_tables", "pseg_eval_pages", "pseg_eval_page_groups",
@@ -63,6 +64,11 @@ class BINARIZE(ctypes.Structure):
 class DESPECKLE(ctypes.Structure):
     """pseg_despeckle: how an ink map loses its specks (max_area 0: not at all; else components of at most max_area pixels)."""
     _fields_ = [("max_area", ctypes.c_int), ("connectivity", ctypes.c_int)]
+
+
+class REGIONS(ctypes.Structure):
+    """pseg_regions: the label id and the sides of the closing, the opening and the joining rectangle (each 1..255)."""
+    _fields_ = [("label", ctypes.c_int), ("k_close", ctypes.c_int), ("k_open", ctypes.c_int), ("k_join", ctypes.c_int)]
 
 
 class MASK_SRC(ctypes.Structure):
@@ -214,6 +220,10 @@ def lib():
     L.pseg_despeckle_maps.argtypes = [i, i, vp, vp, vp, c.POINTER(DESPECKLE), vp, vp]
     L.pseg_despeckle_maps_host.argtypes = [i, vp, vp, vp, c.POINTER(DESPECKLE), vp, vp]
     L.pseg_despeckle_geometry.argtypes = [c.POINTER(i)] * 4
+    L.pseg_text_regions.argtypes = [i, i, vp, vp, vp, c.POINTER(REGIONS), vp, i, vp, vp]
+    L.pseg_text_regions_host.argtypes = [i, vp, vp, vp, c.POINTER(REGIONS), vp, i, vp, vp]
+    L.pseg_regions_geometry.argtypes = [c.POINTER(i)] * 6
+    L.pseg_trace_regions_host.argtypes = [vp, i, i, i, vp, vp, i64, vp]
     L.pseg_prepare_scans_clean.argtypes = [i, i, c.POINTER(SCAN), c.POINTER(BINARIZE), c.POINTER(DESPECKLE), vp, vp, vp]
     L.pseg_predict_chain_scans_clean_png.argtypes = [vp, i, c.POINTER(SCAN), c.POINTER(BINARIZE), c.POINTER(DESPECKLE), c.POINTER(i), i, c.c_uint, vp, i, i,
                                                      c.c_uint, i, CHAIN_SINK, vp]
@@ -1394,6 +1404,122 @@ def despeckle_maps(maps, how, device=0, counts=False, host=False):
             P(*[a.ctypes.data for a in outs]), cnt.ctypes.data if counts else None)
     _check(lib().pseg_despeckle_maps_host(*args) if host else lib().pseg_despeckle_maps(int(device), *args))
     return (outs, cnt) if counts else outs
+
+
+# ---- text regions from label maps (pseg_text_regions) -----------------------------------------------------
+
+REGION_SIDE_MAX = 255
+
+
+def region_kernels(ch):
+    """The sides of the three rectangles for a line height ch: (int(ch), int(ch / 3), int(ch / 1.1)), each clamped to 1..255 (a side
+    of 1 is the identity; the reference fails below a line height of 3).  Host arithmetic."""
+    if ch is None or isinstance(ch, bool) or not np.isfinite(ch) or ch < 0:
+        raise PsegError("region_kernels needs a non-negative line height, got %r" % (ch,))
+    return tuple(min(REGION_SIDE_MAX, max(1, int(v))) for v in (ch, ch / 3, ch / 1.1))
+
+
+class TextRegions:
+    """How a label map becomes text regions (include/pseg.h, pseg_regions): the label id, 0..255, and either the page's line height
+    (char_height: the sides are region_kernels of it) or the three sides themselves (kernels, each 1..255)."""
+
+    def __init__(self, label, char_height=None, kernels=None):
+        if isinstance(label, bool) or not isinstance(label, (int, np.integer)) or not 0 <= int(label) <= 255:
+            raise PsegError("TextRegions: label must be an integer in 0..255, got %r" % (label,))
+        if (char_height is None) == (kernels is None):
+            raise PsegError("TextRegions takes either char_height or kernels")
+        if kernels is None:
+            kernels = region_kernels(char_height)
+        else:
+            kernels = tuple(kernels)
+            if len(kernels) != 3 or any(isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= REGION_SIDE_MAX
+                                        for k in kernels):
+                raise PsegError("TextRegions: kernels must be three integers in 1..%d, got %r" % (REGION_SIDE_MAX, kernels))
+        self.label, self.kernels = int(label), tuple(int(k) for k in kernels)
+
+    def __repr__(self):
+        return "TextRegions(label=%r, kernels=%r)" % (self.label, self.kernels)
+
+    def __eq__(self, other):
+        return isinstance(other, TextRegions) and (self.label, self.kernels) == (other.label, other.kernels)
+
+    def __hash__(self):
+        return hash((self.label, self.kernels))
+
+
+def regions_geometry():
+    """(word, band, band_words, tile_h, tile_w, slots) of pseg_text_regions' kernels (pseg_regions_geometry; no device)."""
+    v = [ctypes.c_int() for _ in range(6)]
+    _check(lib().pseg_regions_geometry(*[ctypes.byref(x) for x in v]))
+    return tuple(x.value for x in v)
+
+
+def _regions_call(ms, entries, device, masks, max_regions, host):
+    n = len(ms)
+    table = (REGIONS * n)(*[REGIONS(e.label, *e.kernels) for e in entries])
+    P, I = ctypes.c_void_p * n, ctypes.c_int * n
+    outs = [np.empty(m.shape, np.uint8) for m in ms] if masks else None
+    rows = np.zeros((n, max_regions, 8), np.int32)
+    cnt = np.zeros(n, np.int32)
+    args = (n, P(*[m.ctypes.data for m in ms]), I(*[m.shape[0] for m in ms]), I(*[m.shape[1] for m in ms]), table,
+            P(*[a.ctypes.data for a in outs]) if masks else None, int(max_regions), rows.ctypes.data if max_regions else None, cnt.ctypes.data)
+    _check(lib().pseg_text_regions_host(*args) if host else lib().pseg_text_regions(int(device), *args))
+    return outs, rows, cnt
+
+
+def text_regions(label_maps, how, device=0, masks=True, max_regions=256, host=False):
+    """The text regions of a list of label maps (uint8 (H,W)) in one device-resident call (pseg_text_regions): how is a TextRegions
+    or one per map.  -> one dict per map: "mask" (uint8 (H,W), 1 = region; None with masks=False), "boxes" (r,4) int32 x0, y0, x1, y1
+    (exclusive), "areas" (r,) int32, "seeds" (r,2) int32 (y, x) -- the region's first pixel in raster order, by which the rows are
+    sorted.  A map with more than max_regions regions is run again alone with max_regions = its count.  host=True: the same bytes from
+    the host entry (pseg_text_regions_host), no device."""
+    ms = [np.ascontiguousarray(m, dtype=np.uint8) for m in label_maps]
+    for k, m in enumerate(ms):
+        if m.ndim != 2:
+            raise PsegError("map %d: an (H,W) label map is expected, got shape %r" % (k, m.shape))
+    n = len(ms)
+    entries = [how] * n if isinstance(how, TextRegions) else list(how)
+    if len(entries) != n:
+        raise PsegError("text_regions must have one entry per map (%d for %d maps)" % (len(entries), n))
+    for k, e in enumerate(entries):
+        if not isinstance(e, TextRegions):
+            raise PsegError("map %d: text_regions takes a TextRegions, got %r" % (k, e))
+    if isinstance(max_regions, bool) or int(max_regions) != max_regions or max_regions < 0:
+        raise PsegError("text_regions: max_regions must be a non-negative integer, got %r" % (max_regions,))
+    if n == 0:
+        return []
+    outs, rows, cnt = _regions_call(ms, entries, device, masks, int(max_regions), host)
+    res = []
+    for k in range(n):
+        r, c = rows[k], int(cnt[k])
+        if c > max_regions:
+            _, r1, c1 = _regions_call([ms[k]], [entries[k]], device, False, c, host)
+            r, c = r1[0], int(c1[0])
+        r = r[:c]
+        res.append({"mask": outs[k] if masks else None, "boxes": r[:, 0:4].copy(), "areas": r[:, 4].copy(), "seeds": r[:, 5:7].copy()})
+    return res
+
+
+def trace_regions(mask, record):
+    """The crack polygons of the regions of one text_regions record on its mask (pseg_trace_regions_host; host only): a list of (v,2)
+    int32 arrays of (x, y) pixel corners, clockwise from the seed's top-left corner, direction changes only."""
+    m = np.ascontiguousarray(mask, dtype=np.uint8)
+    if m.ndim != 2:
+        raise PsegError("trace_regions: an (H,W) mask is expected, got shape %r" % (m.shape,))
+    seeds = np.asarray(record["seeds"], np.int32).reshape(-1, 2)
+    r = seeds.shape[0]
+    table = np.zeros((max(r, 1), 8), np.int32)
+    table[:r, 5:7] = seeds
+    first = np.zeros(r + 1, np.int64)
+    cap = 64 * max(r, 1)
+    for _ in range(2):
+        xy = np.zeros((cap, 2), np.int32)
+        first[:] = 0
+        _check(lib().pseg_trace_regions_host(m.ctypes.data, m.shape[0], m.shape[1], r, table.ctypes.data, xy.ctypes.data, cap, first.ctypes.data))
+        if first[r] <= cap:
+            break
+        cap = int(first[r])
+    return [xy[first[i]:first[i + 1]].copy() for i in range(r)]
 
 
 # ---- training masks as label maps (pseg_label_masks) ----------------------------------------------------
