@@ -243,7 +243,9 @@ int pseg_host_unregister(void* p);
 
 /* Copy an intermediate activation to the host as float32 NHWC (true channel count) --
  * layer-by-layer parity tests.  `layer` is the Keras layer name.  dims[3] = {H,W,C} of the
- * padded canvas at that layer.  Valid after a predict call. */
+ * padded canvas at that layer.  Valid after a predict call.  PSEG_EUNSUPPORTED for a tensor the bf16 plan
+ * never writes as such: one that lives inside a fused kernel, one stored after its readers' ReLU, and
+ * "input" where the first layer reads the uint8 page itself (one-channel fcn graphs). */
 int pseg_get_activation(pseg_engine* e, const char* layer, float* out, int64_t cap, int dims[3]);
 
 /* The engine's own hipStream_t (what NULL stream arguments mean; the train step always runs on it): lets a caller

@@ -160,6 +160,13 @@ class _Ctx:
         self.nm = _Namer()
         self.acts = OrderedDict()
 
+    # the value-preserving ops of the graphs, as methods: another context (oracle/exact.py) walks the same graph functions
+    pad32 = staticmethod(_pad32)
+    crop = staticmethod(_crop)
+    up2 = staticmethod(_up2)
+    cat = staticmethod(lambda a, b: _cat(a, b))
+    pool = staticmethod(core.maxpool2)
+
     def conv(self, x, relu=False, stride=1, name=None, add=None, in_relu=False, keep=None):
         name = name or self.nm("conv2d")
         if in_relu:
@@ -216,28 +223,28 @@ def _cat(a, b):
 
 def _fcn(c, x, skip):
     """lib/model.py:45-92 (skip=True) / :206-234 (skip=False)."""
-    x, pads = _pad32(x)
+    x, pads = c.pad32(x)
     c1 = c.conv(x, relu=True)
     c2 = c.conv(c1)
-    c3 = c.conv(core.maxpool2(c2), relu=True)
+    c3 = c.conv(c.pool(c2), relu=True)
     c4 = c.conv(c3)
-    c5 = c.conv(core.maxpool2(c4), relu=True)
+    c5 = c.conv(c.pool(c4), relu=True)
     c6 = c.conv(c5)
-    c7 = c.conv(core.maxpool2(c6), relu=True)
+    c7 = c.conv(c.pool(c6), relu=True)
     d1 = c.tconv5(c7, relu=True)
     d2 = c.deconv2(d1, relu=True)
     if skip:
-        d2 = _cat(d2, c6)          # [deconv, skip] order, :73
+        d2 = c.cat(d2, c6)        # [deconv, skip] order, :73
     d3 = c.tconv5(d2, relu=True)
     if skip:
-        d3 = _cat(d3, c5)          # :77
+        d3 = c.cat(d3, c5)        # :77
     d4 = c.deconv2(d3, relu=True)
     if skip:
-        d4 = _cat(d4, c3)          # :81
+        d4 = c.cat(d4, c3)        # :81
     d5 = c.deconv2(d4)
     if skip:
-        d5 = _cat(d5, c2)          # :85
-    d5 = _crop(d5, pads)           # :86
+        d5 = c.cat(d5, c2)        # :85
+    d5 = c.crop(d5, pads)           # :86
     return c.conv(d5, name="logits")
 
 
@@ -251,7 +258,7 @@ def _dropped(t, drop, op_index):
 def _unet(c, x, drop=None):
     """lib/model.py:151-203.  Dropout is the identity at inference; drop = (seed, step) applies the train step's Dropout
     behind levels 3 and 4 (op indices 10 and 13 of the engine's op list), after the level's activation is recorded."""
-    x, pads = _pad32(x)
+    x, pads = c.pad32(x)
     skips = []
     t = x
     for lvl in range(5):
@@ -261,20 +268,20 @@ def _unet(c, x, drop=None):
             t = _dropped(t, drop, 10 if lvl == 3 else 13)
         if lvl < 4:
             skips.append(t)
-            t = core.maxpool2(t)
+            t = c.pool(t)
     for lvl in range(4):
-        up = c.conv(_up2(t), relu=True)            # k2 SAME: pad 0 before / 1 after
-        t = _cat(skips[3 - lvl], up)               # [skip, up] order, :176
+        up = c.conv(c.up2(t), relu=True)          # k2 SAME: pad 0 before / 1 after
+        t = c.cat(skips[3 - lvl], up)             # [skip, up] order, :176
         t = c.conv(t, relu=True)
         t = c.conv(t, relu=True)
-    t = _crop(t, pads)
+    t = c.crop(t, pads)
     return c.conv(t, name="logits")
 
 
 def _res_unet(c, x, bn=False):
     """lib/model.py:237-307.  bn=False is the reference as shipped (BatchNorm flag hard-wired off, :265); bn=True places
     BatchNormalization where bn_act would, names in Keras creation order."""
-    x, pads = _pad32(x)
+    x, pads = c.pad32(x)
     bnn = (lambda: c.nm("batch_normalization")) if bn else (lambda: None)
 
     def pre(t, name):
@@ -313,8 +320,8 @@ def _res_unet(c, x, bn=False):
     b1 = c.conv(a, in_relu=ir)
     d = b1
     for sk in (e4, e3, e2, e1):
-        d = residual(_cat(_up2(d), sk))                     # [up, skip] order, :240
-    d = _crop(d, pads)
+        d = residual(c.cat(c.up2(d), sk))                 # [up, skip] order, :240
+    d = c.crop(d, pads)
     return c.conv(d, name="logits")
 
 

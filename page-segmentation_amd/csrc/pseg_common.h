@@ -256,6 +256,7 @@ int mfma_launch_pool(Engine& e, Op& op, hipStream_t st);     // OP_POOL (unfused
 int mfma_launch_logits(Engine& e, Op& op, float* d_logits, float* d_probs, int64_t* d_labels,
                        uint8_t* d_labels_u8, hipStream_t st);
 int mfma_preprocess(Engine& e, const uint8_t* d_img, hipStream_t st);
+bool mfma_input_is_staged(const Engine& e);                 // false: every reader of the input takes the uint8 page itself, the input tensor is never written
 
 struct TimingSlot {
     std::string name;

@@ -6002,15 +6002,18 @@ bool mfma_tail_emits_margin(const Engine& e) {
 
 // The fused first-layer kernels read the uint8 page directly (e.cur_img); graphs whose first
 // conv is not on that path get a bf16 canvas of x/255.
-int mfma_preprocess(Engine& e, const uint8_t* d_img, hipStream_t st) {
-    e.cur_img = d_img;
-    bool all_special = true;
+bool mfma_input_is_staged(const Engine& e) {
     for (auto& op : e.ops)
         if (op.src0 == e.input_tensor || op.src1 == e.input_tensor) {
             auto* P = (MfmaPlan*)op.plan;
-            if (!P || P->kind != PLAN_CONV1) all_special = false;
+            if (!P || P->kind != PLAN_CONV1) return true;
         }
-    if (all_special) return PSEG_OK;
+    return false;
+}
+
+int mfma_preprocess(Engine& e, const uint8_t* d_img, hipStream_t st) {
+    e.cur_img = d_img;
+    if (!mfma_input_is_staged(e)) return PSEG_OK;
     Tensor& in = e.tensors[e.input_tensor];
     const size_t n = (size_t)e.Hp * e.Wp;
     preprocess_bf16_kernel<<<(int)std::min<size_t>((n + 255) / 256, 8192), 256, 0, st>>>(
