@@ -374,7 +374,8 @@ int pseg_cc_vote_device(int device, int64_t* d_pred, const uint8_t* d_binary, in
  * algorithmic bytes per pixel; widen to int64 only at the host boundary. */
 int pseg_cc_vote_device_u8(int device, uint8_t* d_pred, const uint8_t* d_binary, int H, int W,
                            int n_classes, void* stream);
-/* Frees the device workspace the vote entries cache per device (waits for its last user). */
+/* Frees every workspace the library caches for this device: the vote's (after waiting for its last user), the PNG encoder's, the
+ * bounding-box scratch of pseg_bbox_fill_device_u8 and those of the list entries below, with their streams and events. */
 int pseg_release_workspace(int device);
 
 /* add_bounding_boxes (lib/postprocess.py:29-42): every 4-connected component of each class

@@ -13,19 +13,6 @@ namespace pseg {
 
 constexpr int BZ_WINDOW_MIN = 3, BZ_WINDOW_MAX = 255;
 
-// how pseg_binarize_scans cuts its list (include/pseg.h), and pseg_despeckle_maps with it: the end of the group that starts at scan g0
-constexpr int BZ_GROUP_SCANS = 64;
-constexpr size_t BZ_GROUP_BYTES = (size_t)64 << 20;
-inline int binarize_group_end(int n, const int* H, const int* W, int g0) {
-    int g1 = g0;
-    size_t bytes = 0;
-    while (g1 < n && g1 - g0 < BZ_GROUP_SCANS && (g1 == g0 || bytes + (size_t)H[g1] * W[g1] <= BZ_GROUP_BYTES)) {
-        bytes += (size_t)H[g1] * W[g1];
-        ++g1;
-    }
-    return g1;
-}
-
 // periodic 'mirror' extension without an edge repeat (NumPy's mode='reflect', mirror_idx of pseg_resize.hip): d c b | a b c d | c b a
 __host__ __device__ inline int bz_mirror(int i, int n) {
     if (n == 1) return 0;

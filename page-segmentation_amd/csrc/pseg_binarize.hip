@@ -8,13 +8,12 @@
 //   bz_cols_*   one thread per column of a band of BZ_BAND rows: the first window from 2 r + 1 words, then one add and one subtract
 //               per row, bz_decide on the pair of sums, the ink byte and (where asked for) the float64 threshold
 // _list: ragged over a group's scans through a table (as ch_hist_kernel, pseg_lineheight.hip); _one: one scan, the record by value.
-#include "pseg_common.h"
+#include "pseg_list.h"
 #include "pseg_binarize.h"
 
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <mutex>
 
 namespace pseg {
 
@@ -35,7 +34,6 @@ struct BzScan {
     int row0, col0;                     // workgroups of the group's scans in front of this one (row / column launch)
 };
 
-static constexpr size_t bz_up256(size_t v) { return (v + 255) & ~(size_t)255; }
 static inline int bz_pitch(int W) { return (W + 1) & ~1; }
 
 template <int BzScan::*FIRST>
@@ -172,7 +170,7 @@ int binarize_check(const pseg_binarize& b, int index) {
     return PSEG_OK;
 }
 
-size_t binarize_rows_bytes(int H, int W) { return bz_up256((size_t)H * bz_pitch(W) * sizeof(unsigned long long)); }
+size_t binarize_rows_bytes(int H, int W) { return up256((size_t)H * bz_pitch(W) * sizeof(unsigned long long)); }
 
 int binarize_enqueue(const uint8_t* d_scan, int H, int W, const pseg_binarize& how, uint8_t* d_rows, uint8_t* d_ink, double* d_thr, hipStream_t st) {
     BzScan s;
@@ -189,26 +187,21 @@ int binarize_enqueue(const uint8_t* d_scan, int H, int W, const pseg_binarize& h
 
 // ---- workspace of the list entry: grow-only, one per device (the group's table, scans and planes; a page-locked copy of the table);
 // a call holds the device's lock to its end and ends synchronised.  pseg_release_workspace frees it.
-struct BzWs { GrowDev dev; GrowPin pin; };
-static std::mutex g_bz_mu[64];
-static BzWs g_bz_ws[64];
-
-void binarize_release_workspace(int dev) {
-    std::lock_guard<std::mutex> lk(g_bz_mu[dev & 63]);
-    g_bz_ws[dev & 63].dev.release();
-    g_bz_ws[dev & 63].pin.release();
-    despeckle_release_workspace(dev);                                  // the stage behind the binarisation (pseg_despeckle.hip): its own lock
-}
+struct BzWs {
+    GrowDev dev; GrowPin pin;
+    void release() { dev.release(); pin.release(); }
+};
+static PerDevice<BzWs> g_bz;
 
 static int bz_group(BzWs& ws, int g0, int g1, const uint8_t* const* gray, const int* H, const int* W, const pseg_binarize* how,
                     uint8_t* const* out_ink, double* const* out_thr) {
     const int n = g1 - g0;
-    constexpr size_t tab_b = bz_up256((size_t)BZ_GROUP_SCANS * sizeof(BzScan));
+    constexpr size_t tab_b = up256((size_t)LIST_GROUP_ITEMS * sizeof(BzScan));
     PSEG_TRY(ws.pin.ensure(tab_b, "binarisation table"));
     BzScan* const h_tab = ws.pin.as<BzScan>();
     memset(h_tab, 0, tab_b);
     std::vector<size_t> o_scan(n), o_rows(n), o_ink(n), o_thr(n);
-    size_t off = tab_b;
+    Bump at{tab_b};
     long long rows_total = 0, cols_total = 0;
     for (int k = 0; k < n; ++k) {
         const int i = g0 + k;
@@ -221,12 +214,12 @@ static int bz_group(BzWs& ws, int g0, int g1, const uint8_t* const* gray, const 
         cols_total += cb;
         if (rows_total > 0x7fffffffLL || cols_total > 0x7fffffffLL) return fail(PSEG_EUNSUPPORTED, "scans %d..%d: too many tiles for one launch", g0, g1 - 1);
         const size_t px = (size_t)s.H * s.W;
-        o_scan[k] = off; off += bz_up256(px);
-        o_ink[k] = off; off += bz_up256(px);
-        o_rows[k] = off; off += s.fixed ? 0 : binarize_rows_bytes(s.H, s.W);
-        o_thr[k] = off; off += out_thr && out_thr[i] ? bz_up256(px * sizeof(double)) : 0;
+        o_scan[k] = at.take(px);
+        o_ink[k] = at.take(px);
+        o_rows[k] = at.take(s.fixed ? 0 : binarize_rows_bytes(s.H, s.W));
+        o_thr[k] = at.take(out_thr && out_thr[i] ? px * sizeof(double) : 0);
     }
-    PSEG_TRY(ws.dev.ensure(off, "binarisation workspace"));
+    PSEG_TRY(ws.dev.ensure(at.off, "binarisation workspace"));
     uint8_t* const d = ws.dev.p;
     for (int k = 0; k < n; ++k) {
         BzScan& s = h_tab[k];
@@ -236,10 +229,7 @@ static int bz_group(BzWs& ws, int g0, int g1, const uint8_t* const* gray, const 
         s.thr = out_thr && out_thr[g0 + k] ? (double*)(d + o_thr[k]) : nullptr;
     }
     hipStream_t st = nullptr;
-    struct Drain {                                                     // an error return in the middle leaves no copy from / to the caller's arrays in flight
-        bool armed = true;
-        ~Drain() { if (armed) (void)hipStreamSynchronize(nullptr); }
-    } drain;
+    GroupDrain drain{st};
     PSEG_HIP(hipMemcpyAsync(d, h_tab, (size_t)n * sizeof(BzScan), hipMemcpyHostToDevice, st));
     for (int k = 0; k < n; ++k)
         PSEG_HIP(hipMemcpyAsync(d + o_scan[k], gray[g0 + k], (size_t)h_tab[k].H * h_tab[k].W, hipMemcpyHostToDevice, st));
@@ -318,17 +308,8 @@ int pseg_binarize_scans(int device, int n, const uint8_t* const* gray, const int
                         uint8_t* const* out_ink, double* const* out_threshold) {
     if (n == 0) return PSEG_OK;
     PSEG_TRY(bz_check_list(n, gray, H, W, how, out_ink));
-    int nd = 0;
-    if (hipGetDeviceCount(&nd) != hipSuccess || nd == 0) return fail(PSEG_EHIP, "no HIP device visible: libpseg has no CPU fallback");
-    if (device < 0 || device >= nd) return fail(PSEG_EINVAL, "device %d of %d", device, nd);
-    PSEG_HIP(hipSetDevice(device));
-    std::lock_guard<std::mutex> lk(g_bz_mu[device & 63]);
-    for (int g0 = 0; g0 < n;) {
-        const int g1 = binarize_group_end(n, H, W, g0);
-        PSEG_TRY(bz_group(g_bz_ws[device & 63], g0, g1, gray, H, W, how, out_ink, out_threshold));
-        g0 = g1;
-    }
-    return PSEG_OK;
+    return run_list(g_bz, device, n, [&](int i) { return (size_t)H[i] * W[i]; },
+                    [&](BzWs& ws, int g0, int g1) { return bz_group(ws, g0, g1, gray, H, W, how, out_ink, out_threshold); });
 }
 
 int pseg_binarize_scans_host(int n, const uint8_t* const* gray, const int* H, const int* W, const pseg_binarize* how,

@@ -9,7 +9,7 @@
 #include <algorithm>
 #include <cstring>
 
-#include "pseg_common.h"
+#include "pseg_list.h"
 
 namespace pseg {
 
@@ -270,7 +270,6 @@ extern "C" int pseg_predict_chain_png(pseg_engine* h, const uint8_t* img, int H,
     return pseg_predict_chain_png_lv(h, img, H, W, Ho, Wo, binary, post_ops, n_post, flags, labels, labels_u8, lut, n_lut, 0, png, cap, n_bytes);
 }
 // ---- a page list through the chain to PNG streams (lib/predictor.py:27-30 x :49-54) ------------------------------------------
-static inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // The mixed planner: pages by canvas (stable: canvases by first appearance, list order within one), then plan_units over the canvases
 static void plan_units_mixed(int n, const int* H, const int* W, int cap, std::vector<int>& order, std::vector<int>& ub, std::vector<int>& ug) {

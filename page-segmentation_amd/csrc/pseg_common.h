@@ -409,10 +409,6 @@ __host__ __device__ inline bool glyph_shaped(int h, int w) {
     const double ar = (double)w / (double)h;
     return GLYPH_AR_LO < ar && ar < GLYPH_AR_HI;
 }
-void char_heights_release_workspace(int dev);   // pseg_lineheight.hip: the list entry's per-device workspace (pseg_release_workspace)
-void pngdec_release_workspace(int dev);   // pseg_pngdec.hip: the PNG decoder's per-device workspace and stream (pseg_release_workspace)
-void png_release_workspace(int dev);   // pseg_png.hip: the encoder's per-device workspace (pseg_release_workspace)
-void eval_pages_release_workspace(int dev);   // pseg_evalpages.hip: the page scorer's per-device workspace and stream (pseg_release_workspace)
 // pseg_png.hip, for the page chain: the masks of `pages` label maps of one shape as PNG streams in one set of launches, enqueued on
 // `st` without a wait; the workspace (PngPages::bytes, from png_pages_layout) is the caller's.  Page p's sizes: ((u64*)d_ws)[4 p + k];
 // its stream k (k-th requested mask): d_ws + head + p * page + k * per + slots_b + meta_b + offs_b, chunk CRCs left to
@@ -466,12 +462,8 @@ int scan_front_enqueue(const pseg_scan& s, const uint8_t* d_scan, const double* 
 int binarize_check(const pseg_binarize& b, int index);
 size_t binarize_rows_bytes(int H, int W);
 int binarize_enqueue(const uint8_t* d_scan, int H, int W, const pseg_binarize& how, uint8_t* d_rows, uint8_t* d_ink, double* d_thr, hipStream_t st);
-void binarize_release_workspace(int dev);   // the list entry's per-device workspace (pseg_release_workspace)
-void label_masks_release_workspace(int dev);   // pseg_labelmasks.hip: pseg_label_masks' per-device workspace (pseg_release_workspace)
-void regions_release_workspace(int dev);   // pseg_regions.hip: pseg_text_regions' per-device workspace and stream (pseg_release_workspace)
 // pseg_despeckle.hip: despeckle_check refuses a bad pseg_despeckle ("map <index>: ..."); despeckle_tile_bytes is the workspace of one
-// 32 x 64 tile (root slots, rim table, task list, run list, list lengths); the per-device workspace and stream of pseg_despeckle_maps
-// are freed with the binarisation's (binarize_release_workspace, i.e. pseg_release_workspace).  For the scan chain's front end:
+// 32 x 64 tile (root slots, rim table, task list, run list, list lengths).  For the scan chain's front end:
 // despeckle_work_bytes is the workspace of one H x W map (a multiple of 256: 256 bytes, then the per-tile arrays); despeckle_enqueue
 // launches the four kernels of one map on `st` without a wait, in place on d_ink (H x W, non-zero = ink; kept ink becomes 1); d_work
 // is 256-byte aligned.  max_area == 0: no launch.
@@ -479,7 +471,6 @@ int despeckle_check(const pseg_despeckle& d, int index, const char* what = "map"
 size_t despeckle_tile_bytes();
 size_t despeckle_work_bytes(int H, int W);
 int despeckle_enqueue(uint8_t* d_ink, int H, int W, const pseg_despeckle& how, uint8_t* d_work, hipStream_t st);
-void despeckle_release_workspace(int dev);
 // the entry of a list that asks for a despeckling, or NULL
 inline const pseg_despeckle* despeckle_of(const pseg_despeckle* how, int i) { return how && how[i].max_area != 0 ? &how[i] : nullptr; }
 // the entry of a list that asks for an adaptive binarisation, or NULL

@@ -13,11 +13,9 @@
 // ever decrease, so a chain is shorter than the index space, and the larger root of a union strictly decreases from try to try).
 #include <algorithm>
 #include <cstring>
-#include <mutex>
 #include <vector>
 
-#include "pseg_common.h"
-#include "pseg_binarize.h"
+#include "pseg_list.h"
 #include "pseg_despeckle.h"
 
 namespace pseg {
@@ -455,20 +453,16 @@ __global__ __launch_bounds__(256) void ds_apply_kernel(uint8_t* buf, const DsMap
 // ---- workspace: grow-only, one per device (table, records, the group's maps, the per-tile arrays; a page-locked copy of table and
 // records), under its own lock and on its own stream; a call holds the lock to its end and every group ends synchronised.
 // pseg_release_workspace frees it.
-struct DsWs { GrowDev dev; GrowPin pin; hipStream_t st = nullptr; };
-static std::mutex g_ds_mu[64];
-static DsWs g_ds_ws[64];
-
-void despeckle_release_workspace(int dev) {
-    std::lock_guard<std::mutex> lk(g_ds_mu[dev & 63]);
-    DsWs& ws = g_ds_ws[dev & 63];
-    ws.dev.release();
-    ws.pin.release();
-    if (ws.st) (void)hipStreamDestroy(ws.st);
-    ws.st = nullptr;
-}
-
-static constexpr size_t ds_up256(size_t v) { return (v + 255) & ~(size_t)255; }
+struct DsWs {
+    GrowDev dev; GrowPin pin; hipStream_t st = nullptr;
+    void release() {
+        dev.release();
+        pin.release();
+        if (st) (void)hipStreamDestroy(st);
+        st = nullptr;
+    }
+};
+static PerDevice<DsWs> g_ds;
 
 // per tile: 192 root slots (parent + size), the rim table, the task list, the run list, three list lengths
 size_t despeckle_tile_bytes() { return (size_t)DS_OPEN_MAX * 8 + DS_RIM + (size_t)DS_TASK_MAX * 4 + (size_t)DS_RUN_MAX * 4 + 12; }
@@ -478,15 +472,16 @@ struct DsLayout { size_t par, size, rim, task, run, rootn, taskn, runn, total; }
 static DsLayout ds_layout(size_t base, size_t tiles) {
     DsLayout L;
     const size_t nslots = tiles * DS_OPEN_MAX;
-    L.par = base;
-    L.size = L.par + ds_up256(nslots * 4);
-    L.rim = L.size + ds_up256(nslots * 4);
-    L.task = L.rim + ds_up256(tiles * DS_RIM);
-    L.run = L.task + ds_up256(tiles * DS_TASK_MAX * 4);
-    L.rootn = L.run + ds_up256(tiles * DS_RUN_MAX * 4);
-    L.taskn = L.rootn + ds_up256(tiles * 4);
-    L.runn = L.taskn + ds_up256(tiles * 4);
-    L.total = L.runn + ds_up256(tiles * 4);
+    Bump at{base};
+    L.par = at.take(nslots * 4);
+    L.size = at.take(nslots * 4);
+    L.rim = at.take(tiles * DS_RIM);
+    L.task = at.take(tiles * DS_TASK_MAX * 4);
+    L.run = at.take(tiles * DS_RUN_MAX * 4);
+    L.rootn = at.take(tiles * 4);
+    L.taskn = at.take(tiles * 4);
+    L.runn = at.take(tiles * 4);
+    L.total = at.off;
     return L;
 }
 
@@ -532,8 +527,8 @@ int despeckle_enqueue(uint8_t* d_ink, int H, int W, const pseg_despeckle& how, u
 
 static int ds_group(DsWs& ws, int g0, int g1, const uint8_t* const* ink, const int* H, const int* W, const pseg_despeckle* how,
                     uint8_t* const* out, int64_t* out_counts) {
-    constexpr int GROUP_MAX = BZ_GROUP_SCANS;
-    constexpr size_t tab_b = ds_up256((size_t)GROUP_MAX * sizeof(DsMap)), rec_b = ds_up256((size_t)GROUP_MAX * 3 * 8);
+    constexpr int GROUP_MAX = LIST_GROUP_ITEMS;
+    constexpr size_t tab_b = up256((size_t)GROUP_MAX * sizeof(DsMap)), rec_b = up256((size_t)GROUP_MAX * 3 * 8);
     // the table: the maps of connectivity 8, then those of connectivity 4; a map that is not despeckled has no entry
     int idx[GROUP_MAX], n = 0, n8 = 0;
     for (int pass = 0; pass < 2; ++pass)
@@ -543,7 +538,7 @@ static int ds_group(DsWs& ws, int g0, int g1, const uint8_t* const* ink, const i
         PSEG_TRY(ws.pin.ensure(tab_b + rec_b, "despeckle records"));
         DsMap* const h_tab = ws.pin.as<DsMap>();
         std::memset(h_tab, 0, tab_b);
-        size_t off = tab_b + rec_b;
+        Bump at{tab_b + rec_b};
         long long tiles = 0, tiles8 = 0;
         for (int k = 0; k < n; ++k) {
             const int i = idx[k];
@@ -551,23 +546,19 @@ static int ds_group(DsWs& ws, int g0, int g1, const uint8_t* const* ink, const i
             t.H = H[i]; t.W = W[i]; t.max_area = how[i].max_area;
             t.tiles_x = cdiv(W[i], DS_TW);
             t.tile0 = (int)tiles;
-            t.off = off; off += ds_up256((size_t)H[i] * W[i]);
+            t.off = at.take((size_t)H[i] * W[i]);
             tiles += (long long)t.tiles_x * cdiv(H[i], DS_TH);
             if (k < n8) tiles8 = tiles;
         }
         if (tiles * DS_OPEN_MAX > 0x7fffffffLL) return fail(PSEG_EUNSUPPORTED, "maps %d..%d: too many tiles for 32-bit slot ids", g0, g1 - 1);
-        const DsLayout L = ds_layout(off, (size_t)tiles);
+        const DsLayout L = ds_layout(at.off, (size_t)tiles);
         PSEG_TRY(ws.dev.ensure(L.total, "despeckle workspace"));
         if (!ws.st) PSEG_HIP(hipStreamCreateWithFlags(&ws.st, hipStreamNonBlocking));
         hipStream_t st = ws.st;
         uint8_t* const d = ws.dev.p;
         const DsMap* const d_tab = (const DsMap*)d;
         unsigned long long* const d_rec = (unsigned long long*)(d + tab_b);
-        struct Drain {                                                 // an error return in the middle leaves no copy from / to the caller's arrays in flight
-            hipStream_t s;
-            bool armed = true;
-            ~Drain() { if (armed) (void)hipStreamSynchronize(s); }
-        } drain{st};
+        GroupDrain drain{st};
         PSEG_HIP(hipMemcpyAsync(d, h_tab, (size_t)n * sizeof(DsMap), hipMemcpyHostToDevice, st));
         PSEG_HIP(hipMemsetAsync(d_rec, 0, (size_t)n * 3 * 8, st));
         for (int k = 0; k < n; ++k)
@@ -666,17 +657,8 @@ int pseg_despeckle_maps(int device, int n, const uint8_t* const* ink, const int*
                         uint8_t* const* out, int64_t* out_counts) {
     if (n == 0) return PSEG_OK;
     PSEG_TRY(ds_check_list(n, ink, H, W, how, out));
-    int nd = 0;
-    if (hipGetDeviceCount(&nd) != hipSuccess || nd == 0) return fail(PSEG_EHIP, "no HIP device visible: libpseg has no CPU fallback");
-    if (device < 0 || device >= nd) return fail(PSEG_EINVAL, "device %d of %d", device, nd);
-    PSEG_HIP(hipSetDevice(device));
-    std::lock_guard<std::mutex> lk(g_ds_mu[device & 63]);
-    for (int g0 = 0; g0 < n;) {
-        const int g1 = binarize_group_end(n, H, W, g0);
-        PSEG_TRY(ds_group(g_ds_ws[device & 63], g0, g1, ink, H, W, how, out, out_counts));
-        g0 = g1;
-    }
-    return PSEG_OK;
+    return run_list(g_ds, device, n, [&](int i) { return (size_t)H[i] * W[i]; },
+                    [&](DsWs& ws, int g0, int g1) { return ds_group(ws, g0, g1, ink, H, W, how, out, out_counts); });
 }
 
 int pseg_despeckle_maps_host(int n, const uint8_t* const* ink, const int* H, const int* W, const pseg_despeckle* how,

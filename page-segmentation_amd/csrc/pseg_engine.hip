@@ -10,7 +10,7 @@
 #include <map>
 #include <mutex>
 
-#include "pseg_common.h"
+#include "pseg_list.h"
 
 namespace pseg {
 
@@ -1258,11 +1258,7 @@ int pseg::create_engine(int arch, int n_classes, int in_channels, int device, in
     if (n_classes < 1 || n_classes > 256) return fail(PSEG_EINVAL, "n_classes %d out of range", n_classes);
     if (in_channels != 1 && in_channels != 3) return fail(PSEG_EINVAL, "in_channels must be 1 or 3");
     if (mode != PSEG_MODE_F32_EXACT && mode != PSEG_MODE_BF16) return fail(PSEG_EINVAL, "bad mode %d", mode);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        return fail(PSEG_EHIP, "no HIP device visible: libpseg has no CPU fallback");
-    if (device < 0 || device >= ndev) return fail(PSEG_EINVAL, "device %d of %d", device, ndev);
-    PSEG_HIP(hipSetDevice(device));
+    PSEG_TRY(open_device(device));
     auto* h = new pseg_engine();
     Engine& e = h->e;
     e.knobs = inherit ? inherit : knobs_snapshot(plan);   // the knobs are read here, once per engine, never per launch

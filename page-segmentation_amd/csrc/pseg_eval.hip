@@ -10,7 +10,7 @@
 #include <cstring>
 #include <vector>
 
-#include "pseg_common.h"
+#include "pseg_list.h"
 
 #include <rocprim/rocprim.hpp>
 
@@ -183,15 +183,6 @@ __global__ __launch_bounds__(256) void comp_hist_kernel(const int* lab, const vo
     }
 }
 
-static int set_dev_eval(int device) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n == 0)
-        return fail(PSEG_EHIP, "no HIP device visible: libpseg has no CPU fallback");
-    if (device < 0 || device >= n) return fail(PSEG_EINVAL, "device %d of %d", device, n);
-    PSEG_HIP(hipSetDevice(device));
-    return PSEG_OK;
-}
-
 struct DevBuf {                    // scope-bound device allocation
     void* p = nullptr;
     ~DevBuf() { if (p) (void)hipFree(p); }
@@ -220,7 +211,7 @@ int pseg_eval_confusion(int device, const void* pred, int pred_bytes, const void
     const size_t slots = (size_t)2 * K * K;
     std::memset(counts, 0, slots * 8);
     if (n == 0) return PSEG_OK;
-    PSEG_TRY(set_dev_eval(device));
+    PSEG_TRY(open_device(device));
     DevBuf dp, dm, db, dc;
     PSEG_TRY(dp.alloc((size_t)n * pred_bytes));
     PSEG_TRY(dm.alloc((size_t)n * mask_bytes));
@@ -246,7 +237,7 @@ int pseg_cc_label(int device, const uint8_t* binary, int H, int W, int connectiv
     *num_labels = 1;
     if (H == 0 || W == 0) return PSEG_OK;
     if ((int64_t)H * W > 0x7fffffffLL) return fail(PSEG_EUNSUPPORTED, "page too large for 32-bit component indices");
-    PSEG_TRY(set_dev_eval(device));
+    PSEG_TRY(open_device(device));
     const int n = H * W, grid = cdiv(n, 256);
     DevBuf dbin, dL, dkey, dflag, dpos, dtmp;
     PSEG_TRY(dbin.alloc(n));
@@ -310,7 +301,7 @@ int pseg_cc_tables(int device, const int32_t* labels, int H, int W, int num_labe
     if (hist_pred) std::memset(hist_pred, 0, (size_t)num_labels * K * 8);
     if (hist_mask) std::memset(hist_mask, 0, (size_t)num_labels * K * 8);
     if (n == 0) return PSEG_OK;
-    PSEG_TRY(set_dev_eval(device));
+    PSEG_TRY(open_device(device));
     const int grid = cdiv(n, 256);
     hipStream_t st = 0;
     DevBuf dlab;

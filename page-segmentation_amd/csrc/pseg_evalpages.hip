@@ -14,10 +14,9 @@
 // ever decrease, so a chain is shorter than the index space, and the larger root of a union strictly decreases from try to try).
 #include <algorithm>
 #include <cstring>
-#include <mutex>
 #include <vector>
 
-#include "pseg_common.h"
+#include "pseg_list.h"
 
 namespace pseg {
 
@@ -31,9 +30,6 @@ constexpr int EP_RIM = 2 * (EP_TH + EP_TW);
 constexpr int EP_TASK_MAX = 192;
 constexpr int EP_RULES = 8, EP_WATCH = 2 * EP_RULES;
 constexpr int EP_VER = EP_RULES * 4 + 1;           // a page's verdict counters, then its component count
-// how pseg_eval_pages cuts its list into groups (include/pseg.h)
-constexpr int EP_GROUP_PAGES = 64;
-constexpr size_t EP_GROUP_PIXELS = (size_t)64 << 20;
 constexpr int EP_HIST_BLOCKS = 256;                // histogram workgroups of one page, at most
 
 // li / fi: place of the rule's label / filter label among the watched labels, -1: none (cc_equal has no label; filter label 0 is no filter)
@@ -537,31 +533,16 @@ __global__ __launch_bounds__(256) void ep_judge_kernel(const EpRules* __restrict
 // ---- workspace: grow-only, one per device (table, records, the group's maps, the per-tile arrays; a page-locked copy of table and
 // records), under its own lock and on its own stream; a call holds the lock to its end and every group ends synchronised.
 // pseg_release_workspace frees it.
-struct EpWs { GrowDev dev; GrowPin pin; hipStream_t st = nullptr; };
-static std::mutex g_ep_mu[64];
-static EpWs g_ep_ws[64];
-
-void eval_pages_release_workspace(int dev) {
-    std::lock_guard<std::mutex> lk(g_ep_mu[dev & 63]);
-    EpWs& ws = g_ep_ws[dev & 63];
-    ws.dev.release();
-    ws.pin.release();
-    if (ws.st) (void)hipStreamDestroy(ws.st);
-    ws.st = nullptr;
-}
-
-static inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-// the end of the group that starts at page g0
-static int ep_group_end(int n, const int* H, const int* W, int g0) {
-    int g1 = g0;
-    size_t px = 0;
-    while (g1 < n && g1 - g0 < EP_GROUP_PAGES && (g1 == g0 || px + (size_t)H[g1] * W[g1] <= EP_GROUP_PIXELS)) {
-        px += (size_t)H[g1] * W[g1];
-        ++g1;
+struct EpWs {
+    GrowDev dev; GrowPin pin; hipStream_t st = nullptr;
+    void release() {
+        dev.release();
+        pin.release();
+        if (st) (void)hipStreamDestroy(st);
+        st = nullptr;
     }
-    return g1;
-}
+};
+static PerDevice<EpWs> g_ep;
 
 struct EpOut { std::vector<int64_t> counts, comps, verdicts; };
 
@@ -569,11 +550,11 @@ static int ep_group(EpWs& ws, int g0, int g1, const pseg_eval_page* pages, int n
     const int n = g1 - g0, K = ncls + 1;
     const size_t slots = (size_t)2 * K * K;
     const int ver0 = (int)slots, rec_words = (int)slots + EP_VER, cw = 2 + 2 * rules.n_watch;
-    const size_t tab_b = up256(sizeof(EpRules) + (size_t)EP_GROUP_PAGES * sizeof(EpPage)), rec_b = up256((size_t)n * rec_words * 8);
+    const size_t tab_b = up256(sizeof(EpRules) + (size_t)LIST_GROUP_ITEMS * sizeof(EpPage)), rec_b = up256((size_t)n * rec_words * 8);
     PSEG_TRY(ws.pin.ensure(tab_b + rec_b, "page-score records"));
     std::memcpy(ws.pin.p, &rules, sizeof(EpRules));
     EpPage* const h_tab = (EpPage*)(ws.pin.p + sizeof(EpRules));
-    size_t off = tab_b + rec_b;
+    Bump at{tab_b + rec_b};
     long long tiles = 0, blks = 0;
     for (int k = 0; k < n; ++k) {
         const pseg_eval_page& s = pages[g0 + k];
@@ -585,31 +566,25 @@ static int ep_group(EpWs& ws, int g0, int g1, const pseg_eval_page* pages, int n
         t.tile0 = (int)tiles;
         t.blk0 = (int)blks;
         t.nblk = bytes ? (int)std::max<size_t>(1, std::min<size_t>(EP_HIST_BLOCKS, ((bytes >> 4) + 1023) / 1024)) : 0;
-        t.pred = off; off += up256(bytes);
-        t.mask = off; off += up256(bytes);
-        t.bin = off;
-        if (t.has_bin) off += up256(bytes);
+        t.pred = at.take(bytes);
+        t.mask = at.take(bytes);
+        t.bin = at.take(t.has_bin ? bytes : 0);
         if (t.has_bin && bytes) tiles += (long long)t.tiles_x * cdiv(s.H, EP_TH);
         blks += t.nblk;
     }
     if (tiles * EP_OPEN_MAX > 0x7fffffffLL) return fail(PSEG_EUNSUPPORTED, "pages %d..%d: too many tiles for 32-bit slot ids", g0, g1 - 1);
     // per tile: 192 root slots (parent + cw counters each), the rim table, the task list, two list lengths
     const size_t nslots = (size_t)tiles * EP_OPEN_MAX;
-    const size_t o_par = off, o_cnt = o_par + up256(nslots * 4), o_rim = o_cnt + up256(nslots * cw * 4);
-    const size_t o_task = o_rim + up256((size_t)tiles * EP_RIM), o_rootn = o_task + up256((size_t)tiles * EP_TASK_MAX * 4);
-    const size_t o_taskn = o_rootn + up256((size_t)tiles * 4), total = o_taskn + up256((size_t)tiles * 4);
-    PSEG_TRY(ws.dev.ensure(total, "page-score workspace"));
+    const size_t o_par = at.take(nslots * 4), o_cnt = at.take(nslots * cw * 4), o_rim = at.take((size_t)tiles * EP_RIM);
+    const size_t o_task = at.take((size_t)tiles * EP_TASK_MAX * 4), o_rootn = at.take((size_t)tiles * 4), o_taskn = at.take((size_t)tiles * 4);
+    PSEG_TRY(ws.dev.ensure(at.off, "page-score workspace"));
     if (!ws.st) PSEG_HIP(hipStreamCreateWithFlags(&ws.st, hipStreamNonBlocking));
     hipStream_t st = ws.st;
     uint8_t* const d = ws.dev.p;
     const EpRules* const d_rules = (const EpRules*)d;
     const EpPage* const d_tab = (const EpPage*)(d + sizeof(EpRules));
     unsigned long long* const d_rec = (unsigned long long*)(d + tab_b);
-    struct Drain {                                                     // an error return in the middle leaves no copy from the caller's arrays in flight
-        hipStream_t s;
-        bool armed = true;
-        ~Drain() { if (armed) (void)hipStreamSynchronize(s); }
-    } drain{st};
+    GroupDrain drain{st};
     PSEG_HIP(hipMemcpyAsync(d, ws.pin.p, sizeof(EpRules) + (size_t)n * sizeof(EpPage), hipMemcpyHostToDevice, st));
     PSEG_HIP(hipMemsetAsync(d_rec, 0, (size_t)n * rec_words * 8, st));
     for (int k = 0; k < n; ++k) {
@@ -667,7 +642,7 @@ int pseg_eval_page_groups(int n_pages, const int* H, const int* W, int* first, i
         if (H[i] < 0 || W[i] < 0) return fail(PSEG_EINVAL, "page %d: negative size", i);
     int ng = 0;
     for (int g0 = 0; g0 < n_pages; ++ng) {
-        const int g1 = ep_group_end(n_pages, H, W, g0);
+        const int g1 = list_group_end(n_pages, g0, [&](int i) { return (size_t)H[i] * W[i]; });
         if (ng < max_groups) {
             if (first) first[ng] = g0;
             if (count) count[ng] = g1 - g0;
@@ -711,23 +686,13 @@ int pseg_eval_pages(int device, int n_pages, const pseg_eval_page* pages, int n_
         if ((int64_t)p.H * p.W > 0 && (!p.pred || !p.mask)) return fail(PSEG_EINVAL, "page %d: NULL map", i);
     }
     if (n_pages == 0) return PSEG_OK;
-    int nd = 0;
-    if (hipGetDeviceCount(&nd) != hipSuccess || nd == 0) return fail(PSEG_EHIP, "no HIP device visible: libpseg has no CPU fallback");
-    if (device < 0 || device >= nd) return fail(PSEG_EINVAL, "device %d of %d", device, nd);
-    PSEG_HIP(hipSetDevice(device));
-    std::lock_guard<std::mutex> lk(g_ep_mu[device & 63]);
     const size_t slots = (size_t)2 * (n_classes + 1) * (n_classes + 1);
     EpOut out;                                                         // the caller's arrays are written once every group has run
     if (counts) out.counts.assign((size_t)n_pages * slots, 0);
     if (components) out.comps.assign((size_t)n_pages, 0);
     if (verdicts && n_rules) out.verdicts.assign((size_t)n_pages * n_rules * 4, 0);
-    std::vector<int> H((size_t)n_pages), W((size_t)n_pages);
-    for (int i = 0; i < n_pages; ++i) { H[i] = pages[i].H; W[i] = pages[i].W; }
-    for (int g0 = 0; g0 < n_pages;) {
-        const int g1 = ep_group_end(n_pages, H.data(), W.data(), g0);
-        PSEG_TRY(ep_group(g_ep_ws[device & 63], g0, g1, pages, n_classes, connectivity, R, out));
-        g0 = g1;
-    }
+    PSEG_TRY(run_list(g_ep, device, n_pages, [&](int i) { return (size_t)pages[i].H * pages[i].W; },
+                      [&](EpWs& ws, int g0, int g1) { return ep_group(ws, g0, g1, pages, n_classes, connectivity, R, out); }));
     if (counts) std::copy(out.counts.begin(), out.counts.end(), counts);
     if (components) std::copy(out.comps.begin(), out.comps.end(), components);
     if (verdicts && n_rules) std::copy(out.verdicts.begin(), out.verdicts.end(), verdicts);

@@ -8,17 +8,14 @@
 // row's tail go byte by byte.  The colour table sits in LDS, one word per entry, and is searched linearly; the counts go into 257
 // LDS counters per workgroup, a thread adding once per stretch of equal ids, and the non-zero ones into the mask's row of 64-bit
 // counters with one vector atomic each.
-#include "pseg_common.h"
+#include "pseg_list.h"
 #include "pseg_labelmasks.h"
 
 #include <cstring>
-#include <mutex>
 
 namespace pseg {
 
 constexpr int LM_NTH = 256, LM_RUN = 8, LM_RUNS = 32, LM_TH = LM_NTH / LM_RUNS;    // threads, pixels per run, runs and rows per workgroup
-constexpr int LM_GROUP_MASKS = 64;                                                 // how pseg_label_masks cuts its list (include/pseg.h)
-constexpr size_t LM_GROUP_BYTES = (size_t)64 << 20;
 static_assert(LM_RUN == 8, "a full run is one uint2 store");
 static_assert((long long)LM_NTH * LM_RUN < (1ll << 32), "a workgroup's pixels fit a 32-bit counter");
 
@@ -31,7 +28,6 @@ struct LmMask {
     int tiles_x, blk0;                  // workgroups per band of LM_TH rows; workgroups of the group's masks in front of this one
 };
 
-static constexpr size_t lm_up256(size_t v) { return (v + 255) & ~(size_t)255; }
 static inline size_t lm_src_bytes(const pseg_mask_src& m) { return (size_t)m.H0 * m.W0 * m.channels; }
 // runs of a row: the head and the 8-byte words the row touches behind it
 static inline int lm_tiles_x(int W) { return cdiv(cdiv(W, LM_RUN) + 1, LM_RUNS); }
@@ -117,38 +113,23 @@ __global__ __launch_bounds__(LM_NTH) void lm_list_kernel(const LmMask* __restric
 
 // ---- workspace: grow-only, one per device (the group's table, colour table, counters, sources and label maps; a page-locked copy of
 // the tables and the counters' read-back slot); a call holds the device's lock to its end and ends synchronised.
-struct LmWs { GrowDev dev; GrowPin pin; };
-static std::mutex g_lm_mu[64];
-static LmWs g_lm_ws[64];
-
-void label_masks_release_workspace(int dev) {
-    std::lock_guard<std::mutex> lk(g_lm_mu[dev & 63]);
-    g_lm_ws[dev & 63].dev.release();
-    g_lm_ws[dev & 63].pin.release();
-}
+struct LmWs {
+    GrowDev dev; GrowPin pin;
+    void release() { dev.release(); pin.release(); }
+};
+static PerDevice<LmWs> g_lm;
 
 // the packed table of a checked colour list
 static void lm_table(const uint8_t* colors, const uint8_t* ids, int n_colors, uint32_t* tab) {
     for (int k = 0; k < n_colors; ++k) tab[k] = lm_pack(colors[3 * k], colors[3 * k + 1], colors[3 * k + 2], ids[k]);
 }
 
-// where the group that starts at g0 ends: 64 masks, or before 64 MiB of source bytes are passed (a single mask may pass them)
-static int lm_group_end(int n, const pseg_mask_src* masks, int g0) {
-    int g1 = g0;
-    size_t bytes = 0;
-    while (g1 < n && g1 - g0 < LM_GROUP_MASKS && (g1 == g0 || bytes + lm_src_bytes(masks[g1]) <= LM_GROUP_BYTES)) {
-        bytes += lm_src_bytes(masks[g1]);
-        ++g1;
-    }
-    return g1;
-}
-
 static int lm_group(LmWs& ws, int g0, int g1, const pseg_mask_src* masks, const int* H, const int* W, const uint32_t* table, int n_colors,
                     uint8_t* const* out_labels, int64_t* out_counts) {
     const int n = g1 - g0;
-    constexpr size_t tab_b = lm_up256((size_t)LM_GROUP_MASKS * sizeof(LmMask));
-    constexpr size_t col_b = lm_up256((size_t)LM_COLORS_MAX * sizeof(uint32_t));
-    constexpr size_t cnt_b = lm_up256((size_t)LM_GROUP_MASKS * LM_BINS * sizeof(unsigned long long));
+    constexpr size_t tab_b = up256((size_t)LIST_GROUP_ITEMS * sizeof(LmMask));
+    constexpr size_t col_b = up256((size_t)LM_COLORS_MAX * sizeof(uint32_t));
+    constexpr size_t cnt_b = up256((size_t)LIST_GROUP_ITEMS * LM_BINS * sizeof(unsigned long long));
     PSEG_TRY(ws.pin.ensure(tab_b + col_b + cnt_b, "label-map tables"));
     LmMask* const h_tab = ws.pin.as<LmMask>();
     uint32_t* const h_col = (uint32_t*)(ws.pin.p + tab_b);
@@ -157,7 +138,7 @@ static int lm_group(LmWs& ws, int g0, int g1, const pseg_mask_src* masks, const 
     memset(h_col, 0, col_b);
     memcpy(h_col, table, (size_t)n_colors * sizeof(uint32_t));
     std::vector<size_t> o_src(n), o_out(n);
-    size_t off = tab_b + col_b + cnt_b;
+    Bump at{tab_b + col_b + cnt_b};
     long long blocks = 0;
     for (int k = 0; k < n; ++k) {
         const int i = g0 + k;
@@ -169,10 +150,10 @@ static int lm_group(LmWs& ws, int g0, int g1, const pseg_mask_src* masks, const 
         s.blk0 = (int)blocks;
         blocks += (long long)s.tiles_x * cdiv(s.H, LM_TH);
         if (blocks > 0x7fffffffLL) return fail(PSEG_EUNSUPPORTED, "masks %d..%d: too many tiles for one launch", g0, g1 - 1);
-        o_src[k] = off; off += lm_up256(lm_src_bytes(masks[i]));
-        o_out[k] = off; off += lm_up256((size_t)s.H * s.W);
+        o_src[k] = at.take(lm_src_bytes(masks[i]));
+        o_out[k] = at.take((size_t)s.H * s.W);
     }
-    PSEG_TRY(ws.dev.ensure(off, "label-map workspace"));
+    PSEG_TRY(ws.dev.ensure(at.off, "label-map workspace"));
     uint8_t* const d = ws.dev.p;
     for (int k = 0; k < n; ++k) {
         h_tab[k].src = d + o_src[k];
@@ -181,10 +162,7 @@ static int lm_group(LmWs& ws, int g0, int g1, const pseg_mask_src* masks, const 
     const uint32_t* const d_col = (const uint32_t*)(d + tab_b);
     unsigned long long* const d_cnt = (unsigned long long*)(d + tab_b + col_b);
     hipStream_t st = nullptr;
-    struct Drain {                                                     // an error return in the middle leaves no copy from / to the caller's arrays in flight
-        bool armed = true;
-        ~Drain() { if (armed) (void)hipStreamSynchronize(nullptr); }
-    } drain;
+    GroupDrain drain{st};
     PSEG_HIP(hipMemcpyAsync(d, h_tab, tab_b + col_b, hipMemcpyHostToDevice, st));
     for (int k = 0; k < n; ++k) PSEG_HIP(hipMemcpyAsync(d + o_src[k], masks[g0 + k].px, lm_src_bytes(masks[g0 + k]), hipMemcpyHostToDevice, st));
     if (out_counts) {
@@ -258,17 +236,8 @@ int pseg_label_masks(int device, int n, const pseg_mask_src* masks, const int* H
     uint32_t table[LM_COLORS_MAX] = {0};
     PSEG_TRY(lm_check_list(n, masks, H, W, colors, ids, n_colors, out_labels, table));
     if (!colors || !ids) n_colors = 0;                                 // (only 1-channel masks, or no colours at all)
-    int nd = 0;
-    if (hipGetDeviceCount(&nd) != hipSuccess || nd == 0) return fail(PSEG_EHIP, "no HIP device visible: libpseg has no CPU fallback");
-    if (device < 0 || device >= nd) return fail(PSEG_EINVAL, "device %d of %d", device, nd);
-    PSEG_HIP(hipSetDevice(device));
-    std::lock_guard<std::mutex> lk(g_lm_mu[device & 63]);
-    for (int g0 = 0; g0 < n;) {
-        const int g1 = lm_group_end(n, masks, g0);
-        PSEG_TRY(lm_group(g_lm_ws[device & 63], g0, g1, masks, H, W, table, n_colors, out_labels, out_counts));
-        g0 = g1;
-    }
-    return PSEG_OK;
+    return run_list(g_lm, device, n, [&](int i) { return lm_src_bytes(masks[i]); },
+                    [&](LmWs& ws, int g0, int g1) { return lm_group(ws, g0, g1, masks, H, W, table, n_colors, out_labels, out_counts); });
 }
 
 int pseg_label_masks_host(int n, const pseg_mask_src* masks, const int* H, const int* W, const uint8_t* colors, const uint8_t* ids, int n_colors,
@@ -285,8 +254,8 @@ int pseg_label_masks_geometry(int* run, int* runs, int* rows, int* group_masks, 
     if (run) *run = LM_RUN;
     if (runs) *runs = LM_RUNS;
     if (rows) *rows = LM_TH;
-    if (group_masks) *group_masks = LM_GROUP_MASKS;
-    if (group_bytes) *group_bytes = (int64_t)LM_GROUP_BYTES;
+    if (group_masks) *group_masks = LIST_GROUP_ITEMS;
+    if (group_bytes) *group_bytes = (int64_t)LIST_GROUP_BYTES;
     return PSEG_OK;
 }
 
@@ -297,7 +266,7 @@ int pseg_label_masks_groups(int n, const pseg_mask_src* masks, int* group_of) {
             return fail(PSEG_EINVAL, "mask %d: empty shape, or channels other than 1 or 3", i);
     int g = 0;
     for (int g0 = 0; g0 < n; ++g) {
-        const int g1 = lm_group_end(n, masks, g0);
+        const int g1 = list_group_end(n, g0, [&](int i) { return lm_src_bytes(masks[i]); });
         for (int i = g0; i < g1; ++i) group_of[i] = g;
         g0 = g1;
     }

@@ -12,10 +12,9 @@
 // more than CH_LEFT, CH_RIGHT columns or CH_BELOW rows, so neither it nor the component it is part of passes the filter; a fragment
 // that reaches the top side has its first pixel above the owned tile; every other fragment is a whole component of the scan, and its
 // first pixel lies in exactly one owned tile.  So the filter on the fragment's box IS the test, and no side has to be looked at.
-#include "pseg_common.h"
+#include "pseg_list.h"
 
 #include <algorithm>
-#include <mutex>
 
 namespace pseg {
 
@@ -35,9 +34,6 @@ constexpr int CH_BIN0 = GLYPH_H_LO + 1, CH_NBINS = GLYPH_H_HI - GLYPH_H_LO - 1; 
 // a scan's record, 32-bit words: the histogram, the threshold, the height bins
 constexpr int CH_REC_HIST = 0, CH_REC_THR = 256, CH_REC_BINS = 260, CH_REC_WORDS = 320;
 static_assert(CH_REC_BINS + CH_NBINS <= CH_REC_WORDS, "record layout");
-// how pseg_char_heights cuts its list into groups (include/pseg.h)
-constexpr int CH_GROUP_SCANS = 64;
-constexpr size_t CH_GROUP_BYTES = (size_t)64 << 20;
 constexpr int CH_HIST_BLOCKS = 256;                                    // histogram workgroups of one scan, at most
 
 // one scan of a group: the prefix tables of the ragged launches (tile0: window workgroups, blk0: histogram workgroups in front of it)
@@ -265,15 +261,11 @@ __global__ __launch_bounds__(CH_NTH) void ch_window_kernel(const uint8_t* __rest
 
 // ---- workspace: grow-only, one per device (the group's table, records and scan bytes; a page-locked copy of table and records);
 // a call holds the device's lock to its end and ends synchronised.  pseg_release_workspace frees it.
-struct ChWs { GrowDev dev; GrowPin pin; };
-static std::mutex g_ch_mu[64];
-static ChWs g_ch_ws[64];
-
-void char_heights_release_workspace(int dev) {
-    std::lock_guard<std::mutex> lk(g_ch_mu[dev & 63]);
-    g_ch_ws[dev & 63].dev.release();
-    g_ch_ws[dev & 63].pin.release();
-}
+struct ChWs {
+    GrowDev dev; GrowPin pin;
+    void release() { dev.release(); pin.release(); }
+};
+static PerDevice<ChWs> g_ch;
 
 // upper median of the heights a record's bins hold: the smallest h whose cumulative count exceeds n / 2 -- hs[hs.size() / 2] of the sorted list
 static int median_from_bins(const unsigned* bins, int n_bins, int first) {
@@ -289,11 +281,11 @@ static int median_from_bins(const unsigned* bins, int n_bins, int first) {
 
 static int ch_group(ChWs& ws, int g0, int g1, const uint8_t* const* gray, const int* H, const int* W, int inverse, int* heights, int* otsu) {
     const int n = g1 - g0;
-    constexpr size_t tab_b = (size_t)CH_GROUP_SCANS * sizeof(ChScan), rec_b = (size_t)CH_GROUP_SCANS * CH_REC_WORDS * 4;
+    constexpr size_t tab_b = (size_t)LIST_GROUP_ITEMS * sizeof(ChScan), rec_b = (size_t)LIST_GROUP_ITEMS * CH_REC_WORDS * 4;
     static_assert(tab_b % 16 == 0 && rec_b % 16 == 0, "the scans start 16-byte aligned");
     PSEG_TRY(ws.pin.ensure(tab_b + rec_b, "line-height records"));
     ChScan* const h_tab = ws.pin.as<ChScan>();
-    size_t off = tab_b + rec_b;
+    Bump at{tab_b + rec_b};
     long long tiles = 0, blks = 0;
     for (int k = 0; k < n; ++k) {
         ChScan& s = h_tab[k];
@@ -303,21 +295,17 @@ static int ch_group(ChWs& ws, int g0, int g1, const uint8_t* const* gray, const 
         s.tile0 = (int)tiles;
         s.blk0 = (int)blks;
         s.nblk = (int)std::max<size_t>(1, std::min<size_t>(CH_HIST_BLOCKS, ((bytes >> 4) + 1023) / 1024));
-        s.off = off;
-        off += (bytes + 15) & ~(size_t)15;
+        s.off = at.take(bytes, 16);
         tiles += (long long)s.tiles_x * cdiv(s.H, CH_TH);
         blks += s.nblk;
     }
     if (tiles > 0x7fffffffLL) return fail(PSEG_EUNSUPPORTED, "scans %d..%d: too many tiles for one launch", g0, g1 - 1);
-    PSEG_TRY(ws.dev.ensure(off, "line-height workspace"));
+    PSEG_TRY(ws.dev.ensure(at.off, "line-height workspace"));
     uint8_t* const d = ws.dev.p;
     ChScan* const d_tab = (ChScan*)d;
     unsigned* const d_rec = (unsigned*)(d + tab_b);
     hipStream_t st = nullptr;
-    struct Drain {                                                     // an error return in the middle leaves no copy from the caller's arrays in flight
-        bool armed = true;
-        ~Drain() { if (armed) (void)hipStreamSynchronize(nullptr); }
-    } drain;
+    GroupDrain drain{st};
     PSEG_HIP(hipMemcpyAsync(d_tab, h_tab, (size_t)n * sizeof(ChScan), hipMemcpyHostToDevice, st));
     PSEG_HIP(hipMemsetAsync(d_rec, 0, (size_t)n * CH_REC_WORDS * 4, st));
     for (int k = 0; k < n; ++k)
@@ -352,22 +340,9 @@ int pseg_char_heights(int device, int n, const uint8_t* const* gray, const int* 
         if (H[i] <= 0 || W[i] <= 0) return fail(PSEG_EINVAL, "scan %d: empty image", i);
         if ((int64_t)H[i] * W[i] > 0x7fffffffLL) return fail(PSEG_EUNSUPPORTED, "scan %d: image too large", i);
     }
-    int nd = 0;
-    if (hipGetDeviceCount(&nd) != hipSuccess || nd == 0) return fail(PSEG_EHIP, "no HIP device visible: libpseg has no CPU fallback");
-    if (device < 0 || device >= nd) return fail(PSEG_EINVAL, "device %d of %d", device, nd);
-    PSEG_HIP(hipSetDevice(device));
-    std::lock_guard<std::mutex> lk(g_ch_mu[device & 63]);
     std::vector<int> hs((size_t)n), ts((size_t)n);                     // the caller's arrays are written once every group has run
-    for (int g0 = 0; g0 < n;) {
-        int g1 = g0;
-        size_t bytes = 0;
-        while (g1 < n && g1 - g0 < CH_GROUP_SCANS && (g1 == g0 || bytes + (size_t)H[g1] * W[g1] <= CH_GROUP_BYTES)) {
-            bytes += (size_t)H[g1] * W[g1];
-            ++g1;
-        }
-        PSEG_TRY(ch_group(g_ch_ws[device & 63], g0, g1, gray, H, W, inverse, hs.data(), ts.data()));
-        g0 = g1;
-    }
+    PSEG_TRY(run_list(g_ch, device, n, [&](int i) { return (size_t)H[i] * W[i]; },
+                      [&](ChWs& ws, int g0, int g1) { return ch_group(ws, g0, g1, gray, H, W, inverse, hs.data(), ts.data()); }));
     std::copy(hs.begin(), hs.end(), heights);
     if (otsu) std::copy(ts.begin(), ts.end(), otsu);
     return PSEG_OK;

@@ -28,9 +28,8 @@
 // band as a dynamic and as a fixed block and packs the cheaper one (pass B; the dynamic header goes into the bit buffer in front
 // of segment 0).  A band that stays fixed is level 0's band bit for bit, so no band outgrows png_band_bound.
 #include <algorithm>
-#include <mutex>
 
-#include "pseg_common.h"
+#include "pseg_list.h"
 
 namespace pseg {
 
@@ -782,19 +781,11 @@ static int png_fill_crcs(uint8_t* png, size_t total) {
 
 // ---- workspace: grow-only, one per device (band slots, band tables, the assembled streams); a call holds the device's lock to
 // its end and ends synchronised, so one call at a time uses it.  pseg_release_workspace frees it. -------------------------------
-struct PngWs { void* p = nullptr; size_t bytes = 0; };
-static std::mutex g_png_mu[64];
-static PngWs g_png_ws[64];
-
-void png_release_workspace(int dev) {
-    std::lock_guard<std::mutex> lk(g_png_mu[dev & 63]);
-    PngWs& w = g_png_ws[dev & 63];
-    if (w.p) (void)hipFree(w.p);
-    w.p = nullptr;
-    w.bytes = 0;
-}
-
-static inline size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
+struct PngWs {
+    GrowDev dev;
+    void release() { dev.release(); }
+};
+static PerDevice<PngWs> g_png;
 
 // Encodes `nout` images of one shape from `src` (output k = mask mask_id[k]) into host[k]; synchronises `st`.
 template <class SRC>
@@ -808,30 +799,21 @@ static int png_run(int device, const SRC& src, int H, int W, int C, int band_row
     J.slot = (png_band_bound((size_t)J.R * J.L) + 3) & ~(size_t)3;
     J.page = 0;
     J.tab = nullptr; J.npages = 0; J.pred_alt = nullptr;
-    const size_t slots_b = al256((size_t)J.nb * J.slot), meta_b = al256((size_t)J.nb * sizeof(PngBandMeta)), offs_b = al256((size_t)J.nb * 8),
-                 out_b = al256(bound + 32);
-    const size_t per = slots_b + meta_b + offs_b + out_b, need = 256 + (size_t)nout * per;
-    std::lock_guard<std::mutex> lk(g_png_mu[device & 63]);
-    PngWs& w = g_png_ws[device & 63];
-    if (w.bytes < need) {
-        if (w.p) (void)hipFree(w.p);
-        w.p = nullptr;
-        w.bytes = 0;
-        if (hipMalloc(&w.p, need) != hipSuccess) {
-            w.p = nullptr;
-            (void)hipGetLastError();
-            return fail(PSEG_ENOMEM, "hipMalloc(png workspace, %zu bytes) failed", need);
-        }
-        w.bytes = need;
-    }
-    uint8_t* base = (uint8_t*)w.p;
+    Bump blk;                                                          // one output's block: band slots, band table, offsets, stream
+    const size_t o_slots = blk.take((size_t)J.nb * J.slot), o_meta = blk.take((size_t)J.nb * sizeof(PngBandMeta)),
+                 o_offs = blk.take((size_t)J.nb * 8), o_out = blk.take(bound + 32);
+    const size_t per = blk.off, need = 256 + (size_t)nout * per;
+    std::lock_guard<std::mutex> lk(g_png.mu[device]);
+    GrowDev& w = g_png.ws[device].dev;
+    PSEG_TRY(w.ensure(need, "png workspace"));
+    uint8_t* base = w.p;
     J.total = (unsigned long long*)base;
     for (int k = 0; k < 4; ++k) {
         uint8_t* q = base + 256 + (size_t)std::min(k, nout - 1) * per;
-        J.slots[k] = q;
-        J.meta[k] = (PngBandMeta*)(q + slots_b);
-        J.offs[k] = (unsigned long long*)(q + slots_b + meta_b);
-        J.out[k] = q + slots_b + meta_b + offs_b;
+        J.slots[k] = q + o_slots;
+        J.meta[k] = (PngBandMeta*)(q + o_meta);
+        J.offs[k] = (unsigned long long*)(q + o_offs);
+        J.out[k] = q + o_out;
         J.mask_id[k] = mask_id[std::min(k, nout - 1)];
     }
     if (level == 0) png_band_kernel<SRC, 0><<<dim3(J.nb, nout), PNG_T, 0, st>>>(src, J);
@@ -862,12 +844,12 @@ int png_pages_layout(int H, int W, int level, int nout, int pages, PngPages* L) 
     const int R = png_rows(H, W, 3, 0, level), nb = (int)(((size_t)H + R - 1) / R);
     const size_t Lb = (size_t)W * 3 + 1, slot = (png_band_bound((size_t)R * Lb) + 3) & ~(size_t)3;
     L->bound = png_bound(H, W, 3, 0, level);
-    L->slots_b = al256((size_t)nb * slot);
-    L->meta_b = al256((size_t)nb * sizeof(PngBandMeta));
-    L->offs_b = al256((size_t)nb * 8);
-    L->per = L->slots_b + L->meta_b + L->offs_b + al256(L->bound + 32);
+    L->slots_b = up256((size_t)nb * slot);
+    L->meta_b = up256((size_t)nb * sizeof(PngBandMeta));
+    L->offs_b = up256((size_t)nb * 8);
+    L->per = L->slots_b + L->meta_b + L->offs_b + up256(L->bound + 32);
     L->page = (size_t)nout * L->per;
-    L->head = al256((size_t)pages * 4 * sizeof(unsigned long long));
+    L->head = up256((size_t)pages * 4 * sizeof(unsigned long long));
     L->bytes = L->head + (size_t)pages * L->page;
     return PSEG_OK;
 }
@@ -908,7 +890,7 @@ int png_pages_enqueue(const PngPages& L, uint8_t* d_ws, const uint8_t* d_pred, s
 int png_pages_layout_mixed(int level, int nout, int pages, MixedPage* tab, PngPagesMixed* L) {
     if (!tab || !L || (level != 0 && level != 1) || nout < 1 || nout > 4 || pages < 1 || pages > PNG_MIXED_MAX)
         return fail(PSEG_EINVAL, "png: a ragged launch of %d pages (1..%d), %d outputs, level %d", pages, PNG_MIXED_MAX, nout, level);
-    L->head = al256((size_t)pages * 4 * sizeof(unsigned long long));
+    L->head = up256((size_t)pages * 4 * sizeof(unsigned long long));
     size_t pos = L->head;
     long long bands = 0;
     for (int p = 0; p < pages; ++p) {
@@ -919,10 +901,10 @@ int png_pages_layout_mixed(int level, int nout, int pages, MixedPage* tab, PngPa
         m.L = m.Wl * 3 + 1;
         m.slot = (png_band_bound((size_t)m.R * m.L) + 3) & ~(size_t)3;
         m.bound = png_bound(m.Hl, m.Wl, 3, 0, level);
-        m.slots_b = al256((size_t)m.nb * m.slot);
-        m.meta_b = al256((size_t)m.nb * sizeof(PngBandMeta));
-        m.offs_b = al256((size_t)m.nb * 8);
-        m.per = m.slots_b + m.meta_b + m.offs_b + al256(m.bound + 32);
+        m.slots_b = up256((size_t)m.nb * m.slot);
+        m.meta_b = up256((size_t)m.nb * sizeof(PngBandMeta));
+        m.offs_b = up256((size_t)m.nb * 8);
+        m.per = m.slots_b + m.meta_b + m.offs_b + up256(m.bound + 32);
         m.ws_off = pos;
         m.band0 = (int)bands;
         m.pad = 0;
@@ -981,15 +963,6 @@ int png_pages_enqueue_mixed(const PngPagesMixed& L, const MixedPage* h_tab, cons
 
 int png_finish_host(uint8_t* png, size_t total) { return png_fill_crcs(png, total); }
 
-static int png_set_dev(int device) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n == 0)
-        return fail(PSEG_EHIP, "no HIP device visible: libpseg has no CPU fallback");
-    if (device < 0 || device >= n) return fail(PSEG_EINVAL, "device %d of %d", device, n);
-    PSEG_HIP(hipSetDevice(device));
-    return PSEG_OK;
-}
-
 static int png_check(int H, int W, int channels, int band_rows, int level) {
     if (level != 0 && level != 1) return fail(PSEG_EINVAL, "png: level %d (0 = fixed Huffman codes, 1 = dynamic codes per band)", level);
     if (H < 1 || W < 1) return fail(PSEG_EINVAL, "png: image of %d x %d pixels", H, W);
@@ -1027,7 +1000,7 @@ int pseg_png_encode_device_lv(int device, const uint8_t* d_src, int H, int W, in
     PSEG_TRY(png_check(H, W, channels, band_rows, level));
     if (cap < png_bound(H, W, channels, band_rows, level))
         return fail(PSEG_EINVAL, "png: output buffer of %zu bytes, pseg_png_bound is %zu", cap, png_bound(H, W, channels, band_rows, level));
-    PSEG_TRY(png_set_dev(device));
+    PSEG_TRY(open_device(device));
     PngSrcPlain src{d_src, W, channels};
     uint8_t* const host[4] = {out, nullptr, nullptr, nullptr};
     size_t* const nb[4] = {n_bytes, nullptr, nullptr, nullptr};
@@ -1056,7 +1029,7 @@ int pseg_masks_png_device_u8_lv(int device, const uint8_t* d_pred, const uint8_t
         ++nout;
     }
     if (nout == 0) return PSEG_OK;
-    PSEG_TRY(png_set_dev(device));
+    PSEG_TRY(open_device(device));
     PngSrcMasks src{d_pred, d_binary, d_lut, n_lut, W};
     return png_run(device, src, H, W, 3, band_rows, level, nout, host, nb, ids, (hipStream_t)stream);
 }
@@ -1071,7 +1044,7 @@ int pseg_png_encode_lv(int device, const uint8_t* src, int H, int W, int channel
     PSEG_TRY(png_check(H, W, channels, band_rows, level));
     if (cap < png_bound(H, W, channels, band_rows, level))
         return fail(PSEG_EINVAL, "png: output buffer of %zu bytes, pseg_png_bound is %zu", cap, png_bound(H, W, channels, band_rows, level));
-    PSEG_TRY(png_set_dev(device));
+    PSEG_TRY(open_device(device));
     const size_t n = (size_t)H * W * channels;
     uint8_t* d = nullptr;
     if (hipMalloc((void**)&d, n) != hipSuccess) { (void)hipGetLastError(); return fail(PSEG_ENOMEM, "hipMalloc failed in png_encode"); }
@@ -1090,7 +1063,7 @@ int pseg_masks_png_lv(int device, const int64_t* pred, const uint8_t* binary, co
     if (!pred || !binary || !lut || !out || !cap || !n_bytes) return fail(PSEG_EINVAL, "NULL argument");
     if (n_lut < 1 || n_lut > 256) return fail(PSEG_EINVAL, "n_lut %d out of range (1..256)", n_lut);
     PSEG_TRY(png_check(H, W, 3, band_rows, level));
-    PSEG_TRY(png_set_dev(device));
+    PSEG_TRY(open_device(device));
     const size_t n = (size_t)H * W;
     // labels outside the colour table are black (masks_kernel): on the uint8 map they become 255, which is black while the table
     // has fewer than 256 entries

@@ -10,12 +10,11 @@
 //   pngdec_unfilter_kernel  64 rows per pass, lane k on row r0 + k one byte behind lane k - 1: "up" is the neighbour lane's last
 //                           result, "left" and "upper left" a per-lane history of bpp bytes; writes the gray scan.
 // The file's record carries its status; a file that fails anywhere writes no output byte.
-#include "pseg_common.h"
+#include "pseg_list.h"
 #include "pseg_pngdec.h"
 
 #include <algorithm>
 #include <cstring>
-#include <mutex>
 
 namespace pseg {
 
@@ -25,8 +24,6 @@ constexpr unsigned PD_WIN = 8192;                                      // input 
 constexpr unsigned PD_FLUSH = 16384;                                   // the ring is flushed once this much is waiting
 constexpr unsigned PD_PIECE = 8192;                                    // stored blocks enter the ring in pieces of this size
 static_assert(PD_RING >= 32768 + PD_FLUSH + 16 + 258 && PD_RING >= 32768 + PD_FLUSH + 16 + PD_PIECE, "a write never lands on a byte that waits for its flush or that a match may still read");
-constexpr int PD_GROUP_FILES = 64;
-constexpr size_t PD_GROUP_BYTES = (size_t)64 << 20;
 
 struct PdRec {
     unsigned long long in_off, inf_off;                                // the file's IDAT bytes and inflated bytes in the workspace, 16-byte aligned
@@ -188,21 +185,19 @@ __global__ __launch_bounds__(PD_NTH) void pngdec_unfilter_kernel(uint8_t* ws, Pd
 }
 
 // ---- workspace: grow-only, one per device, guarded by its own lock; its own stream.  pseg_release_workspace frees it.
-struct PdWs { GrowDev dev; GrowPin pin, pin_out; hipStream_t st = nullptr; hipEvent_t ev = nullptr; };
-static std::mutex g_pd_mu[64];
-static PdWs g_pd_ws[64];
-
-void pngdec_release_workspace(int dev) {
-    std::lock_guard<std::mutex> lk(g_pd_mu[dev & 63]);
-    PdWs& ws = g_pd_ws[dev & 63];
-    ws.dev.release();
-    ws.pin.release();
-    ws.pin_out.release();
-    if (ws.st) (void)hipStreamDestroy(ws.st);
-    if (ws.ev) (void)hipEventDestroy(ws.ev);
-    ws.st = nullptr;
-    ws.ev = nullptr;
-}
+struct PdWs {
+    GrowDev dev; GrowPin pin, pin_out; hipStream_t st = nullptr; hipEvent_t ev = nullptr;
+    void release() {
+        dev.release();
+        pin.release();
+        pin_out.release();
+        if (st) (void)hipStreamDestroy(st);
+        if (ev) (void)hipEventDestroy(ev);
+        st = nullptr;
+        ev = nullptr;
+    }
+};
+static PerDevice<PdWs> g_pd;
 
 struct PdFile { pngdec::Probe pr; std::vector<pngdec::Span> idat; };
 static inline size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
@@ -211,7 +206,7 @@ static inline size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
 // page-locked staging and reach outs[i] only for the files that decoded; else outs[i] is device memory the unfilter kernel writes.
 static int pd_group(PdWs& ws, const int* idx, int n, const uint8_t* const* files, const std::vector<PdFile>& pf, uint8_t* const* outs,
                     bool to_host, int* status) {
-    constexpr size_t rec_b = (size_t)PD_GROUP_FILES * sizeof(PdRec);
+    constexpr size_t rec_b = (size_t)LIST_GROUP_ITEMS * sizeof(PdRec);
     size_t idat_b = 0, inf_b = 0, gray_b = 0;
     for (int k = 0; k < n; ++k) {
         const pngdec::Probe& pr = pf[idx[k]].pr;
@@ -225,27 +220,21 @@ static int pd_group(PdWs& ws, const int* idx, int n, const uint8_t* const* files
     if (to_host) PSEG_TRY(ws.pin_out.ensure(rec_b + gray_b, "PNG decoder read-back"));
     uint8_t* const d = ws.dev.p;
     PdRec* const h_rec = ws.pin.as<PdRec>();
-    size_t in_off = rec_b, inf_off = rec_b + idat_b, gray_off = rec_b + idat_b + inf_b;
+    Bump in{rec_b}, inf{rec_b + idat_b}, gray{rec_b + idat_b + inf_b};
     for (int k = 0; k < n; ++k) {
         const PdFile& f = pf[idx[k]];
         PdRec& r = h_rec[k];
-        r.in_off = in_off; r.inf_off = inf_off;
         r.in_len = (unsigned)f.pr.n_idat;
         r.expect = (unsigned)((size_t)f.pr.H * ((size_t)f.pr.W * f.pr.channels + 1));
+        r.in_off = in.take(f.pr.n_idat, 16); r.inf_off = inf.take(r.expect, 16);
         r.H = f.pr.H; r.W = f.pr.W; r.ch = f.pr.channels; r.status = PSEG_OK;
-        r.out = to_host ? d + gray_off : outs[idx[k]];
-        uint8_t* dst = ws.pin.p + in_off;
+        r.out = to_host ? d + gray.take((size_t)r.H * r.W, 16) : outs[idx[k]];
+        uint8_t* dst = ws.pin.p + r.in_off;
         for (const pngdec::Span& s : f.idat) { memcpy(dst, files[idx[k]] + s.off, s.len); dst += s.len; }
         memset(dst, 0, up16(f.pr.n_idat) - f.pr.n_idat);
-        in_off += up16(f.pr.n_idat);
-        inf_off += up16(r.expect);
-        if (to_host) gray_off += up16((size_t)r.H * r.W);
     }
     hipStream_t st = ws.st;
-    struct Drain {
-        hipStream_t s; bool armed = true;
-        ~Drain() { if (armed) (void)hipStreamSynchronize(s); }
-    } drain{st};
+    GroupDrain drain{st};
     PSEG_HIP(hipMemcpyAsync(d, ws.pin.p, rec_b + idat_b, hipMemcpyHostToDevice, st));
     pngdec_inflate_kernel<<<(unsigned)n, PD_NTH, 0, st>>>(d, (PdRec*)d);
     pngdec_unfilter_kernel<<<(unsigned)n, PD_NTH, 0, st>>>(d, (PdRec*)d);
@@ -293,30 +282,22 @@ static int pd_decode(int device, int n, const uint8_t* const* files, const size_
         if (st[i] == PSEG_OK) ok.push_back(i);
     }
     if (!ok.empty()) {
-        int nd = 0;
-        if (hipGetDeviceCount(&nd) != hipSuccess || nd == 0) return fail(PSEG_EHIP, "no HIP device visible: libpseg has no CPU fallback");
-        if (device < 0 || device >= nd) return fail(PSEG_EINVAL, "device %d of %d", device, nd);
-        PSEG_HIP(hipSetDevice(device));
-        std::lock_guard<std::mutex> lk(g_pd_mu[device & 63]);
-        PdWs& ws = g_pd_ws[device & 63];
-        if (!ws.st) PSEG_HIP(hipStreamCreateWithFlags(&ws.st, hipStreamNonBlocking));
-        if (after) {                                                   // what the caller's stream still does with the outputs comes first
-            if (!ws.ev) PSEG_HIP(hipEventCreateWithFlags(&ws.ev, hipEventDisableTiming));
-            PSEG_HIP(hipEventRecord(ws.ev, after));
-            PSEG_HIP(hipStreamWaitEvent(ws.st, ws.ev, 0));
-        }
-        for (size_t g0 = 0; g0 < ok.size();) {
-            size_t g1 = g0, bytes = 0;
-            while (g1 < ok.size() && g1 - g0 < (size_t)PD_GROUP_FILES) {
-                const pngdec::Probe& pr = pf[ok[g1]].pr;
-                const size_t b = (size_t)pr.H * ((size_t)pr.W * pr.channels + 1);
-                if (g1 > g0 && bytes + b > PD_GROUP_BYTES) break;
-                bytes += b;
-                ++g1;
+        auto inflated = [&](int k) {
+            const pngdec::Probe& pr = pf[ok[k]].pr;
+            return (size_t)pr.H * ((size_t)pr.W * pr.channels + 1);
+        };
+        auto first = [&](PdWs& ws) {
+            if (!ws.st) PSEG_HIP(hipStreamCreateWithFlags(&ws.st, hipStreamNonBlocking));
+            if (after) {                                               // what the caller's stream still does with the outputs comes first
+                if (!ws.ev) PSEG_HIP(hipEventCreateWithFlags(&ws.ev, hipEventDisableTiming));
+                PSEG_HIP(hipEventRecord(ws.ev, after));
+                PSEG_HIP(hipStreamWaitEvent(ws.st, ws.ev, 0));
             }
-            PSEG_TRY(pd_group(ws, ok.data() + g0, (int)(g1 - g0), files, pf, outs, to_host, st.data()));
-            g0 = g1;
-        }
+            return (int)PSEG_OK;
+        };
+        PSEG_TRY(run_list(g_pd, device, (int)ok.size(), inflated, first, [&](PdWs& ws, int g0, int g1) {
+            return pd_group(ws, ok.data() + g0, g1 - g0, files, pf, outs, to_host, st.data());
+        }));
     }
     std::copy(st.begin(), st.end(), status);
     return PSEG_OK;

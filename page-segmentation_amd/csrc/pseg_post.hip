@@ -6,9 +6,8 @@
 // row-major access, wave-aggregated atomics where many lanes hit one counter.
 #include <algorithm>
 #include <cstring>
-#include <mutex>
 
-#include "pseg_common.h"
+#include "pseg_list.h"
 
 namespace pseg {
 
@@ -730,24 +729,24 @@ __global__ __launch_bounds__(256) void vote_apply_runs_kernel(const int* __restr
 // waits for that user's kernels, so two streams (or two threads) never run on the buffers at once.
 // pseg_release_workspace() frees it.
 struct VoteWs {
-    void* p[3] = {nullptr, nullptr, nullptr};
-    size_t bytes[3] = {0, 0, 0};
+    GrowDev buf[3];                    // page-global path: the label image, the histogram; tile path: the per-tile arrays
     hipEvent_t last = nullptr;
     hipStream_t last_stream = nullptr;
     bool used = false;
+    void release() {
+        if (used && last) (void)hipEventSynchronize(last);
+        for (GrowDev& b : buf) b.release();
+        if (last) (void)hipEventDestroy(last);
+        last = nullptr; used = false; last_stream = nullptr;
+    }
 };
-static std::mutex g_ws_mu;
-static VoteWs g_ws[64];
-
-int release_workspace(int dev) {
-    std::lock_guard<std::mutex> lk(g_ws_mu);
-    VoteWs& w = g_ws[dev & 63];
-    if (w.used && w.last) (void)hipEventSynchronize(w.last);
-    for (int i = 0; i < 3; ++i) { if (w.p[i]) (void)hipFree(w.p[i]); w.p[i] = nullptr; w.bytes[i] = 0; }
-    if (w.last) (void)hipEventDestroy(w.last);
-    w.last = nullptr; w.used = false; w.last_stream = nullptr;
-    return PSEG_OK;
-}
+static PerDevice<VoteWs> g_vote;
+// the two int64 planes of pseg_bbox_fill_device_u8 (kept between calls: 200 MB at 4096x3072 were allocated and freed per call)
+struct BoxWs {
+    GrowDev dev;
+    void release() { dev.release(); }
+};
+static PerDevice<BoxWs> g_box;
 
 template <typename LT>
 static int cc_vote_device(LT* d_pred, const uint8_t* d_bin, int H, int W, int ncls,
@@ -758,18 +757,14 @@ static int cc_vote_device(LT* d_pred, const uint8_t* d_bin, int H, int W, int nc
     const int n = H * W;
     int dev = 0;
     PSEG_HIP(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lk(g_ws_mu);
-    VoteWs& w = g_ws[dev & 63];
+    if (dev >= PSEG_MAX_DEVICES) return fail(PSEG_EUNSUPPORTED, "device %d: the per-device tables hold %d devices", dev, PSEG_MAX_DEVICES);
+    std::lock_guard<std::mutex> lk(g_vote.mu[dev]);
+    VoteWs& w = g_vote.ws[dev];
     if (!w.last) PSEG_HIP(hipEventCreateWithFlags(&w.last, hipEventDisableTiming));
-    auto need = [&](int slot, size_t bytes) -> void* {
-        if (w.bytes[slot] < bytes) {
-            if (w.used) (void)hipEventSynchronize(w.last);     // the previous user may still be running on the old block
-            if (w.p[slot]) (void)hipFree(w.p[slot]);
-            w.p[slot] = nullptr; w.bytes[slot] = 0;
-            if (hipMalloc(&w.p[slot], bytes) != hipSuccess) { w.p[slot] = nullptr; return nullptr; }
-            w.bytes[slot] = bytes;
-        }
-        return w.p[slot];
+    auto need = [&](int slot, size_t bytes) -> uint8_t* {      // NULL: PSEG_ENOMEM, the message set
+        GrowDev& b = w.buf[slot];
+        if (b.cap < bytes && w.used) (void)hipEventSynchronize(w.last);   // the previous user may still be running on the block ensure() frees
+        return b.ensure(bytes, "vote workspace") == PSEG_OK ? b.p : nullptr;
     };
     const int tiles = cdiv(W, CT_W) * cdiv(H, CT_H);
     const bool global_path = PSEG_KNOB("PSEG_CCL_GLOBAL") || ncls > V_NCLS_MAX;
@@ -779,7 +774,7 @@ static int cc_vote_device(LT* d_pred, const uint8_t* d_bin, int H, int W, int nc
         // page-global union-find over pixel indices: a label image and one row of counters per possible root
         int* d_L = (int*)need(0, (size_t)n * 4);
         int* d_hist = (int*)need(1, (size_t)n * ncls * 4);
-        if (!d_L || !d_hist) return fail(PSEG_ENOMEM, "hipMalloc(vote workspace) failed");
+        if (!d_L || !d_hist) return PSEG_ENOMEM;
         rc = ccl_run<0>(d_bin, nullptr, d_L, H, W, st, d_hist, ncls);     // the compress pass clears the roots' counters
         if (rc == PSEG_OK) {
             vote_count_kernel<LT><<<cdiv(W, VT) * cdiv(H, VT), 256, 0, st>>>(d_L, d_pred, d_hist, H, W, ncls);
@@ -788,16 +783,18 @@ static int cc_vote_device(LT* d_pred, const uint8_t* d_bin, int H, int W, int nc
     } else {
         // per tile: V_OPEN_MAX root slots (parent + a row of counters each), the rim table, the run list, two list lengths
         const size_t slots = (size_t)tiles * V_OPEN_MAX;
-        const size_t runs_b = (size_t)tiles * V_RUN_MAX * sizeof(VRun), par_b = slots * 4, hist_b = slots * ncls * 4, rim_b = round_up((size_t)tiles * V_RIM, (size_t)16);
-        const size_t task_b = (size_t)tiles * V_TASK_MAX * 2;
-        char* d_aux = (char*)need(2, runs_b + par_b + hist_b + rim_b + task_b + 3 * (size_t)tiles * 4);
-        if (!d_aux) return fail(PSEG_ENOMEM, "hipMalloc(vote workspace) failed");
-        VRun* d_runs = (VRun*)d_aux;
-        int* d_par = (int*)(d_aux + runs_b);
-        int* d_hist = (int*)(d_aux + runs_b + par_b);
-        uint8_t* d_rim = (uint8_t*)(d_aux + runs_b + par_b + hist_b);
-        unsigned short* d_tasks = (unsigned short*)(d_aux + runs_b + par_b + hist_b + rim_b);
-        int* d_rootn = (int*)(d_aux + runs_b + par_b + hist_b + rim_b + task_b);
+        Bump at;                                          // (the arrays lie packed: only the rim table's size is rounded, to 16)
+        const size_t o_runs = at.take((size_t)tiles * V_RUN_MAX * sizeof(VRun), 1), o_par = at.take(slots * 4, 1), o_hist = at.take(slots * ncls * 4, 1),
+                     o_rim = at.take((size_t)tiles * V_RIM, 16), o_tasks = at.take((size_t)tiles * V_TASK_MAX * 2, 1),
+                     o_rootn = at.take(3 * (size_t)tiles * 4, 1);
+        uint8_t* d_aux = need(2, at.off);
+        if (!d_aux) return PSEG_ENOMEM;
+        VRun* d_runs = (VRun*)(d_aux + o_runs);
+        int* d_par = (int*)(d_aux + o_par);
+        int* d_hist = (int*)(d_aux + o_hist);
+        uint8_t* d_rim = d_aux + o_rim;
+        unsigned short* d_tasks = (unsigned short*)(d_aux + o_tasks);
+        int* d_rootn = (int*)(d_aux + o_rootn);
         int* d_runn = d_rootn + tiles;
         int* d_taskn = d_runn + tiles;
         const size_t lds = (size_t)ncls * V_RUN_MAX * 2 + (size_t)ncls * CT_H * 8;
@@ -1066,22 +1063,13 @@ __global__ void binarize_kernel(const uint8_t* img, int n, int t, int inverse, u
 
 using namespace pseg;
 
-static int set_dev(int device) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n == 0)
-        return fail(PSEG_EHIP, "no HIP device visible: libpseg has no CPU fallback");
-    if (device < 0 || device >= n) return fail(PSEG_EINVAL, "device %d of %d", device, n);
-    PSEG_HIP(hipSetDevice(device));
-    return PSEG_OK;
-}
-
 extern "C" {
 
 int pseg_cc_vote_device(int device, int64_t* d_pred, const uint8_t* d_binary, int H, int W,
                         int n_classes, void* stream) {
     if (!d_pred || !d_binary) return fail(PSEG_EINVAL, "NULL argument");
     if (n_classes < 1) return fail(PSEG_EINVAL, "n_classes must be >= 1");
-    PSEG_TRY(set_dev(device));
+    PSEG_TRY(open_device(device));
     return cc_vote_device<int64_t>(d_pred, d_binary, H, W, n_classes, (hipStream_t)stream);
 }
 
@@ -1089,20 +1077,14 @@ int pseg_cc_vote_device_u8(int device, uint8_t* d_pred, const uint8_t* d_binary,
                            int n_classes, void* stream) {
     if (!d_pred || !d_binary) return fail(PSEG_EINVAL, "NULL argument");
     if (n_classes < 1 || n_classes > 256) return fail(PSEG_EINVAL, "n_classes must be in 1..256");
-    PSEG_TRY(set_dev(device));
+    PSEG_TRY(open_device(device));
     return cc_vote_device<uint8_t>(d_pred, d_binary, H, W, n_classes, (hipStream_t)stream);
 }
 
 int pseg_release_workspace(int device) {
-    PSEG_TRY(set_dev(device));
-    png_release_workspace(device);
-    char_heights_release_workspace(device);
-    pngdec_release_workspace(device);
-    eval_pages_release_workspace(device);
-    binarize_release_workspace(device);
-    label_masks_release_workspace(device);
-    regions_release_workspace(device);
-    return release_workspace(device);
+    PSEG_TRY(open_device(device));
+    release_workspaces(device);                                        // every PerDevice of the library (pseg_list.h)
+    return PSEG_OK;
 }
 
 int pseg_cc_vote(int device, int64_t* pred, const uint8_t* binary, int H, int W, int n_classes) {
@@ -1115,7 +1097,7 @@ int pseg_cc_vote(int device, int64_t* pred, const uint8_t* binary, int H, int W,
         for (size_t i = 0; i < n; ++i) m = std::max(m, pred[i]);
         n_classes = (int)m + 1;
     }
-    PSEG_TRY(set_dev(device));
+    PSEG_TRY(open_device(device));
     int64_t* d_pred = nullptr;
     uint8_t* d_bin = nullptr;
     PSEG_HIP(hipMalloc((void**)&d_pred, n * 8));
@@ -1139,7 +1121,7 @@ int pseg_bbox_fill(int device, const int64_t* pred, int64_t* out, int H, int W, 
     if (H == 0 || W == 0) return PSEG_OK;
     if ((int64_t)H * W > 0x7fffffffLL) return fail(PSEG_EUNSUPPORTED, "page too large");
     const size_t n = (size_t)H * W;
-    PSEG_TRY(set_dev(device));
+    PSEG_TRY(open_device(device));
     int64_t *d_pred = nullptr, *d_out = nullptr;
     PSEG_HIP(hipMalloc((void**)&d_pred, n * 8));
     if (hipMalloc((void**)&d_out, n * 8) != hipSuccess) { (void)hipFree(d_pred); return fail(PSEG_ENOMEM, "hipMalloc failed"); }
@@ -1167,22 +1149,15 @@ int pseg_bbox_fill_device_u8(int device, const uint8_t* d_pred, uint8_t* d_out, 
     if (!d_pred || !d_out) return fail(PSEG_EINVAL, "NULL argument");
     if (H <= 0 || W <= 0) return PSEG_OK;
     if ((int64_t)H * W > 0x7fffffffLL) return fail(PSEG_EUNSUPPORTED, "page too large");
-    PSEG_TRY(set_dev(device));
+    PSEG_TRY(open_device(device));
     hipStream_t st = (hipStream_t)stream;
     const size_t n = (size_t)H * W;
-    // the two int64 planes live in the device's bounding-box scratch (kept between calls: 200 MB at 4096x3072 were allocated and
-    // freed per call); the call ends synchronised and holds the scratch's lock to its end, so one call at a time uses it
-    static std::mutex mu[64];
-    static int64_t* scratch[64] = {nullptr};
-    static size_t scratch_bytes[64] = {0};
-    std::lock_guard<std::mutex> lk(mu[device & 63]);
-    if (scratch_bytes[device & 63] < n * 16) {
-        if (scratch[device & 63]) (void)hipFree(scratch[device & 63]);
-        scratch[device & 63] = nullptr; scratch_bytes[device & 63] = 0;
-        PSEG_HIP(hipMalloc((void**)&scratch[device & 63], n * 16));
-        scratch_bytes[device & 63] = n * 16;
-    }
-    int64_t* const d_tmp = scratch[device & 63];
+    // the two int64 planes live in the device's bounding-box scratch; the call ends synchronised and holds the scratch's lock to its
+    // end, so one call at a time uses it
+    std::lock_guard<std::mutex> lk(g_box.mu[device]);
+    GrowDev& scratch = g_box.ws[device].dev;
+    PSEG_TRY(scratch.ensure(n * 16, "bounding-box scratch"));
+    int64_t* const d_tmp = scratch.as<int64_t>();
     const int g = (int)std::min<size_t>((n + 255) / 256, 8192);
     widen_u8_i64_kernel<<<g, 256, 0, st>>>(d_pred, d_tmp, n);
     int rc = bbox_fill_device(d_tmp, d_tmp + n, H, W, st);
@@ -1199,7 +1174,7 @@ int pseg_masks_device(int device, const int64_t* d_pred, const uint8_t* d_binary
                       uint8_t* d_overlay, uint8_t* d_inverted, uint8_t* d_fg_color, void* stream) {
     if (!d_pred || !d_binary || !d_lut) return fail(PSEG_EINVAL, "NULL argument");
     if (H <= 0 || W <= 0) return PSEG_OK;
-    PSEG_TRY(set_dev(device));
+    PSEG_TRY(open_device(device));
     return masks_device<int64_t>(d_pred, d_binary, d_lut, n_lut, H, W, d_color, d_overlay, d_inverted, d_fg_color, (hipStream_t)stream);
 }
 
@@ -1208,7 +1183,7 @@ int pseg_masks_device_u8(int device, const uint8_t* d_pred, const uint8_t* d_bin
                          uint8_t* d_overlay, uint8_t* d_inverted, uint8_t* d_fg_color, void* stream) {
     if (!d_pred || !d_binary || !d_lut) return fail(PSEG_EINVAL, "NULL argument");
     if (H <= 0 || W <= 0) return PSEG_OK;
-    PSEG_TRY(set_dev(device));
+    PSEG_TRY(open_device(device));
     return masks_device<uint8_t>(d_pred, d_binary, d_lut, n_lut, H, W, d_color, d_overlay, d_inverted, d_fg_color, (hipStream_t)stream);
 }
 
@@ -1218,7 +1193,7 @@ int pseg_masks(int device, const int64_t* pred, const uint8_t* binary, const uin
     if (!pred || !binary || !lut || n_lut < 1) return fail(PSEG_EINVAL, "bad argument");
     if (H < 0 || W < 0) return fail(PSEG_EINVAL, "negative shape");
     if (H == 0 || W == 0) return PSEG_OK;
-    PSEG_TRY(set_dev(device));
+    PSEG_TRY(open_device(device));
     const size_t n = (size_t)H * W;
     // one slab: pred | 4 outputs (16-byte aligned each: the kernel stores dwords) | binary | lut
     uint8_t* d = nullptr;
@@ -1249,7 +1224,7 @@ int pseg_otsu_char_height(int device, const uint8_t* gray, int H, int W, int inv
     if (!gray || !height) return fail(PSEG_EINVAL, "NULL argument");
     if (H <= 0 || W <= 0) return fail(PSEG_EINVAL, "empty image");
     if ((int64_t)H * W > 0x7fffffffLL) return fail(PSEG_EUNSUPPORTED, "image too large");
-    PSEG_TRY(set_dev(device));
+    PSEG_TRY(open_device(device));
     const int n = H * W;
     const int grid = cdiv(n, 256);
     uint8_t *d_img = nullptr, *d_bin = nullptr;

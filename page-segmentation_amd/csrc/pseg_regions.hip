@@ -18,11 +18,9 @@
 // them to the root without a store: a link is never taken for a root.
 #include <algorithm>
 #include <cstring>
-#include <mutex>
 #include <vector>
 
-#include "pseg_common.h"
-#include "pseg_binarize.h"
+#include "pseg_list.h"
 #include "pseg_regions.h"
 
 namespace pseg {
@@ -463,20 +461,16 @@ __global__ __launch_bounds__(256) void rg_emit_kernel(const RgMap* __restrict__ 
 
 // ---- workspace: grow-only, one per device, under its own lock and on its own stream; a call holds the lock to its end and every
 // group ends synchronised.  pseg_release_workspace frees it.
-struct RgWs { GrowDev dev; GrowPin pin; hipStream_t st = nullptr; };
-static std::mutex g_rg_mu[64];
-static RgWs g_rg_ws[64];
-
-void regions_release_workspace(int dev) {
-    std::lock_guard<std::mutex> lk(g_rg_mu[dev & 63]);
-    RgWs& ws = g_rg_ws[dev & 63];
-    ws.dev.release();
-    ws.pin.release();
-    if (ws.st) (void)hipStreamDestroy(ws.st);
-    ws.st = nullptr;
-}
-
-static constexpr size_t rg_up256(size_t v) { return (v + 255) & ~(size_t)255; }
+struct RgWs {
+    GrowDev dev; GrowPin pin; hipStream_t st = nullptr;
+    void release() {
+        dev.release();
+        pin.release();
+        if (st) (void)hipStreamDestroy(st);
+        st = nullptr;
+    }
+};
+static PerDevice<RgWs> g_rg;
 
 static bool rg_row_less(const int* a, const int* b) { return a[5] != b[5] ? a[5] < b[5] : a[6] < b[6]; }
 // a map's rows by seed (the device appends them in no order)
@@ -489,12 +483,12 @@ static void rg_sort_rows(int* rows, int count) {
 static int rg_group(RgWs& ws, int g0, int g1, const uint8_t* const* labels, const int* H, const int* W, const pseg_regions* how,
                     uint8_t* const* out_mask, int max_regions, int32_t* out_table, int* out_count) {
     const int n = g1 - g0;
-    const size_t tab_b = rg_up256((size_t)n * sizeof(RgMap)), cnt_b = rg_up256((size_t)n * 4);
-    const size_t rows_b = rg_up256((size_t)n * max_regions * RG_ROW_INTS * 4);
+    const size_t tab_b = up256((size_t)n * sizeof(RgMap)), cnt_b = up256((size_t)n * 4);
+    const size_t rows_b = up256((size_t)n * max_regions * RG_ROW_INTS * 4);
     PSEG_TRY(ws.pin.ensure(tab_b + cnt_b + rows_b, "text regions records"));
     RgMap* const h_tab = ws.pin.as<RgMap>();
     std::memset(h_tab, 0, tab_b);
-    size_t off = tab_b + cnt_b + rows_b;
+    Bump at{tab_b + cnt_b + rows_b};
     long long tiles = 0, mbs = 0;
     for (int k = 0; k < n; ++k) {
         const int i = g0 + k;
@@ -504,18 +498,17 @@ static int rg_group(RgWs& ws, int g0, int g1, const uint8_t* const* labels, cons
         t.tiles_x = t.wpr; t.tile0 = (int)tiles;
         t.mbx = cdiv(t.wpr, RG_WC); t.mb0 = (int)mbs;
         t.want_mask = out_mask && out_mask[i];
-        t.lab_off = off; off += rg_up256((size_t)H[i] * W[i]);
-        t.plane_off = off; off += rg_up256((size_t)3 * H[i] * t.wpr * 8);
+        t.lab_off = at.take((size_t)H[i] * W[i]);
+        t.plane_off = at.take((size_t)3 * H[i] * t.wpr * 8);
         t.row_off = (unsigned long long)k * max_regions;
         tiles += (long long)t.tiles_x * cdiv(H[i], RG_TH);
         mbs += (long long)t.mbx * cdiv(H[i], RG_BAND);
     }
     if (tiles * RG_SLOTS > 0x7fffffffLL) return fail(PSEG_EUNSUPPORTED, "maps %d..%d: too many tiles for 32-bit slot ids", g0, g1 - 1);
     const size_t nslots = (size_t)tiles * RG_SLOTS;
-    const size_t o_par = off, o_stat = o_par + rg_up256(nslots * 4), o_slot = o_stat + rg_up256(nslots * RG_STAT * 4),
-                 o_rim = o_slot + rg_up256((size_t)tiles * RG_NPX), o_rootn = o_rim + rg_up256((size_t)tiles * RG_RIM),
-                 total = o_rootn + rg_up256((size_t)tiles * 4);
-    PSEG_TRY(ws.dev.ensure(total, "text regions workspace"));
+    const size_t o_par = at.take(nslots * 4), o_stat = at.take(nslots * RG_STAT * 4), o_slot = at.take((size_t)tiles * RG_NPX),
+                 o_rim = at.take((size_t)tiles * RG_RIM), o_rootn = at.take((size_t)tiles * 4);
+    PSEG_TRY(ws.dev.ensure(at.off, "text regions workspace"));
     if (!ws.st) PSEG_HIP(hipStreamCreateWithFlags(&ws.st, hipStreamNonBlocking));
     hipStream_t st = ws.st;
     uint8_t* const d = ws.dev.p;
@@ -527,11 +520,7 @@ static int rg_group(RgWs& ws, int g0, int g1, const uint8_t* const* labels, cons
     uint8_t* const d_slot = d + o_slot;
     uint8_t* const d_rim = d + o_rim;
     int* const d_rootn = (int*)(d + o_rootn);
-    struct Drain {                                                     // an error return in the middle leaves no copy from / to the caller's arrays in flight
-        hipStream_t s;
-        bool armed = true;
-        ~Drain() { if (armed) (void)hipStreamSynchronize(s); }
-    } drain{st};
+    GroupDrain drain{st};
     PSEG_HIP(hipMemcpyAsync(d, h_tab, (size_t)n * sizeof(RgMap), hipMemcpyHostToDevice, st));
     PSEG_HIP(hipMemsetAsync(d_cnt, 0, (size_t)n * 4, st));
     for (int k = 0; k < n; ++k)
@@ -730,17 +719,9 @@ int pseg_text_regions(int device, int n, const uint8_t* const* labels, const int
                       uint8_t* const* out_mask, int max_regions, int32_t* out_table, int* out_count) {
     if (n == 0) return PSEG_OK;
     PSEG_TRY(rg_check_list(n, labels, H, W, how, max_regions, out_table, out_count));
-    int nd = 0;
-    if (hipGetDeviceCount(&nd) != hipSuccess || nd == 0) return fail(PSEG_EHIP, "no HIP device visible: libpseg has no CPU fallback");
-    if (device < 0 || device >= nd) return fail(PSEG_EINVAL, "device %d of %d", device, nd);
-    PSEG_HIP(hipSetDevice(device));
-    std::lock_guard<std::mutex> lk(g_rg_mu[device & 63]);
-    for (int g0 = 0; g0 < n;) {
-        const int g1 = binarize_group_end(n, H, W, g0);
-        PSEG_TRY(rg_group(g_rg_ws[device & 63], g0, g1, labels, H, W, how, out_mask, max_regions, out_table, out_count));
-        g0 = g1;
-    }
-    return PSEG_OK;
+    return run_list(g_rg, device, n, [&](int i) { return (size_t)H[i] * W[i]; }, [&](RgWs& ws, int g0, int g1) {
+        return rg_group(ws, g0, g1, labels, H, W, how, out_mask, max_regions, out_table, out_count);
+    });
 }
 
 int pseg_text_regions_host(int n, const uint8_t* const* labels, const int* H, const int* W, const pseg_regions* how,

@@ -17,18 +17,9 @@
 #include <cstring>
 #include <vector>
 
-#include "pseg_common.h"
+#include "pseg_list.h"
 
 namespace pseg {
-
-static int rz_set_dev(int device) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
-        return fail(PSEG_EHIP, "no HIP device available: the MI355X engine needs a GPU (no CPU fallback)");
-    if (device < 0 || device >= n) return fail(PSEG_EINVAL, "device %d out of range (%d visible)", device, n);
-    PSEG_HIP(hipSetDevice(device));
-    return PSEG_OK;
-}
 
 // periodic 'mirror' / skimage 'reflect' extension (no edge repeat): d c b | a b c d | c b a
 __device__ __forceinline__ int mirror_idx(int i, int n) {
@@ -593,7 +584,7 @@ int pseg_gaussian_kernel(double sigma, double* w, int cap, int* radius) {
 int pseg_resize_nearest(int device, const void* src, int H, int W, int elem_bytes, void* dst, int Ho, int Wo) {
     if (!src || !dst) return fail(PSEG_EINVAL, "NULL argument");
     PSEG_TRY(check_shape(H, W, Ho, Wo));
-    PSEG_TRY(rz_set_dev(device));
+    PSEG_TRY(open_device(device));
     DevMem mem;
     uint8_t *d_s = nullptr, *d_d = nullptr;
     const size_t ns = (size_t)H * W * elem_bytes, nd = (size_t)Ho * Wo * elem_bytes;
@@ -608,7 +599,7 @@ int pseg_resize_nearest(int device, const void* src, int H, int W, int elem_byte
 int pseg_resize_nearest_device(int device, const void* d_src, int H, int W, int elem_bytes, void* d_dst, int Ho, int Wo, void* stream) {
     if (!d_src || !d_dst) return fail(PSEG_EINVAL, "NULL argument");
     PSEG_TRY(check_shape(H, W, Ho, Wo));
-    PSEG_TRY(rz_set_dev(device));
+    PSEG_TRY(open_device(device));
     return nearest_dev(d_src, H, W, elem_bytes, d_dst, Ho, Wo, (hipStream_t)stream);
 }
 
@@ -616,7 +607,7 @@ int pseg_scale_image(int device, const void* src, int src_is_f64, int H, int W, 
                      const double* wy, int ry, const double* wx, int rx) {
     if (!src || !dst) return fail(PSEG_EINVAL, "NULL argument");
     PSEG_TRY(check_shape(H, W, Ho, Wo));
-    PSEG_TRY(rz_set_dev(device));
+    PSEG_TRY(open_device(device));
     DevMem mem;
     const size_t n = (size_t)H * W, no = (size_t)Ho * Wo;
     unsigned long long* d_stats = nullptr;
@@ -649,7 +640,7 @@ int pseg_affine_warp_fill(int device, const float* src, int H, int W, const doub
     if (order != 0 && order != 3) return fail(PSEG_EUNSUPPORTED, "interpolation order %d (0 and 3 are built)", order);
     if (fill_mode < 0 || fill_mode > 3) return fail(PSEG_EUNSUPPORTED, "fill mode %d (0 'nearest', 1 'constant', 2 'reflect', 3 'wrap')", fill_mode);
     PSEG_TRY(check_shape(H, W, H, W));
-    PSEG_TRY(rz_set_dev(device));
+    PSEG_TRY(open_device(device));
     DevMem mem;
     const size_t n = (size_t)H * W;
     float *d_s = nullptr, *d_d = nullptr;
@@ -716,7 +707,7 @@ __global__ __launch_bounds__(256) void brightness_apply_kernel(const float* x, f
 
 int pseg_brightness_shift(int device, const float* src, int64_t n, float brightness, float* dst) {
     if (!src || !dst || n < 1) return fail(PSEG_EINVAL, "NULL argument / empty plane");
-    PSEG_TRY(rz_set_dev(device));
+    PSEG_TRY(open_device(device));
     DevMem mem;
     float *d_s = nullptr, *d_d = nullptr;
     unsigned* d_mm = nullptr;
@@ -742,7 +733,7 @@ int pseg_prepare_images(int device, const uint8_t* image, const uint8_t* binary,
     PSEG_TRY(check_shape(H0, W0, H1, W1));
     const bool two = H2 > 0 && W2 > 0;
     if (two) PSEG_TRY(check_shape(H1, W1, H2, W2));
-    PSEG_TRY(rz_set_dev(device));
+    PSEG_TRY(open_device(device));
     DevMem mem;
     hipStream_t st = nullptr;
     const size_t n0 = (size_t)H0 * W0, n1 = (size_t)H1 * W1, n2 = two ? (size_t)H2 * W2 : 0;
@@ -1267,8 +1258,6 @@ size_t scan_front_weights(const pseg_scan& s, double* dst) {
     return n;
 }
 
-static inline size_t sf_up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // the filtered planes of a scan
 static size_t scan_filt_work(const pseg_scan& s) {
     double sig[2];
@@ -1276,7 +1265,7 @@ static size_t scan_filt_work(const pseg_scan& s) {
     scan_radii(s, sig, rad);
     if (rad[0] == 0 && rad[1] == 0) return 0;
     const bool fused = rad[0] <= SF_RMAX && rad[1] <= SF_RMAX;
-    return sf_up256((size_t)s.H0 * s.W0) * (!fused && rad[0] > 0 && rad[1] > 0 ? 2 : 1);
+    return up256((size_t)s.H0 * s.W0) * (!fused && rad[0] > 0 && rad[1] > 0 ? 2 : 1);
 }
 
 // behind them, for an adaptive binarisation: the row-sum plane; for that or a despeckling: the scan-sized ink plane unless d_orig takes
@@ -1285,7 +1274,7 @@ size_t scan_front_work(const pseg_scan& s, const pseg_binarize* how, const pseg_
     const bool adaptive = how && how->window != 0, clean = dsp && dsp->max_area != 0;
     size_t b = scan_filt_work(s);
     if (adaptive) b += binarize_rows_bytes(s.H0, s.W0);
-    if ((adaptive || clean) && !s.final_is_scan) b += sf_up256((size_t)s.H0 * s.W0);
+    if ((adaptive || clean) && !s.final_is_scan) b += up256((size_t)s.H0 * s.W0);
     if (clean) b += despeckle_work_bytes(s.H0, s.W0);
     return b;
 }
@@ -1315,7 +1304,7 @@ int scan_front_enqueue(const pseg_scan& s, const uint8_t* d_scan, const double* 
     }
     scan_stats_kernel<<<sgrid, 256, 0, st>>>(d_scan, n0, d_rec, stats_orig);
     if (clean && d_ink) {
-        uint8_t* const dwork = d_work + scan_filt_work(s) + (adaptive ? binarize_rows_bytes(H0, W0) : 0) + (s.final_is_scan ? 0 : sf_up256(n0));
+        uint8_t* const dwork = d_work + scan_filt_work(s) + (adaptive ? binarize_rows_bytes(H0, W0) : 0) + (s.final_is_scan ? 0 : up256(n0));
         PSEG_TRY(despeckle_enqueue(d_ink, H0, W0, *dsp, dwork, st));
     }
     const uint8_t* plane = d_scan;
@@ -1327,7 +1316,7 @@ int scan_front_enqueue(const pseg_scan& s, const uint8_t* d_scan, const double* 
         } else {
             // one pass per launch, the last one into the first plane of the workspace
             const dim3 grid(cdiv(W0, 256), H0);
-            uint8_t* const second = d_work + sf_up256(n0);
+            uint8_t* const second = d_work + up256(n0);
             const uint8_t* cur = d_scan;
             if (rad[0] > 0) {
                 uint8_t* const out = rad[1] > 0 ? second : d_work;
@@ -1374,15 +1363,15 @@ extern "C" int pseg_prepare_scans_clean(int device, int n, const pseg_scan* scan
         if (dsp) PSEG_TRY(despeckle_check(dsp[i], i, "scan"));
         if (!out_img[i] || !out_bin[i]) return fail(PSEG_EINVAL, "scan %d: NULL argument", i);
         at[i] = At{b_scan, b_work, n_w, b_img};
-        b_scan += sf_up256((size_t)scans[i].H0 * scans[i].W0);
+        b_scan += up256((size_t)scans[i].H0 * scans[i].W0);
         pseg_scan alone = scans[i];                             // (final_is_scan is the chain's: here the ink plane may have no other home)
         alone.final_is_scan = 0;
         b_work += scan_front_work(alone, binarize_of(how, i), despeckle_of(dsp, i));
         n_w += scan_front_weights(scans[i], nullptr);
-        b_img += sf_up256((size_t)scans[i].H * scans[i].W);
+        b_img += up256((size_t)scans[i].H * scans[i].W);
     }
     if (n == 0) return PSEG_OK;
-    PSEG_TRY(rz_set_dev(device));
+    PSEG_TRY(open_device(device));
     DevMem mem;
     hipStream_t st = nullptr;
     uint8_t *d_scan = nullptr, *d_work = nullptr, *d_img = nullptr, *d_bin = nullptr, *d_orig = nullptr;
@@ -1397,7 +1386,7 @@ extern "C" int pseg_prepare_scans_clean(int device, int n, const pseg_scan* scan
     PSEG_TRY(mem.alloc(&d_orig, b_scan));
     std::vector<double> h_w(std::max<size_t>(n_w, 1));
     for (int i = 0; i < n; ++i) scan_front_weights(scans[i], h_w.data() + at[i].w);
-    struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{st};     // (h_w and the caller's arrays outlive the copies)
+    GroupDrain drain{st};                                       // never disarmed: h_w and the caller's arrays outlive the copies
     if (n_w) PSEG_HIP(hipMemcpyAsync(d_w, h_w.data(), n_w * 8, hipMemcpyHostToDevice, st));
     PSEG_HIP(hipMemsetAsync(d_rec, 0, (size_t)n * SCAN_REC_WORDS * sizeof(unsigned), st));
     for (int i = 0; i < n; ++i) {

@@ -198,3 +198,57 @@ def test_cc_vote_full_size_page_properties(gpu):
     same_run = (binary[:, 1:] != 0) & (binary[:, :-1] != 0)
     assert np.array_equal(voted[:, 1:][same_run], voted[:, :-1][same_run])
     assert np.array_equal(gpu.cc_vote(pred.astype(np.int64), binary, 6), voted.astype(np.int64))
+
+
+def _bbox_u8_device(gpu, pred_u8):
+    """pseg_bbox_fill_device_u8 on device buffers (the entry the Predictor chain's bounding-box post-op uses)."""
+    import ctypes
+    import torch
+    from pseg_amd import engine as E
+    dev = torch.device("cuda:0")
+    d_p = torch.from_numpy(pred_u8.copy()).to(dev)
+    d_o = torch.zeros_like(d_p)
+    H, W = pred_u8.shape
+    st = torch.cuda.current_stream(dev).cuda_stream
+    vp = ctypes.c_void_p
+    E._check(E.lib().pseg_bbox_fill_device_u8(0, vp(d_p.data_ptr()), vp(d_o.data_ptr()), H, W, 4, vp(st)))
+    torch.cuda.synchronize()
+    return d_o.cpu().numpy()
+
+
+def test_bbox_fill_scratch_is_released_and_comes_back(gpu, oracle_mod):
+    """pseg_release_workspace frees the bounding-box scratch of pseg_bbox_fill_device_u8 like every other per-device workspace:
+    a small map, a release, a larger map (the scratch grows from nothing), a release, the small map again."""
+    rng = np.random.default_rng(41)
+    maps = {}
+    for H, W in [(33, 65), (64, 129)]:
+        pred = np.zeros((H, W), np.uint8)
+        for _ in range(10):
+            y, x = rng.integers(0, H), rng.integers(0, W)
+            pred[y:y + rng.integers(1, H // 3), x:x + rng.integers(1, W // 3)] = rng.integers(0, 4)
+        pred[rng.random((H, W)) < 0.02] = 3
+        maps[(H, W)] = (pred, oracle_mod.add_bounding_boxes(pred.astype(np.int64)))
+    for k, shape in enumerate([(33, 65), (64, 129), (33, 65)]):
+        pred, want = maps[shape]
+        assert np.array_equal(_bbox_u8_device(gpu, pred).astype(np.int64), want), (k, shape)
+        if k < 2:
+            assert gpu.lib().pseg_release_workspace(0) == 0
+
+
+def test_cc_vote_workspace_is_released_and_comes_back(gpu, oracle_mod):
+    """The vote before and after pseg_release_workspace, alternating two shapes (the later one needs the larger workspace), on the
+    tile path (3 classes) and the page-global path (13 classes), host and device entries."""
+    rng = np.random.default_rng(43)
+    cases = []
+    for H, W in [(33, 65), (17, 300)]:
+        for C in (3, 13):
+            binary = (rng.random((H, W)) < 0.45).astype(np.uint8)
+            pred = rng.integers(0, C, size=(H, W)).astype(np.int64)
+            cases.append((pred, binary, C, oracle_mod.vote_connected_component_class(pred, binary)))
+    for k in range(3):
+        for pred, binary, C, want in cases:
+            assert np.array_equal(gpu.cc_vote(pred.copy(), binary, C), want), (k, pred.shape, C)
+            assert np.array_equal(_vote_u8_device(gpu, pred.astype(np.uint8), binary, C).astype(np.int64), want), (k, pred.shape, C, "u8")
+            if k == 1:
+                assert gpu.lib().pseg_release_workspace(0) == 0       # between every two calls of the middle round
+        assert gpu.lib().pseg_release_workspace(0) == 0
