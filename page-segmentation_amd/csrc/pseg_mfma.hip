@@ -4120,6 +4120,23 @@ static int producer_of(const Engine& e, int tensor) {
     return -1;
 }
 
+// operand slots (src0, src1, add) that read tensor t; count_fused_pools = false leaves out the pools folded into their producer
+static int readers(const Engine& e, int t, bool count_fused_pools) {
+    int n = 0;
+    for (auto& o : e.ops)
+        if (count_fused_pools || !(o.fused_away && o.type == OP_POOL)) n += (o.src0 == t) + (o.src1 == t) + (o.add == t);
+    return n;
+}
+
+// into_tail: a ReLU'd transposed conv (<= 32 couts, <= 16 input chunks) whose output only the tail's deconv reads can run inside
+// tail_fused2_kernel
+static bool inner_deconv_fits_tail(const Engine& e, const Op& dq) {
+    if (dq.type != OP_DECONV2 || !dq.relu || dq.Cout > 32 || dq.tail_logits >= 0 || dq.into_tail >= 0) return false;
+    if ((e.tensors[dq.src0].Cs + (dq.src1 >= 0 ? e.tensors[dq.src1].Cs : 0)) / 8 > 16) return false;
+    if (dq.src1 >= 0 && (e.tensors[dq.src0].Cs > 64 || e.tensors[dq.src1].Cs > 64)) return false;   // k-steps 0-1 <- source 0, 2-3 <- source 1
+    return readers(e, dq.dst, true) == 1;
+}
+
 // Fold every MaxPooling2D into the epilogue of the conv that produces its input.
 int mfma_plan_graph(Engine& e) {
     const bool spec = !PSEG_KNOB("PSEG_GENERIC");   // the fusions below need specialised kernel instances
@@ -4205,9 +4222,7 @@ int mfma_plan_graph(Engine& e) {
             if (lg.type != OP_LOGITS || e.n_classes > 16) continue;
             const int pi = producer_of(e, lg.src0);
             if (pi < 0 || e.ops[pi].type != OP_DECONV2 || e.ops[pi].Cout > 32) continue;
-            int users = 0;
-            for (auto& o : e.ops) users += (o.src0 == lg.src0) + (o.src1 == lg.src0) + (o.add == lg.src0);
-            if (users != 1) continue;
+            if (readers(e, lg.src0, true) != 1) continue;
             if (lg.src1 >= 0 && e.tensors[lg.src1].Cs > 32) continue;
             e.ops[pi].tail_logits = (int)li;
             e.tensors[e.ops[pi].dst].fused = true;
@@ -4225,9 +4240,7 @@ int mfma_plan_graph(Engine& e) {
             if (cv.type != OP_CONV || cv.Cout != 64 || cv.stride != 1 || cv.k != 3 || cv.up0 || cv.up1 ||
                 cv.transposed || cv.pool_dst >= 0) continue;
             if (cv.in_relu && cv.add < 0) continue;    // plain conv (unet) or [pre-activation +] residual add (res_unet)
-            int users = 0;
-            for (auto& o : e.ops) users += (o.src0 == lg.src0) + (o.src1 == lg.src0) + (o.add == lg.src0);
-            if (users != 1) continue;
+            if (readers(e, lg.src0, true) != 1) continue;
             cv.tail_logits = (int)li;
             e.tensors[cv.dst].fused = true;
             lg.fused_away = true;
@@ -4237,15 +4250,8 @@ int mfma_plan_graph(Engine& e) {
         for (size_t ci = 0; ci < e.ops.size(); ++ci) {
             Op& c1 = e.ops[ci];
             if (c1.type != OP_CONV || c1.src0 != e.input_tensor || c1.src1 >= 0 || c1.k != 5 || c1.Cout != 20 || c1.stride != 1) continue;
-            int users = 0, user = -1;
-            for (size_t j = 0; j < e.ops.size(); ++j) {
-                const Op& o = e.ops[j];
-                const int u = (o.src0 == c1.dst) + (o.src1 == c1.dst) + (o.add == c1.dst);
-                users += u;
-                if (u) user = (int)j;
-            }
-            if (users != 1) continue;
-            Op& c2 = e.ops[user];
+            if (readers(e, c1.dst, true) != 1) continue;
+            Op& c2 = *std::find_if(e.ops.begin(), e.ops.end(), [&](const Op& o) { return o.src0 == c1.dst || o.src1 == c1.dst || o.add == c1.dst; });
             if (c2.type != OP_CONV || c2.k != 5 || c2.stride != 1 || c2.src1 >= 0 || c2.up0 || c2.in_relu || c2.add >= 0 || c2.transposed || c2.Cout > 32) continue;
             c2.fuse1 = (int)ci;
             c1.fused_away = true;
@@ -4263,9 +4269,7 @@ int mfma_plan_graph(Engine& e) {
             Op& pc = e.ops[pi];
             if (pc.type != OP_CONV || pc.k != 5 || pc.stride != 1 || pc.Cout != 80 || !pc.relu || pc.add >= 0 || pc.in_relu || pc.up0 || pc.up1 ||
                 pc.pool_dst >= 0 || pc.fuse1 >= 0 || pc.tail_logits >= 0 || pc.skiplog >= 0 || pc.relu_dst >= 0) continue;
-            int users = 0;
-            for (auto& o : e.ops) users += (o.src0 == pc.dst) + (o.src1 == pc.dst) + (o.add == pc.dst);
-            if (users != 1) continue;
+            if (readers(e, pc.dst, true) != 1) continue;
             pc.dq_fuse = (int)di;
             dq.fused_away = true;
             e.tensors[pc.dst].fused = true;
@@ -4283,9 +4287,7 @@ int mfma_plan_graph(Engine& e) {
     if (!PSEG_KNOB("PSEG_NO_POOL_ONLY"))
         for (auto& cv : e.ops) {
             if (cv.type != OP_CONV || cv.pool_dst < 0 || cv.add >= 0) continue;
-            int users = 0;
-            for (auto& o : e.ops) users += ((o.src0 == cv.dst) + (o.src1 == cv.dst) + (o.add == cv.dst)) * (o.fused_away && o.type == OP_POOL ? 0 : 1);
-            if (users == 0) { cv.pool_only = true; e.tensors[cv.dst].fused = true; }
+            if (readers(e, cv.dst, false) == 0) { cv.pool_only = true; e.tensors[cv.dst].fused = true; }
         }
     // skip connection into a composed tail (fcn_skip: conv2 -> logits): when the full-resolution conv output has no
     // other reader than its fused pool and the logits layer, the conv stores its logits contribution (4 or 8 floats
@@ -4300,9 +4302,7 @@ int mfma_plan_graph(Engine& e) {
             if (pi < 0) continue;
             Op& cv = e.ops[pi];
             if (cv.type != OP_CONV || cv.pool_dst < 0 || cv.fuse1 < 0 || cv.Cout > 32 || cv.relu || cv.add >= 0 || cv.tail_logits >= 0) continue;
-            int users = 0;
-            for (auto& o : e.ops) users += ((o.src0 == cv.dst) + (o.src1 == cv.dst) + (o.add == cv.dst)) * (o.fused_away && o.type == OP_POOL ? 0 : 1);
-            if (users != 1) continue;                                   // the logits layer only
+            if (readers(e, cv.dst, false) != 1) continue;                                  // the logits layer only
             const int nks0 = cdiv((e.tensors[dc.src0].Cs + (dc.src1 >= 0 ? e.tensors[dc.src1].Cs : 0)) / 8, 4);
             if (nks0 != 3) continue;                                    // the composed-tail instances that take the buffer
             cv.skiplog = dc.tail_logits;
@@ -4311,14 +4311,8 @@ int mfma_plan_graph(Engine& e) {
             // is computed inside the tail kernel (tail_fused2_kernel) instead of being stored and read back
             if (PSEG_KNOB("PSEG_NO_TAIL2") || dc.src1 < 0 || e.tensors[dc.src1].Cs > 64) continue;
             const int di = producer_of(e, dc.src0);
-            if (di < 0) continue;
+            if (di < 0 || !inner_deconv_fits_tail(e, e.ops[di])) continue;
             Op& dq = e.ops[di];
-            if (dq.type != OP_DECONV2 || !dq.relu || dq.Cout > 32 || dq.tail_logits >= 0 || dq.into_tail >= 0) continue;
-            if ((e.tensors[dq.src0].Cs + (dq.src1 >= 0 ? e.tensors[dq.src1].Cs : 0)) / 8 > 16) continue;
-            if (dq.src1 >= 0 && (e.tensors[dq.src0].Cs > 64 || e.tensors[dq.src1].Cs > 64)) continue;   // k-steps 0-1 <- source 0, 2-3 <- source 1
-            int du = 0;
-            for (auto& o : e.ops) du += (o.src0 == dq.dst) + (o.src1 == dq.dst) + (o.add == dq.dst);
-            if (du != 1) continue;
             dq.into_tail = (int)(&dc - e.ops.data());
             dq.fused_away = true;
             e.tensors[dq.dst].fused = true;
@@ -4329,14 +4323,8 @@ int mfma_plan_graph(Engine& e) {
             if (dc.type != OP_DECONV2 || dc.tail_logits < 0 || dc.relu || dc.src1 >= 0 || e.ops[dc.tail_logits].src1 >= 0) continue;
             if (e.tensors[dc.src0].Cs != 32) continue;
             const int di = producer_of(e, dc.src0);
-            if (di < 0) continue;
+            if (di < 0 || !inner_deconv_fits_tail(e, e.ops[di])) continue;
             Op& dq = e.ops[di];
-            if (dq.type != OP_DECONV2 || !dq.relu || dq.Cout > 32 || dq.tail_logits >= 0 || dq.into_tail >= 0) continue;
-            if ((e.tensors[dq.src0].Cs + (dq.src1 >= 0 ? e.tensors[dq.src1].Cs : 0)) / 8 > 16) continue;
-            if (dq.src1 >= 0 && (e.tensors[dq.src0].Cs > 64 || e.tensors[dq.src1].Cs > 64)) continue;   // k-steps 0-1 <- source 0, 2-3 <- source 1
-            int du = 0;
-            for (auto& o : e.ops) du += (o.src0 == dq.dst) + (o.src1 == dq.dst) + (o.add == dq.dst);
-            if (du != 1) continue;
             dq.into_tail = (int)(&dc - e.ops.data());
             dq.fused_away = true;
             e.tensors[dq.dst].fused = true;
@@ -4414,6 +4402,17 @@ static std::vector<Chunk> pair_chunks(int KS, int nc, int sigma, int pitch_slots
     return out;
 }
 
+// ... for a dense tile of row_slots slots per row: the row pad (0-15 slots) whose k-chunk pairing the bank model likes best
+static int best_pad(int KS, int nc, int sg, int row_slots, bool pair2, int plane) {
+    int pad = 0, best_cyc = 1 << 30;
+    for (int pd = 0; pd < 16; ++pd) {
+        int cyc = 0;
+        (void)pair_chunks(KS, nc, sg, row_slots + pd, &cyc, pair2, plane);
+        if (cyc < best_cyc) { best_cyc = cyc; pad = pd; }
+    }
+    return pad;
+}
+
 static bool is_conv1_special(const Engine& e, const Op& op, int* ks, int* cout) {
     if (op.type != OP_CONV || op.src0 != e.input_tensor || op.src1 >= 0 || e.in_ch != 1) return false;
     if (op.stride != 1 || op.up0 || op.in_relu || op.add >= 0 || op.pool_dst >= 0) return false;
@@ -4432,112 +4431,154 @@ static int upload(T** d, const std::vector<T>& h) {
     return PSEG_OK;
 }
 
-int mfma_pack_op(Engine& e, Op& op, const std::vector<float>& w, const std::vector<float>& bias) {
-    mfma_free_op(op);
-    auto* P = new MfmaPlan();
-    op.plan = P;
-    P->w_keep = w;
-    P->b_keep = bias;
-    // the switches that several kernel families share; every family's flag below includes its own
-    const bool spec = P->spec = !PSEG_KNOB("PSEG_GENERIC");
-    const bool persist = !PSEG_KNOB("PSEG_NO_PERSIST"), ws_on = !PSEG_KNOB("PSEG_NO_WS");
-    const Tensor& s0 = e.tensors[op.src0];
-    const Tensor* s1 = op.src1 >= 0 ? &e.tensors[op.src1] : nullptr;
-    const int C0 = s0.C, Cs0 = s0.Cs, C1 = s1 ? s1->C : 0, Cs1 = s1 ? s1->Cs : 0;
-    const int Cin = C0 + C1, Cout = op.Cout, k = op.k;
-    auto rb = [](float f) { return bf2f(f2bf(f)); };
+static float rb(float f) { return bf2f(f2bf(f)); }
 
-    int ks1, co1;
-    if (is_conv1_special(e, op, &ks1, &co1)) {
-        P->kind = PLAN_CONV1;
-        P->KS = ks1;
-        std::vector<float> wf((size_t)k * k * Cout), lut(256);
-        for (size_t i = 0; i < wf.size(); ++i) wf[i] = rb(w[i]);  // Cin == 1: [tap][Cout]
-        for (int i = 0; i < 256; ++i) lut[i] = rb((float)i / 255.0f);
-        PSEG_TRY(upload(&P->d_wf, wf));
-        PSEG_TRY(upload(&P->d_lut, lut));
-        // MFMA form: A fragments [k-step][cout tile][lane][8]; lane = (cout & 15, g), k-step s:
-        // kernel row ky = 4s + g, element j = kernel column kx
-        const int nks = (k + 3) / 4, nt = cdiv(Cout, 16);
-        std::vector<uint16_t> apk((size_t)nks * nt * 64 * 8, 0);
-        for (int sidx = 0; sidx < nks; ++sidx)
-            for (int q = 0; q < nt; ++q)
-                for (int l = 0; l < 64; ++l) {
-                    const int co = q * 16 + (l & 15), ky = 4 * sidx + (l >> 4);
-                    if (co >= Cout || ky >= k) continue;
-                    for (int j = 0; j < k; ++j)
-                        apk[(((size_t)sidx * nt + q) * 64 + l) * 8 + j] = f2bf(w[((size_t)ky * k + j) * Cout + co]);
-                }
-        PSEG_TRY(upload(&P->d_wpk, apk));
-        std::vector<float> bb((size_t)std::max(nt * 16, 32), 0.0f);
-        for (int c = 0; c < Cout; ++c) bb[c] = bias[c];
-        PSEG_TRY(upload(&P->d_bias, bb));
-        if (k == 5 && Cout <= 32) {
-            // v_mfma_f32_32x32x16_bf16 form: A fragment of k-step s, lane l = (cout l % 32, half l / 32): kernel row 2 s + half,
-            // element j = kernel column (rows / columns past the 5 x 5 kernel carry zeros)
-            std::vector<uint16_t> a32((size_t)3 * 64 * 8, 0);
-            for (int sidx = 0; sidx < 3; ++sidx)
-                for (int l = 0; l < 64; ++l) {
-                    const int co = l & 31, ky = 2 * sidx + (l >> 5);
-                    if (co >= Cout || ky >= k) continue;
-                    for (int j = 0; j < k; ++j) a32[((size_t)sidx * 64 + l) * 8 + j] = f2bf(w[((size_t)ky * k + j) * Cout + co]);
-                }
-            PSEG_TRY(upload(&P->d_wpk32, a32));
-        }
-        return PSEG_OK;
+// bias zero-padded to n floats
+static std::vector<float> padded(const std::vector<float>& bias, int count, int n) {
+    std::vector<float> b((size_t)n, 0.0f);
+    std::copy_n(bias.begin(), count, b.begin());
+    return b;
+}
+
+// One 64 x 8 A fragment of logits weights: lane l = (row l & 15, group g = l >> 4), element j <-> channel chan(g, j); weight(row, channel)
+// answers 0 where the fragment keeps its zero (a row past the classes, a channel past the layer).
+template <class Chan, class Weight>
+static void logits_frag(uint16_t* out, Chan chan, Weight weight) {
+    for (int l = 0; l < 64; ++l)
+        for (int j = 0; j < 8; ++j) out[l * 8 + j] = f2bf(weight(l & 15, chan(l >> 4, j)));
+}
+// ... the channel map of two accumulator tiles base / 16 and base / 16 + 1 as an MFMA B operand: lane group g holds channels
+// base + 4g .. + 3 in elements 0-3 and base + 16 + 4g .. + 3 in elements 4-7
+static auto acc_tiles(int base) {
+    return [base](int g, int j) { return j < 4 ? base + 4 * g + j : base + 16 + 4 * g + (j - 4); };
+}
+// ... and of k-step s of a tensor read from memory: lane group g holds the eight storage channels of chunk 4s + g
+static auto chunk_chans(int s) {
+    return [s](int g, int j) { return (4 * s + g) * 8 + j; };
+}
+
+// What every stage of mfma_pack_op reads about the layer: the operands, the source channel counts (C: true, Cs: storage) and the
+// switches that several kernel families share (every family's flag includes its own).  Nothing here changes after it is built.
+struct PackCtx {
+    Engine& e;
+    Op& op;
+    MfmaPlan* P;
+    const std::vector<float>& w;
+    const std::vector<float>& bias;
+    const Tensor* s1;          // second source of a concat, or null
+    int C0, Cs0, C1, Cs1, Cin, Cout;
+    bool deconv, tail;         // Conv2DTranspose k2 s2; ... with the logits layer fused behind it
+    int KS;                    // taps per side of the MFMA conv (a transposed conv is four pointwise ones: 1)
+    bool spec, persist, ws_on;
+    // concat-storage channel cs -> true input channel (or -1 for pad)
+    int true_ci(int cs) const {
+        if (cs < Cs0) return cs < C0 ? cs : -1;
+        return cs - Cs0 < C1 ? C0 + cs - Cs0 : -1;
     }
-    if (op.type == OP_LOGITS) {
-        P->kind = PLAN_LOGITS;
-        P->cmax = Cout <= 4 ? 4 : (Cout <= 8 ? 8 : (Cout <= 16 ? 16 : (Cout <= 32 ? 32 : 64)));
-        if (Cout > PSEG_MAXC) return fail(PSEG_EUNSUPPORTED, "bf16 mode supports at most %d classes (got %d)", PSEG_MAXC, Cout);
-        std::vector<float> wf((size_t)(Cs0 + Cs1) * P->cmax, 0.0f), bb(P->cmax, 0.0f);
-        for (int ci = 0; ci < Cin; ++ci) {
-            const int cs = ci < C0 ? ci : Cs0 + (ci - C0);
-            for (int c = 0; c < Cout; ++c) wf[(size_t)cs * P->cmax + c] = rb(w[(size_t)ci * Cout + c]);
-        }
-        for (int c = 0; c < Cout; ++c) bb[c] = bias[c];
-        PSEG_TRY(upload(&P->d_wf, wf));
-        if (P->cmax > 16) {   // more classes than one MFMA tile has rows: the one-pixel-per-thread kernel (logits_bf16_kernel<32 / 64>)
-            PSEG_TRY(upload(&P->d_bias, bb));
-            return PSEG_OK;
-        }
-        // MFMA form: A fragments [k-step][lane = (class, g)][8 channels of chunk 4s + g], bias padded to 16
-        const int nks = cdiv((Cs0 + Cs1) / 8, 4);
-        std::vector<uint16_t> wa((size_t)nks * 64 * 8, 0);
-        for (int sidx = 0; sidx < nks; ++sidx)
+    // weight of (tap, ci, n): conv: w[(tap*Cin+ci)*Cout + n]; deconv: n = ab*CoP + co -> w[(ab*Cin+ci)*Cout+co]
+    float wval(int tap, int ci, int n) const {
+        if (!deconv) return n < Cout ? w[((size_t)tap * Cin + ci) * Cout + n] : 0.0f;
+        const int ab = n / P->CoP, co = n % P->CoP;
+        return (ab < 4 && co < Cout) ? w[((size_t)ab * Cin + ci) * Cout + co] : 0.0f;
+    }
+};
+
+// What the generic path's tile and ring stages decide and the later stages read (the rest of their answers are MfmaPlan fields).
+struct TileRing {
+    int sigma = 0, pitch_pad = 1;               // LDS pixel stride and extra slots per tile row, in 16-byte slots
+    int plane_slots = 0;                        // stride 2: first slot of the odd-column plane of a tile row
+    std::vector<Chunk> ord_full, ord_last;      // k-chunk order of a full / the last channel block
+    std::vector<int> tab_full, tab_last;        // ... and their LDS offsets, as uploaded
+    int in_bytes = 0, ks_max = 0, tab_bytes = 0;
+    int GK = 0, NB = 0;                         // the weight ring: k-steps per group, slots
+    bool no_pair8 = false;                      // PSEG_NO_ROWREUSE set (any value)
+};
+
+// The first layer (Cin = 1) in its two fragment forms, the f32 weights and the x/255 table of conv1_rows_kernel.
+static int pack_conv1(const PackCtx& c, int ks1) {
+    MfmaPlan* const P = c.P;
+    const std::vector<float>& w = c.w;
+    const int k = c.op.k, Cout = c.Cout;
+    P->kind = PLAN_CONV1;
+    P->KS = ks1;
+    std::vector<float> wf((size_t)k * k * Cout), lut(256);
+    for (size_t i = 0; i < wf.size(); ++i) wf[i] = rb(w[i]);  // Cin == 1: [tap][Cout]
+    for (int i = 0; i < 256; ++i) lut[i] = rb((float)i / 255.0f);
+    PSEG_TRY(upload(&P->d_wf, wf));
+    PSEG_TRY(upload(&P->d_lut, lut));
+    // MFMA form: A fragments [k-step][cout tile][lane][8]; lane = (cout & 15, g), k-step s:
+    // kernel row ky = 4s + g, element j = kernel column kx
+    const int nks = (k + 3) / 4, nt = cdiv(Cout, 16);
+    std::vector<uint16_t> apk((size_t)nks * nt * 64 * 8, 0);
+    for (int sidx = 0; sidx < nks; ++sidx)
+        for (int q = 0; q < nt; ++q)
             for (int l = 0; l < 64; ++l) {
-                const int cls = l & 15, chunk = 4 * sidx + (l >> 4);
-                if (cls >= Cout) continue;
-                for (int j = 0; j < 8; ++j) {
-                    const int cs = chunk * 8 + j;
-                    if (cs >= Cs0 + Cs1) continue;
-                    const int ci = cs < Cs0 ? (cs < C0 ? cs : -1) : (cs - Cs0 < C1 ? C0 + cs - Cs0 : -1);
-                    if (ci >= 0) wa[((size_t)sidx * 64 + l) * 8 + j] = f2bf(w[(size_t)ci * Cout + cls]);
-                }
+                const int co = q * 16 + (l & 15), ky = 4 * sidx + (l >> 4);
+                if (co >= Cout || ky >= k) continue;
+                for (int j = 0; j < k; ++j)
+                    apk[(((size_t)sidx * nt + q) * 64 + l) * 8 + j] = f2bf(w[((size_t)ky * k + j) * Cout + co]);
             }
-        PSEG_TRY(upload(&P->d_wpk, wa));
-        bb.resize(16, 0.0f);
-        PSEG_TRY(upload(&P->d_bias, bb));
-        return PSEG_OK;
+    PSEG_TRY(upload(&P->d_wpk, apk));
+    PSEG_TRY(upload(&P->d_bias, padded(c.bias, Cout, std::max(nt * 16, 32))));
+    if (k == 5 && Cout <= 32) {
+        // v_mfma_f32_32x32x16_bf16 form: A fragment of k-step s, lane l = (cout l % 32, half l / 32): kernel row 2 s + half,
+        // element j = kernel column (rows / columns past the 5 x 5 kernel carry zeros)
+        std::vector<uint16_t> a32((size_t)3 * 64 * 8, 0);
+        for (int sidx = 0; sidx < 3; ++sidx)
+            for (int l = 0; l < 64; ++l) {
+                const int co = l & 31, ky = 2 * sidx + (l >> 5);
+                if (co >= Cout || ky >= k) continue;
+                for (int j = 0; j < k; ++j) a32[((size_t)sidx * 64 + l) * 8 + j] = f2bf(w[((size_t)ky * k + j) * Cout + co]);
+            }
+        PSEG_TRY(upload(&P->d_wpk32, a32));
     }
-    if (op.type == OP_POOL) return PSEG_OK;
+    return PSEG_OK;
+}
 
-    // upsample -> k2 conv of the deep decoder levels: GEMM over the source pixels + gather-sum (pseg_upsplit.hip).
-    // Measured at 2048x1536 (unet): 1024->512 216 -> ~75 us, 512->256 228 -> ~110 us, 256->128 246 -> ~185 us; at
-    // 128->64 the two extra passes over the full-resolution tensor cost more than the direct kernel (PSEG_UPSPLIT_MIN_CIN).
-    if (op.type == OP_CONV && k == 2 && op.up0 && !s1 && op.stride == 1 && !op.in_relu && op.add < 0 && op.pool_dst < 0 &&
-        op.tail_logits < 0 && op.fuse1 < 0 && !op.transposed && !PSEG_KNOB("PSEG_NO_UPSPLIT") && spec) {
-        // (the two-pass form lost to the direct kernel at 128 -> 64 channels on the full-resolution map; the fused form does not)
-        const int min_cin = PSEG_KNOB("PSEG_UPSPLIT_TWO_PASS") ? 256 : 64;
-        if (Cin >= min_cin) {
-            P->kind = PLAN_UPSPLIT;
-            return upsplit_create(&P->upsplit, w, bias, Cin, Cs0, Cout, e.tensors[op.dst].Cs);
-        }
+// The logits layer on its own: f32 weights [storage channel][cmax] for logits_bf16_kernel, and up to 16 classes the MFMA form.
+static int pack_logits(const PackCtx& c) {
+    MfmaPlan* const P = c.P;
+    const std::vector<float>& w = c.w;
+    const int C0 = c.C0, Cs0 = c.Cs0, Cs1 = c.Cs1, Cout = c.Cout;
+    P->kind = PLAN_LOGITS;
+    P->cmax = Cout <= 4 ? 4 : (Cout <= 8 ? 8 : (Cout <= 16 ? 16 : (Cout <= 32 ? 32 : 64)));
+    if (Cout > PSEG_MAXC) return fail(PSEG_EUNSUPPORTED, "bf16 mode supports at most %d classes (got %d)", PSEG_MAXC, Cout);
+    std::vector<float> wf((size_t)(Cs0 + Cs1) * P->cmax, 0.0f);
+    for (int ci = 0; ci < c.Cin; ++ci) {
+        const int cs = ci < C0 ? ci : Cs0 + (ci - C0);
+        for (int n = 0; n < Cout; ++n) wf[(size_t)cs * P->cmax + n] = rb(w[(size_t)ci * Cout + n]);
     }
-    // ---- generic MFMA conv / deconv2 ------------------------------------------------------------
-    const bool deconv = op.type == OP_DECONV2;
-    const int KS = deconv ? 1 : k;
-    const bool tail = deconv && op.tail_logits >= 0;
+    PSEG_TRY(upload(&P->d_wf, wf));
+    // more classes than one MFMA tile has rows: the one-pixel-per-thread kernel (logits_bf16_kernel<32 / 64>)
+    if (P->cmax > 16) return upload(&P->d_bias, padded(c.bias, Cout, P->cmax));
+    // MFMA form: A fragments [k-step][lane = (class, g)][8 channels of chunk 4s + g], bias padded to 16
+    const int nks = cdiv((Cs0 + Cs1) / 8, 4);
+    std::vector<uint16_t> wa((size_t)nks * 64 * 8, 0);
+    for (int sidx = 0; sidx < nks; ++sidx)   // (true_ci answers -1 for every storage channel past the sources' real ones)
+        logits_frag(&wa[(size_t)sidx * 512], chunk_chans(sidx), [&](int cls, int cs) { return cls < Cout && c.true_ci(cs) >= 0 ? w[(size_t)c.true_ci(cs) * Cout + cls] : 0.0f; });
+    PSEG_TRY(upload(&P->d_wpk, wa));
+    return upload(&P->d_bias, padded(c.bias, Cout, 16));
+}
+
+// upsample -> k2 conv of the deep decoder levels: GEMM over the source pixels + gather-sum (pseg_upsplit.hip).
+// Measured at 2048x1536 (unet): 1024->512 216 -> ~75 us, 512->256 228 -> ~110 us, 256->128 246 -> ~185 us; at
+// 128->64 the two extra passes over the full-resolution tensor cost more than the direct kernel (PSEG_UPSPLIT_MIN_CIN).
+static bool takes_upsplit(const PackCtx& c) {
+    const Op& op = c.op;
+    if (!(op.type == OP_CONV && op.k == 2 && op.up0 && !c.s1 && op.stride == 1 && !op.in_relu && op.add < 0 && op.pool_dst < 0 &&
+          op.tail_logits < 0 && op.fuse1 < 0 && !op.transposed && !PSEG_KNOB("PSEG_NO_UPSPLIT") && c.spec)) return false;
+    // (the two-pass form lost to the direct kernel at 128 -> 64 channels on the full-resolution map; the fused form does not)
+    return c.Cin >= (PSEG_KNOB("PSEG_UPSPLIT_TWO_PASS") ? 256 : 64);
+}
+
+// ---- generic MFMA conv / deconv2 ------------------------------------------------------------
+// The tile: cout tiles per N block (NT), pixel tiles per wave (MT), waves (NW), the channel blocks, the shape flags that follow from
+// them (nw8_ok, pairc2, wg3, pp_shape, pp), the LDS pixel stride and row pitch, and the two k-chunk tables, which it uploads.
+static int plan_tile(const PackCtx& c, TileRing& R) {
+    const Op& op = c.op;
+    MfmaPlan* const P = c.P;
+    const bool deconv = c.deconv, tail = c.tail, spec = c.spec;
+    const int KS = c.KS, C0 = c.C0, Cs0 = c.Cs0, Cout = c.Cout;
     P->CoP = tail ? 32 : round_up(Cout, 4);
     const int Ntrue = deconv ? 4 * P->CoP : Cout;
     int NTall = cdiv(Ntrue, 16);
@@ -4565,11 +4606,11 @@ int mfma_pack_op(Engine& e, Op& op, const std::vector<float>& w, const std::vect
                 !op.in_relu && op.add < 0 && op.fuse1 < 0 && (P->nblocks_n == 1 || KS == 3) && spec;
     P->NW = (P->nw8_ok && op.nw_hint == 8) ? 8 : 4;
     const int TH = P->NW * (P->MT / 2);
-    const int totc = (Cs0 + Cs1) / 8;
+    const int totc = (Cs0 + c.Cs1) / 8;
     // fused conv1 + conv2 on the wave-specialised kernel: 20 input channels = 2.5 chunks per pixel -- the half chunk pairs up
     // with the right neighbour's (the producers write the tile that way), 65 k-chunks instead of 75
-    P->pairc2 = op.fuse1 >= 0 && !deconv && KS == 5 && C0 == 20 && Cs0 == 24 && !s1 && op.stride == 1 && op.pool_dst >= 0 && !op.relu &&
-                op.add < 0 && !op.in_relu && Cout <= 32 && ws_on && !PSEG_KNOB("PSEG_NO_PAIRC2") && persist && spec;
+    P->pairc2 = op.fuse1 >= 0 && !deconv && KS == 5 && C0 == 20 && Cs0 == 24 && !c.s1 && op.stride == 1 && op.pool_dst >= 0 && !op.relu &&
+                op.add < 0 && !op.in_relu && Cout <= 32 && c.ws_on && !PSEG_KNOB("PSEG_NO_PAIRC2") && c.persist && spec;
     P->nc_full = totc <= 5 ? totc : (KS == 1 && totc <= 16 ? totc : 4);
     P->nblk = cdiv(totc, P->nc_full);
     P->nc_last = totc - (P->nblk - 1) * P->nc_full;
@@ -4580,47 +4621,35 @@ int mfma_pack_op(Engine& e, Op& op, const std::vector<float>& w, const std::vect
     // conflicts are far cheaper than streaming the weights group by group).
     int sigma = sigma_for(P->nc_full);
     int pitch_pad = 1;   // extra 16-byte slots per tile row
-    // ... for a dense tile: the pad whose k-chunk pairing the bank model likes best
-    auto best_pad = [&](int sg, int row_slots, bool pair2, int plane) {
-        int pad = 0, best_cyc = 1 << 30;
-        for (int pd = 0; pd < 16; ++pd) {
-            int cyc = 0;
-            (void)pair_chunks(KS, P->nc_full, sg, row_slots + pd, &cyc, pair2, plane);
-            if (cyc < best_cyc) { best_cyc = cyc; pad = pd; }
-        }
-        return pad;
-    };
     P->THH = (TH - 1) * P->stride + KS;
     P->TWH = (TW - 1) * P->stride + KS;
-    {
-        const int ksf = cdiv(KS * KS * P->nc_full, 4);
-        auto fits = [&](int sg, int pad) {
-            const int in_b = P->THH * ((P->TWH * sg + pad) * 16);
-            return P->nblk == 1 && in_b + round_up(ksf, 4) * NT * 1024 + ksf * 16 + 64 <= 80 * 1024;
-        };
-        // (the dense tile was also tried where it is not needed for residency -- conv3 at sigma = 4: 78.7 vs 79.0 us,
-        // neither the third of the DMA lanes spent on pad slots nor the read conflicts matter there)
-        // Three workgroups per CU (12 waves, three per SIMD) for the NT = 3 k5 layers: their instances need 147
-        // registers, so only LDS limits the occupancy.  The dense tile (sigma = chunks per pixel, row pitch chosen
-        // by the bank model) plus a two-slot ring fit 53 KB.  A workgroup's life is prologue -> k-loop ->
-        // epilogue with the MFMA pipe used only in the middle; a third resident workgroup fills more of the
-        // gaps: conv3 78 -> 67 us, deconv3 79 -> 66 us, better than the 16-row resident variant (70 us).
-        P->wg3 = P->NW == 4 && !deconv && ((KS == 5 && (NT == 3 || NT == 4) && P->nblocks_n == 1) || (KS == 3 && NT == 4) ||
-                                                 (KS == 2 && NT == 4 && op.up0 && !s1)) &&
-                 (P->nc_full == 4 || P->nc_full == 5) && op.stride == 1 &&
-                 (!op.up0 || KS == 2 || KS == 3) && !op.up1 && ((!op.in_relu && op.add < 0) || (KS == 3)) && op.fuse1 < 0 && spec;
-        // (stride 2: always the dense tile -- its columns are de-interleaved by parity at staging time, which makes the fragment
-        // reads those of a stride-1 layer, and the 4.3 input pixels per output pixel are the layer's LDS and DMA bill)
-        // conv_pp_kernel (conv3 / conv4: resident weights, two tile buffers).  (A 64-byte pixel pitch -- conv3's four chunks -- cannot be
-        // read without 2-way bank conflicts: the eight lanes of a 16-lane read group that share a chunk cover four distinct 16-byte
-        // windows.  An 80-byte pitch removes them and was measured in this kernel: 52.1 vs 52.0 us, so the dense tile stays.)
-        // (wg3 gives the rest of the kernel's shape: four waves, MT 4, stride 1, sigma 4 or 5, no fused input or epilogue work)
-        P->pp_shape = P->wg3 && KS == 5 && NT == 3 && P->nblocks_n == 1 && op.Cout <= 40 && !op.transposed && op.src1 < 0 && !PSEG_KNOB("PSEG_NO_PP");
-        P->pp = P->pp_shape && P->nblk == 1;
-        if (P->wg3 || (deint && P->nc_full >= 2) || (P->nblk == 1 && !fits(sigma, 1) && P->nc_full < sigma && fits(P->nc_full, 16))) {
-            sigma = P->nc_full;
-            pitch_pad = best_pad(sigma, P->TWH * sigma, P->pairc2, deint ? ((P->TWH + 1) / 2) * sigma : 0);
-        }
+    const int ksf = cdiv(KS * KS * P->nc_full, 4);
+    auto fits = [&](int sg, int pad) {
+        const int in_b = P->THH * ((P->TWH * sg + pad) * 16);
+        return P->nblk == 1 && in_b + round_up(ksf, 4) * NT * 1024 + ksf * 16 + 64 <= 80 * 1024;
+    };
+    // (the dense tile was also tried where it is not needed for residency -- conv3 at sigma = 4: 78.7 vs 79.0 us,
+    // neither the third of the DMA lanes spent on pad slots nor the read conflicts matter there)
+    // Three workgroups per CU (12 waves, three per SIMD) for the NT = 3 k5 layers: their instances need 147
+    // registers, so only LDS limits the occupancy.  The dense tile (sigma = chunks per pixel, row pitch chosen
+    // by the bank model) plus a two-slot ring fit 53 KB.  A workgroup's life is prologue -> k-loop ->
+    // epilogue with the MFMA pipe used only in the middle; a third resident workgroup fills more of the
+    // gaps: conv3 78 -> 67 us, deconv3 79 -> 66 us, better than the 16-row resident variant (70 us).
+    P->wg3 = P->NW == 4 && !deconv && ((KS == 5 && (NT == 3 || NT == 4) && P->nblocks_n == 1) || (KS == 3 && NT == 4) ||
+                                             (KS == 2 && NT == 4 && op.up0 && !c.s1)) &&
+             (P->nc_full == 4 || P->nc_full == 5) && op.stride == 1 &&
+             (!op.up0 || KS == 2 || KS == 3) && !op.up1 && ((!op.in_relu && op.add < 0) || (KS == 3)) && op.fuse1 < 0 && spec;
+    // (stride 2: always the dense tile -- its columns are de-interleaved by parity at staging time, which makes the fragment
+    // reads those of a stride-1 layer, and the 4.3 input pixels per output pixel are the layer's LDS and DMA bill)
+    // conv_pp_kernel (conv3 / conv4: resident weights, two tile buffers).  (A 64-byte pixel pitch -- conv3's four chunks -- cannot be
+    // read without 2-way bank conflicts: the eight lanes of a 16-lane read group that share a chunk cover four distinct 16-byte
+    // windows.  An 80-byte pitch removes them and was measured in this kernel: 52.1 vs 52.0 us, so the dense tile stays.)
+    // (wg3 gives the rest of the kernel's shape: four waves, MT 4, stride 1, sigma 4 or 5, no fused input or epilogue work)
+    P->pp_shape = P->wg3 && KS == 5 && NT == 3 && P->nblocks_n == 1 && op.Cout <= 40 && !op.transposed && op.src1 < 0 && !PSEG_KNOB("PSEG_NO_PP");
+    P->pp = P->pp_shape && P->nblk == 1;
+    if (P->wg3 || (deint && P->nc_full >= 2) || (P->nblk == 1 && !fits(sigma, 1) && P->nc_full < sigma && fits(P->nc_full, 16))) {
+        sigma = P->nc_full;
+        pitch_pad = best_pad(KS, P->nc_full, sigma, P->TWH * sigma, P->pairc2, deint ? ((P->TWH + 1) / 2) * sigma : 0);
     }
     if (P->pairc2) {
         if (sigma != 3) return fail(PSEG_EUNSUPPORTED, "paired half chunks need the dense 48-byte pixel (sigma 3, got %d)", sigma);
@@ -4629,57 +4658,67 @@ int mfma_pack_op(Engine& e, Op& op, const std::vector<float>& w, const std::vect
     if (P->NW != 4 && sigma != 6) return fail(PSEG_EUNSUPPORTED, "6/8-wave plan needs the sigma = 6 tile (got %d)", sigma);
     P->PS2 = sigma * 16;
     P->row_pitch = (P->TWH * sigma + pitch_pad) * 16;
-    const int plane_slots = deint ? ((P->TWH + 1) / 2) * sigma : 0;   // stride 2: first slot of the odd-column plane of a tile row
-    const auto ord_full = pair_chunks(KS, P->nc_full, sigma, P->row_pitch / 16, nullptr, P->pairc2, plane_slots);
-    const auto ord_last = pair_chunks(KS, P->nc_last, sigma, P->row_pitch / 16, nullptr, P->pairc2, plane_slots);
-    P->ks_full = (int)ord_full.size() / 4;
-    P->ks_last = (int)ord_last.size() / 4;
-    if ((int)ord_full.size() > MAX_TAB) return fail(PSEG_EUNSUPPORTED, "k-chunk table too large");
+    const int plane_slots = deint ? ((P->TWH + 1) / 2) * sigma : 0;
+    R.sigma = sigma; R.pitch_pad = pitch_pad; R.plane_slots = plane_slots;
+    R.ord_full = pair_chunks(KS, P->nc_full, sigma, P->row_pitch / 16, nullptr, P->pairc2, plane_slots);
+    R.ord_last = pair_chunks(KS, P->nc_last, sigma, P->row_pitch / 16, nullptr, P->pairc2, plane_slots);
+    P->ks_full = (int)R.ord_full.size() / 4;
+    P->ks_last = (int)R.ord_last.size() / 4;
+    if ((int)R.ord_full.size() > MAX_TAB) return fail(PSEG_EUNSUPPORTED, "k-chunk table too large");
     auto mk_tab = [&](const std::vector<Chunk>& ord) {
         std::vector<int> t(ord.size());
         for (size_t i = 0; i < ord.size(); ++i) {
-            const Chunk c = ord[i];
-            if (c.cc < 0) { t[i] = 0; continue; }  // dummy: finite data, zero weights
-            const int kx = c.tap % KS;
-            t[i] = (c.tap / KS) * P->row_pitch + (plane_slots ? ((kx & 1) * plane_slots + (kx >> 1) * sigma) * 16 : kx * P->PS2) + c.cc * 16;
+            const Chunk ch = ord[i];
+            if (ch.cc < 0) { t[i] = 0; continue; }  // dummy: finite data, zero weights
+            const int kx = ch.tap % KS;
+            t[i] = (ch.tap / KS) * P->row_pitch + (plane_slots ? ((kx & 1) * plane_slots + (kx >> 1) * sigma) * 16 : kx * P->PS2) + ch.cc * 16;
         }
         return t;
     };
-    const std::vector<int> tab_full = mk_tab(ord_full), tab_last = mk_tab(ord_last);
-    PSEG_TRY(upload(&P->d_tab_full, tab_full));
-    PSEG_TRY(upload(&P->d_tab_last, tab_last));
-    // Row reuse (k5, four chunks per pixel, a wave owning two adjacent output rows): when every k-step is one tap and the steps run
-    // tap-major, the pixel fragments of the wave's UPPER row under tap (ky, kx) are the fragments of its LOWER row under tap
-    // (ky - 1, kx) -- same LDS address, same lane layout -- so the k-loop keeps them in registers for five steps instead of reading
-    // them again: 60 instead of 100 pixel-fragment reads per tile and channel block.  Same operands in the same order for every
-    // accumulator: the same bits.  Decided on the tables as uploaded, not on how pair_chunks happens to order them.
-    bool no_pair8 = false;
-    {
-        auto shifts = [&](const std::vector<Chunk>& ord, const std::vector<int>& t) {
-            if (ord.size() != 100) return false;
-            for (const Chunk& c : ord)
-                if (c.cc < 0) return false;
-            for (int s = 0; s < 20; ++s)
-                for (int gq = 0; gq < 4; ++gq)
-                    if (t[(s + 5) * 4 + gq] != t[s * 4 + gq] + P->row_pitch) return false;
-            return true;
-        };
-        // PSEG_NO_ROWREUSE (plan switch: tests, A/B): "pair" keeps row reuse and takes only the paired third tile (below) away; any other
-        // value takes both
-        const char* const sw = PSEG_KNOB("PSEG_NO_ROWREUSE");
-        no_pair8 = sw != nullptr;
-        P->rowreuse = !deconv && KS == 5 && op.stride == 1 && !op.up0 && !op.up1 && !op.in_relu && P->MT == 4 && P->NW == 4 &&
-                      shifts(ord_full, tab_full) && shifts(ord_last, tab_last) && !(sw && strcmp(sw, "pair") != 0) && spec;
-        if (PSEG_KNOB("PSEG_LOG_GENERIC") && KS == 5 && P->MT == 4 && sigma == 4)
-            fprintf(stderr, "[pseg] rowreuse %s: %d\n", op.layer.c_str(), P->rowreuse ? 1 : 0);
-    }
-    // LDS budget: input tile + a ring of NB weight groups (GK k-steps each) + table; aim at two
-    // workgroups per CU (<= 80 KiB each).  GK*NT must be a multiple of 4 so that every wave
-    // issues the same number of LDS-DMA loads per group (counted vmcnt).  PSEG_GK / PSEG_NB /
-    // PSEG_LDS_KB override for experiments.
-    const int in_bytes = P->THH * P->row_pitch;
-    const int ks_max = std::max(P->ks_full, P->ks_last);
-    const int tab_bytes = ks_max * 16;
+    R.tab_full = mk_tab(R.ord_full);
+    R.tab_last = mk_tab(R.ord_last);
+    PSEG_TRY(upload(&P->d_tab_full, R.tab_full));
+    PSEG_TRY(upload(&P->d_tab_last, R.tab_last));
+    return PSEG_OK;
+}
+
+// Row reuse (k5, four chunks per pixel, a wave owning two adjacent output rows): when every k-step is one tap and the steps run
+// tap-major, the pixel fragments of the wave's UPPER row under tap (ky, kx) are the fragments of its LOWER row under tap
+// (ky - 1, kx) -- same LDS address, same lane layout -- so the k-loop keeps them in registers for five steps instead of reading
+// them again: 60 instead of 100 pixel-fragment reads per tile and channel block.  Same operands in the same order for every
+// accumulator: the same bits.  Decided on the tables as uploaded, not on how pair_chunks happens to order them.
+static void plan_rowreuse(const PackCtx& c, TileRing& R) {
+    const Op& op = c.op;
+    MfmaPlan* const P = c.P;
+    auto shifts = [&](const std::vector<Chunk>& ord, const std::vector<int>& t) {
+        if (ord.size() != 100) return false;
+        for (const Chunk& ch : ord)
+            if (ch.cc < 0) return false;
+        for (int s = 0; s < 20; ++s)
+            for (int gq = 0; gq < 4; ++gq)
+                if (t[(s + 5) * 4 + gq] != t[s * 4 + gq] + P->row_pitch) return false;
+        return true;
+    };
+    // PSEG_NO_ROWREUSE (plan switch: tests, A/B): "pair" keeps row reuse and takes only the paired third tile (pack_pair8) away; any
+    // other value takes both
+    const char* const sw = PSEG_KNOB("PSEG_NO_ROWREUSE");
+    R.no_pair8 = sw != nullptr;
+    P->rowreuse = !c.deconv && c.KS == 5 && op.stride == 1 && !op.up0 && !op.up1 && !op.in_relu && P->MT == 4 && P->NW == 4 &&
+                  shifts(R.ord_full, R.tab_full) && shifts(R.ord_last, R.tab_last) && !(sw && strcmp(sw, "pair") != 0) && c.spec;
+    if (PSEG_KNOB("PSEG_LOG_GENERIC") && c.KS == 5 && P->MT == 4 && R.sigma == 4)
+        fprintf(stderr, "[pseg] rowreuse %s: %d\n", op.layer.c_str(), P->rowreuse ? 1 : 0);
+}
+
+// LDS budget: input tile + a ring of NB weight groups (GK k-steps each) + table; aim at two
+// workgroups per CU (<= 80 KiB each; 156 KiB for an 8-wave workgroup, 53 KiB for three per CU).  GK*NT must be a multiple of 4
+// so that every wave issues the same number of LDS-DMA loads per group (counted vmcnt).  The layer shape alone decides GK and
+// NB: there is no override.
+static int plan_ring(const PackCtx& c, TileRing& R) {
+    MfmaPlan* const P = c.P;
+    const int NT = P->NT, TH = P->NW * (P->MT / 2);
+    const int in_bytes = R.in_bytes = P->THH * P->row_pitch;
+    const int ks_max = R.ks_max = std::max(P->ks_full, P->ks_last);
+    const int tab_bytes = R.tab_bytes = ks_max * 16;
     int budget = P->NW == 8 ? 156 * 1024 : 80 * 1024;
     if (P->wg3) budget = 53 * 1024;
     auto total = [&](int gk, int nbuf) { return round_up(in_bytes, 16) + nbuf * gk * NT * 1024 + tab_bytes + 16; };
@@ -4702,516 +4741,527 @@ int mfma_pack_op(Engine& e, Op& op, const std::vector<float>& w, const std::vect
         NB = 1;
         GK = round_up(ks_max, gstep);
     }
-    if (total(GK, NB) > 160 * 1024) return fail(PSEG_EUNSUPPORTED, "layer %s needs %d B of LDS", op.layer.c_str(), total(GK, NB));
-    P->GK = GK;
-    P->NB = NB;
+    if (total(GK, NB) > 160 * 1024) return fail(PSEG_EUNSUPPORTED, "layer %s needs %d B of LDS", c.op.layer.c_str(), total(GK, NB));
+    P->GK = R.GK = GK;
+    P->NB = R.NB = NB;
     const int gpb_full = cdiv(P->ks_full, GK), gpb_last = cdiv(P->ks_last, GK);
     P->G = (P->nblk - 1) * gpb_full + gpb_last;
     P->lds_w_off = round_up(in_bytes, 16);
     P->lds_tab_off = P->lds_w_off + NB * GK * NT * 1024;
     P->lds_bytes = P->lds_tab_off + tab_bytes + 16;
-    if (!deconv && P->MT == 4)   // the epilogue's store patch (plain conv instances) lives in the tile's and the ring's place
+    if (!c.deconv && P->MT == 4)   // the epilogue's store patch (plain conv instances) lives in the tile's and the ring's place
         P->lds_bytes = std::max(P->lds_bytes, P->NW * (P->MT / 2) * TW * (NT * 32 + 8));
-    if (op.fuse1 >= 0) {   // two bf16 copies of the (TH+8) x 48 uint8 tile
+    if (c.op.fuse1 >= 0) {   // two bf16 copies of the (TH+8) x 48 uint8 tile
         P->lds_f1_off = round_up(P->lds_bytes, 16);
         P->lds_bytes = P->lds_f1_off + 2 * (TH + 8) * 96;
     }
-    // ---- persistent forms of a single-block layer with resident weights (PSEG_NO_PERSIST=1: none of them) -----------------------
-    // Two workgroups per CU walking 12 tiles each: the 38 KB weight set and the k-chunk table are staged once per workgroup instead
-    // of once per tile.  Worth 1-3 % on the fused conv1+conv2 kernel (the DMA it saves was mostly hidden by the co-resident
-    // workgroup); needs the per-trip opaque lane ids to keep two waves per SIMD.
-    const bool resident1 = P->NB == 1 && P->nblk == 1 && P->nblocks_n == 1 && persist && spec;
+    return PSEG_OK;
+}
+
+// ---- persistent forms of a single-block layer with resident weights (PSEG_NO_PERSIST=1: none of them) -----------------------
+// Two workgroups per CU walking 12 tiles each: the 38 KB weight set and the k-chunk table are staged once per workgroup instead
+// of once per tile.  Worth 1-3 % on the fused conv1+conv2 kernel (the DMA it saves was mostly hidden by the co-resident
+// workgroup); needs the per-trip opaque lane ids to keep two waves per SIMD.
+static void plan_persistent(const PackCtx& c, const TileRing& R) {
+    const Op& op = c.op;
+    MfmaPlan* const P = c.P;
+    const bool resident1 = P->NB == 1 && P->nblk == 1 && P->nblocks_n == 1 && c.persist && c.spec;
     P->persist_f1 = op.fuse1 >= 0 && resident1;
     // wave-specialised persistent kernel (conv12_ws_kernel): one 512-thread workgroup per CU, two input tiles + the resident weights
     // in LDS.  PSEG_NO_WS=1 falls back to the every-wave-does-everything fused instance above.
-    P->ws = P->persist_f1 && !deconv && P->MT == 8 && NT == 2 && KS == 5 && sigma == 3 && op.pool_dst >= 0 && op.add < 0 && !op.in_relu && !op.relu && ws_on;
+    P->ws = P->persist_f1 && !c.deconv && P->MT == 8 && P->NT == 2 && c.KS == 5 && R.sigma == 3 && op.pool_dst >= 0 && op.add < 0 && !op.in_relu && !op.relu && c.ws_on;
     // (the alternative tile loops exist for the default packing only)
     const char* const ws_form = PSEG_KNOB("PSEG_WS_FORM");
     P->ws_form = (ws_form && P->ws && P->pairc2 && op.skiplog >= 0 && (atoi(ws_form) == 1 || atoi(ws_form) == 2)) ? atoi(ws_form) : 0;
     // ... and the k3 stride-2 single-block layers whose instances exist (launch_generic_any2): many tiles, nine k-steps each
-    P->persist_s2 = op.fuse1 < 0 && resident1 && !deconv && KS == 3 && sigma == 4 && P->MT == 2 && NT == 4 && op.stride == 2 && !op.up0 && !op.up1 &&
+    P->persist_s2 = op.fuse1 < 0 && resident1 && !c.deconv && c.KS == 3 && R.sigma == 4 && P->MT == 2 && P->NT == 4 && op.stride == 2 && !op.up0 && !op.up1 &&
                     op.pool_dst < 0 && op.relu_dst < 0 && op.skiplog < 0 && op.tail_logits < 0 && op.dq_fuse < 0 && op.add < 0;
+}
 
-    // ---- pack weights into MFMA A-fragment order -----------------------------------------------
-    // concat-storage channel cs -> true input channel (or -1 for pad)
-    auto true_ci = [&](int cs) {
-        if (cs < Cs0) return cs < C0 ? cs : -1;
-        const int c = cs - Cs0;
-        return c < C1 ? C0 + c : -1;
-    };
-    // weight of (tap, ci, n): conv: w[(tap*Cin+ci)*Cout + n]; deconv: n = ab*CoP + co -> w[(ab*Cin+ci)*Cout+co]
-    auto wval = [&](int tap, int ci, int n) -> float {
-        if (!deconv) return n < Cout ? w[((size_t)tap * Cin + ci) * Cout + n] : 0.0f;
-        const int ab = n / P->CoP, co = n % P->CoP;
-        return (ab < 4 && co < Cout) ? w[((size_t)ab * Cin + ci) * Cout + co] : 0.0f;
-    };
-    // layout [group][N block][k-step in group][cout tile][lane][8]; every channel block is
-    // zero-padded to whole groups
-    auto pack_w = [&](const int GK, const int G) {      // ... for weight groups of GK k-steps, G of them
-    const int gpb_full = cdiv(P->ks_full, GK);
+// ---- pack weights into MFMA A-fragment order -----------------------------------------------
+// The ring stream for weight groups of GK k-steps, G of them: layout [group][N block][k-step in group][cout tile][lane][8]; every
+// channel block is zero-padded to whole groups
+static std::vector<uint16_t> pack_ring_stream(const PackCtx& c, const TileRing& R, const int GK, const int G) {
+    const MfmaPlan* const P = c.P;
+    const int NT = P->NT, KS = c.KS, gpb_full = cdiv(P->ks_full, GK);
     std::vector<uint16_t> pk((size_t)G * GK * P->NTtot * 512, 0);
     for (int b = 0; b < P->nblk; ++b) {
         const bool last = b == P->nblk - 1;
-        const auto& ord = last ? ord_last : ord_full;
+        const auto& ord = last ? R.ord_last : R.ord_full;
         const int ksb = last ? P->ks_last : P->ks_full;
         const int kstep0 = b * gpb_full * GK;
         for (int s = 0; s < ksb; ++s)
             for (int t = 0; t < P->NTtot; ++t)
                 for (int l = 0; l < 64; ++l) {
-                    const Chunk c = ord[(size_t)s * 4 + (l >> 4)];
-                    if (c.cc < 0) continue;
+                    const Chunk ch = ord[(size_t)s * 4 + (l >> 4)];
+                    if (ch.cc < 0) continue;
                     const int n = t * 16 + (l & 15);
                     const int kq = (kstep0 + s) / GK, ksg = (kstep0 + s) % GK, nbk = t / NT, tl = t % NT;
                     uint16_t* o = &pk[(((((size_t)kq * P->nblocks_n + nbk) * GK + ksg) * NT + tl) * 64 + l) * 8];
                     for (int j = 0; j < 8; ++j) {
-                        if (P->pairc2 && c.cc == P->nc_full - 1) {
+                        if (P->pairc2 && ch.cc == P->nc_full - 1) {
                             // elements 0-3: channels 16-19 under tap kx, elements 4-7: channels 16-19 under tap kx + 1 (the tile
                             // holds the right neighbour's four channels there); kx = 4 has no right tap
-                            const int tap = c.tap + (j >> 2), ci = c.cc * 8 + (j & 3);
-                            if ((c.tap % KS) + (j >> 2) < KS) o[j] = f2bf(wval(tap, ci, n));
+                            const int tap = ch.tap + (j >> 2), ci = ch.cc * 8 + (j & 3);
+                            if ((ch.tap % KS) + (j >> 2) < KS) o[j] = f2bf(c.wval(tap, ci, n));
                             continue;
                         }
-                        const int ci = true_ci((b * P->nc_full + c.cc) * 8 + j);
-                        if (ci >= 0) o[j] = f2bf(wval(c.tap, ci, n));
+                        const int ci = c.true_ci((b * P->nc_full + ch.cc) * 8 + j);
+                        if (ci >= 0) o[j] = f2bf(c.wval(ch.tap, ci, n));
                     }
                 }
     }
     return pk;
+}
+
+// ---- paired third tile (conv_pp_kernel's row-reuse loop, 40 couts) ----------------------------------------------------------
+// The third cout tile of a 40-channel layer has eight real rows.  A wave owns output rows r and r + 1, and under row reuse the
+// B fragment of k-step s + 5 of row r IS the B fragment of k-step s of row r + 1.  So one A fragment serves both rows: entry
+// e = 0..29 holds the third tile's rows 0-7 of k-step e in its rows 0-7 (zero for e >= 25) and the same eight rows of k-step
+// e - 5 in its rows 8-15 (zero for e < 5); the k layout inside a fragment is the tile's own.  30 MFMAs per column tile and
+// channel block instead of 2 x 25, one accumulator tile instead of two.  Stated on k-steps, not taps: it holds for whatever
+// tap order the row-reuse check accepted, given that steps s and s + 5 read the same chunk of a pixel (checked here).
+static int pack_pair8(const PackCtx& c, const TileRing& R) {
+    const Op& op = c.op;
+    MfmaPlan* const P = c.P;
+    const int NT = P->NT, GK = R.GK, NB = R.NB, Cout = c.Cout;
+    auto same_chunks = [](const std::vector<Chunk>& ord) {
+        for (int s = 0; s < 20; ++s)
+            for (int gq = 0; gq < 4; ++gq)
+                if (ord[(size_t)(s + 5) * 4 + gq].cc != ord[(size_t)s * 4 + gq].cc) return false;
+        return true;
     };
-    PSEG_TRY(upload(&P->d_wpk, pack_w(GK, P->G)));
-    // ---- paired third tile (conv_pp_kernel's row-reuse loop, 40 couts) ----------------------------------------------------------
-    // The third cout tile of a 40-channel layer has eight real rows.  A wave owns output rows r and r + 1, and under row reuse the
-    // B fragment of k-step s + 5 of row r IS the B fragment of k-step s of row r + 1.  So one A fragment serves both rows: entry
-    // e = 0..29 holds the third tile's rows 0-7 of k-step e in its rows 0-7 (zero for e >= 25) and the same eight rows of k-step
-    // e - 5 in its rows 8-15 (zero for e < 5); the k layout inside a fragment is the tile's own.  30 MFMAs per column tile and
-    // channel block instead of 2 x 25, one accumulator tile instead of two.  Stated on k-steps, not taps: it holds for whatever
-    // tap order the row-reuse check accepted, given that steps s and s + 5 read the same chunk of a pixel (checked here).
-    {
-        auto same_chunks = [&](const std::vector<Chunk>& ord) {
-            for (int s = 0; s < 20; ++s)
-                for (int gq = 0; gq < 4; ++gq)
-                    if (ord[(size_t)(s + 5) * 4 + gq].cc != ord[(size_t)s * 4 + gq].cc) return false;
-            return true;
+    P->pair8 = P->rowreuse && (P->pp || (GK == 4 && NB > 1)) && !R.no_pair8 && NT == 3 && P->nblocks_n == 1 && Cout > 32 && Cout <= 40 && P->ks_full == 25 &&
+               P->ks_last == 25 && same_chunks(R.ord_full) && same_chunks(R.ord_last);
+    if (!P->pair8) {
+        if (PSEG_KNOB("PSEG_LOG_GENERIC") && P->rowreuse && NT == 3) fprintf(stderr, "[pseg] pair8 %s: 0\n", op.layer.c_str());
+        return PSEG_OK;
+    }
+    std::vector<uint16_t> pr((size_t)P->nblk * 30 * 512, 0);
+    for (int b = 0; b < P->nblk; ++b) {
+        const auto& ord = b == P->nblk - 1 ? R.ord_last : R.ord_full;
+        for (int en = 0; en < 30; ++en)
+            for (int l = 0; l < 64; ++l) {
+                const int row = l & 15, s = row < 8 ? en : en - 5;          // the k-step whose weights this row carries
+                if (s < 0 || s >= 25) continue;
+                const Chunk ch = ord[(size_t)s * 4 + (l >> 4)];
+                uint16_t* o = &pr[(((size_t)b * 30 + en) * 64 + l) * 8];
+                for (int j = 0; j < 8; ++j) {
+                    const int ci = c.true_ci((b * P->nc_full + ch.cc) * 8 + j);
+                    if (ci >= 0) o[j] = f2bf(c.wval(ch.tap, ci, 32 + (row & 7)));
+                }
+            }
+    }
+    if (P->pp) PSEG_TRY(upload(&P->d_wpk_pair, pr));
+    // The ring stream of conv_mfma_kernel's row-reuse instance (groups of four k-steps, every channel block padded to whole
+    // groups): entry e < 25 takes the place of the third-tile piece of k-step e -- its rows 8-15 were the zero rows of couts
+    // 40-47 -- and entries 25-29 go to pieces 3-7 of the block's last group, which holds k-step 24 and three steps of zero
+    // padding.  Same groups, same 12 KB per group, same number of DMA pieces per wave: the ring layout does not change.
+    if (GK == 4 && NB > 1) {
+        std::vector<uint16_t> rp = pack_ring_stream(c, R, GK, P->G);
+        const std::vector<uint16_t> orig = rp;
+        const int gpb = cdiv(P->ks_full, GK);
+        auto piece = [&](int b, int en) -> size_t {      // first element of the piece that holds paired entry en of block b
+            const int s = std::min(en, 24), k0 = b * gpb * GK + s;
+            return ((size_t)(k0 / GK) * GK * NT + (size_t)(k0 % GK) * NT + (en < 25 ? 2 : 3 + (en - 25))) * 512;
         };
-        P->pair8 = P->rowreuse && (P->pp || (GK == 4 && NB > 1)) && !no_pair8 && NT == 3 && P->nblocks_n == 1 && Cout > 32 && Cout <= 40 && P->ks_full == 25 &&
-                   P->ks_last == 25 && same_chunks(ord_full) && same_chunks(ord_last);
-        if (P->pair8) {
-            std::vector<uint16_t> pr((size_t)P->nblk * 30 * 512, 0);
-            for (int b = 0; b < P->nblk; ++b) {
-                const auto& ord = b == P->nblk - 1 ? ord_last : ord_full;
-                for (int en = 0; en < 30; ++en)
-                    for (int l = 0; l < 64; ++l) {
-                        const int row = l & 15, s = row < 8 ? en : en - 5;          // the k-step whose weights this row carries
-                        if (s < 0 || s >= 25) continue;
-                        const Chunk c = ord[(size_t)s * 4 + (l >> 4)];
-                        uint16_t* o = &pr[(((size_t)b * 30 + en) * 64 + l) * 8];
-                        for (int j = 0; j < 8; ++j) {
-                            const int ci = true_ci((b * P->nc_full + c.cc) * 8 + j);
-                            if (ci >= 0) o[j] = f2bf(wval(c.tap, ci, 32 + (row & 7)));
-                        }
-                    }
-            }
-            if (P->pp) PSEG_TRY(upload(&P->d_wpk_pair, pr));
-            // The ring stream of conv_mfma_kernel's row-reuse instance (groups of four k-steps, every channel block padded to whole
-            // groups): entry e < 25 takes the place of the third-tile piece of k-step e -- its rows 8-15 were the zero rows of couts
-            // 40-47 -- and entries 25-29 go to pieces 3-7 of the block's last group, which holds k-step 24 and three steps of zero
-            // padding.  Same groups, same 12 KB per group, same number of DMA pieces per wave: the ring layout does not change.
-            if (GK == 4 && NB > 1) {
-                std::vector<uint16_t> rp = pack_w(GK, P->G);
-                const std::vector<uint16_t> orig = rp;
-                const int gpb = cdiv(P->ks_full, GK);
-                auto piece = [&](int b, int en) -> size_t {      // first element of the piece that holds paired entry en of block b
-                    const int s = std::min(en, 24), k0 = b * gpb * GK + s;
-                    return ((size_t)(k0 / GK) * GK * NT + (size_t)(k0 % GK) * NT + (en < 25 ? 2 : 3 + (en - 25))) * 512;
-                };
-                for (int b = 0; b < P->nblk; ++b)
-                    for (int en = 5; en < 30; ++en)
-                        for (int gq = 0; gq < 4; ++gq)
-                            for (int row = 0; row < 8; ++row)
-                                std::copy_n(&orig[piece(b, en - 5) + (size_t)(gq * 16 + row) * 8], 8, &rp[piece(b, en) + (size_t)(gq * 16 + 8 + row) * 8]);
-                PSEG_TRY(upload(&P->d_wpk_rpair, rp));
-            }
-            if (PSEG_KNOB("PSEG_LOG_GENERIC")) {
-                uint32_t h = 2166136261u;                    // FNV-1a of the table's bytes: tests restate the packing and compare
-                for (const uint16_t v : pr) { h = (h ^ (v & 0xffu)) * 16777619u; h = (h ^ (uint32_t)(v >> 8)) * 16777619u; }
-                fprintf(stderr, "[pseg] pair8 %s: 1 (%d channel block(s) x 30 entries, %zu bytes, fnv1a %08x; pp table %d: resident weights %d -> %d bytes; "
-                        "ring stream %d: groups of %d k-steps and %d KB as unpaired, entry s in the third-tile piece of k-step s, entries 25-29 in pieces 3-7 of a block's last group)\n",
-                        op.layer.c_str(), P->nblk, pr.size() * 2, h, P->d_wpk_pair ? 1 : 0, P->ks_full * 2560, P->ks_full * 2048 + 30 * 1024,
-                        P->d_wpk_rpair ? 1 : 0, GK, GK * NT);
-            }
-        } else if (PSEG_KNOB("PSEG_LOG_GENERIC") && P->rowreuse && NT == 3)
-            fprintf(stderr, "[pseg] pair8 %s: 0\n", op.layer.c_str());
+        for (int b = 0; b < P->nblk; ++b)
+            for (int en = 5; en < 30; ++en)
+                for (int gq = 0; gq < 4; ++gq)
+                    for (int row = 0; row < 8; ++row)
+                        std::copy_n(&orig[piece(b, en - 5) + (size_t)(gq * 16 + row) * 8], 8, &rp[piece(b, en) + (size_t)(gq * 16 + 8 + row) * 8]);
+        PSEG_TRY(upload(&P->d_wpk_rpair, rp));
     }
-    // ---- tile triples (conv_mfma_kernel, TT_ = 3): three teams on their own tiles share ONE weight ring in the CU's pooled LDS --------
-    // Same tile, table, k order and epilogue per team; what is planned here is the second ring layout: 160 KB minus three tiles (the
-    // teams' store patches lie over tiles and ring once every wave is out of the k-loop) and the table.  PSEG_NO_TRIPLE=1: the plan
-    // switch back; PSEG_TRIPLE=1: every planned layer on any page size, page units included (tests, A/B).
-    {
-        const bool inst = KS == 5 && P->MT == 4 && ((NT == 4 && (sigma == 4 || sigma == 5)) || (NT == 3 && sigma == 4 && op.pool_dst < 0));   // triple_run
-        const bool shape = P->wg3 && !P->pp_shape && inst && P->nblocks_n == 1 && !op.up0 && !op.up1 && !op.in_relu && op.add < 0 && op.fuse1 < 0 &&
-                           op.tail_logits < 0 && op.skiplog < 0 && op.relu_dst < 0 && op.dq_fuse < 0 && NB > 1;
-        const int stride = round_up(in_bytes, 16), LDS_MAX = 160 * 1024;
-        const int steps = (LDS_MAX - 3 * stride - tab_bytes - 16) / (NT * 1024);      // k-steps the shared ring can hold
-        // two slots of the largest BALANCED groups that fit: every group boundary is a barrier of all twelve waves, with no other
-        // workgroup on the CU to fill it, so fewer and longer groups win over more groups in flight (measured -- profiles/tile_triples.txt,
-        // conv6: 9 x 2 39.5, 5 x 3 40.5, 4 x 4 42.5, 2 x 6 46.9 us).  A row-reuse layer takes the groups of eight its triple instance is
-        // compiled for (25 = 3 x 8 + 1; groups of four, the one-tile workgroup's: 58 us against its 55).
-        const bool rr8 = P->rowreuse && NT == 3 && P->ks_full == 25 && P->ks_last == 25 && steps >= 16;
-        const int nb3 = 2, cap = std::min(steps / 2, 16);
-        const int gk3 = rr8 ? 8 : (cap >= 1 ? cdiv(ks_max, cdiv(ks_max, cap)) : 0);
-        if (shape && gk3 >= 1 && nb3 >= 2 && !PSEG_KNOB("PSEG_NO_TRIPLE")) {
-            const char* const sw = PSEG_KNOB("PSEG_TRIPLE");
-            P->triple = true;
-            P->triple_all = sw && atoi(sw) != 0;
-            MfmaPlan::TripleLayout& T = P->tr;
-            T.GK = gk3; T.NB = nb3; T.stride = stride;
-            T.G = (P->nblk - 1) * cdiv(P->ks_full, gk3) + cdiv(P->ks_last, gk3);
-            T.w_off = 3 * stride;
-            T.tab_off = T.w_off + nb3 * gk3 * NT * 1024;
-            T.lds = std::max(T.tab_off + tab_bytes + 16, 3 * 4 * (P->MT / 2) * TW * (NT * 32 + 8));
-            if (gk3 != GK) PSEG_TRY(upload(&T.d_wpk, pack_w(gk3, T.G)));
-        }
-        if (PSEG_KNOB("PSEG_LOG_GENERIC") && shape)
-            fprintf(stderr, "[pseg] triple %s: %d (one tile per workgroup: GK %d NB %d lds %d; triples: GK %d NB %d lds %d)\n", op.layer.c_str(),
-                    P->triple ? 1 : 0, GK, NB, P->lds_bytes, P->triple ? P->tr.GK : 0, P->triple ? P->tr.NB : 0, P->triple ? P->tr.lds : 0);
+    if (PSEG_KNOB("PSEG_LOG_GENERIC")) {
+        uint32_t h = 2166136261u;                    // FNV-1a of the table's bytes: tests restate the packing and compare
+        for (const uint16_t v : pr) { h = (h ^ (v & 0xffu)) * 16777619u; h = (h ^ (uint32_t)(v >> 8)) * 16777619u; }
+        fprintf(stderr, "[pseg] pair8 %s: 1 (%d channel block(s) x 30 entries, %zu bytes, fnv1a %08x; pp table %d: resident weights %d -> %d bytes; "
+                "ring stream %d: groups of %d k-steps and %d KB as unpaired, entry s in the third-tile piece of k-step s, entries 25-29 in pieces 3-7 of a block's last group)\n",
+                op.layer.c_str(), P->nblk, pr.size() * 2, h, P->d_wpk_pair ? 1 : 0, P->ks_full * 2560, P->ks_full * 2048 + 30 * 1024,
+                P->d_wpk_rpair ? 1 : 0, GK, GK * NT);
     }
+    return PSEG_OK;
+}
+
+// ---- tile triples (conv_mfma_kernel, TT_ = 3): three teams on their own tiles share ONE weight ring in the CU's pooled LDS --------
+// Same tile, table, k order and epilogue per team; what is planned here is the second ring layout: 160 KB minus three tiles (the
+// teams' store patches lie over tiles and ring once every wave is out of the k-loop) and the table.  PSEG_NO_TRIPLE=1: the plan
+// switch back; PSEG_TRIPLE=1: every planned layer on any page size, page units included (tests, A/B).
+static int plan_triple(const PackCtx& c, const TileRing& R) {
+    const Op& op = c.op;
+    MfmaPlan* const P = c.P;
+    const int NT = P->NT, KS = c.KS, sigma = R.sigma, GK = R.GK, NB = R.NB, in_bytes = R.in_bytes, tab_bytes = R.tab_bytes, ks_max = R.ks_max;
+    const bool inst = KS == 5 && P->MT == 4 && ((NT == 4 && (sigma == 4 || sigma == 5)) || (NT == 3 && sigma == 4 && op.pool_dst < 0));   // triple_run
+    const bool shape = P->wg3 && !P->pp_shape && inst && P->nblocks_n == 1 && !op.up0 && !op.up1 && !op.in_relu && op.add < 0 && op.fuse1 < 0 &&
+                       op.tail_logits < 0 && op.skiplog < 0 && op.relu_dst < 0 && op.dq_fuse < 0 && NB > 1;
+    const int stride = round_up(in_bytes, 16), LDS_MAX = 160 * 1024;
+    const int steps = (LDS_MAX - 3 * stride - tab_bytes - 16) / (NT * 1024);      // k-steps the shared ring can hold
+    // two slots of the largest BALANCED groups that fit: every group boundary is a barrier of all twelve waves, with no other
+    // workgroup on the CU to fill it, so fewer and longer groups win over more groups in flight (measured -- profiles/tile_triples.txt,
+    // conv6: 9 x 2 39.5, 5 x 3 40.5, 4 x 4 42.5, 2 x 6 46.9 us).  A row-reuse layer takes the groups of eight its triple instance is
+    // compiled for (25 = 3 x 8 + 1; groups of four, the one-tile workgroup's: 58 us against its 55).
+    const bool rr8 = P->rowreuse && NT == 3 && P->ks_full == 25 && P->ks_last == 25 && steps >= 16;
+    const int nb3 = 2, cap = std::min(steps / 2, 16);
+    const int gk3 = rr8 ? 8 : (cap >= 1 ? cdiv(ks_max, cdiv(ks_max, cap)) : 0);
+    if (shape && gk3 >= 1 && nb3 >= 2 && !PSEG_KNOB("PSEG_NO_TRIPLE")) {
+        const char* const sw = PSEG_KNOB("PSEG_TRIPLE");
+        P->triple = true;
+        P->triple_all = sw && atoi(sw) != 0;
+        MfmaPlan::TripleLayout& T = P->tr;
+        T.GK = gk3; T.NB = nb3; T.stride = stride;
+        T.G = (P->nblk - 1) * cdiv(P->ks_full, gk3) + cdiv(P->ks_last, gk3);
+        T.w_off = 3 * stride;
+        T.tab_off = T.w_off + nb3 * gk3 * NT * 1024;
+        T.lds = std::max(T.tab_off + tab_bytes + 16, 3 * 4 * (P->MT / 2) * TW * (NT * 32 + 8));
+        if (gk3 != GK) PSEG_TRY(upload(&T.d_wpk, pack_ring_stream(c, R, gk3, T.G)));
+    }
+    if (PSEG_KNOB("PSEG_LOG_GENERIC") && shape)
+        fprintf(stderr, "[pseg] triple %s: %d (one tile per workgroup: GK %d NB %d lds %d; triples: GK %d NB %d lds %d)\n", op.layer.c_str(),
+                P->triple ? 1 : 0, GK, NB, P->lds_bytes, P->triple ? P->tr.GK : 0, P->triple ? P->tr.NB : 0, P->triple ? P->tr.lds : 0);
+    return PSEG_OK;
+}
+
+// the layer's bias per packed output row: a transposed conv repeats it for each of its four sub-pixels
+static int pack_bias(const PackCtx& c) {
+    const MfmaPlan* const P = c.P;
     std::vector<float> bb((size_t)P->NTtot * 16, 0.0f);
     for (int n = 0; n < P->NTtot * 16; ++n) {
-        if (!deconv) { if (n < Cout) bb[n] = bias[n]; }
-        else { const int ab = n / P->CoP, co = n % P->CoP; if (ab < 4 && co < Cout) bb[n] = bias[co]; }
+        if (!c.deconv) { if (n < c.Cout) bb[n] = c.bias[n]; }
+        else { const int ab = n / P->CoP, co = n % P->CoP; if (ab < 4 && co < c.Cout) bb[n] = c.bias[co]; }
     }
-    PSEG_TRY(upload(&P->d_bias, bb));
-    // ---- second packing for conv_sp_kernel: k5 stride-1 layers with one N block whose weights are streamed ----------
-    if (!deconv && KS == 5 && op.stride == 1 && !op.up0 && !op.up1 && !op.in_relu && op.add < 0 && op.fuse1 < 0 && op.tail_logits < 0 &&
-        op.skiplog < 0 && op.relu_dst < 0 && P->nblocks_n == 1 && NT >= 3 && NT <= 5 && (op.dq_fuse < 0 || NT == 5) && !P->pp_shape &&
-        !PSEG_KNOB("PSEG_NO_SP") && spec) {
-        const int sg = P->nc_full;                 // dense tile: sigma = chunks per pixel of a block
-        const int rowp = ((TW + KS - 1) * sg + best_pad(sg, (TW + KS - 1) * sg, false, 0)) * 16, TBLK = round_up((8 + KS - 1) * rowp, 16);
-        const auto o_full = pair_chunks(KS, P->nc_full, sg, rowp / 16), o_last = pair_chunks(KS, P->nc_last, sg, rowp / 16);
-        const int ksf = (int)o_full.size() / 4, ksl = (int)o_last.size() / 4;
-        const int K0 = (P->nblk - 1) * ksf + ksl, K = round_up(K0, 2);
-        const bool dq = op.dq_fuse >= 0;
-        const int S = round_up(K + (dq ? cdiv(SP_DQ_PIECES, NT) : 0), SP_GK);
-        const int nslot = P->nblk == 1 ? 2 : P->nblk;
-        const int tiles_b = nslot * TBLK, tabb = K * 16, LDS_MAX = 160 * 1024;
-        const int patchb = dq ? 4 * 2 * 16 * (128 + 8) : 4 * 2 * TW * (NT * 32 + 8);   // the transposed conv's 16-pixel patches / the plain epilogue's two rows per wave
-        auto ring_for = [&](bool patch) {          // largest even ring (<= 16 steps: vmcnt counts, SP_PUB) that fits
-            int rk = (LDS_MAX - tiles_b - round_up(tabb, 1024) - 64 - (patch ? patchb : 0)) / (NT * 1024);
-            rk = std::min(rk, 16) & ~1;
-            return rk;
-        };
-        const int rk_min = dq ? 12 : 10;           // five ring slots of two k-steps; the transposed conv's 10 pseudo-steps sit in the ring at once
-        const bool patch = dq || ring_for(true) >= rk_min;
-        const int RK = ring_for(patch);
-        // the kernel instances (sp_run), a row pitch the kernel is compiled for, channel blocks that have ONE source each,
-        // at most four of them (the tile loaders' counted waits), 64 output channels behind a fused transposed conv
-        const bool inst = (NT == 5 && sg == 4 && (dq || patch)) || (NT == 4 && (sg == 4 || sg == 5) && patch) || (NT == 3 && sg == 4);
-        const bool shape_ok = rowp == sp_row_pitch(sg) && P->nblk <= 4 && (!s1 || (Cs0 / 8) % P->nc_full == 0) &&
-                              (!dq || e.tensors[e.ops[op.dq_fuse].dst].Cs == 64);
-        if (RK >= rk_min && inst && shape_ok && ksf >= 2) {
-            P->sp = true;
-            P->sp_NT = NT; P->sp_sigma = sg; P->sp_K = K; P->sp_S = S; P->sp_blk_steps = ksf;
-            P->sp_nblk = P->nblk; P->sp_nc_full = P->nc_full; P->sp_nc_last = P->nc_last;
-            P->sp_fl = (dq ? SP_DQ : 0) | (patch && !dq ? SP_PATCH : 0) | (op.pool_dst >= 0 ? SP_POOL : 0);
-            // every real k-chunk of the layer in stream order: f(k-step of the tile, lane group, channel block, chunk).  (Dummies keep
-            // offset 0 -- finite data -- and zero weights.)
-            auto walk = [&](auto f) {
-                for (int b = 0; b < P->nblk; ++b) {
-                    const bool last = b == P->nblk - 1;
-                    const auto& ord = last ? o_last : o_full;
-                    const int ksb = last ? ksl : ksf;
-                    for (int st = 0; st < ksb; ++st)
-                        for (int gi = 0; gi < 4; ++gi) {
-                            const Chunk c = ord[(size_t)st * 4 + gi];
-                            if (c.cc >= 0) f(b * ksf + st, gi, b, c);
-                        }
+    return upload(&c.P->d_bias, bb);
+}
+
+// ---- second packing for conv_sp_kernel: k5 stride-1 layers with one N block whose weights are streamed ----------
+// One weight stream (d_sp_wpk) in one chunk order for every layout of the layer -- conv_sp_kernel on tiles of 8 x 32 and 8 x 24,
+// conv_sp2_kernel on both -- each with its own LDS layout and k-chunk table, and the engine's give-up record.
+static int plan_streamed(const PackCtx& c) {
+    Engine& e = c.e;
+    const Op& op = c.op;
+    MfmaPlan* const P = c.P;
+    const int NT = P->NT, KS = c.KS;
+    if (!(!c.deconv && KS == 5 && op.stride == 1 && !op.up0 && !op.up1 && !op.in_relu && op.add < 0 && op.fuse1 < 0 && op.tail_logits < 0 &&
+          op.skiplog < 0 && op.relu_dst < 0 && P->nblocks_n == 1 && NT >= 3 && NT <= 5 && (op.dq_fuse < 0 || NT == 5) && !P->pp_shape &&
+          !PSEG_KNOB("PSEG_NO_SP") && c.spec)) return PSEG_OK;
+    const int sg = P->nc_full;                 // dense tile: sigma = chunks per pixel of a block
+    const int rowp = ((TW + KS - 1) * sg + best_pad(KS, P->nc_full, sg, (TW + KS - 1) * sg, false, 0)) * 16, TBLK = round_up((8 + KS - 1) * rowp, 16);
+    const auto o_full = pair_chunks(KS, P->nc_full, sg, rowp / 16), o_last = pair_chunks(KS, P->nc_last, sg, rowp / 16);
+    const int ksf = (int)o_full.size() / 4, ksl = (int)o_last.size() / 4;
+    const int K0 = (P->nblk - 1) * ksf + ksl, K = round_up(K0, 2);
+    const bool dq = op.dq_fuse >= 0;
+    const int S = round_up(K + (dq ? cdiv(SP_DQ_PIECES, NT) : 0), SP_GK);
+    const int nslot = P->nblk == 1 ? 2 : P->nblk;
+    const int tiles_b = nslot * TBLK, tabb = K * 16, LDS_MAX = 160 * 1024;
+    const int patchb = dq ? 4 * 2 * 16 * (128 + 8) : 4 * 2 * TW * (NT * 32 + 8);   // the transposed conv's 16-pixel patches / the plain epilogue's two rows per wave
+    auto ring_for = [&](bool patch) {          // largest even ring (<= 16 steps: vmcnt counts, SP_PUB) that fits
+        return std::min((LDS_MAX - tiles_b - round_up(tabb, 1024) - 64 - (patch ? patchb : 0)) / (NT * 1024), 16) & ~1;
+    };
+    const int rk_min = dq ? 12 : 10;           // five ring slots of two k-steps; the transposed conv's 10 pseudo-steps sit in the ring at once
+    const bool patch = dq || ring_for(true) >= rk_min;
+    const int RK = ring_for(patch);
+    // the kernel instances (sp_run), a row pitch the kernel is compiled for, channel blocks that have ONE source each,
+    // at most four of them (the tile loaders' counted waits), 64 output channels behind a fused transposed conv
+    const bool inst = (NT == 5 && sg == 4 && (dq || patch)) || (NT == 4 && (sg == 4 || sg == 5) && patch) || (NT == 3 && sg == 4);
+    const bool shape_ok = rowp == sp_row_pitch(sg) && P->nblk <= 4 && (!c.s1 || (c.Cs0 / 8) % P->nc_full == 0) &&
+                          (!dq || e.tensors[e.ops[op.dq_fuse].dst].Cs == 64);
+    if (!(RK >= rk_min && inst && shape_ok && ksf >= 2)) return PSEG_OK;
+    P->sp = true;
+    P->sp_NT = NT; P->sp_sigma = sg; P->sp_K = K; P->sp_S = S; P->sp_blk_steps = ksf;
+    P->sp_nblk = P->nblk; P->sp_nc_full = P->nc_full; P->sp_nc_last = P->nc_last;
+    P->sp_fl = (dq ? SP_DQ : 0) | (patch && !dq ? SP_PATCH : 0) | (op.pool_dst >= 0 ? SP_POOL : 0);
+    // every real k-chunk of the layer in stream order: f(k-step of the tile, lane group, channel block, chunk).  (Dummies keep
+    // offset 0 -- finite data -- and zero weights.)
+    auto walk = [&](auto f) {
+        for (int b = 0; b < P->nblk; ++b) {
+            const bool last = b == P->nblk - 1;
+            const auto& ord = last ? o_last : o_full;
+            const int ksb = last ? ksl : ksf;
+            for (int st = 0; st < ksb; ++st)
+                for (int gi = 0; gi < 4; ++gi) {
+                    const Chunk ch = ord[(size_t)st * 4 + gi];
+                    if (ch.cc >= 0) f(b * ksf + st, gi, b, ch);
                 }
-            };
-            // conv_sp_kernel's k-chunk table for a tile of row pitch `pitch` in block slots of `tblk` bytes
-            auto sp_table = [&](int pitch, int tblk) {
-                std::vector<int> tab((size_t)K * 4, 0);
-                walk([&](int st, int gi, int b, Chunk c) {
-                    tab[(size_t)st * 4 + gi] = (P->nblk == 1 ? 0 : b * tblk) + (c.tap / KS) * pitch + (c.tap % KS) * sg * 16 + c.cc * 16;
-                });
-                return tab;
-            };
-            // LDS of one kernel at one tile width: block slots | weight ring of rk steps | store patch | k-chunk table | flags
-            auto lay_out = [&](MfmaPlan::SpLayout& L, int pitch, int tblk, int slots, int rk, int patch_b, int tab_b, int flag_b) {
-                L.ok = true; L.row_pitch = pitch; L.TBLK = tblk; L.RK = rk;
-                L.ring_off = slots * tblk; L.patch_off = L.ring_off + rk * NT * 1024; L.tab_off = L.patch_off + patch_b;
-                L.flag_off = L.tab_off + tab_b; L.lds = L.flag_off + flag_b;
-            };
-            lay_out(P->sp_lay[0], rowp, TBLK, nslot, RK, patch ? patchb : 0, round_up(tabb, 1024), 64);      // (the table arrives in 1 KiB DMA pieces)
-            std::vector<uint16_t> spk((size_t)S * NT * 512, 0);
-            walk([&](int st, int gi, int b, Chunk c) {
-                for (int t = 0; t < NT; ++t)
-                    for (int p16 = 0; p16 < 16; ++p16) {
-                        uint16_t* o = &spk[(((size_t)st * NT + t) * 64 + gi * 16 + p16) * 8];
-                        for (int j = 0; j < 8; ++j) {
-                            const int ci = true_ci((b * P->nc_full + c.cc) * 8 + j);
-                            if (ci >= 0) o[j] = f2bf(wval(c.tap, ci, t * 16 + p16));
-                        }
-                    }
-            });
-            PSEG_TRY(upload(&P->sp_lay[0].d_tab, sp_table(rowp, TBLK)));
-            PSEG_TRY(upload(&P->d_sp_wpk, spk));
-            // the narrow tile (8 x 24, instances for the 80-channel layers): same chunk ORDER (same products in the same order: same
-            // bits), offsets for its own row pitch, a ring as deep as its smaller tile allows
-            if (NT == 5 && sg == 4 && op.pool_dst < 0 && !PSEG_KNOB("PSEG_NO_SP24")) {
-                const int TWN = 24, rowpn = sp_row_pitch(sg, TWN), TBLKn = round_up((8 + KS - 1) * rowpn, 16), tiles_n = nslot * TBLKn;
-                const int patchn = dq ? patchb : 4 * 2 * TWN * (NT * 32 + 8);
-                const int rkn = std::min((LDS_MAX - tiles_n - round_up(tabb, 1024) - 64 - patchn) / (NT * 1024), 16) & ~1;
-                if (rkn >= rk_min) {
-                    lay_out(P->sp_lay[1], rowpn, TBLKn, nslot, rkn, patchn, round_up(tabb, 1024), 64);
-                    PSEG_TRY(upload(&P->sp_lay[1].d_tab, sp_table(rowpn, TBLKn)));
-                }
-            }
-            // conv_sp2_kernel: two compute teams on a pool of four block slots (NT 3 / 4 layers; the fused transposed conv stays above).
-            // PSEG_SP2 (plan switch: tests, A/B): 0 off, 1 every eligible launch, 24 / 32 likewise with that tile width
-            const char* const sp2_sw = PSEG_KNOB("PSEG_SP2");
-            P->sp2_all = sp2_sw && atoi(sp2_sw) != 0;
-            P->sp2_tw = sp2_sw ? atoi(sp2_sw) : 0;
-            if (!dq && NT <= 4 && !(sp2_sw && atoi(sp2_sw) == 0)) {
-                for (int v = 0; v < 2; ++v) {
-                    const int twv = v == 0 ? 32 : 24, rowpv = sp_row_pitch(sg, twv), TBLKv = round_up((8 + KS - 1) * rowpv, 16);
-                    const int patchv = 8 * 8 * (NT * 32 + 8), tabv = round_up((K + 2) * 128, 1024);     // table: [k-step][lane group][column & 7]
-                    const int rkv = std::min((LDS_MAX - SP2_NSLOT * TBLKv - patchv - tabv - 128) / (NT * 1024), 16) & ~1;
-                    if (rkv < 10) continue;
-                    lay_out(P->sp2_lay[v], rowpv, TBLKv, SP2_NSLOT, rkv, patchv, tabv, 128);
-                    std::vector<int> tabq((size_t)(K + 2) * 32, 0);       // (two rows beyond K: the loop looks its offsets up two steps ahead, unclamped)
-                    walk([&](int st, int gi, int, Chunk c) {
-                        for (int p7 = 0; p7 < 8; ++p7) {
-                            // four-chunk blocks are stored swizzled: chunk c of halo column x in slot c ^ 2 ((x >> 2) & 1); x = p + kx (+ 16)
-                            const int slot = sg == 4 ? c.cc ^ ((((p7 + c.tap % KS) >> 2) & 1) << 1) : c.cc;
-                            tabq[((size_t)st * 4 + gi) * 8 + p7] = (c.tap / KS) * rowpv + (c.tap % KS) * sg * 16 + slot * 16;   // inside the block's slot
-                        }
-                    });
-                    for (int r = K; r < K + 2; ++r) std::copy(tabq.begin() + (size_t)(K - 1) * 32, tabq.begin() + (size_t)K * 32, tabq.begin() + (size_t)r * 32);
-                    PSEG_TRY(upload(&P->sp2_lay[v].d_tab, tabq));
-                }
-            }
-            if (!e.d_sp_err) {   // the engine's give-up record of conv_sp_kernel (engine_status)
-                PSEG_HIP(hipMalloc((void**)&e.d_sp_err, 32));
-                PSEG_HIP(hipMemset(e.d_sp_err, 0, 32));
-                PSEG_HIP(hipHostMalloc((void**)&e.h_sp_err, 32, hipHostMallocDefault));
-            }
-            if (PSEG_KNOB("PSEG_LOG_SP"))
-                fprintf(stderr, "[pseg] conv_sp plan %s: NT %d sigma %d fl %d nblk %d (nc %d / %d) K %d S %d blk_steps %d row_pitch %d TBLK %d RK %d lds %d\n", op.layer.c_str(),
-                        NT, sg, P->sp_fl, P->nblk, P->nc_full, P->nc_last, K, S, ksf, rowp, TBLK, RK, P->sp_lay[0].lds);
         }
-    }
-    if (deconv && op.into_tail >= 0) {
-        // this transposed conv runs inside the composed tail: A fragments [ab][cout tile 2][k-step 4][lane = (cout & 15, g)][8],
-        // element j <-> storage channel (4s + g) * 8 + j of the concatenated quarter-resolution sources
-        std::vector<uint16_t> wq((size_t)4 * 2 * 4 * 64 * 8, 0);
-        for (int ab = 0; ab < 4; ++ab)
-            for (int t = 0; t < 2; ++t)
-                for (int sidx = 0; sidx < 4; ++sidx)
-                    for (int l = 0; l < 64; ++l) {
-                        // one source: chunk 4s + g; two sources (each <= 8 chunks): k-steps 0-1 take source 0, k-steps 2-3 source 1, so that
-                        // every fragment load of the tail kernel reads ONE tensor
-                        const int co = t * 16 + (l & 15), gg = l >> 4;
-                        if (co >= Cout) continue;
-                        int chunk = 4 * sidx + gg;
-                        if (s1) {
-                            const int c2 = 4 * (sidx & 1) + gg;
-                            if (c2 >= (sidx < 2 ? Cs0 : Cs1) / 8) continue;
-                            chunk = sidx < 2 ? c2 : Cs0 / 8 + c2;
-                        }
-                        for (int j = 0; j < 8; ++j) {
-                            const int cs = chunk * 8 + j;
-                            if (cs >= Cs0 + Cs1) continue;
-                            const int ci = true_ci(cs);
-                            if (ci >= 0) wq[((((size_t)ab * 2 + t) * 4 + sidx) * 64 + l) * 8 + j] = f2bf(w[((size_t)ab * Cin + ci) * Cout + co]);
-                        }
-                    }
-        std::vector<float> bq(32, 0.0f);
-        for (int c = 0; c < Cout; ++c) bq[c] = bias[c];
-        PSEG_TRY(upload(&P->d_q_w, wq));
-        PSEG_TRY(upload(&P->d_q_bias, bq));
-    }
-    if (deconv) {
-        bool fused_behind_conv = false;
-        for (auto& o : e.ops) fused_behind_conv |= o.dq_fuse == (int)(&op - e.ops.data());
-        if (fused_behind_conv) {
-            // this transposed conv runs in the epilogue of the conv that produces its input: the B operand of k-step s is built
-            // from that conv's accumulator tiles 2s and 2s + 1 -- lane (pixel, g) holds channels 16 (2s) + 4g .. + 3 in elements
-            // 0-3 and 16 (2s + 1) + 4g .. + 3 in elements 4-7 -- so A fragment (ab, cout tile t, s): lane (cout 16t + l % 16,
-            // g = l / 16), element j <-> input channel 16 (2s + j / 4) + 4g + j % 4
-            std::vector<uint16_t> wq((size_t)4 * 4 * 3 * 64 * 8, 0);
-            for (int ab = 0; ab < 4; ++ab)
-                for (int t = 0; t < 4; ++t)
-                    for (int sidx = 0; sidx < 3; ++sidx)
-                        for (int l = 0; l < 64; ++l) {
-                            const int co = t * 16 + (l & 15), gg = l >> 4;
-                            if (co >= Cout) continue;
-                            for (int j = 0; j < 8; ++j) {
-                                const int ci = 16 * (2 * sidx + (j >> 2)) + 4 * gg + (j & 3);
-                                if (ci < Cin) wq[((((size_t)ab * 4 + t) * 3 + sidx) * 64 + l) * 8 + j] = f2bf(w[((size_t)ab * Cin + ci) * Cout + co]);
-                            }
-                        }
-            std::vector<float> bq(64, 0.0f);
-            for (int c = 0; c < Cout; ++c) bq[c] = bias[c];
-            PSEG_TRY(upload(&P->d_dq_w, wq));
-            PSEG_TRY(upload(&P->d_dq_bias, bq));
-            // conv_sp_kernel takes these 48 fragments from its weight ring: they follow the conv's k-steps in the producer's stream
-            for (auto& o : e.ops) {
-                auto* PC = (MfmaPlan*)o.plan;
-                if (o.dq_fuse != (int)(&op - e.ops.data()) || !PC || !PC->sp) continue;
-                if (!(PC->sp_fl & SP_DQ) || (size_t)(PC->sp_S - PC->sp_K) * PC->sp_NT * 512 < wq.size()) return fail(PSEG_EINVAL, "conv_sp_kernel: no room for the transposed conv's fragments");
-                PSEG_HIP(hipMemcpy(PC->d_sp_wpk + (size_t)PC->sp_K * PC->sp_NT * 512, wq.data(), wq.size() * 2, hipMemcpyHostToDevice));
-            }
-        }
-    }
-    if (!deconv && op.skiplog >= 0) {
-        // skip-logits fusion: the logits kernel rows of this layer's channels (they follow the deconv channels in the
-        // concat, Keras (1,1,Cdec+Cout,C): w[(Cdec + co)*C + c]) as ONE A fragment: lane l = (class = l & 15, g = l >> 4),
-        // element j <-> cout co = j < 4 ? 4g + j : 16 + 4g + (j - 4)
-        const Op& lg = e.ops[op.skiplog];
-        const std::vector<float>& lw = e.params[lg.kparam].host;
-        const int C = lg.Cout, Cdec = lg.Cin - Cout;
-        std::vector<uint16_t> wq(64 * 8, 0);
-        for (int l = 0; l < 64; ++l) {
-            const int cls = l & 15, gg = l >> 4;
-            if (cls >= C) continue;
-            for (int j = 0; j < 8; ++j) {
-                const int co = j < 4 ? 4 * gg + j : 16 + 4 * gg + (j - 4);
-                if (co < Cout) wq[l * 8 + j] = f2bf(lw[(size_t)(Cdec + co) * C + cls]);
-            }
-        }
-        PSEG_TRY(upload(&P->d_tail_wa, wq));
-        P->skip_CP = C <= 4 ? 4 : 8;
-    }
-    if (!deconv && op.tail_logits >= 0) {
-        // conv + logits fusion: logits kernel (Keras (1,1,64,C): w[co*C + c]) in the fragment order of the two
-        // epilogue MFMAs: lane l = (class = l & 15, g = l >> 4), MFMA q, element j <-> cout
-        // co = j < 4 ? 16(2q) + 4g + j : 16(2q+1) + 4g + (j - 4)
-        if (NT != 4 || P->nblocks_n != 1) return fail(PSEG_EUNSUPPORTED, "conv + logits fusion needs a 64-cout layer");
-        const Op& lg = e.ops[op.tail_logits];
-        const std::vector<float>& lw = e.params[lg.kparam].host;
-        const std::vector<float>& lbias = e.params[lg.bparam].host;
-        const int C = lg.Cout;
-        std::vector<uint16_t> wq[2] = {std::vector<uint16_t>(64 * 8, 0), std::vector<uint16_t>(64 * 8, 0)};
-        for (int q = 0; q < 2; ++q)
-            for (int l = 0; l < 64; ++l) {
-                const int cls = l & 15, gg = l >> 4;
-                if (cls >= C) continue;
+    };
+    // conv_sp_kernel's k-chunk table for a tile of row pitch `pitch` in block slots of `tblk` bytes
+    auto sp_table = [&](int pitch, int tblk) {
+        std::vector<int> tab((size_t)K * 4, 0);
+        walk([&](int st, int gi, int b, Chunk ch) {
+            tab[(size_t)st * 4 + gi] = (P->nblk == 1 ? 0 : b * tblk) + (ch.tap / KS) * pitch + (ch.tap % KS) * sg * 16 + ch.cc * 16;
+        });
+        return tab;
+    };
+    // LDS of one kernel at one tile width: block slots | weight ring of rk steps | store patch | k-chunk table | flags
+    auto lay_out = [&](MfmaPlan::SpLayout& L, int pitch, int tblk, int slots, int rk, int patch_b, int tab_b, int flag_b) {
+        L.ok = true; L.row_pitch = pitch; L.TBLK = tblk; L.RK = rk;
+        L.ring_off = slots * tblk; L.patch_off = L.ring_off + rk * NT * 1024; L.tab_off = L.patch_off + patch_b;
+        L.flag_off = L.tab_off + tab_b; L.lds = L.flag_off + flag_b;
+    };
+    lay_out(P->sp_lay[0], rowp, TBLK, nslot, RK, patch ? patchb : 0, round_up(tabb, 1024), 64);      // (the table arrives in 1 KiB DMA pieces)
+    std::vector<uint16_t> spk((size_t)S * NT * 512, 0);
+    walk([&](int st, int gi, int b, Chunk ch) {
+        for (int t = 0; t < NT; ++t)
+            for (int p16 = 0; p16 < 16; ++p16) {
+                uint16_t* o = &spk[(((size_t)st * NT + t) * 64 + gi * 16 + p16) * 8];
                 for (int j = 0; j < 8; ++j) {
-                    const int co = j < 4 ? 16 * (2 * q) + 4 * gg + j : 16 * (2 * q + 1) + 4 * gg + (j - 4);
-                    if (co < Cout) wq[q][l * 8 + j] = f2bf(lw[(size_t)co * C + cls]);
+                    const int ci = c.true_ci((b * P->nc_full + ch.cc) * 8 + j);
+                    if (ci >= 0) o[j] = f2bf(c.wval(ch.tap, ci, t * 16 + p16));
                 }
             }
-        std::vector<float> tb(16, 0.0f);
-        for (int c = 0; c < C; ++c) tb[c] = lbias[c];
-        PSEG_TRY(upload(&P->d_tail_wa, wq[0]));
-        PSEG_TRY(upload(&P->d_tail_wb, wq[1]));
-        PSEG_TRY(upload(&P->d_tail_bias, tb));
-    }
-    if (tail) {
-        // logits weights (Keras (1,1,Cin,C): w[ci*C + c]) in the fragment order of the fused
-        // tail: lane l = (class = l & 15, g = l >> 4), element j <-> deconv channel
-        // co = j < 4 ? 4g + j : 16 + 4g + (j - 4); skip channel 8g + j.
-        const Op& lg = e.ops[op.tail_logits];
-        const std::vector<float>& lw = e.params[lg.kparam].host;
-        const std::vector<float>& lbias = e.params[lg.bparam].host;
-        const int C = lg.Cout, Cd = Cout;
-        const int Cskip = lg.src1 >= 0 ? e.tensors[lg.src1].C : 0;
-        std::vector<uint16_t> wa(64 * 8, 0), wbk(64 * 8, 0);
-        for (int l = 0; l < 64; ++l) {
-            const int cls = l & 15, gg = l >> 4;
-            if (cls >= C) continue;
-            for (int j = 0; j < 8; ++j) {
-                const int co = j < 4 ? 4 * gg + j : 16 + 4 * gg + (j - 4);
-                if (co < Cd) wa[l * 8 + j] = f2bf(lw[(size_t)co * C + cls]);
-                const int ch = 8 * gg + j;
-                if (ch < Cskip) wbk[l * 8 + j] = f2bf(lw[(size_t)(Cd + ch) * C + cls]);
-            }
-        }
-        std::vector<float> tb(16, 0.0f);
-        for (int c = 0; c < C; ++c) tb[c] = lbias[c];
-        PSEG_TRY(upload(&P->d_tail_wa, wa));
-        PSEG_TRY(upload(&P->d_tail_wb, wbk));
-        PSEG_TRY(upload(&P->d_tail_bias, tb));
-        // ---- composed tail: M_ab = Wl_dec . Wd[ab] (from the bf16-rounded kernels, float64 products) ----
-        bool skip_in_buffer = false;     // the skip producer stores its logits contribution (op.skiplog): no skip GEMM here
-        if (lg.src1 >= 0) { const int sp = producer_of(e, lg.src1); skip_in_buffer = sp >= 0 && e.ops[sp].skiplog >= 0; }
-        const int nks0 = cdiv((Cs0 + Cs1) / 8, 4), nkss = (Cskip > 0 && !skip_in_buffer) ? cdiv(round_up(Cskip, 8) / 8, 4) : 0;
-        const int CP = C <= 4 ? 4 : (C <= 8 ? 8 : 16);
-        const bool shapes_ok = (nks0 == 3 && nkss == 1) || (nks0 == 1 && nkss == 0) || (nks0 == 3 && skip_in_buffer);
-        if (skip_in_buffer && (op.relu || !shapes_ok || CP > 8)) return fail(PSEG_EUNSUPPORTED, "skip-logits fusion was planned for a tail that cannot be composed");
-        if (!op.relu && !PSEG_KNOB("PSEG_NO_TAIL_COMPOSE") && shapes_ok) {
-            const int NTL = CP / 4;
-            std::vector<double> M((size_t)4 * C * Cin, 0.0);       // [ab][cls][ci]
-            for (int ab = 0; ab < 4; ++ab)
-                for (int cls = 0; cls < C; ++cls)
-                    for (int ci = 0; ci < Cin; ++ci) {
-                        double acc = 0.0;
-                        for (int co = 0; co < Cd; ++co)
-                            acc += (double)rb(lw[(size_t)co * C + cls]) * (double)rb(w[((size_t)ab * Cin + ci) * Cout + co]);
-                        M[((size_t)ab * C + cls) * Cin + ci] = acc;
-                    }
-            std::vector<uint16_t> a1((size_t)NTL * nks0 * 64 * 8, 0), a2((size_t)4 * std::max(nkss, 1) * 64 * 8, 0);
-            for (int t = 0; t < NTL; ++t)
-                for (int sidx = 0; sidx < nks0; ++sidx)
-                    for (int l = 0; l < 64; ++l) {
-                        const int row = 16 * t + (l & 15), ab = row / CP, cls = row % CP;
-                        if (cls >= C) continue;
-                        const int chunk = 4 * sidx + (l >> 4);
-                        for (int j = 0; j < 8; ++j) {
-                            const int ci = true_ci(chunk * 8 + j);
-                            if (chunk * 8 + j < Cs0 + Cs1 && ci >= 0)
-                                a1[(((size_t)t * nks0 + sidx) * 64 + l) * 8 + j] = f2bf((float)M[((size_t)ab * C + cls) * Cin + ci]);
-                        }
-                    }
-            for (int ab = 0; ab < 4 && nkss; ++ab)
-                for (int sidx = 0; sidx < nkss; ++sidx)
-                    for (int l = 0; l < 64; ++l) {
-                        const int row = 16 * (ab * CP / 16) + (l & 15);
-                        if (row / CP != ab) continue;
-                        const int cls = row % CP;
-                        if (cls >= C) continue;
-                        for (int j = 0; j < 8; ++j) {
-                            const int ch = (4 * sidx + (l >> 4)) * 8 + j;
-                            if (ch < Cskip) a2[(((size_t)ab * nkss + sidx) * 64 + l) * 8 + j] = f2bf(lw[(size_t)(Cd + ch) * C + cls]);
-                        }
-                    }
-            std::vector<float> beta((size_t)NTL * 16, 0.0f);
-            for (int row = 0; row < NTL * 16; ++row) {
-                const int cls = row % CP;
-                if (cls >= C) continue;
-                double acc = (double)lbias[cls];
-                for (int co = 0; co < Cd; ++co) acc += (double)rb(lw[(size_t)co * C + cls]) * (double)bias[co];
-                beta[row] = (float)acc;
-            }
-            PSEG_TRY(upload(&P->d_tc_wA1, a1));
-            PSEG_TRY(upload(&P->d_tc_wA2, a2));
-            PSEG_TRY(upload(&P->d_tc_beta, beta));
-            P->tc_CP = CP; P->tc_nks0 = nks0; P->tc_nkss = nkss;
-            const int dqi = producer_of(e, op.src0);
-            if (dqi >= 0 && e.ops[dqi].into_tail >= 0 && ((skip_in_buffer && s1) || (lg.src1 < 0 && !s1))) {
-                // the same composed kernel M in the operand order of tail_fused2_kernel: the inner deconv's channels arrive as
-                // two accumulator tiles (lane group g, element j <-> channel j < 4 ? 4g + j : 16 + 4g + (j - 4)), the concat
-                // source as storage chunks 4s + g
-                std::vector<uint16_t> wd((size_t)NTL * 64 * 8, 0), wc((size_t)NTL * 2 * 64 * 8, 0);
-                for (int t = 0; t < NTL; ++t)
-                    for (int l = 0; l < 64; ++l) {
-                        const int row = 16 * t + (l & 15), ab = row / CP, cls = row % CP, gg = l >> 4;
-                        if (cls >= C) continue;
-                        for (int j = 0; j < 8; ++j) {
-                            const int ch = j < 4 ? 4 * gg + j : 16 + 4 * gg + (j - 4);
-                            if (ch < C0) wd[((size_t)t * 64 + l) * 8 + j] = f2bf((float)M[((size_t)ab * C + cls) * Cin + ch]);
-                            for (int sidx = 0; sidx < 2; ++sidx) {
-                                const int cc = (4 * sidx + gg) * 8 + j;
-                                if (cc < C1) wc[(((size_t)t * 2 + sidx) * 64 + l) * 8 + j] = f2bf((float)M[((size_t)ab * C + cls) * Cin + C0 + cc]);
-                            }
-                        }
-                    }
-                PSEG_TRY(upload(&P->d_t2_wD, wd));
-                PSEG_TRY(upload(&P->d_t2_wC, wc));
-                P->tail2 = true;
-            }
+    });
+    PSEG_TRY(upload(&P->sp_lay[0].d_tab, sp_table(rowp, TBLK)));
+    PSEG_TRY(upload(&P->d_sp_wpk, spk));
+    // the narrow tile (8 x 24, instances for the 80-channel layers): same chunk ORDER (same products in the same order: same
+    // bits), offsets for its own row pitch, a ring as deep as its smaller tile allows
+    if (NT == 5 && sg == 4 && op.pool_dst < 0 && !PSEG_KNOB("PSEG_NO_SP24")) {
+        const int TWN = 24, rowpn = sp_row_pitch(sg, TWN), TBLKn = round_up((8 + KS - 1) * rowpn, 16), tiles_n = nslot * TBLKn;
+        const int patchn = dq ? patchb : 4 * 2 * TWN * (NT * 32 + 8);
+        const int rkn = std::min((LDS_MAX - tiles_n - round_up(tabb, 1024) - 64 - patchn) / (NT * 1024), 16) & ~1;
+        if (rkn >= rk_min) {
+            lay_out(P->sp_lay[1], rowpn, TBLKn, nslot, rkn, patchn, round_up(tabb, 1024), 64);
+            PSEG_TRY(upload(&P->sp_lay[1].d_tab, sp_table(rowpn, TBLKn)));
         }
     }
+    // conv_sp2_kernel: two compute teams on a pool of four block slots (NT 3 / 4 layers; the fused transposed conv stays above).
+    // PSEG_SP2 (plan switch: tests, A/B): 0 off, 1 every eligible launch, 24 / 32 likewise with that tile width
+    const char* const sp2_sw = PSEG_KNOB("PSEG_SP2");
+    P->sp2_all = sp2_sw && atoi(sp2_sw) != 0;
+    P->sp2_tw = sp2_sw ? atoi(sp2_sw) : 0;
+    if (!dq && NT <= 4 && !(sp2_sw && atoi(sp2_sw) == 0)) {
+        for (int v = 0; v < 2; ++v) {
+            const int twv = v == 0 ? 32 : 24, rowpv = sp_row_pitch(sg, twv), TBLKv = round_up((8 + KS - 1) * rowpv, 16);
+            const int patchv = 8 * 8 * (NT * 32 + 8), tabv = round_up((K + 2) * 128, 1024);     // table: [k-step][lane group][column & 7]
+            const int rkv = std::min((LDS_MAX - SP2_NSLOT * TBLKv - patchv - tabv - 128) / (NT * 1024), 16) & ~1;
+            if (rkv < 10) continue;
+            lay_out(P->sp2_lay[v], rowpv, TBLKv, SP2_NSLOT, rkv, patchv, tabv, 128);
+            std::vector<int> tabq((size_t)(K + 2) * 32, 0);       // (two rows beyond K: the loop looks its offsets up two steps ahead, unclamped)
+            walk([&](int st, int gi, int, Chunk ch) {
+                for (int p7 = 0; p7 < 8; ++p7) {
+                    // four-chunk blocks are stored swizzled: chunk c of halo column x in slot c ^ 2 ((x >> 2) & 1); x = p + kx (+ 16)
+                    const int slot = sg == 4 ? ch.cc ^ ((((p7 + ch.tap % KS) >> 2) & 1) << 1) : ch.cc;
+                    tabq[((size_t)st * 4 + gi) * 8 + p7] = (ch.tap / KS) * rowpv + (ch.tap % KS) * sg * 16 + slot * 16;   // inside the block's slot
+                }
+            });
+            for (int r = K; r < K + 2; ++r) std::copy(tabq.begin() + (size_t)(K - 1) * 32, tabq.begin() + (size_t)K * 32, tabq.begin() + (size_t)r * 32);
+            PSEG_TRY(upload(&P->sp2_lay[v].d_tab, tabq));
+        }
+    }
+    if (!e.d_sp_err) {   // the engine's give-up record of conv_sp_kernel (engine_status)
+        PSEG_HIP(hipMalloc((void**)&e.d_sp_err, 32));
+        PSEG_HIP(hipMemset(e.d_sp_err, 0, 32));
+        PSEG_HIP(hipHostMalloc((void**)&e.h_sp_err, 32, hipHostMallocDefault));
+    }
+    if (PSEG_KNOB("PSEG_LOG_SP"))
+        fprintf(stderr, "[pseg] conv_sp plan %s: NT %d sigma %d fl %d nblk %d (nc %d / %d) K %d S %d blk_steps %d row_pitch %d TBLK %d RK %d lds %d\n", op.layer.c_str(),
+                NT, sg, P->sp_fl, P->nblk, P->nc_full, P->nc_last, K, S, ksf, rowp, TBLK, RK, P->sp_lay[0].lds);
+    return PSEG_OK;
+}
+
+// A fragments [ab][cout tile of nt][k-step of nks][lane = (cout & 15, g)][8] of a transposed conv that runs inside another kernel:
+// element j <-> true input channel chan(s, g, j), or none (-1)
+template <class Chan>
+static std::vector<uint16_t> deconv_frags(const PackCtx& c, int nt, int nks, Chan chan) {
+    std::vector<uint16_t> wq((size_t)4 * nt * nks * 512, 0);
+    for (int ab = 0; ab < 4; ++ab)
+        for (int t = 0; t < nt; ++t)
+            for (int s = 0; s < nks; ++s)
+                logits_frag(&wq[(((size_t)ab * nt + t) * nks + s) * 512], [&](int g, int j) { return chan(s, g, j); }, [&](int r, int ci) {
+                    return 16 * t + r < c.Cout && ci >= 0 ? c.w[((size_t)ab * c.Cin + ci) * c.Cout + 16 * t + r] : 0.0f;
+                });
+    return wq;
+}
+
+// into_tail: this transposed conv runs inside the composed tail: A fragments [ab][cout tile 2][k-step 4][lane = (cout & 15, g)][8],
+// element j <-> storage channel (4s + g) * 8 + j of the concatenated quarter-resolution sources
+static int pack_into_tail(const PackCtx& c) {
+    // one source: chunk 4s + g; two sources (each <= 8 chunks): k-steps 0-1 take source 0, k-steps 2-3 source 1, so that
+    // every fragment load of the tail kernel reads ONE tensor
+    PSEG_TRY(upload(&c.P->d_q_w, deconv_frags(c, 2, 4, [&](int s, int g, int j) {
+        if (!c.s1) return c.true_ci((4 * s + g) * 8 + j);
+        const int c2 = 4 * (s & 1) + g;
+        return c2 < (s < 2 ? c.Cs0 : c.Cs1) / 8 ? c.true_ci((s < 2 ? c2 : c.Cs0 / 8 + c2) * 8 + j) : -1;
+    })));
+    return upload(&c.P->d_q_bias, padded(c.bias, c.Cout, 32));
+}
+
+// dq_fuse: this transposed conv runs in the epilogue of the conv that produces its input: the B operand of k-step s is built
+// from that conv's accumulator tiles 2s and 2s + 1 -- lane (pixel, g) holds channels 16 (2s) + 4g .. + 3 in elements
+// 0-3 and 16 (2s + 1) + 4g .. + 3 in elements 4-7 -- so A fragment (ab, cout tile t, s): lane (cout 16t + l % 16,
+// g = l / 16), element j <-> input channel 16 (2s + j / 4) + 4g + j % 4
+static int pack_dq(const PackCtx& c) {
+    const Op& op = c.op;
+    MfmaPlan* const P = c.P;
+    bool fused_behind_conv = false;
+    for (auto& o : c.e.ops) fused_behind_conv |= o.dq_fuse == (int)(&op - c.e.ops.data());
+    if (!fused_behind_conv) return PSEG_OK;
+    const std::vector<uint16_t> wq = deconv_frags(c, 4, 3, [&](int s, int g, int j) { const int ci = acc_tiles(32 * s)(g, j); return ci < c.Cin ? ci : -1; });
+    PSEG_TRY(upload(&P->d_dq_w, wq));
+    PSEG_TRY(upload(&P->d_dq_bias, padded(c.bias, c.Cout, 64)));
+    // conv_sp_kernel takes these 48 fragments from its weight ring: they follow the conv's k-steps in the producer's stream
+    for (auto& o : c.e.ops) {
+        auto* PC = (MfmaPlan*)o.plan;
+        if (o.dq_fuse != (int)(&op - c.e.ops.data()) || !PC || !PC->sp) continue;
+        if (!(PC->sp_fl & SP_DQ) || (size_t)(PC->sp_S - PC->sp_K) * PC->sp_NT * 512 < wq.size()) return fail(PSEG_EINVAL, "conv_sp_kernel: no room for the transposed conv's fragments");
+        PSEG_HIP(hipMemcpy(PC->d_sp_wpk + (size_t)PC->sp_K * PC->sp_NT * 512, wq.data(), wq.size() * 2, hipMemcpyHostToDevice));
+    }
+    return PSEG_OK;
+}
+
+// skip-logits fusion: the logits kernel rows of this layer's channels (they follow the deconv channels in the
+// concat, Keras (1,1,Cdec+Cout,C): w[(Cdec + co)*C + c]) as ONE A fragment: lane l = (class = l & 15, g = l >> 4),
+// element j <-> cout co = j < 4 ? 4g + j : 16 + 4g + (j - 4)
+static int pack_skiplog(const PackCtx& c) {
+    const Op& lg = c.e.ops[c.op.skiplog];
+    const std::vector<float>& lw = c.e.params[lg.kparam].host;
+    const int C = lg.Cout, Cdec = lg.Cin - c.Cout, Cout = c.Cout;
+    std::vector<uint16_t> wq(64 * 8, 0);
+    logits_frag(wq.data(), acc_tiles(0), [&](int cls, int co) { return cls < C && co < Cout ? lw[(size_t)(Cdec + co) * C + cls] : 0.0f; });
+    PSEG_TRY(upload(&c.P->d_tail_wa, wq));
+    c.P->skip_CP = C <= 4 ? 4 : 8;
+    return PSEG_OK;
+}
+
+// conv + logits fusion: logits kernel (Keras (1,1,64,C): w[co*C + c]) in the fragment order of the two
+// epilogue MFMAs: lane l = (class = l & 15, g = l >> 4), MFMA q, element j <-> cout
+// co = j < 4 ? 16(2q) + 4g + j : 16(2q+1) + 4g + (j - 4)
+static int pack_conv_logits(const PackCtx& c) {
+    MfmaPlan* const P = c.P;
+    if (P->NT != 4 || P->nblocks_n != 1) return fail(PSEG_EUNSUPPORTED, "conv + logits fusion needs a 64-cout layer");
+    const Op& lg = c.e.ops[c.op.tail_logits];
+    const std::vector<float>& lw = c.e.params[lg.kparam].host;
+    const int C = lg.Cout, Cout = c.Cout;
+    std::vector<uint16_t> wq[2] = {std::vector<uint16_t>(64 * 8, 0), std::vector<uint16_t>(64 * 8, 0)};
+    for (int q = 0; q < 2; ++q)
+        logits_frag(wq[q].data(), acc_tiles(32 * q), [&](int cls, int co) { return cls < C && co < Cout ? lw[(size_t)co * C + cls] : 0.0f; });
+    PSEG_TRY(upload(&P->d_tail_wa, wq[0]));
+    PSEG_TRY(upload(&P->d_tail_wb, wq[1]));
+    return upload(&P->d_tail_bias, padded(c.e.params[lg.bparam].host, C, 16));
+}
+
+// The composed tail: deconv5 o logits as one GEMM, M_ab = Wl_dec . Wd[ab] (from the bf16-rounded kernels, float64 products), for
+// tail_composed_kernel (a1: the deconv's sources, a2: the skip, beta: the composed bias) and, where the inner deconv runs inside
+// the tail too (into_tail), in the operand order of tail_fused2_kernel.  skip_in_buffer: the skip producer stores its logits
+// contribution (op.skiplog), no skip GEMM here.
+static int pack_composed_tail(const PackCtx& c, const Op& lg, bool skip_in_buffer, int CP, int nks0, int nkss) {
+    Engine& e = c.e;
+    MfmaPlan* const P = c.P;
+    const std::vector<float>&w = c.w, &lw = e.params[lg.kparam].host, &lbias = e.params[lg.bparam].host;
+    const int C0 = c.C0, C1 = c.C1, Cin = c.Cin, Cout = c.Cout;
+    const int C = lg.Cout, Cd = Cout, Cskip = lg.src1 >= 0 ? e.tensors[lg.src1].C : 0, NTL = CP / 4;
+    std::vector<double> M((size_t)4 * C * Cin, 0.0);       // [ab][cls][ci]
+    for (int ab = 0; ab < 4; ++ab)
+        for (int cls = 0; cls < C; ++cls)
+            for (int ci = 0; ci < Cin; ++ci) {
+                double acc = 0.0;
+                for (int co = 0; co < Cd; ++co)
+                    acc += (double)rb(lw[(size_t)co * C + cls]) * (double)rb(w[((size_t)ab * Cin + ci) * Cout + co]);
+                M[((size_t)ab * C + cls) * Cin + ci] = acc;
+            }
+    std::vector<uint16_t> a1((size_t)NTL * nks0 * 64 * 8, 0), a2((size_t)4 * std::max(nkss, 1) * 64 * 8, 0);
+    // M at fragment row `row` = (ab, class) of the tail's output rows and input channel ci; 0 past the classes and for no channel
+    auto m = [&](int row, int ci) { return row % CP < C && ci >= 0 ? (float)M[((size_t)(row / CP) * C + row % CP) * Cin + ci] : 0.0f; };
+    for (int t = 0; t < NTL; ++t)
+        for (int sidx = 0; sidx < nks0; ++sidx)
+            logits_frag(&a1[((size_t)t * nks0 + sidx) * 512], chunk_chans(sidx), [&](int r, int cs) { return m(16 * t + r, c.true_ci(cs)); });
+    for (int ab = 0; ab < 4 && nkss; ++ab)      // sub-pixel ab's rows of the 16-row tile they lie in
+        for (int sidx = 0; sidx < nkss; ++sidx)
+            logits_frag(&a2[((size_t)ab * nkss + sidx) * 512], chunk_chans(sidx), [&](int r, int ch) {
+                const int row = 16 * (ab * CP / 16) + r;
+                return row / CP == ab && row % CP < C && ch < Cskip ? lw[(size_t)(Cd + ch) * C + row % CP] : 0.0f;
+            });
+    std::vector<float> beta((size_t)NTL * 16, 0.0f);
+    for (int row = 0; row < NTL * 16; ++row) {
+        const int cls = row % CP;
+        if (cls >= C) continue;
+        double acc = (double)lbias[cls];
+        for (int co = 0; co < Cd; ++co) acc += (double)rb(lw[(size_t)co * C + cls]) * (double)c.bias[co];
+        beta[row] = (float)acc;
+    }
+    PSEG_TRY(upload(&P->d_tc_wA1, a1));
+    PSEG_TRY(upload(&P->d_tc_wA2, a2));
+    PSEG_TRY(upload(&P->d_tc_beta, beta));
+    P->tc_CP = CP; P->tc_nks0 = nks0; P->tc_nkss = nkss;
+    const int dqi = producer_of(e, c.op.src0);
+    if (!(dqi >= 0 && e.ops[dqi].into_tail >= 0 && ((skip_in_buffer && c.s1) || (lg.src1 < 0 && !c.s1)))) return PSEG_OK;
+    // the same composed kernel M in the operand order of tail_fused2_kernel: the inner deconv's channels arrive as
+    // two accumulator tiles (lane group g, element j <-> channel j < 4 ? 4g + j : 16 + 4g + (j - 4)), the concat
+    // source as storage chunks 4s + g
+    std::vector<uint16_t> wd((size_t)NTL * 64 * 8, 0), wc((size_t)NTL * 2 * 64 * 8, 0);
+    for (int t = 0; t < NTL; ++t) {
+        logits_frag(&wd[(size_t)t * 512], acc_tiles(0), [&](int r, int ch) { return m(16 * t + r, ch < C0 ? ch : -1); });
+        for (int sidx = 0; sidx < 2; ++sidx)
+            logits_frag(&wc[((size_t)t * 2 + sidx) * 512], chunk_chans(sidx), [&](int r, int cc) { return m(16 * t + r, cc < C1 ? C0 + cc : -1); });
+    }
+    PSEG_TRY(upload(&P->d_t2_wD, wd));
+    PSEG_TRY(upload(&P->d_t2_wC, wc));
+    P->tail2 = true;
+    return PSEG_OK;
+}
+
+// The fused tail (deconv5 with the logits layer behind it): logits weights (Keras (1,1,Cin,C): w[ci*C + c]) in the fragment order
+// of the fused tail: lane l = (class = l & 15, g = l >> 4), element j <-> deconv channel co = j < 4 ? 4g + j : 16 + 4g + (j - 4);
+// skip channel 8g + j.  Then the composed form, where the tail's shape has an instance.
+static int pack_tail(const PackCtx& c) {
+    Engine& e = c.e;
+    const Op& op = c.op;
+    MfmaPlan* const P = c.P;
+    const Op& lg = e.ops[op.tail_logits];
+    const std::vector<float>& lw = e.params[lg.kparam].host;
+    const int C = lg.Cout, Cd = c.Cout, Cskip = lg.src1 >= 0 ? e.tensors[lg.src1].C : 0;
+    std::vector<uint16_t> wa(64 * 8, 0), wbk(64 * 8, 0);
+    logits_frag(wa.data(), acc_tiles(0), [&](int cls, int co) { return cls < C && co < Cd ? lw[(size_t)co * C + cls] : 0.0f; });
+    logits_frag(wbk.data(), chunk_chans(0), [&](int cls, int ch) { return cls < C && ch < Cskip ? lw[(size_t)(Cd + ch) * C + cls] : 0.0f; });
+    PSEG_TRY(upload(&P->d_tail_wa, wa));
+    PSEG_TRY(upload(&P->d_tail_wb, wbk));
+    PSEG_TRY(upload(&P->d_tail_bias, padded(e.params[lg.bparam].host, C, 16)));
+    bool skip_in_buffer = false;     // the skip producer stores its logits contribution (op.skiplog): no skip GEMM here
+    if (lg.src1 >= 0) { const int sp = producer_of(e, lg.src1); skip_in_buffer = sp >= 0 && e.ops[sp].skiplog >= 0; }
+    const int nks0 = cdiv((c.Cs0 + c.Cs1) / 8, 4), nkss = (Cskip > 0 && !skip_in_buffer) ? cdiv(round_up(Cskip, 8) / 8, 4) : 0;
+    const int CP = C <= 4 ? 4 : (C <= 8 ? 8 : 16);
+    const bool shapes_ok = (nks0 == 3 && nkss == 1) || (nks0 == 1 && nkss == 0) || (nks0 == 3 && skip_in_buffer);
+    if (skip_in_buffer && (op.relu || !shapes_ok || CP > 8)) return fail(PSEG_EUNSUPPORTED, "skip-logits fusion was planned for a tail that cannot be composed");
+    if (!op.relu && !PSEG_KNOB("PSEG_NO_TAIL_COMPOSE") && shapes_ok) return pack_composed_tail(c, lg, skip_in_buffer, CP, nks0, nkss);
+    return PSEG_OK;
+}
+
+// The plan of one layer.  Every stage reads the context (and the generic path's tile / ring record) and writes MfmaPlan fields; the
+// order is the order of the uploads, the fail() checks and the [pseg] log lines, and a flag is decided before the stages that read it.
+int mfma_pack_op(Engine& e, Op& op, const std::vector<float>& w, const std::vector<float>& bias) {
+    mfma_free_op(op);
+    auto* P = new MfmaPlan();
+    op.plan = P;
+    P->w_keep = w;
+    P->b_keep = bias;
+    const Tensor& s0 = e.tensors[op.src0];
+    const Tensor* s1 = op.src1 >= 0 ? &e.tensors[op.src1] : nullptr;
+    const bool deconv = op.type == OP_DECONV2;
+    P->spec = !PSEG_KNOB("PSEG_GENERIC");
+    const PackCtx c{e, op, P, w, bias, s1, s0.C, s0.Cs, s1 ? s1->C : 0, s1 ? s1->Cs : 0, s0.C + (s1 ? s1->C : 0), op.Cout,
+                    deconv, deconv && op.tail_logits >= 0, deconv ? 1 : op.k,
+                    P->spec, !PSEG_KNOB("PSEG_NO_PERSIST"), !PSEG_KNOB("PSEG_NO_WS")};
+    int ks1, co1;
+    if (is_conv1_special(e, op, &ks1, &co1)) return pack_conv1(c, ks1);
+    if (op.type == OP_LOGITS) return pack_logits(c);
+    if (op.type == OP_POOL) return PSEG_OK;
+    if (takes_upsplit(c)) {
+        P->kind = PLAN_UPSPLIT;
+        return upsplit_create(&P->upsplit, w, bias, c.Cin, c.Cs0, c.Cout, e.tensors[op.dst].Cs);
+    }
+    TileRing R;
+    PSEG_TRY(plan_tile(c, R));
+    plan_rowreuse(c, R);
+    PSEG_TRY(plan_ring(c, R));
+    plan_persistent(c, R);
+    PSEG_TRY(upload(&P->d_wpk, pack_ring_stream(c, R, R.GK, P->G)));
+    PSEG_TRY(pack_pair8(c, R));
+    PSEG_TRY(plan_triple(c, R));
+    PSEG_TRY(pack_bias(c));
+    PSEG_TRY(plan_streamed(c));
+    if (deconv && op.into_tail >= 0) PSEG_TRY(pack_into_tail(c));
+    if (deconv) PSEG_TRY(pack_dq(c));
+    if (!deconv && op.skiplog >= 0) PSEG_TRY(pack_skiplog(c));
+    if (!deconv && op.tail_logits >= 0) PSEG_TRY(pack_conv_logits(c));
+    if (c.tail) PSEG_TRY(pack_tail(c));
     return PSEG_OK;
 }
 
