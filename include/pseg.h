@@ -355,6 +355,50 @@ int pseg_train_apply(pseg_engine* e, float lr, float grad_scale);
 /* Gradient of one parameter in Keras layout (tests). */
 int pseg_train_get_gradient(pseg_engine* e, const char* name, float* out, int64_t count);
 
+/* ONE layer's weight (+ bias) gradient on the caller's device tensors (tests): the launch the train step makes for such a
+ * layer -- same argument helpers, same kernel choice, same ordered reductions -- on the engine's stream, under its plan
+ * switches, with the train state's partial-sum scratch.  Needs pseg_train_init; host-synchronous.  NHWC float32 tensors.
+ *   mode 0: conv / logits.  dW[ky][kx][ci0 + ci][co] = sum over (y, x) of Xz[y*stride + ky - pt][x*stride + kx - pl][ci] * dY'[y][x][co],
+ *           Xz zero outside the Hx x Wx map, read through a nearest x2 upsample when `xup` (X then holds (Hx/2) x (Wx/2)
+ *           pixels), rectified when `in_relu`; dY' = dY where maskY > 0 (maskY NULL: dY); pt / pl: TF SAME for (Hy, Wy).
+ *           Hy = ceil(Hx / stride), Wy likewise; stride 1 or 2.  `logits`: KW = 1, no padding, the Hy x Wy page in the
+ *           top-left corner of an Hx x Wx canvas (Hy <= Hx, Wy <= Wx), no mask.
+ *   mode 1: Conv2DTranspose k2 s2.  dW[a][b][ci][co] = sum over (i, j) of X[i][j][ci] * dY'[2i + a][2j + b][co]; Hy = 2 Hx, Wy = 2 Wx.
+ *   dB[co] = sum of dY' (NULL: none; a transposed conv takes one only where a two-source instance runs).
+ * X holds XC0 channels per pixel, rows `xpitch` pixels apart; X1 (NULL: none) XC1 channels of the same extent: the second
+ * concat source, taken in the same launch (logits and transposed convs that have a two-source instance, ci0 = 0,
+ * Cin = XC0 + XC1).  Other layers run one source per call: channels ci0 .. ci0 + XC0 of a dW with Cin input channels.
+ * dY / maskY rows are Wy pixels of Cout channels.  slots > 0 replaces "compute units x workgroups per unit" in the strip
+ * planners of the flattened-row, channel-block and two-source kernels (0: ask the device); strip_rows > 0 replaces the train
+ * step's rows-per-strip proposal for the kernels that take it from the caller (0: the train step's formula).
+ * ran (may be NULL) reports the launch. */
+enum { PSEG_WGRAD_PAIR = 0, PSEG_WGRAD_FLAT = 1, PSEG_WGRAD_BLK = 2, PSEG_WGRAD_C1 = 3, PSEG_WGRAD_KX5 = 4, PSEG_WGRAD_TAP = 5,
+       PSEG_WGRAD_WIDE = 6 };
+typedef struct pseg_wgrad_layer {
+    const float* X;
+    const float* X1;
+    const float* dY;
+    const float* maskY;
+    float* dW;
+    float* dB;
+    int32_t mode, KW, stride, xup, in_relu, logits;
+    int32_t XC0, XC1, ci0, Cin, Cout;
+    int32_t Hx, Wx, xpitch, Hy, Wy;
+    int32_t slots, strip_rows;
+} pseg_wgrad_layer;
+typedef struct pseg_wgrad_plan {
+    int32_t variant;         /* PSEG_WGRAD_* */
+    int32_t instance;        /* PAIR / FLAT / BLK: row of the kernel's instance table; else -1 */
+    int32_t ti, tj;          /* C1 / KX5 / TAP / WIDE: the template instance (tiles of 16 rows x 16 columns); else 0 */
+    int32_t lds_staged;      /* KX5: 1 = the LDS-staged form, 0 = the direct one */
+    int32_t strip_rows;      /* rows of the walk per strip */
+    int32_t cgroups;         /* column groups a row strip is cut into (1 where the kernel has none) */
+    int32_t nstrips;         /* workgroup strips = rows of the partial-sum scratch */
+    int32_t piece_width;     /* PAIR / FLAT / BLK: pixels per column piece; else 0 */
+    int32_t deterministic;   /* 1 = partial sums + ordered reduction, 0 = float atomics into dW / dB (which the caller zeroed) */
+} pseg_wgrad_plan;
+int pseg_train_wgrad_layer(pseg_engine* e, const pseg_wgrad_layer* layer, pseg_wgrad_plan* ran);
+
 /* model.evaluate step (lib/network.py:244-246): forward + loss/metrics only. */
 int pseg_eval_step(pseg_engine* e, const uint8_t* img, const uint8_t* mask, int H, int W,
                    float metrics[4]);

@@ -831,7 +831,10 @@ __global__ __launch_bounds__(256) void wgrad_c1_kernel(WgradArgs a) {
 
 // Chooses the kernel instance for a layer, launches it and (deterministic form) sums the strips' partial results.
 // grid = (strips, taps) as the scalar kernel takes it; `scratch` / `scratch_cap` = the train state's partial-sum buffer.
-static int launch_wgrad(const WgradArgs& a_in, dim3 grid, hipStream_t st, float** scratch, size_t* scratch_cap) {
+// `slots` > 0 (pseg_train_wgrad_layer only) stands in for the device's workgroup slots in the strip planners; `ran`, when given,
+// receives what was launched.
+static int launch_wgrad(const WgradArgs& a_in, dim3 grid, hipStream_t st, float** scratch, size_t* scratch_cap, int slots = 0,
+                        pseg_wgrad_plan* ran = nullptr) {
     WgradArgs a = a_in;
     const int itH = a.mode == 0 ? a.Hy : a.Hx;
     const int taps = (int)grid.y;
@@ -841,11 +844,12 @@ static int launch_wgrad(const WgradArgs& a_in, dim3 grid, hipStream_t st, float*
     WgradFlatPlan flat;
     const bool lds = a.mode == 0 && a.stride == 1 && !a.xup;
     const int ti = (a.XC + 15) / 16, tj = (a.Cout + 15) / 16;
+    int ran_ti = 0, ran_tj = 0;                                // template instance of the pseg_train.hip kernels (for `ran`)
     if (a.XC0 > 0) {                                          // both concat sources + the bias gradient in one pass (pseg_wgrad_flat.hip)
-        if (!wgrad_pair_plan(a, taps, &flat)) return fail(PSEG_EINVAL, "no two-source weight-gradient instance for this layer");
+        if (!wgrad_pair_plan(a, taps, &flat, slots)) return fail(PSEG_EINVAL, "no two-source weight-gradient instance for this layer");
         variant = V_PAIR;
         a.strip_rows = flat.strip_rows;
-    } else if (!scalar && wgrad_flat_plan(a, taps, &flat)) {
+    } else if (!scalar && wgrad_flat_plan(a, taps, &flat, slots)) {
         variant = V_FLAT;                                      // the k5 layers of fcn / fcn_skip (pseg_wgrad_flat.hip)
         a.strip_rows = flat.strip_rows;
     } else if (a.XC == 1 && a.mode == 0 && a.stride == 1 && !a.xup && !a.in_relu && a.KW * a.KW <= 32 && a.Cout <= 64 && !scalar) {
@@ -896,6 +900,8 @@ static int launch_wgrad(const WgradArgs& a_in, dim3 grid, hipStream_t st, float*
                 if (tj <= 2) wgrad_c1_kernel<2, 2><<<nstrips, 256, 0, st>>>(a);
                 else wgrad_c1_kernel<2, 4><<<nstrips, 256, 0, st>>>(a);
             }
+            ran_ti = a.KW * a.KW <= 16 ? 1 : 2;
+            ran_tj = tj <= 2 ? 2 : 4;
             break;
         }
         case V_KX5: {
@@ -903,6 +909,7 @@ static int launch_wgrad(const WgradArgs& a_in, dim3 grid, hipStream_t st, float*
 #define PSEG_WG5(TI_, TJ_) if (ti <= TI_ && tj <= TJ_) {                                                   \
                 if (lds) wgrad_lds_kernel<TI_, TJ_, 5><<<g5, 256, 0, st>>>(a);                                       \
                 else wgrad_mfma_kernel<TI_, TJ_, 5><<<g5, 256, 0, st>>>(a);                                          \
+                ran_ti = TI_; ran_tj = TJ_;                                                                          \
                 break; }
             PSEG_WG5(1, 2) PSEG_WG5(2, 2) PSEG_WG5(2, 3)
 #undef PSEG_WG5
@@ -914,6 +921,7 @@ static int launch_wgrad(const WgradArgs& a_in, dim3 grid, hipStream_t st, float*
             const dim3 g2(taps, nstrips);
 #define PSEG_WG(TI_, TJ_) if (ti <= TI_ && tj <= TJ_) {                                                    \
             wgrad_mfma_kernel<TI_, TJ_, 1><<<g2, 256, 0, st>>>(a);   /* one tap per workgroup: the direct kernel is faster than the LDS-staged one */ \
+            ran_ti = TI_; ran_tj = TJ_;                                                                    \
             break; }
             PSEG_WG(1, 2) PSEG_WG(2, 2) PSEG_WG(2, 3) PSEG_WG(3, 3) PSEG_WG(3, 5) PSEG_WG(5, 3) PSEG_WG(5, 5)
 #undef PSEG_WG
@@ -923,6 +931,7 @@ static int launch_wgrad(const WgradArgs& a_in, dim3 grid, hipStream_t st, float*
             // wide layers (unet / res_unet): 64 x 64 channel blocks on blockIdx.z
             const dim3 g3(taps, nstrips, cdiv(a.XC, 64) * cdiv(a.Cout, 64));
             wgrad_mfma_kernel<4, 4, 1><<<g3, 256, 0, st>>>(a);
+            ran_ti = ran_tj = 4;
             break;
         }
         case V_SCALAR: {
@@ -942,7 +951,74 @@ static int launch_wgrad(const WgradArgs& a_in, dim3 grid, hipStream_t st, float*
         if (a.partB) column_sum_kernel<float><<<a.Cout, 256, 0, st>>>(a.partB, 4 * nstrips, a.Cout, a.dB);
         PSEG_HIP(hipGetLastError());
     }
+    if (ran) {
+        const bool planned = variant == V_PAIR || variant == V_FLAT;
+        const bool blk = variant == V_FLAT && flat.instance >= 1000;
+        static const int code[] = {PSEG_WGRAD_PAIR, PSEG_WGRAD_FLAT, PSEG_WGRAD_C1, PSEG_WGRAD_KX5, PSEG_WGRAD_TAP, PSEG_WGRAD_WIDE, -1};
+        ran->variant = blk ? PSEG_WGRAD_BLK : code[variant];
+        ran->instance = planned ? flat.instance % 1000 : -1;
+        ran->ti = ran_ti;
+        ran->tj = ran_tj;
+        ran->lds_staged = variant == V_KX5 && lds;
+        ran->strip_rows = a.strip_rows;
+        ran->cgroups = planned ? flat.cgroups : 1;
+        ran->nstrips = nstrips;
+        ran->piece_width = planned ? flat.pw : 0;
+        ran->deterministic = det;
+    }
     return PSEG_OK;
+}
+
+// ---- how a layer becomes WgradArgs: shared by the train step and pseg_train_wgrad_layer (which runs ONE of these launches on
+// the caller's tensors, so that what the per-layer tests check is what training runs)
+constexpr int WGRAD_STRIPS_TARGET = 1536;
+// rows per strip the caller proposes to the kernels of this file (the flattened-row and two-source kernels plan their own)
+static int wgrad_caller_strip_rows(int itH, int taps) { return std::max(1, cdiv(itH * taps, WGRAD_STRIPS_TARGET)); }
+// TF SAME: pad_total = max((out-1)*s + k - in, 0), before = total / 2 (as run_exact); the logits layer has none
+static void wgrad_same_pad(bool logits, int Hy, int Wy, int Hx, int Wx, int k, int stride, int* pt, int* pl) {
+    *pt = *pl = 0;
+    if (logits) return;
+    *pt = std::max((Hy - 1) * stride + k - Hx, 0) / 2;
+    *pl = std::max((Wy - 1) * stride + k - Wx, 0) / 2;
+}
+// what every form shares: the output gradient (rows of Wy pixels) under the layer's ReLU mask, the layer's channel counts, outputs
+static void wgrad_common_args(WgradArgs& a, const float* dY, const float* maskY, int Hy, int Wy, int Cout, int Cin, float* dW, float* dB) {
+    a.dY = dY; a.maskY = maskY; a.Hy = Hy; a.Wy = Wy; a.ypitch = Wy; a.Cout = Cout; a.Cin = Cin; a.dW = dW; a.dB = dB;
+}
+// the 1x1 logits layer (mode 0) or a k2 s2 transposed conv (mode 1), both concat sources and the bias gradient in one pass
+// (wgrad_pair_kernel); launched with dim3(1, k * k)
+static WgradArgs wgrad_pair_args(int mode, const float* X0, int C0, const float* X1, int C1, int Hx, int Wx, int xpitch, int in_relu,
+                                 const float* dY, const float* maskY, int Hy, int Wy, int Cout, int Cin, int k, int pt, int pl,
+                                 float* dW, float* dB) {
+    WgradArgs a{};
+    a.X = X0; a.XC0 = C0; a.X1 = X1; a.XC = C0 + C1; a.ci0 = 0;
+    a.Hx = Hx; a.Wx = Wx; a.xpitch = xpitch; a.xup = 0; a.stride = 1; a.in_relu = in_relu;
+    wgrad_common_args(a, dY, maskY, Hy, Wy, Cout, Cin, dW, dB);
+    a.KW = k; a.pt = pt; a.pl = pl; a.mode = mode; a.strip_rows = 1;
+    return a;
+}
+// one source of a conv / logits layer (channels ci0 .. ci0 + XC of dW); launched with dim3(cdiv(Hy, strip_rows), k * k)
+static WgradArgs wgrad_conv_args(const float* X, int XC, int ci0, int Hx, int Wx, int xpitch, int xup, int stride, int in_relu,
+                                 const float* dY, const float* maskY, int Hy, int Wy, int Cout, int Cin, int k, int pt, int pl,
+                                 float* dW, float* dB) {
+    WgradArgs a{};
+    a.X = X; a.XC = XC; a.ci0 = ci0; a.Hx = Hx; a.Wx = Wx; a.xpitch = xpitch;
+    a.xup = xup; a.stride = stride; a.in_relu = in_relu;
+    wgrad_common_args(a, dY, maskY, Hy, Wy, Cout, Cin, dW, dB);
+    a.KW = k; a.pt = pt; a.pl = pl; a.mode = 0;
+    a.strip_rows = wgrad_caller_strip_rows(Hy, k * k);
+    return a;
+}
+// one source of a k2 s2 transposed conv on the kernels of this file (no bias gradient: bias_grad_kernel); launched with
+// dim3(cdiv(Hx, strip_rows), 4)
+static WgradArgs wgrad_deconv_args(const float* X, int XC, int ci0, int Hx, int Wx, int xpitch, const float* dY, const float* maskY,
+                                   int Cout, int Cin, float* dW) {
+    WgradArgs a{};
+    a.X = X; a.XC = XC; a.ci0 = ci0; a.Hx = Hx; a.Wx = Wx; a.xpitch = xpitch;
+    wgrad_common_args(a, dY, maskY, 2 * Hx, 2 * Wx, Cout, Cin, dW, nullptr);
+    a.KW = 2; a.mode = 1;
+    a.strip_rows = wgrad_caller_strip_rows(Hx, 4);
+    return a;
 }
 
 // dst[i] += src[i] (masked by maskX[i] > 0 when given): residual addend gradients, pre-activation ReLU dgrad
@@ -1255,7 +1331,6 @@ static int train_compute(Engine& e, int H, int W, bool backward, bool img_f32) {
     auto ensure_wd = [&](size_t floats) -> int {
         return ensure_buf((void**)&t->d_wd, &t->wd_bytes, (floats + COT) * 4);
     };
-    const int strips_target = 1536;
     const bool scalar_wgrad = false;
     // Second stream for the weight gradients.  A layer's weight gradient and its data gradient both only READ the layer's output
     // gradient, and nothing downstream of a weight gradient runs before the optimizer: the weight-gradient kernels (and their
@@ -1305,10 +1380,7 @@ static int train_compute(Engine& e, int H, int W, bool backward, bool img_f32) {
             const int Hx = e.tH(s0) << op.up0, Wx = e.tW(s0) << op.up0;
             const int k = op.k, st_ = op.stride;
             int pt = 0, pl = 0;
-            if (!lg) {   // TF SAME: pad_total = max((out-1)*s + k - in, 0), before = total / 2 (as run_exact)
-                pt = std::max((Hy - 1) * st_ + k - Hx, 0) / 2;
-                pl = std::max((Wy - 1) * st_ + k - Wx, 0) / 2;
-            }
+            wgrad_same_pad(lg, Hy, Wy, Hx, Wx, k, st_, &pt, &pl);
             // residual addend (Add() after the bias): its gradient is the layer's output gradient
             if (op.add >= 0) {
                 const Tensor& ad = e.tensors[op.add];
@@ -1319,11 +1391,8 @@ static int train_compute(Engine& e, int H, int W, bool backward, bool img_f32) {
             // ---- wgrad + bias grad ----
             bool paired = false;
             if (lg && !scalar_wgrad) {   // the 1x1 logits layer: both sources and the bias in one pass over dY
-                WgradArgs a{};
-                a.X = (const float*)s0.d; a.XC0 = C0; a.X1 = s1 ? (const float*)s1->d : nullptr; a.XC = C0 + C1; a.ci0 = 0;
-                a.Hx = Hx; a.Wx = Wx; a.xpitch = Wx; a.xup = 0; a.stride = 1; a.in_relu = op.in_relu;
-                a.dY = dY; a.maskY = maskY; a.Hy = Hy; a.Wy = Wy; a.ypitch = Wy; a.Cout = op.Cout; a.Cin = op.Cin;
-                a.KW = k; a.pt = pt; a.pl = pl; a.mode = 0; a.strip_rows = 1; a.dW = gw; a.dB = gb;
+                const WgradArgs a = wgrad_pair_args(0, (const float*)s0.d, C0, s1 ? (const float*)s1->d : nullptr, C1, Hx, Wx, Wx, op.in_relu,
+                                                    dY, maskY, Hy, Wy, op.Cout, op.Cin, k, pt, pl, gw, gb);
                 WgradFlatPlan pp;
                 if (!op.up0 && !op.up1 && st_ == 1 && wgrad_pair_plan(a, k * k, &pp)) {
                     PSEG_TRY(dy_ready());
@@ -1334,14 +1403,8 @@ static int train_compute(Engine& e, int H, int W, bool backward, bool img_f32) {
             for (int sidx = 0; sidx < (paired ? 0 : (s1 ? 2 : 1)); ++sidx) {
                 const Tensor& sx = sidx == 0 ? s0 : *s1;
                 const int up = sidx == 0 ? op.up0 : op.up1;
-                WgradArgs a{};
-                a.X = (const float*)sx.d; a.XC = sx.C; a.ci0 = sidx == 0 ? 0 : C0; a.Hx = Hx; a.Wx = Wx; a.xpitch = Wx >> up;
-                a.xup = up; a.stride = st_; a.in_relu = op.in_relu;
-                a.dY = dY; a.maskY = maskY;
-                a.Hy = Hy; a.Wy = Wy; a.ypitch = Wy; a.Cout = op.Cout; a.Cin = op.Cin;
-                a.KW = k; a.pt = pt; a.pl = pl; a.mode = 0;
-                a.strip_rows = std::max(1, cdiv(Hy * k * k, strips_target));
-                a.dW = gw; a.dB = sidx == 0 ? gb : nullptr;
+                const WgradArgs a = wgrad_conv_args((const float*)sx.d, sx.C, sidx == 0 ? 0 : C0, Hx, Wx, Wx >> up, up, st_, op.in_relu,
+                                                    dY, maskY, Hy, Wy, op.Cout, op.Cin, k, pt, pl, gw, sidx == 0 ? gb : nullptr);
                 dim3 grid(cdiv(Hy, a.strip_rows), k * k);
                 PSEG_TRY(dy_ready());
                 PSEG_TRY(launch_wgrad(a, grid, ws, &t->d_wpart, &t->wpart_bytes));
@@ -1403,12 +1466,8 @@ static int train_compute(Engine& e, int H, int W, bool backward, bool img_f32) {
             const int Hx = e.tH(s0), Wx = e.tW(s0);
             bool paired = false;
             if (!scalar_wgrad) {   // both sources and the bias gradient in one pass over dY
-                WgradArgs a{};
-                a.X = (const float*)s0.d; a.XC0 = C0; a.X1 = s1 ? (const float*)s1->d : nullptr; a.XC = C0 + C1; a.ci0 = 0;
-                a.Hx = Hx; a.Wx = Wx; a.xpitch = Wx;
-                a.dY = dY; a.maskY = op.relu ? Y : nullptr;
-                a.Hy = 2 * Hx; a.Wy = 2 * Wx; a.ypitch = 2 * Wx; a.Cout = op.Cout; a.Cin = op.Cin;
-                a.KW = 2; a.mode = 1; a.strip_rows = 1; a.dW = gw; a.dB = gb;
+                const WgradArgs a = wgrad_pair_args(1, (const float*)s0.d, C0, s1 ? (const float*)s1->d : nullptr, C1, Hx, Wx, Wx, 0,
+                                                    dY, op.relu ? Y : nullptr, 2 * Hx, 2 * Wx, op.Cout, op.Cin, 2, 0, 0, gw, gb);
                 WgradFlatPlan pp;
                 if (wgrad_pair_plan(a, 4, &pp)) {
                     PSEG_TRY(dy_ready());
@@ -1418,13 +1477,8 @@ static int train_compute(Engine& e, int H, int W, bool backward, bool img_f32) {
             }
             for (int sidx = 0; sidx < (paired ? 0 : (s1 ? 2 : 1)); ++sidx) {
                 const Tensor& sx = sidx == 0 ? s0 : *s1;
-                WgradArgs a{};
-                a.X = (const float*)sx.d; a.XC = sx.C; a.ci0 = sidx == 0 ? 0 : C0; a.Hx = Hx; a.Wx = Wx; a.xpitch = Wx;
-                a.dY = dY; a.maskY = op.relu ? Y : nullptr;
-                a.Hy = 2 * Hx; a.Wy = 2 * Wx; a.ypitch = 2 * Wx; a.Cout = op.Cout; a.Cin = op.Cin;
-                a.KW = 2; a.mode = 1;
-                a.strip_rows = std::max(1, cdiv(Hx * 4, strips_target));
-                a.dW = gw; a.dB = nullptr;
+                const WgradArgs a = wgrad_deconv_args((const float*)sx.d, sx.C, sidx == 0 ? 0 : C0, Hx, Wx, Wx, dY, op.relu ? Y : nullptr,
+                                                      op.Cout, op.Cin, gw);
                 dim3 grid(cdiv(Hx, a.strip_rows), 4);
                 PSEG_TRY(dy_ready());
                 PSEG_TRY(launch_wgrad(a, grid, ws, &t->d_wpart, &t->wpart_bytes));
@@ -1776,6 +1830,61 @@ int pseg_train_apply(pseg_engine* h, float lr, float grad_scale) {
     if (!h) return fail(PSEG_EINVAL, "NULL engine");
     KnobScope knob_scope(h->e);
     return train_apply(h->e, lr, grad_scale);
+}
+
+int pseg_train_wgrad_layer(pseg_engine* h, const pseg_wgrad_layer* L, pseg_wgrad_plan* ran) {
+    if (!h || !L) return fail(PSEG_EINVAL, "NULL argument");
+    Engine& e = h->e;
+    KnobScope knob_scope(e);
+    TrainState* t = TS(e);
+    if (!t) return fail(PSEG_EINVAL, "pseg_train_init has not been called");
+    if (!L->X || !L->dY || !L->dW) return fail(PSEG_EINVAL, "X, dY and dW are required");
+    if ((L->X1 != nullptr) != (L->XC1 > 0) || L->XC0 < 1 || L->XC1 < 0 || L->Cout < 1 || L->ci0 < 0 || L->ci0 + L->XC0 + L->XC1 > L->Cin)
+        return fail(PSEG_EINVAL, "channel counts %d + %d at %d do not fit %d input channels", L->XC0, L->XC1, L->ci0, L->Cin);
+    if (L->Hx < 1 || L->Wx < 1 || L->Hy < 1 || L->Wy < 1 || L->slots < 0 || L->strip_rows < 0) return fail(PSEG_EINVAL, "bad extent");
+    const bool lg = L->logits != 0;
+    const int up = L->xup ? 1 : 0, k = L->KW;
+    if (L->mode == 0) {
+        if (k < 1 || k > 5 || (L->stride != 1 && L->stride != 2)) return fail(PSEG_EINVAL, "kernel %d / stride %d", k, L->stride);
+        if (up && ((L->Hx | L->Wx) & 1)) return fail(PSEG_EINVAL, "an upsampled source has even extents");
+        if (lg ? (k != 1 || L->stride != 1 || up || L->maskY || L->Hy > L->Hx || L->Wy > L->Wx)
+               : (L->Hy != cdiv(L->Hx, L->stride) || L->Wy != cdiv(L->Wx, L->stride)))
+            return fail(PSEG_EINVAL, "output %dx%d does not belong to input %dx%d", L->Hy, L->Wy, L->Hx, L->Wx);
+    } else if (L->mode == 1) {
+        if (k != 2 || L->stride != 1 || up || L->in_relu || lg || L->Hy != 2 * L->Hx || L->Wy != 2 * L->Wx)
+            return fail(PSEG_EINVAL, "a transposed conv is k2 s2: output 2H x 2W");
+    } else {
+        return fail(PSEG_EINVAL, "mode %d", L->mode);
+    }
+    if (L->xpitch < (L->Wx >> up)) return fail(PSEG_EINVAL, "xpitch %d is shorter than a row", L->xpitch);
+    PSEG_HIP(hipSetDevice(e.device));
+    int pt = 0, pl = 0;
+    if (L->mode == 0) wgrad_same_pad(lg, L->Hy, L->Wy, L->Hx, L->Wx, k, L->stride, &pt, &pl);
+    // the train step's order: the one-pass form where the layer has an instance, else one source per launch
+    WgradArgs a{};
+    dim3 grid(1, k * k);
+    bool paired = false;
+    if (L->mode == 1 || lg) {
+        a = wgrad_pair_args(L->mode, L->X, L->XC0, L->X1, L->XC1, L->Hx, L->Wx, L->xpitch, L->in_relu, L->dY, L->maskY, L->Hy, L->Wy,
+                            L->Cout, L->Cin, k, pt, pl, L->dW, L->dB);
+        WgradFlatPlan pp;
+        paired = wgrad_pair_plan(a, k * k, &pp, L->slots);
+    }
+    if (!paired) {
+        if (L->X1) return fail(PSEG_EINVAL, "no two-source weight-gradient instance for this layer: one source per call");
+        if (L->mode == 1) {
+            if (L->dB) return fail(PSEG_EINVAL, "the bias gradient of this transposed conv is not part of its weight-gradient launch");
+            a = wgrad_deconv_args(L->X, L->XC0, L->ci0, L->Hx, L->Wx, L->xpitch, L->dY, L->maskY, L->Cout, L->Cin, L->dW);
+        } else {
+            a = wgrad_conv_args(L->X, L->XC0, L->ci0, L->Hx, L->Wx, L->xpitch, up, L->stride, L->in_relu, L->dY, L->maskY, L->Hy, L->Wy,
+                                L->Cout, L->Cin, k, pt, pl, L->dW, L->dB);
+        }
+        if (L->strip_rows > 0) a.strip_rows = L->strip_rows;
+        grid = dim3(cdiv(L->mode == 1 ? L->Hx : L->Hy, a.strip_rows), k * k);
+    }
+    PSEG_TRY(launch_wgrad(a, grid, e.stream, &t->d_wpart, &t->wpart_bytes, L->slots, ran));
+    PSEG_HIP(hipStreamSynchronize(e.stream));
+    return PSEG_OK;
 }
 
 int pseg_train_get_gradient(pseg_engine* h, const char* name, float* out, int64_t count) {

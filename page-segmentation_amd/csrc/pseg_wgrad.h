@@ -50,11 +50,14 @@ struct WgradFlatPlan {
     int instance = -1;       // index into the instance table
     int nstrips = 0;         // rows of `part` the launch writes (column groups x row strips)
     int strip_rows = 0, cgroups = 0;
+    int pw = 0;              // pixels per column piece of the instance
 };
-bool wgrad_flat_plan(const WgradArgs& a, int taps, WgradFlatPlan* plan);
+// slots > 0 stands in for "CUs x workgroups per CU" of the current device (pseg_train_wgrad_layer: the tests walk the plans
+// of other device sizes); 0 asks the device
+bool wgrad_flat_plan(const WgradArgs& a, int taps, WgradFlatPlan* plan, int slots = 0);
 // ... and of the layers whose time is the tensors they read: the k2 s2 transposed convs and the 1x1 logits layer, both concat
 // sources and the bias gradient in ONE pass over dY (a: X / XC0 = first source, X1 / XC - XC0 = second, dB set)
-bool wgrad_pair_plan(const WgradArgs& a, int taps, WgradFlatPlan* plan);
+bool wgrad_pair_plan(const WgradArgs& a, int taps, WgradFlatPlan* plan, int slots = 0);
 int wgrad_pair_launch(const WgradArgs& a, const WgradFlatPlan& plan, hipStream_t st);
 int wgrad_flat_launch(const WgradArgs& a, const WgradFlatPlan& plan, hipStream_t st);
 

@@ -413,7 +413,7 @@ static const BlkInstance g_blk[] = {
 };
 #undef PSEG_BLK
 
-bool wgrad_blk_plan(const WgradArgs& a, int taps, WgradFlatPlan* plan) {
+bool wgrad_blk_plan(const WgradArgs& a, int taps, WgradFlatPlan* plan, int slots) {
     if (a.mode != 0 || a.stride != 1 || a.xup || taps != a.KW * a.KW || PSEG_KNOB("PSEG_WGRAD_NO_FLAT")) return false;
     if ((size_t)a.Wx * a.XC * 4 >= (1ull << 31) || (size_t)a.Wy * a.Cout * 4 >= (1ull << 31)) return false;   // 32-bit buffer offsets per row
     for (int k = 0; k < (int)(sizeof(g_blk) / sizeof(g_blk[0])); ++k) {
@@ -433,7 +433,7 @@ bool wgrad_blk_plan(const WgradArgs& a, int taps, WgradFlatPlan* plan) {
         const int cpr = cdiv(a.Wy, f.PW);
         // one resident round of workgroups: blocks x strips ~ what the chip holds; a strip costs a full copy of the layer's
         // gradient in the partial-sum buffer, so layers with many blocks take few
-        const int target = std::max(1, ncu_dev[dev] * f.wg_per_cu / nz);
+        const int target = std::max(1, (slots > 0 ? slots : ncu_dev[dev] * f.wg_per_cu) / nz);
         const int min_rows = 8;
         int cgroups = cpr, rows = 1;
         for (;;) {
@@ -444,6 +444,7 @@ bool wgrad_blk_plan(const WgradArgs& a, int taps, WgradFlatPlan* plan) {
         }
         cgroups = cdiv(cpr, cdiv(cpr, cgroups));
         plan->instance = 1000 + k;
+        plan->pw = f.PW;
         plan->strip_rows = rows;
         plan->cgroups = cgroups;
         plan->nstrips = cdiv(a.Hy, rows) * cgroups;
@@ -490,9 +491,9 @@ static const FlatInstance g_flat[] = {
 };
 #undef PSEG_FLAT
 
-bool wgrad_flat_plan(const WgradArgs& a, int taps, WgradFlatPlan* plan) {
+bool wgrad_flat_plan(const WgradArgs& a, int taps, WgradFlatPlan* plan, int slots) {
     if (a.mode != 0 || a.stride != 1 || a.xup || taps != a.KW * a.KW || PSEG_KNOB("PSEG_WGRAD_NO_FLAT")) return false;
-    if (a.KW == 3 && !PSEG_KNOB("PSEG_WGRAD_NO_BLK") && wgrad_blk_plan(a, taps, plan)) return true;   // unet / res_unet: channel blocks
+    if (a.KW == 3 && !PSEG_KNOB("PSEG_WGRAD_NO_BLK") && wgrad_blk_plan(a, taps, plan, slots)) return true;   // unet / res_unet: channel blocks
     if ((size_t)a.Wx * a.XC * 4 >= (1ull << 31) || (size_t)a.Wy * a.Cout * 4 >= (1ull << 31)) return false;   // 32-bit buffer offsets per row
     for (int k = 0; k < (int)(sizeof(g_flat) / sizeof(g_flat[0])); ++k) {
         const FlatInstance& f = g_flat[k];
@@ -519,7 +520,7 @@ bool wgrad_flat_plan(const WgradArgs& a, int taps, WgradFlatPlan* plan) {
             int n = 0;
             ncu_dev[dev] = (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256;
         }
-        const int target = ncu_dev[dev] * wg_per_cu[dev][k];
+        const int target = slots > 0 ? slots : ncu_dev[dev] * wg_per_cu[dev][k];
         const int min_rows = f.KYN > 1 ? 8 : 2;               // a strip shorter than this mostly primes its ring
         int cgroups = cpr, rows = 1;
         for (;;) {
@@ -530,6 +531,7 @@ bool wgrad_flat_plan(const WgradArgs& a, int taps, WgradFlatPlan* plan) {
         }
         cgroups = cdiv(cpr, cdiv(cpr, cgroups));              // no empty group
         plan->instance = k;
+        plan->pw = f.PW;
         plan->strip_rows = rows;
         plan->cgroups = cgroups;
         plan->nstrips = cdiv(a.Hy, rows) * cgroups;
@@ -756,7 +758,7 @@ static const PairInstance g_pair[] = {
 };
 #undef PSEG_PAIR
 
-bool wgrad_pair_plan(const WgradArgs& a, int taps, WgradFlatPlan* plan) {
+bool wgrad_pair_plan(const WgradArgs& a, int taps, WgradFlatPlan* plan, int slots) {
     if (a.stride != 1 || a.xup || a.in_relu || PSEG_KNOB("PSEG_WGRAD_NO_PAIR")) return false;
     if ((size_t)a.Wx * a.XC * 4 >= (1ull << 31) || (size_t)a.Wy * a.Cout * 4 >= (1ull << 31)) return false;
     for (int k = 0; k < (int)(sizeof(g_pair) / sizeof(g_pair[0])); ++k) {
@@ -780,7 +782,7 @@ bool wgrad_pair_plan(const WgradArgs& a, int taps, WgradFlatPlan* plan) {
             ncu_dev[dev] = (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256;
         }
         // these layers are bound by the bytes they read: a workgroup per slot of ONE resident round, whole rows per workgroup
-        const int target = ncu_dev[dev] * wg_per_cu[dev][k];
+        const int target = slots > 0 ? slots : ncu_dev[dev] * wg_per_cu[dev][k];
         const int cpr = cdiv(itW, f.PW);
         // (row strips x column groups) with at most `target` workgroups and the fewest steps for the busiest one
         int best_cg = 1, best_rows = itH, best_steps = 1 << 30;
@@ -792,6 +794,7 @@ bool wgrad_pair_plan(const WgradArgs& a, int taps, WgradFlatPlan* plan) {
         }
         const int cgroups = best_cg;
         plan->instance = k;
+        plan->pw = f.PW;
         plan->strip_rows = best_rows;
         plan->cgroups = cgroups;
         plan->nstrips = cdiv(itH, plan->strip_rows) * cgroups;

@@ -22,7 +22,7 @@ EXPORTED_SYMBOLS = (
     "pseg_timing_enable", "pseg_timing_reset", "pseg_timing_num_slots", "pseg_timing_get",
     "pseg_train_init", "pseg_train_set_optimizer", "pseg_train_set_loss", "pseg_train_set_dropout_seed", "pseg_train_forward_backward", "pseg_train_forward_backward_f32",
     "pseg_train_forward_backward_aug", "pseg_train_augment_sample", "pseg_train_grad_buffer", "pseg_train_metrics",
-    "pseg_train_apply", "pseg_train_get_gradient", "pseg_eval_step",
+    "pseg_train_apply", "pseg_train_get_gradient", "pseg_train_wgrad_layer", "pseg_eval_step",
     "pseg_allreduce_unique_id", "pseg_allreduce_init", "pseg_train_allreduce", "pseg_allreduce_destroy",
     "pseg_cc_vote", "pseg_cc_vote_device", "pseg_cc_vote_device_u8", "pseg_release_workspace", "pseg_bbox_fill",
     "pseg_masks", "pseg_masks_device", "pseg_masks_device_u8", "pseg_bbox_fill_device_u8",
@@ -85,6 +85,22 @@ class EVAL_RULE(ctypes.Structure):
     """pseg_eval_rule: cc_matching (kind 0) or cc_equal (kind 1) with its only_label filter."""
     _fields_ = [("kind", ctypes.c_int), ("label", ctypes.c_int), ("threshold_tp", ctypes.c_double), ("threshold_fp", ctypes.c_double),
                 ("threshold_mask", ctypes.c_double), ("filter_label", ctypes.c_int), ("filter_threshold", ctypes.c_double)]
+
+
+class WGRAD_LAYER(ctypes.Structure):
+    """pseg_wgrad_layer: one layer's weight gradient on device tensors (pseg_train_wgrad_layer)."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("X", "X1", "dY", "maskY", "dW", "dB")] + [(n, ctypes.c_int32) for n in (
+        "mode", "KW", "stride", "xup", "in_relu", "logits", "XC0", "XC1", "ci0", "Cin", "Cout", "Hx", "Wx", "xpitch", "Hy", "Wy",
+        "slots", "strip_rows")]
+
+
+class WGRAD_PLAN(ctypes.Structure):
+    """pseg_wgrad_plan: what pseg_train_wgrad_layer launched."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("variant", "instance", "ti", "tj", "lds_staged", "strip_rows", "cgroups", "nstrips",
+                                              "piece_width", "deterministic")]
+
+
+WGRAD_VARIANTS = ("PAIR", "FLAT", "BLK", "C1", "KX5", "TAP", "WIDE")   # PSEG_WGRAD_*
 
 
 class PsegError(Exception):
@@ -161,6 +177,7 @@ def lib():
     L.pseg_train_metrics.argtypes = [vp, c.POINTER(f)]
     L.pseg_train_apply.argtypes = [vp, f, f]
     L.pseg_train_get_gradient.argtypes = [vp, c.c_char_p, vp, i64]
+    L.pseg_train_wgrad_layer.argtypes = [vp, c.POINTER(WGRAD_LAYER), c.POINTER(WGRAD_PLAN)]
     L.pseg_eval_step.argtypes = [vp, vp, vp, i, i, c.POINTER(f)]
     L.pseg_allreduce_unique_id.argtypes = [vp]
     L.pseg_allreduce_init.argtypes = [vp, i, i, vp]
@@ -845,6 +862,23 @@ class Engine:
             a = np.empty(shp, np.float32)
             _check(L.pseg_train_get_gradient(self._h, name.encode(), _ptr(a), a.size))
             out[name] = a
+        return out
+
+    def wgrad_layer(self, X, dY, dW, *, mode=0, KW, Cin, Cout, Hx, Wx, Hy, Wy, XC0, X1=None, XC1=0, ci0=0, maskY=None, dB=None,
+                    stride=1, xup=False, in_relu=False, logits=False, xpitch=None, slots=0, strip_rows=0):
+        """One layer's weight (+ bias) gradient as the train step launches it, on device tensors (pseg_train_wgrad_layer; needs
+        train_init).  X, X1, dY, maskY, dW, dB: device pointers (int) or objects with data_ptr() -- float32, NHWC, already
+        written (the call runs on the engine's stream and waits for it).  -> dict of the launch: variant (one of
+        WGRAD_VARIANTS), instance, ti, tj, lds_staged, strip_rows, cgroups, nstrips, piece_width, deterministic."""
+        def dp(t):
+            return None if t is None else int(t.data_ptr() if hasattr(t, "data_ptr") else t)
+        a = WGRAD_LAYER(dp(X), dp(X1), dp(dY), dp(maskY), dp(dW), dp(dB), int(mode), int(KW), int(stride), int(bool(xup)),
+                        int(bool(in_relu)), int(bool(logits)), int(XC0), int(XC1), int(ci0), int(Cin), int(Cout), int(Hx), int(Wx),
+                        int((Wx >> int(bool(xup))) if xpitch is None else xpitch), int(Hy), int(Wy), int(slots), int(strip_rows))
+        ran = WGRAD_PLAN()
+        _check(lib().pseg_train_wgrad_layer(self._h, ctypes.byref(a), ctypes.byref(ran)))
+        out = {n: int(getattr(ran, n)) for n, _ in WGRAD_PLAN._fields_}
+        out["variant"] = WGRAD_VARIANTS[out["variant"]]
         return out
 
     def stream(self):

@@ -259,6 +259,8 @@ def test_bf16_unet_large_page_vs_bf16_oracle(gpu, oracle_mod):
 
 # ---------------------------------------------------------------------------------------------------------------------------
 # C. train step with column groups
+# (one plan of one wgrad_blk_kernel instance, through a whole step; test_wgrad_layers_gpu.py runs every instance of every
+# weight-gradient kernel on its own, exactly, under every strip plan)
 
 
 @pytest.mark.parametrize("arch", ["unet", "res_unet"])

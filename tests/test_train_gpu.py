@@ -61,8 +61,11 @@ def test_gradients_alternative_kernel_paths(gpu, oracle_mod, monkeypatch, knob):
         assert np.abs(g[k] - g_o[k]).max() <= 2e-3 * np.abs(g_o[k]).max() + 1e-9, (knob, k)
 
 
-# (160 x 288 / 144 x 272 -- a page smaller than its canvas: several row pieces per map -- 4.5 at full, 2.25 at quarter resolution -- and row strips cut into column
-# groups: the walk of the flattened-row and two-source weight-gradient kernels beyond a single piece, with ragged right edges)
+# (160 x 288 / 144 x 272 -- a page smaller than its canvas: several row pieces per map -- 4.5 at full, 2.25 at quarter resolution --
+# with ragged right edges.  On a 256-CU device these pages still give every flattened-row and two-source weight-gradient launch ONE
+# row per strip, the flattened-row kernel one column group walking up to five pieces, the two-source kernel up to five groups of one
+# piece: the LDS row ring never carries across rows and no group walks several pieces from a column start past 0.  Row strips of
+# several rows, column groups, short last strips and ragged groups are run layer by layer, exactly, in test_wgrad_layers_gpu.py.)
 @pytest.mark.parametrize("arch,C,shape", [("fcn_skip", 3, (64, 96)), ("fcn_skip", 6, (70, 50)), ("fcn", 3, (96, 64)), ("fcn_skip", 24, (64, 64)),
                                           ("fcn_skip", 3, (160, 288)), ("fcn", 4, (144, 272))])
 def test_loss_metrics_and_gradients(gpu, oracle_mod, arch, C, shape):
