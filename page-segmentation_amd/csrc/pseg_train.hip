@@ -7,8 +7,17 @@
 //   lib/metrics.py:60-85   jacard / dice with the +100 smoothing, per class over (H,W), mean over classes
 //   lib/network.py:90-104  optimizer(lr, clipnorm): per-tensor clip_by_norm (TF2.5 `clipnorm`), then Adam
 //   lib/architecture.py:83 Keras Adam: lr_t = lr*sqrt(1-b2^t)/(1-b1^t); m,v EMA; p -= lr_t*m/(sqrt(v)+eps), eps=1e-7
-// Round-1 scope: fcn / fcn_skip graphs (stride-1 convs, k2s2 transposed convs, 2x2 max-pool,
-// concat); correctness first -- these are plain float32 VALU kernels, not tuned.
+// What the file holds, in order:
+//   kernels   loss / metrics and the alternative losses' gradients; weight transforms, pool, residual, upsample and dilation
+//             helpers of the data gradients; the matrix-core weight-gradient kernels of the layers that have no instance in
+//             pseg_wgrad_flat.hip (wgrad_mfma / wgrad_lds / wgrad_c1) with their ordered reductions; bias gradient; the
+//             per-tensor norms and the optimizers
+//   launch_wgrad + wgrad_layer   one weight-gradient launch; a layer's weight gradient (two-source form or one launch per
+//             source), shared by the train step and pseg_train_wgrad_layer
+//   train_compute   the step on all four graphs (fcn, fcn_skip, unet, res_unet): forward under the training flags, loss and
+//             metrics, then the reverse walk over the ops -- backward_conv / backward_deconv2 / backward_bn / backward_pool
+//             on a Backward context; the data gradients are float32 convolutions of the engine (launch_conv_exact)
+//   train_augment / train_metrics / train_apply and the C entries
 // All parameter gradients live in ONE flat device buffer (plus the metric accumulators) so that
 // data-parallel training needs a single RCCL all-reduce.
 #include <algorithm>
@@ -21,6 +30,26 @@
 namespace pseg {
 
 constexpr int COT = 16;
+
+// workgroups of 256 threads for n elements of a grid-stride kernel, at most `cap`
+static int grid_1d(size_t n, size_t cap) { return (int)std::min<size_t>((n + 255) / 256, cap); }
+
+// a device buffer of the train state that only grows: {pointer, capacity in bytes}
+template <typename T>
+struct DevBuf {
+    T* p = nullptr;
+    size_t cap = 0;
+    int ensure(size_t bytes) {
+        if (cap >= bytes && p) return PSEG_OK;
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+        PSEG_HIP(hipMalloc((void**)&p, bytes));
+        cap = bytes;
+        return PSEG_OK;
+    }
+    void release() { (void)hipFree(p); p = nullptr; cap = 0; }
+};
 
 struct TrainState {
     float beta1 = 0.9f, beta2 = 0.999f, eps = 1e-7f, clipnorm = 1.0f, clipvalue = 0.0f;
@@ -40,37 +69,25 @@ struct TrainState {
     int nslices = 0;
     std::vector<int64_t> off;    // per param offset in the flat buffers
     int64_t nparam = 0, nflat = 0;
-    std::vector<float*> tgrad;   // per tensor gradient (canvas dims), lazily sized
-    std::vector<size_t> tbytes;
-    float* d_wd = nullptr;       // scratch: transformed weights for dgrad
-    size_t wd_bytes = 0;
-    float* d_wdrem = nullptr;    // scratch: the left-over output channels of those weights as shifted copies (conv_xb_kernel REM), rebuilt per launch
-    size_t wdrem_bytes = 0;
-    float* d_wpart = nullptr;    // scratch: per-strip partial weight / bias gradients of the layer being reduced (deterministic sums)
-    size_t wpart_bytes = 0;
-    float* d_mpart = nullptr;    // scratch: per-block partial loss / metric sums
-    size_t mpart_bytes = 0;
-    void* d_bpart = nullptr;     // scratch: per-block partial bias gradients of a transposed conv (float64)
-    size_t bpart_bytes = 0;
-    float* d_tmp = nullptr;      // scratch: data gradient at the conv's input extent (upsampled / pre-activation sources)
-    float* d_tmp2 = nullptr;     // scratch: zero-dilated output gradient (stride-2 convs)
-    size_t tmp_bytes = 0, tmp2_bytes = 0;
+    std::vector<DevBuf<float>> tgrad;   // per tensor gradient (canvas dims), lazily sized
+    DevBuf<float> d_wd;          // scratch: transformed weights for dgrad
+    DevBuf<float> d_wdrem;       // scratch: the left-over output channels of those weights as shifted copies (conv_xb_kernel REM), rebuilt per launch
+    DevBuf<float> d_wpart;       // scratch: per-strip partial weight / bias gradients of the layer being reduced (deterministic sums)
+    DevBuf<float> d_mpart;       // scratch: per-block partial loss / metric sums
+    DevBuf<double> d_bpart;      // scratch: per-block partial bias gradients of a transposed conv (float64)
+    DevBuf<float> d_tmp;         // scratch: data gradient at the conv's input extent (upsampled / pre-activation sources)
+    DevBuf<float> d_tmp2;        // scratch: zero-dilated output gradient (stride-2 convs)
     uint32_t drop_seed = 0x1234u;
     int64_t fwd_count = 0;       // training forwards so far: the Dropout mask changes every step
-    float* d_logits = nullptr;
-    float* d_dlogits = nullptr;
-    uint8_t* d_mask = nullptr;
-    uint8_t* d_img = nullptr;
-    size_t logits_bytes = 0, mask_bytes = 0, img_bytes = 0;
+    DevBuf<float> d_logits, d_dlogits;
+    DevBuf<uint8_t> d_mask, d_img;
     // device-resident augmentation (pseg_train_forward_backward_aug): the uploaded uint8 page and mask, the float64 spline
     // coefficient plane of one channel, min / max keys of the brightness stretch; the sample itself lands in d_img / d_mask
-    uint8_t* d_aug_img = nullptr;
-    uint8_t* d_aug_mask = nullptr;
-    double* d_aug_coef = nullptr;
-    unsigned* d_aug_mm = nullptr;
-    size_t aug_img_bytes = 0, aug_mask_bytes = 0, aug_coef_bytes = 0, aug_mm_bytes = 0;
+    DevBuf<uint8_t> d_aug_img, d_aug_mask;
+    DevBuf<double> d_aug_coef;
+    DevBuf<unsigned> d_aug_mm;
     int H = 0, W = 0;
-    // weight gradients run on a stream of their own beside the data gradients (both only read dY; see train_forward_backward)
+    // weight gradients run on a stream of their own beside the data gradients (both only read dY; see open_weight_stream)
     hipStream_t wstream = nullptr;
     hipEvent_t ev_dy = nullptr, ev_wdone = nullptr;
 };
@@ -82,11 +99,11 @@ void train_free(Engine& e) {
     if (!t) return;
     (void)hipFree(t->d_grad); (void)hipFree(t->d_m); (void)hipFree(t->d_v); (void)hipFree(t->d_norm);
     (void)hipFree(t->d_part); (void)hipFree(t->d_slice_nblk); (void)hipFree(t->d_slice_pi);
-    for (auto p : t->tgrad) (void)hipFree(p);
-    (void)hipFree(t->d_wd); (void)hipFree(t->d_wdrem); (void)hipFree(t->d_logits); (void)hipFree(t->d_dlogits);
-    (void)hipFree(t->d_wpart); (void)hipFree(t->d_mpart); (void)hipFree(t->d_bpart);
-    (void)hipFree(t->d_mask); (void)hipFree(t->d_img); (void)hipFree(t->d_tmp); (void)hipFree(t->d_tmp2);
-    (void)hipFree(t->d_aug_img); (void)hipFree(t->d_aug_mask); (void)hipFree(t->d_aug_coef); (void)hipFree(t->d_aug_mm);
+    for (auto& g : t->tgrad) g.release();
+    t->d_wd.release(); t->d_wdrem.release(); t->d_logits.release(); t->d_dlogits.release();
+    t->d_wpart.release(); t->d_mpart.release(); t->d_bpart.release();
+    t->d_mask.release(); t->d_img.release(); t->d_tmp.release(); t->d_tmp2.release();
+    t->d_aug_img.release(); t->d_aug_mask.release(); t->d_aug_coef.release(); t->d_aug_mm.release();
     if (t->wstream) { (void)hipStreamSynchronize(t->wstream); (void)hipStreamDestroy(t->wstream); }
     if (t->ev_dy) (void)hipEventDestroy(t->ev_dy);
     if (t->ev_wdone) (void)hipEventDestroy(t->ev_wdone);
@@ -337,90 +354,6 @@ __global__ __launch_bounds__(256) void column_sum_kernel(const T* rows, int nrow
         __syncthreads();
     }
     if (threadIdx.x == 0) out[c] = (float)sh[0];
-}
-
-constexpr int WG_PC = 32;  // pixels per LDS chunk
-
-__global__ __launch_bounds__(256) void wgrad_kernel(WgradArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float sm[];
-    const int XCp = (a.XC + 3) & ~3, COp = (a.Cout + 3) & ~3;
-    float* Xs = sm;                    // [WG_PC][XCp]
-    float* Ys = sm + WG_PC * XCp;      // [WG_PC][COp]
-    const int tap = blockIdx.y;
-    const int ky = tap / a.KW, kx = tap % a.KW;
-    const int itW = a.mode == 0 ? a.Wy : a.Wx, itH = a.mode == 0 ? a.Hy : a.Hx;
-    const int r0 = blockIdx.x * a.strip_rows, r1 = min(r0 + a.strip_rows, itH);
-    const int tiles_ci = XCp / 4, tiles_co = COp / 4, ntl = tiles_ci * tiles_co;
-    float acc[3][16];
-#pragma unroll
-    for (int q = 0; q < 3; ++q)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[q][i] = 0.0f;
-    float bsum = 0.0f;
-    const int npx = (r1 - r0) * itW;
-    for (int p0 = 0; p0 < npx; p0 += WG_PC) {
-        __syncthreads();
-        for (int i = threadIdx.x; i < WG_PC * XCp; i += 256) {
-            const int pp = i / XCp, c = i - pp * XCp;
-            const int p = p0 + pp;
-            float v = 0.0f;
-            if (p < npx && c < a.XC) {
-                const int y = r0 + p / itW, x = p % itW;
-                int sy, sx;
-                if (a.mode == 0) { sy = y + ky - a.pt; sx = x + kx - a.pl; } else { sy = y; sx = x; }
-                if (sy >= 0 && sy < a.Hx && sx >= 0 && sx < a.Wx) v = a.X[((size_t)sy * a.xpitch + sx) * a.XC + c];
-            }
-            Xs[i] = v;
-        }
-        for (int i = threadIdx.x; i < WG_PC * COp; i += 256) {
-            const int pp = i / COp, c = i - pp * COp;
-            const int p = p0 + pp;
-            float v = 0.0f;
-            if (p < npx && c < a.Cout) {
-                const int y = r0 + p / itW, x = p % itW;
-                const int dy = a.mode == 0 ? y : 2 * y + (tap >> 1), dx = a.mode == 0 ? x : 2 * x + (tap & 1);
-                const size_t o = ((size_t)dy * a.ypitch + dx) * a.Cout + c;
-                v = a.dY[o];
-                if (a.maskY && !(a.maskY[o] > 0.0f)) v = 0.0f;
-            }
-            Ys[i] = v;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int q = 0; q < 3; ++q) {
-            const int tl = threadIdx.x + q * 256;
-            if (tl < ntl) {
-                const int tci = tl / tiles_co, tco = tl - tci * tiles_co;
-                for (int pp = 0; pp < WG_PC; ++pp) {
-                    const float4 xv = *(const float4*)(Xs + pp * XCp + tci * 4);
-                    const float4 yv = *(const float4*)(Ys + pp * COp + tco * 4);
-                    const float xs[4] = {xv.x, xv.y, xv.z, xv.w}, ys[4] = {yv.x, yv.y, yv.z, yv.w};
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) acc[q][i * 4 + j] = __builtin_fmaf(xs[i], ys[j], acc[q][i * 4 + j]);
-                }
-            }
-        }
-        if (a.dB && tap == 0 && (int)threadIdx.x < a.Cout)
-            for (int pp = 0; pp < WG_PC; ++pp) bsum += Ys[pp * COp + threadIdx.x];
-    }
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-        const int tl = threadIdx.x + q * 256;
-        if (tl < ntl) {
-            const int tci = tl / tiles_co, tco = tl - tci * tiles_co;
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int ci = tci * 4 + i, co = tco * 4 + j;
-                    if (ci < a.XC && co < a.Cout) wg_out(a, blockIdx.x, tap, ci, co, acc[q][i * 4 + j]);
-                }
-        }
-    }
-    if (a.dB && tap == 0 && (int)threadIdx.x < a.Cout)
-        for (int w = 0; w < 4; ++w) wg_out_bias(a, blockIdx.x, w, threadIdx.x, w == 0 ? bsum : 0.0f);
 }
 
 // Matrix-core weight gradient.  dW[tap][ci][co] += sum over pixels of X[pixel + tap][ci] * dY[pixel][co]
@@ -830,17 +763,16 @@ __global__ __launch_bounds__(256) void wgrad_c1_kernel(WgradArgs a) {
 }
 
 // Chooses the kernel instance for a layer, launches it and (deterministic form) sums the strips' partial results.
-// grid = (strips, taps) as the scalar kernel takes it; `scratch` / `scratch_cap` = the train state's partial-sum buffer.
+// grid = (strips, taps) as the caller proposes them; `scratch` = the train state's partial-sum buffer.
 // `slots` > 0 (pseg_train_wgrad_layer only) stands in for the device's workgroup slots in the strip planners; `ran`, when given,
 // receives what was launched.
-static int launch_wgrad(const WgradArgs& a_in, dim3 grid, hipStream_t st, float** scratch, size_t* scratch_cap, int slots = 0,
+static int launch_wgrad(const WgradArgs& a_in, dim3 grid, hipStream_t st, DevBuf<float>& scratch, int slots = 0,
                         pseg_wgrad_plan* ran = nullptr) {
     WgradArgs a = a_in;
     const int itH = a.mode == 0 ? a.Hy : a.Hx;
     const int taps = (int)grid.y;
     // ---- which instance, with which strips
-    enum { V_PAIR, V_FLAT, V_C1, V_KX5, V_TAP, V_WIDE, V_SCALAR } variant;
-    const bool scalar = false;
+    enum { V_PAIR, V_FLAT, V_C1, V_KX5, V_TAP, V_WIDE } variant;
     WgradFlatPlan flat;
     const bool lds = a.mode == 0 && a.stride == 1 && !a.xup;
     const int ti = (a.XC + 15) / 16, tj = (a.Cout + 15) / 16;
@@ -849,13 +781,13 @@ static int launch_wgrad(const WgradArgs& a_in, dim3 grid, hipStream_t st, float*
         if (!wgrad_pair_plan(a, taps, &flat, slots)) return fail(PSEG_EINVAL, "no two-source weight-gradient instance for this layer");
         variant = V_PAIR;
         a.strip_rows = flat.strip_rows;
-    } else if (!scalar && wgrad_flat_plan(a, taps, &flat, slots)) {
+    } else if (wgrad_flat_plan(a, taps, &flat, slots)) {
         variant = V_FLAT;                                      // the k5 layers of fcn / fcn_skip (pseg_wgrad_flat.hip)
         a.strip_rows = flat.strip_rows;
-    } else if (a.XC == 1 && a.mode == 0 && a.stride == 1 && !a.xup && !a.in_relu && a.KW * a.KW <= 32 && a.Cout <= 64 && !scalar) {
+    } else if (a.XC == 1 && a.mode == 0 && a.stride == 1 && !a.xup && !a.in_relu && a.KW * a.KW <= 32 && a.Cout <= 64) {
         variant = V_C1;
         a.strip_rows = std::max(1, cdiv(a.Hy, 1024));
-    } else if (a.XC <= 16 * WGM_MAXT && a.Cout <= 16 * WGM_MAXT && !scalar) {
+    } else if (a.XC <= 16 * WGM_MAXT && a.Cout <= 16 * WGM_MAXT) {
         // a whole kernel row per workgroup for the small k5 layers (mode 0: taps of a row share dY)
         if (a.mode == 0 && a.KW == 5 && taps % 5 == 0 && ((ti <= 2 && tj <= 2) || (ti <= 2 && tj <= 3) || (ti <= 1 && tj <= 2))) {
             variant = V_KX5;                                   // five times fewer "taps": five times more strips
@@ -863,7 +795,7 @@ static int launch_wgrad(const WgradArgs& a_in, dim3 grid, hipStream_t st, float*
         } else {
             variant = V_TAP;
         }
-    } else if (!scalar) {
+    } else {
         variant = V_WIDE;
         // wide layers sit on small maps and get their parallelism from the 64 x 64 channel blocks and the taps: few strips
         // (every strip is a full copy of the layer's gradient in the partial-sum buffer -- 19 MB for 512 -> 1024 channels; at one
@@ -871,8 +803,6 @@ static int launch_wgrad(const WgradArgs& a_in, dim3 grid, hipStream_t st, float*
         const int nblk = cdiv(a.XC, 64) * cdiv(a.Cout, 64);
         const int want = std::max(1, 2048 / std::max(1, taps * nblk));
         a.strip_rows = std::max(a.strip_rows, cdiv(itH, want));
-    } else {
-        variant = V_SCALAR;
     }
     const int nstrips = (variant == V_FLAT || variant == V_PAIR) ? flat.nstrips : cdiv(itH, a.strip_rows);
     // ---- deterministic form: partial sums per strip, then one ordered reduction (PSEG_WGRAD_ATOMIC=1: float atomics)
@@ -880,14 +810,12 @@ static int launch_wgrad(const WgradArgs& a_in, dim3 grid, hipStream_t st, float*
     if (det) {
         a.pstride = (size_t)taps * a.XC * a.Cout;
         const size_t need = ((size_t)nstrips * a.pstride + (size_t)4 * nstrips * a.Cout) * sizeof(float);
-        if (*scratch_cap < need) {
-            if (*scratch) { PSEG_HIP(hipStreamSynchronize(st)); (void)hipFree(*scratch); }
-            *scratch = nullptr; *scratch_cap = 0;
-            PSEG_HIP(hipMalloc((void**)scratch, need));
-            *scratch_cap = need;
+        if (scratch.cap < need) {
+            if (scratch.p) PSEG_HIP(hipStreamSynchronize(st));   // what is in flight on st still reads the buffer about to be freed
+            PSEG_TRY(scratch.ensure(need));
         }
-        a.part = *scratch;
-        a.partB = a.dB ? *scratch + (size_t)nstrips * a.pstride : nullptr;
+        a.part = scratch.p;
+        a.partB = a.dB ? scratch.p + (size_t)nstrips * a.pstride : nullptr;
     }
     switch (variant) {
         case V_PAIR: PSEG_TRY(wgrad_pair_launch(a, flat, st)); break;
@@ -934,19 +862,12 @@ static int launch_wgrad(const WgradArgs& a_in, dim3 grid, hipStream_t st, float*
             ran_ti = ran_tj = 4;
             break;
         }
-        case V_SCALAR: {
-            const int XCp = (a.XC + 3) & ~3, COp = (a.Cout + 3) & ~3;
-            if (a.stride != 1 || a.xup || a.in_relu || (XCp / 4) * (COp / 4) > 768)
-                return fail(PSEG_EUNSUPPORTED, "the scalar weight-gradient kernel does not cover this layer");
-            wgrad_kernel<<<dim3(nstrips, taps), 256, (size_t)WG_PC * (XCp + COp) * 4, st>>>(a);
-            break;
-        }
     }
     PSEG_HIP(hipGetLastError());
     if (det) {
         const size_t n = a.pstride;
         wgrad_reduce_groups_kernel<<<dim3((unsigned)((n + 255) / 256), (unsigned)cdiv(nstrips, WGR_GROUP)), 256, 0, st>>>(a.part, a.pstride, nstrips);
-        wgrad_reduce_kernel<<<(int)std::min<size_t>((n + 255) / 256, 2048), 256, 0, st>>>(a.part, a.pstride, nstrips, taps, a.XC, a.Cout, a.Cin, a.ci0, a.dW,
+        wgrad_reduce_kernel<<<grid_1d(n, 2048), 256, 0, st>>>(a.part, a.pstride, nstrips, taps, a.XC, a.Cout, a.Cin, a.ci0, a.dW,
                                                                                           a.partB, a.dB);
         if (a.partB) column_sum_kernel<float><<<a.Cout, 256, 0, st>>>(a.partB, 4 * nstrips, a.Cout, a.dB);
         PSEG_HIP(hipGetLastError());
@@ -954,7 +875,7 @@ static int launch_wgrad(const WgradArgs& a_in, dim3 grid, hipStream_t st, float*
     if (ran) {
         const bool planned = variant == V_PAIR || variant == V_FLAT;
         const bool blk = variant == V_FLAT && flat.instance >= 1000;
-        static const int code[] = {PSEG_WGRAD_PAIR, PSEG_WGRAD_FLAT, PSEG_WGRAD_C1, PSEG_WGRAD_KX5, PSEG_WGRAD_TAP, PSEG_WGRAD_WIDE, -1};
+        static const int code[] = {PSEG_WGRAD_PAIR, PSEG_WGRAD_FLAT, PSEG_WGRAD_C1, PSEG_WGRAD_KX5, PSEG_WGRAD_TAP, PSEG_WGRAD_WIDE};
         ran->variant = blk ? PSEG_WGRAD_BLK : code[variant];
         ran->instance = planned ? flat.instance % 1000 : -1;
         ran->ti = ran_ti;
@@ -1019,6 +940,64 @@ static WgradArgs wgrad_deconv_args(const float* X, int XC, int ci0, int Hx, int 
     a.KW = 2; a.mode = 1;
     a.strip_rows = wgrad_caller_strip_rows(Hx, 4);
     return a;
+}
+
+// ---- a layer's weight (+ bias) gradient: ONE routine for the conv / logits layers and the transposed convs of the train step and
+// for pseg_train_wgrad_layer
+struct WgradLayer {
+    int mode = 0;                        // 0 conv / logits, 1 k2 s2 transposed conv
+    bool try_pair = false;               // the caller's precondition for the two-source form
+    // concat sources: X[s] holds XC[s] channels per pixel, rows xpitch[s] pixels apart, read through a nearest x2 upsample when
+    // xup[s]; in dW source 0 starts at channel ci0 and source 1 follows it
+    int nsrc = 1;
+    const float* X[2] = {};
+    int XC[2] = {}, xup[2] = {}, xpitch[2] = {};
+    int ci0 = 0;
+    int Hx = 0, Wx = 0, in_relu = 0;     // extent of the layer's input (shared by the sources)
+    const float* dY = nullptr;
+    const float* maskY = nullptr;
+    int Hy = 0, Wy = 0, Cout = 0, Cin = 0, k = 1, stride = 1, pt = 0, pl = 0;
+    float* dW = nullptr;
+    float* dB = nullptr;
+};
+// the rule: both sources and the bias gradient in one pass over dY where the caller allows it and the layer has an instance
+// (*a: that launch's arguments), else one launch per source
+static bool wgrad_layer_pairs(const WgradLayer& L, int slots, WgradArgs* a) {
+    if (!L.try_pair) return false;
+    *a = wgrad_pair_args(L.mode, L.X[0], L.XC[0], L.nsrc > 1 ? L.X[1] : nullptr, L.nsrc > 1 ? L.XC[1] : 0, L.Hx, L.Wx, L.xpitch[0],
+                         L.in_relu, L.dY, L.maskY, L.Hy, L.Wy, L.Cout, L.Cin, L.k, L.pt, L.pl, L.dW, L.dB);
+    WgradFlatPlan pp;
+    return wgrad_pair_plan(*a, L.k * L.k, &pp, slots);
+}
+// everything enqueued on `st` so far is visible to the next kernel on `ws` (the train step's weight-gradient stream)
+static int dy_ready(TrainState* t, hipStream_t st, hipStream_t ws) {
+    if (ws != st) { PSEG_HIP(hipEventRecord(t->ev_dy, st)); PSEG_HIP(hipStreamWaitEvent(ws, t->ev_dy, 0)); }
+    return PSEG_OK;
+}
+// Launches the layer's weight gradient on `ws`, each launch behind what `st` holds so far.  *paired: the two-source form ran (it
+// takes the bias gradient of a transposed conv with it; the per-source form of mode 1 leaves L.dB alone).  slots / strip_rows / ran:
+// as pseg_train_wgrad_layer documents them, 0 in the train step.
+static int wgrad_layer(const WgradLayer& L, TrainState* t, hipStream_t st, hipStream_t ws, bool* paired = nullptr, int slots = 0,
+                       int strip_rows = 0, pseg_wgrad_plan* ran = nullptr) {
+    WgradArgs a{};
+    const bool pair = wgrad_layer_pairs(L, slots, &a);
+    if (paired) *paired = pair;
+    for (int s = 0; s < (pair ? 1 : L.nsrc); ++s) {
+        dim3 grid(1, L.k * L.k);
+        if (!pair) {
+            const int ci0 = L.ci0 + (s == 0 ? 0 : L.XC[0]);
+            if (L.mode == 1)
+                a = wgrad_deconv_args(L.X[s], L.XC[s], ci0, L.Hx, L.Wx, L.xpitch[s], L.dY, L.maskY, L.Cout, L.Cin, L.dW);
+            else
+                a = wgrad_conv_args(L.X[s], L.XC[s], ci0, L.Hx, L.Wx, L.xpitch[s], L.xup[s], L.stride, L.in_relu, L.dY, L.maskY, L.Hy, L.Wy,
+                                    L.Cout, L.Cin, L.k, L.pt, L.pl, L.dW, s == 0 ? L.dB : nullptr);
+            if (strip_rows > 0) a.strip_rows = strip_rows;
+            grid.x = cdiv(L.mode == 1 ? L.Hx : L.Hy, a.strip_rows);
+        }
+        PSEG_TRY(dy_ready(t, st, ws));
+        PSEG_TRY(launch_wgrad(a, grid, ws, t->d_wpart, slots, ran));
+    }
+    return PSEG_OK;
 }
 
 // dst[i] += src[i] (masked by maskX[i] > 0 when given): residual addend gradients, pre-activation ReLU dgrad
@@ -1190,22 +1169,6 @@ __global__ void fill_kernel(float* p, int64_t n, float v) {
 // ---------------------------------------------------------------------------------------------
 // host orchestration
 // ---------------------------------------------------------------------------------------------
-static int ensure_buf(void** p, size_t* cap, size_t bytes) {
-    if (*cap >= bytes && *p) return PSEG_OK;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    PSEG_HIP(hipMalloc(p, bytes));
-    *cap = bytes;
-    return PSEG_OK;
-}
-
-static int producer_of(const Engine& e, int tensor) {
-    for (size_t i = 0; i < e.ops.size(); ++i)
-        if (e.ops[i].dst == tensor) return (int)i;
-    return -1;
-}
-
 static int train_init(Engine& e, float b1, float b2, float eps, float clipnorm, float clipvalue) {
     if (e.mode != PSEG_MODE_F32_EXACT) return fail(PSEG_EUNSUPPORTED, "training runs on the float32 engine (mode F32_EXACT)");
     if (e.n_classes > PSEG_MAXC) return fail(PSEG_EUNSUPPORTED, "training supports at most %d classes", PSEG_MAXC);
@@ -1228,8 +1191,7 @@ static int train_init(Engine& e, float b1, float b2, float eps, float clipnorm, 
     PSEG_HIP(hipMemset(t->d_m, 0, (size_t)t->nparam * 4));
     PSEG_HIP(hipMemset(t->d_v, 0, (size_t)t->nparam * 4));
     PSEG_HIP(hipDeviceSynchronize());   // null-stream memsets are not ordered with the engine's non-blocking stream
-    t->tgrad.assign(e.tensors.size(), nullptr);
-    t->tbytes.assign(e.tensors.size(), 0);
+    t->tgrad.assign(e.tensors.size(), DevBuf<float>());
     return PSEG_OK;
 }
 
@@ -1246,13 +1208,10 @@ static int train_stage(Engine& e, int H, int W, bool img_f32) {
     PSEG_TRY(set_canvas(e, H, W, e.stream));
     const int C = e.n_classes;
     const size_t npx = (size_t)H * W;
-    PSEG_TRY(ensure_buf((void**)&t->d_img, &t->img_bytes, npx * e.in_ch * (img_f32 ? 4 : 1)));
-    PSEG_TRY(ensure_buf((void**)&t->d_mask, &t->mask_bytes, npx));
-    size_t lb = t->logits_bytes;
-    PSEG_TRY(ensure_buf((void**)&t->d_logits, &lb, npx * C * 4));
-    lb = t->logits_bytes;
-    PSEG_TRY(ensure_buf((void**)&t->d_dlogits, &lb, npx * C * 4));
-    t->logits_bytes = lb;
+    PSEG_TRY(t->d_img.ensure(npx * e.in_ch * (img_f32 ? 4 : 1)));
+    PSEG_TRY(t->d_mask.ensure(npx));
+    PSEG_TRY(t->d_logits.ensure(npx * C * 4));
+    PSEG_TRY(t->d_dlogits.ensure(npx * C * 4));
     t->H = H; t->W = W;
     return PSEG_OK;
 }
@@ -1264,272 +1223,340 @@ static int train_fwd_bwd(Engine& e, const uint8_t* img, const uint8_t* mask, int
     TrainState* t = TS(e);
     hipStream_t st = e.stream;
     const size_t npx = (size_t)H * W;
-    if (img_f32) PSEG_HIP(hipMemcpyAsync(t->d_img, img_f32, npx * e.in_ch * 4, hipMemcpyHostToDevice, st));
-    else PSEG_HIP(hipMemcpyAsync(t->d_img, img, npx * e.in_ch, hipMemcpyHostToDevice, st));
-    PSEG_HIP(hipMemcpyAsync(t->d_mask, mask, npx, hipMemcpyHostToDevice, st));
+    if (img_f32) PSEG_HIP(hipMemcpyAsync(t->d_img.p, img_f32, npx * e.in_ch * 4, hipMemcpyHostToDevice, st));
+    else PSEG_HIP(hipMemcpyAsync(t->d_img.p, img, npx * e.in_ch, hipMemcpyHostToDevice, st));
+    PSEG_HIP(hipMemcpyAsync(t->d_mask.p, mask, npx, hipMemcpyHostToDevice, st));
     return train_compute(e, H, W, backward, img_f32 != nullptr);
+}
+
+// ---- the step's forward half
+// forward under the training flags: Dropout layers are live in a training forward (Keras fit), the identity in an evaluation step
+static int train_forward(Engine& e, TrainState* t, uint32_t drop_key, bool training, int relaxed, bool img_f32) {
+    e.cur_img_f32 = img_f32 ? (const float*)t->d_img.p : nullptr;
+    e.drop_key = drop_key;
+    e.bn_training = training;   // Keras fit: BatchNormalization layers normalise with the batch statistics; evaluate / predict with the moving ones
+    e.relaxed_f32 = relaxed;    // wide layers: channel-blocked matrix-core kernel (summation order differs from predict)
+    const int rc_fwd = run_exact(e, t->d_img.p, t->d_logits.p, nullptr, nullptr, nullptr, e.stream);
+    e.drop_key = 0;
+    e.bn_training = false;
+    e.relaxed_f32 = 0;
+    e.cur_img_f32 = nullptr;
+    return rc_fwd;
+}
+
+// loss, metrics and the gradient of the loss with respect to the logits (t->d_dlogits)
+static int train_loss_metrics(Engine& e, TrainState* t, int H, int W, bool backward) {
+    hipStream_t st = e.stream;
+    const int C = e.n_classes;
+    const size_t npx = (size_t)H * W;
+    float* acc = t->d_grad + t->nparam;
+    // a backward pass starts from zeroed parameter gradients; an evaluation step only resets the metric slots
+    if (backward) PSEG_HIP(hipMemsetAsync(t->d_grad, 0, (size_t)t->nflat * 4, st));
+    else PSEG_HIP(hipMemsetAsync(acc, 0, (size_t)(t->nflat - t->nparam) * 4, st));
+    const int nblk = cdiv((int)npx, 256), nslot = 2 + 2 * C;
+    PSEG_TRY(t->d_mpart.ensure((size_t)nblk * nslot * 4));
+    ce_metrics_kernel<<<nblk, 256, 0, st>>>(t->d_logits.p, t->d_mask.p, (int)npx, C, 1.0f / (float)npx, t->d_dlogits.p, t->d_mpart.p);
+    metrics_final_kernel<<<nslot, 256, 0, st>>>(t->d_mpart.p, nblk, nslot, acc);
+    if (t->loss_kind != PSEG_LOSS_CE)
+        loss_grad_kernel<<<cdiv((int)npx, 256), 256, 0, st>>>(t->loss_kind, t->d_logits.p, t->d_mask.p, (int)npx, C, 1.0f / (float)npx,
+                                                            acc, t->d_dlogits.p, acc + 2 + 2 * PSEG_MAXC);
+    PSEG_HIP(hipGetLastError());
+    return PSEG_OK;
+}
+
+// ---- the backward pass: what its steps share.
+// Tensor gradients (canvas dims) are not zeroed: the first consumer met on the way back STORES its contribution
+// (fresh[i]), the later ones accumulate -- a memset per tensor and a read of the zeros by the first writer were 0.3 ms of a
+// 15 ms step.  Writers without a store form (and a gradient nobody wrote before it is read) zero the buffer first.
+struct Backward {
+    Engine& e;
+    TrainState* t;
+    hipStream_t st, ws;          // main stream; the weight gradients' stream (open_weight_stream; == st under PSEG_TRAIN_ONE_STREAM)
+    int H, W;                    // the page (the canvas may be larger)
+    uint32_t drop_key;
+    int relaxed;                 // 0 under PSEG_TRAIN_STRICT
+    std::vector<char> fresh;
+    float* grad(int tensor) const { return t->tgrad[tensor].p; }
+    float* param_grad(int param) const { return param >= 0 ? t->d_grad + t->off[param] : nullptr; }
+    size_t tensor_bytes(int i) const { const Tensor& tn = e.tensors[i]; return (size_t)e.tH(tn) * e.tW(tn) * tn.C * 4; }
+    int zero_if_fresh(int i) {
+        if (i >= 0 && fresh[i]) { PSEG_HIP(hipMemsetAsync(grad(i), 0, tensor_bytes(i), st)); fresh[i] = 0; }
+        return PSEG_OK;
+    }
+    int dy_ready() { return pseg::dy_ready(t, st, ws); }
+    int ensure_wd(size_t floats) { return t->d_wd.ensure((floats + COT) * 4); }
+};
+
+static int size_tensor_grads(Backward& b) {
+    for (size_t i = 0; i < b.e.tensors.size(); ++i) {
+        if ((int)i == b.e.input_tensor) continue;
+        DevBuf<float>& g = b.t->tgrad[i];
+        const size_t bytes = b.tensor_bytes((int)i);
+        if (bytes > g.cap) {
+            PSEG_TRY(g.ensure(bytes));
+            // a new buffer starts as NaNs (once, not per step): a region no writer covers then shows in every gradient
+            // test instead of depending on what the allocator hands back
+            PSEG_HIP(hipMemsetAsync(g.p, 0xFF, bytes, b.st));
+        }
+    }
+    return PSEG_OK;
+}
+
+// Second stream for the weight gradients.  A layer's weight gradient and its data gradient both only READ the layer's output
+// gradient, and nothing downstream of a weight gradient runs before the optimizer: the weight-gradient kernels (and their
+// ordered reductions) go to `ws`, gated by an event recorded on the main stream once dY is final; the main stream carries on
+// with the data gradients and joins at the end.  Two MFMA-bound kernels of 65-85 % pipe-busy each fill each other's gaps.
+static int open_weight_stream(Backward& b) {
+    TrainState* t = b.t;
+    if (PSEG_KNOB("PSEG_TRAIN_ONE_STREAM")) return PSEG_OK;
+    if (!t->wstream) {
+        PSEG_HIP(hipStreamCreateWithFlags(&t->wstream, hipStreamNonBlocking));
+        PSEG_HIP(hipEventCreateWithFlags(&t->ev_dy, hipEventDisableTiming));
+        PSEG_HIP(hipEventCreateWithFlags(&t->ev_wdone, hipEventDisableTiming));
+    }
+    b.ws = t->wstream;
+    return PSEG_OK;
+}
+// every way out of the backward pass -- also an early error return -- leaves the main stream waiting for what was enqueued on `ws`:
+// the next step's zeroing of the gradient buffer and its forward must not overtake weight-gradient kernels still in flight
+struct Join {
+    hipStream_t ws, st; hipEvent_t ev; bool done = false;
+    void now() { if (!done && ws != st && ev) { (void)hipEventRecord(ev, ws); (void)hipStreamWaitEvent(st, ev, 0); } done = true; }
+    ~Join() { now(); }
+};
+
+// the layer as wgrad_layer takes it: sources, extents, output gradient under its mask, the parameter gradients
+static WgradLayer op_wgrad_layer(const Backward& b, const Op& op, int mode, int Hx, int Wx, const float* dY, const float* maskY, int Hy,
+                                 int Wy) {
+    WgradLayer L;
+    L.mode = mode;
+    L.nsrc = op.src1 >= 0 ? 2 : 1;
+    for (int s = 0; s < L.nsrc; ++s) {
+        const Tensor& sx = b.e.tensors[s == 0 ? op.src0 : op.src1];
+        const int up = mode == 1 ? 0 : (s == 0 ? op.up0 : op.up1);
+        L.X[s] = (const float*)sx.d; L.XC[s] = sx.C; L.xup[s] = up; L.xpitch[s] = Wx >> up;
+    }
+    L.Hx = Hx; L.Wx = Wx;
+    L.dY = dY; L.maskY = maskY; L.Hy = Hy; L.Wy = Wy; L.Cout = op.Cout; L.Cin = op.Cin;
+    L.dW = b.param_grad(op.kparam); L.dB = b.param_grad(op.bparam);
+    return L;
+}
+
+// ---- conv and logits layers
+struct ConvBack {                // what the steps of one layer share
+    bool lg;                     // the logits layer: dY = the loss gradient at the page extent, no mask, no padding
+    const float* dY;
+    const float* maskY;          // the layer's output where it has a ReLU
+    int Hy, Wy;
+    int Hx, Wx;                  // extent of the conv's input: both concat sources share it (a half-resolution source is read through up0 / up1)
+    int pt, pl;
+};
+
+// residual addend (Add() after the bias): its gradient is the layer's output gradient
+static int conv_residual_grad(Backward& b, const Op& op, const ConvBack& g) {
+    const Tensor& ad = b.e.tensors[op.add];
+    const size_t n = (size_t)b.e.tH(ad) * b.e.tW(ad) * ad.C;
+    PSEG_TRY(b.zero_if_fresh(op.add));
+    accum_kernel<<<grid_1d(n, 8192), 256, 0, b.st>>>(b.grad(op.add), g.dY, g.maskY, nullptr, n);
+    return PSEG_OK;
+}
+
+// wgrad + bias grad; the 1x1 logits layer: both sources and the bias in one pass over dY
+static int conv_weight_grad(Backward& b, const Op& op, const ConvBack& g) {
+    WgradLayer L = op_wgrad_layer(b, op, 0, g.Hx, g.Wx, g.dY, g.maskY, g.Hy, g.Wy);
+    L.try_pair = g.lg && !op.up0 && !op.up1 && op.stride == 1;
+    L.in_relu = op.in_relu; L.k = op.k; L.stride = op.stride; L.pt = g.pt; L.pl = g.pl;
+    return wgrad_layer(L, b.t, b.st, b.ws);
+}
+
+// stride 2: the (ReLU-masked) output gradient, zero-dilated to the input extent, in t->d_tmp2
+static int conv_dilate_dy(Backward& b, const Op& op, const ConvBack& g) {
+    const size_t bytes = (size_t)g.Hx * g.Wx * op.Cout * 4;
+    PSEG_TRY(b.t->d_tmp2.ensure(bytes));
+    const size_t n = bytes / 4;
+    dilate2_kernel<<<grid_1d(n, 8192), 256, 0, b.st>>>(b.t->d_tmp2.p, g.dY, g.maskY, g.Hy, g.Wy, op.Cout);
+    return PSEG_OK;
+}
+
+// dgrad into the gradient of source `sidx` (skipped for the network input)
+// = a stride-1 convolution of the (ReLU-masked, for stride 2 zero-dilated) output gradient dYd / maskd with the flipped
+// kernel at the conv's input extent.  Plain sources accumulate in place; an upsampled source gets the sum of
+// its 2x2 blocks, a pre-activation source the X > 0 mask -- both through a scratch tensor.
+static int conv_data_grad(Backward& b, const Op& op, const ConvBack& g, int sidx, const float* dYd, const float* maskd) {
+    Engine& e = b.e;
+    TrainState* t = b.t;
+    hipStream_t st = b.st;
+    const int src = sidx == 0 ? op.src0 : op.src1;
+    if (src == e.input_tensor) return PSEG_OK;
+    const Tensor& sx = e.tensors[src];
+    const int up = sidx == 0 ? op.up0 : op.up1;
+    const int k = op.k, c0 = sidx == 0 ? 0 : e.tensors[op.src0].C, nc = sx.C;
+    const bool direct = !up && !op.in_relu;
+    PSEG_TRY(b.ensure_wd((size_t)k * k * op.Cout * nc));
+    wd_conv_kernel<<<grid_1d((size_t)k * k * op.Cout * nc, 2048), 256, 0, st>>>(op.d_w, k, k, op.Cin, op.Cout, c0, nc, t->d_wd.p);   // (64 blocks took 49 us for unet's 4.7 M-element kernels)
+    if (!direct) PSEG_TRY(t->d_tmp.ensure((size_t)g.Hx * g.Wx * nc * 4));
+    ConvArgs a{};
+    a.src0 = dYd; a.C0 = op.Cout; a.Hin = op.stride == 2 ? g.Hx : g.Hy; a.Win = op.stride == 2 ? g.Wx : g.Wy;
+    a.w = t->d_wd.p; a.bias = nullptr; a.KH = a.KW = k; a.stride = 1;
+    if (const size_t wrb = wrem_bytes_for(k, k, op.Cout, nc)) {   // (the scratch kernel changes with every layer: no validity flag)
+        PSEG_TRY(t->d_wdrem.ensure(wrb));
+        a.wrem_buf = t->d_wdrem.p; a.wrem_cap = t->d_wdrem.cap;
+    }
+    a.pt = k - 1 - g.pt; a.pl = k - 1 - g.pl;
+    a.Hout = g.lg ? b.H : g.Hx; a.Wout = g.lg ? b.W : g.Wx; a.Cout = nc;
+    a.mask = maskd;
+    a.relaxed = b.relaxed;
+    a.dst = direct ? b.grad(src) : t->d_tmp.p;
+    // (the logits layer writes the page extent only: on a padded canvas the rest of the gradient must be zeros)
+    if (direct && g.lg && (b.H != g.Hx || b.W != g.Wx)) PSEG_TRY(b.zero_if_fresh(src));
+    a.add = (direct && !b.fresh[src]) ? b.grad(src) : nullptr;
+    if (direct) b.fresh[src] = 0; else PSEG_TRY(b.zero_if_fresh(src));
+    a.dst_pitch = g.Wx;
+    PSEG_TRY(launch_conv_exact(a, st));
+    if (!direct) {
+        const float* maskX = op.in_relu ? (const float*)sx.d : nullptr;
+        const size_t n = (size_t)e.tH(sx) * e.tW(sx) * nc;
+        const int grid = grid_1d(n, 8192);
+        if (up) upsample_bwd_kernel<<<grid, 256, 0, st>>>(b.grad(src), t->d_tmp.p, maskX, e.tH(sx), e.tW(sx), nc);
+        else accum_kernel<<<grid, 256, 0, st>>>(b.grad(src), t->d_tmp.p, nullptr, maskX, n);
+    }
+    PSEG_HIP(hipGetLastError());
+    return PSEG_OK;
+}
+
+static int backward_conv(Backward& b, const Op& op) {
+    Engine& e = b.e;
+    if (op.stride != 1 && op.stride != 2) return fail(PSEG_EUNSUPPORTED, "backward of layer %s (stride %d) is not built", op.layer.c_str(), op.stride);
+    const Tensor& s0 = e.tensors[op.src0];
+    ConvBack g;
+    g.lg = op.type == OP_LOGITS;
+    g.dY = g.lg ? b.t->d_dlogits.p : b.grad(op.dst);
+    g.maskY = (op.relu && !g.lg) ? (const float*)e.tensors[op.dst].d : nullptr;
+    g.Hy = g.lg ? b.H : e.tH(e.tensors[op.dst]); g.Wy = g.lg ? b.W : e.tW(e.tensors[op.dst]);
+    g.Hx = e.tH(s0) << op.up0; g.Wx = e.tW(s0) << op.up0;
+    wgrad_same_pad(g.lg, g.Hy, g.Wy, g.Hx, g.Wx, op.k, op.stride, &g.pt, &g.pl);
+    if (op.add >= 0) PSEG_TRY(conv_residual_grad(b, op, g));
+    PSEG_TRY(conv_weight_grad(b, op, g));
+    const float* dYd = g.dY;
+    const float* maskd = g.maskY;
+    if (op.stride == 2) {
+        PSEG_TRY(conv_dilate_dy(b, op, g));
+        dYd = b.t->d_tmp2.p;
+        maskd = nullptr;
+    }
+    for (int sidx = 0; sidx < (op.src1 >= 0 ? 2 : 1); ++sidx) PSEG_TRY(conv_data_grad(b, op, g, sidx, dYd, maskd));
+    return PSEG_OK;
+}
+
+// ---- k2 s2 transposed convs
+// dgrad into the gradient of source `sidx`
+// = a k2 stride-2 convolution of the (ReLU-masked) output gradient with wd[ab][co][c],
+// accumulated in place: the matrix-core kernel when its tile fits, else the scalar one
+static int deconv2_data_grad(Backward& b, const Op& op, int sidx, const float* dY, const float* Y, int Hx, int Wx) {
+    TrainState* t = b.t;
+    hipStream_t st = b.st;
+    const int src = sidx == 0 ? op.src0 : op.src1;
+    const int c0 = sidx == 0 ? 0 : b.e.tensors[op.src0].C, nc = b.e.tensors[src].C;
+    PSEG_TRY(b.ensure_wd((size_t)4 * op.Cout * nc));
+    wd_deconv_kernel<<<grid_1d((size_t)4 * op.Cout * nc, 2048), 256, 0, st>>>(op.d_w, op.Cin, op.Cout, c0, nc, t->d_wd.p);
+    ConvArgs c{};
+    c.src0 = dY; c.C0 = op.Cout; c.mask = op.relu ? Y : nullptr;
+    c.Hin = 2 * Hx; c.Win = 2 * Wx; c.Hout = Hx; c.Wout = Wx;
+    c.w = t->d_wd.p; c.KH = c.KW = 2; c.stride = 2; c.Cout = nc;
+    c.add = b.fresh[src] ? nullptr : b.grad(src); c.dst = b.grad(src);
+    c.relaxed = 1;
+    const int rc = launch_conv_exact_mfma(c, st);
+    if (rc < 0) return rc;
+    if (rc != 0) b.fresh[src] = 0;
+    if (rc == 0) {
+        PSEG_TRY(b.zero_if_fresh(src));
+        dim3 grid(cdiv(Hx * Wx, 256), cdiv(nc, COT));
+        deconv2_dgrad_kernel<<<grid, 256, 0, st>>>(dY, Y, op.relu, Hx, Wx, op.Cout, t->d_wd.p, nc, b.grad(src));
+    }
+    PSEG_HIP(hipGetLastError());
+    return PSEG_OK;
+}
+
+static int backward_deconv2(Backward& b, const Op& op) {
+    Engine& e = b.e;
+    TrainState* t = b.t;
+    const Tensor& s0 = e.tensors[op.src0];
+    const float* dY = b.grad(op.dst);
+    const float* Y = (const float*)e.tensors[op.dst].d;
+    const float* maskY = op.relu ? Y : nullptr;
+    const int Hx = e.tH(s0), Wx = e.tW(s0);
+    // both sources and the bias gradient in one pass over dY where the layer has an instance
+    WgradLayer L = op_wgrad_layer(b, op, 1, Hx, Wx, dY, maskY, 2 * Hx, 2 * Wx);
+    L.try_pair = true;
+    L.k = 2;
+    bool paired = false;
+    PSEG_TRY(wgrad_layer(L, t, b.st, b.ws, &paired));
+    if (!paired) {
+        if (op.Cout > 256) return fail(PSEG_EUNSUPPORTED, "bias gradient supports at most 256 channels");
+        PSEG_TRY(t->d_bpart.ensure((size_t)BG_BLOCKS * op.Cout * 8));
+        PSEG_TRY(b.dy_ready());
+        bias_grad_kernel<<<BG_BLOCKS, 256, 0, b.ws>>>(dY, maskY, (size_t)4 * Hx * Wx, op.Cout, t->d_bpart.p);
+        column_sum_kernel<double><<<op.Cout, 256, 0, b.ws>>>(t->d_bpart.p, BG_BLOCKS, op.Cout, L.dB);
+    }
+    PSEG_HIP(hipGetLastError());
+    for (int sidx = 0; sidx < (op.src1 >= 0 ? 2 : 1); ++sidx) PSEG_TRY(deconv2_data_grad(b, op, sidx, dY, Y, Hx, Wx));
+    return PSEG_OK;
+}
+
+// ---- BatchNormalization: dgamma / dbeta into this op's channel slice of the layer's gradient vectors, dx accumulated into the source
+static int backward_bn(Backward& b, const Op& op) {
+    Engine& e = b.e;
+    const Tensor& s0 = e.tensors[op.src0];
+    const float* Y = (const float*)e.tensors[op.dst].d;
+    if (op.src0 != e.input_tensor) PSEG_TRY(b.zero_if_fresh(op.src0));
+    return bn_backward((const float*)s0.d, op.relu ? Y : nullptr, b.grad(op.dst), op.src0 == e.input_tensor ? nullptr : b.grad(op.src0),
+                       (size_t)e.tH(s0) * e.tW(s0), op.Cin, op.d_w, op.d_b, b.param_grad(op.kparam) + op.bn_c0,
+                       b.param_grad(op.bparam) + op.bn_c0, b.st);
+}
+
+// ---- 2x2 max-pool
+static int backward_pool(Backward& b, const Op& op) {
+    Engine& e = b.e;
+    const Tensor& s0 = e.tensors[op.src0];
+    const size_t n = (size_t)(e.tH(s0) / 2) * (e.tW(s0) / 2) * s0.C;
+    pool_bwd_kernel<<<grid_1d(n, 8192), 256, 0, b.st>>>((const float*)s0.d, b.grad(op.dst), e.tH(s0), e.tW(s0), s0.C, b.grad(op.src0),
+                                                      (int)b.fresh[op.src0]);
+    b.fresh[op.src0] = 0;
+    PSEG_HIP(hipGetLastError());
+    return PSEG_OK;
 }
 
 // the compute part of the step on the page in t->d_img (uint8, or float32 on the 0..255 scale) and the mask in t->d_mask
 static int train_compute(Engine& e, int H, int W, bool backward, bool img_f32) {
     TrainState* t = TS(e);
     hipStream_t st = e.stream;
-    const int C = e.n_classes;
-    const size_t npx = (size_t)H * W;
-    e.cur_img_f32 = img_f32 ? (const float*)t->d_img : nullptr;
-    // Dropout layers are live in a training forward (Keras fit), the identity in an evaluation step
+    const int relaxed = PSEG_KNOB("PSEG_TRAIN_STRICT") ? 0 : 1;
     const uint32_t drop_key = backward ? (t->drop_seed * 0x632BE5ABu + (uint32_t)t->fwd_count * 0x9E3779B9u) | 1u : 0u;
     if (backward) ++t->fwd_count;
-    e.drop_key = drop_key;
-    e.bn_training = backward;   // Keras fit: BatchNormalization layers normalise with the batch statistics; evaluate / predict with the moving ones
-    e.relaxed_f32 = PSEG_KNOB("PSEG_TRAIN_STRICT") ? 0 : 1;   // wide layers: channel-blocked matrix-core kernel (summation order differs from predict)
-    const int rc_fwd = run_exact(e, t->d_img, t->d_logits, nullptr, nullptr, nullptr, st);
-    e.drop_key = 0;
-    e.bn_training = false;
-    e.relaxed_f32 = 0;
-    e.cur_img_f32 = nullptr;
-    PSEG_TRY(rc_fwd);
-    float* acc = t->d_grad + t->nparam;
-    // a backward pass starts from zeroed parameter gradients; an evaluation step only resets the metric slots
-    if (backward) PSEG_HIP(hipMemsetAsync(t->d_grad, 0, (size_t)t->nflat * 4, st));
-    else PSEG_HIP(hipMemsetAsync(acc, 0, (size_t)(t->nflat - t->nparam) * 4, st));
-    {
-        const int nblk = cdiv((int)npx, 256), nslot = 2 + 2 * C;
-        PSEG_TRY(ensure_buf((void**)&t->d_mpart, &t->mpart_bytes, (size_t)nblk * nslot * 4));
-        ce_metrics_kernel<<<nblk, 256, 0, st>>>(t->d_logits, t->d_mask, (int)npx, C, 1.0f / (float)npx, t->d_dlogits, t->d_mpart);
-        metrics_final_kernel<<<nslot, 256, 0, st>>>(t->d_mpart, nblk, nslot, acc);
-    }
-    if (t->loss_kind != PSEG_LOSS_CE)
-        loss_grad_kernel<<<cdiv((int)npx, 256), 256, 0, st>>>(t->loss_kind, t->d_logits, t->d_mask, (int)npx, C, 1.0f / (float)npx,
-                                                            acc, t->d_dlogits, acc + 2 + 2 * PSEG_MAXC);
-    PSEG_HIP(hipGetLastError());
+    PSEG_TRY(train_forward(e, t, drop_key, backward, relaxed, img_f32));
+    PSEG_TRY(train_loss_metrics(e, t, H, W, backward));
     if (!backward) return PSEG_OK;
 
-    // tensor gradients (canvas dims).  They are not zeroed: the first consumer met on the way back STORES its contribution
-    // (fresh[i]), the later ones accumulate -- a memset per tensor and a read of the zeros by the first writer were 0.3 ms of a
-    // 15 ms step.  Writers without a store form (and a gradient nobody wrote before it is read) zero the buffer first.
-    std::vector<char> fresh(e.tensors.size(), 1);
-    auto tbytes_of = [&](int i) { const Tensor& tn = e.tensors[i]; return (size_t)e.tH(tn) * e.tW(tn) * tn.C * 4; };
-    auto zero_if_fresh = [&](int i) -> int {
-        if (i >= 0 && fresh[i]) { PSEG_HIP(hipMemsetAsync(t->tgrad[i], 0, tbytes_of(i), st)); fresh[i] = 0; }
-        return PSEG_OK;
-    };
-    for (size_t i = 0; i < e.tensors.size(); ++i) {
-        if ((int)i == e.input_tensor) continue;
-        const Tensor& tn = e.tensors[i];
-        const size_t bytes = (size_t)e.tH(tn) * e.tW(tn) * tn.C * 4;
-        if (bytes > t->tbytes[i]) {
-            (void)hipFree(t->tgrad[i]);
-            t->tgrad[i] = nullptr;
-            PSEG_HIP(hipMalloc((void**)&t->tgrad[i], bytes));
-            t->tbytes[i] = bytes;
-            // a new buffer starts as NaNs (once, not per step): a region no writer covers then shows in every gradient
-            // test instead of depending on what the allocator hands back
-            PSEG_HIP(hipMemsetAsync(t->tgrad[i], 0xFF, bytes, st));
-        }
-    }
-    auto ensure_wd = [&](size_t floats) -> int {
-        return ensure_buf((void**)&t->d_wd, &t->wd_bytes, (floats + COT) * 4);
-    };
-    const bool scalar_wgrad = false;
-    // Second stream for the weight gradients.  A layer's weight gradient and its data gradient both only READ the layer's output
-    // gradient, and nothing downstream of a weight gradient runs before the optimizer: the weight-gradient kernels (and their
-    // ordered reductions) go to `ws`, gated by an event recorded on the main stream once dY is final; the main stream carries on
-    // with the data gradients and joins at the end.  Two MFMA-bound kernels of 65-85 % pipe-busy each fill each other's gaps.
-    hipStream_t ws = st;
-    if (!PSEG_KNOB("PSEG_TRAIN_ONE_STREAM")) {
-        if (!t->wstream) {
-            PSEG_HIP(hipStreamCreateWithFlags(&t->wstream, hipStreamNonBlocking));
-            PSEG_HIP(hipEventCreateWithFlags(&t->ev_dy, hipEventDisableTiming));
-            PSEG_HIP(hipEventCreateWithFlags(&t->ev_wdone, hipEventDisableTiming));
-        }
-        ws = t->wstream;
-    }
-    // every way out of this function -- also an early error return -- leaves the main stream waiting for what was enqueued on `ws`:
-    // the next step's zeroing of the gradient buffer and its forward must not overtake weight-gradient kernels still in flight
-    struct Join {
-        hipStream_t ws, st; hipEvent_t ev; bool done = false;
-        void now() { if (!done && ws != st && ev) { (void)hipEventRecord(ev, ws); (void)hipStreamWaitEvent(st, ev, 0); } done = true; }
-        ~Join() { now(); }
-    } join{ws, st, t->ev_wdone};
-    auto dy_ready = [&]() -> int {      // everything enqueued on the main stream so far is visible to the next kernel on ws
-        if (ws != st) { PSEG_HIP(hipEventRecord(t->ev_dy, st)); PSEG_HIP(hipStreamWaitEvent(ws, t->ev_dy, 0)); }
-        return PSEG_OK;
-    };
-
+    Backward b{e, t, st, st, H, W, drop_key, relaxed, std::vector<char>(e.tensors.size(), 1)};
+    PSEG_TRY(size_tensor_grads(b));
+    PSEG_TRY(open_weight_stream(b));
+    Join join{b.ws, st, t->ev_wdone};
     for (int oi = (int)e.ops.size() - 1; oi >= 0; --oi) {
-        Op& op = e.ops[oi];
-        const Tensor& s0 = e.tensors[op.src0];
-        const Tensor* s1 = op.src1 >= 0 ? &e.tensors[op.src1] : nullptr;
-        const int C0 = s0.C, C1 = s1 ? s1->C : 0;
-        float* gw = op.kparam >= 0 ? t->d_grad + t->off[op.kparam] : nullptr;
-        float* gb = op.bparam >= 0 ? t->d_grad + t->off[op.bparam] : nullptr;
-        if (op.type != OP_LOGITS) PSEG_TRY(zero_if_fresh(op.dst));   // (a tensor nothing consumed: its gradient is zero)
+        const Op& op = e.ops[oi];
+        if (op.type != OP_LOGITS) PSEG_TRY(b.zero_if_fresh(op.dst));   // (a tensor nothing consumed: its gradient is zero)
         if (op.dropout > 0.0f && drop_key) {   // same mask and scale as the forward, on the gradient of the dropped tensor
             const Tensor& d = e.tensors[op.dst];
-            launch_dropout(t->tgrad[op.dst], (size_t)e.tH(d) * e.tW(d) * d.C, drop_key + 0x85EBCA77u * (uint32_t)oi, op.dropout, st);
+            launch_dropout(b.grad(op.dst), (size_t)e.tH(d) * e.tW(d) * d.C, drop_key + 0x85EBCA77u * (uint32_t)oi, op.dropout, st);
         }
-        if (op.type == OP_LOGITS || op.type == OP_CONV) {
-            if (op.stride != 1 && op.stride != 2) return fail(PSEG_EUNSUPPORTED, "backward of layer %s (stride %d) is not built", op.layer.c_str(), op.stride);
-            const bool lg = op.type == OP_LOGITS;
-            const float* dY = lg ? t->d_dlogits : t->tgrad[op.dst];
-            const float* Y = lg ? nullptr : (const float*)e.tensors[op.dst].d;
-            const float* maskY = (op.relu && Y) ? Y : nullptr;
-            const int Hy = lg ? H : e.tH(e.tensors[op.dst]), Wy = lg ? W : e.tW(e.tensors[op.dst]);
-            // extent of the conv's input: both concat sources share it (a half-resolution source is read through up0 / up1)
-            const int Hx = e.tH(s0) << op.up0, Wx = e.tW(s0) << op.up0;
-            const int k = op.k, st_ = op.stride;
-            int pt = 0, pl = 0;
-            wgrad_same_pad(lg, Hy, Wy, Hx, Wx, k, st_, &pt, &pl);
-            // residual addend (Add() after the bias): its gradient is the layer's output gradient
-            if (op.add >= 0) {
-                const Tensor& ad = e.tensors[op.add];
-                const size_t n = (size_t)e.tH(ad) * e.tW(ad) * ad.C;
-                PSEG_TRY(zero_if_fresh(op.add));
-                accum_kernel<<<(int)std::min<size_t>((n + 255) / 256, 8192), 256, 0, st>>>(t->tgrad[op.add], dY, maskY, nullptr, n);
-            }
-            // ---- wgrad + bias grad ----
-            bool paired = false;
-            if (lg && !scalar_wgrad) {   // the 1x1 logits layer: both sources and the bias in one pass over dY
-                const WgradArgs a = wgrad_pair_args(0, (const float*)s0.d, C0, s1 ? (const float*)s1->d : nullptr, C1, Hx, Wx, Wx, op.in_relu,
-                                                    dY, maskY, Hy, Wy, op.Cout, op.Cin, k, pt, pl, gw, gb);
-                WgradFlatPlan pp;
-                if (!op.up0 && !op.up1 && st_ == 1 && wgrad_pair_plan(a, k * k, &pp)) {
-                    PSEG_TRY(dy_ready());
-                    PSEG_TRY(launch_wgrad(a, dim3(1, k * k), ws, &t->d_wpart, &t->wpart_bytes));
-                    paired = true;
-                }
-            }
-            for (int sidx = 0; sidx < (paired ? 0 : (s1 ? 2 : 1)); ++sidx) {
-                const Tensor& sx = sidx == 0 ? s0 : *s1;
-                const int up = sidx == 0 ? op.up0 : op.up1;
-                const WgradArgs a = wgrad_conv_args((const float*)sx.d, sx.C, sidx == 0 ? 0 : C0, Hx, Wx, Wx >> up, up, st_, op.in_relu,
-                                                    dY, maskY, Hy, Wy, op.Cout, op.Cin, k, pt, pl, gw, sidx == 0 ? gb : nullptr);
-                dim3 grid(cdiv(Hy, a.strip_rows), k * k);
-                PSEG_TRY(dy_ready());
-                PSEG_TRY(launch_wgrad(a, grid, ws, &t->d_wpart, &t->wpart_bytes));
-            }
-            // ---- dgrad into the source gradients (skipped for the network input) ----
-            // = a stride-1 convolution of the (ReLU-masked, for stride 2 zero-dilated) output gradient with the flipped
-            // kernel at the conv's input extent.  Plain sources accumulate in place; an upsampled source gets the sum of
-            // its 2x2 blocks, a pre-activation source the X > 0 mask -- both through a scratch tensor.
-            const float* dYd = dY;
-            const float* maskd = maskY;
-            if (st_ == 2) {
-                const size_t bytes = (size_t)Hx * Wx * op.Cout * 4;
-                PSEG_TRY(ensure_buf((void**)&t->d_tmp2, &t->tmp2_bytes, bytes));
-                const size_t n = bytes / 4;
-                dilate2_kernel<<<(int)std::min<size_t>((n + 255) / 256, 8192), 256, 0, st>>>(t->d_tmp2, dY, maskY, Hy, Wy, op.Cout);
-                dYd = t->d_tmp2;
-                maskd = nullptr;
-            }
-            for (int sidx = 0; sidx < (s1 ? 2 : 1); ++sidx) {
-                const int src = sidx == 0 ? op.src0 : op.src1;
-                if (src == e.input_tensor) continue;
-                const int up = sidx == 0 ? op.up0 : op.up1;
-                const int c0 = sidx == 0 ? 0 : C0, nc = sidx == 0 ? C0 : C1;
-                const bool direct = !up && !op.in_relu;
-                PSEG_TRY(ensure_wd((size_t)k * k * op.Cout * nc));
-                wd_conv_kernel<<<(int)std::min<size_t>(((size_t)k * k * op.Cout * nc + 255) / 256, 2048), 256, 0, st>>>(op.d_w, k, k, op.Cin, op.Cout, c0, nc, t->d_wd);   // (64 blocks took 49 us for unet's 4.7 M-element kernels)
-                if (!direct) PSEG_TRY(ensure_buf((void**)&t->d_tmp, &t->tmp_bytes, (size_t)Hx * Wx * nc * 4));
-                ConvArgs a{};
-                a.src0 = dYd; a.C0 = op.Cout; a.Hin = st_ == 2 ? Hx : Hy; a.Win = st_ == 2 ? Wx : Wy;
-                a.w = t->d_wd; a.bias = nullptr; a.KH = a.KW = k; a.stride = 1;
-                if (const size_t wrb = wrem_bytes_for(k, k, op.Cout, nc)) {   // (the scratch kernel changes with every layer: no validity flag)
-                    PSEG_TRY(ensure_buf((void**)&t->d_wdrem, &t->wdrem_bytes, wrb));
-                    a.wrem_buf = t->d_wdrem; a.wrem_cap = t->wdrem_bytes;
-                }
-                a.pt = k - 1 - pt; a.pl = k - 1 - pl;
-                a.Hout = lg ? H : Hx; a.Wout = lg ? W : Wx; a.Cout = nc;
-                a.mask = maskd;
-                a.relaxed = PSEG_KNOB("PSEG_TRAIN_STRICT") ? 0 : 1;
-                a.dst = direct ? t->tgrad[src] : t->d_tmp;
-                // (the logits layer writes the page extent only: on a padded canvas the rest of the gradient must be zeros)
-                if (direct && lg && (H != Hx || W != Wx)) PSEG_TRY(zero_if_fresh(src));
-                a.add = (direct && !fresh[src]) ? t->tgrad[src] : nullptr;
-                if (direct) fresh[src] = 0; else PSEG_TRY(zero_if_fresh(src));
-                a.dst_pitch = Wx;
-                PSEG_TRY(launch_conv_exact(a, st));
-                if (!direct) {
-                    const Tensor& sx = e.tensors[src];
-                    const float* maskX = op.in_relu ? (const float*)sx.d : nullptr;
-                    const size_t n = (size_t)e.tH(sx) * e.tW(sx) * nc;
-                    const int g = (int)std::min<size_t>((n + 255) / 256, 8192);
-                    if (up) upsample_bwd_kernel<<<g, 256, 0, st>>>(t->tgrad[src], t->d_tmp, maskX, e.tH(sx), e.tW(sx), nc);
-                    else accum_kernel<<<g, 256, 0, st>>>(t->tgrad[src], t->d_tmp, nullptr, maskX, n);
-                }
-                PSEG_HIP(hipGetLastError());
-            }
-        } else if (op.type == OP_DECONV2) {
-            const float* dY = t->tgrad[op.dst];
-            const float* Y = (const float*)e.tensors[op.dst].d;
-            const int Hx = e.tH(s0), Wx = e.tW(s0);
-            bool paired = false;
-            if (!scalar_wgrad) {   // both sources and the bias gradient in one pass over dY
-                const WgradArgs a = wgrad_pair_args(1, (const float*)s0.d, C0, s1 ? (const float*)s1->d : nullptr, C1, Hx, Wx, Wx, 0,
-                                                    dY, op.relu ? Y : nullptr, 2 * Hx, 2 * Wx, op.Cout, op.Cin, 2, 0, 0, gw, gb);
-                WgradFlatPlan pp;
-                if (wgrad_pair_plan(a, 4, &pp)) {
-                    PSEG_TRY(dy_ready());
-                    PSEG_TRY(launch_wgrad(a, dim3(1, 4), ws, &t->d_wpart, &t->wpart_bytes));
-                    paired = true;
-                }
-            }
-            for (int sidx = 0; sidx < (paired ? 0 : (s1 ? 2 : 1)); ++sidx) {
-                const Tensor& sx = sidx == 0 ? s0 : *s1;
-                const WgradArgs a = wgrad_deconv_args((const float*)sx.d, sx.C, sidx == 0 ? 0 : C0, Hx, Wx, Wx, dY, op.relu ? Y : nullptr,
-                                                      op.Cout, op.Cin, gw);
-                dim3 grid(cdiv(Hx, a.strip_rows), 4);
-                PSEG_TRY(dy_ready());
-                PSEG_TRY(launch_wgrad(a, grid, ws, &t->d_wpart, &t->wpart_bytes));
-            }
-            if (!paired) {
-            if (op.Cout > 256) return fail(PSEG_EUNSUPPORTED, "bias gradient supports at most 256 channels");
-            PSEG_TRY(ensure_buf((void**)&t->d_bpart, &t->bpart_bytes, (size_t)BG_BLOCKS * op.Cout * 8));
-            PSEG_TRY(dy_ready());
-            bias_grad_kernel<<<BG_BLOCKS, 256, 0, ws>>>(dY, op.relu ? Y : nullptr, (size_t)4 * Hx * Wx, op.Cout, (double*)t->d_bpart);
-            column_sum_kernel<double><<<op.Cout, 256, 0, ws>>>((const double*)t->d_bpart, BG_BLOCKS, op.Cout, gb);
-            }
-            PSEG_HIP(hipGetLastError());
-            for (int sidx = 0; sidx < (s1 ? 2 : 1); ++sidx) {
-                const int src = sidx == 0 ? op.src0 : op.src1;
-                const int c0 = sidx == 0 ? 0 : C0, nc = sidx == 0 ? C0 : C1;
-                PSEG_TRY(ensure_wd((size_t)4 * op.Cout * nc));
-                wd_deconv_kernel<<<(int)std::min<size_t>(((size_t)4 * op.Cout * nc + 255) / 256, 2048), 256, 0, st>>>(op.d_w, op.Cin, op.Cout, c0, nc, t->d_wd);
-                // = a k2 stride-2 convolution of the (ReLU-masked) output gradient with wd[ab][co][c],
-                // accumulated in place: the matrix-core kernel when its tile fits, else the scalar one
-                ConvArgs c{};
-                c.src0 = dY; c.C0 = op.Cout; c.mask = op.relu ? Y : nullptr;
-                c.Hin = 2 * Hx; c.Win = 2 * Wx; c.Hout = Hx; c.Wout = Wx;
-                c.w = t->d_wd; c.KH = c.KW = 2; c.stride = 2; c.Cout = nc;
-                c.add = fresh[src] ? nullptr : t->tgrad[src]; c.dst = t->tgrad[src];
-                c.relaxed = 1;
-                const int rc = launch_conv_exact_mfma(c, st);
-                if (rc < 0) return rc;
-                if (rc != 0) fresh[src] = 0;
-                if (rc == 0) {
-                    PSEG_TRY(zero_if_fresh(src));
-                    dim3 grid(cdiv(Hx * Wx, 256), cdiv(nc, COT));
-                    deconv2_dgrad_kernel<<<grid, 256, 0, st>>>(dY, Y, op.relu, Hx, Wx, op.Cout, t->d_wd, nc, t->tgrad[src]);
-                }
-                PSEG_HIP(hipGetLastError());
-            }
-        } else if (op.type == OP_BN) {
-            // dgamma / dbeta into this op's channel slice of the layer's gradient vectors, dx accumulated into the source
-            const float* Y = (const float*)e.tensors[op.dst].d;
-            if (op.src0 != e.input_tensor) PSEG_TRY(zero_if_fresh(op.src0));
-            PSEG_TRY(bn_backward((const float*)s0.d, op.relu ? Y : nullptr, t->tgrad[op.dst],
-                                 op.src0 == e.input_tensor ? nullptr : t->tgrad[op.src0], (size_t)e.tH(s0) * e.tW(s0), op.Cin, op.d_w,
-                                 op.d_b, gw + op.bn_c0, gb + op.bn_c0, st));
-        } else if (op.type == OP_POOL) {
-            const size_t n = (size_t)(e.tH(s0) / 2) * (e.tW(s0) / 2) * s0.C;
-            pool_bwd_kernel<<<(int)std::min<size_t>((n + 255) / 256, 8192), 256, 0, st>>>(
-                (const float*)s0.d, t->tgrad[op.dst], e.tH(s0), e.tW(s0), s0.C, t->tgrad[op.src0], (int)fresh[op.src0]);
-            fresh[op.src0] = 0;
-            PSEG_HIP(hipGetLastError());
+        switch (op.type) {
+            case OP_LOGITS:
+            case OP_CONV: PSEG_TRY(backward_conv(b, op)); break;
+            case OP_DECONV2: PSEG_TRY(backward_deconv2(b, op)); break;
+            case OP_BN: PSEG_TRY(backward_bn(b, op)); break;
+            case OP_POOL: PSEG_TRY(backward_pool(b, op)); break;
+            default: break;
         }
     }
-    (void)producer_of;
     join.now();   // the optimizer / all-reduce / readers see every gradient
     return PSEG_OK;
 }
@@ -1541,21 +1568,21 @@ static int train_augment(Engine& e, const uint8_t* img, const uint8_t* mask, int
     TrainState* t = TS(e);
     hipStream_t st = e.stream;
     const size_t npx = (size_t)H * W;
-    auto grow = [](void** p, size_t* cap, size_t bytes) -> int {
-        if (ensure_buf(p, cap, bytes) == PSEG_OK) return PSEG_OK;
+    auto grow = [](auto& buf, size_t bytes) -> int {
+        if (buf.ensure(bytes) == PSEG_OK) return PSEG_OK;
         const std::string why = last_error();
         return fail(PSEG_ENOMEM, "augmentation buffer of %zu bytes: %s", bytes, why.c_str());
     };
-    PSEG_TRY(grow((void**)&t->d_img, &t->img_bytes, npx * e.in_ch * 4));
-    PSEG_TRY(grow((void**)&t->d_mask, &t->mask_bytes, npx));
-    PSEG_TRY(grow((void**)&t->d_aug_img, &t->aug_img_bytes, npx * e.in_ch));
-    PSEG_TRY(grow((void**)&t->d_aug_mask, &t->aug_mask_bytes, npx));
-    PSEG_TRY(grow((void**)&t->d_aug_mm, &t->aug_mm_bytes, 8));
-    if (m) PSEG_TRY(grow((void**)&t->d_aug_coef, &t->aug_coef_bytes, augment_coef_count(H, W, image_fill) * 8));
-    PSEG_HIP(hipMemcpyAsync(t->d_aug_img, img, npx * e.in_ch, hipMemcpyHostToDevice, st));
-    PSEG_HIP(hipMemcpyAsync(t->d_aug_mask, mask, npx, hipMemcpyHostToDevice, st));
-    const AugSample a{t->d_aug_img, t->d_aug_mask, H, W, e.in_ch, m, off, flips, image_fill, mask_fill, image_cval, mask_cval,
-                      use_brightness, brightness, t->d_aug_coef, t->d_aug_mm, (float*)t->d_img, t->d_mask};
+    PSEG_TRY(grow(t->d_img, npx * e.in_ch * 4));
+    PSEG_TRY(grow(t->d_mask, npx));
+    PSEG_TRY(grow(t->d_aug_img, npx * e.in_ch));
+    PSEG_TRY(grow(t->d_aug_mask, npx));
+    PSEG_TRY(grow(t->d_aug_mm, 8));
+    if (m) PSEG_TRY(grow(t->d_aug_coef, augment_coef_count(H, W, image_fill) * 8));
+    PSEG_HIP(hipMemcpyAsync(t->d_aug_img.p, img, npx * e.in_ch, hipMemcpyHostToDevice, st));
+    PSEG_HIP(hipMemcpyAsync(t->d_aug_mask.p, mask, npx, hipMemcpyHostToDevice, st));
+    const AugSample a{t->d_aug_img.p, t->d_aug_mask.p, H, W, e.in_ch, m, off, flips, image_fill, mask_fill, image_cval, mask_cval,
+                      use_brightness, brightness, t->d_aug_coef.p, t->d_aug_mm.p, (float*)t->d_img.p, t->d_mask.p};
     return augment_sample_device(a, st);
 }
 
@@ -1598,8 +1625,7 @@ static int train_apply(Engine& e, float lr, float gscale) {
     PSEG_HIP(hipSetDevice(e.device));
     hipStream_t st = e.stream;
     t->step += 1;
-    OptScalars o_{};
-    OptScalars& o = o_;
+    OptScalars o{};
     o.lr = lr; o.b1 = t->beta1; o.b2 = t->beta2; o.eps = t->eps;
     const double b1t = std::pow((double)t->beta1, (double)t->step), b2t = std::pow((double)t->beta2, (double)t->step);
     if (t->optimizer == PSEG_OPT_ADAM) o.lr = (float)(lr * std::sqrt(1.0 - b2t) / (1.0 - b1t));
@@ -1652,13 +1678,13 @@ static int train_apply(Engine& e, float lr, float gscale) {
             for (int which = 0; which < 2; ++which, ++slice) {
                 const int pi = which == 0 ? op.kparam : op.bparam;
                 const int64_t n = bn ? op.Cin : (int64_t)e.params[pi].host.size();
-                const int64_t o = t->off[pi] + (bn ? op.bn_c0 : 0);
-                float* g = t->d_grad + o;
+                const int64_t at = t->off[pi] + (bn ? op.bn_c0 : 0);
+                float* g = t->d_grad + at;
                 float* p = bn ? op.d_w + which * op.Cin : (which == 0 ? op.d_w : op.d_b);
                 const int grid = (int)std::min<int64_t>((n + 255) / 256, SUMSQ_MAXB);
                 if (pass == 0) sumsq_kernel<<<grid, 256, 0, st>>>(g, n, gscale, t->d_part + (size_t)slice * SUMSQ_MAXB);
-                else opt_kernel<<<grid, 256, 0, st>>>(t->optimizer, p, g, t->d_m + o, t->d_v + o, n, gscale,
-                                                     t->d_norm + pi, t->clipnorm, t->clipvalue, o_);
+                else opt_kernel<<<grid, 256, 0, st>>>(t->optimizer, p, g, t->d_m + at, t->d_v + at, n, gscale,
+                                                     t->d_norm + pi, t->clipnorm, t->clipvalue, o);
             }
         }
         if (pass == 0) sumsq_final_kernel<<<t->nslices, 256, 0, st>>>(t->d_part, t->d_slice_nblk, t->d_slice_pi, t->d_norm);
@@ -1798,8 +1824,8 @@ int pseg_train_augment_sample(pseg_engine* h, const uint8_t* img, const uint8_t*
     PSEG_TRY(train_augment(e, img, mask, H, W, m, off, flips, image_fill_mode, image_cval, mask_fill_mode, mask_cval,
                            use_brightness, brightness));
     const size_t npx = (size_t)H * W;
-    PSEG_HIP(hipMemcpyAsync(out_img, t->d_img, npx * e.in_ch * 4, hipMemcpyDeviceToHost, e.stream));
-    PSEG_HIP(hipMemcpyAsync(out_mask, t->d_mask, npx, hipMemcpyDeviceToHost, e.stream));
+    PSEG_HIP(hipMemcpyAsync(out_img, t->d_img.p, npx * e.in_ch * 4, hipMemcpyDeviceToHost, e.stream));
+    PSEG_HIP(hipMemcpyAsync(out_mask, t->d_mask.p, npx, hipMemcpyDeviceToHost, e.stream));
     PSEG_HIP(hipStreamSynchronize(e.stream));
     return PSEG_OK;
 }
@@ -1858,31 +1884,23 @@ int pseg_train_wgrad_layer(pseg_engine* h, const pseg_wgrad_layer* L, pseg_wgrad
     }
     if (L->xpitch < (L->Wx >> up)) return fail(PSEG_EINVAL, "xpitch %d is shorter than a row", L->xpitch);
     PSEG_HIP(hipSetDevice(e.device));
-    int pt = 0, pl = 0;
-    if (L->mode == 0) wgrad_same_pad(lg, L->Hy, L->Wy, L->Hx, L->Wx, k, L->stride, &pt, &pl);
-    // the train step's order: the one-pass form where the layer has an instance, else one source per launch
-    WgradArgs a{};
-    dim3 grid(1, k * k);
-    bool paired = false;
-    if (L->mode == 1 || lg) {
-        a = wgrad_pair_args(L->mode, L->X, L->XC0, L->X1, L->XC1, L->Hx, L->Wx, L->xpitch, L->in_relu, L->dY, L->maskY, L->Hy, L->Wy,
-                            L->Cout, L->Cin, k, pt, pl, L->dW, L->dB);
-        WgradFlatPlan pp;
-        paired = wgrad_pair_plan(a, k * k, &pp, L->slots);
-    }
-    if (!paired) {
+    // the train step's routine: the one-pass form where the layer has an instance, else one source per launch
+    WgradLayer wl;
+    wl.mode = L->mode;
+    wl.try_pair = L->mode == 1 || lg;
+    wl.nsrc = L->X1 ? 2 : 1;
+    wl.X[0] = L->X; wl.XC[0] = L->XC0; wl.X[1] = L->X1; wl.XC[1] = L->XC1;
+    wl.xup[0] = wl.xup[1] = up; wl.xpitch[0] = wl.xpitch[1] = L->xpitch;
+    wl.ci0 = L->ci0; wl.Hx = L->Hx; wl.Wx = L->Wx; wl.in_relu = L->in_relu;
+    wl.dY = L->dY; wl.maskY = L->maskY; wl.Hy = L->Hy; wl.Wy = L->Wy; wl.Cout = L->Cout; wl.Cin = L->Cin;
+    wl.k = k; wl.stride = L->stride; wl.dW = L->dW; wl.dB = L->dB;
+    if (L->mode == 0) wgrad_same_pad(lg, L->Hy, L->Wy, L->Hx, L->Wx, k, L->stride, &wl.pt, &wl.pl);
+    WgradArgs pair_args{};
+    if (!wgrad_layer_pairs(wl, L->slots, &pair_args)) {
         if (L->X1) return fail(PSEG_EINVAL, "no two-source weight-gradient instance for this layer: one source per call");
-        if (L->mode == 1) {
-            if (L->dB) return fail(PSEG_EINVAL, "the bias gradient of this transposed conv is not part of its weight-gradient launch");
-            a = wgrad_deconv_args(L->X, L->XC0, L->ci0, L->Hx, L->Wx, L->xpitch, L->dY, L->maskY, L->Cout, L->Cin, L->dW);
-        } else {
-            a = wgrad_conv_args(L->X, L->XC0, L->ci0, L->Hx, L->Wx, L->xpitch, up, L->stride, L->in_relu, L->dY, L->maskY, L->Hy, L->Wy,
-                                L->Cout, L->Cin, k, pt, pl, L->dW, L->dB);
-        }
-        if (L->strip_rows > 0) a.strip_rows = L->strip_rows;
-        grid = dim3(cdiv(L->mode == 1 ? L->Hx : L->Hy, a.strip_rows), k * k);
+        if (L->mode == 1 && L->dB) return fail(PSEG_EINVAL, "the bias gradient of this transposed conv is not part of its weight-gradient launch");
     }
-    PSEG_TRY(launch_wgrad(a, grid, e.stream, &t->d_wpart, &t->wpart_bytes, L->slots, ran));
+    PSEG_TRY(wgrad_layer(wl, t, e.stream, e.stream, nullptr, L->slots, L->strip_rows, ran));
     PSEG_HIP(hipStreamSynchronize(e.stream));
     return PSEG_OK;
 }

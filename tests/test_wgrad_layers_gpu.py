@@ -31,8 +31,8 @@ compared with every reported plan):
   * flat instances with KYN == 1 (conv6, conv7, deconv1, deconv3; min_rows = 2): (b).  One group is reached only when one piece
     per group already gave one row per strip, and then one group gives one row per strip as well.
   * pair: nothing; their cases are five pieces wide because with three pieces (f) is out of reach.
-The kernels of pseg_train.hip take strip_rows from the caller: their cases pass it.  V_SCALAR (wgrad_kernel) is unreachable --
-`scalar` in launch_wgrad is a constant false -- and has no case.
+The kernels of pseg_train.hip take strip_rows from the caller: their cases pass it.  Every variant launch_wgrad can choose
+(PAIR, FLAT / BLK, C1, KX5, TAP, WIDE) has a case.
 """
 import numpy as np
 import pytest
