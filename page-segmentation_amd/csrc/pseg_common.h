@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -119,7 +120,7 @@ int run_pipeline(Stage& g, int nu, const PipeSet* set, hipStream_t s_in, hipStre
 }
 
 // Knobs.  Two kinds, one lookup (PSEG_KNOB):
-//   * ENVIRONMENT knobs -- the PSEG_ENV_KNOBS list below, fourteen names, documented in README.md: operational choices a deployment
+//   * ENVIRONMENT knobs -- the PSEG_ENV_KNOBS list below, thirteen names, documented in README.md: operational choices a deployment
 //     may make (page-unit size, the persistent kernel families off, checks, logging).  Nothing else in the process environment
 //     reaches the release library.
 //   * PLAN SWITCHES -- alternative kernel / fusion choices that must not change results beyond the documented bars; every one is
@@ -140,8 +141,7 @@ int run_pipeline(Stage& g, int nu, const PipeSet* set, hipStream_t s_in, hipStre
 // not even hold the names).
 #define PSEG_ENV_KNOBS                                                                                                          \
     "PSEG_BATCH_PAGES", "PSEG_NO_PAGE_BATCH", "PSEG_GENERIC", "PSEG_NO_SP", "PSEG_NO_PP", "PSEG_NO_WS", "PSEG_SP_CHECK",        \
-    "PSEG_EXACT_TAU", "PSEG_EXACT_FULL", "PSEG_TRAIN_ONE_STREAM", "PSEG_TRAIN_STRICT", "PSEG_LOG_GENERIC", "PSEG_LOG_SP",       \
-    "PSEG_CCL_GLOBAL"
+    "PSEG_EXACT_TAU", "PSEG_EXACT_FULL", "PSEG_TRAIN_ONE_STREAM", "PSEG_LOG_GENERIC", "PSEG_LOG_SP", "PSEG_CCL_GLOBAL"
 #ifndef PSEG_DIAG
 #define PSEG_DIAG 0
 #endif
@@ -177,6 +177,29 @@ constexpr int PSEG_CHAIN_BLOCK = 16;   // float32 mode: input channels per pass 
 constexpr int PSEG_MAXC = 64;   // classes the train-step metric slots and the wide bf16 logits kernel are sized for
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline int round_up(int a, int b) { return cdiv(a, b) * b; }
+// TF SAME padding in front of one axis: pad_total = max((out - 1) * stride + k - in, 0), before = total / 2; a stride-1 Conv2DTranspose runs
+// as a convolution with the flipped kernel, where "before" and "after" swap (odd k: equal)
+static inline int same_pad(int out, int in, int k, int stride, bool transposed) {
+    const int total = std::max((out - 1) * stride + k - in, 0);
+    return transposed ? total - total / 2 : total / 2;
+}
+// What a launcher that may decline a layer answers: PSEG_OK (launched), ROUTE_NO (not a layer for this route: ask the next), or an
+// error (< 0).  The bf16 routes of mfma_launch_conv and the float32 routes of launch_conv_exact / forward_deconv2 share it.
+constexpr int ROUTE_NO = 1;
+// Every kernel with dynamic LDS is launched here: the CU's whole 160 KB allowed once per device and kernel instance, the launch, its
+// error.  dev < 0: the current device is looked up.  `more`: the kernel's arguments behind its record.
+template <auto KERNEL, typename Arg, typename... More>
+int launch_lds(const Arg& a, dim3 grid, unsigned threads, size_t lds, int dev, hipStream_t st, More... more) {
+    static bool attr_set[64] = {false};
+    if (dev < 0) PSEG_HIP(hipGetDevice(&dev));
+    if (!attr_set[dev & 63]) {
+        PSEG_HIP(hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        attr_set[dev & 63] = true;
+    }
+    KERNEL<<<grid, threads, lds, st>>>(a, more...);
+    PSEG_HIP(hipGetLastError());
+    return PSEG_OK;
+}
 // crop / tile halo: >= the receptive-field radius of the graph (fcn / fcn_skip: 75 pixels counting the one-sided growth of the
 // 2x2 pools; unet ~122, res_unet ~124), a multiple of 32.  Shared by the label-exact mode's crops and the tile plan.
 static inline int halo_of(int arch) { return (arch == PSEG_ARCH_FCN_SKIP || arch == PSEG_ARCH_FCN) ? 96 : 160; }
@@ -303,7 +326,6 @@ struct Engine {
     void* batch = nullptr;   // BatchState (pseg_engine.hip), freed by pseg_destroy
     void* chain = nullptr;   // ChainState (pseg_chain.hip), freed by chain_free; chain_trim frees the page list's staging memory
     void* dist = nullptr;    // DistState (pseg_allreduce_init): RCCL communicator of the data-parallel train step
-    int relaxed_f32 = 0;     // != 0 during a train / eval step: wide float32 layers may run channel-blocked on the matrix cores
     uint32_t drop_key = 0;   // != 0 while a TRAINING forward runs: Dropout layers are live (key = seed / step mix)
     const float* cur_img_f32 = nullptr;   // float32 exact mode: float page (0..255 scale) instead of the uint8 one (augmented training samples)
     int* d_sp_err = nullptr;   // bf16 mode: the give-up record of conv_sp_kernel's bounded counter waits (8 ints: code, wave, need, have,
@@ -335,7 +357,7 @@ struct ConvArgs {
     int deconv4;         // MFMA kernel only: Conv2DTranspose k2 s2 as one GEMM, n = ab*Cout + co -> (2y + a, 2x + b)
     int dbg;             // MFMA kernel only: timing experiments (PSEG_XM_DBG: 1 no staging loads, 2 no stores, 4 no k-loop) -- wrong results
     float* pool_dst;     // blocked MFMA kernel, 8-row tiles only: also store the 2x2 max-pool of the output ((Hout/2) x (Wout/2) x Cout)
-    int relaxed;         // MFMA kernel only: the caller accepts a channel-blocked summation order (train step) for layers whose all-channel tile does not fit LDS
+    int unused_;         // read by nothing: holds the place of a retired field, so that every compiled kernel keeps its argument layout
     const float* wrem = nullptr;   // blocked MFMA kernel, set by its launcher: the left-over output channels' kernel, shifted copies [KH][KW + DX - 1][Cin][16] (conv_xb_kernel REM)
     float* wrem_buf = nullptr;     // caller-owned buffer for that kernel (wrem_bytes_for() bytes; null or too small: padded cout tiles instead)
     size_t wrem_cap = 0;
@@ -343,9 +365,11 @@ struct ConvArgs {
 };
 // bytes of ConvArgs.wrem_buf a KH x KW, Cin -> Cout stride-1 layer needs for its left-over channel tile, 0 when it has none
 size_t wrem_bytes_for(int KH, int KW, int Cin, int Cout);
-int launch_conv_exact(const ConvArgs& a, hipStream_t st, bool* pooled = nullptr);   // *pooled: ConvArgs.pool_dst was written by the conv kernel
+// Asks its routes in order -- first-layer vector ALU, matrix core, 1x1, scalar -- and always launches: PSEG_OK or an error.
+// *pooled: ConvArgs.pool_dst was written by the conv kernel (else the caller pools).
+int launch_conv_exact(const ConvArgs& a, hipStream_t st, bool* pooled = nullptr);
 // HBM-bound float32 layers on the vector ALU (pseg_exact_valu.hip): first layer; Conv2DTranspose k2 s2, optionally with the
-// logits layer + argmax behind it.  1 = launched, 0 = not a layer for these kernels, < 0 error.
+// logits layer + argmax behind it.  PSEG_OK / ROUTE_NO / error.
 struct TailArgs {
     const float* src0; const float* src1; int C0, C1, Hin, Win;
     const float* w; const float* bias; int Cout, relu;
@@ -357,7 +381,7 @@ struct TailArgs {
 };
 int launch_conv_first_valu(const ConvArgs& a, hipStream_t st);
 int launch_deconv2_valu(const TailArgs& a, bool tail, hipStream_t st);
-int launch_conv_exact_mfma(const ConvArgs& a, hipStream_t st);   // 1 launched, 0 does not fit, < 0 error
+int launch_conv_exact_mfma(const ConvArgs& a, hipStream_t st, bool* pooled = nullptr);   // matrix cores (pseg_exact_mfma.hip): PSEG_OK / ROUTE_NO / error
 // split form of UpSampling2D(2) -> Conv2D(k2) (pseg_upsplit.hip)
 struct UpSplit;
 int upsplit_create(UpSplit** out, const std::vector<float>& w, const std::vector<float>& bias, int Cin, int Cs0, int Cout, int CoS);

@@ -411,33 +411,22 @@ static void free_dev(void*& p) {
     p = nullptr;
 }
 
-// Upload weights in correlation form.  Conv2D: as is.  Conv2DTranspose s1 (kh,kw,Cout,Cin):
-// Wc[ky][kx][ci][co] = K[KH-1-ky][KW-1-kx][co][ci].  Conv2DTranspose k2 s2: [a][b][ci][co] =
-// K[a][b][co][ci].
-int launch_conv_exact(const ConvArgs& a, hipStream_t st, bool* pooled) {
-    // matrix-core path (same bits, see pseg_exact_mfma.hip)
-    if (pooled) *pooled = false;
-    const int rv = a.pool_dst ? 0 : launch_conv_first_valu(a, st);     // 1 or 3 input channels: HBM-bound, vector ALU
-    if (rv != 0) return rv < 0 ? rv : PSEG_OK;
-    const int rc = launch_conv_exact_mfma(a, st);
-    if (rc != 0) {
-        if (pooled) *pooled = rc == 2;
-        return rc < 0 ? rc : PSEG_OK;
-    }
+// a plain 1x1 layer of at most 127 input channels (the logits layer): a row's pixels through LDS, conv1x1_exact_kernel
+static int launch_conv1x1_exact(const ConvArgs& a, hipStream_t st) {
     const int Cin = a.C0 + a.C1;
-    if (a.KH == 1 && a.KW == 1 && a.stride == 1 && !a.pt && !a.pl && !a.up0 && !a.up1 && !a.in_relu && !a.mask && Cin <= 127) {
-        static bool attr_set[64] = {false};
-        int dev = 0;
-        PSEG_HIP(hipGetDevice(&dev));
-        if (!attr_set[dev & 63]) {
-            PSEG_HIP(hipFuncSetAttribute((const void*)conv1x1_exact_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            attr_set[dev & 63] = true;
-        }
-        dim3 g1(cdiv(a.Wout, 256), a.Hout, cdiv(a.Cout, COT));
-        conv1x1_exact_kernel<<<g1, 256, (size_t)256 * (Cin + 1) * sizeof(float), st>>>(a);
-        PSEG_HIP(hipGetLastError());
-        return PSEG_OK;
-    }
+    if (a.KH != 1 || a.KW != 1 || a.stride != 1 || a.pt || a.pl || a.up0 || a.up1 || a.in_relu || a.mask || Cin > 127) return ROUTE_NO;
+    const dim3 grid(cdiv(a.Wout, 256), a.Hout, cdiv(a.Cout, COT));
+    return launch_lds<conv1x1_exact_kernel>(a, grid, 256, (size_t)256 * (Cin + 1) * sizeof(float), -1, st);
+}
+
+// The routes of a float32 convolution, in the order they are asked (all give the same bits): the first layer on the vector ALU
+// (1 or 3 input channels: HBM-bound), the matrix cores (pseg_exact_mfma.hip), the 1x1 kernel, and the scalar kernel, which takes anything.
+int launch_conv_exact(const ConvArgs& a, hipStream_t st, bool* pooled) {
+    if (pooled) *pooled = false;
+    int rc;
+    if ((rc = launch_conv_first_valu(a, st)) != ROUTE_NO) return rc;
+    if ((rc = launch_conv_exact_mfma(a, st, pooled)) != ROUTE_NO) return rc;
+    if ((rc = launch_conv1x1_exact(a, st)) != ROUTE_NO) return rc;
     dim3 grid(cdiv(a.Hout * a.Wout, 256), cdiv(a.Cout, COT));
     conv_exact_kernel<<<grid, 256, 0, st>>>(a);
     PSEG_HIP(hipGetLastError());
@@ -473,6 +462,9 @@ static int upload_bn(Engine& e, Op& op) {
     return PSEG_OK;
 }
 
+// Upload weights in correlation form.  Conv2D: as is.  Conv2DTranspose s1 (kh,kw,Cout,Cin):
+// Wc[ky][kx][ci][co] = K[KH-1-ky][KW-1-kx][co][ci].  Conv2DTranspose k2 s2: [a][b][ci][co] =
+// K[a][b][co][ci].
 int upload_weights(Engine& e) {
     // the copies below are ordered on the null stream only: earlier asynchronous predicts must have finished
     PSEG_HIP(hipDeviceSynchronize());
@@ -657,192 +649,228 @@ bool page_slot_fits(Engine& e, int H, int W) {
     return !page_slot_room(e, H, W, &per_slot, &room) || per_slot <= room;
 }
 
+// ---- the float32 forward pass: one function per layer kind, run_exact dispatches
+// One run: where its outputs go (each optional), and the two things one layer hands to a later one.
+struct ExactRun {
+    Engine& e;
+    float* logits; float* probs; int64_t* labels; uint8_t* labels_u8;
+    hipStream_t st;
+    const Op* skip_pool = nullptr;      // the OP_POOL a conv's epilogue has already written
+    const Op* fused_logits = nullptr;   // the OP_LOGITS that ran, with the argmax, inside the transposed conv in front of it
+};
+
+static const Op* next_op(const Engine& e, const Op& op) { return &op + 1 < e.ops.data() + e.ops.size() ? &op + 1 : nullptr; }
+
+// the concatenated sources of a layer, their extent, its kernel and bias: the head of ConvArgs, TailArgs and DeconvArgs alike
+template <class Args>
+static void fill_sources(const Engine& e, const Op& op, Args& a) {
+    const Tensor& s0 = e.tensors[op.src0];
+    const Tensor* s1 = op.src1 >= 0 ? &e.tensors[op.src1] : nullptr;
+    a.src0 = (const float*)s0.d; a.src1 = s1 ? (const float*)s1->d : nullptr;
+    a.C0 = s0.C; a.C1 = s1 ? s1->C : 0;
+    a.Hin = e.tH(s0); a.Win = e.tW(s0);
+    a.w = op.d_w; a.bias = op.d_b;
+}
+
+// the caller's logits buffer, else the engine's scratch one (H x W x C float32)
+static int logits_or_tmp(Engine& e, float* d_logits, int C, float** out) {
+    if (!d_logits) {
+        PSEG_TRY(e.logits_tmp.ensure((size_t)e.H * e.W * C * sizeof(float), "logits"));
+        d_logits = e.logits_tmp.as<float>();
+    }
+    *out = d_logits;
+    return PSEG_OK;
+}
+
+static void launch_softmax_argmax(const float* logits, size_t n, int C, float* probs, int64_t* labels, uint8_t* labels_u8, hipStream_t st) {
+    softmax_argmax_kernel<<<(int)std::min<size_t>((n + 255) / 256, 8192), 256, 0, st>>>(logits, n, C, probs, labels, labels_u8);
+}
+
+static void forward_preprocess(ExactRun& r, const uint8_t* d_img) {
+    Engine& e = r.e;
+    const Tensor& in = e.tensors[e.input_tensor];
+    const size_t n = (size_t)e.Hp * e.Wp * in.C;
+    const int grid = (int)std::min<size_t>((n + 255) / 256, 4096);
+    if (e.cur_img_f32) preprocess_exact_f32_kernel<<<grid, 256, 0, r.st>>>(e.cur_img_f32, e.H, e.W, in.C, (float*)in.d, e.Hp, e.Wp);
+    else preprocess_exact_kernel<<<grid, 256, 0, r.st>>>(d_img, e.H, e.W, in.C, e.d_lut, (float*)in.d, e.Hp, e.Wp);
+}
+
+// what OP_CONV and OP_LOGITS share; the output (extent, padding, pointer) is the caller's
+static ConvArgs conv_args(const Engine& e, Op& op) {
+    ConvArgs a{};
+    fill_sources(e, op, a);
+    a.up0 = op.up0; a.up1 = op.up1;
+    a.Hin <<= op.up0; a.Win <<= op.up0;
+    a.KH = a.KW = op.k;
+    a.stride = op.stride;
+    a.in_relu = op.in_relu; a.relu = op.relu;
+    a.Cout = op.Cout;
+    a.wrem_buf = op.d_wrem; a.wrem_cap = op.wrem_bytes; a.wrem_valid = &op.wrem_valid;
+    return a;
+}
+
+static int forward_conv(ExactRun& r, Op& op) {
+    Engine& e = r.e;
+    const Tensor& d = e.tensors[op.dst];
+    ConvArgs a = conv_args(e, op);
+    a.Hout = e.tH(d); a.Wout = e.tW(d);
+    a.pt = same_pad(a.Hout, a.Hin, op.k, op.stride, op.transposed);
+    a.pl = same_pad(a.Wout, a.Win, op.k, op.stride, op.transposed);
+    a.add = op.add >= 0 ? (const float*)e.tensors[op.add].d : nullptr;
+    a.dst = (float*)d.d;
+    // MaxPooling2D right behind this layer (every encoder stage of fcn / unet) can be pooled in the conv's epilogue
+    // (measured, fcn_skip 2048x1536: the fused form saves the pool passes -- 91 + 27 + 13 us -- and costs the three
+    // producers 84 + 40 + 12 us in their epilogues: no gain, so the separate streaming pass stays the default;
+    // PSEG_EXACT_POOL_FUSE=1 selects the fused form, tests keep both bit-identical)
+    const Op* nx = next_op(e, op);
+    const bool want_pool = nx && nx->type == OP_POOL && nx->src0 == op.dst && op.add < 0 && !(e.drop_key && op.dropout > 0.0f) &&
+                           PSEG_KNOB("PSEG_EXACT_POOL_FUSE");
+    if (want_pool) a.pool_dst = (float*)e.tensors[nx->dst].d;
+    bool pooled = false;
+    PSEG_TRY(launch_conv_exact(a, r.st, &pooled));
+    r.skip_pool = pooled ? nx : nullptr;
+    return PSEG_OK;
+}
+
+// the crop (lib/model.py:29-42) is folded into the output extent: the input stays the padded canvas, output (y, x) reads input (y, x)
+static int forward_logits(ExactRun& r, Op& op) {
+    Engine& e = r.e;
+    if (&op == r.fused_logits) return PSEG_OK;
+    ConvArgs a = conv_args(e, op);
+    a.Hout = e.H; a.Wout = e.W;
+    PSEG_TRY(logits_or_tmp(e, r.logits, op.Cout, &a.dst));
+    PSEG_TRY(launch_conv_exact(a, r.st));
+    if (r.probs || r.labels || r.labels_u8) launch_softmax_argmax(a.dst, (size_t)e.H * e.W, op.Cout, r.probs, r.labels, r.labels_u8, r.st);
+    return PSEG_OK;
+}
+
+// The logits layer that can run behind this transposed conv in deconv2_valu_kernel, on the values still in registers: the
+// conv's only reader (fcn_skip / fcn: deconv5), 1x1, at most 8 classes over 20 channels, its skip source at the same scale.
+static const Op* tail_logits_of(const Engine& e, const Op& op) {
+    const Op* nx = next_op(e, op);
+    if (!nx || nx->type != OP_LOGITS || nx->src0 != op.dst || nx->k != 1 || op.relu || op.Cout != 20 || nx->Cout > 8) return nullptr;
+    if ((e.drop_key && op.dropout > 0.0f) || PSEG_KNOB("PSEG_EXACT_NO_TAIL_FUSE")) return nullptr;
+    if (nx->src1 >= 0 && e.tensors[nx->src1].s != e.tensors[op.dst].s) return nullptr;
+    return nx;
+}
+
+// stage 1 of forward_deconv2: the vector-ALU kernel with the logits layer `nx` and the argmax behind it
+static int deconv2_with_tail(ExactRun& r, const Op* nx, TailArgs& ta) {
+    Engine& e = r.e;
+    if (!nx) return ROUTE_NO;
+    const Tensor* sk = nx->src1 >= 0 ? &e.tensors[nx->src1] : nullptr;
+    ta.skip = sk ? (const float*)sk->d : nullptr; ta.Cs = sk ? sk->C : 0;
+    ta.wl = nx->d_w; ta.bl = nx->d_b; ta.ncls = nx->Cout; ta.H = e.H; ta.W = e.W;
+    if (r.logits || r.probs) PSEG_TRY(logits_or_tmp(e, r.logits, nx->Cout, &ta.logits));
+    ta.labels = r.labels; ta.labels_u8 = r.labels_u8;
+    const int rc = launch_deconv2_valu(ta, true, r.st);
+    if (rc != PSEG_OK) return rc;
+    r.fused_logits = nx;
+    if (r.probs) launch_softmax_argmax(ta.logits, (size_t)e.H * e.W, nx->Cout, r.probs, nullptr, nullptr, r.st);
+    return PSEG_OK;
+}
+
+// stage 3: Conv2DTranspose k2 s2 as one GEMM on the matrix cores, n = ab * Cout + co -> (2y + a, 2x + b)
+static ConvArgs deconv2_gemm_args(const Engine& e, const Op& op) {
+    ConvArgs c{};
+    fill_sources(e, op, c);
+    c.Hout = c.Hin; c.Wout = c.Win;
+    c.KH = c.KW = 1;
+    c.stride = 1;
+    c.Cout = op.Cout;
+    c.relu = op.relu;
+    c.dst = (float*)e.tensors[op.dst].d;
+    c.dst_pitch = 2 * c.Win;
+    c.deconv4 = 1;
+    return c;
+}
+
+// Conv2DTranspose k2 s2 is HBM-bound: one output pixel per thread on the vector ALU (pseg_exact_valu.hip), with the logits layer
+// behind it where there is one; then the same kernel alone, the matrix-core GEMM form, and the scalar kernel.
+static int forward_deconv2(ExactRun& r, Op& op) {
+    Engine& e = r.e;
+    TailArgs ta{};
+    fill_sources(e, op, ta);
+    ta.Cout = op.Cout; ta.relu = op.relu;
+    ta.dst = (float*)e.tensors[op.dst].d;
+    int rc;
+    if ((rc = deconv2_with_tail(r, tail_logits_of(e, op), ta)) != ROUTE_NO) return rc;
+    if ((rc = launch_deconv2_valu(ta, false, r.st)) != ROUTE_NO) return rc;
+    if ((rc = launch_conv_exact_mfma(deconv2_gemm_args(e, op), r.st)) != ROUTE_NO) return rc;
+    DeconvArgs a{};
+    fill_sources(e, op, a);
+    a.dst = ta.dst;
+    a.Cout = op.Cout; a.relu = op.relu;
+    dim3 grid(cdiv(a.Hin * a.Win, 256), cdiv(op.Cout, COT), 4);
+    deconv2_exact_kernel<<<grid, 256, 0, r.st>>>(a);
+    return PSEG_OK;
+}
+
+static int forward_bn(ExactRun& r, Op& op) {
+    Engine& e = r.e;
+    const Tensor& s0 = e.tensors[op.src0];
+    const size_t npx = (size_t)e.tH(s0) * e.tW(s0);
+    float* y = (float*)e.tensors[op.dst].d;
+    if (e.bn_training) return bn_train_forward((const float*)s0.d, y, npx, op.Cin, op.d_w, op.d_b, op.relu, op.up0, r.st);
+    return bn_infer((const float*)s0.d, y, npx, op.Cin, op.d_w, op.d_b, op.relu, r.st);
+}
+
+static int forward_pool(ExactRun& r, Op& op) {
+    Engine& e = r.e;
+    if (&op == r.skip_pool) return PSEG_OK;   // done in the producing conv's epilogue
+    const Tensor& s0 = e.tensors[op.src0];
+    const size_t n = (size_t)(e.tH(s0) / 2) * (e.tW(s0) / 2) * s0.C;
+    pool_exact_kernel<<<(int)std::min<size_t>((n + 255) / 256, 8192), 256, 0, r.st>>>((const float*)s0.d, e.tH(s0), e.tW(s0), s0.C, (float*)e.tensors[op.dst].d);
+    return PSEG_OK;
+}
+
+// training forward: Dropout on this op's output, in place
+static void forward_dropout(ExactRun& r, const Op& op) {
+    Engine& e = r.e;
+    if (!e.drop_key || !(op.dropout > 0.0f)) return;
+    const Tensor& d = e.tensors[op.dst];
+    launch_dropout((float*)d.d, (size_t)e.tH(d) * e.tW(d) * d.C, e.drop_key + 0x85EBCA77u * (uint32_t)(&op - e.ops.data()), op.dropout, r.st);
+}
+
 int run_exact(Engine& e, const uint8_t* d_img, float* d_logits, float* d_probs,
                      int64_t* d_labels, uint8_t* d_labels_u8, hipStream_t st) {
-    Tensor& in = e.tensors[e.input_tensor];
-    {
-        const size_t n = (size_t)e.Hp * e.Wp * in.C;
-        const int grid = (int)std::min<size_t>((n + 255) / 256, 4096);
-        if (e.cur_img_f32)
-            preprocess_exact_f32_kernel<<<grid, 256, 0, st>>>(e.cur_img_f32, e.H, e.W, in.C, (float*)in.d, e.Hp, e.Wp);
-        else
-            preprocess_exact_kernel<<<grid, 256, 0, st>>>(d_img, e.H, e.W, in.C, e.d_lut, (float*)in.d,
-                                                          e.Hp, e.Wp);
-    }
-    const Op* skip_pool = nullptr;
-    const Op* fused_logits = nullptr;
+    ExactRun r{e, d_logits, d_probs, d_labels, d_labels_u8, st};
+    forward_preprocess(r, d_img);
     for (auto& op : e.ops) {
         hipEvent_t ev0;
         PSEG_TRY(time_begin(e, op, st, &ev0));
-        const Tensor& s0 = e.tensors[op.src0];
-        const Tensor* s1 = op.src1 >= 0 ? &e.tensors[op.src1] : nullptr;
-        if (&op == fused_logits) {
-            // logits + argmax ran inside the transposed conv in front of it
-        } else if (op.type == OP_CONV || op.type == OP_LOGITS) {
-            ConvArgs a{};
-            a.src0 = (const float*)s0.d;
-            a.src1 = s1 ? (const float*)s1->d : nullptr;
-            a.C0 = s0.C;
-            a.C1 = s1 ? s1->C : 0;
-            a.up0 = op.up0;
-            a.up1 = op.up1;
-            a.Hin = e.tH(s0) << op.up0;
-            a.Win = e.tW(s0) << op.up0;
-            a.w = op.d_w;
-            a.bias = op.d_b;
-            a.KH = a.KW = op.k;
-            a.stride = op.stride;
-            a.in_relu = op.in_relu;
-            a.relu = op.relu;
-            a.Cout = op.Cout;
-            a.relaxed = e.relaxed_f32;
-            a.wrem_buf = op.d_wrem; a.wrem_cap = op.wrem_bytes; a.wrem_valid = &op.wrem_valid;
-            if (op.type == OP_LOGITS) {
-                // crop (lib/model.py:29-42) folded into the output extent
-                a.Hout = e.H;
-                a.Wout = e.W;
-                a.pt = a.pl = 0;
-                float* zl = d_logits;
-                if (!zl) {
-                    PSEG_TRY(e.logits_tmp.ensure((size_t)e.H * e.W * op.Cout * sizeof(float), "logits"));
-                    zl = e.logits_tmp.as<float>();
-                }
-                a.dst = zl;
-                // the kernel indexes src rows with Win: rows of the padded canvas
-                // logical input dims stay the canvas; output (y,x) reads input (y,x)
-                PSEG_TRY(launch_conv_exact(a, st));
-                if (d_probs || d_labels || d_labels_u8) {
-                    const size_t n = (size_t)e.H * e.W;
-                    const int g2 = (int)std::min<size_t>((n + 255) / 256, 8192);
-                    softmax_argmax_kernel<<<g2, 256, 0, st>>>(zl, n, op.Cout, d_probs, d_labels,
-                                                             d_labels_u8);
-                }
-            } else {
-                const Tensor& d = e.tensors[op.dst];
-                a.Hout = e.tH(d);
-                a.Wout = e.tW(d);
-                // TF SAME: pad_total = max((out-1)*s + k - in, 0); before = total / 2
-                const int tot_h = std::max((a.Hout - 1) * op.stride + op.k - a.Hin, 0);
-                const int tot_w = std::max((a.Wout - 1) * op.stride + op.k - a.Win, 0);
-                a.pt = tot_h / 2;
-                a.pl = tot_w / 2;
-                if (op.transposed) {  // flipped kernel: "before" and "after" swap (odd k: equal)
-                    a.pt = tot_h - a.pt;
-                    a.pl = tot_w - a.pl;
-                }
-                a.add = op.add >= 0 ? (const float*)e.tensors[op.add].d : nullptr;
-                a.dst = (float*)d.d;
-                // MaxPooling2D right behind this layer (every encoder stage of fcn / unet): pooled in the conv's epilogue
-                const Op* nx = (&op + 1 < e.ops.data() + e.ops.size()) ? &op + 1 : nullptr;
-                // (measured, fcn_skip 2048x1536: the fused form saves the pool passes -- 91 + 27 + 13 us -- and costs the three
-                // producers 84 + 40 + 12 us in their epilogues: no gain, so the separate streaming pass stays the default;
-                // PSEG_EXACT_POOL_FUSE=1 selects the fused form, tests keep both bit-identical)
-                const bool want_pool = nx && nx->type == OP_POOL && nx->src0 == op.dst && op.add < 0 && !(e.drop_key && op.dropout > 0.0f) &&
-                                       PSEG_KNOB("PSEG_EXACT_POOL_FUSE");
-                if (want_pool) a.pool_dst = (float*)e.tensors[nx->dst].d;
-                bool pooled = false;
-                PSEG_TRY(launch_conv_exact(a, st, &pooled));
-                skip_pool = pooled ? nx : nullptr;
-            }
-        } else if (op.type == OP_BN) {
-            const size_t npx = (size_t)e.tH(s0) * e.tW(s0);
-            float* y = (float*)e.tensors[op.dst].d;
-            if (e.bn_training) PSEG_TRY(bn_train_forward((const float*)s0.d, y, npx, op.Cin, op.d_w, op.d_b, op.relu, op.up0, st));
-            else PSEG_TRY(bn_infer((const float*)s0.d, y, npx, op.Cin, op.d_w, op.d_b, op.relu, st));
-        } else if (op.type == OP_DECONV2) {
-            // Conv2DTranspose k2 s2: HBM-bound -- one output pixel per thread on the vector ALU (pseg_exact_valu.hip); when
-            // its only reader is the logits layer (fcn_skip / fcn: deconv5), that layer and the argmax run in the same
-            // kernel on the values still in registers.  Fallbacks: the matrix-core GEMM form, then the scalar kernel.
-            bool done = false;
-            {
-                TailArgs ta{};
-                ta.src0 = (const float*)s0.d; ta.src1 = s1 ? (const float*)s1->d : nullptr;
-                ta.C0 = s0.C; ta.C1 = s1 ? s1->C : 0; ta.Hin = e.tH(s0); ta.Win = e.tW(s0);
-                ta.w = op.d_w; ta.bias = op.d_b; ta.Cout = op.Cout; ta.relu = op.relu;
-                ta.dst = (float*)e.tensors[op.dst].d;
-                const Op* nx = (&op + 1 < e.ops.data() + e.ops.size()) ? &op + 1 : nullptr;
-                bool tail = nx && nx->type == OP_LOGITS && nx->src0 == op.dst && nx->k == 1 && !op.relu && op.Cout == 20 && nx->Cout <= 8 &&
-                            !(e.drop_key && op.dropout > 0.0f) && !PSEG_KNOB("PSEG_EXACT_NO_TAIL_FUSE");
-                if (tail) {
-                    const Tensor* sk = nx->src1 >= 0 ? &e.tensors[nx->src1] : nullptr;
-                    if (sk && sk->s != e.tensors[op.dst].s) tail = false;
-                    if (tail) {
-                        ta.skip = sk ? (const float*)sk->d : nullptr; ta.Cs = sk ? sk->C : 0;
-                        ta.wl = nx->d_w; ta.bl = nx->d_b; ta.ncls = nx->Cout; ta.H = e.H; ta.W = e.W;
-                        float* zl = d_logits;
-                        if (!zl && d_probs) {
-                            PSEG_TRY(e.logits_tmp.ensure((size_t)e.H * e.W * nx->Cout * sizeof(float), "logits"));
-                            zl = e.logits_tmp.as<float>();
-                        }
-                        ta.logits = zl; ta.labels = d_labels; ta.labels_u8 = d_labels_u8;
-                    }
-                }
-                int rv = launch_deconv2_valu(ta, tail, st);
-                if (rv == 0 && tail) { tail = false; rv = launch_deconv2_valu(ta, false, st); }
-                if (rv < 0) return rv;
-                done = rv == 1;
-                if (done && tail) {
-                    fused_logits = nx;
-                    if (d_probs) {
-                        const size_t n = (size_t)e.H * e.W;
-                        softmax_argmax_kernel<<<(int)std::min<size_t>((n + 255) / 256, 8192), 256, 0, st>>>(ta.logits, n, nx->Cout, d_probs, nullptr, nullptr);
-                    }
-                }
-            }
-            if (!done) {
-                ConvArgs c{};
-                c.src0 = (const float*)s0.d;
-                c.src1 = s1 ? (const float*)s1->d : nullptr;
-                c.C0 = s0.C;
-                c.C1 = s1 ? s1->C : 0;
-                c.Hin = c.Hout = e.tH(s0);
-                c.Win = c.Wout = e.tW(s0);
-                c.w = op.d_w;
-                c.bias = op.d_b;
-                c.KH = c.KW = 1;
-                c.stride = 1;
-                c.Cout = op.Cout;
-                c.relu = op.relu;
-                c.dst = (float*)e.tensors[op.dst].d;
-                c.dst_pitch = 2 * c.Win;
-                c.deconv4 = 1;
-                c.relaxed = e.relaxed_f32;
-                const int rc = launch_conv_exact_mfma(c, st);
-                if (rc < 0) return rc;
-                done = rc == 1;
-            }
-            if (!done) {
-            DeconvArgs a{};
-            a.src0 = (const float*)s0.d;
-            a.src1 = s1 ? (const float*)s1->d : nullptr;
-            a.C0 = s0.C;
-            a.C1 = s1 ? s1->C : 0;
-            a.Hin = e.tH(s0);
-            a.Win = e.tW(s0);
-            a.w = op.d_w;
-            a.bias = op.d_b;
-            a.dst = (float*)e.tensors[op.dst].d;
-            a.Cout = op.Cout;
-            a.relu = op.relu;
-            dim3 grid(cdiv(a.Hin * a.Win, 256), cdiv(op.Cout, COT), 4);
-            deconv2_exact_kernel<<<grid, 256, 0, st>>>(a);
-            }
-        } else if (op.type == OP_POOL && &op == skip_pool) {
-            // done in the producing conv's epilogue
-        } else if (op.type == OP_POOL) {
-            const size_t n = (size_t)(e.tH(s0) / 2) * (e.tW(s0) / 2) * s0.C;
-            const int grid = (int)std::min<size_t>((n + 255) / 256, 8192);
-            pool_exact_kernel<<<grid, 256, 0, st>>>((const float*)s0.d, e.tH(s0), e.tW(s0), s0.C,
-                                                    (float*)e.tensors[op.dst].d);
+        switch (op.type) {
+            case OP_CONV: PSEG_TRY(forward_conv(r, op)); break;
+            case OP_LOGITS: PSEG_TRY(forward_logits(r, op)); break;
+            case OP_DECONV2: PSEG_TRY(forward_deconv2(r, op)); break;
+            case OP_BN: PSEG_TRY(forward_bn(r, op)); break;
+            case OP_POOL: PSEG_TRY(forward_pool(r, op)); break;
         }
-        if (e.drop_key && op.dropout > 0.0f) {   // training forward: Dropout on this op's output, in place
-            const Tensor& d = e.tensors[op.dst];
-            launch_dropout((float*)d.d, (size_t)e.tH(d) * e.tW(d) * d.C, e.drop_key + 0x85EBCA77u * (uint32_t)(&op - e.ops.data()), op.dropout, st);
-        }
+        forward_dropout(r, op);
         PSEG_HIP(hipGetLastError());
         PSEG_TRY(time_end(e, op, st, ev0));
     }
     return PSEG_OK;
+}
+
+// one live op of the bf16 graph on the tensors of the page slot in use, with its timing pair
+static int bf16_launch_op(Engine& e, Op& op, float* d_logits, float* d_probs, int64_t* d_labels, uint8_t* d_labels_u8, hipStream_t st) {
+    hipEvent_t ev0;
+    PSEG_TRY(time_begin(e, op, st, &ev0));
+    switch (op.type) {
+        case OP_CONV: PSEG_TRY(mfma_launch_conv(e, op, st)); break;
+        case OP_DECONV2: PSEG_TRY(mfma_launch_deconv2(e, op, st)); break;
+        case OP_POOL: PSEG_TRY(mfma_launch_pool(e, op, st)); break;
+        case OP_BN: {
+            const Tensor& s0 = e.tensors[op.src0];
+            PSEG_TRY(bn_infer_bf16((const uint16_t*)s0.d, (uint16_t*)e.tensors[op.dst].d, (size_t)e.tH(s0) * e.tW(s0), s0.Cs, op.d_w, op.relu, st));
+            break;
+        }
+        case OP_LOGITS: PSEG_TRY(mfma_launch_logits(e, op, d_logits, d_probs, d_labels, d_labels_u8, st)); break;
+        default: return fail(PSEG_EUNSUPPORTED, "unknown op type (layer %s)", op.layer.c_str());
+    }
+    PSEG_HIP(hipGetLastError());
+    return time_end(e, op, st, ev0);
 }
 
 static int run_bf16(Engine& e, const uint8_t* d_img, float* d_logits, float* d_probs,
@@ -850,36 +878,14 @@ static int run_bf16(Engine& e, const uint8_t* d_img, float* d_logits, float* d_p
     PSEG_TRY(mfma_preprocess(e, d_img, st));
     e.cur_margin = d_margin;
     e.margin_done = false;
-    if (d_margin && !d_logits && !mfma_tail_emits_margin(e)) {
-        // this graph's tail kernel has no margin output: take the float32 logits and derive the margin from them
-        PSEG_TRY(e.logits_tmp.ensure((size_t)e.H * e.W * e.n_classes * sizeof(float), "logits"));
-        d_logits = e.logits_tmp.as<float>();
-    }
+    // a graph whose tail kernel has no margin output: take the float32 logits and derive the margin from them
+    if (d_margin && !mfma_tail_emits_margin(e)) PSEG_TRY(logits_or_tmp(e, d_logits, e.n_classes, &d_logits));
     e.cur_logits = d_logits;
     e.cur_probs = d_probs;
     e.cur_labels = d_labels;
     e.cur_labels_u8 = d_labels_u8;
-    for (auto& op : e.ops) {
-        if (op.fused_away) continue;
-        hipEvent_t ev0;
-        PSEG_TRY(time_begin(e, op, st, &ev0));
-        switch (op.type) {
-            case OP_CONV: PSEG_TRY(mfma_launch_conv(e, op, st)); break;
-            case OP_DECONV2: PSEG_TRY(mfma_launch_deconv2(e, op, st)); break;
-            case OP_POOL: PSEG_TRY(mfma_launch_pool(e, op, st)); break;
-            case OP_BN: {
-                const Tensor& s0 = e.tensors[op.src0];
-                PSEG_TRY(bn_infer_bf16((const uint16_t*)s0.d, (uint16_t*)e.tensors[op.dst].d, (size_t)e.tH(s0) * e.tW(s0), s0.Cs,
-                                       op.d_w, op.relu, st));
-                break;
-            }
-            case OP_LOGITS:
-                PSEG_TRY(mfma_launch_logits(e, op, d_logits, d_probs, d_labels, d_labels_u8, st));
-                break;
-        }
-        PSEG_HIP(hipGetLastError());
-        PSEG_TRY(time_end(e, op, st, ev0));
-    }
+    for (auto& op : e.ops)
+        if (!op.fused_away) PSEG_TRY(bf16_launch_op(e, op, d_logits, d_probs, d_labels, d_labels_u8, st));
     if (d_margin && !e.margin_done) {
         if (!d_logits) return fail(PSEG_EINVAL, "margin map requested but neither the tail kernel nor a logits buffer provides it");
         launch_margin_from_logits(d_logits, (size_t)e.H * e.W, e.n_classes, d_margin, st);
@@ -906,24 +912,7 @@ static int run_bf16_pages(Engine& e, const uint8_t* d_imgs, int n, int64_t* d_la
         e.cur_labels = d_labels ? d_labels + (size_t)p * npx : nullptr;
         e.cur_labels_u8 = d_labels_u8 ? d_labels_u8 + (size_t)p * npx : nullptr;
     };
-    auto launch = [&](Op& op) -> int {
-        hipEvent_t ev0;
-        PSEG_TRY(time_begin(e, op, st, &ev0));
-        switch (op.type) {
-            case OP_CONV: PSEG_TRY(mfma_launch_conv(e, op, st)); break;
-            case OP_DECONV2: PSEG_TRY(mfma_launch_deconv2(e, op, st)); break;
-            case OP_POOL: PSEG_TRY(mfma_launch_pool(e, op, st)); break;
-            case OP_BN: {
-                const Tensor& s0 = e.tensors[op.src0];
-                PSEG_TRY(bn_infer_bf16((const uint16_t*)s0.d, (uint16_t*)e.tensors[op.dst].d, (size_t)e.tH(s0) * e.tW(s0), s0.Cs, op.d_w, op.relu, st));
-                break;
-            }
-            case OP_LOGITS: PSEG_TRY(mfma_launch_logits(e, op, nullptr, nullptr, e.cur_labels, e.cur_labels_u8, st)); break;   // (the slot's label maps)
-            default: return fail(PSEG_EUNSUPPORTED, "page units: unknown op type (layer %s)", op.layer.c_str());
-        }
-        PSEG_HIP(hipGetLastError());
-        return time_end(e, op, st, ev0);
-    };
+    auto launch = [&](Op& op) { return bf16_launch_op(e, op, nullptr, nullptr, e.cur_labels, e.cur_labels_u8, st); };   // (the slot's label maps)
     int rc = PSEG_OK;
     std::vector<Op*> live;
     for (auto& op : e.ops)
@@ -960,13 +949,18 @@ static int run_bf16_pages(Engine& e, const uint8_t* d_imgs, int n, int64_t* d_la
     return rc;
 }
 
-// pseg_predict_batch's device leg for a group of same-shape pages
-int predict_device_pages(Engine& e, const uint8_t* d_imgs, int n, int H, int W, int64_t* d_labels, uint8_t* d_labels_u8, hipStream_t st) {
+// what every device entry does first: the engine's device current, every weight set and uploaded, the canvas (and page slots) of this call
+static int engine_ready(Engine& e, int H, int W, hipStream_t st, int pages) {
     PSEG_HIP(hipSetDevice(e.device));
     for (auto& p : e.params)
         if (!p.set) return fail(PSEG_EINVAL, "weight '%s' was never set", p.name.c_str());
     if (e.weights_dirty) PSEG_TRY(upload_weights(e));
-    PSEG_TRY(set_canvas(e, H, W, st, n));
+    return set_canvas(e, H, W, st, pages);
+}
+
+// pseg_predict_batch's device leg for a group of same-shape pages
+int predict_device_pages(Engine& e, const uint8_t* d_imgs, int n, int H, int W, int64_t* d_labels, uint8_t* d_labels_u8, hipStream_t st) {
+    PSEG_TRY(engine_ready(e, H, W, st, n));
     return run_bf16_pages(e, d_imgs, n, d_labels, d_labels_u8, st);
 }
 
@@ -984,17 +978,10 @@ bool pages_capable(Engine& e) {
 int predict_device(Engine& e, const uint8_t* d_img, int H, int W, float* d_logits,
                    float* d_probs, int64_t* d_labels, uint8_t* d_labels_u8,
                    hipStream_t st, float* d_margin) {
-    PSEG_HIP(hipSetDevice(e.device));
-    for (auto& p : e.params)
-        if (!p.set) return fail(PSEG_EINVAL, "weight '%s' was never set", p.name.c_str());
-    if (e.weights_dirty) PSEG_TRY(upload_weights(e));
-    PSEG_TRY(set_canvas(e, H, W, st));
+    PSEG_TRY(engine_ready(e, H, W, st, 1));
     if (e.mode == PSEG_MODE_BF16)
         return run_bf16(e, d_img, d_logits, d_probs, d_labels, d_labels_u8, d_margin, st);
-    if (d_margin && !d_logits) {
-        PSEG_TRY(e.logits_tmp.ensure((size_t)H * W * e.n_classes * sizeof(float), "logits"));
-        d_logits = e.logits_tmp.as<float>();
-    }
+    if (d_margin) PSEG_TRY(logits_or_tmp(e, d_logits, e.n_classes, &d_logits));
     PSEG_TRY(run_exact(e, d_img, d_logits, d_probs, d_labels, d_labels_u8, st));
     if (d_margin) launch_margin_from_logits(d_logits, (size_t)H * W, e.n_classes, d_margin, st);
     return PSEG_OK;

@@ -59,8 +59,8 @@ __global__ __launch_bounds__(256) void conv_exact_mfma_kernel(ConvArgs a, int Cp
 #pragma unroll
         for (int t = 0; t < NT; ++t) acc[m][t] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    // Channel blocks: CB == Cin (one block, the oracle's chain order) unless the caller allowed a relaxed order
-    // (train step): then the chain runs (block, ky, kx, ci) over tiles of CB channels that fit LDS.
+    // Channel blocks: every launch passes CB == Cin (one block: the first layers' flattened chain); with a smaller CB the chain
+    // would run (block, ky, kx, ci) over tiles of CB channels.
     for (int cb = 0; cb < Cin; cb += CB) {
     const int cn = min(CB, Cin - cb);
     if (cb) __syncthreads();                         // every wave is done reading the previous block's tile
@@ -768,20 +768,6 @@ __global__ __launch_bounds__(256) void conv_xb_kernel(ConvArgs a, int THH, int T
     }
 }
 
-template <int MT, int NT, int TAILK, int REM = 0>
-static int launch_xb(const ConvArgs& a, int THH, int TWH, dim3 grid, size_t lds, hipStream_t st) {
-    static bool attr_set[64] = {false};
-    int dev = 0;
-    PSEG_HIP(hipGetDevice(&dev));
-    if (!attr_set[dev & 63]) {
-        PSEG_HIP(hipFuncSetAttribute((const void*)conv_xb_kernel<MT, NT, TAILK, REM>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_set[dev & 63] = true;
-    }
-    conv_xb_kernel<MT, NT, TAILK, REM><<<grid, 256, lds, st>>>(a, THH, TWH, (1u << 20) / (unsigned)TWH + 1u);
-    PSEG_HIP(hipGetLastError());
-    return PSEG_OK;
-}
-
 // wr[ky][kxp][ci][dx * rem + j] = w[ky][kxp - dx][ci][cmain + j] (0 when kxp - dx is not a tap): the left-over channels'
 // kernel as DX shifted copies, one per pixel of the group a tile column stands for (see conv_xb_kernel, REM)
 __global__ void wrem_kernel(const float* w, int KH, int KW, int Cin, int Cout, int cmain, int rem, float* wr) {
@@ -801,122 +787,162 @@ size_t wrem_bytes_for(int KH, int KW, int Cin, int Cout) {
     return (size_t)KH * (KW + 16 / rem - 1) * Cin * 16 * 4;
 }
 
-template <int MT, int NT, bool FLAT>
-static int launch_xm(const ConvArgs& a, int Cp, int THH, int TWH, int CB, dim3 grid, size_t lds, hipStream_t st) {
-    static bool attr_set[64] = {false};
-    int dev = 0;
-    PSEG_HIP(hipGetDevice(&dev));
-    if (!attr_set[dev & 63]) {
-        PSEG_HIP(hipFuncSetAttribute((const void*)conv_exact_mfma_kernel<MT, NT, FLAT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_set[dev & 63] = true;
-    }
-    conv_exact_mfma_kernel<MT, NT, FLAT><<<grid, 256, lds, st>>>(a, Cp, THH, TWH, CB);
-    PSEG_HIP(hipGetLastError());
-    return PSEG_OK;
+// ---- launch: choose, prepare, launch -----------------------------------------------------------------------------------------
+// What the matrix-core route does with one layer: a function of the ConvArgs (and the PSEG_EXACT_* plan switches) alone.
+enum XFamily { XF_NONE, XF_FLAT, XF_BLOCKED, XF_BLOCKED_REM };   // not a layer for these kernels / conv_exact_mfma_kernel / conv_xb_kernel / ... with REM
+struct XChoice {
+    XFamily family = XF_NONE;
+    int MT = 0, NT = 0, nblk = 0;   // pixel tiles per wave, cout tiles per workgroup, cout blocks (grid.y)
+    int tailk = 0;                  // k-steps of the last channel slab when it has at most 12 channels, else 0 (a full slab's loop)
+    int rem = 0, ntm = 0;           // XF_BLOCKED_REM: the left-over output channels (4 or 8) and the full cout tiles in front of them
+    int THH = 0, TWH = 0, Cp = 0;   // halo tile rows, columns; XF_FLAT: its channel pitch
+    size_t lds = 0;
+    dim3 grid;
+    bool pooled = false;            // the kernel also writes ConvArgs.pool_dst
+};
+
+// first layers (fewer than 8 input channels): K flattened across taps (one slab: the oracle's order), all-channel tile, no fused pool
+static XChoice choose_flat(const ConvArgs& a, int Cin, int ntall) {
+    XChoice c;
+    if (a.deconv4) return c;
+    c.Cp = std::max(Cin, 2);
+    while (c.Cp % 4 != 2) ++c.Cp;
+    c.MT = 4;
+    c.THH = (8 - 1) * a.stride + a.KH;
+    c.TWH = (XTW - 1) * a.stride + a.KW;
+    c.lds = (size_t)c.THH * c.TWH * c.Cp * 4;
+    if (c.lds > 150 * 1024) return c;
+    c.NT = ntall <= 4 ? ntall : (ntall == 5 ? 5 : 4);
+    c.nblk = cdiv(ntall, c.NT);
+    c.grid = dim3(cdiv(a.Wout, XTW) * cdiv(a.Hout, 8), c.nblk);
+    c.family = XF_FLAT;
+    return c;
 }
 
-// Returns 1 when the layer was launched on a matrix-core kernel (2: with ConvArgs.pool_dst written too), 0 when it is not
-// one for them (caller falls back to the 1x1 / scalar kernels: a handful of output channels), < 0 on error.
-int launch_conv_exact_mfma(const ConvArgs& a_in, hipStream_t st) {
-    ConvArgs a = a_in;
-    if (const char* dv = PSEG_DIAG_KNOB("PSEG_XM_DBG")) a.dbg = atoi(dv);   // wrong-result timing switches: diagnostic build only
-    const int Cin = a.C0 + a.C1;
-    if (Cin < 1 || a.Cout < 1 || a.KH != a.KW) return 0;
-    const int Ntot = a.deconv4 ? 4 * a.Cout : a.Cout;
-    if (Ntot < 8) return 0;                    // a handful of couts (logits): the 1x1 / scalar kernels waste less
-    const int ntall = cdiv(Ntot, 16);
-    const int TWH = (XTW - 1) * a.stride + a.KW;
-    if (Cin < 8) {
-        // first layers: K flattened across taps (one slab: the oracle's order), all-channel tile
-        if (a.deconv4) return 0;
-        a.pool_dst = nullptr;                  // (no fused pool on this path: the caller sees return code 1 and pools itself)
-        int Cp = std::max(Cin, 2);
-        while (Cp % 4 != 2) ++Cp;
-        const int THH = (8 - 1) * a.stride + a.KH;
-        const size_t lds = (size_t)THH * TWH * Cp * 4;
-        if (lds > 150 * 1024) return 0;
-        const int NT = ntall <= 4 ? ntall : (ntall == 5 ? 5 : 4);
-        dim3 grid(cdiv(a.Wout, XTW) * cdiv(a.Hout, 8), cdiv(ntall, NT));
-        switch (NT) {
-            case 1: PSEG_TRY((launch_xm<4, 1, true>(a, Cp, THH, TWH, Cin, grid, lds, st))); break;
-            case 2: PSEG_TRY((launch_xm<4, 2, true>(a, Cp, THH, TWH, Cin, grid, lds, st))); break;
-            case 3: PSEG_TRY((launch_xm<4, 3, true>(a, Cp, THH, TWH, Cin, grid, lds, st))); break;
-            case 4: PSEG_TRY((launch_xm<4, 4, true>(a, Cp, THH, TWH, Cin, grid, lds, st))); break;
-            default: PSEG_TRY((launch_xm<4, 5, true>(a, Cp, THH, TWH, Cin, grid, lds, st))); break;
-        }
-        return 1;
-    }
-    // blocked chain: 8-row tiles unless the 16-channel slab of a strided layer's halo tile would leave fewer than three
-    // workgroups per CU (then 4-row tiles)
-    auto lds_of = [&](int mt) { return (size_t)((4 * (mt / 2) - 1) * a.stride + a.KH) * TWH * XCP * 4; };
-    int MT = (lds_of(4) <= 52 * 1024) ? 4 : 2;
-    const bool pooled = a.pool_dst != nullptr && MT == 4 && a.stride == 1 && !a.deconv4 && !a.add && !(a.Hout & 1) && !(a.Wout & 1);
-    if (!pooled) a.pool_dst = nullptr;
-    if (lds_of(MT) > 150 * 1024) return 0;
-    const int TH = 4 * (MT / 2);
-    const int THH = (TH - 1) * a.stride + a.KH;
-    const int tiles = cdiv(a.Wout, XTW) * cdiv(a.Hout, TH);
-    // cout tiles per workgroup: at most four (64 accumulator registers), split evenly over the cout blocks; small layers
-    // (1/8-resolution: 192 tiles for 256 CUs) split further until the chip is full -- restaging a 31 KB slab per cout
-    // block costs little next to 25 taps of float32 MFMAs
+// Cout tiles per workgroup and cout blocks of the blocked chain.  At most four tiles (64 accumulator registers), split evenly over
+// the cout blocks; small layers (1/8-resolution: 192 tiles for 256 CUs) split further until the chip is full -- restaging a 31 KB
+// slab per cout block costs little next to 25 taps of float32 MFMAs.
+static void choose_cout_split(int ntall, int tiles, int* NT_out, int* nblk_out) {
     int nblk = cdiv(ntall, 4), NT = cdiv(ntall, nblk);
     while (NT > 1 && tiles * nblk < 1024) { --NT; nblk = cdiv(ntall, NT); }
     NT = cdiv(ntall, nblk);                    // even split: 4 tiles over 2 blocks are 2 + 2, not 3 + 1 (idle MFMAs on the empty tiles)
     // quarter-resolution layers of a 2048x1536 page (768 tiles): the chip holds 768 three- or four-tile workgroups at once (three
     // waves per SIMD), so one cout block beats two -- 3 tiles cannot split evenly (2 + 1 with a dead tile: deconv3 612 -> 461 us),
-    // 4 tiles as 2 + 2 stage every slab twice (conv5 / conv6 226 -> 218, 326 -> 308 us).  PSEG_EXACT_SPLIT=1: the split forms.
+    // 4 tiles as 2 + 2 stage every slab twice (conv5 / conv6 226 -> 218, 326 -> 308 us).
     if ((ntall == 3 || ntall == 4) && nblk == 2 && tiles >= 512) { NT = ntall; nblk = 1; }
-    const size_t lds = lds_of(MT);
-    dim3 grid(tiles, nblk);
+    *NT_out = NT;
+    *nblk_out = nblk;
+}
+
+// left-over output channels (Cout = 16 k + 4 or + 8) as shifted-pixel tiles instead of a padded cout tile: 8-row tiles of a plain
+// stride-1 layer with at least 512 tiles (PSEG_EXACT_REM_ANY: any size; PSEG_EXACT_NO_REM: never) whose caller lent a buffer for
+// the shifted kernel copies
+static bool rem_form_pays(const ConvArgs& a, int Cin, int MT, int tiles) {
+    const int rem = a.Cout % 16, ntm = a.Cout / 16;
+    return (rem == 4 || rem == 8) && (ntm == 1 || ntm == 2) && MT == 4 && !a.deconv4 && a.stride == 1 && !a.out_sy && !a.out_sx &&
+           (tiles >= 512 || PSEG_KNOB("PSEG_EXACT_REM_ANY")) && !PSEG_KNOB("PSEG_EXACT_NO_REM") && a.wrem_buf &&
+           a.wrem_cap >= wrem_bytes_for(a.KH, a.KW, Cin, a.Cout);
+}
+
+// blocked chain: 8-row tiles unless the 16-channel slab of a strided layer's halo tile would leave fewer than three workgroups per
+// CU (then 4-row tiles)
+static XChoice choose_blocked(const ConvArgs& a, int Cin, int ntall) {
+    XChoice c;
+    c.TWH = (XTW - 1) * a.stride + a.KW;
+    auto lds_of = [&](int mt) { return (size_t)((4 * (mt / 2) - 1) * a.stride + a.KH) * c.TWH * XCP * 4; };
+    c.MT = (lds_of(4) <= 52 * 1024) ? 4 : 2;
+    c.lds = lds_of(c.MT);
+    if (c.lds > 150 * 1024) return c;
+    const int TH = 4 * (c.MT / 2);
+    c.THH = (TH - 1) * a.stride + a.KH;
+    const int tiles = cdiv(a.Wout, XTW) * cdiv(a.Hout, TH);
     const int tail_ch = Cin % XCB;                              // channels of the last slab (0: a full one)
-    const int tailk = (tail_ch == 0 || tail_ch > 12) ? 0 : (tail_ch + 3) / 4;
-    // left-over output channels (Cout = 16 k + 4 or + 8) as shifted-pixel tiles instead of a padded cout tile
-    {
-        const int rem = a.Cout % 16, ntm = a.Cout / 16;
-        if ((rem == 4 || rem == 8) && (ntm == 1 || ntm == 2) && MT == 4 && !a.deconv4 && a.stride == 1 && !a.out_sy && !a.out_sx && (tiles >= 512 || PSEG_KNOB("PSEG_EXACT_REM_ANY")) &&
-            !PSEG_KNOB("PSEG_EXACT_NO_REM") && a.wrem_buf && a.wrem_cap >= wrem_bytes_for(a.KH, a.KW, Cin, a.Cout)) {
-            const size_t wbytes = wrem_bytes_for(a.KH, a.KW, Cin, a.Cout);
-            // the shifted copies live in a buffer of the caller's (the op's, beside its kernel; the train step's scratch for the
-            // flipped kernels of the data gradients) and are rebuilt only when the weights behind them changed -- no allocation,
-            // no pool, nothing but kernels on `st`
-            float* const wr = a.wrem_buf;
-            if (!a.wrem_valid || !*a.wrem_valid) {
-                wrem_kernel<<<(int)std::min<size_t>((wbytes / 4 + 255) / 256, 1024), 256, 0, st>>>(a.w, a.KH, a.KW, Cin, a.Cout, ntm * 16, rem, wr);
-                if (a.wrem_valid) *a.wrem_valid = true;
-            }
-            a.wrem = wr;
-            a.pool_dst = nullptr;                               // (the caller pools: return code 1)
-            const dim3 g1(tiles, 1);
-            int rc = PSEG_OK;
-#define PSEG_XR(NT_, REM_)                                                                        \
-            if (ntm == NT_ && rem == REM_) {                                                          \
-                switch (tailk) {                                                                      \
-                    case 0: rc = launch_xb<4, NT_, 0, REM_>(a, THH, TWH, g1, lds, st); break;         \
-                    case 1: rc = launch_xb<4, NT_, 1, REM_>(a, THH, TWH, g1, lds, st); break;         \
-                    case 2: rc = launch_xb<4, NT_, 2, REM_>(a, THH, TWH, g1, lds, st); break;         \
-                    default: rc = launch_xb<4, NT_, 3, REM_>(a, THH, TWH, g1, lds, st); break;        \
-                }                                                                                     \
-            }
-            PSEG_XR(1, 4) PSEG_XR(2, 8) PSEG_XR(1, 8) PSEG_XR(2, 4)
-#undef PSEG_XR
-            if (rc != PSEG_OK) return rc;
-            return 1;
-        }
+    c.tailk = (tail_ch == 0 || tail_ch > 12) ? 0 : (tail_ch + 3) / 4;
+    if (rem_form_pays(a, Cin, c.MT, tiles)) {                   // (no fused pool in this form: the caller pools)
+        c.family = XF_BLOCKED_REM;
+        c.rem = a.Cout % 16;
+        c.ntm = c.NT = a.Cout / 16;
+        c.nblk = 1;
+    } else {
+        c.family = XF_BLOCKED;
+        choose_cout_split(ntall, tiles, &c.NT, &c.nblk);
+        c.pooled = a.pool_dst != nullptr && c.MT == 4 && a.stride == 1 && !a.deconv4 && !a.add && !(a.Hout & 1) && !(a.Wout & 1);
     }
-#define PSEG_XB(MT_, NT_)                                                                        \
-    if (MT == MT_ && NT == NT_) {                                                                \
-        switch (tailk) {                                                                         \
-            case 0: PSEG_TRY((launch_xb<MT_, NT_, 0>(a, THH, TWH, grid, lds, st))); break;       \
-            case 1: PSEG_TRY((launch_xb<MT_, NT_, 1>(a, THH, TWH, grid, lds, st))); break;       \
-            case 2: PSEG_TRY((launch_xb<MT_, NT_, 2>(a, THH, TWH, grid, lds, st))); break;       \
-            default: PSEG_TRY((launch_xb<MT_, NT_, 3>(a, THH, TWH, grid, lds, st))); break;      \
-        }                                                                                        \
-        return pooled ? 2 : 1;                                                                   \
+    c.grid = dim3(tiles, c.nblk);
+    return c;
+}
+
+static XChoice choose_exact_mfma(const ConvArgs& a) {
+    const int Cin = a.C0 + a.C1;
+    if (Cin < 1 || a.Cout < 1 || a.KH != a.KW) return XChoice();
+    const int Ntot = a.deconv4 ? 4 * a.Cout : a.Cout;
+    if (Ntot < 8) return XChoice();            // a handful of couts (logits): the 1x1 / scalar kernels waste less
+    return Cin < 8 ? choose_flat(a, Cin, cdiv(Ntot, 16)) : choose_blocked(a, Cin, cdiv(Ntot, 16));
+}
+
+// The shifted copies of the left-over channels' kernel live in a buffer of the caller's (the op's, beside its kernel; the train
+// step's scratch for the flipped kernels of the data gradients) and are rebuilt only when the weights behind them changed -- no
+// allocation, no pool, nothing but kernels on `st`.  No validity flag: rebuilt on every launch.
+static void prepare_wrem(const ConvArgs& a, const XChoice& c, hipStream_t st) {
+    if (a.wrem_valid && *a.wrem_valid) return;
+    const size_t wbytes = wrem_bytes_for(a.KH, a.KW, a.C0 + a.C1, a.Cout);
+    wrem_kernel<<<(int)std::min<size_t>((wbytes / 4 + 255) / 256, 1024), 256, 0, st>>>(a.w, a.KH, a.KW, a.C0 + a.C1, a.Cout, c.ntm * 16, c.rem, a.wrem_buf);
+    if (a.wrem_valid) *a.wrem_valid = true;
+}
+
+// the instance tables
+static int launch_flat(const ConvArgs& a, const XChoice& c, hipStream_t st) {
+    const int Cin = a.C0 + a.C1;
+    switch (c.NT) {
+        case 1: return launch_lds<conv_exact_mfma_kernel<4, 1, true>>(a, c.grid, 256, c.lds, -1, st, c.Cp, c.THH, c.TWH, Cin);
+        case 2: return launch_lds<conv_exact_mfma_kernel<4, 2, true>>(a, c.grid, 256, c.lds, -1, st, c.Cp, c.THH, c.TWH, Cin);
+        case 3: return launch_lds<conv_exact_mfma_kernel<4, 3, true>>(a, c.grid, 256, c.lds, -1, st, c.Cp, c.THH, c.TWH, Cin);
+        case 4: return launch_lds<conv_exact_mfma_kernel<4, 4, true>>(a, c.grid, 256, c.lds, -1, st, c.Cp, c.THH, c.TWH, Cin);
+        default: return launch_lds<conv_exact_mfma_kernel<4, 5, true>>(a, c.grid, 256, c.lds, -1, st, c.Cp, c.THH, c.TWH, Cin);
     }
-    PSEG_XB(4, 1) PSEG_XB(4, 2) PSEG_XB(4, 3) PSEG_XB(4, 4)
-    PSEG_XB(2, 1) PSEG_XB(2, 2) PSEG_XB(2, 3) PSEG_XB(2, 4)
-#undef PSEG_XB
-    return 0;
+}
+template <int MT, int NT, int REM = 0>
+static int launch_xb(const ConvArgs& a, const XChoice& c, hipStream_t st) {
+    const unsigned inv_twh = (1u << 20) / (unsigned)c.TWH + 1u;
+    switch (c.tailk) {
+        case 0: return launch_lds<conv_xb_kernel<MT, NT, 0, REM>>(a, c.grid, 256, c.lds, -1, st, c.THH, c.TWH, inv_twh);
+        case 1: return launch_lds<conv_xb_kernel<MT, NT, 1, REM>>(a, c.grid, 256, c.lds, -1, st, c.THH, c.TWH, inv_twh);
+        case 2: return launch_lds<conv_xb_kernel<MT, NT, 2, REM>>(a, c.grid, 256, c.lds, -1, st, c.THH, c.TWH, inv_twh);
+        default: return launch_lds<conv_xb_kernel<MT, NT, 3, REM>>(a, c.grid, 256, c.lds, -1, st, c.THH, c.TWH, inv_twh);
+    }
+}
+static int launch_blocked(const ConvArgs& a, const XChoice& c, hipStream_t st) {
+    if (c.family == XF_BLOCKED_REM) {
+        if (c.ntm == 1) return c.rem == 4 ? launch_xb<4, 1, 4>(a, c, st) : launch_xb<4, 1, 8>(a, c, st);
+        return c.rem == 4 ? launch_xb<4, 2, 4>(a, c, st) : launch_xb<4, 2, 8>(a, c, st);
+    }
+    switch (c.MT * 10 + c.NT) {
+        case 41: return launch_xb<4, 1>(a, c, st);
+        case 42: return launch_xb<4, 2>(a, c, st);
+        case 43: return launch_xb<4, 3>(a, c, st);
+        case 44: return launch_xb<4, 4>(a, c, st);
+        case 21: return launch_xb<2, 1>(a, c, st);
+        case 22: return launch_xb<2, 2>(a, c, st);
+        case 23: return launch_xb<2, 3>(a, c, st);
+        case 24: return launch_xb<2, 4>(a, c, st);
+    }
+    return ROUTE_NO;
+}
+
+// PSEG_OK when the layer was launched on a matrix-core kernel (*pooled: with ConvArgs.pool_dst written too), ROUTE_NO when it is
+// not one for them (the caller falls back to the 1x1 / scalar kernels: a handful of output channels), an error otherwise.
+int launch_conv_exact_mfma(const ConvArgs& a_in, hipStream_t st, bool* pooled) {
+    if (pooled) *pooled = false;
+    const XChoice c = choose_exact_mfma(a_in);
+    if (c.family == XF_NONE) return ROUTE_NO;
+    if (c.family == XF_BLOCKED_REM) prepare_wrem(a_in, c, st);
+    ConvArgs a = a_in;                         // the kernel's copy: what the choice says, nothing else, differs from the caller's
+    if (const char* dv = PSEG_DIAG_KNOB("PSEG_XM_DBG")) a.dbg = atoi(dv);   // wrong-result timing switches: diagnostic build only
+    if (!c.pooled) a.pool_dst = nullptr;
+    if (c.family == XF_BLOCKED_REM) a.wrem = a.wrem_buf;
+    const int rc = c.family == XF_FLAT ? launch_flat(a, c, st) : launch_blocked(a, c, st);
+    if (pooled) *pooled = rc == PSEG_OK && c.pooled;
+    return rc;
 }
 
 }  // namespace pseg

@@ -410,76 +410,50 @@ __global__ __launch_bounds__(256) void deconv2_valu_kernel(TailArgs a) {
     }
 }
 
-template <typename K>
-static int set_lds_attr(K kernel) {
-    PSEG_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    return PSEG_OK;
-}
-
-// 1 = launched, 0 = not a layer for this kernel
+// PSEG_OK = launched, ROUTE_NO = not a layer for this kernel
 int launch_conv_first_valu(const ConvArgs& a, hipStream_t st) {
-    if (PSEG_KNOB("PSEG_EXACT_NO_VALU")) return 0;
+    if (PSEG_KNOB("PSEG_EXACT_NO_VALU")) return ROUTE_NO;
     if (a.C1 || a.C0 > 3 || a.KH != a.KW || a.stride != 1 || a.up0 || a.in_relu || a.mask || a.deconv4 || a.pool_dst ||
         a.out_sy || a.out_sx || a.Cout < 8 || a.Cout > 256)
-        return 0;
+        return ROUTE_NO;
     const int K = a.KH;
     size_t lds = (size_t)(FV_TH + K - 1) * (FV_TW + K - 1) * a.C0 * 4;
     int CT = (a.Cout == 20 || a.Cout == 16 || a.Cout == 32) ? a.Cout : ((a.Cout & 31) == 0 ? 32 : ((a.Cout % 20) == 0 ? 20 : ((a.Cout % 30) == 0 ? 30 : 16)));
     dim3 grid(cdiv(a.Wout, FV_TW) * cdiv(a.Hout, FV_TH), cdiv(a.Cout, CT));
     if (CT == a.Cout && !a.add && (CT & 1) == 0) lds = ((lds + 15) & ~(size_t)15) + (size_t)256 * CT * 4;   // the store patches (see the kernel)
     switch (CT) {
-        case 16: conv_first_valu_kernel<16><<<grid, 256, lds, st>>>(a); break;
-        case 20: conv_first_valu_kernel<20><<<grid, 256, lds, st>>>(a); break;
-        case 30: conv_first_valu_kernel<30><<<grid, 256, lds, st>>>(a); break;
-        default: conv_first_valu_kernel<32><<<grid, 256, lds, st>>>(a); break;
+        case 16: return launch_lds<conv_first_valu_kernel<16>>(a, grid, 256, lds, -1, st);
+        case 20: return launch_lds<conv_first_valu_kernel<20>>(a, grid, 256, lds, -1, st);
+        case 30: return launch_lds<conv_first_valu_kernel<30>>(a, grid, 256, lds, -1, st);
+        default: return launch_lds<conv_first_valu_kernel<32>>(a, grid, 256, lds, -1, st);
     }
-    PSEG_HIP(hipGetLastError());
-    return 1;
 }
 
-// Conv2DTranspose k2 s2; with `tail` the logits layer and argmax run behind it (tail.skip etc. filled in).  1 = launched.
+// output channels per thread of the plain transposed conv's instance
+static int deconv2_ct(int Cout) { return (Cout % 30) == 0 ? 30 : ((Cout % 20) == 0 ? 20 : ((Cout & 31) == 0 ? 32 : 16)); }
+
+// Conv2DTranspose k2 s2; with `tail` the logits layer and argmax run behind it (tail.skip etc. filled in).  PSEG_OK = launched.
 int launch_deconv2_valu(const TailArgs& a, bool tail, hipStream_t st) {
-    if (PSEG_KNOB("PSEG_EXACT_NO_VALU")) return 0;
+    if (PSEG_KNOB("PSEG_EXACT_NO_VALU")) return ROUTE_NO;
     const int Cin = a.C0 + a.C1;
-    if (Cin < 1 || Cin > 512 || a.Cout < 4 || (size_t)a.Hin * a.Win > 0x3fffffff) return 0;
+    if (Cin < 1 || Cin > 512 || a.Cout < 4 || (size_t)a.Hin * a.Win > 0x3fffffff) return ROUTE_NO;
     size_t lds = std::max((size_t)DV_PX * (Cin + 1) * 4, tail ? (size_t)4 * DV_PX * (a.Cs + 1) * 4 : (size_t)0);
-    {   // the store patch of a whole-pixel instance (CT == Cout: 2 rows x 2 * DV_PX pixels x Cout)
-        const int ct = tail ? 20 : ((a.Cout % 30) == 0 ? 30 : ((a.Cout % 20) == 0 ? 20 : ((a.Cout & 31) == 0 ? 32 : 16)));
-        if (ct == a.Cout) lds = std::max(lds, (size_t)4 * DV_PX * a.Cout * 4);
-    }
-    static bool attr[64] = {false};
-    int dev = 0;
-    PSEG_HIP(hipGetDevice(&dev));
-    if (!attr[dev & 63]) {
-        PSEG_TRY(set_lds_attr(deconv2_valu_kernel<20, 3>));
-        PSEG_TRY(set_lds_attr(deconv2_valu_kernel<20, 4>));
-        PSEG_TRY(set_lds_attr(deconv2_valu_kernel<20, 6>));
-        PSEG_TRY(set_lds_attr(deconv2_valu_kernel<20, 8>));
-        PSEG_TRY(set_lds_attr(deconv2_valu_kernel<20, 0>));
-        PSEG_TRY(set_lds_attr(deconv2_valu_kernel<30, 0>));
-        PSEG_TRY(set_lds_attr(deconv2_valu_kernel<32, 0>));
-        PSEG_TRY(set_lds_attr(deconv2_valu_kernel<16, 0>));
-        attr[dev & 63] = true;
-    }
-    const int nwg = cdiv(a.Win, DV_PX) * a.Hin;
+    const int CT = tail ? 20 : deconv2_ct(a.Cout);
+    if (CT == a.Cout) lds = std::max(lds, (size_t)4 * DV_PX * a.Cout * 4);   // the store patch of a whole-pixel instance (2 rows x 2 * DV_PX pixels x Cout)
+    const dim3 grid(cdiv(a.Win, DV_PX) * a.Hin, tail ? 1 : cdiv(a.Cout, CT));
     if (tail) {
-        if (a.Cout != 20 || a.ncls < 1 || a.ncls > 8 || a.relu || (a.Cs > 0 && !a.skip) || a.Cs > 32 || lds > 150 * 1024) return 0;
-        if (a.ncls <= 3) deconv2_valu_kernel<20, 3><<<dim3(nwg), 256, lds, st>>>(a);
-        else if (a.ncls == 4) deconv2_valu_kernel<20, 4><<<dim3(nwg), 256, lds, st>>>(a);
-        else if (a.ncls <= 6) deconv2_valu_kernel<20, 6><<<dim3(nwg), 256, lds, st>>>(a);
-        else deconv2_valu_kernel<20, 8><<<dim3(nwg), 256, lds, st>>>(a);
-    } else {
-        const int CT = (a.Cout % 30) == 0 ? 30 : ((a.Cout % 20) == 0 ? 20 : ((a.Cout & 31) == 0 ? 32 : 16));
-        const dim3 grid(nwg, cdiv(a.Cout, CT));
-        switch (CT) {
-            case 30: deconv2_valu_kernel<30, 0><<<grid, 256, lds, st>>>(a); break;
-            case 20: deconv2_valu_kernel<20, 0><<<grid, 256, lds, st>>>(a); break;
-            case 32: deconv2_valu_kernel<32, 0><<<grid, 256, lds, st>>>(a); break;
-            default: deconv2_valu_kernel<16, 0><<<grid, 256, lds, st>>>(a); break;
-        }
+        if (a.Cout != 20 || a.ncls < 1 || a.ncls > 8 || a.relu || (a.Cs > 0 && !a.skip) || a.Cs > 32 || lds > 150 * 1024) return ROUTE_NO;
+        if (a.ncls <= 3) return launch_lds<deconv2_valu_kernel<20, 3>>(a, grid, 256, lds, -1, st);
+        if (a.ncls == 4) return launch_lds<deconv2_valu_kernel<20, 4>>(a, grid, 256, lds, -1, st);
+        if (a.ncls <= 6) return launch_lds<deconv2_valu_kernel<20, 6>>(a, grid, 256, lds, -1, st);
+        return launch_lds<deconv2_valu_kernel<20, 8>>(a, grid, 256, lds, -1, st);
     }
-    PSEG_HIP(hipGetLastError());
-    return 1;
+    switch (CT) {
+        case 30: return launch_lds<deconv2_valu_kernel<30, 0>>(a, grid, 256, lds, -1, st);
+        case 20: return launch_lds<deconv2_valu_kernel<20, 0>>(a, grid, 256, lds, -1, st);
+        case 32: return launch_lds<deconv2_valu_kernel<32, 0>>(a, grid, 256, lds, -1, st);
+        default: return launch_lds<deconv2_valu_kernel<16, 0>>(a, grid, 256, lds, -1, st);
+    }
 }
 
 }  // namespace pseg

@@ -5268,8 +5268,8 @@ int mfma_pack_op(Engine& e, Op& op, const std::vector<float>& w, const std::vect
 // ---- launch plumbing ------------------------------------------------------------------------------------------------------------
 // How a bf16 conv launch is chosen: the plan's flags (mfma_pack_op: layer shape + plan switches) say which kernel families may
 // take the layer, the size predicates below (canvas, page slots, CUs) say which of them pays for THIS launch, and mfma_launch_conv
-// asks the routes in a fixed order.  A route answers PSEG_OK (launched), ROUTE_NO (not this route: ask the next) or an error (< 0).
-constexpr int ROUTE_NO = 1;
+// asks the routes in a fixed order.  A route answers PSEG_OK (launched), ROUTE_NO (not this route: ask the next) or an error (< 0);
+// every kernel with dynamic LDS goes through launch_lds (pseg_common.h).
 
 // what a launch knows beyond its plan
 struct Extent {
@@ -5288,19 +5288,6 @@ static int device_cus(int* dev_out = nullptr) {
     int& n = cache[dev & 63];
     if (n == 0 && (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1)) n = 256;
     return n;
-}
-
-// Every conv kernel with dynamic LDS is launched here: the CU's whole 160 KB allowed once per device and kernel, the launch, its error.
-template <auto KERNEL, typename Arg>
-static int launch_lds(const Arg& a, dim3 grid, unsigned threads, int lds, int dev, hipStream_t st) {
-    static bool attr_set[64] = {false};
-    if (!attr_set[dev & 63]) {
-        PSEG_HIP(hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_set[dev & 63] = true;
-    }
-    KERNEL<<<grid, threads, lds, st>>>(a);
-    PSEG_HIP(hipGetLastError());
-    return PSEG_OK;
 }
 
 // the XCD bands of a launch of `units` workgroups' worth of work (PSEG_NO_XCD=1: plain order)
@@ -5593,11 +5580,8 @@ static int fill_conv(Engine& e, const Op& op, MfmaPlan& P, MConv& a, dim3* grid)
     a.Hout = e.tH(d);
     a.Wout = e.tW(d);
     a.stride = op.stride;
-    const int tot_h = std::max((a.Hout - 1) * op.stride + op.k - a.Hin, 0);
-    const int tot_w = std::max((a.Wout - 1) * op.stride + op.k - a.Win, 0);
-    a.pt = tot_h / 2;
-    a.pl = tot_w / 2;
-    if (op.transposed) { a.pt = tot_h - a.pt; a.pl = tot_w - a.pl; }
+    a.pt = same_pad(a.Hout, a.Hin, op.k, op.stride, op.transposed);
+    a.pl = same_pad(a.Wout, a.Win, op.k, op.stride, op.transposed);
     a.pool_dst = op.pool_dst >= 0 ? (uint16_t*)e.tensors[op.pool_dst].d : nullptr;
     if (op.pool_dst >= 0) { const Tensor& pt = e.tensors[op.pool_dst]; a.pool_bytes = (unsigned)((size_t)e.tH(pt) * e.tW(pt) * pt.Cs * 2); }
     a.add = op.add >= 0 ? (const uint16_t*)e.tensors[op.add].d : nullptr;

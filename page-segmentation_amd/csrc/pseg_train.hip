@@ -895,12 +895,10 @@ static int launch_wgrad(const WgradArgs& a_in, dim3 grid, hipStream_t st, DevBuf
 constexpr int WGRAD_STRIPS_TARGET = 1536;
 // rows per strip the caller proposes to the kernels of this file (the flattened-row and two-source kernels plan their own)
 static int wgrad_caller_strip_rows(int itH, int taps) { return std::max(1, cdiv(itH * taps, WGRAD_STRIPS_TARGET)); }
-// TF SAME: pad_total = max((out-1)*s + k - in, 0), before = total / 2 (as run_exact); the logits layer has none
+// TF SAME padding in front (same_pad, as the forward pass); the logits layer has none
 static void wgrad_same_pad(bool logits, int Hy, int Wy, int Hx, int Wx, int k, int stride, int* pt, int* pl) {
-    *pt = *pl = 0;
-    if (logits) return;
-    *pt = std::max((Hy - 1) * stride + k - Hx, 0) / 2;
-    *pl = std::max((Wy - 1) * stride + k - Wx, 0) / 2;
+    *pt = logits ? 0 : same_pad(Hy, Hx, k, stride, false);
+    *pl = logits ? 0 : same_pad(Wy, Wx, k, stride, false);
 }
 // what every form shares: the output gradient (rows of Wy pixels) under the layer's ReLU mask, the layer's channel counts, outputs
 static void wgrad_common_args(WgradArgs& a, const float* dY, const float* maskY, int Hy, int Wy, int Cout, int Cin, float* dW, float* dB) {
@@ -1231,15 +1229,13 @@ static int train_fwd_bwd(Engine& e, const uint8_t* img, const uint8_t* mask, int
 
 // ---- the step's forward half
 // forward under the training flags: Dropout layers are live in a training forward (Keras fit), the identity in an evaluation step
-static int train_forward(Engine& e, TrainState* t, uint32_t drop_key, bool training, int relaxed, bool img_f32) {
+static int train_forward(Engine& e, TrainState* t, uint32_t drop_key, bool training, bool img_f32) {
     e.cur_img_f32 = img_f32 ? (const float*)t->d_img.p : nullptr;
     e.drop_key = drop_key;
     e.bn_training = training;   // Keras fit: BatchNormalization layers normalise with the batch statistics; evaluate / predict with the moving ones
-    e.relaxed_f32 = relaxed;    // wide layers: channel-blocked matrix-core kernel (summation order differs from predict)
     const int rc_fwd = run_exact(e, t->d_img.p, t->d_logits.p, nullptr, nullptr, nullptr, e.stream);
     e.drop_key = 0;
     e.bn_training = false;
-    e.relaxed_f32 = 0;
     e.cur_img_f32 = nullptr;
     return rc_fwd;
 }
@@ -1274,7 +1270,6 @@ struct Backward {
     hipStream_t st, ws;          // main stream; the weight gradients' stream (open_weight_stream; == st under PSEG_TRAIN_ONE_STREAM)
     int H, W;                    // the page (the canvas may be larger)
     uint32_t drop_key;
-    int relaxed;                 // 0 under PSEG_TRAIN_STRICT
     std::vector<char> fresh;
     float* grad(int tensor) const { return t->tgrad[tensor].p; }
     float* param_grad(int param) const { return param >= 0 ? t->d_grad + t->off[param] : nullptr; }
@@ -1405,7 +1400,6 @@ static int conv_data_grad(Backward& b, const Op& op, const ConvBack& g, int sidx
     a.pt = k - 1 - g.pt; a.pl = k - 1 - g.pl;
     a.Hout = g.lg ? b.H : g.Hx; a.Wout = g.lg ? b.W : g.Wx; a.Cout = nc;
     a.mask = maskd;
-    a.relaxed = b.relaxed;
     a.dst = direct ? b.grad(src) : t->d_tmp.p;
     // (the logits layer writes the page extent only: on a padded canvas the rest of the gradient must be zeros)
     if (direct && g.lg && (b.H != g.Hx || b.W != g.Wx)) PSEG_TRY(b.zero_if_fresh(src));
@@ -1464,14 +1458,14 @@ static int deconv2_data_grad(Backward& b, const Op& op, int sidx, const float* d
     c.Hin = 2 * Hx; c.Win = 2 * Wx; c.Hout = Hx; c.Wout = Wx;
     c.w = t->d_wd.p; c.KH = c.KW = 2; c.stride = 2; c.Cout = nc;
     c.add = b.fresh[src] ? nullptr : b.grad(src); c.dst = b.grad(src);
-    c.relaxed = 1;
     const int rc = launch_conv_exact_mfma(c, st);
-    if (rc < 0) return rc;
-    if (rc != 0) b.fresh[src] = 0;
-    if (rc == 0) {
+    if (rc == ROUTE_NO) {
         PSEG_TRY(b.zero_if_fresh(src));
         dim3 grid(cdiv(Hx * Wx, 256), cdiv(nc, COT));
         deconv2_dgrad_kernel<<<grid, 256, 0, st>>>(dY, Y, op.relu, Hx, Wx, op.Cout, t->d_wd.p, nc, b.grad(src));
+    } else {
+        PSEG_TRY(rc);
+        b.fresh[src] = 0;
     }
     PSEG_HIP(hipGetLastError());
     return PSEG_OK;
@@ -1530,14 +1524,13 @@ static int backward_pool(Backward& b, const Op& op) {
 static int train_compute(Engine& e, int H, int W, bool backward, bool img_f32) {
     TrainState* t = TS(e);
     hipStream_t st = e.stream;
-    const int relaxed = PSEG_KNOB("PSEG_TRAIN_STRICT") ? 0 : 1;
     const uint32_t drop_key = backward ? (t->drop_seed * 0x632BE5ABu + (uint32_t)t->fwd_count * 0x9E3779B9u) | 1u : 0u;
     if (backward) ++t->fwd_count;
-    PSEG_TRY(train_forward(e, t, drop_key, backward, relaxed, img_f32));
+    PSEG_TRY(train_forward(e, t, drop_key, backward, img_f32));
     PSEG_TRY(train_loss_metrics(e, t, H, W, backward));
     if (!backward) return PSEG_OK;
 
-    Backward b{e, t, st, st, H, W, drop_key, relaxed, std::vector<char>(e.tensors.size(), 1)};
+    Backward b{e, t, st, st, H, W, drop_key, std::vector<char>(e.tensors.size(), 1)};
     PSEG_TRY(size_tensor_grads(b));
     PSEG_TRY(open_weight_stream(b));
     Join join{b.ws, st, t->ev_wdone};
