@@ -69,7 +69,7 @@ int pseg_create(int arch, int n_classes, int in_channels, int device, int mode,
 enum { PSEG_FLAG_BATCHNORM = 1 };
 int pseg_create_ex(int arch, int n_classes, int in_channels, int device, int mode, unsigned flags,
                    pseg_engine** out);
-/* ... with PLAN SWITCHES: alternative kernel / fusion choices of the bf16 and float32 engines ("PSEG_NO_DQ=1;PSEG_WS_FORM=2";
+/* ... with PLAN SWITCHES: alternative kernel / fusion choices of the bf16 and float32 engines ("PSEG_NO_DQ=1;PSEG_NO_PAIRC2=1";
  * NULL or "" = pseg_create_ex).  Test and measurement entry: every switch leaves the results within the documented bars (most
  * are bit-identical) and is pinned by a test; the process environment cannot set them -- the release library reads only the
  * names pseg_env_knobs() lists from the environment (README.md documents them), once per engine at creation. */

@@ -125,7 +125,7 @@ int run_pipeline(Stage& g, int nu, const PipeSet* set, hipStream_t s_in, hipStre
 //     reaches the release library.
 //   * PLAN SWITCHES -- alternative kernel / fusion choices that must not change results beyond the documented bars; every one is
 //     exercised by a bit-identity or tolerance test.  They exist for those tests and for A/B measurements and enter ONLY through
-//     pseg_create_plan's `switches` string ("PSEG_NO_DQ=1;PSEG_WS_FORM=2"); the Python test harness builds that string from
+//     pseg_create_plan's `switches` string ("PSEG_NO_DQ=1;PSEG_NO_PAIRC2=1"); the Python test harness builds that string from
 //     os.environ when pseg_amd.engine.PLAN_FROM_ENV is set (tests/conftest.py, tools/), a product caller never does.
 // pseg_create* takes ONE snapshot (the listed environment knobs + the plan switches) for the new engine; the engine keeps it for
 // its whole life (std::shared_ptr) and every entry point that takes an engine answers queries from the engine's OWN snapshot
@@ -356,8 +356,7 @@ struct ConvArgs {
     int out_sy, out_sx, out_oy, out_ox;   // MFMA kernel only: output pixel (y*sy + oy, x*sx + ox); 0 strides = 1
     int deconv4;         // MFMA kernel only: Conv2DTranspose k2 s2 as one GEMM, n = ab*Cout + co -> (2y + a, 2x + b)
     int dbg;             // MFMA kernel only: timing experiments (PSEG_XM_DBG: 1 no staging loads, 2 no stores, 4 no k-loop) -- wrong results
-    float* pool_dst;     // blocked MFMA kernel, 8-row tiles only: also store the 2x2 max-pool of the output ((Hout/2) x (Wout/2) x Cout)
-    int unused_;         // read by nothing: holds the place of a retired field, so that every compiled kernel keeps its argument layout
+    void* unused_[2];    // read by nothing: holds the place of two retired fields, so that every compiled kernel keeps its argument layout
     const float* wrem = nullptr;   // blocked MFMA kernel, set by its launcher: the left-over output channels' kernel, shifted copies [KH][KW + DX - 1][Cin][16] (conv_xb_kernel REM)
     float* wrem_buf = nullptr;     // caller-owned buffer for that kernel (wrem_bytes_for() bytes; null or too small: padded cout tiles instead)
     size_t wrem_cap = 0;
@@ -366,8 +365,7 @@ struct ConvArgs {
 // bytes of ConvArgs.wrem_buf a KH x KW, Cin -> Cout stride-1 layer needs for its left-over channel tile, 0 when it has none
 size_t wrem_bytes_for(int KH, int KW, int Cin, int Cout);
 // Asks its routes in order -- first-layer vector ALU, matrix core, 1x1, scalar -- and always launches: PSEG_OK or an error.
-// *pooled: ConvArgs.pool_dst was written by the conv kernel (else the caller pools).
-int launch_conv_exact(const ConvArgs& a, hipStream_t st, bool* pooled = nullptr);
+int launch_conv_exact(const ConvArgs& a, hipStream_t st);
 // HBM-bound float32 layers on the vector ALU (pseg_exact_valu.hip): first layer; Conv2DTranspose k2 s2, optionally with the
 // logits layer + argmax behind it.  PSEG_OK / ROUTE_NO / error.
 struct TailArgs {
@@ -381,7 +379,7 @@ struct TailArgs {
 };
 int launch_conv_first_valu(const ConvArgs& a, hipStream_t st);
 int launch_deconv2_valu(const TailArgs& a, bool tail, hipStream_t st);
-int launch_conv_exact_mfma(const ConvArgs& a, hipStream_t st, bool* pooled = nullptr);   // matrix cores (pseg_exact_mfma.hip): PSEG_OK / ROUTE_NO / error
+int launch_conv_exact_mfma(const ConvArgs& a, hipStream_t st);   // matrix cores (pseg_exact_mfma.hip): PSEG_OK / ROUTE_NO / error
 // split form of UpSampling2D(2) -> Conv2D(k2) (pseg_upsplit.hip)
 struct UpSplit;
 int upsplit_create(UpSplit** out, const std::vector<float>& w, const std::vector<float>& bias, int Cin, int Cs0, int Cout, int CoS);

@@ -421,11 +421,10 @@ static int launch_conv1x1_exact(const ConvArgs& a, hipStream_t st) {
 
 // The routes of a float32 convolution, in the order they are asked (all give the same bits): the first layer on the vector ALU
 // (1 or 3 input channels: HBM-bound), the matrix cores (pseg_exact_mfma.hip), the 1x1 kernel, and the scalar kernel, which takes anything.
-int launch_conv_exact(const ConvArgs& a, hipStream_t st, bool* pooled) {
-    if (pooled) *pooled = false;
+int launch_conv_exact(const ConvArgs& a, hipStream_t st) {
     int rc;
     if ((rc = launch_conv_first_valu(a, st)) != ROUTE_NO) return rc;
-    if ((rc = launch_conv_exact_mfma(a, st, pooled)) != ROUTE_NO) return rc;
+    if ((rc = launch_conv_exact_mfma(a, st)) != ROUTE_NO) return rc;
     if ((rc = launch_conv1x1_exact(a, st)) != ROUTE_NO) return rc;
     dim3 grid(cdiv(a.Hout * a.Wout, 256), cdiv(a.Cout, COT));
     conv_exact_kernel<<<grid, 256, 0, st>>>(a);
@@ -650,12 +649,11 @@ bool page_slot_fits(Engine& e, int H, int W) {
 }
 
 // ---- the float32 forward pass: one function per layer kind, run_exact dispatches
-// One run: where its outputs go (each optional), and the two things one layer hands to a later one.
+// One run: where its outputs go (each optional), and the one thing a layer hands to a later one.
 struct ExactRun {
     Engine& e;
     float* logits; float* probs; int64_t* labels; uint8_t* labels_u8;
     hipStream_t st;
-    const Op* skip_pool = nullptr;      // the OP_POOL a conv's epilogue has already written
     const Op* fused_logits = nullptr;   // the OP_LOGITS that ran, with the argmax, inside the transposed conv in front of it
 };
 
@@ -718,18 +716,9 @@ static int forward_conv(ExactRun& r, Op& op) {
     a.pl = same_pad(a.Wout, a.Win, op.k, op.stride, op.transposed);
     a.add = op.add >= 0 ? (const float*)e.tensors[op.add].d : nullptr;
     a.dst = (float*)d.d;
-    // MaxPooling2D right behind this layer (every encoder stage of fcn / unet) can be pooled in the conv's epilogue
-    // (measured, fcn_skip 2048x1536: the fused form saves the pool passes -- 91 + 27 + 13 us -- and costs the three
-    // producers 84 + 40 + 12 us in their epilogues: no gain, so the separate streaming pass stays the default;
-    // PSEG_EXACT_POOL_FUSE=1 selects the fused form, tests keep both bit-identical)
-    const Op* nx = next_op(e, op);
-    const bool want_pool = nx && nx->type == OP_POOL && nx->src0 == op.dst && op.add < 0 && !(e.drop_key && op.dropout > 0.0f) &&
-                           PSEG_KNOB("PSEG_EXACT_POOL_FUSE");
-    if (want_pool) a.pool_dst = (float*)e.tensors[nx->dst].d;
-    bool pooled = false;
-    PSEG_TRY(launch_conv_exact(a, r.st, &pooled));
-    r.skip_pool = pooled ? nx : nullptr;
-    return PSEG_OK;
+    // (a MaxPooling2D behind this layer runs as its own streaming pass, forward_pool: pooling in this layer's epilogue saved
+    // the pass and cost the producers as much, HISTORY.md)
+    return launch_conv_exact(a, r.st);
 }
 
 // the crop (lib/model.py:29-42) is folded into the output extent: the input stays the padded canvas, output (y, x) reads input (y, x)
@@ -817,7 +806,6 @@ static int forward_bn(ExactRun& r, Op& op) {
 
 static int forward_pool(ExactRun& r, Op& op) {
     Engine& e = r.e;
-    if (&op == r.skip_pool) return PSEG_OK;   // done in the producing conv's epilogue
     const Tensor& s0 = e.tensors[op.src0];
     const size_t n = (size_t)(e.tH(s0) / 2) * (e.tW(s0) / 2) * s0.C;
     pool_exact_kernel<<<(int)std::min<size_t>((n + 255) / 256, 8192), 256, 0, r.st>>>((const float*)s0.d, e.tH(s0), e.tW(s0), s0.C, (float*)e.tensors[op.dst].d);

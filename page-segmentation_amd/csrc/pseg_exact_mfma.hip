@@ -722,50 +722,6 @@ __global__ __launch_bounds__(256) void conv_xb_kernel(ConvArgs a, int THH, int T
             *(float4*)(a.dst + off0) = make_float4(v[0], v[1], v[2], v[3]);
         }
     }
-    // ---- fused MaxPooling2D 2x2 (lib/model.py:54,59,64) of the tensor just stored: a wave holds both rows of its pixel
-    // pairs (accumulator tiles m and m + 2), the horizontal neighbour sits in lane p16 ^ 1.  The same comparisons in the same
-    // order as pool_exact_kernel -- (x, x+1) of the upper row, of the lower row, then the two winners -- so the same bits
-    // (signed zeros included); the separate pass re-read the whole tensor (377 MB after conv2).
-    if constexpr (MT == 4) {
-        if (a.pool_dst) {
-            const int Wp = a.Wout >> 1;
-            const int yp = (oy0 >> 1) + wave;
-#pragma unroll
-            for (int c = 0; c < 2; ++c) {
-                const int x = ox0 + c * 16 + p16;
-#pragma unroll
-                for (int t = 0; t < NT; ++t) {
-                    const int n0 = co_base + t * 16 + 4 * g;
-                    float o[4];
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int co = n0 + r < Ntot ? n0 + r : 0;
-                        float u0 = a.bias ? acc[c][t][r] + a.bias[co] : acc[c][t][r];
-                        float u1 = a.bias ? acc[2 + c][t][r] + a.bias[co] : acc[2 + c][t][r];
-                        if (a.relu) { u0 = u0 > 0.0f ? u0 : 0.0f; u1 = u1 > 0.0f ? u1 : 0.0f; }
-                        const float r0 = __shfl_xor(u0, 1), r1 = __shfl_xor(u1, 1);
-                        const float mt = u0 > r0 ? u0 : r0, mb = u1 > r1 ? u1 : r1;
-                        o[r] = mt > mb ? mt : mb;
-                    }
-                    if ((p16 & 1) || 2 * yp + 1 >= a.Hout || x + 1 >= a.Wout) continue;
-                    if (n0 >= Ntot) continue;
-                    float* od = a.pool_dst + ((size_t)yp * Wp + (x >> 1)) * a.Cout + n0;
-                    if (vecw == 4 && n0 + 3 < Ntot) {
-                        *(float4*)od = make_float4(o[0], o[1], o[2], o[3]);
-                    } else if (vecw >= 2) {
-                        if (n0 + 1 < Ntot) *(float2*)od = make_float2(o[0], o[1]);
-                        else od[0] = o[0];
-                        if (n0 + 3 < Ntot) *(float2*)(od + 2) = make_float2(o[2], o[3]);
-                        else if (n0 + 2 < Ntot) od[2] = o[2];
-                    } else {
-#pragma unroll
-                        for (int r = 0; r < 4; ++r)
-                            if (n0 + r < Ntot) od[r] = o[r];
-                    }
-                }
-            }
-        }
-    }
 }
 
 // wr[ky][kxp][ci][dx * rem + j] = w[ky][kxp - dx][ci][cmain + j] (0 when kxp - dx is not a tap): the left-over channels'
@@ -798,10 +754,9 @@ struct XChoice {
     int THH = 0, TWH = 0, Cp = 0;   // halo tile rows, columns; XF_FLAT: its channel pitch
     size_t lds = 0;
     dim3 grid;
-    bool pooled = false;            // the kernel also writes ConvArgs.pool_dst
 };
 
-// first layers (fewer than 8 input channels): K flattened across taps (one slab: the oracle's order), all-channel tile, no fused pool
+// first layers (fewer than 8 input channels): K flattened across taps (one slab: the oracle's order), all-channel tile
 static XChoice choose_flat(const ConvArgs& a, int Cin, int ntall) {
     XChoice c;
     if (a.deconv4) return c;
@@ -858,7 +813,7 @@ static XChoice choose_blocked(const ConvArgs& a, int Cin, int ntall) {
     const int tiles = cdiv(a.Wout, XTW) * cdiv(a.Hout, TH);
     const int tail_ch = Cin % XCB;                              // channels of the last slab (0: a full one)
     c.tailk = (tail_ch == 0 || tail_ch > 12) ? 0 : (tail_ch + 3) / 4;
-    if (rem_form_pays(a, Cin, c.MT, tiles)) {                   // (no fused pool in this form: the caller pools)
+    if (rem_form_pays(a, Cin, c.MT, tiles)) {
         c.family = XF_BLOCKED_REM;
         c.rem = a.Cout % 16;
         c.ntm = c.NT = a.Cout / 16;
@@ -866,7 +821,6 @@ static XChoice choose_blocked(const ConvArgs& a, int Cin, int ntall) {
     } else {
         c.family = XF_BLOCKED;
         choose_cout_split(ntall, tiles, &c.NT, &c.nblk);
-        c.pooled = a.pool_dst != nullptr && c.MT == 4 && a.stride == 1 && !a.deconv4 && !a.add && !(a.Hout & 1) && !(a.Wout & 1);
     }
     c.grid = dim3(tiles, c.nblk);
     return c;
@@ -929,20 +883,16 @@ static int launch_blocked(const ConvArgs& a, const XChoice& c, hipStream_t st) {
     return ROUTE_NO;
 }
 
-// PSEG_OK when the layer was launched on a matrix-core kernel (*pooled: with ConvArgs.pool_dst written too), ROUTE_NO when it is
-// not one for them (the caller falls back to the 1x1 / scalar kernels: a handful of output channels), an error otherwise.
-int launch_conv_exact_mfma(const ConvArgs& a_in, hipStream_t st, bool* pooled) {
-    if (pooled) *pooled = false;
+// PSEG_OK when the layer was launched on a matrix-core kernel, ROUTE_NO when it is not one for them (the caller falls back to the
+// 1x1 / scalar kernels: a handful of output channels), an error otherwise.
+int launch_conv_exact_mfma(const ConvArgs& a_in, hipStream_t st) {
     const XChoice c = choose_exact_mfma(a_in);
     if (c.family == XF_NONE) return ROUTE_NO;
     if (c.family == XF_BLOCKED_REM) prepare_wrem(a_in, c, st);
     ConvArgs a = a_in;                         // the kernel's copy: what the choice says, nothing else, differs from the caller's
     if (const char* dv = PSEG_DIAG_KNOB("PSEG_XM_DBG")) a.dbg = atoi(dv);   // wrong-result timing switches: diagnostic build only
-    if (!c.pooled) a.pool_dst = nullptr;
     if (c.family == XF_BLOCKED_REM) a.wrem = a.wrem_buf;
-    const int rc = c.family == XF_FLAT ? launch_flat(a, c, st) : launch_blocked(a, c, st);
-    if (pooled) *pooled = rc == PSEG_OK && c.pooled;
-    return rc;
+    return c.family == XF_FLAT ? launch_flat(a, c, st) : launch_blocked(a, c, st);
 }
 
 }  // namespace pseg

@@ -413,7 +413,7 @@ __global__ __launch_bounds__(256) void deconv2_valu_kernel(TailArgs a) {
 // PSEG_OK = launched, ROUTE_NO = not a layer for this kernel
 int launch_conv_first_valu(const ConvArgs& a, hipStream_t st) {
     if (PSEG_KNOB("PSEG_EXACT_NO_VALU")) return ROUTE_NO;
-    if (a.C1 || a.C0 > 3 || a.KH != a.KW || a.stride != 1 || a.up0 || a.in_relu || a.mask || a.deconv4 || a.pool_dst ||
+    if (a.C1 || a.C0 > 3 || a.KH != a.KW || a.stride != 1 || a.up0 || a.in_relu || a.mask || a.deconv4 ||
         a.out_sy || a.out_sx || a.Cout < 8 || a.Cout > 256)
         return ROUTE_NO;
     const int K = a.KH;

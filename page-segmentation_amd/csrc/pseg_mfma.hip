@@ -1326,10 +1326,7 @@ constexpr int WS_TILE0 = 16;      // the tiles start 16 bytes into LDS: a pixel'
 
 // PAIRC2: channels 16-19 of a pixel are written twice -- into bytes 32-39 of its own 48-byte slot and into bytes 40-47 of its
 // LEFT neighbour's slot -- so that the k-chunk "third chunk under tap kx" also carries tap kx + 1 (see pair_chunks): 17 k-steps.
-// FORM: the consumers' tile loop -- 0: one k-loop per tile, epilogue after it (default); 1: two phases of four pixel tiles, the
-// epilogue of the previous half between the MFMAs (PSEG_WS_FORM=1); 2: one k-loop per tile with the epilogue of the PREVIOUS
-// tile between its MFMAs, two accumulator sets (PSEG_WS_FORM=2).  All three produce the same bits.
-template <bool SKIPLOG, bool PAIRC2, int FORM = 0>
+template <bool SKIPLOG, bool PAIRC2>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv12_ws_kernel(MConv a) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     char* const smem = smem_raw + WS_TILE0;
@@ -1623,10 +1620,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 
     // =============================== CONSUMERS ===============================
     // A wave owns four rows x 32 pixels of the tile = eight 16-pixel tiles m (row m >> 1, column tile m & 1) x two cout tiles.
-    // Two forms of the tile loop (bit-identical results): the default runs ONE k-loop over all eight pixel tiles and then the
-    // epilogue; PSEG_WS_FORM=1 computes the tile in two phases of four pixel tiles (rows 0-1, then rows 2-3) and issues the
-    // epilogue of the half finished just before -- fused 2x2 max-pool (its row pairs lie inside a half), bf16 rounding, the
-    // skip-logits MFMAs, all stores -- in pieces between the current phase's MFMAs.
+    // The tile loop runs ONE k-loop over all eight pixel tiles (every A fragment serves eight of them) and then the epilogue --
+    // fused 2x2 max-pool, bf16 rounding, the skip-logits MFMAs, all stores -- half by half (rows 0-1, then rows 2-3: the pool's
+    // row pairs lie inside a half); the producer on the same SIMD gets the matrix pipe and most issue slots meanwhile.  Hiding
+    // the epilogue behind the consumer's own MFMAs was measured twice and lost both times (HISTORY.md).
     // B fragment of pixel tile m for k-step s: one ds_read_b128 at (tile + lane pixel + chunk offset of (s, g)) + an
     // immediate ((m >> 1) rows, (m & 1) * 16 pixels); A fragment (s, t): weights + lane * 16 + an immediate.  The 19 chunk
     // offsets of this lane group stay in registers for the whole kernel.
@@ -1652,9 +1649,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 
     f32x4 accA[4][NT], accB[4][NT];                            // the two halves: pixel tiles 0-3 (rows 0, 1) and 4-7 (rows 2, 3)
     uint2 pks[NT][4];                                          // bf16 pairs of the half being drained (B operand of the skip-logits MFMA)
-    // one piece of the epilogue of half `HB` (0: rows 0-1, 1: rows 2-3) of the tile at (doy, dox); `acc` holds it
+    // one piece of the epilogue of half `hb` (0: rows 0-1, 1: rows 2-3) of the tile at (doy, dox); `acc` holds it
     // P(t2, c): column tile c (local tiles c and c + 2 are vertical neighbours): rounding + pool + stores of cout tile t2
-    auto piece_P = [&](f32x4 (&acc)[4][NT], int hb, int doy, int dox, bool valid, auto t2c, auto cc) {
+    auto piece_P = [&](f32x4 (&acc)[4][NT], int hb, int doy, int dox, auto t2c, auto cc) {
         constexpr int t2 = decltype(t2c)::value, c = decltype(cc)::value;
         const unsigned noff = t2 == 0 ? noff0 : noff1;
         float q[4];
@@ -1664,320 +1661,98 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         for (int h = 0; h < 2; ++h) {
             const f32x4 v = acc[c + 2 * h][t2];
             const uint2 pk = make_uint2(pk_bf16(v[0], v[1]), pk_bf16(v[2], v[3]));
-            if constexpr (SKIPLOG) { if constexpr (FORM != 2) pks[t2][c + 2 * h] = pk; }
+            if constexpr (SKIPLOG) pks[t2][c + 2 * h] = pk;
             else {
                 const int y = doy + wave * (MT / 2) + 2 * hb + h, x = dox + c * 16 + p16;
-                const unsigned o = (valid && y < a.Hout && x < a.Wout && noff != OOBS) ? (unsigned)(y * a.Wout + x) * (unsigned)(CsO * 2) + noff : OOBS;
+                const unsigned o = (y < a.Hout && x < a.Wout && noff != OOBS) ? (unsigned)(y * a.Wout + x) * (unsigned)(CsO * 2) + noff : OOBS;
                 __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, pk), rd, o, 0, 0);
             }
         }
         const int y = (doy >> 1) + wave * (MT / 4) + hb;
         const int x = (dox >> 1) + ((c * 16 + p16) >> 1);
-        const bool ok = valid && !(p16 & 1) && y < Ho2 && x < Wo2 && noff != OOBS;
+        const bool ok = !(p16 & 1) && y < Ho2 && x < Wo2 && noff != OOBS;
         const unsigned o = ok ? (unsigned)(y * Wo2 + x) * (unsigned)(CsO * 2) + noff : OOBS;
         const uint2 pk = make_uint2(pk_bf16(q[0], q[1]), pk_bf16(q[2], q[3]));
         __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, pk), rp, o, 0, 0);
     };
     // S(c): the skip-logits products of local tiles c and c + 2 (both cout tiles rounded by then)
-    auto piece_S = [&](int hb, int doy, int dox, bool valid, auto cc, f32x4 (*sacc)[NT] = nullptr) {
+    auto piece_S = [&](int hb, int doy, int dox, auto cc) {
         constexpr int c = decltype(cc)::value;
         if constexpr (SKIPLOG) {
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 const int lm = c + 2 * h;
                 f32x4 z = f32x4{0.f, 0.f, 0.f, 0.f};
-                uint4 bq;
-                if constexpr (FORM == 2) {   // no registers for the pairs piece_P rounded: round them again from the accumulators
-                    const f32x4 v0 = sacc[lm][0], v1 = sacc[lm][1];
-                    bq = make_uint4(pk_bf16(v0[0], v0[1]), pk_bf16(v0[2], v0[3]), pk_bf16(v1[0], v1[1]), pk_bf16(v1[2], v1[3]));
-                } else {
-                    bq = make_uint4(pks[0][lm].x, pks[0][lm].y, pks[1][lm].x, pks[1][lm].y);
-                }
+                const uint4 bq = make_uint4(pks[0][lm].x, pks[0][lm].y, pks[1][lm].x, pks[1][lm].y);
                 z = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wq, __builtin_bit_cast(bf16x8, bq), z, 0, 0, 0);
                 const int y = doy + wave * (MT / 2) + 2 * hb + h, x = dox + c * 16 + p16;
-                const unsigned o = (valid && y < a.Hout && x < a.Wout && 4 * g < a.skip_CP) ? ((unsigned)(y * a.Wout + x) * (unsigned)a.skip_CP + 4u * g) * 4u : OOBS;
+                const unsigned o = (y < a.Hout && x < a.Wout && 4 * g < a.skip_CP) ? ((unsigned)(y * a.Wout + x) * (unsigned)a.skip_CP + 4u * g) * 4u : OOBS;
                 __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, z), rs, o, 0, 0);
             }
         }
     };
-    // one phase: accumulate half `hb` of the tile in `in_t` into `acc`; between the MFMAs, drain `dacc` = half `dhb` of the tile
-    // at (doy, dox) (valid = such a half exists)
-    auto phase = [&](const char* in_t, f32x4 (&acc)[4][NT], auto hbc, f32x4 (&dacc)[4][NT], int dhb, int doy, int dox, bool valid) {
-        constexpr int hb = decltype(hbc)::value;
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {                           // start value = bias (the first MFMA's C operand: no add later)
-            acc[m][0] = f32x4{bias0.x, bias0.y, bias0.z, bias0.w};
-            acc[m][1] = f32x4{bias1.x, bias1.y, bias1.z, bias1.w};
-        }
-        bf16x8 xs[2][4], ws2[2][NT];
-#define WS_LOAD(SET, S)                                                                                   \
-        {                                                                                                 \
-            const char* va_ = in_t + offv[S];                                                             \
-            ws2[SET][0] = *(const bf16x8*)(wb + ((S) * NT) * 1024);                                       \
-            _Pragma("unroll") for (int m = 0; m < 4; ++m)                                                 \
-                xs[SET][m] = *(const bf16x8*)(va_ + (2 * hb + (m >> 1)) * ROWP + (m & 1) * 16 * PS2);     \
-            ws2[SET][1] = *(const bf16x8*)(wb + ((S) * NT + 1) * 1024);                                   \
-        }
-        WS_LOAD(0, 0)
-#pragma unroll
-        for (int s2 = 0; s2 < KSTEPS; ++s2) {
-            __builtin_amdgcn_sched_barrier(0);                  // a k-step is one scheduling region
-            if (s2 + 1 < KSTEPS) WS_LOAD((s2 + 1) & 1, s2 + 1)
-#pragma unroll
-            for (int t2 = 0; t2 < NT; ++t2)
-#pragma unroll
-                for (int m = 0; m < 4; ++m)
-                    acc[m][t2] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ws2[s2 & 1][t2], xs[s2 & 1][m], acc[m][t2], 0, 0, 0);
-            // the drained half's epilogue, one piece per k-step (P needs nothing; S(c) needs P(0, c) and P(1, c))
-            if (s2 == 1) piece_P(dacc, dhb, doy, dox, valid, std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
-            if (s2 == 3) piece_P(dacc, dhb, doy, dox, valid, std::integral_constant<int, 1>{}, std::integral_constant<int, 0>{});
-            if (s2 == 5) piece_S(dhb, doy, dox, valid, std::integral_constant<int, 0>{});
-            if (s2 == 7) piece_P(dacc, dhb, doy, dox, valid, std::integral_constant<int, 0>{}, std::integral_constant<int, 1>{});
-            if (s2 == 9) piece_P(dacc, dhb, doy, dox, valid, std::integral_constant<int, 1>{}, std::integral_constant<int, 1>{});
-            if (s2 == 11) piece_S(dhb, doy, dox, valid, std::integral_constant<int, 1>{});
-            // issue order: the address add, then behind each MFMA one fragment read of the next step (six of them) and two
-            // VALU instructions of the epilogue piece
-            if (s2 + 1 < KSTEPS) __builtin_amdgcn_sched_group_barrier(0x002, 1, 0);
-#pragma unroll
-            for (int r = 0; r < 8; ++r) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                if (r < 6 && s2 + 1 < KSTEPS) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x002, PSEG_WS_EPI_VALU, 0);
-            }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#undef WS_LOAD
-    };
     long long tk = 0, te = 0, tw = 0;
-    int poy = 0, pox = 0;
-    if constexpr (FORM == 2) {
-        // One k-loop per tile (every A fragment serves eight pixel tiles) AND no epilogue phase: the finished tile's accumulators
-        // stay in a second register set and drain in twelve pieces between the MFMAs of the next tile's k-loop.
-        f32x4 accC[4][NT], accD[4][NT];                         // second accumulator set (halves as accA / accB)
-        auto tile_pass = [&](const char* in_t, f32x4 (&cA)[4][NT], f32x4 (&cB)[4][NT], f32x4 (&dA)[4][NT], f32x4 (&dB)[4][NT],
-                             int doy, int dox, bool valid) {
-            {   // (the bias is re-read per tile: eight registers that would otherwise live through the k-loop)
-                const float4 bb0 = *(const float4*)(a.bias + 4 * g), bb1 = *(const float4*)(a.bias + 16 + 4 * g);
-#pragma unroll
-                for (int m = 0; m < 4; ++m) {
-                    cA[m][0] = cB[m][0] = f32x4{bb0.x, bb0.y, bb0.z, bb0.w};
-                    cA[m][1] = cB[m][1] = f32x4{bb1.x, bb1.y, bb1.z, bb1.w};
-                }
-            }
-            // Registers are the limit of this form (two accumulator sets): ONE set of pixel fragments -- the MFMAs of a k-step run
-            // pixel tile by pixel tile (both cout tiles of tile m back to back), and the next step's fragment of tile m is read
-            // into the same registers right behind them, 14 MFMAs before its first use -- two sets of kernel fragments, and the 17
-            // chunk offsets come from the LDS table one k-step ahead instead of living in registers.
-            bf16x8 xs[MT], ws2[2][NT];
-            const char* const bt = in_t + (wave * (MT / 2)) * ROWP + p16 * PS2;
-            const int* const tbl = tab_l + g;
-            int toff[2];
-            toff[0] = tbl[0];
-            toff[1] = tbl[4];
-            {
-                const char* va_ = bt + toff[0];
-                ws2[0][0] = *(const bf16x8*)(wb);
-#pragma unroll
-                for (int m = 0; m < MT; ++m) xs[m] = *(const bf16x8*)(va_ + (m >> 1) * ROWP + (m & 1) * 16 * PS2);
-                ws2[0][1] = *(const bf16x8*)(wb + 1024);
-            }
-#pragma unroll
-            for (int s2 = 0; s2 < KSTEPS; ++s2) {
-                __builtin_amdgcn_sched_barrier(0);
-                const bool more = s2 + 1 < KSTEPS;
-                const char* va_ = bt + toff[(s2 + 1) & 1];
-                if (more) {
-                    ws2[(s2 + 1) & 1][0] = *(const bf16x8*)(wb + ((s2 + 1) * NT) * 1024);
-                    ws2[(s2 + 1) & 1][1] = *(const bf16x8*)(wb + ((s2 + 1) * NT + 1) * 1024);
-                }
-#pragma unroll
-                for (int m = 0; m < MT; ++m) {
-                    f32x4& a0_ = m < 4 ? cA[m][0] : cB[m - 4][0];
-                    f32x4& a1_ = m < 4 ? cA[m][1] : cB[m - 4][1];
-                    a0_ = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ws2[s2 & 1][0], xs[m], a0_, 0, 0, 0);
-                    a1_ = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ws2[s2 & 1][1], xs[m], a1_, 0, 0, 0);
-                    if (more) xs[m] = *(const bf16x8*)(va_ + (m >> 1) * ROWP + (m & 1) * 16 * PS2);
-                }
-                if (s2 + 2 < KSTEPS) toff[s2 & 1] = tbl[(s2 + 2) * 4];        // slot s2 & 1 was consumed by the previous region's reads
-                // the previous tile's epilogue: half 0 in k-steps 1-6, half 1 in k-steps 7-12
-                if (s2 >= 1 && s2 <= 12) {
-                    const int hb = s2 <= 6 ? 0 : 1, pc = (s2 - 1) % 6;
-                    f32x4 (&hacc)[4][NT] = s2 <= 6 ? dA : dB;
-                    if (pc == 0) piece_P(hacc, hb, doy, dox, valid, std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
-                    if (pc == 1) piece_P(hacc, hb, doy, dox, valid, std::integral_constant<int, 1>{}, std::integral_constant<int, 0>{});
-                    if (pc == 2) piece_S(hb, doy, dox, valid, std::integral_constant<int, 0>{}, hacc);
-                    if (pc == 3) piece_P(hacc, hb, doy, dox, valid, std::integral_constant<int, 0>{}, std::integral_constant<int, 1>{});
-                    if (pc == 4) piece_P(hacc, hb, doy, dox, valid, std::integral_constant<int, 1>{}, std::integral_constant<int, 1>{});
-                    if (pc == 5) piece_S(hb, doy, dox, valid, std::integral_constant<int, 1>{}, hacc);
-                }
-                // issue order: the address add and the two kernel-fragment reads, then per pixel tile its two MFMAs, the read of its
-                // next fragment and two epilogue VALU instructions
-                if (more) {
-                    __builtin_amdgcn_sched_group_barrier(0x002, 1, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-                }
-#pragma unroll
-                for (int r = 0; r < MT; ++r) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-                    if (more) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
-                }
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        };
-        // two tiles per trip: the accumulator sets keep their roles (A/B accumulate even tiles, C/D odd ones), so no register
-        // moves at the loop edge
-        auto origin = [&](int i, int& oy, int& ox) {
-            const int t = xcd_tile((int)blockIdx.x + i * (int)gridDim.x);
-            const int ty = t / tiles_x, tx = t - ty * tiles_x;
-            oy = ty * TH; ox = tx * TW;
-        };
-        for (int i = 0; i < n_my; i += 2) {
-            long long c0 = a.trace ? (long long)__builtin_amdgcn_s_memtime() : 0;
-            int oy0, ox0;
-            origin(i, oy0, ox0);
-            tile_pass(smem, accA, accB, accC, accD, poy, pox, i > 0);              // even tile: buffer 0
-            poy = oy0; pox = ox0;
-            long long c2 = a.trace ? (long long)__builtin_amdgcn_s_memtime() : 0;
-            lds_barrier();
-            if (a.trace) { tk += c2 - c0; tw += (long long)__builtin_amdgcn_s_memtime() - c2; }
-            if (i + 1 < n_my) {
-                c0 = a.trace ? (long long)__builtin_amdgcn_s_memtime() : 0;
-                origin(i + 1, oy0, ox0);
-                tile_pass(smem + TB, accC, accD, accA, accB, poy, pox, true);      // odd tile: buffer 1
-                poy = oy0; pox = ox0;
-                c2 = a.trace ? (long long)__builtin_amdgcn_s_memtime() : 0;
-                lds_barrier();
-                if (a.trace) { tk += c2 - c0; tw += (long long)__builtin_amdgcn_s_memtime() - c2; }
-            }
-        }
-        {   // the last tile drains on its own
-            const long long c1 = a.trace ? (long long)__builtin_amdgcn_s_memtime() : 0;
-            asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7" ::: "memory");
-            const bool odd = (n_my & 1) == 0;                     // the last tile (n_my - 1) used set C/D when its index is odd
-#pragma unroll
-            for (int hb = 0; hb < 2; ++hb) {
-                if (odd) {
-                    f32x4 (&hacc)[4][NT] = hb == 0 ? accC : accD;
-                    piece_P(hacc, hb, poy, pox, n_my > 0, std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
-                    piece_P(hacc, hb, poy, pox, n_my > 0, std::integral_constant<int, 1>{}, std::integral_constant<int, 0>{});
-                    piece_S(hb, poy, pox, n_my > 0, std::integral_constant<int, 0>{}, hacc);
-                    piece_P(hacc, hb, poy, pox, n_my > 0, std::integral_constant<int, 0>{}, std::integral_constant<int, 1>{});
-                    piece_P(hacc, hb, poy, pox, n_my > 0, std::integral_constant<int, 1>{}, std::integral_constant<int, 1>{});
-                    piece_S(hb, poy, pox, n_my > 0, std::integral_constant<int, 1>{}, hacc);
-                } else {
-                    f32x4 (&hacc)[4][NT] = hb == 0 ? accA : accB;
-                    piece_P(hacc, hb, poy, pox, n_my > 0, std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
-                    piece_P(hacc, hb, poy, pox, n_my > 0, std::integral_constant<int, 1>{}, std::integral_constant<int, 0>{});
-                    piece_S(hb, poy, pox, n_my > 0, std::integral_constant<int, 0>{}, hacc);
-                    piece_P(hacc, hb, poy, pox, n_my > 0, std::integral_constant<int, 0>{}, std::integral_constant<int, 1>{});
-                    piece_P(hacc, hb, poy, pox, n_my > 0, std::integral_constant<int, 1>{}, std::integral_constant<int, 1>{});
-                    piece_S(hb, poy, pox, n_my > 0, std::integral_constant<int, 1>{}, hacc);
-                }
-            }
-            if (a.trace) te += (long long)__builtin_amdgcn_s_memtime() - c1;
-        }
-        if (a.trace && lane == 0) {
-            unsigned long long* o = a.trace + ((size_t)blockIdx.x * 8 + wave) * 4;
-            o[0] = (unsigned long long)tk; o[1] = (unsigned long long)te; o[2] = (unsigned long long)tw; o[3] = (unsigned long long)n_my;
-        }
-        return;
-    }
-    if constexpr (FORM == 0) {
-        // Default form: the whole tile in ONE k-loop (eight pixel tiles per A fragment) and the epilogue after it; the producer
-        // on the same SIMD gets the matrix pipe and most issue slots meanwhile.  The two-phase form below (PSEG_WS_FORM=1) hides
-        // the epilogue behind the consumer's own MFMAs but reads every A fragment twice (+17 % LDS reads): 99.5 vs 94.5 us.
-        for (int i = 0; i < n_my; ++i) {
-            const long long c0 = a.trace ? (long long)__builtin_amdgcn_s_memtime() : 0;
-            const char* in_t = smem + (i & 1) * TB;
-            const int t = xcd_tile((int)blockIdx.x + i * (int)gridDim.x);
-            const int ty = t / tiles_x, tx = t - ty * tiles_x;
-            const int oy0 = ty * TH, ox0 = tx * TW;
-#pragma unroll
-            for (int m = 0; m < 4; ++m) {
-                accA[m][0] = accB[m][0] = f32x4{bias0.x, bias0.y, bias0.z, bias0.w};
-                accA[m][1] = accB[m][1] = f32x4{bias1.x, bias1.y, bias1.z, bias1.w};
-            }
-            {
-                bf16x8 xs[2][MT], ws2[2][NT];
-#define WS_LOAD8(SET, S)                                                                              \
-                {                                                                                     \
-                    const char* va_ = in_t + offv[S];                                                 \
-                    ws2[SET][0] = *(const bf16x8*)(wb + ((S) * NT) * 1024);                           \
-                    _Pragma("unroll") for (int m = 0; m < MT; ++m)                                    \
-                        xs[SET][m] = *(const bf16x8*)(va_ + (m >> 1) * ROWP + (m & 1) * 16 * PS2);    \
-                    ws2[SET][1] = *(const bf16x8*)(wb + ((S) * NT + 1) * 1024);                       \
-                }
-                WS_LOAD8(0, 0)
-#pragma unroll
-                for (int s2 = 0; s2 < KSTEPS; ++s2) {
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (s2 + 1 < KSTEPS) WS_LOAD8((s2 + 1) & 1, s2 + 1)
-#pragma unroll
-                    for (int t2 = 0; t2 < NT; ++t2)
-#pragma unroll
-                        for (int m = 0; m < MT; ++m) {
-                            f32x4& ac = m < 4 ? accA[m][t2] : accB[m - 4][t2];
-                            ac = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ws2[s2 & 1][t2], xs[s2 & 1][m], ac, 0, 0, 0);
-                        }
-                    if (s2 + 1 < KSTEPS) {
-                        __builtin_amdgcn_sched_group_barrier(0x002, 1, 0);
-#pragma unroll
-                        for (int r = 0; r < 10; ++r) {
-                            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                        }
-                        __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);
-                    }
-                }
-                __builtin_amdgcn_sched_barrier(0);
-#undef WS_LOAD8
-            }
-            const long long c1 = a.trace ? (long long)__builtin_amdgcn_s_memtime() : 0;
-            asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7" ::: "memory");
-#pragma unroll
-            for (int hb = 0; hb < 2; ++hb) {
-                f32x4 (&hacc)[4][NT] = hb == 0 ? accA : accB;
-                piece_P(hacc, hb, oy0, ox0, true, std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
-                piece_P(hacc, hb, oy0, ox0, true, std::integral_constant<int, 1>{}, std::integral_constant<int, 0>{});
-                piece_S(hb, oy0, ox0, true, std::integral_constant<int, 0>{});
-                piece_P(hacc, hb, oy0, ox0, true, std::integral_constant<int, 0>{}, std::integral_constant<int, 1>{});
-                piece_P(hacc, hb, oy0, ox0, true, std::integral_constant<int, 1>{}, std::integral_constant<int, 1>{});
-                piece_S(hb, oy0, ox0, true, std::integral_constant<int, 1>{});
-            }
-            const long long c2 = a.trace ? (long long)__builtin_amdgcn_s_memtime() : 0;
-            lds_barrier();
-            if (a.trace) { tk += c1 - c0; te += c2 - c1; tw += (long long)__builtin_amdgcn_s_memtime() - c2; }
-        }
-        if (a.trace && lane == 0) {
-            unsigned long long* o = a.trace + ((size_t)blockIdx.x * 8 + wave) * 4;
-            o[0] = (unsigned long long)tk; o[1] = (unsigned long long)te; o[2] = (unsigned long long)tw; o[3] = (unsigned long long)n_my;
-        }
-        return;
-    }
     for (int i = 0; i < n_my; ++i) {
         const long long c0 = a.trace ? (long long)__builtin_amdgcn_s_memtime() : 0;
         const char* in_t = smem + (i & 1) * TB;
         const int t = xcd_tile((int)blockIdx.x + i * (int)gridDim.x);
         const int ty = t / tiles_x, tx = t - ty * tiles_x;
         const int oy0 = ty * TH, ox0 = tx * TW;
-        phase(in_t, accA, std::integral_constant<int, 0>{}, accB, 1, poy, pox, i > 0);     // rows 0-1; drains rows 2-3 of the previous tile
-        phase(in_t, accB, std::integral_constant<int, 1>{}, accA, 0, oy0, ox0, true);      // rows 2-3; drains rows 0-1 of this tile
-        poy = oy0; pox = ox0;
-        const long long c2 = a.trace ? (long long)__builtin_amdgcn_s_memtime() : 0;
-        lds_barrier();                                         // tile i drained, tile i + 1 full
-        if (a.trace) { tk += c2 - c0; tw += (long long)__builtin_amdgcn_s_memtime() - c2; }
-    }
-    {   // rows 2-3 of the last tile: nothing left to hide behind
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+            accA[m][0] = accB[m][0] = f32x4{bias0.x, bias0.y, bias0.z, bias0.w};
+            accA[m][1] = accB[m][1] = f32x4{bias1.x, bias1.y, bias1.z, bias1.w};
+        }
+        {
+            bf16x8 xs[2][MT], ws2[2][NT];
+#define WS_LOAD8(SET, S)                                                                          \
+            {                                                                                     \
+                const char* va_ = in_t + offv[S];                                                 \
+                ws2[SET][0] = *(const bf16x8*)(wb + ((S) * NT) * 1024);                           \
+                _Pragma("unroll") for (int m = 0; m < MT; ++m)                                    \
+                    xs[SET][m] = *(const bf16x8*)(va_ + (m >> 1) * ROWP + (m & 1) * 16 * PS2);    \
+                ws2[SET][1] = *(const bf16x8*)(wb + ((S) * NT + 1) * 1024);                       \
+            }
+            WS_LOAD8(0, 0)
+#pragma unroll
+            for (int s2 = 0; s2 < KSTEPS; ++s2) {
+                __builtin_amdgcn_sched_barrier(0);
+                if (s2 + 1 < KSTEPS) WS_LOAD8((s2 + 1) & 1, s2 + 1)
+#pragma unroll
+                for (int t2 = 0; t2 < NT; ++t2)
+#pragma unroll
+                    for (int m = 0; m < MT; ++m) {
+                        f32x4& ac = m < 4 ? accA[m][t2] : accB[m - 4][t2];
+                        ac = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ws2[s2 & 1][t2], xs[s2 & 1][m], ac, 0, 0, 0);
+                    }
+                if (s2 + 1 < KSTEPS) {
+                    __builtin_amdgcn_sched_group_barrier(0x002, 1, 0);
+#pragma unroll
+                    for (int r = 0; r < 10; ++r) {
+                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+                    }
+                    __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#undef WS_LOAD8
+        }
         const long long c1 = a.trace ? (long long)__builtin_amdgcn_s_memtime() : 0;
-        asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7" ::: "memory");   // (inline-asm readers of accumulator registers follow)
-        piece_P(accB, 1, poy, pox, n_my > 0, std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
-        piece_P(accB, 1, poy, pox, n_my > 0, std::integral_constant<int, 1>{}, std::integral_constant<int, 0>{});
-        piece_S(1, poy, pox, n_my > 0, std::integral_constant<int, 0>{});
-        piece_P(accB, 1, poy, pox, n_my > 0, std::integral_constant<int, 0>{}, std::integral_constant<int, 1>{});
-        piece_P(accB, 1, poy, pox, n_my > 0, std::integral_constant<int, 1>{}, std::integral_constant<int, 1>{});
-        piece_S(1, poy, pox, n_my > 0, std::integral_constant<int, 1>{});
-        if (a.trace) te += (long long)__builtin_amdgcn_s_memtime() - c1;
+        asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7" ::: "memory");
+#pragma unroll
+        for (int hb = 0; hb < 2; ++hb) {
+            f32x4 (&hacc)[4][NT] = hb == 0 ? accA : accB;
+            piece_P(hacc, hb, oy0, ox0, std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
+            piece_P(hacc, hb, oy0, ox0, std::integral_constant<int, 1>{}, std::integral_constant<int, 0>{});
+            piece_S(hb, oy0, ox0, std::integral_constant<int, 0>{});
+            piece_P(hacc, hb, oy0, ox0, std::integral_constant<int, 0>{}, std::integral_constant<int, 1>{});
+            piece_P(hacc, hb, oy0, ox0, std::integral_constant<int, 1>{}, std::integral_constant<int, 1>{});
+            piece_S(hb, oy0, ox0, std::integral_constant<int, 1>{});
+        }
+        const long long c2 = a.trace ? (long long)__builtin_amdgcn_s_memtime() : 0;
+        lds_barrier();
+        if (a.trace) { tk += c1 - c0; te += c2 - c1; tw += (long long)__builtin_amdgcn_s_memtime() - c2; }
     }
     if (a.trace && lane == 0) {
         unsigned long long* o = a.trace + ((size_t)blockIdx.x * 8 + wave) * 4;
@@ -4065,7 +3840,6 @@ struct MfmaPlan {
     bool pp_shape = false;      // a conv3 / conv4 shape planned for conv_pp_kernel: kept off conv_sp_kernel and the layer-major page launches
     bool pp = false;            // ... that conv_pp_kernel can run (one channel block), when the page has enough tiles
     bool ws = false;            // conv12_ws_kernel (fused conv1 + conv2, wave-specialised)
-    int ws_form = 0;            // ... its alternative tile loops (PSEG_WS_FORM = 1 / 2: the default packing with skip logits only)
     bool persist_f1 = false;    // fused conv1 + conv2 on conv_mfma_kernel: two persistent workgroups per CU
     bool persist_s2 = false;    // single-block stride-2 k3 layer: persistent instances, when a page has many tiles
     bool triple = false;        // conv_mfma_kernel as tile triples (three teams on one weight ring): shape, switches and its ring layout below
@@ -4506,9 +4280,12 @@ static int pack_conv1(const PackCtx& c, int ks1) {
     for (int i = 0; i < 256; ++i) lut[i] = rb((float)i / 255.0f);
     PSEG_TRY(upload(&P->d_wf, wf));
     PSEG_TRY(upload(&P->d_lut, lut));
+    const int nt = cdiv(Cout, 16);
+    PSEG_TRY(upload(&P->d_bias, padded(c.bias, Cout, std::max(nt * 16, 32))));
+    if (k == 3) return PSEG_OK;                               // conv1_rows_kernel reads the f32 weights only
     // MFMA form: A fragments [k-step][cout tile][lane][8]; lane = (cout & 15, g), k-step s:
     // kernel row ky = 4s + g, element j = kernel column kx
-    const int nks = (k + 3) / 4, nt = cdiv(Cout, 16);
+    const int nks = (k + 3) / 4;
     std::vector<uint16_t> apk((size_t)nks * nt * 64 * 8, 0);
     for (int sidx = 0; sidx < nks; ++sidx)
         for (int q = 0; q < nt; ++q)
@@ -4519,7 +4296,6 @@ static int pack_conv1(const PackCtx& c, int ks1) {
                     apk[(((size_t)sidx * nt + q) * 64 + l) * 8 + j] = f2bf(w[((size_t)ky * k + j) * Cout + co]);
             }
     PSEG_TRY(upload(&P->d_wpk, apk));
-    PSEG_TRY(upload(&P->d_bias, padded(c.bias, Cout, std::max(nt * 16, 32))));
     if (k == 5 && Cout <= 32) {
         // v_mfma_f32_32x32x16_bf16 form: A fragment of k-step s, lane l = (cout l % 32, half l / 32): kernel row 2 s + half,
         // element j = kernel column (rows / columns past the 5 x 5 kernel carry zeros)
@@ -4560,15 +4336,14 @@ static int pack_logits(const PackCtx& c) {
     return upload(&P->d_bias, padded(c.bias, Cout, 16));
 }
 
-// upsample -> k2 conv of the deep decoder levels: GEMM over the source pixels + gather-sum (pseg_upsplit.hip).
-// Measured at 2048x1536 (unet): 1024->512 216 -> ~75 us, 512->256 228 -> ~110 us, 256->128 246 -> ~185 us; at
-// 128->64 the two extra passes over the full-resolution tensor cost more than the direct kernel (PSEG_UPSPLIT_MIN_CIN).
+// upsample -> k2 conv of the decoder levels: GEMM over the source pixels, outputs summed by the same workgroup (pseg_upsplit.hip).
+// Measured at 2048x1536 (unet), direct kernel -> this: 1024->512 216 -> 80 us, 512->256 228 -> 94 us, 256->128 246 -> 141 us,
+// 128->64 258 -> 200 us.
 static bool takes_upsplit(const PackCtx& c) {
     const Op& op = c.op;
     if (!(op.type == OP_CONV && op.k == 2 && op.up0 && !c.s1 && op.stride == 1 && !op.in_relu && op.add < 0 && op.pool_dst < 0 &&
           op.tail_logits < 0 && op.fuse1 < 0 && !op.transposed && !PSEG_KNOB("PSEG_NO_UPSPLIT") && c.spec)) return false;
-    // (the two-pass form lost to the direct kernel at 128 -> 64 channels on the full-resolution map; the fused form does not)
-    return c.Cin >= (PSEG_KNOB("PSEG_UPSPLIT_TWO_PASS") ? 256 : 64);
+    return c.Cin >= 64;
 }
 
 // ---- generic MFMA conv / deconv2 ------------------------------------------------------------
@@ -4770,9 +4545,6 @@ static void plan_persistent(const PackCtx& c, const TileRing& R) {
     // wave-specialised persistent kernel (conv12_ws_kernel): one 512-thread workgroup per CU, two input tiles + the resident weights
     // in LDS.  PSEG_NO_WS=1 falls back to the every-wave-does-everything fused instance above.
     P->ws = P->persist_f1 && !c.deconv && P->MT == 8 && P->NT == 2 && c.KS == 5 && R.sigma == 3 && op.pool_dst >= 0 && op.add < 0 && !op.in_relu && !op.relu && c.ws_on;
-    // (the alternative tile loops exist for the default packing only)
-    const char* const ws_form = PSEG_KNOB("PSEG_WS_FORM");
-    P->ws_form = (ws_form && P->ws && P->pairc2 && op.skiplog >= 0 && (atoi(ws_form) == 1 || atoi(ws_form) == 2)) ? atoi(ws_form) : 0;
     // ... and the k3 stride-2 single-block layers whose instances exist (launch_generic_any2): many tiles, nine k-steps each
     P->persist_s2 = op.fuse1 < 0 && resident1 && !c.deconv && c.KS == 3 && R.sigma == 4 && P->MT == 2 && P->NT == 4 && op.stride == 2 && !op.up0 && !op.up1 &&
                     op.pool_dst < 0 && op.relu_dst < 0 && op.skiplog < 0 && op.tail_logits < 0 && op.dq_fuse < 0 && op.add < 0;
@@ -5743,12 +5515,11 @@ static int route_pp(const Op& op, const MfmaPlan& P, const MConv& a, const Exten
     return pp_run(w, rr, dim3((unsigned)x.cus), lds, x.dev, st);
 }
 
-#define PSEG_WS(SKIP_, PAIR_, FORM_)                                                                  \
-    if ((w.skip_logits != nullptr) == SKIP_ && P.pairc2 == PAIR_ && P.ws_form == FORM_)                \
-        return launch_lds<conv12_ws_kernel<SKIP_, PAIR_, FORM_>>(w, grid, 512, lds, dev, st);
+#define PSEG_WS(SKIP_, PAIR_)                                                                         \
+    if ((w.skip_logits != nullptr) == SKIP_ && P.pairc2 == PAIR_)                                     \
+        return launch_lds<conv12_ws_kernel<SKIP_, PAIR_>>(w, grid, 512, lds, dev, st);
 static int ws_run(const MfmaPlan& P, const MConv& w, dim3 grid, int lds, int dev, hipStream_t st) {
-    PSEG_WS(false, false, 0) PSEG_WS(false, true, 0) PSEG_WS(true, false, 0)
-    PSEG_WS(true, true, 0) PSEG_WS(true, true, 1) PSEG_WS(true, true, 2)       // (PSEG_WS_FORM: the alternative tile loops)
+    PSEG_WS(false, false) PSEG_WS(false, true) PSEG_WS(true, false) PSEG_WS(true, true)
     return ROUTE_NO;
 }
 #undef PSEG_WS
@@ -5824,8 +5595,6 @@ static int launch_conv1(const Engine& e, const Op& op, const MfmaPlan& P, hipStr
     dim3 g1(e.Wp / 32, cdiv(e.Hp, 16));
     uint16_t* o = (uint16_t*)d.d;
     if (P.KS == 5 && op.Cout == 20) conv1_mfma_kernel<5, 20><<<g1, 256, 0, st>>>(img, e.H, e.W, e.Wp, P.d_wpk, P.d_bias, o, op.relu);
-    else if (P.KS == 3 && op.Cout == 64) conv1_mfma_kernel<3, 64><<<g1, 256, 0, st>>>(img, e.H, e.W, e.Wp, P.d_wpk, P.d_bias, o, op.relu);
-    else if (P.KS == 3 && op.Cout == 32) conv1_mfma_kernel<3, 32><<<g1, 256, 0, st>>>(img, e.H, e.W, e.Wp, P.d_wpk, P.d_bias, o, op.relu);
     else conv1_mfma_kernel<1, 32><<<g1, 256, 0, st>>>(img, e.H, e.W, e.Wp, P.d_wpk, P.d_bias, o, op.relu);
     return PSEG_OK;
 }

@@ -369,7 +369,7 @@ class Engine:
 
     def __init__(self, arch="fcn_skip", n_classes=3, in_channels=1, device=0, mode=MODE_BF16, batch_norm=False, plan=None):
         """batch_norm: BatchNormalization at res_unet's bn_act sites (lib/model.py:265-271; PSEG_FLAG_BATCHNORM).
-        plan: plan switches for pseg_create_plan, "PSEG_NO_DQ=1;PSEG_WS_FORM=2" or a dict (tests and A/B measurements: every
+        plan: plan switches for pseg_create_plan, "PSEG_NO_DQ=1;PSEG_NO_PAIRC2=1" or a dict (tests and A/B measurements: every
         switch keeps the results within the documented bars).  With PLAN_FROM_ENV set (tests/conftest.py, tools/) and no plan given,
         the PSEG_* variables of os.environ that the library does not read itself become the plan -- the test suite keeps steering
         kernels with monkeypatch.setenv while the release library ignores the environment beyond pseg_env_knobs()."""

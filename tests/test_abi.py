@@ -65,7 +65,7 @@ def test_plan_switches_do_not_come_from_the_environment(monkeypatch):
     from pseg_amd import engine as E
     assert E.PLAN_FROM_ENV                                                  # (tests/conftest.py: the harness translates for the tests)
     listed = pseg_amd.lib().pseg_env_knobs().decode().split("\n")
-    assert "PSEG_NO_SP" in listed and "PSEG_NO_DQ" not in listed and "PSEG_WS_FORM" not in listed
+    assert "PSEG_NO_SP" in listed and "PSEG_NO_DQ" not in listed and "PSEG_NO_PAIRC2" not in listed
 
 
 def test_oracle_library_is_separate_from_the_product():
