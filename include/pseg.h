@@ -989,6 +989,44 @@ int pseg_regions_geometry(int* word, int* band, int* band_words, int* tile_h, in
  * too small, the needed size is returned in first[n_regions], no vertex and no other offset is written, and the call is PSEG_OK.  A
  * row whose seed is not the first pixel of a region of the mask is PSEG_EINVAL. */
 int pseg_trace_regions_host(const uint8_t* mask, int H, int W, int n_regions, const int32_t* table, int32_t* xy, int64_t cap, int64_t* first);
+/* pseg_text_regions with the crack polygons traced on the device, from the bit plane of T (64 pixels to a word; horizontal stretches
+ * are taken a word at a time): a count pass, a scan of the counts over the group's rows and a write pass, one lane per region, no host
+ * wait between them.  Table, counts and masks are exactly pseg_text_regions'; the polygons are exactly pseg_trace_regions_host's for
+ * the same rows.  xy: cap int32 (x, y) pairs for the whole list; first: n x (max_regions + 1) offsets in vertices: region r of map i
+ * owns [first[i][r], first[i][r + 1]), the offsets run across the list (first[i][0] is the end of map i - 1) and those behind a map's
+ * last region repeat its end.  status[i]: PSEG_OK; PSEG_EUNSUPPORTED when out_count[i] > max_regions (no polygons, its row of offsets
+ * is the running offset); PSEG_EHIP when a walk did not close within its bound of 4 (H + 1) (W + 1) + 4 steps (likewise).  When the
+ * list's vertex total exceeds cap, first[n - 1][max_regions] holds the needed total, no vertex and no other offset is written, tables,
+ * counts, masks and status are valid, and the call is PSEG_OK.  Refused as pseg_text_regions refuses, and PSEG_EINVAL for a NULL first
+ * or status, a negative cap, or a cap without xy; nothing is written then.  A group costs pseg_text_regions' launches, three more, and
+ * a second host wait for exactly the rows' vertex counts, offsets and vertices it holds. */
+int pseg_text_regions_poly(int device, int n, const uint8_t* const* labels, const int* H, const int* W, const pseg_regions* how,
+                           uint8_t* const* out_mask, int max_regions, int32_t* out_table, int* out_count,
+                           int32_t* xy, int64_t cap, int64_t* first /* n x (max_regions + 1) */, int* status /* n */);
+/* The same bytes on the host, without a device: pseg_text_regions_host, then the same word-run walk over host bit planes. */
+int pseg_text_regions_poly_host(int n, const uint8_t* const* labels, const int* H, const int* W, const pseg_regions* how,
+                                uint8_t* const* out_mask, int max_regions, int32_t* out_table, int* out_count,
+                                int32_t* xy, int64_t cap, int64_t* first, int* status);
+/* The page chain with the text regions as a stage: pseg_predict_chain_pages_png (mixed == 0) or pseg_predict_chain_pages_mixed_png
+ * (mixed != 0) with bit 5 of `want`: after a unit's post-processors its final label maps go, where they lie on the device, through
+ * pseg_text_regions' launches and the tracer of pseg_text_regions_poly on the engine's stream; the maps never visit the host for it.
+ * how: one pseg_regions per page of the list (checked before any device work: "page 3: ..."); how == NULL is the plain entry (bit 5
+ * is refused then), and without bit 5 nothing of the stage runs.  want == 32 alone is a valid request.  max_regions >= 1 and
+ * max_vertices >= 0 are every page's capacities.  The stage's workspace and records belong to the staging sets: sized by the plan,
+ * freed by pseg_engine_trim; after a unit's done event exactly the rows and vertices its pages hold are downloaded.
+ * sink(user, page, 5, blob, n_bytes) comes after the page's label map.  The blob is int32: n_regions, n_vertices, status, 0; then
+ * n_regions rows of 8 (pseg_text_regions' table, sorted by seed); then n_regions + 1 offsets in vertices; then n_vertices (x, y)
+ * pairs.  n_regions > max_regions: the header alone, status PSEG_EUNSUPPORTED.  n_vertices > max_vertices: the header and the rows,
+ * status PSEG_ENOMEM (n_vertices is what the page needs).  A walk that gave up: the header and the rows, status PSEG_EHIP. */
+int pseg_predict_chain_pages_regions_png(pseg_engine* e, int n_pages, const uint8_t* const* imgs, const int* H, const int* W,
+                                         const int* Ho, const int* Wo, const uint8_t* const* binaries, const int* post_ops, int n_post,
+                                         unsigned flags, const uint8_t* lut, int n_lut, int level, unsigned want, int unit_cap, int mixed,
+                                         const pseg_regions* how, int max_regions, int max_vertices, pseg_chain_sink sink, void* user);
+/* pseg_predict_chain_scans_clean_png with the same stage (rg: one pseg_regions per scan, or NULL). */
+int pseg_predict_chain_scans_regions_png(pseg_engine* e, int n_scans, const pseg_scan* scans, const pseg_binarize* how,
+                                         const pseg_despeckle* dsp, const int* post_ops, int n_post, unsigned flags,
+                                         const uint8_t* lut, int n_lut, int level, unsigned want, int unit_cap,
+                                         const pseg_regions* rg, int max_regions, int max_vertices, pseg_chain_sink sink, void* user);
 
 #ifdef __cplusplus
 }

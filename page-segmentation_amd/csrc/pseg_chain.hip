@@ -10,18 +10,21 @@
 #include <cstring>
 
 #include "pseg_list.h"
+#include "pseg_regions.h"
 
 namespace pseg {
 
 // One of the two staging sets of the page chain (pseg_predict_chain_pages_png): everything a unit of pages touches.
 struct PagesSet {
-    enum { IMG = 0, LAB = 1, LAB2 = 2, BIN = 3, PNG = 4, PAD = 5, CLAB = 6, SCAN = 7, FILT = 8, REC = 9, NDEV = 10 };
+    enum { IMG = 0, LAB = 1, LAB2 = 2, BIN = 3, PNG = 4, PAD = 5, CLAB = 6, SCAN = 7, FILT = 8, REC = 9, RGN = 10, NDEV = 11 };
     // pages / network labels / resize + bbox ping-pong / binarisations / encoder workspace / mixed units: the pages padded to canvas-sized
-    // page slots / the slots' canvas-sized label maps / scan chain: the unit's scans / their filtered planes / their records
+    // page slots / the slots' canvas-sized label maps / scan chain: the unit's scans / their filtered planes / their records / the regions
+    // stage's workspace (pseg_regions.h, RgStageLay)
     GrowDev d[NDEV];
     GrowPin h_in;                        // pages and binarisations of callers with pageable arrays
     GrowPin h_out;                       // the unit's encoded streams (+ label maps), grown to the bytes units really have
     GrowPin h_tot;                       // [pages][4] stream sizes (unsigned long long)
+    GrowPin h_rg;                        // the regions stage: its table of maps, then the unit's counts and map records as they come back
 };
 struct ChainPagesState {
     PagesSet set[2];
@@ -47,7 +50,7 @@ static void pages_release(ChainPagesState& p) {
     for (GrowPin* b : {&p.h_tab, &p.h_wt}) b->release();
     for (PagesSet& s : p.set) {
         for (GrowDev& b : s.d) b.release();
-        for (GrowPin* b : {&s.h_in, &s.h_out, &s.h_tot}) b->release();
+        for (GrowPin* b : {&s.h_in, &s.h_out, &s.h_tot, &s.h_rg}) b->release();
     }
 }
 
@@ -328,8 +331,21 @@ struct ChainPlan {
     std::vector<ChainUnit> un;
     std::vector<MixedPage> tab;
     std::vector<size_t> lab2_off, scan_off, filt_off, wt_off;       // LAB2; a scan call: the scan in SCAN, its filtered plane (and an adaptive binarisation's planes) in FILT, its weights in the call's table
-    size_t n_wt = 0, mx[PagesSet::NDEV] = {}, mx_in = 0, mx_tot = 0;
+    size_t n_wt = 0, mx[PagesSet::NDEV] = {}, mx_in = 0, mx_tot = 0, mx_rg_pin = 0;
+    const pseg_regions* rg = nullptr;                               // the regions stage: per page of the caller's list, or none
+    int rg_R = 0; long long rg_V = 0;                               // its max_regions and max_vertices
 };
+
+// what the regions stage of a unit needs: its workspace and its page-locked records (the table, the counts, the map records)
+static int chain_rg_sizes(const ChainPlan& p, int i0, int g, size_t* dev, size_t* pin) {
+    std::vector<int> Hl(g), Wl(g);
+    for (int k = 0; k < g; ++k) { Hl[k] = p.tab[i0 + k].Hl; Wl[k] = p.tab[i0 + k].Wl; }
+    RgStageLay lay;
+    PSEG_TRY(rg_stage_plan(g, Hl.data(), Wl.data(), p.rg_R, p.rg_V, &lay));
+    *dev = lay.bytes;
+    *pin = lay.tab_bytes + up256((size_t)g * 4) + up256((size_t)g * RG_MAPV * 8);
+    return PSEG_OK;
+}
 
 // The pass that ends the plan: every block of every page lies inside its mx[], the offsets that kernels and DMA rely on are aligned
 // (or dense: same-shape pages go up in one DMA, same-shape page slots write their maps one behind the other), the units tile the list
@@ -372,6 +388,11 @@ static int chain_plan_check(const ChainPlan& p, const std::vector<ChainReq>& req
             dense_img += npx * p.in_ch;
             dense_lab += npx;
         }
+        if (p.rg) {
+            size_t dev = 0, pin = 0;
+            PSEG_TRY(chain_rg_sizes(p, i0, g, &dev, &pin));
+            unit_ok = unit_ok && dev <= p.mx[B::RGN] && pin <= p.mx_rg_pin;
+        }
         if (!unit_ok || in_b > p.mx_in) return fail(PSEG_EHIP, "page chain plan: unit %zu (page %d ...) outgrows its staging", u, p.ord[i0]);
     }
     if (next != p.n) return fail(PSEG_EHIP, "page chain plan: the units end at position %d of %d", next, p.n);
@@ -382,9 +403,10 @@ static int chain_plan_check(const ChainPlan& p, const std::vector<ChainReq>& req
 // (pseg_chain_units_mixed).  scans != NULL: a scan call (mixed), whose pages and ink maps the front end writes on the device.
 static int chain_pages_plan(int n, const int* H, const int* W, const int* Ho, const int* Wo, const std::vector<ChainReq>& req, const pseg_scan* scans,
                             const pseg_binarize* how, const pseg_despeckle* dsp, const int* post_ops, int n_post, int in_ch, int cap, bool page_slots, bool mixed,
-                            int level, int nout, ChainPlan* out) {
+                            int level, int nout, const pseg_regions* rg, int max_regions, int max_vertices, ChainPlan* out) {
     typedef PagesSet B;
     ChainPlan& p = *out;
+    p.rg = rg; p.rg_R = max_regions; p.rg_V = max_vertices;
     p.mixed = mixed;
     p.n = n;
     p.in_ch = in_ch;
@@ -439,8 +461,11 @@ static int chain_pages_plan(int n, const int* H, const int* W, const int* Ho, co
             else PSEG_TRY(png_pages_layout(req[p0].Hl, req[p0].Wl, level, nout, g, &q.L));
         }
         const size_t cpx = mixed && q.slots ? (size_t)round_up(H[p0], 32) * round_up(W[p0], 32) : 0;
+        size_t rg_dev = 0, rg_pin = 0;
+        if (p.rg) PSEG_TRY(chain_rg_sizes(p, i0, g, &rg_dev, &rg_pin));
+        p.mx_rg_pin = std::max(p.mx_rg_pin, rg_pin);
         const size_t ext[B::NDEV] = {o_img, lab_b, p.two_maps ? o_lab2 : 0, p.any_bin ? o_bin : 0, mixed ? q.M.bytes : q.L.bytes, (size_t)g * cpx * in_ch,
-                                     (size_t)g * cpx, o_scan, o_filt, scans ? (size_t)g * SCAN_REC_WORDS * sizeof(unsigned) : 0};
+                                     (size_t)g * cpx, o_scan, o_filt, scans ? (size_t)g * SCAN_REC_WORDS * sizeof(unsigned) : 0, rg_dev};
         for (int k = 0; k < B::NDEV; ++k) p.mx[k] = std::max(p.mx[k], ext[k]);
         p.mx_in = std::max(p.mx_in, in_b);
         p.mx_tot = std::max(p.mx_tot, (size_t)g * 4 * sizeof(unsigned long long));
@@ -456,6 +481,7 @@ static int pages_reserve(ChainPagesState& ps, const ChainPlan& p, bool any_pagea
             if (p.mx[k]) PSEG_TRY(s.d[k].ensure(p.mx[k], "page chain staging"));
         if (any_pageable) PSEG_TRY(s.h_in.ensure(p.mx_in, "page chain staging"));
         PSEG_TRY(s.h_tot.ensure(std::max<size_t>(p.mx_tot, 64), "page chain staging"));
+        if (p.mx_rg_pin) PSEG_TRY(s.h_rg.ensure(p.mx_rg_pin, "page chain staging"));
     }
     if (lut) {
         PSEG_TRY(ps.d_lut.ensure(768, "page chain colour table"));
@@ -493,6 +519,13 @@ struct PagesRun {
     // where a unit's outputs lie in its page-locked slot: per page the requested streams (8-byte aligned), then the label map (and the
     // sizes, copied out of the set's page-locked words: those are written again by the unit after next while this one is delivered)
     std::vector<size_t> offs[2], tot[2];
+    // the regions stage (p.rg): the layout of the unit's workspace; per page where its rows, vertex counts, offsets and vertices lie in the
+    // page-locked slot; the counts and map records, copied out of the set's page-locked words for the same reason; the blob under way
+    RgStageLay rg_lay[2];
+    std::vector<size_t> rg_of[2];
+    std::vector<int> rg_cnt[2];
+    std::vector<long long> rg_mapv[2];
+    std::vector<int32_t> rg_blob;
 
     static uint8_t* final_map(const PagesSet& s, const MixedPage& m) { return s.d[m.pred_sel ? B::LAB2 : B::LAB].p + m.pred_off; }
     bool pinned(int pi) const { return host_is_pinned(imgs[pi]) && (scans || !req[pi].need_bin || host_is_pinned(binaries[pi])); }
@@ -622,12 +655,34 @@ struct PagesRun {
         PSEG_HIP(hipMemcpyAsync(s.h_tot.p, s.d[B::PNG].p, (size_t)g * 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
         return PSEG_OK;
     }
+    // 5. the text regions of the unit's final maps, where they lie: the stage of pseg_regions.hip and its tracer; the counts and the map
+    // records go to page-locked memory, as the streams' sizes do
+    int regions(int u, PagesSet& s) {
+        const int i0 = p.ub[u], g = p.ug[u];
+        std::vector<const uint8_t*> lab(g);
+        std::vector<int> Hl(g), Wl(g);
+        std::vector<pseg_regions> hw(g);
+        for (int k = 0; k < g; ++k) {
+            const MixedPage& m = p.tab[i0 + k];
+            lab[k] = final_map(s, m); Hl[k] = m.Hl; Wl[k] = m.Wl; hw[k] = p.rg[p.ord[i0 + k]];
+        }
+        RgStageLay& L = rg_lay[u & 1];
+        uint8_t* const d = s.d[B::RGN].p;
+        // the buffers' real capacities go along: the stage refuses a layout that outgrows them, whatever the plan said
+        const size_t rec_b = up256((size_t)g * 4) + up256((size_t)g * RG_MAPV * 8);
+        if (s.h_rg.cap < rec_b) return fail(PSEG_EHIP, "page chain: the regions records of unit %d outgrow their staging", u);
+        PSEG_TRY(rg_stage_enqueue(st, d, s.h_rg.p, g, lab.data(), Hl.data(), Wl.data(), hw.data(), p.rg_R, p.rg_V, s.d[B::RGN].cap, s.h_rg.cap - rec_b, &L));
+        PSEG_HIP(hipMemcpyAsync(s.h_rg.p + L.tab_bytes, d + L.cnt, (size_t)g * 4, hipMemcpyDeviceToHost, st));
+        PSEG_HIP(hipMemcpyAsync(s.h_rg.p + L.tab_bytes + up256((size_t)g * 4), d + L.mapv, (size_t)g * RG_MAPV * 8, hipMemcpyDeviceToHost, st));
+        return PSEG_OK;
+    }
     int compute(int u, const PipeSet&) {
         PagesSet& s = ps.set[u & 1];
         if (scans) PSEG_TRY(front_end(u, s));
         PSEG_TRY(network(u, s));
         PSEG_TRY(post(u, s));
-        return nout > 0 ? encode(u, s) : PSEG_OK;
+        if (nout > 0) PSEG_TRY(encode(u, s));
+        return p.rg ? regions(u, s) : PSEG_OK;
     }
     int download(int u, const PipeSet& ev) {
         PagesSet& s = ps.set[u & 1];
@@ -654,6 +709,25 @@ struct PagesRun {
             if (want_lab) pos += ((size_t)p.tab[i0 + k].Hl * p.tab[i0 + k].Wl + 7) & ~(size_t)7;
         }
         of[(size_t)g * 5] = pos;
+        const RgStageLay& RL = rg_lay[u & 1];
+        if (p.rg) {                                            // per page exactly what it holds: rows, vertex counts, offsets, vertices
+            const int* h_cnt = (const int*)(s.h_rg.p + RL.tab_bytes);
+            const long long* h_mapv = (const long long*)(s.h_rg.p + RL.tab_bytes + up256((size_t)g * 4));
+            rg_cnt[u & 1].assign(h_cnt, h_cnt + g);
+            rg_mapv[u & 1].assign(h_mapv, h_mapv + (size_t)g * RG_MAPV);
+            std::vector<size_t>& ro = rg_of[u & 1];
+            ro.assign((size_t)g * 4, 0);
+            for (int k = 0; k < g; ++k) {
+                const int c = h_cnt[k];
+                const size_t cc = c < 0 || c > p.rg_R ? 0 : (size_t)c;
+                const long long tv = h_mapv[(size_t)k * RG_MAPV];
+                if (tv < 0 || (h_mapv[(size_t)k * RG_MAPV + 3] && tv > p.rg_V)) return fail(PSEG_EHIP, "regions: page %d reports %lld vertices", p.ord[i0 + k], tv);
+                ro[(size_t)k * 4] = pos; pos += cc * RG_ROW_INTS * 4;
+                ro[(size_t)k * 4 + 1] = pos; pos += cc * 8;
+                ro[(size_t)k * 4 + 2] = pos; pos += cc * 8;
+                ro[(size_t)k * 4 + 3] = pos; pos += h_mapv[(size_t)k * RG_MAPV + 3] ? (size_t)tv * 8 : 0;
+            }
+        }
         // the slot was handed to the sink by finish(u - 2): idle.  It grows to what units really hold, with a quarter of headroom.
         if (s.h_out.cap < pos) PSEG_TRY(s.h_out.ensure(pos + pos / 4 + 4096, "page chain streams"));
         for (int k = 0; k < g; ++k) {
@@ -664,6 +738,18 @@ struct PagesRun {
                 PSEG_HIP(hipMemcpyAsync(s.h_out.p + of[(size_t)k * 5 + j], src, tt[(size_t)k * 4 + j], hipMemcpyDeviceToHost, s_out));
             }
             if (want_lab) PSEG_HIP(hipMemcpyAsync(s.h_out.p + of[(size_t)k * 5 + 4], final_map(s, m), (size_t)m.Hl * m.Wl, hipMemcpyDeviceToHost, s_out));
+            if (p.rg) {
+                const std::vector<size_t>& ro = rg_of[u & 1];
+                const uint8_t* const d = s.d[B::RGN].p;
+                const size_t r0 = (size_t)k * p.rg_R, cc = (ro[(size_t)k * 4 + 2] - ro[(size_t)k * 4 + 1]) / 8;
+                const size_t nvb = rg_mapv[u & 1][(size_t)k * RG_MAPV + 3] ? (size_t)rg_mapv[u & 1][(size_t)k * RG_MAPV] * 8 : 0;
+                if (cc) {
+                    PSEG_HIP(hipMemcpyAsync(s.h_out.p + ro[(size_t)k * 4], d + RL.rows + r0 * RG_ROW_INTS * 4, cc * RG_ROW_INTS * 4, hipMemcpyDeviceToHost, s_out));
+                    PSEG_HIP(hipMemcpyAsync(s.h_out.p + ro[(size_t)k * 4 + 1], d + RL.nv + r0 * 8, cc * 8, hipMemcpyDeviceToHost, s_out));
+                    PSEG_HIP(hipMemcpyAsync(s.h_out.p + ro[(size_t)k * 4 + 2], d + RL.voff + r0 * 8, cc * 8, hipMemcpyDeviceToHost, s_out));
+                }
+                if (nvb) PSEG_HIP(hipMemcpyAsync(s.h_out.p + ro[(size_t)k * 4 + 3], d + RL.xy + (size_t)k * p.rg_V * 8, nvb, hipMemcpyDeviceToHost, s_out));
+            }
         }
         return PSEG_OK;
     }
@@ -682,6 +768,14 @@ struct PagesRun {
             }
             if (want_lab && sink(user, pi, 4, s.h_out.p + of[(size_t)k * 5 + 4], (size_t)m.Hl * m.Wl) != 0)
                 return fail(PSEG_ECALLBACK, "the sink stopped the call at page %d, output 4", pi);
+            if (p.rg) {
+                const std::vector<size_t>& ro = rg_of[u & 1];
+                rg_stage_blob(rg_cnt[u & 1][k], p.rg_R, p.rg_V, &rg_mapv[u & 1][(size_t)k * RG_MAPV], (int32_t*)(s.h_out.p + ro[(size_t)k * 4]),
+                              (const long long*)(s.h_out.p + ro[(size_t)k * 4 + 1]), (const long long*)(s.h_out.p + ro[(size_t)k * 4 + 2]),
+                              (const int32_t*)(s.h_out.p + ro[(size_t)k * 4 + 3]), rg_blob);
+                if (sink(user, pi, 5, (const uint8_t*)rg_blob.data(), rg_blob.size() * 4) != 0)
+                    return fail(PSEG_ECALLBACK, "the sink stopped the call at page %d, output 5", pi);
+            }
         }
         return PSEG_OK;
     }
@@ -692,14 +786,19 @@ struct PagesRun {
 static int chain_pages_run(pseg_engine* h, int n, const uint8_t* const* imgs, const int* H, const int* W, const int* Ho, const int* Wo,
                            const uint8_t* const* binaries, const int* post_ops, int n_post, unsigned flags, const uint8_t* lut, int n_lut, int level,
                            unsigned want, int unit_cap, pseg_chain_sink sink, void* user, const bool mixed, const pseg_scan* scans = nullptr,
-                           const pseg_binarize* how = nullptr, const pseg_despeckle* dsp = nullptr) {
+                           const pseg_binarize* how = nullptr, const pseg_despeckle* dsp = nullptr, const pseg_regions* rg = nullptr, int max_regions = 0,
+                           int max_vertices = 0) {
     if (!h) return fail(PSEG_EINVAL, "NULL engine");
     KnobScope knob_scope(h->e);
     Engine& e = h->e;
     if (n < 0 || (n > 0 && (!imgs || !H || !W))) return fail(PSEG_EINVAL, "bad argument");
     if (scans && (e.in_ch != 1 || !mixed)) return fail(PSEG_EUNSUPPORTED, "the scan chain takes an engine with one input channel (this one has %d)", e.in_ch);
     if (!sink) return fail(PSEG_EINVAL, "NULL sink");
-    if (want == 0 || (want & ~31u)) return fail(PSEG_EINVAL, "want 0x%x: bits 0..3 select the masks, bit 4 the label map, at least one", want);
+    if (want == 0 || (want & ~(rg ? 63u : 31u)))
+        return fail(PSEG_EINVAL, "want 0x%x: bits 0..3 select the masks, bit 4 the label map%s, at least one", want, rg ? ", bit 5 the text regions" : "");
+    if (!(want & 32u)) rg = nullptr;                           // the stage runs only where it is asked for
+    if (rg && (max_regions < 1 || max_vertices < 0 || (int64_t)max_regions * 64 * RG_ROW_INTS > 0x7fffffffLL))
+        return fail(PSEG_EINVAL, "regions: max_regions %d, max_vertices %d", max_regions, max_vertices);
     if (unit_cap < 0 || unit_cap > 64) return fail(PSEG_EINVAL, "unit_cap %d (0 = default, at most 64)", unit_cap);
     int mask_id[4] = {0, 0, 0, 0}, nout = 0;
     for (int k = 0; k < 4; ++k)
@@ -712,6 +811,10 @@ static int chain_pages_run(pseg_engine* h, int n, const uint8_t* const* imgs, co
                              want_png, want_png, lut, n_lut, level, &req[i]));
         if (want_png && pseg_png_bound_lv(req[i].Hl, req[i].Wl, 3, 0, level) == 0) return fail(PSEG_EINVAL, "page %d: png: a row of %d pixels is too long", i, req[i].Wl);
         if (mixed && (H[i] > 0x7FFFFFE0 || W[i] > 0x7FFFFFE0)) return fail(PSEG_EINVAL, "page %d: bad shape %d x %d", i, H[i], W[i]);
+        if (rg) {
+            PSEG_TRY(rg_stage_check(rg[i], "page", i));
+            if ((int64_t)req[i].Hl * req[i].Wl > 0x7fffffffLL) return fail(PSEG_EUNSUPPORTED, "page %d: map too large for the regions", i);
+        }
     }
     if (n == 0) return PSEG_OK;
     PSEG_HIP(hipSetDevice(e.device));
@@ -737,7 +840,7 @@ static int chain_pages_run(pseg_engine* h, int n, const uint8_t* const* imgs, co
         }
     } else if (!page_slots) cap = std::min(8, std::max(1, n / 4));       // (the encoder's launches still take a unit's pages together)
     ChainPlan plan;
-    PSEG_TRY(chain_pages_plan(n, H, W, Ho, Wo, req, scans, how, dsp, post_ops, n_post, e.in_ch, cap, page_slots, mixed, level, nout, &plan));
+    PSEG_TRY(chain_pages_plan(n, H, W, Ho, Wo, req, scans, how, dsp, post_ops, n_post, e.in_ch, cap, page_slots, mixed, level, nout, rg, max_regions, max_vertices, &plan));
     PagesRun run{h, plan, *c.pages, req, imgs, binaries, scans, how, dsp, post_ops, n_post, exact, want_png ? lut : nullptr, n_lut, level, nout, mask_id,
                  (want & 16u) != 0, sink, user, s_in, e.stream, s_out, {}, {}};
     PSEG_TRY(run_pipeline(run, (int)plan.ub.size(), c.pages->ev, s_in, e.stream, s_out));
@@ -748,14 +851,24 @@ extern "C" int pseg_predict_chain_pages_png(pseg_engine* h, int n, const uint8_t
                                             const int* Wo, const uint8_t* const* binaries, const int* post_ops, int n_post, unsigned flags,
                                             const uint8_t* lut, int n_lut, int level, unsigned want, int unit_cap, pseg_chain_sink sink,
                                             void* user) {
-    return chain_pages_run(h, n, imgs, H, W, Ho, Wo, binaries, post_ops, n_post, flags, lut, n_lut, level, want, unit_cap, sink, user, false);
+    return pseg_predict_chain_pages_regions_png(h, n, imgs, H, W, Ho, Wo, binaries, post_ops, n_post, flags, lut, n_lut, level, want, unit_cap, 0, nullptr, 0, 0,
+                                                sink, user);
 }
 
 extern "C" int pseg_predict_chain_pages_mixed_png(pseg_engine* h, int n, const uint8_t* const* imgs, const int* H, const int* W, const int* Ho,
                                                   const int* Wo, const uint8_t* const* binaries, const int* post_ops, int n_post, unsigned flags,
                                                   const uint8_t* lut, int n_lut, int level, unsigned want, int unit_cap, pseg_chain_sink sink,
                                                   void* user) {
-    return chain_pages_run(h, n, imgs, H, W, Ho, Wo, binaries, post_ops, n_post, flags, lut, n_lut, level, want, unit_cap, sink, user, true);
+    return pseg_predict_chain_pages_regions_png(h, n, imgs, H, W, Ho, Wo, binaries, post_ops, n_post, flags, lut, n_lut, level, want, unit_cap, 1, nullptr, 0, 0,
+                                                sink, user);
+}
+
+extern "C" int pseg_predict_chain_pages_regions_png(pseg_engine* h, int n, const uint8_t* const* imgs, const int* H, const int* W, const int* Ho,
+                                                    const int* Wo, const uint8_t* const* binaries, const int* post_ops, int n_post, unsigned flags,
+                                                    const uint8_t* lut, int n_lut, int level, unsigned want, int unit_cap, int mixed,
+                                                    const pseg_regions* how, int max_regions, int max_vertices, pseg_chain_sink sink, void* user) {
+    return chain_pages_run(h, n, imgs, H, W, Ho, Wo, binaries, post_ops, n_post, flags, lut, n_lut, level, want, unit_cap, sink, user, mixed != 0, nullptr,
+                           nullptr, nullptr, how, max_regions, max_vertices);
 }
 
 extern "C" int pseg_predict_chain_scans_png(pseg_engine* h, int n, const pseg_scan* scans, const int* post_ops, int n_post, unsigned flags,
@@ -772,6 +885,13 @@ extern "C" int pseg_predict_chain_scans_bin_png(pseg_engine* h, int n, const pse
 extern "C" int pseg_predict_chain_scans_clean_png(pseg_engine* h, int n, const pseg_scan* scans, const pseg_binarize* how, const pseg_despeckle* dsp,
                                                   const int* post_ops, int n_post, unsigned flags, const uint8_t* lut, int n_lut, int level, unsigned want,
                                                   int unit_cap, pseg_chain_sink sink, void* user) {
+    return pseg_predict_chain_scans_regions_png(h, n, scans, how, dsp, post_ops, n_post, flags, lut, n_lut, level, want, unit_cap, nullptr, 0, 0, sink, user);
+}
+
+extern "C" int pseg_predict_chain_scans_regions_png(pseg_engine* h, int n, const pseg_scan* scans, const pseg_binarize* how, const pseg_despeckle* dsp,
+                                                    const int* post_ops, int n_post, unsigned flags, const uint8_t* lut, int n_lut, int level, unsigned want,
+                                                    int unit_cap, const pseg_regions* rg, int max_regions, int max_vertices, pseg_chain_sink sink,
+                                                    void* user) {
     if (n < 0 || (n > 0 && !scans)) return fail(PSEG_EINVAL, "bad argument");
     if (!sink) return fail(PSEG_EINVAL, "NULL sink");
     // every scan is checked before any device work starts; the pages' shapes then go through the page entries' checks
@@ -788,5 +908,5 @@ extern "C" int pseg_predict_chain_scans_clean_png(pseg_engine* h, int n, const p
         Wo[i] = scans[i].final_is_scan ? scans[i].W0 : 0;
     }
     return chain_pages_run(h, n, gray.data(), H.data(), W.data(), Ho.data(), Wo.data(), gray.data(), post_ops, n_post, flags, lut, n_lut, level, want,
-                           unit_cap, sink, user, true, scans, how, dsp);
+                           unit_cap, sink, user, true, scans, how, dsp, rg, max_regions, max_vertices);
 }

@@ -10,8 +10,11 @@
 #pragma once
 
 #include <cstdint>
+#include <vector>
 
 #include <hip/hip_runtime.h>
+
+#include "../../include/pseg.h"
 
 namespace pseg {
 
@@ -96,5 +99,110 @@ __host__ __device__ inline rg_word rg_xpass(const rg_word* row, int wpr, int W, 
 __host__ __device__ inline int rg_band_first(int y0, int k) { return y0 - (k >> 1); }
 
 __host__ __device__ inline bool rg_side_ok(int k) { return k >= 1 && k <= RG_SIDE_MAX; }
+
+// ---- the crack polygon of a region on a canonical bit plane (the word-run walk of the device tracer and of its host twin) -------------
+// Directions: 0 east, 1 south, 2 west, 3 north (y grows downwards).  At a corner, heading d, `right` is the pixel ahead on the
+// region's side and `left` the one ahead on the other side.
+__host__ __device__ inline int rg_turn(int d, bool right, bool left) { return !right ? ((d + 1) & 3) : left ? ((d + 3) & 3) : d; }
+
+__host__ __device__ inline bool rg_bit(const rg_word* T, int H, int W, int wpr, int x, int y) {
+    return x >= 0 && x < W && y >= 0 && y < H && ((T[(size_t)y * wpr + (x >> 6)] >> (x & 63)) & 1ull) != 0;
+}
+__host__ __device__ inline int rg_ctz(rg_word v) {
+#ifdef __HIP_DEVICE_COMPILE__
+    return (int)__ffsll((long long)v) - 1;
+#else
+    return __builtin_ctzll(v);
+#endif
+}
+__host__ __device__ inline int rg_clz(rg_word v) {
+#ifdef __HIP_DEVICE_COMPILE__
+    return (int)__clzll((long long)v);
+#else
+    return __builtin_clzll(v);
+#endif
+}
+
+// How many corners in a row, from corner x on, go straight on a horizontal heading: R is the row of the `right` pixels, L the row of
+// the `left` ones (either may be NULL: a row outside the map).  East: the pixels x, x + 1, ... with R set and L unset, a word at a
+// time by ctz; west: the pixels x - 1, x - 2, ... by clz.  The planes are canonical, so a run ends at the map's last column by itself.
+__host__ __device__ inline int rg_hrun(const rg_word* R, const rg_word* L, int wpr, int x, bool east) {
+    if (!R) return 0;
+    int n = 0;
+    if (east) {
+        int j = x >> 6, b = x & 63;
+        for (int it = 0; it < wpr && j < wpr; ++it, ++j, b = 0) {
+            const rg_word bad = ~((R[j] & ~(L ? L[j] : 0ull)) >> b);   // the shift brings in zeros: c <= 64 - b
+            const int c = bad ? rg_ctz(bad) : 64;
+            n += c;
+            if (c < 64 - b) break;
+        }
+    } else {
+        if (x <= 0) return 0;
+        int j = (x - 1) >> 6, b = (x - 1) & 63;
+        for (int it = 0; it < wpr && j >= 0; ++it, --j, b = 63) {
+            const rg_word g = (R[j] & ~(L ? L[j] : 0ull)) << (63 - b);
+            const int c = ~g ? rg_clz(~g) : 64;
+            n += c < b + 1 ? c : b + 1;
+            if (c < b + 1) break;
+        }
+    }
+    return n;
+}
+
+// The walk from the seed (sx, sy) of a region of plane T: clockwise from the seed's top-left corner, arriving there heading north;
+// a vertex wherever the direction changes.  Horizontal stretches are taken a run at a time (rg_hrun), vertical ones row by row.
+// Returns the number of vertices, or -1 when the walk does not close within 4 (H + 1) (W + 1) + 4 steps.  xy may be NULL (count
+// only); never more than `limit` vertices are written.
+__host__ __device__ inline long long rg_trace_words(const rg_word* T, int H, int W, int wpr, int sx, int sy, int32_t* xy, long long limit) {
+    int vx = sx, vy = sy, d = 3;
+    long long nv = 0, steps = 0;
+    const long long bound = 4ll * ((long long)H + 1) * ((long long)W + 1) + 4;
+    for (long long it = 0; it < bound && steps < bound; ++it) {
+        if (d == 0 || d == 2) {
+            // east: right (x, vy), left (x, vy - 1); west: right (x - 1, vy - 1), left (x - 1, vy)
+            const int ry = d == 0 ? vy : vy - 1, ly = d == 0 ? vy - 1 : vy;
+            const int n = rg_hrun(ry >= 0 && ry < H ? T + (size_t)ry * wpr : nullptr, ly >= 0 && ly < H ? T + (size_t)ly * wpr : nullptr, wpr, vx, d == 0);
+            if (n > 0) {
+                vx += d == 0 ? n : -n;
+                steps += n;
+                if (vx == sx && vy == sy) return nv;
+            }
+        }
+        int rx, ry, lx, ly;
+        switch (d) {
+            case 0: rx = vx; ry = vy; lx = vx; ly = vy - 1; break;
+            case 1: rx = vx - 1; ry = vy; lx = vx; ly = vy; break;
+            case 2: rx = vx - 1; ry = vy - 1; lx = vx - 1; ly = vy; break;
+            default: rx = vx; ry = vy - 1; lx = vx - 1; ly = vy - 1; break;
+        }
+        const int nd = rg_turn(d, rg_bit(T, H, W, wpr, rx, ry), rg_bit(T, H, W, wpr, lx, ly));
+        if (nd != d) {
+            if (xy && nv < limit) { xy[2 * nv] = vx; xy[2 * nv + 1] = vy; }
+            ++nv;
+        }
+        d = nd;
+        vx += d == 0 ? 1 : d == 2 ? -1 : 0;
+        vy += d == 1 ? 1 : d == 3 ? -1 : 0;
+        ++steps;
+        if (vx == sx && vy == sy) return nv;
+    }
+    return -1;
+}
+
+// ---- the stream-ordered stage for the page chain (pseg_regions.hip; host) --------------------------------------------------------------
+// Label maps already on the device in; plane 2, the unsorted rows, the counts, the vertex counts, their offsets, the maps' records
+// (total, first vertex, status, fits) and the vertices (max_vertices per map, map k at k * max_vertices) on the device out, at these
+// byte offsets of a workspace of `bytes` bytes.  rg_stage_plan sizes it up front (host arithmetic); rg_stage_enqueue fills the
+// page-locked table (tab_bytes) and launches on the caller's stream: no host wait, no allocation.  d_cap and h_cap are what the caller
+// really holds at d and h_tab: a layout that outgrows either is refused before anything is launched.
+struct RgStageLay { size_t cnt, rows, nv, voff, mapv, xy, bytes, tab_bytes; };
+constexpr int RG_MAPV = 4;                         // long long per map: the vertex total, its first vertex in the group's array, the status, fits
+int rg_stage_check(const pseg_regions& how, const char* what, int i);
+int rg_stage_plan(int n, const int* H, const int* W, int max_regions, long long max_vertices, RgStageLay* out);
+int rg_stage_enqueue(hipStream_t st, uint8_t* d, void* h_tab, int n, const uint8_t* const* d_labels, const int* H, const int* W,
+                     const pseg_regions* how, int max_regions, long long max_vertices, size_t d_cap, size_t h_cap, RgStageLay* out);
+void rg_stage_blob(int count, int max_regions, long long max_vertices, const long long* mapv, int32_t* rows, const long long* nv,
+                   const long long* voff, const int32_t* xy, std::vector<int32_t>& blob);
 
 }  // namespace pseg

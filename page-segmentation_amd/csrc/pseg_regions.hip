@@ -34,8 +34,8 @@ struct RgMap {
     int H, W, wpr, label;
     int k[3];
     int tile0, tiles_x, mb0, mbx, want_mask;
-    unsigned long long lab_off;                    // the label map's bytes in the group's buffer (the mask's bytes on the way back)
-    unsigned long long plane_off;                  // three planes of H * wpr words
+    unsigned long long lab;                        // the label map's bytes on the device (an address; the mask's bytes on the way back)
+    unsigned long long plane_off;                  // three planes of H * wpr words, in the group's workspace
     unsigned long long row_off;                    // the map's first row in the group's table
 };
 
@@ -66,7 +66,7 @@ __global__ __launch_bounds__(256) void rg_pack_kernel(uint8_t* buf, const RgMap*
     const RgMap pg = tab[pi];
     const int lt = tile - pg.tile0, ty = lt / pg.tiles_x, tx = lt - ty * pg.tiles_x;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint8_t* const lab = buf + pg.lab_off;
+    const uint8_t* const lab = (const uint8_t*)pg.lab;
     rg_word* const A = rg_plane(buf, pg, 0);
     const int x = tx * RG_TW + lane;
 #pragma unroll
@@ -84,7 +84,7 @@ __global__ __launch_bounds__(256) void rg_unpack_kernel(uint8_t* buf, const RgMa
     if (!pg.want_mask) return;
     const int lt = tile - pg.tile0, ty = lt / pg.tiles_x, tx = lt - ty * pg.tiles_x;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint8_t* const out = buf + pg.lab_off;
+    uint8_t* const out = (uint8_t*)pg.lab;
     const rg_word* const T = rg_plane(buf, pg, 2);
     const int x = tx * RG_TW + lane;
 #pragma unroll
@@ -459,13 +459,101 @@ __global__ __launch_bounds__(256) void rg_emit_kernel(const RgMap* __restrict__ 
     }
 }
 
+// ---- the crack polygons of the emitted rows, from plane 2: a count pass, a scan, a write pass --------------------------
+// One lane per emitted row (map k, row r in the order the rows were appended): the walk of pseg_regions.h from the row's seed.  A walk
+// is a chain of dependent loads, so a lane per region keeps 64 of them in flight per wave; the word scans need no helper lanes.
+// WRITE 0: nv[k * max_regions + r] = the vertex count, -1 for a walk that gave up.  WRITE 1: the vertices at voff[...], only for a
+// map that the scan let through (mapv[4 k + 3]), and never more of them than the count pass counted.
+template <int WRITE>
+__global__ __launch_bounds__(64) void rg_trace_kernel(const uint8_t* buf, const RgMap* __restrict__ tab, int n, const int* __restrict__ rows,
+                                                      const int* __restrict__ counts, int max_regions, long long* nv,
+                                                      const long long* __restrict__ voff, const long long* __restrict__ mapv, int* xy) {
+    const long long t = (long long)blockIdx.x * 64 + threadIdx.x;
+    const int k = (int)(t / max_regions), r = (int)(t - (long long)k * max_regions);
+    if (k >= n) return;
+    const int c = counts[k];
+    if (c > max_regions || r >= c) return;
+    if (WRITE && !mapv[(size_t)k * RG_MAPV + 3]) return;
+    const RgMap pg = tab[k];
+    const rg_word* const T = (const rg_word*)(buf + pg.plane_off) + (size_t)2 * pg.H * pg.wpr;
+    const int* const row = rows + ((size_t)pg.row_off + r) * RG_ROW_INTS;
+    const int sy = row[5], sx = row[6];
+    const bool seed_ok = sy >= 0 && sy < pg.H && sx >= 0 && sx < pg.W;
+    if (WRITE) {
+        const long long cnt = nv[t];
+        if (seed_ok && cnt > 0) (void)rg_trace_words(T, pg.H, pg.W, pg.wpr, sx, sy, xy + 2 * voff[t], cnt);
+    } else {
+        nv[t] = seed_ok ? rg_trace_words(T, pg.H, pg.W, pg.wpr, sx, sy, nullptr, 0) : -1;
+    }
+}
+
+// The exclusive scan of the counts over the rows of the group, one workgroup: voff[k * max_regions + r] = where row r of map k
+// starts in the group's vertex array, mapv[4 k ..] = the map's total, its first vertex, its status and whether the write pass runs.
+// per_map: every map owns vcap vertices at k * vcap; else the maps lie one behind the other in vcap vertices for the group, and a
+// map that does not fit still moves the offsets on (the totals are always delivered).  A map with a walk that gave up, or with more
+// rows than max_regions, has no vertices.
+__global__ __launch_bounds__(256) void rg_scan_kernel(const int* __restrict__ counts, int n, int max_regions, const long long* __restrict__ nv,
+                                                      long long* __restrict__ voff, long long* __restrict__ mapv, long long vcap, int per_map) {
+    __shared__ long long part[256];
+    __shared__ int bad;
+    const int tid = threadIdx.x;
+    long long run = 0;                                                 // uniform: the vertices of the maps before k
+    for (int k = 0; k < n; ++k) {
+        const int c = counts[k], m = (c > max_regions || c < 0) ? 0 : c;
+        const long long* const v = nv + (size_t)k * max_regions;
+        if (tid == 0) bad = 0;
+        __syncthreads();
+        long long sum = 0;
+        bool neg = false;
+        for (int r = tid; r < m; r += 256) {
+            const long long x = v[r];
+            neg |= x < 0;
+            sum += x < 0 ? 0 : x;
+        }
+        if (neg) atomicOr(&bad, 1);
+        part[tid] = sum;
+        __syncthreads();
+        for (int s = 128; s > 0; s >>= 1) {
+            if (tid < s) part[tid] += part[tid + s];
+            __syncthreads();
+        }
+        const bool gave_up = bad != 0;
+        const long long tot = gave_up ? 0 : part[0];
+        const long long base = per_map ? (long long)k * vcap : run;
+        const bool fits = !gave_up && c <= max_regions && (per_map ? tot <= vcap : base + tot <= vcap);
+        __syncthreads();
+        long long carry = base;
+        for (int r0 = 0; r0 < m; r0 += 256) {                          // inclusive scan of a chunk of 256 by doubling
+            const int r = r0 + tid;
+            const long long x = (r < m && !gave_up) ? v[r] : 0;
+            part[tid] = x;
+            __syncthreads();
+            for (int s = 1; s < 256; s <<= 1) {
+                const long long add = tid >= s ? part[tid - s] : 0;
+                __syncthreads();
+                part[tid] += add;
+                __syncthreads();
+            }
+            if (r < m) voff[(size_t)k * max_regions + r] = carry + part[tid] - x;
+            carry += part[255];
+            __syncthreads();
+        }
+        if (tid == 0) {
+            long long* const o = mapv + (size_t)k * RG_MAPV;
+            o[0] = tot; o[1] = base; o[2] = gave_up ? (long long)PSEG_EHIP : (c > max_regions ? (long long)PSEG_EUNSUPPORTED : (long long)PSEG_OK); o[3] = fits ? 1 : 0;
+        }
+        run += tot;
+    }
+}
+
 // ---- workspace: grow-only, one per device, under its own lock and on its own stream; a call holds the lock to its end and every
 // group ends synchronised.  pseg_release_workspace frees it.
 struct RgWs {
-    GrowDev dev; GrowPin pin; hipStream_t st = nullptr;
+    GrowDev dev; GrowPin pin, pinv; hipStream_t st = nullptr;   // pinv: the vertices of a polygon call's group
     void release() {
         dev.release();
         pin.release();
+        pinv.release();
         if (st) (void)hipStreamDestroy(st);
         st = nullptr;
     }
@@ -480,52 +568,65 @@ static void rg_sort_rows(int* rows, int count) {
     std::sort(r, r + count, [](const Row& a, const Row& b) { return rg_row_less(a.v, b.v); });
 }
 
-static int rg_group(RgWs& ws, int g0, int g1, const uint8_t* const* labels, const int* H, const int* W, const pseg_regions* how,
-                    uint8_t* const* out_mask, int max_regions, int32_t* out_table, int* out_count) {
-    const int n = g1 - g0;
-    const size_t tab_b = up256((size_t)n * sizeof(RgMap)), cnt_b = up256((size_t)n * 4);
-    const size_t rows_b = up256((size_t)n * max_regions * RG_ROW_INTS * 4);
-    PSEG_TRY(ws.pin.ensure(tab_b + cnt_b + rows_b, "text regions records"));
-    RgMap* const h_tab = ws.pin.as<RgMap>();
+// ---- the stream-ordered stage: label maps on the device in, plane 2, the unsorted rows and the counts on the device out -------------
+// rg_plan lays a group out in a workspace of lay.bytes bytes (host arithmetic; the caller sizes its buffer with it up front) and fills
+// the maps' table except the label addresses; rg_enqueue launches the group on the caller's stream: no host wait, no allocation.
+struct RgLay {
+    size_t cnt, rows, par, stat, slot, rim, rootn, nv, voff, mapv, xy, bytes;   // byte offsets in the workspace; the table is at 0
+    int tiles, mbs, poly, per_map;
+    long long vcap;                                // vertices: of every map (per_map) or of the group
+};
+
+static int rg_plan(int n, const int* H, const int* W, const pseg_regions* how, int max_regions, int poly, long long vcap, int per_map,
+                   RgMap* h_tab, RgLay& lay) {
+    const size_t tab_b = up256((size_t)n * sizeof(RgMap));
     std::memset(h_tab, 0, tab_b);
-    Bump at{tab_b + cnt_b + rows_b};
+    Bump at{tab_b};
+    lay.cnt = at.take((size_t)n * 4);
+    lay.rows = at.take((size_t)n * max_regions * RG_ROW_INTS * 4);
     long long tiles = 0, mbs = 0;
     for (int k = 0; k < n; ++k) {
-        const int i = g0 + k;
         RgMap& t = h_tab[k];
-        t.H = H[i]; t.W = W[i]; t.wpr = rg_words(W[i]); t.label = how[i].label;
-        t.k[0] = how[i].k_close; t.k[1] = how[i].k_open; t.k[2] = how[i].k_join;
+        t.H = H[k]; t.W = W[k]; t.wpr = rg_words(W[k]);
+        if (how) { t.label = how[k].label; t.k[0] = how[k].k_close; t.k[1] = how[k].k_open; t.k[2] = how[k].k_join; }
         t.tiles_x = t.wpr; t.tile0 = (int)tiles;
         t.mbx = cdiv(t.wpr, RG_WC); t.mb0 = (int)mbs;
-        t.want_mask = out_mask && out_mask[i];
-        t.lab_off = at.take((size_t)H[i] * W[i]);
-        t.plane_off = at.take((size_t)3 * H[i] * t.wpr * 8);
+        t.plane_off = at.take((size_t)3 * H[k] * t.wpr * 8);
         t.row_off = (unsigned long long)k * max_regions;
-        tiles += (long long)t.tiles_x * cdiv(H[i], RG_TH);
-        mbs += (long long)t.mbx * cdiv(H[i], RG_BAND);
+        tiles += (long long)t.tiles_x * cdiv(H[k], RG_TH);
+        mbs += (long long)t.mbx * cdiv(H[k], RG_BAND);
     }
-    if (tiles * RG_SLOTS > 0x7fffffffLL) return fail(PSEG_EUNSUPPORTED, "maps %d..%d: too many tiles for 32-bit slot ids", g0, g1 - 1);
+    if (tiles * RG_SLOTS > 0x7fffffffLL) return fail(PSEG_EUNSUPPORTED, "%d maps: too many tiles for 32-bit slot ids", n);
     const size_t nslots = (size_t)tiles * RG_SLOTS;
-    const size_t o_par = at.take(nslots * 4), o_stat = at.take(nslots * RG_STAT * 4), o_slot = at.take((size_t)tiles * RG_NPX),
-                 o_rim = at.take((size_t)tiles * RG_RIM), o_rootn = at.take((size_t)tiles * 4);
-    PSEG_TRY(ws.dev.ensure(at.off, "text regions workspace"));
-    if (!ws.st) PSEG_HIP(hipStreamCreateWithFlags(&ws.st, hipStreamNonBlocking));
-    hipStream_t st = ws.st;
-    uint8_t* const d = ws.dev.p;
+    lay.par = at.take(nslots * 4);
+    lay.stat = at.take(nslots * RG_STAT * 4);
+    lay.slot = at.take((size_t)tiles * RG_NPX);
+    lay.rim = at.take((size_t)tiles * RG_RIM);
+    lay.rootn = at.take((size_t)tiles * 4);
+    lay.nv = lay.voff = lay.mapv = lay.xy = at.off;
+    if (poly) {
+        lay.nv = at.take((size_t)n * max_regions * 8);
+        lay.voff = at.take((size_t)n * max_regions * 8);
+        lay.mapv = at.take((size_t)n * RG_MAPV * 8);
+        lay.xy = at.take((size_t)(per_map ? vcap * n : vcap) * 8);
+    }
+    lay.bytes = at.off;
+    lay.tiles = (int)tiles; lay.mbs = (int)mbs; lay.poly = poly; lay.per_map = per_map; lay.vcap = vcap;
+    return PSEG_OK;
+}
+
+static int rg_enqueue(hipStream_t st, uint8_t* d, const RgMap* h_tab, const RgLay& lay, int n, int max_regions) {
     const RgMap* const d_tab = (const RgMap*)d;
-    int* const d_cnt = (int*)(d + tab_b);
-    int* const d_rows = (int*)(d + tab_b + cnt_b);
-    int* const d_par = (int*)(d + o_par);
-    int* const d_stat = (int*)(d + o_stat);
-    uint8_t* const d_slot = d + o_slot;
-    uint8_t* const d_rim = d + o_rim;
-    int* const d_rootn = (int*)(d + o_rootn);
-    GroupDrain drain{st};
+    int* const d_cnt = (int*)(d + lay.cnt);
+    int* const d_rows = (int*)(d + lay.rows);
+    int* const d_par = (int*)(d + lay.par);
+    int* const d_stat = (int*)(d + lay.stat);
+    uint8_t* const d_slot = d + lay.slot;
+    uint8_t* const d_rim = d + lay.rim;
+    int* const d_rootn = (int*)(d + lay.rootn);
     PSEG_HIP(hipMemcpyAsync(d, h_tab, (size_t)n * sizeof(RgMap), hipMemcpyHostToDevice, st));
     PSEG_HIP(hipMemsetAsync(d_cnt, 0, (size_t)n * 4, st));
-    for (int k = 0; k < n; ++k)
-        PSEG_HIP(hipMemcpyAsync(d + h_tab[k].lab_off, labels[g0 + k], (size_t)h_tab[k].H * h_tab[k].W, hipMemcpyHostToDevice, st));
-    const int nt = (int)tiles, nm = (int)mbs, cap = nt * RG_SLOTS;
+    const int nt = lay.tiles, nm = lay.mbs, cap = nt * RG_SLOTS;
     rg_pack_kernel<<<nt, 256, 0, st>>>(d, d_tab, n);
     for (int op = 0; op < RG_OPS; ++op) rg_morph_kernel<<<nm, 256, 0, st>>>(d, d_tab, n, op);
     rg_tile_kernel<0><<<nt, 256, 0, st>>>(d, d_tab, n, d_par, d_stat, d_slot, d_rim, d_rootn, d_rows, d_cnt, max_regions);
@@ -539,26 +640,195 @@ static int rg_group(RgWs& ws, int g0, int g1, const uint8_t* const* labels, cons
     bool any_mask = false;
     for (int k = 0; k < n; ++k) any_mask |= h_tab[k].want_mask != 0;
     if (any_mask) rg_unpack_kernel<<<nt, 256, 0, st>>>(d, d_tab, n);
+    if (lay.poly && max_regions > 0) {
+        long long* const d_nv = (long long*)(d + lay.nv);
+        long long* const d_voff = (long long*)(d + lay.voff);
+        long long* const d_mapv = (long long*)(d + lay.mapv);
+        const int nb = cdiv(n * max_regions, 64);                       // (rg_check_list: the table's ints fit 31 bits)
+        rg_trace_kernel<0><<<nb, 64, 0, st>>>(d, d_tab, n, d_rows, d_cnt, max_regions, d_nv, d_voff, d_mapv, nullptr);
+        rg_scan_kernel<<<1, 256, 0, st>>>(d_cnt, n, max_regions, d_nv, d_voff, d_mapv, lay.vcap, lay.per_map);
+        rg_trace_kernel<1><<<nb, 64, 0, st>>>(d, d_tab, n, d_rows, d_cnt, max_regions, d_nv, d_voff, d_mapv, (int*)(d + lay.xy));
+    }
     PSEG_HIP(hipGetLastError());
+    return PSEG_OK;
+}
+
+// what a polygon call gathers over its groups before anything reaches the caller's arrays
+struct RgPolyOut {
+    int64_t cap;
+    std::vector<int32_t> xy;                       // the vertices so far, in the order of the sorted rows
+    std::vector<int64_t> first;                    // n x (max_regions + 1)
+    std::vector<int> status;
+    int64_t need = 0;                              // the vertices of the list so far
+};
+
+// a map's sorted rows, its polygons behind the list's, its row of offsets: seg(j) hands out the vertices of the row that was at j
+// before the sort and their number
+template <class Seg>
+static void rg_poly_map(RgPolyOut& po, int i, int max_regions, int32_t* rows, int c, int st, long long tot, Seg seg) {
+    int64_t* const f = po.first.data() + (size_t)i * (max_regions + 1);
+    po.status[i] = st;
+    const bool over = po.need + tot > po.cap || po.need > po.cap;
+    po.need += tot;
+    if (st != PSEG_OK || over) {
+        for (int j = 0; j <= max_regions; ++j) f[j] = (int64_t)(po.xy.size() / 2);
+        return;
+    }
+    for (int j = 0; j < c; ++j) {
+        long long nv = 0;
+        const int32_t* const src = seg(rows[(size_t)j * RG_ROW_INTS + 7], &nv);
+        rows[(size_t)j * RG_ROW_INTS + 7] = 0;
+        f[j] = (int64_t)(po.xy.size() / 2);
+        po.xy.insert(po.xy.end(), src, src + 2 * nv);
+    }
+    for (int j = c; j <= max_regions; ++j) f[j] = (int64_t)(po.xy.size() / 2);
+}
+
+static int rg_group(RgWs& ws, int g0, int g1, const uint8_t* const* labels, const int* H, const int* W, const pseg_regions* how,
+                    uint8_t* const* out_mask, int max_regions, int32_t* out_table, int* out_count, RgPolyOut* po) {
+    const int n = g1 - g0;
+    const size_t tab_b = up256((size_t)n * sizeof(RgMap));
+    long long vcap = 0;
+    if (po && max_regions > 0) {                                       // no polygon has more vertices than twice the map's corners
+        for (int k = 0; k < n; ++k) vcap += 2ll * (H[g0 + k] + 1) * (W[g0 + k] + 1);
+        vcap = std::min<long long>(vcap, std::max<int64_t>(po->cap - po->need, 0));
+    }
+    const size_t rows_n = (size_t)n * max_regions;
+    Bump hp{tab_b};                                                    // the page-locked records: table, counts, rows, vertex counts, offsets, map records
+    const size_t p_cnt = hp.take((size_t)n * 4), p_rows = hp.take(rows_n * RG_ROW_INTS * 4), p_nv = hp.take(po ? rows_n * 8 : 0),
+                 p_voff = hp.take(po ? rows_n * 8 : 0), p_mapv = hp.take(po ? (size_t)n * RG_MAPV * 8 : 0);
+    PSEG_TRY(ws.pin.ensure(hp.off, "text regions records"));
+    RgMap* const h_tab = ws.pin.as<RgMap>();
+    RgLay lay;
+    PSEG_TRY(rg_plan(n, H + g0, W + g0, how + g0, max_regions, po != nullptr, vcap, 0, h_tab, lay));
+    Bump at{lay.bytes};                                                // the label maps' bytes behind the stage's workspace
+    std::vector<size_t> lab_off(n);
+    for (int k = 0; k < n; ++k) lab_off[k] = at.take((size_t)H[g0 + k] * W[g0 + k]);
+    PSEG_TRY(ws.dev.ensure(at.off, "text regions workspace"));
+    if (!ws.st) PSEG_HIP(hipStreamCreateWithFlags(&ws.st, hipStreamNonBlocking));
+    hipStream_t st = ws.st;
+    uint8_t* const d = ws.dev.p;
+    for (int k = 0; k < n; ++k) {
+        h_tab[k].lab = (unsigned long long)(uintptr_t)(d + lab_off[k]);
+        h_tab[k].want_mask = out_mask && out_mask[g0 + k];
+    }
+    GroupDrain drain{st};
+    for (int k = 0; k < n; ++k)
+        PSEG_HIP(hipMemcpyAsync(d + lab_off[k], labels[g0 + k], (size_t)h_tab[k].H * h_tab[k].W, hipMemcpyHostToDevice, st));
+    PSEG_TRY(rg_enqueue(st, d, h_tab, lay, n, max_regions));
     for (int k = 0; k < n; ++k)
         if (h_tab[k].want_mask)
-            PSEG_HIP(hipMemcpyAsync(out_mask[g0 + k], d + h_tab[k].lab_off, (size_t)h_tab[k].H * h_tab[k].W, hipMemcpyDeviceToHost, st));
-    int* const h_cnt = (int*)(ws.pin.p + tab_b);
-    int* const h_rows = (int*)(ws.pin.p + tab_b + cnt_b);
-    PSEG_HIP(hipMemcpyAsync(h_cnt, d_cnt, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+            PSEG_HIP(hipMemcpyAsync(out_mask[g0 + k], d + lab_off[k], (size_t)h_tab[k].H * h_tab[k].W, hipMemcpyDeviceToHost, st));
+    int* const h_cnt = (int*)(ws.pin.p + p_cnt);
+    int* const h_rows = (int*)(ws.pin.p + p_rows);
+    const long long* const h_nv = (const long long*)(ws.pin.p + p_nv);
+    const long long* const h_voff = (const long long*)(ws.pin.p + p_voff);
+    const long long* const h_mapv = (const long long*)(ws.pin.p + p_mapv);
+    PSEG_HIP(hipMemcpyAsync(h_cnt, d + lay.cnt, (size_t)n * 4, hipMemcpyDeviceToHost, st));
     if (max_regions > 0 && out_table)
-        PSEG_HIP(hipMemcpyAsync(h_rows, d_rows, (size_t)n * max_regions * RG_ROW_INTS * 4, hipMemcpyDeviceToHost, st));
-    PSEG_HIP(hipStreamSynchronize(st));                                // the group's one wait
+        PSEG_HIP(hipMemcpyAsync(h_rows, d + lay.rows, rows_n * RG_ROW_INTS * 4, hipMemcpyDeviceToHost, st));
+    if (po && max_regions > 0) PSEG_HIP(hipMemcpyAsync((void*)h_mapv, d + lay.mapv, (size_t)n * RG_MAPV * 8, hipMemcpyDeviceToHost, st));
+    PSEG_HIP(hipStreamSynchronize(st));                                // the group's one wait (a polygon call: one more for the vertices)
+    const int32_t* h_xy = nullptr;
+    if (po && max_regions > 0) {
+        long long gtot = 0;
+        for (int k = 0; k < n; ++k) gtot += h_mapv[(size_t)k * RG_MAPV];
+        if (gtot > 0 && gtot <= vcap) {                                // exactly what the group holds: per map its rows' counts and offsets, then the vertices
+            PSEG_TRY(ws.pinv.ensure((size_t)gtot * 8, "text regions vertices"));
+            for (int k = 0; k < n; ++k) {
+                const int c = h_cnt[k];
+                if (c <= 0 || c > max_regions) continue;
+                const size_t o = (size_t)k * max_regions * 8;
+                PSEG_HIP(hipMemcpyAsync((uint8_t*)h_nv + o, d + lay.nv + o, (size_t)c * 8, hipMemcpyDeviceToHost, st));
+                PSEG_HIP(hipMemcpyAsync((uint8_t*)h_voff + o, d + lay.voff + o, (size_t)c * 8, hipMemcpyDeviceToHost, st));
+            }
+            PSEG_HIP(hipMemcpyAsync(ws.pinv.p, d + lay.xy, (size_t)gtot * 8, hipMemcpyDeviceToHost, st));
+            PSEG_HIP(hipStreamSynchronize(st));
+            h_xy = (const int32_t*)ws.pinv.p;
+        }
+    }
     drain.armed = false;
     for (int k = 0; k < n; ++k) {
         const int c = h_cnt[k];
         out_count[g0 + k] = c;
-        if (!out_table || c > max_regions || c <= 0) continue;
+        const bool rows_ok = out_table && c <= max_regions && c > 0;
         int* const src = h_rows + (size_t)k * max_regions * RG_ROW_INTS;
-        rg_sort_rows(src, c);
-        std::memcpy(out_table + (size_t)(g0 + k) * max_regions * RG_ROW_INTS, src, (size_t)c * RG_ROW_INTS * 4);
+        if (rows_ok) {
+            if (po) for (int j = 0; j < c; ++j) src[(size_t)j * RG_ROW_INTS + 7] = j;   // the sort carries a row's place along
+            rg_sort_rows(src, c);
+        }
+        if (po) {
+            const long long* const mv = h_mapv + (size_t)k * RG_MAPV;
+            const int stt = c > max_regions ? (int)PSEG_EUNSUPPORTED : max_regions > 0 ? (int)mv[2] : (int)PSEG_OK;
+            rg_poly_map(*po, g0 + k, max_regions, src, rows_ok ? c : 0, stt, (max_regions > 0 && stt == PSEG_OK) ? mv[0] : 0, [&](int j, long long* nv) {
+                const size_t t = (size_t)k * max_regions + j;
+                *nv = h_xy ? h_nv[t] : 0;
+                return h_xy ? h_xy + 2 * h_voff[t] : nullptr;
+            });
+        }
+        if (rows_ok) std::memcpy(out_table + (size_t)(g0 + k) * max_regions * RG_ROW_INTS, src, (size_t)c * RG_ROW_INTS * 4);
     }
     return PSEG_OK;
+}
+
+// ---- the stage as the page chain sees it (pseg_regions.h) ---------------------------------------------------------------------------
+int rg_stage_check(const pseg_regions& how, const char* what, int i) {
+    if (how.label < 0 || how.label > 255) return fail(PSEG_EINVAL, "%s %d: label %d outside 0..255", what, i, how.label);
+    const int k[3] = {how.k_close, how.k_open, how.k_join};
+    for (int j = 0; j < 3; ++j)
+        if (!rg_side_ok(k[j])) return fail(PSEG_EINVAL, "%s %d: side %d outside 1..%d", what, i, k[j], RG_SIDE_MAX);
+    return PSEG_OK;
+}
+static void rg_stage_lay(const RgLay& lay, int n, RgStageLay* out) {
+    out->cnt = lay.cnt; out->rows = lay.rows; out->nv = lay.nv; out->voff = lay.voff; out->mapv = lay.mapv; out->xy = lay.xy;
+    out->bytes = lay.bytes; out->tab_bytes = up256((size_t)n * sizeof(RgMap));
+}
+int rg_stage_plan(int n, const int* H, const int* W, int max_regions, long long max_vertices, RgStageLay* out) {
+    std::vector<RgMap> tab(up256((size_t)n * sizeof(RgMap)) / sizeof(RgMap) + 1);
+    RgLay lay;
+    PSEG_TRY(rg_plan(n, H, W, nullptr, max_regions, 1, max_vertices, 1, tab.data(), lay));
+    rg_stage_lay(lay, n, out);
+    return PSEG_OK;
+}
+int rg_stage_enqueue(hipStream_t st, uint8_t* d, void* h_tab, int n, const uint8_t* const* d_labels, const int* H, const int* W,
+                     const pseg_regions* how, int max_regions, long long max_vertices, size_t d_cap, size_t h_cap, RgStageLay* out) {
+    RgLay lay;
+    RgMap* const tab = (RgMap*)h_tab;
+    if (up256((size_t)n * sizeof(RgMap)) > h_cap) return fail(PSEG_EHIP, "regions stage: a table of %d maps does not fit %zu page-locked bytes", n, h_cap);
+    PSEG_TRY(rg_plan(n, H, W, how, max_regions, 1, max_vertices, 1, tab, lay));
+    if (lay.bytes > d_cap) return fail(PSEG_EHIP, "regions stage: %zu bytes of workspace, %zu reserved", lay.bytes, d_cap);   // before anything is launched
+    for (int k = 0; k < n; ++k) tab[k].lab = (unsigned long long)(uintptr_t)d_labels[k];
+    rg_stage_lay(lay, n, out);
+    return rg_enqueue(st, d, tab, lay, n, max_regions);
+}
+// One page's blob from what the stage left (pseg.h, pseg_predict_chain_pages_regions_png): rows, nv and voff are the page's first
+// min(count, max_regions) entries in the order the device appended them (rows is sorted here), xy the page's vertices, base its first
+// vertex in the group's array.
+void rg_stage_blob(int count, int max_regions, long long max_vertices, const long long* mapv, int32_t* rows, const long long* nv,
+                   const long long* voff, const int32_t* xy, std::vector<int32_t>& blob) {
+    const long long tot = mapv[0], base = mapv[1];
+    const int st = count > max_regions ? (int)PSEG_EUNSUPPORTED : mapv[2] != PSEG_OK ? (int)mapv[2] : tot > max_vertices ? (int)PSEG_ENOMEM : (int)PSEG_OK;
+    blob.assign(4, 0);
+    blob[0] = count; blob[1] = (int32_t)tot; blob[2] = st;
+    if (count > max_regions || count <= 0) return;
+    for (int j = 0; j < count; ++j) rows[(size_t)j * RG_ROW_INTS + 7] = j;
+    rg_sort_rows(rows, count);
+    std::vector<int> perm(count);
+    for (int j = 0; j < count; ++j) { perm[j] = rows[(size_t)j * RG_ROW_INTS + 7]; rows[(size_t)j * RG_ROW_INTS + 7] = 0; }
+    blob.insert(blob.end(), rows, rows + (size_t)count * RG_ROW_INTS);
+    if (st != PSEG_OK) return;
+    const size_t o_first = blob.size();
+    blob.resize(o_first + count + 1 + 2 * (size_t)tot);
+    int32_t* const first = blob.data() + o_first;
+    int32_t* const out = first + count + 1;
+    long long run = 0;
+    for (int j = 0; j < count; ++j) {
+        const int s = perm[j];
+        first[j] = (int32_t)run;
+        std::memcpy(out + 2 * run, xy + 2 * (voff[s] - base), (size_t)nv[s] * 8);
+        run += nv[s];
+    }
+    first[count] = (int32_t)run;
 }
 
 // what both list entries refuse, before any work
@@ -571,10 +841,7 @@ static int rg_check_list(int n, const uint8_t* const* labels, const int* H, cons
         if (!labels[i]) return fail(PSEG_EINVAL, "map %d: NULL argument", i);
         if (H[i] <= 0 || W[i] <= 0) return fail(PSEG_EINVAL, "map %d: empty image (%d,%d)", i, H[i], W[i]);
         if ((int64_t)H[i] * W[i] > 0x7fffffffLL) return fail(PSEG_EUNSUPPORTED, "map %d: image too large", i);
-        if (how[i].label < 0 || how[i].label > 255) return fail(PSEG_EINVAL, "map %d: label %d outside 0..255", i, how[i].label);
-        const int k[3] = {how[i].k_close, how[i].k_open, how[i].k_join};
-        for (int j = 0; j < 3; ++j)
-            if (!rg_side_ok(k[j])) return fail(PSEG_EINVAL, "map %d: side %d outside 1..%d", i, k[j], RG_SIDE_MAX);
+        PSEG_TRY(rg_stage_check(how[i], "map", i));
     }
     return PSEG_OK;
 }
@@ -625,7 +892,8 @@ static void rg_host_label(const std::vector<uint8_t>& px, int H, int W, std::vec
     for (size_t o = 0; o < px.size(); ++o)
         if (lab[o] >= 0) lab[o] = rg_host_find(par, lab[o]);
 }
-static void rg_host_one(const uint8_t* labels, int H, int W, const pseg_regions& how, uint8_t* out_mask, int max_regions, int32_t* table, int* count) {
+static void rg_host_one(const uint8_t* labels, int H, int W, const pseg_regions& how, uint8_t* out_mask, int max_regions, int32_t* table, int* count,
+                        std::vector<rg_word>* plane_T = nullptr) {
     const int wpr = rg_words(W);
     const size_t px = (size_t)H * W;
     std::vector<rg_word> A((size_t)H * wpr, 0ull), B, C;
@@ -677,6 +945,12 @@ static void rg_host_one(const uint8_t* labels, int H, int W, const pseg_regions&
     *count = c;
     if (table && c <= max_regions && c > 0) std::memcpy(table, rows.data(), rows.size() * 4);
     if (out_mask) std::memcpy(out_mask, T.data(), px);
+    if (plane_T) {                                                     // T as the device leaves it: a canonical bit plane
+        plane_T->assign((size_t)H * wpr, 0ull);
+        for (int y = 0; y < H; ++y)
+            for (int x = 0; x < W; ++x)
+                if (T[(size_t)y * W + x]) (*plane_T)[(size_t)y * wpr + (x >> 6)] |= 1ull << (x & 63);
+    }
 }
 
 // ---- the crack polygon of a region: its outer boundary along pixel edges, clockwise from the seed's top-left corner -----------------
@@ -720,7 +994,7 @@ int pseg_text_regions(int device, int n, const uint8_t* const* labels, const int
     if (n == 0) return PSEG_OK;
     PSEG_TRY(rg_check_list(n, labels, H, W, how, max_regions, out_table, out_count));
     return run_list(g_rg, device, n, [&](int i) { return (size_t)H[i] * W[i]; }, [&](RgWs& ws, int g0, int g1) {
-        return rg_group(ws, g0, g1, labels, H, W, how, out_mask, max_regions, out_table, out_count);
+        return rg_group(ws, g0, g1, labels, H, W, how, out_mask, max_regions, out_table, out_count, nullptr);
     });
 }
 
@@ -731,6 +1005,90 @@ int pseg_text_regions_host(int n, const uint8_t* const* labels, const int* H, co
     for (int i = 0; i < n; ++i)
         rg_host_one(labels[i], H[i], W[i], how[i], out_mask ? out_mask[i] : nullptr, max_regions,
                     out_table ? out_table + (size_t)i * max_regions * RG_ROW_INTS : nullptr, &out_count[i]);
+    return PSEG_OK;
+}
+
+}  // extern "C"
+
+namespace pseg {
+
+static int rg_check_poly(int n, const int32_t* xy, int64_t cap, const int64_t* first, const int* status) {
+    if (n > 0 && (!first || !status)) return fail(PSEG_EINVAL, "NULL argument");
+    if (cap < 0 || (cap > 0 && !xy)) return fail(PSEG_EINVAL, "a vertex capacity of %lld with %s array", (long long)cap, xy ? "an" : "no");
+    return PSEG_OK;
+}
+static void rg_poly_begin(RgPolyOut& po, int n, int max_regions, int64_t cap) {
+    po.cap = cap;
+    po.first.assign((size_t)n * (max_regions + 1), 0);
+    po.status.assign(n, PSEG_OK);
+}
+// the capacity protocol: too small -> the needed total in the last offset, no vertex and no other offset
+static void rg_poly_deliver(const RgPolyOut& po, int n, int max_regions, int32_t* xy, int64_t* first, int* status) {
+    std::memcpy(status, po.status.data(), (size_t)n * sizeof(int));
+    if (po.need > po.cap) {
+        first[(size_t)n * (max_regions + 1) - 1] = po.need;
+        return;
+    }
+    if (!po.xy.empty()) std::memcpy(xy, po.xy.data(), po.xy.size() * 4);
+    std::memcpy(first, po.first.data(), po.first.size() * 8);
+}
+
+}  // namespace pseg
+
+extern "C" {
+
+int pseg_text_regions_poly(int device, int n, const uint8_t* const* labels, const int* H, const int* W, const pseg_regions* how,
+                           uint8_t* const* out_mask, int max_regions, int32_t* out_table, int* out_count,
+                           int32_t* xy, int64_t cap, int64_t* first, int* status) {
+    if (n == 0) return PSEG_OK;
+    PSEG_TRY(rg_check_list(n, labels, H, W, how, max_regions, out_table, out_count));
+    PSEG_TRY(rg_check_poly(n, xy, cap, first, status));
+    RgPolyOut po;
+    rg_poly_begin(po, n, max_regions, cap);
+    PSEG_TRY(run_list(g_rg, device, n, [&](int i) { return (size_t)H[i] * W[i]; }, [&](RgWs& ws, int g0, int g1) {
+        return rg_group(ws, g0, g1, labels, H, W, how, out_mask, max_regions, out_table, out_count, &po);
+    }));
+    rg_poly_deliver(po, n, max_regions, xy, first, status);
+    return PSEG_OK;
+}
+
+int pseg_text_regions_poly_host(int n, const uint8_t* const* labels, const int* H, const int* W, const pseg_regions* how,
+                                uint8_t* const* out_mask, int max_regions, int32_t* out_table, int* out_count,
+                                int32_t* xy, int64_t cap, int64_t* first, int* status) {
+    if (n == 0) return PSEG_OK;
+    PSEG_TRY(rg_check_list(n, labels, H, W, how, max_regions, out_table, out_count));
+    PSEG_TRY(rg_check_poly(n, xy, cap, first, status));
+    RgPolyOut po;
+    rg_poly_begin(po, n, max_regions, cap);
+    std::vector<rg_word> T;
+    std::vector<int32_t> rows, seg;
+    std::vector<long long> nv, off;
+    for (int i = 0; i < n; ++i) {
+        int32_t* const tb = out_table ? out_table + (size_t)i * max_regions * RG_ROW_INTS : nullptr;
+        rg_host_one(labels[i], H[i], W[i], how[i], out_mask ? out_mask[i] : nullptr, max_regions, tb, &out_count[i], &T);
+        const int c = out_count[i], wpr = rg_words(W[i]);
+        const bool rows_ok = tb && c <= max_regions && c > 0;
+        int st = c > max_regions ? PSEG_EUNSUPPORTED : PSEG_OK;
+        rows.assign(tb, tb + (rows_ok ? (size_t)c * RG_ROW_INTS : 0));
+        nv.assign(rows_ok ? c : 0, 0);
+        off.assign(rows_ok ? c + 1 : 1, 0);
+        for (int j = 0; rows_ok && j < c; ++j) {
+            nv[j] = rg_trace_words(T.data(), H[i], W[i], wpr, rows[(size_t)j * RG_ROW_INTS + 6], rows[(size_t)j * RG_ROW_INTS + 5], nullptr, 0);
+            if (nv[j] < 0) st = PSEG_EHIP;
+            off[j + 1] = off[j] + (nv[j] < 0 ? 0 : nv[j]);
+            rows[(size_t)j * RG_ROW_INTS + 7] = j;
+        }
+        const long long tot = st == PSEG_OK ? off.back() : 0;
+        const bool fits = st == PSEG_OK && po.need + tot <= po.cap;
+        seg.assign(fits ? (size_t)tot * 2 : 0, 0);                     // exactly the map's vertices
+        for (int j = 0; fits && j < c; ++j)
+            (void)rg_trace_words(T.data(), H[i], W[i], wpr, rows[(size_t)j * RG_ROW_INTS + 6], rows[(size_t)j * RG_ROW_INTS + 5], seg.data() + 2 * off[j], nv[j]);
+        rg_poly_map(po, i, max_regions, rows.data(), rows_ok ? c : 0, st, tot, [&](int j, long long* cnt) {
+            *cnt = fits ? nv[j] : 0;
+            return fits ? seg.data() + 2 * off[j] : (const int32_t*)nullptr;
+        });
+    }
+    rg_poly_deliver(po, n, max_regions, xy, first, status);
     return PSEG_OK;
 }
 

@@ -46,9 +46,12 @@ def _label_of(color_map_or_label, name="text"):
 
 
 def regions_of_record(record):
-    """The TextRegion list of one pseg_amd.text_regions record (its mask is needed: masks=True)."""
+    """The TextRegion list of one pseg_amd.text_regions record: from its "polygons" when it has them (polygons=True: no mask is
+    needed), else traced on the host from its mask (masks=True)."""
     from pseg_amd import engine
-    polys = engine.trace_regions(record["mask"], record)
+    polys = record.get("polygons")
+    if polys is None:
+        polys = engine.trace_regions(record["mask"], record)
     return [TextRegion(p, b, a, s) for p, b, a, s in zip(polys, record["boxes"], record["areas"], record["seeds"])]
 
 

@@ -262,18 +262,34 @@ class Predictor:
             scores += evaluate_pages([data.mask for data in part], labels, binaries, rules, connectivity)
         return scores
 
-    def predict_regions(self, dataset: Dataset, label, chunk=64):
+    #: predict_regions' route when none is given: "list" until the chain route has been measured against it (README, text regions)
+    REGIONS_ROUTE_DEFAULT = "list"
+
+    def predict_regions(self, dataset: Dataset, label, chunk=64, route=None):
         """The text regions of every page of a dataset: one list of pc_segmentation.TextRegion per page, in dataset order.  Per
         chunk of `chunk` pages the label maps come from the list route evaluate_dataset uses (the settings' post-processors and
         high_res_output; pages it cannot take go through predict_single), at their final shape, and ONE pseg_amd.text_regions call
         turns them into masks and region tables; the polygons are traced on the host.  label: the label id, or a ColorMap (its
-        label named "text").  A page's char_height is its line_height_px at the scale of its label map."""
+        label named "text").  A page's char_height is its line_height_px at the scale of its label map.
+        route: "list" is the above; "chain" makes ONE chain call per chunk with the regions stage (Engine.predict_chain_pages with
+        which=(), labels=False, regions=...): the label maps never leave the device, the regions and their polygons come back.  A
+        page whose record has a non-zero status, or one the list chain cannot take, goes through the list route, in place and in
+        order.  None: REGIONS_ROUTE_DEFAULT.  Both routes give the same regions."""
         from pseg_amd import engine
         from .pc_segmentation import _label_of, regions_of_record
+        route = self.REGIONS_ROUTE_DEFAULT if route is None else route
+        if route not in ("chain", "list"):
+            raise Exception("predict_regions: route must be 'chain' or 'list', got %r" % (route,))
         lid = _label_of(label)
         pages = list(dataset.data)
         out = []
         step = max(1, int(chunk))
+
+        def height(data, final_h):
+            ch = data.line_height_px or 1
+            if data.original_shape is not None and data.original_shape[0]:
+                ch = ch * final_h / data.original_shape[0]
+            return ch
         for i in range(0, len(pages), step):
             part = pages[i:i + step]
             inputs = []
@@ -282,7 +298,20 @@ class Predictor:
                 if inputs[-1] is not None and not self._list_takes(np.shape(inputs[-1][1])[:2]):
                     inputs[-1] = None
             labels = [None] * len(part)
+            done = [None] * len(part)
             on_device = [k for k, got in enumerate(inputs) if got is not None]
+            if on_device and route == "chain":
+                shapes = set((tuple(np.shape(inputs[k][1])[:2]), inputs[k][3] or tuple(np.shape(inputs[k][1])[:2])) for k in on_device)
+                hows = [engine.TextRegions(lid, char_height=height(part[k], (inputs[k][3] or np.shape(inputs[k][1]))[0])) for k in on_device]
+                got = self.network.model.predict_chain_pages(
+                    [inputs[k][1] for k in on_device], binaries=[inputs[k][2] for k in on_device],
+                    out_shapes=[inputs[k][3] for k in on_device], post_ops=inputs[on_device[0]][4],
+                    exact_labels=self.network.exact == "labels", which=(), labels=False, mixed=self.MIXED_DEFAULT and len(shapes) > 1,
+                    regions=hows)
+                for j, k in enumerate(on_device):
+                    if got[j]["regions"]["status"] == 0:
+                        done[k] = regions_of_record(got[j]["regions"])
+                on_device = [k for k in on_device if done[k] is None]
             if on_device:
                 shapes = set((tuple(np.shape(inputs[k][1])[:2]), inputs[k][3] or tuple(np.shape(inputs[k][1])[:2])) for k in on_device)
                 got = self.network.model.predict_chain_pages(
@@ -291,15 +320,15 @@ class Predictor:
                     exact_labels=self.network.exact == "labels", which=(), labels=True, mixed=self.MIXED_DEFAULT and len(shapes) > 1)
                 for j, k in enumerate(on_device):
                     labels[k] = got[j]["labels"]
-            how = []
-            for k, data in enumerate(part):
+            how, rest = [], [k for k in range(len(part)) if done[k] is None]
+            for k in rest:
                 if inputs[k] is None:
-                    labels[k] = np.asarray(self.predict_single(data).labels).astype(np.uint8)
-                ch = data.line_height_px or 1
-                if data.original_shape is not None and data.original_shape[0]:
-                    ch = ch * np.shape(labels[k])[0] / data.original_shape[0]
-                how.append(engine.TextRegions(lid, char_height=ch))
-            out += [regions_of_record(rec) for rec in engine.text_regions(labels, how)]
+                    labels[k] = np.asarray(self.predict_single(part[k]).labels).astype(np.uint8)
+                how.append(engine.TextRegions(lid, char_height=height(part[k], np.shape(labels[k])[0])))
+            if rest:
+                for k, rec in zip(rest, engine.text_regions([labels[k] for k in rest], how)):
+                    done[k] = regions_of_record(rec)
+            out += done
         return out
 
     def _scan_route(self, entry: SingleData, path):
@@ -310,7 +339,7 @@ class Predictor:
                 and self._chain_ops() is not None and net.n_classes <= 256 and not getattr(net, "_rgb", False))
 
     def write_masks_scans(self, entries, loader, output_dir=None, level=None, chunk_pages=64, decode_threads=2, decode="host", binarize=None,
-                          despeckle=None):
+                          despeckle=None, regions=None, on_regions=None):
         """loader.load_images + write_masks_dataset for entries that name their scan by image_path, without the normalised page, the
         binarisation or the label map visiting the host: the decoded gray scans go through Engine.predict_chain_scans chunk_pages at
         a time (binarisation and line-height normalisation on the device, then the page chain), and each PNG stream is written to
@@ -339,7 +368,16 @@ class Predictor:
         despeckle: None or a pseg_amd.Despeckle: the ink map (of either threshold) loses every component of at most max_area pixels
         on the device inside the chain, in front of the sampler -- the files of DatasetLoader(despeckle=...).load_images +
         write_masks_dataset.  A max_area=None takes pseg_amd.despeckle_area of the entry's line height, the measured one for
-        entries measured here; the fallback route loads the entry with the same despeckling."""
+        entries measured here; the fallback route loads the entry with the same despeckling.
+        regions: None, or a label id or a ColorMap (its label named "text"): the chain call gets the regions stage
+        (Engine.predict_chain_scans(regions=...)), so a book goes from files to mask files and region polygons in one pass, and
+        on_regions(entry_index, [TextRegion]) is called for every entry, in order, before its paths are yielded.  The regions are
+        predict_regions' for the loaded entry: char_height is the entry's line_height_px at the scale of its label map, the
+        measured height for entries measured here.  The mask files are those of the call without `regions`.  A page whose record
+        comes back with a non-zero status, and every entry on the fallback route, gets its regions from predict_regions(route="list")
+        on the loaded entry."""
+        if (regions is None) != (on_regions is None):
+            raise Exception("write_masks_scans: regions and on_regions go together")
         if decode not in ("host", "device"):
             raise Exception(f"decode must be 'host' or 'device', got {decode!r}")
         from .dataset import check_binarize, check_despeckle
@@ -349,6 +387,8 @@ class Predictor:
         from pseg_amd import engine as _eng
         from . import dataset as _ds
         from . import output
+        from .pc_segmentation import _label_of, regions_of_record
+        lid = None if regions is None else _label_of(regions)
         level = output.DEVICE_PNG_LEVEL if level is None else level
         output_dir = output_dir if output_dir is not None else self.settings.output
         if output_dir is None:
@@ -359,6 +399,15 @@ class Predictor:
         step = max(1, int(chunk_pages))
         names = ("color", "overlay", "inverted")
         high_res = bool(self.settings.high_res_output)
+
+        def load(entry):
+            """The entry as the fallback route loads it (the caller's entry is not modified)."""
+            if despeckle is not None:
+                return loader._load_images(entry, binarize if binarize is not None else getattr(loader, "binarize", None), despeckle)
+            return loader.load_images(entry) if binarize is None else loader._load_images(entry, binarize)
+
+        def regions_of_loaded(loaded):
+            return self.predict_regions(Dataset([loaded], self.settings.color_map), lid, route="list")[0]
 
         def decode_entry(entry):
             return np.ascontiguousarray(_ds._imread_gray(entry.image_path), dtype=np.uint8)
@@ -424,25 +473,36 @@ class Predictor:
                         scans[k] = (scan, scale)
                 stop = len(chunk) if failed is None else failed[0]
                 on_device = [k for k in range(stop) if scans[k] is not None]
+                found = [None] * len(chunk)
                 if on_device:
-                    def to_file(page, name, stream, paths=paths, on_device=on_device):
+                    def to_file(page, name, stream, paths=paths, on_device=on_device, found=found):
+                        if name == "regions":
+                            if stream["status"] == 0:
+                                found[on_device[page]] = regions_of_record(stream)
+                            return
                         with open(paths[on_device[page]][names.index(name)], "wb") as f:
                             f.write(stream)
                     # (the keyword goes only with a binarisation: today's call is unchanged)
                     how = {} if binarize is None else {"binarize": [binarize.resolved(chunk[k].line_height_px) for k in on_device]}
                     if despeckle is not None:
                         how["despeckle"] = [despeckle.resolved(chunk[k].line_height_px) for k in on_device]
+                    if lid is not None:                    # predict_regions' rule: the line height at the scale of the label map
+                        final_h = [scans[k][0].shape[0] if high_res else _eng.rescale_shape(scans[k][0].shape, scans[k][1])[0] for k in on_device]
+                        how["regions"] = [_eng.TextRegions(lid, char_height=chunk[k].line_height_px * fh / scans[k][0].shape[0])
+                                          for k, fh in zip(on_device, final_h)]
                     self.network.model.predict_chain_scans(
                         [scans[k][0] for k in on_device], [scans[k][1] for k in on_device], high_res=high_res,
                         post_ops=self._chain_ops(), exact_labels=self.network.exact == "labels", lut=self.settings.color_map.lut(),
                         which=names, png_level=level, sink=to_file, **how)
                 for k in range(stop):
+                    loaded = None
                     if scans[k] is None:
-                        if despeckle is not None:
-                            loaded = loader._load_images(chunk[k], binarize if binarize is not None else getattr(loader, "binarize", None), despeckle)
-                        else:
-                            loaded = loader.load_images(chunk[k]) if binarize is None else loader._load_images(chunk[k], binarize)
+                        loaded = load(chunk[k])
                         self.write_masks(loaded, output_dir=output_dir, level=level)
+                    if lid is not None:
+                        if found[k] is None:
+                            found[k] = regions_of_loaded(loaded if loaded is not None else load(dataclasses.replace(chunk[k])))
+                        on_regions(i + k, found[k])
                     yield paths[k]
                 if failed is not None:
                     raise failed[1]

@@ -36,6 +36,7 @@ EXPORTED_SYMBOLS = (
     "pseg_label_masks", "pseg_label_masks_host", "pseg_label_masks_geometry", "pseg_label_masks_groups",
     "pseg_despeckle_maps", "pseg_despeckle_maps_host", "pseg_despeckle_geometry", "pseg_prepare_scans_clean", "pseg_predict_chain_scans_clean_png",
     "pseg_text_regions", "pseg_text_regions_host", "pseg_regions_geometry", "pseg_trace_regions_host",
+    "pseg_text_regions_poly", "pseg_text_regions_poly_host", "pseg_predict_chain_pages_regions_png", "pseg_predict_chain_scans_regions_png",
     "pseg_rescale_shape", "pseg_gaussian_kernel", "pseg_resize_nearest", "pseg_resize_nearest_device", "pseg_scale_image",
     "pseg_prepare_images", "pseg_affine_warp", "pseg_affine_warp_fill", "pseg_brightness_shift",
     "pseg_eval_confusion", "pseg_cc_label", "pseg_cc_tables", "pseg_eval_pages", "pseg_eval_page_groups",
@@ -241,9 +242,15 @@ def lib():
     L.pseg_text_regions_host.argtypes = [i, vp, vp, vp, c.POINTER(REGIONS), vp, i, vp, vp]
     L.pseg_regions_geometry.argtypes = [c.POINTER(i)] * 6
     L.pseg_trace_regions_host.argtypes = [vp, i, i, i, vp, vp, i64, vp]
+    L.pseg_predict_chain_pages_regions_png.argtypes = list(L.pseg_predict_chain_pages_png.argtypes[:-2]) + [i, c.POINTER(REGIONS), i, i] + \
+        list(L.pseg_predict_chain_pages_png.argtypes[-2:])
+    L.pseg_text_regions_poly.argtypes = [i, i, vp, vp, vp, c.POINTER(REGIONS), vp, i, vp, vp, vp, i64, vp, vp]
+    L.pseg_text_regions_poly_host.argtypes = [i, vp, vp, vp, c.POINTER(REGIONS), vp, i, vp, vp, vp, i64, vp, vp]
     L.pseg_prepare_scans_clean.argtypes = [i, i, c.POINTER(SCAN), c.POINTER(BINARIZE), c.POINTER(DESPECKLE), vp, vp, vp]
     L.pseg_predict_chain_scans_clean_png.argtypes = [vp, i, c.POINTER(SCAN), c.POINTER(BINARIZE), c.POINTER(DESPECKLE), c.POINTER(i), i, c.c_uint, vp, i, i,
                                                      c.c_uint, i, CHAIN_SINK, vp]
+    L.pseg_predict_chain_scans_regions_png.argtypes = list(L.pseg_predict_chain_scans_clean_png.argtypes[:-2]) + [c.POINTER(REGIONS), i, i] + \
+        list(L.pseg_predict_chain_scans_clean_png.argtypes[-2:])
     L.pseg_prepare_scans_bin.argtypes = [i, i, c.POINTER(SCAN), c.POINTER(BINARIZE), vp, vp, vp]
     L.pseg_predict_chain_scans_bin_png.argtypes = [vp, i, c.POINTER(SCAN), c.POINTER(BINARIZE), c.POINTER(i), i, c.c_uint, vp, i, i, c.c_uint, i, CHAIN_SINK, vp]
     L.pseg_label_masks.argtypes = [i, i, c.POINTER(MASK_SRC), vp, vp, vp, vp, i, vp, vp]
@@ -591,7 +598,8 @@ class Engine:
         return {"labels": lab, "masks": tuple(outs) if masks else None}
 
     def predict_chain_pages(self, images, binaries=None, out_shapes=None, post_ops=(), exact_labels=False, lut=None,
-                            which=("color", "overlay", "inverted"), labels=False, png_level=0, unit_cap=0, sink=None, mixed=False):
+                            which=("color", "overlay", "inverted"), labels=False, png_level=0, unit_cap=0, sink=None, mixed=False,
+                            regions=None, max_regions=256, max_vertices=1 << 16):
         """A page list through the chain to PNG streams (pseg_predict_chain_pages_png; lib/predictor.py:27-30 over :49-54): per page
         predict -> [nearest resize to out_shapes[i]] -> post-processors -> the masks named in `which` as PNG streams, units of
         same-shape pages pipelined on the device; every stream (and label map, with labels=True) has predict_chain's bytes for that
@@ -601,7 +609,13 @@ class Engine:
         the sink stops the call and is raised again after it.
         mixed=True (pseg_predict_chain_pages_mixed_png): for lists whose pages differ in shape.  Units are formed from the pages of
         one canvas (chain_units_mixed) whatever their own and their final shapes; the bytes are the same, the list return stays in
-        page order, a callable sink sees the units in the planner's order (pages of a unit in the permuted order)."""
+        page order, a callable sink sees the units in the planner's order (pages of a unit in the permuted order).
+        regions: a TextRegions or one per page (pseg_predict_chain_pages_regions_png): the text regions of every page's final label map
+        and their polygons, found and traced on the device behind the post-processors.  Every result dict gains "regions": {"boxes",
+        "areas", "seeds", "polygons", "status"} as text_regions(polygons=True) gives them for that label map; status 0, or
+        PSEG_EUNSUPPORTED (more than max_regions regions: no rows), PSEG_ENOMEM (more than max_vertices vertices: rows, polygons None)
+        or PSEG_EHIP.  A callable sink receives the record under the name "regions", after "labels".  which=() with labels=False asks
+        for the regions alone."""
         for w in which:
             if w not in MASK_NAMES:
                 raise PsegError("unknown mask %r (one of %r)" % (w, MASK_NAMES))
@@ -627,16 +641,23 @@ class Engine:
         hs, ws = I(*[im.shape[0] for im in imgs]), I(*[im.shape[1] for im in imgs])
         ho = I(*[0 if o is None else int(o[0]) for o in outs])
         wo = I(*[0 if o is None else int(o[1]) for o in outs])
+        if regions is not None:
+            rg = regions_table(regions, n, "page")
+            return self._chain_list(final, post_ops, lut, which, labels, sink,
+                                    lambda ops, t, want, cb: lib().pseg_predict_chain_pages_regions_png(
+                                        self._h, n, ip, hs, ws, ho, wo, bp, ops, len(post_ops), 1 if exact_labels else 0, _ptr(t),
+                                        0 if t is None else t.shape[0], int(png_level), want, int(unit_cap), 1 if mixed else 0, rg, int(max_regions),
+                                        int(max_vertices), cb, None), regions=True)
         entry = lib().pseg_predict_chain_pages_mixed_png if mixed else lib().pseg_predict_chain_pages_png
         return self._chain_list(final, post_ops, lut, which, labels, sink,
                                 lambda ops, t, want, cb: entry(self._h, n, ip, hs, ws, ho, wo, bp, ops, len(post_ops), 1 if exact_labels else 0,
                                                                _ptr(t), 0 if t is None else t.shape[0], int(png_level), want, int(unit_cap), cb, None))
 
-    def _chain_list(self, final, post_ops, lut, which, labels, sink, call):
+    def _chain_list(self, final, post_ops, lut, which, labels, sink, call, regions=False):
         """The part the list entries share: op ids, colour table, `want` bits and the C sink that feeds `sink` or collects the result
         dicts; call(ops, table, want, c_sink) -> the entry's return code.  final[i]: the shape of page i's label map."""
         n = len(final)
-        want = sum(1 << MASK_NAMES.index(w) for w in set(which)) | (16 if labels else 0)
+        want = sum(1 << MASK_NAMES.index(w) for w in set(which)) | (16 if labels else 0) | (32 if regions else 0)
         ops = (ctypes.c_int * max(len(post_ops), 1))(*[self.POST_OPS[o] if isinstance(o, str) else int(o) for o in post_ops])
         t = None if lut is None else np.ascontiguousarray(lut, dtype=np.uint8).reshape(-1, 3)
         collected = [{"labels": None, "masks": {}} for _ in range(n)] if sink is None else None
@@ -646,12 +667,14 @@ class Engine:
             try:
                 if k == 4:
                     item, name = np.ctypeslib.as_array(data, (n_bytes,)).reshape(final[page]).copy(), "labels"
+                elif k == 5:
+                    item, name = regions_of_blob(np.frombuffer(ctypes.string_at(data, n_bytes), np.int32)), "regions"
                 else:
                     item, name = ctypes.string_at(data, n_bytes), MASK_NAMES[k]
                 if sink is not None:
                     sink(page, name, item)
-                elif k == 4:
-                    collected[page]["labels"] = item
+                elif k == 4 or k == 5:
+                    collected[page][name] = item
                 else:
                     collected[page]["masks"][name] = item
                 return 0
@@ -667,7 +690,7 @@ class Engine:
 
     def predict_chain_scans(self, scans, scales, high_res=False, post_ops=(), exact_labels=False, lut=None,
                             which=("color", "overlay", "inverted"), labels=False, png_level=0, unit_cap=0, sink=None, binarize=None,
-                            despeckle=None):
+                            despeckle=None, regions=None, max_regions=256, max_vertices=1 << 16):
         """Scans as they come off disk through the chain to PNG streams (pseg_predict_chain_scans_png): scans[i] a gray uint8 (H0,W0)
         array, scales[i] = target_line_height / line_height_px.  The binarisation (ink = scan <= 127) and the line-height
         normalisation run on the device in front of the network: neither the normalised page nor the ink map visits the host.
@@ -678,7 +701,8 @@ class Engine:
         binarize: None (ink = scan <= 127), a Sauvola with a window, or one of either per scan (binarize_table): the ink map of
         binarize_scans takes the place of scan <= 127 everywhere (pseg_predict_chain_scans_bin_png).
         despeckle: None, a Despeckle with its max_area, or one of either per scan (despeckle_table): despeckle_maps of that ink map
-        takes its place everywhere (pseg_predict_chain_scans_clean_png); None is the call without the argument."""
+        takes its place everywhere (pseg_predict_chain_scans_clean_png); None is the call without the argument.
+        regions, max_regions, max_vertices: predict_chain_pages' (pseg_predict_chain_scans_regions_png)."""
         for w in which:
             if w not in MASK_NAMES:
                 raise PsegError("unknown mask %r (one of %r)" % (w, MASK_NAMES))
@@ -686,6 +710,13 @@ class Engine:
         n = len(plans)
         how = None if binarize is None else binarize_table(binarize, n)
         final = [keep[k].shape if high_res else plans[k][:2] for k in range(n)]
+        if regions is not None:
+            rg = regions_table(regions, n, "scan")
+            dsp = None if despeckle is None else despeckle_table(despeckle, n, "scan")
+            return self._chain_list(final, post_ops, lut, which, labels, sink,
+                                    lambda ops, t, want, cb: lib().pseg_predict_chain_scans_regions_png(
+                                        self._h, n, table, how, dsp, ops, len(post_ops), 1 if exact_labels else 0, _ptr(t), 0 if t is None else t.shape[0],
+                                        int(png_level), want, int(unit_cap), rg, int(max_regions), int(max_vertices), cb, None), regions=True)
         if despeckle is not None:
             dsp = despeckle_table(despeckle, n, "scan")
             return self._chain_list(final, post_ops, lut, which, labels, sink,
@@ -1009,6 +1040,7 @@ def masks_png(pred, binary, lut, which=("color", "overlay", "inverted"), band_ro
 # ---- PNG scans decoded on the device (include/pseg.h) ---------------------------------
 
 PNG_OK, PNG_EINVAL, PNG_EUNSUPPORTED = 0, -1, -5      # PSEG_OK, PSEG_EINVAL, PSEG_EUNSUPPORTED: the per-file statuses
+PSEG_OK, PSEG_EHIP, PSEG_ENOMEM, PSEG_EUNSUPPORTED = 0, -3, -4, -5   # include/pseg.h: the per-map / per-page statuses of the text regions
 
 
 def _file_ptr(data):
@@ -1481,6 +1513,31 @@ class TextRegions:
         return hash((self.label, self.kernels))
 
 
+def regions_table(regions, n, what="page"):
+    """A TextRegions, or one per page, as the C table of the chain's regions stage."""
+    entries = [regions] * n if isinstance(regions, TextRegions) else list(regions)
+    if len(entries) != n:
+        raise PsegError("regions must have one entry per %s (%d for %d)" % (what, len(entries), n))
+    for k, e in enumerate(entries):
+        if not isinstance(e, TextRegions):
+            raise PsegError("%s %d: regions takes a TextRegions, got %r" % (what, k, e))
+    return (REGIONS * max(n, 1))(*[REGIONS(e.label, *e.kernels) for e in entries])
+
+
+def regions_of_blob(blob):
+    """One page's blob of the chain's regions stage (include/pseg.h, pseg_predict_chain_pages_regions_png; int32) as a record: "boxes",
+    "areas", "seeds", "polygons" (None unless status is 0) and "status"."""
+    r, v, status = int(blob[0]), int(blob[1]), int(blob[2])
+    have_rows = blob.size >= 4 + 8 * r and (status == 0 or blob.size > 4)
+    rows = blob[4:4 + 8 * r].reshape(r, 8) if have_rows else np.zeros((0, 8), np.int32)
+    polys = None
+    if status == 0:
+        first = blob[4 + 8 * r:4 + 8 * r + r + 1]
+        xy = blob[4 + 9 * r + 1:4 + 9 * r + 1 + 2 * v].reshape(v, 2)
+        polys = [xy[first[j]:first[j + 1]].copy() for j in range(r)]
+    return {"boxes": rows[:, 0:4].copy(), "areas": rows[:, 4].copy(), "seeds": rows[:, 5:7].copy(), "polygons": polys, "status": status}
+
+
 def regions_geometry():
     """(word, band, band_words, tile_h, tile_w, slots) of pseg_text_regions' kernels (pseg_regions_geometry; no device)."""
     v = [ctypes.c_int() for _ in range(6)]
@@ -1501,12 +1558,46 @@ def _regions_call(ms, entries, device, masks, max_regions, host):
     return outs, rows, cnt
 
 
-def text_regions(label_maps, how, device=0, masks=True, max_regions=256, host=False):
+def _regions_poly_call(ms, entries, device, masks, max_regions, host):
+    """_regions_call with the polygons (pseg_text_regions_poly / _host): -> outs, rows, cnt, polys; polys[k] is the list of (v,2) int32
+    arrays of map k, or None where the map has more than max_regions regions.  One retry with the needed capacity."""
+    n = len(ms)
+    table = (REGIONS * n)(*[REGIONS(e.label, *e.kernels) for e in entries])
+    P, I = ctypes.c_void_p * n, ctypes.c_int * n
+    cap = 1024 * n
+    for _ in range(2):
+        outs = [np.empty(m.shape, np.uint8) for m in ms] if masks else None
+        rows = np.zeros((n, max_regions, 8), np.int32)
+        cnt = np.zeros(n, np.int32)
+        xy = np.zeros((cap, 2), np.int32)
+        first = np.zeros((n, max_regions + 1), np.int64)
+        status = np.zeros(n, np.int32)
+        args = (n, P(*[m.ctypes.data for m in ms]), I(*[m.shape[0] for m in ms]), I(*[m.shape[1] for m in ms]), table,
+                P(*[a.ctypes.data for a in outs]) if masks else None, int(max_regions), rows.ctypes.data if max_regions else None,
+                cnt.ctypes.data, xy.ctypes.data, cap, first.ctypes.data, status.ctypes.data)
+        _check(lib().pseg_text_regions_poly_host(*args) if host else lib().pseg_text_regions_poly(int(device), *args))
+        if first[n - 1, max_regions] <= cap:
+            break
+        cap = int(first[n - 1, max_regions])
+    polys = []
+    for k in range(n):
+        if status[k] == PSEG_EUNSUPPORTED:                # more regions than max_regions
+            polys.append(None)
+            continue
+        if status[k] != 0:
+            raise PsegError("map %d: a region's boundary walk did not close (status %d)" % (k, int(status[k])))
+        polys.append([xy[first[k, r]:first[k, r + 1]].copy() for r in range(int(cnt[k]))])
+    return outs, rows, cnt, polys
+
+
+def text_regions(label_maps, how, device=0, masks=True, max_regions=256, host=False, polygons=False):
     """The text regions of a list of label maps (uint8 (H,W)) in one device-resident call (pseg_text_regions): how is a TextRegions
     or one per map.  -> one dict per map: "mask" (uint8 (H,W), 1 = region; None with masks=False), "boxes" (r,4) int32 x0, y0, x1, y1
     (exclusive), "areas" (r,) int32, "seeds" (r,2) int32 (y, x) -- the region's first pixel in raster order, by which the rows are
     sorted.  A map with more than max_regions regions is run again alone with max_regions = its count.  host=True: the same bytes from
-    the host entry (pseg_text_regions_host), no device."""
+    the host entry (pseg_text_regions_host), no device.  polygons=True: every record also has "polygons", a list of (v,2) int32 arrays of
+    (x, y) pixel corners -- trace_regions' polygons, traced on the device from the bit planes in the same call
+    (pseg_text_regions_poly; with host=True its host twin)."""
     ms = [np.ascontiguousarray(m, dtype=np.uint8) for m in label_maps]
     for k, m in enumerate(ms):
         if m.ndim != 2:
@@ -1522,15 +1613,26 @@ def text_regions(label_maps, how, device=0, masks=True, max_regions=256, host=Fa
         raise PsegError("text_regions: max_regions must be a non-negative integer, got %r" % (max_regions,))
     if n == 0:
         return []
-    outs, rows, cnt = _regions_call(ms, entries, device, masks, int(max_regions), host)
+    polys = None
+    if polygons:
+        outs, rows, cnt, polys = _regions_poly_call(ms, entries, device, masks, int(max_regions), host)
+    else:
+        outs, rows, cnt = _regions_call(ms, entries, device, masks, int(max_regions), host)
     res = []
     for k in range(n):
         r, c = rows[k], int(cnt[k])
+        pk = polys[k] if polygons else None
         if c > max_regions:
-            _, r1, c1 = _regions_call([ms[k]], [entries[k]], device, False, c, host)
+            if polygons:
+                _, r1, c1, p1 = _regions_poly_call([ms[k]], [entries[k]], device, False, c, host)
+                pk = p1[0]
+            else:
+                _, r1, c1 = _regions_call([ms[k]], [entries[k]], device, False, c, host)
             r, c = r1[0], int(c1[0])
         r = r[:c]
         res.append({"mask": outs[k] if masks else None, "boxes": r[:, 0:4].copy(), "areas": r[:, 4].copy(), "seeds": r[:, 5:7].copy()})
+        if polygons:
+            res[-1]["polygons"] = pk
     return res
 
 

@@ -3,7 +3,9 @@
 // triples of tests/test_regions_host.py and shapes drawn at random -- against a plain per-pixel loop (every window offset spelled out,
 // no words, no separable passes) and a flood fill: the whole list in one call, then every map alone with its input, its mask and its
 // table placed in exact-size allocations, so that a read or write past them is caught; then pseg_trace_regions_host with exact-size
-// vertex and offset arrays, the shoelace area of every polygon of a region without an island against the table, and the cap protocol.
+// vertex and offset arrays, the shoelace area of every polygon of a region without an island against the table, and the cap protocol;
+// then pseg_text_regions_poly_host -- the word-run walk over bit planes that the device tracer shares (pseg_regions.h) -- against those
+// polygons, again from exact-size arrays and with its capacity protocol.
 // Exit status 0: no mismatch, and the refusals refuse.
 #include <cstdarg>
 #include <cstdio>
@@ -207,7 +209,7 @@ int main(int argc, char** argv) {
         if (pseg_text_regions_host(n, in.data(), H.data(), W.data(), how.data(), op.data(), cap, table.data(), count.data()) != PSEG_EUNSUPPORTED || !same()) { fprintf(stderr, "2^31 pixels were not refused\n"); ++bad; }
         if (pseg_text_regions_host(n, in.data(), nullptr, W.data(), how.data(), op.data(), cap, table.data(), count.data()) != PSEG_EINVAL) { fprintf(stderr, "a NULL array was not refused\n"); ++bad; }
     }
-    long long regions = 0, vertices = 0, islands = 0;
+    long long regions = 0, vertices = 0, islands = 0, twins = 0;
     for (int i = 0; i < n; ++i) {
         const Case& c = cases[i];
         const size_t px = c.px.size();
@@ -271,6 +273,33 @@ int main(int argc, char** argv) {
                         ++bad;
                     }
                 }
+                // the host twin of the device tracer (the word-run walk over bit planes) against the pixel walk above: the same rows,
+                // offsets and vertices from exact-size arrays, then a capacity one vertex short
+                int64_t* f2 = (int64_t*)malloc((size_t)(r + 1) * 8);
+                int32_t* xy2 = (int32_t*)malloc((size_t)(need ? need : 1) * 8);
+                int32_t* tb2 = (int32_t*)malloc((size_t)(r ? r : 1) * 8 * 4);
+                int st = -7;
+                cnt = -7;
+                if (pseg_text_regions_poly_host(1, &ip, &c.H, &c.W, &c.how, nullptr, r, r ? tb2 : nullptr, &cnt, need ? xy2 : nullptr, need, f2, &st) != PSEG_OK ||
+                    st != PSEG_OK || cnt != r || (r > 0 && memcmp(tb2, tb, (size_t)r * 8 * 4) != 0) || memcmp(f2, first, (size_t)(r + 1) * 8) != 0 ||
+                    (need > 0 && memcmp(xy2, xy, (size_t)need * 8) != 0)) {
+                    fprintf(stderr, "case %d: the word-run walk differs from the pixel walk: %s\n", i, pseg::last_error().c_str());
+                    ++bad;
+                }
+                ++twins;
+                if (need > 0) {
+                    for (int k = 0; k <= r; ++k) f2[k] = -7;
+                    int32_t* xy3 = (int32_t*)malloc((size_t)(need > 1 ? need - 1 : 1) * 8);
+                    memset(xy3, 0x5A, (size_t)(need > 1 ? need - 1 : 1) * 8);
+                    bool ok = pseg_text_regions_poly_host(1, &ip, &c.H, &c.W, &c.how, nullptr, r, tb2, &cnt, need > 1 ? xy3 : nullptr, need - 1, f2, &st) == PSEG_OK &&
+                              st == PSEG_OK && cnt == r && f2[r] == need && xy3[0] == 0x5A5A5A5A;
+                    for (int k = 0; k < r; ++k) ok = ok && f2[k] == -7;
+                    if (!ok) { fprintf(stderr, "case %d: a capacity of %lld for %lld vertices\n", i, (long long)need - 1, (long long)need); ++bad; }
+                    free(xy3);
+                }
+                free(tb2);
+                free(xy2);
+                free(f2);
             }
             free(xy);
         }
@@ -279,7 +308,7 @@ int main(int argc, char** argv) {
         free(op);
         free(in);
     }
-    printf("regions_check: %d cases against a per-pixel loop and a flood fill (%lld regions, %lld with an island, %lld vertices), %d mismatches\n",
-           n, regions, islands, vertices, bad);
+    printf("regions_check: %d cases against a per-pixel loop and a flood fill (%lld regions, %lld with an island, %lld vertices; the word-run walk of %lld cases "
+           "against the pixel walk), %d mismatches\n", n, regions, islands, vertices, twins, bad);
     return bad ? 1 : 0;
 }
