@@ -1028,6 +1028,62 @@ int pseg_predict_chain_scans_regions_png(pseg_engine* e, int n_scans, const pseg
                                          const uint8_t* lut, int n_lut, int level, unsigned want, int unit_cap,
                                          const pseg_regions* rg, int max_regions, int max_vertices, pseg_chain_sink sink, void* user);
 
+/* ---- Deskewing on the device: the skew of an ink map from strip profiles, an exact rotation --------------------- */
+
+/* Integer arithmetic only: every division below is a floor division, every >> an arithmetic shift, for negative values too.
+ * Limits: 1 <= H, W <= 16384; a denominator 64 <= D <= 4096; steps 1 <= A <= 128 with 4 A <= D (a slope is at most 1/4); for a
+ * rotation |index| * 4 <= D, order 0 or 1, fill 0..255.  Anything else is PSEG_EINVAL, the message names the map ("map 3: ...") and
+ * nothing is written.  n == 0 returns PSEG_OK before a device is touched.
+ *
+ * THE SKEW of an ink map (uint8, dense, non-zero = ink):
+ *   strips      a strip is 32 columns wide, K = ceil(W / 32); R[y][k] = ink pixels of row y in columns 32 k .. min(32 k + 31, W - 1)
+ *   candidates  a = -A .. A, the slope of candidate a is a / D
+ *   centre      cx2(k) = 64 k + 32 - W: the doubled nominal centre of strip k relative to the map's centre (also for a ragged last strip)
+ *   offset      off(a, k) = floor((a * cx2(k) + D) / (2 D))
+ *   apron       M = max |off(a, k)| over candidates and strips (reached at a = +-A, k = 0 or K - 1)
+ *   profile     P_a[j] = sum over k of R[j + off(a, k)][k]  for j = -M .. H - 1 + M; rows outside 0 .. H - 1 count 0.  The apron
+ *               drops nothing: the sum of P_a is the same for every a
+ *   score       score(a) = sum over j of P_a[j]^2, uint64 (at most 2^28 * 2^15)
+ *   winner      the largest score; ties go to the smallest |a|, then to a > 0.  A map without ink has index 0
+ * Text lines that run along y = y0 + (a / D) (x - cx) make candidate a the sharpest.
+ *
+ * THE ROTATION by index a over D: the output has the input's shape and is turned about the map's centre.
+ *   r = sqrt((double)(D D + a a));  C = floor(16384.0 * D / r + 0.5);  S = sign(a) * floor(16384.0 * |a| / r + 0.5)   (on the host)
+ *   for output pixel (y, x):  u = 2 x - (W - 1),  v = 2 y - (H - 1)
+ *     X = C u - S v + (W - 1) * 16384,   Y = S u + C v + (H - 1) * 16384      source coordinates in 1 / 32768 pixel, |X|, |Y| < 2^30
+ *   order 0:  xs = (X + 16384) >> 15, ys likewise;  out = src[ys][xs], or fill outside the map
+ *   order 1:  x0 = X >> 15, fx = X & 32767, y0, fy likewise, w = 32768;
+ *             out = ((w-fx)(w-fy) p00 + fx (w-fy) p01 + (w-fx) fy p10 + fx fy p11 + 2^29) >> 30   in 64 bits; a tap outside takes fill
+ * Index 0 is the identity, byte for byte.  Rotating by the estimated index makes the text lines horizontal; an output cannot be
+ * its own source. */
+typedef struct pseg_skew   { int steps, denom; } pseg_skew;
+typedef struct pseg_rotate { int index, denom, order, fill; } pseg_rotate;
+
+/* The skew indices of n ink maps.  out_scores: NULL, or n pointers each NULL or to 2 * steps + 1 scores (candidate a at a + steps).
+ * Host pointers, synchronous.  The list is cut into groups as pseg_despeckle_maps cuts it (64 maps, or 64 MiB of map bytes); a group
+ * costs three ragged launches (strip counts, a workgroup per candidate and map with one plain store -- no atomics, so the scores are
+ * deterministic --, the pick) and ONE host wait, nothing is allocated per map.  The workspace is grow-only, cached per device with
+ * its own stream and freed by pseg_release_workspace.  Every map is checked before any device work. */
+int pseg_skew_maps(int device, int n, const uint8_t* const* ink, const int* H, const int* W, const pseg_skew* how,
+                   int32_t* out_index, uint64_t* const* out_scores);
+/* The same on the host, without a device: the same functions (csrc/pseg_skew.h) in plain loops. */
+int pseg_skew_maps_host(int n, const uint8_t* const* ink, const int* H, const int* W, const pseg_skew* how,
+                        int32_t* out_index, uint64_t* const* out_scores);
+/* n maps rotated, one launch and one wait per group. */
+int pseg_rotate_maps(int device, int n, const uint8_t* const* src, const int* H, const int* W, const pseg_rotate* rot,
+                     uint8_t* const* out);
+int pseg_rotate_maps_host(int n, const uint8_t* const* src, const int* H, const int* W, const pseg_rotate* rot,
+                          uint8_t* const* out);
+/* Estimate and correct in one device-resident call.  ink[i] NULL (or ink NULL): ink = gray <= 127, decided on the device.
+ * out_gray[i] = gray[i] rotated by the winner, order 1, fill 255; out_index[i] the winner.  Four launches and one wait per group:
+ * no host wait lies between the estimate and the rotation, which reads the winner from device memory. */
+int pseg_deskew_scans(int device, int n, const uint8_t* const* gray, const uint8_t* const* ink, const int* H, const int* W,
+                      const pseg_skew* how, uint8_t* const* out_gray, int32_t* out_index);
+int pseg_deskew_scans_host(int n, const uint8_t* const* gray, const uint8_t* const* ink, const int* H, const int* W,
+                           const pseg_skew* how, uint8_t* const* out_gray, int32_t* out_index);
+/* The constants of the contract (host arithmetic, no device; every pointer may be NULL). */
+int pseg_skew_geometry(int* strip, int* max_steps, int* max_side);
+
 #ifdef __cplusplus
 }
 #endif

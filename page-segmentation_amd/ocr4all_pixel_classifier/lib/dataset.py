@@ -127,29 +127,60 @@ def _despeckle_binary(bin_, despeckle, line_height_px):
     return np.where(clean != 0, 0, 255).astype(np.uint8)
 
 
+def check_deskew(deskew):
+    """deskew=None (the scan as it is) or a pseg_amd.Skew; anything else raises."""
+    from pseg_amd import engine as _eng
+    if deskew is not None and not isinstance(deskew, _eng.Skew):
+        raise Exception(f"deskew must be None or a pseg_amd.Skew, got {deskew!r}")
+    return deskew
+
+
+def check_on_skew(deskew, on_skew):
+    if on_skew is not None and (deskew is None or not callable(on_skew)):
+        raise Exception("on_skew must be a callable and goes with a deskew")
+    return on_skew
+
+
 class DatasetLoader:
-    def __init__(self, target_line_height, color_map: ColorMap, prediction=False, max_width=None, binarize=None, despeckle=None):
+    def __init__(self, target_line_height, color_map: ColorMap, prediction=False, max_width=None, binarize=None, despeckle=None,
+                 deskew=None, on_skew=None):
         self.target_line_height = target_line_height
         self.prediction = prediction
         self.color_map = color_map
         self.max_width = max_width
         self.binarize = check_binarize(binarize)    # None: > 127 (imread_bin); a pseg_amd.Sauvola: the adaptive ink map on the device
         self.despeckle = check_despeckle(despeckle)  # None, or a pseg_amd.Despeckle: the ink map derived from the scan loses its specks
+        self.deskew = check_deskew(deskew)          # None, or a pseg_amd.Skew: the scan read from image_path is deskewed first, the mask with it
+        self.on_skew = check_on_skew(deskew, on_skew)   # on_skew(entry, index, denom) for every entry that was deskewed
 
     def load_images(self, entry: SingleData) -> SingleData:
         """lib/dataset.py:160-191.  The reference derives the binary from the *image* attribute /
         path (attr 'image', :172) and never reads binary_path; kept.  With a binarize, the adaptive map of the gray scan takes
         _imread_bin's place: the records carry the ink map the scan chain works on.  With a despeckle, the ink map derived from the
-        scan's file (either way) loses its specks first; a pre-loaded entry.image, which is its own binary, is left as it is."""
-        return self._load_images(entry, self.binarize, getattr(self, "despeckle", None))
+        scan's file (either way) loses its specks first; a pre-loaded entry.image, which is its own binary, is left as it is.
+        With a deskew, the gray scan read from image_path goes through pseg_amd.deskew_scans first (the skew estimated on
+        scan <= 127, the scan rotated by it, order 1, fill 255); the ink map is then derived from the deskewed scan exactly as
+        without (> 127, or binarize, then despeckle), and outside prediction the mask is rotated by the same index (order 0, fill 0:
+        the background id) before it is resized.  Page, ink map and mask are in the deskewed frame; original_shape is the scan's,
+        which the rotation keeps.  on_skew(entry, index, denom) is called where given.  A pre-loaded entry.image is not deskewed."""
+        return self._load_images(entry, self.binarize, getattr(self, "despeckle", None), getattr(self, "deskew", None), getattr(self, "on_skew", None))
 
-    def _load_images(self, entry: SingleData, binarize, despeckle=None) -> SingleData:
+    def _load_images(self, entry: SingleData, binarize, despeckle=None, deskew=None, on_skew=None) -> SingleData:
         img = entry.image if entry.image is not None else _imread_gray(entry.image_path)
         original_shape = img.shape
+        skew_index = None
+        if deskew is not None and entry.image is None:
+            from pseg_amd import engine as _eng
+            (img,), idx = _eng.deskew_scans([img], deskew)
+            skew_index = int(idx[0])
+            if on_skew is not None:
+                on_skew(entry, skew_index, deskew.denom)
         if entry.image is not None:
             bin_ = entry.image
         elif binarize is not None:
             bin_ = _binarize_gray(img, binarize, entry.line_height_px)
+        elif skew_index is not None:
+            bin_ = np.where(img > 127, 255, 0).astype(np.uint8)        # _imread_bin's rule on the deskewed scan
         else:
             bin_ = _imread_bin(entry.image_path)
         if despeckle is not None and entry.image is None:
@@ -159,6 +190,9 @@ class DatasetLoader:
         if not self.prediction:
             from .util import preserving_resize
             mask = entry.mask if entry.mask is not None else self.color_map.imread_labels(entry.mask_path)
+            if skew_index is not None:
+                from pseg_amd import engine as _eng
+                mask = _eng.rotate_maps([np.asarray(mask).astype(np.uint8)], [skew_index], denom=deskew.denom, order=0, fill=0)[0]
             mask = preserving_resize(mask, img.shape)
             assert mask.shape == img.shape
             entry.mask = mask.astype(np.uint8)
@@ -200,10 +234,19 @@ class DatasetLoader:
         entries in front of it are loaded.
         report: a list that receives one item per entry, {"label_counts": int64[256] pixels per label id, "unknown": int pixels of
         a colour the colour map does not know (they became label 0)}, or None for a fallback or prediction entry.  Every mask with
-        unknown > 0 is logged as one warning with its file name and the count."""
+        unknown > 0 is logged as one warning with its file name and the count.
+        With self.deskew set, EVERY entry goes through self.load_images, in place and in order, on purpose: the list entries hand
+        scan and mask to the device in one call each, and the rotation of both by one estimated index sits between them only in
+        load_images.  The records are load_data's."""
         from concurrent.futures import ThreadPoolExecutor
         from pseg_amd import engine as _eng
         entries = list(entries)
+        if getattr(self, "deskew", None) is not None:
+            for e in entries:
+                self.load_images(e)
+                if report is not None:
+                    report.append(None)
+            return Dataset(entries, self.color_map)
         step = max(1, int(chunk))
         colors, ids = (None, None) if self.prediction else self.color_map.table()
 

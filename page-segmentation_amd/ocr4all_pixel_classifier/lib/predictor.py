@@ -339,7 +339,7 @@ class Predictor:
                 and self._chain_ops() is not None and net.n_classes <= 256 and not getattr(net, "_rgb", False))
 
     def write_masks_scans(self, entries, loader, output_dir=None, level=None, chunk_pages=64, decode_threads=2, decode="host", binarize=None,
-                          despeckle=None, regions=None, on_regions=None):
+                          despeckle=None, regions=None, on_regions=None, deskew=None, on_skew=None):
         """loader.load_images + write_masks_dataset for entries that name their scan by image_path, without the normalised page, the
         binarisation or the label map visiting the host: the decoded gray scans go through Engine.predict_chain_scans chunk_pages at
         a time (binarisation and line-height normalisation on the device, then the page chain), and each PNG stream is written to
@@ -375,14 +375,23 @@ class Predictor:
         predict_regions' for the loaded entry: char_height is the entry's line_height_px at the scale of its label map, the
         measured height for entries measured here.  The mask files are those of the call without `regions`.  A page whose record
         comes back with a non-zero status, and every entry on the fallback route, gets its regions from predict_regions(route="list")
-        on the loaded entry."""
+        on the loaded entry.
+        deskew: None or a pseg_amd.Skew: after a chunk's scans are decoded and its missing line heights measured (on the scans as
+        decoded), ONE pseg_amd.deskew_scans call per chunk replaces the arrays of the entries on the scan route by their deskewed
+        scans (skew estimated on scan <= 127, rotation order 1, fill 255); the fallback route loads the entry with the same
+        deskew.  on_skew(entry_index, index, denom) is called for every deskewed entry, in order, before its paths are yielded (a
+        pre-loaded entry.image is not deskewed and gets no call).  The mask files are those of DatasetLoader(deskew=...).load_images
+        + write_masks_dataset.  THE MASKS (and regions) ARE IN THE DESKEWED FRAME: a mask decoded to an array goes back to the
+        scan's frame with pseg_amd.rotate_maps([mask], -index, denom) (order 0)."""
         if (regions is None) != (on_regions is None):
             raise Exception("write_masks_scans: regions and on_regions go together")
         if decode not in ("host", "device"):
             raise Exception(f"decode must be 'host' or 'device', got {decode!r}")
-        from .dataset import check_binarize, check_despeckle
+        from .dataset import check_binarize, check_despeckle, check_deskew, check_on_skew
         check_binarize(binarize)
         check_despeckle(despeckle)
+        check_deskew(deskew)
+        check_on_skew(deskew, on_skew)
         from concurrent.futures import ThreadPoolExecutor
         from pseg_amd import engine as _eng
         from . import dataset as _ds
@@ -400,8 +409,14 @@ class Predictor:
         names = ("color", "overlay", "inverted")
         high_res = bool(self.settings.high_res_output)
 
-        def load(entry):
+        def load(entry, skews=None, k=None):
             """The entry as the fallback route loads it (the caller's entry is not modified)."""
+            if deskew is not None:
+                def note(_, index, denom):
+                    if skews is not None:
+                        skews[k] = index
+                return loader._load_images(entry, binarize if binarize is not None else getattr(loader, "binarize", None),
+                                           despeckle if despeckle is not None else getattr(loader, "despeckle", None), deskew, note)
             if despeckle is not None:
                 return loader._load_images(entry, binarize if binarize is not None else getattr(loader, "binarize", None), despeckle)
             return loader.load_images(entry) if binarize is None else loader._load_images(entry, binarize)
@@ -474,6 +489,11 @@ class Predictor:
                 stop = len(chunk) if failed is None else failed[0]
                 on_device = [k for k in range(stop) if scans[k] is not None]
                 found = [None] * len(chunk)
+                skews = [None] * len(chunk)
+                if on_device and deskew is not None:       # one list call per chunk: the scan-route entries' arrays, deskewed
+                    turned, idx = _eng.deskew_scans([scans[k][0] for k in on_device], deskew, device=device)
+                    for k, t, a in zip(on_device, turned, idx):
+                        scans[k], skews[k] = (t, scans[k][1]), int(a)
                 if on_device:
                     def to_file(page, name, stream, paths=paths, on_device=on_device, found=found):
                         if name == "regions":
@@ -497,8 +517,10 @@ class Predictor:
                 for k in range(stop):
                     loaded = None
                     if scans[k] is None:
-                        loaded = load(chunk[k])
+                        loaded = load(chunk[k], skews, k)
                         self.write_masks(loaded, output_dir=output_dir, level=level)
+                    if on_skew is not None and skews[k] is not None:
+                        on_skew(i + k, skews[k], deskew.denom)
                     if lid is not None:
                         if found[k] is None:
                             found[k] = regions_of_loaded(loaded if loaded is not None else load(dataclasses.replace(chunk[k])))

@@ -9,6 +9,7 @@ from .engine import (  # noqa: F401
     Sauvola, sauvola_window, binarize_scans,
     label_masks, label_masks_geometry, label_mask_groups,
     Despeckle, despeckle_area, despeckle_maps, despeckle_geometry,
+    Skew, skew_degrees, skew_maps, rotate_maps, deskew_scans, skew_geometry,
     TextRegions, region_kernels, text_regions, trace_regions, regions_geometry,
 )
 from .build import build_library  # noqa: F401

@@ -35,6 +35,7 @@ EXPORTED_SYMBOLS = (
     "pseg_binarize_scans", "pseg_binarize_scans_host", "pseg_binarize_geometry", "pseg_prepare_scans_bin", "pseg_predict_chain_scans_bin_png",
     "pseg_label_masks", "pseg_label_masks_host", "pseg_label_masks_geometry", "pseg_label_masks_groups",
     "pseg_despeckle_maps", "pseg_despeckle_maps_host", "pseg_despeckle_geometry", "pseg_prepare_scans_clean", "pseg_predict_chain_scans_clean_png",
+    "pseg_skew_maps", "pseg_skew_maps_host", "pseg_rotate_maps", "pseg_rotate_maps_host", "pseg_deskew_scans", "pseg_deskew_scans_host", "pseg_skew_geometry",
     "pseg_text_regions", "pseg_text_regions_host", "pseg_regions_geometry", "pseg_trace_regions_host",
     "pseg_text_regions_poly", "pseg_text_regions_poly_host", "pseg_predict_chain_pages_regions_png", "pseg_predict_chain_scans_regions_png",
     "pseg_rescale_shape", "pseg_gaussian_kernel", "pseg_resize_nearest", "pseg_resize_nearest_device", "pseg_scale_image",
@@ -65,6 +66,16 @@ class BINARIZE(ctypes.Structure):
 class DESPECKLE(ctypes.Structure):
     """pseg_despeckle: how an ink map loses its specks (max_area 0: not at all; else components of at most max_area pixels)."""
     _fields_ = [("max_area", ctypes.c_int), ("connectivity", ctypes.c_int)]
+
+
+class SKEW(ctypes.Structure):
+    """pseg_skew: the candidates -steps .. steps of the skew estimate, a slope being index / denom."""
+    _fields_ = [("steps", ctypes.c_int), ("denom", ctypes.c_int)]
+
+
+class ROTATE(ctypes.Structure):
+    """pseg_rotate: a rotation by index / denom (order 0: nearest, 1: bilinear; fill: the byte outside the map)."""
+    _fields_ = [("index", ctypes.c_int), ("denom", ctypes.c_int), ("order", ctypes.c_int), ("fill", ctypes.c_int)]
 
 
 class REGIONS(ctypes.Structure):
@@ -238,6 +249,13 @@ def lib():
     L.pseg_despeckle_maps.argtypes = [i, i, vp, vp, vp, c.POINTER(DESPECKLE), vp, vp]
     L.pseg_despeckle_maps_host.argtypes = [i, vp, vp, vp, c.POINTER(DESPECKLE), vp, vp]
     L.pseg_despeckle_geometry.argtypes = [c.POINTER(i)] * 4
+    L.pseg_skew_maps.argtypes = [i, i, vp, vp, vp, c.POINTER(SKEW), vp, vp]
+    L.pseg_skew_maps_host.argtypes = [i, vp, vp, vp, c.POINTER(SKEW), vp, vp]
+    L.pseg_rotate_maps.argtypes = [i, i, vp, vp, vp, c.POINTER(ROTATE), vp]
+    L.pseg_rotate_maps_host.argtypes = [i, vp, vp, vp, c.POINTER(ROTATE), vp]
+    L.pseg_deskew_scans.argtypes = [i, i, vp, vp, vp, vp, c.POINTER(SKEW), vp, vp]
+    L.pseg_deskew_scans_host.argtypes = [i, vp, vp, vp, vp, c.POINTER(SKEW), vp, vp]
+    L.pseg_skew_geometry.argtypes = [c.POINTER(i)] * 3
     L.pseg_text_regions.argtypes = [i, i, vp, vp, vp, c.POINTER(REGIONS), vp, i, vp, vp]
     L.pseg_text_regions_host.argtypes = [i, vp, vp, vp, c.POINTER(REGIONS), vp, i, vp, vp]
     L.pseg_regions_geometry.argtypes = [c.POINTER(i)] * 6
@@ -1470,6 +1488,142 @@ def despeckle_maps(maps, how, device=0, counts=False, host=False):
             P(*[a.ctypes.data for a in outs]), cnt.ctypes.data if counts else None)
     _check(lib().pseg_despeckle_maps_host(*args) if host else lib().pseg_despeckle_maps(int(device), *args))
     return (outs, cnt) if counts else outs
+
+
+# ---- deskewing: the skew of ink maps from strip profiles, an exact rotation (pseg_skew_maps, pseg_rotate_maps) ----------------
+
+SKEW_DENOM_MIN, SKEW_DENOM_MAX, SKEW_STEPS_MAX = 64, 4096, 128
+
+
+def _skew_int(v, what, name):
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+        raise PsegError("%s: %s must be an integer, got %r" % (what, name, v))
+    return int(v)
+
+
+class Skew:
+    """How a page's skew is searched (include/pseg.h, pseg_skew): slopes index / denom for index = -steps .. steps, with
+    steps = floor(tan(radians(max_degrees)) * denom) clamped to 1 .. min(128, denom // 4).  denom: 64 .. 4096; max_degrees: a finite
+    angle above 0 and below 90.  One step of the default is 0.056 degrees."""
+
+    def __init__(self, max_degrees=5.0, denom=1024):
+        denom = _skew_int(denom, "Skew", "denom")
+        if not SKEW_DENOM_MIN <= denom <= SKEW_DENOM_MAX:
+            raise PsegError("Skew: denom must lie in %d..%d, got %r" % (SKEW_DENOM_MIN, SKEW_DENOM_MAX, denom))
+        if isinstance(max_degrees, bool) or not isinstance(max_degrees, (int, float, np.integer, np.floating)) \
+                or not np.isfinite(max_degrees) or not 0 < max_degrees < 90:
+            raise PsegError("Skew: max_degrees must be a finite angle above 0 and below 90, got %r" % (max_degrees,))
+        self.max_degrees, self.denom = float(max_degrees), denom
+        self.steps = int(min(max(np.floor(np.tan(np.radians(self.max_degrees)) * denom), 1), SKEW_STEPS_MAX, denom // 4))
+
+    def __repr__(self):
+        return "Skew(max_degrees=%r, denom=%r)" % (self.max_degrees, self.denom)
+
+    def __eq__(self, other):
+        return isinstance(other, Skew) and (self.steps, self.denom) == (other.steps, other.denom)
+
+    def __hash__(self):
+        return hash((self.steps, self.denom))
+
+
+def skew_degrees(index, denom):
+    """The angle of slope index / denom in degrees.  Host arithmetic."""
+    return float(np.degrees(np.arctan2(float(index), float(denom))))
+
+
+def skew_geometry():
+    """(strip, max_steps, max_side) of the skew contract (pseg_skew_geometry; no device)."""
+    v = [ctypes.c_int() for _ in range(3)]
+    _check(lib().pseg_skew_geometry(*[ctypes.byref(x) for x in v]))
+    return tuple(x.value for x in v)
+
+
+def _skew_table(how, n, what="map"):
+    entries = [how] * n if isinstance(how, Skew) else list(how) if isinstance(how, (list, tuple)) else None
+    if entries is None:
+        raise PsegError("a Skew or one per %s is expected, got %r" % (what, how))
+    if len(entries) != n:
+        raise PsegError("skew must have one entry per %s (%d for %d %ss)" % (what, len(entries), n, what))
+    table = (SKEW * max(n, 1))()
+    for k, s in enumerate(entries):
+        if not isinstance(s, Skew):
+            raise PsegError("%s %d: a Skew is expected, got %r" % (what, k, s))
+        table[k] = SKEW(s.steps, s.denom)
+    return table, entries
+
+
+def _skew_maps2d(maps, what="map"):
+    ms = [np.ascontiguousarray(m, dtype=np.uint8) for m in maps]
+    for k, m in enumerate(ms):
+        if m.ndim != 2:
+            raise PsegError("%s %d: an (H,W) map is expected, got shape %r" % (what, k, m.shape))
+    return ms
+
+
+def skew_maps(maps, how, device=0, scores=False, host=False):
+    """The skew indices (int32, slope index / how.denom) of a list of ink maps (uint8, non-zero = ink) in one device-resident call
+    (pseg_skew_maps); how is a Skew or one per map.  scores=True: -> (indices, [uint64 (2 steps + 1,) per map]).  host=True: the same
+    numbers from the host entry (pseg_skew_maps_host), no device."""
+    ms = _skew_maps2d(maps)
+    n = len(ms)
+    table, entries = _skew_table(how, n)
+    idx = np.zeros(n, np.int32)
+    sc = [np.zeros(2 * s.steps + 1, np.uint64) for s in entries] if scores else []
+    if n:
+        P, I = ctypes.c_void_p * n, ctypes.c_int * n
+        args = (n, P(*[m.ctypes.data for m in ms]), I(*[m.shape[0] for m in ms]), I(*[m.shape[1] for m in ms]), table,
+                idx.ctypes.data, P(*[a.ctypes.data for a in sc]) if scores else None)
+        _check(lib().pseg_skew_maps_host(*args) if host else lib().pseg_skew_maps(int(device), *args))
+    return (idx, sc) if scores else idx
+
+
+def rotate_maps(maps, indices, denom=1024, order=0, fill=0, device=0, host=False):
+    """A list of uint8 maps turned about their centres by the slopes indices[i] / denom (pseg_rotate_maps): rotating by the index
+    skew_maps gave makes the text lines horizontal, rotating by its negative maps a result back.  order 0 (nearest; label maps) or 1
+    (bilinear); fill: the byte outside the map.  indices: one integer for all maps or one per map.  host=True: the same bytes from
+    the host entry, no device."""
+    ms = _skew_maps2d(maps)
+    n = len(ms)
+    ind = [indices] * n if isinstance(indices, (int, np.integer)) and not isinstance(indices, bool) else list(indices)
+    if len(ind) != n:
+        raise PsegError("rotate_maps: one index per map (%d for %d maps)" % (len(ind), n))
+    denom, order, fill = _skew_int(denom, "rotate_maps", "denom"), _skew_int(order, "rotate_maps", "order"), _skew_int(fill, "rotate_maps", "fill")
+    table = (ROTATE * max(n, 1))()
+    for k, a in enumerate(ind):
+        table[k] = ROTATE(_skew_int(a, "map %d" % k, "index"), denom, order, fill)
+    outs = [np.empty(m.shape, np.uint8) for m in ms]
+    if n:
+        P, I = ctypes.c_void_p * n, ctypes.c_int * n
+        args = (n, P(*[m.ctypes.data for m in ms]), I(*[m.shape[0] for m in ms]), I(*[m.shape[1] for m in ms]), table,
+                P(*[a.ctypes.data for a in outs]))
+        _check(lib().pseg_rotate_maps_host(*args) if host else lib().pseg_rotate_maps(int(device), *args))
+    return outs
+
+
+def deskew_scans(scans, how, inks=None, device=0, host=False):
+    """A list of gray scans (uint8) deskewed in one device-resident call (pseg_deskew_scans): the skew is estimated on scan <= 127
+    -- or on inks[i] (non-zero = ink) where given; inks is None or has an ink map or None per scan --, and the scan is rotated by the
+    winner, order 1, fill 255, without a host wait in between.  -> (scans, int32 indices).  host=True: the same bytes from the host
+    entry, no device."""
+    gs = _skew_maps2d(scans, "scan")
+    n = len(gs)
+    table, _ = _skew_table(how, n, "scan")
+    ks = None
+    if inks is not None:
+        ks = [None if m is None else np.ascontiguousarray(m, dtype=np.uint8) for m in inks]
+        if len(ks) != n:
+            raise PsegError("deskew_scans: one ink map (or None) per scan (%d for %d scans)" % (len(ks), n))
+        for k, m in enumerate(ks):
+            if m is not None and m.shape != gs[k].shape:
+                raise PsegError("scan %d: the ink map's shape %r is not the scan's %r" % (k, m.shape, gs[k].shape))
+    idx = np.zeros(n, np.int32)
+    outs = [np.empty(g.shape, np.uint8) for g in gs]
+    if n:
+        P, I = ctypes.c_void_p * n, ctypes.c_int * n
+        args = (n, P(*[g.ctypes.data for g in gs]), None if ks is None else P(*[None if m is None else m.ctypes.data for m in ks]),
+                I(*[g.shape[0] for g in gs]), I(*[g.shape[1] for g in gs]), table, P(*[a.ctypes.data for a in outs]), idx.ctypes.data)
+        _check(lib().pseg_deskew_scans_host(*args) if host else lib().pseg_deskew_scans(int(device), *args))
+    return outs, idx
 
 
 # ---- text regions from label maps (pseg_text_regions) -----------------------------------------------------
