@@ -167,10 +167,34 @@ int pseg_engine_page_fits(pseg_engine* e, int H, int W);
  * before it returns; callers of pseg_predict_device / pseg_predict_pages_device call this where they synchronise. */
 int pseg_engine_status(pseg_engine* e, void* stream);
 
-/* Frees the activation tensors (all page slots) and the tile staging of the engine; the next predict call allocates what its page needs.  An
- * engine grows to the largest canvas x page-slot count it has seen (16 slots at 2048x1536: 14 GB) and keeps that; this is the
- * way back (tf.keras.backend.clear_session in lib/trainer.py:112 is the reference's).  Waits for the device. */
+/* Frees the activation memory (both address maps, all page slots) and the tile staging of the engine; the next predict call allocates what
+ * its page needs.  An engine grows to the largest canvas x page-slot count it has seen and keeps that; this is the way back
+ * (tf.keras.backend.clear_session in lib/trainer.py:112 is the reference's).  Waits for the device.
+ *
+ * A bf16 engine has two address maps.  The entries that return label maps alone (with or without the margin map: pseg_predict_device
+ * without logits and probs, _pages_device, _batch, the chain, tiled and label-exact entries) run on the COMPACT map: one arena per page
+ * slot in which a tensor takes the bytes of tensors whose last reader has run (pseg_plan_arena; fcn_skip at 2048x1536: 0.21 GB per slot,
+ * 16 slots 3.4 GB).  pseg_predict, and any call that asks for logits or probabilities, runs on the FULL map: one buffer per tensor
+ * (0.9 GB per slot), which is what pseg_get_activation reads.  The label maps are the same bits on either.  Plan switch
+ * PSEG_NO_COMPACT=1: the full map for everything. */
 int pseg_engine_trim(pseg_engine* e);
+
+/* The compact map's plan for an H x W page of a bf16 engine created with these plan `switches` (NULL: none) -- host arithmetic over
+ * the graph, no device.  One row per tensor that some kernel launch of a page writes or reads (a layer fused into a neighbour counts
+ * in the launch that runs it; "skip_logits" is fcn_skip's plane of conv2's logits contribution); tensors no launch touches have no row
+ * and no bytes.  A tensor's live range is [producer, last_reader], indices into the page's launch order (the names say which kernels);
+ * two rows whose live ranges intersect never overlap in bytes, and a tensor never takes bytes that a launch reads in the same launch
+ * that writes it.  Offsets are multiples of 256 inside one page slot; page slot p of a unit starts p * *arena_bytes further.
+ * shared = 0: the tensor's producer leaves stored bytes unwritten (the pad channels behind a stand-alone Conv2DTranspose k2 s2), so it
+ * keeps private bytes, zeroed when the canvas is laid out.  *full_bytes: one slot of the full map.  Returns the number of rows and
+ * fills rows[0 .. n) (NULL: count only; PSEG_EINVAL when max_rows is too small), or a negative PSEG_E*. */
+typedef struct pseg_arena_row {
+    char name[48], producer_name[32], last_reader_name[32];
+    int64_t bytes, offset;
+    int producer, last_reader, shared, reserved;
+} pseg_arena_row;
+int pseg_plan_arena(int arch, int n_classes, int in_channels, const char* switches, int H, int W, pseg_arena_row* rows, int max_rows,
+                    int64_t* arena_bytes, int64_t* full_bytes);
 
 /* Predictor.predict (lib/predictor.py:27-30): label maps of a list of pages of individual sizes.
  * The upload of page i+1 and the download of page i-1 overlap the compute of page i (two staging
@@ -243,7 +267,9 @@ int pseg_host_unregister(void* p);
 
 /* Copy an intermediate activation to the host as float32 NHWC (true channel count) --
  * layer-by-layer parity tests.  `layer` is the Keras layer name.  dims[3] = {H,W,C} of the
- * padded canvas at that layer.  Valid after a predict call.  PSEG_EUNSUPPORTED for a tensor the bf16 plan
+ * padded canvas at that layer.  Answers from the last run on the full address map (pseg_engine_trim's note): the last pseg_predict,
+ * or the last call that asked for logits or probabilities.  PSEG_EINVAL while there has been none -- the labels-only entries do
+ * not materialise activations, whatever ran through them leaves this call's answer as it was.  PSEG_EUNSUPPORTED for a tensor the bf16 plan
  * never writes as such: one that lives inside a fused kernel, one stored after its readers' ReLU, and
  * "input" where the first layer reads the uint8 page itself (one-channel fcn graphs). */
 int pseg_get_activation(pseg_engine* e, const char* layer, float* out, int64_t cap, int dims[3]);

@@ -213,9 +213,11 @@ struct Tensor {
     int C = 0;          // true channel count
     int Cs = 0;         // storage channels: C (f32 mode) or round_up(C, 8) (bf16 mode)
     void* d = nullptr;  // device buffer, NHWC, (Hp>>s) x (Wp>>s) x Cs -- of the page slot in use (Engine::pages slots; slot 0 = base)
-    void* base = nullptr;       // the allocation: `pages` slots of page_bytes each (bf16 page batches), d == base outside a per-page run
+    void* base = nullptr;       // slot 0 in the address map in use (install_map): `pages` slots of page_bytes each (bf16 page batches), d == base
+                                // outside a per-page run.  Full map: == own; compact map: inside Engine::arena, or its start for a tensor no launch touches
     size_t page_bytes = 0;      // bytes of one page slot at the current canvas
-    size_t bytes = 0;           // bytes allocated
+    void* own = nullptr;        // full map: this tensor's own allocation
+    size_t bytes = 0;           // ... and its size
     bool fused = false; // bf16 mode: never written to HBM (lives only inside a fused kernel)
     bool relu_stored = false;   // bf16 mode: stored after the pre-activation ReLU of its readers (mfma_plan_graph)
 };
@@ -271,7 +273,6 @@ struct Engine;
 // host-side packing + upload; w = correlation-form f32 weights as uploaded for the exact path
 int mfma_pack_op(Engine& e, Op& op, const std::vector<float>& w, const std::vector<float>& bias);
 void mfma_free_op(Op& op);
-void mfma_trim_op(Op& op);                                   // frees the plan's canvas-sized buffers (pseg_engine_trim)
 int mfma_plan_graph(Engine& e);                              // pool fusion etc., once per engine
 int mfma_launch_conv(Engine& e, Op& op, hipStream_t st);     // OP_CONV
 int mfma_launch_deconv2(Engine& e, Op& op, hipStream_t st);  // OP_DECONV2
@@ -289,6 +290,32 @@ struct TimingSlot {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
 };
 
+// ---- the two address maps of a bf16 engine -------------------------------------------------------------------------
+// FULL: one allocation per tensor (Tensor::own) and one for the skip-logits plane -- what pseg_get_activation reads; the only map of a
+// float32 engine.  COMPACT: one arena; a tensor's bytes are reused by tensors that are produced after its last reader (plan_arena).
+// One row of the compact plan: a tensor some launch writes or reads (tensor = index, -1: the skip-logits plane).
+struct ArenaRow {
+    std::string name;
+    int tensor = -1;
+    size_t bytes = 0, offset = 0;        // inside one page slot of the arena
+    int producer = 0, last_reader = 0;   // indices into ArenaPlan::launches: the live range, both ends included
+    bool shared = false;                 // false: private, once-zeroed bytes behind the shared part (its producer leaves stored bytes unwritten)
+};
+struct ArenaPlan {
+    std::vector<std::string> launches;   // the kernels of one page in launch order ("preprocess" first where the input tensor is staged)
+    std::vector<ArenaRow> rows;          // in the order they were placed (producer launch, larger first)
+    size_t shared_bytes = 0;             // [0, shared_bytes): the part tensors share (what PSEG_COMPACT_POISON fills)
+    size_t total_bytes = 0;              // one slot of the arena
+    size_t full_bytes = 0;               // one slot of the full map (every tensor + the skip-logits plane)
+    size_t untouched_max = 0;            // the largest tensor no launch touches (it is handed the arena's start)
+};
+struct Engine;
+// Host arithmetic over the graph as mfma_plan_graph left it (no HIP call): pseg_graph.cpp.  bf16 engines only.
+int plan_arena(const Engine& e, int Hp, int Wp, ArenaPlan& out);
+bool mfma_reads_page(const Engine& e, const Op& op);   // a first layer that takes the uint8 page itself (pseg_mfma.hip: is_conv1_special)
+enum { MAP_FULL = 0, MAP_COMPACT = 1 };
+struct CanvasMap { int Hp = 0, Wp = 0, pages = 0; };   // the canvas and page slots a map's buffers are laid out for (Hp = 0: none)
+
 struct Engine {
     std::shared_ptr<const KnobSnap> knobs;   // the PSEG_* snapshot this engine was created under (see PSEG_KNOB)
     int arch = 0, n_classes = 0, in_ch = 1, device = 0, mode = 0;
@@ -302,6 +329,18 @@ struct Engine {
     // canvas
     int H = 0, W = 0, Hp = 0, Wp = 0;
     int pages = 1;                 // page slots every activation tensor has room for (bf16 page batches: pseg_predict_batch)
+    // Hp, Wp, pages and every Tensor::base / page_bytes describe the map in use; set_canvas lays a map out and installs it
+    CanvasMap maps[2];             // MAP_FULL, MAP_COMPACT
+    int map_in_use = MAP_FULL;
+    bool host_parity = false;      // while pseg_predict runs: the full map, whatever is asked for (pseg_get_activation is documented against it)
+    int act_H = 0, act_W = 0;      // the page of the last run on the full map (0: none so far) -- what pseg_get_activation answers from
+    void* arena = nullptr;         // compact map: `pages` slots of arena_plan.total_bytes, slot p at arena + p * total_bytes, a tensor at ArenaRow::offset inside its slot
+    size_t arena_bytes = 0;        // bytes allocated
+    ArenaPlan arena_plan;          // ... laid out by this plan (maps[MAP_COMPACT]'s canvas)
+    void* skip_own = nullptr;      // full map: the skip-logits plane's own allocation (fcn_skip: conv2's logits contribution, f32 [canvas pixel][4 or 8])
+    size_t skip_own_bytes = 0;
+    void* skip_base = nullptr;     // the plane in the map in use: slot 0, skip_bytes long (0: the graph has none), the next slot's skip_stride further
+    size_t skip_bytes = 0, skip_stride = 0;
     int page = 0;                  // page slot the per-page launches of a batch run are working on
     int batch_pages = 0;           // > 1 while a launch covers that many page slots at once (a tile index carries the page)
     bool weights_dirty = true;
@@ -516,13 +555,15 @@ int create_engine(int arch, int n_classes, int in_channels, int device, int mode
 void exact_free(Engine& e);
 void chain_free(Engine& e);
 void dist_free(Engine& e);                      // RCCL communicator (pseg_dist.hip)                     // Predictor chain buffers (pseg_chain.hip)                     // label-exact mode state (pseg_exactlabels.hip)
-int set_canvas(Engine& e, int H, int W, hipStream_t st, int pages = 1);
+int set_canvas(Engine& e, int H, int W, hipStream_t st, int pages = 1, bool labels_only = false);   // labels_only: the call returns label maps (and margins) alone -- the compact map, unless PSEG_NO_COMPACT or pseg_predict
 // What set_canvas refuses and what a page slot costs, host arithmetic over the graph's tensors (shared with fit_page_slots and the
 // AUTO tiling mode).  canvas_refused: a bf16 engine whose largest tensor at this canvas would reach 4 GiB; canvas_slot_bytes: the
 // activation tensors of one page slot; page_slot_fits: one whole-page slot leaves a fifth of the device's free memory untouched
 // (what the engine already holds counts as free).
 bool canvas_refused(const Engine& e, int Hp, int Wp);
 size_t canvas_slot_bytes(const Engine& e, int Hp, int Wp);
+size_t skip_plane_bytes(const Engine& e, int Hp, int Wp);          // one slot of the skip-logits plane, 0 where the graph has none
+bool compact_wanted(const Engine& e);                               // a bf16 engine without PSEG_NO_COMPACT
 bool page_slot_fits(Engine& e, int H, int W);
 // pseg_tiles.hip: one page's label map(s) from same-shape tiles through the page-slot path, asynchronous on `st`; and the network
 // stage of the label-only entries: tiled where the engine's tiling mode asks for it, else predict_device

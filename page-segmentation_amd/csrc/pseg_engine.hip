@@ -532,54 +532,33 @@ size_t canvas_slot_bytes(const Engine& e, int Hp, int Wp) {
     return b;
 }
 
-int set_canvas(Engine& e, int H, int W, hipStream_t st, int pages) {
-    if (H <= 0 || W <= 0) return fail(PSEG_EINVAL, "empty page %dx%d", H, W);
-    const int Hp = round_up(H, 32), Wp = round_up(W, 32);
-    e.H = H;
-    e.W = W;
-    if (Hp == e.Hp && Wp == e.Wp && pages <= e.pages) return PSEG_OK;
-    pages = std::max(pages, Hp == e.Hp && Wp == e.Wp ? e.pages : 1);
-    // A canvas change re-allocates and clears the activation tensors.  Work of earlier calls may still be in
-    // flight on the engine's (non-blocking) stream or on a caller's stream: drain the device first, and clear on
-    // the stream the coming kernels run on -- a hipMemset on the null stream is NOT ordered with non-blocking
-    // streams (that race corrupted the first predict after shrinking from a 4096x3072 canvas).
+bool compact_wanted(const Engine& e) { return e.mode == PSEG_MODE_BF16 && !PSEG_KNOB("PSEG_NO_COMPACT"); }
+
+// A run installs its map: every tensor's slot-0 address and slot stride, the skip-logits plane, the canvas -- as run_bf16_pages'
+// slot() installs a page slot.  The launchers read nothing else.
+static void install_map(Engine& e, int m) {
+    const CanvasMap& c = e.maps[m];
     const size_t esz = e.mode == PSEG_MODE_BF16 ? 2 : 4;
-    if (canvas_refused(e, Hp, Wp))
-        return fail(PSEG_EUNSUPPORTED, "page %dx%d: a tensor of this graph would reach 4 GiB (32-bit buffer addressing in the bf16 kernels); "
-                                       "predict its label map in tiles (pseg_predict_tiled_device, or pseg_engine_set_tiling for pseg_predict, "
-                                       "pseg_predict_device and pseg_predict_chain) or use the float32 mode", H, W);
-    PSEG_HIP(hipDeviceSynchronize());
-    // The new canvas is committed only when every tensor has its buffer: a failed allocation leaves the engine with NO canvas
-    // (Hp = Wp = 0, one slot, every pointer null or valid for its recorded size), so the next call allocates again instead of
-    // returning early on the "same shape" test and running kernels on freed or undersized buffers.
-    e.Hp = e.Wp = 0;
-    e.pages = 1;
-    for (auto& t : e.tensors) {
-        const size_t pb = (size_t)(Hp >> t.s) * (Wp >> t.s) * t.Cs * esz;
-        const size_t bytes = pb * pages;
-        if (bytes > t.bytes) {
-            free_dev(t.base);
-            t.d = nullptr;
-            t.bytes = 0;
-            const hipError_t er = hipMalloc(&t.base, bytes);
-            if (er != hipSuccess) {
-                (void)hipGetLastError();
-                t.base = nullptr;
-                return fail(er == hipErrorOutOfMemory ? PSEG_ENOMEM : PSEG_EHIP, "canvas %dx%d x %d page slot(s): hipMalloc of %zu bytes for tensor '%s' failed: %s",
-                            Hp, Wp, pages, bytes, t.name.c_str(), hipGetErrorString(er));
-            }
-            t.bytes = bytes;
+    e.map_in_use = m;
+    e.Hp = c.Hp;
+    e.Wp = c.Wp;
+    e.pages = std::max(c.pages, 1);
+    if (m == MAP_COMPACT) {
+        const size_t slot = e.arena_plan.total_bytes;
+        for (auto& t : e.tensors) { t.base = t.d = e.arena; t.page_bytes = slot; }     // (a tensor no launch touches: plan_arena)
+        e.skip_base = nullptr;
+        e.skip_bytes = e.skip_stride = 0;
+        for (auto& r : e.arena_plan.rows) {
+            void* at = e.arena ? (char*)e.arena + r.offset : nullptr;
+            if (r.tensor >= 0) e.tensors[r.tensor].base = e.tensors[r.tensor].d = at;
+            else { e.skip_base = at; e.skip_bytes = r.bytes; e.skip_stride = slot; }
         }
-        t.page_bytes = pb;
-        t.d = t.base;
-        // float32 mode: fresh buffers start at zero; bf16 mode: the pad channels no kernel writes must read as
-        // zero after every layout change
-        if (t.d && bytes) PSEG_HIP(hipMemsetAsync(t.d, 0, bytes, st));
+    } else {
+        for (auto& t : e.tensors) { t.base = t.d = t.own; t.page_bytes = (size_t)(c.Hp >> t.s) * (c.Wp >> t.s) * t.Cs * esz; }
+        e.skip_base = e.skip_own;
+        e.skip_bytes = e.skip_stride = e.mode == PSEG_MODE_BF16 ? skip_plane_bytes(e, c.Hp, c.Wp) : 0;
     }
-    e.Hp = Hp;
-    e.Wp = Wp;
-    e.pages = pages;
-    const double px = (double)Hp * Wp;
+    const double px = (double)c.Hp * c.Wp;
     for (auto& op : e.ops) e.slots[op.timing_slot].flops = op.flops_per_canvas_px * px;
     // a launch that also runs a fused-away layer (conv1 inside conv2, logits inside the tail) does that layer's work too
     for (auto& op : e.ops) {
@@ -587,6 +566,108 @@ int set_canvas(Engine& e, int H, int W, hipStream_t st, int pages) {
         if (op.tail_logits >= 0) e.slots[op.timing_slot].flops += e.ops[op.tail_logits].flops_per_canvas_px * px;
         if (op.into_tail >= 0) e.slots[e.ops[op.into_tail].timing_slot].flops += op.flops_per_canvas_px * px;
     }
+}
+
+// grow-only device block, zeroed on `st`: PSEG_ENOMEM / PSEG_EHIP with the canvas in the message
+static int canvas_block(void** p, size_t* have, size_t bytes, const char* what, int Hp, int Wp, int pages, hipStream_t st) {
+    if (bytes > *have) {
+        free_dev(*p);
+        *have = 0;
+        const hipError_t er = hipMalloc(p, bytes);
+        if (er != hipSuccess) {
+            (void)hipGetLastError();
+            *p = nullptr;
+            return fail(er == hipErrorOutOfMemory ? PSEG_ENOMEM : PSEG_EHIP, "canvas %dx%d x %d page slot(s): hipMalloc of %zu bytes for %s failed: %s",
+                        Hp, Wp, pages, bytes, what, hipGetErrorString(er));
+        }
+        *have = bytes;
+    }
+    // float32 mode: fresh buffers start at zero; bf16 mode: the bytes a kernel leaves alone (the pad channels behind a stand-alone
+    // Conv2DTranspose k2 s2) must read as zero after every layout change
+    if (*p && bytes) PSEG_HIP(hipMemsetAsync(*p, 0, bytes, st));
+    return PSEG_OK;
+}
+
+static void log_arena_plan(const ArenaPlan& P, int Hp, int Wp) {
+    fprintf(stderr, "[pseg] arena plan %dx%d: %zu tensors, arena %zu bytes (shared part %zu), full map %zu bytes\n", Hp, Wp, P.rows.size(), P.total_bytes,
+            P.shared_bytes, P.full_bytes);
+    for (auto& r : P.rows)
+        fprintf(stderr, "[pseg]   %-28s %11zu bytes at %11zu  written by %2d %-22s last read by %2d %-22s %s\n", r.name.c_str(), r.bytes, r.offset, r.producer,
+                P.launches[r.producer].c_str(), r.last_reader, P.launches[r.last_reader].c_str(), r.shared ? "shared" : "private (its producer leaves stored bytes unwritten)");
+}
+
+// both address maps, every page slot: the engine is left without a canvas
+static void free_canvas(Engine& e) {
+    for (auto& t : e.tensors) { free_dev(t.own); t.base = t.d = nullptr; t.bytes = 0; t.page_bytes = 0; }
+    free_dev(e.skip_own);
+    e.skip_own_bytes = 0;
+    free_dev(e.arena);
+    e.arena_bytes = 0;
+    e.arena_plan = ArenaPlan();
+    e.skip_base = nullptr;
+    e.skip_bytes = e.skip_stride = 0;
+    e.maps[MAP_FULL] = e.maps[MAP_COMPACT] = CanvasMap();
+    e.map_in_use = MAP_FULL;
+    e.act_H = e.act_W = 0;
+    e.Hp = e.Wp = 0;
+    e.pages = 1;
+}
+
+// labels_only: the call hands back label maps (and margins) alone.  Such a call runs on the compact map -- nobody can ask for its
+// activations -- unless it is pseg_predict (host_parity) or the engine was created with PSEG_NO_COMPACT; everything else, and the
+// float32 engine, runs on the full map.  Each map keeps its own canvas; both grow only.
+int set_canvas(Engine& e, int H, int W, hipStream_t st, int pages, bool labels_only) {
+    if (H <= 0 || W <= 0) return fail(PSEG_EINVAL, "empty page %dx%d", H, W);
+    const int Hp = round_up(H, 32), Wp = round_up(W, 32);
+    e.H = H;
+    e.W = W;
+    const int m = labels_only && !e.host_parity && compact_wanted(e) ? MAP_COMPACT : MAP_FULL;
+    CanvasMap& c = e.maps[m];
+    if (Hp == c.Hp && Wp == c.Wp && pages <= c.pages) {
+        if (e.map_in_use != m || e.Hp != Hp || e.Wp != Wp) install_map(e, m);
+        if (m == MAP_FULL) { e.act_H = H; e.act_W = W; }
+        return PSEG_OK;
+    }
+    pages = std::max(pages, Hp == c.Hp && Wp == c.Wp ? c.pages : 1);
+    // A canvas change re-allocates and clears the activation tensors.  Work of earlier calls may still be in
+    // flight on the engine's (non-blocking) stream or on a caller's stream: drain the device first, and clear on
+    // the stream the coming kernels run on -- a hipMemset on the null stream is NOT ordered with non-blocking
+    // streams (that race corrupted the first predict after shrinking from a 4096x3072 canvas).
+    if (canvas_refused(e, Hp, Wp))
+        return fail(PSEG_EUNSUPPORTED, "page %dx%d: a tensor of this graph would reach 4 GiB (32-bit buffer addressing in the bf16 kernels); "
+                                       "predict its label map in tiles (pseg_predict_tiled_device, or pseg_engine_set_tiling for pseg_predict, "
+                                       "pseg_predict_device and pseg_predict_chain) or use the float32 mode", H, W);
+    PSEG_HIP(hipDeviceSynchronize());
+    // The new canvas is committed only when every buffer of the map is there: a failed allocation leaves the engine with NO canvas
+    // installed and none recorded for this map (Hp = Wp = 0, every pointer null or valid for its recorded size), so the next call
+    // allocates again instead of returning early on the "same shape" test and running kernels on freed or undersized buffers.
+    c = CanvasMap();
+    e.Hp = e.Wp = 0;
+    e.pages = 1;
+    // ... and frees both maps: the caller that retries with fewer page slots (PSEG_ENOMEM) finds all of the engine's memory free
+    const int rc = [&]() -> int {
+        if (m == MAP_COMPACT) {
+            ArenaPlan plan;
+            PSEG_TRY(plan_arena(e, Hp, Wp, plan));
+            if (PSEG_KNOB("PSEG_LOG_GENERIC")) log_arena_plan(plan, Hp, Wp);
+            // (private tensors are zeroed here, once; the shared part needs no clearing -- every tensor in it is written whole before it is read)
+            PSEG_TRY(canvas_block(&e.arena, &e.arena_bytes, plan.total_bytes * pages, "the activation arena", Hp, Wp, pages, st));
+            e.arena_plan = std::move(plan);
+        } else {
+            const size_t esz = e.mode == PSEG_MODE_BF16 ? 2 : 4;
+            for (auto& t : e.tensors)
+                PSEG_TRY(canvas_block(&t.own, &t.bytes, (size_t)(Hp >> t.s) * (Wp >> t.s) * t.Cs * esz * pages, ("tensor '" + t.name + "'").c_str(), Hp, Wp, pages, st));
+            if (e.mode == PSEG_MODE_BF16)
+                PSEG_TRY(canvas_block(&e.skip_own, &e.skip_own_bytes, skip_plane_bytes(e, Hp, Wp) * pages, "the skip-logits plane", Hp, Wp, pages, st));
+        }
+        return PSEG_OK;
+    }();
+    if (rc != PSEG_OK) { free_canvas(e); return rc; }
+    c.Hp = Hp;
+    c.Wp = Wp;
+    c.pages = pages;
+    install_map(e, m);
+    if (m == MAP_FULL) { e.act_H = H; e.act_W = W; }
     return PSEG_OK;
 }
 
@@ -623,12 +704,20 @@ int engine_status(Engine& e, hipStream_t st) {
                 layer, r[0], r[1], r[6], r[2], r[3], r[4], r[5]);
 }
 
-// *per_slot: the bytes of one slot of this canvas (skip logits: 16 B/px per slot); *room: four fifths of free + held.  false: no answer from the device.
+// *per_slot: the bytes of one slot of this canvas in the map the label-only entries use (page units and the AUTO tiling mode ask): the
+// arena, or every tensor and the skip-logits plane; *room: four fifths of free + what that map holds.  false: no answer from the device.
 static bool page_slot_room(Engine& e, int H, int W, double* per_slot, double* room) {
     const int Hp = round_up(H, 32), Wp = round_up(W, 32);
     size_t held = 0;
-    for (auto& t : e.tensors) held += t.bytes;
-    *per_slot = (double)((size_t)Hp * Wp * 16 + canvas_slot_bytes(e, Hp, Wp));
+    ArenaPlan plan;
+    if (compact_wanted(e) && plan_arena(e, Hp, Wp, plan) == PSEG_OK) {
+        held = e.arena_bytes;
+        *per_slot = (double)plan.total_bytes;
+    } else {
+        for (auto& t : e.tensors) held += t.bytes;
+        held += e.skip_own_bytes;
+        *per_slot = (double)(skip_plane_bytes(e, Hp, Wp) + canvas_slot_bytes(e, Hp, Wp));
+    }
     size_t fr = 0, tot = 0;
     if (hipMemGetInfo(&fr, &tot) != hipSuccess) { (void)hipGetLastError(); return false; }
     *room = 0.8 * ((double)fr + (double)held);
@@ -861,8 +950,17 @@ static int bf16_launch_op(Engine& e, Op& op, float* d_logits, float* d_probs, in
     return time_end(e, op, st, ev0);
 }
 
+// PSEG_COMPACT_POISON (plan switch, tests): the shared part of a slot's arena is filled with 0xFF bytes -- bf16 NaNs -- in front of every
+// run on the compact map.  A tensor wrongly planned as "written whole by its producer" then turns the label map into garbage.
+static int poison_slot(Engine& e, int p, hipStream_t st) {
+    if (e.map_in_use != MAP_COMPACT || !e.arena || !PSEG_KNOB("PSEG_COMPACT_POISON") || !e.arena_plan.shared_bytes) return PSEG_OK;
+    PSEG_HIP(hipMemsetAsync((char*)e.arena + (size_t)p * e.arena_plan.total_bytes, 0xFF, e.arena_plan.shared_bytes, st));
+    return PSEG_OK;
+}
+
 static int run_bf16(Engine& e, const uint8_t* d_img, float* d_logits, float* d_probs,
                     int64_t* d_labels, uint8_t* d_labels_u8, float* d_margin, hipStream_t st) {
+    PSEG_TRY(poison_slot(e, 0, st));
     PSEG_TRY(mfma_preprocess(e, d_img, st));
     e.cur_margin = d_margin;
     e.margin_done = false;
@@ -894,8 +992,9 @@ static int run_bf16_pages(Engine& e, const uint8_t* d_imgs, int n, int64_t* d_la
     e.margin_done = false;
     e.cur_logits = nullptr;
     e.cur_probs = nullptr;
+    for (int p = 0; p < n; ++p) PSEG_TRY(poison_slot(e, p, st));
     auto slot = [&](int p) {
-        for (auto& t : e.tensors) t.d = t.base ? (char*)t.base + (size_t)p * t.page_bytes : nullptr;
+        for (auto& t : e.tensors) t.d = t.base ? (char*)t.base + (size_t)p * t.page_bytes : nullptr;   // (compact map: the tensor's place in slot p of the arena)
         e.page = p;
         e.cur_labels = d_labels ? d_labels + (size_t)p * npx : nullptr;
         e.cur_labels_u8 = d_labels_u8 ? d_labels_u8 + (size_t)p * npx : nullptr;
@@ -938,17 +1037,17 @@ static int run_bf16_pages(Engine& e, const uint8_t* d_imgs, int n, int64_t* d_la
 }
 
 // what every device entry does first: the engine's device current, every weight set and uploaded, the canvas (and page slots) of this call
-static int engine_ready(Engine& e, int H, int W, hipStream_t st, int pages) {
+static int engine_ready(Engine& e, int H, int W, hipStream_t st, int pages, bool labels_only) {
     PSEG_HIP(hipSetDevice(e.device));
     for (auto& p : e.params)
         if (!p.set) return fail(PSEG_EINVAL, "weight '%s' was never set", p.name.c_str());
     if (e.weights_dirty) PSEG_TRY(upload_weights(e));
-    return set_canvas(e, H, W, st, pages);
+    return set_canvas(e, H, W, st, pages, labels_only);
 }
 
 // pseg_predict_batch's device leg for a group of same-shape pages
 int predict_device_pages(Engine& e, const uint8_t* d_imgs, int n, int H, int W, int64_t* d_labels, uint8_t* d_labels_u8, hipStream_t st) {
-    PSEG_TRY(engine_ready(e, H, W, st, n));
+    PSEG_TRY(engine_ready(e, H, W, st, n, true));     // (label maps alone)
     return run_bf16_pages(e, d_imgs, n, d_labels, d_labels_u8, st);
 }
 
@@ -966,7 +1065,7 @@ bool pages_capable(Engine& e) {
 int predict_device(Engine& e, const uint8_t* d_img, int H, int W, float* d_logits,
                    float* d_probs, int64_t* d_labels, uint8_t* d_labels_u8,
                    hipStream_t st, float* d_margin) {
-    PSEG_TRY(engine_ready(e, H, W, st, 1));
+    PSEG_TRY(engine_ready(e, H, W, st, 1, !d_logits && !d_probs));
     if (e.mode == PSEG_MODE_BF16)
         return run_bf16(e, d_img, d_logits, d_probs, d_labels, d_labels_u8, d_margin, st);
     if (d_margin) PSEG_TRY(logits_or_tmp(e, d_logits, e.n_classes, &d_logits));
@@ -1044,7 +1143,7 @@ int batch_copy_streams(Engine& e, hipStream_t* s_in, hipStream_t* s_out) {
     return PSEG_OK;
 }
 
-// pages per unit of a list (PSEG_BATCH_PAGES caps a unit; default 8: 7 GB of activations at 2048x1536; 1 = page by page)
+// pages per unit of a list (PSEG_BATCH_PAGES caps a unit; default 8: 1.7 GB of activations at 2048x1536 on the compact map; 1 = page by page)
 static int unit_cap_of(Engine& e, int n, const int* H, const int* W) {
     int cap = 8;
     if (const char* ev = PSEG_KNOB("PSEG_BATCH_PAGES")) cap = std::max(1, std::min(64, atoi(ev)));
@@ -1169,7 +1268,7 @@ static int predict_batch(Engine& e, int n, const uint8_t* const* imgs, const int
         run.in_pinned[i] = host_is_pinned(imgs[i]);
         run.out_pinned[i] = (!labels || host_is_pinned(labels[i])) && (!labels_u8 || host_is_pinned(labels_u8[i]));
     }
-    // Unit sizes.  PSEG_BATCH_PAGES caps a unit (default 8: 7 GB of activations at 2048x1536; 1 = page by page).  The upload of the
+    // Unit sizes.  PSEG_BATCH_PAGES caps a unit (default 8: 1.7 GB of activations at 2048x1536 on the compact map; 1 = page by page).  The upload of the
     // FIRST unit and the download of the LAST one have no compute beside them: a list cut into equal units of 8 pages waits 8 page
     // uploads at its head and 8 downloads at its tail (32 pages: 2 of 14 ms).  So a run of same-shape pages that opens the list
     // starts with units of 1, 2, 4, ... pages, one that closes it ends ... 4, 2, 1 (every unit's copies still fit under its
@@ -1275,7 +1374,7 @@ int pseg_destroy(pseg_engine* h) {
     exact_free(e);
     chain_free(e);
     batch_free(e);
-    for (auto& t : e.tensors) { free_dev(t.base); t.d = nullptr; }
+    free_canvas(e);
     for (auto& op : e.ops) {
         free_dev((void*&)op.d_w);
         free_dev((void*&)op.d_b);
@@ -1364,7 +1463,7 @@ int pseg_predict_pages_device(pseg_engine* h, const uint8_t* d_imgs, int n, int 
     if (e.weights_dirty) PSEG_TRY(upload_weights(e));
     const size_t npx = (size_t)H * W;
     if (n > 1 && pages_capable(e)) {
-        int cap = 16;                         // page slots per unit of a device-resident batch (14 GB of activations at 2048x1536; 8 and 16 measure alike)
+        int cap = 16;                         // page slots per unit of a device-resident batch (3.4 GB of activations at 2048x1536 on the compact map; 8 and 16 measure alike)
         if (const char* ev = PSEG_KNOB("PSEG_BATCH_PAGES")) cap = std::max(1, std::min(64, atoi(ev)));
         cap = fit_page_slots(e, H, W, std::min(cap, n));
         for (int i = 0; i < n;) {
@@ -1392,6 +1491,9 @@ int pseg_predict(pseg_engine* h, const uint8_t* img, int H, int W, float* logits
     if (H <= 0 || W <= 0) return fail(PSEG_EINVAL, "empty page %dx%d", H, W);
     Engine& e = h->e;
     PSEG_HIP(hipSetDevice(e.device));
+    // the host parity entry: its run is the one pseg_get_activation answers from, so it stays on the full address map
+    struct Parity { Engine& e; ~Parity() { e.host_parity = false; } } parity{e};
+    e.host_parity = true;
     const size_t npx = (size_t)H * W, C = e.n_classes;
     PSEG_TRY(e.img_stage.ensure(npx * e.in_ch, "page"));
     if (labels) PSEG_TRY(e.lab_stage.ensure(npx * 8, "labels"));
@@ -1421,10 +1523,7 @@ int pseg_engine_trim(pseg_engine* h) {
     Engine& e = h->e;
     PSEG_HIP(hipSetDevice(e.device));
     PSEG_HIP(hipDeviceSynchronize());
-    for (auto& t : e.tensors) { free_dev(t.base); t.d = nullptr; t.bytes = 0; t.page_bytes = 0; }
-    for (auto& op : e.ops) mfma_trim_op(op);                 // (the skip-logits planes grow with canvas x slots too)
-    e.Hp = e.Wp = 0;
-    e.pages = 1;
+    free_canvas(e);
     e.logits_tmp.release();
     e.tile_img.release();
     e.tile_lab.release();
@@ -1450,6 +1549,42 @@ int pseg_batch_units(int n_pages, const int* H, const int* W, int cap, int* unit
         if (unit_count) unit_count[u] = ug[u];
     }
     return (int)ub.size();
+}
+
+int pseg_plan_arena(int arch, int n_classes, int in_channels, const char* switches, int H, int W, pseg_arena_row* rows, int max_rows,
+                    int64_t* arena_bytes, int64_t* full_bytes) {
+    if (H <= 0 || W <= 0) return fail(PSEG_EINVAL, "empty page %dx%d", H, W);
+    if (n_classes < 1 || n_classes > 256 || (in_channels != 1 && in_channels != 3)) return fail(PSEG_EINVAL, "n_classes %d / in_channels %d out of range", n_classes, in_channels);
+    // the graph and its fusions as pseg_create_plan builds them for a bf16 engine -- host code, no device
+    Engine e;
+    e.knobs = knobs_snapshot(switches);
+    KnobScope ks(e);
+    e.arch = arch;
+    e.n_classes = n_classes;
+    e.in_ch = in_channels;
+    e.mode = PSEG_MODE_BF16;
+    PSEG_TRY(build_graph(e));
+    PSEG_TRY(mfma_plan_graph(e));
+    ArenaPlan P;
+    PSEG_TRY(plan_arena(e, round_up(H, 32), round_up(W, 32), P));
+    if (PSEG_KNOB("PSEG_LOG_GENERIC")) log_arena_plan(P, round_up(H, 32), round_up(W, 32));
+    if (rows && (int)P.rows.size() > max_rows) return fail(PSEG_EINVAL, "%zu tensors, room for %d", P.rows.size(), max_rows);
+    for (size_t i = 0; rows && i < P.rows.size(); ++i) {
+        const ArenaRow& r = P.rows[i];
+        pseg_arena_row& o = rows[i];
+        memset(&o, 0, sizeof o);
+        strncpy(o.name, r.name.c_str(), sizeof o.name - 1);
+        strncpy(o.producer_name, P.launches[r.producer].c_str(), sizeof o.producer_name - 1);
+        strncpy(o.last_reader_name, P.launches[r.last_reader].c_str(), sizeof o.last_reader_name - 1);
+        o.bytes = (int64_t)r.bytes;
+        o.offset = (int64_t)r.offset;
+        o.producer = r.producer;
+        o.last_reader = r.last_reader;
+        o.shared = r.shared ? 1 : 0;
+    }
+    if (arena_bytes) *arena_bytes = (int64_t)P.total_bytes;
+    if (full_bytes) *full_bytes = (int64_t)P.full_bytes;
+    return (int)P.rows.size();
 }
 
 int pseg_host_alloc(void** p, size_t bytes) {
@@ -1493,22 +1628,26 @@ int pseg_get_activation(pseg_engine* h, const char* layer, float* out, int64_t c
     PSEG_HIP(hipSetDevice(e.device));
     for (auto& t : e.tensors) {
         if (t.name != layer) continue;
-        if (!t.d || e.Hp == 0) return fail(PSEG_EINVAL, "no predict call has run yet");
+        // the last run on the FULL address map: pseg_predict, or a call that asked for logits or probabilities
+        const CanvasMap& fm = e.maps[MAP_FULL];
+        if (!t.own || fm.Hp == 0 || e.act_H == 0)
+            return fail(PSEG_EINVAL, "no predict call has run yet that keeps its activations: pseg_get_activation answers from the last pseg_predict (or a call that "
+                                     "asked for logits or probabilities); the labels-only entries do not materialise activations");
         if (t.fused) return fail(PSEG_EUNSUPPORTED, "layer '%s' is fused into its consumer and never materialised", layer);
         if (e.mode == PSEG_MODE_BF16 && &t == &e.tensors[e.input_tensor] && !mfma_input_is_staged(e))
             return fail(PSEG_EUNSUPPORTED, "layer '%s' is fused into its consumer and never materialised: the first layer reads the uint8 page", layer);
         if (t.relu_stored) return fail(PSEG_EUNSUPPORTED, "layer '%s' is fused with its readers' pre-activation ReLU: stored as max(x, 0) (PSEG_NO_RELU_FWD=1 keeps the tensor)", layer);
-        const int H = e.tH(t), W = e.tW(t);
+        const int H = fm.Hp >> t.s, W = fm.Wp >> t.s;
         if (dims) { dims[0] = H; dims[1] = W; dims[2] = t.C; }
         const int64_t n = (int64_t)H * W * t.C;
         if (!out) return PSEG_OK;
         if (cap < n) return fail(PSEG_EINVAL, "activation '%s' needs %lld floats", layer, (long long)n);
         PSEG_HIP(hipStreamSynchronize(e.stream));
         if (e.mode == PSEG_MODE_F32_EXACT) {
-            PSEG_HIP(hipMemcpy(out, t.d, (size_t)n * 4, hipMemcpyDeviceToHost));
+            PSEG_HIP(hipMemcpy(out, t.own, (size_t)n * 4, hipMemcpyDeviceToHost));
         } else {
             std::vector<uint16_t> tmp((size_t)H * W * t.Cs);
-            PSEG_HIP(hipMemcpy(tmp.data(), t.d, tmp.size() * 2, hipMemcpyDeviceToHost));
+            PSEG_HIP(hipMemcpy(tmp.data(), t.own, tmp.size() * 2, hipMemcpyDeviceToHost));
             for (int64_t p = 0; p < (int64_t)H * W; ++p)
                 for (int c = 0; c < t.C; ++c) out[p * t.C + c] = bf16_to_f32(tmp[(size_t)p * t.Cs + c]);
         }

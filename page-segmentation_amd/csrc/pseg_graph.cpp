@@ -313,4 +313,123 @@ int build_graph(Engine& e) {
     return PSEG_OK;
 }
 
+// ---- the compact address map: which tensor may take whose bytes ------------------------------------------------------
+namespace {
+
+constexpr size_t ARENA_ALIGN = 256;
+size_t arena_align(size_t v) { return (v + ARENA_ALIGN - 1) / ARENA_ALIGN * ARENA_ALIGN; }
+
+// the op whose kernel does op i's work: itself, or the neighbour mfma_plan_graph folded it into (-1: none -- a planner bug)
+int host_op(const Engine& e, int i) {
+    for (int hop = 0; hop < 4 && e.ops[i].fused_away; ++hop) {
+        const Op& f = e.ops[i];
+        int h = f.into_tail;
+        for (size_t j = 0; j < e.ops.size() && h < 0; ++j) {
+            const Op& o = e.ops[j];
+            if (o.fuse1 == i || o.tail_logits == i || o.dq_fuse == i || (f.type == OP_POOL && o.type == OP_CONV && o.pool_dst == f.dst)) h = (int)j;
+        }
+        if (h < 0) return -1;
+        i = h;
+    }
+    return e.ops[i].fused_away ? -1 : i;
+}
+
+// Does the kernel that produces op's output write every stored byte of it -- the pad channels up to Cs and every canvas pixel?  Read off
+// the epilogues (pseg_mfma.hip, pseg_upsplit.hip, pseg_bn.hip): the conv kernels store every 8-byte piece with cout < Cs (the pad couts
+// carry zero weights and a zero bias: they store 0, as do their pools), the first-layer, pool, upsplit, BatchNormalization and preprocess
+// kernels walk all Cs channels, the skip-logits plane gets all of its padded classes; every one of them walks the whole canvas.  The one
+// kernel that leaves bytes alone is the stand-alone Conv2DTranspose k2 s2 (MODE_DECONV): it stores round_up(Cout, 4) channels per pixel
+// (run on the accumulators of the conv in front of it, fused_away, it stores every 16-byte piece of the pixel).
+bool writes_every_byte(const Op& op, const Tensor& t) { return op.type != OP_DECONV2 || op.fused_away || round_up(op.Cout, 4) >= t.Cs; }
+
+}  // namespace
+
+size_t skip_plane_bytes(const Engine& e, int Hp, int Wp) {
+    for (auto& op : e.ops)
+        if (op.skiplog >= 0) return (size_t)Hp * Wp * (e.n_classes <= 4 ? 4 : 8) * sizeof(float);   // (MfmaPlan::skip_CP, checked at the launch)
+    return 0;
+}
+
+// Greedy best fit over the producers in launch order.  A fused-away op reads and writes in the launch that runs it.  Tensor T may take
+// bytes of tensor U only if every reader of U is a STRICTLY earlier launch than T's producer (a kernel reads halos of its sources while
+// other workgroups already store).  Both must be written whole by their producers (writes_every_byte): a tensor that is not gets private
+// bytes behind the shared part, zeroed once by set_canvas -- what every tensor had before.
+int plan_arena(const Engine& e, int Hp, int Wp, ArenaPlan& out) {
+    out = ArenaPlan();
+    if (e.mode != PSEG_MODE_BF16) return fail(PSEG_EUNSUPPORTED, "the compact address map belongs to the bf16 engine");
+    const int nT = (int)e.tensors.size(), PLANE = nT;
+    bool staged = false;                                   // mfma_input_is_staged, from the graph
+    for (auto& op : e.ops)
+        if ((op.src0 == e.input_tensor || op.src1 == e.input_tensor) && !mfma_reads_page(e, op)) staged = true;
+    std::vector<int> launch_of(e.ops.size(), -1);
+    if (staged) out.launches.push_back("preprocess");
+    for (size_t i = 0; i < e.ops.size(); ++i)
+        if (!e.ops[i].fused_away) { launch_of[i] = (int)out.launches.size(); out.launches.push_back(e.ops[i].layer); }
+    std::vector<int> prod(nT + 1, -1), last(nT + 1, -1), writer(nT + 1, -1);
+    const size_t plane_bytes = skip_plane_bytes(e, Hp, Wp);
+    auto touched = [&](int t) { return t == PLANE || (t >= 0 && !e.tensors[t].fused && (t != e.input_tensor || staged)); };
+    auto wr = [&](int t, int L, int op) { if (!touched(t)) return; if (prod[t] < 0) { prod[t] = L; writer[t] = op; } last[t] = std::max(last[t], L); };
+    int bad = -1;
+    auto rd = [&](int t, int L) { if (!touched(t)) return; if (prod[t] < 0) bad = t; last[t] = std::max(last[t], L); };
+    if (staged) wr(e.input_tensor, 0, -1);
+    for (size_t i = 0; i < e.ops.size(); ++i) {
+        const Op& op = e.ops[i];
+        const int h = host_op(e, (int)i);
+        if (h < 0) return fail(PSEG_EINVAL, "arena plan: no launch runs layer %s", op.layer.c_str());
+        const int L = launch_of[h];
+        if (!mfma_reads_page(e, op))
+            for (int s : {op.src0, op.src1, op.add}) rd(s, L);
+        if (op.type == OP_LOGITS && op.src1 >= 0)
+            for (auto& p : e.ops)
+                if (p.dst == op.src1 && p.skiplog == (int)i) rd(PLANE, L);
+        if (op.skiplog >= 0) wr(PLANE, L, (int)i);
+        wr(op.dst, L, (int)i);
+        wr(op.relu_dst, L, (int)i);
+    }
+    if (bad >= 0) return fail(PSEG_EINVAL, "arena plan: tensor '%s' is read before a launch writes it", e.tensors[bad].name.c_str());
+    auto bytes_of = [&](int t) { return t == PLANE ? plane_bytes : (size_t)(Hp >> e.tensors[t].s) * (Wp >> e.tensors[t].s) * e.tensors[t].Cs * 2; };
+    std::vector<int> order;
+    for (int t = 0; t <= nT; ++t) {
+        if (t < nT) out.full_bytes += bytes_of(t);
+        if (prod[t] >= 0) order.push_back(t);
+        else if (t < nT) out.untouched_max = std::max(out.untouched_max, bytes_of(t));
+    }
+    out.full_bytes += plane_bytes;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return prod[a] != prod[b] ? prod[a] < prod[b] : bytes_of(a) > bytes_of(b); });
+    for (int t : order) {
+        ArenaRow r;
+        r.tensor = t == PLANE ? -1 : t;
+        r.name = t == PLANE ? "skip_logits" : e.tensors[t].name;
+        r.bytes = bytes_of(t);
+        r.producer = prod[t];
+        r.last_reader = last[t];
+        r.shared = t == PLANE || writer[t] < 0 || writes_every_byte(e.ops[writer[t]], e.tensors[t]);
+        out.rows.push_back(r);
+    }
+    // the shared part: best fit into the gaps the still-live shared tensors leave, else behind the last of them
+    for (size_t i = 0; i < out.rows.size(); ++i) {
+        ArenaRow& r = out.rows[i];
+        if (!r.shared) continue;
+        const size_t need = arena_align(r.bytes);
+        std::vector<std::pair<size_t, size_t>> busy;       // [begin, end) of the placed tensors whose readers are not all earlier launches
+        for (size_t j = 0; j < i; ++j)
+            if (out.rows[j].shared && out.rows[j].last_reader >= r.producer) busy.emplace_back(out.rows[j].offset, out.rows[j].offset + arena_align(out.rows[j].bytes));
+        std::sort(busy.begin(), busy.end());
+        size_t at = 0, best = (size_t)-1, best_gap = (size_t)-1;
+        for (auto& b : busy) {
+            if (b.first > at && b.first - at >= need && b.first - at < best_gap) { best = at; best_gap = b.first - at; }
+            at = std::max(at, b.second);
+        }
+        r.offset = best != (size_t)-1 ? best : at;
+        out.shared_bytes = std::max(out.shared_bytes, r.offset + need);
+    }
+    out.total_bytes = out.shared_bytes;
+    for (auto& r : out.rows)
+        if (!r.shared) { r.offset = out.total_bytes; out.total_bytes += arena_align(r.bytes); }
+    // a tensor no launch touches is still handed to its launch as a pointer (zero-length descriptors, operands a fused kernel ignores):
+    // it gets the arena's start, and the arena is at least as long
+    out.total_bytes = std::max(out.total_bytes, arena_align(out.untouched_max));
+    return PSEG_OK;
+}
+
 }  // namespace pseg

@@ -110,7 +110,12 @@ struct MConv {
     int dbg;   // ablation bits (PSEG_DBG): 1 skip input staging, 2 skip MFMAs, 4 skip epilogue, 8 skip weight DMA
     int rowreuse;   // the k-chunk table is tap-major with one k-step per tap (checked on the host, MfmaPlan::rowreuse): row-reuse k-loops may run
     const uint16_t* wpk_pair;   // paired third cout tile (MfmaPlan::pair8): [30 entries][64 lanes][8] bf16 A fragments, or null
+    unsigned long long pstride; // bytes from one page slot of a tensor to the next: 0 = the tensor's own size (full map), else the arena's slot (compact map)
 };
+// byte offset of page slot `pg` of a tensor of `bytes` bytes per page (launches over several page slots)
+__device__ __forceinline__ size_t slot_off(unsigned pg, unsigned long long pstride, unsigned bytes) {
+    return (size_t)pg * (pstride ? (size_t)pstride : (size_t)bytes);
+}
 
 // single v_max_f32: fmaxf() makes hipcc canonicalise both operands first (3 instructions per max
 // on MFMA outputs); NaNs are not a concern for the ReLU / max-pool epilogue.
@@ -252,10 +257,10 @@ __global__ __launch_bounds__(NW_ * TT_ * 64) __attribute__((amdgpu_waves_per_eu(
     if (gridDim.z > 1) {
         // a launch over several page slots (pseg_predict_batch): blockIdx.z = the slot; only plain layers are launched this way
         // (sources, output and fused pool -- mfma_op_batchable)
-        a.src0 = (const uint16_t*)((const char*)a.src0 + (size_t)blockIdx.z * a.bytes0);
-        if (a.src1) a.src1 = (const uint16_t*)((const char*)a.src1 + (size_t)blockIdx.z * a.bytes1);
-        a.dst = (uint16_t*)((char*)a.dst + (size_t)blockIdx.z * a.dst_bytes);
-        if (a.pool_dst) a.pool_dst = (uint16_t*)((char*)a.pool_dst + (size_t)blockIdx.z * a.pool_bytes);
+        a.src0 = (const uint16_t*)((const char*)a.src0 + slot_off(blockIdx.z, a.pstride, a.bytes0));
+        if (a.src1) a.src1 = (const uint16_t*)((const char*)a.src1 + slot_off(blockIdx.z, a.pstride, a.bytes1));
+        a.dst = (uint16_t*)((char*)a.dst + slot_off(blockIdx.z, a.pstride, a.dst_bytes));
+        if (a.pool_dst) a.pool_dst = (uint16_t*)((char*)a.pool_dst + slot_off(blockIdx.z, a.pstride, a.pool_bytes));
     }
     constexpr bool FIXED = KS_ > 0;
     const int c_stride = FIXED ? ST_ : a.stride;
@@ -2796,6 +2801,7 @@ struct SConv {
     unsigned long long* trace;       // PSEG_SP_TRACE=<layer>: 16 s_memtime stamps per workgroup, or null
     int dbg;                         // diagnostic build only (PSEG_SP_DBG, wrong results): 1 no weight DMA, 2 no tile DMA (timing only); 8 the weight loaders stop after their
                                      // first groups and every wait gives up after 64 polls -- the give-up path itself, for tests/test_bf16_gpu.py
+    unsigned long long pstride;      // as MConv::pstride
 };
 enum { SP_POOL = 1, SP_DQ = 2, SP_PATCH = 4 };
 constexpr int SP_GK = 2;             // k-steps per weight group (the unit of the ready / done counters)
@@ -2899,7 +2905,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             const bool s1 = c0 >= a.nch0;                     // (wave-uniform) the block's chunks come from the second source
             const int nchs = s1 ? a.nch1 : a.nch0, cs0 = s1 ? c0 - a.nch0 : c0;
             const unsigned pbytes = s1 ? a.bytes1 : a.bytes0;
-            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)(s1 ? a.src1 : a.src0) + (size_t)pg * pbytes), 0, pbytes, 0x00020000);
+            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)(s1 ? a.src1 : a.src0) + slot_off(pg, a.pstride, pbytes)), 0, pbytes, 0x00020000);
             unsigned col[J];
 #pragma unroll
             for (int j = 0; j < J; ++j) {
@@ -3167,7 +3173,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 bq[m][1] = make_uint4(pk[2][0], pk[2][1], pk[3][0], pk[3][1]);
                 bq[m][2] = make_uint4(pk[4 % NT][0], pk[4 % NT][1], 0u, 0u);
             }
-            const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc((void*)((char*)a.dq_dst + (size_t)pg * a.dq_bytes), 0, a.dq_bytes, 0x00020000);
+            const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc((void*)((char*)a.dq_dst + slot_off(pg, a.pstride, a.dq_bytes)), 0, a.dq_bytes, 0x00020000);
             const int W2 = 2 * a.Wout;
             constexpr int QPP = 128 + 8;                      // patch bytes per pixel (64 channels + 8: conflict-free 8-byte writes)
             char* const patch = smem + a.lds_patch_off + wave * (2 * 16 * QPP);   // two patches: tile m + 1 is written while tile m's lines leave
@@ -3222,8 +3228,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 if (lane == 0) flags[4 + wave] = (kg + K + (12 * (ab + 1)) / NT) >> 1;
             }
         } else {
-            const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc((void*)((char*)a.dst + (size_t)pg * a.dst_bytes), 0, a.dst_bytes, 0x00020000);
-            const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc((void*)(POOL ? (char*)a.pool_dst + (size_t)pg * a.pool_bytes : (char*)a.dst), 0, POOL ? a.pool_bytes : 0u, 0x00020000);
+            const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc((void*)((char*)a.dst + slot_off(pg, a.pstride, a.dst_bytes)), 0, a.dst_bytes, 0x00020000);
+            const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc((void*)(POOL ? (char*)a.pool_dst + slot_off(pg, a.pstride, a.pool_bytes) : (char*)a.dst), 0, POOL ? a.pool_bytes : 0u, 0x00020000);
             unsigned pixoff[MT];
 #pragma unroll
             for (int m = 0; m < MT; ++m) {
@@ -3413,7 +3419,7 @@ __global__ __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
             const bool s1 = c0 >= a.nch0;
             const int nchs = s1 ? a.nch1 : a.nch0, cs0 = s1 ? c0 - a.nch0 : c0;
             const unsigned pbytes = s1 ? a.bytes1 : a.bytes0;
-            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)(s1 ? a.src1 : a.src0) + (size_t)pg * pbytes), 0, pbytes, 0x00020000);
+            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)(s1 ? a.src1 : a.src0) + slot_off(pg, a.pstride, pbytes)), 0, pbytes, 0x00020000);
             unsigned col[J];
 #pragma unroll
             for (int j = 0; j < J; ++j) {
@@ -3694,8 +3700,8 @@ __global__ __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
         // ---- epilogue from registers: one 16-pixel tile at a time through this wave's LDS patch ------------------------
         asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7" ::: "memory");
         if (tile_ok) {
-            const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc((void*)((char*)a.dst + (size_t)pg * a.dst_bytes), 0, a.dst_bytes, 0x00020000);
-            const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc((void*)(POOL ? (char*)a.pool_dst + (size_t)pg * a.pool_bytes : (char*)a.dst), 0, POOL ? a.pool_bytes : 0u, 0x00020000);
+            const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc((void*)((char*)a.dst + slot_off(pg, a.pstride, a.dst_bytes)), 0, a.dst_bytes, 0x00020000);
+            const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc((void*)(POOL ? (char*)a.pool_dst + slot_off(pg, a.pstride, a.pool_bytes) : (char*)a.dst), 0, POOL ? a.pool_bytes : 0u, 0x00020000);
             constexpr int PP = NT * 32 + 8;                   // patch bytes per pixel (+ 8: conflict-free 8-byte writes)
             constexpr int PPX = NT * 2;                       // 16-byte pieces per pixel
             constexpr int NP = 8 * PPX;                       // pieces of half a pixel tile (eight pixels: <= 64, one store per lane)
@@ -3829,9 +3835,7 @@ struct MfmaPlan {
     uint16_t* d_t2_wC = nullptr;
     bool tail2 = false;
     bool pairc2 = false;           // fused conv1+conv2 (conv12_ws_kernel): channels 16-19 of two neighbouring pixels share a k-chunk (17 k-steps instead of 19)
-    float* d_skiplog = nullptr;    // skip-logits buffer [canvas pixel][skip_CP] (op.skiplog >= 0), grown with the canvas
-    size_t skiplog_bytes = 0;
-    int skip_CP = 0;
+    int skip_CP = 0;               // op.skiplog >= 0: floats per canvas pixel of the skip-logits plane (the plane is the engine's: Engine::skip_base)
     UpSplit* upsplit = nullptr;   // PLAN_UPSPLIT: GEMM + gather-sum form of upsample -> k2 conv
     // ---- which kernel family may take this layer: everything about the choice that does not depend on the canvas (the layer-shape
     // tests and the plan switches), decided once in mfma_pack_op.  The launch adds only the size predicates (sp_pays ... s2_persists).
@@ -3870,22 +3874,12 @@ void mfma_free_op(Op& op) {
     (void)hipFree(p->d_tail_wa); (void)hipFree(p->d_tail_wb); (void)hipFree(p->d_tail_bias);
     (void)hipFree(p->d_tc_wA1); (void)hipFree(p->d_tc_wA2); (void)hipFree(p->d_tc_beta);
     upsplit_free(p->upsplit);
-    (void)hipFree(p->d_skiplog);
     (void)hipFree(p->d_dq_w); (void)hipFree(p->d_dq_bias);
     (void)hipFree(p->d_q_w); (void)hipFree(p->d_q_bias); (void)hipFree(p->d_t2_wD); (void)hipFree(p->d_t2_wC);
     (void)hipFree(p->d_sp_wpk); (void)hipFree(p->tr.d_wpk); (void)hipFree(p->d_wpk_pair); (void)hipFree(p->d_wpk_rpair);
     for (int v = 0; v < 2; ++v) { (void)hipFree(p->sp_lay[v].d_tab); (void)hipFree(p->sp2_lay[v].d_tab); }
     delete p;
     op.plan = nullptr;
-}
-
-// pseg_engine_trim: the canvas-sized buffers a plan owns (the skip-logits planes: 16 B per canvas pixel and page slot)
-void mfma_trim_op(Op& op) {
-    auto* p = (MfmaPlan*)op.plan;
-    if (!p) return;
-    (void)hipFree(p->d_skiplog);
-    p->d_skiplog = nullptr;
-    p->skiplog_bytes = 0;
 }
 
 static int producer_of(const Engine& e, int tensor) {
@@ -3979,6 +3973,7 @@ int mfma_plan_graph(Engine& e) {
                     c.name += "/relu";
                     c.d = nullptr;
                     c.base = nullptr;
+                    c.own = nullptr;
                     c.bytes = 0;
                     c.page_bytes = 0;
                     e.tensors.push_back(c);
@@ -4194,6 +4189,10 @@ static bool is_conv1_special(const Engine& e, const Op& op, int* ks, int* cout) 
     for (auto& c : combos)
         if (op.k == c[0] && op.Cout == c[1]) { *ks = c[0]; *cout = c[1]; return true; }
     return false;
+}
+bool mfma_reads_page(const Engine& e, const Op& op) {
+    int ks, co;
+    return is_conv1_special(e, op, &ks, &co);
 }
 
 template <typename T>
@@ -5333,6 +5332,7 @@ static void fill_common(const Engine& e, const Op& op, const MfmaPlan& P, MConv&
     a.CoP = P.CoP;
     a.nb_loop = 1;
     a.nb_total = P.nblocks_n;
+    a.pstride = e.map_in_use == MAP_COMPACT ? (unsigned long long)e.arena_plan.total_bytes : 0ull;   // == Tensor::page_bytes of every tensor in that map
     a.dbg = PSEG_DIAG_KNOB("PSEG_DBG") ? atoi(PSEG_DIAG_KNOB("PSEG_DBG")) : 0;   // wrong-result ablations: diagnostic build only
     if (PSEG_KNOB("PSEG_NO_LDS_STORE")) a.dbg |= 32;   // direct 8-byte stores instead of the LDS patch (same bytes)
 }
@@ -5360,15 +5360,10 @@ static int fill_conv(Engine& e, const Op& op, MfmaPlan& P, MConv& a, dim3* grid)
     a.deconv = 0;
     if (op.tail_logits >= 0) fill_tail(e, op, P, a);   // logits / softmax / argmax in this conv's epilogue
     if (op.skiplog >= 0) {
-        const size_t need = (size_t)a.Hout * a.Wout * P.skip_CP * 4;     // one page slot
-        if (need * e.pages > P.skiplog_bytes) {
-            PSEG_HIP(hipDeviceSynchronize());
-            (void)hipFree(P.d_skiplog);
-            P.d_skiplog = nullptr; P.skiplog_bytes = 0;
-            PSEG_HIP(hipMalloc((void**)&P.d_skiplog, need * e.pages));
-            P.skiplog_bytes = need * e.pages;
-        }
-        a.skip_logits = (float*)((char*)P.d_skiplog + (size_t)e.page * need);
+        // the plane is part of the address map in use (set_canvas), one slot per page slot
+        if (!e.skip_base || e.skip_bytes != (size_t)a.Hout * a.Wout * P.skip_CP * 4)
+            return fail(PSEG_EINVAL, "layer %s: the canvas has no skip-logits plane of %d floats per pixel", op.layer.c_str(), P.skip_CP);
+        a.skip_logits = (float*)((char*)e.skip_base + (size_t)e.page * e.skip_stride);
         a.skip_CP = P.skip_CP;
         a.tail_wa = P.d_tail_wa;
     }
@@ -5404,6 +5399,7 @@ static SConv sp_args(const Engine& e, const Op& op, const MfmaPlan& P, const MCo
     c.wpk = P.d_sp_wpk; c.bias = P.d_bias;
     c.dst = a.dst; c.dst_bytes = a.dst_bytes; c.nch_out = a.nch_out; c.pool_dst = a.pool_dst; c.pool_bytes = a.pool_bytes;
     c.dq_bias = a.dq_bias; c.dq_dst = a.dq_dst; c.dq_bytes = a.dq_bytes; c.dq_nch = a.dq_nch; c.dq_relu = a.dq_relu;
+    c.pstride = a.pstride;
     c.err = e.d_sp_err;
     c.layer_id = (int)(&op - e.ops.data());
     c.dbg = PSEG_DIAG_KNOB("PSEG_SP_DBG") ? atoi(PSEG_DIAG_KNOB("PSEG_SP_DBG")) : 0;
@@ -5682,8 +5678,9 @@ static int launch_composed_tail(Engine& e, const Op& op, const MfmaPlan& P, hipS
         const int sp = producer_of(e, lg.src1);
         if (sp >= 0 && e.ops[sp].skiplog >= 0) {
             auto* PS = (MfmaPlan*)e.ops[sp].plan;
-            if (!PS || !PS->d_skiplog || PS->skip_CP != P.tc_CP) return fail(PSEG_EINVAL, "skip-logits buffer missing for the composed tail");
-            t.S = (const float*)((const char*)PS->d_skiplog + (size_t)e.page * ((size_t)e.Hp * e.Wp * PS->skip_CP * 4));   // this page slot's plane
+            if (!PS || !e.skip_base || PS->skip_CP != P.tc_CP || e.skip_bytes != (size_t)e.Hp * e.Wp * PS->skip_CP * 4)
+                return fail(PSEG_EINVAL, "skip-logits buffer missing for the composed tail");
+            t.S = (const float*)((const char*)e.skip_base + (size_t)e.page * e.skip_stride);   // this page slot's plane
             t.skip = nullptr;
         }
     }

@@ -16,7 +16,7 @@ FLAG_BATCHNORM = 1
 EXPORTED_SYMBOLS = (
     "pseg_abi_version", "pseg_last_error", "pseg_device_count", "pseg_create", "pseg_create_ex", "pseg_create_plan", "pseg_env_knobs", "pseg_destroy",
     "pseg_num_weights", "pseg_weight_info", "pseg_set_weights", "pseg_get_weights",
-    "pseg_predict", "pseg_predict_device", "pseg_predict_pages_device", "pseg_engine_status", "pseg_engine_trim", "pseg_batch_units", "pseg_rccl_abi_pinned", "pseg_predict_batch", "pseg_predict_chain", "pseg_get_activation", "pseg_flops_per_pixel", "pseg_engine_stream",
+    "pseg_predict", "pseg_predict_device", "pseg_predict_pages_device", "pseg_engine_status", "pseg_engine_trim", "pseg_plan_arena", "pseg_batch_units", "pseg_rccl_abi_pinned", "pseg_predict_batch", "pseg_predict_chain", "pseg_get_activation", "pseg_flops_per_pixel", "pseg_engine_stream",
     "pseg_host_alloc", "pseg_host_free", "pseg_host_register", "pseg_host_unregister",
     "pseg_predict_margin_device", "pseg_predict_exact_labels_device", "pseg_predict_exact_labels", "pseg_label_exact_stats", "pseg_label_exact_stats_ex",
     "pseg_timing_enable", "pseg_timing_reset", "pseg_timing_num_slots", "pseg_timing_get",
@@ -1925,6 +1925,33 @@ def batch_units(shapes, cap=8):
     nu = lib().pseg_batch_units(n, H, W, int(cap), first, count, n)
     _check(min(nu, 0))
     return [(first[u], count[u]) for u in range(nu)]
+
+
+class _ArenaRow(ctypes.Structure):
+    _fields_ = [("name", ctypes.c_char * 48), ("producer_name", ctypes.c_char * 32), ("last_reader_name", ctypes.c_char * 32),
+                ("bytes", ctypes.c_int64), ("offset", ctypes.c_int64),
+                ("producer", ctypes.c_int), ("last_reader", ctypes.c_int), ("shared", ctypes.c_int), ("reserved", ctypes.c_int)]
+
+
+def plan_arena(arch, H, W, n_classes=3, in_channels=1, plan=None):
+    """The compact address map of a bf16 engine for an H x W page (pseg_plan_arena; host logic, no GPU): (rows, arena_bytes, full_bytes),
+    rows = [dict(name, bytes, offset, producer, last_reader, producer_name, last_reader_name, shared)] in placement order.  plan: the
+    engine's plan switches, a string or a dict as for Engine."""
+    arch_id = ARCH_IDS[arch] if isinstance(arch, str) else int(arch)
+    if isinstance(plan, dict):
+        plan = ";".join("%s=%s" % kv for kv in sorted(plan.items()))
+    L = lib()
+    L.pseg_plan_arena.argtypes = [ctypes.c_int] * 3 + [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_ArenaRow), ctypes.c_int,
+                                  ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]
+    args = (arch_id, int(n_classes), int(in_channels), (plan or "").encode(), int(H), int(W))
+    n = L.pseg_plan_arena(*args, None, 0, None, None)
+    _check(min(n, 0))
+    rows = (_ArenaRow * max(n, 1))()
+    arena, full = ctypes.c_int64(), ctypes.c_int64()
+    _check(min(L.pseg_plan_arena(*args, rows, n, ctypes.byref(arena), ctypes.byref(full)), 0))
+    return ([dict(name=r.name.decode(), bytes=r.bytes, offset=r.offset, producer=r.producer, last_reader=r.last_reader,
+                  producer_name=r.producer_name.decode(), last_reader_name=r.last_reader_name.decode(), shared=bool(r.shared)) for r in rows[:n]],
+            arena.value, full.value)
 
 
 def chain_units(shapes, out_shapes=None, cap=8):
